@@ -16,6 +16,11 @@ Region i -> rank i % N, no data-path collective (runner.py:470-500).
 At N = 1 the line also carries `config2` (the batched pair-HMM of BASELINE config 2 on resident batches: reference-equivalent and
 executed GCUPS, every reference DP executed, the hard workload, k_dp_jobs' roofline) and `other_configs` (3, 4 streamed, 5).
 `--config 2|3|4|5` puts that config alone on the line (same contract); `--config 4` is the default line without the sub-blocks.
+
+The JSON line on stdout carries the headline keys only (HEADLINE_KEYS); `--detail FILE` (e.g. bench_detail.json) writes the whole line,
+sub-blocks included, to FILE.  `--dump-outputs DIR` (config 4; e.g. bench_outputs) writes what the timed path computed in its last step --
+the merged VCF record text rank 0 receives -- as float arrays DIR/<name>.npy (dump_record_text), so that two builds can be compared output
+for output on the same seeded inputs.
 """
 import argparse
 import ctypes as C
@@ -30,6 +35,64 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBPS = 8000.0        # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+
+# what the stdout line keeps (a consumer may read only the last few KB of the output); the rest goes to --detail FILE
+HEADLINE_KEYS = ("metric", "value", "value_is", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+                 "dtype", "data", "config", "windows_per_sec", "gcups", "gcups_executed", "timed_s", "roofline", "cpu_baseline", "detail", "dump_outputs")
+
+
+
+def headline(line):
+    """The stdout line: the keys of HEADLINE_KEYS that `line` has."""
+    return {k: line[k] for k in HEADLINE_KEYS if k in line}
+
+
+DUMP_MAX_BYTES = 64 * 10 ** 6
+DUMP_SAMPLE_SEED = 20261015
+
+
+def dump_record_text(out_dir, text):
+    """The merged VCF record text of the last timed step as arrays, one value per record line:
+        record_region  float32  region index of the CHROM column (r<index>; -1 for any other name)
+        record_pos     float32 (float64 past 2**24)  POS
+        record_qual    float64  QUAL (NaN for '.')
+        record_crc32   float64  zlib.crc32 of the whole line (every other column)
+        summary        float64  [records, records written, text bytes, zlib.crc32 of the whole text]
+    When all records do not fit in DUMP_MAX_BYTES, a fixed seeded sample of them is written (sorted) and record_index.npy says which."""
+    import zlib
+    tb = text.encode("ascii") if isinstance(text, str) else bytes(text)
+    ends = np.flatnonzero(np.frombuffer(tb, dtype=np.uint8) == 10)
+    if len(tb) and (len(ends) == 0 or ends[-1] != len(tb) - 1):
+        ends = np.append(ends, len(tb))                                     # a last line without its newline
+    starts = np.concatenate([[0], ends[:-1] + 1]).astype(np.int64).tolist()
+    n = len(ends)
+    ends = ends.tolist()
+    region = np.empty(n, dtype=np.float32)
+    pos = np.empty(n, dtype=np.float64)
+    qual = np.empty(n, dtype=np.float64)
+    crc = np.empty(n, dtype=np.float64)
+    for i in range(n):
+        ln = tb[starts[i]:ends[i]]
+        f = ln.split(b"\t", 6)
+        c = f[0]
+        region[i] = int(c[1:]) if c[:1] == b"r" and c[1:].isdigit() else -1
+        pos[i] = int(f[1])
+        qual[i] = float("nan") if f[5] == b"." else float(f[5])
+        crc[i] = zlib.crc32(ln)
+    arrays = {"record_region": region, "record_pos": pos.astype(np.float32) if n == 0 or pos.max() < 2 ** 24 else pos,
+              "record_qual": qual, "record_crc32": crc}
+    per_row = sum(x.itemsize for x in arrays.values())
+    rows = np.arange(n)
+    if n * per_row > DUMP_MAX_BYTES - 4096:
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=(DUMP_MAX_BYTES - 4096) // (per_row + 8), replace=False))
+        arrays = {k: x[rows] for k, x in arrays.items()}
+        arrays["record_index"] = rows.astype(np.float64)
+    arrays["summary"] = np.array([n, len(rows), len(tb), zlib.crc32(tb)], dtype=np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    return {"dir": out_dir, "files": sorted(k + ".npy" for k in arrays), "records": int(n), "records_written": int(len(rows)),
+            "bytes": int(sum(a.nbytes for a in arrays.values()))}
 
 
 def cpu_model():
@@ -342,7 +405,14 @@ def main():
     ap.add_argument("--no-wgs", action="store_true", help=argparse.SUPPRESS)     # (round 5: the config-2 line carried a wgs block; accepted, ignored)
     ap.add_argument("--min-seconds", type=float, default=0.25, help="a step is made of as many passes (one batch each) as it takes for the K timed steps to last this long")
     ap.add_argument("--selftest-ranks", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="config 4: after the timed steps write the record text of the last step as DIR/<name>.npy (dump_record_text)")
+    ap.add_argument("--detail", metavar="FILE", default=None, help="write the whole line (every sub-block) to FILE as JSON; stdout keeps HEADLINE_KEYS")
     a = ap.parse_args()
+    if a.steps is not None and a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and a.config not in (None, 4):
+        ap.error("--dump-outputs: the config-4 line (the default) only")
 
     if a.gpus > 1 and "RANK" not in os.environ:
         # started without a launcher: become N ranks, one per GPU (the driver's N>1 form goes through torch.distributed.run itself)
@@ -363,8 +433,15 @@ def main():
     else:
         line = line_wgs(a, rk)
     if rk.rank == 0 and line is not None:
-        line.pop("merged_text", None)
-        print(json.dumps(line))
+        text = line.pop("merged_text", None)
+        if a.dump_outputs:
+            line["dump_outputs"] = dump_record_text(a.dump_outputs, text)
+        del text
+        if a.detail:
+            line["detail"] = a.detail
+            with open(a.detail, "w") as f:
+                json.dump(line, f)
+        print(json.dumps(headline(line)))
     rk.close()
 
 

@@ -1755,6 +1755,74 @@ def gen_dp(out):
     print("dp_cases:", n, "cases;", len(tb_idx), "with traceback")
 
 
+def gen_dp_fuzz(out):
+    """The 1500 fuzz cases of tests/test_oracle.py::test_dp_fuzz_against_reference_build (seed 99) with the unmodified
+    align.c's answers: fastAlignmentRoutine score + traceback strings + firstpos, calculateFlankScore where the score is > 0."""
+    from oracle.oracle import RefAlign
+    ref = RefAlign()
+    rng = np.random.default_rng(99)
+    n, LMAX = 1500, 250
+    haps = np.zeros((n, LMAX + 15), dtype=np.uint8)
+    reads = np.zeros((n, LMAX), dtype=np.uint8)
+    quals = np.zeros((n, LMAX), dtype=np.uint8)
+    gos = np.zeros((n, LMAX + 15), dtype=np.uint8)
+    lens = np.zeros(n, dtype=np.int32)
+    score = np.zeros(n, dtype=np.int32)
+    firstpos = np.zeros(n, dtype=np.int32)
+    flank = np.full(n, -1, dtype=np.int32)             # -1: score 0, no flank score asked for
+    a1s, a2s = [], []
+    for j in range(n):
+        L = int(rng.choice([7, 9, 25, 64, 101, 150, 250]))
+        hap = bytearray(rng.choice(list(B + b"N"), L + 15, p=[.24, .24, .24, .24, .04]).tolist())
+        off = int(rng.integers(0, 16))
+        read = bytearray(hap[off:off + L])
+        for _ in range(int(rng.integers(0, 6))):
+            read[int(rng.integers(0, L))] = B[int(rng.integers(0, 4))]
+        if L > 30 and rng.random() < 0.5:
+            p = int(rng.integers(5, L - 8)); k = int(rng.integers(1, 7))
+            read = (read[:p] + read[p + k:] + bytearray(rng.choice(list(B), k).tolist()))[:L]
+        q = bytes(rng.integers(0, 94, L).astype(np.uint8).tolist())
+        go = bytes(rng.integers(1, 46, L + 15).astype(np.uint8).tolist())
+        sc, a1, a2, fp = ref.dp_align(bytes(hap), bytes(read), q, go)
+        assert ref.dp_score(bytes(hap), bytes(read), q, go) == sc
+        haps[j, :L + 15] = np.frombuffer(bytes(hap), dtype=np.uint8)
+        reads[j, :L] = np.frombuffer(bytes(read), dtype=np.uint8)
+        quals[j, :L] = np.frombuffer(q, dtype=np.uint8)
+        gos[j, :L + 15] = np.frombuffer(go, dtype=np.uint8)
+        lens[j], score[j], firstpos[j] = L, sc, fp
+        a1s.append(a1.decode()); a2s.append(a2.decode())
+        if sc > 0:
+            flank[j] = ref.flank_score(L + 15, 20, q, go, fp, a1, a2)
+    np.savez_compressed(os.path.join(out, "dp_fuzz_cases.npz"), haps=haps, reads=reads, quals=quals, gos=gos, lens=lens, score=score,
+                        aln1=np.array(a1s), aln2=np.array(a2s), firstpos=firstpos, flank=flank)
+    print("dp_fuzz_cases: %d cases, %d with a flank score" % (n, int((flank >= 0).sum())))
+
+
+def gen_tandem(out):
+    """The 400 sequences of tests/test_oracle.py::test_tandem_annotation_matches_unmodified_reference_build (seed 11) with the
+    unmodified tandem.c's annotate() in both modes (whole sequence / start only): size and displacement bytes per base."""
+    import ctypes as C
+    lib = C.CDLL(os.path.join(ROOT, "oracle", "_ref", "libtandem_ref.so"))
+    rng = np.random.default_rng(11)
+    seqs, outs = [], {k: [] for k in ("full_size", "full_disp", "start_size", "start_disp")}
+    for it in range(400):
+        n = int(rng.integers(1, 300))
+        seq = bytearray(bytes(rng.choice(list(b"ACGT" if it % 3 else b"ACGTNacgtn"), n).astype(np.uint8)))
+        for _ in range(int(rng.integers(0, 5))):
+            p = int(rng.integers(0, n)); u = bytes(rng.choice(list(b"ACGT"), int(rng.integers(1, 13))).astype(np.uint8)); k = int(rng.integers(2, 90))
+            seq[p:p + k] = (u * k)[:k]
+        seq = bytes(seq[:n])
+        seqs.append(seq)
+        for full, tag in ((True, "full"), (False, "start")):
+            s, d = C.create_string_buffer(n + 1), C.create_string_buffer(n + 1)
+            lib.annotate(seq, s, d, -n if full else n)
+            outs[tag + "_size"].append(s.raw[:n]); outs[tag + "_disp"].append(d.raw[:n])
+    cat = lambda xs: np.frombuffer(b"".join(xs), dtype=np.uint8)
+    off = np.concatenate([[0], np.cumsum([len(s) for s in seqs])]).astype(np.int64)
+    np.savez_compressed(os.path.join(out, "tandem_cases.npz"), seq=cat(seqs), off=off, **{k: cat(v) for k, v in outs.items()})
+    print("tandem_cases: %d sequences, %d bases" % (len(seqs), int(off[-1])))
+
+
 # ------------------------------------------------------------------------------------------------
 def gen_mapalign(out):
     import calign_drv
@@ -3165,9 +3233,13 @@ def main():
         sys.exit("reference tree not found at %s: golden vectors can only be regenerated in the build container" % REF)
     subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle")])
     build_scratch(a.scratch)
-    todo = a.only.split(",") if a.only else ["dp", "mapalign", "assembler", "population", "haplotype", "filter", "hapseq", "candidates", "readqc", "infostats", "pvalues", "vcf", "regionprep", "indelprior", "refcall", "region"]
+    todo = a.only.split(",") if a.only else ["dp", "dpfuzz", "tandem", "mapalign", "assembler", "population", "haplotype", "filter", "hapseq", "candidates", "readqc", "infostats", "pvalues", "vcf", "regionprep", "indelprior", "refcall", "region"]
     if "dp" in todo:
         gen_dp(HERE)
+    if "dpfuzz" in todo:
+        gen_dp_fuzz(HERE)
+    if "tandem" in todo:
+        gen_tandem(HERE)
     if "mapalign" in todo:
         gen_mapalign(HERE)
     if "assembler" in todo:

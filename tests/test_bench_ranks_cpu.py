@@ -209,3 +209,49 @@ def test_cgroup_cpu_accounting_of_the_timed_region():
     assert B.cgroup_cpu_delta(None, b) is None and B.cgroup_cpu_delta(a, None) is None
     st = B.cgroup_cpu_stat()                                                 # whatever this machine has: a record with the three parts, or None
     assert st is None or {"st", "quota_us", "period_us"} <= set(st)
+
+
+def test_dump_outputs_are_the_record_text_of_the_last_step(tmp_path):
+    """`bench.py --dump-outputs DIR`: the record text the timed path hands rank 0, one value per record line (region, POS, QUAL, crc32 of the
+    line), float arrays; the same arguments give the same arrays run after run (seeded inputs); and a larger text becomes a fixed seeded sample
+    under the size cap."""
+    import zlib
+    import numpy as np
+    import bench
+    from tests import fakedev
+    from tools import bench_other
+    lib = fakedev.fake_caller_lib()
+    os.environ.update(PLAT_CALLER_WORKERS="2", PLAT_CALLER_CHUNK="2")
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
+        os.environ.pop(k, None)
+    rk1 = bench.Ranks(1, need_gpu=False)
+    dumps = []
+    for run in range(2):
+        line = bench_other.line_config4(_args(6), rk1, lib=lib, region_len=3000, region_kw=REGION_KW)
+        text = line.pop("merged_text")
+        info = bench.dump_record_text(str(tmp_path / ("run%d" % run)), text)
+        dumps.append({f[:-4]: np.load(os.path.join(info["dir"], f)) for f in info["files"]})
+        assert len(json.dumps(bench.headline(dict(line, dump_outputs=info)))) < 4096
+    a, b = dumps
+    assert sorted(a) == ["record_crc32", "record_pos", "record_qual", "record_region", "summary"]
+    assert all(x.dtype in (np.float32, np.float64) for x in a.values())
+    assert all(np.array_equal(a[k], b[k], equal_nan=True) for k in a)
+    lines = text.split("\n")[:-1]
+    assert len(lines) > 10 and a["summary"].tolist() == [len(lines), len(lines), len(text), zlib.crc32(text.encode())]
+    assert a["record_pos"].tolist() == [int(ln.split("\t")[1]) for ln in lines]
+    assert a["record_region"].tolist() == [int(ln.split("\t")[0][1:]) for ln in lines]
+    assert a["record_crc32"].tolist() == [zlib.crc32(ln.encode()) for ln in lines]
+    big = "".join("chr%d\t%d\t.\tA\tC\t%s\tPASS\n" % (i % 3, i + 1, "." if i % 7 == 0 else str(i % 90)) for i in range(5000))
+    cap = bench.DUMP_MAX_BYTES
+    try:
+        bench.DUMP_MAX_BYTES = 4096 + 2000 * 32
+        s1 = bench.dump_record_text(str(tmp_path / "s1"), big)
+        s2 = bench.dump_record_text(str(tmp_path / "s2"), big)
+    finally:
+        bench.DUMP_MAX_BYTES = cap
+    assert s1["records"] == 5000 and s1["records_written"] == 2000 and s1["bytes"] <= 4096 + 2000 * 32
+    idx = np.load(str(tmp_path / "s1" / "record_index.npy"))
+    assert np.array_equal(idx, np.load(str(tmp_path / "s2" / "record_index.npy"))) and np.all(np.diff(idx) > 0)
+    q = np.load(str(tmp_path / "s1" / "record_qual.npy"))
+    assert np.array_equal(np.isnan(q), idx % 7 == 0) and np.all(np.load(str(tmp_path / "s1" / "record_region.npy")) == -1)
+    assert np.array_equal(np.load(str(tmp_path / "s1" / "record_pos.npy")), idx + 1)

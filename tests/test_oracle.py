@@ -2,7 +2,8 @@
 
  * against the committed golden vectors (generated from the reference's own code by
    tests/golden/gen_golden.py), and
- * directly against the unmodified reference align.c when oracle/_ref/libalign_ref.so is present.
+ * directly against the unmodified reference align.c / tandem.c when oracle/_ref is present (their stored answers are
+   checked either way).
 """
 import gzip
 import json
@@ -10,7 +11,6 @@ import math
 import os
 
 import numpy as np
-import pytest
 
 from oracle.oracle import RefAlign
 
@@ -47,31 +47,27 @@ def test_dp_known_answers(oracle):
     assert oracle.dp_score(bytes(h2), bytes(r2), q, go) == 0
 
 
-@pytest.mark.skipif(not RefAlign.available(), reason="oracle/_ref not built (reference tree absent)")
-def test_dp_fuzz_against_reference_build(oracle):
-    ref = RefAlign()
-    rng = np.random.default_rng(99)
-    B = b"ACGT"
-    for it in range(1500):
-        L = int(rng.choice([7, 9, 25, 64, 101, 150, 250]))
-        hap = bytearray(rng.choice(list(B + b"N"), L + 15, p=[.24, .24, .24, .24, .04]).tolist())
-        off = int(rng.integers(0, 16))
-        read = bytearray(hap[off:off + L])
-        for _ in range(int(rng.integers(0, 6))):
-            read[int(rng.integers(0, L))] = B[int(rng.integers(0, 4))]
-        if L > 30 and rng.random() < 0.5:
-            p = int(rng.integers(5, L - 8)); k = int(rng.integers(1, 7))
-            read = (read[:p] + read[p + k:] + bytearray(rng.choice(list(B), k).tolist()))[:L]
-        q = bytes(rng.integers(0, 94, L).astype(np.uint8).tolist())
-        go = bytes(rng.integers(1, 46, L + 15).astype(np.uint8).tolist())
-        a = oracle.dp_align(bytes(hap), bytes(read), q, go)
-        b = ref.dp_align(bytes(hap), bytes(read), q, go)
-        assert a == b
-        assert oracle.dp_score(bytes(hap), bytes(read), q, go) == ref.dp_score(bytes(hap), bytes(read), q, go) == a[0]
+def test_dp_fuzz_against_reference_build(oracle, golden_dir):
+    """1500 fuzz cases (N's in the haplotype, substitutions, deletions, qual 0..93, gap-open 1..45) with the answers of the unmodified
+    align.c stored in dp_fuzz_cases.npz (tests/golden/gen_golden.py gen_dp_fuzz); the live reference build is asked too when present."""
+    g = np.load(os.path.join(golden_dir, "dp_fuzz_cases.npz"))
+    ref = RefAlign() if RefAlign.available() else None
+    assert len(g["lens"]) == 1500 and (g["flank"] >= 0).sum() > 1000
+    for j in range(len(g["lens"])):
+        L = int(g["lens"][j])
+        hap, read = g["haps"][j, :L + 15].tobytes(), g["reads"][j, :L].tobytes()
+        q, go = g["quals"][j, :L].tobytes(), g["gos"][j, :L + 15].tobytes()
+        want = (int(g["score"][j]), str(g["aln1"][j]).encode(), str(g["aln2"][j]).encode(), int(g["firstpos"][j]))
+        a = oracle.dp_align(hap, read, q, go)
+        assert a == want, j
+        assert oracle.dp_score(hap, read, q, go) == want[0]
+        if ref is not None:
+            assert ref.dp_align(hap, read, q, go) == want and ref.dp_score(hap, read, q, go) == want[0]
         if a[0] > 0:
             fa = oracle.flank_score(L + 15, 20, q, go, a[3], a[1], a[2])
-            fb = ref.flank_score(L + 15, 20, q, go, b[3], b[1], b[2])
-            assert fa == fb
+            assert fa == int(g["flank"][j]), j
+            if ref is not None:
+                assert ref.flank_score(L + 15, 20, q, go, a[3], a[1], a[2]) == fa
 
 
 def test_mapalign_golden(oracle, golden_dir):
@@ -300,28 +296,25 @@ def test_variant_read_stats_match_reference_golden(oracle, golden_dir):
     assert nsup > 400
 
 
-def test_tandem_annotation_matches_unmodified_reference_build():
-    """platypus_amd.indelprior.annotate against oracle/_ref/libtandem_ref.so = the UNMODIFIED src/c/tandem.c (built by
-    oracle/Makefile from where it lies in the reference tree; the prebuilt file travels to the GPU box)."""
+def test_tandem_annotation_matches_unmodified_reference_build(golden_dir):
+    """platypus_amd.indelprior.annotate against the UNMODIFIED src/c/tandem.c: 400 sequences (N's, lower case, planted repeats of
+    units 1..12), both modes, with the reference's answers stored in tandem_cases.npz (tests/golden/gen_golden.py gen_tandem); the
+    live reference build (oracle/_ref/libtandem_ref.so, built by oracle/Makefile where the reference tree lies) is asked too when present."""
     import ctypes as C
-    import os
-    import numpy as np
-    import pytest
     from platypus_amd.indelprior import annotate
+    g = np.load(os.path.join(golden_dir, "tandem_cases.npz"))
     so = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "libtandem_ref.so")
-    if not os.path.exists(so):
-        pytest.skip("oracle/_ref/libtandem_ref.so not built (reference tree absent)")
-    lib = C.CDLL(so)
-    rng = np.random.default_rng(11)
-    for it in range(400):
-        n = int(rng.integers(1, 300))
-        seq = bytearray(bytes(rng.choice(list(b"ACGT" if it % 3 else b"ACGTNacgtn"), n).astype(np.uint8)))
-        for _ in range(int(rng.integers(0, 5))):
-            p = int(rng.integers(0, n)); u = bytes(rng.choice(list(b"ACGT"), int(rng.integers(1, 13))).astype(np.uint8)); k = int(rng.integers(2, 90))
-            seq[p:p + k] = (u * k)[:k]
-        seq = bytes(seq[:n])
-        for full in (True, False):
-            s, d = C.create_string_buffer(n + 1), C.create_string_buffer(n + 1)
-            lib.annotate(seq, s, d, -n if full else n)
+    lib = C.CDLL(so) if os.path.exists(so) else None
+    off = g["off"]
+    assert len(off) == 401
+    for i in range(len(off) - 1):
+        a, b = int(off[i]), int(off[i + 1])
+        seq, n = g["seq"][a:b].tobytes(), b - a
+        for full, tag in ((True, "full"), (False, "start")):
+            want = (list(g[tag + "_size"][a:b]), list(g[tag + "_disp"][a:b]))
             got = annotate(seq, full)
-            assert (list(got[0]), list(got[1])) == (list(s.raw[:n]), list(d.raw[:n])), (seq, full)
+            assert (list(got[0]), list(got[1])) == want, (seq, full)
+            if lib is not None:
+                s, d = C.create_string_buffer(n + 1), C.create_string_buffer(n + 1)
+                lib.annotate(seq, s, d, -n if full else n)
+                assert (list(s.raw[:n]), list(d.raw[:n])) == want, (seq, full)

@@ -587,7 +587,7 @@ def line_config4(a, rk, lib=None, region_len=100000, region_kw=None, resident=No
     per_chunk = int(os.environ.get("PLAT_CALLER_CHUNK", str(auto_chunk) if resident else "16"))
     pin = os.environ.get("PLAT_CALLER_PINNED", "1") == "1" and lib is None
     packed = os.environ.get("PLAT_CALLER_PACKED", "1") == "1"
-    repeats = max(1, min(int(a.steps or 10), 200))                           # K steps = K runs over the rank's share, timed in one bracket (a run is ~0.1 s)
+    repeats = max(1, int(a.steps or 10))                                     # K steps = K runs over the rank's share, timed in one bracket (a run is ~0.1 s)
     r = config4(rk.dev_index, mine, region_len, workers, per_chunk, repeats=repeats, pin=pin, lib=lib, region_kw=region_kw, rk=rk, packed=packed,
                 resident=resident, job_regions=None if os.environ.get("PLAT_BENCH_LINE_MERGE") == "1" else list(range(total)),
                 warm_rounds=getattr(a, "warmup", 2) or 2)
