@@ -319,6 +319,29 @@ cdef extern from "platypus_mi355x.h":
     int plat_read_qc_batch(plat_ctx* ctx, const plat_readqc_batch* batch, const plat_readqc_options* options, int32_t* out_ok,
                            int32_t* out_reason, void* stream) nogil
 
+    # ---- the read buffers of fetched streams: checkAndTrimRead + addReadToBuffer's split (cwindow.pyx:560-595), gathered on the device
+    ctypedef struct plat_read_buffers_in:
+        plat_readqc_batch qc
+        int32_t n_streams
+        int32_t _pad
+        const int32_t* stream_begin
+        const uint8_t* read_seq
+        const int32_t* read_end
+    ctypedef struct plat_read_buffers_tables:
+        int64_t* off
+        int32_t* cig_off
+        uint8_t* seq
+        uint8_t* qual
+        int16_t* cigar
+        int32_t* pos
+        int32_t* end
+        uint8_t* mapq
+        int32_t* flags
+        int32_t* mate_pos
+    int plat_read_buffers_batch(plat_ctx* ctx, const plat_read_buffers_in* inp, const plat_readqc_options* options, int32_t* out_ok,
+                                int32_t* out_reason, int32_t* out_perm, int32_t* out_counts, const plat_read_buffers_tables* tab,
+                                void* stream) nogil
+
     # ---- window read slices out of a resident read table (cwindow.pyx:208-264,655-689)
     # the read table of a loader that wrote one byte per base (2-bit base | quality << 2) expanded to ASCII on the device
     int plat_unpack_reads(plat_ctx* ctx, int64_t n_bytes, const uint8_t* packed, uint8_t* out_seq, uint8_t* out_qual, int64_t n_exc,
@@ -384,3 +407,49 @@ cdef extern from "platypus_mi355x.h":
     int plat_assemble_batch_async(plat_ctx* ctx, const plat_assembly_batch* batch, const plat_assembly_hints* hints, int kmer_size, int min_qual,
                                   int min_weight, int no_cycles, int max_vars_per_region, int blob_per_region, int32_t* var_count, int32_t* var_pos,
                                   int32_t* var_nrem, int32_t* var_nadd, int32_t* var_off, uint8_t* var_blob, int32_t* status, void* stream) nogil
+
+
+# The region loop of libplat_caller.so fed with fetched reads (include/platypus_caller_fetched.h): what loadBAMData (platypusutils.pyx:449-686)
+# would hand over instead of its bamReadBuffers.  The tables, options and statistics of platypus_caller.h are used through pointers here.
+cdef extern from "platypus_caller_fetched.h":
+    ctypedef struct plat_caller:
+        pass
+    ctypedef struct plat_read_table:
+        pass
+    ctypedef struct plat_caller_options:
+        pass
+    ctypedef struct plat_caller_stats:
+        pass
+    ctypedef struct plat_fetched_reads:
+        plat_read_table fetched
+        plat_read_table broken_mates
+        const int16_t* chrom_id
+        const int16_t* mate_chrom_id
+        const int32_t* insert_size
+    ctypedef struct plat_fetched_region:
+        const char* chrom
+        int32_t start
+        int32_t end
+        const uint8_t* contig_seq
+        int64_t contig_len
+        const plat_fetched_reads* samples
+        const uint8_t* dev_contig_seq
+    ctypedef struct plat_caller_qc_options:
+        int32_t minGoodQualBases
+        int32_t minMapQual
+        int32_t minBaseQual
+        int32_t trimOverlapping
+        int32_t trimAdapter
+        int32_t trimReadFlank
+        int32_t trimSoftClipped
+        int32_t filterDuplicates
+        int32_t filterReadsWithUnmappedMates
+        int32_t filterReadsWithDistantMates
+        int32_t filterReadPairsWithSmallInserts
+    ctypedef struct plat_fetched_region_info:
+        int32_t loaded
+        int32_t* sample_counts
+    void plat_caller_default_qc_options(plat_caller_qc_options* out)
+    int plat_call_fetched_regions(plat_caller* c, const plat_fetched_region* regions, int n_regions, int n_samples,
+                                  const char* const* sample_names, plat_caller_options* options, const plat_caller_qc_options* qc,
+                                  char** out_text, size_t* out_len, plat_fetched_region_info* info, plat_caller_stats* stats) nogil

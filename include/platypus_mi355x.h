@@ -507,6 +507,43 @@ typedef struct plat_readqc_options {
 int plat_read_qc_batch(plat_ctx* ctx, const plat_readqc_batch* batch, const plat_readqc_options* options,
                        int32_t* out_ok, int32_t* out_reason, void* stream);
 
+/* ---- read buffers from fetched reads ----------------------------------------------------------------
+ * Replaces  the loop of loadBAMData over a fetch (platypusutils.pyx:505-541) through bamReadBuffer.addReadToBuffer
+ *           (cwindow.pyx:560-595): checkAndTrimRead on every read, then `reads.append` / `badReads.append` and the
+ *           isSorted bookkeeping.
+ * n_streams streams (one stream = the reads one bamReadBuffer is handed, in fetch order) lie back to back in one read table:
+ * stream s = reads [stream_begin[s], stream_begin[s+1]), and qc.stream_of[r] must be the stream of read r.  The call runs
+ * plat_read_qc_batch's checkAndTrimRead in place (qc.read_qual trimmed, BAM_FQCFAIL set in qc.read_flags; verdicts in out_ok /
+ * out_reason) and then splits every stream, stably, in one pass over its verdicts (wave ballots and prefix sums):
+ *   out_perm[stream_begin[s] + k]  the read (index into the table) at place k of the stream's buffers: its accepted reads in
+ *                                  fetch order (`reads`), then its rejected reads in fetch order (`badReads`)
+ *   out_counts[10*s + ..]          {n_good, unsorted (1: some read's pos is lower than the pos of the read before it -- the
+ *                                  reference's isSorted = False), then the 8-slot histogram of out_reason (0..7)}
+ * Optional, all or none (`tab.seq` NULL: none): the two buffers of every stream GATHERED into the tables of `tab` -- what
+ * plat_read_table's dev_* arrays describe.  Reads go to tab.pos / end / mapq / flags / mate_pos[stream_begin[s] + k] in
+ * out_perm's order; their bases and trimmed qualities to tab.seq / tab.qual and CIGAR pairs to tab.cigar at the same places as the
+ * stream's input bytes and pairs (qc.read_off[stream_begin[s]], qc.cig_off[stream_begin[s]]), `reads` first.  tab.off / tab.cig_off
+ * hold two tables per stream, each starting at 0 and closed by its total: `reads` at [stream_begin[s] + 2s, +n_good+1), `badReads`
+ * right behind it, [stream_begin[s] + 2s + n_good + 1, +n_bad+1).  Sizes: off / cig_off n_reads + 2*n_streams, seq / qual the
+ * input's bytes + PLAT_BLOB_PAD, cigar 2 * the input's pairs.                                                                  */
+typedef struct plat_read_buffers_in {
+    plat_readqc_batch qc;            /* the table; qc.read_off / qc.cig_off start at 0 */
+    int32_t n_streams, _pad;
+    const int32_t* stream_begin;     /* [n_streams+1], stream_begin[0] = 0, stream_begin[n_streams] = qc.n_reads */
+    const uint8_t* read_seq;         /* for the gathered tables (NULL without them) */
+    const int32_t* read_end;
+} plat_read_buffers_in;
+
+typedef struct plat_read_buffers_tables {
+    int64_t* off; int32_t* cig_off;
+    uint8_t* seq; uint8_t* qual; int16_t* cigar;
+    int32_t* pos; int32_t* end; uint8_t* mapq; int32_t* flags; int32_t* mate_pos;
+} plat_read_buffers_tables;
+
+int plat_read_buffers_batch(plat_ctx* ctx, const plat_read_buffers_in* in, const plat_readqc_options* options, int32_t* out_ok,
+                            int32_t* out_reason, int32_t* out_perm, int32_t* out_counts, const plat_read_buffers_tables* tab /* may be NULL */,
+                            void* stream);
+
 /* ---- read statistics of the VCF INFO field ---------------------------------------
  * Replaces the per-variant loop over a window's reads in  cdef dict vcfINFO(...)   vcfutils.pyx:1300-1390
  * (readOverlapsVariant :901-913, readQualIsGoodVariantPosition :917-943, variantSupportedByRead :961-1072).

@@ -87,6 +87,15 @@ class ReadQCOptions(C.Structure):
                                          "filter_small_insert", "filter_duplicates")]
 
 
+class ReadBuffersIn(C.Structure):
+    _fields_ = [("qc", ReadQCBatch), ("n_streams", C.c_int32), ("_pad", C.c_int32), ("stream_begin", C.c_void_p), ("read_seq", C.c_void_p),
+                ("read_end", C.c_void_p)]
+
+
+class ReadBuffersTables(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("off", "cig_off", "seq", "qual", "cigar", "pos", "end", "mapq", "flags", "mate_pos")]
+
+
 class InfoStatsBatch(C.Structure):
     _fields_ = [("n_vars", C.c_int32), ("n_ind", C.c_int32)] + [(k, C.c_void_p) for k in (
         "var_window", "var_pos", "var_bam_min", "var_bam_max", "var_n_added", "var_n_removed", "var_added", "var_added_off",
@@ -151,6 +160,8 @@ SIGNATURES = {
     "plat_copy_pieces": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "plat_concat_read_tables": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 9 + [C.c_int64] * 3 + [C.c_void_p]),
     "plat_read_qc_batch": (C.c_int, [C.c_void_p, C.POINTER(ReadQCBatch), C.POINTER(ReadQCOptions), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "plat_read_buffers_batch": (C.c_int, [C.c_void_p, C.POINTER(ReadBuffersIn), C.POINTER(ReadQCOptions), C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.POINTER(ReadBuffersTables), C.c_void_p]),
     "plat_variant_read_stats_batch": (C.c_int, [C.c_void_p, C.POINTER(InfoStatsBatch), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
     "plat_variant_info_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -161,6 +172,10 @@ SIGNATURES = {
                                             C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p]),
 }
+
+# entry points a stand-in library built against an earlier header may lack (the CPU suite's fake device): bind() leaves them
+# unbound there; load() still requires every declared symbol of the real library
+ADDED_LATER = ("plat_read_buffers_batch",)
 
 _lib = None
 
@@ -189,13 +204,19 @@ def load():
         import torch  # noqa: F401
     except ImportError:
         pass
-    _lib = bind(C.CDLL(LIB_PATH))
+    lib = bind(C.CDLL(LIB_PATH))
+    missing = [name for name in SIGNATURES if not hasattr(lib, name)]
+    if missing:
+        raise RuntimeError("libplat_mi355x.so does not export %s" % ", ".join(missing))
+    _lib = lib
     return _lib
 
 
 def bind(lib):
     """Attach the prototypes of include/platypus_mi355x.h to a loaded library exporting that ABI."""
     for name, (res, args) in SIGNATURES.items():
+        if name in ADDED_LATER and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)      # AttributeError here == the library does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

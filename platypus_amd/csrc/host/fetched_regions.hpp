@@ -1,0 +1,315 @@
+// fetched_regions.hpp -- plat_call_fetched_regions (include/platypus_caller_fetched.h): the region loop for reads as a BAM fetch returns
+// them.  In front of plat_call_regions: the loader's per-read work of loadBAMData (platypusutils.pyx:505-541) through
+// bamReadBuffer.addReadToBuffer (cwindow.pyx:560-595) -- checkAndTrimRead, reads / badReads, isSorted, maxReads -- on the device
+// (plat_read_buffers_batch), the buffers gathered there and handed to the loop as device-resident tables (plat_read_table.dev_*).
+// Included at the end of region_caller.cpp (it calls plat_call_regions and reads plat_caller).
+#pragma once
+#include <climits>
+#include "../../../include/platypus_caller_fetched.h"
+
+// The device entry point is referenced weakly: the CPU test suite links this library against a stand-in device library that predates it
+// (the call then returns PLAT_ERR_UNSUPPORTED).
+#pragma weak plat_read_buffers_batch
+
+namespace plathost {
+
+// device memory of one call, freed on every way out
+struct FetchedDeviceBuffers {
+    plat_ctx* ctx;
+    std::vector<void*> held;
+    explicit FetchedDeviceBuffers(plat_ctx* c) : ctx(c) {}
+    template <class T> T* alloc(size_t n) {
+        void* p = nullptr;
+        ck(plat_malloc(ctx, std::max<size_t>(n, 1) * sizeof(T), &p), "plat_malloc");
+        held.push_back(p);
+        return (T*)p;
+    }
+    template <class T> T* upload(const std::vector<T>& h, void* stream) {
+        T* d = alloc<T>(h.size());
+        if (!h.empty()) ck(plat_memcpy_h2d(ctx, d, h.data(), h.size() * sizeof(T), stream), "plat_memcpy_h2d");
+        return d;
+    }
+    ~FetchedDeviceBuffers() { for (void* p : held) plat_free(ctx, p); }
+};
+
+// one buffer (reads or badReads) of one sample as the host's stages see it: per-read arrays and bases, no qualities
+struct FetchedHostTable {
+    std::vector<int64_t> off;
+    std::vector<int32_t> pos, end, flags, matePos, cigOff;
+    std::vector<uint8_t> mapq, seq;
+    std::vector<int16_t> cigar;
+};
+
+static std::string fetchedWhere(const plat_fetched_region& r, int k, int i) {
+    return "region " + std::to_string(k) + " (" + (r.chrom ? r.chrom : "?") + ":" + std::to_string(r.start) + "-" + std::to_string(r.end) +
+           "), sample " + std::to_string(i);
+}
+
+}  // namespace plathost
+
+CALLER_EXPORT void plat_caller_default_qc_options(plat_caller_qc_options* o) {
+    if (!o) return;
+    o->minGoodQualBases = 20; o->minMapQual = 20; o->minBaseQual = 20;
+    o->trimOverlapping = 1; o->trimAdapter = 1; o->trimReadFlank = 0; o->trimSoftClipped = 1;
+    o->filterDuplicates = 1; o->filterReadsWithUnmappedMates = 1; o->filterReadsWithDistantMates = 1; o->filterReadPairsWithSmallInserts = 1;
+}
+
+CALLER_EXPORT int plat_call_fetched_regions(plat_caller* c, const plat_fetched_region* regions, int n_regions, int n_samples,
+                                            const char* const* sample_names, plat_caller_options* options, const plat_caller_qc_options* qc,
+                                            char** out_text, size_t* out_len, plat_fetched_region_info* info, plat_caller_stats* stats)
+{
+    int rc = checkCallArgs(c, options, out_text, out_len, n_regions, n_samples);
+    if (rc != PLAT_OK) return rc;
+    if (!qc || (n_regions > 0 && !regions)) return PLAT_ERR_INVALID;
+    if (!plat_read_buffers_batch) {
+        c->lastError = "plat_call_fetched_regions: the device library has no plat_read_buffers_batch";
+        return PLAT_ERR_UNSUPPORTED;
+    }
+    const auto t0 = Clock::now();
+    // loadBAMData's bail-out (:538-541): `totalReads >= maxReads` after each fetched read, summed over the samples; a region with no reads
+    // never gets there
+    const double mr = options->maxReads;
+    const long long maxReads = mr >= (double)INT_MAX ? INT_MAX : (mr <= (double)INT_MIN ? INT_MIN : (long long)mr);     // (cdef int maxReads)
+    std::vector<int> loaded((size_t)n_regions, 0);
+    long long nReads = 0, nBytes = 0, nPairs = 0, nBroken = 0, nBrokenBytes = 0, nBrokenPairs = 0;
+    int nStreams = 0;
+    for (int k = 0; k < n_regions; ++k) {
+        const plat_fetched_region& r = regions[k];
+        if (!r.samples) return PLAT_ERR_INVALID;
+        long long total = 0;
+        for (int i = 0; i < n_samples; ++i) {
+            const plat_read_table* tabs[2] = {&r.samples[i].fetched, &r.samples[i].broken_mates};
+            for (const plat_read_table* t : tabs) {
+                if (t->n_reads < 0) return PLAT_ERR_INVALID;
+                if (t->encoding == PLAT_READS_PACKED) {
+                    c->lastError = "plat_call_fetched_regions: PLAT_READS_PACKED tables are not supported (" + fetchedWhere(r, k, i) + ")";
+                    return PLAT_ERR_UNSUPPORTED;
+                }
+                if (t->encoding != PLAT_READS_ASCII) return PLAT_ERR_INVALID;
+                if (t->n_reads && (!t->seq || !t->qual || !t->off || !t->pos || !t->end || !t->mapq || !t->flags || !t->mate_pos || !t->cig_off ||
+                                   (t->cig_off[t->n_reads] && !t->cigar) || t->off[0] != 0 || t->cig_off[0] != 0))
+                    return PLAT_ERR_INVALID;
+            }
+            const plat_fetched_reads& f = r.samples[i];
+            if (f.fetched.n_reads && (!f.chrom_id || !f.mate_chrom_id || !f.insert_size)) return PLAT_ERR_INVALID;
+            total += f.fetched.n_reads;
+        }
+        loaded[(size_t)k] = !(total > 0 && total >= maxReads);
+        if (!loaded[(size_t)k]) continue;
+        for (int i = 0; i < n_samples; ++i) {
+            const plat_read_table& t = r.samples[i].fetched;
+            const plat_read_table& m = r.samples[i].broken_mates;
+            nReads += t.n_reads; nBytes += t.n_reads ? t.off[t.n_reads] : 0; nPairs += t.n_reads ? t.cig_off[t.n_reads] : 0;
+            nBroken += m.n_reads; nBrokenBytes += m.n_reads ? m.off[m.n_reads] : 0; nBrokenPairs += m.n_reads ? m.cig_off[m.n_reads] : 0;
+            ++nStreams;
+        }
+    }
+    if (nReads > INT_MAX - 2ll * nStreams - 1 || nBroken > INT_MAX - (long long)nStreams - 1 || nPairs > INT_MAX || nBrokenPairs > INT_MAX) {
+        c->lastError = "plat_call_fetched_regions: more reads than one call takes (call the region list in parts)";
+        return PLAT_ERR_OVERFLOW;
+    }
+    Slot& z = *c->slots[0];
+    FetchedDeviceBuffers dev(z.ctx);
+    std::vector<std::vector<FetchedHostTable>> host;                     // [stream][0 reads, 1 badReads]
+    std::vector<plat_read_table> tabs;                                    // 3 per stream: reads, badReads, brokenMates
+    std::vector<plat_sample_reads> sampleReads;
+    std::vector<plat_region> called;
+    std::vector<int32_t> counts((size_t)nStreams * 10, 0);
+    try {
+        // the fetched tables, stream after stream (one stream = one sample of one loaded region), and the broken mates, table after table
+        // with offsets from 0 per table
+        std::vector<uint8_t> seq, qual, mapq, bSeq, bQual, bMapq;
+        std::vector<int64_t> off, bOff;
+        std::vector<int32_t> pos, end, flags, matePos, insert, cigOff, streamOf, streamBegin, bPos, bEnd, bFlags, bCigOff;
+        std::vector<int16_t> cigar, chrom, mateChrom, bCigar;
+        std::vector<long long> bOffAt, bByteAt, bPairAt, bReadAt;
+        seq.reserve((size_t)nBytes + PLAT_BLOB_PAD); qual.reserve((size_t)nBytes + PLAT_BLOB_PAD);
+        off.reserve((size_t)nReads + 1); cigOff.reserve((size_t)nReads + 1);
+        streamBegin.push_back(0);
+        int s = 0;
+        for (int k = 0; k < n_regions; ++k) {
+            if (!loaded[(size_t)k]) continue;
+            for (int i = 0; i < n_samples; ++i, ++s) {
+                const plat_fetched_reads& f = regions[k].samples[i];
+                const plat_read_table& t = f.fetched;
+                const int n = t.n_reads;
+                const int64_t b0 = (int64_t)seq.size();
+                const int32_t c0 = (int32_t)cigar.size() / 2;
+                if (n) {
+                    const size_t nb = (size_t)t.off[n], nc = (size_t)t.cig_off[n];
+                    seq.insert(seq.end(), t.seq, t.seq + nb); qual.insert(qual.end(), t.qual, t.qual + nb);
+                    for (int r = 0; r < n; ++r) { off.push_back(b0 + t.off[r]); cigOff.push_back(c0 + t.cig_off[r]); }
+                    pos.insert(pos.end(), t.pos, t.pos + n); end.insert(end.end(), t.end, t.end + n); mapq.insert(mapq.end(), t.mapq, t.mapq + n);
+                    flags.insert(flags.end(), t.flags, t.flags + n); matePos.insert(matePos.end(), t.mate_pos, t.mate_pos + n);
+                    chrom.insert(chrom.end(), f.chrom_id, f.chrom_id + n); mateChrom.insert(mateChrom.end(), f.mate_chrom_id, f.mate_chrom_id + n);
+                    insert.insert(insert.end(), f.insert_size, f.insert_size + n);
+                    if (nc) cigar.insert(cigar.end(), t.cigar, t.cigar + 2 * nc);
+                    streamOf.insert(streamOf.end(), (size_t)n, s);
+                }
+                streamBegin.push_back((int32_t)pos.size());
+                const plat_read_table& m = f.broken_mates;
+                bOffAt.push_back((long long)bOff.size()); bByteAt.push_back((long long)bSeq.size()); bPairAt.push_back((long long)bCigar.size() / 2);
+                bReadAt.push_back((long long)bPos.size());
+                if (m.n_reads) {
+                    const size_t nb = (size_t)m.off[m.n_reads], nc = (size_t)m.cig_off[m.n_reads];
+                    bSeq.insert(bSeq.end(), m.seq, m.seq + nb); bQual.insert(bQual.end(), m.qual, m.qual + nb);
+                    bOff.insert(bOff.end(), m.off, m.off + m.n_reads + 1); bCigOff.insert(bCigOff.end(), m.cig_off, m.cig_off + m.n_reads + 1);
+                    bPos.insert(bPos.end(), m.pos, m.pos + m.n_reads); bEnd.insert(bEnd.end(), m.end, m.end + m.n_reads);
+                    bMapq.insert(bMapq.end(), m.mapq, m.mapq + m.n_reads); bFlags.insert(bFlags.end(), m.flags, m.flags + m.n_reads);
+                    if (nc) bCigar.insert(bCigar.end(), m.cigar, m.cigar + 2 * nc);
+                }
+            }
+        }
+        off.push_back((int64_t)seq.size()); cigOff.push_back((int32_t)cigar.size() / 2);
+        cigar.push_back(0); cigar.push_back(0); bCigar.push_back(0); bCigar.push_back(0);
+        seq.resize(seq.size() + PLAT_BLOB_PAD, 0); qual.resize(qual.size() + PLAT_BLOB_PAD, 0);
+        bSeq.resize(bSeq.size() + PLAT_BLOB_PAD, 0); bQual.resize(bQual.size() + PLAT_BLOB_PAD, 0);
+        const int N = (int)nReads;
+
+        // upload once; QC, split and gather on the device
+        void* st = z.stream;
+        plat_read_buffers_in in;
+        memset(&in, 0, sizeof in);
+        in.qc.n_reads = N;
+        in.qc.read_qual = dev.upload(qual, st); in.qc.read_off = dev.upload(off, st); in.qc.read_pos = dev.upload(pos, st);
+        in.qc.read_mapq = dev.upload(mapq, st); in.qc.read_flags = dev.upload(flags, st); in.qc.chrom_id = dev.upload(chrom, st);
+        in.qc.mate_chrom_id = dev.upload(mateChrom, st); in.qc.insert_size = dev.upload(insert, st); in.qc.mate_pos = dev.upload(matePos, st);
+        in.qc.cigar = dev.upload(cigar, st); in.qc.cig_off = dev.upload(cigOff, st); in.qc.stream_of = dev.upload(streamOf, st);
+        in.n_streams = nStreams; in.stream_begin = dev.upload(streamBegin, st);
+        in.read_seq = dev.upload(seq, st); in.read_end = dev.upload(end, st);
+        plat_readqc_options qo;
+        qo.min_good_qual_bases = qc->minGoodQualBases; qo.min_map_qual = qc->minMapQual; qo.min_base_qual = qc->minBaseQual;
+        qo.trim_overlapping = qc->trimOverlapping; qo.trim_adapter = qc->trimAdapter; qo.trim_read_flank = qc->trimReadFlank;
+        qo.trim_soft_clipped = qc->trimSoftClipped; qo.filter_mate_unmapped = qc->filterReadsWithUnmappedMates;
+        qo.filter_mate_distant = qc->filterReadsWithDistantMates; qo.filter_small_insert = qc->filterReadPairsWithSmallInserts;
+        qo.filter_duplicates = qc->filterDuplicates;
+        plat_read_buffers_tables g;
+        g.off = dev.alloc<int64_t>((size_t)N + 2 * (size_t)nStreams); g.cig_off = dev.alloc<int32_t>((size_t)N + 2 * (size_t)nStreams);
+        g.seq = dev.alloc<uint8_t>(seq.size()); g.qual = dev.alloc<uint8_t>(qual.size()); g.cigar = dev.alloc<int16_t>(cigar.size());
+        g.pos = dev.alloc<int32_t>((size_t)N); g.end = dev.alloc<int32_t>((size_t)N); g.mapq = dev.alloc<uint8_t>((size_t)N);
+        g.flags = dev.alloc<int32_t>((size_t)N); g.mate_pos = dev.alloc<int32_t>((size_t)N);
+        ck(plat_memset(z.ctx, g.seq, 0, seq.size(), st), "plat_memset");       // (the blob's slack: 7-bit bytes for kernels that read whole dwords)
+        ck(plat_memset(z.ctx, g.qual, 0, qual.size(), st), "plat_memset");
+        ck(plat_memset(z.ctx, g.cigar, 0, cigar.size() * sizeof(int16_t), st), "plat_memset");
+        int32_t* dOk = dev.alloc<int32_t>((size_t)N);
+        int32_t* dWhy = dev.alloc<int32_t>((size_t)N);
+        int32_t* dPerm = dev.alloc<int32_t>((size_t)N);
+        int32_t* dCounts = dev.alloc<int32_t>((size_t)nStreams * 10);
+        if (nStreams) ck(plat_read_buffers_batch(z.ctx, &in, &qo, dOk, dWhy, dPerm, dCounts, &g, st), "plat_read_buffers_batch");
+        // broken mates: as handed over, resident
+        uint8_t* dbSeq = dev.upload(bSeq, st); uint8_t* dbQual = dev.upload(bQual, st); int64_t* dbOff = dev.upload(bOff, st);
+        int32_t* dbPos = dev.upload(bPos, st); int32_t* dbEnd = dev.upload(bEnd, st); uint8_t* dbMapq = dev.upload(bMapq, st);
+        int32_t* dbFlags = dev.upload(bFlags, st); int16_t* dbCigar = dev.upload(bCigar, st); int32_t* dbCigOff = dev.upload(bCigOff, st);
+        // what the host's stages need back: the split, the counts and the flags after QC (QCFail, improper pairs)
+        std::vector<int32_t> perm((size_t)N), flagsQc((size_t)N);
+        if (N) {
+            ck(plat_memcpy_d2h(z.ctx, perm.data(), dPerm, sizeof(int32_t) * (size_t)N, st), "plat_memcpy_d2h");
+            ck(plat_memcpy_d2h(z.ctx, flagsQc.data(), in.qc.read_flags, sizeof(int32_t) * (size_t)N, st), "plat_memcpy_d2h");
+        }
+        if (nStreams) ck(plat_memcpy_d2h(z.ctx, counts.data(), dCounts, sizeof(int32_t) * counts.size(), st), "plat_memcpy_d2h");
+        ck(plat_stream_sync(z.ctx, st), "plat_stream_sync");
+
+        // the buffers, as the host sees them and as the device holds them
+        host.resize((size_t)nStreams);
+        tabs.resize(3 * (size_t)nStreams);
+        s = 0;
+        for (int k = 0; k < n_regions; ++k) {
+            if (!loaded[(size_t)k]) continue;
+            for (int i = 0; i < n_samples; ++i, ++s) {
+                const int b = streamBegin[(size_t)s], n = streamBegin[(size_t)s + 1] - b, nGood = counts[10 * (size_t)s];
+                if (nGood < 0 || nGood > n) throw DeviceError(PLAT_ERR_BAD_INPUT, "plat_read_buffers_batch: stream " + std::to_string(s) + " was not split");
+                if (counts[10 * (size_t)s + 1]) {
+                    c->lastError = "plat_call_fetched_regions: the fetched reads of " + fetchedWhere(regions[k], k, i) +
+                                   " are not sorted by position (a BAM fetch is coordinate-sorted; the reference would sort them with an unstable qsort)";
+                    return PLAT_ERR_BAD_INPUT;
+                }
+                const int64_t byte0 = off[(size_t)b];
+                const int32_t pair0 = cigOff[(size_t)b];
+                host[(size_t)s].resize(2);
+                int64_t byteAt = byte0;
+                int32_t pairAt = pair0;
+                for (int part = 0; part < 2; ++part) {
+                    const int p0 = part == 0 ? 0 : nGood, p1 = part == 0 ? nGood : n, m = p1 - p0;
+                    FetchedHostTable& h = host[(size_t)s][(size_t)part];
+                    h.off.resize((size_t)m + 1); h.cigOff.resize((size_t)m + 1);
+                    h.pos.resize((size_t)m); h.end.resize((size_t)m); h.flags.resize((size_t)m); h.matePos.resize((size_t)m); h.mapq.resize((size_t)m);
+                    int64_t bo = 0;
+                    int32_t co = 0;
+                    for (int q = 0; q < m; ++q) {
+                        const int r = perm[(size_t)(b + p0 + q)];
+                        h.off[(size_t)q] = bo; h.cigOff[(size_t)q] = co;
+                        const int64_t len = off[(size_t)r + 1] - off[(size_t)r];
+                        const int32_t nc = cigOff[(size_t)r + 1] - cigOff[(size_t)r];
+                        h.seq.insert(h.seq.end(), seq.begin() + off[(size_t)r], seq.begin() + off[(size_t)r] + len);
+                        h.cigar.insert(h.cigar.end(), cigar.begin() + 2 * (size_t)cigOff[(size_t)r], cigar.begin() + 2 * ((size_t)cigOff[(size_t)r] + (size_t)nc));
+                        h.pos[(size_t)q] = pos[(size_t)r]; h.end[(size_t)q] = end[(size_t)r]; h.mapq[(size_t)q] = mapq[(size_t)r];
+                        h.flags[(size_t)q] = flagsQc[(size_t)r]; h.matePos[(size_t)q] = matePos[(size_t)r];
+                        bo += len; co += nc;
+                    }
+                    h.off[(size_t)m] = bo; h.cigOff[(size_t)m] = co;
+                    h.seq.resize(h.seq.size() + PLAT_BLOB_PAD, 0);
+                    h.cigar.push_back(0); h.cigar.push_back(0);
+                    plat_read_table& t = tabs[3 * (size_t)s + (size_t)part];
+                    memset(&t, 0, sizeof t);
+                    t.n_reads = m; t.encoding = PLAT_READS_ASCII;
+                    t.seq = h.seq.data(); t.qual = nullptr; t.off = h.off.data(); t.pos = h.pos.data(); t.end = h.end.data(); t.mapq = h.mapq.data();
+                    t.flags = h.flags.data(); t.mate_pos = h.matePos.data(); t.cigar = h.cigar.data(); t.cig_off = h.cigOff.data();
+                    // the device's copy (plat_read_buffers_batch's layout: `reads` then `badReads` at the stream's input bytes and pairs)
+                    const size_t oi = (size_t)b + 2 * (size_t)s + (part == 0 ? 0 : (size_t)nGood + 1);
+                    t.dev_seq = g.seq + byteAt; t.dev_qual = g.qual + byteAt; t.dev_off = g.off + oi; t.dev_cig_off = g.cig_off + oi;
+                    t.dev_cigar = g.cigar + 2 * (size_t)pairAt; t.dev_pos = g.pos + b + p0; t.dev_end = g.end + b + p0;
+                    t.dev_mapq = g.mapq + b + p0; t.dev_flags = g.flags + b + p0;
+                    byteAt += bo; pairAt += co;
+                }
+                const plat_read_table& m = regions[k].samples[i].broken_mates;
+                plat_read_table& t = tabs[3 * (size_t)s + 2];
+                t = m;
+                t.dev_seq = dbSeq + bByteAt[(size_t)s]; t.dev_qual = dbQual + bByteAt[(size_t)s]; t.dev_off = dbOff + bOffAt[(size_t)s];
+                t.dev_cig_off = dbCigOff + bOffAt[(size_t)s]; t.dev_cigar = dbCigar + 2 * bPairAt[(size_t)s];
+                const long long r0 = bReadAt[(size_t)s];
+                t.dev_pos = dbPos + r0; t.dev_end = dbEnd + r0; t.dev_mapq = dbMapq + r0; t.dev_flags = dbFlags + r0;
+                if (!m.n_reads) { t.dev_off = nullptr; t.dev_seq = nullptr; }
+            }
+        }
+    } catch (const DeviceError& e) {
+        c->lastError = e.what();
+        return e.code;
+    }
+    // the loop over the regions that were loaded, exactly as plat_call_regions runs it
+    sampleReads.resize((size_t)nStreams);
+    for (int s = 0; s < nStreams; ++s) sampleReads[(size_t)s] = plat_sample_reads{tabs[3 * (size_t)s], tabs[3 * (size_t)s + 1], tabs[3 * (size_t)s + 2]};
+    int s = 0;
+    for (int k = 0; k < n_regions; ++k) {
+        if (!loaded[(size_t)k]) continue;
+        const plat_fetched_region& r = regions[k];
+        called.push_back(plat_region{r.chrom, r.start, r.end, r.contig_seq, r.contig_len, sampleReads.data() + s, r.dev_contig_seq});
+        s += n_samples;
+    }
+    plat_caller_stats st;
+    rc = plat_call_regions(c, called.data(), (int)called.size(), n_samples, sample_names, options, out_text, out_len, &st);
+    if (rc != PLAT_OK) return rc;
+    std::vector<int64_t> lengths((size_t)n_regions, 0);
+    for (int k = 0, j = 0; k < n_regions; ++k) if (loaded[(size_t)k]) lengths[(size_t)k] = c->lastLengths[(size_t)j++];
+    c->lastLengths.swap(lengths);
+    if (info) {
+        s = 0;
+        for (int k = 0; k < n_regions; ++k) {
+            info[k].loaded = loaded[(size_t)k];
+            for (int i = 0; i < n_samples; ++i) {
+                int32_t* out = info[k].sample_counts ? info[k].sample_counts + 10 * i : nullptr;
+                if (!out) continue;
+                if (!loaded[(size_t)k]) { for (int q = 0; q < 10; ++q) out[q] = 0; continue; }
+                const int32_t* cs = counts.data() + 10 * (size_t)(s + i);
+                const int n = regions[k].samples[i].fetched.n_reads;
+                out[0] = cs[0]; out[1] = n - cs[0];
+                for (int q = 0; q < 8; ++q) out[2 + q] = cs[2 + q];
+            }
+            if (loaded[(size_t)k]) s += n_samples;
+        }
+    }
+    st.n_regions = n_regions;
+    st.input_bytes = 2 * (nBytes + nBrokenBytes);
+    st.seconds_total = secs(t0, Clock::now());
+    if (stats) *stats = st;
+    return PLAT_OK;
+}

@@ -700,3 +700,4 @@ CALLER_EXPORT void plat_caller_debug_set_order(const char* names, char* out, siz
     for (const std::string& k : py2_set_order(in)) { if (!t.empty()) t += '\n'; t += k; }
     snprintf(out, cap, "%s", t.c_str());
 }
+#include "fetched_regions.hpp"

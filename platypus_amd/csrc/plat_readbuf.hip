@@ -1,0 +1,166 @@
+// plat_readbuf.hip -- the read buffers of fetched streams (plat_read_buffers_batch, include/platypus_mi355x.h):
+// checkAndTrimRead (k_read_qc, plat_candidates.hip) in place, then bamReadBuffer.addReadToBuffer's split into `reads` / `badReads`
+// (cwindow.pyx:560-595) as a stable per-stream partition, then, optionally, the two buffers gathered into device tables.
+#include "plat_internal.hpp"
+
+namespace plat {
+constexpr int SPLIT_THREADS = 512;                       // 8 waves per stream
+constexpr int SPLIT_WAVES = SPLIT_THREADS / 64;
+constexpr int SPLIT_MASKS = 4096;                        // verdict masks kept in LDS (32 KB): streams up to 256 k reads are read once
+
+__device__ __forceinline__ long long wave_incl_scan(long long v, int lane) {
+    for (int d = 1; d < 64; d <<= 1) {
+        const long long u = __shfl_up(v, d, 64);
+        if (lane >= d) v += u;
+    }
+    return v;
+}
+
+// One workgroup per stream.  Pass 1 walks the verdicts once in tiles of 512 reads: per wave a ballot of out_ok (kept in LDS), popcounts
+// of the 8 reasons, and the sortedness test against the previous read.  Pass 2 walks the ballots (LDS; re-taken from out_ok only past
+// SPLIT_MASKS tiles' worth) and places every read: its rank among the accepted (or the rejected) reads of the stream = the counts of the
+// tiles before + of the waves before (LDS) + the popcount of its wave's ballot below its lane.  With tables, the same prefix sums over
+// the reads' byte lengths and CIGAR pair counts give each read's offsets inside its buffer.
+__global__ void __launch_bounds__(SPLIT_THREADS)
+k_read_split(int n_reads, const int32_t* __restrict__ stream_begin, const int32_t* __restrict__ ok, const int32_t* __restrict__ reason,
+             const int32_t* __restrict__ pos, const int64_t* __restrict__ read_off, const int32_t* __restrict__ cig_off,
+             int32_t* __restrict__ perm, int32_t* __restrict__ counts, int64_t* __restrict__ t_off, int32_t* __restrict__ t_cigoff)
+{
+    __shared__ unsigned long long s_mask[SPLIT_MASKS];
+    __shared__ int s_hist[8], s_good, s_unsorted;
+    __shared__ long long s_wave[SPLIT_WAVES][6];
+    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = stream_begin[s], n = stream_begin[s + 1] - b;
+    if (b < 0 || n < 0 || (long long)b + n > n_reads || (s == 0 && b != 0)) {      // not a partition of the table: nothing of the stream is written
+        if (tid == 0) counts[10 * s] = -1;
+        return;
+    }
+    if (tid < 8) s_hist[tid] = 0;
+    if (tid == 0) { s_good = 0; s_unsorted = 0; }
+    __syncthreads();
+    // pass 1
+    int good = 0, hist[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    bool unsorted = false;
+    for (int t0 = 0; t0 < n; t0 += SPLIT_THREADS) {
+        const int i = t0 + tid;
+        const bool in = i < n;
+        const bool g = in && ok[b + i] != 0;
+        const int why = in ? reason[b + i] : -1;
+        if (in && i > 0 && pos[b + i] < pos[b + i - 1]) unsorted = true;
+        const unsigned long long m = __ballot(g);
+        const int tile = t0 / SPLIT_THREADS;
+        if (lane == 0 && tile * SPLIT_WAVES + wave < SPLIT_MASKS) s_mask[tile * SPLIT_WAVES + wave] = m;
+        good += __popcll(m);
+        for (int k = 0; k < 8; ++k) hist[k] += __popcll(__ballot(why == k));
+    }
+    if (lane == 0) {
+        atomicAdd(&s_good, good);
+        for (int k = 0; k < 8; ++k) if (hist[k]) atomicAdd(&s_hist[k], hist[k]);
+    }
+    if (unsorted) s_unsorted = 1;
+    __syncthreads();
+    const int nGood = s_good;
+    if (tid < 8) counts[10 * s + 2 + tid] = s_hist[tid];
+    if (tid == 0) { counts[10 * s] = nGood; counts[10 * s + 1] = s_unsorted; }
+    // pass 2
+    const bool tables = t_off != nullptr;
+    const long long offBase = (long long)b + 2ll * s;                 // the stream's two offset tables
+    long long run[6] = {0, 0, 0, 0, 0, 0};                            // good, bad, good bytes, bad bytes, good pairs, bad pairs placed so far
+    const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;
+    for (int t0 = 0; t0 < n; t0 += SPLIT_THREADS) {
+        const int i = t0 + tid, tile = t0 / SPLIT_THREADS;
+        const bool in = i < n;
+        const unsigned long long vmask = __ballot(in);
+        const unsigned long long m = tile * SPLIT_WAVES + wave < SPLIT_MASKS ? s_mask[tile * SPLIT_WAVES + wave] : __ballot(in && ok[b + i] != 0);
+        const bool g = (m >> lane) & 1ull;
+        long long v[6];
+        v[0] = __popcll(m & below); v[1] = __popcll(~m & vmask & below);
+        v[2] = v[3] = v[4] = v[5] = 0;
+        long long len = 0, pairs = 0;
+        if (tables) {
+            if (in) { len = read_off[b + i + 1] - read_off[b + i]; pairs = cig_off[b + i + 1] - cig_off[b + i]; }
+            const long long sl = wave_incl_scan(g ? len : 0, lane), bl = wave_incl_scan(in && !g ? len : 0, lane);
+            const long long sp = wave_incl_scan(g ? pairs : 0, lane), bp = wave_incl_scan(in && !g ? pairs : 0, lane);
+            v[2] = sl - (g ? len : 0); v[3] = bl - (in && !g ? len : 0); v[4] = sp - (g ? pairs : 0); v[5] = bp - (in && !g ? pairs : 0);
+            if (lane == 63) { s_wave[wave][2] = sl; s_wave[wave][3] = bl; s_wave[wave][4] = sp; s_wave[wave][5] = bp; }
+        }
+        if (lane == 0) { s_wave[wave][0] = __popcll(m); s_wave[wave][1] = __popcll(~m & vmask); }
+        __syncthreads();
+        long long before[6] = {run[0], run[1], run[2], run[3], run[4], run[5]};
+        for (int w = 0; w < wave; ++w) for (int k = 0; k < 6; ++k) before[k] += s_wave[w][k];
+        if (in) {
+            const long long rank = g ? before[0] + v[0] : before[1] + v[1];
+            perm[b + (g ? rank : nGood + rank)] = b + i;
+            if (tables) {
+                const long long at = offBase + (g ? rank : nGood + 1 + rank);
+                t_off[at] = g ? before[2] + v[2] : before[3] + v[3];
+                t_cigoff[at] = (int32_t)(g ? before[4] + v[4] : before[5] + v[5]);
+            }
+        }
+        for (int w = 0; w < SPLIT_WAVES; ++w) for (int k = 0; k < 6; ++k) run[k] += s_wave[w][k];
+        __syncthreads();                                              // (s_wave is rewritten by the next tile)
+    }
+    if (tables && tid == 0) {                                         // the closing entries: each buffer's bytes and pairs
+        t_off[offBase + nGood] = run[2]; t_cigoff[offBase + nGood] = (int32_t)run[4];
+        t_off[offBase + n + 1] = run[3]; t_cigoff[offBase + n + 1] = (int32_t)run[5];
+    }
+}
+
+// One wave per place of the split: lane 0 the read's scalars, the lanes its bases, qualities and CIGAR pairs.
+__global__ void __launch_bounds__(256)
+k_read_gather(int n_reads, int n_streams, const int32_t* __restrict__ stream_begin, plat_readqc_batch q, const uint8_t* __restrict__ seq,
+              const int32_t* __restrict__ end, const int32_t* __restrict__ perm, const int32_t* __restrict__ counts, plat_read_buffers_tables t)
+{
+    const int place = (int)((blockIdx.x * (long long)blockDim.x + threadIdx.x) >> 6), lane = threadIdx.x & 63;
+    if (place >= n_reads) return;
+    const int src = perm[place];
+    if (src < 0 || src >= n_reads) return;
+    const int s = q.stream_of[src];
+    if (s < 0 || s >= n_streams) return;
+    const int b = stream_begin[s], n = stream_begin[s + 1] - b, nGood = counts[10 * s], k = place - b;
+    if (nGood < 0 || nGood > n || k < 0 || k >= n || src < b || src >= b + n) return;        // (a stream_of that does not match stream_begin)
+    const bool g = k < nGood;
+    const long long offBase = (long long)b + 2ll * s;
+    const long long at = offBase + (g ? k : k + 1);
+    const long long byte = q.read_off[b] + (g ? 0 : t.off[offBase + nGood]) + t.off[at];
+    const long long pair = (long long)q.cig_off[b] + (g ? 0 : t.cig_off[offBase + nGood]) + t.cig_off[at];
+    const long long from = q.read_off[src], len = q.read_off[src + 1] - from;
+    const int c0 = q.cig_off[src], nc = q.cig_off[src + 1] - c0;
+    if (byte < 0 || byte + len > q.read_off[n_reads] || pair < 0 || pair + nc > q.cig_off[n_reads]) return;
+    for (long long j = lane; j < len; j += 64) { t.seq[byte + j] = seq[from + j]; t.qual[byte + j] = q.read_qual[from + j]; }
+    for (int j = lane; j < 2 * nc; j += 64) t.cigar[2 * pair + j] = q.cigar[2ll * c0 + j];
+    if (lane == 0) {
+        t.pos[place] = q.read_pos[src]; t.end[place] = end[src]; t.mapq[place] = q.read_mapq[src];
+        t.flags[place] = q.read_flags[src]; t.mate_pos[place] = q.mate_pos[src];
+    }
+}
+}  // namespace plat
+
+PLAT_EXPORT int plat_read_buffers_batch(plat_ctx* ctx, const plat_read_buffers_in* in, const plat_readqc_options* options, int32_t* out_ok,
+                                        int32_t* out_reason, int32_t* out_perm, int32_t* out_counts, const plat_read_buffers_tables* tab, void* stream)
+{
+    if (!ctx || !in || !options || in->n_streams < 0 || in->qc.n_reads < 0) return PLAT_ERR_INVALID;
+    const plat_readqc_batch& q = in->qc;
+    if (in->n_streams == 0) return q.n_reads == 0 ? PLAT_OK : PLAT_ERR_INVALID;
+    if (!in->stream_begin || !out_ok || !out_reason || !out_perm || !out_counts || (q.n_reads > 0 && !q.read_pos)) return PLAT_ERR_INVALID;
+    const bool tables = tab && tab->seq;
+    if (tables && (!in->read_seq || !in->read_end || !tab->off || !tab->cig_off || !tab->qual || !tab->cigar || !tab->pos || !tab->end ||
+                   !tab->mapq || !tab->flags || !tab->mate_pos))
+        return PLAT_ERR_INVALID;
+    PLAT_HIP(ctx, hipSetDevice(ctx->device));
+    const hipStream_t st = (hipStream_t)stream;
+    if (q.n_reads > 0) {
+        const int rc = plat_read_qc_batch(ctx, &q, options, out_ok, out_reason, stream);
+        if (rc != PLAT_OK) return rc;
+    }
+    { PLAT_KT_BEGIN(ctx, PLAT_KT_OTHER, st); hipLaunchKernelGGL(plat::k_read_split, dim3((unsigned)in->n_streams), dim3(plat::SPLIT_THREADS), 0, st, q.n_reads, in->stream_begin,
+                       out_ok, out_reason, q.read_pos, tables ? q.read_off : nullptr, tables ? q.cig_off : nullptr, out_perm, out_counts,
+                       tables ? tab->off : nullptr, tables ? tab->cig_off : nullptr); PLAT_KT_END(ctx, PLAT_KT_OTHER, st); }
+    if (tables && q.n_reads > 0) {
+        const unsigned blocks = (unsigned)(((long long)q.n_reads + 3) / 4);
+        { PLAT_KT_BEGIN(ctx, PLAT_KT_OTHER, st); hipLaunchKernelGGL(plat::k_read_gather, dim3(blocks), dim3(256), 0, st, q.n_reads, in->n_streams, in->stream_begin, q,
+                           in->read_seq, in->read_end, out_perm, out_counts, *tab); PLAT_KT_END(ctx, PLAT_KT_OTHER, st); }
+    }
+    PLAT_HIP(ctx, hipGetLastError());
+    return PLAT_OK;
+}

@@ -439,6 +439,72 @@ class Engine:
             a = e
         return out
 
+    def read_buffers(self, streams, min_good_qual_bases=20, min_map_qual=20, min_base_qual=20, trim_overlapping=1, trim_adapter=1,
+                     trim_read_flank=0, trim_soft_clipped=1, enabled=(1, 1, 1, 1)):
+        """plat_read_buffers_batch: checkAndTrimRead over whole streams (as read_qc), then every stream's split into `reads` / `badReads`
+        and the two buffers gathered.  `streams`: list of lists of dicts {seq, qual, pos, end, mapq, flag, chromID, mateChromID, insertSize,
+        matePos, cigar} in fetch order.  Returns per stream a dict: ok, reason, flags (after QC, fetch order), perm (indices into the stream:
+        accepted then rejected), n_good, unsorted, hist [8], and reads / bad: the gathered buffers (seq, qual, off, pos, end, mapq, flags,
+        mate_pos, cigar [n, 2], cig_off)."""
+        torch = _torch()
+        reads = [r for st in streams for r in st]
+        n, ns = len(reads), len(streams)
+
+        def dev(a, dt):
+            return torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(self.device)
+        lens = [len(r["qual"]) for r in reads]
+        off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+        ncig = [len(r["cigar"]) for r in reads]
+        coff = np.concatenate([[0], np.cumsum(ncig)]).astype(np.int32)
+        raw = lambda x: x.encode() if isinstance(x, str) else bytes(x)
+        cat = lambda key: np.concatenate([np.frombuffer(raw(r[key]), dtype=np.uint8) for r in reads]) if n else np.zeros(0, np.uint8)
+        nb, npairs = int(off[-1]), int(coff[-1])
+        qual = dev(pad_blob(cat("qual")), np.uint8)
+        seq = dev(pad_blob(cat("seq")), np.uint8)
+        sbeg = np.concatenate([[0], np.cumsum([len(st) for st in streams])]).astype(np.int32)
+        t = dict(off=dev(off, np.int64), pos=dev([r["pos"] for r in reads] + [0], np.int32), end=dev([r["end"] for r in reads] + [0], np.int32),
+                 mapq=dev([r["mapq"] for r in reads] + [0], np.uint8), flags=dev([r["flag"] for r in reads] + [0], np.int32),
+                 cid=dev([r["chromID"] for r in reads] + [0], np.int16), mcid=dev([r["mateChromID"] for r in reads] + [0], np.int16),
+                 ins=dev([r["insertSize"] for r in reads] + [0], np.int32), mpos=dev([r["matePos"] for r in reads] + [0], np.int32),
+                 cig=dev([x for r in reads for c in r["cigar"] for x in c] + [0, 0], np.int16), coff=dev(coff, np.int32),
+                 sof=dev(np.repeat(np.arange(ns), [len(st) for st in streams]).tolist() + [0], np.int32), sbeg=dev(sbeg, np.int32))
+        b = _lib.ReadBuffersIn()
+        q = b.qc
+        q.n_reads = n
+        q.read_qual, q.read_off, q.read_pos, q.read_mapq, q.read_flags = qual.data_ptr(), t["off"].data_ptr(), t["pos"].data_ptr(), t["mapq"].data_ptr(), t["flags"].data_ptr()
+        q.chrom_id, q.mate_chrom_id, q.insert_size, q.mate_pos = t["cid"].data_ptr(), t["mcid"].data_ptr(), t["ins"].data_ptr(), t["mpos"].data_ptr()
+        q.cigar, q.cig_off, q.stream_of = t["cig"].data_ptr(), t["coff"].data_ptr(), t["sof"].data_ptr()
+        b.n_streams, b.stream_begin, b.read_seq, b.read_end = ns, t["sbeg"].data_ptr(), seq.data_ptr(), t["end"].data_ptr()
+        o = _lib.ReadQCOptions(min_good_qual_bases, min_map_qual, min_base_qual, trim_overlapping, trim_adapter, trim_read_flank,
+                               trim_soft_clipped, *[int(x) for x in enabled])
+        e = lambda k, dt: torch.zeros(max(k, 1), dtype=dt, device=self.device)
+        ok, why, perm, counts = e(n, torch.int32), e(n, torch.int32), e(n, torch.int32), e(10 * ns, torch.int32)
+        g = dict(off=e(n + 2 * ns, torch.int64), cig_off=e(n + 2 * ns, torch.int32), seq=e(nb + _lib.PLAT_BLOB_PAD, torch.uint8),
+                 qual=e(nb + _lib.PLAT_BLOB_PAD, torch.uint8), cigar=e(2 * npairs, torch.int16), pos=e(n, torch.int32), end=e(n, torch.int32),
+                 mapq=e(n, torch.uint8), flags=e(n, torch.int32), mate_pos=e(n, torch.int32))
+        tab = _lib.ReadBuffersTables(*[g[k].data_ptr() for k, _ in _lib.ReadBuffersTables._fields_])
+        _lib.check(self.lib.plat_read_buffers_batch(self.ctx, C.byref(b), C.byref(o), ok.data_ptr(), why.data_ptr(), perm.data_ptr(), counts.data_ptr(),
+                                                    C.byref(tab), self._stream()), "plat_read_buffers_batch")
+        self._sync()
+        h = {k: v.cpu().numpy() for k, v in g.items()}
+        ok_h, why_h, perm_h, cnt_h, fl_h = ok.cpu().numpy(), why.cpu().numpy(), perm.cpu().numpy(), counts.cpu().numpy(), t["flags"].cpu().numpy()
+        out = []
+        for s in range(ns):
+            a, z = int(sbeg[s]), int(sbeg[s + 1])
+            ng = int(cnt_h[10 * s])
+            res = dict(ok=ok_h[a:z], reason=why_h[a:z], flags=fl_h[a:z], perm=perm_h[a:z] - a, n_good=ng, unsorted=int(cnt_h[10 * s + 1]),
+                       hist=cnt_h[10 * s + 2:10 * s + 10])
+            byte, pair = int(off[a]), int(coff[a])
+            for name, p0, p1, ob in (("reads", 0, ng, a + 2 * s), ("bad", ng, z - a, a + 2 * s + ng + 1)):
+                m = p1 - p0
+                to, tc = h["off"][ob:ob + m + 1], h["cig_off"][ob:ob + m + 1]
+                res[name] = dict(off=to, cig_off=tc, seq=h["seq"][byte:byte + to[-1]], qual=h["qual"][byte:byte + to[-1]],
+                                 cigar=h["cigar"][2 * pair:2 * (pair + tc[-1])].reshape(-1, 2), pos=h["pos"][a + p0:a + p1], end=h["end"][a + p0:a + p1],
+                                 mapq=h["mapq"][a + p0:a + p1], flags=h["flags"][a + p0:a + p1], mate_pos=h["mate_pos"][a + p0:a + p1])
+                byte += int(to[-1]); pair += int(tc[-1])
+            out.append(res)
+        return out
+
     # ---- SURVEY 8(f) rank 3: read statistics of the VCF INFO field --------------------------------------------
     def variant_read_stats(self, windows, bad_reads_window=11, exact=0):
         """vcfINFO's per-read loop for a list of windows.  A window: dict {variants: [dict(pos, removed, added, bam_min,

@@ -1,11 +1,13 @@
-"""ctypes binding of libplat_caller.so (include/platypus_caller.h): the native region loop.
+"""ctypes binding of libplat_caller.so (include/platypus_caller.h, include/platypus_caller_fetched.h): the native region loop.
 
     reads of a region in host memory (structure-of-arrays)  ->  VCF record lines
 
 `ReadTable` / `RegionReads` are the array form of ReadArray / bamReadBuffer (cwindow.pyx:92-236,485-513);
 `NativeCaller.call_regions` is callVariantsInRegion (variantcaller.pyx:535-615) for a list of regions and writes the
 text platypus_amd.caller.callVariantsInRegions writes (tests/test_native_caller_*.py compare the two).  The library
-is host code on top of libplat_mi355x.so; like the rest of the package it has no CPU fallback."""
+is host code on top of libplat_mi355x.so; like the rest of the package it has no CPU fallback.
+`FetchedRegion` / `NativeCaller.call_fetched_regions` take the reads as a BAM fetch returns them instead (the loader's
+addReadToBuffer QC and split run on the device, cwindow.pyx:560-595)."""
 import ctypes as C
 import os
 import subprocess
@@ -89,6 +91,36 @@ class CallerStats(C.Structure):
         d["seconds_stage"] = dict(zip(self.STAGES, list(self.seconds_stage)))
         d["kernel_ms"], d["kernel_launches"] = list(self.kernel_ms), list(self.kernel_launches)
         return d
+
+
+class _FetchedReads(C.Structure):
+    _fields_ = [("fetched", _ReadTable), ("broken_mates", _ReadTable), ("chrom_id", C.c_void_p), ("mate_chrom_id", C.c_void_p),
+                ("insert_size", C.c_void_p)]
+
+
+class _FetchedRegion(C.Structure):
+    _fields_ = [("chrom", C.c_char_p), ("start", C.c_int32), ("end", C.c_int32), ("contig_seq", C.c_void_p),
+                ("contig_len", C.c_int64), ("samples", C.POINTER(_FetchedReads)), ("dev_contig_seq", C.c_void_p)]
+
+
+_QC_FIELDS = ("minGoodQualBases", "minMapQual", "minBaseQual", "trimOverlapping", "trimAdapter", "trimReadFlank", "trimSoftClipped",
+              "filterDuplicates", "filterReadsWithUnmappedMates", "filterReadsWithDistantMates", "filterReadPairsWithSmallInserts")
+
+
+class CallerQCOptions(C.Structure):
+    """plat_caller_qc_options: the options bamReadBuffer's constructor reads (cwindow.pyx:490-526)."""
+    _fields_ = [(k, C.c_int32) for k in _QC_FIELDS]
+
+    @classmethod
+    def from_options(cls, options):
+        o = cls()
+        for k in _QC_FIELDS:
+            setattr(o, k, int(getattr(options, k)))
+        return o
+
+
+class _FetchedRegionInfo(C.Structure):
+    _fields_ = [("loaded", C.c_int32), ("sample_counts", C.c_void_p)]
 
 
 class ReadTable:
@@ -185,6 +217,41 @@ class RegionReads:
         a.samples = ss
 
 
+class FetchedRegion:
+    """One region as loadBAMData has it in hand (platypusutils.pyx:449-686): per sample the reads a `fetch` returned, in fetch order,
+    with chromID / mateChromID / insertSize per read, and the broken mates (sorted by mate position)."""
+
+    def __init__(self, chrom, start, end, contig_seq, samples):
+        self.chrom, self.start, self.end = chrom, int(start), int(end)
+        self.contig = np.ascontiguousarray(np.frombuffer(contig_seq, dtype=np.uint8) if isinstance(contig_seq, (bytes, bytearray)) else contig_seq,
+                                           dtype=np.uint8)
+        self.samples = samples                                  # [(fetched ReadTable, broken ReadTable, chrom_id, mate_chrom_id, insert_size)]
+        self._c = None
+
+    @classmethod
+    def from_reads(cls, chrom, start, end, fasta, samples):
+        """samples: per sample (fetched, brokenMates), lists of hostapi.AlignedRead -- fetched in fetch order; brokenMates are sorted by
+        mate position here, as bamReadBuffer.sortBrokenMates does (cwindow.pyx:759-766)."""
+        out = []
+        for fetched, broken in samples:
+            c = lambda f, dt: np.ascontiguousarray([f(r) for r in fetched], dtype=dt)
+            out.append((ReadTable.from_reads(fetched), ReadTable.from_reads(sorted(broken, key=lambda r: r.matePos)),
+                        c(lambda r: r.chromID, np.int16), c(lambda r: r.mateChromID, np.int16), c(lambda r: r.insertSize, np.int32)))
+        return cls(chrom, start, end, fasta._seq[chrom], out)
+
+    def fill(self, a, n_samples):
+        """Write this region into the plat_fetched_region `a` (the arrays stay owned by, and alive with, this object)."""
+        assert len(self.samples) == n_samples
+        if self._c is None:
+            ss = (_FetchedReads * len(self.samples))()
+            for i, (f, b, cid, mcid, ins) in enumerate(self.samples):
+                ss[i].fetched, ss[i].broken_mates = f.struct(), b.struct()
+                ss[i].chrom_id, ss[i].mate_chrom_id, ss[i].insert_size = cid.ctypes.data, mcid.ctypes.data, ins.ctypes.data
+            self._c = (self.chrom.encode(), self.contig.ctypes.data, len(self.contig), ss)
+        a.chrom, a.contig_seq, a.contig_len, a.samples = self._c
+        a.start, a.end = self.start, self.end
+
+
 def region_from_arrays(reg, pin=False, packed=False):
     """RegionReads of a synth.config4_region_arrays() region (every read in `reads`; no badReads / brokenMates)."""
     empty = ReadTable([], [], [0], [], [], [], [], [], [], [0])
@@ -261,6 +328,11 @@ def _bind(lib):
                                       C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(CallerStats)]
     lib.plat_call_regions_stream.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_char_p), C.POINTER(CallerOptions), C.c_void_p, C.c_void_p,
                                              C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(CallerStats)]
+    lib.plat_caller_default_qc_options.argtypes = [C.POINTER(CallerQCOptions)]
+    lib.plat_caller_default_qc_options.restype = None
+    lib.plat_call_fetched_regions.argtypes = [C.c_void_p, C.POINTER(_FetchedRegion), C.c_int, C.c_int, C.POINTER(C.c_char_p), C.POINTER(CallerOptions),
+                                              C.POINTER(CallerQCOptions), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(_FetchedRegionInfo),
+                                              C.POINTER(CallerStats)]
     lib.plat_merge_record_texts.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     lib.plat_caller_region_text_lengths.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     lib.plat_merge_region_blocks.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
@@ -472,6 +544,36 @@ class NativeCaller:
             self.lib.plat_caller_free(text)
         options.rlen = int(o.rlen)
         self.stats = st.as_dict()
+        return out
+
+    def call_fetched_regions(self, regions, sample_names, options):
+        """regions: list of FetchedRegion.  The loader's work (addReadToBuffer's QC and split, isSorted, maxReads) on the device, then the
+        region loop as call_regions runs it; the QC options come from the same `options`.  Returns the record lines (str); options.rlen is
+        updated as the reference updates it.  self.loaded[k] (0: region k reached maxReads and was not called) and self.read_counts[k]
+        (int32 [n_samples, 10]: n_good, n_bad, the 8 reason counts -- filteredReadCountsByType slots 0-6 and secondary alignments) describe
+        the last call."""
+        n, nS = len(regions), len(sample_names)
+        arr = (_FetchedRegion * max(n, 1))()
+        for k, r in enumerate(regions):
+            r.fill(arr[k], nS)
+        names = (C.c_char_p * nS)(*[s.encode() for s in sample_names])
+        o, q = CallerOptions.from_options(options), CallerQCOptions.from_options(options)
+        counts = np.zeros((max(n, 1), nS, 10), dtype=np.int32)
+        info = (_FetchedRegionInfo * max(n, 1))()
+        for k in range(n):
+            info[k].sample_counts = counts[k].ctypes.data
+        text, length, st = C.c_void_p(), C.c_size_t(), CallerStats()
+        rc = self.lib.plat_call_fetched_regions(self.h, arr, n, nS, names, C.byref(o), C.byref(q), C.byref(text), C.byref(length), info, C.byref(st))
+        if rc != 0:
+            raise _lib.PlatypusDeviceError(rc, (self.lib.plat_caller_last_error(self.h) or b"").decode(), "plat_call_fetched_regions")
+        try:
+            out = C.string_at(text, length.value).decode("ascii")
+        finally:
+            self.lib.plat_caller_free(text)
+        options.rlen = int(o.rlen)
+        self.stats = st.as_dict()
+        self.loaded = [int(info[k].loaded) for k in range(n)]
+        self.read_counts = counts[:n]
         return out
 
     def region_text_lengths(self, n_regions):

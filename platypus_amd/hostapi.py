@@ -201,6 +201,28 @@ class bamReadBuffer:
         self.reads, self.badReads, self.brokenMates = ReadArray(reads), ReadArray(badReads), ReadArray(brokenMates, byMatePos=True)
         self.sample = sample
 
+    @classmethod
+    def fromFetchedReads(cls, reads, brokenMates=(), options=None, sample="sample", readsBefore=0):
+        """The buffer loadBAMData builds from one sample's fetch (platypusutils.pyx:505-541 through addReadToBuffer, cwindow.pyx:560-595):
+        `reads` in fetch order go through checkAndTrimRead (checkAndTrimReads: qualities and flags are changed IN PLACE, as the reference
+        changes its cAlignedReads) and then to `reads` or `badReads` in that order; `brokenMates` are kept as fetched.  Returns None when the
+        fetch reaches options.maxReads -- counted, as loadBAMData counts it, over every sample of the region: `readsBefore` = the reads of the
+        samples before this one.  Reads that are not sorted by position (the reference's isSorted = False, then an unstable qsort) are
+        refused with ValueError.  The native region loop does the same on the device: fastcaller.NativeCaller.call_fetched_regions."""
+        options = options if options is not None else default_options()
+        reads = list(reads)
+        if reads and readsBefore + len(reads) >= int(options.maxReads):
+            return None
+        for a, b in zip(reads, reads[1:]):
+            if b.pos < a.pos:
+                raise ValueError("fetched reads are not sorted by position (read at %d follows one at %d)" % (b.pos, a.pos))
+        enabled = (options.filterReadsWithUnmappedMates, options.filterReadsWithDistantMates, options.filterReadPairsWithSmallInserts,
+                   options.filterDuplicates)
+        ok, counts = checkAndTrimReads(reads, options, enabled) if reads else ([], [0 if (k < 2 or k == 6 or enabled[k - 2]) else -1 for k in range(7)])
+        buf = cls([r for r, g in zip(reads, ok) if g], [r for r, g in zip(reads, ok) if not g], brokenMates, sample=sample)
+        buf.filteredReadCountsByType = counts
+        return buf
+
     def countReadsCoveringRegion(self, start, end):                               # cwindow.pyx:649-653
         return self.reads.countReadsCoveringRegion(start, end)
 

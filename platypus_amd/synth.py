@@ -465,3 +465,51 @@ def config4_region_arrays(index, seed=4004, region_len=100000, n_samples=1, dept
                             pos=pos[order], end=endp[order], mapq=np.full(n_reads, 60, dtype=np.uint8), flags=flags[order],
                             mate_pos=np.full(n_reads, -1, dtype=np.int32), cigar=cigar.reshape(-1), cig_off=cig_off))
     return dict(chrom="r%d" % index, start=start, end=end, ref=ref, variants=out_vars, samples=samples, truth=truth)
+
+
+def config4_fetched_region(index, seed=4711, region_len=100000, n_samples=1, **kw):
+    """A config-4 region (config4_region_arrays) as a BAM fetch would return it: per sample hostapi.AlignedRead objects in fetch order,
+    paired-end flags, and the trouble a real fetch has -- duplicates (flagged, and positional twins), low mapping quality, unmapped reads,
+    unmapped and distant mates, improper pairs, secondary alignments, small inserts and overlapping mates, low-quality tails, soft clips --
+    for the loader's QC (checkAndTrimRead, cwindow.pyx:332-481).  Returns (region dict of config4_region_arrays, [reads per sample])."""
+    from .fastcaller import aligned_reads_from_arrays
+    reg = config4_region_arrays(index, region_len=region_len, n_samples=n_samples, **kw)
+    rng = np.random.default_rng([seed, index])
+    samples = []
+    for s in reg["samples"]:
+        reads = aligned_reads_from_arrays(s)
+        for r in reads:
+            r.bitFlag = 1 | 2 | (16 if rng.random() < 0.5 else 32) | (64 if rng.random() < 0.5 else 128)
+            r.insertSize = int(rng.integers(300, 500)) * (-1 if r.bitFlag & 16 else 1)
+            r.chromID = r.mateChromID = 0
+            t = rng.random()
+            if t < 0.03:
+                r.bitFlag |= 1024
+            elif t < 0.05:
+                r.mapq = int(rng.choice([0, 5, 19]))
+            elif t < 0.06:
+                r.bitFlag |= 4
+            elif t < 0.07:
+                r.bitFlag |= 8
+            elif t < 0.08:
+                r.mateChromID = 3
+            elif t < 0.09:
+                r.bitFlag &= ~2
+            elif t < 0.10:
+                r.bitFlag |= 256
+            elif t < 0.12:
+                r.insertSize = int(rng.integers(20, 140)) * (-1 if r.bitFlag & 16 else 1)
+            elif t < 0.15:
+                r.insertSize = int(rng.integers(160, 290))
+            if rng.random() < 0.2:
+                k = int(rng.integers(3, 40))
+                r.qual = r.qual[:-k] + bytes([int(rng.integers(0, 5))]) * k
+            if rng.random() < 0.05 and len(r.cigarOps) == 1 and r.cigarOps[0][0] == 0:
+                k = int(rng.integers(2, 12))
+                r.cigarOps = [(4, k), (0, r.rlen - k)]
+        for a, b in zip(reads, reads[1:]):                     # positional duplicates right behind their twin
+            if rng.random() < 0.01:
+                b.pos, b.end, b.matePos = a.pos, a.pos + b.rlen, a.matePos
+        reads.sort(key=lambda r: r.pos)
+        samples.append(reads)
+    return reg, samples
