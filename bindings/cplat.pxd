@@ -341,6 +341,21 @@ cdef extern from "platypus_mi355x.h":
     int plat_read_buffers_batch(plat_ctx* ctx, const plat_read_buffers_in* inp, const plat_readqc_options* options, int32_t* out_ok,
                                 int32_t* out_reason, int32_t* out_perm, int32_t* out_counts, const plat_read_buffers_tables* tab,
                                 void* stream) nogil
+    # the same for a PLAT_READS_PACKED table (one byte per base + exceptions): QC and trimming on the packed bytes, no quality array
+    ctypedef struct plat_read_buffers_packed_in:
+        plat_readqc_batch qc
+        int32_t n_streams
+        int32_t _pad
+        const int32_t* stream_begin
+        uint8_t* read_packed
+        const int32_t* read_end
+        int64_t n_exc
+        const int64_t* exc_index
+        const uint8_t* exc_base
+        uint8_t* exc_qual
+    int plat_read_buffers_packed_batch(plat_ctx* ctx, const plat_read_buffers_packed_in* inp, const plat_readqc_options* options, int32_t* out_ok,
+                                       int32_t* out_reason, int32_t* out_perm, int32_t* out_counts, const plat_read_buffers_tables* tab,
+                                       void* stream) nogil
 
     # ---- window read slices out of a resident read table (cwindow.pyx:208-264,655-689)
     # the read table of a loader that wrote one byte per base (2-bit base | quality << 2) expanded to ASCII on the device

@@ -13,13 +13,22 @@
  * split (a permutation, per-read flags after QC, per-stream counts), not bases or qualities; it keeps host copies of the split tables'
  * per-read arrays and bases for its own stages, whose `qual` is NULL (no host stage reads qualities).
  *
+ * The fetched tables may be PLAT_READS_ASCII or PLAT_READS_PACKED (include/platypus_caller.h), one encoding for every fetched table of
+ * a call (empty tables aside; a call that mixes them is refused, PLAT_ERR_UNSUPPORTED with a message naming the table).  Packed tables
+ * are checked and trimmed on their packed bytes and exceptions (plat_read_buffers_packed_batch): no quality array is built or uploaded,
+ * and the split tables are PLAT_READS_PACKED as well -- the gathered, trimmed bytes on the device, the exceptions re-indexed into each
+ * table with their trimmed qualities (the host reads those back).  The host copy of a split table's packed bytes keeps the quality
+ * bits it was handed (no host stage reads them).  The records are those of the same call on ASCII tables.  Broken-mate tables may each
+ * be of either encoding; they pass through unchanged.  plat_caller_stats.input_bytes counts the bases and qualities that cross the
+ * link: 2 bytes per base of an ASCII table, 1 per base + 10 per exception of a packed one.
+ *
  * Differences from the reference, by design:
  *  - a stream whose reads are not sorted by position (isSorted = False in the reference) is refused (PLAT_ERR_BAD_INPUT, message in
  *    plat_caller_last_error): a BAM fetch is coordinate-sorted, and the reference's sortReads is a qsort whose order of equal keys is
  *    not reproduced here;
- *  - PLAT_READS_PACKED fetched tables are refused (PLAT_ERR_UNSUPPORTED): trimming would have to rewrite packed bytes and exceptions;
  *  - the fetched tables of the whole call are resident on the device at once (a caller with a very long region list calls in parts).
- * A library linked against a device library without plat_read_buffers_batch returns PLAT_ERR_UNSUPPORTED.
+ * A library linked against a device library without plat_read_buffers_batch (packed tables: plat_read_buffers_packed_batch) returns
+ * PLAT_ERR_UNSUPPORTED.
  */
 #ifndef PLATYPUS_CALLER_FETCHED_H
 #define PLATYPUS_CALLER_FETCHED_H
@@ -30,9 +39,10 @@
 extern "C" {
 #endif
 
-/* One sample of one region: the reads of the fetch, in fetch order (seq = ASCII bases, qual = raw phred; the table's dev_* fields and
- * hints are ignored), and per fetched read the three fields checkAndTrimRead reads that plat_read_table has no room for.  broken_mates:
- * as plat_sample_reads.broken_mates (sorted by mate_pos), passed through unchanged. */
+/* One sample of one region: the reads of the fetch, in fetch order (PLAT_READS_ASCII: seq = ASCII bases, qual = raw phred;
+ * PLAT_READS_PACKED: seq = packed bytes + exceptions; the table's dev_* fields and hints are ignored), and per fetched read the three
+ * fields checkAndTrimRead reads that plat_read_table has no room for.  broken_mates: as plat_sample_reads.broken_mates (sorted by
+ * mate_pos), passed through unchanged. */
 typedef struct plat_fetched_reads {
     plat_read_table fetched;
     plat_read_table broken_mates;

@@ -544,6 +544,29 @@ int plat_read_buffers_batch(plat_ctx* ctx, const plat_read_buffers_in* in, const
                             int32_t* out_reason, int32_t* out_perm, int32_t* out_counts, const plat_read_buffers_tables* tab /* may be NULL */,
                             void* stream);
 
+/* The same for a table in PLAT_READS_PACKED form (include/platypus_caller.h): one byte per base, bits 0..1 the base and bits 2..7 the
+ * quality, plus exceptions (bases other than A/C/G/T, qualities above 63).  No quality array is read or written: qc.read_qual is
+ * unused.  The quality of base i is exc_qual[k] when exc_index[k] == i (read as int8_t, as plat_read_qc_batch reads read_qual: a
+ * quality >= 128 counts as below min_base_qual), else read_packed[i] >> 2.  checkAndTrimRead's verdicts and trimming are those of
+ * plat_read_buffers_batch; a trimmed base keeps its base bits and gets quality bits 0, a trimmed exception exc_qual 0 (both in place).
+ * Outputs as plat_read_buffers_batch, with tab.qual unused: tab.seq receives the trimmed packed bytes at the same places.  The
+ * exceptions are not gathered: a gathered read's exceptions are those of its input bytes (exc_index, ascending, into read_packed). */
+typedef struct plat_read_buffers_packed_in {
+    plat_readqc_batch qc;            /* the table; qc.read_qual unused (NULL); qc.read_off / qc.cig_off start at 0 */
+    int32_t n_streams, _pad;
+    const int32_t* stream_begin;     /* [n_streams+1], as plat_read_buffers_in */
+    uint8_t* read_packed;            /* [qc.read_off[n_reads] + PLAT_BLOB_PAD] packed bytes, in/out (trimmed in place) */
+    const int32_t* read_end;         /* for the gathered tables (NULL without them) */
+    int64_t n_exc;
+    const int64_t* exc_index;        /* [n_exc] ascending byte indices into read_packed; the exc_* may be NULL when n_exc == 0 */
+    const uint8_t* exc_base;         /* [n_exc] the real letters (not read by the QC) */
+    uint8_t* exc_qual;               /* [n_exc] the real qualities, in/out (trimmed in place) */
+} plat_read_buffers_packed_in;
+
+int plat_read_buffers_packed_batch(plat_ctx* ctx, const plat_read_buffers_packed_in* in, const plat_readqc_options* options, int32_t* out_ok,
+                                   int32_t* out_reason, int32_t* out_perm, int32_t* out_counts,
+                                   const plat_read_buffers_tables* tab /* may be NULL; tab.qual unused */, void* stream);
+
 /* ---- read statistics of the VCF INFO field ---------------------------------------
  * Replaces the per-variant loop over a window's reads in  cdef dict vcfINFO(...)   vcfutils.pyx:1300-1390
  * (readOverlapsVariant :901-913, readQualIsGoodVariantPosition :917-943, variantSupportedByRead :961-1072).

@@ -92,6 +92,11 @@ class ReadBuffersIn(C.Structure):
                 ("read_end", C.c_void_p)]
 
 
+class ReadBuffersPackedIn(C.Structure):
+    _fields_ = [("qc", ReadQCBatch), ("n_streams", C.c_int32), ("_pad", C.c_int32), ("stream_begin", C.c_void_p), ("read_packed", C.c_void_p),
+                ("read_end", C.c_void_p), ("n_exc", C.c_int64), ("exc_index", C.c_void_p), ("exc_base", C.c_void_p), ("exc_qual", C.c_void_p)]
+
+
 class ReadBuffersTables(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("off", "cig_off", "seq", "qual", "cigar", "pos", "end", "mapq", "flags", "mate_pos")]
 
@@ -162,6 +167,8 @@ SIGNATURES = {
     "plat_read_qc_batch": (C.c_int, [C.c_void_p, C.POINTER(ReadQCBatch), C.POINTER(ReadQCOptions), C.c_void_p, C.c_void_p, C.c_void_p]),
     "plat_read_buffers_batch": (C.c_int, [C.c_void_p, C.POINTER(ReadBuffersIn), C.POINTER(ReadQCOptions), C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.POINTER(ReadBuffersTables), C.c_void_p]),
+    "plat_read_buffers_packed_batch": (C.c_int, [C.c_void_p, C.POINTER(ReadBuffersPackedIn), C.POINTER(ReadQCOptions), C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.POINTER(ReadBuffersTables), C.c_void_p]),
     "plat_variant_read_stats_batch": (C.c_int, [C.c_void_p, C.POINTER(InfoStatsBatch), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
     "plat_variant_info_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -175,7 +182,7 @@ SIGNATURES = {
 
 # entry points a stand-in library built against an earlier header may lack (the CPU suite's fake device): bind() leaves them
 # unbound there; load() still requires every declared symbol of the real library
-ADDED_LATER = ("plat_read_buffers_batch",)
+ADDED_LATER = ("plat_read_buffers_batch", "plat_read_buffers_packed_batch")
 
 _lib = None
 

@@ -2,6 +2,8 @@
 // them.  In front of plat_call_regions: the loader's per-read work of loadBAMData (platypusutils.pyx:505-541) through
 // bamReadBuffer.addReadToBuffer (cwindow.pyx:560-595) -- checkAndTrimRead, reads / badReads, isSorted, maxReads -- on the device
 // (plat_read_buffers_batch), the buffers gathered there and handed to the loop as device-resident tables (plat_read_table.dev_*).
+// PLAT_READS_PACKED fetched tables go through plat_read_buffers_packed_batch instead: QC and trimming on the packed bytes and exceptions,
+// no quality array anywhere.
 // Included at the end of region_caller.cpp (it calls plat_call_regions and reads plat_caller).
 #pragma once
 #include <climits>
@@ -10,6 +12,7 @@
 // The device entry point is referenced weakly: the CPU test suite links this library against a stand-in device library that predates it
 // (the call then returns PLAT_ERR_UNSUPPORTED).
 #pragma weak plat_read_buffers_batch
+#pragma weak plat_read_buffers_packed_batch
 
 namespace plathost {
 
@@ -32,13 +35,28 @@ struct FetchedDeviceBuffers {
     ~FetchedDeviceBuffers() { for (void* p : held) plat_free(ctx, p); }
 };
 
-// one buffer (reads or badReads) of one sample as the host's stages see it: per-read arrays and bases, no qualities
+// one buffer (reads or badReads) of one sample as the host's stages see it: per-read arrays and bases, no qualities (packed: the bytes as
+// handed over -- the host's stages read their base bits only -- and the exceptions, indexed into the buffer, with the trimmed qualities)
 struct FetchedHostTable {
-    std::vector<int64_t> off;
+    std::vector<int64_t> off, excIndex;
     std::vector<int32_t> pos, end, flags, matePos, cigOff;
-    std::vector<uint8_t> mapq, seq;
+    std::vector<uint8_t> mapq, seq, excBase, excQual;
     std::vector<int16_t> cigar;
 };
+
+static const char* encodingName(int e) { return e == PLAT_READS_PACKED ? "PLAT_READS_PACKED" : "PLAT_READS_ASCII"; }
+
+// the exceptions of a packed table: ascending indices inside its bytes
+static bool exceptionsValid(const plat_read_table& t) {
+    if (t.encoding != PLAT_READS_PACKED) return true;
+    if (t.n_exceptions < 0) return false;
+    if (t.n_exceptions == 0) return true;
+    if (!t.exc_index || !t.exc_base || !t.exc_qual) return false;
+    const int64_t nb = t.n_reads ? t.off[t.n_reads] : 0;
+    for (int64_t e = 0; e < t.n_exceptions; ++e)
+        if (t.exc_index[e] < 0 || t.exc_index[e] >= nb || (e && t.exc_index[e] <= t.exc_index[e - 1])) return false;
+    return true;
+}
 
 static std::string fetchedWhere(const plat_fetched_region& r, int k, int i) {
     return "region " + std::to_string(k) + " (" + (r.chrom ? r.chrom : "?") + ":" + std::to_string(r.start) + "-" + std::to_string(r.end) +
@@ -71,8 +89,10 @@ CALLER_EXPORT int plat_call_fetched_regions(plat_caller* c, const plat_fetched_r
     const double mr = options->maxReads;
     const long long maxReads = mr >= (double)INT_MAX ? INT_MAX : (mr <= (double)INT_MIN ? INT_MIN : (long long)mr);     // (cdef int maxReads)
     std::vector<int> loaded((size_t)n_regions, 0);
-    long long nReads = 0, nBytes = 0, nPairs = 0, nBroken = 0, nBrokenBytes = 0, nBrokenPairs = 0;
+    long long nReads = 0, nBytes = 0, nPairs = 0, nBroken = 0, nBrokenBytes = 0, nBrokenPairs = 0, nExc = 0, linkBytes = 0;
     int nStreams = 0;
+    int encoding = -1;                                                   // of the call's fetched tables (one for all)
+    std::string firstOfEncoding;
     for (int k = 0; k < n_regions; ++k) {
         const plat_fetched_region& r = regions[k];
         if (!r.samples) return PLAT_ERR_INVALID;
@@ -81,16 +101,22 @@ CALLER_EXPORT int plat_call_fetched_regions(plat_caller* c, const plat_fetched_r
             const plat_read_table* tabs[2] = {&r.samples[i].fetched, &r.samples[i].broken_mates};
             for (const plat_read_table* t : tabs) {
                 if (t->n_reads < 0) return PLAT_ERR_INVALID;
-                if (t->encoding == PLAT_READS_PACKED) {
-                    c->lastError = "plat_call_fetched_regions: PLAT_READS_PACKED tables are not supported (" + fetchedWhere(r, k, i) + ")";
-                    return PLAT_ERR_UNSUPPORTED;
-                }
-                if (t->encoding != PLAT_READS_ASCII) return PLAT_ERR_INVALID;
-                if (t->n_reads && (!t->seq || !t->qual || !t->off || !t->pos || !t->end || !t->mapq || !t->flags || !t->mate_pos || !t->cig_off ||
-                                   (t->cig_off[t->n_reads] && !t->cigar) || t->off[0] != 0 || t->cig_off[0] != 0))
+                if (t->encoding != PLAT_READS_ASCII && t->encoding != PLAT_READS_PACKED) return PLAT_ERR_INVALID;
+                if (t->n_reads && (!t->seq || (t->encoding == PLAT_READS_ASCII && !t->qual) || !t->off || !t->pos || !t->end || !t->mapq ||
+                                   !t->flags || !t->mate_pos || !t->cig_off || (t->cig_off[t->n_reads] && !t->cigar) || t->off[0] != 0 || t->cig_off[0] != 0))
                     return PLAT_ERR_INVALID;
+                if (!exceptionsValid(*t)) return PLAT_ERR_INVALID;
             }
             const plat_fetched_reads& f = r.samples[i];
+            if (f.fetched.n_reads) {                                     // (an empty table has no bytes to encode)
+                if (encoding < 0) { encoding = f.fetched.encoding; firstOfEncoding = fetchedWhere(r, k, i); }
+                else if (f.fetched.encoding != encoding) {
+                    c->lastError = std::string("plat_call_fetched_regions: the fetched tables of one call share one encoding: the fetched reads of ") +
+                                   fetchedWhere(r, k, i) + " are " + encodingName(f.fetched.encoding) + ", those of " + firstOfEncoding + " " +
+                                   encodingName(encoding);
+                    return PLAT_ERR_UNSUPPORTED;
+                }
+            }
             if (f.fetched.n_reads && (!f.chrom_id || !f.mate_chrom_id || !f.insert_size)) return PLAT_ERR_INVALID;
             total += f.fetched.n_reads;
         }
@@ -101,8 +127,20 @@ CALLER_EXPORT int plat_call_fetched_regions(plat_caller* c, const plat_fetched_r
             const plat_read_table& m = r.samples[i].broken_mates;
             nReads += t.n_reads; nBytes += t.n_reads ? t.off[t.n_reads] : 0; nPairs += t.n_reads ? t.cig_off[t.n_reads] : 0;
             nBroken += m.n_reads; nBrokenBytes += m.n_reads ? m.off[m.n_reads] : 0; nBrokenPairs += m.n_reads ? m.cig_off[m.n_reads] : 0;
+            // the bases and qualities that cross the link: 2 bytes per base, or (packed) 1 + 10 per exception (index, base, quality)
+            for (const plat_read_table* x : {&t, &m}) {
+                const long long nb = x->n_reads ? x->off[x->n_reads] : 0;
+                const long long ne = x->n_reads && x->encoding == PLAT_READS_PACKED ? x->n_exceptions : 0;
+                linkBytes += x->encoding == PLAT_READS_PACKED ? nb + 10 * ne : 2 * nb;
+            }
+            if (t.n_reads && t.encoding == PLAT_READS_PACKED) nExc += t.n_exceptions;
             ++nStreams;
         }
+    }
+    const bool packed = encoding == PLAT_READS_PACKED;
+    if (packed && !plat_read_buffers_packed_batch) {
+        c->lastError = "plat_call_fetched_regions: the device library has no plat_read_buffers_packed_batch (PLAT_READS_PACKED fetched tables)";
+        return PLAT_ERR_UNSUPPORTED;
     }
     if (nReads > INT_MAX - 2ll * nStreams - 1 || nBroken > INT_MAX - (long long)nStreams - 1 || nPairs > INT_MAX || nBrokenPairs > INT_MAX) {
         c->lastError = "plat_call_fetched_regions: more reads than one call takes (call the region list in parts)";
@@ -118,12 +156,14 @@ CALLER_EXPORT int plat_call_fetched_regions(plat_caller* c, const plat_fetched_r
     try {
         // the fetched tables, stream after stream (one stream = one sample of one loaded region), and the broken mates, table after table
         // with offsets from 0 per table
-        std::vector<uint8_t> seq, qual, mapq, bSeq, bQual, bMapq;
-        std::vector<int64_t> off, bOff;
+        std::vector<uint8_t> seq, qual, mapq, bSeq, bQual, bMapq, excBase, excQual;
+        std::vector<int64_t> off, bOff, excIdx;
         std::vector<int32_t> pos, end, flags, matePos, insert, cigOff, streamOf, streamBegin, bPos, bEnd, bFlags, bCigOff;
         std::vector<int16_t> cigar, chrom, mateChrom, bCigar;
-        std::vector<long long> bOffAt, bByteAt, bPairAt, bReadAt;
-        seq.reserve((size_t)nBytes + PLAT_BLOB_PAD); qual.reserve((size_t)nBytes + PLAT_BLOB_PAD);
+        std::vector<long long> bOffAt, bByteAt, bQualAt, bPairAt, bReadAt;
+        seq.reserve((size_t)nBytes + PLAT_BLOB_PAD);
+        if (!packed) qual.reserve((size_t)nBytes + PLAT_BLOB_PAD);
+        excIdx.reserve((size_t)nExc); excBase.reserve((size_t)nExc); excQual.reserve((size_t)nExc);
         off.reserve((size_t)nReads + 1); cigOff.reserve((size_t)nReads + 1);
         streamBegin.push_back(0);
         int s = 0;
@@ -137,7 +177,11 @@ CALLER_EXPORT int plat_call_fetched_regions(plat_caller* c, const plat_fetched_r
                 const int32_t c0 = (int32_t)cigar.size() / 2;
                 if (n) {
                     const size_t nb = (size_t)t.off[n], nc = (size_t)t.cig_off[n];
-                    seq.insert(seq.end(), t.seq, t.seq + nb); qual.insert(qual.end(), t.qual, t.qual + nb);
+                    seq.insert(seq.end(), t.seq, t.seq + nb);
+                    if (!packed) qual.insert(qual.end(), t.qual, t.qual + nb);
+                    for (int64_t e = 0; packed && e < t.n_exceptions; ++e) {       // (ascending: each table's lie above the tables' before)
+                        excIdx.push_back(b0 + t.exc_index[e]); excBase.push_back(t.exc_base[e]); excQual.push_back(t.exc_qual[e]);
+                    }
                     for (int r = 0; r < n; ++r) { off.push_back(b0 + t.off[r]); cigOff.push_back(c0 + t.cig_off[r]); }
                     pos.insert(pos.end(), t.pos, t.pos + n); end.insert(end.end(), t.end, t.end + n); mapq.insert(mapq.end(), t.mapq, t.mapq + n);
                     flags.insert(flags.end(), t.flags, t.flags + n); matePos.insert(matePos.end(), t.mate_pos, t.mate_pos + n);
@@ -149,10 +193,11 @@ CALLER_EXPORT int plat_call_fetched_regions(plat_caller* c, const plat_fetched_r
                 streamBegin.push_back((int32_t)pos.size());
                 const plat_read_table& m = f.broken_mates;
                 bOffAt.push_back((long long)bOff.size()); bByteAt.push_back((long long)bSeq.size()); bPairAt.push_back((long long)bCigar.size() / 2);
-                bReadAt.push_back((long long)bPos.size());
-                if (m.n_reads) {
+                bReadAt.push_back((long long)bPos.size()); bQualAt.push_back((long long)bQual.size());
+                if (m.n_reads) {                                      // (a packed table: its bytes only; its exceptions stay in the caller's arrays)
                     const size_t nb = (size_t)m.off[m.n_reads], nc = (size_t)m.cig_off[m.n_reads];
-                    bSeq.insert(bSeq.end(), m.seq, m.seq + nb); bQual.insert(bQual.end(), m.qual, m.qual + nb);
+                    bSeq.insert(bSeq.end(), m.seq, m.seq + nb);
+                    if (m.encoding == PLAT_READS_ASCII) bQual.insert(bQual.end(), m.qual, m.qual + nb);
                     bOff.insert(bOff.end(), m.off, m.off + m.n_reads + 1); bCigOff.insert(bCigOff.end(), m.cig_off, m.cig_off + m.n_reads + 1);
                     bPos.insert(bPos.end(), m.pos, m.pos + m.n_reads); bEnd.insert(bEnd.end(), m.end, m.end + m.n_reads);
                     bMapq.insert(bMapq.end(), m.mapq, m.mapq + m.n_reads); bFlags.insert(bFlags.end(), m.flags, m.flags + m.n_reads);
@@ -162,7 +207,8 @@ CALLER_EXPORT int plat_call_fetched_regions(plat_caller* c, const plat_fetched_r
         }
         off.push_back((int64_t)seq.size()); cigOff.push_back((int32_t)cigar.size() / 2);
         cigar.push_back(0); cigar.push_back(0); bCigar.push_back(0); bCigar.push_back(0);
-        seq.resize(seq.size() + PLAT_BLOB_PAD, 0); qual.resize(qual.size() + PLAT_BLOB_PAD, 0);
+        seq.resize(seq.size() + PLAT_BLOB_PAD, 0);
+        if (!packed) qual.resize(qual.size() + PLAT_BLOB_PAD, 0);
         bSeq.resize(bSeq.size() + PLAT_BLOB_PAD, 0); bQual.resize(bQual.size() + PLAT_BLOB_PAD, 0);
         const int N = (int)nReads;
 
@@ -171,12 +217,21 @@ CALLER_EXPORT int plat_call_fetched_regions(plat_caller* c, const plat_fetched_r
         plat_read_buffers_in in;
         memset(&in, 0, sizeof in);
         in.qc.n_reads = N;
-        in.qc.read_qual = dev.upload(qual, st); in.qc.read_off = dev.upload(off, st); in.qc.read_pos = dev.upload(pos, st);
+        in.qc.read_qual = packed ? nullptr : dev.upload(qual, st); in.qc.read_off = dev.upload(off, st); in.qc.read_pos = dev.upload(pos, st);
         in.qc.read_mapq = dev.upload(mapq, st); in.qc.read_flags = dev.upload(flags, st); in.qc.chrom_id = dev.upload(chrom, st);
         in.qc.mate_chrom_id = dev.upload(mateChrom, st); in.qc.insert_size = dev.upload(insert, st); in.qc.mate_pos = dev.upload(matePos, st);
         in.qc.cigar = dev.upload(cigar, st); in.qc.cig_off = dev.upload(cigOff, st); in.qc.stream_of = dev.upload(streamOf, st);
         in.n_streams = nStreams; in.stream_begin = dev.upload(streamBegin, st);
         in.read_seq = dev.upload(seq, st); in.read_end = dev.upload(end, st);
+        plat_read_buffers_packed_in pin;                                   // packed: the same table, the bytes in/out, the exceptions (not their bases)
+        memset(&pin, 0, sizeof pin);
+        uint8_t* dExcQual = nullptr;
+        if (packed) {
+            pin.qc = in.qc; pin.n_streams = in.n_streams; pin.stream_begin = in.stream_begin;
+            pin.read_packed = const_cast<uint8_t*>(in.read_seq); pin.read_end = in.read_end;
+            pin.n_exc = (int64_t)excIdx.size();
+            if (!excIdx.empty()) { pin.exc_index = dev.upload(excIdx, st); dExcQual = dev.upload(excQual, st); pin.exc_qual = dExcQual; }
+        }
         plat_readqc_options qo;
         qo.min_good_qual_bases = qc->minGoodQualBases; qo.min_map_qual = qc->minMapQual; qo.min_base_qual = qc->minBaseQual;
         qo.trim_overlapping = qc->trimOverlapping; qo.trim_adapter = qc->trimAdapter; qo.trim_read_flank = qc->trimReadFlank;
@@ -185,17 +240,18 @@ CALLER_EXPORT int plat_call_fetched_regions(plat_caller* c, const plat_fetched_r
         qo.filter_duplicates = qc->filterDuplicates;
         plat_read_buffers_tables g;
         g.off = dev.alloc<int64_t>((size_t)N + 2 * (size_t)nStreams); g.cig_off = dev.alloc<int32_t>((size_t)N + 2 * (size_t)nStreams);
-        g.seq = dev.alloc<uint8_t>(seq.size()); g.qual = dev.alloc<uint8_t>(qual.size()); g.cigar = dev.alloc<int16_t>(cigar.size());
+        g.seq = dev.alloc<uint8_t>(seq.size()); g.qual = packed ? nullptr : dev.alloc<uint8_t>(qual.size()); g.cigar = dev.alloc<int16_t>(cigar.size());
         g.pos = dev.alloc<int32_t>((size_t)N); g.end = dev.alloc<int32_t>((size_t)N); g.mapq = dev.alloc<uint8_t>((size_t)N);
         g.flags = dev.alloc<int32_t>((size_t)N); g.mate_pos = dev.alloc<int32_t>((size_t)N);
         ck(plat_memset(z.ctx, g.seq, 0, seq.size(), st), "plat_memset");       // (the blob's slack: 7-bit bytes for kernels that read whole dwords)
-        ck(plat_memset(z.ctx, g.qual, 0, qual.size(), st), "plat_memset");
+        if (!packed) ck(plat_memset(z.ctx, g.qual, 0, qual.size(), st), "plat_memset");
         ck(plat_memset(z.ctx, g.cigar, 0, cigar.size() * sizeof(int16_t), st), "plat_memset");
         int32_t* dOk = dev.alloc<int32_t>((size_t)N);
         int32_t* dWhy = dev.alloc<int32_t>((size_t)N);
         int32_t* dPerm = dev.alloc<int32_t>((size_t)N);
         int32_t* dCounts = dev.alloc<int32_t>((size_t)nStreams * 10);
-        if (nStreams) ck(plat_read_buffers_batch(z.ctx, &in, &qo, dOk, dWhy, dPerm, dCounts, &g, st), "plat_read_buffers_batch");
+        if (nStreams && packed) ck(plat_read_buffers_packed_batch(z.ctx, &pin, &qo, dOk, dWhy, dPerm, dCounts, &g, st), "plat_read_buffers_packed_batch");
+        else if (nStreams) ck(plat_read_buffers_batch(z.ctx, &in, &qo, dOk, dWhy, dPerm, dCounts, &g, st), "plat_read_buffers_batch");
         // broken mates: as handed over, resident
         uint8_t* dbSeq = dev.upload(bSeq, st); uint8_t* dbQual = dev.upload(bQual, st); int64_t* dbOff = dev.upload(bOff, st);
         int32_t* dbPos = dev.upload(bPos, st); int32_t* dbEnd = dev.upload(bEnd, st); uint8_t* dbMapq = dev.upload(bMapq, st);
@@ -207,6 +263,7 @@ CALLER_EXPORT int plat_call_fetched_regions(plat_caller* c, const plat_fetched_r
             ck(plat_memcpy_d2h(z.ctx, flagsQc.data(), in.qc.read_flags, sizeof(int32_t) * (size_t)N, st), "plat_memcpy_d2h");
         }
         if (nStreams) ck(plat_memcpy_d2h(z.ctx, counts.data(), dCounts, sizeof(int32_t) * counts.size(), st), "plat_memcpy_d2h");
+        if (dExcQual) ck(plat_memcpy_d2h(z.ctx, excQual.data(), dExcQual, excQual.size(), st), "plat_memcpy_d2h");     // (trimmed)
         ck(plat_stream_sync(z.ctx, st), "plat_stream_sync");
 
         // the buffers, as the host sees them and as the device holds them
@@ -244,6 +301,12 @@ CALLER_EXPORT int plat_call_fetched_regions(plat_caller* c, const plat_fetched_r
                         h.cigar.insert(h.cigar.end(), cigar.begin() + 2 * (size_t)cigOff[(size_t)r], cigar.begin() + 2 * ((size_t)cigOff[(size_t)r] + (size_t)nc));
                         h.pos[(size_t)q] = pos[(size_t)r]; h.end[(size_t)q] = end[(size_t)r]; h.mapq[(size_t)q] = mapq[(size_t)r];
                         h.flags[(size_t)q] = flagsQc[(size_t)r]; h.matePos[(size_t)q] = matePos[(size_t)r];
+                        if (!excIdx.empty()) {                        // the read's exceptions, re-indexed into this buffer
+                            for (auto e = std::lower_bound(excIdx.begin(), excIdx.end(), off[(size_t)r]); e != excIdx.end() && *e < off[(size_t)r + 1]; ++e) {
+                                const size_t x = (size_t)(e - excIdx.begin());
+                                h.excIndex.push_back(bo + (*e - off[(size_t)r])); h.excBase.push_back(excBase[x]); h.excQual.push_back(excQual[x]);
+                            }
+                        }
                         bo += len; co += nc;
                     }
                     h.off[(size_t)m] = bo; h.cigOff[(size_t)m] = co;
@@ -251,12 +314,16 @@ CALLER_EXPORT int plat_call_fetched_regions(plat_caller* c, const plat_fetched_r
                     h.cigar.push_back(0); h.cigar.push_back(0);
                     plat_read_table& t = tabs[3 * (size_t)s + (size_t)part];
                     memset(&t, 0, sizeof t);
-                    t.n_reads = m; t.encoding = PLAT_READS_ASCII;
+                    t.n_reads = m; t.encoding = packed ? PLAT_READS_PACKED : PLAT_READS_ASCII;
                     t.seq = h.seq.data(); t.qual = nullptr; t.off = h.off.data(); t.pos = h.pos.data(); t.end = h.end.data(); t.mapq = h.mapq.data();
                     t.flags = h.flags.data(); t.mate_pos = h.matePos.data(); t.cigar = h.cigar.data(); t.cig_off = h.cigOff.data();
+                    if (packed) {
+                        t.n_exceptions = (int64_t)h.excIndex.size();
+                        t.exc_index = h.excIndex.data(); t.exc_base = h.excBase.data(); t.exc_qual = h.excQual.data();
+                    }
                     // the device's copy (plat_read_buffers_batch's layout: `reads` then `badReads` at the stream's input bytes and pairs)
                     const size_t oi = (size_t)b + 2 * (size_t)s + (part == 0 ? 0 : (size_t)nGood + 1);
-                    t.dev_seq = g.seq + byteAt; t.dev_qual = g.qual + byteAt; t.dev_off = g.off + oi; t.dev_cig_off = g.cig_off + oi;
+                    t.dev_seq = g.seq + byteAt; t.dev_qual = packed ? nullptr : g.qual + byteAt; t.dev_off = g.off + oi; t.dev_cig_off = g.cig_off + oi;
                     t.dev_cigar = g.cigar + 2 * (size_t)pairAt; t.dev_pos = g.pos + b + p0; t.dev_end = g.end + b + p0;
                     t.dev_mapq = g.mapq + b + p0; t.dev_flags = g.flags + b + p0;
                     byteAt += bo; pairAt += co;
@@ -264,11 +331,12 @@ CALLER_EXPORT int plat_call_fetched_regions(plat_caller* c, const plat_fetched_r
                 const plat_read_table& m = regions[k].samples[i].broken_mates;
                 plat_read_table& t = tabs[3 * (size_t)s + 2];
                 t = m;
-                t.dev_seq = dbSeq + bByteAt[(size_t)s]; t.dev_qual = dbQual + bByteAt[(size_t)s]; t.dev_off = dbOff + bOffAt[(size_t)s];
+                t.dev_seq = dbSeq + bByteAt[(size_t)s]; t.dev_qual = m.encoding == PLAT_READS_ASCII ? dbQual + bQualAt[(size_t)s] : nullptr;
+                t.dev_off = dbOff + bOffAt[(size_t)s];
                 t.dev_cig_off = dbCigOff + bOffAt[(size_t)s]; t.dev_cigar = dbCigar + 2 * bPairAt[(size_t)s];
                 const long long r0 = bReadAt[(size_t)s];
                 t.dev_pos = dbPos + r0; t.dev_end = dbEnd + r0; t.dev_mapq = dbMapq + r0; t.dev_flags = dbFlags + r0;
-                if (!m.n_reads) { t.dev_off = nullptr; t.dev_seq = nullptr; }
+                if (!m.n_reads) { t.dev_off = nullptr; t.dev_seq = nullptr; t.dev_qual = nullptr; }
             }
         }
     } catch (const DeviceError& e) {
@@ -308,7 +376,7 @@ CALLER_EXPORT int plat_call_fetched_regions(plat_caller* c, const plat_fetched_r
         }
     }
     st.n_regions = n_regions;
-    st.input_bytes = 2 * (nBytes + nBrokenBytes);
+    st.input_bytes = linkBytes;
     st.seconds_total = secs(t0, Clock::now());
     if (stats) *stats = st;
     return PLAT_OK;

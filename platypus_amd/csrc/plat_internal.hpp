@@ -95,3 +95,7 @@ static inline int plat_reserve(plat_ctx* ctx, plat_scratch& s, size_t bytes) {
     s.cap = want;
     return PLAT_OK;
 }
+
+// checkAndTrimRead over a PLAT_READS_PACKED table (k_read_qc_packed, plat_candidates.hip): the first step of plat_read_buffers_packed_batch
+int plat_read_qc_packed_launch(plat_ctx* ctx, const plat_read_buffers_packed_in& in, const plat_readqc_options& options, int32_t* out_ok,
+                               int32_t* out_reason, hipStream_t stream);

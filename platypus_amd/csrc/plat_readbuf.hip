@@ -1,6 +1,8 @@
 // plat_readbuf.hip -- the read buffers of fetched streams (plat_read_buffers_batch, include/platypus_mi355x.h):
 // checkAndTrimRead (k_read_qc, plat_candidates.hip) in place, then bamReadBuffer.addReadToBuffer's split into `reads` / `badReads`
 // (cwindow.pyx:560-595) as a stable per-stream partition, then, optionally, the two buffers gathered into device tables.
+// plat_read_buffers_packed_batch: the same for PLAT_READS_PACKED tables (k_read_qc_packed, then the same split and a gather of the packed
+// bytes).
 #include "plat_internal.hpp"
 
 namespace plat {
@@ -106,7 +108,9 @@ k_read_split(int n_reads, const int32_t* __restrict__ stream_begin, const int32_
     }
 }
 
-// One wave per place of the split: lane 0 the read's scalars, the lanes its bases, qualities and CIGAR pairs.
+// One wave per place of the split: lane 0 the read's scalars, the lanes its bases, qualities and CIGAR pairs.  QUAL = false: a packed
+// table (bases and qualities in one byte; t.qual is not written)
+template <bool QUAL>
 __global__ void __launch_bounds__(256)
 k_read_gather(int n_reads, int n_streams, const int32_t* __restrict__ stream_begin, plat_readqc_batch q, const uint8_t* __restrict__ seq,
               const int32_t* __restrict__ end, const int32_t* __restrict__ perm, const int32_t* __restrict__ counts, plat_read_buffers_tables t)
@@ -127,7 +131,10 @@ k_read_gather(int n_reads, int n_streams, const int32_t* __restrict__ stream_beg
     const long long from = q.read_off[src], len = q.read_off[src + 1] - from;
     const int c0 = q.cig_off[src], nc = q.cig_off[src + 1] - c0;
     if (byte < 0 || byte + len > q.read_off[n_reads] || pair < 0 || pair + nc > q.cig_off[n_reads]) return;
-    for (long long j = lane; j < len; j += 64) { t.seq[byte + j] = seq[from + j]; t.qual[byte + j] = q.read_qual[from + j]; }
+    for (long long j = lane; j < len; j += 64) {
+        t.seq[byte + j] = seq[from + j];
+        if (QUAL) t.qual[byte + j] = q.read_qual[from + j];
+    }
     for (int j = lane; j < 2 * nc; j += 64) t.cigar[2 * pair + j] = q.cigar[2ll * c0 + j];
     if (lane == 0) {
         t.pos[place] = q.read_pos[src]; t.end[place] = end[src]; t.mapq[place] = q.read_mapq[src];
@@ -135,6 +142,26 @@ k_read_gather(int n_reads, int n_streams, const int32_t* __restrict__ stream_beg
     }
 }
 }  // namespace plat
+
+namespace {
+// the split of every stream and, with tables, the gather: shared by both entry points (the verdicts are in out_ok / out_reason)
+template <bool QUAL>
+int split_and_gather(plat_ctx* ctx, const plat_readqc_batch& q, int n_streams, const int32_t* stream_begin, const uint8_t* seq, const int32_t* end,
+                     const int32_t* out_ok, const int32_t* out_reason, int32_t* out_perm, int32_t* out_counts, const plat_read_buffers_tables* tab,
+                     bool tables, hipStream_t st)
+{
+    { PLAT_KT_BEGIN(ctx, PLAT_KT_OTHER, st); hipLaunchKernelGGL(plat::k_read_split, dim3((unsigned)n_streams), dim3(plat::SPLIT_THREADS), 0, st, q.n_reads, stream_begin,
+                       out_ok, out_reason, q.read_pos, tables ? q.read_off : nullptr, tables ? q.cig_off : nullptr, out_perm, out_counts,
+                       tables ? tab->off : nullptr, tables ? tab->cig_off : nullptr); PLAT_KT_END(ctx, PLAT_KT_OTHER, st); }
+    if (tables && q.n_reads > 0) {
+        const unsigned blocks = (unsigned)(((long long)q.n_reads + 3) / 4);
+        { PLAT_KT_BEGIN(ctx, PLAT_KT_OTHER, st); hipLaunchKernelGGL(plat::k_read_gather<QUAL>, dim3(blocks), dim3(256), 0, st, q.n_reads, n_streams, stream_begin, q,
+                           seq, end, out_perm, out_counts, *tab); PLAT_KT_END(ctx, PLAT_KT_OTHER, st); }
+    }
+    PLAT_HIP(ctx, hipGetLastError());
+    return PLAT_OK;
+}
+}  // namespace
 
 PLAT_EXPORT int plat_read_buffers_batch(plat_ctx* ctx, const plat_read_buffers_in* in, const plat_readqc_options* options, int32_t* out_ok,
                                         int32_t* out_reason, int32_t* out_perm, int32_t* out_counts, const plat_read_buffers_tables* tab, void* stream)
@@ -153,14 +180,29 @@ PLAT_EXPORT int plat_read_buffers_batch(plat_ctx* ctx, const plat_read_buffers_i
         const int rc = plat_read_qc_batch(ctx, &q, options, out_ok, out_reason, stream);
         if (rc != PLAT_OK) return rc;
     }
-    { PLAT_KT_BEGIN(ctx, PLAT_KT_OTHER, st); hipLaunchKernelGGL(plat::k_read_split, dim3((unsigned)in->n_streams), dim3(plat::SPLIT_THREADS), 0, st, q.n_reads, in->stream_begin,
-                       out_ok, out_reason, q.read_pos, tables ? q.read_off : nullptr, tables ? q.cig_off : nullptr, out_perm, out_counts,
-                       tables ? tab->off : nullptr, tables ? tab->cig_off : nullptr); PLAT_KT_END(ctx, PLAT_KT_OTHER, st); }
-    if (tables && q.n_reads > 0) {
-        const unsigned blocks = (unsigned)(((long long)q.n_reads + 3) / 4);
-        { PLAT_KT_BEGIN(ctx, PLAT_KT_OTHER, st); hipLaunchKernelGGL(plat::k_read_gather, dim3(blocks), dim3(256), 0, st, q.n_reads, in->n_streams, in->stream_begin, q,
-                           in->read_seq, in->read_end, out_perm, out_counts, *tab); PLAT_KT_END(ctx, PLAT_KT_OTHER, st); }
-    }
-    PLAT_HIP(ctx, hipGetLastError());
-    return PLAT_OK;
+    return split_and_gather<true>(ctx, q, in->n_streams, in->stream_begin, in->read_seq, in->read_end, out_ok, out_reason, out_perm, out_counts,
+                                  tab, tables, st);
+}
+
+PLAT_EXPORT int plat_read_buffers_packed_batch(plat_ctx* ctx, const plat_read_buffers_packed_in* in, const plat_readqc_options* options,
+                                               int32_t* out_ok, int32_t* out_reason, int32_t* out_perm, int32_t* out_counts,
+                                               const plat_read_buffers_tables* tab, void* stream)
+{
+    if (!ctx || !in || !options || in->n_streams < 0 || in->qc.n_reads < 0 || in->n_exc < 0) return PLAT_ERR_INVALID;
+    const plat_readqc_batch& q = in->qc;
+    if (in->n_streams == 0) return q.n_reads == 0 ? PLAT_OK : PLAT_ERR_INVALID;
+    if (!in->stream_begin || !out_ok || !out_reason || !out_perm || !out_counts) return PLAT_ERR_INVALID;
+    if (q.n_reads > 0 && (!in->read_packed || !q.read_off || !q.read_pos || !q.read_mapq || !q.read_flags || !q.chrom_id || !q.mate_chrom_id ||
+                          !q.insert_size || !q.mate_pos || !q.cigar || !q.cig_off || !q.stream_of))
+        return PLAT_ERR_INVALID;
+    if (in->n_exc > 0 && (!in->exc_index || !in->exc_qual)) return PLAT_ERR_INVALID;
+    const bool tables = tab && tab->seq;
+    if (tables && (!in->read_end || !tab->off || !tab->cig_off || !tab->cigar || !tab->pos || !tab->end || !tab->mapq || !tab->flags || !tab->mate_pos))
+        return PLAT_ERR_INVALID;
+    PLAT_HIP(ctx, hipSetDevice(ctx->device));
+    const hipStream_t st = (hipStream_t)stream;
+    const int rc = plat_read_qc_packed_launch(ctx, *in, *options, out_ok, out_reason, st);
+    if (rc != PLAT_OK) return rc;
+    return split_and_gather<false>(ctx, q, in->n_streams, in->stream_begin, in->read_packed, in->read_end, out_ok, out_reason, out_perm, out_counts,
+                                   tab, tables, st);
 }

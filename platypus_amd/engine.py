@@ -440,12 +440,16 @@ class Engine:
         return out
 
     def read_buffers(self, streams, min_good_qual_bases=20, min_map_qual=20, min_base_qual=20, trim_overlapping=1, trim_adapter=1,
-                     trim_read_flank=0, trim_soft_clipped=1, enabled=(1, 1, 1, 1)):
+                     trim_read_flank=0, trim_soft_clipped=1, enabled=(1, 1, 1, 1), packed=False):
         """plat_read_buffers_batch: checkAndTrimRead over whole streams (as read_qc), then every stream's split into `reads` / `badReads`
         and the two buffers gathered.  `streams`: list of lists of dicts {seq, qual, pos, end, mapq, flag, chromID, mateChromID, insertSize,
         matePos, cigar} in fetch order.  Returns per stream a dict: ok, reason, flags (after QC, fetch order), perm (indices into the stream:
         accepted then rejected), n_good, unsorted, hist [8], and reads / bad: the gathered buffers (seq, qual, off, pos, end, mapq, flags,
-        mate_pos, cigar [n, 2], cig_off)."""
+        mate_pos, cigar [n, 2], cig_off).
+        packed=True: the reads go over as PLAT_READS_PACKED (one byte per base, exceptions for bases other than A/C/G/T and qualities above
+        63) through plat_read_buffers_packed_batch; no quality array is built.  The buffers' seq / qual are then DECODED from the gathered
+        packed bytes and the trimmed exceptions, and each buffer also holds `packed` (its gathered bytes) and `exc_index` (its exceptions,
+        indexed into those bytes); every stream holds exc_qual (its exceptions' trimmed qualities, in input order)."""
         torch = _torch()
         reads = [r for st in streams for r in st]
         n, ns = len(reads), len(streams)
@@ -459,8 +463,16 @@ class Engine:
         raw = lambda x: x.encode() if isinstance(x, str) else bytes(x)
         cat = lambda key: np.concatenate([np.frombuffer(raw(r[key]), dtype=np.uint8) for r in reads]) if n else np.zeros(0, np.uint8)
         nb, npairs = int(off[-1]), int(coff[-1])
-        qual = dev(pad_blob(cat("qual")), np.uint8)
-        seq = dev(pad_blob(cat("seq")), np.uint8)
+        if packed:
+            seq_h, qual_h = cat("seq"), cat("qual")
+            exc = np.nonzero(~np.isin(seq_h, np.frombuffer(b"ACGT", np.uint8)) | (qual_h > 63))[0].astype(np.int64)
+            exc_base, exc_qual_in = seq_h[exc].copy(), qual_h[exc].copy()
+            qual = None
+            seq = dev(pad_blob((((seq_h >> 1) & 3) | (np.minimum(qual_h, 63) << 2)).astype(np.uint8)), np.uint8)
+            d_exc = dict(idx=dev(np.append(exc, 0), np.int64), base=dev(np.append(exc_base, 0), np.uint8), qual=dev(np.append(exc_qual_in, 0), np.uint8))
+        else:
+            qual = dev(pad_blob(cat("qual")), np.uint8)
+            seq = dev(pad_blob(cat("seq")), np.uint8)
         sbeg = np.concatenate([[0], np.cumsum([len(st) for st in streams])]).astype(np.int32)
         t = dict(off=dev(off, np.int64), pos=dev([r["pos"] for r in reads] + [0], np.int32), end=dev([r["end"] for r in reads] + [0], np.int32),
                  mapq=dev([r["mapq"] for r in reads] + [0], np.uint8), flags=dev([r["flag"] for r in reads] + [0], np.int32),
@@ -468,13 +480,17 @@ class Engine:
                  ins=dev([r["insertSize"] for r in reads] + [0], np.int32), mpos=dev([r["matePos"] for r in reads] + [0], np.int32),
                  cig=dev([x for r in reads for c in r["cigar"] for x in c] + [0, 0], np.int16), coff=dev(coff, np.int32),
                  sof=dev(np.repeat(np.arange(ns), [len(st) for st in streams]).tolist() + [0], np.int32), sbeg=dev(sbeg, np.int32))
-        b = _lib.ReadBuffersIn()
+        b = _lib.ReadBuffersPackedIn() if packed else _lib.ReadBuffersIn()
         q = b.qc
         q.n_reads = n
-        q.read_qual, q.read_off, q.read_pos, q.read_mapq, q.read_flags = qual.data_ptr(), t["off"].data_ptr(), t["pos"].data_ptr(), t["mapq"].data_ptr(), t["flags"].data_ptr()
+        q.read_qual, q.read_off, q.read_pos, q.read_mapq, q.read_flags = (0 if packed else qual.data_ptr()), t["off"].data_ptr(), t["pos"].data_ptr(), t["mapq"].data_ptr(), t["flags"].data_ptr()
         q.chrom_id, q.mate_chrom_id, q.insert_size, q.mate_pos = t["cid"].data_ptr(), t["mcid"].data_ptr(), t["ins"].data_ptr(), t["mpos"].data_ptr()
         q.cigar, q.cig_off, q.stream_of = t["cig"].data_ptr(), t["coff"].data_ptr(), t["sof"].data_ptr()
-        b.n_streams, b.stream_begin, b.read_seq, b.read_end = ns, t["sbeg"].data_ptr(), seq.data_ptr(), t["end"].data_ptr()
+        if packed:
+            b.n_streams, b.stream_begin, b.read_packed, b.read_end = ns, t["sbeg"].data_ptr(), seq.data_ptr(), t["end"].data_ptr()
+            b.n_exc, b.exc_index, b.exc_base, b.exc_qual = len(exc), d_exc["idx"].data_ptr(), d_exc["base"].data_ptr(), d_exc["qual"].data_ptr()
+        else:
+            b.n_streams, b.stream_begin, b.read_seq, b.read_end = ns, t["sbeg"].data_ptr(), seq.data_ptr(), t["end"].data_ptr()
         o = _lib.ReadQCOptions(min_good_qual_bases, min_map_qual, min_base_qual, trim_overlapping, trim_adapter, trim_read_flank,
                                trim_soft_clipped, *[int(x) for x in enabled])
         e = lambda k, dt: torch.zeros(max(k, 1), dtype=dt, device=self.device)
@@ -482,12 +498,33 @@ class Engine:
         g = dict(off=e(n + 2 * ns, torch.int64), cig_off=e(n + 2 * ns, torch.int32), seq=e(nb + _lib.PLAT_BLOB_PAD, torch.uint8),
                  qual=e(nb + _lib.PLAT_BLOB_PAD, torch.uint8), cigar=e(2 * npairs, torch.int16), pos=e(n, torch.int32), end=e(n, torch.int32),
                  mapq=e(n, torch.uint8), flags=e(n, torch.int32), mate_pos=e(n, torch.int32))
-        tab = _lib.ReadBuffersTables(*[g[k].data_ptr() for k, _ in _lib.ReadBuffersTables._fields_])
-        _lib.check(self.lib.plat_read_buffers_batch(self.ctx, C.byref(b), C.byref(o), ok.data_ptr(), why.data_ptr(), perm.data_ptr(), counts.data_ptr(),
-                                                    C.byref(tab), self._stream()), "plat_read_buffers_batch")
+        if packed:
+            g["qual"] = None
+        tab = _lib.ReadBuffersTables(*[(g[k].data_ptr() if g[k] is not None else 0) for k, _ in _lib.ReadBuffersTables._fields_])
+        fn = "plat_read_buffers_packed_batch" if packed else "plat_read_buffers_batch"
+        _lib.check(getattr(self.lib, fn)(self.ctx, C.byref(b), C.byref(o), ok.data_ptr(), why.data_ptr(), perm.data_ptr(), counts.data_ptr(),
+                                         C.byref(tab), self._stream()), fn)
         self._sync()
-        h = {k: v.cpu().numpy() for k, v in g.items()}
+        h = {k: v.cpu().numpy() for k, v in g.items() if v is not None}
         ok_h, why_h, perm_h, cnt_h, fl_h = ok.cpu().numpy(), why.cpu().numpy(), perm.cpu().numpy(), counts.cpu().numpy(), t["flags"].cpu().numpy()
+        if packed:
+            # decode the gathered bytes: every input byte's place in the gathered blob (through the split), then the trimmed exceptions there
+            exc_trim = d_exc["qual"].cpu().numpy()[:len(exc)]
+            h["packed"] = h["seq"]
+            h["seq"] = np.frombuffer(b"ACTG", np.uint8)[h["packed"] & 3]
+            h["qual"] = (h["packed"] >> 2).astype(np.uint8)
+            dst = np.zeros(n, dtype=np.int64)
+            for s in range(ns):
+                a, z = int(sbeg[s]), int(sbeg[s + 1])
+                ng = int(cnt_h[10 * s])
+                byte = int(off[a])
+                for p0, p1, ob in ((0, ng, a + 2 * s), (ng, z - a, a + 2 * s + ng + 1)):
+                    to = h["off"][ob:ob + p1 - p0 + 1]
+                    dst[perm_h[a + p0:a + p1]] = byte + to[:-1]
+                    byte += int(to[-1])
+            src = np.searchsorted(off, exc, side="right") - 1
+            at = dst[src] + (exc - off[src]) if len(exc) else np.zeros(0, np.int64)
+            h["seq"][at], h["qual"][at] = exc_base, exc_trim
         out = []
         for s in range(ns):
             a, z = int(sbeg[s]), int(sbeg[s + 1])
@@ -501,7 +538,12 @@ class Engine:
                 res[name] = dict(off=to, cig_off=tc, seq=h["seq"][byte:byte + to[-1]], qual=h["qual"][byte:byte + to[-1]],
                                  cigar=h["cigar"][2 * pair:2 * (pair + tc[-1])].reshape(-1, 2), pos=h["pos"][a + p0:a + p1], end=h["end"][a + p0:a + p1],
                                  mapq=h["mapq"][a + p0:a + p1], flags=h["flags"][a + p0:a + p1], mate_pos=h["mate_pos"][a + p0:a + p1])
+                if packed:
+                    res[name]["packed"] = h["packed"][byte:byte + to[-1]]
+                    res[name]["exc_index"] = np.sort(at[(at >= byte) & (at < byte + to[-1])]) - byte
                 byte += int(to[-1]); pair += int(tc[-1])
+            if packed:
+                res["exc_qual"] = exc_trim[(exc >= off[a]) & (exc < off[z])]
             out.append(res)
         return out
 

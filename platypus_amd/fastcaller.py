@@ -229,13 +229,14 @@ class FetchedRegion:
         self._c = None
 
     @classmethod
-    def from_reads(cls, chrom, start, end, fasta, samples):
+    def from_reads(cls, chrom, start, end, fasta, samples, packed=False):
         """samples: per sample (fetched, brokenMates), lists of hostapi.AlignedRead -- fetched in fetch order; brokenMates are sorted by
-        mate position here, as bamReadBuffer.sortBrokenMates does (cwindow.pyx:759-766)."""
+        mate position here, as bamReadBuffer.sortBrokenMates does (cwindow.pyx:759-766).  packed=True hands both tables over as
+        PLAT_READS_PACKED (one byte per base + exceptions; the device then checks and trims the packed bytes)."""
         out = []
         for fetched, broken in samples:
             c = lambda f, dt: np.ascontiguousarray([f(r) for r in fetched], dtype=dt)
-            out.append((ReadTable.from_reads(fetched), ReadTable.from_reads(sorted(broken, key=lambda r: r.matePos)),
+            out.append((ReadTable.from_reads(fetched, packed), ReadTable.from_reads(sorted(broken, key=lambda r: r.matePos), packed),
                         c(lambda r: r.chromID, np.int16), c(lambda r: r.mateChromID, np.int16), c(lambda r: r.insertSize, np.int32)))
         return cls(chrom, start, end, fasta._seq[chrom], out)
 
