@@ -10,12 +10,14 @@ variants -> windows -> haplotypes (device) -> pair-HMM likelihoods / genotype li
 native region loop, then the job's ONE exchange (record text to rank 0, RCCL under "nccl") and the merge -- all inside the timed region.
 `value` = pair-HMM GCUPS, reference-equivalent (band cells of the fastAlignmentRoutine calls the reference would make for
 the called windows / wall time); `config.windows_per_sec` = the metric's second half; `roofline` = the loop's dominant kernel by summed
-live launch time (deterministic: tools/bench_other.config4_gcups); `cpu_baseline` = the unmodified reference align.c on the host's cores.
+live launch time (deterministic: tools/bench_other.config4_gcups); `cpu_baseline` (--full) = the unmodified reference align.c on the host's cores.
 Region i -> rank i % N, no data-path collective (runner.py:470-500).
 
-At N = 1 the line also carries `config2` (the batched pair-HMM of BASELINE config 2 on resident batches: reference-equivalent and
-executed GCUPS, every reference DP executed, the hard workload, k_dp_jobs' roofline) and `other_configs` (3, 4 streamed, 5).
-`--config 2|3|4|5` puts that config alone on the line (same contract); `--config 4` is the default line without the sub-blocks.
+A plain run does only what the headline needs: it sets up, warms up, times the K steps, writes --dump-outputs and prints the line.
+`--full` adds everything else the benchmark measures: `cpu_baseline`, and at N = 1 `config2` (the batched pair-HMM of BASELINE config 2
+on resident batches: reference-equivalent and executed GCUPS, every reference DP executed, the hard workload, k_dp_jobs' roofline) and
+`other_configs` (3, 4 streamed, 5); on the --config 2|3|5 lines the CPU baseline and the secondary measurements (--no-extras).
+`--config 2|3|4|5` puts that config alone on the line (same contract); `--config 4` is the default line without the sub-blocks, with --full too.
 
 The JSON line on stdout carries the headline keys only (HEADLINE_KEYS); `--detail FILE` (e.g. bench_detail.json) writes the whole line,
 sub-blocks included, to FILE.  `--dump-outputs DIR` (config 4; e.g. bench_outputs) writes what the timed path computed in its last step --
@@ -382,7 +384,7 @@ def selftest_ranks(a):
     rk.close()
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None, help="timed steps (default: 10 passes over the WGS share; --config 2: 400 steps)")
@@ -392,8 +394,10 @@ def main():
     ap.add_argument("--regions", type=int, default=None, help="config 3: assembly tiles per GPU per step (2000); config 4: regions of the WHOLE job "
                                                               "(default 3875 per GPU), region i -> rank i %% N")
     ap.add_argument("--batches", type=int, default=8, help="distinct resident batches the steps walk through")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary measurements (all-DP, hard workload, other configs)")
+    ap.add_argument("--full", action="store_true", help="also measure everything beyond the headline: the CPU baseline, the config-2 and "
+                                                        "other-config sub-blocks, the secondary measurements (off: a plain run)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the secondary measurements (all-DP, hard workload, other configs)")
     ap.add_argument("--streams", type=int, default=3,
                     help="independent batches in flight per GPU: one plat_ctx + HIP stream each; step i runs on stream i %% S "
                          "(1 = strictly one batch at a time)")
@@ -408,12 +412,18 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="config 4: after the timed steps write the record text of the last step as DIR/<name>.npy (dump_record_text)")
     ap.add_argument("--detail", metavar="FILE", default=None, help="write the whole line (every sub-block) to FILE as JSON; stdout keeps HEADLINE_KEYS")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     if a.steps is not None and a.steps < 1:
         ap.error("--steps must be at least 1")
     if a.dump_outputs and a.config not in (None, 4):
         ap.error("--dump-outputs: the config-4 line (the default) only")
+    if not a.full:                              # a plain run: the headline alone
+        a.no_cpu_baseline = a.no_extras = True
+    return a
 
+
+def main():
+    a = parse_args()
     if a.gpus > 1 and "RANK" not in os.environ:
         # started without a launcher: become N ranks, one per GPU (the driver's N>1 form goes through torch.distributed.run itself)
         import subprocess
@@ -447,7 +457,7 @@ def main():
 
 def line_wgs(a, rk):
     """The default line: BASELINE config 4 on this job's GPUs (tools/bench_other.line_config4: value / config / roofline / cpu_baseline are the WGS
-    job's), + at N = 1 the config-2 sub-block and the other configs."""
+    job's), + with --full at N = 1 the config-2 sub-block and the other configs."""
     from types import SimpleNamespace
     from tools import bench_other
     a.steps = a.steps or 10

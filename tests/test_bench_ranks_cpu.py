@@ -255,3 +255,14 @@ def test_dump_outputs_are_the_record_text_of_the_last_step(tmp_path):
     q = np.load(str(tmp_path / "s1" / "record_qual.npy"))
     assert np.array_equal(np.isnan(q), idx % 7 == 0) and np.all(np.load(str(tmp_path / "s1" / "record_region.npy")) == -1)
     assert np.array_equal(np.load(str(tmp_path / "s1" / "record_pos.npy")), idx + 1)
+
+
+def test_plain_run_measures_the_headline_alone():
+    """`bench.py --gpus 1 --steps K --warmup W` does only what its headline needs: the CPU baseline and the secondary measurements
+    (sub-blocks, all-DP, hard workload, end to end) run only under `--full`, where --no-cpu-baseline / --no-extras still leave them out."""
+    import bench
+    plain = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert not plain.full and plain.no_cpu_baseline and plain.no_extras and (plain.steps, plain.warmup) == (3, 1)
+    full = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1", "--full"])
+    assert full.full and not full.no_cpu_baseline and not full.no_extras
+    assert bench.parse_args(["--full", "--no-extras"]).no_extras and not bench.parse_args(["--full", "--no-extras"]).no_cpu_baseline

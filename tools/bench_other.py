@@ -240,7 +240,8 @@ def config4(device, indices, region_len, workers, per_chunk, repeats=1, n_sample
     src = source.RegionSource(indices, len(indices) if resident else n_slots, **kw)
     if resident:
         import torch
-        src.make_resident(None if lib is not None else torch.device("cuda", device), threads=max(2, loaders))
+        # (before the timed region: the generation may use every CPU the rank is granted, not only the loaders' share)
+        src.make_resident(None if lib is not None else torch.device("cuda", device), threads=max(2, loaders, getattr(rk, "cpus", 0)))
     names = ["S%d" % (i + 1) for i in range(n_samples)]
     nc = F.NativeCaller(device, workers, per_chunk, lib=lib)
     # (the timed runs are the steady state of a long job -- a rank's share of a genome is eight such lists --: ONE UNTIMED PASS over the

@@ -16,7 +16,7 @@
 #   pmcseed three SQ passes over k_seed / k_dp_jobs / k_prep_reads (instruction mix, waits, LDS conflicts)
 #   dpstall where k_dp_jobs' wave cycles go: parked on waits / issue stalls / active (SQ counters), config 2 as it runs and with every DP executed
 #   nextk   kernel stats of the "next row" kernels (tools/next_kernels.py)
-#   line    the default bench line, bench.py --config 3/4/5, the two-rank launches on the one GPU
+#   line    the default bench line and bench.py --config 3/4/5 with --full, the two-rank launches on the one GPU
 #   soaks   ungapped cross-check (plain + wrap regime), native region-loop soak, assembler soak; SOAK_SECONDS each (default 400)
 # gpurun only brings back gpurun_out/: the summaries are written to profiles/ on the box AND copied to $O/out; copy them from there.
 TAG=${1:-r06}; shift
@@ -32,14 +32,14 @@ pmc() { d=$1; c=$2; shift 2; rm -rf $O/$d; rocprofv3 --kernel-trace --pmc $c --o
 for p in $PARTS; do case $p in
   tests) (cd $R && python -m pytest tests -q -m gpu 2>&1 | tail -5 > $O/pytest_gpu.txt; cat $O/pytest_gpu.txt) ;;
   c2) prof stats1 python $R/bench.py $B2 --streams 1; prof stats3 python $R/bench.py $B2 ;;
-  c3) prof stats_c3 python $R/bench.py --config 3 --regions 2000 --steps 5 --no-extras; prof stats_c3e python $R/bench.py --config 3 --regions 2000 --steps 1 ;;
+  c3) prof stats_c3 python $R/bench.py --config 3 --regions 2000 --steps 5 --no-extras; prof stats_c3e python $R/bench.py --config 3 --regions 2000 --steps 1 --full ;;
   c4) PLAT_CALLER_CHUNK=128 prof stats_c4 python $R/bench.py --config 4 --regions 12288 --steps 1 --no-cpu-baseline
       f=$(ls $O/stats_c4/*/*kernel_trace.csv 2>/dev/null | head -1); [ -n "$f" ] && python $R/tools/trace_overlap.py $f 3 300 > $O/config4_overlap.json ;;
   c4solo) PLAT_CALLER_WORKERS=1 PLAT_CALLER_CHUNK=128 prof stats_c4solo python $R/bench.py --config 4 --regions 2048 --steps 1 --no-cpu-baseline ;;
   pmc4) for c in FETCH_SIZE WRITE_SIZE; do PLAT_CALLER_CHUNK=128 pmc pmc4_$c $c python $R/bench.py --config 4 --regions 12288 --steps 1 --no-cpu-baseline; done
         PLAT_CALLER_CHUNK=128 pmc pmc4_SQ "SQ_INSTS_VALU GRBM_GUI_ACTIVE SQ_WAVES" python $R/bench.py --config 4 --regions 12288 --steps 1 --no-cpu-baseline ;;
   mapa) (cd $R && hipcc --offload-arch=gfx950 -O3 -o /tmp/dp_mapping_a tools/ubench/dp_mapping_a.hip -Lplatypus_amd -lplat_mi355x && LD_LIBRARY_PATH=platypus_amd /tmp/dp_mapping_a 400000 150 | tail -1 > $O/dp_mapping_a.json; cat $O/dp_mapping_a.json) ;;
-  c5) prof stats_c5 python $R/bench.py --config 5 --windows 200 --steps 10 --warmup 2 ;;
+  c5) prof stats_c5 python $R/bench.py --config 5 --windows 200 --steps 10 --warmup 2 --full ;;
   pmc2) for c in FETCH_SIZE WRITE_SIZE; do pmc pmc_$c $c python $R/bench.py --config 2 --steps 4 --warmup 1 --min-seconds 0 --no-cpu-baseline --no-extras --batches 2 --streams 1; done
         pmc pmc_SQ "SQ_INSTS_VALU GRBM_GUI_ACTIVE SQ_WAVES" python $R/bench.py --config 2 --steps 4 --warmup 1 --min-seconds 0 --no-cpu-baseline --no-extras --batches 2 --streams 1 ;;
   pmc3) for c in FETCH_SIZE WRITE_SIZE; do pmc pmc3_$c $c python $R/bench.py --config 3 --regions 2000 --steps 2 --no-extras; done
@@ -61,8 +61,8 @@ for p in $PARTS; do case $p in
           echo "# PLAT_NO_UNGAPPED=1 PLAT_NO_EXACT=1: every reference DP executed (1.57 M DPs per launch):"; python tools/pmc_summary.py $O/dps_all_a 2>&1 | grep "k_dp_jobs"; } > $O/dp_stalls.txt; cat $O/dp_stalls.txt) ;;
   nextk) prof nextk python $R/tools/next_kernels.py ;;
   line) (cd $R
-        python bench.py > $O/bench_line.json 2> $O/bench_line.err
-        for c in 3 4 5; do python bench.py --config $c > $O/bench_config$c.json 2> $O/bench_config$c.err; done
+        python bench.py --full > $O/bench_line.json 2> $O/bench_line.err
+        for c in 3 4 5; do python bench.py --config $c --full > $O/bench_config$c.json 2> $O/bench_config$c.err; done
         python bench.py --gpus 2 --steps 5 --no-extras > $O/bench_2ranks.json 2> $O/bench_2ranks.err
         python bench.py --gpus 2 --config 4 --regions 4096 > $O/bench_c4_2ranks.json 2> $O/bench_c4_2ranks.err
         PLAT_CALLER_LOADERS=2 taskset -c 0,1 python bench.py --config 4 --regions 4096 --steps 3 --no-cpu-baseline > $O/bench_config4_2cpus.json 2> $O/bench_config4_2cpus.err

@@ -146,8 +146,8 @@ def main(o, tag):
     stats(o + "/stats1", prof + "/" + tag + "_kernel_stats.txt", CMD + b2 + " --streams 1   (MI355X; config 2, one batch at a time)")
     stats(o + "/stats3", prof + "/" + tag + "_kernel_stats_pipelined.txt", CMD + b2 + "   (MI355X; config 2, default: 3 batches in flight, kernels of different batches overlap)")
     stats(o + "/stats_c3", prof + "/" + tag + "_assemble_stats.txt", CMD + "--config 3 --regions 2000 --steps 5 --no-extras   (MI355X; config 3: 2000 assembly tiles per launch)")
-    stats(o + "/stats_c3e", prof + "/" + tag + "_config3_end_to_end_stats.txt", CMD + "--config 3 --regions 2000 --steps 1   (MI355X; config 3 incl. END TO END: 2000 regions through the native region loop with --assemble=1, 32 regions per chunk)")
-    stats(o + "/stats_c5", prof + "/" + tag + "_config5_stats.txt", CMD + "--config 5 --windows 200 --steps 10 --warmup 2   (MI355X; config 5: 200 windows x 100 samples per step)")
+    stats(o + "/stats_c3e", prof + "/" + tag + "_config3_end_to_end_stats.txt", CMD + "--config 3 --regions 2000 --steps 1 --full   (MI355X; config 3 incl. END TO END: 2000 regions through the native region loop with --assemble=1, 32 regions per chunk)")
+    stats(o + "/stats_c5", prof + "/" + tag + "_config5_stats.txt", CMD + "--config 5 --windows 200 --steps 10 --warmup 2 --full   (MI355X; config 5: 200 windows x 100 samples per step, incl. end to end)")
     stats(o + "/stats_c4", prof + "/" + tag + "_config4_stats.txt", CMD + C4 + "   (MI355X; config 4: 12 288 regions x 100 kb of the synthetic genome, inputs resident in HBM, through the native region loop, 24 host threads x 128 regions per chunk as the whole-genome line runs: one serialized counting pass, two warm rounds and one timed pass; avg_us is stretched by the kernels of the other chunks running at the same time -- " + tag + "_config4_overlap.json says how many)")
     stats(o + "/nextk", prof + "/" + tag + "_next_kernels.txt", "rocprofv3 --kernel-trace --stats --output-format csv -- python tools/next_kernels.py   (MI355X; the kernels of the SURVEY 8(f) \"next\" rows on their own, sizes in the script)")
     stats(o + "/stats_c4solo", prof + "/" + tag + "_config4_stats_one_worker.txt", CMD + C4SOLO + "   (MI355X; config 4 with ONE host worker: no two kernels of the loop ever share the chip, avg_us = the kernel by itself on a chunk of 128 regions -- what bench.py's live timers (kernel_time_ranking) measure in its counting pass and what the line's roofline is computed from)")
