@@ -341,6 +341,26 @@ cdef extern from "platypus_mi355x.h":
     int plat_read_buffers_batch(plat_ctx* ctx, const plat_read_buffers_in* inp, const plat_readqc_options* options, int32_t* out_ok,
                                 int32_t* out_reason, int32_t* out_perm, int32_t* out_counts, const plat_read_buffers_tables* tab,
                                 void* stream) nogil
+    # ---- read tables from raw BAM alignment records: ReadIterator.get (htslibWrapper.pyx:328-406) on the device
+    ctypedef struct plat_bam_decode_out:
+        int64_t cap_bases
+        int64_t cap_pairs
+        int64_t* read_off
+        int32_t* cig_off
+        uint8_t* seq
+        uint8_t* qual
+        int16_t* cigar
+        int32_t* pos
+        int32_t* end
+        uint8_t* mapq
+        int32_t* flags
+        int16_t* chrom_id
+        int16_t* mate_chrom_id
+        int32_t* insert_size
+        int32_t* mate_pos
+        int64_t* status
+    int plat_bam_decode_batch(plat_ctx* ctx, int n_records, const uint8_t* blob, int64_t blob_len, const int64_t* rec_off,
+                              const int64_t* rec_limit, const plat_bam_decode_out* out, void* stream) nogil
     # the same for a PLAT_READS_PACKED table (one byte per base + exceptions): QC and trimming on the packed bytes, no quality array
     ctypedef struct plat_read_buffers_packed_in:
         plat_readqc_batch qc
@@ -468,3 +488,26 @@ cdef extern from "platypus_caller_fetched.h":
     int plat_call_fetched_regions(plat_caller* c, const plat_fetched_region* regions, int n_regions, int n_samples,
                                   const char* const* sample_names, plat_caller_options* options, const plat_caller_qc_options* qc,
                                   char** out_text, size_t* out_len, plat_fetched_region_info* info, plat_caller_stats* stats) nogil
+
+# The region loop fed with raw BAM alignment records (include/platypus_caller_bam.h): what the integrator holds after sam_itr_next,
+# decoded on the device (plat_bam_decode_batch).
+cdef extern from "platypus_caller_bam.h":
+    ctypedef struct plat_bam_records:
+        int32_t n_records
+        const uint8_t* data
+        int64_t data_len
+        const int64_t* rec_off
+    ctypedef struct plat_bam_sample:
+        plat_bam_records fetched
+        plat_bam_records broken_mates
+    ctypedef struct plat_bam_region:
+        const char* chrom
+        int32_t start
+        int32_t end
+        const uint8_t* contig_seq
+        int64_t contig_len
+        const plat_bam_sample* samples
+        const uint8_t* dev_contig_seq
+    int plat_call_bam_regions(plat_caller* c, const plat_bam_region* regions, int n_regions, int n_samples,
+                              const char* const* sample_names, plat_caller_options* options, const plat_caller_qc_options* qc,
+                              char** out_text, size_t* out_len, plat_fetched_region_info* info, plat_caller_stats* stats) nogil

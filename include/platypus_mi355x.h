@@ -567,6 +567,60 @@ int plat_read_buffers_packed_batch(plat_ctx* ctx, const plat_read_buffers_packed
                                    int32_t* out_reason, int32_t* out_perm, int32_t* out_counts,
                                    const plat_read_buffers_tables* tab /* may be NULL; tab.qual unused */, void* stream);
 
+/* ---- read tables from raw BAM alignment records ---------------------------------------------------------
+ * Replaces  ReadIterator.get   htslibWrapper.pyx:328-406   (what the loader does with every record sam_itr_next returns: three
+ *           mallocs, 4-bit code -> letter, quality bytes copied, CIGAR words unpacked, pos moved over a leading soft clip, bam_endpos)
+ * for n_records uncompressed BAM alignment records lying anywhere in one byte blob.  Record i starts at blob[rec_off[i]]; rec_off need
+ * not be ascending or gap-free, and nothing is assumed about alignment (the CIGAR words are in general not 4-byte aligned).
+ *
+ * A record is the alignment block of the SAM/BAM specification section 4.2, little-endian, STARTING AT refID (the 4-byte block_size is
+ * not part of it):
+ *     0 refID int32 | 4 pos int32 | 8 l_read_name uint8 | 9 mapq uint8 | 10 bin uint16 | 12 n_cigar_op uint16 | 14 flag uint16 |
+ *     16 l_seq int32 | 20 next_refID int32 | 24 next_pos int32 | 28 tlen int32 | 32 read_name[l_read_name] |
+ *     cigar[n_cigar_op] uint32, each len << 4 | op | seq[(l_seq + 1) / 2], high nibble first | qual[l_seq] | aux data (ignored)
+ * Its extent is what its own fields say.  rec_limit (optional, [n_records]): record i must end at or before blob[rec_limit[i]] -- for a
+ * blob made of several callers' blobs back to back, where a record must not run into the next one's bytes.
+ *
+ * Decode rules (get, restated):
+ *   seq[i]  = "=ACMGRSVTWYHKDBN"[nibble i] (:363-365, _getBase); qual[i] = the raw byte (:366; get asserts qual <= 93 at :367,
+ *             here a larger byte is passed through as it is, as the ASCII fetched path takes it)
+ *   cigar   = (op, len) int16 pairs (:373-380)
+ *   flags = flag, mapq = mapq, chrom_id = refID, mate_chrom_id = next_refID, mate_pos = next_pos, insert_size = tlen (:393-402)
+ *   pos     = the record's pos, minus the length of the FIRST CIGAR operation when that is S (op 4) (:372,386-387,397); a leading H followed
+ *             by S does not move it
+ *   end     = bam_endpos (:398) of the htslib the reference declares (bit-field bam1_core_t and `int32_t bam_endpos` of
+ *             htslibWrapper.pxd:116-183: an htslib 1.x before 1.10): the record's pos + 1 when flag & 4 or n_cigar_op == 0, else
+ *             the record's pos + the summed lengths of the operations M, D, N, = and X -- a sum that may be 0: a mapped record whose
+ *             CIGAR consumes no reference gets end == its pos.  (htslib from 1.10 on returns pos + 1 there.)  end counts from the
+ *             record's own pos, not the soft-clip-adjusted one, and is kept in 32 bits as bam_endpos returns it.
+ * Refused (status PLAT_ERR_BAD_INPUT; the record then decodes to an empty read: read_off[i+1] == read_off[i], its per-read fields
+ * are not written) -- where get returns NULL (:334-338; loadBAMData, platypusutils.pyx:510-513, dereferences it) or cAlignedRead's
+ * `short` fields (htslibWrapper.pxd:187-201) would silently wrap:
+ *   a record that runs past the blob or its rec_limit (or rec_off < 0); l_seq <= 0; qual[0] == 0xff; l_seq, a CIGAR length, refID or next_refID above
+ *   32767 (refID / next_refID below -32768); n_cigar_op above 32767; a CIGAR op above 8; pos after the soft-clip shift outside int32.
+ *
+ * Output: a plat_read_buffers_in without further work -- read_off [n+1] (from 0) and cig_off [n+1] by a device-wide scan of the
+ * records' lengths, seq / qual [cap_bases + PLAT_BLOB_PAD] (the PLAT_BLOB_PAD bytes behind the last base are zeroed), cigar
+ * [2 * cap_pairs], and the per-read arrays [n].  seq and qual must be 16-byte aligned.  The capacities are checked on the device: more
+ * bases than cap_bases or more pairs than cap_pairs is status PLAT_ERR_OVERFLOW and no base, quality or pair is written.  A caller
+ * can bound them without reading a record: every record has 32 fixed bytes and 1.5 bytes per base, so
+ *   bases <= (blob_len - 32 n) * 2 / 3 + n   and   pairs <= (blob_len - 32 n) / 4   (records that do not overlap).
+ * status [4] (device, written by the call): {0 or the error, the index of the first offending record (lowest index; for
+ * PLAT_ERR_OVERFLOW the first record that does not fit) or -1, total bases, total pairs}.  A record error wins over an overflow.
+ * The call enqueues three kernels (per-record parse, scan, expansion: 16 bases per lane, the record's bytes loaded as the aligned
+ * words that cover them) and does not wait; errors are reported through status only, nothing traps.                           */
+typedef struct plat_bam_decode_out {
+    int64_t cap_bases, cap_pairs;
+    int64_t* read_off; int32_t* cig_off;
+    uint8_t* seq; uint8_t* qual; int16_t* cigar;
+    int32_t* pos; int32_t* end; uint8_t* mapq; int32_t* flags;
+    int16_t* chrom_id; int16_t* mate_chrom_id; int32_t* insert_size; int32_t* mate_pos;
+    int64_t* status;
+} plat_bam_decode_out;
+
+int plat_bam_decode_batch(plat_ctx* ctx, int n_records, const uint8_t* blob, int64_t blob_len, const int64_t* rec_off,
+                          const int64_t* rec_limit /* may be NULL */, const plat_bam_decode_out* out, void* stream);
+
 /* ---- read statistics of the VCF INFO field ---------------------------------------
  * Replaces the per-variant loop over a window's reads in  cdef dict vcfINFO(...)   vcfutils.pyx:1300-1390
  * (readOverlapsVariant :901-913, readQualIsGoodVariantPosition :917-943, variantSupportedByRead :961-1072).

@@ -101,6 +101,12 @@ class ReadBuffersTables(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("off", "cig_off", "seq", "qual", "cigar", "pos", "end", "mapq", "flags", "mate_pos")]
 
 
+class BamDecodeOut(C.Structure):
+    _fields_ = [("cap_bases", C.c_int64), ("cap_pairs", C.c_int64)] + [(k, C.c_void_p) for k in (
+        "read_off", "cig_off", "seq", "qual", "cigar", "pos", "end", "mapq", "flags", "chrom_id", "mate_chrom_id", "insert_size", "mate_pos",
+        "status")]
+
+
 class InfoStatsBatch(C.Structure):
     _fields_ = [("n_vars", C.c_int32), ("n_ind", C.c_int32)] + [(k, C.c_void_p) for k in (
         "var_window", "var_pos", "var_bam_min", "var_bam_max", "var_n_added", "var_n_removed", "var_added", "var_added_off",
@@ -169,6 +175,7 @@ SIGNATURES = {
                                           C.c_void_p, C.POINTER(ReadBuffersTables), C.c_void_p]),
     "plat_read_buffers_packed_batch": (C.c_int, [C.c_void_p, C.POINTER(ReadBuffersPackedIn), C.POINTER(ReadQCOptions), C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.POINTER(ReadBuffersTables), C.c_void_p]),
+    "plat_bam_decode_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(BamDecodeOut), C.c_void_p]),
     "plat_variant_read_stats_batch": (C.c_int, [C.c_void_p, C.POINTER(InfoStatsBatch), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
     "plat_variant_info_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -182,7 +189,7 @@ SIGNATURES = {
 
 # entry points a stand-in library built against an earlier header may lack (the CPU suite's fake device): bind() leaves them
 # unbound there; load() still requires every declared symbol of the real library
-ADDED_LATER = ("plat_read_buffers_batch", "plat_read_buffers_packed_batch")
+ADDED_LATER = ("plat_read_buffers_batch", "plat_read_buffers_packed_batch", "plat_bam_decode_batch")
 
 _lib = None
 

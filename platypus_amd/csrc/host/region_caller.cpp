@@ -701,3 +701,4 @@ CALLER_EXPORT void plat_caller_debug_set_order(const char* names, char* out, siz
     snprintf(out, cap, "%s", t.c_str());
 }
 #include "fetched_regions.hpp"
+#include "bam_regions.hpp"

@@ -547,6 +547,49 @@ class Engine:
             out.append(res)
         return out
 
+    def bam_decode(self, blob, rec_off, cap_bases=None, cap_pairs=None, rec_limit=None, check=True):
+        """plat_bam_decode_batch: ReadIterator.get (htslibWrapper.pyx:328-406) on the device.  blob: the bytes (uint8 array or bytes) holding
+        uncompressed BAM alignment records, record i starting (at its refID) at blob[rec_off[i]].  Returns a dict of numpy arrays: off
+        [n+1], cig_off [n+1], seq / qual [bases], cigar [pairs, 2], pos, end, mapq, flags, chrom_id, mate_chrom_id, insert_size, mate_pos
+        [n], status [4] = {error, first offending record, bases, pairs}, and guard_intact: nothing was written behind the capacities (the
+        PLAT_BLOB_PAD zeros behind the last base aside).  cap_bases / cap_pairs default to the bound the blob's length gives.  A refused
+        record or a short capacity raises PlatypusDeviceError (check=False: returns, with status saying so)."""
+        torch = _torch()
+        blob = np.frombuffer(blob, dtype=np.uint8) if isinstance(blob, (bytes, bytearray)) else np.ascontiguousarray(blob, dtype=np.uint8)
+        rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
+        n, nbytes = len(rec_off), len(blob)
+        body = max(0, nbytes - 32 * n)
+        cap_b = body * 2 // 3 + n if cap_bases is None else int(cap_bases)
+        cap_p = body // 4 if cap_pairs is None else int(cap_pairs)
+        guard, fill = 64, 0xEE
+        d_blob = torch.from_numpy(np.append(blob, np.zeros(1, np.uint8))).to(self.device)
+        d_off = torch.from_numpy(np.append(rec_off, 0)).to(self.device)
+        d_lim = torch.from_numpy(np.append(np.ascontiguousarray(rec_limit, dtype=np.int64), 0)).to(self.device) if rec_limit is not None else None
+        e = lambda k, dt: torch.full((k,), fill if dt in (torch.uint8,) else 0, dtype=dt, device=self.device)
+        g = dict(read_off=e(n + 1, torch.int64), cig_off=e(n + 1, torch.int32), seq=e(cap_b + _lib.PLAT_BLOB_PAD + guard, torch.uint8),
+                 qual=e(cap_b + _lib.PLAT_BLOB_PAD + guard, torch.uint8), cigar=torch.full((2 * cap_p + guard,), 0x7EEE, dtype=torch.int16, device=self.device),
+                 pos=e(max(n, 1), torch.int32), end=e(max(n, 1), torch.int32), mapq=e(max(n, 1), torch.uint8), flags=e(max(n, 1), torch.int32),
+                 chrom_id=e(max(n, 1), torch.int16), mate_chrom_id=e(max(n, 1), torch.int16), insert_size=e(max(n, 1), torch.int32),
+                 mate_pos=e(max(n, 1), torch.int32), status=e(4, torch.int64))
+        o = _lib.BamDecodeOut(cap_b, cap_p, *[g[k].data_ptr() for k, _ in _lib.BamDecodeOut._fields_[2:]])
+        _lib.check(self.lib.plat_bam_decode_batch(self.ctx, n, d_blob.data_ptr(), nbytes, d_off.data_ptr(), d_lim.data_ptr() if d_lim is not None else None,
+                                                  C.byref(o), self._stream()), "plat_bam_decode_batch")
+        self._sync()
+        h = {k: v.cpu().numpy() for k, v in g.items()}
+        st = h["status"]
+        fits = int(st[0]) != -8
+        nb, npairs = (int(st[2]), int(st[3])) if fits else (0, 0)
+        tail = h["seq"][nb:], h["qual"][nb:]
+        pad = _lib.PLAT_BLOB_PAD if fits else 0
+        intact = all(not t[:pad].any() and (t[pad:] == fill).all() for t in tail) and bool((h["cigar"][2 * npairs:] == 0x7EEE).all())
+        out = dict(off=h["read_off"], cig_off=h["cig_off"], seq=h["seq"][:nb], qual=h["qual"][:nb], cigar=h["cigar"][:2 * npairs].reshape(-1, 2),
+                   status=st, guard_intact=intact)
+        for k in ("pos", "end", "mapq", "flags", "chrom_id", "mate_chrom_id", "insert_size", "mate_pos"):
+            out[k] = h[k][:n]
+        if check and int(st[0]) != 0:
+            raise _lib.PlatypusDeviceError(int(st[0]), "record %d" % int(st[1]), "plat_bam_decode_batch")
+        return out
+
     # ---- SURVEY 8(f) rank 3: read statistics of the VCF INFO field --------------------------------------------
     def variant_read_stats(self, windows, bad_reads_window=11, exact=0):
         """vcfINFO's per-read loop for a list of windows.  A window: dict {variants: [dict(pos, removed, added, bam_min,

@@ -7,7 +7,8 @@
 text platypus_amd.caller.callVariantsInRegions writes (tests/test_native_caller_*.py compare the two).  The library
 is host code on top of libplat_mi355x.so; like the rest of the package it has no CPU fallback.
 `FetchedRegion` / `NativeCaller.call_fetched_regions` take the reads as a BAM fetch returns them instead (the loader's
-addReadToBuffer QC and split run on the device, cwindow.pyx:560-595)."""
+addReadToBuffer QC and split run on the device, cwindow.pyx:560-595); `BamRegion` / `NativeCaller.call_bam_regions` take the raw BAM
+alignment records (include/platypus_caller_bam.h: ReadIterator.get, htslibWrapper.pyx:328-406, runs on the device too)."""
 import ctypes as C
 import os
 import subprocess
@@ -121,6 +122,19 @@ class CallerQCOptions(C.Structure):
 
 class _FetchedRegionInfo(C.Structure):
     _fields_ = [("loaded", C.c_int32), ("sample_counts", C.c_void_p)]
+
+
+class _BamRecords(C.Structure):
+    _fields_ = [("n_records", C.c_int32), ("data", C.c_void_p), ("data_len", C.c_int64), ("rec_off", C.c_void_p)]
+
+
+class _BamSample(C.Structure):
+    _fields_ = [("fetched", _BamRecords), ("broken_mates", _BamRecords)]
+
+
+class _BamRegion(C.Structure):
+    _fields_ = [("chrom", C.c_char_p), ("start", C.c_int32), ("end", C.c_int32), ("contig_seq", C.c_void_p),
+                ("contig_len", C.c_int64), ("samples", C.POINTER(_BamSample)), ("dev_contig_seq", C.c_void_p)]
 
 
 class ReadTable:
@@ -253,6 +267,40 @@ class FetchedRegion:
         a.start, a.end = self.start, self.end
 
 
+class BamRegion:
+    """One region as the integrator holds it after sam_itr_next (include/platypus_caller_bam.h): per sample the uncompressed BAM alignment
+    records of the fetch, in fetch order, and of the broken mates, in mate-position order -- each as (data uint8 array, rec_off int64
+    array), record i starting at its refID at data[rec_off[i]]."""
+
+    def __init__(self, chrom, start, end, contig_seq, samples):
+        self.chrom, self.start, self.end = chrom, int(start), int(end)
+        self.contig = np.ascontiguousarray(np.frombuffer(contig_seq, dtype=np.uint8) if isinstance(contig_seq, (bytes, bytearray)) else contig_seq,
+                                           dtype=np.uint8)
+        c = lambda t: (np.ascontiguousarray(t[0], dtype=np.uint8), np.ascontiguousarray(t[1], dtype=np.int64))
+        self.samples = [(c(f), c(b)) for f, b in samples]    # [((data, rec_off) fetched, (data, rec_off) broken mates)]
+        self._c = None
+
+    @classmethod
+    def from_reads(cls, chrom, start, end, fasta, samples, **layout):
+        """samples: per sample (fetched, brokenMates), lists of hostapi.AlignedRead as FetchedRegion.from_reads takes them, encoded as
+        records (synth.bam_records; **layout: its names / aux / lead / block_size).  The broken mates are listed in mate-position order."""
+        from . import synth
+        return cls(chrom, start, end, fasta._seq[chrom],
+                   [(synth.bam_records(fetched, **layout), synth.bam_records(sorted(broken, key=lambda r: r.matePos))) for fetched, broken in samples])
+
+    def fill(self, a, n_samples):
+        """Write this region into the plat_bam_region `a` (the arrays stay owned by, and alive with, this object)."""
+        assert len(self.samples) == n_samples
+        if self._c is None:
+            ss = (_BamSample * len(self.samples))()
+            for i, pair in enumerate(self.samples):
+                for t, (data, off) in zip((ss[i].fetched, ss[i].broken_mates), pair):
+                    t.n_records, t.data, t.data_len, t.rec_off = len(off), data.ctypes.data, len(data), off.ctypes.data
+            self._c = (self.chrom.encode(), self.contig.ctypes.data, len(self.contig), ss)
+        a.chrom, a.contig_seq, a.contig_len, a.samples = self._c
+        a.start, a.end = self.start, self.end
+
+
 def region_from_arrays(reg, pin=False, packed=False):
     """RegionReads of a synth.config4_region_arrays() region (every read in `reads`; no badReads / brokenMates)."""
     empty = ReadTable([], [], [0], [], [], [], [], [], [], [0])
@@ -334,6 +382,9 @@ def _bind(lib):
     lib.plat_call_fetched_regions.argtypes = [C.c_void_p, C.POINTER(_FetchedRegion), C.c_int, C.c_int, C.POINTER(C.c_char_p), C.POINTER(CallerOptions),
                                               C.POINTER(CallerQCOptions), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(_FetchedRegionInfo),
                                               C.POINTER(CallerStats)]
+    lib.plat_call_bam_regions.argtypes = [C.c_void_p, C.POINTER(_BamRegion), C.c_int, C.c_int, C.POINTER(C.c_char_p), C.POINTER(CallerOptions),
+                                          C.POINTER(CallerQCOptions), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(_FetchedRegionInfo),
+                                          C.POINTER(CallerStats)]
     lib.plat_merge_record_texts.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     lib.plat_caller_region_text_lengths.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     lib.plat_merge_region_blocks.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
@@ -547,14 +598,19 @@ class NativeCaller:
         self.stats = st.as_dict()
         return out
 
-    def call_fetched_regions(self, regions, sample_names, options):
+    def call_bam_regions(self, regions, sample_names, options):
+        """regions: list of BamRegion.  As call_fetched_regions, with ReadIterator.get (htslibWrapper.pyx:328-406) on the device in front: the
+        records are uploaded as they are and decoded there (plat_bam_decode_batch); the same text, rlen, self.loaded and self.read_counts."""
+        return self.call_fetched_regions(regions, sample_names, options, _entry="plat_call_bam_regions", _struct=_BamRegion)
+
+    def call_fetched_regions(self, regions, sample_names, options, _entry="plat_call_fetched_regions", _struct=_FetchedRegion):
         """regions: list of FetchedRegion.  The loader's work (addReadToBuffer's QC and split, isSorted, maxReads) on the device, then the
         region loop as call_regions runs it; the QC options come from the same `options`.  Returns the record lines (str); options.rlen is
         updated as the reference updates it.  self.loaded[k] (0: region k reached maxReads and was not called) and self.read_counts[k]
         (int32 [n_samples, 10]: n_good, n_bad, the 8 reason counts -- filteredReadCountsByType slots 0-6 and secondary alignments) describe
         the last call."""
         n, nS = len(regions), len(sample_names)
-        arr = (_FetchedRegion * max(n, 1))()
+        arr = (_struct * max(n, 1))()
         for k, r in enumerate(regions):
             r.fill(arr[k], nS)
         names = (C.c_char_p * nS)(*[s.encode() for s in sample_names])
@@ -564,9 +620,9 @@ class NativeCaller:
         for k in range(n):
             info[k].sample_counts = counts[k].ctypes.data
         text, length, st = C.c_void_p(), C.c_size_t(), CallerStats()
-        rc = self.lib.plat_call_fetched_regions(self.h, arr, n, nS, names, C.byref(o), C.byref(q), C.byref(text), C.byref(length), info, C.byref(st))
+        rc = getattr(self.lib, _entry)(self.h, arr, n, nS, names, C.byref(o), C.byref(q), C.byref(text), C.byref(length), info, C.byref(st))
         if rc != 0:
-            raise _lib.PlatypusDeviceError(rc, (self.lib.plat_caller_last_error(self.h) or b"").decode(), "plat_call_fetched_regions")
+            raise _lib.PlatypusDeviceError(rc, (self.lib.plat_caller_last_error(self.h) or b"").decode(), _entry)
         try:
             out = C.string_at(text, length.value).decode("ascii")
         finally:

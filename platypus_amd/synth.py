@@ -513,3 +513,50 @@ def config4_fetched_region(index, seed=4711, region_len=100000, n_samples=1, **k
         reads.sort(key=lambda r: r.pos)
         samples.append(reads)
     return reg, samples
+
+
+BAM_LETTERS = b"=ACMGRSVTWYHKDBN"           # 4-bit base code -> letter (SAM/BAM specification 4.2.3; htslib's seq_nt16_str)
+
+
+_BAM_CODES = bytes(BAM_LETTERS.find(bytes([b])) & 0xff for b in range(256))       # letter -> code, 255 for a letter outside the table
+
+
+def bam_record(read, name=b"r\0", aux=b"", bin_=0):
+    """The uncompressed BAM alignment record of a hostapi.AlignedRead: the alignment block of the SAM/BAM specification 4.2,
+    little-endian, from refID on (no block_size) -- the inverse of plat_bam_decode_batch's decode rules.  `read.pos` is a
+    cAlignedRead.pos, already moved back over a leading soft clip (htslibWrapper.pyx:386-387), so the record's pos is read.pos + the
+    length of a leading S.  `read.end` is not stored (a BAM record has no end: the decoder derives it from pos and the CIGAR).
+    name: the read_name bytes as they lie in the record (1-255, NUL included); aux: bytes behind the qualities."""
+    import struct
+    seq, qual, cig = read.seq, read.qual, read.cigarOps
+    if not 1 <= len(name) <= 255:
+        raise ValueError("read_name holds 1-255 bytes")
+    if len(seq) == 0 or len(seq) != len(qual):
+        raise ValueError("a record has bases, and as many qualities")
+    if len(cig) > 65535 or any(not (0 <= op <= 15 and 0 <= ln < (1 << 28)) for op, ln in cig):
+        raise ValueError("CIGAR does not fit a BAM record")
+    codes = np.frombuffer(seq.translate(_BAM_CODES) + (b"\0" if len(seq) & 1 else b""), dtype=np.uint8)
+    if codes.max() > 15:
+        raise ValueError("a base outside %s" % BAM_LETTERS.decode())
+    pos = read.pos + (cig[0][1] if cig and cig[0][0] == 4 else 0)
+    core = struct.pack("<iiBBHHHiiii", read.chromID, pos, len(name), read.mapq, bin_, len(cig), read.bitFlag, len(seq), read.mateChromID,
+                       read.matePos, read.insertSize)
+    return (core + bytes(name) + b"".join(struct.pack("<I", (ln << 4) | op) for op, ln in cig) +
+            ((codes[0::2] << 4) | codes[1::2]).tobytes() + bytes(qual) + bytes(aux))
+
+
+def bam_records(reads, names=None, aux=None, lead=0, block_size=False):
+    """Records of `reads` (bam_record) back to back in one blob: (data uint8 array, rec_off int64 array).  names / aux: per read (default: a
+    two-byte name, no aux data); lead: bytes in front of the first record; block_size=True: every record is preceded by its 4-byte
+    block_size, as in an inflated BGZF stream, with rec_off pointing past it."""
+    import struct
+    parts, off, at = [b"\xa5" * lead], [], lead
+    for i, r in enumerate(reads):
+        rec = bam_record(r, names[i] if names is not None else b"r\0", aux[i] if aux is not None else b"")
+        if block_size:
+            parts.append(struct.pack("<i", len(rec)))
+            at += 4
+        off.append(at)
+        parts.append(rec)
+        at += len(rec)
+    return np.frombuffer(b"".join(parts), dtype=np.uint8).copy(), np.array(off, dtype=np.int64)

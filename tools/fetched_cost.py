@@ -9,6 +9,13 @@ plat_read_buffers_packed_batch).
 The kernels on their own (k_read_qc or k_read_qc_packed, k_read_split, k_read_gather against the chunk's other kernels), in a run of
 their own:
     rocprofv3 --kernel-trace --stats -d OUT -- python tools/fetched_cost.py --reps 1 [--packed]
+
+--bam: the three ways to hand fetched reads over, in one run: plat_call_fetched_regions on ASCII tables ("fetched_ascii") and on packed
+tables ("fetched_packed"), and plat_call_bam_regions on the raw BAM alignment records of the same reads ("bam": ReadIterator.get on the
+device, plat_bam_decode_batch) -- wall time, process CPU per region and input bytes of each.  The reads' `end` is the decode rule's
+(a record holds none), for all three.  Under rocprofv3 the same run gives k_bam_core / k_bam_scan / k_bam_expand next to k_unpack_pieces
+(the packed call expands a table of the same bases); "bam_expand_bytes" / "unpack_pieces_bytes" are their algorithmic bytes (3.5 and 3
+per base).
 """
 import argparse
 import copy
@@ -31,7 +38,10 @@ def main():
     ap.add_argument("--workers", type=int, default=4)
     ap.add_argument("--per-chunk", type=int, default=4)
     ap.add_argument("--packed", action="store_true", help="PLAT_READS_PACKED tables for both calls")
+    ap.add_argument("--bam", action="store_true", help="ASCII fetched, packed fetched and raw BAM records in one run")
     a = ap.parse_args()
+    if a.bam:
+        return bam_main(a)
     opts = default_options()
     enabled = (opts.filterReadsWithUnmappedMates, opts.filterReadsWithDistantMates, opts.filterReadPairsWithSmallInserts, opts.filterDuplicates)
     fetched, split, n_reads, n_bytes = [], [], 0, 0
@@ -66,6 +76,48 @@ def main():
         # (packed: one byte per base for both, the gather's bases and qualities in one byte; exceptions left out)
         out["read_buffers_bytes"] = dict(qc=n_bytes + 40 * n_reads, split=20 * n_reads, gather=(2 if a.packed else 4) * n_bytes + 60 * n_reads)
         out["same_text"] = out["pre_split"]["text_bytes"] == out["fetched"]["text_bytes"]
+    finally:
+        nc.close()
+    print(json.dumps(out))
+
+
+def bam_main(a):
+    ascii_, packed, bam, n_reads, n_bytes = [], [], [], 0, 0
+    for i in range(a.regions):
+        reg, samples = synth.config4_fetched_region(i, region_len=a.region_len)
+        fasta = H.FastaFile({reg["chrom"]: reg["ref"].tobytes()})
+        for rs in samples:
+            for r in rs:                                                 # bam_endpos as plat_bam_decode_batch states it
+                clip = r.cigarOps[0][1] if r.cigarOps and r.cigarOps[0][0] == 4 else 0
+                r.end = r.pos + clip + (1 if (r.bitFlag & 4) or not r.cigarOps else sum(ln for op, ln in r.cigarOps if op in (0, 2, 3, 7, 8)))
+            n_reads += len(rs)
+            n_bytes += sum(r.rlen for r in rs)
+        pairs = [(rs, []) for rs in samples]
+        ascii_.append(F.FetchedRegion.from_reads(reg["chrom"], reg["start"], reg["end"], fasta, pairs))
+        packed.append(F.FetchedRegion.from_reads(reg["chrom"], reg["start"], reg["end"], fasta, pairs, packed=True))
+        # names as a sequencer writes them (~40 bytes) and an aux block of the usual tags' size: what rides along on the link
+        names = [[("HWI-ST1234:100:C1ABCACXX:%d:%04d:%05d" % (1 + k % 8, k % 2316, k % 99991)).encode() + b"\0" for k in range(len(rs))] for rs in samples]
+        aux = [[b"NMC\x00MDZ150\x00ASC\x96XSC\x00RGZgrp1\x00"] * len(rs) for rs in samples]
+        bam.append(F.BamRegion(reg["chrom"], reg["start"], reg["end"], fasta._seq[reg["chrom"]],
+                               [(synth.bam_records(rs, names=nm, aux=ax, block_size=True), synth.bam_records([])) for rs, nm, ax in zip(samples, names, aux)]))
+    nc = F.NativeCaller(0, a.workers, a.per_chunk)
+    out = dict(regions=a.regions, region_len=a.region_len, reads=n_reads, read_bases=n_bytes)
+    texts = {}
+    try:
+        for name, call, regs in (("fetched_ascii", nc.call_fetched_regions, ascii_), ("fetched_packed", nc.call_fetched_regions, packed),
+                                 ("bam", nc.call_bam_regions, bam)):
+            best = None
+            for _ in range(a.reps):
+                o = default_options()
+                w0, c0 = time.perf_counter(), time.process_time()
+                texts[name] = call(regs, ["S1"], o)
+                w, c = time.perf_counter() - w0, time.process_time() - c0
+                if best is None or w < best[0]:
+                    best = (w, c, nc.stats["n_windows_called"], nc.stats["input_bytes"])
+            w, c, nw, ib = best
+            out[name] = dict(seconds=w, windows_per_sec=nw / w, cpu_seconds_per_region=c / a.regions, windows=nw, text_bytes=len(texts[name]), input_bytes=ib)
+        out["same_text"] = texts["bam"] == texts["fetched_ascii"] == texts["fetched_packed"]
+        out["bam_expand_bytes"], out["unpack_pieces_bytes"] = int(3.5 * n_bytes), 3 * n_bytes
     finally:
         nc.close()
     print(json.dumps(out))
