@@ -361,6 +361,37 @@ cdef extern from "platypus_mi355x.h":
         int64_t* status
     int plat_bam_decode_batch(plat_ctx* ctx, int n_records, const uint8_t* blob, int64_t blob_len, const int64_t* rec_off,
                               const int64_t* rec_limit, const plat_bam_decode_out* out, void* stream) nogil
+    # ---- BGZF blocks inflated on the device, and the BAM iterator over the inflated bytes (sam_itr_next)
+    ctypedef struct plat_bgzf_inflate_out:
+        int64_t cap_bytes
+        uint8_t* data
+        int64_t* out_off
+        int64_t* status
+    int plat_bgzf_inflate_batch(plat_ctx* ctx, int n_blocks, const uint8_t* blob, int64_t blob_len, const int64_t* blk_off,
+                                const int64_t* blk_limit, const plat_bgzf_inflate_out* out, void* stream) nogil
+    ctypedef struct plat_bam_find_in:
+        int32_t n_streams
+        int32_t n_chunks
+        int32_t n_blocks
+        int32_t _pad
+        const uint8_t* data
+        const int64_t* out_off
+        const int32_t* stream_chunk_begin
+        const int32_t* chunk_blk_first
+        const int32_t* chunk_blk_end
+        const int32_t* chunk_first_uoffset
+        const int32_t* chunk_stop_blk
+        const int32_t* chunk_stop_uoffset
+        const int32_t* tid
+        const int32_t* beg
+        const int32_t* end
+    ctypedef struct plat_bam_find_out:
+        int64_t cap_records
+        int64_t* rec_off
+        int64_t* rec_limit
+        int32_t* stream_begin
+        int64_t* status
+    int plat_bam_find_records(plat_ctx* ctx, const plat_bam_find_in* inp, const plat_bam_find_out* out, void* stream) nogil
     # the same for a PLAT_READS_PACKED table (one byte per base + exceptions): QC and trimming on the packed bytes, no quality array
     ctypedef struct plat_read_buffers_packed_in:
         plat_readqc_batch qc
@@ -511,3 +542,31 @@ cdef extern from "platypus_caller_bam.h":
     int plat_call_bam_regions(plat_caller* c, const plat_bam_region* regions, int n_regions, int n_samples,
                               const char* const* sample_names, plat_caller_options* options, const plat_caller_qc_options* qc,
                               char** out_text, size_t* out_len, plat_fetched_region_info* info, plat_caller_stats* stats) nogil
+
+# The region loop fed with the BGZF blocks of an index lookup (include/platypus_caller_bgzf.h): inflated, iterated and decoded on the
+# device (plat_bgzf_inflate_batch, plat_bam_find_records, plat_bam_decode_batch).
+cdef extern from "platypus_caller_bgzf.h":
+    ctypedef struct plat_bgzf_chunk:
+        const uint8_t* data
+        int64_t data_len
+        int32_t first_uoffset
+        int64_t end_coffset
+        int32_t end_uoffset
+    ctypedef struct plat_bgzf_sample:
+        int32_t n_chunks
+        const plat_bgzf_chunk* chunks
+        plat_bam_records broken_mates
+    ctypedef struct plat_bgzf_region:
+        const char* chrom
+        int32_t start
+        int32_t end
+        const uint8_t* contig_seq
+        int64_t contig_len
+        const uint8_t* dev_contig_seq
+        int32_t tid
+        int32_t itr_beg
+        int32_t itr_end
+        const plat_bgzf_sample* samples
+    int plat_call_bgzf_regions(plat_caller* c, const plat_bgzf_region* regions, int n_regions, int n_samples,
+                               const char* const* sample_names, plat_caller_options* options, const plat_caller_qc_options* qc,
+                               char** out_text, size_t* out_len, plat_fetched_region_info* info, plat_caller_stats* stats) nogil

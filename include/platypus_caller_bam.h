@@ -25,7 +25,8 @@
  * caller stays usable.  plat_caller_stats.input_bytes counts the record bytes uploaded: the blobs as handed over, names and aux data
  * included -- more than either encoding of the fetched call puts on the link.  A library linked against a device library without
  * plat_bam_decode_batch returns PLAT_ERR_UNSUPPORTED.
- * Not handled: the CG-tag convention for CIGARs of more than 65535 operations, read groups, CRAM, and anything compressed.
+ * Not handled: the CG-tag convention for CIGARs of more than 65535 operations, read groups and CRAM.  For the compressed BGZF blocks
+ * of a BAM file, inflated and iterated on the device in front of this call, see platypus_caller_bgzf.h.
  */
 #ifndef PLATYPUS_CALLER_BAM_H
 #define PLATYPUS_CALLER_BAM_H

@@ -621,6 +621,86 @@ typedef struct plat_bam_decode_out {
 int plat_bam_decode_batch(plat_ctx* ctx, int n_records, const uint8_t* blob, int64_t blob_len, const int64_t* rec_off,
                           const int64_t* rec_limit /* may be NULL */, const plat_bam_decode_out* out, void* stream);
 
+/* ---- BGZF blocks inflated on the device ------------------------------------------------------------------
+ * Replaces  bgzf_read_block / inflate / crc32  of the loader (what stands between a BAM file's bytes and the records above) for n_blocks
+ * BGZF blocks lying anywhere in one byte blob.  blk_off[i] is the offset of block i's first byte (0x1f); blk_limit (optional): block i
+ * must end at or before blob[blk_limit[i]].
+ *
+ * A block is RFC 1952 + SAM specification 4.1: 1f 8b 08, FLG == 4 (FEXTRA and nothing else), MTIME / XFL / OS ignored, XLEN, the extra
+ * subfields walked for `BC` with SLEN 2 (BSIZE = block length - 1) wherever it stands among them, the deflate data up to 8 bytes before
+ * the block's end, then CRC32 and ISIZE, little-endian.  ISIZE <= 65536; ISIZE 0 (the EOF block) is valid and yields nothing.  Inflate is
+ * RFC 1951 in full: stored, fixed and dynamic blocks, several deflate blocks per BGZF block, distances up to 32768 inside the block's
+ * own output.  The CRC32 is computed on the device over the inflated bytes.
+ *
+ * Refused (status PLAT_ERR_BAD_INPUT; a block refused by its header takes no room in the output, one refused later keeps its ISIZE
+ * bytes of room and nothing is written there; the other blocks are inflated):
+ *   a block that runs past blob_len or its blk_limit (or blk_off < 0); a bad magic or FLG, malformed subfields or none that is BC; BSIZE
+ *   too small for header and trailer; ISIZE above 65536; block type 3; a stored LEN / NLEN mismatch; HLIT above 29 or HDIST above 29; an
+ *   over-subscribed code-length set or an incomplete one (other than a single one-bit code), no end-of-block code, a repeat code with
+ *   nothing to repeat, more code lengths than HLIT + HDIST; a symbol with no code, length symbols 286 / 287, distance symbols 30 / 31;
+ *   a distance that reaches before the block's output; input exhausted before the end-of-block symbol of the last deflate block; output
+ *   other than exactly ISIZE bytes; a CRC32 mismatch.
+ * Every loop is bounded by the block's input bits and ISIZE: no input makes a lane write outside [out_off[i], out_off[i + 1]), read
+ * outside its block, or spin.
+ *
+ * Output: data [cap_bytes + PLAT_BLOB_PAD], 16-byte aligned, the blocks' bytes back to back (the PLAT_BLOB_PAD bytes behind the last
+ * one zeroed); out_off [n_blocks + 1] from 0, a device scan of the ISIZEs.  More bytes than cap_bytes is PLAT_ERR_OVERFLOW and no
+ * payload byte is written (the blocks are still decoded and CRC-checked in LDS, so that a block error is found).
+ * status [4] (device): {0 or the error, the lowest offending block (for PLAT_ERR_OVERFLOW the first that does not fit) or -1, total
+ * inflated bytes, 0}.  A block error wins over an overflow.  The call enqueues four kernels (headers, scan, inflate: one wave per block
+ * with the block's 64 KiB window in LDS, status) and does not wait; nothing traps.                                              */
+typedef struct plat_bgzf_inflate_out {
+    int64_t cap_bytes;
+    uint8_t* data;
+    int64_t* out_off;
+    int64_t* status;
+} plat_bgzf_inflate_out;
+
+int plat_bgzf_inflate_batch(plat_ctx* ctx, int n_blocks, const uint8_t* blob, int64_t blob_len, const int64_t* blk_off,
+                            const int64_t* blk_limit /* may be NULL */, const plat_bgzf_inflate_out* out, void* stream);
+
+/* ---- the BAM iterator over inflated blocks -----------------------------------------------------------------
+ * Replaces  sam_itr_next  (htslibWrapper.pxd:175-177, htslibWrapper.pyx:312,412; the htslib 1.x before 1.10 the reference declares) for
+ * n_streams fetches over the output of plat_bgzf_inflate_batch (data, out_off; n_blocks blocks), without the host knowing an inflated
+ * offset.  Stream s is the chunks stream_chunk_begin[s] .. stream_chunk_begin[s + 1] of its index lookup, walked one after the other.
+ * Chunk c is the contiguous inflated bytes of blocks chunk_blk_first[c] .. chunk_blk_end[c] - 1; its first block_size word starts
+ * chunk_first_uoffset[c] bytes into them; it ends at offset chunk_stop_uoffset[c] of block chunk_stop_blk[c] (a block
+ * of the same chunk; -1: at the end of its bytes; never past them).  tid, beg, end [n_streams]: the iterator's
+ * window, 0-based half-open.
+ *
+ * The rule, per chunk, from its first offset on:
+ *   stop the chunk at or past its end or the end of its bytes; read block_size (int32); refuse the stream (PLAT_ERR_BAD_INPUT) when
+ *   block_size < 32 or the record runs past the chunk's bytes; t = refID, b = pos; when t != tid or b >= end the STREAM ends: the record
+ *   is not kept and nothing behind it is read, later chunks included (the iterator's `finished`); else e = b + (n_cigar_op ? the summed
+ *   lengths of M, D, N, = and X : 1) -- not bam_endpos: flag 4 plays no part and e may equal b -- and the record is kept when e > beg
+ *   (and end > b); either way continue at the next record.  A kept or skipped record whose CIGAR words do not lie inside its
+ *   block_size bytes refuses the stream too.  Records may span blocks: a chunk's bytes are contiguous.
+ *
+ * Output: rec_off / rec_limit [cap_records] for plat_bam_decode_batch (rec_off ascending per stream, pointing at refID past each
+ * block_size; rec_limit the record's end), the kept records of all streams back to back; stream_begin [n_streams + 1].  status [4]:
+ * {0 or the error, the lowest offending stream (for PLAT_ERR_OVERFLOW the first whose records do not fit cap_records) or -1, kept
+ * records, records walked}.  On PLAT_ERR_OVERFLOW stream_begin is clamped to cap_records and nothing is written behind it, while
+ * status[2] still counts every kept record: a caller can size its tables from it and call again (inflated bytes / 36 + 1 always
+ * suffices).  Three kernels (count, scan, write), one workgroup per stream, the stream staged through LDS; no wait, nothing traps.
+ * data must be followed by the PLAT_BLOB_PAD bytes plat_bgzf_inflate_batch zeroes.                                            */
+typedef struct plat_bam_find_in {
+    int32_t n_streams, n_chunks, n_blocks, _pad;
+    const uint8_t* data; const int64_t* out_off;
+    const int32_t* stream_chunk_begin;
+    const int32_t* chunk_blk_first; const int32_t* chunk_blk_end; const int32_t* chunk_first_uoffset;
+    const int32_t* chunk_stop_blk; const int32_t* chunk_stop_uoffset;
+    const int32_t* tid; const int32_t* beg; const int32_t* end;
+} plat_bam_find_in;
+
+typedef struct plat_bam_find_out {
+    int64_t cap_records;
+    int64_t* rec_off; int64_t* rec_limit;
+    int32_t* stream_begin;
+    int64_t* status;
+} plat_bam_find_out;
+
+int plat_bam_find_records(plat_ctx* ctx, const plat_bam_find_in* in, const plat_bam_find_out* out, void* stream);
+
 /* ---- read statistics of the VCF INFO field ---------------------------------------
  * Replaces the per-variant loop over a window's reads in  cdef dict vcfINFO(...)   vcfutils.pyx:1300-1390
  * (readOverlapsVariant :901-913, readQualIsGoodVariantPosition :917-943, variantSupportedByRead :961-1072).

@@ -107,6 +107,20 @@ class BamDecodeOut(C.Structure):
         "status")]
 
 
+class BgzfInflateOut(C.Structure):
+    _fields_ = [("cap_bytes", C.c_int64), ("data", C.c_void_p), ("out_off", C.c_void_p), ("status", C.c_void_p)]
+
+
+class BamFindIn(C.Structure):
+    _fields_ = [("n_streams", C.c_int32), ("n_chunks", C.c_int32), ("n_blocks", C.c_int32), ("_pad", C.c_int32)] + [(k, C.c_void_p) for k in (
+        "data", "out_off", "stream_chunk_begin", "chunk_blk_first", "chunk_blk_end", "chunk_first_uoffset", "chunk_stop_blk", "chunk_stop_uoffset",
+        "tid", "beg", "end")]
+
+
+class BamFindOut(C.Structure):
+    _fields_ = [("cap_records", C.c_int64), ("rec_off", C.c_void_p), ("rec_limit", C.c_void_p), ("stream_begin", C.c_void_p), ("status", C.c_void_p)]
+
+
 class InfoStatsBatch(C.Structure):
     _fields_ = [("n_vars", C.c_int32), ("n_ind", C.c_int32)] + [(k, C.c_void_p) for k in (
         "var_window", "var_pos", "var_bam_min", "var_bam_max", "var_n_added", "var_n_removed", "var_added", "var_added_off",
@@ -176,6 +190,8 @@ SIGNATURES = {
     "plat_read_buffers_packed_batch": (C.c_int, [C.c_void_p, C.POINTER(ReadBuffersPackedIn), C.POINTER(ReadQCOptions), C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.POINTER(ReadBuffersTables), C.c_void_p]),
     "plat_bam_decode_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(BamDecodeOut), C.c_void_p]),
+    "plat_bgzf_inflate_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(BgzfInflateOut), C.c_void_p]),
+    "plat_bam_find_records": (C.c_int, [C.c_void_p, C.POINTER(BamFindIn), C.POINTER(BamFindOut), C.c_void_p]),
     "plat_variant_read_stats_batch": (C.c_int, [C.c_void_p, C.POINTER(InfoStatsBatch), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
     "plat_variant_info_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -189,7 +205,7 @@ SIGNATURES = {
 
 # entry points a stand-in library built against an earlier header may lack (the CPU suite's fake device): bind() leaves them
 # unbound there; load() still requires every declared symbol of the real library
-ADDED_LATER = ("plat_read_buffers_batch", "plat_read_buffers_packed_batch", "plat_bam_decode_batch")
+ADDED_LATER = ("plat_read_buffers_batch", "plat_read_buffers_packed_batch", "plat_bam_decode_batch", "plat_bgzf_inflate_batch", "plat_bam_find_records")
 
 _lib = None
 

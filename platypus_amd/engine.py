@@ -590,6 +590,81 @@ class Engine:
             raise _lib.PlatypusDeviceError(int(st[0]), "record %d" % int(st[1]), "plat_bam_decode_batch")
         return out
 
+    def bgzf_inflate(self, blob, blk_off, cap_bytes=None, blk_limit=None, check=True, keep_device=False):
+        """plat_bgzf_inflate_batch: the BGZF blocks starting at blob[blk_off[i]] inflated and CRC-checked on the device.  Returns a dict: data
+        (the inflated bytes, back to back), out_off [n+1], status [4] = {error, lowest offending block, total bytes, 0} and guard_intact:
+        nothing was written in front of data or behind cap_bytes (the PLAT_BLOB_PAD zeros behind the last byte aside).  cap_bytes defaults to
+        the sum of the blocks' ISIZE words as a reader of the trailers finds them.  A refused block or a short capacity raises
+        PlatypusDeviceError (check=False: returns, with status saying so).  keep_device=True adds the device tensors (for bam_find_records)."""
+        torch = _torch()
+        blob = np.frombuffer(blob, dtype=np.uint8) if isinstance(blob, (bytes, bytearray)) else np.ascontiguousarray(blob, dtype=np.uint8)
+        blk_off = np.ascontiguousarray(blk_off, dtype=np.int64)
+        n, nbytes = len(blk_off), len(blob)
+        if cap_bytes is None:                                             # BSIZE at its usual place, ISIZE in the last four bytes
+            cap_bytes = 0
+            for o in blk_off.tolist():
+                if 0 <= o and o + 18 <= nbytes:
+                    end = o + int(blob[o + 16]) + (int(blob[o + 17]) << 8) + 1
+                    if end <= nbytes and end - 4 >= 0:
+                        cap_bytes += min(int.from_bytes(blob[end - 4:end].tobytes(), "little"), 65536)
+        cap = int(cap_bytes)
+        guard, fill = 64, 0xEE
+        d_blob = torch.from_numpy(np.append(blob, np.zeros(1, np.uint8))).to(self.device)
+        d_off = torch.from_numpy(np.append(blk_off, 0)).to(self.device)
+        d_lim = torch.from_numpy(np.append(np.ascontiguousarray(blk_limit, dtype=np.int64), 0)).to(self.device) if blk_limit is not None else None
+        d_all = torch.full((guard + cap + _lib.PLAT_BLOB_PAD + guard,), fill, dtype=torch.uint8, device=self.device)
+        assert d_all.data_ptr() % 16 == 0 and guard % 16 == 0
+        d_out_off = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
+        d_status = torch.zeros(4, dtype=torch.int64, device=self.device)
+        o = _lib.BgzfInflateOut(cap, d_all.data_ptr() + guard, d_out_off.data_ptr(), d_status.data_ptr())
+        _lib.check(self.lib.plat_bgzf_inflate_batch(self.ctx, n, d_blob.data_ptr(), nbytes, d_off.data_ptr(), d_lim.data_ptr() if d_lim is not None else None,
+                                                    C.byref(o), self._stream()), "plat_bgzf_inflate_batch")
+        self._sync()
+        h, st = d_all.cpu().numpy(), d_status.cpu().numpy()
+        fits = int(st[0]) != -8
+        total = int(st[2]) if fits else 0
+        pad = _lib.PLAT_BLOB_PAD if fits else 0
+        tail = h[guard + total:]
+        intact = bool((h[:guard] == fill).all()) and not tail[:pad].any() and bool((tail[pad:] == fill).all())
+        out = dict(data=h[guard:guard + total], out_off=d_out_off.cpu().numpy(), status=st, guard_intact=intact)
+        if keep_device:
+            out["device"] = dict(all=d_all, data_ptr=d_all.data_ptr() + guard, out_off=d_out_off, n_blocks=n)
+        if check and int(st[0]) != 0:
+            raise _lib.PlatypusDeviceError(int(st[0]), "block %d" % int(st[1]), "plat_bgzf_inflate_batch")
+        return out
+
+    def bam_find_records(self, inflated, streams, cap_records=None, check=True):
+        """plat_bam_find_records: sam_itr_next over the output of bgzf_inflate(..., keep_device=True).  streams: per stream (tid, beg, end,
+        chunks), chunks a list of (blk_first, blk_end, first_uoffset, stop_blk or -1, stop_uoffset).  Returns a dict: rec_off / rec_limit
+        (the kept records of all streams back to back), stream_begin [n+1], status [4] = {error, lowest offending stream, kept, walked} and
+        guard_intact: nothing was written behind cap_records (default: one record per 36 inflated bytes, the bound the format gives)."""
+        torch = _torch()
+        dv = inflated["device"]
+        total = int(inflated["status"][2])
+        cap = total // 36 + 1 if cap_records is None else int(cap_records)
+        i32 = lambda a: torch.from_numpy(np.append(np.asarray(a, dtype=np.int32), np.int32(0))).to(self.device)
+        chunks = [c for s in streams for c in s[3]]
+        begin = np.concatenate([[0], np.cumsum([len(s[3]) for s in streams])]) if streams else np.zeros(1)
+        cols = [i32([c[k] for c in chunks]) for k in range(5)]
+        d_begin, d_tid, d_beg, d_end = i32(begin)[:len(streams) + 1], i32([s[0] for s in streams]), i32([s[1] for s in streams]), i32([s[2] for s in streams])
+        guard, fill = 16, 0x7EEE7EEE7EEE7EEE
+        d_off = torch.full((cap + guard,), fill, dtype=torch.int64, device=self.device)
+        d_lim = torch.full((cap + guard,), fill, dtype=torch.int64, device=self.device)
+        d_sb = torch.zeros(len(streams) + 1, dtype=torch.int32, device=self.device)
+        d_status = torch.zeros(4, dtype=torch.int64, device=self.device)
+        fi = _lib.BamFindIn(len(streams), len(chunks), dv["n_blocks"], 0, dv["data_ptr"], dv["out_off"].data_ptr(), d_begin.data_ptr(),
+                            *[c.data_ptr() for c in cols], d_tid.data_ptr(), d_beg.data_ptr(), d_end.data_ptr())
+        fo = _lib.BamFindOut(cap, d_off.data_ptr(), d_lim.data_ptr(), d_sb.data_ptr(), d_status.data_ptr())
+        _lib.check(self.lib.plat_bam_find_records(self.ctx, C.byref(fi), C.byref(fo), self._stream()), "plat_bam_find_records")
+        self._sync()
+        st, off, lim = d_status.cpu().numpy(), d_off.cpu().numpy(), d_lim.cpu().numpy()
+        kept = min(int(st[2]), cap)
+        out = dict(rec_off=off[:kept], rec_limit=lim[:kept], stream_begin=d_sb.cpu().numpy(), status=st,
+                   guard_intact=bool((off[kept:] == fill).all() and (lim[kept:] == fill).all()))
+        if check and int(st[0]) != 0:
+            raise _lib.PlatypusDeviceError(int(st[0]), "stream %d" % int(st[1]), "plat_bam_find_records")
+        return out
+
     # ---- SURVEY 8(f) rank 3: read statistics of the VCF INFO field --------------------------------------------
     def variant_read_stats(self, windows, bad_reads_window=11, exact=0):
         """vcfINFO's per-read loop for a list of windows.  A window: dict {variants: [dict(pos, removed, added, bam_min,

@@ -137,6 +137,19 @@ class _BamRegion(C.Structure):
                 ("contig_len", C.c_int64), ("samples", C.POINTER(_BamSample)), ("dev_contig_seq", C.c_void_p)]
 
 
+class _BgzfChunk(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("data_len", C.c_int64), ("first_uoffset", C.c_int32), ("end_coffset", C.c_int64), ("end_uoffset", C.c_int32)]
+
+
+class _BgzfSample(C.Structure):
+    _fields_ = [("n_chunks", C.c_int32), ("chunks", C.POINTER(_BgzfChunk)), ("broken_mates", _BamRecords)]
+
+
+class _BgzfRegion(C.Structure):
+    _fields_ = [("chrom", C.c_char_p), ("start", C.c_int32), ("end", C.c_int32), ("contig_seq", C.c_void_p), ("contig_len", C.c_int64),
+                ("dev_contig_seq", C.c_void_p), ("tid", C.c_int32), ("itr_beg", C.c_int32), ("itr_end", C.c_int32), ("samples", C.POINTER(_BgzfSample))]
+
+
 class ReadTable:
     """One ReadArray as arrays (cAlignedRead fields, htslibWrapper.pxd:187-201).  `reads`: the order the ReadArray holds them in
     (sorted by pos; brokenMates by mate position)."""
@@ -301,6 +314,91 @@ class BamRegion:
         a.start, a.end = self.start, self.end
 
 
+class BgzfRegion:
+    """One region as an index lookup leaves it (include/platypus_caller_bgzf.h): the iterator's window (tid, itr_beg, itr_end) and per
+    sample the chunks of the fetch -- each (data uint8 array of whole BGZF blocks, first_uoffset, end_coffset or -1, end_uoffset) -- and
+    the broken mates as uncompressed records (data, rec_off), in mate-position order."""
+
+    def __init__(self, chrom, start, end, contig_seq, tid, itr_beg, itr_end, samples):
+        self.chrom, self.start, self.end = chrom, int(start), int(end)
+        self.tid, self.itr_beg, self.itr_end = int(tid), int(itr_beg), int(itr_end)
+        self.contig = np.ascontiguousarray(np.frombuffer(contig_seq, dtype=np.uint8) if isinstance(contig_seq, (bytes, bytearray)) else contig_seq,
+                                           dtype=np.uint8)
+        u8 = lambda d: np.frombuffer(d, dtype=np.uint8) if isinstance(d, (bytes, bytearray)) else np.ascontiguousarray(d, dtype=np.uint8)
+        self.samples = [([(u8(d), int(fu), int(ec), int(eu)) for d, fu, ec, eu in chunks],
+                         (np.ascontiguousarray(b[0], dtype=np.uint8), np.ascontiguousarray(b[1], dtype=np.int64))) for chunks, b in samples]
+        self._c = None
+
+    @property
+    def compressed_bytes(self):
+        return sum(len(d) for chunks, _ in self.samples for d, _, _, _ in chunks)
+
+    @classmethod
+    def from_reads(cls, chrom, start, end, fasta, samples, level=6, strategy=0, block_payload=0xff00, decoys=None, itr=None, n_chunks=1, **layout):
+        """samples: per sample (fetched, brokenMates), lists of hostapi.AlignedRead as BamRegion.from_reads takes them.  The fetched reads
+        become records behind their block_size words (synth.bam_records; **layout: its names / aux), then one BGZF stream of
+        block_payload-byte blocks (synth.bgzf_stream at level / strategy; records span blocks wherever a boundary falls), then n_chunks
+        chunks of it that meet at a record boundary inside a block both of them hold.  decoys = (in front, behind): reads whose records
+        are written around the fetched ones -- what else the blocks of a lookup hold -- for the iterator to skip or stop at.  itr =
+        (tid, beg, end): the iterator's window; by default the reads' chromID and the smallest window every fetched read passes."""
+        from . import synth
+        front, behind = decoys if decoys is not None else ([], [])
+        out, window = [], []
+        made = dict(chunks=0, records_spanning_blocks=0, blocks=0)        # what the layout came to (for tests and tools)
+        for fetched, broken in samples:
+            parts = [synth.bam_records(rs, block_size=True, **(layout if rs is fetched else {}))[0].tobytes() for rs in (front, fetched, behind)]
+            data = b"".join(parts)
+            stream, off = synth.bgzf_stream(data, block_payload=block_payload, level=level, strategy=strategy)
+            off = [int(o) for o in off] + [len(stream)]
+            # chunk boundaries: record starts among the fetched records, as evenly spread as they come
+            rec_at, at = [], len(parts[0])
+            while at < len(parts[0]) + len(parts[1]):
+                rec_at.append(at)
+                at += 4 + int.from_bytes(data[at:at + 4], "little")
+            cuts = [rec_at[len(rec_at) * j // n_chunks] for j in range(1, n_chunks)] if len(rec_at) >= n_chunks else []
+            made["records_spanning_blocks"] += sum(1 for a, b in zip(rec_at, rec_at[1:] + [at]) if a // block_payload != (b - 1) // block_payload)
+            made["blocks"] += len(off) - 1
+            chunks, lo = [], 0                                            # lo: inflated offset where the chunk starts
+            for hi in cuts + [None]:
+                b0 = lo // block_payload
+                if hi is None:
+                    chunks.append((stream[off[b0]:], lo % block_payload, -1, 0))
+                else:
+                    b1 = hi // block_payload                              # (the block of the chunk's end: a boundary at a block's end is offset 0 of the next)
+                    chunks.append((stream[off[b0]:off[b1 + 1]], lo % block_payload, off[b1] - off[b0], hi % block_payload))
+                    lo = hi
+            out.append((chunks, synth.bam_records(sorted(broken, key=lambda r: r.matePos))))
+            made["chunks"] = max(made["chunks"], len(chunks))
+            for r in fetched:
+                clip = r.cigarOps[0][1] if r.cigarOps and r.cigarOps[0][0] == 4 else 0
+                b = r.pos + clip
+                window.append((r.chromID, b, b + (sum(ln for op, ln in r.cigarOps if op in (0, 2, 3, 7, 8)) if r.cigarOps else 1)))
+        if itr is None:
+            itr = (window[0][0], min(e for _, _, e in window) - 1, max(b for _, b, _ in window) + 1) if window else (0, int(start), int(end))
+        reg = cls(chrom, start, end, fasta._seq[chrom], itr[0], itr[1], itr[2], out)
+        reg.made = made
+        return reg
+
+    def fill(self, a, n_samples):
+        """Write this region into the plat_bgzf_region `a` (the arrays stay owned by, and alive with, this object)."""
+        assert len(self.samples) == n_samples
+        if self._c is None:
+            ss = (_BgzfSample * len(self.samples))()
+            keep = []
+            for i, (chunks, (bdata, boff)) in enumerate(self.samples):
+                cc = (_BgzfChunk * max(len(chunks), 1))()
+                for q, (d, fu, ec, eu) in enumerate(chunks):
+                    cc[q].data, cc[q].data_len, cc[q].first_uoffset, cc[q].end_coffset, cc[q].end_uoffset = d.ctypes.data, len(d), fu, ec, eu
+                keep.append(cc)
+                ss[i].n_chunks, ss[i].chunks = len(chunks), cc
+                t = ss[i].broken_mates
+                t.n_records, t.data, t.data_len, t.rec_off = len(boff), bdata.ctypes.data, len(bdata), boff.ctypes.data
+            self._c = (self.chrom.encode(), self.contig.ctypes.data, len(self.contig), ss, keep)
+        a.chrom, a.contig_seq, a.contig_len, a.samples = self._c[:4]
+        a.start, a.end = self.start, self.end
+        a.tid, a.itr_beg, a.itr_end = self.tid, self.itr_beg, self.itr_end
+
+
 def region_from_arrays(reg, pin=False, packed=False):
     """RegionReads of a synth.config4_region_arrays() region (every read in `reads`; no badReads / brokenMates)."""
     empty = ReadTable([], [], [0], [], [], [], [], [], [], [0])
@@ -352,6 +450,7 @@ def build(verbose=False):
     """g++ the host library and link it to libplat_mi355x.so (built first if needed)."""
     _lib.build()
     srcs = [os.path.join(HOST_SRC, f) for f in sorted(os.listdir(HOST_SRC)) if f.endswith((".cpp", ".hpp"))]
+    srcs.append(os.path.join(_lib.CSRC, "bgzf_inflate.hpp"))           # (the BGZF front end reads block headers with the device's own parser)
     if os.path.exists(LIB_PATH) and os.path.getmtime(LIB_PATH) >= max([os.path.getmtime(f) for f in srcs] + [os.path.getmtime(_lib.LIB_PATH)]):
         return LIB_PATH
     # (-O3: the region loop is many small functions over small containers; +10 % windows/s over -O2 on the same box.  No -march: the library
@@ -385,6 +484,9 @@ def _bind(lib):
     lib.plat_call_bam_regions.argtypes = [C.c_void_p, C.POINTER(_BamRegion), C.c_int, C.c_int, C.POINTER(C.c_char_p), C.POINTER(CallerOptions),
                                           C.POINTER(CallerQCOptions), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(_FetchedRegionInfo),
                                           C.POINTER(CallerStats)]
+    lib.plat_call_bgzf_regions.argtypes = [C.c_void_p, C.POINTER(_BgzfRegion), C.c_int, C.c_int, C.POINTER(C.c_char_p), C.POINTER(CallerOptions),
+                                           C.POINTER(CallerQCOptions), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(_FetchedRegionInfo),
+                                           C.POINTER(CallerStats)]
     lib.plat_merge_record_texts.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     lib.plat_caller_region_text_lengths.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     lib.plat_merge_region_blocks.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
@@ -602,6 +704,12 @@ class NativeCaller:
         """regions: list of BamRegion.  As call_fetched_regions, with ReadIterator.get (htslibWrapper.pyx:328-406) on the device in front: the
         records are uploaded as they are and decoded there (plat_bam_decode_batch); the same text, rlen, self.loaded and self.read_counts."""
         return self.call_fetched_regions(regions, sample_names, options, _entry="plat_call_bam_regions", _struct=_BamRegion)
+
+    def call_bgzf_regions(self, regions, sample_names, options):
+        """regions: list of BgzfRegion.  As call_bam_regions, with the BGZF blocks inflated (plat_bgzf_inflate_batch) and sam_itr_next applied
+        (plat_bam_find_records) on the device in front: the compressed bytes are uploaded as they are; the same text, rlen, self.loaded and
+        self.read_counts; stats["input_bytes"] counts the compressed bytes."""
+        return self.call_fetched_regions(regions, sample_names, options, _entry="plat_call_bgzf_regions", _struct=_BgzfRegion)
 
     def call_fetched_regions(self, regions, sample_names, options, _entry="plat_call_fetched_regions", _struct=_FetchedRegion):
         """regions: list of FetchedRegion.  The loader's work (addReadToBuffer's QC and split, isSorted, maxReads) on the device, then the

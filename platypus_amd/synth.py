@@ -560,3 +560,42 @@ def bam_records(reads, names=None, aux=None, lead=0, block_size=False):
         parts.append(rec)
         at += len(rec)
     return np.frombuffer(b"".join(parts), dtype=np.uint8).copy(), np.array(off, dtype=np.int64)
+
+
+BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")        # SAM specification 4.1.2, verbatim
+
+
+def bgzf_block(payload, level=6, strategy=0, extra_subfields=b""):
+    """One BGZF block (RFC 1952 + SAM specification 4.1) holding `payload` (at most 65536 bytes), deflated by Python's zlib (raw,
+    wbits=-15) at `level` with `strategy` (zlib.Z_DEFAULT_STRATEGY, Z_FIXED, Z_HUFFMAN_ONLY, Z_RLE, ...).  extra_subfields: bytes of
+    other gzip extra subfields (SI1 SI2 SLEN data ...), written IN FRONT of the BC subfield.  A writer only: nothing here inflates.
+    ValueError when the block would not fit BSIZE's 16 bits."""
+    import struct
+    import zlib
+    payload = bytes(payload)
+    if len(payload) > 65536:
+        raise ValueError("a BGZF block holds at most 65536 bytes")
+    c = zlib.compressobj(level, zlib.DEFLATED, -15, 9, strategy)
+    cdata = c.compress(payload) + c.flush()
+    xlen = len(extra_subfields) + 6
+    total = 12 + xlen + len(cdata) + 8
+    if total > 65536 or xlen > 65535:
+        raise ValueError("the block does not fit BSIZE (%d bytes)" % total)
+    return (b"\x1f\x8b\x08\x04\x00\x00\x00\x00\x00\xff" + struct.pack("<H", xlen) + bytes(extra_subfields) + b"BC\x02\x00" +
+            struct.pack("<H", total - 1) + cdata + struct.pack("<II", zlib.crc32(payload), len(payload)))
+
+
+def bgzf_stream(data, block_payload=0xff00, level=6, strategy=0, eof=True):
+    """`data` as BGZF blocks of block_payload bytes each (the last one shorter), back to back, with the EOF block behind them:
+    (bytes, block offsets int64 array, EOF block included when written).  gzip.decompress gives `data` back."""
+    data = bytes(data)
+    parts, off, at = [], [], 0
+    for k in range(0, len(data), block_payload):
+        b = bgzf_block(data[k:k + block_payload], level, strategy)
+        off.append(at)
+        parts.append(b)
+        at += len(b)
+    if eof:
+        off.append(at)
+        parts.append(BGZF_EOF)
+    return b"".join(parts), np.array(off, dtype=np.int64)

@@ -16,6 +16,11 @@ device, plat_bam_decode_batch) -- wall time, process CPU per region and input by
 (a record holds none), for all three.  Under rocprofv3 the same run gives k_bam_core / k_bam_scan / k_bam_expand next to k_unpack_pieces
 (the packed call expands a table of the same bases); "bam_expand_bytes" / "unpack_pieces_bytes" are their algorithmic bytes (3.5 and 3
 per base).
+
+--bgzf (with --bam): a fourth way, plat_call_bgzf_regions on the same records as BGZF blocks (zlib level --level, the same names and aux
+data as "bam"): "bgzf" next to the three, with its link bytes (the compressed bytes), and "host_zlib": single-thread zlib inflate of the
+same blocks on the host (seconds, bytes in and out) -- what the device takes off the CPU.  Under rocprofv3 the run gives k_bgzf_inflate,
+k_bam_find and the other new kernels next to the decode's.
 """
 import argparse
 import copy
@@ -39,8 +44,10 @@ def main():
     ap.add_argument("--per-chunk", type=int, default=4)
     ap.add_argument("--packed", action="store_true", help="PLAT_READS_PACKED tables for both calls")
     ap.add_argument("--bam", action="store_true", help="ASCII fetched, packed fetched and raw BAM records in one run")
+    ap.add_argument("--bgzf", action="store_true", help="with --bam: the BGZF call on the same records, and host zlib inflate of the same blocks")
+    ap.add_argument("--level", type=int, default=6, help="zlib level of the BGZF blocks")
     a = ap.parse_args()
-    if a.bam:
+    if a.bam or a.bgzf:
         return bam_main(a)
     opts = default_options()
     enabled = (opts.filterReadsWithUnmappedMates, opts.filterReadsWithDistantMates, opts.filterReadPairsWithSmallInserts, opts.filterDuplicates)
@@ -82,7 +89,7 @@ def main():
 
 
 def bam_main(a):
-    ascii_, packed, bam, n_reads, n_bytes = [], [], [], 0, 0
+    ascii_, packed, bam, bgzf, n_reads, n_bytes = [], [], [], [], 0, 0
     for i in range(a.regions):
         reg, samples = synth.config4_fetched_region(i, region_len=a.region_len)
         fasta = H.FastaFile({reg["chrom"]: reg["ref"].tobytes()})
@@ -100,12 +107,14 @@ def bam_main(a):
         aux = [[b"NMC\x00MDZ150\x00ASC\x96XSC\x00RGZgrp1\x00"] * len(rs) for rs in samples]
         bam.append(F.BamRegion(reg["chrom"], reg["start"], reg["end"], fasta._seq[reg["chrom"]],
                                [(synth.bam_records(rs, names=nm, aux=ax, block_size=True), synth.bam_records([])) for rs, nm, ax in zip(samples, names, aux)]))
+        if a.bgzf:
+            bgzf.append(F.BgzfRegion.from_reads(reg["chrom"], reg["start"], reg["end"], fasta, pairs, level=a.level, names=names[0], aux=aux[0]))
     nc = F.NativeCaller(0, a.workers, a.per_chunk)
     out = dict(regions=a.regions, region_len=a.region_len, reads=n_reads, read_bases=n_bytes)
     texts = {}
     try:
         for name, call, regs in (("fetched_ascii", nc.call_fetched_regions, ascii_), ("fetched_packed", nc.call_fetched_regions, packed),
-                                 ("bam", nc.call_bam_regions, bam)):
+                                 ("bam", nc.call_bam_regions, bam)) + ((("bgzf", nc.call_bgzf_regions, bgzf),) if a.bgzf else ()):
             best = None
             for _ in range(a.reps):
                 o = default_options()
@@ -118,6 +127,33 @@ def bam_main(a):
             out[name] = dict(seconds=w, windows_per_sec=nw / w, cpu_seconds_per_region=c / a.regions, windows=nw, text_bytes=len(texts[name]), input_bytes=ib)
         out["same_text"] = texts["bam"] == texts["fetched_ascii"] == texts["fetched_packed"]
         out["bam_expand_bytes"], out["unpack_pieces_bytes"] = int(3.5 * n_bytes), 3 * n_bytes
+        if a.bgzf:
+            import zlib
+            out["same_text"] = out["same_text"] and texts["bgzf"] == texts["bam"]
+            out["bgzf_level"] = a.level
+            # single-thread zlib over the same blocks: the deflate data of every block, the CRC32 over its output
+            blocks = []
+            for reg in bgzf:
+                for chunks, _ in reg.samples:
+                    for d, _, _, _ in chunks:
+                        d, at = d.tobytes(), 0
+                        while at < len(d):
+                            n = int.from_bytes(d[at + 16:at + 18], "little") + 1
+                            blocks.append(d[at + 18:at + n - 8])
+                            at += n
+            best, n_out = None, 0
+            for _ in range(a.reps):
+                w0 = time.perf_counter()
+                n_out = 0
+                for b in blocks:
+                    o = zlib.decompress(b, -15)
+                    zlib.crc32(o)
+                    n_out += len(o)
+                w = time.perf_counter() - w0
+                best = w if best is None or w < best else best
+            n_in = sum(len(b) for b in blocks)
+            out["host_zlib"] = dict(seconds=best, blocks=len(blocks), compressed_bytes=n_in, inflated_bytes=n_out, inflated_mb_per_sec=n_out / best / 1e6,
+                                    seconds_per_region=best / a.regions)
     finally:
         nc.close()
     print(json.dumps(out))
