@@ -155,7 +155,7 @@ typedef struct plat_caller_stats {
     int64_t n_dp_reference, cells_reference, n_dp_launched, cells_launched;
     /* ... and, same switch, the likelihood batches' shapes and live kernel times (plat_profile, HIP events on the worker's stream):
      * number of batches, their haplotype / read bytes, reads, algorithmic bytes of the DP launches (4 * len + 34 per DP), and the
-     * summed durations of k_seed and k_dp_jobs -- what a roofline entry of the region pipeline's largest kernels is computed from */
+     * summed durations of the seeding kernels (k_sweep + k_pairs) and k_dp_jobs -- what a roofline entry of the region pipeline's largest kernels is computed from */
     int64_t n_align_batches, align_hap_bytes, align_read_bytes, align_reads, align_dp_bytes;
     double seconds_kernel_seed, seconds_kernel_dp;
     double seconds_kernel_sweep, seconds_kernel_pairs;   /* the two kernels of the seeding stage on their own (seed = sweep + pairs) */

@@ -89,10 +89,10 @@ typedef struct plat_profile {
     float ms_dp;          /* banded DP kernel (the dominant kernel)                               */
     float ms_finalize;    /* candidate selection + score -> log-likelihood                        */
     float ms_genotype;    /* genotype likelihood kernel                                           */
-    float ms_seed_kernel; /* k_seed alone (the first and largest kernel of the seed stage)         */
+    float ms_seed_kernel; /* k_sweep + k_pairs (the seed stage without k_seed_slow)               */
     int64_t dp_jobs;      /* DPs in the DP launch                                                 */
     int64_t dp_alg_bytes; /* algorithmic bytes of the DP launch                                   */
-    float ms_sweep;       /* k_sweep alone (round 4: the seeding stage is two kernels; 0 with PLAT_SEED_FUSED=1) */
+    float ms_sweep;       /* k_sweep alone (the seeding stage is two kernels)                       */
     float ms_pairs;       /* k_pairs alone                                                         */
     float ms_unpack;      /* the last plat_unpack_reads_pieces launch on this context since the profile was switched on (0: none) */
     float ms_candidates;  /* the last plat_candidates_batch launch (k_candidates)                     */

@@ -8,7 +8,7 @@
 // The reference's lane shifts (_mm_slli/_mm_srli_si128 by one lane) are a register renaming plus one v_perm_b32
 // (see V8).  No MFMA: this is a min-plus recurrence, not a contraction.
 //
-// Inputs arrive as pre-converted 32-bit WORDS (built once per batch by k_prep_reads / k_seed and
+// Inputs arrive as pre-converted 32-bit WORDS (built once per batch by k_prep_reads / k_sweep and
 // then re-used by every DP that touches the base):
 //     read word  rw = (byte << 9) | (4*qual) << 16      pad rows past the read end: '0' / 64*4 (align.c:223-226)
 //     hap  word  hw = (byte << 9) | (4*gapopen) << 16

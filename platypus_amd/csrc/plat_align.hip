@@ -8,10 +8,12 @@
 //                 descriptor (length, skip rule, mapq, plain-ACGT flag, quality sum / minimum / count below Q20).
 //                 (Rounds 1-2 also wrote a tile of pre-converted 4-byte DP words per base of every read; since the
 //                 seeding proofs only one pair in eight reaches the DP, which now builds its words from the bytes.)
-//   k_seed        one workgroup per haplotype: bytes staged in LDS, gap-open annotation (a7, chaplotype.pyx:552-590)
-//                 written as one byte per haplotype position, 7-mer index in LDS (a4, calign.pyx:94-124),
-//                 then one wave per read: diagonal vote (calign.pyx:206-220) with 16-bit LDS counters and the
-//                 arg-max candidate list in ascending order (calign.pyx:222-233) -> DP jobs
+//   k_sweep       one workgroup per haplotype: its bit planes, the gap-open annotation (a7, chaplotype.pyx:552-590) written as
+//                 one byte per haplotype position, the 7-mer multiplicities
+//   k_pairs       one lane per (haplotype, read) pair: proves the one arg-max diagonal of the vote (calign.pyx:206-233) without
+//                 counting votes, and finishes exact and provably ungapped pairs without a DP -> DP jobs
+//   k_seed_slow   the pairs k_pairs left open, one wave per pair: 7-mer index in LDS (a4, calign.pyx:94-124), diagonal vote
+//                 (calign.pyx:206-220) with 16-bit LDS counters, arg-max candidate list in ascending order (calign.pyx:222-233)
 //   k_dp_jobs     one lane per banded DP (a1, align.c:77-586), see dp_core.hpp
 //   k_finalize    per (read, haplotype): the reference's candidate selection replayed on the job scores
 //                 (calign.pyx:235-267), score -> log-likelihood (a8, chaplotype.pyx:621-676)
@@ -39,7 +41,7 @@ __device__ __forceinline__ int job_hap(const Job& j) { return j.hap & (JOB_BIGQ 
 //  bit2: quality sum above DP_SWAR_MAX_QSUM -> its DPs use the packed 16-bit adds)
 struct ReadInfo { uint32_t col, aux; int32_t pos; uint32_t lfm; };      // aux bits 0..15: number of bases with quality < LOWQ (the ungapped proof)
 constexpr unsigned LOWQ = 20u;
-enum { SHORTCUT_UNGAPPED = 1, SHORTCUT_EXACT = 2, SHORTCUT_NLOW = 4, SHORTCUT_BIGQ = 8, SEED_LEAN = 1024, SEED_XCD = 2048 };   // what k_seed may finish without a DP (PLAT_NO_UNGAPPED / PLAT_NO_EXACT
+enum { SHORTCUT_UNGAPPED = 1, SHORTCUT_EXACT = 2, SHORTCUT_NLOW = 4, SHORTCUT_BIGQ = 8, SEED_LEAN = 1024, SEED_XCD = 2048 };   // what k_pairs may finish without a DP (PLAT_NO_UNGAPPED / PLAT_NO_EXACT
                                                                          // switch them off; PLAT_NO_NLOW values unique windows by the smallest quality only)
 __device__ __forceinline__ long long job_slot(long long pair, long long npairs, int extra_base, int k) {
     return k == 0 ? pair : npairs + extra_base + (k - 1);
@@ -49,7 +51,7 @@ enum { CNT_ERR = 0, CNT_MAXHAP, CNT_MAXREAD, CNT_NEXTRA, CNT_PAIRS_ALIGNED, CNT_
        CNT_NJOBS_RUN, CNT_TILE_TOTAL, CNT_SLOW_SEED, CNT_MAXH, CNT_NDENSE, CNT_HAPBLOB, CNT_NPAIRS, CNT_READBLOB, CNT_T0, CNT_T1, CNT_T2, CNT_T3, CNT_T4, CNT_NWAVES, CNT_N };
 static_assert(CNT_N <= 64, "the pinned read-back area holds 64 words");
 
-// The dense list of live DP job slots, built where the jobs are made (k_seed / k_seed_slow): DENSE_SEGS segments of `segcap`
+// The dense list of live DP job slots, built where the jobs are made (k_pairs / k_seed_slow): DENSE_SEGS segments of `segcap`
 // entries, one counter each, a whole window's jobs in one segment (w % DENSE_SEGS); a wave reserves room for its live jobs
 // with ONE atomic.  The counters sit 4 KB apart (different L2 channels: one address takes ~90 atomics/us) behind the
 // other counters; k_dense_total copies them into cnt[] for the host and sums them.
@@ -128,7 +130,7 @@ k_validate(plat_window_batch b, long long* cnt, int32_t* __restrict__ hap_win, i
         maxread = max(maxread, lm);
         maxR = max(maxR, (int)min(R, 1ll << 30));
     }
-    // (the 7-bit ASCII check of the blobs is done where the bytes are read anyway: k_prep_reads and k_seed)
+    // (the 7-bit ASCII check of the blobs is done where the bytes are read anyway: k_prep_reads and k_sweep)
     atomicMax(&s_max[0], maxhap); atomicMax(&s_max[1], maxread); atomicMax(&s_max[2], maxR);
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -251,10 +253,10 @@ k_prep_reads(plat_window_batch b, const int32_t* __restrict__ win_rows, const lo
     __shared__ int s_off[65];
     __shared__ unsigned s_dirty[2];                      // bit rl: read rl of the group holds a byte other than A, C, G, T
     __shared__ unsigned s_qsum[64];                      // sum of the base qualities of read rl (picks the DP's add flavour)
-    __shared__ unsigned s_qmin[64];                      // smallest base quality of read rl (k_seed's ungapped-alignment proof)
+    __shared__ unsigned s_qmin[64];                      // smallest base quality of read rl (k_pairs' ungapped-alignment proof)
     __shared__ unsigned s_nlow[64];                      // number of bases of read rl with quality < LOWQ (same proof)
     // (grid.x a multiple of 8: XCD x -- workgroups go to the XCDs round robin -- takes the x-th eighth of the windows, the eighth whose
-    // haplotypes k_seed gives to the same XCD: what this kernel writes is what that one reads, and some of it is still in that L2)
+    // pairs k_pairs gives to the same XCD: what this kernel writes is what that one reads, and some of it is still in that L2)
     int w = blockIdx.x;
     if (xcd) {
         w = (int)(blockIdx.x & 7u) * (int)(gridDim.x >> 3) + (int)(blockIdx.x >> 3);
@@ -455,9 +457,9 @@ __device__ __forceinline__ unsigned kmer_head(const unsigned* table, unsigned co
     return e & 0xFFFFu;
 }
 
-// k_seed: one workgroup per haplotype; ONE LANE PER (read, haplotype) PAIR.
-// LDS carve (dynamic):  table u32[tsize] | next u16[maxhap+2] | planes u64[4][nw64] (h0, h1, eq, nu) |
-//                       counts u16[nwaves][cw] | scalars
+// The seeding stage: k_sweep per haplotype, k_pairs with ONE LANE PER (read, haplotype) PAIR, k_seed_slow for the pairs that leaves open.
+// LDS carve of k_sweep and k_seed_slow (dynamic):  table u32[tsize] | next u16[maxhap+2] | planes u64[4][nw64] (h0, h1, eq, nu) |
+//                       counts u16[nwaves][cw] (k_seed_slow only) | scalars
 // The k-mer index has two modes: haplotypes up to 4096 bp use a small open-addressing table (load factor <= 0.8);
 // longer ones (up to the reference's cap of 16384) index all 4^7 codes directly, as the reference does
 // (calign.pyx:98-99).
@@ -477,7 +479,6 @@ __device__ __forceinline__ unsigned kmer_head(const unsigned* table, unsigned co
 // wave counts that pair's diagonals in 16-bit LDS counters (two per dword, 32-bit LDS atomics; bit 15 = claim flag
 // that picks one representative lane per arg-max diagonal) and emits the candidates in ascending order.
 typedef unsigned long long u64;
-constexpr int SEED_CHUNKS = 4;
 constexpr int UNG_KMAX = 4;           // mismatches on the candidate diagonal the ungapped-alignment proof takes on
 
 __device__ __forceinline__ u64 funnel(u64 lo, u64 hi, int sh) { return sh ? (lo >> sh) | (hi << (64 - sh)) : lo; }
@@ -696,13 +697,15 @@ __device__ __forceinline__ void seed_build_index(unsigned* table, unsigned short
     __syncthreads();
 }
 
-struct SeedPlanes { u64 m0, m1, me; };
 __device__ __forceinline__ void wave_sync() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
 
 // One single-wave workgroup sweeps one haplotype: planes, gap-open bytes, multiplicity maps, nu plane, per-chunk gap-open minima, flags.
-// Returns have_index (the counting table overflowed: the exact maximum came from the index, which then overwrote the maps).
-__device__ __forceinline__ bool seed_sweep(unsigned* table, unsigned short* nxt, u64* h0, u64* h1, u64* eqp, u64* nup, int* s_scal, int nw64,
-                                           const uint8_t* __restrict__ hs, int hapLen, long long hoff, bool first_group, uint8_t* __restrict__ gob,
+// Multiplicities come from two 16384-bit maps over the 14-bit k-mer codes ("seen at least once / twice"), filled with one LDS atomicOr
+// per k-mer, plus a 32-entry counting table for the few codes seen three times or more.  (LDS per workgroup decides how many haplotypes
+// a CU works on at once: 6 KB instead of 9.4 KB with a third map.)  The maps lie where a k-mer index would: only when the counting table
+// overflows is the index built here, over the maps, for the exact maximum.
+__device__ __forceinline__ void seed_sweep(unsigned* table, unsigned short* nxt, u64* h0, u64* h1, u64* eqp, u64* nup, int* s_scal, int nw64,
+                                           const uint8_t* __restrict__ hs, int hapLen, long long hoff, uint8_t* __restrict__ gob,
                                            long long* cnt, int shortcuts, bool direct, int tsize, unsigned tmask, int nch, bool& stop)
 {
     const int tid = threadIdx.x, nthr = blockDim.x;
@@ -730,7 +733,7 @@ __device__ __forceinline__ bool seed_sweep(unsigned* table, unsigned short* nxt,
         // (the loop is written without divergent branches: every `if` on a lane condition costs half a dozen scalar
         //  instructions of exec-mask bookkeeping, and this sweep had three scalar instructions for every vector one)
         auto ldb = [&](int t) -> unsigned { const int p = 64 * t + lane; return p < hapLen ? (unsigned)hs[p] : 0u; };
-        typedef SeedPlanes Planes;
+        struct Planes { u64 m0, m1, me; };
         u64 anyN = 0ull, anyOther = 0ull;                // wave-uniform: a byte 'N' / a byte other than A, C, G, T, N was seen
         unsigned accBits = 0u;                           // per lane: OR of its bytes (7-bit ASCII check after the loop)
         auto mk = [&](int t, unsigned c, unsigned cnext_chunk) -> Planes {
@@ -761,7 +764,7 @@ __device__ __forceinline__ bool seed_sweep(unsigned* table, unsigned short* nxt,
                 const u64 v = funnel(P0.me, P1.me, lane);
                 const int run = min(48, (int)__ffsll((long long)~v) - 1);     // trailing ones of v (v never has 64 ones beyond the cap)
                 const int go = s_go[run < 0 ? 48 : run];
-                if (p < hapLen && first_group) gob[hoff + p] = (uint8_t)go;       // localGapOpen[p]: the DP builds its haplotype words from it
+                if (p < hapLen) gob[hoff + p] = (uint8_t)go;                      // localGapOpen[p]: the DP builds its haplotype words from it
             }
             {   // multiplicity maps of the k-mers at positions 0..hapLen-8: "seen", "seen twice"; lanes past the last k-mer OR in nothing
                 const unsigned code = plane_code(P0.m0, P1.m0, P0.m1, P1.m1, lane);
@@ -810,7 +813,7 @@ __device__ __forceinline__ bool seed_sweep(unsigned* table, unsigned short* nxt,
         s_gmin[t] = (unsigned char)s_go[longest];
     }
     __syncthreads();
-    if (shortcuts & 256) { stop = true; return false; }  // (measurement only, PLAT_SEED_DEBUG: the haplotype sweep alone)
+    if (shortcuts & 256) { stop = true; return; }        // (measurement only, PLAT_SEED_DEBUG: the haplotype sweep alone)
     if (lane < 32) level = max(level, trip[lane] ? 2 + (int)(trip[lane] >> 16) : 0);
 #pragma unroll
     for (int s2 = 32; s2 > 0; s2 >>= 1) level = max(level, __shfl_xor(level, s2));
@@ -828,669 +831,22 @@ __device__ __forceinline__ bool seed_sweep(unsigned* table, unsigned short* nxt,
         if (lane == 0) nup[t] = md;
     }
     __syncthreads();
-    bool have_index = false;
     if (s_scal[1] >= 0x7FFF) {                           // counting table overflowed: the exact maximum comes from the index chains
         __syncthreads();
         if (tid == 0) s_scal[1] = 1;
         __syncthreads();
         seed_build_index(table, nxt, h0, h1, nup, s_scal, hapLen, nch, direct, tsize, tmask, true);
-        have_index = true;
-    }
-    return have_index;
-}
-
-// ---- the haplotypes of a window share almost everything -----------------------------------------------------------------------
-// They are the window's reference sequence with a few variants applied, so sweeping each of them repeats most of the work.
-// k_seed_base sweeps the FIRST haplotype of every window once and leaves the result in global memory (per window, SEED_BASE_*
-// below: flags, the "seen at least once" map, the four planes, the per-chunk gap-open minima; its gap-open bytes are in `gob`).
-// k_seed then DERIVES a haplotype of the same length that differs from that base in at most SEED_MAXDIFF bases instead of sweeping it:
-// the base's planes, with the chunks the differing bases touch rebuilt; gap-open bytes recomputed within 48 positions of them; and a
-// CONSERVATIVE nu plane instead of multiplicity maps of its own:
-//   * a 7-mer that does not contain a differing base keeps the base's flag.  If it is unique in the base it is unique here as long as
-//     no new 7-mer equals it (checked: a new 7-mer whose code the base has seen at all sends the haplotype to the full sweep); if it is
-//     flagged in the base it stays flagged, even when the copies that made it so are among the <= 7 per difference that disappeared;
-//   * the <= 7 new 7-mers per differing base are unique (none is in the base, and they are checked against each other);
-//   * the largest multiplicity is at most the base's.
-// A flag too many only weakens the proofs (more votes granted to other diagonals, fewer unique windows): a pair may go to the DP that
-// a full sweep would have finished, never the other way round -- the scores are the same.  The base haplotype itself is "derived" with
-// no difference, i.e. loaded.
-constexpr int SEED_MAXDIFF = 8;
-constexpr int SEED_BASE_SCAL = 0, SEED_BASE_SEEN = 16, SEED_BASE_PLANES = 16 + 2048;      // byte offsets inside a window's record
-__host__ __device__ __forceinline__ size_t seed_base_stride(int maxhap) {
-    const size_t nw64 = (((size_t)maxhap + 63) >> 6) + 8;
-    return (size_t)SEED_BASE_PLANES + 32 * nw64 + ((nw64 + 15) & ~(size_t)15);
-}
-
-__device__ __forceinline__ SeedPlanes seed_chunk_planes(int t, unsigned c, unsigned cnext_chunk, int hapLen, int lane) {
-    const int p = 64 * t + lane;
-    unsigned cn = (unsigned)__shfl_down((int)c, 1);
-    const unsigned first_next = (unsigned)__shfl((int)cnext_chunk, 0);
-    cn = lane == 63 ? first_next : cn;
-    const unsigned b2 = base2(c);                                        // bytes past the end are 0 -> code 0
-    SeedPlanes P;
-    P.m0 = __ballot(p < hapLen && (b2 & 1u));
-    P.m1 = __ballot(p < hapLen && (b2 & 2u));
-    P.me = __ballot(p + 1 < hapLen && c == cn && c != (unsigned)'N');
-    return P;
-}
-
-// Returns false when the haplotype has to be swept in full.  base: the window's record; hb / gob_base: the base haplotype's bytes and
-// gap-open bytes; table .. s_gmin: this workgroup's LDS working set (as seed_sweep leaves it); write_gob: store the gap-open bytes.
-__device__ __forceinline__ bool seed_derive(const unsigned char* __restrict__ base, const uint8_t* __restrict__ hb, const uint8_t* __restrict__ gob_base,
-                                            unsigned* table, u64* h0, u64* h1, u64* eqp, u64* nup, int* s_scal, unsigned char* s_gmin, int nw64,
-                                            const uint8_t* __restrict__ hs, int hapLen, bool is_base, bool write_gob, uint8_t* __restrict__ gob,
-                                            long long* cnt)
-{
-    const int lane = threadIdx.x & 63;
-    const int nch = (hapLen + 63) >> 6;                  // <= 64: haplotypes up to 4096 bases are derived
-    const int* bscal = (const int*)(base + SEED_BASE_SCAL);
-    const unsigned* bseen = (const unsigned*)(base + SEED_BASE_SEEN);
-    const u64* bplanes = (const u64*)(base + SEED_BASE_PLANES);
-    const unsigned char* bgmin = base + SEED_BASE_PLANES + 32 * (size_t)nw64;
-    signed char* s_go = (signed char*)(s_scal + 4);
-    auto ldb = [&](int t) -> unsigned { const int p = 64 * t + lane; return p < hapLen ? (unsigned)hs[p] : 0u; };
-    auto ld4 = [&](const uint8_t* q) -> uint32_t { uint32_t v; __builtin_memcpy(&v, q, 4); return v; };
-    // (everything that does not depend on the differences is requested first: the base's planes, minima and flags)
-    u64 pl[2];
-    pl[0] = lane < 4 * nw64 ? bplanes[lane] : 0ull;
-    pl[1] = lane + 64 < 4 * nw64 ? bplanes[lane + 64] : 0ull;
-    const unsigned char gm0 = lane < nch ? bgmin[lane] : (unsigned char)0;
-    const int bs0 = bscal[0], bs1 = bscal[1], bs2 = bscal[2];
-    // a. where it differs from the base, four bases per lane and trip (blobs are followed by PLAT_BLOB_PAD readable bytes); lane j gets
-    // the position of the j-th differing base
-    int ndiff = 0, mypos = -1;
-    uint32_t acc = 0u;
-    if (!is_base)
-        for (int o0 = 0; o0 < hapLen; o0 += 1024) {      // four trips' loads in flight
-            uint32_t xa[4], xd[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int o = o0 + 256 * k + 4 * lane;
-                const bool in = o < hapLen;
-                const uint32_t va = in ? ld4(hs + o) : 0u, vb = in ? ld4(hb + o) : 0u;
-                const int nv = hapLen - o;                // bytes of this dword inside the haplotype
-                const uint32_t keep = nv >= 4 ? 0xFFFFFFFFu : (nv <= 0 ? 0u : ((1u << (8 * nv)) - 1u));
-                xa[k] = va & keep; xd[k] = (va ^ vb) & keep;
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                acc |= xa[k];
-                u64 m = __ballot(xd[k] != 0u);
-                while (m) {                              // (wave-uniform; a handful of trips in the whole haplotype)
-                    const int L = (int)__ffsll((long long)m) - 1;
-                    m &= m - 1ull;
-                    const uint32_t x = (uint32_t)__shfl((int)xd[k], L);
-#pragma unroll
-                    for (int q = 0; q < 4; ++q)
-                        if ((x >> (8 * q)) & 0xFFu) {
-                            if (lane == ndiff) mypos = o0 + 256 * k + 4 * L + q;
-                            ++ndiff;
-                        }
-                    if (ndiff > SEED_MAXDIFF) return false;
-                }
-            }
-        }
-    if (acc & 0x80808080u) set_err(cnt, PLAT_ERR_BAD_INPUT);               // 7-bit ASCII only (the DP packs bases as byte << 9)
-    bool newN = false, newOther = false;
-    if (ndiff) {
-        const unsigned a = (lane < ndiff) ? (unsigned)hs[mypos] : (unsigned)'A';
-        newN = __any(a == (unsigned)'N');
-        newOther = __any(a != 'A' && a != 'C' && a != 'G' && a != 'T' && a != 'N');
-    }
-    // b. the base's planes (h0, h1, eq, nu are contiguous), the gap-open table
-    if (lane < 4 * nw64) h0[lane] = pl[0];
-    if (lane + 64 < 4 * nw64) h0[lane + 64] = pl[1];
-    for (int i = lane + 128; i < 4 * nw64; i += 64) h0[i] = bplanes[i];
-    if (lane < 49) s_go[lane] = c_homopol_go[lane];
-    wave_sync();
-    // c. plane words that change: the chunk of a differing base, and the chunk before it when the base is its first (eq looks one base
-    // ahead); gap-open bytes that may change: the 48 positions in front of a changed run bit
-    u64 redo = 0ull, godirty = 0ull;
-    for (int j = 0; j < ndiff; ++j) {
-        const int p = __shfl(mypos, j);
-        redo |= 1ull << (p >> 6);
-        if (p > 0) redo |= 1ull << ((p - 1) >> 6);
-        for (int t = max(p - 49, 0) >> 6; t <= (p >> 6); ++t) godirty |= 1ull << t;
-    }
-    for (u64 m = redo; m; m &= m - 1ull) {
-        const int t = (int)__ffsll((long long)m) - 1;
-        const SeedPlanes Q = seed_chunk_planes(t, ldb(t), ldb(t + 1), hapLen, lane);
-        const u64 val = lane == 0 ? Q.m0 : (lane == 1 ? Q.m1 : Q.me);
-        if (lane < 3) h0[lane * nw64 + t] = val;
-    }
-    wave_sync();
-    // d. gap-open bytes (a7): the base's, four at a time; then the chunks marked above recomputed from the run plane
-    if (write_gob) {
-        for (int o = 4 * lane; o < hapLen; o += 256) {
-            const uint32_t v = ld4(gob_base + o);
-            if (o + 4 <= hapLen) __builtin_memcpy(gob + o, &v, 4);
-            else for (int q = 0; o + q < hapLen; ++q) gob[o + q] = (uint8_t)(v >> (8 * q));
-        }
-        for (u64 m = godirty; m; m &= m - 1ull) {
-            const int t = (int)__ffsll((long long)m) - 1, p = 64 * t + lane;
-            const u64 v = funnel(eqp[t], eqp[t + 1], lane);
-            const int run = min(48, (int)__ffsll((long long)~v) - 1);
-            if (p < hapLen) gob[p] = (uint8_t)s_go[run < 0 ? 48 : run];
-        }
-    }
-    for (int t = lane; t < nch; t += 64) {               // per-chunk minima: the base's, recomputed where a run may have changed
-        unsigned char gm = t < 64 ? gm0 : bgmin[t];
-        if ((godirty >> t) & 1ull) {
-            const u64 e0 = eqp[t], e1 = eqp[t + 1];
-            const int nvalid = min(64, hapLen - 64 * t);
-            u64 left = nvalid >= 64 ? ~0ull : ((1ull << nvalid) - 1ull);
-            int longest = 0;
-            while (longest < 48) {
-                left &= funnel(e0, e1, longest);
-                if (left == 0ull) break;
-                ++longest;
-            }
-            gm = (unsigned char)s_go[longest];
-        }
-        s_gmin[t] = gm;
-    }
-    // e. the 7-mers that contain a differing base are new: none of them may be a code the base has seen, nor equal another new one
-    int prev = -1;
-    for (int j = 0; j < ndiff; ++j) {
-        const int p = __shfl(mypos, j);
-        const int sidx = p - 6 + lane;                   // lanes 0..6: the 7-mers starting at p-6 .. p (those not taken by the difference before)
-        const bool valid = lane < 7 && sidx >= 0 && sidx > prev && sidx < hapLen - 7;
-        unsigned code = 0xFFFFFFFFu;
-        if (valid) { const int t = sidx >> 6; code = plane_code(h0[t], h0[t + 1], h1[t], h1[t + 1], sidx & 63); }
-        if (lane < 7) table[7 * j + lane] = code;        // (the index area is free: no index of this haplotype exists yet)
-        if (valid) atomicAnd(&((unsigned*)nup)[sidx >> 5], ~(1u << (sidx & 31)));
-        prev = p;
-    }
-    wave_sync();
-    const int n = 7 * ndiff;
-    const unsigned mycode = lane < n ? table[lane] : 0xFFFFFFFFu;
-    const bool hit = mycode != 0xFFFFFFFFu && ((bseen[mycode >> 5] >> (mycode & 31u)) & 1u);      // the base's "seen at least once" map: one look-up per lane
-    if (__any(hit)) return false;
-    for (int j = 0; j < n; ++j) {
-        const unsigned cj = table[j];
-        if (cj != 0xFFFFFFFFu && __any(lane != j && mycode == cj)) return false;
-    }
-    // f. flags: N / other bytes may only have been added (a flag too many sends pairs to the DP's general path, nothing else)
-    if (lane == 0) { s_scal[0] = bs0 | (newN ? 1 : 0); s_scal[1] = bs1; s_scal[2] = bs2 | (newOther ? 1 : 0); }
-    wave_sync();
-    return true;
-}
-
-// One single-wave workgroup per window: the full sweep of the window's first haplotype (its gap-open bytes and has_n flag are final),
-// left in the window's record for k_seed.  ok = 0 when nothing can be derived from it (counting table overflowed: the index overwrote
-// the maps; haplotype shorter than 16 bases).
-__global__ void __launch_bounds__(64)
-k_seed_base(plat_window_batch b, uint8_t* __restrict__ gob, uint8_t* __restrict__ hap_has_n, long long* cnt, unsigned char* __restrict__ basebuf,
-            int tsize_max, int maxhap, int shortcuts)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int nw64 = ((maxhap + 63) >> 6) + 8;
-    unsigned* table = (unsigned*)smem;
-    unsigned short* nxt = (unsigned short*)(smem + (size_t)tsize_max * 4);
-    u64* h0 = (u64*)(smem + (size_t)tsize_max * 4 + (((size_t)maxhap + 2) * 2 + 7 & ~(size_t)7));
-    u64* h1 = h0 + nw64;
-    u64* eqp = h1 + nw64;
-    u64* nup = eqp + nw64;
-    int* s_scal = (int*)(nup + nw64);
-    unsigned char* s_gmin = (unsigned char*)((unsigned*)(s_scal + 4 + 16) + 32);
-    if (cnt[CNT_ERR] != 0) return;
-    const int w = blockIdx.x, lane = threadIdx.x;
-    unsigned char* rec = basebuf + (size_t)w * seed_base_stride(maxhap);
-    const int h = b.win_hap_begin[w];
-    if (b.win_hap_begin[w + 1] <= h) return;
-    const long long hoff = b.hap_off[h];
-    const int hapLen = (int)(b.hap_off[h + 1] - hoff);
-    const bool direct = hapLen > 4096;
-    int tsize = 64;
-    if (direct) tsize = 16384;
-    else while (tsize < hapLen + hapLen / 4) tsize <<= 1;
-    const unsigned tmask = (unsigned)tsize - 1u;
-    const int nch = (hapLen + 63) >> 6;
-    bool stop = false;
-    const bool have_index = seed_sweep(table, nxt, h0, h1, eqp, nup, s_scal, nw64, b.hap_seq + hoff, hapLen, hoff, true, gob, cnt, shortcuts, direct, tsize,
-                                       tmask, nch, stop);
-    const bool ok = !have_index && !stop && hapLen >= 16 && hapLen <= 4096;
-    if (lane == 0) {
-        hap_has_n[h] = (uint8_t)s_scal[0];
-        int* o = (int*)(rec + SEED_BASE_SCAL);
-        o[0] = s_scal[0]; o[1] = s_scal[1]; o[2] = s_scal[2]; o[3] = ok ? 1 : 0;
-    }
-    if (!ok) return;
-    unsigned* oseen = (unsigned*)(rec + SEED_BASE_SEEN);
-    for (int i = lane; i < 512; i += 64) oseen[i] = table[i];
-    u64* oplanes = (u64*)(rec + SEED_BASE_PLANES);
-    for (int i = lane; i < 4 * nw64; i += 64) oplanes[i] = h0[i];
-    unsigned char* ogmin = rec + SEED_BASE_PLANES + 32 * (size_t)nw64;
-    for (int t = lane; t < nch; t += 64) ogmin[t] = s_gmin[t];
-}
-
-__global__ void __launch_bounds__(64)
-k_seed(plat_window_batch b, const int32_t* __restrict__ hap_win, const int32_t* __restrict__ win_rows,
-       const long long* __restrict__ tile_off, const ReadInfo* __restrict__ rinfo,
-       const uint16_t* __restrict__ codes, uint8_t* __restrict__ gob, uint8_t* __restrict__ hap_has_n,
-       PairRec* __restrict__ pairs, Job* __restrict__ jobs, long long npairs, int extra_cap, long long* cnt,
-       SlowRec* __restrict__ slow_list, int tsize_max, int maxhap, int shortcuts,
-       int32_t* __restrict__ dense, long long segcap, const double* __restrict__ mapq_lut, double* __restrict__ out_ll,
-       int32_t* __restrict__ out_score, const unsigned char* __restrict__ basebuf)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int nw64 = ((maxhap + 63) >> 6) + 8;           // plane words incl. slack for the shifted window of a hypothesis
-    unsigned* table = (unsigned*)smem;
-    unsigned short* nxt = (unsigned short*)(smem + (size_t)tsize_max * 4);      // tsize_max = carve size >= 1024 dwords: the multiplicity maps overlay the table
-    u64* h0 = (u64*)(smem + (size_t)tsize_max * 4 + (((size_t)maxhap + 2) * 2 + 7 & ~(size_t)7));
-    u64* h1 = h0 + nw64;
-    u64* eqp = h1 + nw64;
-    u64* nup = eqp + nw64;
-    int* s_scal = (int*)(nup + nw64);                    // [0] has_n  [1] maxmult, then the gap-open table
-
-    // Workgroups go to the 8 XCDs round robin by their linear id, and each XCD has its own L2: with SEED_XCD (grid.x a multiple of 8) XCD x
-    // takes the x-th eighth of the haplotypes in order, so that the haplotypes of a window -- which all read the window's read planes and
-    // ReadInfo -- run on ONE XCD at about the same time and those bytes leave HBM once, not once per XCD.
-    int h = blockIdx.x;
-    if (shortcuts & SEED_XCD) {
-        const int per = (int)(gridDim.x >> 3);
-        h = (int)(blockIdx.x & 7u) * per + (int)(blockIdx.x >> 3);
-        if (h >= b.n_haps) return;
-    }
-    if (cnt[CNT_ERR] != 0) return;                       // an earlier stage refused the batch
-    const int w = hap_win[h];
-    const int tid = threadIdx.x, nthr = blockDim.x;
-    const int lane = tid & 63, wave = tid >> 6, nw = nthr >> 6;
-    {   // this workgroup's group of read chunks lies beyond the window's reads: nothing to do
-        const int Rw = b.win_read_begin[w + 1] - b.win_read_begin[w];
-        if (blockIdx.y > 0 && (int)blockIdx.y * SEED_CHUNKS * nw * 64 >= Rw) return;
-    }
-    const bool first_group = blockIdx.y == 0;            // writes the per-haplotype outputs (hapw, has_n)
-    const long long hoff = b.hap_off[h];
-    const int hapLen = (int)(b.hap_off[h + 1] - hoff);
-    const uint8_t* hs = b.hap_seq + hoff;
-
-    const bool direct = hapLen > 4096;
-    int tsize = 64;
-    if (direct) tsize = 16384;
-    else while (tsize < hapLen + hapLen / 4) tsize <<= 1;
-    const unsigned tmask = (unsigned)tsize - 1u;
-    const int nch = (hapLen + 63) >> 6;                  // chunks of 64 haplotype positions
-
-    // Setup, fast part: the proof of hypothesis A only needs the planes, nu and maxmult.  Multiplicities come from two
-    // 16384-bit maps over the 14-bit k-mer codes ("seen at least once / twice"), filled with one LDS atomicOr per k-mer,
-    // plus a 32-entry counting table for the few codes seen three times or more.  The maps overlay the k-mer index, which
-    // is only built (seed_build_index) when some pair of this workgroup needs a look-up: hypothesis B, the no-vote test,
-    // the exact vote, or more than 32 distinct codes of multiplicity >= 3.  (LDS per workgroup decides how many
-    // haplotypes a CU works on at once: 6 KB instead of 9.4 KB with a third map.)
-    unsigned char* s_gmin = (unsigned char*)((unsigned*)(s_scal + 4 + 16) + 32);     // [nw64] smallest gap-open penalty per chunk (seed_sweep)
-    bool stop = false, have_index = false, derived = false;
-    if (basebuf) {                                       // the window's first haplotype was swept by k_seed_base: derive this one from it if possible
-        const unsigned char* rec = basebuf + (size_t)w * seed_base_stride(maxhap);
-        const int hB = b.win_hap_begin[w];
-        const long long hoffB = b.hap_off[hB];
-        if (((const int*)(rec + SEED_BASE_SCAL))[3] != 0 && (int)(b.hap_off[hB + 1] - hoffB) == hapLen)
-            derived = seed_derive(rec, b.hap_seq + hoffB, gob + hoffB, table, h0, h1, eqp, nup, s_scal, s_gmin, nw64, hs, hapLen, h == hB,
-                                  first_group && h != hB, gob + hoff, cnt);
-    }
-    if (!derived) have_index = seed_sweep(table, nxt, h0, h1, eqp, nup, s_scal, nw64, hs, hapLen, hoff, first_group, gob, cnt, shortcuts, direct, tsize, tmask, nch, stop);
-    if (stop) return;
-    if (tid == 0 && first_group) hap_has_n[h] = (uint8_t)s_scal[0];
-    const int maxmult = s_scal[1];
-    const bool hap_plain = s_scal[2] == 0;               // only A, C, G, T, N: equal 2-bit codes of plain read bases mean equal bytes or a haplotype N
-
-    const int rb = b.win_read_begin[w], R = b.win_read_begin[w + 1] - rb;
-    const int hl = h - b.win_hap_begin[w];
-    const int hapStart = b.win_start[w] - b.win_flank[w];                   // chaplotype.pyx:606
-    const long long pbase = b.pair_off[w] + (long long)hl * R;
-    const u64* rd2 = (const u64*)(codes + tile_off[w]);
-    const int nkp = hapLen - 7;                          // haplotype k-mer positions 0..hapLen-8 (calign.pyx:109)
-
-    // reads are processed in chunks of 64 (one lane per read); blockIdx.y selects a group of SEED_CHUNKS chunks so that
-    // windows with thousands of reads (population mode) spread over many workgroups (each rebuilds the small index)
-    const int cbeg = (int)blockIdx.y * SEED_CHUNKS * nw * 64;
-    const int cend = min(R, cbeg + SEED_CHUNKS * nw * 64);
-    for (int c0 = cbeg + wave * 64; c0 < cend; c0 += nw * 64) {
-        const int rl = c0 + lane;
-        const bool valid = rl < R;
-        ReadInfo ri = ReadInfo{0, 0, 0, 0};
-        if (valid) ri = rinfo[rb + rl];
-        const int L = (int)(ri.lfm & 0xFFFFu);
-        const int rflags = (int)((ri.lfm >> 16) & 0xFFu);
-        const uint8_t mapq = (uint8_t)(ri.lfm >> 24);
-        const long long pidx = pbase + rl;
-        const bool skipped = (rflags & 1) != 0, tooshort = L < 7;
-        const int hq = h | ((rflags & 4) ? JOB_BIGQ : 0);                   // haplotype index + the read's add-flavour flag
-        const bool hapshort = valid && !skipped && !tooshort && hapLen < L + 15;
-        if (hapshort) set_err(cnt, PLAT_ERR_HAP_TOO_SHORT);
-        const bool live = valid && !skipped && !tooshort && !hapshort;
-        const int nk = live ? L - 7 : 0;
-        const int idx0 = min(ri.pos - hapStart, hapLen - L - 15);           // calign.pyx:252
-        const u64* col = rd2 + (valid ? rl : 0);
-
-        // ---- bit-parallel proof
-        const bool canfast = live && L <= 256;
-        int nCl = canfast ? (L + 63) >> 6 : 0, nCmax = nCl;
-#pragma unroll
-        for (int s2 = 32; s2 > 0; s2 >>= 1) nCmax = max(nCmax, __shfl_xor(nCmax, s2));
-        u64 r0[4], r1[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            r0[c] = c < nCl ? col[(long long)(2 * c) * R] : 0ull;
-            r1[c] = c < nCl ? col[(long long)(2 * c + 1) * R] : 0ull;
-        }
-        int dstar = idx0;
-        bool proven = false, triedB = false, exact = false;
-        u64 missA[4] = {0ull, 0ull, 0ull, 0ull}, uniqA[4] = {0ull, 0ull, 0ull, 0ull};   // of hypothesis A, when it is proven (see "ungapped" below)
-        bool provenA = false;
-        for (int attempt = 0; attempt < 2; ++attempt) {
-            const bool run = canfast && !proven && dstar >= 0 && (attempt == 0 || triedB);
-            if (__any(run)) {
-                const int wq = run ? (dstar >> 6) : 0, sb = dstar & 63;
-                const int nvalid = min(nk, nkp - dstar);                 // k-mers i < nvalid lie on haplotype positions
-                u64 Z[5], NU[4];
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    if (c < nCmax) {
-                        const u64 x = (funnel(h0[wq + c], h0[wq + c + 1], sb) ^ r0[c]) | (funnel(h1[wq + c], h1[wq + c + 1], sb) ^ r1[c]);
-                        Z[c] = ~x;
-                        NU[c] = funnel(nup[wq + c], nup[wq + c + 1], sb);
-                    } else { Z[c] = 0ull; NU[c] = 0ull; }
-                }
-                Z[4] = 0ull;
-                u64 P2[5];
-#pragma unroll
-                for (int c = 0; c < 4; ++c) P2[c] = Z[c] & ((Z[c] >> 1) | (Z[c + 1] << 63));
-                P2[4] = 0ull;
-                int C = 0, NUc = 0;
-                u64 U7[4];                               // k-mer i of the read equals the haplotype's at d*+i AND that k-mer is unique in the haplotype
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    U7[c] = 0ull;
-                    if (c < nCmax) {
-                        const u64 P4 = P2[c] & ((P2[c] >> 2) | (P2[c + 1] << 62));
-                        u64 P7 = P4 & ((P2[c] >> 4) | (P2[c + 1] << 60)) & ((Z[c] >> 6) | (Z[c + 1] << 58));
-                        const int nb = nvalid - 64 * c;
-                        const u64 msk = nb >= 64 ? ~0ull : (nb <= 0 ? 0ull : ((1ull << nb) - 1ull));
-                        P7 &= msk;
-                        C += __popcll(P7);
-                        NUc += __popcll(P7 & NU[c]);
-                        U7[c] = P7 & ~NU[c];
-                    }
-                }
-                const int X = NUc * (maxmult - 1) + (nk - C) * maxmult;
-                if (run && X < C) {
-                    proven = true;
-                    // does the whole read match the haplotype on d*?  (Z: one bit per base, 1 = equal codes)
-                    u64 miss = 0ull;
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        const int nb = L - 64 * c;
-                        const u64 mc = ~Z[c] & (nb >= 64 ? ~0ull : (nb <= 0 ? 0ull : ((1ull << nb) - 1ull)));
-                        miss |= mc;
-                        if (attempt == 0) { missA[c] = mc; uniqA[c] = U7[c]; }
-                    }
-                    exact = miss == 0ull;
-                    provenA = attempt == 0;
-                }
-            }
-            if (attempt == 0) {
-                // everything below needs k-mer look-ups: build the index now if this workgroup (= one wave) has not yet
-                if (!have_index && __any(live && !proven)) {
-                    seed_build_index(table, nxt, h0, h1, nup, s_scal, hapLen, nch, direct, tsize, tmask, false);
-                    have_index = true;
-                }
-                // hypothesis B for the lanes A could not prove: diagonal of the first haplotype-unique k-mer
-                if (canfast && !proven) {
-                    for (int i = 0; i < nk; ++i) {
-                        const unsigned hd = kmer_head(table, read_code(col, R, i), direct, tmask);
-                        if (hd != 0u && nxt[hd] == 0u) {
-                            const int d = (int)hd - i - 1;
-                            if (d != idx0 && d >= 0) { dstar = d; triedB = true; }
-                            break;
-                        }
-                    }
-                }
-                if (!__any(triedB)) break;
-            }
-        }
-        // no k-mer of the read occurs in the haplotype <=> maxcount == 0 (calign.pyx:222): decided, no candidate.
-        // (tested only for pairs the proof left open)
-        bool novote = false;
-        if (live && !proven) {
-            novote = true;
-            for (int i = 0; i < nk && novote; ++i)
-                if (kmer_head(table, read_code(col, R, i), direct, tmask) != 0u) novote = false;
-        }
-        const bool decided = !live || novote || proven;
-        int ncand = 0, cidx = idx0;
-        bool orig_in = false;
-        if (live && proven && dstar + L + 15 < hapLen) { ncand = 1; cidx = dstar; orig_in = (idx0 == dstar); }   // calign.pyx:228
-        // The read equals the haplotype on the one candidate diagonal: that DP scores 0 (no cost is negative and the
-        // all-match path costs 0; a haplotype N costs 0 as well, align.c:17,314-318) and calign.pyx:242-247 returns it
-        // at once.  No DP is launched for the pair.
-        const bool zero = (shortcuts & SHORTCUT_EXACT) && ncand == 1 && exact && hap_plain && !((rflags >> 1) & 1);
-        // ---- "ungapped": the read differs from the haplotype in 1..UNG_KMAX bases on the one candidate diagonal d*, which is also
-        // the mapping position, and NO other path of the band can be cheaper than paying those mismatches.  Then the single DP
-        // of the pair returns U = sum of the mismatching bases' qualities and is not launched.  Cost model (align.c:314-335,
-        // 466-484): a mismatch costs qual[y]; a deletion of l bases go[x] + 3 (l - 1); an insertion of l bases go[x] + 2 + 5 (l - 1);
-        // nothing is negative; the band is d*-8 .. d*+7 (needs d* >= 8), the path may start and end on any diagonal.
-        // The one fact every bound uses: where 7-mer i of the read equals the haplotype's 7-mer at d*+i and that 7-mer occurs
-        // ONCE in the haplotype, the read has a mismatch in [i, i+7) on every other diagonal; n such starts inside a stretch the
-        // path spends on ONE other diagonal give ceil(n/7) disjoint windows, together worth V(.) (each holds a mismatching base,
-        // a base costs >= the read's smallest quality m, all but n_low of its bases cost >= 20).  A gap opening costs >= G, the
-        // smallest gap-open penalty of the slice, and an insertion skips read bases: <= 8 when it leaves or rejoins d*, <= 15
-        // otherwise, so a gap in the middle of a stretch spoils <= 21 starts = 3 windows.
-        // A path is a chain of stretches ON d*, which pay exactly the mismatches p_j inside them, and EXCURSIONS, each of which
-        // dodges a run of mismatches j..j'.  If every possible excursion costs at least the qualities it dodges, and a path that
-        // never touches d* costs >= U, no path beats U.  Windows are counted per stretch between two mismatches (they cannot
-        // overlap across a mismatching base): W(a,b) = sum over those stretches of ceil(#unique-matching starts inside [a,b) / 7).
-        // A FURTHER gap inside an excursion spoils the windows it cuts or skips, at a price: a deletion or a one-base insertion
-        // one window for >= G, an insertion of 2..8 two for >= G+7, of 9..15 three for >= G+42; so spoiling windows costs
-        // >= v'' = min((G+7)/2, (G+42)/3) apiece, and windows are worth phi(n) = V(n) with its slopes capped at v''
-        // (= V itself once G >= 33):
-        //   never on d*                                     phi(W(0, L-6)) >= U
-        //   elsewhere, then on d* from after p_j            G + min(phi(W), 7 + phi(W-1)) >= q_1 + .. + q_j,  W = W(0, p_j-6): the gap
-        //                                                   that joins d* is a deletion or a one-base insertion, or a longer
-        //                                                   insertion that costs >= 7 more and skips <= 7 more starts
-        //   on d* up to a gap before p_j, then elsewhere    the same with W = W(p_j+1, L-6) and q_j + .. + q_k
-        //   leaves d* before p_j, rejoins after p_j'        two gaps = an insertion and a deletion of l bases each:
-        //                                                   2G + 8l - 6 + windows, i.e. >= 2G + min(2 + phi(W), 10 + phi(W-1));
-        //                                                   more gaps: >= 2G + max(G, phi(W-2));  W = W(p_j+1, p_j'-6);
-        //                                                   all >= q_j + .. + q_j'
-        // (haplotype without N, read of plain A/C/G/T: equal codes = equal bytes.)
-        int ung_score = -1;
-        int why = 0;                                     // (PLAT_SEED_DEBUG=512: why the pair reached the DP; counted below)
-        {
-            const int mq = (rflags >> 3) & 31;
-            // The proof's cost model is exact arithmetic; align.c adds in wrapping int16 ("no overflow checks", align.c:81).  A read whose
-            // quality sum allows a band cell to pass 0x7FFF (rflags bit 2, the flag that also picks the DP's add flavour, dp_core.hpp)
-            // is left to the DP, which wraps as the reference does.  (The exact-match shortcut above needs no such guard: re-biased
-            // values are unsigned, nothing is below 0, and the all-match path stays at 0 whatever the other cells do.)
-            const bool wrapfree = !(rflags & 4) || (shortcuts & SHORTCUT_BIGQ);      // (SHORTCUT_BIGQ: measurement only, PLAT_UNGAPPED_BIGQ=1)
-            const bool cand = (shortcuts & SHORTCUT_UNGAPPED) && ncand == 1 && orig_in && provenA && !exact && hap_plain && s_scal[0] == 0 &&
-                              !((rflags >> 1) & 1) && cidx >= 8 && L >= 32 && wrapfree;
-            int k = 0;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) k += __popcll(missA[c]);
-            const bool part = cand && k >= 1 && k <= UNG_KMAX;
-            why = !(ncand == 1) ? 1 : !orig_in ? 2 : !provenA ? 3 : exact ? 4 : k > UNG_KMAX ? 5 : !cand ? 8 : 0;
-            int kmw = part ? k : 0;                          // most mismatches any lane of the wave has to look at
-#pragma unroll
-            for (int s2 = 32; s2 > 0; s2 >>= 1) kmw = max(kmw, __shfl_xor(kmw, s2));
-            if (kmw > 0) {
-                int cw[4];
-#pragma unroll
-                for (int c = 0; c < 4; ++c) cw[c] = __popcll(uniqA[c]);
-                auto Cpre = [&](int x) -> int {              // unique-matching k-mer starts in [0, x)
-                    x = min(max(x, 0), 256);
-                    const int wi = x >> 6, sh = x & 63;
-                    const u64 wsel = wi == 0 ? uniqA[0] : wi == 1 ? uniqA[1] : wi == 2 ? uniqA[2] : wi == 3 ? uniqA[3] : 0ull;
-                    const int below = (wi > 0 ? cw[0] : 0) + (wi > 1 ? cw[1] : 0) + (wi > 2 ? cw[2] : 0) + (wi > 3 ? cw[3] : 0);
-                    return below + __popcll(wsel & ((1ull << sh) - 1ull));
-                };
-                auto Wof = [&](int n) -> int { return (max(n, 0) + 6) / 7; };
-                // n_low: how many of the read's bases may cost less than LOWQ (n disjoint windows are worth V(n) = mq min(n, n_low) + LOWQ max(n - n_low, 0))
-                const int nlow = (shortcuts & SHORTCUT_NLOW) ? (int)(ri.aux & 0xFFFFu) : 0x7FFF;
-                // the mismatches in read order (lanes with fewer than kmw repeat their last one with quality 0: its tests repeat too)
-                const uint8_t* rq = b.read_qual + b.read_off[rb + (valid ? rl : 0)];
-                u64 mm[4] = {missA[0], missA[1], missA[2], missA[3]};
-                int pp[UNG_KMAX], qq[UNG_KMAX];
-#pragma unroll
-                for (int j = 0; j < UNG_KMAX; ++j) {
-                    pp[j] = j ? pp[j - 1] : 0; qq[j] = 0;
-                    if (j < kmw) {                           // wave-uniform
-                        int pos = -1;
-#pragma unroll
-                        for (int c = 3; c >= 0; --c) if (mm[c]) pos = 64 * c + (int)__ffsll((long long)mm[c]) - 1;
-                        if (part && pos >= 0) { pp[j] = pos; qq[j] = rq[pos]; }
-#pragma unroll
-                        for (int c = 0; c < 4; ++c) if (pos >= 0 && (pos >> 6) == c) mm[c] &= mm[c] - 1ull;
-                    }
-                }
-                int U = 0;
-#pragma unroll
-                for (int j = 0; j < UNG_KMAX; ++j) U += qq[j];
-                const int st = cidx - 8;
-                int G = 127;
-                if (part) for (int t = st >> 6; t <= (st + L + 14) >> 6; ++t) G = min(G, (int)s_gmin[t]);
-                // everything below in units of 1/6 (v'' has a half and a third in it)
-                const int v6 = min(3 * (G + 7), 2 * (G + 42));
-                const int c_lo = min(6 * mq, v6), c_hi = min(6 * max(mq, (int)LOWQ), v6);
-                auto phi6 = [&](int n) -> int { n = max(n, 0); return c_lo * min(n, nlow) + c_hi * max(n - nlow, 0); };
-                // unique-matching starts before p_j - 6 and before p_j + 1 (none start in between: those 7-mers hold the mismatch)
-                int cm6[UNG_KMAX], cp1[UNG_KMAX];
-#pragma unroll
-                for (int j = 0; j < UNG_KMAX; ++j) {
-                    if (j < kmw) { cm6[j] = Cpre(pp[j] - 6); cp1[j] = Cpre(pp[j] + 1); }
-                    else { cm6[j] = cm6[j - (j > 0)]; cp1[j] = cp1[j - (j > 0)]; }
-                }
-                const int Ctot = Cpre(L - 6);
-                int Iw[UNG_KMAX];                            // windows between mismatch j and the next
-#pragma unroll
-                for (int j = 0; j + 1 < UNG_KMAX; ++j) Iw[j] = Wof(cm6[j + 1] - cp1[j]);
-                Iw[UNG_KMAX - 1] = 0;
-                int Wall = Wof(cm6[0]) + Wof(Ctot - cp1[UNG_KMAX - 1]);
-#pragma unroll
-                for (int j = 0; j + 1 < UNG_KMAX; ++j) Wall += Iw[j];
-                int bad = phi6(Wall) < 6 * U ? 10 : 0;       // never on d*
-                // an excursion at the head or the tail of the read: its gap next to d* is a deletion or a one-base insertion
-                // (no window lost) or a longer insertion (>= 7 more, one window lost)
-                auto edge = [&](int W, int T) -> bool { return 6 * (G - T) + min(phi6(W), 42 + phi6(W - 1)) >= 0; };
-                int Rs = 0, Qs = U, Wbefore = Wof(cm6[0]);   // windows before mismatch j
-#pragma unroll
-                for (int j = 0; j < UNG_KMAX; ++j) {
-                    if (j < kmw) {
-                        Rs += qq[j];
-                        if (!bad && !edge(Wbefore, Rs)) bad = 11;                     // elsewhere, then on d* from after p_j
-                        if (!bad && !edge(Wall - Wbefore, Qs)) bad = 12;              // on d* up to a gap before p_j, then elsewhere
-                        Wbefore += Iw[j];
-                        Qs -= qq[j];
-                        int T = qq[j], Wm = 0;
-                        if (!bad && 2 * G + 2 < T) bad = 13;                          // an excursion around p_j alone
-#pragma unroll
-                        for (int j2 = j + 1; j2 < UNG_KMAX; ++j2) {
-                            if (j2 < kmw) {
-                                T += qq[j2];
-                                Wm += Iw[j2 - 1];
-                                const int slack = 6 * (2 * G - T);
-                                const bool two = slack + 12 + phi6(Wm) >= 0 && slack + 60 + phi6(Wm - 1) >= 0;
-                                const bool more = slack + max(6 * G, phi6(Wm - 2)) >= 0;
-                                if (!bad && !(two && more)) bad = 14;
-                            }
-                        }
-                    }
-                }
-                if (part && !bad) ung_score = U;
-                else if (part) why = bad;
-            }
-        }
-        const bool ungapped = ung_score >= 0;
-        // extra job slot for (one candidate that is not the mapping position): one atomic per wave
-        int base = 0;
-        {
-            const bool need = decided && live && ncand == 1 && !orig_in && !zero;
-            const unsigned long long m = __ballot(need);
-            if (m) {
-                int wb = 0;
-                if (lane == 0) wb = (int)atomicAdd((unsigned long long*)&cnt[CNT_NEXTRA], (unsigned long long)__popcll(m));
-                wb = __shfl(wb, 0);
-                base = wb + __popcll(m & ((1ull << lane) - 1ull));
-                if (need && (long long)base + 1 <= (long long)extra_cap) jobs[npairs + base] = Job{ri.col, hq, idx0, L};
-            }
-        }
-        // Decided pairs: the ones that need no DP are finished here (skipped read: 0.0, chaplotype.pyx:345-346; read < 7 bp or exact
-        // match: score 0; ungapped alignment proven optimal: its score), the others leave a job in their slot.
-        // (SEED_LEAN, the asynchronous entry point: nobody asks for statistics afterwards, and k_finalize_dense only looks at pairs with
-        // a DP -- the 32 bytes of records of a finished pair, 7 pairs in 8 of a clean batch, are not written at all.)
-        bool prim = false;                                   // the pair's primary slot holds a DP
-        const bool recs = !(shortcuts & SEED_LEAN);
-        if (valid && decided) {
-            if (!live) {
-                const bool sk = skipped || hapshort;
-                if (recs) {
-                    pairs[pidx] = PairRec{0, 0, (int16_t)(sk ? -1 : -2), 0, mapq, {0, 0, 0}};
-                    jobs[pidx] = Job{ri.col, h, 0, 0};
-                }
-                out_ll[pidx] = sk ? 0.0 : loglik_of(0, mapq_lut, mapq);
-                if (out_score) out_score[pidx] = sk ? -1 : 0;
-            } else if (zero) {
-                if (recs) {
-                    pairs[pidx] = PairRec{0, L, (int16_t)-3, 0, mapq, {0, 0, 0}};
-                    jobs[pidx] = Job{ri.col, h, cidx, 0};
-                }
-                out_ll[pidx] = loglik_of(0, mapq_lut, mapq);
-                if (out_score) out_score[pidx] = 0;
-            } else if (ungapped) {
-                if (recs) {
-                    pairs[pidx] = PairRec{ung_score, L, (int16_t)-4, 0, mapq, {0, 0, 0}};
-                    jobs[pidx] = Job{ri.col, h, cidx, 0};
-                }
-                out_ll[pidx] = loglik_of(ung_score, mapq_lut, mapq);
-                if (out_score) out_score[pidx] = ung_score;
-            } else {
-                jobs[pidx] = Job{ri.col, hq, cidx, L};
-                pairs[pidx] = PairRec{base, idx0, (int16_t)ncand, (int16_t)(orig_in ? 0 : ncand), mapq, {0, 0, 0}};
-                prim = true;
-            }
-        }
-        if (shortcuts & 512) {                              // measurement only
-            for (int r = 0; r < 16; ++r) {
-                const unsigned long long m = __ballot(prim && why == r);
-                if (m && lane == 0) atomicAdd((unsigned long long*)&cnt[32 + r], (unsigned long long)__popcll(m));
-            }
-        }
-        {   // the wave's live job slots join the dense list: primary slots, then the extra ones, room reserved with one atomic
-            const bool extra = decided && live && ncand == 1 && !orig_in && !zero && valid && (long long)base + 1 <= (long long)extra_cap;
-            const unsigned long long m1 = __ballot(prim), m2 = __ballot(extra);
-            const int n1 = __popcll(m1), n2 = __popcll(m2);
-            if (n1 + n2) {
-                const int seg = w % DENSE_SEGS;
-                long long db = 0;
-                if (lane == 0) db = (long long)atomicAdd((unsigned long long*)dense_counter(cnt, seg), (unsigned long long)(n1 + n2));
-                db = ((long long)(unsigned)__shfl((int)db, 0)) | ((long long)__shfl((int)(db >> 32), 0) << 32);
-                if (db + n1 + n2 <= segcap) {
-                    const unsigned long long below = (1ull << lane) - 1ull;
-                    if (prim) dense[seg * segcap + db + __popcll(m1 & below)] = (int32_t)pidx;
-                    if (extra) dense[seg * segcap + db + n1 + __popcll(m2 & below)] = (int32_t)(npairs + base);
-                }
-            }
-        }
-        // ---- pairs that could not be decided go to the exact vote in k_seed_slow (one wave per pair, spread over the
-        // whole device: a tandem-repeat window would otherwise serialise all its reads on this one wave)
-        const unsigned long long todo = __ballot(valid && !decided);
-        if (todo) {
-            long long sb = 0;
-            if (lane == 0) sb = (long long)atomicAdd((unsigned long long*)&cnt[CNT_SLOW_SEED], (unsigned long long)__popcll(todo));
-            sb = ((long long)(unsigned)__shfl((int)sb, 0)) | ((long long)__shfl((int)(sb >> 32), 0) << 32);
-            if (valid && !decided) slow_list[sb + __popcll(todo & ((1ull << lane) - 1ull))] = SlowRec{h, rl};
-        }
     }
 }
 
-
-// ---- round 4: the seeding stage as TWO kernels -----------------------------------------------------------------------------------------
-// k_seed did two things per haplotype in one single-wave workgroup: the haplotype sweep (planes, gap-open bytes, multiplicity maps) and
-// the per-pair proofs with ONE LANE PER READ of the window -- 34..40 lanes of 64 on a 30x window of 150 bp reads, and that part is two
-// thirds of its vector instructions.  k_sweep keeps the first half and leaves what the proofs read in global memory (per haplotype:
-// flags, largest multiplicity, the planes h0 / h1 / nu, per-chunk gap-open minima: ~0.5 KB); k_pairs packs the window's (haplotype, read)
-// pairs DENSELY, 64 per wave whatever the number of reads, stages the <= SEED_NST haplotype records its pairs touch in LDS and runs the
-// same proofs.  The k-mer index of a haplotype is built in k_pairs only when a pair needs look-ups (hypothesis B, no-vote test), as before.
+// ---- the seeding stage is TWO kernels ---------------------------------------------------------------------------------------------
+// The haplotype sweep (planes, gap-open bytes, multiplicity maps) is work per HAPLOTYPE, the proofs are work per (haplotype, read) PAIR.
+// A single-wave workgroup per haplotype that did both with one lane per read of the window had 34..40 live lanes of 64 on a 30x window of
+// 150 bp reads, and the proofs are two thirds of the stage's vector instructions.  So k_sweep does the first half and leaves what the
+// proofs read in global memory (per haplotype: flags, largest multiplicity, the planes h0 / h1 / nu, per-chunk gap-open minima: ~0.5 KB);
+// k_pairs packs the window's (haplotype, read) pairs DENSELY, 64 per wave whatever the number of reads, stages the <= SEED_NST haplotype
+// records its pairs touch in LDS and runs the proofs.  The k-mer index of a haplotype is built in k_pairs, and only when a pair needs
+// look-ups (hypothesis B, no-vote test).
 constexpr int SEED_NST = 6;            // haplotype records staged per wave of k_pairs: 64 consecutive pairs of a window with R >= 13 reads
                                        // span at most 6 haplotypes; windows with fewer reads give a wave 5 whole haplotypes (5 R <= 60 pairs)
 __host__ __device__ __forceinline__ int seed_pairs_per_wave(int R) { return R >= 13 ? 64 : 5 * (R > 0 ? R : 1); }
@@ -1501,7 +857,7 @@ __host__ __device__ __forceinline__ size_t seed_state_stride(int maxhap) {
 
 __global__ void __launch_bounds__(64)
 k_sweep(plat_window_batch b, uint8_t* __restrict__ gob, uint8_t* __restrict__ hap_has_n, long long* cnt, int tsize_max, int maxhap, int shortcuts,
-        const unsigned char* __restrict__ basebuf, const int32_t* __restrict__ hap_win, unsigned char* __restrict__ state)
+        unsigned char* __restrict__ state)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int nw64 = ((maxhap + 63) >> 6) + 8;
@@ -1513,8 +869,11 @@ k_sweep(plat_window_batch b, uint8_t* __restrict__ gob, uint8_t* __restrict__ ha
     u64* nup = eqp + nw64;
     int* s_scal = (int*)(nup + nw64);
     unsigned char* s_gmin = (unsigned char*)((unsigned*)(s_scal + 4 + 16) + 32);
+    // Workgroups go to the 8 XCDs round robin by their linear id, and each XCD has its own L2: with SEED_XCD (grid.x a multiple of 8) XCD x
+    // takes the x-th eighth of the haplotypes in order.  The haplotypes of a window then run on ONE XCD, and k_pairs gives the x-th eighth
+    // of its waves to XCD x in the same way: most of the records written here are read through the L2 they were written to.
     int h = blockIdx.x;
-    if (shortcuts & SEED_XCD) {                          // haplotype h on XCD floor(8 h / n): see k_seed
+    if (shortcuts & SEED_XCD) {
         const int per = (int)(gridDim.x >> 3);
         h = (int)(blockIdx.x & 7u) * per + (int)(blockIdx.x >> 3);
         if (h >= b.n_haps) return;
@@ -1530,17 +889,8 @@ k_sweep(plat_window_batch b, uint8_t* __restrict__ gob, uint8_t* __restrict__ ha
     else while (tsize < hapLen + hapLen / 4) tsize <<= 1;
     const unsigned tmask = (unsigned)tsize - 1u;
     const int nch = (hapLen + 63) >> 6;
-    bool stop = false, derived = false;
-    if (basebuf) {                                       // PLAT_SEED_SHARE=1: derive from the window's first haplotype where possible (see seed_derive)
-        const int w = hap_win[h];
-        const unsigned char* rec = basebuf + (size_t)w * seed_base_stride(maxhap);
-        const int hB = b.win_hap_begin[w];
-        const long long hoffB = b.hap_off[hB];
-        if (((const int*)(rec + SEED_BASE_SCAL))[3] != 0 && (int)(b.hap_off[hB + 1] - hoffB) == hapLen)
-            derived = seed_derive(rec, b.hap_seq + hoffB, gob + hoffB, table, h0, h1, eqp, nup, s_scal, s_gmin, nw64, hs, hapLen, h == hB,
-                                  h != hB, gob + hoff, cnt);
-    }
-    if (!derived) seed_sweep(table, nxt, h0, h1, eqp, nup, s_scal, nw64, hs, hapLen, hoff, true, gob, cnt, shortcuts, direct, tsize, tmask, nch, stop);
+    bool stop = false;
+    seed_sweep(table, nxt, h0, h1, eqp, nup, s_scal, nw64, hs, hapLen, hoff, gob, cnt, shortcuts, direct, tsize, tmask, nch, stop);
     if (stop) return;
     unsigned char* rec = state + (size_t)h * seed_state_stride(maxhap);
     if (lane == 0) hap_has_n[h] = (uint8_t)s_scal[0];
@@ -1969,7 +1319,7 @@ __device__ __forceinline__ void wave_lds_sync() { __builtin_amdgcn_fence(__ATOMI
 // of the 27 us a pair cost -- linear probing at load 0.65, the slowest of 64 lanes sets each round's time); its waves then vote for one entry
 // each, each wave in its own diagonal counters, leaving the pair's arg-max diagonals in an LDS record.  Then the job slots and dense-list
 // entries of the whole group are reserved with ONE returning atomic per counter (before: two per pair on the same two addresses, ~23 k per
-// launch against the L2's ~90 per microsecond and address) and the waves write their pairs' jobs.  Same LDS carve as k_seed up to the
+// launch against the L2's ~90 per microsecond and address) and the waves write their pairs' jobs.  Same LDS carve as k_sweep up to the
 // counters, of which there is one set per wave.
 constexpr int SLOW_WAVES = 4, SLOW_GROUP = 32;
 __device__ unsigned long long g_slow_ticks[8];            // PLAT_SLOW_TIMING=1 (measurement): thread 0's 100 MHz ticks per phase, summed over groups
@@ -2333,7 +1683,7 @@ k_finalize_multi(const PairRec* __restrict__ pairs, const Job* __restrict__ jobs
     if (out_score) out_score[p] = best;
 }
 
-// The same over the dense list of live job slots (asynchronous entry point: k_seed left no record of the pairs it finished, SEED_LEAN):
+// The same over the dense list of live job slots (asynchronous entry point: k_pairs left no record of the pairs it finished, SEED_LEAN):
 // a pair with several candidate DPs has its primary slot in the list exactly once.
 __global__ void __launch_bounds__(256)
 k_finalize_dense(const PairRec* __restrict__ pairs, const Job* __restrict__ jobs, const int32_t* __restrict__ job_score,
@@ -2445,8 +1795,8 @@ PLAT_EXPORT int plat_dp_batch(plat_ctx* ctx, int n, int lmax, const uint8_t* hap
 }
 
 static int align_seed_launch(plat_ctx* ctx, const plat_window_batch& b, hipStream_t st, long long* cnt, int maxhap,
-                             int maxread, int maxR, long long npairs, int extra_cap, const int32_t* hap_win, const int32_t* win_rows,
-                             const long long* tile_off, int shortcuts, int32_t* dense, long long segcap, double* out_ll, int32_t* out_score,
+                             int maxread, long long npairs, int extra_cap, const int32_t* hap_win, const long long* tile_off,
+                             int shortcuts, int32_t* dense, long long segcap, double* out_ll, int32_t* out_score,
                              const int32_t* wave_win, const int32_t* wave_first, long long wave_cap)
 {
     int tsize_max = 64;                                        // in dwords
@@ -2456,7 +1806,7 @@ static int align_seed_launch(plat_ctx* ctx, const plat_window_batch& b, hipStrea
     const int cw = (maxhap + maxread + 8 + 1) & ~1;            // 16-bit diagonal counters of the exact vote, even count
     const size_t nw64 = (((size_t)maxhap + 63) >> 6) + 8;
     const size_t lds0 = (size_t)tsize_max * 4 + ((((size_t)maxhap + 2) * 2 + 7) & ~(size_t)7) + 4 * nw64 * 8 + 16 + 64 + 128;
-    const size_t lds = lds0 + ((nw64 + 15) & ~(size_t)15);    // k_seed: + one byte per chunk of 64 positions (gap-open minima)
+    const size_t lds = lds0 + ((nw64 + 15) & ~(size_t)15);    // k_sweep: + one byte per chunk of 64 positions (gap-open minima)
     int slow_group = 8;                                         // entries per workgroup round (<= SLOW_GROUP); PLAT_SLOW_GROUP / PLAT_SLOW_WAVES: measurements
     if (const char* eg = getenv("PLAT_SLOW_GROUP")) slow_group = atoi(eg) > 0 && atoi(eg) <= SLOW_GROUP ? atoi(eg) : slow_group;
     int slow_waves = SLOW_WAVES;                                // (a set of diagonal counters per wave; fewer waves when long haplotypes make the sets large)
@@ -2464,61 +1814,31 @@ static int align_seed_launch(plat_ctx* ctx, const plat_window_batch& b, hipStrea
     while (slow_waves > 1 && lds0 + (size_t)slow_waves * (size_t)cw * 2 > 64 * 1024) slow_waves >>= 1;
     const size_t lds_slow = lds0 + (size_t)slow_waves * (size_t)cw * 2;
     if (lds_slow > 160 * 1024 || lds > 160 * 1024) return PLAT_ERR_HAP_TOO_LONG;
-    if (lds > 48 * 1024) {
-        PLAT_HIP(ctx, hipFuncSetAttribute((const void*)k_seed, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        PLAT_HIP(ctx, hipFuncSetAttribute((const void*)k_seed_base, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    }
     if (lds_slow > 48 * 1024)
         PLAT_HIP(ctx, hipFuncSetAttribute((const void*)k_seed_slow, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_slow));
-    // PLAT_SEED_SHARE=1: the windows' first haplotypes are swept once (k_seed_base) and the others derived from them where they can be.
-    // Built, verified and measured in round 3: a quarter fewer vector instructions in k_seed and the same time -- a wave's time is its
-    // chain of latencies, and deriving has as many round trips as sweeping; with k_seed_base's launch on top it is OFF by default.
-    const char* e_sh = getenv("PLAT_SEED_SHARE");          // (read per call)
-    const bool share = maxhap <= 4096 && !(shortcuts & 0x300) && e_sh && e_sh[0] == '1';
-    unsigned char* basebuf = nullptr;
-    if (share) {
-        int rcb = plat_reserve(ctx, ctx->seedbase, (size_t)b.n_windows * seed_base_stride(maxhap) + 64);
-        if (rcb) return rcb;
-        basebuf = (unsigned char*)ctx->seedbase.ptr;
-        hipLaunchKernelGGL(k_seed_base, dim3(b.n_windows), dim3(64), lds, st, b, (uint8_t*)ctx->hapw.ptr, (uint8_t*)ctx->hap_flags.ptr, cnt, basebuf,
-                           tsize_max, maxhap, shortcuts);
-    }
-    // one wave per workgroup (the lazy index build is wave-local); blockIdx.y = group of SEED_CHUNKS x 64 reads
-    const int ngroups = (maxR + SEED_CHUNKS * 64 - 1) / (SEED_CHUNKS * 64);
     const char* e_x = getenv("PLAT_SEED_XCD");             // (read per call; 0 = haplotype h on workgroup h)
     const bool xcd = !(e_x && e_x[0] == '0') && b.n_haps >= 64;
     if (xcd) shortcuts |= SEED_XCD;
     const unsigned gx = xcd ? (unsigned)((b.n_haps + 7) / 8) * 8u : (unsigned)b.n_haps;
-    ctx->ev_split = 0;
-    if (!wave_win)
-        hipLaunchKernelGGL(k_seed, dim3(gx, ngroups > 0 ? ngroups : 1), dim3(64), lds, st, b, hap_win, win_rows, tile_off,
-                           (const ReadInfo*)ctx->rinfo.ptr, (const uint16_t*)ctx->codes.ptr, (uint8_t*)ctx->hapw.ptr,
-                           (uint8_t*)ctx->hap_flags.ptr, (PairRec*)ctx->pair_rec.ptr, (Job*)ctx->jobs.ptr, npairs, extra_cap, cnt,
-                           (SlowRec*)ctx->slow.ptr, tsize_max, maxhap, shortcuts, dense, segcap,
-                           (const double*)ctx->d_mapq_lut, out_ll, out_score, (const unsigned char*)basebuf);
-    else {
-        // the seeding stage as two kernels: the haplotype sweeps, then the (haplotype, read) pairs packed 64 to a wave
-        const size_t stride = seed_state_stride(maxhap);
-        int rcs = plat_reserve(ctx, ctx->seedstate, (size_t)(b.n_haps + SEED_NST + 1) * stride + 64);
-        if (rcs) return rcs;
-        const size_t lds_pairs = (size_t)tsize_max * 4 + ((((size_t)maxhap + 2) * 2 + 15) & ~(size_t)15) + (size_t)SEED_NST * stride + 64;
-        if (lds_pairs > 160 * 1024) return PLAT_ERR_HAP_TOO_LONG;
-        if (lds > 48 * 1024) PLAT_HIP(ctx, hipFuncSetAttribute((const void*)k_sweep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        if (lds_pairs > 48 * 1024) PLAT_HIP(ctx, hipFuncSetAttribute((const void*)k_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pairs));
-        { PLAT_KT_BEGIN(ctx, PLAT_KT_SWEEP, st); hipLaunchKernelGGL(k_sweep, dim3(gx), dim3(64), lds, st, b, (uint8_t*)ctx->hapw.ptr, (uint8_t*)ctx->hap_flags.ptr, cnt, tsize_max, maxhap, shortcuts,
-                           (const unsigned char*)basebuf, hap_win, (unsigned char*)ctx->seedstate.ptr); PLAT_KT_END(ctx, PLAT_KT_SWEEP, st); }
-        PLAT_EV(ctx, 8, st);
-        ctx->ev_split = 1;
-        if (!(shortcuts & 256)) {                              // (PLAT_SEED_DEBUG=256: the sweeps alone)
-            const bool xw = (shortcuts & SEED_XCD) != 0;
-            const unsigned gp = (unsigned)(xw ? ((wave_cap + 7) / 8) * 8 : wave_cap);
-            { PLAT_KT_BEGIN(ctx, PLAT_KT_PAIRS, st); hipLaunchKernelGGL(k_pairs, dim3(gp > 0 ? gp : 1), dim3(64), lds_pairs, st, b, wave_win, wave_first, tile_off, (const ReadInfo*)ctx->rinfo.ptr,
-                               (const uint16_t*)ctx->codes.ptr, (PairRec*)ctx->pair_rec.ptr, (Job*)ctx->jobs.ptr, npairs, extra_cap, cnt,
-                               (SlowRec*)ctx->slow.ptr, tsize_max, maxhap, shortcuts, dense, segcap, (const double*)ctx->d_mapq_lut, out_ll, out_score,
-                               (const unsigned char*)ctx->seedstate.ptr); PLAT_KT_END(ctx, PLAT_KT_PAIRS, st); }
-        }
+    // the haplotype sweeps (one wave per workgroup), then the (haplotype, read) pairs packed 64 to a wave
+    const size_t stride = seed_state_stride(maxhap);
+    int rcs = plat_reserve(ctx, ctx->seedstate, (size_t)(b.n_haps + SEED_NST + 1) * stride + 64);
+    if (rcs) return rcs;
+    const size_t lds_pairs = (size_t)tsize_max * 4 + ((((size_t)maxhap + 2) * 2 + 15) & ~(size_t)15) + (size_t)SEED_NST * stride + 64;
+    if (lds_pairs > 160 * 1024) return PLAT_ERR_HAP_TOO_LONG;
+    if (lds > 48 * 1024) PLAT_HIP(ctx, hipFuncSetAttribute((const void*)k_sweep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (lds_pairs > 48 * 1024) PLAT_HIP(ctx, hipFuncSetAttribute((const void*)k_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pairs));
+    { PLAT_KT_BEGIN(ctx, PLAT_KT_SWEEP, st); hipLaunchKernelGGL(k_sweep, dim3(gx), dim3(64), lds, st, b, (uint8_t*)ctx->hapw.ptr, (uint8_t*)ctx->hap_flags.ptr, cnt, tsize_max, maxhap, shortcuts,
+                       (unsigned char*)ctx->seedstate.ptr); PLAT_KT_END(ctx, PLAT_KT_SWEEP, st); }
+    PLAT_EV(ctx, 8, st);
+    if (!(shortcuts & 256)) {                                  // (PLAT_SEED_DEBUG=256: the sweeps alone)
+        const unsigned gp = (unsigned)(xcd ? ((wave_cap + 7) / 8) * 8 : wave_cap);
+        { PLAT_KT_BEGIN(ctx, PLAT_KT_PAIRS, st); hipLaunchKernelGGL(k_pairs, dim3(gp > 0 ? gp : 1), dim3(64), lds_pairs, st, b, wave_win, wave_first, tile_off, (const ReadInfo*)ctx->rinfo.ptr,
+                           (const uint16_t*)ctx->codes.ptr, (PairRec*)ctx->pair_rec.ptr, (Job*)ctx->jobs.ptr, npairs, extra_cap, cnt,
+                           (SlowRec*)ctx->slow.ptr, tsize_max, maxhap, shortcuts, dense, segcap, (const double*)ctx->d_mapq_lut, out_ll, out_score,
+                           (const unsigned char*)ctx->seedstate.ptr); PLAT_KT_END(ctx, PLAT_KT_PAIRS, st); }
     }
-    PLAT_EV(ctx, 5, st);                                       // k_seed alone: ev[1] .. ev[5]
+    PLAT_EV(ctx, 5, st);                                       // k_sweep + k_pairs: ev[1] .. ev[5], ev[8] between the two
     { PLAT_KT_BEGIN(ctx, PLAT_KT_SEED_SLOW, st); hipLaunchKernelGGL(k_seed_slow, dim3(2048), dim3(64 * slow_waves), lds_slow, st, b, hap_win, tile_off, (const ReadInfo*)ctx->rinfo.ptr,
                        (const uint16_t*)ctx->codes.ptr, (PairRec*)ctx->pair_rec.ptr, (Job*)ctx->jobs.ptr, npairs, extra_cap, cnt,
                        (const SlowRec*)ctx->slow.ptr, tsize_max, maxhap, cw, dense, segcap, getenv("PLAT_SLOW_TIMING") ? 1 : 0, slow_group); PLAT_KT_END(ctx, PLAT_KT_SEED_SLOW, st); }
@@ -2589,8 +1909,6 @@ static int align_impl(plat_ctx* ctx, const plat_window_batch* batch, const plat_
     }
     // waves of k_pairs: <= n_pairs / 64 + n_haps / 5 + n_windows (64 pairs per wave; windows with < 13 reads give a wave 5 whole haplotypes)
     // (asynchronous: the caller stated n_pairs, so the wave map is sized and built right here; synchronous: after the read-back below)
-    const char* e_fused = getenv("PLAT_SEED_FUSED");           // =1: rounds 1-3's single seeding kernel (k_seed) instead of k_sweep + k_pairs (read per call)
-    const bool seed_fused = e_fused && e_fused[0] == '1';
     auto wave_cap_for = [&](long long np) { return std::min<long long>(np / 64 + b.n_haps / 5 + b.n_windows + 8, 0x7FFFFF00ll); };
     long long wave_cap = 0;
     int32_t* wave_win = nullptr;
@@ -2603,7 +1921,7 @@ static int align_impl(plat_ctx* ctx, const plat_window_batch* batch, const plat_
         wave_win = wave_first + b.n_windows + 8;
         return PLAT_OK;
     };
-    if (async && !seed_fused && (rc = reserve_wave_map(hv.n_pairs))) return rc;
+    if (async && (rc = reserve_wave_map(hv.n_pairs))) return rc;
     { PLAT_KT_BEGIN(ctx, PLAT_KT_TILE_SCAN, st); hipLaunchKernelGGL(k_tile_scan, dim3(1), dim3(1024), 0, st, b, win_rows, tile_off, cnt, hv, async ? 1 : 0, wave_win, wave_first, wave_cap); PLAT_KT_END(ctx, PLAT_KT_TILE_SCAN, st); }
     PLAT_HIP(ctx, hipGetLastError());
     int64_t* hb = ctx->h_readback;
@@ -2616,7 +1934,7 @@ static int align_impl(plat_ctx* ctx, const plat_window_batch* batch, const plat_
         hv.max_hap_len = (int)hb[CNT_MAXHAP]; hv.max_read_len = (int)hb[CNT_MAXREAD]; hv.max_reads_per_window = (int)hb[CNT_MAXH];
         hv.hap_blob_len = hb[CNT_HAPBLOB]; hv.n_pairs = hb[CNT_NPAIRS]; hv.read_blob_len = hb[CNT_READBLOB];
         tile_total = hb[CNT_TILE_TOTAL];
-        if (!seed_fused && hv.n_pairs > 0) {                   // the wave map of k_pairs, now that the number of pairs is known (the scan again: same offsets)
+        if (hv.n_pairs > 0) {                                 // the wave map of k_pairs, now that the number of pairs is known (the scan again: same offsets)
             if ((rc = reserve_wave_map(hv.n_pairs))) return rc;
             { PLAT_KT_BEGIN(ctx, PLAT_KT_TILE_SCAN, st); hipLaunchKernelGGL(k_tile_scan, dim3(1), dim3(1024), 0, st, b, win_rows, tile_off, cnt, hv, 0, wave_win, wave_first, wave_cap); PLAT_KT_END(ctx, PLAT_KT_TILE_SCAN, st); }
         }
@@ -2664,7 +1982,7 @@ static int align_impl(plat_ctx* ctx, const plat_window_batch* batch, const plat_
         const int no_ungapped = e_ung && e_ung[0] == '1';
         const char* e_ex = getenv("PLAT_NO_EXACT");        // every reference DP is then run (bench.py's gcups_all_dp)
         const int no_exact = e_ex && e_ex[0] == '1';
-        const char* e_dbg = getenv("PLAT_SEED_DEBUG");     // measurement only: 256 = k_seed stops after the haplotype sweep (results are garbage)
+        const char* e_dbg = getenv("PLAT_SEED_DEBUG");     // measurement only: 256 = the seeding stops after the haplotype sweeps (results are garbage)
         const char* e_nl = getenv("PLAT_NO_NLOW");
         const char* e_bq = getenv("PLAT_UNGAPPED_BIGQ");   // measurement only: lets the ungapped proof take reads in the wrap regime too (tools/ungapped_crosscheck.py --bigq)
         const int shortcuts = ((!calc_flank_score && !no_ungapped) ? SHORTCUT_UNGAPPED : 0) | (no_exact ? 0 : SHORTCUT_EXACT) |
@@ -2673,7 +1991,7 @@ static int align_impl(plat_ctx* ctx, const plat_window_batch* batch, const plat_
         // the dense list of live job slots is built by the seeding kernels themselves (DENSE_SEGS segments, each able to hold every slot)
         const long long segcap = npairs + extra_cap;
         if ((rc = plat_reserve(ctx, ctx->dense, ((size_t)segcap * DENSE_SEGS + 64) * sizeof(int32_t)))) return rc;
-        if ((rc = align_seed_launch(ctx, b, st, cnt, maxhap, maxread, maxR, npairs, (int)extra_cap, hap_win, win_rows, tile_off,
+        if ((rc = align_seed_launch(ctx, b, st, cnt, maxhap, maxread, npairs, (int)extra_cap, hap_win, tile_off,
                                     shortcuts, (int32_t*)ctx->dense.ptr, segcap, out_loglik, out_score, wave_win, wave_first, wave_cap))) return rc;
         njobs = npairs + extra_cap;
         if (async) break;                      // job overflow is caught on the device and reported by plat_stream_sync
@@ -2763,7 +2081,7 @@ static int align_impl(plat_ctx* ctx, const plat_window_batch* batch, const plat_
         PLAT_HIP(ctx, hipMemcpyAsync(hb, cnt, 64 * sizeof(long long), hipMemcpyDeviceToHost, st));
         PLAT_HIP(ctx, hipStreamSynchronize(st));
         if (getenv("PLAT_SEED_DEBUG") && (atoi(getenv("PLAT_SEED_DEBUG")) & 512)) {
-            fprintf(stderr, "k_seed, pairs that left a DP job, by reason:");
+            fprintf(stderr, "k_pairs, pairs that left a DP job, by reason:");
             for (int r = 0; r < 16; ++r) fprintf(stderr, " %lld", (long long)hb[32 + r]);
             fprintf(stderr, "\n");
         }

@@ -66,7 +66,7 @@ PLAT_EXPORT int plat_ctx_destroy(plat_ctx* ctx) {
     if (!ctx) return PLAT_ERR_INVALID;
     hipError_t e;
     plat_scratch* all[] = {&ctx->hapw, &ctx->tile, &ctx->codes, &ctx->rinfo, &ctx->hap_flags, &ctx->pair_rec,
-                           &ctx->jobs, &ctx->job_score, &ctx->counters, &ctx->asm_scratch, &ctx->tb, &ctx->slow, &ctx->dense, &ctx->pop_scratch, &ctx->seedbase, &ctx->merge_tab, &ctx->seedmap, &ctx->seedstate, &ctx->asm_sig};
+                           &ctx->jobs, &ctx->job_score, &ctx->counters, &ctx->asm_scratch, &ctx->tb, &ctx->slow, &ctx->dense, &ctx->pop_scratch, &ctx->merge_tab, &ctx->seedmap, &ctx->seedstate, &ctx->asm_sig};
     for (plat_scratch* s : all)
         if (s->ptr) { e = hipFree(s->ptr); (void)e; }
     if (ctx->d_mapq_lut) { e = hipFree(ctx->d_mapq_lut); (void)e; }
@@ -104,10 +104,8 @@ PLAT_EXPORT int plat_profile_last(plat_ctx* ctx, plat_profile* out) {
         PLAT_HIP(ctx, hipEventElapsedTime(&out->ms_prepare, ctx->ev[0], ctx->ev[1]));
         PLAT_HIP(ctx, hipEventElapsedTime(&out->ms_seed, ctx->ev[1], ctx->ev[2]));
         PLAT_HIP(ctx, hipEventElapsedTime(&out->ms_seed_kernel, ctx->ev[1], ctx->ev[5]));
-        if (ctx->ev_split) {
-            PLAT_HIP(ctx, hipEventElapsedTime(&out->ms_sweep, ctx->ev[1], ctx->ev[8]));
-            PLAT_HIP(ctx, hipEventElapsedTime(&out->ms_pairs, ctx->ev[8], ctx->ev[5]));
-        }
+        PLAT_HIP(ctx, hipEventElapsedTime(&out->ms_sweep, ctx->ev[1], ctx->ev[8]));
+        PLAT_HIP(ctx, hipEventElapsedTime(&out->ms_pairs, ctx->ev[8], ctx->ev[5]));
         PLAT_HIP(ctx, hipEventElapsedTime(&out->ms_dp, ctx->ev[2], ctx->ev[3]));
         PLAT_HIP(ctx, hipEventElapsedTime(&out->ms_finalize, ctx->ev[3], ctx->ev[4]));
         out->dp_jobs = ctx->prof_dp_jobs;

@@ -512,7 +512,7 @@ def test_dp_add_flavours_agree_with_oracle(eng, oracle):
 
 
 def _adversarial_batch(seed, n_windows=260, gapped=False, bigq=False):
-    """Windows built to stress k_seed's ungapped-alignment proof: references with homopolymers and tandem repeats (cheap gaps,
+    """Windows built to stress k_pairs' ungapped-alignment proof: references with homopolymers and tandem repeats (cheap gaps,
     non-unique k-mers) and N runs, reads of 36..250 bp with 0..3 substitutions anywhere -- first and last bases included --, read
     N's, low-quality tails, quality minima down to 0, haplotypes differing by SNPs next to repeats.  gapped: a third of the reads
     also carry a 1..4 base insertion or deletion (often within 20 bases of an end, where the ungapped alignment shows only a
@@ -595,7 +595,7 @@ def _adversarial_batch(seed, n_windows=260, gapped=False, bigq=False):
 
 
 def test_ungapped_shortcut_equals_the_dp_everywhere(eng, oracle):
-    """k_seed finishes pairs whose read differs from the haplotype in one or two bases without a DP when it can prove that no
+    """k_pairs finishes pairs whose read differs from the haplotype in one or two bases without a DP when it can prove that no
     other path of the band is cheaper.  Every score must equal what the DP gives for the same pair (PLAT_NO_UNGAPPED=1 sends
     all of them through the DP), on a stress batch and on BASELINE config 2; a sample is checked against the oracle too."""
     import os
@@ -743,55 +743,31 @@ dist.destroy_process_group()
     assert "MERGED a,b,c" in r.stdout
 
 
-def test_haplotypes_derived_from_the_windows_first_one_give_the_same_scores(eng):
-    """PLAT_SEED_SHARE=1 (off by default): k_seed_base sweeps the first haplotype of every window once, k_seed derives the
-    window's other haplotypes from it (patched planes, conservative uniqueness flags) instead of sweeping them.  Scores and likelihoods
-    are those of the default path on config 2, the hard workload and the stress batches; only the number of DPs launched may grow."""
-    import os
-    from platypus_amd import synth
-    for hb in (synth.config2(1500, seed=9), synth.config2_hard(800, seed=11), _adversarial_batch(5), _adversarial_batch(6, gapped=True), synth.config5(8, 20)):
-        res = {}
-        for mode in ("0", "1"):
-            os.environ["PLAT_SEED_SHARE"] = mode
-            try:
-                db = eng.upload(hb)
-                st = eng.align(db, want_stats=True)
-                eng.synchronize()
-                res[mode] = (db.score.cpu().numpy()[:hb.n_pairs].copy(), db.loglik.cpu().numpy()[:hb.n_pairs].copy(), int(st.n_dp_launched), int(st.n_dp_reference))
-            finally:
-                os.environ.pop("PLAT_SEED_SHARE", None)
-        assert np.array_equal(res["0"][0], res["1"][0]) and np.array_equal(res["0"][1], res["1"][1])
-        assert res["0"][3] == res["1"][3] and res["0"][2] <= res["1"][2] <= 1.02 * res["0"][2] + 50
-
-
-def test_two_kernel_seeding_equals_the_fused_kernel(eng):
-    """Round 4: the seeding stage is k_sweep (per haplotype) + k_pairs ((haplotype, read) pairs packed 64 to a wave, up to six haplotype
-    records staged per wave, the k-mer index built per staged haplotype on demand); PLAT_SEED_FUSED=1 is rounds 1-3's single kernel.
-    Same scores, likelihoods, reference DPs and launched DPs -- on config 2, the hard workload, the stress batches (tandem repeats: many
-    index builds and slow-path pairs), a population batch (thousands of reads per window) and windows with few reads (R < 13: five whole
-    haplotypes per wave), through both entry points."""
-    import os
+def test_pair_packing_of_the_seeding_stage_against_the_oracle(eng, oracle):
+    """The seeding stage is k_sweep (per haplotype) + k_pairs ((haplotype, read) pairs packed 64 to a wave, up to six haplotype records
+    staged per wave, the k-mer index built per staged haplotype on demand).  Scores and log-likelihoods bit-identical to the oracle, and
+    the same log-likelihoods through both entry points -- on config 2 and the hard workload (every fifth window), and on every window of
+    the stress batches (tandem repeats: many index builds and slow-path pairs), a population batch (hundreds of reads per window) and
+    windows with few reads (R < 13: five whole haplotypes per wave; ~15 reads: 64 pairs span five or six haplotypes), where the number
+    of reference DPs is pinned too."""
     from platypus_amd import synth
     few = synth.make_snp_windows(300, 21, read_len=150, depth=4)    # windows of ~5 reads
-    for hb in (synth.config2(1500, seed=9), synth.config2_hard(800, seed=11), _adversarial_batch(5), _adversarial_batch(6, gapped=True),
-               synth.config5(8, 20), few, synth.make_snp_windows(300, 22, read_len=150, depth=12)):      # (~15 reads: 64 pairs span five or six haplotypes)
-        res = {}
-        for mode in ("0", "1"):
-            os.environ["PLAT_SEED_FUSED"] = mode
-            try:
-                db = eng.upload(hb)
-                st = eng.align(db, want_stats=True)
-                eng.synchronize()
-                sync = (db.score.cpu().numpy()[:hb.n_pairs].copy(), db.loglik.cpu().numpy()[:hb.n_pairs].copy(), int(st.n_dp_launched), int(st.n_dp_reference))
-                db2 = eng.upload(hb)
-                eng.align_async(db2)
-                eng.synchronize()
-                res[mode] = sync + (db2.loglik.cpu().numpy()[:hb.n_pairs].copy(),)
-            finally:
-                os.environ.pop("PLAT_SEED_FUSED", None)
-        assert np.array_equal(res["0"][0], res["1"][0]) and np.array_equal(res["0"][1], res["1"][1])
-        assert res["0"][2:4] == res["1"][2:4]
-        assert np.array_equal(res["0"][4], res["0"][1]) and np.array_equal(res["1"][4], res["1"][1])
+    for hb, step in ((synth.config2(1500, seed=9), 5), (synth.config2_hard(800, seed=11), 5), (_adversarial_batch(5), 1),
+                     (_adversarial_batch(6, gapped=True), 1), (synth.config5(8, 20), 1), (few, 1),
+                     (synth.make_snp_windows(300, 22, read_len=150, depth=12), 1)):      # (~15 reads)
+        db, st, ll, sc = run_align(eng, hb)
+        db2 = eng.upload(hb)
+        eng.align_async(db2)
+        eng.synchronize()
+        assert np.array_equal(db2.loglik.cpu().numpy()[:hb.n_pairs], ll)
+        if step == 1:
+            check_against_oracle(oracle, hb, ll, sc, st)
+            continue
+        windows = range(0, hb.n_windows, step)
+        for w, (oll, osc, _) in zip(windows, oracle_windows(oracle, hb, windows)):
+            a, b = hb.pair_off[w], hb.pair_off[w + 1]
+            assert np.array_equal(sc[a:b].reshape(osc.shape), osc), "scores differ in window %d" % w
+            assert np.array_equal(ll[a:b].reshape(oll.shape), oll), "log-likelihoods differ in window %d" % w
 
 
 def test_region_text_exchange_over_rccl_with_two_ranks():

@@ -253,7 +253,7 @@ def config4(device, indices, region_len, workers, per_chunk, repeats=1, n_sample
     if nwarm:                                                                 # every worker's scratch buffers at full size, code paths warm
         # The untimed pass also COUNTS: with plat_caller_count_cells on, every likelihood batch goes through the synchronous entry point,
         # whose statistics kernels count the fastAlignmentRoutine calls the reference would make and their band cells (the GCUPS
-        # numerator) and the DPs the device ran, and the live kernel timers (HIP events) give k_seed / k_dp_jobs durations per batch.  The
+        # numerator) and the DPs the device ran, and the live kernel timers (HIP events) give k_sweep + k_pairs / k_dp_jobs durations per batch.  The
         # timed runs below call the same regions through the asynchronous entry point, counting nothing.
         nc.count_cells(True)
         nc.call_stream(nwarm, src.load_fn, src.h, names, default_options(**(options_kw or {})), n_slots, loaders)

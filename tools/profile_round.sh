@@ -13,7 +13,7 @@
 #   mapa    tools/ubench/dp_mapping_a.hip: mapping A of the DP, bit exact, against the library -> $TAG_dp_mapping_a.json
 #   pmc2    PMC passes of config 2 (FETCH_SIZE | WRITE_SIZE | SQ counters; one pass per set, only --kernel-trace next to --pmc)
 #   pmc3    PMC passes of the assembler (FETCH | WRITE | SQ | wait counters)
-#   pmcseed three SQ passes over k_seed / k_dp_jobs / k_prep_reads (instruction mix, waits, LDS conflicts)
+#   pmcseed three SQ passes over k_sweep / k_pairs / k_dp_jobs / k_prep_reads (instruction mix, waits, LDS conflicts)
 #   dpstall where k_dp_jobs' wave cycles go: parked on waits / issue stalls / active (SQ counters), config 2 as it runs and with every DP executed
 #   nextk   kernel stats of the "next row" kernels (tools/next_kernels.py)
 #   line    the default bench line and bench.py --config 3/4/5 with --full, the two-rank launches on the one GPU

@@ -178,7 +178,7 @@ def main(o, tag):
         d["kernel_source_hash"] = bench_other.kernel_source_hash()      # (bench.py quotes these counters only for a build of the same kernel sources)
         d.update(kernel="k_dp_jobs", **pack(per["plat::k_dp_jobs<false>"]))
         d["source"] = "profiles/" + tag + "_pmc_hbm.txt (rocprofv3 --pmc, separate passes: FETCH_SIZE, WRITE_SIZE raw counters x 1024; SQ_INSTS_VALU; GRBM_GUI_ACTIVE / 8 XCDs)"
-        for kn in ("k_seed", "k_sweep", "k_pairs"):
+        for kn in ("k_sweep", "k_pairs"):
             if "plat::" + kn in per:
                 d[kn] = pack(per["plat::" + kn])
         d["k_prep_reads"] = pack(per["plat::k_prep_reads"])

@@ -1,4 +1,4 @@
-"""Cross-check of k_seed's ungapped-alignment shortcut against the DP it replaces: the same batches aligned with the shortcut and
+"""Cross-check of k_pairs' ungapped-alignment shortcut against the DP it replaces: the same batches aligned with the shortcut and
 with PLAT_NO_UNGAPPED=1 (every pair through the DP) must give identical scores.  Stress batches (tests/test_gpu_parity.py::
 _adversarial_batch: repeats, cheap gaps, mismatches at the read ends, quality minima down to 1) with fresh seeds until the time
 budget is used, then BASELINE config 2 and a config-5 sample.   usage: python tools/ungapped_crosscheck.py [seconds] [first seed] [--bigq]
