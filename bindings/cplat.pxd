@@ -450,6 +450,43 @@ cdef extern from "platypus_mi355x.h":
     int plat_variant_info_batch(plat_ctx* ctx, int n_vars, const int64_t* counts, const int64_t* minq_off, const int32_t* minq,
                                 const int32_t* n_minq, double* out_terms, int32_t* out_mmlq, void* stream) nogil
 
+    # ---- packed bases read where they lie: the packed counterparts of the entry points above
+    ctypedef struct plat_packed_reads:
+        const uint8_t* const* read_src
+        int64_t n_exc
+        const int64_t* exc_index
+        const uint8_t* exc_base
+        const uint8_t* exc_qual
+    ctypedef struct plat_table_src_desc:
+        const int64_t* off
+        const int32_t* pos
+        const int32_t* end
+        const uint8_t* mapq
+        const int32_t* flags
+        const int16_t* cigar
+        const int32_t* cig_off
+        int32_t n
+        int32_t scan
+        int64_t first_read
+        int64_t first_byte
+        int64_t first_pair
+        const uint8_t* src
+    int plat_concat_read_tables_src(plat_ctx* ctx, int n_tables, int max_reads_per_table, const plat_table_src_desc* desc, int64_t* dst_off, int32_t* dst_pos,
+                                    int32_t* dst_end, uint8_t* dst_mapq, int32_t* dst_flags, int32_t* dst_cig_off, int16_t* dst_cigar, int32_t* dst_region,
+                                    const uint8_t** dst_src, int64_t n_total_reads, int64_t total_bytes, int64_t total_pairs, void* stream) nogil
+    int plat_pack_codes_pieces(plat_ctx* ctx, int n_pieces, int64_t max_piece_bytes, const plat_unpack_piece* pieces, uint32_t* out_codes,
+                               int64_t total_bytes, int64_t n_exc, const int64_t* exc_index, const uint8_t* exc_base, void* stream) nogil
+    int plat_candidates_batch_packed(plat_ctx* ctx, const plat_candidate_batch* batch, const plat_packed_reads* packed, const uint32_t* read_codes,
+                                     const uint32_t* ref_codes, const int32_t* ref_irregular, int min_flank, int min_base_qual, int gen_snps, int gen_indels,
+                                     int max_per_read, const int32_t* read_region, int32_t* out_rec, int32_t* out_count, int32_t* out_status, void* stream) nogil
+    int plat_gather_reads_packed(plat_ctx* ctx, int64_t n_dst, const int32_t* src_index, const int64_t* dst_off, const plat_packed_reads* packed,
+                                 const int64_t* src_off, const int32_t* src_pos, const int32_t* src_end, const uint8_t* src_mapq,
+                                 const int32_t* src_flags, uint8_t* dst_seq, uint8_t* dst_qual, int32_t* dst_pos, int32_t* dst_end,
+                                 uint8_t* dst_mapq, int32_t* dst_flags, void* stream) nogil
+    int plat_variant_read_stats_packed_batch(plat_ctx* ctx, const plat_infostats_batch* batch, const plat_packed_reads* packed, int bad_reads_window,
+                                             int count_only_exact_indel_matches, int64_t* out_counts, int32_t* out_per_sample,
+                                             int32_t* out_minq, int32_t* out_nminq, void* stream) nogil
+
     # ---- assembleReadsAndDetectVariants (assembler.pxd:3)
     ctypedef struct plat_assembly_batch:
         int32_t n_regions

@@ -40,8 +40,12 @@ extern "C" {
  *                      (0..63); `qual` is not read.  Bases other than A/C/G/T and qualities above 63 are listed as exceptions
  *                      (exc_index = byte index into seq, ascending; exc_base / exc_qual = the real letter and quality; the packed
  *                      byte under an exception is ignored).  Same cost for the loader -- its decode loop writes this byte instead of
- *                      two -- and half the bytes on the link; the device expands the table to ASCII once (plat_unpack_reads), so
- *                      every kernel downstream sees what it sees with PLAT_READS_ASCII and the records are the same. */
+ *                      two -- and half the bytes on the link.  A chunk of packed tables only is never expanded: the device packs the
+ *                      bases' 2-bit codes once and every kernel that walks a read takes letter and quality from the packed byte where
+ *                      it lies (in `seq`'s upload, or at dev_seq), exceptions looked up; a chunk that also holds ASCII tables (or an
+ *                      exception byte other than A/C/G/T/N) is expanded to ASCII once (plat_unpack_reads_pieces).  Either way every
+ *                      kernel sees the letters and qualities it sees with PLAT_READS_ASCII and the records are the same.
+ *                      PLAT_CALLER_EXPAND=1 in the environment forces the expansion (measurements / tests). */
 enum { PLAT_READS_ASCII = 0, PLAT_READS_PACKED = 1 };
 
 /* One ReadArray (cwindow.pyx:92-236) as arrays: cAlignedRead fields (htslibWrapper.pxd:187-201) of n_reads reads.

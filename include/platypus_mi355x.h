@@ -787,6 +787,55 @@ int plat_gather_reads(plat_ctx* ctx, int64_t n_dst, const int32_t* src_index, co
                       const int32_t* src_flags, uint8_t* dst_seq, uint8_t* dst_qual, int32_t* dst_pos,
                       int32_t* dst_end, uint8_t* dst_mapq, int32_t* dst_flags, void* stream);
 
+/* ---- packed bases read where they lie ------------------------------------------------------------------------------------------
+ * A chunk whose reads all come out of PLAT_READS_PACKED tables (exceptions A/C/G/T/N or qualities above 63 only) need not be expanded to
+ * ASCII at all: every kernel that starts from a READ takes the read's packed bytes at their source -- letter "ACTG"[b & 3], quality
+ * b >> 2, or the exception's byte and quality where the blob index read_off[r] + i is listed.  The entry points below are the packed
+ * counterparts of plat_concat_read_tables, plat_unpack_reads_pieces_codes, plat_candidates_batch_codes, plat_gather_reads and
+ * plat_variant_read_stats_batch; each gives what its counterpart gives on the expanded table, bit for bit.
+ *   plat_packed_reads      read_src[r] = device address of read r's packed bytes (any alignment; only the read's own bytes are read);
+ *                          exc_index ascending, blob indices in read_off's units; exc_* may be NULL when n_exc == 0.  All device memory.
+ *   plat_concat_read_tables_src   = plat_concat_read_tables + dst_src[first_read + i] = desc.src + desc.off[i] (src: the table's packed
+ *                          bytes on the device)
+ *   plat_pack_codes_pieces the 2-bit codes of plat_unpack_reads_pieces_codes WITHOUT the ASCII arrays: out_codes[(total_bytes + 15) / 16
+ *                          + 8], exceptions patched in (exc_base only), the 8 words behind the last base zero.  The buffer need not be
+ *                          zeroed: a dword every base of which belongs to one piece is stored whole, the dwords at a piece's two ends are
+ *                          zeroed first and OR-ed in.  Dwords no piece reaches keep what they held.
+ *   plat_candidates_batch_packed  = plat_candidates_batch_codes with the reads' letters and qualities taken from `packed`.
+ *                          batch->read_seq is an OUTPUT here ([read_off[n_reads] + PLAT_BLOB_PAD], need not be initialised): the scan
+ *                          writes the read-side allele of every record it finds, read_seq[rec[4] .. rec[4] + rec[2]), whether or not the
+ *                          record fits the read's slice -- what plat_candidates_merge_batch and plat_stage_b_batch read.  batch->read_qual
+ *                          is not used (may be NULL).
+ *   plat_gather_reads_packed      = plat_gather_reads (ASCII destination) from packed sources
+ *   plat_variant_read_stats_packed_batch = plat_variant_read_stats_batch; batch->read_seq / read_qual are not used (may be NULL)       */
+typedef struct plat_packed_reads {
+    const uint8_t* const* read_src;
+    int64_t n_exc;
+    const int64_t* exc_index;
+    const uint8_t* exc_base;
+    const uint8_t* exc_qual;
+} plat_packed_reads;
+typedef struct plat_table_src_desc {
+    const int64_t* off; const int32_t* pos; const int32_t* end; const uint8_t* mapq; const int32_t* flags; const int16_t* cigar; const int32_t* cig_off;
+    int32_t n, scan; int64_t first_read, first_byte, first_pair;
+    const uint8_t* src;
+} plat_table_src_desc;
+int plat_concat_read_tables_src(plat_ctx* ctx, int n_tables, int max_reads_per_table, const plat_table_src_desc* desc, int64_t* dst_off, int32_t* dst_pos,
+                                int32_t* dst_end, uint8_t* dst_mapq, int32_t* dst_flags, int32_t* dst_cig_off, int16_t* dst_cigar,
+                                int32_t* dst_region, const uint8_t** dst_src, int64_t n_total_reads, int64_t total_bytes, int64_t total_pairs, void* stream);
+int plat_pack_codes_pieces(plat_ctx* ctx, int n_pieces, int64_t max_piece_bytes, const plat_unpack_piece* pieces, uint32_t* out_codes,
+                           int64_t total_bytes, int64_t n_exc, const int64_t* exc_index, const uint8_t* exc_base, void* stream);
+int plat_candidates_batch_packed(plat_ctx* ctx, const plat_candidate_batch* batch, const plat_packed_reads* packed, const uint32_t* read_codes,
+                                 const uint32_t* ref_codes, const int32_t* ref_irregular, int min_flank, int min_base_qual, int gen_snps, int gen_indels,
+                                 int max_per_read, const int32_t* read_region, int32_t* out_rec, int32_t* out_count, int32_t* out_status, void* stream);
+int plat_gather_reads_packed(plat_ctx* ctx, int64_t n_dst, const int32_t* src_index, const int64_t* dst_off, const plat_packed_reads* packed,
+                             const int64_t* src_off, const int32_t* src_pos, const int32_t* src_end, const uint8_t* src_mapq,
+                             const int32_t* src_flags, uint8_t* dst_seq, uint8_t* dst_qual, int32_t* dst_pos, int32_t* dst_end,
+                             uint8_t* dst_mapq, int32_t* dst_flags, void* stream);
+int plat_variant_read_stats_packed_batch(plat_ctx* ctx, const plat_infostats_batch* batch, const plat_packed_reads* packed, int bad_reads_window,
+                                         int count_only_exact_indel_matches, int64_t* out_counts, int32_t* out_per_sample,
+                                         int32_t* out_minq, int32_t* out_nminq, void* stream);
+
 /* ---- a14..a18: assembleReadsAndDetectVariants ---------------------------------------------------
  * Replaces  cdef list assembleReadsAndDetectVariants(chrom, assemStart, assemEnd, refStart, refEnd,
  *                                                    readBuffers, refSeq, options)

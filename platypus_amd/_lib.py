@@ -128,6 +128,14 @@ class InfoStatsBatch(C.Structure):
         "read_pos", "read_end", "read_mapq", "read_flags", "cigar", "cig_off")]
 
 
+class PackedReads(C.Structure):
+    _fields_ = [("read_src", C.c_void_p), ("n_exc", C.c_int64), ("exc_index", C.c_void_p), ("exc_base", C.c_void_p), ("exc_qual", C.c_void_p)]
+
+
+class UnpackPiece(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_int64), ("n", C.c_int64)]
+
+
 # symbol -> (restype, argtypes): exactly the declarations of include/platypus_mi355x.h
 SIGNATURES = {
     "plat_abi_version": (C.c_int, []),
@@ -184,6 +192,13 @@ SIGNATURES = {
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "plat_copy_pieces": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "plat_concat_read_tables": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 9 + [C.c_int64] * 3 + [C.c_void_p]),
+    "plat_concat_read_tables_src": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 10 + [C.c_int64] * 3 + [C.c_void_p]),
+    "plat_pack_codes_pieces": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "plat_candidates_batch_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PackedReads), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                               C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "plat_gather_reads_packed": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(PackedReads)] + [C.c_void_p] * 12),
+    "plat_variant_read_stats_packed_batch": (C.c_int, [C.c_void_p, C.POINTER(InfoStatsBatch), C.POINTER(PackedReads), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p, C.c_void_p, C.c_void_p]),
     "plat_read_qc_batch": (C.c_int, [C.c_void_p, C.POINTER(ReadQCBatch), C.POINTER(ReadQCOptions), C.c_void_p, C.c_void_p, C.c_void_p]),
     "plat_read_buffers_batch": (C.c_int, [C.c_void_p, C.POINTER(ReadBuffersIn), C.POINTER(ReadQCOptions), C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.POINTER(ReadBuffersTables), C.c_void_p]),
@@ -205,7 +220,9 @@ SIGNATURES = {
 
 # entry points a stand-in library built against an earlier header may lack (the CPU suite's fake device): bind() leaves them
 # unbound there; load() still requires every declared symbol of the real library
-ADDED_LATER = ("plat_read_buffers_batch", "plat_read_buffers_packed_batch", "plat_bam_decode_batch", "plat_bgzf_inflate_batch", "plat_bam_find_records")
+ADDED_LATER = ("plat_read_buffers_batch", "plat_read_buffers_packed_batch", "plat_bam_decode_batch", "plat_bgzf_inflate_batch", "plat_bam_find_records",
+               "plat_concat_read_tables_src", "plat_pack_codes_pieces", "plat_candidates_batch_packed", "plat_gather_reads_packed",
+               "plat_variant_read_stats_packed_batch")
 
 _lib = None
 

@@ -134,6 +134,12 @@ struct Slot {
     Staged<plat_unpack_piece> t_pieces;
     Staged<int64_t> t_off;
     Staged<int32_t> t_pos, t_end, t_flags, t_cigoff, t_region;
+    // packed bases read where they lie (a chunk of packed tables only, stage_a.hpp): no t_qual, t_seq holds only the read-side alleles the scan leaves
+    // there; every kernel that starts from a read takes the read's packed bytes at t_src[read] (in the caller's resident table or in t_pack)
+    Staged<const uint8_t*> t_src;
+    Staged<plat_table_src_desc> t_sdesc;
+    bool packedDirect = false;                                             // this chunk's table is read that way ...
+    plat_packed_reads pk = {};                                              // ... through these (t_src + the chunk's exceptions)
     Staged<int16_t> t_cigar;
     // candidate scan
     Staged<uint8_t> c_ref, c_refdev;
@@ -584,6 +590,10 @@ static void runBatch(Slot& s, DeviceBatch& db, const Options& o, bool full, bool
     s.g_seq.reserve(s.ctx, blob + PLAT_BLOB_PAD, false, true, s.stream); s.g_qual.reserve(s.ctx, blob + PLAT_BLOB_PAD, false, true, s.stream);
     const size_t nR = (size_t)db.nReads;
     s.g_pos.reserve(s.ctx, nR + 1, false); s.g_end.reserve(s.ctx, nR + 1, false); s.g_flags.reserve(s.ctx, nR + 1, false); s.g_mapq.reserve(s.ctx, nR + 1, false);
+    if (s.packedDirect)
+        ck(plat_gather_reads_packed(s.ctx, (int64_t)nR, db.src, db.readoff, &s.pk, s.t_off.d, s.t_pos.d, s.t_end.d, s.t_mapq.d, s.t_flags.d, s.g_seq.d, s.g_qual.d,
+                                    s.g_pos.d, s.g_end.d, s.g_mapq.d, s.g_flags.d, s.stream), "plat_gather_reads_packed");
+    else
     ck(plat_gather_reads(s.ctx, (int64_t)nR, db.src, db.readoff, s.t_seq.d, s.t_qual.d, s.t_off.d, s.t_pos.d, s.t_end.d, s.t_mapq.d,
                          s.t_flags.d, s.g_seq.d, s.g_qual.d, s.g_pos.d, s.g_end.d, s.g_mapq.d, s.g_flags.d, s.stream), "plat_gather_reads");
     plat_window_batch& wb = db.wb;

@@ -100,6 +100,7 @@ struct Chunk {
     void regionVariants(RegionWork& r, int scan0);
     bool recordsOnHost = false;
     bool readCodes = false;                                                 // the chunk's read blob has its 2-bit codes in s.t_codes (every table packed, exceptions A/C/G/T/N only)
+    bool packedDirect = false;                                              // ... and nothing else: its bases are read packed, where they lie (s.packedDirect)
     int64_t tabPackedBytes = 0, tabBlobBytes = 0;                          // this chunk's table: packed bytes expanded on the device, bytes of bases in all
     size_t recArenaBytes = 0;
 
@@ -163,9 +164,13 @@ struct Chunk {
             memset(&pf, 0, sizeof pf);
             ck(plat_profile_last(s.ctx, &pf), "plat_profile_last");
             if (getenv("PLAT_CALLER_TRACE")) fprintf(stderr, "[plat_caller] table kernels: unpack %.3f ms (%lld packed bytes), candidates %.3f ms (%lld bytes)\n", pf.ms_unpack, (long long)tabPackedBytes, pf.ms_candidates, (long long)tabBlobBytes);
-            // one byte in, two out per base (+ a quarter: the 2-bit codes, when the chunk has them); the scan has to read the bases once: as 2-bit codes when it
-            // runs on them (qualities and bytes only where codes differ), as bytes otherwise
-            if (pf.ms_unpack > 0) { s.secUnpack += 1e-3 * pf.ms_unpack; s.unpackBytes += 3 * tabPackedBytes + (readCodes ? tabPackedBytes / 4 : 0); s.nUnpack += 1; }
+            // one byte in, two out per base (+ a quarter: the 2-bit codes, when the chunk has them) -- or one byte in and the quarter out when the codes are all
+            // the first pass writes (packedDirect); the scan has to read the bases once: as 2-bit codes when it runs on them (qualities and bytes only where
+            // codes differ), as bytes otherwise
+            if (pf.ms_unpack > 0) {
+                s.secUnpack += 1e-3 * pf.ms_unpack; s.nUnpack += 1;
+                s.unpackBytes += packedDirect ? tabPackedBytes + tabPackedBytes / 4 : 3 * tabPackedBytes + (readCodes ? tabPackedBytes / 4 : 0);
+            }
             if (pf.ms_candidates > 0) { s.secCand += 1e-3 * pf.ms_candidates; s.candBytes += readCodes ? tabBlobBytes / 4 : tabBlobBytes; s.nCand += 1; }
         }
         assembleCollect();

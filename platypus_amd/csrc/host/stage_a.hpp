@@ -3,6 +3,14 @@
 #pragma once
 #include "chunk.hpp"
 
+// The entry points that read packed bases where they lie are referenced weakly, as plat_read_buffers_batch: the CPU suite's stand-in device
+// library predates them.  A device library without ALL of them: every chunk is expanded as before.
+#pragma weak plat_concat_read_tables_src
+#pragma weak plat_pack_codes_pieces
+#pragma weak plat_candidates_batch_packed
+#pragma weak plat_gather_reads_packed
+#pragma weak plat_variant_read_stats_packed_batch
+
 namespace plathost {
 
 // -- A: one device table for every read of the chunk; layout: all `reads` of every (region, sample), then all badReads, then all brokenMates
@@ -17,7 +25,13 @@ inline void Chunk::uploadReads() {
                 nReads[k] += (size_t)t.n_reads;
                 nBytes[k] += (size_t)t.off[t.n_reads];
                 nCig[k] += (size_t)t.cig_off[t.n_reads];
-                if (t.encoding == PLAT_READS_PACKED) { anyPacked = true; nExc += (size_t)std::max<int64_t>(t.n_exceptions, 0); }
+                if (t.encoding == PLAT_READS_PACKED) {
+                    anyPacked = true; nExc += (size_t)std::max<int64_t>(t.n_exceptions, 0);
+                    for (int64_t e = 0; e < t.n_exceptions; ++e) {
+                        const uint8_t eb = t.exc_base[e];
+                        excRegular = excRegular && (eb == 'A' || eb == 'C' || eb == 'G' || eb == 'T' || eb == 'N');
+                    }
+                }
                 else if (t.encoding != PLAT_READS_ASCII) throw DeviceError(PLAT_ERR_INVALID, "plat_read_table.encoding");
                 else if (t.n_reads) allPacked = false;
             }
@@ -27,7 +41,18 @@ inline void Chunk::uploadReads() {
     const size_t N = nReads[0] + nReads[1] + nReads[2], B = nBytes[0] + nBytes[1] + nBytes[2], Cg = nCig[0] + nCig[1] + nCig[2];
     if (N > 0x7FFFFFF0ull) throw DeviceError(PLAT_ERR_OVERFLOW, "chunk read table");
     Slot& z = s;
-    z.t_seq.reserve(z.ctx, B + PLAT_BLOB_PAD, false, true, z.stream); z.t_qual.reserve(z.ctx, B + PLAT_BLOB_PAD, false, true, z.stream);
+    // Every read out of a packed table and no exception with a byte other than A, C, G, T, N (the promise the scan on codes asks for): the chunk is not
+    // expanded at all.  The first pass writes the 2-bit codes only; the scan, the read statistics and the gathers take a read's letters and qualities from
+    // its packed bytes where they lie (t_src); t_seq keeps its place but holds only the read-side alleles the scan leaves at its records' offsets, and
+    // there is no t_qual.  PLAT_CALLER_EXPAND (measurements / tests) or a device library without the entry points: today's full expansion.
+    static const bool noCodes = getenv("PLAT_CALLER_NO_CODES") != nullptr;         // (measurements / tests: the byte scan)
+    static const bool expandAll = getenv("PLAT_CALLER_EXPAND") != nullptr;
+    const bool haveDirect = plat_concat_read_tables_src && plat_pack_codes_pieces && plat_candidates_batch_packed && plat_gather_reads_packed &&
+                            plat_variant_read_stats_packed_batch;
+    packedDirect = anyPacked && allPacked && excRegular && B > 0 && !noCodes && !expandAll && haveDirect;
+    z.packedDirect = packedDirect;
+    z.t_seq.reserve(z.ctx, B + PLAT_BLOB_PAD, false, true, z.stream);
+    if (!packedDirect) z.t_qual.reserve(z.ctx, B + PLAT_BLOB_PAD, false, true, z.stream);
     if (anyPacked) z.t_pack.reserve(z.ctx, B + PLAT_BLOB_PAD, false, true, z.stream);
     // every table with its per-read arrays on the device already: the chunk table is put together there (plat_concat_read_tables)
     bool cols = true;
@@ -41,13 +66,15 @@ inline void Chunk::uploadReads() {
     L.add(z.t_excidx, nExc + 1); L.add(z.t_excb, nExc + 1); L.add(z.t_excq, nExc + 1);
     L.add(z.t_off, N + 1); L.add(z.t_pos, N + 1); L.add(z.t_end, N + 1); L.add(z.t_flags, N + 1); L.add(z.t_mapq, N + 1); L.add(z.t_cigoff, N + 1);
     L.add(z.t_cigar, 2 * Cg + 2); L.add(z.t_region, nReads[0] + 1);
+    if (packedDirect) L.add(z.t_src, N + 1);
     L.commit(z, z.a_tab);
     Layout LD;
     size_t nDesc = 0;
     int mostPerTable = 0;
     const size_t nTables = 3 * regions.size() * (regions.empty() ? 0 : regions[0]->samples.size());
     LD.add(z.t_pieces, nTables + 1);
-    if (cols) LD.add(z.t_desc, nTables + 1);
+    if (cols && packedDirect) LD.add(z.t_sdesc, nTables + 1);
+    else if (cols) LD.add(z.t_desc, nTables + 1);
     LD.commit(z, z.a_desc);
     struct Pending { size_t bo, nb, e0, ne; const uint8_t* dev; };       // dev: expand from this device address instead of t_pack + bo
     std::vector<Pending> packed;
@@ -71,8 +98,6 @@ inline void Chunk::uploadReads() {
                     const bool joins = !t.dev_seq && !packed.empty() && !packed.back().dev && packed.back().bo + packed.back().nb == bo;
                     for (size_t e = 0; e < ne; ++e) {
                         z.t_excidx.h[eo + e] = t.exc_index[e] + (int64_t)bo; z.t_excb.h[eo + e] = t.exc_base[e]; z.t_excq.h[eo + e] = t.exc_qual[e];
-                        const uint8_t eb = t.exc_base[e];
-                        excRegular = excRegular && (eb == 'A' || eb == 'C' || eb == 'G' || eb == 'T' || eb == 'N');
                     }
                     if (joins) { packed.back().nb += nb; packed.back().ne += ne; }
                     else packed.push_back(Pending{bo, nb, eo, ne, t.dev_seq});
@@ -85,8 +110,16 @@ inline void Chunk::uploadReads() {
                     ck(plat_memcpy_h2d(z.ctx, z.t_qual.d + bo, t.qual, nb, z.stream), "plat_memcpy_h2d(qual)");
                     inBytes += 2 * nb;
                 }
+                // (packedDirect: where this table's packed bytes lie on the device -- resident, or its place in t_pack)
+                const uint8_t* tabSrc = t.dev_seq ? t.dev_seq : z.t_pack.d + bo;
                 if (cols) {
-                    if (n) {
+                    if (n && packedDirect) {
+                        plat_table_src_desc& d = z.t_sdesc.h[nDesc++];
+                        d.off = t.dev_off; d.pos = t.dev_pos; d.end = t.dev_end; d.mapq = t.dev_mapq; d.flags = t.dev_flags; d.cigar = t.dev_cigar; d.cig_off = t.dev_cig_off;
+                        d.n = n; d.scan = k == 0 ? scan : -1; d.first_read = (int64_t)ri; d.first_byte = (int64_t)bo; d.first_pair = (int64_t)co;
+                        d.src = tabSrc;
+                        mostPerTable = std::max(mostPerTable, n);
+                    } else if (n) {
                         plat_table_desc& d = z.t_desc.h[nDesc++];
                         d.off = t.dev_off; d.pos = t.dev_pos; d.end = t.dev_end; d.mapq = t.dev_mapq; d.flags = t.dev_flags; d.cigar = t.dev_cigar; d.cig_off = t.dev_cig_off;
                         d.n = n; d.scan = k == 0 ? scan : -1; d.first_read = (int64_t)ri; d.first_byte = (int64_t)bo; d.first_pair = (int64_t)co;
@@ -100,6 +133,7 @@ inline void Chunk::uploadReads() {
                     z.t_off.h[ri + i] = (int64_t)bo + t.off[i];
                     z.t_cigoff.h[ri + i] = (int32_t)(co + (size_t)t.cig_off[i]);
                 }
+                if (packedDirect) for (int i = 0; i < n; ++i) z.t_src.h[ri + i] = tabSrc + t.off[i];
                 if (n) {
                     memcpy(z.t_pos.h + ri, t.pos, sizeof(int32_t) * (size_t)n); memcpy(z.t_end.h + ri, t.end, sizeof(int32_t) * (size_t)n);
                     memcpy(z.t_flags.h + ri, t.flags, sizeof(int32_t) * (size_t)n); memcpy(z.t_mapq.h + ri, t.mapq, (size_t)n);
@@ -112,7 +146,11 @@ inline void Chunk::uploadReads() {
     }
     if (cols) {
         L.uploadFirst(z, z.a_tab, 3);                                   // (the exceptions of packed tables; the per-read arrays are made on the device)
-        if (nDesc) {
+        if (nDesc && packedDirect) {
+            LD.upload(z, z.a_desc);
+            ck(plat_concat_read_tables_src(z.ctx, (int)nDesc, mostPerTable, z.t_sdesc.d, z.t_off.d, z.t_pos.d, z.t_end.d, z.t_mapq.d, z.t_flags.d, z.t_cigoff.d, z.t_cigar.d,
+                                           z.t_region.d, z.t_src.d, (int64_t)N, (int64_t)bo, (int64_t)Cg, z.stream), "plat_concat_read_tables_src");
+        } else if (nDesc) {
             LD.upload(z, z.a_desc);
             ck(plat_concat_read_tables(z.ctx, (int)nDesc, mostPerTable, z.t_desc.d, z.t_off.d, z.t_pos.d, z.t_end.d, z.t_mapq.d, z.t_flags.d, z.t_cigoff.d, z.t_cigar.d,
                                        z.t_region.d, (int64_t)N, (int64_t)bo, (int64_t)Cg, z.stream), "plat_concat_read_tables");
@@ -133,15 +171,20 @@ inline void Chunk::uploadReads() {
         ck(plat_memcpy_h2d(z.ctx, z.t_pieces.d, z.t_pieces.h, packed.size() * sizeof(plat_unpack_piece), z.stream), "plat_memcpy_h2d(pieces)");
         // the bases' 2-bit codes next to the bytes when every read of the chunk comes out of a packed table and no exception carries a byte other than
         // A, C, G, T, N (the promise plat_candidates_batch_codes asks for); a device library without the entry point: the byte scan
-        static const bool noCodes = getenv("PLAT_CALLER_NO_CODES") != nullptr;         // (measurements / tests: the byte scan)
         int rcu = PLAT_ERR_UNSUPPORTED;
-        if (allPacked && excRegular && !noCodes) {
+        if (packedDirect) {                                             // the codes alone: the bytes stay where they are
+            z.t_codes.reserve(z.ctx, (bo + 15) / 16 + 16, false);
+            ck(plat_pack_codes_pieces(z.ctx, (int)packed.size(), (int64_t)most, z.t_pieces.d, z.t_codes.d, (int64_t)bo, (int64_t)eo, z.t_excidx.d, z.t_excb.d, z.stream),
+               "plat_pack_codes_pieces");
+            rcu = PLAT_OK;
+        } else if (allPacked && excRegular && !noCodes) {
             z.t_codes.reserve(z.ctx, (bo + 15) / 16 + 16, false);
             rcu = plat_unpack_reads_pieces_codes(z.ctx, (int)packed.size(), (int64_t)most, z.t_pieces.d, z.t_seq.d, z.t_qual.d, z.t_codes.d, (int64_t)bo, (int64_t)eo,
                                                  z.t_excidx.d, z.t_excb.d, z.t_excq.d, z.stream);
             if (rcu != PLAT_ERR_UNSUPPORTED) ck(rcu, "plat_unpack_reads_pieces_codes");
         }
         readCodes = rcu == PLAT_OK;
+        z.pk = plat_packed_reads{packedDirect ? z.t_src.d : nullptr, (int64_t)eo, z.t_excidx.d, z.t_excb.d, z.t_excq.d};
         if (!readCodes)
             ck(plat_unpack_reads_pieces(z.ctx, (int)packed.size(), (int64_t)most, z.t_pieces.d, z.t_seq.d, z.t_qual.d, (int64_t)bo, (int64_t)eo, z.t_excidx.d, z.t_excb.d,
                                         z.t_excq.d, z.stream), "plat_unpack_reads_pieces");
@@ -221,7 +264,12 @@ inline void Chunk::scanCandidates() {
         if (readCodes) {                                                // the scan on 2-bit codes: the reference blob's codes first (a few MB per chunk)
             z.c_refcodes.reserve(z.ctx, (blobLen + 15) / 16 + 16, false); z.c_refirr.reserve(z.ctx, (size_t)nScan + 1, false);
             rcs = plat_ref_codes(z.ctx, nScan, refDev, z.c_refoff.d, (int64_t)blobLen, z.c_refcodes.d, z.c_refirr.d, z.stream);
-            if (rcs == PLAT_OK)
+            if (packedDirect) {                                         // (letters and qualities from the packed bytes; leaves its records' alleles in t_seq)
+                ck(rcs, "plat_ref_codes");                              // (no expanded bytes to fall back to)
+                cb.read_qual = nullptr;
+                ck(plat_candidates_batch_packed(z.ctx, &cb, &z.pk, z.t_codes.d, z.c_refcodes.d, z.c_refirr.d, o.minFlank, o.minBaseQual, o.genSNPs, o.genIndels, maxPerRead,
+                                                z.t_region.d, z.c_rec.d, z.c_cnt.d, z.c_status.d, z.stream), "plat_candidates_batch_packed");
+            } else if (rcs == PLAT_OK)
                 rcs = plat_candidates_batch_codes(z.ctx, &cb, z.t_codes.d, z.c_refcodes.d, z.c_refirr.d, o.minFlank, o.minBaseQual, o.genSNPs, o.genIndels, maxPerRead,
                                                   z.t_region.d, z.c_rec.d, z.c_cnt.d, z.c_status.d, z.stream);
             if (rcs != PLAT_ERR_UNSUPPORTED) ck(rcs, "plat_candidates_batch_codes");
@@ -355,7 +403,10 @@ inline void Chunk::assembleLaunch() {
         const size_t nR = src.size(), nb = (size_t)roff.back();
         z.as_seq.reserve(z.ctx, nb + PLAT_BLOB_PAD, false, true, z.stream); z.as_qual.reserve(z.ctx, nb + PLAT_BLOB_PAD, false, true, z.stream);
         z.as_pos.reserve(z.ctx, nR + 1, false); z.as_end.reserve(z.ctx, nR + 1, false); z.as_flags.reserve(z.ctx, nR + 1, false); z.as_mapq.reserve(z.ctx, nR + 1, false);
-        if (nR) ck(plat_gather_reads(z.ctx, (int64_t)nR, z.as_src.d, z.as_roff.d, z.t_seq.d, z.t_qual.d, z.t_off.d, z.t_pos.d, z.t_end.d, z.t_mapq.d, z.t_flags.d,
+        if (nR && packedDirect)
+            ck(plat_gather_reads_packed(z.ctx, (int64_t)nR, z.as_src.d, z.as_roff.d, &z.pk, z.t_off.d, z.t_pos.d, z.t_end.d, z.t_mapq.d, z.t_flags.d, z.as_seq.d, z.as_qual.d,
+                                        z.as_pos.d, z.as_end.d, z.as_mapq.d, z.as_flags.d, z.stream), "plat_gather_reads_packed(assembler)");
+        else if (nR) ck(plat_gather_reads(z.ctx, (int64_t)nR, z.as_src.d, z.as_roff.d, z.t_seq.d, z.t_qual.d, z.t_off.d, z.t_pos.d, z.t_end.d, z.t_mapq.d, z.t_flags.d,
                                      z.as_seq.d, z.as_qual.d, z.as_pos.d, z.as_end.d, z.as_mapq.d, z.as_flags.d, z.stream), "plat_gather_reads(assembler)");
         plat_assembly_batch& ab = asmBatch;
         memset(&ab, 0, sizeof ab);

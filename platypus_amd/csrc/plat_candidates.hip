@@ -202,8 +202,67 @@ __device__ __forceinline__ unsigned long long codes_at(const unsigned long long*
     return (lo >> sh) | (c[w + 1] << (64 - sh));
 }
 
-__global__ void __launch_bounds__(64)
-k_candidates_codes(plat_candidate_batch b, const unsigned long long* __restrict__ read_codes, const unsigned long long* __restrict__ ref_codes,
+// ---- a read's letters and qualities, wherever they lie ------------------------------------------------------------------------------------
+// The kernels that start from a READ (the scan on codes, the read statistics, the gather) are written once over one of these: base(i) /
+// qual(i) of the read's i-th base (qual: the raw byte; the scan reads it unsigned, the statistics signed, as the reference's two loops do).
+// ASCII tables: the expanded bytes.
+struct ReadAscii {
+    const uint8_t* s; const uint8_t* q;
+    __device__ __forceinline__ uint8_t base(int i) const { return s[i]; }
+    __device__ __forceinline__ uint8_t qual(int i) const { return q[i]; }
+    __device__ __forceinline__ bool has_n(int at, int n) const { return plat::has_n(s + at, n); }
+};
+struct SrcAscii {
+    static constexpr bool packed = false;
+    const uint8_t* seq; const uint8_t* qual;
+    __device__ __forceinline__ ReadAscii read(int, long long soff, long long) const { return ReadAscii{seq + soff, qual + soff}; }
+};
+// PLAT_READS_PACKED bytes at their source: letter "ACTG"[b & 3], quality b >> 2 -- or the exception's, where the blob index at + i is listed
+// in exc_index[e0, e1) (the read's own exceptions: two lower bounds per read, and only in a chunk that has any; most reads have none and
+// never touch the exception arrays)
+struct ReadPacked {
+    const uint8_t* p; long long at; const int64_t* idx; const uint8_t* eb; const uint8_t* eq; long long e0, e1;
+    __device__ __forceinline__ long long find(int i) const {
+        long long lo = e0, hi = e1;
+        while (lo < hi) { const long long mid = (lo + hi) >> 1; if (idx[mid] < at + i) lo = mid + 1; else hi = mid; }
+        return lo < e1 && idx[lo] == at + i ? lo : -1;
+    }
+    __device__ __forceinline__ uint8_t base(int i) const {
+        if (e0 != e1) { const long long k = find(i); if (k >= 0) return eb[k]; }
+        return (uint8_t)((0x47544341u >> (8u * (p[i] & 3u))) & 0xFFu);
+    }
+    __device__ __forceinline__ uint8_t qual(int i) const {
+        if (e0 != e1) { const long long k = find(i); if (k >= 0) return eq[k]; }
+        return (uint8_t)(p[i] >> 2);
+    }
+    __device__ __forceinline__ bool has_n(int a, int n) const {                    // (only an exception can be an N)
+        for (long long k = e0; k < e1; ++k) if (idx[k] >= at + a && idx[k] < at + a + n && eb[k] == 'N') return true;
+        return false;
+    }
+};
+struct SrcPacked {
+    static constexpr bool packed = true;
+    plat_packed_reads pk;
+    // read r, whose bytes are [soff, soff + rlen) of the blob
+    __device__ __forceinline__ ReadPacked read(int r, long long soff, long long rlen) const {
+        long long e0 = 0, e1 = 0;
+        if (pk.n_exc > 0) {
+            long long lo = 0, hi = pk.n_exc;
+            while (lo < hi) { const long long mid = (lo + hi) >> 1; if (pk.exc_index[mid] < soff) lo = mid + 1; else hi = mid; }
+            e0 = lo; hi = pk.n_exc;
+            while (lo < hi) { const long long mid = (lo + hi) >> 1; if (pk.exc_index[mid] < soff + rlen) lo = mid + 1; else hi = mid; }
+            e1 = lo;
+        }
+        return ReadPacked{pk.read_src[r], soff, pk.exc_index, pk.exc_base, pk.exc_qual, e0, e1};
+    }
+};
+
+// the scan of read r on codes, over either storage.  SrcPacked: no expanded bytes exist, so the lane leaves the read-side allele of every
+// record it finds in b.read_seq (the chunk's t_seq) at the record's own offset -- all that the kernels starting from a RECORD (merge, filter,
+// stage B) ever read of it.  Written whether or not the record fits the slice: the same bytes again on the retry with more room.
+template <class S>
+__device__ __forceinline__ void candidates_codes_one(const plat_candidate_batch& b, const S& src, const unsigned long long* __restrict__ read_codes,
+                   const unsigned long long* __restrict__ ref_codes,
                    const int32_t* __restrict__ ref_irregular, int min_flank, int min_base_qual, int gen_snps, int gen_indels, int max_per_read,
                    const int32_t* __restrict__ read_region, int32_t* __restrict__ rec, int32_t* __restrict__ count, int32_t* __restrict__ status)
 {
@@ -218,9 +277,12 @@ k_candidates_codes(plat_candidate_batch b, const unsigned long long* __restrict_
         const bool byBytes = ref_irregular[g] != 0;      // a reference byte other than A, C, G, T, N in this region: the byte scan
         const uint8_t* ref = b.ref_seq + roff;
         const long long soff = b.read_off[r];
-        const uint8_t* readSeq = b.read_seq + soff;
-        const uint8_t* readQual = b.read_qual + soff;
         const int rlen = (int)(b.read_off[r + 1] - soff);
+        const auto rd = src.read(r, soff, rlen);
+        // the read-side allele [start, start + n) of a record about to be put
+        auto allele = [&](int start, int n) {
+            if constexpr (S::packed) { uint8_t* o = const_cast<uint8_t*>(b.read_seq) + soff + start; for (int i = 0; i < n; ++i) o[i] = rd.base(start + i); }
+        };
         const int readStart = b.read_pos[r];
         const int16_t* ops = b.cigar + 2ll * b.cig_off[r];
         const int cigarLength = b.cig_off[r + 1] - b.cig_off[r];
@@ -232,8 +294,10 @@ k_candidates_codes(plat_candidate_batch b, const unsigned long long* __restrict_
                 if (ci > 0 && ops[2 * ci - 2] == 0 && ops[2 * ci - 1] >= min_flank) flanked = true;
                 else if (ci < cigarLength - 1 && ops[2 * ci + 2] == 0 && ops[2 * ci + 3] >= min_flank) flanked = true;
                 if (flag == 1) {
-                    if (flanked && gen_indels && !has_n(readSeq + readOffset, length))
+                    if (flanked && gen_indels && !rd.has_n(readOffset, length)) {
+                        allele(readOffset, length);
                         out.put(readStart + refOffset - 1, 0, length, -1, soff + readOffset);
+                    }
                     readOffset += length;
                 } else {
                     if (flanked) {
@@ -259,22 +323,24 @@ k_candidates_codes(plat_candidate_batch b, const unsigned long long* __restrict_
                         if (refIndex0 + lo < 0) { st = PLAT_ERR_BAD_INPUT; hi = lo; }
                         else if (refIndex0 + hi > refLen) { st = PLAT_ERR_BAD_INPUT; hi = refLen - refIndex0; }
                     }
-                    const uint8_t* rp = readSeq + readOffset;
                     const uint8_t* fp = ref + refIndex0;
                     auto mismatch = [&](int index) {
                         const int readIndex = index + readOffset, refIndex = refIndex0 + index;
-                        const uint8_t readChar = rp[index], refChar = fp[index];
-                        if (readChar != refChar && readChar != 'N' && refChar != 'N' && (int)readQual[readIndex] >= min_base_qual) {
-                            if (msr == -1) { msr = mer = refIndex; msd = med = readIndex; }
-                            else if (refIndex - mer <= min_flank) { mer = refIndex; med = readIndex; }
-                            else {
+                        const uint8_t readChar = rd.base(readIndex), refChar = fp[index];
+                        if (readChar != refChar && readChar != 'N' && refChar != 'N' && (int)rd.qual(readIndex) >= min_base_qual) {
+                            // the first mismatch opens a run; one within minFlank of the run's end extends it; any other closes it and opens the next
+                            // (written as selects on the four values: as three branches that each store some of them, the compiler keeps two in scratch)
+                            const bool extend = msr != -1 && refIndex - mer <= min_flank;
+                            if (msr != -1 && !extend) {
+                                allele(msd, med - msd + 1);
                                 out.put(msr + refSeqStart, mer - msr + 1, med - msd + 1, roff + msr, soff + msd);
-                                msr = mer = refIndex; msd = med = readIndex;
                             }
+                            msr = extend ? msr : refIndex; msd = extend ? msd : readIndex;
+                            mer = refIndex; med = readIndex;
                         }
                     };
                     if (byBytes) {
-                        for (int index = lo; index < hi; ++index) if (rp[index] != fp[index]) mismatch(index);
+                        for (int index = lo; index < hi; ++index) if (rd.base(readOffset + index) != fp[index]) mismatch(index);
                     } else {
                         // 32 bases per word; CODE_TRIP words (160 bases: a whole 150-base read) are requested together
                         constexpr int CODE_TRIP = 5;
@@ -301,7 +367,7 @@ k_candidates_codes(plat_candidate_batch b, const unsigned long long* __restrict_
                             }
                         }
                     }
-                    if (msr != -1) out.put(msr + refSeqStart, mer - msr + 1, med - msd + 1, roff + msr, soff + msd);
+                    if (msr != -1) { allele(msd, med - msd + 1); out.put(msr + refSeqStart, mer - msr + 1, med - msd + 1, roff + msr, soff + msd); }
                 }
                 readOffset += length;
                 refOffset += length;
@@ -316,6 +382,25 @@ k_candidates_codes(plat_candidate_batch b, const unsigned long long* __restrict_
     if (out.n > max_per_read && st == 0) st = PLAT_ERR_OVERFLOW;
     count[r] = out.n;
     status[r] = st;
+}
+
+__global__ void __launch_bounds__(64)
+k_candidates_codes(plat_candidate_batch b, const unsigned long long* __restrict__ read_codes, const unsigned long long* __restrict__ ref_codes,
+                   const int32_t* __restrict__ ref_irregular, int min_flank, int min_base_qual, int gen_snps, int gen_indels, int max_per_read,
+                   const int32_t* __restrict__ read_region, int32_t* __restrict__ rec, int32_t* __restrict__ count, int32_t* __restrict__ status)
+{
+    candidates_codes_one(b, SrcAscii{b.read_seq, b.read_qual}, read_codes, ref_codes, ref_irregular, min_flank, min_base_qual, gen_snps, gen_indels, max_per_read,
+                         read_region, rec, count, status);
+}
+
+// ... and on packed bytes at their source (plat_candidates_batch_packed)
+__global__ void __launch_bounds__(64)
+k_candidates_packed(plat_candidate_batch b, plat_packed_reads pk, const unsigned long long* __restrict__ read_codes, const unsigned long long* __restrict__ ref_codes,
+                    const int32_t* __restrict__ ref_irregular, int min_flank, int min_base_qual, int gen_snps, int gen_indels, int max_per_read,
+                    const int32_t* __restrict__ read_region, int32_t* __restrict__ rec, int32_t* __restrict__ count, int32_t* __restrict__ status)
+{
+    candidates_codes_one(b, SrcPacked{pk}, read_codes, ref_codes, ref_irregular, min_flank, min_base_qual, gen_snps, gen_indels, max_per_read,
+                         read_region, rec, count, status);
 }
 
 }  // namespace plat
@@ -361,8 +446,32 @@ PLAT_EXPORT int plat_candidates_batch_codes(plat_ctx* ctx, const plat_candidate_
     return PLAT_OK;
 }
 
-namespace plat {
-}  // namespace plat
+PLAT_EXPORT int plat_candidates_batch_packed(plat_ctx* ctx, const plat_candidate_batch* batch, const plat_packed_reads* packed, const uint32_t* read_codes,
+                                             const uint32_t* ref_codes, const int32_t* ref_irregular, int min_flank, int min_base_qual, int gen_snps, int gen_indels,
+                                             int max_per_read, const int32_t* read_region, int32_t* out_rec, int32_t* out_count, int32_t* out_status, void* stream)
+{
+    if (!ctx || !batch || !packed || max_per_read < 1 || min_flank < 0 || !read_codes || !ref_codes || !ref_irregular) return PLAT_ERR_INVALID;
+    if (((uintptr_t)read_codes & 7) || ((uintptr_t)ref_codes & 7)) return PLAT_ERR_INVALID;             // (read as 64-bit words)
+    const plat_candidate_batch b = *batch;
+    const plat_packed_reads pk = *packed;
+    if (b.n_regions < 0 || b.n_reads < 0 || pk.n_exc < 0) return PLAT_ERR_INVALID;
+    if (b.n_reads == 0) return PLAT_OK;
+    if (!b.ref_seq || !b.ref_off || !b.ref_seq_start || !b.contig_len || !b.read_seq || !b.read_off || !pk.read_src ||
+        (pk.n_exc > 0 && (!pk.exc_index || !pk.exc_base || !pk.exc_qual)) ||
+        !b.read_pos || !b.read_flags || !b.cigar || !b.cig_off || !read_region || !out_rec || !out_count || !out_status)
+        return PLAT_ERR_INVALID;
+    PLAT_HIP(ctx, hipSetDevice(ctx->device));
+    PLAT_EV_TAB(ctx, 2, (hipStream_t)stream);
+    { PLAT_KT_BEGIN(ctx, PLAT_KT_CANDIDATES, (hipStream_t)stream);
+      hipLaunchKernelGGL(plat::k_candidates_packed, dim3((unsigned)((b.n_reads + 63) / 64)), dim3(64), 0, (hipStream_t)stream, b, pk, (const unsigned long long*)read_codes,
+                         (const unsigned long long*)ref_codes, ref_irregular, min_flank, min_base_qual, gen_snps, gen_indels, max_per_read, read_region, out_rec, out_count,
+                         out_status);
+      PLAT_KT_END(ctx, PLAT_KT_CANDIDATES, (hipStream_t)stream); }
+    PLAT_EV_TAB(ctx, 3, (hipStream_t)stream);
+    ctx->ev_valid_cand = ctx->profile;
+    PLAT_HIP(ctx, hipGetLastError());
+    return PLAT_OK;
+}
 
 PLAT_EXPORT int plat_candidates_batch(plat_ctx* ctx, const plat_candidate_batch* batch, int min_flank, int min_base_qual,
                                       int gen_snps, int gen_indels, int max_per_read, const int32_t* read_region,
@@ -697,18 +806,21 @@ int plat_read_qc_packed_launch(plat_ctx* ctx, const plat_read_buffers_packed_in&
 // ballot popcount, the MMLQ window minima are written in read order (prefix popcount).
 namespace plat {
 
-__device__ __forceinline__ bool qual_good_at(const int8_t* q, int rlen, int readPos, int vmin, int vmax) {
+template <class R>
+__device__ __forceinline__ bool qual_good_at(const R& rd, int rlen, int readPos, int vmin, int vmax) {
     int a = max(0, min(rlen, vmin - readPos)), e = max(0, min(rlen, vmax - readPos));
-    for (int i = a; i < e; ++i) if (q[i] < 5) return false;
+    for (int i = a; i < e; ++i) if ((int8_t)rd.qual(i) < 5) return false;
     return true;
 }
 
-__device__ __forceinline__ bool bytes_equal(const uint8_t* a, const uint8_t* b, int n) {
-    for (int i = 0; i < n; ++i) if (a[i] != b[i]) return false;
+template <class R>
+__device__ __forceinline__ bool bytes_equal(const R& rd, int at, const uint8_t* b, int n) {
+    for (int i = 0; i < n; ++i) if (rd.base(at + i) != b[i]) return false;
     return true;
 }
 
-__device__ __forceinline__ bool read_supports(const uint8_t* seq, int rlen, int readStart, const int16_t* ops, int ncig, int varPos,
+template <class R>
+__device__ __forceinline__ bool read_supports(const R& seq, int rlen, int readStart, const int16_t* ops, int ncig, int varPos,
                                               int nAdded, int nRemoved, const uint8_t* added, int exact)
 {
     int refOffset = 0, readOffset = 0;
@@ -717,7 +829,7 @@ __device__ __forceinline__ bool read_supports(const uint8_t* seq, int rlen, int 
         if (flag == 1) {                                                     // insertion, :984-1003
             if (nAdded != nRemoved) {
                 if (!exact) return true;
-                if (nAdded - nRemoved == length && readOffset + nAdded <= rlen && bytes_equal(seq + readOffset, added, nAdded)) return true;
+                if (nAdded - nRemoved == length && readOffset + nAdded <= rlen && bytes_equal(seq, readOffset, added, nAdded)) return true;
                 return false;
             }
             readOffset += length;
@@ -727,7 +839,7 @@ __device__ __forceinline__ bool read_supports(const uint8_t* seq, int rlen, int 
         } else if (flag == 0 || flag == 7 || flag == 8) {                    // M, =, X, :1027-1048
             const int start = varPos - readStart + readOffset - refOffset;
             if (refOffset + readStart <= varPos && refOffset + readStart + length > varPos && nAdded == nRemoved &&
-                start >= 0 && start + nAdded <= rlen && bytes_equal(seq + start, added, nAdded))
+                start >= 0 && start + nAdded <= rlen && bytes_equal(seq, start, added, nAdded))
                 return true;
             readOffset += length;
             refOffset += length;
@@ -742,9 +854,9 @@ __device__ __forceinline__ bool read_supports(const uint8_t* seq, int rlen, int 
     return false;
 }
 
-__global__ void __launch_bounds__(64)
-k_variant_read_stats(plat_infostats_batch b, int bad_reads_window, int exact, int64_t* __restrict__ out, int32_t* __restrict__ per_sample,
-                     int32_t* __restrict__ minq, int32_t* __restrict__ nminq)
+template <class S>
+__device__ __forceinline__ void variant_read_stats_one(const plat_infostats_batch& b, const S& src, int bad_reads_window, int exact, int64_t* __restrict__ out,
+                                                       int32_t* __restrict__ per_sample, int32_t* __restrict__ minq, int32_t* __restrict__ nminq)
 {
     const int v = blockIdx.x, lane = threadIdx.x;
     const int w = b.var_window[v];
@@ -768,7 +880,7 @@ k_variant_read_stats(plat_infostats_batch b, int bad_reads_window, int exact, in
             if (r < be) {
                 const int rlen = (int)(b.read_off[r + 1] - b.read_off[r]);
                 hit = b.read_pos[r] <= vmax && b.read_end[r] > vmin &&
-                      qual_good_at((const int8_t*)b.read_qual + b.read_off[r], rlen, b.read_pos[r], vmin, vmax);
+                      qual_good_at(src.read(r, b.read_off[r], rlen), rlen, b.read_pos[r], vmin, vmax);
                 if (hit) m2 = (long long)b.read_mapq[r] * b.read_mapq[r];
             }
             c[1] += __popcll(__ballot(hit));
@@ -783,17 +895,19 @@ k_variant_read_stats(plat_infostats_batch b, int bad_reads_window, int exact, in
             if (r < ge) {
                 const long long so = b.read_off[r];
                 const int rlen = (int)(b.read_off[r + 1] - so);
-                const int8_t* q = (const int8_t*)b.read_qual + so;
                 const int rp = b.read_pos[r];
-                hit = rp <= vmax && b.read_end[r] > vmin && qual_good_at(q, rlen, rp, vmin, vmax);
-                if (hit) {
+                if (rp <= vmax && b.read_end[r] > vmin) {
+                    const auto rd = src.read(r, so, rlen);
+                    hit = qual_good_at(rd, rlen, rp, vmin, vmax);
+                    if (hit) {
                     rev = (b.read_flags[r] & 16) != 0;
                     m2 = (long long)b.read_mapq[r] * b.read_mapq[r];
-                    sup = read_supports(b.read_seq + so, rlen, rp, b.cigar + 2ll * b.cig_off[r], b.cig_off[r + 1] - b.cig_off[r], varPos,
+                    sup = read_supports(rd, rlen, rp, b.cigar + 2ll * b.cig_off[r], b.cig_off[r + 1] - b.cig_off[r], varPos,
                                         nAdded, nRemoved, added, exact);
                     if (sup && inGt) {                                       // MMLQ window, :1372-1383
                         const int ws = max(0, vmin - rp - half), we = min(rlen, vmax - rp + half);
-                        for (int k = ws; k < we; ++k) wmin = (k == ws) ? (int)q[k] : min(wmin, (int)q[k]);
+                        for (int k = ws; k < we; ++k) { const int qk = (int)(int8_t)rd.qual(k); wmin = (k == ws) ? qk : min(wmin, qk); }
+                    }
                     }
                 }
             }
@@ -823,6 +937,21 @@ k_variant_read_stats(plat_infostats_batch b, int bad_reads_window, int exact, in
     }
 }
 
+__global__ void __launch_bounds__(64)
+k_variant_read_stats(plat_infostats_batch b, int bad_reads_window, int exact, int64_t* __restrict__ out, int32_t* __restrict__ per_sample,
+                     int32_t* __restrict__ minq, int32_t* __restrict__ nminq)
+{
+    variant_read_stats_one(b, SrcAscii{b.read_seq, b.read_qual}, bad_reads_window, exact, out, per_sample, minq, nminq);
+}
+
+// ... and on packed bytes at their source (plat_variant_read_stats_packed_batch)
+__global__ void __launch_bounds__(64)
+k_variant_read_stats_packed(plat_infostats_batch b, plat_packed_reads pk, int bad_reads_window, int exact, int64_t* __restrict__ out,
+                            int32_t* __restrict__ per_sample, int32_t* __restrict__ minq, int32_t* __restrict__ nminq)
+{
+    variant_read_stats_one(b, SrcPacked{pk}, bad_reads_window, exact, out, per_sample, minq, nminq);
+}
+
 }  // namespace plat
 
 PLAT_EXPORT int plat_variant_read_stats_batch(plat_ctx* ctx, const plat_infostats_batch* batch, int bad_reads_window,
@@ -841,6 +970,27 @@ PLAT_EXPORT int plat_variant_read_stats_batch(plat_ctx* ctx, const plat_infostat
     PLAT_HIP(ctx, hipSetDevice(ctx->device));
     { PLAT_KT_BEGIN(ctx, PLAT_KT_VARIANT_READ_STATS, (hipStream_t)stream); hipLaunchKernelGGL(plat::k_variant_read_stats, dim3(b.n_vars), dim3(64), 0, (hipStream_t)stream, b, bad_reads_window,
                        count_only_exact_indel_matches, out_counts, out_per_sample, out_minq, out_nminq); PLAT_KT_END(ctx, PLAT_KT_VARIANT_READ_STATS, (hipStream_t)stream); }
+    PLAT_HIP(ctx, hipGetLastError());
+    return PLAT_OK;
+}
+
+PLAT_EXPORT int plat_variant_read_stats_packed_batch(plat_ctx* ctx, const plat_infostats_batch* batch, const plat_packed_reads* packed, int bad_reads_window,
+                                                     int count_only_exact_indel_matches, int64_t* out_counts, int32_t* out_per_sample,
+                                                     int32_t* out_minq, int32_t* out_nminq, void* stream)
+{
+    if (!ctx || !batch || !packed || bad_reads_window < 1) return PLAT_ERR_INVALID;
+    const plat_infostats_batch b = *batch;
+    const plat_packed_reads pk = *packed;
+    if (b.n_vars < 0 || b.n_ind < 1 || pk.n_exc < 0) return PLAT_ERR_INVALID;
+    if (b.n_vars == 0) return PLAT_OK;
+    if (!b.var_window || !b.var_pos || !b.var_bam_min || !b.var_bam_max || !b.var_n_added || !b.var_n_removed || !b.var_added ||
+        !b.var_added_off || !b.var_in_genotype || !b.minq_off || !b.good_begin || !b.good_end || !b.bad_begin || !b.bad_end ||
+        !pk.read_src || (pk.n_exc > 0 && (!pk.exc_index || !pk.exc_base || !pk.exc_qual)) || !b.read_off || !b.read_pos || !b.read_end ||
+        !b.read_mapq || !b.read_flags || !b.cigar || !b.cig_off || !out_counts || !out_per_sample || !out_minq || !out_nminq)
+        return PLAT_ERR_INVALID;
+    PLAT_HIP(ctx, hipSetDevice(ctx->device));
+    { PLAT_KT_BEGIN(ctx, PLAT_KT_VARIANT_READ_STATS, (hipStream_t)stream); hipLaunchKernelGGL(plat::k_variant_read_stats_packed, dim3(b.n_vars), dim3(64), 0, (hipStream_t)stream, b, pk,
+                       bad_reads_window, count_only_exact_indel_matches, out_counts, out_per_sample, out_minq, out_nminq); PLAT_KT_END(ctx, PLAT_KT_VARIANT_READ_STATS, (hipStream_t)stream); }
     PLAT_HIP(ctx, hipGetLastError());
     return PLAT_OK;
 }
@@ -996,7 +1146,68 @@ k_gather_reads(long long n_dst, const int32_t* __restrict__ src_index, const int
         if (l16 == 0) { dst_pos[d] = src_pos[s]; dst_end[d] = src_end[s]; dst_mapq[d] = src_mapq[s]; dst_flags[d] = src_flags[s]; }
     }
 }
+
+// The same from packed sources (plat_gather_reads_packed): sixteen lanes per destination read, each turns 16 packed bytes into the base line
+// AND the quality line (half the bytes in for the same bytes out).  A read with exceptions -- rare -- goes byte by byte through the accessor.
+__global__ void __launch_bounds__(256)
+k_gather_reads_packed(long long n_dst, const int32_t* __restrict__ src_index, const int64_t* __restrict__ dst_off, plat_packed_reads pk,
+                      const int64_t* __restrict__ src_off, const int32_t* __restrict__ src_pos, const int32_t* __restrict__ src_end,
+                      const uint8_t* __restrict__ src_mapq, const int32_t* __restrict__ src_flags, uint8_t* __restrict__ dst_seq,
+                      uint8_t* __restrict__ dst_qual, int32_t* __restrict__ dst_pos, int32_t* __restrict__ dst_end, uint8_t* __restrict__ dst_mapq,
+                      int32_t* __restrict__ dst_flags)
+{
+    typedef unsigned long long __attribute__((aligned(1))) u64u;
+    const int l16 = threadIdx.x & 15;
+    const long long ng = ((long long)gridDim.x * blockDim.x) >> 4;
+    const SrcPacked sp{pk};
+    for (long long d = (((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 4); d < n_dst; d += ng) {
+        const int s = src_index[d];
+        const long long so = src_off[s], n = src_off[s + 1] - so, to = dst_off[d];
+        const ReadPacked rd = sp.read(s, so, n);
+        uint8_t* dseq = dst_seq + to;
+        uint8_t* dqual = dst_qual + to;
+        if (n >= 16 && rd.e0 == rd.e1) {                                // pieces of 16 bytes; the last one ends AT the read's end (it may overlap the one before)
+            const long long np = (n + 15) >> 4;
+            for (long long k = l16; k < np; k += 16) {
+                const long long i = k + 1 < np ? 16 * k : n - 16;
+                const unsigned long long a = *(const u64u*)(rd.p + i), c = *(const u64u*)(rd.p + i + 8);
+                const uint32_t w[4] = {(uint32_t)a, (uint32_t)(a >> 32), (uint32_t)c, (uint32_t)(c >> 32)};
+                uint32_t sq[4], ql[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    sq[q] = __builtin_amdgcn_perm(0u, 0x47544341u, w[q] & 0x03030303u);       // byte selector 0..3 -> 'A' 'C' 'T' 'G'
+                    ql[q] = (w[q] >> 2) & 0x3F3F3F3Fu;
+                }
+                *(u64u*)(dseq + i) = (unsigned long long)sq[0] | ((unsigned long long)sq[1] << 32);
+                *(u64u*)(dseq + i + 8) = (unsigned long long)sq[2] | ((unsigned long long)sq[3] << 32);
+                *(u64u*)(dqual + i) = (unsigned long long)ql[0] | ((unsigned long long)ql[1] << 32);
+                *(u64u*)(dqual + i + 8) = (unsigned long long)ql[2] | ((unsigned long long)ql[3] << 32);
+            }
+        } else for (long long i = l16; i < n; i += 16) { dseq[i] = rd.base((int)i); dqual[i] = rd.qual((int)i); }
+        if (l16 == 0) { dst_pos[d] = src_pos[s]; dst_end[d] = src_end[s]; dst_mapq[d] = src_mapq[s]; dst_flags[d] = src_flags[s]; }
+    }
+}
 }  // namespace plat
+
+PLAT_EXPORT int plat_gather_reads_packed(plat_ctx* ctx, int64_t n_dst, const int32_t* src_index, const int64_t* dst_off, const plat_packed_reads* packed,
+                                         const int64_t* src_off, const int32_t* src_pos, const int32_t* src_end, const uint8_t* src_mapq,
+                                         const int32_t* src_flags, uint8_t* dst_seq, uint8_t* dst_qual, int32_t* dst_pos, int32_t* dst_end,
+                                         uint8_t* dst_mapq, int32_t* dst_flags, void* stream)
+{
+    if (!ctx || n_dst < 0 || !packed || packed->n_exc < 0) return PLAT_ERR_INVALID;
+    if (n_dst == 0) return PLAT_OK;
+    const plat_packed_reads pk = *packed;
+    if (!src_index || !dst_off || !pk.read_src || (pk.n_exc > 0 && (!pk.exc_index || !pk.exc_base || !pk.exc_qual)) || !src_off || !src_pos || !src_end ||
+        !src_mapq || !src_flags || !dst_seq || !dst_qual || !dst_pos || !dst_end || !dst_mapq || !dst_flags)
+        return PLAT_ERR_INVALID;
+    PLAT_HIP(ctx, hipSetDevice(ctx->device));
+    const long long nblk = (n_dst + 15) / 16;                         // 256 threads = 16 reads
+    { PLAT_KT_BEGIN(ctx, PLAT_KT_GATHER_READS, (hipStream_t)stream); hipLaunchKernelGGL(plat::k_gather_reads_packed, dim3((unsigned)(nblk < 65535 * 8 ? nblk : 65535 * 8)), dim3(256), 0, (hipStream_t)stream,
+                       (long long)n_dst, src_index, dst_off, pk, src_off, src_pos, src_end, src_mapq, src_flags, dst_seq, dst_qual, dst_pos, dst_end, dst_mapq,
+                       dst_flags); PLAT_KT_END(ctx, PLAT_KT_GATHER_READS, (hipStream_t)stream); }
+    PLAT_HIP(ctx, hipGetLastError());
+    return PLAT_OK;
+}
 
 PLAT_EXPORT int plat_gather_reads(plat_ctx* ctx, int64_t n_dst, const int32_t* src_index, const int64_t* dst_off,
                                   const uint8_t* src_seq, const uint8_t* src_qual, const int64_t* src_off, const int32_t* src_pos,
@@ -1195,18 +1406,114 @@ static int unpack_pieces(plat_ctx* ctx, int n_pieces, int64_t max_piece_bytes, c
     return PLAT_OK;
 }
 
+// ---- the codes alone, the packed bytes staying where they are (plat_pack_codes_pieces) ------------------------------------------------------
+namespace plat {
+// Before the pass: the code dwords a piece does not fill by itself -- the one holding its first base and the one behind its last, where they are
+// shared with a neighbouring piece or with nothing -- and the 8 words behind the blob's last base start as zeros; everything else is stored whole.
+// (The whole-buffer memset of plat_unpack_reads_pieces_codes was a quarter byte per base written twice.)
+__global__ void __launch_bounds__(256)
+k_codes_edges(const plat_unpack_piece* __restrict__ pieces, int n_pieces, long long total_bytes, uint32_t* __restrict__ codes)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < n_pieces) {
+        const plat_unpack_piece pc = pieces[k];
+        if (pc.n > 0) {
+            if (pc.dst & 15) codes[pc.dst >> 4] = 0u;
+            if ((pc.dst + pc.n) & 15) codes[(pc.dst + pc.n) >> 4] = 0u;
+        }
+    } else if (k < n_pieces + 8) codes[(total_bytes + 15) / 16 + (k - n_pieces)] = 0u;
+}
+
+// blockIdx.y = piece; one thread per code dword of the piece's place in the blob (16 bases: one 128-bit load, or two 64-bit ones from a source of
+// another alignment, and one 32-bit store); a dword the piece shares is OR-ed in, once
+__global__ void __launch_bounds__(256)
+k_unpack_pieces_codes(const plat_unpack_piece* __restrict__ pieces, uint32_t* __restrict__ codes)
+{
+    const plat_unpack_piece pc = pieces[blockIdx.y];
+    const uint8_t* packed = pc.src;
+    const long long n = pc.n;
+    if (n <= 0) return;
+    const long long d0 = pc.dst >> 4, d1 = (pc.dst + n + 15) >> 4;
+    const bool srcAligned = (((uintptr_t)packed - (uintptr_t)(pc.dst & 15)) & 15) == 0;
+    for (long long d = d0 + (long long)blockIdx.x * blockDim.x + threadIdx.x; d < d1; d += (long long)gridDim.x * blockDim.x) {
+        const long long i0 = 16 * d - pc.dst;                              // the dword's first base, counted from the piece's
+        if (i0 >= 0 && i0 + 16 <= n) {
+            uint32_t w[4];
+            if (srcAligned) { const uint4 v = *(const uint4*)(packed + i0); w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w; }
+            else {
+                const unsigned long long lo = load_u64_bytes(packed + i0), hi = load_u64_bytes(packed + i0 + 8);
+                w[0] = (uint32_t)lo; w[1] = (uint32_t)(lo >> 32); w[2] = (uint32_t)hi; w[3] = (uint32_t)(hi >> 32);
+            }
+            uint32_t cw = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                uint32_t t = w[k] & 0x03030303u;
+                t = (t | (t >> 6)) & 0x000F000Fu;
+                cw |= ((t | (t >> 12)) & 0xFFu) << (8 * k);
+            }
+            codes[d] = cw;
+        } else {
+            uint32_t cw = 0;
+            for (long long i = i0 < 0 ? 0 : i0; i < n && i < i0 + 16; ++i) cw |= ((uint32_t)packed[i] & 3u) << (2 * (int)(i - i0));
+            atomicOr(&codes[d], cw);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256)
+k_codes_exceptions(long long n_exc, long long n, const int64_t* __restrict__ idx, const uint8_t* __restrict__ eb, uint32_t* __restrict__ codes)
+{
+    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_exc) return;
+    const long long i = idx[k];
+    if (i < 0 || i >= n) return;
+    const unsigned sh = 2u * (unsigned)(i & 15);                           // the base's code follows its byte: (ASCII >> 1) & 3
+    atomicAnd(&codes[i >> 4], ~(3u << sh));
+    atomicOr(&codes[i >> 4], (((unsigned)eb[k] >> 1) & 3u) << sh);
+}
+}  // namespace plat
+
+PLAT_EXPORT int plat_pack_codes_pieces(plat_ctx* ctx, int n_pieces, int64_t max_piece_bytes, const plat_unpack_piece* pieces, uint32_t* out_codes,
+                                       int64_t total_bytes, int64_t n_exc, const int64_t* exc_index, const uint8_t* exc_base, void* stream)
+{
+    if (!ctx || n_pieces < 0 || max_piece_bytes < 0 || total_bytes < 0 || n_exc < 0) return PLAT_ERR_INVALID;
+    if (n_pieces == 0) return PLAT_OK;
+    if (!pieces || !out_codes || (n_exc > 0 && (!exc_index || !exc_base))) return PLAT_ERR_INVALID;
+    PLAT_HIP(ctx, hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(plat::k_codes_edges, dim3((unsigned)((n_pieces + 8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, pieces, n_pieces, (long long)total_bytes, out_codes);
+    long long gx = (max_piece_bytes / 16 + 256) / 256;
+    gx = gx < 1 ? 1 : (gx > 1024 ? 1024 : gx);
+    PLAT_EV_TAB(ctx, 0, (hipStream_t)stream);
+    for (int p0 = 0; p0 < n_pieces; p0 += PLAT_GRID_Y_MAX) {      // (gridDim.y holds at most 65 535 pieces: one launch per batch of them)
+        const int np = n_pieces - p0 < PLAT_GRID_Y_MAX ? n_pieces - p0 : PLAT_GRID_Y_MAX;
+        { PLAT_KT_BEGIN(ctx, PLAT_KT_UNPACK_PIECES, (hipStream_t)stream); hipLaunchKernelGGL(plat::k_unpack_pieces_codes, dim3((unsigned)gx, (unsigned)np), dim3(256), 0, (hipStream_t)stream, pieces + p0, out_codes); PLAT_KT_END(ctx, PLAT_KT_UNPACK_PIECES, (hipStream_t)stream); }
+    }
+    PLAT_EV_TAB(ctx, 1, (hipStream_t)stream);
+    ctx->ev_valid_unpack = ctx->profile;
+    if (n_exc > 0)
+        hipLaunchKernelGGL(plat::k_codes_exceptions, dim3((unsigned)((n_exc + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (long long)n_exc, (long long)total_bytes,
+                           exc_index, exc_base, out_codes);
+    PLAT_HIP(ctx, hipGetLastError());
+    return PLAT_OK;
+}
+
 // ---- a chunk's read table put together on the device from resident tables (plat_concat_read_tables) ----------------------------------
 namespace plat {
-__global__ void __launch_bounds__(256)
-k_concat_tables(const plat_table_desc* __restrict__ desc, int64_t* __restrict__ dst_off, int32_t* __restrict__ dst_pos, int32_t* __restrict__ dst_end,
+__device__ __forceinline__ void concat_src(const plat_table_desc&, int, long long, const uint8_t**) {}
+__device__ __forceinline__ void concat_src(const plat_table_src_desc& d, int i, long long r, const uint8_t** dst_src) { dst_src[r] = d.src + d.off[i]; }
+
+// (D = plat_table_src_desc: + the per-read source pointer column of a chunk whose packed bytes are read where they lie)
+template <class D>
+__device__ __forceinline__ void concat_tables_one(const D* __restrict__ desc, int64_t* __restrict__ dst_off, int32_t* __restrict__ dst_pos, int32_t* __restrict__ dst_end,
                 uint8_t* __restrict__ dst_mapq, int32_t* __restrict__ dst_flags, int32_t* __restrict__ dst_cig_off, int16_t* __restrict__ dst_cigar,
-                int32_t* __restrict__ dst_region, long long n_total, long long total_bytes, long long total_pairs)
+                int32_t* __restrict__ dst_region, const uint8_t** __restrict__ dst_src, long long n_total, long long total_bytes, long long total_pairs)
 {
-    const plat_table_desc d = desc[blockIdx.y];
+    const D d = desc[blockIdx.y];
     const int stride = gridDim.x * blockDim.x;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < d.n; i += stride) {
         const long long r = d.first_read + i;
         dst_off[r] = d.first_byte + d.off[i];
+        concat_src(d, i, r, dst_src);
         dst_pos[r] = d.pos[i]; dst_end[r] = d.end[i]; dst_mapq[r] = d.mapq[i]; dst_flags[r] = d.flags[i];
         const int c0 = d.cig_off[i], c1 = d.cig_off[i + 1];
         dst_cig_off[r] = (int32_t)(d.first_pair + c0);
@@ -1221,7 +1528,42 @@ k_concat_tables(const plat_table_desc* __restrict__ desc, int64_t* __restrict__ 
         dst_cigar[2 * total_pairs] = 0; dst_cigar[2 * total_pairs + 1] = 0;
     }
 }
+
+__global__ void __launch_bounds__(256)
+k_concat_tables(const plat_table_desc* __restrict__ desc, int64_t* __restrict__ dst_off, int32_t* __restrict__ dst_pos, int32_t* __restrict__ dst_end,
+                uint8_t* __restrict__ dst_mapq, int32_t* __restrict__ dst_flags, int32_t* __restrict__ dst_cig_off, int16_t* __restrict__ dst_cigar,
+                int32_t* __restrict__ dst_region, long long n_total, long long total_bytes, long long total_pairs)
+{
+    concat_tables_one(desc, dst_off, dst_pos, dst_end, dst_mapq, dst_flags, dst_cig_off, dst_cigar, dst_region, nullptr, n_total, total_bytes, total_pairs);
+}
+
+__global__ void __launch_bounds__(256)
+k_concat_tables_src(const plat_table_src_desc* __restrict__ desc, int64_t* __restrict__ dst_off, int32_t* __restrict__ dst_pos, int32_t* __restrict__ dst_end,
+                    uint8_t* __restrict__ dst_mapq, int32_t* __restrict__ dst_flags, int32_t* __restrict__ dst_cig_off, int16_t* __restrict__ dst_cigar,
+                    int32_t* __restrict__ dst_region, const uint8_t** __restrict__ dst_src, long long n_total, long long total_bytes, long long total_pairs)
+{
+    concat_tables_one(desc, dst_off, dst_pos, dst_end, dst_mapq, dst_flags, dst_cig_off, dst_cigar, dst_region, dst_src, n_total, total_bytes, total_pairs);
+}
 }  // namespace plat
+
+PLAT_EXPORT int plat_concat_read_tables_src(plat_ctx* ctx, int n_tables, int max_reads_per_table, const plat_table_src_desc* desc, int64_t* dst_off, int32_t* dst_pos,
+                                            int32_t* dst_end, uint8_t* dst_mapq, int32_t* dst_flags, int32_t* dst_cig_off, int16_t* dst_cigar,
+                                            int32_t* dst_region, const uint8_t** dst_src, int64_t n_total_reads, int64_t total_bytes, int64_t total_pairs, void* stream)
+{
+    if (!ctx || n_tables < 0 || max_reads_per_table < 0 || n_total_reads < 0) return PLAT_ERR_INVALID;
+    if (!dst_off || !dst_pos || !dst_end || !dst_mapq || !dst_flags || !dst_cig_off || !dst_cigar || !dst_region || !dst_src) return PLAT_ERR_INVALID;
+    if (n_tables < 1 || !desc) return PLAT_ERR_INVALID;
+    PLAT_HIP(ctx, hipSetDevice(ctx->device));
+    unsigned gx = (unsigned)((max_reads_per_table + 255) / 256);
+    gx = gx < 1 ? 1 : (gx > 64 ? 64 : gx);
+    for (int t0 = 0; t0 < n_tables; t0 += PLAT_GRID_Y_MAX) {      // (every batch's first block also writes the table's closing entries: the same values)
+        const int nt = n_tables - t0 < PLAT_GRID_Y_MAX ? n_tables - t0 : PLAT_GRID_Y_MAX;
+        { PLAT_KT_BEGIN(ctx, PLAT_KT_CONCAT_TABLES, (hipStream_t)stream); hipLaunchKernelGGL(plat::k_concat_tables_src, dim3(gx, (unsigned)nt), dim3(256), 0, (hipStream_t)stream, desc + t0, dst_off, dst_pos, dst_end,
+                           dst_mapq, dst_flags, dst_cig_off, dst_cigar, dst_region, dst_src, (long long)n_total_reads, (long long)total_bytes, (long long)total_pairs); PLAT_KT_END(ctx, PLAT_KT_CONCAT_TABLES, (hipStream_t)stream); }
+    }
+    PLAT_HIP(ctx, hipGetLastError());
+    return PLAT_OK;
+}
 
 PLAT_EXPORT int plat_concat_read_tables(plat_ctx* ctx, int n_tables, int max_reads_per_table, const plat_table_desc* desc, int64_t* dst_off, int32_t* dst_pos,
                                         int32_t* dst_end, uint8_t* dst_mapq, int32_t* dst_flags, int32_t* dst_cig_off, int16_t* dst_cigar,

@@ -325,7 +325,55 @@ class Engine:
         words = (c.reshape(n, 16) << (2 * np.arange(16, dtype=np.uint32))).sum(axis=1, dtype=np.uint64).astype(np.uint32)
         return np.concatenate([words, np.zeros(8, dtype=np.uint32)])
 
-    def candidates(self, regions, min_flank=10, min_base_qual=20, gen_snps=1, gen_indels=1, max_per_read=64, codes=False):
+    def pack_reads(self, seqs, quals, gaps=None):
+        """Reads as a PLAT_READS_PACKED table on the device, for the entry points that read packed bases where they lie: one byte per base
+        ((ASCII >> 1) & 3 | min(quality, 63) << 2), exceptions (a base other than A/C/G/T, a quality above 63) indexed by the read blob's byte
+        index.  gaps[i]: bytes left free in front of read i's packed bytes (its source pointer then has that alignment shift; default none).
+        Returns dict(reads=_lib.PackedReads, src, blob, off, exc_index, exc_base, exc_qual); keep it alive while `reads` is used."""
+        torch = _torch()
+        n = len(seqs)
+        gaps = [0] * n if gaps is None else list(gaps)
+        lens = np.array([len(x) for x in seqs], dtype=np.int64)
+        off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+        seq = np.frombuffer(b"".join(bytes(x) for x in seqs), dtype=np.uint8)
+        qual = np.frombuffer(b"".join(bytes(x) for x in quals), dtype=np.uint8)
+        plain = (seq == 65) | (seq == 67) | (seq == 71) | (seq == 84)
+        ex = np.nonzero(~plain | (qual > 63))[0].astype(np.int64)
+        byte = (((seq >> 1) & 3) | (np.minimum(qual, 63) << 2)).astype(np.uint8)
+        at = np.cumsum(np.asarray(gaps, dtype=np.int64) + np.concatenate([[0], lens[:-1]])) if n else np.zeros(0, dtype=np.int64)
+        blob = np.full(int(at[-1] + lens[-1]) + _lib.PLAT_BLOB_PAD if n else _lib.PLAT_BLOB_PAD, 0xA7, dtype=np.uint8)
+        for i in range(n):
+            blob[at[i]:at[i] + lens[i]] = byte[off[i]:off[i + 1]]
+
+        def dev(a, dt):
+            return torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(self.device)
+        t = dict(blob=dev(blob, np.uint8), off=dev(off, np.int64), exc_index=dev(np.concatenate([ex, [0]]), np.int64),
+                 exc_base=dev(np.concatenate([seq[ex], [0]]), np.uint8), exc_qual=dev(np.concatenate([qual[ex], [0]]), np.uint8))
+        t["src"] = dev(t["blob"].data_ptr() + at if n else np.zeros(1), np.int64)
+        pk = _lib.PackedReads()
+        pk.read_src, pk.n_exc = t["src"].data_ptr(), len(ex)
+        pk.exc_index, pk.exc_base, pk.exc_qual = t["exc_index"].data_ptr(), t["exc_base"].data_ptr(), t["exc_qual"].data_ptr()
+        t["reads"] = pk
+        return t
+
+    def pack_codes_pieces(self, pieces, n_pieces, max_piece_bytes, codes, total_bytes, exc_index=None, exc_base=None):
+        """plat_pack_codes_pieces on device tensors (pieces: plat_unpack_piece records as bytes; codes: the output words)."""
+        n_exc = 0 if exc_index is None else int(exc_index.numel())
+        _lib.check(self.lib.plat_pack_codes_pieces(self.ctx, n_pieces, max_piece_bytes, pieces.data_ptr(), codes.data_ptr(), total_bytes, n_exc,
+                                                   exc_index.data_ptr() if n_exc else 0, exc_base.data_ptr() if n_exc else 0, self._stream()), "plat_pack_codes_pieces")
+        self._sync()
+
+    def gather_reads_packed(self, n_dst, src_index, dst_off, packed, src_off, src_pos, src_end, src_mapq, src_flags, dst_seq, dst_qual, dst_pos, dst_end,
+                            dst_mapq, dst_flags):
+        """plat_gather_reads_packed on device tensors (packed: a _lib.PackedReads, e.g. pack_reads()["reads"])."""
+        _lib.check(self.lib.plat_gather_reads_packed(self.ctx, n_dst, src_index.data_ptr(), dst_off.data_ptr(), C.byref(packed), src_off.data_ptr(), src_pos.data_ptr(),
+                                                     src_end.data_ptr(), src_mapq.data_ptr(), src_flags.data_ptr(), dst_seq.data_ptr(), dst_qual.data_ptr(),
+                                                     dst_pos.data_ptr(), dst_end.data_ptr(), dst_mapq.data_ptr(), dst_flags.data_ptr(), self._stream()),
+                   "plat_gather_reads_packed")
+        self._sync()
+
+    def candidates(self, regions, min_flank=10, min_base_qual=20, gen_snps=1, gen_indels=1, max_per_read=64, codes=False, packed=False, gaps=None,
+                   retry=True):
         """VariantCandidateGenerator.addCandidatesFromReads for a list of regions.
 
         `regions`: list of dicts {ref: bytes (contig[ref_seq_start:...]), ref_seq_start, contig_len, reads: [dict(seq, qual,
@@ -359,11 +407,27 @@ class Engine:
         b.ref_seq, b.ref_off, b.ref_seq_start, b.contig_len = t["ref"].data_ptr(), t["ref_off"].data_ptr(), t["rss"].data_ptr(), t["clen"].data_ptr()
         b.read_seq, b.read_qual, b.read_off = t["seq"].data_ptr(), t["qual"].data_ptr(), t["read_off"].data_ptr()
         b.read_pos, b.read_flags, b.cigar, b.cig_off = t["pos"].data_ptr(), t["flags"].data_ptr(), t["cig"].data_ptr(), t["cig_off"].data_ptr()
+        if packed:
+            # plat_candidates_batch_packed: letters and qualities from the packed bytes (pack_reads); read_seq is its OUTPUT for the records' read-side
+            # alleles (filled with a pattern here) and there are no expanded qualities
+            pk = self.pack_reads([r["seq"] for r in reads], [r["qual"] for r in reads], gaps)
+            t["seq"] = torch.full((len(seq_blob) + _lib.PLAT_BLOB_PAD,), 0xEE, dtype=torch.uint8, device=self.device)
+            b.read_seq, b.read_qual = t["seq"].data_ptr(), 0
         while True:
-            rec = torch.empty(nR * max_per_read * 5, dtype=torch.int32, device=self.device)
+            rec = torch.full((nR * max_per_read * 5,), -77, dtype=torch.int32, device=self.device)
             cnt = torch.empty(nR, dtype=torch.int32, device=self.device)
             stt = torch.empty(nR, dtype=torch.int32, device=self.device)
-            if codes:
+            if packed:
+                rc_t = dev(self.base_codes(seq_blob), np.uint32)
+                fc_t = torch.zeros((len(ref_blob) + 15) // 16 + 16, dtype=torch.int32, device=self.device)
+                irr = torch.zeros(nG + 1, dtype=torch.int32, device=self.device)
+                _lib.check(self.lib.plat_ref_codes(self.ctx, nG, t["ref"].data_ptr(), t["ref_off"].data_ptr(), len(ref_blob), fc_t.data_ptr(), irr.data_ptr(),
+                                                   self._stream()), "plat_ref_codes")
+                rc = self.lib.plat_candidates_batch_packed(self.ctx, C.byref(b), C.byref(pk["reads"]), rc_t.data_ptr(), fc_t.data_ptr(), irr.data_ptr(), min_flank,
+                                                           min_base_qual, gen_snps, gen_indels, max_per_read, t["region_of"].data_ptr(), rec.data_ptr(),
+                                                           cnt.data_ptr(), stt.data_ptr(), self._stream())
+                self.last_ref_irregular = irr
+            elif codes:
                 # the scan on 2-bit codes (plat_candidates_batch_codes): the reads' codes from the host here (the region loop gets them from the unpack
                 # kernel), the reference's from plat_ref_codes; the caller promises reads of A, C, G, T, N only
                 rc_t = dev(self.base_codes(seq_blob), np.uint32)
@@ -381,6 +445,11 @@ class Engine:
             _lib.check(rc, "plat_candidates_batch")
             self._sync()
             cnt_h, st_h = cnt.cpu().numpy(), stt.cpu().numpy()
+            # (tests: what this pass wrote, as it is -- records, counts, statuses, the read blob the kernel was given)
+            self.last_candidates = dict(rec=rec.cpu().numpy().reshape(nR, max_per_read, 5), count=cnt_h, status=st_h, read_seq=t["seq"].cpu().numpy()[:len(seq_blob)],
+                                        max_per_read=max_per_read)
+            if not retry:
+                return None
             if (st_h == -9).any():
                 raise _lib.PlatypusDeviceError(-9, "a read reaches outside the reference window handed over", "plat_candidates_batch")
             if (st_h == -8).any():
@@ -666,7 +735,7 @@ class Engine:
         return out
 
     # ---- read statistics of the VCF INFO field --------------------------------------------
-    def variant_read_stats(self, windows, bad_reads_window=11, exact=0):
+    def variant_read_stats(self, windows, bad_reads_window=11, exact=0, packed=False, gaps=None):
         """vcfINFO's per-read loop for a list of windows.  A window: dict {variants: [dict(pos, removed, added, bam_min,
         bam_max)], samples: [dict(good=[reads], bad=[reads])], var_in_genotype: [nVars][nInd]}; a read = dict(seq, qual, pos, end,
         mapq, flag, cigar).  All windows must have the same number of samples.  Returns per window a list over its variants of
@@ -714,8 +783,15 @@ class Engine:
         ps = torch.empty(nV * nI * 2, dtype=torch.int32, device=self.device)
         mq = torch.empty(max(mtot, 1), dtype=torch.int32, device=self.device)
         nmq = torch.empty(nV, dtype=torch.int32, device=self.device)
-        _lib.check(self.lib.plat_variant_read_stats_batch(self.ctx, C.byref(b), bad_reads_window, exact, out.data_ptr(), ps.data_ptr(),
-                                                          mq.data_ptr(), nmq.data_ptr(), self._stream()), "plat_variant_read_stats_batch")
+        if packed:                                  # plat_variant_read_stats_packed_batch: no expanded bases or qualities at all
+            pk = self.pack_reads([r["seq"] for r in reads], [r["qual"] for r in reads], gaps)
+            b.read_seq, b.read_qual = 0, 0
+            _lib.check(self.lib.plat_variant_read_stats_packed_batch(self.ctx, C.byref(b), C.byref(pk["reads"]), bad_reads_window, exact, out.data_ptr(),
+                                                                     ps.data_ptr(), mq.data_ptr(), nmq.data_ptr(), self._stream()),
+                       "plat_variant_read_stats_packed_batch")
+        else:
+            _lib.check(self.lib.plat_variant_read_stats_batch(self.ctx, C.byref(b), bad_reads_window, exact, out.data_ptr(), ps.data_ptr(),
+                                                              mq.data_ptr(), nmq.data_ptr(), self._stream()), "plat_variant_read_stats_batch")
         self._sync()
         out_h, ps_h, mq_h, nmq_h = out.cpu().numpy().reshape(nV, 16), ps.cpu().numpy().reshape(nV, nI, 2), mq.cpu().numpy(), nmq.cpu().numpy()
         res = [[] for _ in windows]
