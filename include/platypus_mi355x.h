@@ -340,7 +340,9 @@ int plat_candidates_batch(plat_ctx* ctx, const plat_candidate_batch* batch, int 
  * scan_longest[g] = ReadArray.getLengthOfLongestRead().  Output per scan (out_n[2g] counts only when out_n[2g+1] == 0): out_n[2g] candidates that pass, unordered, 8 ints each at
  * out_cand[8*(g*cap_per_scan + i)]: {id of the first record with this content (read index * max_per_read + k: sort by it for
  * the dictionary's order), reads showing it, reads covering its position, then the record's five fields}.  out_n[2g+1] = 0,
- * PLAT_ERR_BAD_INPUT (a read outside its reference window, or read pointers out of order: the reference raises),
+ * PLAT_ERR_BAD_INPUT (a read outside its reference window, or "Read start pointer > read end pointer" where the reference raises it: the
+ * start pointer walks past the end pointer only over reads whose read_end lies at or before a site they start before -- read positions
+ * out of order cannot bring it about by themselves, a read_end inconsistent with its read can),
  * PLAT_ERR_OVERFLOW (more than 6144 distinct records or more than cap_per_scan candidates: merge this scan on the host) or
  * -(2^20 + n) when a read has n > max_per_read records (scan again with room for n).                                        */
 int plat_candidates_merge_batch(plat_ctx* ctx, const plat_candidate_batch* batch, const int32_t* read_end, int n_scans,
@@ -414,9 +416,24 @@ int plat_concat_read_tables(plat_ctx* ctx, int n_tables, int max_reads_per_table
  *               small for this region), dictionaries replayed, 0}; status 0, or
  *               PLAT_SB_HOST: this region needs the caller's own code (more candidates / variants / windows than the capacities, an
  *               indel at the edge of its reference window, an order that depends on a Python dictionary, an exception the reference
- *               would raise, ...) -- nothing else of the region is valid then.
+ *               would raise, ...) -- nothing else of the region is valid then (its slices of the arrays below may have been written,
+ *               inside their capacities; hdr[3], hdr[4], hdr[6], hdr[7] are not).  The reason codes in use:
+ *                 1  a pure insertion / deletion at refPos >= 100 whose normalisation window [wmin, wmax) = [max(1, pos - w), min(pos + w,
+ *                    contig_len - 1)), w = max(nAdded, nRemoved) + rlen, is not inside the reference window handed over (wmin < ref_seq_start
+ *                    or wmax > ref_seq_start + length), or whose tail is empty (cut + nRemoved + 1 >= wmax - wmin, cut = pos - wmin: it ends
+ *                    where the contig does); "Error in variant conversion to standard format"; nRemoved >= 2^24 or nAdded >= 2^16
+ *                 2  an order that depends on a dictionary (two kept variants with one (refPos, type, nRemoved), or three or more
+ *                    candidates with one such key among which one variant occurs twice next to a different one; more than 48 candidates
+ *                    with one key count as such) and no records to replay it with (cand_rec or region_name_hash NULL) or more than 5400
+ *                    distinct records in the scan
+ *                 3  the replayed dictionary does not hold every candidate (a candidate that is no record of the scan: a caller's error)
+ *                 5  cand_n[2g + 1] != 0 (the merge's own verdict), more than 1024 candidates, more than cap_per_scan
+ *                 6  more variants than cap_vars, more windows than cap_windows (windows wider than maxSize are dropped first and take no
+ *                    room), more added bases than cap_added (every insertion that normalisation moved takes its bases, kept or not, then
+ *                    every kept variant whose bases still lie in read_seq); 6 wins over 1
+ *               (4 is reserved: no path sets it.)
  *   variants    [g*cap_vars + i]: var_pos, var_nrem, var_nadd, var_support (nSupportingReads), var_bam_min, var_bam_max
- *               (bamMinPos / bamMaxPos), var_rem_pos (contig coordinate of the removed bases), var_add_off (offset of the added
+ *               (bamMinPos / bamMaxPos), var_rem_pos (contig coordinate of the removed bases; not specified when var_nrem is 0), var_add_off (offset of the added
  *               bases in added[g*cap_added ..]); sorted as the reference's list is.
  *   windows     [g*cap_windows + k]: win_start, win_end, win_var_first, win_var_n (its variants = a run of the region's list),
  *               win_flags (PLAT_SBW_*), win_ptrs[6 * ..] = {reads begin, end, badReads begin, end, brokenMates begin, end} (indices
@@ -429,10 +446,16 @@ int plat_concat_read_tables(plat_ctx* ctx, int n_tables, int max_reads_per_table
  *               of a window, most haplotypes of a window, overflow (a batch capacity was too small: nothing of the batch is valid), ...}
  * No host round trip inside; the caller reads hdr / totals back once. */
 #define PLAT_SB_HOST 1
-#define PLAT_SBW_SKIP 1          /* no reads / too many reads / skipDifficultWindows: the loop does not call this window */
-#define PLAT_SBW_HOST 2          /* the caller prepares this window itself (greedy haplotype filter, filterVariantsByCoverage, an exception) */
-#define PLAT_SBW_DUPLICATE 4     /* in the batch, but two of its haplotypes have the same sequence and an indel among their variants (or
-                                  * agree on more bytes than the device looks at): mergeHaplotypes / the order is the caller's */
+#define PLAT_SBW_SKIP 1          /* no good reads / more than maxReads / more variants than maxVariants with skipDifficultWindows / one haplotype
+                                  * left after equal sequences were merged: the loop does not call this window (win_n_haps = 0, not in the batch) */
+#define PLAT_SBW_HOST 2          /* the caller prepares this window itself: more variants than maxVariants (filterVariantsByCoverage), more than
+                                  * log2(maxHaplotypes - 1) or than 5 (the greedy haplotype filter), a haplotype the reference raises on (longer
+                                  * than 16384, beginPos > endPos), "Read start pointer > read end pointer", a window whose haplotypes or variant
+                                  * positions reach outside the reference window handed over ([max(start, 0) - flank, min(end, contig_len - 1) +
+                                  * flank) clamped to the contig), 2^31 bytes of reads or haplotypes (win_n_haps = 0, not in the batch) */
+#define PLAT_SBW_DUPLICATE 4     /* in the batch with EVERY valid combination (order unspecified), but two of its haplotypes have the same sequence and
+                                  * an indel / replacement among their variants (or a multi-nucleotide variant with 0 or more than 16 differences), or
+                                  * agree on the 384 bytes behind the window's common prefix and go on: mergeHaplotypes / the order is the caller's */
 typedef struct plat_stage_b_options {
     int32_t minReads, maxSize, mergeClusteredVariants, maxVarDist, minVarDist, largeWindows, maxVariants, maxHaplotypes;
     int32_t filterVarsByCoverage, skipDifficultWindows;

@@ -136,6 +136,33 @@ class UnpackPiece(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_int64), ("n", C.c_int64)]
 
 
+class StageBOptions(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("minReads", "maxSize", "mergeClusteredVariants", "maxVarDist", "minVarDist", "largeWindows", "maxVariants",
+                                         "maxHaplotypes", "filterVarsByCoverage", "skipDifficultWindows")] + [("maxReads", C.c_double)]
+
+
+class StageBIn(C.Structure):
+    _fields_ = ([("n_regions", C.c_int32), ("cap_per_scan", C.c_int32)] +
+                [(k, C.c_void_p) for k in ("cand", "cand_n", "cand_rec", "region_name_hash", "ref_seq", "ref_off", "ref_seq_start", "contig_len",
+                                           "region_start", "region_end", "region_rlen", "read_seq", "read_off", "read_pos", "read_end",
+                                           "tab_begin", "tab_n", "tab_longest", "broken_mate_pos")] +
+                [(k, C.c_int32) for k in ("broken_base", "cap_vars", "cap_windows", "cap_added", "cap_batch_windows", "cap_batch_haps", "cap_batch_reads")] +
+                [("cap_hap_bytes", C.c_int64)])
+
+
+# the output arrays of plat_stage_b_out in the header's order, with the element type of each
+STAGE_B_OUT_FIELDS = (
+    ("hdr", "i4"), ("var_pos", "i4"), ("var_nrem", "i4"), ("var_nadd", "i4"), ("var_support", "i4"), ("var_bam_min", "i4"), ("var_bam_max", "i4"),
+    ("var_rem_pos", "i4"), ("var_add_off", "i4"), ("added", "u1"), ("win_start", "i4"), ("win_end", "i4"), ("win_var_first", "i4"), ("win_var_n", "i4"),
+    ("win_flags", "i4"), ("win_ptrs", "i4"), ("win_n_haps", "i4"), ("win_batch", "i4"), ("b_hap_begin", "i4"), ("b_read_begin", "i4"), ("b_start", "i4"),
+    ("b_end", "i4"), ("b_flank", "i4"), ("b_pair_off", "i8"), ("b_gl_off", "i8"), ("b_seg_begin", "i4"), ("b_n_good", "i4"), ("b_hap_off", "i8"),
+    ("b_hap_mask", "u4"), ("b_hap_seq", "u1"), ("b_read_off", "i8"), ("b_read_src", "i4"), ("b_read_kind", "u1"), ("totals", "i8"), ("scratch", "i4"))
+
+
+class StageBOut(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k, _ in STAGE_B_OUT_FIELDS]
+
+
 # symbol -> (restype, argtypes): exactly the declarations of include/platypus_mi355x.h
 SIGNATURES = {
     "plat_abi_version": (C.c_int, []),
@@ -182,7 +209,7 @@ SIGNATURES = {
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "plat_candidates_merge_batch": (C.c_int, [C.c_void_p, C.POINTER(CandidateBatch), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "plat_stage_b_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "plat_stage_b_batch": (C.c_int, [C.c_void_p, C.POINTER(StageBIn), C.POINTER(StageBOptions), C.POINTER(StageBOut), C.c_void_p]),
     "plat_unpack_reads_pieces": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p]),
     "plat_unpack_reads_pieces_codes": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,

@@ -83,6 +83,26 @@ def _py2_heap_order(heap):
     return [vs[k] for k in py2_dict_slot_order([py2_variant_hash(v.refName, v.refPos, v.removed, v.added) for v in vs])]
 
 
+def order_can_matter(norm, kept):
+    """`sorted` is stable: candidates that compare equal (two alleles of one type and length at one position) stay in dictionary
+    order; every other order is decided by the keys.  It reaches the result where two KEPT variants compare equal, or where a run
+    of equal keys holds a variant twice (equal neighbours merge: who is whose neighbour depends on it) next to a different one."""
+    tied = lambda a, c: not (a < c) and not (c < a)
+    if any(tied(a, c) for a, c in zip(kept, kept[1:])):
+        return True
+    i = 0
+    while i < len(norm):
+        e = i + 1
+        while e < len(norm) and not (norm[i] < norm[e]):
+            e += 1
+        if e - i >= 3:
+            pairs = [(norm[x] == norm[y]) for x in range(i, e) for y in range(x + 1, e)]
+            if any(pairs) and not all(pairs):
+                return True
+        i = e
+    return False
+
+
 def generateVariantsInRegions(regions, refFile, options):
     """generateVariantsInRegion for a list of (chrom, start, end, readBuffers): ONE candidate scan on the device for every
     sample of every region, then the reference's per-sample support filter, merge, left-normalisation and filterVariants.
@@ -143,25 +163,6 @@ def generateVariantsInRegions(regions, refFile, options):
         cands.extend(clone(v) for v in extras[k])                                # rawBamVariants + assemblerVariants (:521)
         norm = sorted(leftNormaliseIndel(v, refFile, rlens[k]) for v in cands)
         return norm, filterVariants(norm, refFile, rlens[k], options.minReads, options.maxSize, options.verbosity, options)
-
-    def order_can_matter(norm, kept):
-        """`sorted` is stable: candidates that compare equal (two alleles of one type and length at one position) stay in dictionary
-        order; every other order is decided by the keys.  It reaches the result where two KEPT variants compare equal, or where a run
-        of equal keys holds a variant twice (equal neighbours merge: who is whose neighbour depends on it) next to a different one."""
-        tied = lambda a, c: not (a < c) and not (c < a)
-        if any(tied(a, c) for a, c in zip(kept, kept[1:])):
-            return True
-        i = 0
-        while i < len(norm):
-            e = i + 1
-            while e < len(norm) and not (norm[i] < norm[e]):
-                e += 1
-            if e - i >= 3:
-                pairs = [(norm[x] == norm[y]) for x in range(i, e) for y in range(x + 1, e)]
-                if any(pairs) and not all(pairs):
-                    return True
-            i = e
-        return False
 
     for k in range(len(regions)):
         norm, kept = candidates(k, False)

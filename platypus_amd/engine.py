@@ -373,13 +373,15 @@ class Engine:
         self._sync()
 
     def candidates(self, regions, min_flank=10, min_base_qual=20, gen_snps=1, gen_indels=1, max_per_read=64, codes=False, packed=False, gaps=None,
-                   retry=True):
+                   retry=True, keep_device=False):
         """VariantCandidateGenerator.addCandidatesFromReads for a list of regions.
 
         `regions`: list of dicts {ref: bytes (contig[ref_seq_start:...]), ref_seq_start, contig_len, reads: [dict(seq, qual,
         pos, flag, cigar [(op, len), ...])]}.  Returns per region the per-occurrence records [(refPos, removed, added,
-        read index)] in the reference's emission order (merging equal variants is the caller's dictionary step)."""
+        read index)] in the reference's emission order (merging equal variants is the caller's dictionary step).
+        keep_device: the records and the tables behind them stay on the device for candidates_merge() / stage_b() until the next scan."""
         torch = _torch()
+        self._cand_dev = self._merge_dev = None
         nG = len(regions)
         reads = [r for g in regions for r in g["reads"]]
         nR = len(reads)
@@ -448,6 +450,10 @@ class Engine:
             # (tests: what this pass wrote, as it is -- records, counts, statuses, the read blob the kernel was given)
             self.last_candidates = dict(rec=rec.cpu().numpy().reshape(nR, max_per_read, 5), count=cnt_h, status=st_h, read_seq=t["seq"].cpu().numpy()[:len(seq_blob)],
                                         max_per_read=max_per_read)
+            if keep_device:
+                # (candidates_merge / stage_b: the records and the tables those two read, as they lie on the device)
+                self._cand_dev = dict(tensors={k: t[k] for k in ("ref", "ref_off", "rss", "clen", "seq", "pos")}, rec=rec, count=cnt, status=stt,
+                                      max_per_read=max_per_read, n_regions=nG, n_reads=nR)
             if not retry:
                 return None
             if (st_h == -9).any():
@@ -464,6 +470,143 @@ class Engine:
             for p_, nrem, nadd, ro, ao in rec_h[r, :cnt_h[r]].tolist():
                 out[g].append((p_, ref_blob[ro:ro + nrem] if nrem else b"", seq_blob[ao:ao + nadd] if nadd else b"", r - int(first[g])))
         return out
+
+    # ---- the dictionary step behind the scan, and stage B ----------------------------------------------------
+    SENTINEL = 0xA5                                                              # every byte of an output array before the call
+    _cand_dev = _merge_dev = None
+
+    def _sentinel(self, n, dt):
+        torch = _torch()
+        return torch.full((int(n) * np.dtype(dt).itemsize,), self.SENTINEL, dtype=torch.uint8, device=self.device)
+
+    @classmethod
+    def sentinel_of(cls, dt):
+        """The value an untouched element of an output array of candidates_merge / stage_b holds."""
+        return np.frombuffer(bytes([cls.SENTINEL]) * np.dtype(dt).itemsize, dtype=dt)[0]
+
+    def candidates_merge(self, scan_read_begin, read_end, scan_longest, min_var_freq, cap_per_scan):
+        """plat_candidates_merge_batch on the records the last candidates(keep_device=True) call left on the device.  Scan g = reads
+        [scan_read_begin[g], scan_read_begin[g + 1]) of that call's read table; read_end[r] = cAlignedRead.end.  Returns (out_cand
+        [n_scans, cap_per_scan, 8], out_n [n_scans, 2]) on the host; rows the kernels did not write hold the sentinel.  The device
+        arrays stay for stage_b()."""
+        torch = _torch()
+        cd = self._cand_dev
+        if cd is None:
+            raise RuntimeError("candidates_merge() needs the records of a candidates(..., keep_device=True) call")
+        nS = len(scan_read_begin) - 1
+        t = cd["tensors"]
+        b = _lib.CandidateBatch()                                                # the merge reads the alleles' bytes and the reads' positions, nothing else
+        b.n_regions, b.n_reads = cd["n_regions"], cd["n_reads"]
+        b.ref_seq, b.read_seq, b.read_pos = t["ref"].data_ptr(), t["seq"].data_ptr(), t["pos"].data_ptr()
+        dev = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(self.device)
+        t_end, t_begin, t_long = dev(read_end, np.int32), dev(scan_read_begin, np.int32), dev(scan_longest, np.int32)
+        assert len(read_end) == cd["n_reads"] and len(scan_longest) == nS
+        out_cand, out_n = self._sentinel(max(nS, 1) * cap_per_scan * 8, np.int32), self._sentinel(2 * max(nS, 1), np.int32)
+        _lib.check(self.lib.plat_candidates_merge_batch(self.ctx, C.byref(b), t_end.data_ptr(), nS, t_begin.data_ptr(), t_long.data_ptr(),
+                                                        cd["max_per_read"], cd["rec"].data_ptr(), cd["count"].data_ptr(), cd["status"].data_ptr(),
+                                                        float(min_var_freq), cap_per_scan, out_cand.data_ptr(), out_n.data_ptr(), self._stream()),
+                   "plat_candidates_merge_batch")
+        self._sync()
+        self._merge_dev = dict(cand=out_cand, cand_n=out_n, cap_per_scan=cap_per_scan, n_scans=nS, read_end=t_end, keep=(t_begin, t_long))
+        return (out_cand.cpu().numpy().view(np.int32).reshape(max(nS, 1), cap_per_scan, 8)[:nS],
+                out_n.cpu().numpy().view(np.int32).reshape(max(nS, 1), 2)[:nS])
+
+    def _empty_merge(self, n_scans):
+        """The context's table of distinct records, sized for n_scans scans and empty: what plat_stage_b_batch reads when the candidates
+        do not come from a merge on this context."""
+        torch = _torch()
+        z = torch.zeros(64 + n_scans + 1, dtype=torch.int32, device=self.device)
+        o = torch.zeros(8 + 2 * n_scans, dtype=torch.int32, device=self.device)
+        b = _lib.CandidateBatch()
+        b.n_regions, b.n_reads = n_scans, 0
+        for k, _ in _lib.CandidateBatch._fields_[2:]:
+            setattr(b, k, z.data_ptr())
+        _lib.check(self.lib.plat_candidates_merge_batch(self.ctx, C.byref(b), z.data_ptr(), n_scans, z.data_ptr(), z.data_ptr(), 1, z.data_ptr(), z.data_ptr(),
+                                                        z.data_ptr(), 0.0, 1, o.data_ptr(), o.data_ptr(), self._stream()), "plat_candidates_merge_batch")
+        self._sync()
+
+    def stage_b(self, regions, tables, options, cand=None, cand_n=None, read_seq=None, cap_per_scan=None, with_records=False, cap_vars=64, cap_windows=32,
+                cap_added=256, cap_batch_windows=64, cap_batch_haps=512, cap_batch_reads=1024, cap_hap_bytes=1 << 20):
+        """plat_stage_b_batch.  `regions`: dicts {ref, ref_seq_start, contig_len, start, end, rlen[, name_hash]}; `tables`: the read table the
+        window pointers and the batch index into -- dict(read_off [n + 1], read_pos [n], read_end [n], tab_begin / tab_n / tab_longest
+        [3 * regions], broken_mate_pos, broken_base).  Candidates: `cand` [regions, cap_per_scan, 8] rows of plat_candidates_merge_batch's
+        out_cand made by hand (offsets into the concatenated `ref`s and into `read_seq`) with `cand_n` [regions, 2]; cand_rec is NULL then.
+        Or cand=None: the arrays candidates_merge() left on the device, with the reference windows and the read blob of that scan (`ref`,
+        `ref_seq_start`, `contig_len` of the dicts and `read_seq` are not used then); with_records hands the scan's records over for the
+        dictionary replay (cand_rec, region_name_hash), otherwise both are NULL.  `options`: the fields of plat_stage_b_options.
+        Every output array starts filled with the sentinel byte.  Returns a dict of every array of plat_stage_b_out on the host (hdr
+        [regions, 8], per-region arrays [regions, cap], win_ptrs [regions, cap_windows, 6], totals [16]); the scratch stays on the device."""
+        torch = _torch()
+        nG = len(regions)
+        dev = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(self.device)
+        keep = []
+
+        def ptr(a, dt):
+            keep.append(dev(a, dt))
+            return keep[-1].data_ptr()
+        bi = _lib.StageBIn()
+        bi.n_regions = nG
+        if cand is None:
+            cd, md = self._cand_dev, self._merge_dev
+            assert md["n_scans"] == nG == cd["n_regions"]
+            t = cd["tensors"]
+            bi.cap_per_scan, bi.cand, bi.cand_n = md["cap_per_scan"], md["cand"].data_ptr(), md["cand_n"].data_ptr()
+            bi.ref_seq, bi.ref_off, bi.ref_seq_start, bi.contig_len = t["ref"].data_ptr(), t["ref_off"].data_ptr(), t["rss"].data_ptr(), t["clen"].data_ptr()
+            bi.read_seq = t["seq"].data_ptr()
+            if with_records:
+                bi.cand_rec = cd["rec"].data_ptr()
+                bi.region_name_hash = ptr([g["name_hash"] for g in regions], np.int64)
+        else:
+            cand = np.ascontiguousarray(cand, dtype=np.int32)
+            assert cand.shape == (nG, cap_per_scan, 8) and read_seq is not None
+            self._empty_merge(nG)
+            bi.cap_per_scan, bi.cand, bi.cand_n = cap_per_scan, ptr(cand, np.int32), ptr(cand_n, np.int32)
+            ref_blob = b"".join(bytes(g["ref"]) for g in regions)
+            bi.ref_seq = ptr(pad_blob(np.frombuffer(ref_blob, dtype=np.uint8)), np.uint8)
+            bi.ref_off = ptr(np.concatenate([[0], np.cumsum([len(g["ref"]) for g in regions])]), np.int64)
+            bi.ref_seq_start, bi.contig_len = ptr([g["ref_seq_start"] for g in regions], np.int32), ptr([g["contig_len"] for g in regions], np.int32)
+            bi.read_seq = ptr(pad_blob(np.frombuffer(bytes(read_seq), dtype=np.uint8)), np.uint8)
+        bi.region_start, bi.region_end = ptr([g["start"] for g in regions], np.int32), ptr([g["end"] for g in regions], np.int32)
+        bi.region_rlen = ptr([g["rlen"] for g in regions], np.int32)
+        n_reads = len(tables["read_pos"])
+        assert len(tables["read_off"]) == n_reads + 1 and len(tables["read_end"]) == n_reads
+        for k in ("tab_begin", "tab_n", "tab_longest"):
+            assert len(tables[k]) == 3 * nG
+        assert all(0 <= b0 and b0 + n <= n_reads for b0, n in zip(tables["tab_begin"], tables["tab_n"]))
+        bi.read_off, bi.read_pos, bi.read_end = ptr(tables["read_off"], np.int64), ptr(list(tables["read_pos"]) + [0], np.int32), ptr(list(tables["read_end"]) + [0], np.int32)
+        bi.tab_begin, bi.tab_n, bi.tab_longest = ptr(tables["tab_begin"], np.int32), ptr(tables["tab_n"], np.int32), ptr(tables["tab_longest"], np.int32)
+        bi.broken_mate_pos, bi.broken_base = ptr(list(tables["broken_mate_pos"]) + [0], np.int32), int(tables["broken_base"])
+        bi.cap_vars, bi.cap_windows, bi.cap_added = cap_vars, cap_windows, cap_added
+        bi.cap_batch_windows, bi.cap_batch_haps, bi.cap_batch_reads, bi.cap_hap_bytes = cap_batch_windows, cap_batch_haps, cap_batch_reads, cap_hap_bytes
+        so = _lib.StageBOptions()
+        for k, _ in _lib.StageBOptions._fields_:
+            setattr(so, k, options[k] if isinstance(options, dict) else getattr(options, k))
+        per = dict(hdr=8 * nG, added=nG * cap_added, win_ptrs=6 * nG * cap_windows, totals=16, b_hap_off=cap_batch_haps + 1, b_hap_mask=cap_batch_haps,
+                   b_hap_seq=cap_hap_bytes, b_read_off=cap_batch_reads + 1, b_read_src=cap_batch_reads, b_read_kind=cap_batch_reads,
+                   scratch=56 * nG * cap_windows + 48 * nG + 64)
+        for k in ("b_hap_begin", "b_read_begin", "b_pair_off", "b_gl_off", "b_seg_begin"):
+            per[k] = cap_batch_windows + 1
+        for k in ("b_start", "b_end", "b_flank", "b_n_good"):
+            per[k] = cap_batch_windows
+        bo = _lib.StageBOut()
+        outs = {}
+        for k, dt in _lib.STAGE_B_OUT_FIELDS:
+            n = per.get(k, nG * (cap_vars if k.startswith("var_") else cap_windows))
+            outs[k] = self._sentinel(n, dt)
+            setattr(bo, k, outs[k].data_ptr())
+        _lib.check(self.lib.plat_stage_b_batch(self.ctx, C.byref(bi), C.byref(so), C.byref(bo), self._stream()), "plat_stage_b_batch")
+        self._sync()
+        res = {k: outs[k].cpu().numpy().view(dt) for k, dt in _lib.STAGE_B_OUT_FIELDS if k != "scratch"}
+        res["hdr"] = res["hdr"].reshape(nG, 8)
+        res["added"] = res["added"].reshape(nG, cap_added)
+        for k in res:
+            if k.startswith("var_"):
+                res[k] = res[k].reshape(nG, cap_vars)
+            elif k == "win_ptrs":
+                res[k] = res[k].reshape(nG, cap_windows, 6)
+            elif k.startswith("win_"):
+                res[k] = res[k].reshape(nG, cap_windows)
+        return res
 
     # ---- read QC / trimming (checkAndTrimRead) ---------------------------------------------------------------
     def read_qc(self, streams, min_good_qual_bases=20, min_map_qual=20, min_base_qual=20, trim_overlapping=1, trim_adapter=1,

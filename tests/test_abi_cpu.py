@@ -49,6 +49,12 @@ int main(void){
          offsetof(plat_window_batch, hap_seq), offsetof(plat_window_batch, read_kind));
   printf("%zu %zu\n", sizeof(plat_align_stats), sizeof(plat_assembly_batch));
   printf("%d %d\n", PLAT_BLOB_PAD, PLAT_ABI_VERSION);
+  printf("%zu %zu %zu\n", sizeof(plat_stage_b_in), sizeof(plat_stage_b_options), sizeof(plat_stage_b_out));
+  printf("%zu %zu %zu %zu %zu\n", offsetof(plat_stage_b_in, cand_rec), offsetof(plat_stage_b_in, read_seq), offsetof(plat_stage_b_in, broken_base),
+         offsetof(plat_stage_b_in, cap_batch_windows), offsetof(plat_stage_b_in, cap_hap_bytes));
+  printf("%zu %zu\n", offsetof(plat_stage_b_options, skipDifficultWindows), offsetof(plat_stage_b_options, maxReads));
+  printf("%zu %zu %zu %zu\n", offsetof(plat_stage_b_out, added), offsetof(plat_stage_b_out, b_hap_mask), offsetof(plat_stage_b_out, totals),
+         offsetof(plat_stage_b_out, scratch));
   return 0; }''')
     exe = tmp_path / "lay"
     subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
@@ -59,6 +65,17 @@ int main(void){
     assert vals[2] == WB.hap_seq.offset and vals[3] == WB.read_kind.offset
     assert vals[4] == C.sizeof(_lib.AlignStats) and vals[5] == C.sizeof(_lib.AssemblyBatch)
     assert vals[6] == _lib.PLAT_BLOB_PAD and vals[7] == _lib.PLAT_ABI_VERSION
+    SI, SO, SU = _lib.StageBIn, _lib.StageBOptions, _lib.StageBOut
+    assert vals[8:11] == [C.sizeof(SI), C.sizeof(SO), C.sizeof(SU)]
+    assert vals[11:16] == [SI.cand_rec.offset, SI.read_seq.offset, SI.broken_base.offset, SI.cap_batch_windows.offset, SI.cap_hap_bytes.offset]
+    assert vals[16:18] == [SO.skipDifficultWindows.offset, SO.maxReads.offset]
+    assert vals[18:22] == [SU.added.offset, SU.b_hap_mask.offset, SU.totals.offset, SU.scratch.offset]
+    text = open(HEADER).read()                                                     # ... and the field NAMES, in the header's order
+    body = lambda name: re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), text, re.S).group(1)
+    names = lambda name: re.findall(r"[\s*](\w+)\s*[;,]", re.sub(r"/\*.*?\*/", "", body(name), flags=re.S))
+    assert names("plat_stage_b_in") == [k for k, _ in SI._fields_]
+    assert names("plat_stage_b_options") == [k for k, _ in SO._fields_]
+    assert names("plat_stage_b_out") == [k for k, _ in SU._fields_] == [k for k, _ in _lib.STAGE_B_OUT_FIELDS]
 
 
 def test_product_package_never_imports_the_oracle():
