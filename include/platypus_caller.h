@@ -45,7 +45,8 @@ extern "C" {
  *                      it lies (in `seq`'s upload, or at dev_seq), exceptions looked up; a chunk that also holds ASCII tables (or an
  *                      exception byte other than A/C/G/T/N) is expanded to ASCII once (plat_unpack_reads_pieces).  Either way every
  *                      kernel sees the letters and qualities it sees with PLAT_READS_ASCII and the records are the same.
- *                      PLAT_CALLER_EXPAND=1 in the environment forces the expansion (measurements / tests). */
+ *                      PLAT_CALLER_EXPAND=1 in the environment forces the expansion (measurements / tests; read at every call, as every
+ *                      PLAT_CALLER_* switch: platypus_amd/csrc/host/switches.hpp has the table). */
 enum { PLAT_READS_ASCII = 0, PLAT_READS_PACKED = 1 };
 
 /* One ReadArray (cwindow.pyx:92-236) as arrays: cAlignedRead fields (htslibWrapper.pxd:187-201) of n_reads reads.

@@ -19,6 +19,7 @@
 #include "../../../include/platypus_caller.h"
 #include "../../../include/platypus_mi355x.h"
 #include "records.hpp"
+#include "switches.hpp"
 #include "variants.hpp"
 #define CALLER_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -57,9 +58,8 @@ static void profDump(double) {}
 #endif
 // PLAT_CALLER_TRACE=1 (measurement): of every stage's seconds, the part spent waiting for the device; [8] host, [9] wait (under the stats mutex)
 static double g_stageWait[10];
-static void traceStages(const plat_caller_stats& st) {
-    const char* e = getenv("PLAT_CALLER_TRACE");
-    if (e && e[0] == '1') {
+static void traceStages(const plat_caller_stats& st, const Switches& sw) {
+    if (sw.traceStages) {
         static const char* names[8] = {"upload", "candidate_scan", "variants_windows_haplotypes", "greedy_rounds", "window_batch", "posteriors",
                                        "read_stats_calls", "text"};
         const double n = (double)std::max<int64_t>(1, st.n_regions);
@@ -113,6 +113,15 @@ template <class T> struct Staged {
 };
 typedef Staged<uint8_t> Arena;
 
+// How a chunk's read table is read (planned per chunk: planReadPath, stage_a.hpp).  Bytes: t_seq / t_qual hold every base and quality (ASCII or mixed chunks,
+// or the byte scan asked for); Codes: ... and t_codes their 2-bit codes, which the candidate scan runs on; Packed: t_codes only -- letters and qualities
+// are read from the packed bytes where they lie, through Slot::pk
+enum class ReadPath { Bytes, Codes, Packed };
+// Algorithmic bytes of the first pass over `n` packed bases: one byte in, two out per base (3), + a quarter when the 2-bit codes are written too (3 1/4), or one
+// byte in and the quarter out when the codes are all it writes (1 1/4); and of the scan, which reads the bases once: as 2-bit codes, or as bytes
+static inline int64_t firstPassBytes(ReadPath p, int64_t n) { return p == ReadPath::Packed ? n + n / 4 : p == ReadPath::Codes ? 3 * n + n / 4 : 3 * n; }
+static inline int64_t scanBytes(ReadPath p, int64_t n) { return p == ReadPath::Bytes ? n : n / 4; }
+
 struct SparePools;                                                         // window / Variant storage a worker keeps between the chunks of a call (defined behind WindowWork)
 struct Slot {
     SparePools* spare = nullptr;                                           // (made by the worker's first chunk of a call, freed when its chunks run out)
@@ -138,7 +147,7 @@ struct Slot {
     // there; every kernel that starts from a read takes the read's packed bytes at t_src[read] (in the caller's resident table or in t_pack)
     Staged<const uint8_t*> t_src;
     Staged<plat_table_src_desc> t_sdesc;
-    bool packedDirect = false;                                             // this chunk's table is read that way ...
+    ReadPath path = ReadPath::Bytes;                                       // how this chunk's table is read; Packed: ...
     plat_packed_reads pk = {};                                              // ... through these (t_src + the chunk's exceptions)
     Staged<int16_t> t_cigar;
     // candidate scan
@@ -188,6 +197,13 @@ struct Slot {
     }
     template <class T> void up(Staged<T>& s, size_t n) { if (n) ck(plat_memcpy_h2d(ctx, s.d, s.h, n * sizeof(T), stream), "plat_memcpy_h2d"); }
     template <class T> void down(Staged<T>& s, size_t n) { if (n) ck(plat_memcpy_d2h(ctx, s.h, s.d, n * sizeof(T), stream), "plat_memcpy_d2h"); }
+    // reads src[0 .. n) of the chunk table to the blobs at dstOff, with their per-read fields: from the expanded bytes, or from the packed ones
+    void gatherReads(int64_t n, const int32_t* src, const int64_t* dstOff, uint8_t* seq, uint8_t* qual, int32_t* pos, int32_t* end, uint8_t* mapq, int32_t* flags,
+                     const char* where) {
+        ck(path == ReadPath::Packed
+               ? plat_gather_reads_packed(ctx, n, src, dstOff, &pk, t_off.d, t_pos.d, t_end.d, t_mapq.d, t_flags.d, seq, qual, pos, end, mapq, flags, stream)
+               : plat_gather_reads(ctx, n, src, dstOff, t_seq.d, t_qual.d, t_off.d, t_pos.d, t_end.d, t_mapq.d, t_flags.d, seq, qual, pos, end, mapq, flags, stream), where);
+    }
 };
 
 // Arrays of one stage laid out back to back in one pinned block + one device block: one copy per stage and direction instead of one per
@@ -494,7 +510,7 @@ struct RegionWork {
     }
 };
 
-struct Options : plat_caller_options {};
+struct Options : plat_caller_options { Switches sw; };                    // a call's options and its switches (read when the call is entered)
 
 static void logWindowFailure(const char* chrom, int s, int e, const char* what) {
     fprintf(stderr, "platypus caller: problem calling variants in window %s:%d-%d, skipping it: %s\n", chrom, s, e, what);
@@ -590,12 +606,7 @@ static void runBatch(Slot& s, DeviceBatch& db, const Options& o, bool full, bool
     s.g_seq.reserve(s.ctx, blob + PLAT_BLOB_PAD, false, true, s.stream); s.g_qual.reserve(s.ctx, blob + PLAT_BLOB_PAD, false, true, s.stream);
     const size_t nR = (size_t)db.nReads;
     s.g_pos.reserve(s.ctx, nR + 1, false); s.g_end.reserve(s.ctx, nR + 1, false); s.g_flags.reserve(s.ctx, nR + 1, false); s.g_mapq.reserve(s.ctx, nR + 1, false);
-    if (s.packedDirect)
-        ck(plat_gather_reads_packed(s.ctx, (int64_t)nR, db.src, db.readoff, &s.pk, s.t_off.d, s.t_pos.d, s.t_end.d, s.t_mapq.d, s.t_flags.d, s.g_seq.d, s.g_qual.d,
-                                    s.g_pos.d, s.g_end.d, s.g_mapq.d, s.g_flags.d, s.stream), "plat_gather_reads_packed");
-    else
-    ck(plat_gather_reads(s.ctx, (int64_t)nR, db.src, db.readoff, s.t_seq.d, s.t_qual.d, s.t_off.d, s.t_pos.d, s.t_end.d, s.t_mapq.d,
-                         s.t_flags.d, s.g_seq.d, s.g_qual.d, s.g_pos.d, s.g_end.d, s.g_mapq.d, s.g_flags.d, s.stream), "plat_gather_reads");
+    s.gatherReads((int64_t)nR, db.src, db.readoff, s.g_seq.d, s.g_qual.d, s.g_pos.d, s.g_end.d, s.g_mapq.d, s.g_flags.d, "plat_gather_reads");
     plat_window_batch& wb = db.wb;
     wb.n_windows = db.nWindows; wb.n_haps = db.nHaps; wb.n_reads = db.nReads;
     wb.read_seq = s.g_seq.d; wb.read_qual = s.g_qual.d; wb.read_pos = s.g_pos.d; wb.read_end = s.g_end.d;
@@ -611,7 +622,7 @@ static void runBatch(Slot& s, DeviceBatch& db, const Options& o, bool full, bool
         ck(plat_profile_enable(s.ctx, 1), "plat_profile_enable");
         ck(plat_align_window_batch(s.ctx, &wb, o.calculateFlankScore ? 1 : 0, 0, s.o_loglik.d, nullptr, &as, s.stream), "plat_align_window_batch");
         s.nDpRef += as.n_dp_reference; s.cellsRef += as.cells_reference; s.nDpRun += as.n_dp_launched; s.cellsRun += as.cells_launched;
-        if (getenv("PLAT_CALLER_TRACE")) fprintf(stderr, "[plat_caller] likelihood batch: %d windows, %d haplotypes (longest %d), %lld pairs, %lld for the exact vote, %lld DPs launched / %lld reference\n",
+        if (o.sw.trace) fprintf(stderr, "[plat_caller] likelihood batch: %d windows, %d haplotypes (longest %d), %lld pairs, %lld for the exact vote, %lld DPs launched / %lld reference\n",
                                                  db.nWindows, db.nHaps, db.maxHap, (long long)db.nPairs, (long long)as.n_seed_fallback, (long long)as.n_dp_launched, (long long)as.n_dp_reference);
         plat_profile pf;
         memset(&pf, 0, sizeof pf);

@@ -7,6 +7,7 @@ namespace plathost {
 
 // ---- the chunk pipeline ----------------------------------------------------------------------------------------------------------------
 // One chunk of regions on one worker: members and the stages' entry points; the stages themselves are stage_a.hpp ... stage_f.hpp.
+struct TableSurvey; struct FilledTable;                                    // (stage_a.hpp)
 struct Chunk {
     Slot& s;
     const Options& o;
@@ -16,7 +17,10 @@ struct Chunk {
     plat_caller_stats& st;
     std::mutex& stMutex;
 
+    // -- A: the chunk's read table (stage_a.hpp): survey the tables, plan how they are read (s.path), lay the table out and fill it, run the first pass
     void uploadReads();
+    FilledTable fillTable(const TableSurvey& v);
+    void firstPass(const TableSurvey& v, const FilledTable& f);
     size_t nGood = 0, nBad = 0, nBroken = 0;
     int nScan = 0, maxReadLen = 0;
     int maxPerRead = 8;
@@ -99,8 +103,6 @@ struct Chunk {
 
     void regionVariants(RegionWork& r, int scan0);
     bool recordsOnHost = false;
-    bool readCodes = false;                                                 // the chunk's read blob has its 2-bit codes in s.t_codes (every table packed, exceptions A/C/G/T/N only)
-    bool packedDirect = false;                                              // ... and nothing else: its bases are read packed, where they lie (s.packedDirect)
     int64_t tabPackedBytes = 0, tabBlobBytes = 0;                          // this chunk's table: packed bytes expanded on the device, bytes of bases in all
     size_t recArenaBytes = 0;
 
@@ -163,15 +165,9 @@ struct Chunk {
             plat_profile pf;
             memset(&pf, 0, sizeof pf);
             ck(plat_profile_last(s.ctx, &pf), "plat_profile_last");
-            if (getenv("PLAT_CALLER_TRACE")) fprintf(stderr, "[plat_caller] table kernels: unpack %.3f ms (%lld packed bytes), candidates %.3f ms (%lld bytes)\n", pf.ms_unpack, (long long)tabPackedBytes, pf.ms_candidates, (long long)tabBlobBytes);
-            // one byte in, two out per base (+ a quarter: the 2-bit codes, when the chunk has them) -- or one byte in and the quarter out when the codes are all
-            // the first pass writes (packedDirect); the scan has to read the bases once: as 2-bit codes when it runs on them (qualities and bytes only where
-            // codes differ), as bytes otherwise
-            if (pf.ms_unpack > 0) {
-                s.secUnpack += 1e-3 * pf.ms_unpack; s.nUnpack += 1;
-                s.unpackBytes += packedDirect ? tabPackedBytes + tabPackedBytes / 4 : 3 * tabPackedBytes + (readCodes ? tabPackedBytes / 4 : 0);
-            }
-            if (pf.ms_candidates > 0) { s.secCand += 1e-3 * pf.ms_candidates; s.candBytes += readCodes ? tabBlobBytes / 4 : tabBlobBytes; s.nCand += 1; }
+            if (o.sw.trace) fprintf(stderr, "[plat_caller] table kernels: unpack %.3f ms (%lld packed bytes), candidates %.3f ms (%lld bytes)\n", pf.ms_unpack, (long long)tabPackedBytes, pf.ms_candidates, (long long)tabBlobBytes);
+            if (pf.ms_unpack > 0) { s.secUnpack += 1e-3 * pf.ms_unpack; s.nUnpack += 1; s.unpackBytes += firstPassBytes(s.path, tabPackedBytes); }
+            if (pf.ms_candidates > 0) { s.secCand += 1e-3 * pf.ms_candidates; s.candBytes += scanBytes(s.path, tabBlobBytes); s.nCand += 1; }
         }
         assembleCollect();
         lap(1);

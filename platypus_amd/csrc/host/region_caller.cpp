@@ -162,7 +162,6 @@ struct Feed {
     virtual ~Feed() {}
 };
 
-static bool checkHints() { const char* e = getenv("PLAT_CALLER_CHECK_HINTS"); return e && e[0] == '1'; }     // (read once per call of the library, not once per process)
 static std::unique_ptr<RegionWork> makeRegionWork(const plat_region* in, int index, int n_samples, int& longestOut, bool check) {
     std::unique_ptr<RegionWork> r(new RegionWork());
     r->in = in; r->index = index;
@@ -194,9 +193,8 @@ static inline int nextRlen(int rlen, int longest, int maxSize, int fromBams = 1)
 // Where the chunks of a call begin: whole chunks of `per` regions while every worker gets the same number of them, and what is left of the
 // list in one more round of EQUAL smaller chunks, one per worker -- with 61 chunks for 24 workers thirteen workers did three chunks while
 // eleven did two and then watched; 48 whole chunks + 24 of half the size end together (PLAT_CALLER_EVEN_TAIL=0: chunks of `per` to the end).
-static std::vector<int> chunkBounds(int n, int per, int workers) {
+static std::vector<int> chunkBounds(int n, int per, int workers, bool even) {
     std::vector<int> b{0};
-    static const bool even = [] { const char* e = getenv("PLAT_CALLER_EVEN_TAIL"); return !(e && e[0] == '0'); }();
     int at = 0;
     if (even && workers > 1 && n > per * workers) {
         const int rounds = n / (per * workers);
@@ -216,8 +214,8 @@ struct MemoryFeed : Feed {
     int nChunks;
     std::atomic<int> nextChunk{0};
     std::atomic<bool>& failed;
-    MemoryFeed(std::vector<std::unique_ptr<RegionWork>>& w, int per_, int workers, std::atomic<bool>& f)
-        : work(w), bound(chunkBounds((int)w.size(), per_, workers)), nChunks((int)bound.size() - 1), failed(f) {}
+    MemoryFeed(std::vector<std::unique_ptr<RegionWork>>& w, int per_, int workers, const Switches& sw, std::atomic<bool>& f)
+        : work(w), bound(chunkBounds((int)w.size(), per_, workers, sw.evenTail)), nChunks((int)bound.size() - 1), failed(f) {}
     bool next(std::vector<RegionWork*>& out) override {
         if (failed.load()) return false;
         const int ch = nextChunk.fetch_add(1);
@@ -246,10 +244,10 @@ struct StreamFeed : Feed {
     std::string errText;
     std::atomic<bool>& failed;
     double tLoad = 0, tWait = 0;
-    const bool check = checkHints();
-    StreamFeed(int n_, int nS, int per_, int workers, int maxSize_, int rlen0, plat_region_load_fn l, void* u, int nSlots, std::atomic<bool>& f)
+    const bool check;                                                      // PLAT_CALLER_CHECK_HINTS
+    StreamFeed(int n_, int nS, int per_, int workers, int maxSize_, int rlen0, plat_region_load_fn l, void* u, int nSlots, const Switches& sw, std::atomic<bool>& f)
         : n(n_), nSamples(nS), per(per_), nChunks(0), maxSize(maxSize_), load(l), user(u), work((size_t)n_), desc((size_t)n_),
-          slotOf((size_t)n_, -1), longest((size_t)n_, 0), loaded((size_t)n_, 0), bound(chunkBounds(n_, per_, workers)), chunkOf((size_t)n_, 0), rlen(rlen0), failed(f) {
+          slotOf((size_t)n_, -1), longest((size_t)n_, 0), loaded((size_t)n_, 0), bound(chunkBounds(n_, per_, workers, sw.evenTail)), chunkOf((size_t)n_, 0), rlen(rlen0), failed(f), check(sw.checkHints) {
         nChunks = (int)bound.size() - 1;
         chunkLoaded.assign((size_t)nChunks, 0);
         for (int c = 0; c < nChunks; ++c) for (int k = bound[(size_t)c]; k < bound[(size_t)c + 1]; ++k) chunkOf[(size_t)k] = c;
@@ -343,8 +341,7 @@ static int runWorkers(plat_caller* c, Feed& feed, std::atomic<bool>& failed, con
         // every worker frees its own spare storage when it runs out of chunks.  Keeping it for the next CALL (PLAT_CALLER_KEEP_SPARE=1) measured SLOWER on the
         // whole-genome job: 5.8-6.1 M windows/s against 6.5-6.6 M, 0.207 against 0.172 ms of worker CPU per region -- the next call's worker is a new thread,
         // often on the other NUMA node, and inherits ten thousand cold windows; freeing them all on one thread at the end of the call: 5.0 M
-        static const bool keep = [] { const char* e = getenv("PLAT_CALLER_KEEP_SPARE"); return e && e[0] == '1'; }();
-        if (!keep) { delete slot->spare; slot->spare = nullptr; }
+        if (!o.sw.keepSpare) { delete slot->spare; slot->spare = nullptr; }
     };
     nThreads = std::max(1, std::min<int>((int)c->slots.size(), nThreads));
     for (auto& q : c->slots) {
@@ -444,28 +441,26 @@ CALLER_EXPORT int plat_call_regions(plat_caller* c, const plat_region* regions, 
     plat_caller_stats st;
     memset(&st, 0, sizeof st);
     st.n_regions = n_regions;
-    Options o;
-    static_cast<plat_caller_options&>(o) = *options;
+    const Options o{*options, Switches::read()};                           // (the PLAT_CALLER_* switches as they are now: switches.hpp)
     std::vector<std::unique_ptr<RegionWork>> work;
     int rlen = options->rlen;
-    const bool check = checkHints();
     for (int k = 0; k < n_regions; ++k) {
         int longest = 0;
         std::unique_ptr<RegionWork> r;
-        try { r = makeRegionWork(&regions[k], k, n_samples, longest, check); }
+        try { r = makeRegionWork(&regions[k], k, n_samples, longest, o.sw.checkHints); }
         catch (const std::exception& e) { c->lastError = e.what(); return PLAT_ERR_BAD_INPUT; }          // (a hint that does not describe its table, PLAT_CALLER_CHECK_HINTS=1)
         rlen = nextRlen(rlen, longest, options->maxSize, options->getVariantsFromBAMs);
         r->rlen = rlen;
         work.push_back(std::move(r));
     }
     std::atomic<bool> failed(false);
-    MemoryFeed feed(work, c->regionsPerChunk, (int)c->slots.size(), failed);
+    MemoryFeed feed(work, c->regionsPerChunk, (int)c->slots.size(), o.sw, failed);
     rc = runWorkers(c, feed, failed, o, n_samples, sample_names, st, std::max(1, feed.nChunks));
     if (rc != PLAT_OK) return rc;
     if ((rc = finishText(c, work, out_text, out_len)) != PLAT_OK) return rc;
     options->rlen = rlen;
     st.seconds_total = secs(t0, Clock::now());
-    traceStages(st);
+    traceStages(st, o.sw);
     if (stats) *stats = st;
     return PLAT_OK;
 }
@@ -486,10 +481,9 @@ CALLER_EXPORT int plat_call_regions_stream(plat_caller* c, int n_regions, int n_
     plat_caller_stats st;
     memset(&st, 0, sizeof st);
     st.n_regions = n_regions;
-    Options o;
-    static_cast<plat_caller_options&>(o) = *options;
+    const Options o{*options, Switches::read()};                           // (the PLAT_CALLER_* switches as they are now: switches.hpp)
     std::atomic<bool> failed(false);
-    StreamFeed feed(n_regions, n_samples, per, nWorkers, options->maxSize, options->rlen, load, user, n_slots, failed);
+    StreamFeed feed(n_regions, n_samples, per, nWorkers, options->maxSize, options->rlen, load, user, n_slots, o.sw, failed);
     feed.fromBams = options->getVariantsFromBAMs;
     std::vector<std::thread> loaders;
     for (int i = 0; i < std::min(n_loader_threads, std::max(1, n_regions)); ++i) loaders.emplace_back([&feed] { feed.loader(); });
@@ -504,8 +498,8 @@ CALLER_EXPORT int plat_call_regions_stream(plat_caller* c, int n_regions, int n_
     options->rlen = feed.rlen;
     st.seconds_total = secs(t0, Clock::now());
     st.seconds_load = feed.tLoad; st.seconds_source_wait = feed.tWait;
-    if (getenv("PLAT_CALLER_TRACE")) fprintf(stderr, "[plat_caller] call: workers done after %.2f ms, text put together after %.2f ms\n", 1e3 * tWorkers, 1e3 * st.seconds_total);
-    traceStages(st);
+    if (o.sw.trace) fprintf(stderr, "[plat_caller] call: workers done after %.2f ms, text put together after %.2f ms\n", 1e3 * tWorkers, 1e3 * st.seconds_total);
+    traceStages(st, o.sw);
     if (stats) *stats = st;
     return PLAT_OK;
 }

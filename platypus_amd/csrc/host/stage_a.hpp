@@ -13,75 +13,83 @@
 
 namespace plathost {
 
-// -- A: one device table for every read of the chunk; layout: all `reads` of every (region, sample), then all badReads, then all brokenMates
-inline void Chunk::uploadReads() {
-    size_t nReads[3] = {0, 0, 0}, nBytes[3] = {0, 0, 0}, nCig[3] = {0, 0, 0}, nExc = 0;
-    bool anyPacked = false, allPacked = true, excRegular = true;
+struct TableSurvey {                                                        // what one walk over the chunk's tables finds
+    size_t nReads[3] = {0, 0, 0}, N = 0, B = 0, Cg = 0, nExc = 0;          // reads (per kind: reads, badReads, brokenMates; in all), bytes of bases, CIGAR pairs, exceptions
+    bool anyPacked = false, allPacked = true, excRegular = true;           // (excRegular: no exception with a byte other than A, C, G, T, N)
+    bool cols = true;                                                       // every table has its per-read arrays on the device already (plat_concat_read_tables)
+};
+// ... and what filling the table leaves for the first pass: the pieces of packed bytes to expand (in t_pieces), their exceptions; bytes that crossed the link
+struct FilledTable { int nPieces = 0; size_t mostPiece = 0, nExc = 0, inBytes = 0; };
+
+static TableSurvey surveyTables(const std::vector<RegionWork*>& regions) {
+    TableSurvey v;
     for (RegionWork* r : regions)
         for (SampleView& sv : r->samples) {
-            TableView* tv[3] = {&sv.reads, &sv.bad, &sv.broken};
+            const TableView* tv[3] = {&sv.reads, &sv.bad, &sv.broken};
             for (int k = 0; k < 3; ++k) {
                 const plat_read_table& t = *tv[k]->t;
-                nReads[k] += (size_t)t.n_reads;
-                nBytes[k] += (size_t)t.off[t.n_reads];
-                nCig[k] += (size_t)t.cig_off[t.n_reads];
+                v.nReads[k] += (size_t)t.n_reads; v.N += (size_t)t.n_reads; v.B += (size_t)t.off[t.n_reads]; v.Cg += (size_t)t.cig_off[t.n_reads];
                 if (t.encoding == PLAT_READS_PACKED) {
-                    anyPacked = true; nExc += (size_t)std::max<int64_t>(t.n_exceptions, 0);
-                    for (int64_t e = 0; e < t.n_exceptions; ++e) {
-                        const uint8_t eb = t.exc_base[e];
-                        excRegular = excRegular && (eb == 'A' || eb == 'C' || eb == 'G' || eb == 'T' || eb == 'N');
-                    }
+                    v.anyPacked = true; v.nExc += (size_t)std::max<int64_t>(t.n_exceptions, 0);
+                    for (int64_t e = 0; e < t.n_exceptions && v.excRegular; ++e) v.excRegular = memchr("ACGTN", t.exc_base[e], 5) != nullptr;
                 }
                 else if (t.encoding != PLAT_READS_ASCII) throw DeviceError(PLAT_ERR_INVALID, "plat_read_table.encoding");
-                else if (t.n_reads) allPacked = false;
+                else if (t.n_reads) v.allPacked = false;
+                if (t.n_reads && !(t.dev_off && t.dev_pos && t.dev_end && t.dev_mapq && t.dev_flags && t.dev_cigar && t.dev_cig_off && t.dev_seq)) v.cols = false;
             }
         }
-    // (tables lie back to back in the chunk blob: read i's bytes are [t_off[i], t_off[i + 1]) for every consumer.  A packed table that is
-    //  resident on the device is expanded straight from there; plat_unpack_reads reads a source of another misalignment with unaligned loads)
-    const size_t N = nReads[0] + nReads[1] + nReads[2], B = nBytes[0] + nBytes[1] + nBytes[2], Cg = nCig[0] + nCig[1] + nCig[2];
-    if (N > 0x7FFFFFF0ull) throw DeviceError(PLAT_ERR_OVERFLOW, "chunk read table");
-    Slot& z = s;
-    // Every read out of a packed table and no exception with a byte other than A, C, G, T, N (the promise the scan on codes asks for): the chunk is not
-    // expanded at all.  The first pass writes the 2-bit codes only; the scan, the read statistics and the gathers take a read's letters and qualities from
-    // its packed bytes where they lie (t_src); t_seq keeps its place but holds only the read-side alleles the scan leaves at its records' offsets, and
-    // there is no t_qual.  PLAT_CALLER_EXPAND (measurements / tests) or a device library without the entry points: today's full expansion.
-    static const bool noCodes = getenv("PLAT_CALLER_NO_CODES") != nullptr;         // (measurements / tests: the byte scan)
-    static const bool expandAll = getenv("PLAT_CALLER_EXPAND") != nullptr;
+    if (v.N > 0x7FFFFFF0ull) throw DeviceError(PLAT_ERR_OVERFLOW, "chunk read table");
+    return v;
+}
+
+// Every read out of a packed table and no exception with a byte other than A, C, G, T, N (the promise the scan on codes asks for): the first pass writes
+// the bases' 2-bit codes next to the expanded bytes (Codes) -- or the codes ALONE (Packed): the chunk is not expanded at all; the scan, the read statistics
+// and the gathers take a read's letters and qualities from its packed bytes where they lie (t_src); t_seq keeps its place but holds only the read-side alleles
+// the scan leaves at its records' offsets, and there is no t_qual.  PLAT_CALLER_EXPAND or a device library without the entry points: Codes (which firstPass()
+// takes back to Bytes when the device library has no scan on codes either); PLAT_CALLER_NO_CODES: Bytes.
+static ReadPath planReadPath(const TableSurvey& v, const Switches& sw) {
+    if (!(v.anyPacked && v.allPacked && v.excRegular && v.B > 0) || sw.noCodes) return ReadPath::Bytes;
     const bool haveDirect = plat_concat_read_tables_src && plat_pack_codes_pieces && plat_candidates_batch_packed && plat_gather_reads_packed &&
                             plat_variant_read_stats_packed_batch;
-    packedDirect = anyPacked && allPacked && excRegular && B > 0 && !noCodes && !expandAll && haveDirect;
-    z.packedDirect = packedDirect;
+    return haveDirect && !sw.expand ? ReadPath::Packed : ReadPath::Codes;
+}
+
+// one table's entry of plat_concat_read_tables[_src]: its per-read arrays on the device and where it goes in the chunk table
+template <class D> static D& describeTable(D& d, const plat_read_table& t, int scan, size_t ri, size_t bo, size_t co) {
+    d.off = t.dev_off; d.pos = t.dev_pos; d.end = t.dev_end; d.mapq = t.dev_mapq; d.flags = t.dev_flags; d.cigar = t.dev_cigar; d.cig_off = t.dev_cig_off;
+    d.n = t.n_reads; d.scan = scan; d.first_read = (int64_t)ri; d.first_byte = (int64_t)bo; d.first_pair = (int64_t)co;
+    return d;
+}
+
+// (tables lie back to back in the chunk blob: read i's bytes are [t_off[i], t_off[i + 1]) for every consumer.  A packed table that is
+//  resident on the device is expanded straight from there; plat_unpack_reads reads a source of another misalignment with unaligned loads)
+inline FilledTable Chunk::fillTable(const TableSurvey& v) {
+    Slot& z = s;
+    const bool direct = z.path == ReadPath::Packed, cols = v.cols;
+    const size_t N = v.N, B = v.B, Cg = v.Cg;
     z.t_seq.reserve(z.ctx, B + PLAT_BLOB_PAD, false, true, z.stream);
-    if (!packedDirect) z.t_qual.reserve(z.ctx, B + PLAT_BLOB_PAD, false, true, z.stream);
-    if (anyPacked) z.t_pack.reserve(z.ctx, B + PLAT_BLOB_PAD, false, true, z.stream);
-    // every table with its per-read arrays on the device already: the chunk table is put together there (plat_concat_read_tables)
-    bool cols = true;
-    for (RegionWork* r : regions)
-        for (SampleView& sv : r->samples)
-            for (const TableView* tv : {&sv.reads, &sv.bad, &sv.broken}) {
-                const plat_read_table& t = *tv->t;
-                if (t.n_reads && !(t.dev_off && t.dev_pos && t.dev_end && t.dev_mapq && t.dev_flags && t.dev_cigar && t.dev_cig_off && t.dev_seq)) cols = false;
-            }
+    if (!direct) z.t_qual.reserve(z.ctx, B + PLAT_BLOB_PAD, false, true, z.stream);
+    if (v.anyPacked) z.t_pack.reserve(z.ctx, B + PLAT_BLOB_PAD, false, true, z.stream);
     Layout L;
-    L.add(z.t_excidx, nExc + 1); L.add(z.t_excb, nExc + 1); L.add(z.t_excq, nExc + 1);
+    L.add(z.t_excidx, v.nExc + 1); L.add(z.t_excb, v.nExc + 1); L.add(z.t_excq, v.nExc + 1);
     L.add(z.t_off, N + 1); L.add(z.t_pos, N + 1); L.add(z.t_end, N + 1); L.add(z.t_flags, N + 1); L.add(z.t_mapq, N + 1); L.add(z.t_cigoff, N + 1);
-    L.add(z.t_cigar, 2 * Cg + 2); L.add(z.t_region, nReads[0] + 1);
-    if (packedDirect) L.add(z.t_src, N + 1);
+    L.add(z.t_cigar, 2 * Cg + 2); L.add(z.t_region, v.nReads[0] + 1);
+    if (direct) L.add(z.t_src, N + 1);
     L.commit(z, z.a_tab);
     Layout LD;
     size_t nDesc = 0;
-    int mostPerTable = 0;
+    int mostPerTable = 0;                                               // (tables described to plat_concat_read_tables; most reads in one)
     const size_t nTables = 3 * regions.size() * (regions.empty() ? 0 : regions[0]->samples.size());
     LD.add(z.t_pieces, nTables + 1);
-    if (cols && packedDirect) LD.add(z.t_sdesc, nTables + 1);
+    if (cols && direct) LD.add(z.t_sdesc, nTables + 1);
     else if (cols) LD.add(z.t_desc, nTables + 1);
     LD.commit(z, z.a_desc);
-    struct Pending { size_t bo, nb, e0, ne; const uint8_t* dev; };       // dev: expand from this device address instead of t_pack + bo
-    std::vector<Pending> packed;
-    size_t ri = 0, bo = 0, co = 0, eo = 0, inBytes = 0;
-    int scan = 0;
+    FilledTable f;
+    plat_unpack_piece* pieces = z.t_pieces.h;
+    bool lastInPack = false;                                            // the last piece lies in t_pack (not in a caller's resident table)
+    size_t ri = 0, bo = 0, co = 0;
     for (int k = 0; k < 3; ++k) {
-        scan = 0;
+        int scan = 0;                                                   // (the (region, sample) pair: the scan id of its `reads`)
         for (RegionWork* r : regions)
             for (SampleView& sv : r->samples) {
                 TableView& tv = k == 0 ? sv.reads : (k == 1 ? sv.bad : sv.broken);
@@ -90,111 +98,101 @@ inline void Chunk::uploadReads() {
                 tv.base = (int64_t)ri; tv.blobBase = (int64_t)bo;
                 maxReadLen = std::max(maxReadLen, tv.maxLen);
                 const size_t nb = (size_t)t.off[n], nc = (size_t)t.cig_off[n];
-                if (nb && t.encoding == PLAT_READS_PACKED) {            // one byte per base crosses the link (or none: dev_seq); expanded below
+                // (a packed table's bytes on the device: resident, or its place in t_pack)
+                const uint8_t* tabSrc = t.dev_seq ? t.dev_seq : z.t_pack.d + bo;
+                if (nb && t.encoding == PLAT_READS_PACKED) {            // one byte per base crosses the link (or none: dev_seq); expanded by firstPass()
                     if (!t.dev_seq) ck(plat_memcpy_h2d(z.ctx, z.t_pack.d + bo, t.seq, nb, z.stream), "plat_memcpy_h2d(packed)");
                     const size_t ne = (size_t)std::max<int64_t>(t.n_exceptions, 0);
-                    // every packed table of the chunk is expanded by ONE launch (plat_unpack_reads_pieces): tables that follow each other in
-                    // t_pack join into one piece; exceptions are indexed from the chunk blob's first byte
-                    const bool joins = !t.dev_seq && !packed.empty() && !packed.back().dev && packed.back().bo + packed.back().nb == bo;
-                    for (size_t e = 0; e < ne; ++e) {
-                        z.t_excidx.h[eo + e] = t.exc_index[e] + (int64_t)bo; z.t_excb.h[eo + e] = t.exc_base[e]; z.t_excq.h[eo + e] = t.exc_qual[e];
+                    for (size_t e = 0; e < ne; ++e) {                   // (exceptions are indexed from the chunk blob's first byte)
+                        z.t_excidx.h[f.nExc + e] = t.exc_index[e] + (int64_t)bo; z.t_excb.h[f.nExc + e] = t.exc_base[e]; z.t_excq.h[f.nExc + e] = t.exc_qual[e];
                     }
-                    if (joins) { packed.back().nb += nb; packed.back().ne += ne; }
-                    else packed.push_back(Pending{bo, nb, eo, ne, t.dev_seq});
-                    eo += ne; inBytes += (t.dev_seq ? 0 : nb) + 10 * ne;
+                    // every packed table of the chunk is expanded by ONE launch (plat_unpack_reads_pieces): tables that follow each other in t_pack join into one piece
+                    plat_unpack_piece* last = f.nPieces ? &pieces[f.nPieces - 1] : nullptr;
+                    if (!t.dev_seq && lastInPack && last->dst + last->n == (int64_t)bo) last->n += (int64_t)nb;
+                    else { last = &pieces[f.nPieces++]; *last = plat_unpack_piece{tabSrc, (int64_t)bo, (int64_t)nb}; }
+                    lastInPack = !t.dev_seq;
+                    f.mostPiece = std::max(f.mostPiece, (size_t)last->n); tabPackedBytes += (int64_t)nb;
+                    f.nExc += ne; f.inBytes += (t.dev_seq ? 0 : nb) + 10 * ne;
                 } else if (nb && t.dev_seq && t.dev_qual) {            // resident in HBM already
                     ck(plat_memcpy_d2d(z.ctx, z.t_seq.d + bo, t.dev_seq, nb, z.stream), "plat_memcpy_d2d(seq)");
                     ck(plat_memcpy_d2d(z.ctx, z.t_qual.d + bo, t.dev_qual, nb, z.stream), "plat_memcpy_d2d(qual)");
                 } else if (nb) {                                       // bases and qualities go straight from the caller's memory
                     ck(plat_memcpy_h2d(z.ctx, z.t_seq.d + bo, t.seq, nb, z.stream), "plat_memcpy_h2d(seq)");
                     ck(plat_memcpy_h2d(z.ctx, z.t_qual.d + bo, t.qual, nb, z.stream), "plat_memcpy_h2d(qual)");
-                    inBytes += 2 * nb;
+                    f.inBytes += 2 * nb;
                 }
-                // (packedDirect: where this table's packed bytes lie on the device -- resident, or its place in t_pack)
-                const uint8_t* tabSrc = t.dev_seq ? t.dev_seq : z.t_pack.d + bo;
-                if (cols) {
-                    if (n && packedDirect) {
-                        plat_table_src_desc& d = z.t_sdesc.h[nDesc++];
-                        d.off = t.dev_off; d.pos = t.dev_pos; d.end = t.dev_end; d.mapq = t.dev_mapq; d.flags = t.dev_flags; d.cigar = t.dev_cigar; d.cig_off = t.dev_cig_off;
-                        d.n = n; d.scan = k == 0 ? scan : -1; d.first_read = (int64_t)ri; d.first_byte = (int64_t)bo; d.first_pair = (int64_t)co;
-                        d.src = tabSrc;
-                        mostPerTable = std::max(mostPerTable, n);
-                    } else if (n) {
-                        plat_table_desc& d = z.t_desc.h[nDesc++];
-                        d.off = t.dev_off; d.pos = t.dev_pos; d.end = t.dev_end; d.mapq = t.dev_mapq; d.flags = t.dev_flags; d.cigar = t.dev_cigar; d.cig_off = t.dev_cig_off;
-                        d.n = n; d.scan = k == 0 ? scan : -1; d.first_read = (int64_t)ri; d.first_byte = (int64_t)bo; d.first_pair = (int64_t)co;
-                        mostPerTable = std::max(mostPerTable, n);
+                if (cols && n) {
+                    if (direct) describeTable(z.t_sdesc.h[nDesc++], t, k == 0 ? scan : -1, ri, bo, co).src = tabSrc;
+                    else describeTable(z.t_desc.h[nDesc++], t, k == 0 ? scan : -1, ri, bo, co);
+                    mostPerTable = std::max(mostPerTable, n);
+                } else if (!cols) {
+                    for (int i = 0; i < n; ++i) {
+                        z.t_off.h[ri + i] = (int64_t)bo + t.off[i];
+                        z.t_cigoff.h[ri + i] = (int32_t)(co + (size_t)t.cig_off[i]);
+                        if (direct) z.t_src.h[ri + i] = tabSrc + t.off[i];
                     }
-                    ri += (size_t)n; bo += nb; co += nc;
-                    ++scan;
-                    continue;
-                }
-                for (int i = 0; i < n; ++i) {
-                    z.t_off.h[ri + i] = (int64_t)bo + t.off[i];
-                    z.t_cigoff.h[ri + i] = (int32_t)(co + (size_t)t.cig_off[i]);
-                }
-                if (packedDirect) for (int i = 0; i < n; ++i) z.t_src.h[ri + i] = tabSrc + t.off[i];
-                if (n) {
-                    memcpy(z.t_pos.h + ri, t.pos, sizeof(int32_t) * (size_t)n); memcpy(z.t_end.h + ri, t.end, sizeof(int32_t) * (size_t)n);
-                    memcpy(z.t_flags.h + ri, t.flags, sizeof(int32_t) * (size_t)n); memcpy(z.t_mapq.h + ri, t.mapq, (size_t)n);
-                    if (nc) memcpy(z.t_cigar.h + 2 * co, t.cigar, sizeof(int16_t) * 2 * nc);
-                    if (k == 0) for (int i = 0; i < n; ++i) z.t_region.h[ri + i] = scan;
+                    if (n) {
+                        memcpy(z.t_pos.h + ri, t.pos, sizeof(int32_t) * (size_t)n); memcpy(z.t_end.h + ri, t.end, sizeof(int32_t) * (size_t)n);
+                        memcpy(z.t_flags.h + ri, t.flags, sizeof(int32_t) * (size_t)n); memcpy(z.t_mapq.h + ri, t.mapq, (size_t)n);
+                        if (nc) memcpy(z.t_cigar.h + 2 * co, t.cigar, sizeof(int16_t) * 2 * nc);
+                        if (k == 0) for (int i = 0; i < n; ++i) z.t_region.h[ri + i] = scan;
+                    }
                 }
                 ri += (size_t)n; bo += nb; co += nc;
                 ++scan;
             }
+        nScan = scan;
     }
     if (cols) {
         L.uploadFirst(z, z.a_tab, 3);                                   // (the exceptions of packed tables; the per-read arrays are made on the device)
-        if (nDesc && packedDirect) {
-            LD.upload(z, z.a_desc);
+        if (nDesc) LD.upload(z, z.a_desc);
+        if (nDesc && direct)
             ck(plat_concat_read_tables_src(z.ctx, (int)nDesc, mostPerTable, z.t_sdesc.d, z.t_off.d, z.t_pos.d, z.t_end.d, z.t_mapq.d, z.t_flags.d, z.t_cigoff.d, z.t_cigar.d,
-                                           z.t_region.d, z.t_src.d, (int64_t)N, (int64_t)bo, (int64_t)Cg, z.stream), "plat_concat_read_tables_src");
-        } else if (nDesc) {
-            LD.upload(z, z.a_desc);
+                                           z.t_region.d, z.t_src.d, (int64_t)N, (int64_t)B, (int64_t)Cg, z.stream), "plat_concat_read_tables_src");
+        else if (nDesc)
             ck(plat_concat_read_tables(z.ctx, (int)nDesc, mostPerTable, z.t_desc.d, z.t_off.d, z.t_pos.d, z.t_end.d, z.t_mapq.d, z.t_flags.d, z.t_cigoff.d, z.t_cigar.d,
-                                       z.t_region.d, (int64_t)N, (int64_t)bo, (int64_t)Cg, z.stream), "plat_concat_read_tables");
-        }
+                                       z.t_region.d, (int64_t)N, (int64_t)B, (int64_t)Cg, z.stream), "plat_concat_read_tables");
     }
     if (!cols || !nDesc) {
-        z.t_off.h[N] = (int64_t)bo; z.t_cigoff.h[N] = (int32_t)Cg;
+        z.t_off.h[N] = (int64_t)B; z.t_cigoff.h[N] = (int32_t)Cg;
         z.t_cigar.h[2 * Cg] = 0; z.t_cigar.h[2 * Cg + 1] = 0;
         L.upload(z, z.a_tab);
     }
-    if (!packed.empty()) {
-        size_t most = 0;
-        for (size_t q = 0; q < packed.size(); ++q) {
-            const Pending& p = packed[q];
-            z.t_pieces.h[q] = plat_unpack_piece{p.dev ? p.dev : z.t_pack.d + p.bo, (int64_t)p.bo, (int64_t)p.nb};
-            most = std::max(most, p.nb);
-        }
-        ck(plat_memcpy_h2d(z.ctx, z.t_pieces.d, z.t_pieces.h, packed.size() * sizeof(plat_unpack_piece), z.stream), "plat_memcpy_h2d(pieces)");
-        // the bases' 2-bit codes next to the bytes when every read of the chunk comes out of a packed table and no exception carries a byte other than
-        // A, C, G, T, N (the promise plat_candidates_batch_codes asks for); a device library without the entry point: the byte scan
-        int rcu = PLAT_ERR_UNSUPPORTED;
-        if (packedDirect) {                                             // the codes alone: the bytes stay where they are
-            z.t_codes.reserve(z.ctx, (bo + 15) / 16 + 16, false);
-            ck(plat_pack_codes_pieces(z.ctx, (int)packed.size(), (int64_t)most, z.t_pieces.d, z.t_codes.d, (int64_t)bo, (int64_t)eo, z.t_excidx.d, z.t_excb.d, z.stream),
-               "plat_pack_codes_pieces");
-            rcu = PLAT_OK;
-        } else if (allPacked && excRegular && !noCodes) {
-            z.t_codes.reserve(z.ctx, (bo + 15) / 16 + 16, false);
-            rcu = plat_unpack_reads_pieces_codes(z.ctx, (int)packed.size(), (int64_t)most, z.t_pieces.d, z.t_seq.d, z.t_qual.d, z.t_codes.d, (int64_t)bo, (int64_t)eo,
-                                                 z.t_excidx.d, z.t_excb.d, z.t_excq.d, z.stream);
-            if (rcu != PLAT_ERR_UNSUPPORTED) ck(rcu, "plat_unpack_reads_pieces_codes");
-        }
-        readCodes = rcu == PLAT_OK;
-        z.pk = plat_packed_reads{packedDirect ? z.t_src.d : nullptr, (int64_t)eo, z.t_excidx.d, z.t_excb.d, z.t_excq.d};
-        if (!readCodes)
-            ck(plat_unpack_reads_pieces(z.ctx, (int)packed.size(), (int64_t)most, z.t_pieces.d, z.t_seq.d, z.t_qual.d, (int64_t)bo, (int64_t)eo, z.t_excidx.d, z.t_excb.d,
-                                        z.t_excq.d, z.stream), "plat_unpack_reads_pieces");
-        for (const Pending& p : packed) tabPackedBytes += (int64_t)p.nb;
+    return f;
+}
+
+// the first pass over the packed bytes: ONE launch for every piece -- the codes alone (Packed), bytes + codes (Codes), or the bytes (Bytes)
+inline void Chunk::firstPass(const TableSurvey& v, const FilledTable& f) {
+    if (!f.nPieces) return;
+    Slot& z = s;
+    const int64_t B = (int64_t)v.B, nE = (int64_t)f.nExc, most = (int64_t)f.mostPiece;
+    ck(plat_memcpy_h2d(z.ctx, z.t_pieces.d, z.t_pieces.h, (size_t)f.nPieces * sizeof(plat_unpack_piece), z.stream), "plat_memcpy_h2d(pieces)");
+    if (z.path != ReadPath::Bytes) z.t_codes.reserve(z.ctx, ((size_t)B + 15) / 16 + 16, false);
+    if (z.path == ReadPath::Packed)                                     // the codes alone: the bytes stay where they are
+        ck(plat_pack_codes_pieces(z.ctx, f.nPieces, most, z.t_pieces.d, z.t_codes.d, B, nE, z.t_excidx.d, z.t_excb.d, z.stream), "plat_pack_codes_pieces");
+    else if (z.path == ReadPath::Codes) {
+        const int rcu = plat_unpack_reads_pieces_codes(z.ctx, f.nPieces, most, z.t_pieces.d, z.t_seq.d, z.t_qual.d, z.t_codes.d, B, nE, z.t_excidx.d, z.t_excb.d,
+                                                       z.t_excq.d, z.stream);
+        if (rcu == PLAT_ERR_UNSUPPORTED) z.path = ReadPath::Bytes;      // a device library without the entry point: the chunk ends on the byte path
+        else ck(rcu, "plat_unpack_reads_pieces_codes");
     }
-    tabBlobBytes = (int64_t)bo;
-    nGood = nReads[0]; nScan = scan; nBad = nReads[1]; nBroken = nReads[2];
+    z.pk = plat_packed_reads{z.path == ReadPath::Packed ? z.t_src.d : nullptr, nE, z.t_excidx.d, z.t_excb.d, z.t_excq.d};
+    if (z.path == ReadPath::Bytes)
+        ck(plat_unpack_reads_pieces(z.ctx, f.nPieces, most, z.t_pieces.d, z.t_seq.d, z.t_qual.d, B, nE, z.t_excidx.d, z.t_excb.d, z.t_excq.d, z.stream),
+           "plat_unpack_reads_pieces");
+}
+
+// -- A: one device table for every read of the chunk; layout: all `reads` of every (region, sample), then all badReads, then all brokenMates
+inline void Chunk::uploadReads() {
+    const TableSurvey v = surveyTables(regions);
+    s.path = planReadPath(v, o.sw);
+    const FilledTable f = fillTable(v);
+    firstPass(v, f);
+    tabBlobBytes = (int64_t)v.B;
+    nGood = v.nReads[0]; nBad = v.nReads[1]; nBroken = v.nReads[2];
     std::lock_guard<std::mutex> g(stMutex);
-    st.n_reads += (int64_t)N;
-    st.input_bytes += (int64_t)inBytes;
+    st.n_reads += (int64_t)v.N;
+    st.input_bytes += (int64_t)f.inBytes;
 }
 
 // -- A2: VariantCandidateGenerator.addCandidatesFromReads over the `reads` of every (region, sample) (variant.pyx:459-751)
@@ -252,7 +250,7 @@ inline void Chunk::scanCandidates() {
     cb.ref_seq = refDev; cb.ref_off = z.c_refoff.d; cb.ref_seq_start = z.c_rss.d; cb.contig_len = z.c_clen.d;
     cb.read_seq = z.t_seq.d; cb.read_qual = z.t_qual.d; cb.read_off = z.t_off.d; cb.read_pos = z.t_pos.d; cb.read_flags = z.t_flags.d;
     cb.cigar = z.t_cigar.d; cb.cig_off = z.t_cigoff.d;
-    hostTally = getenv("PLAT_CALLER_HOST_TALLY") != nullptr;         // (measurements / tests: merge the records on the host)
+    hostTally = o.sw.hostTally;                                         // (measurements / tests: merge the records on the host)
     for (;;) {
         // records stay on the device when the merge kernel can take them: c_cnt / c_status / c_rec are laid out for a download
         // all the same (the host tally needs them when a scan overflows the kernel's table)
@@ -260,21 +258,27 @@ inline void Chunk::scanCandidates() {
         LO.add(z.c_cnt, nGood); LO.add(z.c_status, nGood); LO.add(z.c_rec, nGood * (size_t)maxPerRead * 5);
         LO.commit(z, z.a_cout);
         recArenaBytes = LO.total; recordsOnHost = false;
-        int rcs = PLAT_ERR_UNSUPPORTED;
-        if (readCodes) {                                                // the scan on 2-bit codes: the reference blob's codes first (a few MB per chunk)
+        int rcs = PLAT_ERR_UNSUPPORTED;                                 // (PLAT_OK: a scan on codes has run)
+        if (z.path != ReadPath::Bytes) {                                // the scan on 2-bit codes: the reference blob's codes first (a few MB per chunk)
             z.c_refcodes.reserve(z.ctx, (blobLen + 15) / 16 + 16, false); z.c_refirr.reserve(z.ctx, (size_t)nScan + 1, false);
             rcs = plat_ref_codes(z.ctx, nScan, refDev, z.c_refoff.d, (int64_t)blobLen, z.c_refcodes.d, z.c_refirr.d, z.stream);
-            if (packedDirect) {                                         // (letters and qualities from the packed bytes; leaves its records' alleles in t_seq)
-                ck(rcs, "plat_ref_codes");                              // (no expanded bytes to fall back to)
-                cb.read_qual = nullptr;
-                ck(plat_candidates_batch_packed(z.ctx, &cb, &z.pk, z.t_codes.d, z.c_refcodes.d, z.c_refirr.d, o.minFlank, o.minBaseQual, o.genSNPs, o.genIndels, maxPerRead,
-                                                z.t_region.d, z.c_rec.d, z.c_cnt.d, z.c_status.d, z.stream), "plat_candidates_batch_packed");
-            } else if (rcs == PLAT_OK)
+        }
+        switch (z.path) {
+        case ReadPath::Packed:                                          // letters and qualities from the packed bytes; leaves its records' alleles in t_seq
+            ck(rcs, "plat_ref_codes");                                  // (no expanded bytes to fall back to)
+            cb.read_qual = nullptr;
+            ck(plat_candidates_batch_packed(z.ctx, &cb, &z.pk, z.t_codes.d, z.c_refcodes.d, z.c_refirr.d, o.minFlank, o.minBaseQual, o.genSNPs, o.genIndels, maxPerRead,
+                                            z.t_region.d, z.c_rec.d, z.c_cnt.d, z.c_status.d, z.stream), "plat_candidates_batch_packed");
+            break;
+        case ReadPath::Codes:                                           // (a device library without either entry point: the byte scan below)
+            if (rcs == PLAT_OK)
                 rcs = plat_candidates_batch_codes(z.ctx, &cb, z.t_codes.d, z.c_refcodes.d, z.c_refirr.d, o.minFlank, o.minBaseQual, o.genSNPs, o.genIndels, maxPerRead,
                                                   z.t_region.d, z.c_rec.d, z.c_cnt.d, z.c_status.d, z.stream);
             if (rcs != PLAT_ERR_UNSUPPORTED) ck(rcs, "plat_candidates_batch_codes");
+            break;
+        case ReadPath::Bytes: break;
         }
-        if (rcs != PLAT_OK)
+        if (rcs != PLAT_OK)                                             // the byte scan
             ck(plat_candidates_batch(z.ctx, &cb, o.minFlank, o.minBaseQual, o.genSNPs, o.genIndels, maxPerRead, z.t_region.d, z.c_rec.d, z.c_cnt.d,
                                      z.c_status.d, z.stream), "plat_candidates_batch");
         int need = 0;
@@ -403,11 +407,7 @@ inline void Chunk::assembleLaunch() {
         const size_t nR = src.size(), nb = (size_t)roff.back();
         z.as_seq.reserve(z.ctx, nb + PLAT_BLOB_PAD, false, true, z.stream); z.as_qual.reserve(z.ctx, nb + PLAT_BLOB_PAD, false, true, z.stream);
         z.as_pos.reserve(z.ctx, nR + 1, false); z.as_end.reserve(z.ctx, nR + 1, false); z.as_flags.reserve(z.ctx, nR + 1, false); z.as_mapq.reserve(z.ctx, nR + 1, false);
-        if (nR && packedDirect)
-            ck(plat_gather_reads_packed(z.ctx, (int64_t)nR, z.as_src.d, z.as_roff.d, &z.pk, z.t_off.d, z.t_pos.d, z.t_end.d, z.t_mapq.d, z.t_flags.d, z.as_seq.d, z.as_qual.d,
-                                        z.as_pos.d, z.as_end.d, z.as_mapq.d, z.as_flags.d, z.stream), "plat_gather_reads_packed(assembler)");
-        else if (nR) ck(plat_gather_reads(z.ctx, (int64_t)nR, z.as_src.d, z.as_roff.d, z.t_seq.d, z.t_qual.d, z.t_off.d, z.t_pos.d, z.t_end.d, z.t_mapq.d, z.t_flags.d,
-                                     z.as_seq.d, z.as_qual.d, z.as_pos.d, z.as_end.d, z.as_mapq.d, z.as_flags.d, z.stream), "plat_gather_reads(assembler)");
+        if (nR) z.gatherReads((int64_t)nR, z.as_src.d, z.as_roff.d, z.as_seq.d, z.as_qual.d, z.as_pos.d, z.as_end.d, z.as_mapq.d, z.as_flags.d, "plat_gather_reads(assembler)");
         plat_assembly_batch& ab = asmBatch;
         memset(&ab, 0, sizeof ab);
         ab.n_regions = nT; ab.n_reads = (int32_t)nR;

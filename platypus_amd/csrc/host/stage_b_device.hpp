@@ -7,8 +7,7 @@ namespace plathost {
 
 inline bool Chunk::eligibleDeviceB() const {
     if (nInd != 1 || o.assemble || o.outputRefCalls || !o.getVariantsFromBAMs || o.maxHaplotypes < 3 || regions.empty()) return false;
-    const char* e = getenv("PLAT_CALLER_HOST_B");                       // (measurements / tests: stage B on the host)
-    return !(e && e[0] == '1');
+    return !o.sw.hostB;                                                 // (measurements / tests: stage B on the host)
 }
 
 inline void Chunk::launchStageB() {
@@ -56,7 +55,7 @@ inline void Chunk::launchStageB() {
     plat_stage_b_in in;
     memset(&in, 0, sizeof in);
     in.n_regions = (int32_t)nR; in.cap_per_scan = mergeCap; in.cand = z.m_cand.d; in.cand_n = z.m_n.d;
-    in.cand_rec = getenv("PLAT_CALLER_NO_DEVICE_REPLAY") ? nullptr : z.c_rec.d; in.region_name_hash = z.sb_namehash.d;
+    in.cand_rec = o.sw.noDeviceReplay ? nullptr : z.c_rec.d; in.region_name_hash = z.sb_namehash.d;
     in.ref_seq = refDev; in.ref_off = z.c_refoff.d; in.ref_seq_start = z.c_rss.d; in.contig_len = z.c_clen.d;
     in.region_start = z.sb_rstart.d; in.region_end = z.sb_rend.d; in.region_rlen = z.sb_rlen.d;
     in.read_seq = z.t_seq.d; in.read_off = z.t_off.d; in.read_pos = z.t_pos.d; in.read_end = z.t_end.d;

@@ -141,8 +141,8 @@ inline void Chunk::regionVariants(RegionWork& r, int scan0) {
         }
         a = e;
     }
-    if (replay && o.getVariantsFromBAMs && !getenv("PLAT_CALLER_FIRST_OCCURRENCE_ORDER")) {      // (the switch: tests only, to show the replay matters)
-        if (getenv("PLAT_CALLER_TRACE")) fprintf(stderr, "[plat_caller] region %s: candidates that compare equal are kept, dictionaries replayed\n", r.in->chrom ? r.in->chrom : "?");
+    if (replay && o.getVariantsFromBAMs && !o.sw.firstOccurrenceOrder) {      // (the switch: tests only, to show the replay matters)
+        if (o.sw.trace) fprintf(stderr, "[plat_caller] region %s: candidates that compare equal are kept, dictionaries replayed\n", r.in->chrom ? r.in->chrom : "?");
         PROF("s2.rv.replay");
         if (!hostTally && !recordsOnHost) {                             // the scan's records are still on the device: this region's reads' rows
             PROF("s2.rv.replay.d2h");

@@ -207,7 +207,7 @@ inline void Chunk::callWindows(std::vector<WindowWork*>& wins, bool fromDevice) 
     ib.good_begin = z.s_gb.d; ib.good_end = z.s_ge.d; ib.bad_begin = z.s_bb.d; ib.bad_end = z.s_be.d;
     ib.read_seq = z.t_seq.d; ib.read_qual = z.t_qual.d; ib.read_off = z.t_off.d; ib.read_pos = z.t_pos.d; ib.read_end = z.t_end.d; ib.read_mapq = z.t_mapq.d;
     ib.read_flags = z.t_flags.d; ib.cigar = z.t_cigar.d; ib.cig_off = z.t_cigoff.d;
-    if (z.packedDirect) {
+    if (z.path == ReadPath::Packed) {
         ib.read_seq = nullptr; ib.read_qual = nullptr;
         ck(plat_variant_read_stats_packed_batch(z.ctx, &ib, &z.pk, o.badReadsWindow, o.countOnlyExactIndelMatches, z.s_counts.d, z.s_ps.d, z.s_minq.d, z.s_nminq.d,
                                                 z.stream), "plat_variant_read_stats_packed_batch");
@@ -215,8 +215,7 @@ inline void Chunk::callWindows(std::vector<WindowWork*>& wins, bool fromDevice) 
     ck(plat_variant_read_stats_batch(z.ctx, &ib, o.badReadsWindow, o.countOnlyExactIndelMatches, z.s_counts.d, z.s_ps.d, z.s_minq.d, z.s_nminq.d, z.stream),
        "plat_variant_read_stats_batch");
     {   // the loops of ABPV / SbPval / MMLQ behind it, on the device (the host keeps the libm calls; a device library without it: the host's loops)
-        static const bool hostInfo = getenv("PLAT_CALLER_HOST_INFO") != nullptr;
-        const int rci = hostInfo ? PLAT_ERR_UNSUPPORTED
+        const int rci = o.sw.hostInfo ? PLAT_ERR_UNSUPPORTED
                                  : plat_variant_info_batch(z.ctx, (int)nSV, z.s_counts.d, z.s_moff.d, z.s_minq.d, z.s_nminq.d, z.s_terms.d, z.s_mmlq.d, z.stream);
         if (rci != PLAT_ERR_UNSUPPORTED) ck(rci, "plat_variant_info_batch");
         z.infoOnDevice = rci == PLAT_OK;

@@ -1,0 +1,51 @@
+// switches.hpp -- the PLAT_CALLER_* environment switches of the native region loop (libplat_caller.so), read ONCE PER CALL:
+// plat_call_regions and plat_call_regions_stream call Switches::read() at entry (the fetched / BAM / BGZF front ends end in plat_call_regions
+// and read nothing themselves) and the result travels in Options.  A variable set or cleared between two calls takes effect at the next call;
+// inside one call nothing changes.  None of them changes the record text (FIRST_OCCURRENCE_ORDER excepted: that is what it is there to show).
+//
+//   variable (PLAT_CALLER_...)   on when            what it does                                                          who sets it
+//   NO_CODES                     set at all         the candidate scan on bytes: no 2-bit codes, the chunk is expanded    tests, measurements
+//   EXPAND                       set at all         packed chunks are expanded (bytes + codes), not read where they lie   tests, measurements (the A/B baseline)
+//   HOST_TALLY                   set at all         the scan's records are merged on the host, stage B runs there         tests, measurements
+//   HOST_B                       begins with '1'    stage B on the host although the chunk is eligible for the device     tests, measurements
+//   NO_DEVICE_REPLAY             set at all         device stage B gets no records to replay the dictionaries from        tests (the replay matters)
+//   HOST_INFO                    set at all         the ABPV / SbPval / MMLQ loops on the host                            measurements
+//   FIRST_OCCURRENCE_ORDER       set at all         host stage B never replays the dictionaries                           tests (the replay matters)
+//   EVEN_TAIL                    not beginning '0'  the last round of chunks is cut into equal parts, one per worker      measurements ("0": whole chunks to the end)
+//   KEEP_SPARE                   begins with '1'    a worker keeps its spare window storage for the next call             measurements (slower: region_caller.cpp)
+//   CHECK_HINTS                  begins with '1'    plat_read_table.longest_read / most_bases are checked against a walk  tests, a loader under suspicion
+//   TRACE                        set at all         per-chunk / per-call lines on stderr;                                 measurements
+//                                begins with '1'    ... and the per-stage seconds of every call (traceStages)
+// PLAT_CALLER_POLL_US is not here: it is a property of the caller object and is read where that is made (plat_caller_create).
+#pragma once
+#include <cstdlib>
+#include <cstring>
+
+namespace plathost {
+
+struct Switches {
+    bool noCodes = false, expand = false, hostTally = false, hostB = false, noDeviceReplay = false, hostInfo = false, firstOccurrenceOrder = false;
+    bool evenTail = true, keepSpare = false, checkHints = false;
+    bool trace = false, traceStages = false;                              // PLAT_CALLER_TRACE: set at all / begins with '1'
+
+    static Switches read() {
+        auto isSet = [](const char* name) { return getenv(name) != nullptr; };
+        auto isOne = [](const char* name) { const char* e = getenv(name); return e && e[0] == '1'; };
+        Switches w;
+        w.noCodes = isSet("PLAT_CALLER_NO_CODES");
+        w.expand = isSet("PLAT_CALLER_EXPAND");
+        w.hostTally = isSet("PLAT_CALLER_HOST_TALLY");
+        w.hostB = isOne("PLAT_CALLER_HOST_B");
+        w.noDeviceReplay = isSet("PLAT_CALLER_NO_DEVICE_REPLAY");
+        w.hostInfo = isSet("PLAT_CALLER_HOST_INFO");
+        w.firstOccurrenceOrder = isSet("PLAT_CALLER_FIRST_OCCURRENCE_ORDER");
+        { const char* e = getenv("PLAT_CALLER_EVEN_TAIL"); w.evenTail = !(e && e[0] == '0'); }
+        w.keepSpare = isOne("PLAT_CALLER_KEEP_SPARE");
+        w.checkHints = isOne("PLAT_CALLER_CHECK_HINTS");
+        w.trace = isSet("PLAT_CALLER_TRACE");
+        w.traceStages = isOne("PLAT_CALLER_TRACE");
+        return w;
+    }
+};
+
+}  // namespace plathost

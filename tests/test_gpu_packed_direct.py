@@ -1,11 +1,9 @@
 """Packed bases read where they lie: the entry points that take a chunk's reads as PLAT_READS_PACKED bytes at their source, each against its
 counterpart on the expanded (ASCII) table -- plat_pack_codes_pieces / plat_unpack_reads_pieces_codes, plat_gather_reads_packed / plat_gather_reads,
 plat_candidates_batch_packed / plat_candidates_batch_codes, plat_variant_read_stats_packed_batch / plat_variant_read_stats_batch -- and the
-native region loop with and without PLAT_CALLER_EXPAND=1 (today's full expansion).  Integer / byte work: everything is compared exactly."""
-import json
+native region loop on its three read paths: the default, PLAT_CALLER_EXPAND=1 (the full expansion) and PLAT_CALLER_NO_CODES=1 (the byte scan).
+Integer / byte work: everything is compared exactly."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -308,12 +306,28 @@ def test_packed_read_statistics_equal_the_expanded_table_s(eng, scan_regions):
 
 
 # ---- the region loop -----------------------------------------------------------------------------------------------------------------------
-def _region_cases():
+SWITCHES = ("PLAT_CALLER_EXPAND", "PLAT_CALLER_NO_CODES")
+
+
+def _region_cases(inputs, switch=None):
     """The four region-loop cases: {name: [record text, region text lengths, counters]} -- and, from a counting pass over the first, the
-    algorithmic bytes of the first pass (1 1/4 per base when the bases are read where they lie, 3 1/4 when the table is expanded)."""
-    import torch
-    from platypus_amd import fastcaller as F, hostapi as H, synth
-    from platypus_amd.options import default_options
+    algorithmic bytes of the first pass (1 1/4 per base when the bases are read where they lie, 3 1/4 when the table is expanded, 3 without
+    the codes) -- with `switch` (one of SWITCHES, or None) set to 1 in the environment and the other unset, as tests/test_gpu_stage_b.py sets its own."""
+    old = {k: os.environ.pop(k, None) for k in SWITCHES}
+    if switch:
+        os.environ[switch] = "1"
+    try:
+        return _region_cases_here(*inputs)
+    finally:
+        for k, v in old.items():
+            os.environ.pop(k, None)
+            if v is not None:
+                os.environ[k] = v
+
+
+def _region_inputs():
+    """(fasta, [(chrom, start, end, [bamReadBuffer])]) of the region-loop cases."""
+    from platypus_amd import hostapi as H, synth
     rng = np.random.default_rng(2105)
     regs = [synth.config4_region(2100 + i, n_samples=1, region_len=2500, snp_rate=8e-3, indel_rate=3e-3, read_len=100, depth=24) for i in range(3)]
     fasta = H.FastaFile({r["chrom"]: r["ref"] for r in regs})
@@ -337,6 +351,13 @@ def _region_cases():
                 good.append(a)
         broken.sort(key=lambda q: q.matePos)
         work.append((r["chrom"], r["start"], r["end"], [H.bamReadBuffer(good, bad, broken, sample="S1")]))
+    return fasta, work
+
+
+def _region_cases_here(fasta, work):
+    import torch
+    from platypus_amd import fastcaller as F, hostapi as H
+    from platypus_amd.options import default_options
 
     def regions(resident=False, drop=None):
         out, keep = [], []
@@ -382,29 +403,25 @@ def _region_cases():
     return out
 
 
-def _child_main(path):
-    json.dump(_region_cases(), open(path, "w"))
-
-
-def test_region_loop_gives_the_text_of_the_full_expansion(tmp_path):
+def test_region_loop_gives_the_text_of_the_full_expansion():
     """Three small regions in one chunk -- reads, badReads and brokenMates tables, N and Q > 63 exceptions -- resident (dev_seq) and uploaded, a
-    chunk with an empty table, and assemble=1: record text, region text lengths and counters are those of a process run with PLAT_CALLER_EXPAND=1
-    (the switch is read once per process, hence the child).  The counting pass says which path each process took."""
-    assert "PLAT_CALLER_EXPAND" not in os.environ and "PLAT_CALLER_NO_CODES" not in os.environ, "this test needs the default path in its own process"
-    here = _region_cases()
-    path = tmp_path / "expanded.json"
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, PLAT_CALLER_EXPAND="1", PYTHONPATH=root + os.pathsep + os.environ.get("PYTHONPATH", ""))
-    r = subprocess.run([sys.executable, "-c", "from tests.test_gpu_packed_direct import _child_main; _child_main(%r)" % str(path)], cwd=root, env=env,
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-    there = json.load(open(path))
-    for case in ("resident", "uploaded", "empty_table", "assemble"):
-        assert here[case][:2] == there[case][:2], case
-        assert here[case][2][:6] == there[case][2][:6], case
-        assert here[case][0].count("\n") > 20, case
-    assert here["resident"][0] == here["uploaded"][0] and here["resident"][2][6] < here["uploaded"][2][6]
-    assert here["assemble"][2][5] > 0
+    chunk with an empty table, and assemble=1: record text, region text lengths and counters of the default path are those of PLAT_CALLER_EXPAND=1
+    and of PLAT_CALLER_NO_CODES=1, all in this process (the switches are read at every call).  The counting pass says which path each run took;
+    the default path run again last gives what it gave first (a switch frozen at the process's first chunk, or at the first one set, would not)."""
+    inputs = _region_inputs()
+    here = _region_cases(inputs)
+    expanded = _region_cases(inputs, "PLAT_CALLER_EXPAND")
+    bytescan = _region_cases(inputs, "PLAT_CALLER_NO_CODES")
+    again = _region_cases(inputs)
+    for there in (expanded, bytescan):
+        for case in ("resident", "uploaded", "empty_table", "assemble"):
+            assert here[case][:2] == there[case][:2], case
+            assert here[case][2][:6] == there[case][2][:6], case
+            assert here[case][0].count("\n") > 20, case
+    for run in (here, expanded, bytescan):
+        assert run["resident"][0] == run["uploaded"][0] and run["resident"][2][6] < run["uploaded"][2][6]
+        assert run["assemble"][2][5] > 0
     b_here, n = here["first_pass_bytes"]
-    b_there, n2 = there["first_pass_bytes"]
-    assert n == n2 and b_here == n + n // 4 and b_there == 3 * n + n // 4
+    assert [n, n] == [expanded["first_pass_bytes"][1], bytescan["first_pass_bytes"][1]]
+    assert b_here == n + n // 4 and expanded["first_pass_bytes"][0] == 3 * n + n // 4 and bytescan["first_pass_bytes"][0] == 3 * n
+    assert again == here

@@ -364,3 +364,50 @@ def test_the_loaders_own_figures_for_its_tables(fake, monkeypatch):
             st.longest_read += 1
     with pytest.raises(Exception):
         call(lie)
+
+
+# What each PLAT_CALLER_* switch accepts, read off the parse at every site that called getenv before host/switches.hpp took them over (file:line
+# of commit 336c4c0, under platypus_amd/csrc/host/).  Per field: its value with the variable unset, "", "0", "1", "yes".
+_SET_AT_ALL = (0, 1, 1, 1, 1)                                               # getenv(...) != nullptr
+_BEGINS_WITH_1 = (0, 0, 0, 1, 0)                                            # e && e[0] == '1'
+_NOT_BEGINNING_0 = (1, 1, 0, 1, 1)                                          # !(e && e[0] == '0')
+SWITCH_TABLE = {
+    "NO_CODES": {"noCodes": _SET_AT_ALL},                                   # stage_a.hpp:48
+    "EXPAND": {"expand": _SET_AT_ALL},                                      # stage_a.hpp:49
+    "HOST_TALLY": {"hostTally": _SET_AT_ALL},                               # stage_a.hpp:255
+    "HOST_B": {"hostB": _BEGINS_WITH_1},                                    # stage_b_device.hpp:10-11
+    "NO_DEVICE_REPLAY": {"noDeviceReplay": _SET_AT_ALL},                    # stage_b_device.hpp:59
+    "HOST_INFO": {"hostInfo": _SET_AT_ALL},                                 # stage_cde.hpp:218
+    "FIRST_OCCURRENCE_ORDER": {"firstOccurrenceOrder": _SET_AT_ALL},        # stage_b_host.hpp:144
+    "EVEN_TAIL": {"evenTail": _NOT_BEGINNING_0},                            # region_caller.cpp:199
+    "KEEP_SPARE": {"keepSpare": _BEGINS_WITH_1},                            # region_caller.cpp:346
+    "CHECK_HINTS": {"checkHints": _BEGINS_WITH_1},                          # region_caller.cpp:165
+    "TRACE": {"trace": _SET_AT_ALL,                                         # caller_common.hpp:614, chunk.hpp:166, stage_b_host.hpp:145, region_caller.cpp:507
+              "traceStages": _BEGINS_WITH_1},                               # caller_common.hpp:61-62 (traceStages)
+}                                                                           # (region_caller.cpp:74, PLAT_CALLER_POLL_US, stays where the caller is made)
+SWITCH_DEFAULTS = dict(noCodes=0, expand=0, hostTally=0, hostB=0, noDeviceReplay=0, hostInfo=0, firstOccurrenceOrder=0, evenTail=1, keepSpare=0, checkHints=0,
+                       trace=0, traceStages=0)
+
+
+def test_every_switch_parses_as_it_did_at_its_old_site(tmp_path):
+    """tests/switches_driver.cpp (a stand-alone program over host/switches.hpp alone, built with -fsanitize=address,undefined) sets every variable to
+    every spelling the old sites told apart and prints Switches::read(): each field follows its own variable by its own rule, and no other."""
+    import os
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "switches_driver")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan",
+                           "-I", os.path.join(root, "platypus_amd", "csrc"), os.path.join(root, "tests", "switches_driver.cpp"), "-o", exe])
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:verify_asan_link_order=0")     # (as tests/test_bgzf_cpu.py: a library loaded in front of ASan's runtime is no error)
+    out = subprocess.run([exe], env=env, capture_output=True, text=True)
+    assert out.returncode == 0, out.stderr[-2000:]
+    got = {}
+    for line in out.stdout.splitlines():
+        head, fields = line.split(": ")
+        got[tuple(head.split(" "))] = {k: int(v) for k, v in (f.split("=") for f in fields.split())}
+    want = {}
+    for name, rules in SWITCH_TABLE.items():
+        for k, spelling in enumerate(("unset", "empty", "0", "1", "yes")):
+            want[(name, spelling)] = dict(SWITCH_DEFAULTS, **{field: rule[k] for field, rule in rules.items()})
+    assert len(SWITCH_TABLE) == 11 and len(want) == 55 and set(f for r in SWITCH_TABLE.values() for f in r) == set(SWITCH_DEFAULTS)
+    assert got == want
