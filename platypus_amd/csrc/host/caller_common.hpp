@@ -383,6 +383,23 @@ static void heapPushPop(std::vector<ScoredHap>& h, ScoredHap item) {
 struct Ptrs { int gs, ge, bs, be, ks, ke; };
 typedef SmallVec<Ptrs, 2> PtrList;                                        // one per sample                               // window pointers of one sample: reads, badReads, brokenMates
 
+// What only the host's own stage B (prepareWindow, finishHaplotypes) and the greedy filter (greedyRounds) keep of a window.  Nearly every
+// window of a one-sample job is prepared by the device and never has one, so the passes over a chunk's windows do not drag it through the
+// caches.  It is made when a window first takes the host's path.  A window filled in place (WindowList::emplace_back: the device's columns)
+// keeps the block of the object it recycles; a window prepared as a local and moved in (push_back: host stage B) brings its own block and
+// frees the slot's -- one allocation per such window, as the containers in it were before.
+struct HostWindowState {
+    std::string refSeq;                                                    // reference haplotype
+    // greedy filter state
+    VarList byCoverage;
+    size_t step = 0;
+    std::vector<ScoredHap> heap;
+    std::vector<VarList> cands;
+    std::vector<int> sampledSeg;                                           // per sample: [begin, end) into `sampled`
+    std::vector<std::pair<int, int>> sampled;                              // (sample, local index in reads table)
+    void clear() { refSeq.clear(); byCoverage.clear(); step = 0; heap.clear(); cands.clear(); sampledSeg.clear(); sampled.clear(); }
+};
+
 struct WindowWork {
     int region = 0, startPos = 0, endPos = 0;
     VarList vars;                                                          // window["variants"] (after filterVariantsByCoverage)
@@ -390,23 +407,16 @@ struct WindowWork {
     PtrList ptrs;
     int nReads = 0;
     int hapStart = 0, hapEnd = 0, endBuf = 0;                              // Haplotype.startPos / endPos / endBufferSize
-    std::string refSeq;                                                    // reference haplotype
     std::vector<Hap> haps;                                                 // merged, sorted (Population.haplotypes)
     bool live = false;                                                     // goes to the device
-    // greedy filter state
-    bool greedy = false;
-    VarList byCoverage;
-    size_t step = 0;
-    std::vector<ScoredHap> heap;
-    std::vector<VarList> cands;
-    std::vector<int> sampledSeg;                                           // per sample: [begin, end) into `sampled`
-    std::vector<std::pair<int, int>> sampled;                              // (sample, local index in reads table)
+    bool greedy = false;                                                   // in the greedy filter's rounds (its state: host())
+    std::unique_ptr<HostWindowState> hostState;
+    HostWindowState& host() { if (!hostState) hostState.reset(new HostWindowState()); return *hostState; }
     // results
     int bw = -1;                                                           // window index in the device batch
     int hapBegin = 0;                                                      // index of its first haplotype there
     bool onDevice = false;                                                 // prepared by plat_stage_b_batch: its batch entries are on the device already
     VarList distinct;                                                      // _distinctVariants
-    std::vector<double> posterior;                                         // aligned with distinct
     VarList called;                                                        // variantPosteriors keys, in insertion order
     std::vector<double> calledPost;
     std::vector<std::pair<int, VarList>> byPos;                            // varsByPos, insertion order
@@ -422,10 +432,10 @@ struct WindowWork {
         region = 0; startPos = 0; endPos = 0;
         vars.clear(); allVars.clear(); ptrs.clear();
         nReads = 0; hapStart = 0; hapEnd = 0; endBuf = 0;
-        refSeq.clear(); haps.clear(); live = false;
-        greedy = false; byCoverage.clear(); step = 0; heap.clear(); cands.clear(); sampledSeg.clear(); sampled.clear();
+        haps.clear(); live = false;
+        greedy = false; if (hostState) hostState->clear();
         bw = -1; hapBegin = 0; onDevice = false;
-        distinct.clear(); posterior.clear(); called.clear(); calledPost.clear(); byPos.clear(); info.clear();
+        distinct.clear(); called.clear(); calledPost.clear(); byPos.clear(); info.clear();
         firstStatVar = 0; firstSite = 0; failed = false; text.clear(); nRecords = 0; nRefRecords = 0; firstFlat = -1;
     }
 };

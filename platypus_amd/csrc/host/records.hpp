@@ -147,7 +147,8 @@ inline char* put_py2_str(char* p, double x) {                             // at 
 // "%.0f" % x and "%1.4f" % x (the PP and FR fields) without printf for the values that occur: both print the decimal nearest to the
 // double's EXACT value (ties to even).  x * 10^d is computed with its rounding error (fma); the shortcut is taken only when the product is
 // far enough from a tie for that error not to matter, everything else goes through snprintf.
-inline void append_fixed(std::string& out, double x, int decimals) {     // decimals 0 or 4
+// Returns whether the shortcut was taken; *rounded (if given): the integer whose digits were written (decimals == 0: the value itself).
+inline bool append_fixed(std::string& out, double x, int decimals, unsigned long long* rounded = nullptr) {     // decimals 0 or 4
     if (!std::signbit(x) && x < (decimals == 4 ? 1e5 : 1e9)) {        // (x * 1e4 < 1e9: its rounding error stays below 6e-8)
         const double scale = decimals == 4 ? 1e4 : 1.0;
         const double y = x * scale, err = fma(x, scale, -y);              // x * scale == y + err exactly
@@ -159,6 +160,7 @@ inline void append_fixed(std::string& out, double x, int decimals) {     // deci
                 if (frac > 0.5 || (frac == 0.5 && (n & 1ull))) ++n;
             } else if (frac > 0.5) ++n;
             (void)err;
+            if (rounded) *rounded = n;
             char buf[40], *q = buf;
             if (decimals == 0) q = put_uint(q, n);
             else {
@@ -171,12 +173,13 @@ inline void append_fixed(std::string& out, double x, int decimals) {     // deci
                 *q++ = (char)('0' + f % 10);
             }
             out.append(buf, (size_t)(q - buf));
-            return;
+            return true;
         }
     }
     char buf[400];
     snprintf(buf, sizeof buf, decimals == 4 ? "%1.4f" : "%.0f", x);
     out += buf;
+    return false;
 }
 inline void append_int(std::string& out, long long v) {
     char buf[24], *p = buf;
@@ -475,7 +478,12 @@ struct VarInfo {                                                          // vcf
     InlineStr SC;
     std::string PP, FRtext;
     double PPnum = 0.0; int PPint = 0;                                    // float(PP) and int(float(PP)) as the text gives them: parsed once (setPP)
-    void setPP(double posterior) { PP.clear(); append_fixed(PP, posterior, 0); PPnum = strtod(PP.c_str(), nullptr); PPint = atoi(PP.c_str()); }   // "%.0f"
+    void setPP(double posterior) {                                        // "%.0f"
+        PP.clear();
+        unsigned long long n = 0;
+        if (append_fixed(PP, posterior, 0, &n)) { PPnum = (double)n; PPint = (int)n; }   // the integer the text was written from (< 1e9)
+        else { PPnum = strtod(PP.c_str(), nullptr); PPint = atoi(PP.c_str()); }
+    }
     double FRsum = 0.0;
     Num ABPV, SbPval, BRF, MQ, QD;
     long long TR = 0, NF = 0, NR = 0, TC = 0, TCR = 0, TCF = 0;
@@ -492,7 +500,8 @@ inline int homopolymerLengthForOneVariant(const Variant& v, const Fasta& fa) {
     const int64_t lb = std::max<int64_t>(0, (int64_t)v.refPos - 20), le = std::min<int64_t>(fa.len - 1, v.refPos);
     const int64_t rb = std::max<int64_t>(0, (int64_t)v.refPos + 1), re = std::min<int64_t>(fa.len - 1, (int64_t)v.refPos + 21);
     if (le < lb || re < rb) throw WindowError("Cannot have beginPos > endPos in getSequence");
-    const char* left = (const char*)fa.seq + lb; const char* right = (const char*)fa.seq + rb;
+    const RefView ref = v.view(fa, lb, re);
+    const char* left = ref.at(lb); const char* right = ref.at(rb);
     const int64_t nL = le - lb, nR = re - rb;
     if (nL == 0 || nR == 0) return 0;
     int nl = 0, nr = 0;
@@ -504,7 +513,7 @@ inline std::string getSequenceContext(const Variant& v, const Fasta& fa) { retur
 inline void getSequenceContext(const Variant& v, const Fasta& fa, InlineStr& out) {       // the same interval, clamped and checked as getSequence does
     const int64_t b = std::max<int64_t>(0, (int64_t)v.refPos - 10), e = std::min<int64_t>(fa.len - 1, (int64_t)v.refPos + 11);
     if (e < b) throw WindowError("Cannot have beginPos > endPos in getSequence");
-    out.assign((const char*)fa.seq + b, (size_t)(e - b));
+    out.assign(v.view(fa, b, e).at(b), (size_t)(e - b));
 }
 
 template <class Str> inline double computeSCValue(const Str& sequence) {  // vcfutils.pyx:1480-1498
@@ -571,7 +580,9 @@ inline void refAndAlt(int POS, const VarList& variants, const Fasta& fa, std::st
     }
     ALT.clear();
     if (onlySnps) {
-        REF = std::string(1, fa.getCharacter(POS));
+        // getCharacter(POS): from the first variant's reference context when it holds the position
+        const Variant* v0 = variants.empty() ? nullptr : variants[0];
+        REF.assign(1, v0 && v0->ctx.covers(POS, (int64_t)POS + 1) ? *v0->ctx.at(POS) : fa.getCharacter(POS));
         for (const Variant* v : variants) ALT.push_back(v->added);
         return;
     }
@@ -582,6 +593,28 @@ inline void refAndAlt(int POS, const VarList& variants, const Fasta& fa, std::st
         const size_t b = std::min<size_t>(v->nRemoved == v->nAdded ? (size_t)v->nAdded : (size_t)(1 + v->nRemoved), REF.size());
         ALT.push_back(REF.substr(0, a) + v->added + REF.substr(std::max(a, b)));
     }
+}
+
+// Probe of the reference context (tests/test_ref_context_cpu.py, tests/ref_context_driver.cpp): one variant whose removed bases lie at
+// [remPos, remPos + nrem) of the reference, made as Chunk::stageBFromDevice makes it -- with the context, or without it (then every reader
+// reads the Fasta).  One line: HP, SC, the REF of the record at refPos and the removed bases; "!<message>" for a reader that raised.
+inline std::string probeRefContext(const Fasta& fa, int pos, int64_t remPos, size_t nrem, const char* added, size_t nadd, bool withContext) {
+    Variant v;
+    if (withContext) v.assignWithContext(fa, pos, remPos, nrem, added, nadd, 1, PLATYPUS_VAR);
+    else v.assign(pos, (const char*)fa.seq + remPos, nrem, added, nadd, 1, PLATYPUS_VAR);
+    std::string out = "CTX=" + std::to_string(v.ctx.n >= 0 ? 1 : 0) + "\tHP=";
+    try { out += std::to_string(homopolymerLengthForOneVariant(v, fa)); } catch (const WindowError& e) { out += std::string("!") + e.what(); }
+    out += "\tSC=";
+    try { InlineStr sc; getSequenceContext(v, fa, sc); out.append(sc.data(), sc.size()); } catch (const WindowError& e) { out += std::string("!") + e.what(); }
+    out += "\tREF=";
+    try {
+        std::string ref; std::vector<std::string> alt;
+        VarList one{&v};
+        refAndAlt(v.refPos, one, fa, ref, alt);
+        out += ref;
+    } catch (const WindowError& e) { out += std::string("!") + e.what(); }
+    out += "\tREM=" + v.removed;
+    return out;
 }
 
 inline void trimLeftPadding(int& pos, std::string& ref, std::vector<std::string>& alt) {     // vcfutils.pyx:796-839

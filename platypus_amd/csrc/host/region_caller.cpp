@@ -674,6 +674,23 @@ CALLER_EXPORT double plat_caller_debug_prior(const char* ref, long long ref_len,
     Variant v((int)pos, removed ? removed : "", added ? added : "", 1, PLATYPUS_VAR);
     return calculatePrior(v, fa);
 }
+// HP / SC / REF of one variant from the reference itself (with_context = 0) or from the context device stage B's variants carry (1); the removed bases
+// are [rem_pos, rem_pos + n_removed) of `ref`.  For tests/test_ref_context_cpu.py
+CALLER_EXPORT void plat_caller_debug_ref_context(const char* ref, long long ref_len, long long pos, long long rem_pos, int n_removed, const char* added, int with_context,
+                                                 char* out, size_t cap) {
+    Fasta fa;
+    fa.seq = (const uint8_t*)ref; fa.len = ref_len;
+    const std::string t = probeRefContext(fa, (int)pos, rem_pos, (size_t)n_removed, added ? added : "", added ? strlen(added) : 0, with_context != 0);
+    snprintf(out, cap, "%s", t.c_str());
+}
+// PP, float(PP), int(float(PP)) of one posterior as VarInfo::setPP leaves them; via_text = 1: the numbers parsed back from the text
+CALLER_EXPORT void plat_caller_debug_set_pp(double posterior, int via_text, char* pp, size_t cap, double* pp_num, int* pp_int) {
+    VarInfo d;
+    d.setPP(posterior);
+    if (via_text) { d.PPnum = strtod(d.PP.c_str(), nullptr); d.PPint = atoi(d.PP.c_str()); }
+    snprintf(pp, cap, "%s", d.PP.c_str());
+    *pp_num = d.PPnum; *pp_int = d.PPint;
+}
 CALLER_EXPORT void plat_caller_debug_fixed(double x, int decimals, char* out, size_t cap) {
     std::string t;
     append_fixed(t, x, decimals);

@@ -122,12 +122,31 @@ inline void Chunk::stageBFromDevice() {
         r.nCandRecords += hdr[3];
         r.variants.clear();
         const uint8_t* blob = z.sb_added.h + g * (size_t)capA;
+        // The device did the scan: these reference lines are cold on the host.  A variant's context (RefContext) is copied here, once, and the lines of
+        // the variants a few entries ahead are asked for now so that the misses overlap; for a pure indel also the lines indelPrior reads (refPos +- 100).
+        const int32_t* vpos = z.sb_vpos.h + g * (size_t)capV;
+        const int32_t* vnrem = z.sb_vnrem.h + g * (size_t)capV;
+        const int32_t* vnadd = z.sb_vnadd.h + g * (size_t)capV;
+        const bool refCtx = !o.sw.noRefCtx, ahead = refCtx && !o.sw.noRefPrefetch;
+        auto prefetchRef = [&](int i) {
+            const int64_t last = r.fa.len - 1, pos = std::max(0, vpos[i]);
+            if (last < 0) return;
+            const bool indel = (vnrem[i] == 0) != (vnadd[i] == 0);
+            const int64_t a = std::max<int64_t>(0, pos - (indel ? 100 : 20)), e = std::min<int64_t>(last, pos + (indel ? 101 : 21));
+            for (int64_t q = a & ~(int64_t)63; q <= e; q += 64) __builtin_prefetch(r.fa.seq + q);
+        };
+        constexpr int AHEAD = 6;
+        if (ahead) for (int i = 0; i < std::min(nV, AHEAD); ++i) prefetchRef(i);
         for (int i = 0; i < nV; ++i) {
             PROF("s2.fill.variant");
             const size_t k = g * (size_t)capV + (size_t)i;
             const int nrem = z.sb_vnrem.h[k], nadd = z.sb_vnadd.h[k];
-            Variant* v = r.pool.make(z.sb_vpos.h[k], (const char*)r.fa.seq + z.sb_vrempos.h[k], (size_t)nrem,
-                                     (const char*)blob + z.sb_vaddoff.h[k], (size_t)nadd, z.sb_vsupp.h[k], PLATYPUS_VAR);
+            Variant* v = r.pool.next();
+            if (refCtx) {
+                if (ahead && i + AHEAD < nV) prefetchRef(i + AHEAD);
+                v->assignWithContext(r.fa, z.sb_vpos.h[k], z.sb_vrempos.h[k], (size_t)nrem, (const char*)blob + z.sb_vaddoff.h[k], (size_t)nadd, z.sb_vsupp.h[k], PLATYPUS_VAR);
+            } else
+                v->assign(z.sb_vpos.h[k], (const char*)r.fa.seq + z.sb_vrempos.h[k], (size_t)nrem, (const char*)blob + z.sb_vaddoff.h[k], (size_t)nadd, z.sb_vsupp.h[k], PLATYPUS_VAR);
             v->bamMinPos = z.sb_vbmin.h[k]; v->bamMaxPos = z.sb_vbmax.h[k];
             r.variants.push_back(v);
         }

@@ -242,8 +242,9 @@ inline void Chunk::prepareWindow(RegionWork& r, WindowWork& w) {
     w.hapStart = std::max(0, w.startPos);
     w.hapEnd = (int)std::min<int64_t>(w.endPos, r.fa.len - 1);
     w.endBuf = std::min(2 * r.rlen, 500);                               // chaplotype.pyx:142
-    { PROF("s2.pw.refseq"); w.refSeq = haplotypeSequence(r.fa, w.hapStart, w.hapEnd, w.endBuf, VarList()); }
-    if (w.refSeq.size() > 16384) throw WindowError("Haplotype is too long. Max allowed length is 16384");
+    HostWindowState& hw = w.host();
+    { PROF("s2.pw.refseq"); hw.refSeq = haplotypeSequence(r.fa, w.hapStart, w.hapEnd, w.endBuf, VarList()); }
+    if (hw.refSeq.size() > 16384) throw WindowError("Haplotype is too long. Max allowed length is 16384");
     w.ptrs.resize(r.samples.size());
     w.nReads = 0;
     PROF("s2.pw.rest");
@@ -291,22 +292,22 @@ inline void Chunk::prepareWindow(RegionWork& r, WindowWork& w) {
     // greedy growth of the best haplotypes, one variant at a time (most supported first); the alignments of a step are
     // batched over every such window of the chunk (greedyRounds)
     w.greedy = true;
-    w.byCoverage = w.vars;
-    std::stable_sort(w.byCoverage.begin(), w.byCoverage.end(), [](const Variant* a, const Variant* b) { return a->nSupportingReads > b->nSupportingReads; });
-    w.step = 0;
+    hw.byCoverage = w.vars;
+    std::stable_sort(hw.byCoverage.begin(), hw.byCoverage.end(), [](const Variant* a, const Variant* b) { return a->nSupportingReads > b->nSupportingReads; });
+    hw.step = 0;
     // the sampled reads of computeBestScoreForGenotype (variantFilter.pyx:237-283)
     const int windowSize = w.endPos - w.startPos, target = o.coverageSamplingLevel;
     if (windowSize <= 0 || target <= 0) throw WindowError("integer division or modulo by zero");
-    w.sampledSeg.assign(1, 0);
+    hw.sampledSeg.assign(1, 0);
     for (size_t i = 0; i < r.samples.size(); ++i) {
         const Ptrs& p = w.ptrs[i];
         const int n = p.ge - p.gs;
         if (n > 0) {
             const int meanCoverage = r.samples[i].reads.rlen(p.gs) * n / windowSize;            // :264
             const int sampleRate = std::max(1, meanCoverage / target);
-            for (int q = p.gs; q < p.ge; q += sampleRate) w.sampled.push_back({(int)i, q});
+            for (int q = p.gs; q < p.ge; q += sampleRate) hw.sampled.push_back({(int)i, q});
         }
-        w.sampledSeg.push_back((int)w.sampled.size());
+        hw.sampledSeg.push_back((int)hw.sampled.size());
     }
 }
 
@@ -316,7 +317,7 @@ inline void Chunk::finishHaplotypes(RegionWork& r, WindowWork& w, std::vector<Ha
     all.clear();
     all.reserve(haps.size() + 1);
     Hap ref;
-    ref.seq = w.refSeq;
+    ref.seq = w.host().refSeq;
     all.push_back(std::move(ref));
     for (Hap& h : haps) all.push_back(std::move(h));
     SmallVec<size_t, 16> order;
@@ -365,33 +366,35 @@ inline void Chunk::greedyRounds() {
         BatchBuilder b;
         b.nInd = 1;
         for (WindowWork* w : todo) {
-            if (!w->greedy || w->step >= w->byCoverage.size()) continue;
+            if (!w->greedy) continue;
+            HostWindowState& hw = w->host();
+            if (hw.step >= hw.byCoverage.size()) continue;
             RegionWork& r = *regions[(size_t)regionSlot(w->region)];
             try {
-                Variant* tempVar = w->byCoverage[w->step];
-                std::vector<ScoredHap> old = w->heap;
+                Variant* tempVar = hw.byCoverage[hw.step];
+                std::vector<ScoredHap> old = hw.heap;
                 std::stable_sort(old.begin(), old.end(), scoredLess);
-                w->cands.clear();
-                w->cands.push_back(VarList{tempVar});
+                hw.cands.clear();
+                hw.cands.push_back(VarList{tempVar});
                 for (const ScoredHap& sh : old) {
                     VarList both{tempVar};
                     both.insert(both.end(), sh.vs.begin(), sh.vs.end());
                     std::stable_sort(both.begin(), both.end(), variantLess);
-                    if (isHaplotypeValid(both)) w->cands.push_back(both);
+                    if (isHaplotypeValid(both)) hw.cands.push_back(both);
                 }
-                if (w->sampled.empty()) {                               // no reads sampled: every score is -1e20
-                    for (const VarList& vs : w->cands) makeHap(r, *w, vs);
-                    for (const VarList& vs : w->cands) pushScored(*w, ScoredHap{-1e20, vs}, originalMax);
-                    ++w->step;
+                if (hw.sampled.empty()) {                                // no reads sampled: every score is -1e20
+                    for (const VarList& vs : hw.cands) makeHap(r, *w, vs);
+                    for (const VarList& vs : hw.cands) pushScored(*w, ScoredHap{-1e20, vs}, originalMax);
+                    ++hw.step;
                     active.push_back(nullptr);                          // (keeps the loop going without a device window)
                     continue;
                 }
                 std::vector<std::string> seqs;
-                for (const VarList& vs : w->cands) seqs.push_back(makeHap(r, *w, vs).seq);
+                for (const VarList& vs : hw.cands) seqs.push_back(makeHap(r, *w, vs).seq);
                 b.beginWindow(w->hapStart, w->hapEnd, w->endBuf);
-                b.addHap(w->refSeq);
+                b.addHap(hw.refSeq);
                 for (const std::string& q : seqs) b.addHap(q);
-                for (auto& sq : w->sampled) b.addRead(r.samples[(size_t)sq.first].reads, sq.second, 2);   // alignSingleRead: never skipped
+                for (auto& sq : hw.sampled) b.addRead(r.samples[(size_t)sq.first].reads, sq.second, 2);   // alignSingleRead: never skipped
                 b.endSegment(0);
                 b.endWindow();
                 active.push_back(w);
@@ -407,20 +410,21 @@ inline void Chunk::greedyRounds() {
             int bw = 0;
             for (WindowWork* w : active) {
                 if (!w) continue;
-                const int nH = (int)w->cands.size(), n = (int)w->sampled.size();
+                HostWindowState& hw = w->host();
+                const int nH = (int)hw.cands.size(), n = (int)hw.sampled.size();
                 const double* ll = s.o_loglik.h + b.pairoff[(size_t)bw];
                 for (int k = 0; k < nH; ++k) {
                     const double* row = ll + (size_t)(k + 1) * (size_t)n;
                     double best = -1e20;
-                    for (size_t i = 0; i + 1 < w->sampledSeg.size(); ++i) {
-                        if (w->sampledSeg[i] == w->sampledSeg[i + 1]) continue;                     // :261-262
+                    for (size_t i = 0; i + 1 < hw.sampledSeg.size(); ++i) {
+                        if (hw.sampledSeg[i] == hw.sampledSeg[i + 1]) continue;                   // :261-262
                         double score = 0.0;
-                        for (int q = w->sampledSeg[i]; q < w->sampledSeg[i + 1]; ++q) score += log(0.5 * (exp(ll[q]) + exp(row[q])));   // :270-272
+                        for (int q = hw.sampledSeg[i]; q < hw.sampledSeg[i + 1]; ++q) score += log(0.5 * (exp(ll[q]) + exp(row[q])));   // :270-272
                         best = std::max(best, score);
                     }
-                    pushScored(*w, ScoredHap{best, w->cands[(size_t)k]}, originalMax);
+                    pushScored(*w, ScoredHap{best, hw.cands[(size_t)k]}, originalMax);
                 }
-                ++w->step;
+                ++hw.step;
                 ++bw;
             }
         }
@@ -429,7 +433,7 @@ inline void Chunk::greedyRounds() {
         if (!w->greedy) continue;
         RegionWork& r = *regions[(size_t)regionSlot(w->region)];
         try {
-            std::vector<ScoredHap> best = w->heap;                      // sorted(hapsByBestScore, reverse=True): descending, equal ones keep their order
+            std::vector<ScoredHap> best = w->host().heap;               // sorted(hapsByBestScore, reverse=True): descending, equal ones keep their order
             std::stable_sort(best.begin(), best.end(), [](const ScoredHap& a, const ScoredHap& b) { return scoredLess(b, a); });
             std::vector<Hap> haps;
             for (size_t i = 0; i < best.size() && (int)i < maxHaplotypes; ++i) haps.push_back(makeHap(r, *w, best[i].vs));
@@ -443,7 +447,8 @@ inline void Chunk::greedyRounds() {
 }
 
 inline void Chunk::pushScored(WindowWork& w, const ScoredHap& item, int originalMax) {
-    if ((int)w.heap.size() < originalMax) heapPush(w.heap, item); else heapPushPop(w.heap, item);
+    std::vector<ScoredHap>& heap = w.host().heap;
+    if ((int)heap.size() < originalMax) heapPush(heap, item); else heapPushPop(heap, item);
 }
 
 }  // namespace plathost

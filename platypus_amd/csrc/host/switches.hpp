@@ -11,6 +11,9 @@
 //   NO_DEVICE_REPLAY             set at all         device stage B gets no records to replay the dictionaries from        tests (the replay matters)
 //   HOST_INFO                    set at all         the ABPV / SbPval / MMLQ loops on the host                            measurements
 //   FIRST_OCCURRENCE_ORDER       set at all         host stage B never replays the dictionaries                           tests (the replay matters)
+//   NO_REFCTX                    begins with '1'    device stage B's variants carry no reference context: HP, SC and     tests, measurements (the A/B baseline)
+//                                                   the SNP REF read the reference itself, nothing is prefetched
+//   NO_REFPREFETCH               begins with '1'    the context is copied but no reference line is asked for ahead       measurements (what the prefetch alone is worth)
 //   EVEN_TAIL                    not beginning '0'  the last round of chunks is cut into equal parts, one per worker      measurements ("0": whole chunks to the end)
 //   KEEP_SPARE                   begins with '1'    a worker keeps its spare window storage for the next call             measurements (slower: region_caller.cpp)
 //   CHECK_HINTS                  begins with '1'    plat_read_table.longest_read / most_bases are checked against a walk  tests, a loader under suspicion
@@ -25,7 +28,7 @@ namespace plathost {
 
 struct Switches {
     bool noCodes = false, expand = false, hostTally = false, hostB = false, noDeviceReplay = false, hostInfo = false, firstOccurrenceOrder = false;
-    bool evenTail = true, keepSpare = false, checkHints = false;
+    bool evenTail = true, keepSpare = false, checkHints = false, noRefCtx = false, noRefPrefetch = false;
     bool trace = false, traceStages = false;                              // PLAT_CALLER_TRACE: set at all / begins with '1'
 
     static Switches read() {
@@ -40,6 +43,8 @@ struct Switches {
         w.hostInfo = isSet("PLAT_CALLER_HOST_INFO");
         w.firstOccurrenceOrder = isSet("PLAT_CALLER_FIRST_OCCURRENCE_ORDER");
         { const char* e = getenv("PLAT_CALLER_EVEN_TAIL"); w.evenTail = !(e && e[0] == '0'); }
+        w.noRefCtx = isOne("PLAT_CALLER_NO_REFCTX");
+        w.noRefPrefetch = isOne("PLAT_CALLER_NO_REFPREFETCH");
         w.keepSpare = isOne("PLAT_CALLER_KEEP_SPARE");
         w.checkHints = isOne("PLAT_CALLER_CHECK_HINTS");
         w.trace = isSet("PLAT_CALLER_TRACE");

@@ -52,6 +52,29 @@ struct Fasta {
     char getCharacter(int64_t pos) const { return (pos >= len || pos < 0) ? '-' : (char)seq[pos]; }   // :120-132
 };
 
+// The reference bytes of [max(0, refPos - 20), min(len - 1, refPos + 21)) held inside a Variant: the union of what
+// homopolymerLengthForOneVariant, getSequenceContext and getCharacter(POS) read, clamped as getSequence clamps.  Device stage B's variants are
+// made from reference lines the host has not read yet; copying them once saves reading them cold again for HP / SC and once more for REF.
+struct RefContext {
+    int32_t begin = 0;
+    int16_t n = -1;                                                     // < 0: none (the readers go to the Fasta)
+    char c[41];
+    // n < 0 also for an interval getSequence refuses: the readers then read the Fasta and raise where they always did
+    void fill(const Fasta& fa, int refPos) {
+        const int64_t b = std::max<int64_t>(0, (int64_t)refPos - 20), e = std::min<int64_t>(fa.len - 1, (int64_t)refPos + 21);
+        if (e < b) { n = -1; return; }
+        begin = (int32_t)b; n = (int16_t)(e - b);
+        memcpy(c, fa.seq + b, (size_t)n);
+    }
+    bool covers(int64_t b, int64_t e) const { return n >= 0 && b >= begin && e <= (int64_t)begin + n; }
+    const char* at(int64_t pos) const { return c + (pos - begin); }
+};
+// reference bytes by position, from a Variant's context or from the Fasta: one body per reader
+struct RefView {
+    const char* p; int64_t first;                                       // p[0] is position `first`
+    const char* at(int64_t pos) const { return p + (pos - first); }
+};
+
 // ---- Variant ----------------------------------------------------------------------------------------------------------------
 struct Variant {
     int refPos = 0;
@@ -59,13 +82,25 @@ struct Variant {
     int nRemoved = 0, nAdded = 0, nSupportingReads = 0, varSource = PLATYPUS_VAR;
     int minRefPos = 0, maxRefPos = 0, bamMinPos = 0, bamMaxPos = 0, varType = SNP;
     double prior = -1.0;                                                // cached calculatePrior (< 0: not yet)
+    RefContext ctx;                                                     // (device stage B's variants only: Chunk::stageBFromDevice)
 
     Variant() {}
     Variant(int pos, std::string rem, std::string add, int nSupp, int source) { removed = std::move(rem); added = std::move(add); init(pos, nSupp, source); }
     // the same into an object that exists already (VariantPool recycles its objects: the strings keep their storage)
     void assign(int pos, const char* rem, size_t nrem, const char* add, size_t nadd, int nSupp, int source) {
         removed.assign(rem, nrem); added.assign(add, nadd);
+        ctx.n = -1;                                                      // (a recycled object may hold the context of another variant)
         init(pos, nSupp, source);
+    }
+    // with the reference context of `pos`: removed bases the context covers are taken from it, not from the reference again
+    void assignWithContext(const Fasta& fa, int pos, int64_t remPos, size_t nrem, const char* add, size_t nadd, int nSupp, int source) {
+        ctx.fill(fa, std::max(0, pos));
+        removed.assign(ctx.covers(remPos, remPos + (int64_t)nrem) ? ctx.at(remPos) : (const char*)fa.seq + remPos, nrem); added.assign(add, nadd);
+        init(pos, nSupp, source);                                        // (init() leaves the context alone)
+    }
+    // the view a reader of [b, e) takes: the context when it holds all of it
+    RefView view(const Fasta& fa, int64_t b, int64_t e) const {
+        return ctx.covers(b, e) ? RefView{ctx.c, ctx.begin} : RefView{(const char*)fa.seq, 0};
     }
     void init(int pos, int nSupp, int source) {
         refPos = std::max(0, pos);
