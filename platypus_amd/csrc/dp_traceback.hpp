@@ -14,9 +14,15 @@
 // alignment columns (gap-open vs gap-extend depends on the PREVIOUS column, i.e. the next one met when walking
 // backwards) is handled with a one-column delay.
 #pragma once
-#include "dp_unpacked.hpp"
+#include "dp_core.hpp"
 
 namespace plat {
+
+typedef unsigned short u16;
+
+__device__ __forceinline__ u16 a16(u16 a, u16 b) { return (u16)(a + b); }                              // v_add_u16 (wraps)
+__device__ __forceinline__ u16 mn16(u16 a, u16 b) { return (short)a < (short)b ? a : b; }              // v_min_i16
+__device__ __forceinline__ u16 mnu16(u16 a, u16 b) { return a < b ? a : b; }                           // v_min_u16
 
 struct TbView {                      // back-pointer storage of one job
     unsigned long long* base;        // &bp[0][job]

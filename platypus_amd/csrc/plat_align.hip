@@ -19,8 +19,8 @@
 //                 (calign.pyx:235-267), score -> log-likelihood (a8, chaplotype.pyx:621-676)
 #include "dp_core.hpp"
 #include <algorithm>
-#include "dp_unpacked.hpp"
 #include "dp_traceback.hpp"
+#include "switches.hpp"
 #include <stdio.h>
 
 #include "plat_internal.hpp"
@@ -49,7 +49,7 @@ __device__ __forceinline__ long long job_slot(long long pair, long long npairs, 
 
 enum { CNT_ERR = 0, CNT_MAXHAP, CNT_MAXREAD, CNT_NEXTRA, CNT_PAIRS_ALIGNED, CNT_NDP_REF, CNT_CELLS_REF, CNT_CELLS_RUN,
        CNT_NJOBS_RUN, CNT_TILE_TOTAL, CNT_SLOW_SEED, CNT_MAXH, CNT_NDENSE, CNT_HAPBLOB, CNT_NPAIRS, CNT_READBLOB, CNT_T0, CNT_T1, CNT_T2, CNT_T3, CNT_T4, CNT_NWAVES, CNT_N };
-static_assert(CNT_N <= 64, "the pinned read-back area holds 64 words");
+static_assert(CNT_N <= 64, "the pinned read-back area holds 64 words");   // (32..47: k_pairs' reason counters, PLAT_SEED_DEBUG=512; 60 is unused)
 
 // The dense list of live DP job slots, built where the jobs are made (k_pairs / k_seed_slow): DENSE_SEGS segments of `segcap`
 // entries, one counter each, a whole window's jobs in one segment (w % DENSE_SEGS); a wave reserves room for its live jobs
@@ -57,7 +57,6 @@ static_assert(CNT_N <= 64, "the pinned read-back area holds 64 words");
 // other counters; k_dense_total copies them into cnt[] for the host and sums them.
 constexpr int DENSE_SEGS = 8;
 constexpr int DENSE_CNT_STRIDE = 512;                    // in long longs
-constexpr int CNT_DP_TILE = 60;                           // k_dp_jobs' tile counter (dynamic tiles)
 constexpr int CNT_AREA = 64 + DENSE_SEGS * DENSE_CNT_STRIDE;   // long longs reserved (and zeroed) for counters per batch
 __device__ __forceinline__ long long* dense_counter(long long* cnt, int seg) { return cnt + 64 + seg * DENSE_CNT_STRIDE; }
 __device__ __forceinline__ long long dense_count(const long long* cnt, int seg, long long segcap) {
@@ -813,7 +812,6 @@ __device__ __forceinline__ void seed_sweep(unsigned* table, unsigned short* nxt,
         s_gmin[t] = (unsigned char)s_go[longest];
     }
     __syncthreads();
-    if (shortcuts & 256) { stop = true; return; }        // (measurement only, PLAT_SEED_DEBUG: the haplotype sweep alone)
     if (lane < 32) level = max(level, trip[lane] ? 2 + (int)(trip[lane] >> 16) : 0);
 #pragma unroll
     for (int s2 = 32; s2 > 0; s2 >>= 1) level = max(level, __shfl_xor(level, s2));
@@ -1321,7 +1319,8 @@ __device__ __forceinline__ void wave_lds_sync() { __builtin_amdgcn_fence(__ATOMI
 // entries of the whole group are reserved with ONE returning atomic per counter (before: two per pair on the same two addresses, ~23 k per
 // launch against the L2's ~90 per microsecond and address) and the waves write their pairs' jobs.  Same LDS carve as k_sweep up to the
 // counters, of which there is one set per wave.
-constexpr int SLOW_WAVES = 4, SLOW_GROUP = 32;
+// the kernel's static LDS (s_out, s_ent, s_dbase below): it counts against the 160 KB of a workgroup next to the dynamic part (align_seed_launch)
+constexpr size_t SLOW_STATIC_LDS = SLOW_GROUP * (sizeof(SlowOut) + sizeof(SlowRec)) + DENSE_SEGS * sizeof(long long);
 __device__ unsigned long long g_slow_ticks[8];            // PLAT_SLOW_TIMING=1 (measurement): thread 0's 100 MHz ticks per phase, summed over groups
 __global__ void __launch_bounds__(64 * SLOW_WAVES)
 k_seed_slow(plat_window_batch b, const int32_t* __restrict__ hap_win, const long long* __restrict__ tile_off,
@@ -1333,6 +1332,7 @@ k_seed_slow(plat_window_batch b, const int32_t* __restrict__ hap_win, const long
     __shared__ SlowOut s_out[SLOW_GROUP];
     __shared__ SlowRec s_ent[SLOW_GROUP];
     __shared__ long long s_dbase[DENSE_SEGS];
+    static_assert(sizeof s_out + sizeof s_ent + sizeof s_dbase == SLOW_STATIC_LDS, "SLOW_STATIC_LDS is this kernel's static LDS");
     const int nw64 = ((maxhap + 63) >> 6) + 8;
     unsigned* table = (unsigned*)smem;
     unsigned short* nxt = (unsigned short*)(smem + (size_t)tsize_max * 4);
@@ -1481,7 +1481,7 @@ __global__ void k_dense_total(long long* cnt, long long segcap)
 // One DP from the caller's bytes: rs / rq = the read's bases and qualities, hs / gs = the haplotype's bases and gap-open penalties
 // at the slice start (calign.pyx:229,256).  Rows past the read's end are the reference's pads ('0', 64: align.c:223-226); the last
 // extra step reads one haplotype position past the slice (a lane that never reaches the result, dp_core.hpp).
-template <bool HAS_N, bool SWAR, bool UNPACKED>
+template <bool HAS_N, bool SWAR>
 __device__ __forceinline__ int dp_job(const uint8_t* __restrict__ rs, const uint8_t* __restrict__ rq, const uint8_t* __restrict__ hs,
                                       const uint8_t* __restrict__ gs, int len2)
 {
@@ -1492,17 +1492,11 @@ __device__ __forceinline__ int dp_job(const uint8_t* __restrict__ rs, const uint
     auto hw = [&](int h) -> uint32_t { return hap_word(hs[h], gs[h]); };
     auto rw8 = [&](int h) -> Raw8 { return Raw8{load_u64_unaligned(rs + h), load_u64_unaligned(rq + h)}; };
     auto hw8 = [&](int h) -> Raw8 { return Raw8{load_u64_unaligned(hs + h), load_u64_unaligned(gs + h)}; };
-    if (UNPACKED) {
-        DPU<HAS_N> dp;
-        dp.init(w0);                                                         // gapextend 3, nucprior 2: chaplotype.pyx:607-608
-        return dp_run_u<HAS_N>(dp, len2, rw, hw);
-    } else {
-        DP<HAS_N, SWAR> dp;
-        dp.init(w0, 3, 2);
-        auto rw16 = [&](int h) -> Raw16 { Raw16 x; load_16_unaligned(rs + h, x.a0, x.a1); load_16_unaligned(rq + h, x.b0, x.b1); return x; };
-        auto hw16 = [&](int h) -> Raw16 { Raw16 x; load_16_unaligned(hs + h, x.a0, x.a1); load_16_unaligned(gs + h, x.b0, x.b1); return x; };
-        return dp_run8<HAS_N, SWAR>(dp, len2, rw, hw, rw8, hw8, rw16, hw16);
-    }
+    DP<HAS_N, SWAR> dp;
+    dp.init(w0, 3, 2);                                                       // gapextend 3, nucprior 2: chaplotype.pyx:607-608
+    auto rw16 = [&](int h) -> Raw16 { Raw16 x; load_16_unaligned(rs + h, x.a0, x.a1); load_16_unaligned(rq + h, x.b0, x.b1); return x; };
+    auto hw16 = [&](int h) -> Raw16 { Raw16 x; load_16_unaligned(hs + h, x.a0, x.a1); load_16_unaligned(gs + h, x.b0, x.b1); return x; };
+    return dp_run8<HAS_N, SWAR>(dp, len2, rw, hw, rw8, hw8, rw16, hw16);
 }
 
 // One lane per live job slot (dense list).  Slot j < npairs is the primary DP of pair j.  Pairs that need a single DP (one
@@ -1510,31 +1504,19 @@ __device__ __forceinline__ int dp_job(const uint8_t* __restrict__ rs, const uint
 // (a8).  Only pairs with several candidate DPs go through k_finalize_multi.
 // Occupancy is pinned at 4 waves/SIMD: the kernel is VALU-issue bound (5 or 6 waves measured no faster), and the registers it
 // leaves free let the latency-bound kernels of ANOTHER batch (other plat_ctx / stream) run next to it (bench.py --streams).
-template <bool UNPACKED>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4)))
 k_dp_jobs(plat_window_batch b, const uint8_t* __restrict__ gob, const uint8_t* __restrict__ hap_has_n, const Job* __restrict__ jobs,
           const PairRec* __restrict__ pairs, const double* __restrict__ mapq_lut, long long npairs,
-          const int32_t* __restrict__ dense, long long segcap, long long* __restrict__ cnt, long long extra_cap,
-          int32_t* __restrict__ job_score, double* __restrict__ out_ll, int32_t* __restrict__ out_score, int dyn)
+          const int32_t* __restrict__ dense, long long segcap, const long long* __restrict__ cnt, long long extra_cap,
+          int32_t* __restrict__ job_score, double* __restrict__ out_ll, int32_t* __restrict__ out_score)
 {
     if (cnt[CNT_ERR] != 0 || cnt[CNT_NEXTRA] > extra_cap) return;   // refused batch / job overflow (reported by the host)
     // a fixed grid walks the dense list in tiles of 256 jobs (the list's length is only known on the device)
     long long ndense = 0;
 #pragma unroll
     for (int k = 0; k < DENSE_SEGS; ++k) ndense += dense_count(cnt, k, segcap);
-    // dyn: every WAVE pulls tiles of 64 jobs with one atomic (cnt[CNT_DP_TILE], zeroed with the batch's counters) until the list is empty --
-    // the waves of a launch that is several rounds deep finish together instead of in the order the fixed stride dealt them their tiles
-    const int lane = threadIdx.x & 63;
-    long long t0 = dyn ? 0 : (long long)blockIdx.x * blockDim.x;
-    for (;;) {
-        if (dyn) {
-            unsigned long long x = 0;
-            if (lane == 0) x = atomicAdd((unsigned long long*)&cnt[CNT_DP_TILE], 1ull);
-            t0 = 64ll * (long long)(((unsigned long long)(unsigned)__shfl((int)x, 0)) | ((unsigned long long)(unsigned)__shfl((int)(x >> 32), 0) << 32));
-        }
-        if (t0 >= ndense) break;
-        const long long t = t0 + (dyn ? lane : (int)threadIdx.x);
-        const long long t0next = t0 + (long long)gridDim.x * blockDim.x;
+    for (long long t0 = (long long)blockIdx.x * blockDim.x; t0 < ndense; t0 += (long long)gridDim.x * blockDim.x) {
+        const long long t = t0 + (int)threadIdx.x;
         const bool active = t < ndense;
         const long long j = active ? dense_slot(dense, segcap, cnt, t) : 0;
         Job jb = Job{0, 0, 0, 0};
@@ -1556,13 +1538,13 @@ k_dp_jobs(plat_window_batch b, const uint8_t* __restrict__ gob, const uint8_t* _
         int sc = 0;
         // wave-uniform choice of the code path: haplotype N's need the extra mask; the 32-bit SWAR adds are only taken when
         // every read of the wave has a quality sum that rules out a carry between the packed halves (dp_core.hpp)
-        const bool anyN = __any(has_n), anyBig = UNPACKED || __any(bigq);
+        const bool anyN = __any(has_n), anyBig = __any(bigq);
         if (anyN) {
-            if (anyBig) { if (active) sc = dp_job<true, false, UNPACKED>(rs, rq, hs, gs, jb.len); }
-            else        { if (active) sc = dp_job<true, true, UNPACKED>(rs, rq, hs, gs, jb.len); }
+            if (anyBig) { if (active) sc = dp_job<true, false>(rs, rq, hs, gs, jb.len); }
+            else        { if (active) sc = dp_job<true, true>(rs, rq, hs, gs, jb.len); }
         } else {
-            if (anyBig) { if (active) sc = dp_job<false, false, UNPACKED>(rs, rq, hs, gs, jb.len); }
-            else        { if (active) sc = dp_job<false, true, UNPACKED>(rs, rq, hs, gs, jb.len); }
+            if (anyBig) { if (active) sc = dp_job<false, false>(rs, rq, hs, gs, jb.len); }
+            else        { if (active) sc = dp_job<false, true>(rs, rq, hs, gs, jb.len); }
         }
         if (active) {
             if (j >= npairs) job_score[j] = sc;
@@ -1574,7 +1556,6 @@ k_dp_jobs(plat_window_batch b, const uint8_t* __restrict__ gob, const uint8_t* _
                 } else job_score[j] = sc;
             }
         }
-        if (!dyn) t0 = t0next;
     }
 }
 
@@ -1638,7 +1619,7 @@ k_dp_rows(int n, int lmax, const uint8_t* __restrict__ haps, const uint8_t* __re
     const size_t ho = (size_t)j * (lmax + 15), ro = (size_t)j * lmax;
     // The production constants go through the job kernel's own core (16 bytes per array and trip, dp_run8): its loads reach up to 16
     // bytes past a row's end, i.e. into the next row -- every row but the last takes it; the last row (and other constants) goes byte by byte.
-    if (gapextend == 3 && nucprior == 2 && lmax >= 16 && j + 1 < n) out[j] = dp_job<true, false, false>(reads + ro, quals + ro, haps + ho, gos + ho, len2[j]);
+    if (gapextend == 3 && nucprior == 2 && lmax >= 16 && j + 1 < n) out[j] = dp_job<true, false>(reads + ro, quals + ro, haps + ho, gos + ho, len2[j]);
     else out[j] = dp_score_bytes(haps + ho, gos + ho, reads + ro, quals + ro, len2[j], gapextend, nucprior);
 }
 
@@ -1794,7 +1775,7 @@ PLAT_EXPORT int plat_dp_batch(plat_ctx* ctx, int n, int lmax, const uint8_t* hap
     return PLAT_OK;
 }
 
-static int align_seed_launch(plat_ctx* ctx, const plat_window_batch& b, hipStream_t st, long long* cnt, int maxhap,
+static int align_seed_launch(plat_ctx* ctx, const AlignSwitches& sw, const plat_window_batch& b, hipStream_t st, long long* cnt, int maxhap,
                              int maxread, long long npairs, int extra_cap, const int32_t* hap_win, const long long* tile_off,
                              int shortcuts, int32_t* dense, long long segcap, double* out_ll, int32_t* out_score,
                              const int32_t* wave_win, const int32_t* wave_first, long long wave_cap)
@@ -1807,17 +1788,14 @@ static int align_seed_launch(plat_ctx* ctx, const plat_window_batch& b, hipStrea
     const size_t nw64 = (((size_t)maxhap + 63) >> 6) + 8;
     const size_t lds0 = (size_t)tsize_max * 4 + ((((size_t)maxhap + 2) * 2 + 7) & ~(size_t)7) + 4 * nw64 * 8 + 16 + 64 + 128;
     const size_t lds = lds0 + ((nw64 + 15) & ~(size_t)15);    // k_sweep: + one byte per chunk of 64 positions (gap-open minima)
-    int slow_group = 8;                                         // entries per workgroup round (<= SLOW_GROUP); PLAT_SLOW_GROUP / PLAT_SLOW_WAVES: measurements
-    if (const char* eg = getenv("PLAT_SLOW_GROUP")) slow_group = atoi(eg) > 0 && atoi(eg) <= SLOW_GROUP ? atoi(eg) : slow_group;
-    int slow_waves = SLOW_WAVES;                                // (a set of diagonal counters per wave; fewer waves when long haplotypes make the sets large)
-    if (const char* ew = getenv("PLAT_SLOW_WAVES")) slow_waves = atoi(ew) > 0 && atoi(ew) <= SLOW_WAVES ? atoi(ew) : slow_waves;
+    const int slow_group = sw.slowGroup;                        // entries per workgroup round (<= SLOW_GROUP)
+    int slow_waves = sw.slowWaves;                              // (a set of diagonal counters per wave; fewer waves when long haplotypes make the sets large)
     while (slow_waves > 1 && lds0 + (size_t)slow_waves * (size_t)cw * 2 > 64 * 1024) slow_waves >>= 1;
     const size_t lds_slow = lds0 + (size_t)slow_waves * (size_t)cw * 2;
-    if (lds_slow > 160 * 1024 || lds > 160 * 1024) return PLAT_ERR_HAP_TOO_LONG;
+    if (lds_slow + SLOW_STATIC_LDS > 160 * 1024 || lds > 160 * 1024) return PLAT_ERR_HAP_TOO_LONG;
     if (lds_slow > 48 * 1024)
         PLAT_HIP(ctx, hipFuncSetAttribute((const void*)k_seed_slow, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_slow));
-    const char* e_x = getenv("PLAT_SEED_XCD");             // (read per call; 0 = haplotype h on workgroup h)
-    const bool xcd = !(e_x && e_x[0] == '0') && b.n_haps >= 64;
+    const bool xcd = sw.seedXcd && b.n_haps >= 64;              // (PLAT_SEED_XCD=0: haplotype h on workgroup h)
     if (xcd) shortcuts |= SEED_XCD;
     const unsigned gx = xcd ? (unsigned)((b.n_haps + 7) / 8) * 8u : (unsigned)b.n_haps;
     // the haplotype sweeps (one wave per workgroup), then the (haplotype, read) pairs packed 64 to a wave
@@ -1831,18 +1809,16 @@ static int align_seed_launch(plat_ctx* ctx, const plat_window_batch& b, hipStrea
     { PLAT_KT_BEGIN(ctx, PLAT_KT_SWEEP, st); hipLaunchKernelGGL(k_sweep, dim3(gx), dim3(64), lds, st, b, (uint8_t*)ctx->hapw.ptr, (uint8_t*)ctx->hap_flags.ptr, cnt, tsize_max, maxhap, shortcuts,
                        (unsigned char*)ctx->seedstate.ptr); PLAT_KT_END(ctx, PLAT_KT_SWEEP, st); }
     PLAT_EV(ctx, 8, st);
-    if (!(shortcuts & 256)) {                                  // (PLAT_SEED_DEBUG=256: the sweeps alone)
-        const unsigned gp = (unsigned)(xcd ? ((wave_cap + 7) / 8) * 8 : wave_cap);
-        { PLAT_KT_BEGIN(ctx, PLAT_KT_PAIRS, st); hipLaunchKernelGGL(k_pairs, dim3(gp > 0 ? gp : 1), dim3(64), lds_pairs, st, b, wave_win, wave_first, tile_off, (const ReadInfo*)ctx->rinfo.ptr,
-                           (const uint16_t*)ctx->codes.ptr, (PairRec*)ctx->pair_rec.ptr, (Job*)ctx->jobs.ptr, npairs, extra_cap, cnt,
-                           (SlowRec*)ctx->slow.ptr, tsize_max, maxhap, shortcuts, dense, segcap, (const double*)ctx->d_mapq_lut, out_ll, out_score,
-                           (const unsigned char*)ctx->seedstate.ptr); PLAT_KT_END(ctx, PLAT_KT_PAIRS, st); }
-    }
+    const unsigned gp = (unsigned)(xcd ? ((wave_cap + 7) / 8) * 8 : wave_cap);
+    { PLAT_KT_BEGIN(ctx, PLAT_KT_PAIRS, st); hipLaunchKernelGGL(k_pairs, dim3(gp > 0 ? gp : 1), dim3(64), lds_pairs, st, b, wave_win, wave_first, tile_off, (const ReadInfo*)ctx->rinfo.ptr,
+                       (const uint16_t*)ctx->codes.ptr, (PairRec*)ctx->pair_rec.ptr, (Job*)ctx->jobs.ptr, npairs, extra_cap, cnt,
+                       (SlowRec*)ctx->slow.ptr, tsize_max, maxhap, shortcuts, dense, segcap, (const double*)ctx->d_mapq_lut, out_ll, out_score,
+                       (const unsigned char*)ctx->seedstate.ptr); PLAT_KT_END(ctx, PLAT_KT_PAIRS, st); }
     PLAT_EV(ctx, 5, st);                                       // k_sweep + k_pairs: ev[1] .. ev[5], ev[8] between the two
     { PLAT_KT_BEGIN(ctx, PLAT_KT_SEED_SLOW, st); hipLaunchKernelGGL(k_seed_slow, dim3(2048), dim3(64 * slow_waves), lds_slow, st, b, hap_win, tile_off, (const ReadInfo*)ctx->rinfo.ptr,
                        (const uint16_t*)ctx->codes.ptr, (PairRec*)ctx->pair_rec.ptr, (Job*)ctx->jobs.ptr, npairs, extra_cap, cnt,
-                       (const SlowRec*)ctx->slow.ptr, tsize_max, maxhap, cw, dense, segcap, getenv("PLAT_SLOW_TIMING") ? 1 : 0, slow_group); PLAT_KT_END(ctx, PLAT_KT_SEED_SLOW, st); }
-    if (getenv("PLAT_SLOW_TIMING")) {
+                       (const SlowRec*)ctx->slow.ptr, tsize_max, maxhap, cw, dense, segcap, sw.slowTiming ? 1 : 0, slow_group); PLAT_KT_END(ctx, PLAT_KT_SEED_SLOW, st); }
+    if (sw.slowTiming) {
         unsigned long long t[8];
         PLAT_HIP(ctx, hipStreamSynchronize(st));
         PLAT_HIP(ctx, hipMemcpyFromSymbol(t, HIP_SYMBOL(g_slow_ticks), sizeof t));
@@ -1944,6 +1920,7 @@ static int align_impl(plat_ctx* ctx, const plat_window_batch* batch, const plat_
     const int maxhap = hv.max_hap_len, maxread = hv.max_read_len, maxR = hv.max_reads_per_window;
     const long long hapblob = hv.hap_blob_len, npairs = hv.n_pairs;
     if (npairs == 0) return PLAT_OK;
+    const AlignSwitches sw = AlignSwitches::read();           // once per call, ahead of everything a switch changes (switches.hpp): the seeding's second attempt sees what the first saw
     if (tile_total > 0x7FFFFFFFF0ll) return PLAT_ERR_OVERFLOW;
     if ((rc = plat_reserve(ctx, ctx->hapw, (size_t)hapblob + 256))) return rc;           // one gap-open byte per haplotype position
     if ((rc = plat_reserve(ctx, ctx->codes, ((size_t)tile_total + 64) * 2))) return rc;
@@ -1961,8 +1938,7 @@ static int align_impl(plat_ctx* ctx, const plat_window_batch* batch, const plat_
     if (prep_lds > 48 * 1024)
         PLAT_HIP(ctx, hipFuncSetAttribute((const void*)k_prep_reads, hipFuncAttributeMaxDynamicSharedMemorySize, (int)prep_lds));
     {
-        const char* e_x = getenv("PLAT_SEED_XCD");           // (read per call; 0 = window w on workgroup w)
-        const bool xcd = !(e_x && e_x[0] == '0') && b.n_windows >= 64;
+        const bool xcd = sw.seedXcd && b.n_windows >= 64;       // (PLAT_SEED_XCD=0: window w on workgroup w)
         const unsigned gx = xcd ? (unsigned)((b.n_windows + 7) / 8) * 8u : (unsigned)b.n_windows;
         { PLAT_KT_BEGIN(ctx, PLAT_KT_PREP_READS, st); hipLaunchKernelGGL(k_prep_reads, dim3(gx, prep_groups), dim3(256), prep_lds, st, b, win_rows, tile_off,
                            (uint16_t*)ctx->codes.ptr, (ReadInfo*)ctx->rinfo.ptr, cnt, prep_qoff, xcd ? 1 : 0); PLAT_KT_END(ctx, PLAT_KT_PREP_READS, st); }
@@ -1978,20 +1954,13 @@ static int align_impl(plat_ctx* ctx, const plat_window_batch* batch, const plat_
         }
         // the ungapped-alignment shortcut applies to plain scores only (the flank score needs the traceback);
         // PLAT_NO_UNGAPPED=1 sends every such pair through the DP instead (cross-check in tests/test_gpu_parity.py)
-        const char* e_ung = getenv("PLAT_NO_UNGAPPED");    // (read per call: the test flips it inside one process)
-        const int no_ungapped = e_ung && e_ung[0] == '1';
-        const char* e_ex = getenv("PLAT_NO_EXACT");        // every reference DP is then run (bench.py's gcups_all_dp)
-        const int no_exact = e_ex && e_ex[0] == '1';
-        const char* e_dbg = getenv("PLAT_SEED_DEBUG");     // measurement only: 256 = the seeding stops after the haplotype sweeps (results are garbage)
-        const char* e_nl = getenv("PLAT_NO_NLOW");
-        const char* e_bq = getenv("PLAT_UNGAPPED_BIGQ");   // measurement only: lets the ungapped proof take reads in the wrap regime too (tools/ungapped_crosscheck.py --bigq)
-        const int shortcuts = ((!calc_flank_score && !no_ungapped) ? SHORTCUT_UNGAPPED : 0) | (no_exact ? 0 : SHORTCUT_EXACT) |
-                              ((e_nl && e_nl[0] == '1') ? 0 : SHORTCUT_NLOW) | ((e_bq && e_bq[0] == '1') ? SHORTCUT_BIGQ : 0) |
-                              (e_dbg ? (atoi(e_dbg) & 0x300) : 0) | (async ? SEED_LEAN : 0);
+        // PLAT_NO_EXACT=1: every reference DP is then run (bench.py's gcups_all_dp); sw.seedDebug is 0 or 512, k_pairs' reason counters
+        const int shortcuts = ((!calc_flank_score && !sw.noUngapped) ? SHORTCUT_UNGAPPED : 0) | (sw.noExact ? 0 : SHORTCUT_EXACT) |
+                              (sw.noNlow ? 0 : SHORTCUT_NLOW) | (sw.ungappedBigq ? SHORTCUT_BIGQ : 0) | sw.seedDebug | (async ? SEED_LEAN : 0);
         // the dense list of live job slots is built by the seeding kernels themselves (DENSE_SEGS segments, each able to hold every slot)
         const long long segcap = npairs + extra_cap;
         if ((rc = plat_reserve(ctx, ctx->dense, ((size_t)segcap * DENSE_SEGS + 64) * sizeof(int32_t)))) return rc;
-        if ((rc = align_seed_launch(ctx, b, st, cnt, maxhap, maxread, npairs, (int)extra_cap, hap_win, tile_off,
+        if ((rc = align_seed_launch(ctx, sw, b, st, cnt, maxhap, maxread, npairs, (int)extra_cap, hap_win, tile_off,
                                     shortcuts, (int32_t*)ctx->dense.ptr, segcap, out_loglik, out_score, wave_win, wave_first, wave_cap))) return rc;
         njobs = npairs + extra_cap;
         if (async) break;                      // job overflow is caught on the device and reported by plat_stream_sync
@@ -2027,31 +1996,13 @@ static int align_impl(plat_ctx* ctx, const plat_window_batch* batch, const plat_
                                (unsigned long long*)ctx->tb.ptr, slab, (int32_t*)ctx->job_score.ptr, out_loglik, out_score);
         }
     } else {
-        static int dp_impl = -1;                 // 1 = one int16 lane per VGPR (dp_unpacked.hpp), 0 = packed (dp_core.hpp)
-        if (dp_impl < 0) { const char* e = getenv("PLAT_DP_IMPL"); dp_impl = e ? (strcmp(e, "unpacked") == 0) : 0; }   // packed measured faster
         // a fixed grid walks the list (its length lives on the device): two rounds of the blocks a device holds at 4 waves/SIMD
-        static int dp_mult = -1;                                   // workgroups of the fixed grid per CU (PLAT_DP_GRID_PER_CU: measurements)
-        if (dp_mult < 0) { const char* e = getenv("PLAT_DP_GRID_PER_CU"); dp_mult = e && atoi(e) > 0 ? atoi(e) : 8; }
-        const long long want = (ngrid + 255) / 256, fixed = (long long)dp_mult * ctx->n_cu;
-        // PLAT_DP_TILES=1 (measurement, round 5): every wave pulls 64-job tiles with one atomic instead of walking the list with a fixed
-        // stride.  Measured SLOWER on both shapes -- config 2 (3 328 tiles, one per wave) k_dp_jobs 137 -> 180 us, every reference DP
-        // executed (24.5 k tiles) 4 008 -> 3 971 GCUPS: thousands of atomics on one L2 address (~90 per us) cost more than the uneven
-        // last round they remove.  Off by default.
-        static int dp_dyn = -1;
-        if (dp_dyn < 0) { const char* e = getenv("PLAT_DP_TILES"); dp_dyn = e ? (e[0] == '1') : 0; }
-        // dynamic tiles: exactly the blocks the device holds at 4 waves/SIMD (4 per CU), each wave pulling tiles until none is left
-        const long long resident = 4ll * ctx->n_cu;
-        const dim3 grid((unsigned)(dp_dyn ? (want < resident ? want : resident) : (want < fixed ? want : fixed)));
-        if (dp_impl)
-            { PLAT_KT_BEGIN(ctx, PLAT_KT_DP_JOBS, st); hipLaunchKernelGGL(k_dp_jobs<true>, grid, dim3(256), 0, st, b, (const uint8_t*)ctx->hapw.ptr,
-                               (const uint8_t*)ctx->hap_flags.ptr, (const Job*)ctx->jobs.ptr,
-                               (const PairRec*)ctx->pair_rec.ptr, ctx->d_mapq_lut, npairs, dense, segcap, cnt, extra_cap,
-                               (int32_t*)ctx->job_score.ptr, out_loglik, out_score, dp_dyn); PLAT_KT_END(ctx, PLAT_KT_DP_JOBS, st); }
-        else
-            { PLAT_KT_BEGIN(ctx, PLAT_KT_DP_JOBS, st); hipLaunchKernelGGL(k_dp_jobs<false>, grid, dim3(256), 0, st, b, (const uint8_t*)ctx->hapw.ptr,
-                               (const uint8_t*)ctx->hap_flags.ptr, (const Job*)ctx->jobs.ptr,
-                               (const PairRec*)ctx->pair_rec.ptr, ctx->d_mapq_lut, npairs, dense, segcap, cnt, extra_cap,
-                               (int32_t*)ctx->job_score.ptr, out_loglik, out_score, dp_dyn); PLAT_KT_END(ctx, PLAT_KT_DP_JOBS, st); }
+        // (8 workgroups per CU; PLAT_DP_GRID_PER_CU: measurements)
+        const long long want = (ngrid + 255) / 256, fixed = (long long)sw.dpGridPerCu * ctx->n_cu;
+        { PLAT_KT_BEGIN(ctx, PLAT_KT_DP_JOBS, st); hipLaunchKernelGGL(k_dp_jobs, dim3((unsigned)(want < fixed ? want : fixed)), dim3(256), 0, st, b, (const uint8_t*)ctx->hapw.ptr,
+                           (const uint8_t*)ctx->hap_flags.ptr, (const Job*)ctx->jobs.ptr,
+                           (const PairRec*)ctx->pair_rec.ptr, ctx->d_mapq_lut, npairs, dense, segcap, cnt, extra_cap,
+                           (int32_t*)ctx->job_score.ptr, out_loglik, out_score); PLAT_KT_END(ctx, PLAT_KT_DP_JOBS, st); }
     }
     PLAT_EV(ctx, 3, st);
     if (async) {
@@ -2080,7 +2031,7 @@ static int align_impl(plat_ctx* ctx, const plat_window_batch* batch, const plat_
     if (out_stats || ctx->profile) {
         PLAT_HIP(ctx, hipMemcpyAsync(hb, cnt, 64 * sizeof(long long), hipMemcpyDeviceToHost, st));
         PLAT_HIP(ctx, hipStreamSynchronize(st));
-        if (getenv("PLAT_SEED_DEBUG") && (atoi(getenv("PLAT_SEED_DEBUG")) & 512)) {
+        if (sw.seedDebug & 512) {
             fprintf(stderr, "k_pairs, pairs that left a DP job, by reason:");
             for (int r = 0; r < 16; ++r) fprintf(stderr, " %lld", (long long)hb[32 + r]);
             fprintf(stderr, "\n");

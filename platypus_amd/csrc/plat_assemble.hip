@@ -40,6 +40,7 @@
 // k > 15, or a reference / read blob beyond 2^18 bytes is done with table, node words and successor lists in the workgroup's
 // slice of a global scratch buffer (the "global path", the round-1 code).
 #include "plat_internal.hpp"
+#include "switches.hpp"
 #include <type_traits>
 
 namespace plat {
@@ -1756,11 +1757,9 @@ k_assemble(plat_assembly_batch b, AsmParams P, char* scratch, int max_ref, int m
             for (int i = tid; i < ASM_LDS_NODES * ASM_MAX_SUCC; i += nthr) S.succ_c[i] = 0;
         sync_phase(); ASM_FRESH();
         ASM_TICK(8);
-        if (work) {
-            if (tid == 0) s_next_g = (int)gridDim.x + (int)atomicAdd((unsigned long long*)work, 1ull);
-            __syncthreads();
-            g = s_next_g;
-        } else g += gridDim.x;
+        if (tid == 0) s_next_g = (int)gridDim.x + (int)atomicAdd((unsigned long long*)work, 1ull);
+        __syncthreads();
+        g = s_next_g;
     }
     if (wg_sig && tid == 0 && s_dirty == 0) wg_sig[blockIdx.x] = sig;      // (behind the last region's barrier: every store of this workgroup has been issued)
 }
@@ -1874,15 +1873,13 @@ static int asm_launch(plat_ctx* ctx, const plat_assembly_batch& b, int kmer_size
     AsmParams P;
     P.kmer = kmer_size; P.min_qual = min_qual; P.min_weight = min_weight; P.no_cycles = no_cycles;
     P.max_vars = max_vars_per_region; P.blob_per_region = blob_per_region; P.cap = cap; P.max_pos = (int)max_pos;
-    P.timing = getenv("PLAT_ASM_TIMING") != nullptr;
-    { const char* ef = getenv("PLAT_ASM_FUSED"); P.fused = !(ef && ef[0] == '0'); }
-    { const char* ed = getenv("PLAT_ASM_DEBUG"); P.debug = ed ? atoi(ed) : 0; }
+    const AsmSwitches sw = AsmSwitches::read();     // once per call (switches.hpp)
+    P.timing = sw.timing; P.fused = sw.fused; P.debug = sw.debug;
     const size_t per_block = asm_scratch_bytes(cap, (int)max_pos, max_ref, max_reads);
     P.scratch_per_block = (long long)per_block;
     // the kernel is bound by the latency of dependent L2 accesses, not by bandwidth or issue: one region per CU at a time (its graph takes
     // most of the CU's LDS) and as the scratch memory allows (PLAT_ASM_WG_PER_CU overrides, for measurements)
-    int per_cu = 1;                                  // (the graph of a region takes most of a CU's LDS)
-    if (const char* e = getenv("PLAT_ASM_WG_PER_CU")) per_cu = atoi(e) > 0 ? atoi(e) : per_cu;
+    const int per_cu = sw.wgPerCu > 0 ? sw.wgPerCu : 1;     // (the graph of a region takes most of a CU's LDS)
     int nblk = b.n_regions < per_cu * ctx->n_cu ? b.n_regions : per_cu * ctx->n_cu;
     while (nblk > 1 && per_block * (size_t)nblk > ((size_t)96 << 30)) nblk = nblk * 3 / 4;
     {
@@ -1894,7 +1891,7 @@ static int asm_launch(plat_ctx* ctx, const plat_assembly_batch& b, int kmer_size
         if ((rc = plat_reserve(ctx, ctx->asm_sig, 4096 * sizeof(unsigned long long)))) return rc;
         PLAT_HIP(ctx, hipMemsetAsync(ctx->asm_sig.ptr, 0, 4096 * sizeof(unsigned long long), st));
     }
-    unsigned long long* wg_sig = (nblk <= 4096 && !getenv("PLAT_ASM_NO_KEEP")) ? (unsigned long long*)ctx->asm_sig.ptr : nullptr;
+    unsigned long long* wg_sig = (nblk <= 4096 && !sw.noKeep) ? (unsigned long long*)ctx->asm_sig.ptr : nullptr;
     // A launch only rewrites wg_sig[] of the workgroups it runs, and a slice sits at blockIdx.x * per_block: a launch with ANOTHER layout (or one
     // that ran without the signature array) overwrites slices of workgroups whose stored signature it never touches.  Every stored signature is
     // therefore made stale -- the epoch is part of it and only grows -- whenever the layout differs from the previous launch's.
@@ -1916,7 +1913,7 @@ static int asm_launch(plat_ctx* ctx, const plat_assembly_batch& b, int kmer_size
     const int lds_bytes = ASM_LDS_BYTES;
     PLAT_HIP(ctx, hipFuncSetAttribute((const void*)k_assemble, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
     { PLAT_KT_BEGIN(ctx, PLAT_KT_ASSEMBLE, st); hipLaunchKernelGGL(k_assemble, dim3(nblk), dim3(ASM_THREADS), lds_bytes, st, b, P, (char*)ctx->asm_scratch.ptr, max_ref, max_reads,
-                       var_count, var_pos, var_nrem, var_nadd, var_off, var_blob, status, verdict, getenv("PLAT_ASM_STATIC") ? nullptr : work, wg_sig, sig); PLAT_KT_END(ctx, PLAT_KT_ASSEMBLE, st); }   // (PLAT_ASM_STATIC: tile g on workgroup g % grid, for A/B runs)
+                       var_count, var_pos, var_nrem, var_nadd, var_off, var_blob, status, verdict, work, wg_sig, sig); PLAT_KT_END(ctx, PLAT_KT_ASSEMBLE, st); }
     PLAT_HIP(ctx, hipGetLastError());
     if (P.timing) {
         unsigned long long t[16];

@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include "plat_internal.hpp"
+#include "switches.hpp"
 
 PLAT_EXPORT int plat_abi_version(void) { return PLAT_ABI_VERSION; }
 
@@ -239,10 +240,9 @@ PLAT_EXPORT int plat_stream_sync(plat_ctx* ctx, void* stream) {
     // hipEventBlockingSync) still polls for a good while before it blocks -- measured in the region loop: 0.085 ms of CPU per region
     // inside 0.09 ms of waiting -- so the default is a poll of the event every PLAT_SYNC_POLL_US microseconds (40) with the thread
     // asleep in between; PLAT_SYNC_POLL_US=0: hipEventSynchronize; PLAT_SYNC_SPIN=1: hipStreamSynchronize, the runtime's default wait.
-    static const bool spin = [] { const char* e = getenv("PLAT_SYNC_SPIN"); return e && e[0] == '1'; }();
-    static const long env_poll_ns = [] { const char* e = getenv("PLAT_SYNC_POLL_US"); const long v = e ? atol(e) : -1; return v < 0 ? -1L : v * 1000L; }();
-    const long poll_ns = env_poll_ns >= 0 ? env_poll_ns : ctx->sync_poll_ns;          // (the environment wins over plat_sync_poll_us: measurements)
-    if (spin || !ctx->sync_event) PLAT_HIP(ctx, hipStreamSynchronize((hipStream_t)stream));
+    static const plat::SyncSwitches sw = plat::SyncSwitches::read();   // once per process (switches.hpp): this is every worker's wait path
+    const long poll_ns = sw.pollNs >= 0 ? sw.pollNs : ctx->sync_poll_ns;               // (the environment wins over plat_sync_poll_us: measurements)
+    if (sw.spin || !ctx->sync_event) PLAT_HIP(ctx, hipStreamSynchronize((hipStream_t)stream));
     else {
         PLAT_HIP(ctx, hipEventRecord((hipEvent_t)ctx->sync_event, (hipStream_t)stream));
         if (poll_ns == 0) PLAT_HIP(ctx, hipEventSynchronize((hipEvent_t)ctx->sync_event));
@@ -258,7 +258,7 @@ PLAT_EXPORT int plat_stream_sync(plat_ctx* ctx, void* stream) {
                 if (q != hipErrorNotReady) { bad = q; break; }
                 (void)hipGetLastError();                                     // (hipErrorNotReady is sticky in hipGetLastError otherwise)
                 if (!napped) { if (slack0 > 2000) prctl(PR_SET_TIMERSLACK, 2000UL, 0, 0, 0); napped = true; }
-                timespec ts{0, poll_ns};
+                const timespec ts = plat::poll_timespec(poll_ns);                  // (seconds apart: a whole interval in tv_nsec is EINVAL from a second on, and the wait spins)
                 nanosleep(&ts, nullptr);
             }
             if (napped && slack0 > 2000) prctl(PR_SET_TIMERSLACK, (unsigned long)slack0, 0, 0, 0);

@@ -11,6 +11,7 @@
 // Genotype g <-> haplotype pair (a, b), a <= b, in the order of generateAllGenotypesFromHaplotypeList
 // (cgenotype.pyx:193-218): g(a, b) = a*H - a*(a-1)/2 + (b - a).
 #include "plat_internal.hpp"
+#include "switches.hpp"
 
 namespace plat {
 
@@ -546,7 +547,7 @@ PLAT_EXPORT int plat_em_window_batch(plat_ctx* ctx, int n_windows, int n_ind, in
     PLAT_HIP(ctx, hipSetDevice(ctx->device));
     // likelihoods and responsibilities of one window in LDS when they fit: k_em_wide
     const size_t wide = (size_t)max_haps_per_window * 8 + 2 * csr_bytes + (size_t)n_ind * 12 + maxG * 4 + 64;
-    const bool no_wide = getenv("PLAT_EM_NARROW") != nullptr;             // (read per call: the one-wave kernel, for measurements and the cross-check test)
+    const bool no_wide = EmSwitches::read().narrow;                       // (once per call, switches.hpp: the one-wave kernel, for measurements and the cross-check test)
     const size_t lds_dev = ctx->lds_max ? ctx->lds_max : 64 * 1024;     // what a workgroup of this device may ask for (160 KB on gfx950)
     if (wide <= 96 * 1024 && wide <= lds_dev && max_haps_per_window < 32768 && !no_wide) {
         const size_t pairs = (size_t)n_ind * maxG;

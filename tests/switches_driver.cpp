@@ -8,13 +8,13 @@
 static void show(const char* name, const char* spelling) {
     const plathost::Switches w = plathost::Switches::read();
     printf("%s %s: noCodes=%d expand=%d hostTally=%d hostB=%d noDeviceReplay=%d hostInfo=%d firstOccurrenceOrder=%d evenTail=%d keepSpare=%d checkHints=%d "
-           "trace=%d traceStages=%d\n", name, spelling, w.noCodes, w.expand, w.hostTally, w.hostB, w.noDeviceReplay, w.hostInfo, w.firstOccurrenceOrder,
-           w.evenTail, w.keepSpare, w.checkHints, w.trace, w.traceStages);
+           "noRefCtx=%d noRefPrefetch=%d trace=%d traceStages=%d\n", name, spelling, w.noCodes, w.expand, w.hostTally, w.hostB, w.noDeviceReplay, w.hostInfo, w.firstOccurrenceOrder,
+           w.evenTail, w.keepSpare, w.checkHints, w.noRefCtx, w.noRefPrefetch, w.trace, w.traceStages);
 }
 
 int main() {
     const char* names[] = {"NO_CODES", "EXPAND", "HOST_TALLY", "HOST_B", "NO_DEVICE_REPLAY", "HOST_INFO", "FIRST_OCCURRENCE_ORDER", "EVEN_TAIL", "KEEP_SPARE",
-                           "CHECK_HINTS", "TRACE"};
+                           "CHECK_HINTS", "NO_REFCTX", "NO_REFPREFETCH", "TRACE"};
     const char* spellings[] = {"", "0", "1", "yes"};
     char var[64];
     for (const char* n : names) { snprintf(var, sizeof var, "PLAT_CALLER_%s", n); unsetenv(var); }

@@ -382,11 +382,13 @@ SWITCH_TABLE = {
     "EVEN_TAIL": {"evenTail": _NOT_BEGINNING_0},                            # region_caller.cpp:199
     "KEEP_SPARE": {"keepSpare": _BEGINS_WITH_1},                            # region_caller.cpp:346
     "CHECK_HINTS": {"checkHints": _BEGINS_WITH_1},                          # region_caller.cpp:165
+    "NO_REFCTX": {"noRefCtx": _BEGINS_WITH_1},                              # (added with the reference context, after 336c4c0: e && e[0] == '1')
+    "NO_REFPREFETCH": {"noRefPrefetch": _BEGINS_WITH_1},                    # (the same)
     "TRACE": {"trace": _SET_AT_ALL,                                         # caller_common.hpp:614, chunk.hpp:166, stage_b_host.hpp:145, region_caller.cpp:507
               "traceStages": _BEGINS_WITH_1},                               # caller_common.hpp:61-62 (traceStages)
 }                                                                           # (region_caller.cpp:74, PLAT_CALLER_POLL_US, stays where the caller is made)
 SWITCH_DEFAULTS = dict(noCodes=0, expand=0, hostTally=0, hostB=0, noDeviceReplay=0, hostInfo=0, firstOccurrenceOrder=0, evenTail=1, keepSpare=0, checkHints=0,
-                       trace=0, traceStages=0)
+                       noRefCtx=0, noRefPrefetch=0, trace=0, traceStages=0)
 
 
 def test_every_switch_parses_as_it_did_at_its_old_site(tmp_path):
@@ -409,5 +411,91 @@ def test_every_switch_parses_as_it_did_at_its_old_site(tmp_path):
     for name, rules in SWITCH_TABLE.items():
         for k, spelling in enumerate(("unset", "empty", "0", "1", "yes")):
             want[(name, spelling)] = dict(SWITCH_DEFAULTS, **{field: rule[k] for field, rule in rules.items()})
-    assert len(SWITCH_TABLE) == 11 and len(want) == 55 and set(f for r in SWITCH_TABLE.values() for f in r) == set(SWITCH_DEFAULTS)
+    assert len(SWITCH_TABLE) == 13 and len(want) == 65 and set(f for r in SWITCH_TABLE.values() for f in r) == set(SWITCH_DEFAULTS)
     assert got == want
+
+
+# The device library's PLAT_* switches (platypus_amd/csrc/switches.hpp), each by the rule its own getenv site applied at commit 223080b (file:line under
+# platypus_amd/csrc/).  Per field: its value with the variable unset and set to "", "0", "1", "yes", "7", "-3", "33", "2000000", "512", "256", "768".
+DEVICE_SPELLINGS = ("unset", "empty", "0", "1", "yes", "7", "-3", "33", "2000000", "512", "256", "768")
+_D_SET_AT_ALL = (0,) + (1,) * 11                                            # getenv(...) != nullptr
+_D_BEGINS_WITH_1 = (0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0)                     # e && e[0] == '1'
+_D_NOT_BEGINNING_0 = (1, 1, 0, 1, 1, 1, 1, 1, 1, 1, 1, 1)                   # !(e && e[0] == '0')
+DEVICE_SWITCH_TABLE = {
+    "PLAT_NO_UNGAPPED": {"noUngapped": _D_BEGINS_WITH_1},                   # plat_align.hip:1981-1982
+    "PLAT_NO_EXACT": {"noExact": _D_BEGINS_WITH_1},                         # plat_align.hip:1983-1984
+    "PLAT_NO_NLOW": {"noNlow": _D_BEGINS_WITH_1},                           # plat_align.hip:1986,1989
+    "PLAT_UNGAPPED_BIGQ": {"ungappedBigq": _D_BEGINS_WITH_1},               # plat_align.hip:1987,1989
+    "PLAT_SEED_XCD": {"seedXcd": _D_NOT_BEGINNING_0},                       # plat_align.hip:1819-1820, 1964-1965
+    "PLAT_SLOW_GROUP": {"slowGroup": (8, 8, 8, 1, 8, 7, 8, 8, 8, 8, 8, 8)},                 # plat_align.hip:1811: atoi in 1..32 (SLOW_GROUP), else 8
+    "PLAT_SLOW_WAVES": {"slowWaves": (4, 4, 4, 1, 4, 4, 4, 4, 4, 4, 4, 4)},                 # plat_align.hip:1813: atoi in 1..4 (SLOW_WAVES), else 4
+    "PLAT_SLOW_TIMING": {"slowTiming": _D_SET_AT_ALL},                      # plat_align.hip:1844-1845
+    "PLAT_SEED_DEBUG": {"seedDebug": (0, 0, 0, 0, 0, 0, 512, 0, 0, 512, 0, 512)},           # plat_align.hip:1985,1990,2083: atoi & 0x300 then, & 0x200 since bit 256
+    #                                                                         (the sweeps alone) is retired; -3 = ...11111101 has bit 512, 2000000 = 0x1E8480 has not
+    "PLAT_DP_GRID_PER_CU": {"dpGridPerCu": (8, 8, 8, 1, 8, 7, 8, 33, 2000000, 512, 256, 768)},   # plat_align.hip:2034: atoi > 0, else 8
+    "PLAT_ASM_TIMING": {"asmTiming": _D_SET_AT_ALL},                        # plat_assemble.hip:1877
+    "PLAT_ASM_FUSED": {"asmFused": _D_NOT_BEGINNING_0},                     # plat_assemble.hip:1878
+    "PLAT_ASM_DEBUG": {"asmDebug": (0, 0, 0, 1, 0, 7, -3, 33, 2000000, 512, 256, 768)},     # plat_assemble.hip:1879: atoi, 0 when unset
+    "PLAT_ASM_WG_PER_CU": {"asmWgPerCu": (0, 0, 0, 1, 0, 7, 0, 33, 2000000, 512, 256, 768)},     # plat_assemble.hip:1885: atoi > 0 overrides; 0 = not given
+    "PLAT_ASM_NO_KEEP": {"asmNoKeep": _D_SET_AT_ALL},                       # plat_assemble.hip:1897
+    "PLAT_EM_NARROW": {"emNarrow": _D_SET_AT_ALL},                          # plat_population.hip:549
+    "PLAT_SYNC_SPIN": {"syncSpin": _D_BEGINS_WITH_1},                       # plat_ctx.hip:242
+    "PLAT_SYNC_POLL_US": {"syncPollNs": (-1, 0, 0, 1000, 0, 7000, -1, 33000, 2000000000, 512000, 256000, 768000)},   # plat_ctx.hip:243: atol; negative or unset = not
+}                                                                           #                                                  given (-1), else x 1000 ns
+DEVICE_SWITCH_DEFAULTS = dict(noUngapped=0, noExact=0, noNlow=0, ungappedBigq=0, seedXcd=1, slowGroup=8, slowWaves=4, slowTiming=0, seedDebug=0, dpGridPerCu=8,
+                              asmTiming=0, asmFused=1, asmDebug=0, asmWgPerCu=0, asmNoKeep=0, emNarrow=0, syncSpin=0, syncPollNs=-1)
+
+
+def test_every_device_switch_parses_as_it_did_at_its_old_site(tmp_path):
+    """tests/device_switches_driver.cpp (a stand-alone program over csrc/switches.hpp alone, built with -fsanitize=address,undefined) sets every variable
+    of the device library to every spelling and prints the four read()s: each field follows its own variable by its old site's rule, and no other field
+    moves.  The retired variables (PLAT_DP_IMPL, PLAT_DP_TILES, PLAT_ASM_STATIC; PLAT_SEED_DEBUG's bit 256 in the table above) move nothing.  A poll
+    interval splits into seconds and nanoseconds below a second, the total kept."""
+    import os
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "device_switches_driver")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan",
+                           "-I", os.path.join(root, "platypus_amd", "csrc"), os.path.join(root, "tests", "device_switches_driver.cpp"), "-o", exe])
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:verify_asan_link_order=0")     # (as above)
+    out = subprocess.run([exe], env=env, capture_output=True, text=True)
+    assert out.returncode == 0, out.stderr[-2000:]
+    got, polls = {}, {}
+    for line in out.stdout.splitlines():
+        head, fields = line.split(": ")
+        vals = {k: int(v) for k, v in (f.split("=") for f in fields.split())}
+        if head.startswith("poll "):
+            polls[int(head.split(" ")[1])] = vals
+        else:
+            got[tuple(head.split(" "))] = vals
+    want = {("RETIRED", "set"): dict(DEVICE_SWITCH_DEFAULTS)}
+    for name, rules in DEVICE_SWITCH_TABLE.items():
+        for k, spelling in enumerate(DEVICE_SPELLINGS):
+            want[(name, spelling)] = dict(DEVICE_SWITCH_DEFAULTS, **{field: rule[k] for field, rule in rules.items()})
+    assert len(DEVICE_SWITCH_TABLE) == 18 and len(want) == 18 * 12 + 1
+    assert set(f for r in DEVICE_SWITCH_TABLE.values() for f in r) == set(DEVICE_SWITCH_DEFAULTS)
+    assert all(len(rule) == len(DEVICE_SPELLINGS) for r in DEVICE_SWITCH_TABLE.values() for rule in r.values())
+    assert got == want
+    assert polls == {0: dict(sec=0, nsec=0), 40: dict(sec=0, nsec=40000), 999999: dict(sec=0, nsec=999999000), 1000000: dict(sec=1, nsec=0),
+                     2000000: dict(sec=2, nsec=0)}
+    for us, ts in polls.items():
+        assert 0 <= ts["nsec"] < 10 ** 9 and ts["sec"] * 10 ** 9 + ts["nsec"] == us * 1000
+
+
+def test_getenv_is_called_in_the_switch_tables_only():
+    """Under platypus_amd/csrc, getenv( occurs in the two switch tables and at the one PLAT_CALLER_POLL_US site of host/region_caller.cpp, nowhere else:
+    no .hip file reads the environment itself."""
+    import os
+    root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "platypus_amd", "csrc")
+    sites = {}
+    for d, dirs, files in os.walk(root):
+        dirs[:] = [x for x in dirs if x != "build"]
+        for f in files:
+            if not f.endswith((".hip", ".hpp", ".h", ".cpp", ".c", ".cc", ".inc")):
+                continue
+            with open(os.path.join(d, f), errors="replace") as fh:
+                lines = [ln for ln in fh if "getenv(" in ln]
+            if lines:
+                sites[os.path.relpath(os.path.join(d, f), root)] = lines
+    assert set(sites) == {"switches.hpp", os.path.join("host", "switches.hpp"), os.path.join("host", "region_caller.cpp")}
+    assert len(sites[os.path.join("host", "region_caller.cpp")]) == 1 and "PLAT_CALLER_POLL_US" in sites[os.path.join("host", "region_caller.cpp")][0]
