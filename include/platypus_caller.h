@@ -226,6 +226,10 @@ int plat_merge_record_texts(const char* const* texts, const size_t* lengths, int
  * blocks in (chromosome key, start) order and falls back to plat_merge_record_texts where regions overlap. */
 int plat_caller_region_text_lengths(const plat_caller* c, int64_t* out, int n);
 int plat_merge_region_blocks(int n, const char* const* src, const size_t* len, const size_t* at, size_t total, char** out_text);
+/* Gives back a text any call above returned.  Mandatory, and never free(): the library tracks the blocks it hands out, and while a plat_caller
+ * exists it keeps up to two given-back blocks of more than 8 MB for the next call instead of returning them to the system (the last
+ * plat_caller_destroy frees those; with no caller alive the block is freed at once).  A block that went to free() directly would stay on
+ * the library's list with a stale address and size. */
 void plat_caller_free(void* p);
 /* Human-readable message of the last error of a failing plat_call_regions on this caller. */
 const char* plat_caller_last_error(const plat_caller* c);

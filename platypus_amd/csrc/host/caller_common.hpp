@@ -1,4 +1,4 @@
-// caller_common.hpp -- what every stage of the native region loop shares: grow-only pinned + device buffers (Slot), one-copy layouts,
+// caller_common.hpp -- what every stage of the native region loop shares: a worker's pinned + device buffers (Slot), one-copy layouts,
 // read tables as the loop sees them, windows / regions in flight, the window batch and the call that runs it on the device.
 #pragma once
 #include <atomic>
@@ -82,36 +82,38 @@ static inline bool windowClassError(int code) {
            code == PLAT_ERR_HAP_TOO_SHORT || code == PLAT_ERR_BAD_HINTS;
 }
 
-// ---- grow-only buffers: pinned host + device mirror -----------------------------------------------------------------------------
-struct Slot;                                                              // one worker's device context
-template <class T> struct Staged {
-    T* h = nullptr; T* d = nullptr; size_t hcap = 0, dcap = 0, n = 0;
-    bool view = false;                                                     // h / d point into an arena (Layout): nothing owned
+// ---- a worker's buffers: pinned host + device mirror -------------------------------------------------------------------------------
+// Owned: grow-only, freed by its destructor on the context it was reserved on (a Slot declares its context in front of its buffers, so the
+// context outlives them).
+template <class T> struct Buffer {
+    T* h = nullptr; T* d = nullptr; size_t hcap = 0, dcap = 0;
+    plat_ctx* ctx = nullptr;
+    Buffer() = default; Buffer(const Buffer&) = delete; Buffer& operator=(const Buffer&) = delete;
+    ~Buffer() { if (h) plat_host_free(ctx, h); if (d) plat_free(ctx, d); }
     // zeroStream != nullptr: a grown device buffer is zeroed once, on that stream (blob slack must hold 7-bit bytes for the kernels
-    // that validate whole dwords; afterwards it only ever holds old, valid bytes)
-    void reserve(plat_ctx* ctx, size_t want, bool host = true, bool dev = true, void* zeroStream = nullptr) {
+    // that validate whole dwords; afterwards it only ever holds old, valid bytes).  Contents are rewritten by whoever grows a buffer.
+    void reserve(plat_ctx* c, size_t want, bool host = true, bool dev = true, void* zeroStream = nullptr) {
+        ctx = c;
         if (host && want > hcap) {
             const size_t ncap = want + want / 2 + 64;
             T* nh = nullptr;
             ck(plat_host_alloc(ctx, ncap * sizeof(T), (void**)&nh), "plat_host_alloc");
-            if (h) { if (n) memcpy(nh, h, std::min(n, hcap) * sizeof(T)); plat_host_free(ctx, h); }
+            if (h) plat_host_free(ctx, h);
             h = nh; hcap = ncap;
         }
         if (dev && want > dcap) {
             const size_t ncap = want + want / 2 + 64;
             T* nd = nullptr;
             ck(plat_malloc(ctx, ncap * sizeof(T) + PLAT_BLOB_PAD, (void**)&nd), "plat_malloc");
-            if (d) plat_free(ctx, d);                                      // (contents are rewritten by whoever grows a buffer)
+            if (d) plat_free(ctx, d);
             d = nd; dcap = ncap;
             if (zeroStream) ck(plat_memset(ctx, d, 0, ncap * sizeof(T) + PLAT_BLOB_PAD, zeroStream), "plat_memset");
         }
     }
-    void release(plat_ctx* ctx) {
-        if (!view) { if (h) plat_host_free(ctx, h); if (d) plat_free(ctx, d); }
-        h = nullptr; d = nullptr; hcap = dcap = n = 0;
-    }
 };
-typedef Staged<uint8_t> Arena;
+typedef Buffer<uint8_t> Arena;
+// Not owned: where one array of a stage lies in an arena's pinned and device blocks.  Only Layout points it there.
+template <class T> struct View { T* h = nullptr; T* d = nullptr; size_t n = 0; };
 
 // How a chunk's read table is read (planned per chunk: planReadPath, stage_a.hpp).  Bytes: t_seq / t_qual hold every base and quality (ASCII or mixed chunks,
 // or the byte scan asked for); Codes: ... and t_codes their 2-bit codes, which the candidate scan runs on; Packed: t_codes only -- letters and qualities
@@ -123,10 +125,13 @@ static inline int64_t firstPassBytes(ReadPath p, int64_t n) { return p == ReadPa
 static inline int64_t scanBytes(ReadPath p, int64_t n) { return p == ReadPath::Bytes ? n : n / 4; }
 
 struct SparePools;                                                         // window / Variant storage a worker keeps between the chunks of a call (defined behind WindowWork)
+// One worker's device context, stream and buffers.  Everything in it releases itself: adding a buffer is one declaration.
 struct Slot {
-    SparePools* spare = nullptr;                                           // (made by the worker's first chunk of a call, freed when its chunks run out)
-    plat_ctx* ctx = nullptr;
-    void* stream = nullptr;
+    // declared FIRST: members die in reverse order, so every Buffer below is freed while its context lives
+    struct Device { plat_ctx* ctx = nullptr; void* stream = nullptr; ~Device() { if (stream) plat_stream_destroy(ctx, stream); if (ctx) plat_ctx_destroy(ctx); } } dev;
+    plat_ctx*& ctx = dev.ctx; void*& stream = dev.stream;                  // (the names every stage uses)
+    std::unique_ptr<SparePools> spare;                                     // (made by the worker's first chunk of a call, freed when its chunks run out)
+    ~Slot();                                                               // (defined where SparePools is complete)
     bool countCells = false;                                               // plat_caller_count_cells: likelihood batches through the synchronous entry point
     int timeKernel = -1;                                                   // plat_caller_time_kernel: this kernel's launches are timed in the ordinary calls
     int64_t nDpRef = 0, cellsRef = 0, nDpRun = 0, cellsRun = 0;            // ... and their plat_align_stats summed (this worker's share)
@@ -137,53 +142,60 @@ struct Slot {
     int64_t ktLaunches[PLAT_KT_COUNT] = {};
     // chunk read table (device): bases, qualities, offsets, per-read fields, CIGARs; t_pack: the bytes of PLAT_READS_PACKED tables as
     // they crossed the link (expanded into t_seq / t_qual by plat_unpack_reads), t_exc*: their exceptions
-    Staged<uint8_t> t_seq, t_qual, t_mapq, t_pack, t_excb, t_excq;
-    Staged<int64_t> t_excidx;
-    Staged<plat_table_desc> t_desc;
-    Staged<plat_unpack_piece> t_pieces;
-    Staged<int64_t> t_off;
-    Staged<int32_t> t_pos, t_end, t_flags, t_cigoff, t_region;
+    Buffer<uint8_t> t_seq, t_qual, t_pack;
+    View<uint8_t> t_mapq, t_excb, t_excq;
+    View<int64_t> t_excidx, t_off;
+    View<plat_table_desc> t_desc;
+    View<plat_unpack_piece> t_pieces;
+    View<int32_t> t_pos, t_end, t_flags, t_cigoff, t_region;
     // packed bases read where they lie (a chunk of packed tables only, stage_a.hpp): no t_qual, t_seq holds only the read-side alleles the scan leaves
     // there; every kernel that starts from a read takes the read's packed bytes at t_src[read] (in the caller's resident table or in t_pack)
-    Staged<const uint8_t*> t_src;
-    Staged<plat_table_src_desc> t_sdesc;
+    View<const uint8_t*> t_src;
+    View<plat_table_src_desc> t_sdesc;
     ReadPath path = ReadPath::Bytes;                                       // how this chunk's table is read; Packed: ...
     plat_packed_reads pk = {};                                              // ... through these (t_src + the chunk's exceptions)
-    Staged<int16_t> t_cigar;
+    View<int16_t> t_cigar;
     // candidate scan
-    Staged<uint8_t> c_ref, c_refdev;
-    Staged<uint32_t> t_codes, c_refcodes;                                   // 2-bit base codes of the chunk's read blob / reference blob (the scan on codes, round 6)
-    Staged<int32_t> c_refirr;                                               // per scan: the reference window holds a byte other than A, C, G, T, N
-    Staged<plat_unpack_piece> c_pieces;
-    Staged<int64_t> c_refoff;
-    Staged<int32_t> c_rss, c_clen, c_rec, c_cnt, c_status, c_scanbegin, c_scanlongest, m_cand, m_n;
+    View<uint8_t> c_ref;
+    Buffer<uint8_t> c_refdev;
+    Buffer<uint32_t> t_codes, c_refcodes;                                   // 2-bit base codes of the chunk's read blob / reference blob (the scan on codes, round 6)
+    Buffer<int32_t> c_refirr;                                               // per scan: the reference window holds a byte other than A, C, G, T, N
+    View<plat_unpack_piece> c_pieces;
+    View<int64_t> c_refoff;
+    View<int32_t> c_rss, c_clen, c_rec, c_cnt, c_status, c_scanbegin, c_scanlongest, m_cand, m_n;
     // window batch
-    Staged<int32_t> w_hapbegin, w_readbegin, w_start, w_end, w_flank, w_segbegin, w_ngood, w_src, g_pos, g_end, g_flags, o_calls, o_iters, o_hapscore, o_score;
-    Staged<int64_t> w_pairoff, w_hapoff, w_readoff, w_gloff;
-    Staged<uint8_t> w_hapseq, w_kind, g_seq, g_qual, g_mapq;
-    Staged<double> o_loglik, o_gl, o_logl, o_gof, o_freq, o_em;
+    View<int32_t> w_hapbegin, w_readbegin, w_start, w_end, w_flank, w_segbegin, w_ngood, w_src, o_calls, o_hapscore;
+    View<int64_t> w_pairoff, w_hapoff, w_readoff, w_gloff;
+    View<uint8_t> w_hapseq, w_kind;
+    View<double> o_freq;
+    Buffer<int32_t> g_pos, g_end, g_flags, o_iters;
+    Buffer<uint8_t> g_seq, g_qual, g_mapq;
+    Buffer<double> o_loglik, o_gl, o_logl, o_gof, o_em;
     // posteriors / stats / calls
-    Staged<int32_t> p_win, s_vw, s_pos, s_min, s_max, s_nadd, s_nrem, s_gb, s_ge, s_bb, s_be, s_ps, s_minq, s_nminq, k_win, k_nvar, k_vih, k_ref, k_ph;
-    Staged<int64_t> p_off, s_aoff, s_moff, s_counts, k_vo, k_ro, k_lo;
-    Staged<uint8_t> p_mask, s_added, s_vig;
-    Staged<double> p_prior, p_post, k_lik, k_out4, s_terms;
-    Staged<int32_t> s_mmlq;
+    View<int32_t> p_win, s_vw, s_pos, s_min, s_max, s_nadd, s_nrem, s_gb, s_ge, s_bb, s_be, s_ps, s_minq, s_nminq, k_win, k_nvar, k_vih, k_ref, k_ph;
+    View<int64_t> p_off, s_aoff, s_moff, s_counts, k_vo, k_ro, k_lo;
+    View<uint8_t> p_mask, s_added, s_vig;
+    View<double> p_prior, k_lik, k_out4, s_terms;
+    Buffer<double> p_post;
+    View<int32_t> s_mmlq;
     bool infoOnDevice = false;                                            // this chunk's s_terms / s_mmlq are valid (plat_variant_info_batch)
     // assembler tiles (assemble=1)
-    Staged<uint8_t> as_ref, as_seq, as_qual, as_mapq, as_blob;
-    Staged<int64_t> as_refoff, as_roff;
-    Staged<int32_t> as_refstart, as_astart, as_aend, as_rbegin, as_src, as_pos, as_end, as_flags, as_cnt, as_status, as_vpos, as_nrem, as_nadd, as_off;
+    View<uint8_t> as_ref, as_blob;
+    Buffer<uint8_t> as_seq, as_qual, as_mapq;
+    View<int64_t> as_refoff, as_roff;
+    View<int32_t> as_refstart, as_astart, as_aend, as_rbegin, as_src, as_cnt, as_status, as_vpos, as_nrem, as_nadd, as_off;
+    Buffer<int32_t> as_pos, as_end, as_flags;
     // stage B on the device (plat_stage_b_batch): what it reads, what comes back, and the window batch it leaves on the device
-    Staged<int32_t> sb_rstart, sb_rend, sb_rlen, sb_tabbegin, sb_tabn, sb_tablongest, sb_matepos;
-    Staged<int32_t> sb_hdr, sb_vpos, sb_vnrem, sb_vnadd, sb_vsupp, sb_vbmin, sb_vbmax, sb_vrempos, sb_vaddoff, sb_wstart, sb_wend, sb_wvfirst, sb_wvn, sb_wflags,
-                    sb_wptrs, sb_wnhaps, sb_wbatch;
-    Staged<uint8_t> sb_added;
-    Staged<uint32_t> sb_hapmask;
-    Staged<int64_t> sb_totals, sb_namehash;
-    Staged<int32_t> d_hapbegin, d_readbegin, d_start, d_end, d_flank, d_segbegin, d_ngood, d_src, d_scratch;                 // device only
-    Staged<int64_t> d_pairoff, d_gloff, d_hapoff, d_readoff;
-    Staged<uint8_t> d_hapseq, d_kind;
-    // many small arrays travel as ONE copy: they are views into these blocks (Layout)
+    View<int32_t> sb_rstart, sb_rend, sb_rlen, sb_tabbegin, sb_tabn, sb_tablongest, sb_matepos;
+    View<int32_t> sb_hdr, sb_vpos, sb_vnrem, sb_vnadd, sb_vsupp, sb_vbmin, sb_vbmax, sb_vrempos, sb_vaddoff, sb_wstart, sb_wend, sb_wvfirst, sb_wvn, sb_wflags,
+                  sb_wptrs, sb_wnhaps, sb_wbatch;
+    View<uint8_t> sb_added;
+    View<uint32_t> sb_hapmask;
+    View<int64_t> sb_totals, sb_namehash;
+    Buffer<int32_t> d_hapbegin, d_readbegin, d_start, d_end, d_flank, d_segbegin, d_ngood, d_src, d_scratch;                 // device only
+    Buffer<int64_t> d_pairoff, d_gloff, d_hapoff, d_readoff;
+    Buffer<uint8_t> d_hapseq, d_kind;
+    // many small arrays travel as ONE copy: the Views above lie in these blocks (Layout)
     Arena a_tab, a_desc, a_cin, a_cout, a_mout, a_win, a_wout, a_pin, a_sin, a_sout, a_asin, a_asout, a_bin, a_bout;
     // per-region capacities of plat_stage_b_batch's outputs (they are downloaded whole): doubled when a region does not fit
     int sbCapV = 320, sbCapW = 192, sbCapA = 2048;
@@ -195,8 +207,7 @@ struct Slot {
         t_wait += secs(t0, Clock::now());
         ck(rc, where);
     }
-    template <class T> void up(Staged<T>& s, size_t n) { if (n) ck(plat_memcpy_h2d(ctx, s.d, s.h, n * sizeof(T), stream), "plat_memcpy_h2d"); }
-    template <class T> void down(Staged<T>& s, size_t n) { if (n) ck(plat_memcpy_d2h(ctx, s.h, s.d, n * sizeof(T), stream), "plat_memcpy_d2h"); }
+    template <class T> void down(Buffer<T>& s, size_t n) { if (n) ck(plat_memcpy_d2h(ctx, s.h, s.d, n * sizeof(T), stream), "plat_memcpy_d2h"); }
     // reads src[0 .. n) of the chunk table to the blobs at dstOff, with their per-read fields: from the expanded bytes, or from the packed ones
     void gatherReads(int64_t n, const int32_t* src, const int64_t* dstOff, uint8_t* seq, uint8_t* qual, int32_t* pos, int32_t* end, uint8_t* mapq, int32_t* flags,
                      const char* where) {
@@ -209,30 +220,35 @@ struct Slot {
 // Arrays of one stage laid out back to back in one pinned block + one device block: one copy per stage and direction instead of one per
 // array (a copy costs ~5 us of GPU time and as much host time however small it is).
 struct Layout {
-    struct Item { void** h; void** d; size_t bytes, off; };
+    struct Item { void** h; void** d; size_t bytes, off; const void* src; size_t n; void (*copy)(void* dst, const void* src, size_t n); };
     std::vector<Item> items;
     size_t total = 0;
-    template <class T> void add(Staged<T>& st, size_t n) {
-        st.view = true; st.n = n;
-        items.push_back(Item{(void**)&st.h, (void**)&st.d, (n + 8) * sizeof(T), 0});
+    // an array the host writes in place after commit (or the device writes)
+    template <class T> void add(View<T>& v, size_t n) {
+        v.n = n;
+        items.push_back(Item{(void**)&v.h, (void**)&v.d, (n + 8) * sizeof(T), 0, nullptr, 0, nullptr});
+    }
+    // an array that is a copy of `from` (a vector, element by element as T): commit copies it into place, and nothing reads `from` after that.  It must live until then
+    template <class T, class V> void put(View<T>& v, const V& from) {
+        add(v, from.size());
+        Item& it = items.back();
+        it.src = &from; it.n = from.size();
+        it.copy = [](void* dst, const void* src, size_t n) { const V& a = *(const V*)src; T* out = (T*)dst; for (size_t i = 0; i < n; ++i) out[i] = (T)a[i]; };
     }
     void commit(Slot& s, Arena& a) {
         total = 0;
         for (Item& it : items) { it.off = total; total += (it.bytes + 255) & ~(size_t)255; }
         a.reserve(s.ctx, total + PLAT_BLOB_PAD);
-        for (Item& it : items) { *it.h = a.h + it.off; *it.d = a.d + it.off; }
+        for (Item& it : items) {
+            *it.h = a.h + it.off; *it.d = a.d + it.off;
+            if (it.copy) it.copy(*it.h, it.src, it.n);
+        }
     }
-    void upload(Slot& s, Arena& a) { if (total) ck(plat_memcpy_h2d(s.ctx, a.d, a.h, total, s.stream), "plat_memcpy_h2d"); }
-    void uploadFirst(Slot& s, Arena& a, size_t nItems) {
-        const size_t bytes = nItems >= items.size() ? total : items[nItems].off;
-        if (bytes) ck(plat_memcpy_h2d(s.ctx, a.d, a.h, bytes, s.stream), "plat_memcpy_h2d");
-    }
-    // only the first `nItems` arrays (they lie in the order they were added)
-    void downloadFirst(Slot& s, Arena& a, size_t nItems) {
-        const size_t bytes = nItems >= items.size() ? total : items[nItems].off;
-        if (bytes) ck(plat_memcpy_d2h(s.ctx, a.h, a.d, bytes, s.stream), "plat_memcpy_d2h");
-    }
-    void download(Slot& s, Arena& a) { if (total) ck(plat_memcpy_d2h(s.ctx, a.h, a.d, total, s.stream), "plat_memcpy_d2h"); }
+    size_t firstBytes(size_t nItems) const { return nItems >= items.size() ? total : items[nItems].off; }     // of the first `nItems` arrays (they lie in the order they were added)
+    void upload(Slot& s, Arena& a) { uploadFirst(s, a, items.size()); }
+    void uploadFirst(Slot& s, Arena& a, size_t nItems) { if (firstBytes(nItems)) ck(plat_memcpy_h2d(s.ctx, a.d, a.h, firstBytes(nItems), s.stream), "plat_memcpy_h2d"); }
+    void download(Slot& s, Arena& a) { downloadFirst(s, a, items.size()); }
+    void downloadFirst(Slot& s, Arena& a, size_t nItems) { if (firstBytes(nItems)) ck(plat_memcpy_d2h(s.ctx, a.h, a.d, firstBytes(nItems), s.stream), "plat_memcpy_d2h"); }
 };
 
 // ---- a read table of the caller as the region loop sees it (ReadArray, cwindow.pyx:92-236) --------------------------------------
@@ -466,6 +482,7 @@ struct SparePools {
     std::vector<std::vector<WindowWork>> windows;
     std::vector<std::unique_ptr<Variant[]>> variants;
 };
+inline Slot::~Slot() = default;
 struct VariantPool {
     static constexpr size_t BLOCK = 64;
     std::vector<std::unique_ptr<Variant[]>> blocks;
@@ -589,12 +606,6 @@ struct BatchBuilder {
     int nReads() const { return (int)src.size(); }
 };
 
-template <class T, class V> static void fill(Slot& s, Staged<T>& st, const V& v, bool dev = true) {
-    if (!st.view) st.reserve(s.ctx, v.size() + 1, true, dev);
-    for (size_t i = 0; i < v.size(); ++i) st.h[i] = (T)v[i];
-    st.n = v.size();
-}
-
 struct DeviceBatch {                                                       // what stays valid on the device after runWindows
     plat_window_batch wb;
     int nWindows = 0, nHaps = 0, nReads = 0, nInd = 0, maxH = 0;
@@ -670,14 +681,11 @@ static DeviceBatch runWindows(Slot& s, const BatchBuilder& b, const Options& o, 
     if (db.nWindows == 0) return db;
     {
         Layout L;
-        L.add(s.w_hapbegin, b.hapbegin.size()); L.add(s.w_readbegin, b.readbegin.size()); L.add(s.w_start, b.start.size()); L.add(s.w_end, b.end.size());
-        L.add(s.w_flank, b.flank.size()); L.add(s.w_pairoff, b.pairoff.size()); L.add(s.w_hapoff, b.hapoff.size()); L.add(s.w_readoff, b.readoff.size());
-        L.add(s.w_gloff, b.gloff.size()); L.add(s.w_segbegin, b.segbegin.size()); L.add(s.w_ngood, b.ngood.size()); L.add(s.w_src, b.src.size());
-        L.add(s.w_kind, b.kind.size()); L.add(s.w_hapseq, b.hapseq.size() + PLAT_BLOB_PAD);
+        L.put(s.w_hapbegin, b.hapbegin); L.put(s.w_readbegin, b.readbegin); L.put(s.w_start, b.start); L.put(s.w_end, b.end);
+        L.put(s.w_flank, b.flank); L.put(s.w_pairoff, b.pairoff); L.put(s.w_hapoff, b.hapoff); L.put(s.w_readoff, b.readoff);
+        L.put(s.w_gloff, b.gloff); L.put(s.w_segbegin, b.segbegin); L.put(s.w_ngood, b.ngood); L.put(s.w_src, b.src);
+        L.put(s.w_kind, b.kind); L.add(s.w_hapseq, b.hapseq.size() + PLAT_BLOB_PAD);
         L.commit(s, s.a_win);
-        fill(s, s.w_hapbegin, b.hapbegin); fill(s, s.w_readbegin, b.readbegin); fill(s, s.w_start, b.start); fill(s, s.w_end, b.end);
-        fill(s, s.w_flank, b.flank); fill(s, s.w_pairoff, b.pairoff); fill(s, s.w_hapoff, b.hapoff); fill(s, s.w_readoff, b.readoff);
-        fill(s, s.w_gloff, b.gloff); fill(s, s.w_segbegin, b.segbegin); fill(s, s.w_ngood, b.ngood); fill(s, s.w_src, b.src); fill(s, s.w_kind, b.kind);
         memcpy(s.w_hapseq.h, b.hapseq.data(), b.hapseq.size());
         memset(s.w_hapseq.h + b.hapseq.size(), 0, PLAT_BLOB_PAD);
         L.upload(s, s.a_win);

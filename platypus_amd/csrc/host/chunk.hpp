@@ -133,9 +133,9 @@ struct Chunk {
 
     // window storage of the regions this worker has finished, for the regions of its next chunks (WindowList) -- in the worker's Slot; the worker
     // frees it when the call's chunks run out (region_caller.cpp: keeping it for the next call measured slower)
-    std::vector<std::vector<WindowWork>>& spareWindows() { if (!s.spare) s.spare = new SparePools(); return s.spare->windows; }
+    std::vector<std::vector<WindowWork>>& spareWindows() { if (!s.spare) s.spare.reset(new SparePools()); return s.spare->windows; }
 
-    std::vector<std::unique_ptr<Variant[]>>& spareVariants() { if (!s.spare) s.spare = new SparePools(); return s.spare->variants; }
+    std::vector<std::unique_ptr<Variant[]>>& spareVariants() { if (!s.spare) s.spare.reset(new SparePools()); return s.spare->variants; }
 
     void run() {
         // plat_caller_count_cells (the untimed counting pass of a measurement): one chunk at a time, so that the live kernel timers of its

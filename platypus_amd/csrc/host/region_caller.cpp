@@ -38,7 +38,53 @@
 
 using namespace plathost;
 
+// Large text blocks are kept for the next call instead of going back to the system: a whole genome's record text is ~0.8 GB, and a fresh
+// block of that size is 0.2 M first-touch page faults (or 400 huge ones) plus their release per call -- 30-60 ms of a 0.5 s pass.  At most
+// two blocks are kept (the caller typically still holds the previous call's text while the next is written), and only while a plat_caller
+// exists: the last one to be destroyed frees them.
+static std::mutex g_textMutex;
+static std::vector<std::pair<void*, size_t>> g_textLive, g_textSpare;     // (big blocks handed out; blocks given back and kept), with capacities
+static int g_callers = 0;                                                 // live plat_caller objects (under g_textMutex)
+static void countCaller(int by) {
+    std::lock_guard<std::mutex> g(g_textMutex);
+    if ((g_callers += by) > 0) return;
+    for (auto& b : g_textSpare) free(b.first);
+    g_textSpare.clear();
+}
+static void* takeSpareText(size_t bytes) {
+    std::lock_guard<std::mutex> g(g_textMutex);
+    for (size_t i = 0; i < g_textSpare.size(); ++i)
+        if (g_textSpare[i].second >= bytes && g_textSpare[i].second <= 2 * bytes + ((size_t)64 << 20)) {
+            const std::pair<void*, size_t> b = g_textSpare[i];
+            g_textSpare.erase(g_textSpare.begin() + (long)i);
+            g_textLive.push_back(b);
+            return b.first;
+        }
+    return nullptr;
+}
+CALLER_EXPORT void plat_caller_free(void* p) {
+    if (!p) return;
+    {
+        std::lock_guard<std::mutex> g(g_textMutex);
+        for (size_t i = 0; i < g_textLive.size(); ++i)
+            if (g_textLive[i].first == p) {
+                const std::pair<void*, size_t> b = g_textLive[i];
+                g_textLive.erase(g_textLive.begin() + (long)i);
+                if (g_callers == 0) break;                                  // (nobody left to use a spare: back to the system)
+                if (g_textSpare.size() < 2) { g_textSpare.push_back(b); return; }
+                // (two spares already: the smallest of the three goes back to the system)
+                size_t k = 0;
+                for (size_t j = 1; j < g_textSpare.size(); ++j) if (g_textSpare[j].second < g_textSpare[k].second) k = j;
+                if (g_textSpare[k].second < b.second) { p = g_textSpare[k].first; g_textSpare[k] = b; }
+                break;
+            }
+    }
+    free(p);
+}
+
 struct plat_caller {
+    plat_caller() { countCaller(+1); }
+    ~plat_caller() { countCaller(-1); }
     int device = 0, nWorkers = 1, regionsPerChunk = 4;
     bool countCells = false;
     int timeKernel = -1;                                                    // plat_caller_time_kernel
@@ -72,18 +118,12 @@ CALLER_EXPORT int plat_caller_create(int device, int n_workers, int regions_per_
         // a chunk's waits last milliseconds: the workers look at their events every 500 us instead of every 40 (measured on the whole-genome job,
         // 24 workers on 16 CPUs: 5.2 M windows/s at 40 us, 5.8 M at 250, 6.2 M at 500, 6.0 M at 1000, 5.5 M at 2000; PLAT_CALLER_POLL_US / PLAT_SYNC_POLL_US override)
         if (rc == PLAT_OK) { const char* e = getenv("PLAT_CALLER_POLL_US"); rc = plat_sync_poll_us(s->ctx, e && atoi(e) >= 0 ? atoi(e) : (c->regionsPerChunk >= 32 ? 500 : 100)); }
-        if (rc != PLAT_OK) {
-            if (s->ctx) plat_ctx_destroy(s->ctx);
-            for (auto& q : c->slots) { plat_stream_destroy(q->ctx, q->stream); plat_ctx_destroy(q->ctx); }
-            return rc;
-        }
+        if (rc != PLAT_OK) return rc;                                     // (this Slot and the ones made so far release themselves)
         c->slots.push_back(std::move(s));
     }
     *out = c.release();
     return PLAT_OK;
 }
-
-template <class... S> static void releaseAll(plat_ctx* ctx, S&... s) { (void)std::initializer_list<int>{(s.release(ctx), 0)...}; }
 
 CALLER_EXPORT int plat_caller_count_cells(plat_caller* c, int on) {
     if (!c) return PLAT_ERR_INVALID;
@@ -100,60 +140,11 @@ CALLER_EXPORT int plat_caller_time_kernel(plat_caller* c, int id) {
 
 CALLER_EXPORT int plat_caller_destroy(plat_caller* c) {
     if (!c) return PLAT_ERR_INVALID;
-    for (auto& q : c->slots) {
-        Slot& z = *q;
-        releaseAll(z.ctx, z.t_seq, z.t_qual, z.t_mapq, z.t_off, z.t_pos, z.t_end, z.t_flags, z.t_cigoff, z.t_region, z.t_cigar, z.c_ref, z.c_refoff, z.c_rss,
-                   z.c_clen, z.c_rec, z.c_cnt, z.c_status, z.w_hapbegin, z.w_readbegin, z.w_start, z.w_end, z.w_flank, z.w_segbegin, z.w_ngood, z.w_src, z.g_pos,
-                   z.g_end, z.g_flags, z.o_calls, z.o_iters, z.o_hapscore, z.o_score, z.w_pairoff, z.w_hapoff, z.w_readoff, z.w_gloff, z.w_hapseq, z.w_kind, z.g_seq,
-                   z.g_qual, z.g_mapq, z.o_loglik, z.o_gl, z.o_logl, z.o_gof, z.o_freq, z.o_em, z.p_win, z.s_vw, z.s_pos, z.s_min, z.s_max, z.s_nadd, z.s_nrem,
-                   z.s_gb, z.s_ge, z.s_bb, z.s_be, z.s_ps, z.s_minq, z.s_nminq, z.k_win, z.k_nvar, z.k_vih, z.k_ref, z.k_ph, z.p_off, z.s_aoff, z.s_moff, z.s_counts,
-                   z.k_vo, z.k_ro, z.k_lo, z.p_mask, z.s_added, z.s_vig, z.p_prior, z.p_post, z.k_lik, z.k_out4, z.t_pack, z.as_seq, z.as_qual, z.as_mapq, z.as_pos, z.as_end, z.as_flags, z.a_asin, z.a_asout, z.a_tab, z.a_cin, z.a_cout, z.a_mout, z.c_scanbegin, z.c_scanlongest, z.m_cand, z.m_n, z.a_win, z.a_wout,
-                   z.a_pin, z.a_sin, z.a_sout, z.a_bin, z.a_bout, z.a_desc, z.d_hapbegin, z.d_readbegin, z.d_start, z.d_end, z.d_flank, z.d_segbegin, z.d_ngood, z.d_src,
-                   z.d_scratch, z.d_pairoff, z.d_gloff, z.d_hapoff, z.d_readoff, z.d_hapseq, z.d_kind, z.c_refdev, z.t_codes, z.c_refcodes, z.c_refirr, z.t_src, z.t_sdesc);
-        plat_stream_destroy(z.ctx, z.stream);
-        plat_ctx_destroy(z.ctx);
-        delete z.spare; z.spare = nullptr;
-    }
-    delete c;
+    delete c;                                                              // (every Slot frees its buffers, then its stream and context: caller_common.hpp)
     return PLAT_OK;
 }
 
 CALLER_EXPORT const char* plat_caller_last_error(const plat_caller* c) { return c ? c->lastError.c_str() : ""; }
-// Large text blocks are kept for the next call instead of going back to the system: a whole genome's record text is ~0.8 GB, and a fresh
-// block of that size is 0.2 M first-touch page faults (or 400 huge ones) plus their release per call -- 30-60 ms of a 0.5 s pass.  At most
-// two blocks are kept (the caller typically still holds the previous call's text while the next is written).
-static std::mutex g_textMutex;
-static std::vector<std::pair<void*, size_t>> g_textLive, g_textSpare;     // (big blocks handed out; blocks given back and kept), with capacities
-static void* takeSpareText(size_t bytes) {
-    std::lock_guard<std::mutex> g(g_textMutex);
-    for (size_t i = 0; i < g_textSpare.size(); ++i)
-        if (g_textSpare[i].second >= bytes && g_textSpare[i].second <= 2 * bytes + ((size_t)64 << 20)) {
-            const std::pair<void*, size_t> b = g_textSpare[i];
-            g_textSpare.erase(g_textSpare.begin() + (long)i);
-            g_textLive.push_back(b);
-            return b.first;
-        }
-    return nullptr;
-}
-CALLER_EXPORT void plat_caller_free(void* p) {
-    if (!p) return;
-    {
-        std::lock_guard<std::mutex> g(g_textMutex);
-        for (size_t i = 0; i < g_textLive.size(); ++i)
-            if (g_textLive[i].first == p) {
-                const std::pair<void*, size_t> b = g_textLive[i];
-                g_textLive.erase(g_textLive.begin() + (long)i);
-                if (g_textSpare.size() < 2) { g_textSpare.push_back(b); return; }
-                // (two spares already: the smallest of the three goes back to the system)
-                size_t k = 0;
-                for (size_t j = 1; j < g_textSpare.size(); ++j) if (g_textSpare[j].second < g_textSpare[k].second) k = j;
-                if (g_textSpare[k].second < b.second) { p = g_textSpare[k].first; g_textSpare[k] = b; }
-                break;
-            }
-    }
-    free(p);
-}
-
 // ---- where the chunks of a call come from -----------------------------------------------------------------------------------------------
 // (a worker asks for its next chunk of regions, calls it, and hands it back)
 struct Feed {
@@ -341,7 +332,7 @@ static int runWorkers(plat_caller* c, Feed& feed, std::atomic<bool>& failed, con
         // every worker frees its own spare storage when it runs out of chunks.  Keeping it for the next CALL (PLAT_CALLER_KEEP_SPARE=1) measured SLOWER on the
         // whole-genome job: 5.8-6.1 M windows/s against 6.5-6.6 M, 0.207 against 0.172 ms of worker CPU per region -- the next call's worker is a new thread,
         // often on the other NUMA node, and inherits ten thousand cold windows; freeing them all on one thread at the end of the call: 5.0 M
-        if (!o.sw.keepSpare) { delete slot->spare; slot->spare = nullptr; }
+        if (!o.sw.keepSpare) slot->spare.reset();
     };
     nThreads = std::max(1, std::min<int>((int)c->slots.size(), nThreads));
     for (auto& q : c->slots) {
@@ -388,7 +379,7 @@ static void copyPieces(char* out, const std::vector<const char*>& from, const st
 }
 
 // a block for ~100 MB of text: 2 MB aligned and advised for huge pages (a fresh block's first-touch faults are then hundreds, not tens of
-// thousands); freed with free()
+// thousands).  Big blocks are tracked (g_textLive) and come back through plat_caller_free only, which keeps them as spares or frees them
 static char* allocText(size_t bytes) {
     const size_t big = (size_t)2 << 20;
     if (bytes < 4 * big) return (char*)malloc(bytes);

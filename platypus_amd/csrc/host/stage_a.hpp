@@ -219,11 +219,9 @@ inline void Chunk::scanCandidates() {
     {
         Layout L;
         scanbegin.push_back((int32_t)nGood);
-        L.add(z.c_refoff, refoff.size()); L.add(z.c_rss, rss.size()); L.add(z.c_clen, clen.size());
-        L.add(z.c_scanbegin, scanbegin.size()); L.add(z.c_scanlongest, scanlongest.size());
+        L.put(z.c_refoff, refoff); L.put(z.c_rss, rss); L.put(z.c_clen, clen); L.put(z.c_scanbegin, scanbegin); L.put(z.c_scanlongest, scanlongest);
         if (refResident) L.add(z.c_pieces, pieces.size() + 1); else L.add(z.c_ref, blobLen + PLAT_BLOB_PAD);
         L.commit(z, z.a_cin);
-        fill(z, z.c_refoff, refoff); fill(z, z.c_rss, rss); fill(z, z.c_clen, clen); fill(z, z.c_scanbegin, scanbegin); fill(z, z.c_scanlongest, scanlongest);
         if (refResident) {
             for (size_t q = 0; q < pieces.size(); ++q) z.c_pieces.h[q] = pieces[q];
             z.c_refdev.reserve(z.ctx, blobLen + PLAT_BLOB_PAD, false, true, z.stream);
@@ -397,12 +395,10 @@ inline void Chunk::assembleLaunch() {
     const int nT = (int)tiles.size();
     if (nT > 0) {
         Layout L;
-        L.add(z.as_ref, blob.size() + PLAT_BLOB_PAD); L.add(z.as_refoff, refoff.size()); L.add(z.as_refstart, refstart.size()); L.add(z.as_astart, astart.size());
-        L.add(z.as_aend, aend.size()); L.add(z.as_rbegin, rbegin.size()); L.add(z.as_src, src.size()); L.add(z.as_roff, roff.size());
+        L.add(z.as_ref, blob.size() + PLAT_BLOB_PAD); L.put(z.as_refoff, refoff); L.put(z.as_refstart, refstart); L.put(z.as_astart, astart);
+        L.put(z.as_aend, aend); L.put(z.as_rbegin, rbegin); L.put(z.as_src, src); L.put(z.as_roff, roff);
         L.commit(z, z.a_asin);
         memcpy(z.as_ref.h, blob.data(), blob.size()); memset(z.as_ref.h + blob.size(), 0, PLAT_BLOB_PAD);
-        fill(z, z.as_refoff, refoff); fill(z, z.as_refstart, refstart); fill(z, z.as_astart, astart); fill(z, z.as_aend, aend); fill(z, z.as_rbegin, rbegin);
-        fill(z, z.as_src, src); fill(z, z.as_roff, roff);
         L.upload(z, z.a_asin);
         const size_t nR = src.size(), nb = (size_t)roff.back();
         z.as_seq.reserve(z.ctx, nb + PLAT_BLOB_PAD, false, true, z.stream); z.as_qual.reserve(z.ctx, nb + PLAT_BLOB_PAD, false, true, z.stream);

@@ -47,9 +47,8 @@ inline void Chunk::callWindows(std::vector<WindowWork*>& wins, bool fromDevice) 
         nV = pwin.size();
         if (!nV) return;
         Layout L;
-        L.add(z.p_win, nV); L.add(z.p_off, nV + 1); L.add(z.p_mask, pmask.size()); L.add(z.p_prior, nV);
+        L.put(z.p_win, pwin); L.put(z.p_off, poff); L.put(z.p_mask, pmask); L.put(z.p_prior, pprior);       // (nV entries; nV + 1 in poff)
         L.commit(z, z.a_pin);
-        fill(z, z.p_win, pwin); fill(z, z.p_off, poff); fill(z, z.p_mask, pmask); fill(z, z.p_prior, pprior);
         z.p_post.reserve(z.ctx, nV + 1);
         L.upload(z, z.a_pin);
         ck(plat_variant_posterior_batch(z.ctx, (int)nV, nInd, dbb.maxH, dbb.hapbegin, dbb.gloff, dbb.ngood, z.o_gl.d, z.o_freq.d, z.p_win.d,
@@ -184,16 +183,13 @@ inline void Chunk::callWindows(std::vector<WindowWork*>& wins, bool fromDevice) 
     const size_t nSV = svw.size(), nSites = kwin.size();
     kvih.push_back(0);
     Layout L, LO;
-    L.add(z.s_vw, nSV); L.add(z.s_pos, nSV); L.add(z.s_min, nSV); L.add(z.s_max, nSV); L.add(z.s_nadd, nSV); L.add(z.s_nrem, nSV); L.add(z.s_aoff, nSV);
-    L.add(z.s_moff, nSV); L.add(z.s_vig, svig.size()); L.add(z.s_gb, sgb.size()); L.add(z.s_ge, sge.size()); L.add(z.s_bb, sbb.size()); L.add(z.s_be, sbe.size());
+    // (the loop above pushes them in step: nSV entries per array of a variant, nSites per array of a site, nSites + 1 in kvo / kro / klo)
+    L.put(z.s_vw, svw); L.put(z.s_pos, spos); L.put(z.s_min, smin); L.put(z.s_max, smax); L.put(z.s_nadd, snadd); L.put(z.s_nrem, snrem); L.put(z.s_aoff, saoff);
+    L.put(z.s_moff, smoff); L.put(z.s_vig, svig); L.put(z.s_gb, sgb); L.put(z.s_ge, sge); L.put(z.s_bb, sbb); L.put(z.s_be, sbe);
     L.add(z.s_added, sadded.size() + PLAT_BLOB_PAD);
-    L.add(z.k_win, nSites); L.add(z.k_nvar, nSites); L.add(z.k_vo, nSites + 1); L.add(z.k_ro, nSites + 1); L.add(z.k_lo, nSites + 1); L.add(z.k_ref, kref.size());
-    L.add(z.k_vih, kvih.size());
+    L.put(z.k_win, kwin); L.put(z.k_nvar, knvar); L.put(z.k_vo, kvo); L.put(z.k_ro, kro); L.put(z.k_lo, klo); L.put(z.k_ref, kref); L.put(z.k_vih, kvih);
     L.commit(z, z.a_sin);
-    fill(z, z.s_vw, svw); fill(z, z.s_pos, spos); fill(z, z.s_min, smin); fill(z, z.s_max, smax); fill(z, z.s_nadd, snadd); fill(z, z.s_nrem, snrem);
-    fill(z, z.s_aoff, saoff); fill(z, z.s_moff, smoff); fill(z, z.s_vig, svig); fill(z, z.s_gb, sgb); fill(z, z.s_ge, sge); fill(z, z.s_bb, sbb); fill(z, z.s_be, sbe);
     memcpy(z.s_added.h, sadded.data(), sadded.size()); memset(z.s_added.h + sadded.size(), 0, PLAT_BLOB_PAD);
-    fill(z, z.k_win, kwin); fill(z, z.k_nvar, knvar); fill(z, z.k_vo, kvo); fill(z, z.k_ro, kro); fill(z, z.k_lo, klo); fill(z, z.k_ref, kref); fill(z, z.k_vih, kvih);
     L.upload(z, z.a_sin);
     LO.add(z.s_counts, nSV * 16); LO.add(z.s_ps, nSV * (size_t)nInd * 2); LO.add(z.s_nminq, nSV); LO.add(z.s_minq, (size_t)mtot);
     LO.add(z.k_ph, nSites * (size_t)nInd * 2); LO.add(z.k_lik, (size_t)klo.back()); LO.add(z.k_out4, nSites * (size_t)nInd * 4);

@@ -61,7 +61,9 @@ API int plat_ctx_create(int device, plat_ctx** out) {
 API int plat_ctx_destroy(plat_ctx* c) { free(c); return PLAT_OK; }
 API int plat_last_hip_error(const plat_ctx* c) { (void)c; return 0; }
 API int plat_malloc(plat_ctx* c, size_t n, void** out) { (void)c; *out = calloc(n + 64, 1); return *out ? PLAT_OK : PLAT_ERR_NOMEM; }
-API int plat_free(plat_ctx* c, void* p) { (void)c; free(p); return PLAT_OK; }
+/* a release reads its context, as the device library does: one that comes after plat_ctx_destroy is a use after free a sanitizer sees */
+static void touch_ctx(const plat_ctx* c) { (void)*(const volatile int*)&c->sticky; }
+API int plat_free(plat_ctx* c, void* p) { touch_ctx(c); free(p); return PLAT_OK; }
 API int plat_host_alloc(plat_ctx* c, size_t n, void** out) { return plat_malloc(c, n, out); }
 API int plat_host_free(plat_ctx* c, void* p) { return plat_free(c, p); }
 API int plat_memcpy_h2d(plat_ctx* c, void* d, const void* s, size_t n, void* st) { (void)c; (void)st; if (n) memcpy(d, s, n); return PLAT_OK; }
@@ -69,7 +71,7 @@ API int plat_memcpy_d2d(plat_ctx* c, void* d, const void* s, size_t n, void* st)
 API int plat_memcpy_d2h(plat_ctx* c, void* d, const void* s, size_t n, void* st) { (void)c; (void)st; if (n) memcpy(d, s, n); return PLAT_OK; }
 API int plat_memset(plat_ctx* c, void* d, int v, size_t n, void* st) { (void)c; (void)st; if (n) memset(d, v, n); return PLAT_OK; }
 API int plat_stream_create(plat_ctx* c, void** out) { (void)c; *out = (void*)(uintptr_t)0x10; return PLAT_OK; }
-API int plat_stream_destroy(plat_ctx* c, void* s) { (void)c; (void)s; return PLAT_OK; }
+API int plat_stream_destroy(plat_ctx* c, void* s) { touch_ctx(c); (void)s; return PLAT_OK; }
 /* fault injection for the host-side error handling: PLAT_FAKE_FAIL_SYNC="<code>:<n>" makes the n-th plat_stream_sync of the process
  * (counted from 1, over all contexts) return <code> */
 static int g_sync_calls = 0;

@@ -389,3 +389,26 @@ def test_regions_resident_in_hbm_give_the_text_of_streamed_regions():
             src.close()
     assert texts[0] == texts[1] and texts[0].count("\n") > 100
     assert moved[0] > 12 * 20000 * 30 * 0.9 and moved[1] == 0
+
+
+def test_callers_made_and_destroyed_in_one_process_write_the_same_text():
+    """Three cycles of NativeCaller(0, 2, 2) ... close() in one process: a worker's buffers, stream and context release themselves (csrc/host/caller_common.hpp:
+    Slot), and the next caller starts from nothing.  Each cycle makes three calls over the same three regions: one sample packed (device stage B and the
+    packed read path: the sb_*, d_*, t_src and t_codes buffers the CPU stand-in never reserves), two samples ASCII (host stage B), one sample packed with
+    assemble=1.  Same text every cycle; no device-memory figure is looked at (the card is shared)."""
+    from platypus_amd import fastcaller as F
+    kw = dict(region_len=3000, snp_rate=3e-3, indel_rate=1e-3, read_len=100, depth=25)
+    one = [synth.config4_region_arrays(300 + i, **kw) for i in range(3)]
+    two = [synth.config4_region_arrays(300 + i, n_samples=2, **kw) for i in range(3)]
+    cycles = []
+    for _ in range(3):
+        nc = F.NativeCaller(0, 2, 2)
+        try:
+            texts = [nc.call_regions([F.region_from_arrays(r, packed=True) for r in one], ["S1"], default_options()),
+                     nc.call_regions([F.region_from_arrays(r) for r in two], ["S1", "S2"], default_options()),
+                     nc.call_regions([F.region_from_arrays(r, packed=True) for r in one], ["S1"], default_options(assemble=1))]
+        finally:
+            nc.close()
+        assert all(t.count("\n") > 20 for t in texts), [t.count("\n") for t in texts]
+        cycles.append(texts)
+    assert cycles[0] == cycles[1] == cycles[2]

@@ -366,6 +366,40 @@ def test_the_loaders_own_figures_for_its_tables(fake, monkeypatch):
         call(lie)
 
 
+def test_a_caller_leaves_nothing_behind(tmp_path):
+    """tests/caller_lifetime_driver.cpp: the whole native loop on the stand-in device as ONE program under AddressSanitizer, UBSan and LeakSanitizer (run as a
+    program: nothing loads it into python).  Four callers made, used and destroyed, twice over, then the text blocks: every case writes its records, the
+    second pass writes the first's text and leaves the heap where it found it, a block of more than 8 MB is gone with the last caller, and the
+    sanitizers have nothing to report -- not a buffer forgotten by a worker's teardown (a leak), not one freed after its context (the stand-in's
+    release calls read their context)."""
+    import os
+    import subprocess
+    from oracle import oracle as orc
+    orc.build()
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe, fake_o = str(tmp_path / "caller_lifetime_driver"), str(tmp_path / "fake_device.o")
+    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
+    subprocess.check_call(["gcc", "-std=c11", "-O1", "-g"] + san + ["-c", os.path.join(root, "tests", "fakedev", "fake_device.c"), "-o", fake_o])
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-mavx2", "-pthread", "-ffp-contract=off"] + san + ["-static-libasan",
+                           os.path.join(root, "tests", "caller_lifetime_driver.cpp"), os.path.join(root, "platypus_amd", "csrc", "host", "region_caller.cpp"),
+                           os.path.join(root, "tools", "synth", "region_source.cpp"), fake_o, "-L" + os.path.join(root, "oracle"), "-lorc",
+                           "-Wl,-rpath," + os.path.join(root, "oracle"), "-lm", "-o", exe])
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:verify_asan_link_order=0")     # (leaks are what this is about; the link order as in the drivers below)
+    out = subprocess.run([exe], env=env, capture_output=True, text=True)
+    print(out.stdout)
+    assert out.returncode == 0 and out.stderr == "", out.stderr[-3000:]
+    rows = {}
+    for line in out.stdout.splitlines():
+        head, fields = line.split(": ")
+        rows[head] = {k: int(v) for k, v in zip(fields.split()[0::2], fields.split()[1::2])}
+    assert len(rows) == 10
+    for k in (1, 2, 3, 4):
+        one, two = rows["case %d pass 1" % k], rows["case %d pass 2" % k]
+        assert one["lines"] == two["lines"] > 60 and min(one["held"], two["held"]) >= 8 << 20 and abs(two["left"]) <= 1024, (k, one, two)
+    for kind in ("records", "blocks"):                                      # plat_merge_record_texts, plat_merge_region_blocks
+        assert rows["text " + kind]["bytes"] > 8 << 20 and abs(rows["text " + kind]["left"]) <= 1024, rows["text " + kind]
+
+
 # What each PLAT_CALLER_* switch accepts, read off the parse at every site that called getenv before host/switches.hpp took them over (file:line
 # of commit 336c4c0, under platypus_amd/csrc/host/).  Per field: its value with the variable unset, "", "0", "1", "yes".
 _SET_AT_ALL = (0, 1, 1, 1, 1)                                               # getenv(...) != nullptr
