@@ -41,7 +41,7 @@ __device__ __forceinline__ int job_hap(const Job& j) { return j.hap & (JOB_BIGQ 
 //  bit2: quality sum above DP_SWAR_MAX_QSUM -> its DPs use the packed 16-bit adds)
 struct ReadInfo { uint32_t col, aux; int32_t pos; uint32_t lfm; };      // aux bits 0..15: number of bases with quality < LOWQ (the ungapped proof)
 constexpr unsigned LOWQ = 20u;
-enum { SHORTCUT_UNGAPPED = 1, SHORTCUT_EXACT = 2, SHORTCUT_NLOW = 4, SHORTCUT_BIGQ = 8, SEED_LEAN = 1024, SEED_XCD = 2048 };   // what k_pairs may finish without a DP (PLAT_NO_UNGAPPED / PLAT_NO_EXACT
+enum { SHORTCUT_UNGAPPED = 1, SHORTCUT_EXACT = 2, SHORTCUT_NLOW = 4, SHORTCUT_BIGQ = 8, SEED_LEAN = 1024, SEED_XCD = 2048, SEED_ONE_DIAG = 4096 };   // what k_pairs may finish without a DP (PLAT_NO_UNGAPPED / PLAT_NO_EXACT
                                                                          // switch them off; PLAT_NO_NLOW values unique windows by the smallest quality only)
 __device__ __forceinline__ long long job_slot(long long pair, long long npairs, int extra_base, int k) {
     return k == 0 ? pair : npairs + extra_base + (k - 1);
@@ -469,12 +469,24 @@ __device__ __forceinline__ unsigned kmer_head(const unsigned* table, unsigned co
 //   than once in this haplotype".
 // Every lane tries to PROVE that one diagonal d* is the unique arg-max of the reference's diagonal vote
 // (calign.pyx:206-233) without counting votes: the read's planes (<= 256 bp: 4 x 2 words in registers) are XORed
-// with the haplotype's planes shifted to the hypothesis diagonal; a shift-AND ladder marks every read position where 7
-// consecutive bases match = a k-mer that votes for d*;  C = popcount of those marks.  Votes for any OTHER diagonal are
-// at most  X = (#matching k-mers flagged nu) * (maxmult-1) + (#non-matching k-mers) * maxmult  (maxmult = largest
-// 7-mer multiplicity in the haplotype), so X < C  =>  d* is the only candidate of calign.pyx:222-233.
-// Hypothesis A = the read's mapping offset (calign.pyx:252); B = the diagonal of the read's first haplotype-unique k-mer.
-// Pairs that cannot be decided (tandem repeats, ties, reads longer than 256 bp) fall back to the exact vote: the whole
+// with the haplotype's planes shifted to a diagonal d; a shift-AND ladder marks every read position where 7
+// consecutive bases match.  M_d = those marks = the read k-mers that vote for d, so |M_d| is exactly d's count (on one
+// diagonal a k-mer votes at most once: d and i fix the haplotype position).  U_d = the marks of M_d whose haplotype k-mer
+// occurs ONCE in the haplotype (not flagged nu): such a k-mer votes for d and for nothing else.
+//   LEMMA.  For any set S of diagonals, every diagonal outside S has at most  nk - |union of U_d, d in S|  votes.
+// So the largest count of S is the vote's one arg-max when it beats the second largest of S and
+// best + |union of U| > nk.  A lane's S starts with hypothesis A, the read's mapping offset idx0 (calign.pyx:252), and
+// grows by the neighbour diagonals idx0 +- 1 .. SEED_NBR, nearest first (a read over an indel that one haplotype carries
+// matches on idx0 left of the site and on idx0 +- length right of it; a read right of an insertion lies on idx0 + length
+// whole) -- planes only, no index.  Lanes still open wait for their haplotype's k-mer index: hypothesis B = the diagonal
+// of the read's first haplotype-unique k-mer joins S when it lies further out, and the no-vote test's look-ups count the
+// read k-mers that occur nowhere in the haplotype, which vote for nothing and come off the bound as well.
+// The former rule (PLAT_SEED_ONE_DIAG=1, the A/B switch) proves A or B alone: votes off d* are at most
+// X = (#matching k-mers flagged nu) * (maxmult-1) + (#non-matching k-mers) * maxmult  (maxmult = largest 7-mer
+// multiplicity in the haplotype) and X < C proves d*; X < C implies C + |U_d*| > nk, so the Lemma loses none of its pairs.
+// The shortcuts that finish a pair without a DP (exact match, ungapped proof) stay with the pairs the former rule proves
+// on the proven diagonal; a pair only the Lemma proves leaves the DP jobs the exact vote would have left.
+// Pairs that cannot be decided (ties of the vote, tandem repeats, reads longer than 256 bp) fall back to the exact vote: the whole
 // wave counts that pair's diagonals in 16-bit LDS counters (two per dword, 32-bit LDS atomics; bit 15 = claim flag
 // that picks one representative lane per arg-max diagonal) and emits the candidates in ascending order.
 typedef unsigned long long u64;
@@ -845,6 +857,8 @@ __device__ __forceinline__ void seed_sweep(unsigned* table, unsigned short* nxt,
 // k_pairs packs the window's (haplotype, read) pairs DENSELY, 64 per wave whatever the number of reads, stages the <= SEED_NST haplotype
 // records its pairs touch in LDS and runs the proofs.  The k-mer index of a haplotype is built in k_pairs, and only when a pair needs
 // look-ups (hypothesis B, no-vote test).
+constexpr int SEED_NBR = 20;           // k_pairs: neighbour diagonals idx0 +- 1 .. SEED_NBR tried from the planes (the WGS job's indels are 1..10 bases, the
+                                       // tests' 1..20; 16 left the indels of 17..20 bases to the queue)
 constexpr int SEED_NST = 6;            // haplotype records staged per wave of k_pairs: 64 consecutive pairs of a window with R >= 13 reads
                                        // span at most 6 haplotypes; windows with fewer reads give a wave 5 whole haplotypes (5 R <= 60 pairs)
 __host__ __device__ __forceinline__ int seed_pairs_per_wave(int R) { return R >= 13 ? 64 : 5 * (R > 0 ? R : 1); }
@@ -989,10 +1003,68 @@ k_pairs(plat_window_batch b, const int32_t* __restrict__ wave_win, const int32_t
         int dstar = idx0;
         bool proven = false, triedB = false, exact = false, direct = false;
         unsigned tmask = 0u;
-        u64 missA[4] = {0ull, 0ull, 0ull, 0ull}, uniqA[4] = {0ull, 0ull, 0ull, 0ull};   // of hypothesis A, when it is proven (see "ungapped" below)
+        u64 missA[4] = {0ull, 0ull, 0ull, 0ull};         // of hypothesis A, when the former rule proves it (see "ungapped" below)
         bool provenA = false;
-        // pass 0: hypothesis A for every lane (planes only).  Pass s + 1: the lanes of staged haplotype s that A left open need k-mer
-        // look-ups -- that haplotype's index is built (the wave's one index area), hypothesis B is tried, then the no-vote test.
+        const bool onediag = (shortcuts & SEED_ONE_DIAG) != 0;   // PLAT_SEED_ONE_DIAG=1: the former rule, X < C on the hypothesis alone
+        // The lane's tried set S (the Lemma above): the union of the U_d, the largest count, its diagonal, the second largest count.
+        // (A lane that A proves never adds to S: its orU stays U of idx0, which is what the ungapped proof reads.)
+        u64 orU[4] = {0ull, 0ull, 0ull, 0ull};
+        int best = -1, bestd = -1, second = -1;
+        // One diagonal d of a lane that is `on`: C = |M_d|, the marks U7 = U_d, the former bound's verdict X < C, the bases that differ.
+        auto diagonal = [&](int d, bool on, int& C, bool& oldrule, u64 (&U7)[4], u64 (&missw)[4]) {
+            const int wq = on ? (d >> 6) : 0, sb = d & 63;
+            const int nvalid = min(nk, nkp - d);                     // k-mers i < nvalid lie on haplotype positions
+            u64 Z[5], NU[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                if (c < nCmax) {
+                    const u64 x = (funnel(h0[wq + c], h0[wq + c + 1], sb) ^ r0[c]) | (funnel(h1[wq + c], h1[wq + c + 1], sb) ^ r1[c]);
+                    Z[c] = ~x;
+                    NU[c] = funnel(nup[wq + c], nup[wq + c + 1], sb);
+                } else { Z[c] = 0ull; NU[c] = 0ull; }
+            }
+            Z[4] = 0ull;
+            u64 P2[5];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) P2[c] = Z[c] & ((Z[c] >> 1) | (Z[c + 1] << 63));
+            P2[4] = 0ull;
+            int NUc = 0;
+            C = 0;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                U7[c] = 0ull;                            // k-mer i of the read equals the haplotype's at d+i AND that k-mer is unique in the haplotype
+                if (c < nCmax) {
+                    const u64 P4 = P2[c] & ((P2[c] >> 2) | (P2[c + 1] << 62));
+                    u64 P7 = P4 & ((P2[c] >> 4) | (P2[c + 1] << 60)) & ((Z[c] >> 6) | (Z[c + 1] << 58));
+                    const int nb = nvalid - 64 * c;
+                    const u64 msk = nb >= 64 ? ~0ull : (nb <= 0 ? 0ull : ((1ull << nb) - 1ull));
+                    P7 &= msk;
+                    C += __popcll(P7);
+                    NUc += __popcll(P7 & NU[c]);
+                    U7[c] = P7 & ~NU[c];
+                }
+                // does the whole read match the haplotype on d?  (Z: one bit per base, 1 = equal codes)
+                const int nl = L - 64 * c;
+                missw[c] = ~Z[c] & (nl >= 64 ? ~0ull : (nl <= 0 ? 0ull : ((1ull << nl) - 1ull)));
+            }
+            oldrule = NUc * (maxmult - 1) + (nk - C) * maxmult < C;
+        };
+        // d joins S; then: is the largest count of S alone at the top, and above what any diagonal outside S can still get?
+        auto join = [&](int d, bool on, int C, const u64 (&U7)[4]) -> bool {
+            if (on) {
+#pragma unroll
+                for (int c = 0; c < 4; ++c) orU[c] |= U7[c];
+                if (C > best) { second = best; best = C; bestd = d; }
+                else second = max(second, C);
+            }
+            int nu = 0;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) nu += __popcll(orU[c]);
+            return on && best > second && best + nu > nk;
+        };
+        // pass 0: hypothesis A for every lane, then its neighbour diagonals for the lanes A left open (planes only).  Pass s + 1: the lanes
+        // of staged haplotype s that are still open need k-mer look-ups -- that haplotype's index is built (the wave's one index area),
+        // hypothesis B is tried, then the no-vote test.
         bool novote = false;
         for (int pass = 0; pass <= nst; ++pass) {
             const int attempt = pass == 0 ? 0 : 1;
@@ -1010,14 +1082,15 @@ k_pairs(plat_window_batch b, const int32_t* __restrict__ wave_win, const int32_t
                 tmask = (unsigned)tsize - 1u;
                 u64* p0 = (u64*)(recs + 16);
                 seed_build_index(table, nxt, p0, p0 + nw64, p0 + 2 * nw64, (int*)recs, hapLenS, (hapLenS + 63) >> 6, direct, tsize, tmask, false);
-                // hypothesis B for the lanes A could not prove: diagonal of the first haplotype-unique k-mer
+                // hypothesis B for the lanes still open: diagonal of the first haplotype-unique k-mer (an open lane has every diagonal
+                // within SEED_NBR of idx0 in S already)
                 triedB = false;
                 if (mine && canfast) {
                     for (int i = 0; i < nk; ++i) {
                         const unsigned hd = kmer_head(table, read_code(col, R, i), direct, tmask);
                         if (hd != 0u && nxt[hd] == 0u) {
                             const int d = (int)hd - i - 1;
-                            if (d != idx0 && d >= 0) { dstar = d; triedB = true; }
+                            if (d != idx0 && d >= 0 && (onediag || abs(d - idx0) > SEED_NBR)) { dstar = d; triedB = true; }
                             break;
                         }
                     }
@@ -1025,60 +1098,63 @@ k_pairs(plat_window_batch b, const int32_t* __restrict__ wave_win, const int32_t
             }
             const bool run = canfast && !proven && dstar >= 0 && (pass == 0 || triedB);
             if (__any(run)) {
-                const int wq = run ? (dstar >> 6) : 0, sb = dstar & 63;
-                const int nvalid = min(nk, nkp - dstar);                 // k-mers i < nvalid lie on haplotype positions
-                u64 Z[5], NU[4];
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    if (c < nCmax) {
-                        const u64 x = (funnel(h0[wq + c], h0[wq + c + 1], sb) ^ r0[c]) | (funnel(h1[wq + c], h1[wq + c + 1], sb) ^ r1[c]);
-                        Z[c] = ~x;
-                        NU[c] = funnel(nup[wq + c], nup[wq + c + 1], sb);
-                    } else { Z[c] = 0ull; NU[c] = 0ull; }
-                }
-                Z[4] = 0ull;
-                u64 P2[5];
-#pragma unroll
-                for (int c = 0; c < 4; ++c) P2[c] = Z[c] & ((Z[c] >> 1) | (Z[c + 1] << 63));
-                P2[4] = 0ull;
-                int C = 0, NUc = 0;
-                u64 U7[4];                               // k-mer i of the read equals the haplotype's at d*+i AND that k-mer is unique in the haplotype
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    U7[c] = 0ull;
-                    if (c < nCmax) {
-                        const u64 P4 = P2[c] & ((P2[c] >> 2) | (P2[c + 1] << 62));
-                        u64 P7 = P4 & ((P2[c] >> 4) | (P2[c + 1] << 60)) & ((Z[c] >> 6) | (Z[c + 1] << 58));
-                        const int nb = nvalid - 64 * c;
-                        const u64 msk = nb >= 64 ? ~0ull : (nb <= 0 ? 0ull : ((1ull << nb) - 1ull));
-                        P7 &= msk;
-                        C += __popcll(P7);
-                        NUc += __popcll(P7 & NU[c]);
-                        U7[c] = P7 & ~NU[c];
-                    }
-                }
-                const int X = NUc * (maxmult - 1) + (nk - C) * maxmult;
-                if (run && X < C) {
+                int C;
+                bool oldrule;
+                u64 U7[4], missw[4];
+                diagonal(dstar, run, C, oldrule, U7, missw);
+                const bool ok = onediag ? (run && oldrule) : join(dstar, run, C, U7);
+                if (ok) {
                     proven = true;
-                    // does the whole read match the haplotype on d*?  (Z: one bit per base, 1 = equal codes)
+                    // The pairs the former rule proves keep their shortcuts (exact match, ungapped proof); a pair only the Lemma proves
+                    // leaves the DP jobs the exact vote would have left, so the number of DPs run does not depend on the rule.
+                    const bool here = onediag || bestd == dstar;
+                    if (!onediag) dstar = bestd;
                     u64 miss = 0ull;
 #pragma unroll
                     for (int c = 0; c < 4; ++c) {
-                        const int nb = L - 64 * c;
-                        const u64 mc = ~Z[c] & (nb >= 64 ? ~0ull : (nb <= 0 ? 0ull : ((1ull << nb) - 1ull)));
-                        miss |= mc;
-                        if (attempt == 0) { missA[c] = mc; uniqA[c] = U7[c]; }
+                        miss |= missw[c];
+                        if (attempt == 0 && oldrule) { missA[c] = missw[c]; if (onediag) orU[c] = U7[c]; }
                     }
-                    exact = miss == 0ull;
-                    provenA = attempt == 0;
+                    exact = here && oldrule && miss == 0ull;
+                    provenA = attempt == 0 && oldrule;
+                }
+            }
+            // the neighbour diagonals idx0 +- 1 .. SEED_NBR of the lanes A left open, nearest first, until no lane of the wave is open
+            if (pass == 0 && !onediag) {
+                for (int t = 0; t < 2 * SEED_NBR; ++t) {
+                    const bool open = canfast && !proven;
+                    if (!__any(open)) break;
+                    const int delta = (t >> 1) + 1, d = (t & 1) ? idx0 - delta : idx0 + delta;
+                    const bool on = open && d >= 0;
+                    if (!__any(on)) continue;
+                    int C;
+                    bool oldrule;
+                    u64 U7[4], missw[4];
+                    diagonal(on ? d : 0, on, C, oldrule, U7, missw);
+                    if (join(d, on, C, U7)) {
+                        proven = true;
+                        dstar = bestd;
+                        const u64 miss = missw[0] | missw[1] | missw[2] | missw[3];
+                        exact = bestd == d && oldrule && miss == 0ull;
+                    }
                 }
             }
             // no k-mer of the read occurs in the haplotype <=> maxcount == 0 (calign.pyx:222): decided, no candidate.
             // (tested only for pairs the proof left open)
+            // The same look-ups, counted: a read k-mer that occurs nowhere in the haplotype votes for no diagonal, so a diagonal outside
+            // S gets at most nk - |union of U| - absent votes (short reads with a long insertion: its k-mers match nothing).
             if (pass > 0 && mine && !proven) {
+                const bool count = canfast && !onediag && best > second;
+                int absent = 0;
                 novote = true;
-                for (int i = 0; i < nk && novote; ++i)
+                for (int i = 0; i < nk && (novote || count); ++i) {
                     if (kmer_head(table, read_code(col, R, i), direct, tmask) != 0u) novote = false;
+                    else ++absent;
+                }
+                int nu = 0;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) nu += __popcll(orU[c]);
+                if (count && !novote && best + nu + absent > nk) { proven = true; dstar = bestd; exact = false; }
             }
             if (pass == 0 && !__any(live && !proven)) break;
         }
@@ -1141,11 +1217,11 @@ k_pairs(plat_window_batch b, const int32_t* __restrict__ wave_win, const int32_t
             if (kmw > 0) {
                 int cw[4];
 #pragma unroll
-                for (int c = 0; c < 4; ++c) cw[c] = __popcll(uniqA[c]);
+                for (int c = 0; c < 4; ++c) cw[c] = __popcll(orU[c]);
                 auto Cpre = [&](int x) -> int {              // unique-matching k-mer starts in [0, x)
                     x = min(max(x, 0), 256);
                     const int wi = x >> 6, sh = x & 63;
-                    const u64 wsel = wi == 0 ? uniqA[0] : wi == 1 ? uniqA[1] : wi == 2 ? uniqA[2] : wi == 3 ? uniqA[3] : 0ull;
+                    const u64 wsel = wi == 0 ? orU[0] : wi == 1 ? orU[1] : wi == 2 ? orU[2] : wi == 3 ? orU[3] : 0ull;
                     const int below = (wi > 0 ? cw[0] : 0) + (wi > 1 ? cw[1] : 0) + (wi > 2 ? cw[2] : 0) + (wi > 3 ? cw[3] : 0);
                     return below + __popcll(wsel & ((1ull << sh) - 1ull));
                 };
@@ -1310,8 +1386,9 @@ k_pairs(plat_window_batch b, const int32_t* __restrict__ wave_win, const int32_t
 
 __device__ __forceinline__ void wave_lds_sync() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); }
 
-// k_seed_slow: the exact vote for the pairs the seeding kernels queued (a few hundred per launch on config 2, ~11 k per launch of the WGS
-// job: every read over a tandem repeat, for every haplotype of its window).  Round 6: a workgroup is SLOW_WAVES waves and takes groups of
+// k_seed_slow: the exact vote for the pairs the seeding kernels queued (a few hundred per launch on config 2; ~11 k per launch of the WGS
+// job while k_pairs proved one diagonal alone -- its genome is uniformly random, and the queue held the reads over an indel that one
+// haplotype of the window carries, not reads over tandem repeats; profiles/r13_seed_neighbours.md has the count since).  Round 6: a workgroup is SLOW_WAVES waves and takes groups of
 // SLOW_GROUP consecutive queue entries (the entries one seeding wave queued are consecutive and mostly share their haplotype).  Inside a
 // group every run of entries of one haplotype costs ONE index build, made by all the threads together (measured: a build by one wave is 18
 // of the 27 us a pair cost -- linear probing at load 0.65, the slowest of 64 lanes sets each round's time); its waves then vote for one entry
@@ -1956,7 +2033,8 @@ static int align_impl(plat_ctx* ctx, const plat_window_batch* batch, const plat_
         // PLAT_NO_UNGAPPED=1 sends every such pair through the DP instead (cross-check in tests/test_gpu_parity.py)
         // PLAT_NO_EXACT=1: every reference DP is then run (bench.py's gcups_all_dp); sw.seedDebug is 0 or 512, k_pairs' reason counters
         const int shortcuts = ((!calc_flank_score && !sw.noUngapped) ? SHORTCUT_UNGAPPED : 0) | (sw.noExact ? 0 : SHORTCUT_EXACT) |
-                              (sw.noNlow ? 0 : SHORTCUT_NLOW) | (sw.ungappedBigq ? SHORTCUT_BIGQ : 0) | sw.seedDebug | (async ? SEED_LEAN : 0);
+                              (sw.noNlow ? 0 : SHORTCUT_NLOW) | (sw.ungappedBigq ? SHORTCUT_BIGQ : 0) | sw.seedDebug | (async ? SEED_LEAN : 0) |
+                              (sw.seedOneDiag ? SEED_ONE_DIAG : 0);
         // the dense list of live job slots is built by the seeding kernels themselves (DENSE_SEGS segments, each able to hold every slot)
         const long long segcap = npairs + extra_cap;
         if ((rc = plat_reserve(ctx, ctx->dense, ((size_t)segcap * DENSE_SEGS + 64) * sizeof(int32_t)))) return rc;

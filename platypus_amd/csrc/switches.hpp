@@ -14,6 +14,7 @@
 //   PLAT_NO_NLOW           begins with '1'                  the ungapped proof counts every base as a low-quality one         tests, measurements          per call
 //   PLAT_UNGAPPED_BIGQ     begins with '1'                  the ungapped proof takes reads of the wrap regime too             tools/ungapped_crosscheck.py per call
 //   PLAT_SEED_XCD          not beginning '0'                the waves of a window / haplotype on one XCD ("0": w on wg w)     measurements                 per call
+//   PLAT_SEED_ONE_DIAG     begins with '1'                  k_pairs proves on one diagonal by X < C, no neighbour pass (A/B)  tests, measurements          per call
 //   PLAT_SLOW_GROUP        1..SLOW_GROUP, else 8            k_seed_slow: queue entries per workgroup round                    measurements                 per call
 //   PLAT_SLOW_WAVES        1..SLOW_WAVES, else SLOW_WAVES   k_seed_slow: waves per workgroup (before the LDS rule halves it)  measurements                 per call
 //   PLAT_SLOW_TIMING       set at all                       k_seed_slow's ticks per phase on stderr (waits for the stream)    measurements                 per call
@@ -50,7 +51,7 @@ inline int number(const char* name, int unset) { const char* e = getenv(name); r
 }  // namespace env
 
 struct AlignSwitches {
-    bool noUngapped = false, noExact = false, noNlow = false, ungappedBigq = false, seedXcd = true, slowTiming = false;
+    bool noUngapped = false, noExact = false, noNlow = false, ungappedBigq = false, seedXcd = true, slowTiming = false, seedOneDiag = false;
     int slowGroup = 8, slowWaves = SLOW_WAVES, seedDebug = 0, dpGridPerCu = 8;
 
     static AlignSwitches read() {
@@ -61,6 +62,7 @@ struct AlignSwitches {
         w.ungappedBigq = env::isOne("PLAT_UNGAPPED_BIGQ");
         w.seedXcd = env::notZero("PLAT_SEED_XCD");
         w.slowTiming = env::isSet("PLAT_SLOW_TIMING");
+        w.seedOneDiag = env::isOne("PLAT_SEED_ONE_DIAG");
         { const int v = env::number("PLAT_SLOW_GROUP", 0); if (v > 0 && v <= SLOW_GROUP) w.slowGroup = v; }
         { const int v = env::number("PLAT_SLOW_WAVES", 0); if (v > 0 && v <= SLOW_WAVES) w.slowWaves = v; }
         w.seedDebug = env::number("PLAT_SEED_DEBUG", 0) & 0x200;
