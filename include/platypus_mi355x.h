@@ -331,7 +331,8 @@ int plat_candidates_batch(plat_ctx* ctx, const plat_candidate_batch* batch, int 
                           int gen_snps, int gen_indels, int max_per_read, const int32_t* read_region,
                           int32_t* out_rec, int32_t* out_count, int32_t* out_status, void* stream);
 
-/* The dictionary step behind the scan and the per-sample support filter, on the device:
+/* The dictionary step behind the scan and the per-sample support filter, on the device (one kernel, one workgroup per scan, the scan's
+ * dictionary in LDS; the context keeps the first-record ids of every scan's distinct records for plat_stage_b_batch, written in full by every call):
  * Replaces  VariantCandidateGenerator.addVariantToList (variant.pyx:499-527: equal records merge, supporting reads count) and
  *           `computeVariantReadSupportFrac(v, buffer) >= minVarFreq or v.nAdded != v.nRemoved`  (variantcaller.pyx:456-467,
  *           variantFilter.pyx:359-373 over ReadArray.countReadsCoveringRegion, cwindow.pyx:176-206)

@@ -497,114 +497,286 @@ PLAT_EXPORT int plat_candidates_batch(plat_ctx* ctx, const plat_candidate_batch*
 // ------------------------------------------------------------------------------------------------
 // The dictionary step behind the scan (VariantCandidateGenerator.addVariantToList, variant.pyx:499-527) and the per-sample support
 // filter of generateVariantsInRegion (variantcaller.pyx:456-467) for every scan (= region x sample) of a candidate batch.
-// k_candidates_merge: ONE THREAD PER READ puts the read's records into the scan's hash table in global memory (atomics in L2) -- slot =
-// the record with the smallest id among those of equal content (first occurrence: the reference's dictionary order) + the number of reads
-// showing it.  (Round 2 kept the table in LDS, one workgroup per scan: twenty reads per thread one after the other, each a chain of
-// dependent loads -- 140 us for four scans of 20 000 reads, the longest kernel of the region pipeline.)
-// k_candidates_filter: per distinct record, the reads covering its position (ReadArray.countReadsCoveringRegion, cwindow.pyx:176-206)
-// and the filter.
+// k_candidates_merge: ONE WORKGROUP PER SCAN, the scan's hash table in LDS, four phases.
+//   collect  the workgroup strides over the scan's reads (count[] and status[] coalesced, MERGE_READS loads in flight per thread) and
+//            lists the ids of their records in a queue in LDS: a block scan over the counts gives every record its place, so a scan with
+//            more records than the queue holds is worked off in rounds of MERGE_QUEUE records -- whatever its reads hold.
+//   insert   threads stride over the queue, two records each per trip (the second record's loads are issued before the first is used):
+//            slot = hash << 32 | id + 1 of the record with the smallest id among those of equal content (first occurrence: the reference's
+//            dictionary order) + the number of reads showing it.  The hash beside the id means another record's words and bytes are
+//            loaded only where it probably is the same one.
+//   filter   the occupied slots, compacted in slot order; per distinct record the reads covering its position
+//            (ReadArray.countReadsCoveringRegion, cwindow.pyx:176-206: both lower bounds bisected in lock-step, MERGE_LANES records of a
+//            thread in flight together) and the support filter.
+//   out      the counts, the status and the rep + 1 half of the scan's table (EVERY slot: what k_sb_variants' replay reads, so no memset
+//            runs in front of this kernel).
+// (Round 2 kept the table in LDS as well, but gave each thread twenty READS one after the other, each a chain of dependent loads: 140 us
+//  for four scans.  Rounds 3-13 had the table in global memory, a thread per read and a second kernel, a thread per slot, for the filter.)
 namespace plat {
-constexpr int MERGE_SLOTS = 8192, MERGE_LIMIT = 6144, MERGE_PROBES = 1024;
-// per scan: rep + 1 [MERGE_SLOTS] (0 = empty) | count [MERGE_SLOTS]; after the tables of all scans, 4 words per scan: distinct, status, need, -
-__device__ __forceinline__ int32_t* merge_flags(int32_t* mtab, int n_scans, int g) { return mtab + (size_t)n_scans * 2 * MERGE_SLOTS + 4 * (size_t)g; }
+constexpr int MERGE_SLOTS = 8192, MERGE_LIMIT = 6144;
+constexpr int MERGE_THREADS = 1024;               // (1024 against 512: profiles/r14_merge_lds.md)
+constexpr int MERGE_QUEUE = 8192;                 // record ids per round of collect + insert
+constexpr int MERGE_READS = 4;                    // reads per thread and trip of the collect phase
+constexpr int MERGE_LANES = 4;                    // distinct records of a thread whose searches run together in the filter phase
+static_assert(MERGE_QUEUE >= MERGE_LIMIT, "the filter phase lists the occupied slots in the queue");
+static_assert(MERGE_SLOTS % (4 * MERGE_THREADS) == 0, "a thread writes its slots of the table four at a time");
 
-__device__ __forceinline__ bool rec_same(const plat_candidate_batch& b, const int32_t* x, const int32_t* y) {
+struct MergeLds {
+    unsigned long long tab[MERGE_SLOTS];          // hash << 32 | rep + 1; 0 = empty
+    int32_t cnt[MERGE_SLOTS];
+    int32_t queue[MERGE_QUEUE];
+    int32_t wsum[MERGE_THREADS / 64];
+    int32_t distinct, full, bad, need, n_out, st_out;
+};
+
+// exclusive prefix of v over the workgroup's threads and the total; every thread calls it
+__device__ __forceinline__ int merge_block_scan(int v, int32_t* wsum, int& total) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    int inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(inc, d, 64); if (lane >= d) inc += t; }
+    if (lane == 63) wsum[wv] = inc;
+    __syncthreads();
+    int off = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < MERGE_THREADS / 64; ++w) { const int s = wsum[w]; if (w < wv) off += s; tot += s; }
+    __syncthreads();
+    total = tot;
+    return off + inc - v;
+}
+
+__device__ __forceinline__ void merge_load(const int32_t* __restrict__ rec, int id, int32_t* w) {
+    const int32_t* me = rec + 5ll * id;
+#pragma unroll
+    for (int i = 0; i < 5; ++i) w[i] = me[i];
+}
+
+// fr / fa: the first removed / added byte, loaded by the caller (together with another record's)
+__device__ __forceinline__ unsigned merge_hash(const uint8_t* __restrict__ ref_seq, const uint8_t* __restrict__ read_seq, const int32_t* w, unsigned fr, unsigned fa) {
+    unsigned h = (unsigned)w[0] * 2654435761u + (unsigned)w[1] * 40503u + (unsigned)w[2] * 97u;
+    if (w[1] > 0) { h = h * 31u + fr; for (int i = 1; i < w[1]; ++i) h = h * 31u + ref_seq[(long long)w[3] + i]; }
+    if (w[2] > 0) { h = h * 37u + fa; for (int i = 1; i < w[2]; ++i) h = h * 37u + read_seq[(long long)w[4] + i]; }
+    return h;
+}
+
+__device__ __forceinline__ bool rec_same(const uint8_t* __restrict__ ref_seq, const uint8_t* __restrict__ read_seq, const int32_t* x, const int32_t* y) {
     if (x[0] != y[0] || x[1] != y[1] || x[2] != y[2]) return false;
-    for (int i = 0; i < x[1]; ++i) if (b.ref_seq[(long long)x[3] + i] != b.ref_seq[(long long)y[3] + i]) return false;
-    for (int i = 0; i < x[2]; ++i) if (b.read_seq[(long long)x[4] + i] != b.read_seq[(long long)y[4] + i]) return false;
+    for (int i = 0; i < x[1]; ++i) if (ref_seq[(long long)x[3] + i] != ref_seq[(long long)y[3] + i]) return false;
+    for (int i = 0; i < x[2]; ++i) if (read_seq[(long long)x[4] + i] != read_seq[(long long)y[4] + i]) return false;
     return true;
 }
 
-__global__ void __launch_bounds__(256)
-k_candidates_merge(plat_candidate_batch b, const int32_t* __restrict__ scan_read_begin, int n_scans, int max_per_read,
-                   const int32_t* __restrict__ rec, const int32_t* __restrict__ count, const int32_t* __restrict__ status,
-                   int32_t* __restrict__ mtab, int32_t* __restrict__ out_n)
+// record `id` (words w, hash h) into the table; -> 1 where it is the first of its content.  A probe that comes round (the table is full:
+// MERGE_SLOTS > MERGE_LIMIT distinct records) raises L.full, and nothing more is inserted.
+__device__ __forceinline__ int merge_probe(MergeLds& L, const uint8_t* __restrict__ ref_seq, const uint8_t* __restrict__ read_seq, const int32_t* __restrict__ rec,
+                                           int id, const int32_t* w, unsigned h)
 {
-    const int g = blockIdx.y;
-    const int r0 = scan_read_begin[g], N = scan_read_begin[g + 1] - r0;
-    int32_t* tab = mtab + (size_t)g * 2 * MERGE_SLOTS;
-    int32_t* flags = merge_flags(mtab, n_scans, g);
-    if (blockIdx.x == 0 && threadIdx.x == 0) { out_n[2 * g] = 0; out_n[2 * g + 1] = 0; }     // (the filter kernel counts into them)
-    // distinct records are counted per workgroup and added once (most records of a scan are sequencing errors seen once: an atomic per
-    // new record on one word of L2 was most of this kernel); a table filling up meanwhile shows as a probe sequence that does not end
-    __shared__ int s_new;
-    if (threadIdx.x == 0) s_new = 0;
+    if (__hip_atomic_load(&L.full, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) return 0;
+    const unsigned long long mine = ((unsigned long long)h << 32) | (unsigned)(id + 1);
+    unsigned sl = (h ^ (h >> 15)) & (MERGE_SLOTS - 1);
+    for (int tries = 0; tries < MERGE_SLOTS; ++tries) {
+        unsigned long long cur = __hip_atomic_load(&L.tab[sl], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (cur == 0ull) {
+            cur = atomicCAS(&L.tab[sl], 0ull, mine);
+            if (cur == 0ull) { atomicAdd(&L.cnt[sl], 1); return 1; }
+        }
+        if ((unsigned)(cur >> 32) == h) {
+            int32_t o[5];
+            merge_load(rec, (int)(unsigned)cur - 1, o);
+            // (equal content = equal hash: the smaller of two such words is the one with the smaller id)
+            if (rec_same(ref_seq, read_seq, o, w)) { atomicMin(&L.tab[sl], mine); atomicAdd(&L.cnt[sl], 1); return 0; }
+        }
+        sl = (sl + 1u) & (MERGE_SLOTS - 1);
+    }
+    __hip_atomic_store(&L.full, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    return 0;
+}
+
+// the first n ids of the queue into the table; -> the table has taken more than MERGE_LIMIT distinct records (the same for every thread).
+// Ends behind a barrier: the queue may be written again.
+__device__ __forceinline__ bool merge_insert(MergeLds& L, int n, bool full, const uint8_t* __restrict__ ref_seq, const uint8_t* __restrict__ read_seq,
+                                             const int32_t* __restrict__ rec)
+{
+    int fresh = 0;
+    for (int i = threadIdx.x; i < n && !full; i += 2 * MERGE_THREADS) {
+        const bool two = i + MERGE_THREADS < n;
+        const int ida = L.queue[i], idb = two ? L.queue[i + MERGE_THREADS] : ida;
+        int32_t wa[5], wb[5];
+        merge_load(rec, ida, wa);
+        merge_load(rec, idb, wb);
+        const unsigned fra = wa[1] > 0 ? ref_seq[(long long)wa[3]] : 0u, faa = wa[2] > 0 ? read_seq[(long long)wa[4]] : 0u;
+        const unsigned frb = wb[1] > 0 ? ref_seq[(long long)wb[3]] : 0u, fab = wb[2] > 0 ? read_seq[(long long)wb[4]] : 0u;
+        const unsigned ha = merge_hash(ref_seq, read_seq, wa, fra, faa), hb = merge_hash(ref_seq, read_seq, wb, frb, fab);
+        fresh += merge_probe(L, ref_seq, read_seq, rec, ida, wa, ha);
+        if (two) fresh += merge_probe(L, ref_seq, read_seq, rec, idb, wb, hb);
+    }
+    if (fresh) atomicAdd(&L.distinct, fresh);
     __syncthreads();
-    const bool full = flags[0] > MERGE_LIMIT;
-    for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < N && !full; q += gridDim.x * blockDim.x) {
-        const int r = r0 + q, c = count[r];
-        if (status[r] == PLAT_ERR_BAD_INPUT) flags[1] = PLAT_ERR_BAD_INPUT;
-        if (c > max_per_read) { atomicMax(&flags[2], c); continue; }
-        for (int k = 0; k < c; ++k) {
-            const int id = r * max_per_read + k;
-            const int32_t* me = rec + 5ll * id;
-            unsigned h = (unsigned)me[0] * 2654435761u + (unsigned)me[1] * 40503u + (unsigned)me[2] * 97u;
-            for (int i = 0; i < me[1]; ++i) h = h * 31u + b.ref_seq[(long long)me[3] + i];
-            for (int i = 0; i < me[2]; ++i) h = h * 37u + b.read_seq[(long long)me[4] + i];
-            unsigned sl = (h ^ (h >> 15)) & (MERGE_SLOTS - 1);
-            bool placed = false;
-            for (int tries = 0; tries < MERGE_PROBES && !placed; ++tries) {
-                int cur = *(volatile int32_t*)&tab[sl];
-                if (cur == 0) {
-                    const int old = atomicCAS(&tab[sl], 0, id + 1);
-                    if (old == 0) { atomicAdd(&s_new, 1); atomicAdd(&tab[MERGE_SLOTS + sl], 1); placed = true; break; }
-                    cur = old;
-                }
-                if (cur - 1 == id || rec_same(b, rec + 5ll * (cur - 1), me)) { atomicMin(&tab[sl], id + 1); atomicAdd(&tab[MERGE_SLOTS + sl], 1); placed = true; break; }
-                sl = (sl + 1u) & (MERGE_SLOTS - 1);
+    return L.distinct > MERGE_LIMIT || L.full != 0;
+}
+
+__global__ void __launch_bounds__(MERGE_THREADS)
+k_candidates_merge(const uint8_t* __restrict__ ref_seq, const uint8_t* __restrict__ read_seq, const int32_t* __restrict__ read_pos,
+                   const int32_t* __restrict__ read_end, const int32_t* __restrict__ scan_read_begin, const int32_t* __restrict__ scan_longest,
+                   int max_per_read, const int32_t* __restrict__ rec, const int32_t* __restrict__ count, const int32_t* __restrict__ status,
+                   int32_t* __restrict__ mtab, double min_var_freq, int cap, int32_t* __restrict__ out_cand, int32_t* __restrict__ out_n)
+{
+    extern __shared__ __align__(16) unsigned char merge_lds[];
+    MergeLds& L = *reinterpret_cast<MergeLds*>(merge_lds);
+    const int g = blockIdx.x, tid = threadIdx.x;
+    const int r0 = scan_read_begin[g], N = scan_read_begin[g + 1] - r0;
+    for (int sl = tid; sl < MERGE_SLOTS; sl += MERGE_THREADS) { L.tab[sl] = 0ull; L.cnt[sl] = 0; }
+    if (tid == 0) { L.distinct = 0; L.full = 0; L.bad = 0; L.need = 0; L.n_out = 0; L.st_out = 0; }
+    __syncthreads();
+
+    // ---- collect + insert.  The scan's records in the order (trip, thread, read of the thread, k): record number `base + off + ...`; the
+    // queue holds the numbers [qstart, qstart + MERGE_QUEUE)
+    int bad = 0, need = 0, base = 0, qstart = 0;
+    bool full = false;
+    for (int q0 = 0; q0 < N; q0 += MERGE_THREADS * MERGE_READS) {
+        int c[MERGE_READS], st[MERGE_READS];
+#pragma unroll
+        for (int j = 0; j < MERGE_READS; ++j) {
+            const int q = q0 + j * MERGE_THREADS + tid;
+            c[j] = q < N ? count[r0 + q] : 0;
+            st[j] = q < N ? status[r0 + q] : 0;
+        }
+        int mine = 0;
+#pragma unroll
+        for (int j = 0; j < MERGE_READS; ++j) {
+            if (st[j] == PLAT_ERR_BAD_INPUT) bad = 1;
+            if (c[j] > max_per_read) { need = c[j] > need ? c[j] : need; c[j] = 0; }      // more records than the read's slice holds: none of them is read
+            if (c[j] < 0) c[j] = 0;
+            mine += c[j];
+        }
+        int tot;
+        const int off = merge_block_scan(mine, L.wsum, tot);
+        const int hi = base + tot;
+        for (;;) {
+            int at = base + off - qstart;
+#pragma unroll
+            for (int j = 0; j < MERGE_READS; ++j) {
+                const int id0 = (r0 + q0 + j * MERGE_THREADS + tid) * max_per_read;
+                for (int k = 0; k < c[j]; ++k, ++at) if (at >= 0 && at < MERGE_QUEUE) L.queue[at] = id0 + k;
             }
-            if (!placed) atomicMax(&flags[0], MERGE_LIMIT + 1);          // the table is (nearly) full
+            if (hi - qstart <= MERGE_QUEUE) break;
+            __syncthreads();
+            full = merge_insert(L, MERGE_QUEUE, full, ref_seq, read_seq, rec);         // the queue is full and this trip has more
+            qstart += MERGE_QUEUE;
+        }
+        base = hi;
+    }
+    __syncthreads();
+    full = merge_insert(L, base - qstart, full, ref_seq, read_seq, rec);
+    if (bad) L.bad = 1;
+    if (need) atomicMax(&L.need, need);
+    __syncthreads();
+
+    // ---- out, for a scan that is refused: a read the scan refused | -(2^20 + needed records per read) | overflow of the table
+    int4* gtab = reinterpret_cast<int4*>(mtab + (size_t)g * 2 * MERGE_SLOTS);         // (64 KB per scan in a hipMalloc'ed block)
+    constexpr int SPT = MERGE_SLOTS / MERGE_THREADS;                                  // slots per thread: [tid * SPT, tid * SPT + SPT)
+    const int f_bad = L.bad, f_need = L.need;
+    if (f_bad || f_need > 0 || full) {
+#pragma unroll
+        for (int j = 0; j < SPT / 4; ++j) gtab[tid * (SPT / 4) + j] = make_int4(0, 0, 0, 0);
+        if (tid == 0) { out_n[2 * g] = 0; out_n[2 * g + 1] = f_bad ? PLAT_ERR_BAD_INPUT : (f_need > 0 ? -(1 << 20) - f_need : PLAT_ERR_OVERFLOW); }
+        return;
+    }
+
+    // ---- the table's rep + 1 half, every slot, and the occupied slots in slot order (into the queue)
+    int32_t idp[SPT];
+    int occ = 0;
+#pragma unroll
+    for (int j = 0; j < SPT; ++j) { idp[j] = (int32_t)(unsigned)L.tab[tid * SPT + j]; occ += idp[j] != 0; }
+#pragma unroll
+    for (int j = 0; j < SPT / 4; ++j) gtab[tid * (SPT / 4) + j] = make_int4(idp[4 * j], idp[4 * j + 1], idp[4 * j + 2], idp[4 * j + 3]);
+    int n_occ;
+    {
+        int at = merge_block_scan(occ, L.wsum, n_occ);
+#pragma unroll
+        for (int j = 0; j < SPT; ++j) if (idp[j] != 0) L.queue[at++] = tid * SPT + j;
+    }
+    __syncthreads();
+
+    // ---- filter: per distinct record the reads covering its position (countReadsCoveringRegion(start, start + 1), cwindow.pyx:176-206) and
+    // the per-sample support filter (variantcaller.pyx:456-467).  A record exists, so N > 0 and index 0 of the scan's reads can be read.
+    const int32_t* pos = read_pos + r0;
+    const int32_t* endp = read_end + r0;
+    const int longest = scan_longest[g];
+    for (int i0 = tid; i0 < n_occ; i0 += MERGE_THREADS * MERGE_LANES) {
+        int id[MERGE_LANES], sup[MERGE_LANES], w[MERGE_LANES][5];
+        bool on[MERGE_LANES];
+#pragma unroll
+        for (int k = 0; k < MERGE_LANES; ++k) {
+            const int i = i0 + k * MERGE_THREADS;
+            on[k] = i < n_occ;
+            const int sl = L.queue[on[k] ? i : i0];
+            id[k] = (int)(unsigned)L.tab[sl] - 1;
+            sup[k] = L.cnt[sl];
+            merge_load(rec, id[k], w[k]);
+        }
+        // the two lower bounds of every record, all in one loop: each search takes the steps it takes by itself, their loads travel together
+        int lo1[MERGE_LANES], hi1[MERGE_LANES], lo2[MERGE_LANES], hi2[MERGE_LANES];
+        long long key[MERGE_LANES];
+#pragma unroll
+        for (int k = 0; k < MERGE_LANES; ++k) {
+            const int start = w[k][0];
+            key[k] = (long long)start - longest > 1 ? (long long)start - longest : 1;
+            lo1[k] = lo2[k] = 0;
+            hi1[k] = hi2[k] = on[k] ? N : 0;
+        }
+        for (bool any = true; any;) {
+            int p1[MERGE_LANES], p2[MERGE_LANES];
+#pragma unroll
+            for (int k = 0; k < MERGE_LANES; ++k) {
+                p1[k] = pos[lo1[k] < hi1[k] ? (lo1[k] + hi1[k]) >> 1 : 0];
+                p2[k] = pos[lo2[k] < hi2[k] ? (lo2[k] + hi2[k]) >> 1 : 0];
+            }
+            any = false;
+#pragma unroll
+            for (int k = 0; k < MERGE_LANES; ++k) {
+                if (lo1[k] < hi1[k]) { const int mid = (lo1[k] + hi1[k]) >> 1; if ((long long)p1[k] < key[k]) lo1[k] = mid + 1; else hi1[k] = mid; }
+                if (lo2[k] < hi2[k]) { const int mid = (lo2[k] + hi2[k]) >> 1; if (p2[k] < w[k][0] + 1) lo2[k] = mid + 1; else hi2[k] = mid; }
+                any = any || lo1[k] < hi1[k] || lo2[k] < hi2[k];
+            }
+        }
+        // the start pointer walks on over the reads that end at or before the site
+        int s[MERGE_LANES];
+        bool walk[MERGE_LANES];
+#pragma unroll
+        for (int k = 0; k < MERGE_LANES; ++k) { s[k] = lo1[k]; walk[k] = on[k]; }
+        for (bool any = true; any;) {
+            int e[MERGE_LANES];
+#pragma unroll
+            for (int k = 0; k < MERGE_LANES; ++k) e[k] = endp[walk[k] && s[k] < N ? s[k] : 0];
+            any = false;
+#pragma unroll
+            for (int k = 0; k < MERGE_LANES; ++k) {
+                walk[k] = walk[k] && s[k] < N && e[k] <= w[k][0];
+                if (walk[k]) { ++s[k]; any = true; }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < MERGE_LANES; ++k) {
+            if (!on[k]) continue;
+            if (s[k] > lo2[k]) { L.st_out = PLAT_ERR_BAD_INPUT; continue; }             // "Read start pointer > read end pointer": the reference raises
+            const int total = lo2[k] - s[k];
+            const double frac = total == 0 ? 0.0 : (double)sup[k] / (double)total;
+            if (frac >= min_var_freq || w[k][1] != w[k][2]) {
+                const int at = atomicAdd(&L.n_out, 1);
+                if (at < cap) {
+                    int32_t* o = out_cand + 8ll * ((long long)g * cap + at);
+                    o[0] = id[k]; o[1] = sup[k]; o[2] = total; o[3] = w[k][0]; o[4] = w[k][1]; o[5] = w[k][2]; o[6] = w[k][3]; o[7] = w[k][4];
+                }
+            }
         }
     }
     __syncthreads();
-    if (threadIdx.x == 0 && s_new) atomicAdd(&flags[0], s_new);
-}
-
-// per distinct record of a scan: the reads covering its position (ReadArray.countReadsCoveringRegion, cwindow.pyx:176-206) and the
-// per-sample support filter of generateVariantsInRegion (variantcaller.pyx:456-467).  grid = (MERGE_SLOTS / 256, scans).
-__global__ void __launch_bounds__(256)
-k_candidates_filter(plat_candidate_batch b, const int32_t* __restrict__ read_end, const int32_t* __restrict__ scan_read_begin,
-                    const int32_t* __restrict__ scan_longest, int n_scans, const int32_t* __restrict__ rec, int32_t* __restrict__ mtab, double min_var_freq,
-                    int cap, int32_t* __restrict__ out_cand, int32_t* __restrict__ out_n)
-{
-    const int g = blockIdx.y, sl = blockIdx.x * blockDim.x + threadIdx.x;
-    const int32_t* flags = merge_flags(mtab, n_scans, g);
-    const int distinct = flags[0], f_status = flags[1], f_need = flags[2];
-    if (f_need > 0 || f_status != 0 || distinct > MERGE_LIMIT) {
-        // -(2^20 + needed records per read) | overflow of the table | a read the scan refused
-        if (sl == 0) out_n[2 * g + 1] = f_status != 0 ? f_status : (f_need > 0 ? -(1 << 20) - f_need : PLAT_ERR_OVERFLOW);
-        return;
-    }
-    const int id = mtab[(size_t)g * 2 * MERGE_SLOTS + sl] - 1;
-    if (id < 0) return;
-    const int c = mtab[(size_t)g * 2 * MERGE_SLOTS + MERGE_SLOTS + sl];
-    const int r0 = scan_read_begin[g], N = scan_read_begin[g + 1] - r0;
-    const int32_t* pos = b.read_pos + r0;
-    const int32_t* endp = read_end + r0;
-    const int longest = scan_longest[g];
-    const int32_t* me = rec + 5ll * id;
-    const int start = me[0];
-    // countReadsCoveringRegion(start, start + 1), cwindow.pyx:176-206
-    int total = 0;
-    if (N > 0) {
-        const long long key = (long long)start - longest > 1 ? (long long)start - longest : 1;
-        int lo = 0, hi = N;
-        while (lo < hi) { const int mid = (lo + hi) >> 1; if ((long long)pos[mid] < key) lo = mid + 1; else hi = mid; }
-        int s = lo;
-        lo = 0; hi = N;
-        while (lo < hi) { const int mid = (lo + hi) >> 1; if (pos[mid] < start + 1) lo = mid + 1; else hi = mid; }
-        const int e = lo;
-        while (s < N && endp[s] <= start) ++s;
-        if (s > e) { atomicCAS(&out_n[2 * g + 1], 0, PLAT_ERR_BAD_INPUT); return; }    // "Read start pointer > read end pointer": the reference raises
-        total = e - s;
-    }
-    const double frac = total == 0 ? 0.0 : (double)c / (double)total;
-    if (frac >= min_var_freq || me[1] != me[2]) {
-        const int at = atomicAdd(&out_n[2 * g], 1);
-        if (at < cap) {
-            int32_t* o = out_cand + 8ll * ((long long)g * cap + at);
-            o[0] = id; o[1] = c; o[2] = total; o[3] = me[0]; o[4] = me[1]; o[5] = me[2]; o[6] = me[3]; o[7] = me[4];
-        } else atomicCAS(&out_n[2 * g + 1], 0, PLAT_ERR_OVERFLOW);                      // more candidates than the caller's room: its status says so
+    if (tid == 0) {
+        const int n = L.n_out;
+        out_n[2 * g] = n;
+        // (more candidates than the caller's room: its status says so, the count is the full one)
+        out_n[2 * g + 1] = L.st_out != 0 ? L.st_out : (n > cap ? PLAT_ERR_OVERFLOW : 0);
     }
 }
 }  // namespace plat
@@ -621,19 +793,20 @@ PLAT_EXPORT int plat_candidates_merge_batch(plat_ctx* ctx, const plat_candidate_
     if (!b.ref_seq || !b.read_seq || !b.read_pos || !read_end || !scan_read_begin || !scan_longest || !rec || !count || !status || !out_cand || !out_n)
         return PLAT_ERR_INVALID;
     PLAT_HIP(ctx, hipSetDevice(ctx->device));
+    // the context's table: per scan rep + 1 [MERGE_SLOTS] (0 = empty), written in full by the kernel, then MERGE_SLOTS words and, behind
+    // all scans, 4 words per scan that nothing reads any more (the size and the offsets are what plat_stage_b_batch knows)
     const size_t tab_bytes = ((size_t)n_scans * 2 * plat::MERGE_SLOTS + 4 * (size_t)n_scans) * sizeof(int32_t);
     int rcm = plat_reserve(ctx, ctx->merge_tab, tab_bytes);
     if (rcm) return rcm;
     int32_t* mtab = (int32_t*)ctx->merge_tab.ptr;
-    PLAT_HIP(ctx, hipMemsetAsync(mtab, 0, tab_bytes, (hipStream_t)stream));
-    // a thread per read when the scans are of one size; a scan with more than its share is walked in strides
-    long long per = ((long long)b.n_reads + n_scans - 1) / n_scans;
-    unsigned gx = (unsigned)((per + 255) / 256);
-    gx = gx < 1 ? 1 : (gx > 4096 ? 4096 : gx);
-    { PLAT_KT_BEGIN(ctx, PLAT_KT_CAND_MERGE, (hipStream_t)stream); hipLaunchKernelGGL(plat::k_candidates_merge, dim3(gx, (unsigned)n_scans), dim3(256), 0, (hipStream_t)stream, b,
-                       scan_read_begin, n_scans, max_per_read, rec, count, status, mtab, out_n); PLAT_KT_END(ctx, PLAT_KT_CAND_MERGE, (hipStream_t)stream); }
-    { PLAT_KT_BEGIN(ctx, PLAT_KT_CAND_FILTER, (hipStream_t)stream); hipLaunchKernelGGL(plat::k_candidates_filter, dim3(plat::MERGE_SLOTS / 256, (unsigned)n_scans), dim3(256), 0, (hipStream_t)stream, b, read_end,
-                       scan_read_begin, scan_longest, n_scans, rec, mtab, min_var_freq, cap_per_scan, out_cand, out_n); PLAT_KT_END(ctx, PLAT_KT_CAND_FILTER, (hipStream_t)stream); }
+    if (!ctx->merge_attr_set) {                                     // (the attribute is per device: remembered per context, as k_sb_variants')
+        PLAT_HIP(ctx, hipFuncSetAttribute((const void*)plat::k_candidates_merge, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(plat::MergeLds)));
+        ctx->merge_attr_set = true;
+    }
+    { PLAT_KT_BEGIN(ctx, PLAT_KT_CAND_MERGE, (hipStream_t)stream);
+      hipLaunchKernelGGL(plat::k_candidates_merge, dim3((unsigned)n_scans), dim3(plat::MERGE_THREADS), sizeof(plat::MergeLds), (hipStream_t)stream, b.ref_seq, b.read_seq,
+                         b.read_pos, read_end, scan_read_begin, scan_longest, max_per_read, rec, count, status, mtab, min_var_freq, cap_per_scan, out_cand, out_n);
+      PLAT_KT_END(ctx, PLAT_KT_CAND_MERGE, (hipStream_t)stream); }
     PLAT_HIP(ctx, hipGetLastError());
     return PLAT_OK;
 }

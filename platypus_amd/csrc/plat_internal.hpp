@@ -27,6 +27,7 @@ struct plat_ctx {
     unsigned long long asm_epoch = 0;   // counts the (re)allocations of asm_scratch AND the changes of the slice layout between launches: part of the signature k_assemble leaves in asm_sig
     unsigned long long asm_last_layout = 0;   // the previous launch's slice layout (sizes asm_carve is given)
     bool sb_attr_set = false;           // k_sb_variants' dynamic-LDS limit has been raised on this context's device
+    bool merge_attr_set = false;        // ... and k_candidates_merge's
     bool asm_last_kept = false;         // ... and whether it maintained asm_sig (a launch without it dirties slices behind the signatures' back)
     // pinned host read-back area
     int64_t* h_readback = nullptr;
