@@ -392,6 +392,32 @@ cdef extern from "platypus_mi355x.h":
         int32_t* stream_begin
         int64_t* status
     int plat_bam_find_records(plat_ctx* ctx, const plat_bam_find_in* inp, const plat_bam_find_out* out, void* stream) nogil
+    # records routed to samples by read group (the second branch of loadBAMData, platypusutils.pyx:573-666)
+    enum:
+        PLAT_ROUTE_MAX_GROUPS
+        PLAT_ROUTE_MAX_SAMPLES
+        PLAT_ROUTE_LDS_ID_BYTES
+    ctypedef struct plat_bam_route_in:
+        int32_t n_records
+        int32_t n_streams
+        int32_t n_groups
+        int32_t n_samples
+        const uint8_t* blob
+        int64_t blob_len
+        const int64_t* rec_off
+        const int64_t* rec_end
+        const int32_t* stream_begin
+        const uint8_t* group_ids
+        const int32_t* group_off
+        const int32_t* group_sample
+    ctypedef struct plat_bam_route_out:
+        int64_t* rec_off
+        int64_t* rec_limit
+        int32_t* out_begin
+        int32_t* rec_sample
+        int64_t* status
+        int32_t* why
+    int plat_bam_route_batch(plat_ctx* ctx, const plat_bam_route_in* inp, const plat_bam_route_out* out, void* stream) nogil
     # the same for a PLAT_READS_PACKED table (one byte per base + exceptions): QC and trimming on the packed bytes, no quality array
     ctypedef struct plat_read_buffers_packed_in:
         plat_readqc_batch qc
@@ -607,3 +633,49 @@ cdef extern from "platypus_caller_bgzf.h":
     int plat_call_bgzf_regions(plat_caller* c, const plat_bgzf_region* regions, int n_regions, int n_samples,
                                const char* const* sample_names, plat_caller_options* options, const plat_caller_qc_options* qc,
                                char** out_text, size_t* out_len, plat_fetched_region_info* info, plat_caller_stats* stats) nogil
+
+
+# The record front ends for merged files (include/platypus_caller_rg.h): the fetch of every FILE and one table read-group ID -> sample;
+# the records are routed to samples on the device (plat_bam_route_batch).
+cdef extern from "platypus_caller_rg.h":
+    ctypedef struct plat_bam_read_groups:
+        int32_t n_groups
+        const char* const* id
+        const int32_t* sample
+    ctypedef struct plat_bam_file_records:
+        plat_bam_records records
+        const int32_t* rec_len
+    ctypedef struct plat_bam_file:
+        plat_bam_file_records fetched
+        plat_bam_file_records broken_mates
+    ctypedef struct plat_bgzf_file:
+        int32_t n_chunks
+        const plat_bgzf_chunk* chunks
+        plat_bam_file_records broken_mates
+    ctypedef struct plat_bam_rg_region:
+        const char* chrom
+        int32_t start
+        int32_t end
+        const uint8_t* contig_seq
+        int64_t contig_len
+        const plat_bam_file* files
+        const uint8_t* dev_contig_seq
+    ctypedef struct plat_bgzf_rg_region:
+        const char* chrom
+        int32_t start
+        int32_t end
+        const uint8_t* contig_seq
+        int64_t contig_len
+        const uint8_t* dev_contig_seq
+        int32_t tid
+        int32_t itr_beg
+        int32_t itr_end
+        const plat_bgzf_file* files
+    int plat_call_bam_regions_rg(plat_caller* c, const plat_bam_rg_region* regions, int n_regions, int n_files,
+                                 const plat_bam_read_groups* groups, int n_samples, const char* const* sample_names,
+                                 plat_caller_options* options, const plat_caller_qc_options* qc, char** out_text, size_t* out_len,
+                                 plat_fetched_region_info* info, plat_caller_stats* stats) nogil
+    int plat_call_bgzf_regions_rg(plat_caller* c, const plat_bgzf_rg_region* regions, int n_regions, int n_files,
+                                  const plat_bam_read_groups* groups, int n_samples, const char* const* sample_names,
+                                  plat_caller_options* options, const plat_caller_qc_options* qc, char** out_text, size_t* out_len,
+                                  plat_fetched_region_info* info, plat_caller_stats* stats) nogil

@@ -25,8 +25,9 @@
  * caller stays usable.  plat_caller_stats.input_bytes counts the record bytes uploaded: the blobs as handed over, names and aux data
  * included -- more than either encoding of the fetched call puts on the link.  A library linked against a device library without
  * plat_bam_decode_batch returns PLAT_ERR_UNSUPPORTED.
- * Not handled: the CG-tag convention for CIGARs of more than 65535 operations, read groups and CRAM.  For the compressed BGZF blocks
- * of a BAM file, inflated and iterated on the device in front of this call, see platypus_caller_bgzf.h.
+ * Not handled: the CG-tag convention for CIGARs of more than 65535 operations and CRAM.  For the compressed BGZF blocks of a BAM file,
+ * inflated and iterated on the device in front of this call, see platypus_caller_bgzf.h; for merged files, whose records are split by
+ * read group on the device in front of it, see platypus_caller_rg.h.
  */
 #ifndef PLATYPUS_CALLER_BAM_H
 #define PLATYPUS_CALLER_BAM_H

@@ -725,6 +725,74 @@ typedef struct plat_bam_find_out {
 
 int plat_bam_find_records(plat_ctx* ctx, const plat_bam_find_in* in, const plat_bam_find_out* out, void* stream);
 
+/* ---- records routed to samples by read group ------------------------------------------------------------------
+ * Replaces  the second branch of loadBAMData  platypusutils.pyx:573-666  (a BAM file that holds several samples, or a sample spread over
+ * several files: every record's rgID from ReadIterator.get(1, &rgID), htslibWrapper.pyx:348-361 -- bam_aux_get(b, "RG"), bam_aux2Z --
+ * then buffersBySample[samplesByID[rgID]]) for n_streams fetches whose records (as plat_bam_decode_batch takes them) lie in one blob.
+ * Stream s (one fetch of one file) is the records stream_begin[s] .. stream_begin[s + 1] - 1 of rec_off / rec_end; stream_begin[0] = 0,
+ * ascending, stream_begin[n_streams] <= n_records (the records behind it belong to no stream and are not looked at: n_records may be
+ * the capacity of a plat_bam_find_records whose counts the host has not read).  rec_end[i] (required): the offset of record i's end in
+ * the blob, rec_off[i] + its block_size -- the record's own fields do not say where its aux data stops.
+ *
+ * The rule (the loader's, restated over the aux layout of the SAM/BAM specification section 4.2.4; the reference tree holds only the
+ * htslib declarations, htslibWrapper.pxd:172-173):
+ *   extent  the aux area runs from 32 + l_read_name + 4 n_cigar_op + (l_seq + 1) / 2 + l_seq (l_seq as an unsigned word) to the end
+ *   walk    from its start, while at least 3 bytes are left: a 2-byte tag, a 1-byte type, then the value --
+ *             A c C 1 byte | s S 2 bytes | i I f 4 bytes | d 8 bytes | Z H the bytes through the first NUL |
+ *             B 1 subtype byte of cCsSiIf, an int32 count, count x size bytes
+ *           the FIRST field whose tag is RG decides; later RG fields are not looked at
+ *   value   the RG field must have type Z or H; its value is the bytes up to the NUL
+ *   sample  group_sample[g] of the group g whose ID equals the value byte for byte (an ID that is a prefix of another is a
+ *           different ID); of equal IDs the lowest g counts
+ * Refused (PLAT_ERR_BAD_INPUT; where the reference dereferences NULL or raises KeyError) -- out->why names the rule for the lowest such
+ * record: PLAT_ROUTE_NO_RG (no RG field), _RG_NOT_STRING (RG of another type), _NOT_IN_TABLE, _UNKNOWN_TYPE (a field's type or a B
+ * subtype), _NEGATIVE_COUNT (of a B array), _AUX_OVERRUN (a field, a string's NUL or an array runs past the record's end),
+ * _FIXED_OVERRUN (the fixed part already does, or rec_off / rec_end lie outside the blob).  A refused record is left out of the output;
+ * the others are still routed.  Every loop is bounded by the record's end: no input makes a lane read outside [rec_off, rec_end) or spin.
+ *
+ * The group table: n_groups IDs, their bytes back to back in group_ids with group_off [n_groups + 1] (from 0), and group_sample
+ * [n_groups] in 0 .. n_samples - 1.  Limits: n_groups <= PLAT_ROUTE_MAX_GROUPS and n_samples <= PLAT_ROUTE_MAX_SAMPLES, else
+ * PLAT_ERR_UNSUPPORTED is returned and nothing is enqueued.  An ID may have any length: the table of (hash, group) pairs always lies in
+ * LDS; the IDs' bytes lie there too while they hold at most PLAT_ROUTE_LDS_ID_BYTES in all, and are compared where they lie in device
+ * memory beyond that.  n_streams * n_samples must stay below 2^31 (PLAT_ERR_OVERFLOW).
+ *
+ * Output: rec_off / rec_limit [n_records] for plat_bam_decode_batch -- stream s's records as sample 0's, then sample 1's, ..., each in
+ * input order (a stable partition; stream s of sample m becomes the records out_begin[s * n_samples + m] .. out_begin[s * n_samples +
+ * m + 1] - 1), all streams back to back without gaps; out_begin [n_streams * n_samples + 1]; rec_sample [n_records], -1 for a refused
+ * record; status [4] {0 or the error, the lowest offending record or -1, records routed, records refused}; why [1] (may be NULL).  An
+ * out-of-range group_sample or group_off, or a stream_begin that is no such partition, is status PLAT_ERR_INVALID {-1, -1, 0, 0} and
+ * nothing else is written.  The call enqueues six kernels (checks and tile plan, tag: one lane per record; per-tile sample histogram;
+ * scan over tiles; scan over streams and samples; placing), keeps its tile counts in the context's scratch, and does not wait; nothing
+ * traps.                                                                                                                          */
+#define PLAT_ROUTE_MAX_GROUPS 2048
+#define PLAT_ROUTE_MAX_SAMPLES 256
+#define PLAT_ROUTE_LDS_ID_BYTES 24576
+#define PLAT_ROUTE_NO_RG 1
+#define PLAT_ROUTE_RG_NOT_STRING 2
+#define PLAT_ROUTE_NOT_IN_TABLE 3
+#define PLAT_ROUTE_UNKNOWN_TYPE 4
+#define PLAT_ROUTE_NEGATIVE_COUNT 5
+#define PLAT_ROUTE_AUX_OVERRUN 6
+#define PLAT_ROUTE_FIXED_OVERRUN 7
+
+typedef struct plat_bam_route_in {
+    int32_t n_records, n_streams, n_groups, n_samples;
+    const uint8_t* blob; int64_t blob_len;
+    const int64_t* rec_off; const int64_t* rec_end;
+    const int32_t* stream_begin;
+    const uint8_t* group_ids; const int32_t* group_off; const int32_t* group_sample;
+} plat_bam_route_in;
+
+typedef struct plat_bam_route_out {
+    int64_t* rec_off; int64_t* rec_limit;
+    int32_t* out_begin;
+    int32_t* rec_sample;
+    int64_t* status;
+    int32_t* why;
+} plat_bam_route_out;
+
+int plat_bam_route_batch(plat_ctx* ctx, const plat_bam_route_in* in, const plat_bam_route_out* out, void* stream);
+
 /* ---- read statistics of the VCF INFO field ---------------------------------------
  * Replaces the per-variant loop over a window's reads in  cdef dict vcfINFO(...)   vcfutils.pyx:1300-1390
  * (readOverlapsVariant :901-913, readQualIsGoodVariantPosition :917-943, variantSupportedByRead :961-1072).

@@ -121,6 +121,20 @@ class BamFindOut(C.Structure):
     _fields_ = [("cap_records", C.c_int64), ("rec_off", C.c_void_p), ("rec_limit", C.c_void_p), ("stream_begin", C.c_void_p), ("status", C.c_void_p)]
 
 
+class BamRouteIn(C.Structure):
+    _fields_ = [("n_records", C.c_int32), ("n_streams", C.c_int32), ("n_groups", C.c_int32), ("n_samples", C.c_int32), ("blob", C.c_void_p),
+                ("blob_len", C.c_int64)] + [(k, C.c_void_p) for k in ("rec_off", "rec_end", "stream_begin", "group_ids", "group_off", "group_sample")]
+
+
+class BamRouteOut(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("rec_off", "rec_limit", "out_begin", "rec_sample", "status", "why")]
+
+
+ROUTE_MAX_GROUPS, ROUTE_MAX_SAMPLES, ROUTE_LDS_ID_BYTES = 2048, 256, 24576
+ROUTE_WHY = ("routed", "no RG field", "an RG field that is no string", "an RG value that is not in the table", "an aux field of unknown type",
+             "a B array with a negative count", "aux data that runs past the record", "a fixed part that runs past the record")
+
+
 class InfoStatsBatch(C.Structure):
     _fields_ = [("n_vars", C.c_int32), ("n_ind", C.c_int32)] + [(k, C.c_void_p) for k in (
         "var_window", "var_pos", "var_bam_min", "var_bam_max", "var_n_added", "var_n_removed", "var_added", "var_added_off",
@@ -234,6 +248,7 @@ SIGNATURES = {
     "plat_bam_decode_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(BamDecodeOut), C.c_void_p]),
     "plat_bgzf_inflate_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(BgzfInflateOut), C.c_void_p]),
     "plat_bam_find_records": (C.c_int, [C.c_void_p, C.POINTER(BamFindIn), C.POINTER(BamFindOut), C.c_void_p]),
+    "plat_bam_route_batch": (C.c_int, [C.c_void_p, C.POINTER(BamRouteIn), C.POINTER(BamRouteOut), C.c_void_p]),
     "plat_variant_read_stats_batch": (C.c_int, [C.c_void_p, C.POINTER(InfoStatsBatch), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
     "plat_variant_info_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -248,6 +263,7 @@ SIGNATURES = {
 # entry points a stand-in library built against an earlier header may lack (the CPU suite's fake device): bind() leaves them
 # unbound there; load() still requires every declared symbol of the real library
 ADDED_LATER = ("plat_read_buffers_batch", "plat_read_buffers_packed_batch", "plat_bam_decode_batch", "plat_bgzf_inflate_batch", "plat_bam_find_records",
+               "plat_bam_route_batch",
                "plat_concat_read_tables_src", "plat_pack_codes_pieces", "plat_candidates_batch_packed", "plat_gather_reads_packed",
                "plat_variant_read_stats_packed_batch")
 

@@ -20,6 +20,160 @@ static std::string bgzfWhere(const FetchedRegionHead& r, const BgzfChunkAt& a) {
     return fetchedWhere(r, a.region, a.sample) + ", chunk " + std::to_string(a.chunk);
 }
 
+// The chunks of one call -- every (region, unit) in order, a unit being what one index lookup fetched (a sample; a file for the read-group
+// call of rg_regions.hpp) -- from the host's walk over the block headers to the kept records' offsets on the device.
+struct BgzfFront {
+    std::string entry;
+    int nUnits = 0;
+    // the call's blocks and chunks, all regions: which of them load is known once the device has counted the kept records
+    std::vector<BgzfChunkAt> chunkAt;
+    std::vector<const plat_bgzf_chunk*> chunkOf;
+    std::vector<int64_t> blkOff, blkLimit;
+    std::vector<int32_t> firstU, stopBlk, stopU, tid, beg, end;           // per chunk; tid / beg / end per region
+    long long blobBytes = 0, inflated = 0;
+    int nBlocks = 0;
+    plat_bgzf_inflate_out io;
+    plat_bam_find_out fo;
+    long long capRecords = 0;
+    int64_t inflateStatus[4] = {0, -1, 0, 0}, findStatus[4] = {0, -1, 0, 0};
+    std::vector<int32_t> keptBegin;                                       // [streams + 1], of the find that ran last
+
+    void addRegion(int32_t t, int32_t b, int32_t e) { tid.push_back(t); beg.push_back(b); end.push_back(e); }
+
+    // unit i of region k: its chunks checked, the BSIZE chain of each walked (18 header bytes and the trailer of every block)
+    int addUnit(plat_caller* c, const FetchedRegionHead& head, int k, int i, int n_chunks, const plat_bgzf_chunk* chunks)
+    {
+        for (int q = 0; q < n_chunks; ++q) {
+            const plat_bgzf_chunk& ch = chunks[q];
+            if (ch.data_len < 0 || (ch.data_len && !ch.data) || ch.first_uoffset < 0 || ch.first_uoffset > 65535 || ch.end_uoffset < 0 || ch.end_uoffset > 65536 ||
+                ch.end_coffset < -1 || ch.end_coffset > ch.data_len)
+                return PLAT_ERR_INVALID;
+            BgzfChunkAt a{k, i, q, (int)blkOff.size(), 0};
+            int endBlk = ch.end_coffset < 0 || (ch.end_coffset == ch.data_len && ch.end_uoffset == 0) ? -1 : -2;       // -2: not found yet
+            for (int64_t at = 0; at < ch.data_len;) {
+                bgzf::BlockHead h;
+                if (bgzf::parse_header(ch.data, ch.data_len, at, &h) != 0) {
+                    c->lastError = entry + ": the BGZF blocks of " + bgzfWhere(head, a) + " do not chain: no valid block header at offset " +
+                                   std::to_string(at) + " of its data (bad magic, no BC subfield, or a block that leaves the data)";
+                    return PLAT_ERR_BAD_INPUT;
+                }
+                if (at == ch.end_coffset) endBlk = (int)blkOff.size();
+                blkOff.push_back(blobBytes + at); blkLimit.push_back(blobBytes + ch.data_len);
+                inflated += h.isize;
+                at = h.payload + h.payload_len + 8;
+                if (blkOff.size() >= (size_t)INT_MAX) { c->lastError = entry + ": more blocks than one call takes"; return PLAT_ERR_OVERFLOW; }
+            }
+            if (endBlk == -2) {
+                c->lastError = entry + ": end_coffset " + std::to_string(ch.end_coffset) + " of " + bgzfWhere(head, a) + " is not a block boundary of its data";
+                return PLAT_ERR_BAD_INPUT;
+            }
+            a.blkEnd = (int)blkOff.size();
+            chunkAt.push_back(a); chunkOf.push_back(&ch);
+            firstU.push_back(ch.first_uoffset); stopBlk.push_back(endBlk); stopU.push_back(endBlk < 0 ? 0 : ch.end_uoffset);
+            blobBytes += ch.data_len;
+        }
+        return PLAT_OK;
+    }
+
+    // upload and inflate, back to back
+    void inflate(Slot& z, FetchedDeviceBuffers& dev)
+    {
+        void* st = z.stream;
+        nBlocks = (int)blkOff.size();
+        uint8_t* dBlob = dev.alloc<uint8_t>((size_t)blobBytes);
+        { long long base = 0;
+          for (const plat_bgzf_chunk* ch : chunkOf) {
+              if (ch->data_len) ck(plat_memcpy_h2d(z.ctx, dBlob + base, ch->data, (size_t)ch->data_len, st), "plat_memcpy_h2d(blocks)");
+              base += ch->data_len;
+          } }
+        memset(&io, 0, sizeof io);
+        io.cap_bytes = inflated;
+        io.data = dev.alloc<uint8_t>((size_t)inflated + PLAT_BLOB_PAD); io.out_off = dev.alloc<int64_t>((size_t)nBlocks + 1); io.status = dev.alloc<int64_t>(4);
+        ck(plat_bgzf_inflate_batch(z.ctx, nBlocks, dBlob, blobBytes, dev.upload(blkOff, st), dev.upload(blkLimit, st), &io, st), "plat_bgzf_inflate_batch");
+        // every record has a block_size word and 32 fixed bytes
+        capRecords = inflated / 36 + 1;
+        memset(&fo, 0, sizeof fo);
+        fo.cap_records = capRecords; fo.rec_off = dev.alloc<int64_t>((size_t)capRecords); fo.rec_limit = dev.alloc<int64_t>((size_t)capRecords);
+        fo.status = dev.alloc<int64_t>(4);
+        ck(plat_memcpy_d2h(z.ctx, inflateStatus, io.status, sizeof inflateStatus, st), "plat_memcpy_d2h");
+    }
+
+    // the find over the streams of the regions `use` marks (stream = unit i of such a region, in order; its chunks lie back to back in the
+    // call's list); returns the number of streams
+    int find(Slot& z, FetchedDeviceBuffers& dev, const std::vector<int>& use)
+    {
+        void* st = z.stream;
+        const int n_regions = (int)use.size();
+        std::vector<int32_t> chunkBegin(1, 0), cFirst, cEnd, cFirstU, cStopBlk, cStopU, sTid, sBeg, sEnd;
+        size_t q = 0;
+        for (int k = 0; k < n_regions; ++k)
+            for (int i = 0; i < nUnits; ++i) {
+                for (; q < chunkAt.size() && chunkAt[q].region == k && chunkAt[q].sample == i; ++q) {
+                    if (!use[(size_t)k]) continue;
+                    cFirst.push_back(chunkAt[q].blkFirst); cEnd.push_back(chunkAt[q].blkEnd);
+                    cFirstU.push_back(firstU[q]); cStopBlk.push_back(stopBlk[q]); cStopU.push_back(stopU[q]);
+                }
+                if (!use[(size_t)k]) continue;
+                chunkBegin.push_back((int32_t)cFirst.size());
+                sTid.push_back(tid[(size_t)k]); sBeg.push_back(beg[(size_t)k]); sEnd.push_back(end[(size_t)k]);
+            }
+        const int n = (int)sTid.size();
+        plat_bam_find_in fi;
+        memset(&fi, 0, sizeof fi);
+        fi.n_streams = n; fi.n_chunks = (int)cFirst.size(); fi.n_blocks = nBlocks; fi.data = io.data; fi.out_off = io.out_off;
+        fi.chunk_blk_first = dev.upload(cFirst, st); fi.chunk_blk_end = dev.upload(cEnd, st); fi.chunk_first_uoffset = dev.upload(cFirstU, st);
+        fi.chunk_stop_blk = dev.upload(cStopBlk, st); fi.chunk_stop_uoffset = dev.upload(cStopU, st);
+        fi.stream_chunk_begin = dev.upload(chunkBegin, st);
+        fi.tid = dev.upload(sTid, st); fi.beg = dev.upload(sBeg, st); fi.end = dev.upload(sEnd, st);
+        fo.stream_begin = dev.alloc<int32_t>((size_t)n + 1);
+        ck(plat_bam_find_records(z.ctx, &fi, &fo, st), "plat_bam_find_records");
+        keptBegin.assign((size_t)n + 1, 0);
+        ck(plat_memcpy_d2h(z.ctx, keptBegin.data(), fo.stream_begin, keptBegin.size() * sizeof(int32_t), st), "plat_memcpy_d2h");
+        ck(plat_memcpy_d2h(z.ctx, findStatus, fo.status, sizeof findStatus, st), "plat_memcpy_d2h");
+        return n;
+    }
+
+    // after the wait behind the first find (every region took part): 0, or the inflate's or the find's error with its message
+    int firstFailure(plat_caller* c, const std::vector<FetchedRegionHead>& heads) const
+    {
+        if (inflateStatus[0] != 0) {
+            const long long b = inflateStatus[1];
+            size_t q = 0;
+            while (q + 1 < chunkAt.size() && !(b >= chunkAt[q].blkFirst && b < chunkAt[q].blkEnd)) ++q;
+            const BgzfChunkAt a = chunkAt.empty() ? BgzfChunkAt{0, 0, 0, 0, 0} : chunkAt[q];
+            c->lastError = entry + ": block " + std::to_string(b - a.blkFirst) + " of " + bgzfWhere(heads[(size_t)a.region], a) +
+                           (inflateStatus[0] == PLAT_ERR_OVERFLOW ? " does not fit the room its ISIZE words asked for"
+                                                                  : " cannot be inflated (a bad header, an invalid deflate stream, output other than ISIZE bytes, or a CRC32 mismatch)");
+            return (int)inflateStatus[0];
+        }
+        if (findStatus[0] != 0) {                                          // (stream s is unit s % nUnits of region s / nUnits)
+            const int s = (int)findStatus[1], k = s / nUnits;
+            c->lastError = entry + ": the record walk of " + fetchedWhere(heads[(size_t)k], k, s % nUnits) +
+                           " fails (a block_size below 32, or a record or its CIGAR running past the chunk's bytes)";
+            return (int)findStatus[0];
+        }
+        return PLAT_OK;
+    }
+
+    // loadBAMData's bail-out (:538-541) on the kept counts of the first find; true when a region is dropped
+    bool bailOut(long long maxReads, std::vector<int>& loaded) const
+    {
+        bool dropped = false;
+        for (size_t k = 0; k < loaded.size(); ++k) {
+            const long long total = (long long)keptBegin[(k + 1) * (size_t)nUnits] - keptBegin[k * (size_t)nUnits];
+            loaded[k] = !(total > 0 && total >= maxReads);
+            dropped = dropped || !loaded[k];
+        }
+        return dropped;
+    }
+
+    long long loadedBytes(const std::vector<int>& loaded) const {
+        long long b = 0;
+        for (const BgzfChunkAt& a : chunkAt) if (loaded[(size_t)a.region]) b += chunkOf[(size_t)(&a - chunkAt.data())]->data_len;
+        return b;
+    }
+};
+
 }  // namespace plathost
 
 CALLER_EXPORT int plat_call_bgzf_regions(plat_caller* c, const plat_bgzf_region* regions, int n_regions, int n_samples,
@@ -40,141 +194,40 @@ CALLER_EXPORT int plat_call_bgzf_regions(plat_caller* c, const plat_bgzf_region*
     FetchedStage S;
     S.loaded.assign((size_t)n_regions, 0);
     std::vector<FetchedRegionHead> heads;
-    // the call's blocks and chunks, all regions: which of them load is known once the device has counted the kept records
-    std::vector<BgzfChunkAt> chunkAt;
-    std::vector<const plat_bgzf_chunk*> chunkOf;
-    std::vector<int64_t> blkOff, blkLimit;
-    std::vector<int32_t> firstU, stopBlk, stopU;
-    long long blobBytes = 0, inflated = 0;
+    BgzfFront W;
+    W.entry = entry; W.nUnits = n_samples;
     for (int k = 0; k < n_regions; ++k) {
         const plat_bgzf_region& r = regions[k];
         if (!r.samples) return PLAT_ERR_INVALID;
         heads.push_back(FetchedRegionHead{r.chrom, r.start, r.end, r.contig_seq, r.contig_len, r.dev_contig_seq});
+        W.addRegion(r.tid, r.itr_beg, r.itr_end);
         for (int i = 0; i < n_samples; ++i) {
             const plat_bgzf_sample& sm = r.samples[i];
             const plat_bam_records& bm = sm.broken_mates;
             if (sm.n_chunks < 0 || (sm.n_chunks && !sm.chunks) || bm.n_records < 0 || (bm.n_records && (!bm.data || !bm.rec_off || bm.data_len < 0))) return PLAT_ERR_INVALID;
-            for (int q = 0; q < sm.n_chunks; ++q) {
-                const plat_bgzf_chunk& ch = sm.chunks[q];
-                if (ch.data_len < 0 || (ch.data_len && !ch.data) || ch.first_uoffset < 0 || ch.first_uoffset > 65535 || ch.end_uoffset < 0 || ch.end_uoffset > 65536 ||
-                    ch.end_coffset < -1 || ch.end_coffset > ch.data_len)
-                    return PLAT_ERR_INVALID;
-                BgzfChunkAt a{k, i, q, (int)blkOff.size(), 0};
-                int endBlk = ch.end_coffset < 0 || (ch.end_coffset == ch.data_len && ch.end_uoffset == 0) ? -1 : -2;       // -2: not found yet
-                for (int64_t at = 0; at < ch.data_len;) {                  // the BSIZE chain: 18 header bytes and the trailer of every block
-                    bgzf::BlockHead h;
-                    if (bgzf::parse_header(ch.data, ch.data_len, at, &h) != 0) {
-                        c->lastError = entry + ": the BGZF blocks of " + bgzfWhere(heads.back(), a) + " do not chain: no valid block header at offset " +
-                                       std::to_string(at) + " of its data (bad magic, no BC subfield, or a block that leaves the data)";
-                        return PLAT_ERR_BAD_INPUT;
-                    }
-                    if (at == ch.end_coffset) endBlk = (int)blkOff.size();
-                    blkOff.push_back(blobBytes + at); blkLimit.push_back(blobBytes + ch.data_len);
-                    inflated += h.isize;
-                    at = h.payload + h.payload_len + 8;
-                    if (blkOff.size() >= (size_t)INT_MAX) { c->lastError = entry + ": more blocks than one call takes"; return PLAT_ERR_OVERFLOW; }
-                }
-                if (endBlk == -2) {
-                    c->lastError = entry + ": end_coffset " + std::to_string(ch.end_coffset) + " of " + bgzfWhere(heads.back(), a) + " is not a block boundary of its data";
-                    return PLAT_ERR_BAD_INPUT;
-                }
-                a.blkEnd = (int)blkOff.size();
-                chunkAt.push_back(a); chunkOf.push_back(&ch);
-                firstU.push_back(ch.first_uoffset); stopBlk.push_back(endBlk); stopU.push_back(endBlk < 0 ? 0 : ch.end_uoffset);
-                blobBytes += ch.data_len;
-            }
+            rc = W.addUnit(c, heads.back(), k, i, sm.n_chunks, sm.chunks);
+            if (rc != PLAT_OK) return rc;
         }
     }
-    const int nBlocks = (int)blkOff.size();
     Slot& z = *c->slots[0];
     void* st = z.stream;
     FetchedDeviceBuffers dev(z.ctx);
     try {
         // upload, inflate, find: back to back
-        uint8_t* dBlob = dev.alloc<uint8_t>((size_t)blobBytes);
-        { long long base = 0;
-          for (const plat_bgzf_chunk* ch : chunkOf) {
-              if (ch->data_len) ck(plat_memcpy_h2d(z.ctx, dBlob + base, ch->data, (size_t)ch->data_len, st), "plat_memcpy_h2d(blocks)");
-              base += ch->data_len;
-          } }
-        plat_bgzf_inflate_out io;
-        memset(&io, 0, sizeof io);
-        io.cap_bytes = inflated;
-        io.data = dev.alloc<uint8_t>((size_t)inflated + PLAT_BLOB_PAD); io.out_off = dev.alloc<int64_t>((size_t)nBlocks + 1); io.status = dev.alloc<int64_t>(4);
-        ck(plat_bgzf_inflate_batch(z.ctx, nBlocks, dBlob, blobBytes, dev.upload(blkOff, st), dev.upload(blkLimit, st), &io, st), "plat_bgzf_inflate_batch");
-        // every record has a block_size word and 32 fixed bytes
-        const long long capRecords = inflated / 36 + 1;
-        plat_bam_find_out fo;
-        memset(&fo, 0, sizeof fo);
-        fo.cap_records = capRecords; fo.rec_off = dev.alloc<int64_t>((size_t)capRecords); fo.rec_limit = dev.alloc<int64_t>((size_t)capRecords);
-        fo.status = dev.alloc<int64_t>(4);
-        int64_t inflateStatus[4] = {0, -1, 0, 0}, findStatus[4] = {0, -1, 0, 0};
-        std::vector<int32_t> keptBegin;                                   // [streams + 1], of the find that ran last
-        // the find over the streams of the regions `use` marks (stream = sample i of such a region, in order; its chunks lie back to back in the
-        // call's list)
-        auto find = [&](const std::vector<int>& use) {
-            std::vector<int32_t> chunkBegin(1, 0), cFirst, cEnd, cFirstU, cStopBlk, cStopU, tid, beg, end;
-            size_t q = 0;
-            for (int k = 0; k < n_regions; ++k)
-                for (int i = 0; i < n_samples; ++i) {
-                    for (; q < chunkAt.size() && chunkAt[q].region == k && chunkAt[q].sample == i; ++q) {
-                        if (!use[(size_t)k]) continue;
-                        cFirst.push_back(chunkAt[q].blkFirst); cEnd.push_back(chunkAt[q].blkEnd);
-                        cFirstU.push_back(firstU[q]); cStopBlk.push_back(stopBlk[q]); cStopU.push_back(stopU[q]);
-                    }
-                    if (!use[(size_t)k]) continue;
-                    chunkBegin.push_back((int32_t)cFirst.size());
-                    tid.push_back(regions[k].tid); beg.push_back(regions[k].itr_beg); end.push_back(regions[k].itr_end);
-                }
-            const int n = (int)tid.size();
-            plat_bam_find_in fi;
-            memset(&fi, 0, sizeof fi);
-            fi.n_streams = n; fi.n_chunks = (int)cFirst.size(); fi.n_blocks = nBlocks; fi.data = io.data; fi.out_off = io.out_off;
-            fi.chunk_blk_first = dev.upload(cFirst, st); fi.chunk_blk_end = dev.upload(cEnd, st); fi.chunk_first_uoffset = dev.upload(cFirstU, st);
-            fi.chunk_stop_blk = dev.upload(cStopBlk, st); fi.chunk_stop_uoffset = dev.upload(cStopU, st);
-            fi.stream_chunk_begin = dev.upload(chunkBegin, st);
-            fi.tid = dev.upload(tid, st); fi.beg = dev.upload(beg, st); fi.end = dev.upload(end, st);
-            fo.stream_begin = dev.alloc<int32_t>((size_t)n + 1);
-            ck(plat_bam_find_records(z.ctx, &fi, &fo, st), "plat_bam_find_records");
-            keptBegin.assign((size_t)n + 1, 0);
-            ck(plat_memcpy_d2h(z.ctx, keptBegin.data(), fo.stream_begin, keptBegin.size() * sizeof(int32_t), st), "plat_memcpy_d2h");
-            ck(plat_memcpy_d2h(z.ctx, findStatus, fo.status, sizeof findStatus, st), "plat_memcpy_d2h");
-        };
-        ck(plat_memcpy_d2h(z.ctx, inflateStatus, io.status, sizeof inflateStatus, st), "plat_memcpy_d2h");
+        W.inflate(z, dev);
         std::vector<int> all((size_t)n_regions, 1);
-        find(all);
+        W.find(z, dev, all);
         ck(plat_stream_sync(z.ctx, st), "plat_stream_sync");                // the one wait in front of the decode: two status blocks and the kept counts
-        if (inflateStatus[0] != 0) {
-            const long long b = inflateStatus[1];
-            size_t q = 0;
-            while (q + 1 < chunkAt.size() && !(b >= chunkAt[q].blkFirst && b < chunkAt[q].blkEnd)) ++q;
-            const BgzfChunkAt a = chunkAt.empty() ? BgzfChunkAt{0, 0, 0, 0, 0} : chunkAt[q];
-            c->lastError = entry + ": block " + std::to_string(b - a.blkFirst) + " of " + bgzfWhere(heads[(size_t)a.region], a) +
-                           (inflateStatus[0] == PLAT_ERR_OVERFLOW ? " does not fit the room its ISIZE words asked for"
-                                                                  : " cannot be inflated (a bad header, an invalid deflate stream, output other than ISIZE bytes, or a CRC32 mismatch)");
-            return (int)inflateStatus[0];
-        }
-        if (findStatus[0] != 0) {                                          // (every region took part: stream s is sample s % n_samples of region s / n_samples)
-            const int s = (int)findStatus[1], k = s / n_samples;
-            c->lastError = entry + ": the record walk of " + fetchedWhere(heads[(size_t)k], k, s % n_samples) +
-                           " fails (a block_size below 32, or a record or its CIGAR running past the chunk's bytes)";
-            return (int)findStatus[0];
-        }
-        // loadBAMData's bail-out (:538-541) on the kept counts
-        bool dropped = false;
-        for (int k = 0; k < n_regions; ++k) {
-            const long long total = (long long)keptBegin[(size_t)(k + 1) * n_samples] - keptBegin[(size_t)k * n_samples];
-            S.loaded[(size_t)k] = !(total > 0 && total >= maxReads);
-            dropped = dropped || !S.loaded[(size_t)k];
-        }
-        if (dropped) {                                                     // the kept records of the loaded regions alone, back to back
-            find(S.loaded);
+        rc = W.firstFailure(c, heads);
+        if (rc != PLAT_OK) return rc;
+        if (W.bailOut(maxReads, S.loaded)) {                               // the kept records of the loaded regions alone, back to back
+            W.find(z, dev, S.loaded);
             ck(plat_stream_sync(z.ctx, st), "plat_stream_sync");
-            if (findStatus[0] != 0) { c->lastError = entry + ": the record walk fails on its second run"; return (int)findStatus[0]; }
+            if (W.findStatus[0] != 0) { c->lastError = entry + ": the record walk fails on its second run"; return (int)W.findStatus[0]; }
         }
         std::vector<const plat_bam_records*> broken;
         long long nBroken = 0;
-        for (const BgzfChunkAt& a : chunkAt) if (S.loaded[(size_t)a.region]) S.linkBytes += chunkOf[(size_t)(&a - chunkAt.data())]->data_len;
+        S.linkBytes += W.loadedBytes(S.loaded);
         for (int k = 0; k < n_regions; ++k) {
             if (!S.loaded[(size_t)k]) continue;
             for (int i = 0; i < n_samples; ++i) {
@@ -184,15 +237,15 @@ CALLER_EXPORT int plat_call_bgzf_regions(plat_caller* c, const plat_bgzf_region*
             }
         }
         const int nStreams = (int)broken.size();
-        const long long nReads = keptBegin.back();
+        const long long nReads = W.keptBegin.back();
         if (nReads > INT_MAX - 2ll * nStreams - 1 || nBroken > INT_MAX - (long long)nStreams - 1) {
             c->lastError = entry + ": more reads than one call takes (call the region list in parts)";
             return PLAT_ERR_OVERFLOW;
         }
         S.nStreams = nStreams; S.N = (int)nReads; S.packed = false;
         BamDecoded F, B;
-        F.tableBegin = keptBegin;
-        bamDecodeLaunch(z, dev, io.data, inflated, fo.rec_off, fo.rec_limit, nReads, F);
+        F.tableBegin = W.keptBegin;
+        bamDecodeLaunch(z, dev, W.io.data, W.inflated, W.fo.rec_off, W.fo.rec_limit, nReads, F);
         bamDecode(z, dev, broken, B);
         ck(plat_stream_sync(z.ctx, st), "plat_stream_sync");
         rc = bamDecodeFailure(c, entry, F, B, S, heads, n_regions, n_samples);

@@ -705,3 +705,4 @@ CALLER_EXPORT void plat_caller_debug_set_order(const char* names, char* out, siz
 #include "fetched_regions.hpp"
 #include "bam_regions.hpp"
 #include "bgzf_regions.hpp"
+#include "rg_regions.hpp"

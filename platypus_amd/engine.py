@@ -877,6 +877,53 @@ class Engine:
             raise _lib.PlatypusDeviceError(int(st[0]), "stream %d" % int(st[1]), "plat_bam_find_records")
         return out
 
+    def bam_route(self, blob, rec_off, rec_end, stream_begin, group_ids, group_sample, n_samples, n_records=None, check=True):
+        """plat_bam_route_batch: the records of a merged BAM file routed to samples by their RG field, on the device.  blob / rec_off as
+        bam_decode takes them, rec_end [n] the records' ends; stream_begin [n_streams + 1]: the fetches; group_ids: the read groups' IDs
+        (bytes), group_sample [n_groups] their samples.  n_records: the record capacity handed to the call (default: len(rec_off); the
+        records behind stream_begin[-1] are not looked at).  Returns a dict: rec_off / rec_limit (the routed records, per stream sample
+        after sample), out_begin [n_streams * n_samples + 1], rec_sample [n] (-1: refused), status [4] = {error, lowest offending record,
+        routed, refused}, why (the rule that refused that record, an index of _lib.ROUTE_WHY) and guard_intact: nothing was written behind
+        any output (or, when the call is refused as invalid, at all).  A refused record raises PlatypusDeviceError (check=False:
+        returns, with status saying so); limits exceeded raise it with PLAT_ERR_UNSUPPORTED either way."""
+        torch = _torch()
+        blob = np.frombuffer(blob, dtype=np.uint8) if isinstance(blob, (bytes, bytearray)) else np.ascontiguousarray(blob, dtype=np.uint8)
+        rec_off, rec_end = np.ascontiguousarray(rec_off, dtype=np.int64), np.ascontiguousarray(rec_end, dtype=np.int64)
+        stream_begin = np.ascontiguousarray(stream_begin, dtype=np.int32)
+        n = len(rec_off) if n_records is None else int(n_records)
+        n_streams, n_groups = len(stream_begin) - 1, len(group_ids)
+        ids = [bytes(g) for g in group_ids]
+        g_off = np.concatenate([[0], np.cumsum([len(g) for g in ids])]).astype(np.int32)
+        dev = lambda a, dt: torch.from_numpy(np.append(np.asarray(a, dtype=dt), np.zeros(1, dtype=dt))).to(self.device)
+        d_blob, d_off, d_end, d_sb = dev(blob, np.uint8), dev(rec_off, np.int64), dev(rec_end, np.int64), dev(stream_begin, np.int32)
+        d_ids, d_goff, d_gs = dev(np.frombuffer(b"".join(ids), dtype=np.uint8), np.uint8), dev(g_off, np.int32), dev(group_sample, np.int32)
+        guard, f64, f32 = 16, 0x7EEE7EEE7EEE7EEE, 0x7EEE7EEE
+        keys = n_streams * int(n_samples)
+        o_off = torch.full((n + guard,), f64, dtype=torch.int64, device=self.device)
+        o_lim = torch.full((n + guard,), f64, dtype=torch.int64, device=self.device)
+        o_begin = torch.full((keys + 1 + guard,), f32, dtype=torch.int32, device=self.device)
+        o_sample = torch.full((n + guard,), f32, dtype=torch.int32, device=self.device)
+        o_status = torch.full((4 + guard,), f64, dtype=torch.int64, device=self.device)
+        o_why = torch.full((1 + guard,), f32, dtype=torch.int32, device=self.device)
+        qi = _lib.BamRouteIn(n, n_streams, n_groups, int(n_samples), d_blob.data_ptr(), len(blob), d_off.data_ptr(), d_end.data_ptr(), d_sb.data_ptr(),
+                             d_ids.data_ptr(), d_goff.data_ptr(), d_gs.data_ptr())
+        qo = _lib.BamRouteOut(o_off.data_ptr(), o_lim.data_ptr(), o_begin.data_ptr(), o_sample.data_ptr(), o_status.data_ptr(), o_why.data_ptr())
+        _lib.check(self.lib.plat_bam_route_batch(self.ctx, C.byref(qi), C.byref(qo), self._stream()), "plat_bam_route_batch")
+        self._sync()
+        off, lim, begin, smp, st, why = (t.cpu().numpy() for t in (o_off, o_lim, o_begin, o_sample, o_status, o_why))
+        invalid = int(st[0]) == -1
+        routed = 0 if invalid else int(st[2])
+        used = 0 if invalid else int(stream_begin[-1])
+        kb = 0 if invalid else keys + 1
+        intact = bool((off[routed:] == f64).all() and (lim[routed:] == f64).all() and (begin[kb:] == f32).all() and (smp[used:] == f32).all() and
+                      (st[4:] == f64).all() and (why[1:] == f32).all())
+        out = dict(rec_off=off[:routed], rec_limit=lim[:routed], out_begin=begin[:kb], rec_sample=smp[:used], status=st[:4], why=int(why[0]),
+                   guard_intact=intact)
+        if check and int(st[0]) != 0:
+            raise _lib.PlatypusDeviceError(int(st[0]), "record %d: %s" % (int(st[1]), _lib.ROUTE_WHY[out["why"]] if 0 <= out["why"] < 8 else "?"),
+                                           "plat_bam_route_batch")
+        return out
+
     # ---- SURVEY 8(f) rank 3: read statistics of the VCF INFO field --------------------------------------------
     def variant_read_stats(self, windows, bad_reads_window=11, exact=0, packed=False, gaps=None):
         """vcfINFO's per-read loop for a list of windows.  A window: dict {variants: [dict(pos, removed, added, bam_min,

@@ -8,7 +8,9 @@ text platypus_amd.caller.callVariantsInRegions writes (tests/test_native_caller_
 is host code on top of libplat_mi355x.so; like the rest of the package it has no CPU fallback.
 `FetchedRegion` / `NativeCaller.call_fetched_regions` take the reads as a BAM fetch returns them instead (the loader's
 addReadToBuffer QC and split run on the device, cwindow.pyx:560-595); `BamRegion` / `NativeCaller.call_bam_regions` take the raw BAM
-alignment records (include/platypus_caller_bam.h: ReadIterator.get, htslibWrapper.pyx:328-406, runs on the device too)."""
+alignment records (include/platypus_caller_bam.h: ReadIterator.get, htslibWrapper.pyx:328-406, runs on the device too);
+`BamFileRegion` / `BgzfFileRegion` with `NativeCaller.call_bam_regions_rg` / `call_bgzf_regions_rg` take the fetches of merged FILES and a
+read-group table (include/platypus_caller_rg.h: the records are split by sample on the device)."""
 import ctypes as C
 import os
 import subprocess
@@ -148,6 +150,32 @@ class _BgzfSample(C.Structure):
 class _BgzfRegion(C.Structure):
     _fields_ = [("chrom", C.c_char_p), ("start", C.c_int32), ("end", C.c_int32), ("contig_seq", C.c_void_p), ("contig_len", C.c_int64),
                 ("dev_contig_seq", C.c_void_p), ("tid", C.c_int32), ("itr_beg", C.c_int32), ("itr_end", C.c_int32), ("samples", C.POINTER(_BgzfSample))]
+
+
+class _BamReadGroups(C.Structure):
+    _fields_ = [("n_groups", C.c_int32), ("id", C.POINTER(C.c_char_p)), ("sample", C.c_void_p)]
+
+
+class _BamFileRecords(C.Structure):
+    _fields_ = [("records", _BamRecords), ("rec_len", C.c_void_p)]
+
+
+class _BamFile(C.Structure):
+    _fields_ = [("fetched", _BamFileRecords), ("broken_mates", _BamFileRecords)]
+
+
+class _BgzfFile(C.Structure):
+    _fields_ = [("n_chunks", C.c_int32), ("chunks", C.POINTER(_BgzfChunk)), ("broken_mates", _BamFileRecords)]
+
+
+class _BamRgRegion(C.Structure):
+    _fields_ = [("chrom", C.c_char_p), ("start", C.c_int32), ("end", C.c_int32), ("contig_seq", C.c_void_p),
+                ("contig_len", C.c_int64), ("files", C.POINTER(_BamFile)), ("dev_contig_seq", C.c_void_p)]
+
+
+class _BgzfRgRegion(C.Structure):
+    _fields_ = [("chrom", C.c_char_p), ("start", C.c_int32), ("end", C.c_int32), ("contig_seq", C.c_void_p), ("contig_len", C.c_int64),
+                ("dev_contig_seq", C.c_void_p), ("tid", C.c_int32), ("itr_beg", C.c_int32), ("itr_end", C.c_int32), ("files", C.POINTER(_BgzfFile))]
 
 
 class ReadTable:
@@ -399,6 +427,137 @@ class BgzfRegion:
         a.tid, a.itr_beg, a.itr_end = self.tid, self.itr_beg, self.itr_end
 
 
+def merge_by_read_group(entries, key):
+    """One merged file's record list from per-read-group lists: entries = [(sample_index, rg_id, reads)], each list in the order `key`
+    sorts it; a k-way merge on the next read's key, ties to the earlier entry (list the entries by sample: the lower sample).  Returns
+    (reads, aux): the merged reads and each one's aux bytes, RG:Z:<rg_id>."""
+    import heapq
+    heads = [(key(rs[0]), e, 0) for e, (_, _, rs) in enumerate(entries) if rs]
+    heapq.heapify(heads)
+    reads, aux = [], []
+    while heads:
+        _, e, i = heapq.heappop(heads)
+        _, rg, rs = entries[e]
+        reads.append(rs[i]); aux.append(b"RGZ" + (rg if isinstance(rg, bytes) else rg.encode()) + b"\0")
+        if i + 1 < len(rs):
+            heapq.heappush(heads, (key(rs[i + 1]), e, i + 1))
+    return reads, aux
+
+
+def _read_pos(r):
+    return r.pos                                                # (what a sample's stream must be sorted by: the position moved back over a leading soft clip)
+
+
+def _file_records(reads, aux):
+    """(data, rec_off, rec_len) of reads encoded back to back (synth.bam_records) with their aux bytes."""
+    from . import synth
+    data, off = synth.bam_records(reads, aux=aux)
+    return data, off, np.diff(np.append(off, len(data))).astype(np.int32)
+
+
+def _fill_file_records(t, rec):
+    data, off, ln = rec
+    t.records.n_records, t.records.data, t.records.data_len, t.records.rec_off = len(off), data.ctypes.data, len(data), off.ctypes.data
+    t.rec_len = ln.ctypes.data
+
+
+class BamFileRegion:
+    """One region of MERGED files (include/platypus_caller_rg.h): per file the uncompressed records of its fetch, in fetch order, and of
+    the broken mates it fetched, in mate-position order -- each as (data uint8 array, rec_off int64 array, rec_len int32 array).  Every
+    record carries its read group; NativeCaller.call_bam_regions_rg routes them to samples on the device."""
+
+    def __init__(self, chrom, start, end, contig_seq, files):
+        self.chrom, self.start, self.end = chrom, int(start), int(end)
+        self.contig = np.ascontiguousarray(np.frombuffer(contig_seq, dtype=np.uint8) if isinstance(contig_seq, (bytes, bytearray)) else contig_seq,
+                                           dtype=np.uint8)
+        c = lambda t: (np.ascontiguousarray(t[0], dtype=np.uint8), np.ascontiguousarray(t[1], dtype=np.int64), np.ascontiguousarray(t[2], dtype=np.int32))
+        self.files = [(c(f), c(b)) for f, b in files]
+        self._c = None
+
+    @property
+    def record_bytes(self):
+        return sum(len(f[0]) + len(b[0]) for f, b in self.files)
+
+    @classmethod
+    def from_reads(cls, chrom, start, end, fasta, files):
+        """files: per file a list of (sample_index, rg_id, reads, brokenMates) -- the read groups the file holds, reads in fetch
+        (position) order as BamRegion.from_reads takes them.  The groups' records are interleaved by a k-way merge on the next
+        record's position (the read's pos; ties to the earlier entry), the broken mates on their mate position, and every record gets
+        RG:Z:<rg_id>."""
+        out = []
+        for entries in files:
+            f = merge_by_read_group([(s, g, rs) for s, g, rs, _ in entries], _read_pos)
+            b = merge_by_read_group([(s, g, sorted(bs, key=lambda r: r.matePos)) for s, g, _, bs in entries], lambda r: r.matePos)
+            out.append((_file_records(*f), _file_records(*b)))
+        return cls(chrom, start, end, fasta._seq[chrom], out)
+
+    def fill(self, a, n_files):
+        """Write this region into the plat_bam_rg_region `a` (the arrays stay owned by, and alive with, this object)."""
+        assert len(self.files) == n_files
+        if self._c is None:
+            ff = (_BamFile * len(self.files))()
+            for i, (f, b) in enumerate(self.files):
+                _fill_file_records(ff[i].fetched, f)
+                _fill_file_records(ff[i].broken_mates, b)
+            self._c = (self.chrom.encode(), self.contig.ctypes.data, len(self.contig), ff)
+        a.chrom, a.contig_seq, a.contig_len, a.files = self._c
+        a.start, a.end = self.start, self.end
+
+
+class BgzfFileRegion:
+    """One region of MERGED files as index lookups leave it (include/platypus_caller_rg.h): the iterator's window and per file the chunks
+    of its fetch (as BgzfRegion's samples hold them) and its broken mates as uncompressed records (data, rec_off, rec_len)."""
+
+    def __init__(self, chrom, start, end, contig_seq, tid, itr_beg, itr_end, files):
+        self.chrom, self.start, self.end = chrom, int(start), int(end)
+        self.tid, self.itr_beg, self.itr_end = int(tid), int(itr_beg), int(itr_end)
+        self.contig = np.ascontiguousarray(np.frombuffer(contig_seq, dtype=np.uint8) if isinstance(contig_seq, (bytes, bytearray)) else contig_seq,
+                                           dtype=np.uint8)
+        u8 = lambda d: np.frombuffer(d, dtype=np.uint8) if isinstance(d, (bytes, bytearray)) else np.ascontiguousarray(d, dtype=np.uint8)
+        self.files = [([(u8(d), int(fu), int(ec), int(eu)) for d, fu, ec, eu in chunks],
+                       (np.ascontiguousarray(b[0], dtype=np.uint8), np.ascontiguousarray(b[1], dtype=np.int64), np.ascontiguousarray(b[2], dtype=np.int32)))
+                      for chunks, b in files]
+        self._c = None
+
+    @property
+    def compressed_bytes(self):
+        return sum(len(d) for chunks, _ in self.files for d, _, _, _ in chunks)
+
+    @classmethod
+    def from_reads(cls, chrom, start, end, fasta, files, **bgzf):
+        """files: as BamFileRegion.from_reads takes them.  Each file's merged records become one BGZF stream and its chunks as
+        BgzfRegion.from_reads makes them (**bgzf: its level / strategy / block_payload / decoys / n_chunks); the iterator's window is the
+        smallest one every fetched read of every file passes."""
+        out, windows = [], []
+        for entries in files:
+            reads, aux = merge_by_read_group([(s, g, rs) for s, g, rs, _ in entries], _read_pos)
+            one = BgzfRegion.from_reads(chrom, start, end, fasta, [(reads, [])], aux=aux, **bgzf)
+            b = merge_by_read_group([(s, g, sorted(bs, key=lambda r: r.matePos)) for s, g, _, bs in entries], lambda r: r.matePos)
+            out.append((one.samples[0][0], _file_records(*b)))
+            if reads:
+                windows.append((one.tid, one.itr_beg, one.itr_end))
+        itr = (windows[0][0], min(w[1] for w in windows), max(w[2] for w in windows)) if windows else (0, int(start), int(end))
+        return cls(chrom, start, end, fasta._seq[chrom], itr[0], itr[1], itr[2], out)
+
+    def fill(self, a, n_files):
+        """Write this region into the plat_bgzf_rg_region `a` (the arrays stay owned by, and alive with, this object)."""
+        assert len(self.files) == n_files
+        if self._c is None:
+            ff = (_BgzfFile * len(self.files))()
+            keep = []
+            for i, (chunks, b) in enumerate(self.files):
+                cc = (_BgzfChunk * max(len(chunks), 1))()
+                for q, (d, fu, ec, eu) in enumerate(chunks):
+                    cc[q].data, cc[q].data_len, cc[q].first_uoffset, cc[q].end_coffset, cc[q].end_uoffset = d.ctypes.data, len(d), fu, ec, eu
+                keep.append(cc)
+                ff[i].n_chunks, ff[i].chunks = len(chunks), cc
+                _fill_file_records(ff[i].broken_mates, b)
+            self._c = (self.chrom.encode(), self.contig.ctypes.data, len(self.contig), ff, keep)
+        a.chrom, a.contig_seq, a.contig_len, a.files = self._c[:4]
+        a.start, a.end = self.start, self.end
+        a.tid, a.itr_beg, a.itr_end = self.tid, self.itr_beg, self.itr_end
+
+
 def region_from_arrays(reg, pin=False, packed=False):
     """RegionReads of a synth.config4_region_arrays() region (every read in `reads`; no badReads / brokenMates)."""
     empty = ReadTable([], [], [0], [], [], [], [], [], [], [0])
@@ -487,6 +646,10 @@ def _bind(lib):
     lib.plat_call_bgzf_regions.argtypes = [C.c_void_p, C.POINTER(_BgzfRegion), C.c_int, C.c_int, C.POINTER(C.c_char_p), C.POINTER(CallerOptions),
                                            C.POINTER(CallerQCOptions), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(_FetchedRegionInfo),
                                            C.POINTER(CallerStats)]
+    for name, struct in (("plat_call_bam_regions_rg", _BamRgRegion), ("plat_call_bgzf_regions_rg", _BgzfRgRegion)):
+        getattr(lib, name).argtypes = [C.c_void_p, C.POINTER(struct), C.c_int, C.c_int, C.POINTER(_BamReadGroups), C.c_int, C.POINTER(C.c_char_p),
+                                       C.POINTER(CallerOptions), C.POINTER(CallerQCOptions), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                       C.POINTER(_FetchedRegionInfo), C.POINTER(CallerStats)]
     lib.plat_merge_record_texts.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     lib.plat_caller_region_text_lengths.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     lib.plat_merge_region_blocks.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
@@ -711,16 +874,35 @@ class NativeCaller:
         self.read_counts; stats["input_bytes"] counts the compressed bytes."""
         return self.call_fetched_regions(regions, sample_names, options, _entry="plat_call_bgzf_regions", _struct=_BgzfRegion)
 
-    def call_fetched_regions(self, regions, sample_names, options, _entry="plat_call_fetched_regions", _struct=_FetchedRegion):
+    def call_bam_regions_rg(self, regions, read_groups, sample_names, options):
+        """regions: list of BamFileRegion (all with the same number of files); read_groups: {read-group ID: sample index} or a list of
+        (ID, sample index).  As call_bam_regions on the samples' records, with the split by read group (the second branch of loadBAMData,
+        platypusutils.pyx:573-666) on the device in front (plat_bam_route_batch): the same text, rlen, self.loaded and self.read_counts."""
+        return self.call_fetched_regions(regions, sample_names, options, _entry="plat_call_bam_regions_rg", _struct=_BamRgRegion, _groups=read_groups)
+
+    def call_bgzf_regions_rg(self, regions, read_groups, sample_names, options):
+        """regions: list of BgzfFileRegion.  As call_bam_regions_rg, from the files' BGZF blocks (inflate, find, route, decode on the device)."""
+        return self.call_fetched_regions(regions, sample_names, options, _entry="plat_call_bgzf_regions_rg", _struct=_BgzfRgRegion, _groups=read_groups)
+
+    def call_fetched_regions(self, regions, sample_names, options, _entry="plat_call_fetched_regions", _struct=_FetchedRegion, _groups=None):
         """regions: list of FetchedRegion.  The loader's work (addReadToBuffer's QC and split, isSorted, maxReads) on the device, then the
         region loop as call_regions runs it; the QC options come from the same `options`.  Returns the record lines (str); options.rlen is
         updated as the reference updates it.  self.loaded[k] (0: region k reached maxReads and was not called) and self.read_counts[k]
         (int32 [n_samples, 10]: n_good, n_bad, the 8 reason counts -- filteredReadCountsByType slots 0-6 and secondary alignments) describe
         the last call."""
         n, nS = len(regions), len(sample_names)
+        extra = ()
+        n_units = nS
+        if _groups is not None:                                              # the merged-file calls: regions of files, and the read-group table
+            n_units = len(regions[0].files) if regions else 1
+            pairs = list(_groups.items()) if isinstance(_groups, dict) else list(_groups)
+            ids = (C.c_char_p * max(len(pairs), 1))(*[g if isinstance(g, bytes) else g.encode() for g, _ in pairs])
+            smp = np.array([s for _, s in pairs], dtype=np.int32)
+            groups = _BamReadGroups(len(pairs), ids, smp.ctypes.data)
+            extra = (n_units, C.byref(groups), nS)
         arr = (_struct * max(n, 1))()
         for k, r in enumerate(regions):
-            r.fill(arr[k], nS)
+            r.fill(arr[k], n_units)
         names = (C.c_char_p * nS)(*[s.encode() for s in sample_names])
         o, q = CallerOptions.from_options(options), CallerQCOptions.from_options(options)
         counts = np.zeros((max(n, 1), nS, 10), dtype=np.int32)
@@ -728,7 +910,7 @@ class NativeCaller:
         for k in range(n):
             info[k].sample_counts = counts[k].ctypes.data
         text, length, st = C.c_void_p(), C.c_size_t(), CallerStats()
-        rc = getattr(self.lib, _entry)(self.h, arr, n, nS, names, C.byref(o), C.byref(q), C.byref(text), C.byref(length), info, C.byref(st))
+        rc = getattr(self.lib, _entry)(self.h, arr, n, *(extra or (nS,)), names, C.byref(o), C.byref(q), C.byref(text), C.byref(length), info, C.byref(st))
         if rc != 0:
             raise _lib.PlatypusDeviceError(rc, (self.lib.plat_caller_last_error(self.h) or b"").decode(), _entry)
         try:

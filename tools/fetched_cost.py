@@ -21,6 +21,12 @@ per base).
 data as "bam"): "bgzf" next to the three, with its link bytes (the compressed bytes), and "host_zlib": single-thread zlib inflate of the
 same blocks on the host (seconds, bytes in and out) -- what the device takes off the CPU.  Under rocprofv3 the run gives k_bgzf_inflate,
 k_bam_find and the other new kernels next to the decode's.
+
+--read-groups (with --bam --bgzf): the merged-file calls.  The regions get --samples samples; "bam" and "bgzf" are the existing calls on the
+pre-split samples (the baseline), "bam_rg" and "bgzf_rg" are plat_call_bam_regions_rg / plat_call_bgzf_regions_rg on the same reads as
+ONE merged file per region, two read-group IDs per sample, every record carrying its RG field (the pre-split records carry it too: the
+same bytes ride on the link) -- wall time, process CPU per region and link bytes of each, in one run.  --out FILE also writes the JSON
+there.  Under rocprofv3 the run gives k_route_tag, k_route_hist, k_route_place and the route's scans next to k_bam_core.
 """
 import argparse
 import copy
@@ -46,7 +52,12 @@ def main():
     ap.add_argument("--bam", action="store_true", help="ASCII fetched, packed fetched and raw BAM records in one run")
     ap.add_argument("--bgzf", action="store_true", help="with --bam: the BGZF call on the same records, and host zlib inflate of the same blocks")
     ap.add_argument("--level", type=int, default=6, help="zlib level of the BGZF blocks")
+    ap.add_argument("--read-groups", action="store_true", help="with --bam --bgzf: the merged-file calls next to the pre-split ones")
+    ap.add_argument("--samples", type=int, default=3, help="samples per region of the --read-groups run")
+    ap.add_argument("--out", help="also write the JSON line to this file")
     a = ap.parse_args()
+    if a.read_groups:
+        return rg_main(a)
     if a.bam or a.bgzf:
         return bam_main(a)
     opts = default_options()
@@ -157,6 +168,58 @@ def bam_main(a):
     finally:
         nc.close()
     print(json.dumps(out))
+
+
+def rg_main(a):
+    pre_bam, pre_bgzf, rg_bam, rg_bgzf, n_reads, n_bytes = [], [], [], [], 0, 0
+    nS = a.samples
+    for i in range(a.regions):
+        reg, samples = synth.config4_fetched_region(i, region_len=a.region_len, n_samples=nS)
+        fasta = H.FastaFile({reg["chrom"]: reg["ref"].tobytes()})
+        at = (reg["chrom"], reg["start"], reg["end"], fasta)
+        for rs in samples:
+            for r in rs:                                                 # bam_endpos as plat_bam_decode_batch states it
+                clip = r.cigarOps[0][1] if r.cigarOps and r.cigarOps[0][0] == 4 else 0
+                r.end = r.pos + clip + (1 if (r.bitFlag & 4) or not r.cigarOps else sum(ln for op, ln in r.cigarOps if op in (0, 2, 3, 7, 8)))
+            n_reads += len(rs)
+            n_bytes += sum(r.rlen for r in rs)
+        # two read groups per sample: the first and the second half of its reads
+        entries = [(k, "s%d.%s" % (k, ab), rs[:len(rs) // 2] if j == 0 else rs[len(rs) // 2:], []) for k, rs in enumerate(samples) for j, ab in enumerate("ab")]
+        split = [F.merge_by_read_group([e[:3] for e in entries if e[0] == k], F._read_pos) for k in range(nS)]      # (reads, aux) per sample
+        pre_bam.append(F.BamRegion(at[0], at[1], at[2], fasta._seq[at[0]], [(synth.bam_records(rs, aux=ax), synth.bam_records([])) for rs, ax in split]))
+        ones = [F.BgzfRegion.from_reads(*at, [(rs, [])], level=a.level, aux=ax) for rs, ax in split]
+        with_reads = [o for o, (rs, _) in zip(ones, split) if rs]
+        itr = (with_reads[0].tid, min(o.itr_beg for o in with_reads), max(o.itr_end for o in with_reads)) if with_reads else (0, at[1], at[2])
+        pre_bgzf.append(F.BgzfRegion(at[0], at[1], at[2], fasta._seq[at[0]], itr[0], itr[1], itr[2], [o.samples[0] for o in ones]))
+        rg_bam.append(F.BamFileRegion.from_reads(*at, [entries]))
+        rg_bgzf.append(F.BgzfFileRegion.from_reads(*at, [entries], level=a.level))
+    groups = [("s%d.%s" % (k, ab), k) for k in range(nS) for ab in "ab"]
+    names = ["S%d" % (k + 1) for k in range(nS)]
+    nc = F.NativeCaller(0, a.workers, a.per_chunk)
+    out = dict(regions=a.regions, region_len=a.region_len, samples=nS, read_groups=len(groups), reads=n_reads, read_bases=n_bytes, bgzf_level=a.level)
+    texts = {}
+    try:
+        for name, call, regs in (("bam", lambda r, n, o: nc.call_bam_regions(r, n, o), pre_bam), ("bgzf", lambda r, n, o: nc.call_bgzf_regions(r, n, o), pre_bgzf),
+                                 ("bam_rg", lambda r, n, o: nc.call_bam_regions_rg(r, groups, n, o), rg_bam),
+                                 ("bgzf_rg", lambda r, n, o: nc.call_bgzf_regions_rg(r, groups, n, o), rg_bgzf)):
+            best = None
+            for _ in range(a.reps):
+                o = default_options()
+                w0, c0 = time.perf_counter(), time.process_time()
+                texts[name] = call(regs, names, o)
+                w, c = time.perf_counter() - w0, time.process_time() - c0
+                if best is None or w < best[0]:
+                    best = (w, c, nc.stats["n_windows_called"], nc.stats["input_bytes"])
+            w, c, nw, ib = best
+            out[name] = dict(seconds=w, windows_per_sec=nw / w, cpu_seconds_per_region=c / a.regions, windows=nw, text_bytes=len(texts[name]), input_bytes=ib)
+        out["same_text"] = texts["bam"] == texts["bgzf"] == texts["bam_rg"] == texts["bgzf_rg"]
+    finally:
+        nc.close()
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
 
 
 if __name__ == "__main__":
