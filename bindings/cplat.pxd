@@ -418,6 +418,29 @@ cdef extern from "platypus_mi355x.h":
         int64_t* status
         int32_t* why
     int plat_bam_route_batch(plat_ctx* ctx, const plat_bam_route_in* inp, const plat_bam_route_out* out, void* stream) nogil
+    # candidate alleles from source VCF lines (variantutils.py:72-159,168-197 on the device)
+    ctypedef struct plat_source_variants_in:
+        int32_t n_regions
+        int32_t maxSize
+        int32_t longHaps
+        int32_t _pad
+        const uint8_t* text
+        int64_t text_len
+        const int64_t* text_off
+        const int64_t* name_hash
+    ctypedef struct plat_source_variants_out:
+        int64_t cap_variants
+        int32_t* region_begin
+        int32_t* pos
+        int64_t* rem_off
+        int32_t* n_rem
+        int64_t* add_off
+        int32_t* n_add
+        int32_t* hash
+        int32_t* line
+        int32_t* region_stats
+        int64_t* status
+    int plat_source_variants_batch(plat_ctx* ctx, const plat_source_variants_in* inp, const plat_source_variants_out* out, void* stream) nogil
     # the same for a PLAT_READS_PACKED table (one byte per base + exceptions): QC and trimming on the packed bytes, no quality array
     ctypedef struct plat_read_buffers_packed_in:
         plat_readqc_batch qc
@@ -679,3 +702,12 @@ cdef extern from "platypus_caller_rg.h":
                                   const plat_bam_read_groups* groups, int n_samples, const char* const* sample_names,
                                   plat_caller_options* options, const plat_caller_qc_options* qc, char** out_text, size_t* out_len,
                                   plat_fetched_region_info* info, plat_caller_stats* stats) nogil
+
+
+# Candidates from source VCFs (include/platypus_caller_source.h): the lines the integrator's tabix fetches returned, per region of the
+# next call; parsed on the device (plat_source_variants_batch).
+cdef extern from "platypus_caller_source.h":
+    ctypedef struct plat_source_lines:
+        const char* text
+        int64_t len
+    int plat_caller_set_source_lines(plat_caller* c, const plat_source_lines* per_region, int n_regions, int longHaps) nogil

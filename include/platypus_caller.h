@@ -20,7 +20,7 @@
  * window or one batch at a time and is what the parity tests compare this library with.
  *
  * Plain C: pointers and sizes, int status (0 = ok, negative = error of platypus_mi355x.h), no exceptions.
- * All pointers here are HOST pointers.  Not built: source VCFs (PLAT_ERR_UNSUPPORTED).
+ * All pointers here are HOST pointers.  Candidates from source VCFs: platypus_caller_source.h.
  */
 #ifndef PLATYPUS_CALLER_H
 #define PLATYPUS_CALLER_H
@@ -179,6 +179,13 @@ typedef struct plat_caller_stats {
      * (PLAT_KT_* of platypus_mi355x.h, names from plat_kernel_timer_name): the ranking a roofline entry's kernel is chosen by */
     double kernel_ms[32];
     int64_t kernel_launches[32];
+    /* plat_caller_set_source_lines: source VCF lines looked at, the candidates they gave (after set() and sorted(), summed over the regions),
+     * and the time from uploading a chunk's lines to having its candidates (sum over worker threads) */
+    int64_t n_source_lines, n_source_variants;
+    double seconds_source;
+    /* ... chunks whose lines were parsed on the device (plat_source_variants_batch; the others by the host parser), and calls of it that
+     * were repeated with room for every allele after PLAT_ERR_OVERFLOW */
+    int64_t n_source_chunks_device, n_source_retries;
 } plat_caller_stats;
 
 typedef struct plat_caller plat_caller;

@@ -793,6 +793,64 @@ typedef struct plat_bam_route_out {
 
 int plat_bam_route_batch(plat_ctx* ctx, const plat_bam_route_in* in, const plat_bam_route_out* out, void* stream);
 
+/* ---- candidate alleles from source VCF lines ---------------------------------------------------------------------
+ * Replaces  VariantCandidateReader.Variants   src/python/variantutils.py:72-159   (the loop over the lines a tabix fetch returned: ALT
+ *           split at commas, the size test, SNP / MNP / indel trimming) with  isValidVcfLine  :168-197  and the tabix proxy's
+ *           pos = atoi(POS) - 1 (TabProxies.pyx:608)
+ * for n_regions fetches whose text lines lie in one byte blob, as the fetches returned them: region k's lines are
+ * text[text_off[k] .. text_off[k + 1]), every line ended by '\n' (the last line of a region may lack it); where a region has several
+ * source files, their fetches back to back in file order.  text must be 16-byte aligned and followed by PLAT_BLOB_PAD readable bytes;
+ * text_len < 2^31 - 1024.  name_hash [n_regions]: the Python-2 string hash of the region's chromosome, as plat_stage_b_in.region_name_hash.
+ * The set() and sorted() of :161 are the caller's (they need every allele of the region at once and only the alleles).
+ *
+ * The rule, per line:
+ *   skipped   an empty line, or one that starts with '#'.  A fetch never returns either; they are counted and otherwise ignored (by
+ *             design: the reference would try to parse them)
+ *   columns   split at tabs; CHROM, POS, ID, REF and ALT are looked at and NOTHING behind the tab or newline that ends ALT is read
+ *   refused   (status PLAT_ERR_BAD_INPUT; the line yields nothing, the other lines and regions are parsed) -- where pysam raises or atoi
+ *             is undefined: fewer than five columns; a POS that is not 1 to 10 decimal digits, or above 2^31 - 1; POS - 1 + len(REF)
+ *             above 2^31 - 1 (a trimmed position would leave Variant's C int)
+ *   pos       = POS - 1; a line with pos < 0 is invalid
+ *   invalid   (isValidVcfLine: the line yields nothing, no error) REF holds a byte other than A C G T N (upper case), or any element
+ *             of ALT.split(",") does: '.', '*', '<DEL>' and lower case are invalid; an EMPTY element is valid
+ *   per ALT element, in order (lenRef, lenAlt: bytes of REF and of the element; an empty REF or element has length 0, as Python slices):
+ *             |lenAlt - lenRef| > maxSize: skipped, counted
+ *             lenRef == lenAlt == 1: (pos, REF, alt), also when they are equal
+ *             lenRef == lenAlt otherwise: equal leading bases trimmed (pos advances), then equal trailing bases; what is left is emitted
+ *               even when both are empty
+ *             otherwise, longHaps == 1: (pos, REF, alt) untrimmed
+ *             otherwise: the first base of both dropped WITHOUT comparing them (pos stays), then equal leading bases trimmed (pos
+ *               advances); no trailing trim
+ * Every loop is bounded by the end of the line's region: no input makes a lane read outside [text_off[k], text_off[k + 1]) -- apart from
+ * the aligned 16-byte words that cover the text, inside text_len + PLAT_BLOB_PAD -- or spin.
+ *
+ * Output, alleles in input order (line ascending, then ALT element ascending), the regions back to back: region_begin [n_regions + 1];
+ * per allele pos, rem_off / n_rem and add_off / n_add (OFFSETS INTO text: a trimmed allele is a substring of its line's REF or ALT, no
+ * byte goes out), hash (py2_variant_hash of (name_hash, pos, removed, added) narrowed to 32 bits: what the set of :161 probes with) and
+ * line (the line's index within its region, skipped lines counted); region_stats [4 * n_regions]: {lines, skipped, invalid, ALT
+ * elements over maxSize}; status [4] (device): {0 or the error, the lowest refused (region << 32 | line) or -1, alleles, lines}.  More
+ * alleles than cap_variants is PLAT_ERR_OVERFLOW: nothing is written behind the capacity, region_begin is clamped to it, and status[2]
+ * still counts every allele, so that a caller can size its arrays and call again.  A refused line wins over an overflow.  A text_off
+ * that does not ascend inside [0, text_len] is status {PLAT_ERR_INVALID, -1, 0, 0} and nothing else is written.
+ * The call enqueues seven kernels -- checks; line starts marked from aligned 16-byte loads, one wave per 1024 bytes; scan; the regions'
+ * first lines; one lane per line: columns, verdict, allele count; scan; one lane per line: alleles written -- keeps its marks (an
+ * eighth of the text) and per-tile counts in the context's scratch, and does not wait; nothing traps.                             */
+typedef struct plat_source_variants_in {
+    int32_t n_regions, maxSize, longHaps, _pad;
+    const uint8_t* text; int64_t text_len;
+    const int64_t* text_off; const int64_t* name_hash;
+} plat_source_variants_in;
+
+typedef struct plat_source_variants_out {
+    int64_t cap_variants;
+    int32_t* region_begin;
+    int32_t* pos; int64_t* rem_off; int32_t* n_rem; int64_t* add_off; int32_t* n_add; int32_t* hash; int32_t* line;
+    int32_t* region_stats;
+    int64_t* status;
+} plat_source_variants_out;
+
+int plat_source_variants_batch(plat_ctx* ctx, const plat_source_variants_in* in, const plat_source_variants_out* out, void* stream);
+
 /* ---- read statistics of the VCF INFO field ---------------------------------------
  * Replaces the per-variant loop over a window's reads in  cdef dict vcfINFO(...)   vcfutils.pyx:1300-1390
  * (readOverlapsVariant :901-913, readQualIsGoodVariantPosition :917-943, variantSupportedByRead :961-1072).

@@ -42,6 +42,15 @@ def call_variants(argv):
                           dp_launched=int(st.n_dp_launched), output=opts.output)))
 
 
+def read_source_lines(path):
+    """The data lines of a plain or gzip / bgzip-compressed VCF (Python's gzip reads both), as a list of bytes."""
+    import gzip
+    with open(path, "rb") as f:
+        magic = f.read(2)
+    with (gzip.open(path, "rb") if magic == b"\x1f\x8b" else open(path, "rb")) as f:
+        return [ln.rstrip(b"\r\n") for ln in f if ln.strip() and not ln.startswith(b"#")]
+
+
 def call_variants_config4(opts, n_regions):
     """BASELINE config 4 in miniature: procedurally generated regions with reads -> candidates -> windows -> records, every
     device stage batched over all windows (platypus_amd.caller.callVariantsInRegions).  Under torch.distributed.run the regions
@@ -67,7 +76,12 @@ def call_variants_config4(opts, n_regions):
     mine = sharding.regions_for_rank(n_regions, rank, world)
     t0 = time.time()
     text = io.StringIO()
-    if os.environ.get("PLAT_PYTHON_CALLER") == "1" or opts.assemble or not opts.getVariantsFromBAMs:
+    source_files = [read_source_lines(f) for f in (opts.sourceFile or [])]
+    reader = None
+    if source_files:
+        # the CLI's own stand-in for a tabix fetch: the data lines whose [POS - 1, POS - 1 + len(REF)) overlaps the region, in file order
+        reader = H.VariantCandidateReader(source_files, opts)
+    if os.environ.get("PLAT_PYTHON_CALLER") == "1" or opts.assemble or (not opts.getVariantsFromBAMs and not source_files):
         # the Python region loop (platypus_amd.caller): window lists, haplotypes and records as Python objects
         regs = [synth.config4_region(i, region_len=size, n_samples=1, read_len=int(opts.rlen)) for i in mine]
         fasta = H.FastaFile({r["chrom"]: r["ref"] for r in regs})
@@ -75,7 +89,9 @@ def call_variants_config4(opts, n_regions):
                  [H.bamReadBuffer([H.AlignedRead(x["seq"], x["qual"], x["pos"], x["mapq"], x["flag"], end=x["end"], cigarOps=x["cigar"])
                                    for x in r["samples"][0]], sample="S1")]) for r in regs]
         t0 = time.time()
+        names, opts.sourceFile = opts.sourceFile, (source_files or None)      # (the Python loop's reader takes the lines themselves)
         n_windows = caller.callVariantsInRegions(work, fasta, opts, VCF(["S1"]), text) if work else 0
+        opts.sourceFile = names
     else:
         # the native region loop (libplat_caller.so): reads as arrays, host threads, every device stage batched per chunk
         from . import fastcaller as F
@@ -86,7 +102,8 @@ def call_variants_config4(opts, n_regions):
         nc = F.NativeCaller(local % max(1, torch.cuda.device_count()), int(os.environ.get("PLAT_CALLER_WORKERS", "8")),
                             int(os.environ.get("PLAT_CALLER_CHUNK", "4")))
         t0 = time.time()
-        text.write(nc.call_regions(rr, ["S1"], opts) if rr else "")
+        lines = [b"".join(reader.texts(r["chrom"], r["start"], r["end"])) for r in regs] if reader else None
+        text.write(nc.call_regions(rr, ["S1"], opts, source_lines=lines) if rr else "")
         n_windows = nc.stats["n_windows"] if rr else 0
         nc.close()
     recs = sorted(sharding.records_from_vcf_text(text.getvalue()), key=lambda r: (sharding.chrom_key(r[0]), r[1]))

@@ -130,6 +130,16 @@ class BamRouteOut(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("rec_off", "rec_limit", "out_begin", "rec_sample", "status", "why")]
 
 
+class SourceVariantsIn(C.Structure):
+    _fields_ = [("n_regions", C.c_int32), ("maxSize", C.c_int32), ("longHaps", C.c_int32), ("_pad", C.c_int32), ("text", C.c_void_p),
+                ("text_len", C.c_int64), ("text_off", C.c_void_p), ("name_hash", C.c_void_p)]
+
+
+class SourceVariantsOut(C.Structure):
+    _fields_ = [("cap_variants", C.c_int64)] + [(k, C.c_void_p) for k in (
+        "region_begin", "pos", "rem_off", "n_rem", "add_off", "n_add", "hash", "line", "region_stats", "status")]
+
+
 ROUTE_MAX_GROUPS, ROUTE_MAX_SAMPLES, ROUTE_LDS_ID_BYTES = 2048, 256, 24576
 ROUTE_WHY = ("routed", "no RG field", "an RG field that is no string", "an RG value that is not in the table", "an aux field of unknown type",
              "a B array with a negative count", "aux data that runs past the record", "a fixed part that runs past the record")
@@ -249,6 +259,7 @@ SIGNATURES = {
     "plat_bgzf_inflate_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(BgzfInflateOut), C.c_void_p]),
     "plat_bam_find_records": (C.c_int, [C.c_void_p, C.POINTER(BamFindIn), C.POINTER(BamFindOut), C.c_void_p]),
     "plat_bam_route_batch": (C.c_int, [C.c_void_p, C.POINTER(BamRouteIn), C.POINTER(BamRouteOut), C.c_void_p]),
+    "plat_source_variants_batch": (C.c_int, [C.c_void_p, C.POINTER(SourceVariantsIn), C.POINTER(SourceVariantsOut), C.c_void_p]),
     "plat_variant_read_stats_batch": (C.c_int, [C.c_void_p, C.POINTER(InfoStatsBatch), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
     "plat_variant_info_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -263,7 +274,7 @@ SIGNATURES = {
 # entry points a stand-in library built against an earlier header may lack (the CPU suite's fake device): bind() leaves them
 # unbound there; load() still requires every declared symbol of the real library
 ADDED_LATER = ("plat_read_buffers_batch", "plat_read_buffers_packed_batch", "plat_bam_decode_batch", "plat_bgzf_inflate_batch", "plat_bam_find_records",
-               "plat_bam_route_batch",
+               "plat_bam_route_batch", "plat_source_variants_batch",
                "plat_concat_read_tables_src", "plat_pack_codes_pieces", "plat_candidates_batch_packed", "plat_gather_reads_packed",
                "plat_variant_read_stats_packed_batch")
 

@@ -2,7 +2,7 @@
 likelihoods / EM / posteriors -> VCF records.  Same names and argument meaning as the reference:
 
     callVariantsInWindow        src/cython/variantcaller.pyx:74-141
-    generateVariantsInRegion    src/cython/variantcaller.pyx:412-531   (BAM candidates + assembler tiles; source VCFs are not built)
+    generateVariantsInRegion    src/cython/variantcaller.pyx:412-531   (BAM candidates + source VCF lines + assembler tiles)
     doWeNeedToAssembleThisRegion                          :276-321
     callVariantsInRegion        src/cython/variantcaller.pyx:535-615   (loadBAMData replaced by the caller's read buffers)
 
@@ -24,8 +24,6 @@ from .vcfrecords import (genotypeCallSites, genotypeCallTuples, getHaplotypeInfo
 
 
 def _unsupported(options):
-    if getattr(options, "sourceFile", None):
-        raise NotImplementedError("candidates from a source VCF (variantutils.VariantCandidateReader) are not built")
     if getattr(options, "HLATyping", 0):
         raise NotImplementedError("HLA mode")
 
@@ -114,12 +112,18 @@ def generateVariantsInRegions(regions, refFile, options):
                                                                options.minBaseQual, options.maxReads, options.rlen, options,
                                                                options.verbosity, options.genSNPs, options.genIndels)
     out = [[] for _ in regions]
+    # vcfFileVariants (:490-493): options.sourceFile holds the source files' lines (hostapi.VariantCandidateReader); sorted, FILE_VAR
+    fromFile = [[] for _ in regions]
+    if getattr(options, "sourceFile", None):
+        reader = H.VariantCandidateReader(options.sourceFile, options)
+        fromFile = [reader.Variants(chrom, start, end) for chrom, start, end, _ in regions]
     if not options.getVariantsFromBAMs:
         rlens = [options.rlen] * len(regions)
-        if not options.assemble:
+        if not options.assemble and not any(fromFile):
             return out, rlens
-        merged = _assemblerVariants(regions, refFile, options)
+        merged = _assemblerVariants(regions, refFile, options) if options.assemble else [[] for _ in regions]
         for k, cands in enumerate(merged):
+            cands = fromFile[k] + cands                                          # vcfFileVariants + assemblerVariants (:521)
             norm = sorted(leftNormaliseIndel(v, refFile, options.rlen) for v in cands)
             out[k] = filterVariants(norm, refFile, options.rlen, options.minReads, options.maxSize, options.verbosity, options)
         return out, rlens
@@ -160,7 +164,8 @@ def generateVariantsInRegions(regions, refFile, options):
                 if computeVariantReadSupportFrac(v, b) >= options.minVarFreq or v.nAdded != v.nRemoved:
                     everyone.addVariantToList(clone(v))
         cands = sorted(_py2_heap_order(everyone.variantHeap) if exact else everyone.variantHeap.values())
-        cands.extend(clone(v) for v in extras[k])                                # rawBamVariants + assemblerVariants (:521)
+        cands.extend(clone(v) for v in fromFile[k])                              # rawBamVariants + vcfFileVariants + assemblerVariants (:521)
+        cands.extend(clone(v) for v in extras[k])
         norm = sorted(leftNormaliseIndel(v, refFile, rlens[k]) for v in cands)
         return norm, filterVariants(norm, refFile, rlens[k], options.minReads, options.maxSize, options.verbosity, options)
 

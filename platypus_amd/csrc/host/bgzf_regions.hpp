@@ -180,6 +180,7 @@ CALLER_EXPORT int plat_call_bgzf_regions(plat_caller* c, const plat_bgzf_region*
                                          const char* const* sample_names, plat_caller_options* options, const plat_caller_qc_options* qc,
                                          char** out_text, size_t* out_len, plat_fetched_region_info* info, plat_caller_stats* stats)
 {
+    SourceLinesGuard sourceGuard(c);
     int rc = checkCallArgs(c, options, out_text, out_len, n_regions, n_samples);
     if (rc != PLAT_OK) return rc;
     if (!qc || (n_regions > 0 && !regions)) return PLAT_ERR_INVALID;

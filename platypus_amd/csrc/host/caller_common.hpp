@@ -195,8 +195,12 @@ struct Slot {
     Buffer<int32_t> d_hapbegin, d_readbegin, d_start, d_end, d_flank, d_segbegin, d_ngood, d_src, d_scratch;                 // device only
     Buffer<int64_t> d_pairoff, d_gloff, d_hapoff, d_readoff;
     Buffer<uint8_t> d_hapseq, d_kind;
+    // source VCF lines (plat_source_variants_batch): the chunk's text on the device, the regions' offsets and name hashes, what comes back
+    Buffer<uint8_t> src_text;
+    View<int64_t> src_off, src_hash, src_status, src_remoff, src_addoff;
+    View<int32_t> src_begin, src_stats, src_pos, src_nrem, src_nadd, src_hashes, src_line;
     // many small arrays travel as ONE copy: the Views above lie in these blocks (Layout)
-    Arena a_tab, a_desc, a_cin, a_cout, a_mout, a_win, a_wout, a_pin, a_sin, a_sout, a_asin, a_asout, a_bin, a_bout;
+    Arena a_tab, a_desc, a_cin, a_cout, a_mout, a_win, a_wout, a_pin, a_sin, a_sout, a_asin, a_asout, a_bin, a_bout, a_srcin, a_srcout;
     // per-region capacities of plat_stage_b_batch's outputs (they are downloaded whole): doubled when a region does not fit
     int sbCapV = 320, sbCapW = 192, sbCapA = 2048;
     double t_host = 0, t_wait = 0;
@@ -514,6 +518,9 @@ struct RegionWork {
     std::vector<Item> items;
     PtrList cur;                                                           // the samples' window pointers as the loop last left them (a REFCALL line's NR)
     VarList asmVariants;                                                   // assembler candidates, tile after tile (variantcaller.pyx:496-519)
+    const char* srcText = nullptr;                                         // the region's source VCF lines (plat_caller_set_source_lines), the caller's memory
+    int64_t srcLen = 0;
+    VarList srcVariants;                                                   // ... and their candidates, set-reduced and sorted (variantutils.py:161)
     Fasta fa;
     int rlen = 0;
     std::vector<SampleView> samples;
@@ -533,11 +540,12 @@ struct RegionWork {
         std::vector<Item>().swap(items);
         VarList().swap(variants);
         VarList().swap(asmVariants);
+        VarList().swap(srcVariants);
         pool = VariantPool();
     }
 };
 
-struct Options : plat_caller_options { Switches sw; };                    // a call's options and its switches (read when the call is entered)
+struct Options : plat_caller_options { Switches sw; int srcLongHaps = 0; };     // a call's options, its switches (read when the call is entered), the source lines' longHaps
 
 static void logWindowFailure(const char* chrom, int s, int e, const char* what) {
     fprintf(stderr, "platypus caller: problem calling variants in window %s:%d-%d, skipping it: %s\n", chrom, s, e, what);

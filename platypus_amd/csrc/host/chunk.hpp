@@ -85,6 +85,9 @@ struct Chunk {
     // (assembler.pyx:1391-1425: good reads between the window pointers, badReads / brokenMates if the options say so, QCFail reads never)
     // gathered from the chunk's device table; ALL tiles of the chunk in one plat_assemble_batch
     struct Tile { int region, assemStart, assemEnd, refStart; };
+    // -- A4: the chunk's source VCF lines -> candidates (source_variants.hpp)
+    void sourceCandidates();
+    bool hasSourceLines() const { for (const RegionWork* r : regions) if (r->srcLen > 0) return true; return false; }
     void assembleLaunch();
     void assembleEnqueue();
     void assembleCollect();
@@ -159,6 +162,7 @@ struct Chunk {
         { PROF("s0.uploadReads"); uploadReads(); }
         lap(0);
         deviceB = eligibleDeviceB();
+        sourceCandidates();
         assembleLaunch();
         if (o.getVariantsFromBAMs) { PROF("s1.scanCandidates"); scanCandidates(); }
         if (s.countCells) {

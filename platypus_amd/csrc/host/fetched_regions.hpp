@@ -229,6 +229,7 @@ static int fetchedFinish(plat_caller* c, const char* who, FetchedDeviceBuffers& 
         s += n_samples;
     }
     plat_caller_stats st;
+    c->keepSourceLines(loaded);                                          // (plat_caller_set_source_lines lists every region of the front end's call)
     rc = plat_call_regions(c, called.data(), (int)called.size(), n_samples, sample_names, options, out_text, out_len, &st);
     if (rc != PLAT_OK) return rc;
     std::vector<int64_t> lengths((size_t)n_regions, 0);
@@ -270,6 +271,7 @@ CALLER_EXPORT int plat_call_fetched_regions(plat_caller* c, const plat_fetched_r
                                             const char* const* sample_names, plat_caller_options* options, const plat_caller_qc_options* qc,
                                             char** out_text, size_t* out_len, plat_fetched_region_info* info, plat_caller_stats* stats)
 {
+    SourceLinesGuard sourceGuard(c);
     int rc = checkCallArgs(c, options, out_text, out_len, n_regions, n_samples);
     if (rc != PLAT_OK) return rc;
     if (!qc || (n_regions > 0 && !regions)) return PLAT_ERR_INVALID;

@@ -1,6 +1,6 @@
 // region_caller.cpp -- libplat_caller.so: the region loop around the device hot path (include/platypus_caller.h).
 //
-//   generateVariantsInRegion      src/cython/variantcaller.pyx:412-531   (BAM candidates; assembler / source VCFs not built here)
+//   generateVariantsInRegion      src/cython/variantcaller.pyx:412-531   (BAM candidates, assembler tiles, source VCF lines: source_variants.hpp)
 //   callVariantsInRegion          src/cython/variantcaller.pyx:535-615
 //   callVariantsInWindow          src/cython/variantcaller.pyx:74-141
 //   ReadArray window pointers     src/cython/cwindow.pyx:176-264
@@ -28,6 +28,7 @@
 // record texts.  Same text as platypus_amd/caller.py::callVariantsInRegions (tests/test_native_caller_*.py).
 #include <sys/mman.h>
 
+#include "../../../include/platypus_caller_source.h"
 #include "caller_common.hpp"
 #include "chunk.hpp"
 #include "stage_a.hpp"
@@ -91,6 +92,23 @@ struct plat_caller {
     std::vector<std::unique_ptr<Slot>> slots;
     std::string lastError;
     std::vector<int64_t> lastLengths;                                       // bytes of record text of every region of the last call, in list order
+    // plat_caller_set_source_lines: the next call's source VCF lines per region (the caller's memory), cleared when that call returns
+    std::vector<plat_source_lines> sourceLines;
+    bool sourceSet = false;
+    int sourceLongHaps = 0;
+    // a front end that drops regions (the loader's maxReads bail-out) before it calls plat_call_regions keeps the lines of the regions it passes on
+    void keepSourceLines(const std::vector<int>& loaded) {
+        if (!sourceSet || sourceLines.size() != loaded.size()) return;
+        size_t j = 0;
+        for (size_t k = 0; k < loaded.size(); ++k) if (loaded[k]) sourceLines[j++] = sourceLines[k];
+        sourceLines.resize(j);
+    }
+};
+// every entry point holds one: the source lines apply to ONE call and are gone when it returns, however it returns
+struct SourceLinesGuard {
+    plat_caller* c;
+    explicit SourceLinesGuard(plat_caller* c_) : c(c_) {}
+    ~SourceLinesGuard() { if (c) { c->sourceLines.clear(); c->sourceSet = false; c->sourceLongHaps = 0; } }
 };
 
 CALLER_EXPORT void plat_caller_default_options(plat_caller_options* o) {
@@ -236,6 +254,7 @@ struct StreamFeed : Feed {
     std::atomic<bool>& failed;
     double tLoad = 0, tWait = 0;
     const bool check;                                                      // PLAT_CALLER_CHECK_HINTS
+    const std::vector<plat_source_lines>* sourceLines = nullptr;           // plat_caller_set_source_lines: by list position
     StreamFeed(int n_, int nS, int per_, int workers, int maxSize_, int rlen0, plat_region_load_fn l, void* u, int nSlots, const Switches& sw, std::atomic<bool>& f)
         : n(n_), nSamples(nS), per(per_), nChunks(0), maxSize(maxSize_), load(l), user(u), work((size_t)n_), desc((size_t)n_),
           slotOf((size_t)n_, -1), longest((size_t)n_, 0), loaded((size_t)n_, 0), bound(chunkBounds(n_, per_, workers, sw.evenTail)), chunkOf((size_t)n_, 0), rlen(rlen0), failed(f), check(sw.checkHints) {
@@ -268,6 +287,7 @@ struct StreamFeed : Feed {
             std::unique_ptr<RegionWork> r;
             try { r = makeRegionWork(&desc[(size_t)idx], idx, nSamples, lg, check); }
             catch (const std::exception& e) { fail(PLAT_ERR_BAD_INPUT, e.what()); return; }
+            if (sourceLines) { r->srcText = (*sourceLines)[(size_t)idx].text; r->srcLen = (*sourceLines)[(size_t)idx].len; }
             const double dt = secs(t0, Clock::now());
             std::lock_guard<std::mutex> g(m);
             work[(size_t)idx] = std::move(r); slotOf[(size_t)idx] = slot; longest[(size_t)idx] = lg; loaded[(size_t)idx] = 1;
@@ -414,8 +434,12 @@ static int finishText(plat_caller* c, std::vector<std::unique_ptr<RegionWork>>& 
 static int checkCallArgs(plat_caller* c, const plat_caller_options* options, char** out_text, size_t* out_len, int n_regions, int n_samples) {
     if (!c || !options || !out_text || !out_len || n_regions < 0 || n_samples < 1) return PLAT_ERR_INVALID;
     *out_text = nullptr; *out_len = 0;
-    if (!options->getVariantsFromBAMs && !options->assemble) {
-        // (the reference then has no candidates at all unless a source VCF is given, which is not built)
+    if (c->sourceSet && (int)c->sourceLines.size() != n_regions) {
+        c->lastError = "plat_caller_set_source_lines was given " + std::to_string(c->sourceLines.size()) + " regions, the call has " + std::to_string(n_regions);
+        return PLAT_ERR_INVALID;
+    }
+    if (!options->getVariantsFromBAMs && !options->assemble && !c->sourceSet) {
+        // (the reference then has no candidates at all unless a source VCF is given: plat_caller_set_source_lines)
         c->lastError = "getVariantsFromBAMs=0 without assemble=1 leaves no candidate source (source VCFs are not built)";
         return PLAT_ERR_UNSUPPORTED;
     }
@@ -425,6 +449,7 @@ static int checkCallArgs(plat_caller* c, const plat_caller_options* options, cha
 CALLER_EXPORT int plat_call_regions(plat_caller* c, const plat_region* regions, int n_regions, int n_samples, const char* const* sample_names,
                                     plat_caller_options* options, char** out_text, size_t* out_len, plat_caller_stats* stats)
 {
+    SourceLinesGuard sourceGuard(c);
     int rc = checkCallArgs(c, options, out_text, out_len, n_regions, n_samples);
     if (rc != PLAT_OK) return rc;
     if (n_regions > 0 && !regions) return PLAT_ERR_INVALID;
@@ -432,7 +457,7 @@ CALLER_EXPORT int plat_call_regions(plat_caller* c, const plat_region* regions, 
     plat_caller_stats st;
     memset(&st, 0, sizeof st);
     st.n_regions = n_regions;
-    const Options o{*options, Switches::read()};                           // (the PLAT_CALLER_* switches as they are now: switches.hpp)
+    const Options o{*options, Switches::read(), c->sourceLongHaps};        // (the PLAT_CALLER_* switches as they are now: switches.hpp)
     std::vector<std::unique_ptr<RegionWork>> work;
     int rlen = options->rlen;
     for (int k = 0; k < n_regions; ++k) {
@@ -442,6 +467,7 @@ CALLER_EXPORT int plat_call_regions(plat_caller* c, const plat_region* regions, 
         catch (const std::exception& e) { c->lastError = e.what(); return PLAT_ERR_BAD_INPUT; }          // (a hint that does not describe its table, PLAT_CALLER_CHECK_HINTS=1)
         rlen = nextRlen(rlen, longest, options->maxSize, options->getVariantsFromBAMs);
         r->rlen = rlen;
+        if (c->sourceSet) { r->srcText = c->sourceLines[(size_t)k].text; r->srcLen = c->sourceLines[(size_t)k].len; }
         work.push_back(std::move(r));
     }
     std::atomic<bool> failed(false);
@@ -460,6 +486,7 @@ CALLER_EXPORT int plat_call_regions_stream(plat_caller* c, int n_regions, int n_
                                            plat_region_load_fn load, void* user, int n_slots, int n_loader_threads, char** out_text, size_t* out_len,
                                            plat_caller_stats* stats)
 {
+    SourceLinesGuard sourceGuard(c);
     int rc = checkCallArgs(c, options, out_text, out_len, n_regions, n_samples);
     if (rc != PLAT_OK) return rc;
     const int per = c->regionsPerChunk, nWorkers = (int)c->slots.size();
@@ -472,10 +499,11 @@ CALLER_EXPORT int plat_call_regions_stream(plat_caller* c, int n_regions, int n_
     plat_caller_stats st;
     memset(&st, 0, sizeof st);
     st.n_regions = n_regions;
-    const Options o{*options, Switches::read()};                           // (the PLAT_CALLER_* switches as they are now: switches.hpp)
+    const Options o{*options, Switches::read(), c->sourceLongHaps};        // (the PLAT_CALLER_* switches as they are now: switches.hpp)
     std::atomic<bool> failed(false);
     StreamFeed feed(n_regions, n_samples, per, nWorkers, options->maxSize, options->rlen, load, user, n_slots, o.sw, failed);
     feed.fromBams = options->getVariantsFromBAMs;
+    if (c->sourceSet) feed.sourceLines = &c->sourceLines;
     std::vector<std::thread> loaders;
     for (int i = 0; i < std::min(n_loader_threads, std::max(1, n_regions)); ++i) loaders.emplace_back([&feed] { feed.loader(); });
     rc = runWorkers(c, feed, failed, o, n_samples, sample_names, st, std::max(1, feed.nChunks));
@@ -702,6 +730,7 @@ CALLER_EXPORT void plat_caller_debug_set_order(const char* names, char* out, siz
     for (const std::string& k : py2_set_order(in)) { if (!t.empty()) t += '\n'; t += k; }
     snprintf(out, cap, "%s", t.c_str());
 }
+#include "source_variants.hpp"
 #include "fetched_regions.hpp"
 #include "bam_regions.hpp"
 #include "bgzf_regions.hpp"

@@ -184,6 +184,7 @@ CALLER_EXPORT int plat_call_bam_regions_rg(plat_caller* c, const plat_bam_rg_reg
                                            plat_caller_options* options, const plat_caller_qc_options* qc, char** out_text, size_t* out_len,
                                            plat_fetched_region_info* info, plat_caller_stats* stats)
 {
+    SourceLinesGuard sourceGuard(c);
     int rc = checkCallArgs(c, options, out_text, out_len, n_regions, n_samples);
     if (rc != PLAT_OK) return rc;
     if (!qc || n_files < 1 || (n_regions > 0 && !regions)) return PLAT_ERR_INVALID;
@@ -265,6 +266,7 @@ CALLER_EXPORT int plat_call_bgzf_regions_rg(plat_caller* c, const plat_bgzf_rg_r
                                             plat_caller_options* options, const plat_caller_qc_options* qc, char** out_text, size_t* out_len,
                                             plat_fetched_region_info* info, plat_caller_stats* stats)
 {
+    SourceLinesGuard sourceGuard(c);
     int rc = checkCallArgs(c, options, out_text, out_len, n_regions, n_samples);
     if (rc != PLAT_OK) return rc;
     if (!qc || n_files < 1 || (n_regions > 0 && !regions)) return PLAT_ERR_INVALID;

@@ -7,6 +7,7 @@ namespace plathost {
 
 inline bool Chunk::eligibleDeviceB() const {
     if (nInd != 1 || o.assemble || o.outputRefCalls || !o.getVariantsFromBAMs || o.maxHaplotypes < 3 || regions.empty()) return false;
+    if (hasSourceLines()) return false;                                 // (a region with source VCF lines takes the host's stage B, as assembly runs do)
     return !o.sw.hostB;                                                 // (measurements / tests: stage B on the host)
 }
 

@@ -107,10 +107,11 @@ inline void Chunk::regionVariants(RegionWork& r, int scan0) {
         for (const CandKey& k : keys) if (passesSupport(r, i, k)) pass(k.pos, k.rem, k.nrem, k.add, k.nadd, k.count);
     }
     std::stable_sort(everyone.begin(), everyone.end(), variantLess);    // getCandidates(): sorted(values)
-    // rawBamVariants + assemblerVariants (:521), left-normalised, sorted, filtered (:523-531)
+    // rawBamVariants + vcfFileVariants + assemblerVariants (:521), left-normalised, sorted, filtered (:523-531)
     VarList norm;
     auto finish = [&](const VarList& raw) {
         VarList all(raw);
+        all.insert(all.end(), r.srcVariants.begin(), r.srcVariants.end());
         all.insert(all.end(), r.asmVariants.begin(), r.asmVariants.end());
         norm.clear();
         for (Variant* v : all) norm.push_back(leftNormaliseIndel(v, r.fa, r.rlen, r.pool));
@@ -119,6 +120,8 @@ inline void Chunk::regionVariants(RegionWork& r, int scan0) {
     };
     std::vector<Variant> asmBackup;                                     // (filterVariants adds the support of equal neighbours up in place)
     for (const Variant* v : r.asmVariants) asmBackup.push_back(*v);
+    std::vector<Variant> srcBackup;
+    for (const Variant* v : r.srcVariants) srcBackup.push_back(*v);
     finish(everyone);
     // `sorted` is stable: candidates that compare equal (two alleles of one type and length at one position) stay in the order the
     // all-samples dictionary yields them, a Python-2 dict keyed by Variant (hash of (refName, refPos, removed, added),
@@ -184,6 +187,7 @@ inline void Chunk::regionVariants(RegionWork& r, int scan0) {
         for (int k : py2_dict_slot_order(allHash)) everyone.push_back(all[(size_t)k]);     // allSampleVarCandGen.variantHeap.values()
         std::stable_sort(everyone.begin(), everyone.end(), variantLess);
         for (size_t k = 0; k < asmBackup.size(); ++k) *r.asmVariants[k] = asmBackup[k];
+        for (size_t k = 0; k < srcBackup.size(); ++k) *r.srcVariants[k] = srcBackup[k];
         finish(everyone);
     }
 }

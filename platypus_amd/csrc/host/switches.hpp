@@ -17,6 +17,7 @@
 //   EVEN_TAIL                    not beginning '0'  the last round of chunks is cut into equal parts, one per worker      measurements ("0": whole chunks to the end)
 //   KEEP_SPARE                   begins with '1'    a worker keeps its spare window storage for the next call             measurements (slower: region_caller.cpp)
 //   CHECK_HINTS                  begins with '1'    plat_read_table.longest_read / most_bases are checked against a walk  tests, a loader under suspicion
+//   HOST_SOURCE                  begins with '1'    source VCF lines are parsed by the host parser, not on the device      tests, measurements (the kernel's A/B)
 //   TRACE                        set at all         per-chunk / per-call lines on stderr;                                 measurements
 //                                begins with '1'    ... and the per-stage seconds of every call (traceStages)
 // PLAT_CALLER_POLL_US is not here: it is a property of the caller object and is read where that is made (plat_caller_create).
@@ -28,7 +29,7 @@ namespace plathost {
 
 struct Switches {
     bool noCodes = false, expand = false, hostTally = false, hostB = false, noDeviceReplay = false, hostInfo = false, firstOccurrenceOrder = false;
-    bool evenTail = true, keepSpare = false, checkHints = false, noRefCtx = false, noRefPrefetch = false;
+    bool evenTail = true, keepSpare = false, checkHints = false, noRefCtx = false, noRefPrefetch = false, hostSource = false;
     bool trace = false, traceStages = false;                              // PLAT_CALLER_TRACE: set at all / begins with '1'
 
     static Switches read() {
@@ -47,6 +48,7 @@ struct Switches {
         w.noRefPrefetch = isOne("PLAT_CALLER_NO_REFPREFETCH");
         w.keepSpare = isOne("PLAT_CALLER_KEEP_SPARE");
         w.checkHints = isOne("PLAT_CALLER_CHECK_HINTS");
+        w.hostSource = isOne("PLAT_CALLER_HOST_SOURCE");
         w.trace = isSet("PLAT_CALLER_TRACE");
         w.traceStages = isOne("PLAT_CALLER_TRACE");
         return w;

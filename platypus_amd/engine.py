@@ -924,6 +924,48 @@ class Engine:
                                            "plat_bam_route_batch")
         return out
 
+    def source_variants(self, regions, names, max_size=1500, long_haps=0, cap_variants=None, lead=0, text_off=None, check=True):
+        """plat_source_variants_batch: VariantCandidateReader.Variants' line loop (variantutils.py:72-159,168-197) on the device.  regions:
+        per region the bytes a fetch returned (the source files' fetches back to back); names: the regions' chromosomes (bytes / str) or
+        their Python-2 string hashes.  lead: bytes of other text in front of the first region (the regions then start at text_off[0] = lead);
+        text_off: offsets to hand over instead of the ones the regions' lengths give (tests of the checks).  Returns a dict: region_begin
+        [n + 1], pos / rem_off / n_rem / add_off / n_add / hash / line [alleles written], stats [n, 4] = {lines, skipped, invalid, over
+        maxSize}, status [4] = {error, lowest refused (region << 32 | line), alleles, lines}, text (the uploaded bytes: what the offsets
+        index) and guard_intact: nothing was written behind the capacity (or, when the call is refused as invalid, at all).  A refused line
+        or a short capacity raises PlatypusDeviceError (check=False: returns, with status saying so)."""
+        from .vcfrecords import _py2_string_hash
+        torch = _torch()
+        blobs = [bytes(r) for r in regions]
+        n = len(blobs)
+        text = b"\n" * int(lead) + b"".join(blobs)
+        off = np.concatenate([[int(lead)], int(lead) + np.cumsum([len(b) for b in blobs])]).astype(np.int64) if text_off is None else np.asarray(text_off, dtype=np.int64)
+        hashes = np.array([(h if isinstance(h, int) else _py2_string_hash(h.decode("latin-1") if isinstance(h, bytes) else h)) for h in names], dtype=np.uint64).view(np.int64)
+        cap = len(text) + 1 if cap_variants is None else int(cap_variants)
+        guard, f64, f32 = 16, 0x7EEE7EEE7EEE7EEE, 0x7EEE7EEE
+        d_text = torch.from_numpy(np.frombuffer(text + b"\xff" * (_lib.PLAT_BLOB_PAD + 16), dtype=np.uint8).copy()).to(self.device)
+        d_off = torch.from_numpy(np.append(off, 0)).to(self.device)
+        d_hash = torch.from_numpy(np.append(hashes, 0)).to(self.device)
+        i32 = lambda k: torch.full((k + guard,), f32, dtype=torch.int32, device=self.device)
+        i64 = lambda k: torch.full((k + guard,), f64, dtype=torch.int64, device=self.device)
+        g = dict(region_begin=i32(n + 1), pos=i32(cap), rem_off=i64(cap), n_rem=i32(cap), add_off=i64(cap), n_add=i32(cap), hash=i32(cap), line=i32(cap),
+                 region_stats=i32(4 * n), status=i64(4))
+        qi = _lib.SourceVariantsIn(n, int(max_size), int(long_haps), 0, d_text.data_ptr(), len(text), d_off.data_ptr(), d_hash.data_ptr())
+        qo = _lib.SourceVariantsOut(cap, *[g[k].data_ptr() for k, _ in _lib.SourceVariantsOut._fields_[1:]])
+        _lib.check(self.lib.plat_source_variants_batch(self.ctx, C.byref(qi), C.byref(qo), self._stream()), "plat_source_variants_batch")
+        self._sync()
+        h = {k: v.cpu().numpy() for k, v in g.items()}
+        st = h["status"]
+        invalid = int(st[0]) == -1
+        written = 0 if invalid else min(int(st[2]), cap)
+        sizes = dict(region_begin=0 if invalid else n + 1, region_stats=0 if invalid else 4 * n, status=4)
+        intact = all(bool((h[k][sizes.get(k, written):] == (f64 if h[k].dtype == np.int64 else f32)).all()) for k in h)
+        out = {k: h[k][:sizes.get(k, written)] for k in h if k not in ("region_stats", "status")}
+        out.update(stats=h["region_stats"][:sizes["region_stats"]].reshape(-1, 4), status=st[:4], text=text, guard_intact=intact)
+        if check and int(st[0]) != 0:
+            raise _lib.PlatypusDeviceError(int(st[0]), "region %d line %d" % (int(st[1]) >> 32, int(st[1]) & 0xffffffff) if int(st[0]) == -9 else "%d alleles" % int(st[2]),
+                                           "plat_source_variants_batch")
+        return out
+
     # ---- SURVEY 8(f) rank 3: read statistics of the VCF INFO field --------------------------------------------
     def variant_read_stats(self, windows, bad_reads_window=11, exact=0, packed=False, gaps=None):
         """vcfINFO's per-read loop for a list of windows.  A window: dict {variants: [dict(pos, removed, added, bam_min,

@@ -85,7 +85,9 @@ class CallerStats(C.Structure):
                 ("n_regions_stage_b_host", C.c_int64), ("n_windows_stage_b_host", C.c_int64), ("n_regions_dict_replay_device", C.c_int64),
                 ("seconds_worker_cpu", C.c_double), ("seconds_kernel_unpack", C.c_double), ("seconds_kernel_candidates", C.c_double),
                 ("unpack_bytes", C.c_int64), ("candidates_bytes", C.c_int64), ("n_unpack_launches", C.c_int64), ("n_candidates_launches", C.c_int64),
-                ("kernel_ms", C.c_double * 32), ("kernel_launches", C.c_int64 * 32)]
+                ("kernel_ms", C.c_double * 32), ("kernel_launches", C.c_int64 * 32),
+                ("n_source_lines", C.c_int64), ("n_source_variants", C.c_int64), ("seconds_source", C.c_double),
+                ("n_source_chunks_device", C.c_int64), ("n_source_retries", C.c_int64)]
 
     STAGES = ("upload", "candidate_scan", "variants_windows_haplotypes", "greedy_rounds", "window_batch", "posteriors", "read_stats_calls", "text")
 
@@ -94,6 +96,11 @@ class CallerStats(C.Structure):
         d["seconds_stage"] = dict(zip(self.STAGES, list(self.seconds_stage)))
         d["kernel_ms"], d["kernel_launches"] = list(self.kernel_ms), list(self.kernel_launches)
         return d
+
+
+class _SourceLines(C.Structure):
+    """plat_source_lines (include/platypus_caller_source.h)."""
+    _fields_ = [("text", C.c_void_p), ("len", C.c_int64)]
 
 
 class _FetchedReads(C.Structure):
@@ -610,6 +617,7 @@ def build(verbose=False):
     _lib.build()
     srcs = [os.path.join(HOST_SRC, f) for f in sorted(os.listdir(HOST_SRC)) if f.endswith((".cpp", ".hpp"))]
     srcs.append(os.path.join(_lib.CSRC, "bgzf_inflate.hpp"))           # (the BGZF front end reads block headers with the device's own parser)
+    srcs.append(os.path.join(_lib.CSRC, "source_rule.hpp"))            # (... and the host parser of source VCF lines is the device's rule)
     if os.path.exists(LIB_PATH) and os.path.getmtime(LIB_PATH) >= max([os.path.getmtime(f) for f in srcs] + [os.path.getmtime(_lib.LIB_PATH)]):
         return LIB_PATH
     # (-O3: the region loop is many small functions over small containers; +10 % windows/s over -O2 on the same box.  No -march: the library
@@ -653,6 +661,7 @@ def _bind(lib):
     lib.plat_merge_record_texts.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     lib.plat_caller_region_text_lengths.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     lib.plat_merge_region_blocks.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
+    lib.plat_caller_set_source_lines.argtypes = [C.c_void_p, C.POINTER(_SourceLines), C.c_int, C.c_int]
     lib.plat_caller_free.argtypes = [C.c_void_p]
     lib.plat_caller_free.restype = None
     lib.plat_caller_last_error.argtypes = [C.c_void_p]
@@ -842,10 +851,25 @@ class NativeCaller:
         except Exception:
             pass
 
-    def call_regions(self, regions, sample_names, options):
+    def set_source_lines(self, source_lines, long_haps=0):
+        """plat_caller_set_source_lines: the source VCF lines of the NEXT call, per region of its list -- bytes (the text the region's fetches
+        returned, the files' fetches back to back) or a list of bytes (one per source file).  Returns what keeps the memory alive: hold it
+        until that call has returned.  The lines are gone when that call returns."""
+        texts = [b"".join(t) if isinstance(t, (list, tuple)) else bytes(t) for t in source_lines]
+        arr = (_SourceLines * max(len(texts), 1))()
+        for k, t in enumerate(texts):
+            arr[k].text, arr[k].len = C.cast(C.c_char_p(t), C.c_void_p).value if t else None, len(t)
+        rc = self.lib.plat_caller_set_source_lines(self.h, arr, len(texts), int(long_haps))
+        if rc != 0:
+            raise _lib.PlatypusDeviceError(rc, "plat_caller_set_source_lines", "plat_caller_set_source_lines")
+        return texts, arr
+
+    def call_regions(self, regions, sample_names, options, source_lines=None):
         """regions: list of RegionReads.  Returns the record lines of all regions (str), in region order; options.rlen is updated
-        as the reference updates it."""
+        as the reference updates it.  source_lines: per region the text its source VCF fetches returned (set_source_lines; longHaps is
+        options.longHaps): candidates from the source join those of the reads."""
         n, nS = len(regions), len(sample_names)
+        keep = self.set_source_lines(source_lines, getattr(options, "longHaps", 0)) if source_lines is not None else None
         arr = (_Region * max(n, 1))()
         for k, r in enumerate(regions):
             r.fill(arr[k], nS)
@@ -853,6 +877,7 @@ class NativeCaller:
         o = CallerOptions.from_options(options)
         text, length, st = C.c_void_p(), C.c_size_t(), CallerStats()
         rc = self.lib.plat_call_regions(self.h, arr, n, nS, names, C.byref(o), C.byref(text), C.byref(length), C.byref(st))
+        del keep
         if rc != 0:
             raise _lib.PlatypusDeviceError(rc, (self.lib.plat_caller_last_error(self.h) or b"").decode(), "plat_call_regions")
         try:
@@ -863,10 +888,10 @@ class NativeCaller:
         self.stats = st.as_dict()
         return out
 
-    def call_bam_regions(self, regions, sample_names, options):
+    def call_bam_regions(self, regions, sample_names, options, source_lines=None):
         """regions: list of BamRegion.  As call_fetched_regions, with ReadIterator.get (htslibWrapper.pyx:328-406) on the device in front: the
         records are uploaded as they are and decoded there (plat_bam_decode_batch); the same text, rlen, self.loaded and self.read_counts."""
-        return self.call_fetched_regions(regions, sample_names, options, _entry="plat_call_bam_regions", _struct=_BamRegion)
+        return self.call_fetched_regions(regions, sample_names, options, _entry="plat_call_bam_regions", _struct=_BamRegion, source_lines=source_lines)
 
     def call_bgzf_regions(self, regions, sample_names, options):
         """regions: list of BgzfRegion.  As call_bam_regions, with the BGZF blocks inflated (plat_bgzf_inflate_batch) and sam_itr_next applied
@@ -884,13 +909,15 @@ class NativeCaller:
         """regions: list of BgzfFileRegion.  As call_bam_regions_rg, from the files' BGZF blocks (inflate, find, route, decode on the device)."""
         return self.call_fetched_regions(regions, sample_names, options, _entry="plat_call_bgzf_regions_rg", _struct=_BgzfRgRegion, _groups=read_groups)
 
-    def call_fetched_regions(self, regions, sample_names, options, _entry="plat_call_fetched_regions", _struct=_FetchedRegion, _groups=None):
+    def call_fetched_regions(self, regions, sample_names, options, _entry="plat_call_fetched_regions", _struct=_FetchedRegion, _groups=None, source_lines=None):
         """regions: list of FetchedRegion.  The loader's work (addReadToBuffer's QC and split, isSorted, maxReads) on the device, then the
         region loop as call_regions runs it; the QC options come from the same `options`.  Returns the record lines (str); options.rlen is
         updated as the reference updates it.  self.loaded[k] (0: region k reached maxReads and was not called) and self.read_counts[k]
         (int32 [n_samples, 10]: n_good, n_bad, the 8 reason counts -- filteredReadCountsByType slots 0-6 and secondary alignments) describe
-        the last call."""
+        the last call.  source_lines: as call_regions takes them, one entry per region of THIS list (the regions the loader gives up on
+        included: their lines are dropped with them)."""
         n, nS = len(regions), len(sample_names)
+        keep_source = self.set_source_lines(source_lines, getattr(options, "longHaps", 0)) if source_lines is not None else None
         extra = ()
         n_units = nS
         if _groups is not None:                                              # the merged-file calls: regions of files, and the read-group table
@@ -911,6 +938,7 @@ class NativeCaller:
             info[k].sample_counts = counts[k].ctypes.data
         text, length, st = C.c_void_p(), C.c_size_t(), CallerStats()
         rc = getattr(self.lib, _entry)(self.h, arr, n, *(extra or (nS,)), names, C.byref(o), C.byref(q), C.byref(text), C.byref(length), info, C.byref(st))
+        del keep_source
         if rc != 0:
             raise _lib.PlatypusDeviceError(rc, (self.lib.plat_caller_last_error(self.h) or b"").decode(), _entry)
         try:
@@ -932,12 +960,13 @@ class NativeCaller:
             raise _lib.PlatypusDeviceError(rc, "no call yet, or another number of regions", "plat_caller_region_text_lengths")
         return out[:n_regions]
 
-    def call_stream(self, n_regions, load, user, sample_names, options, n_slots, n_loaders=2, raw=False):
+    def call_stream(self, n_regions, load, user, sample_names, options, n_slots, n_loaders=2, raw=False, source_lines=None):
         """plat_call_regions_stream: regions loaded on demand.  `load`: a plat_region_load_fn -- the address of a native function (int,
         e.g. tools/synth's generator: no Python in the loader threads) or a Python callable (index, slot, region_struct) -> status (wrapped;
         tests).  Returns the record lines of all regions in region order: str, or bytes with raw=True (a whole-genome share is ~100 MB of
         text: every decode / encode of it is a pass through memory the caller may not want)."""
         nS = len(sample_names)
+        keep_source = self.set_source_lines(source_lines, getattr(options, "longHaps", 0)) if source_lines is not None else None   # (as call_regions)
         keep = None
         if callable(load):
             fn = load
@@ -956,7 +985,7 @@ class NativeCaller:
         text, length, st = C.c_void_p(), C.c_size_t(), CallerStats()
         rc = self.lib.plat_call_regions_stream(self.h, n_regions, nS, names, C.byref(o), load, user, n_slots, n_loaders, C.byref(text), C.byref(length),
                                                C.byref(st))
-        del keep
+        del keep, keep_source
         if rc != 0:
             raise _lib.PlatypusDeviceError(rc, (self.lib.plat_caller_last_error(self.h) or b"").decode(), "plat_call_regions_stream")
         out = _native_text(self.lib, text, length.value, raw)

@@ -10,6 +10,7 @@ done by the HIP library (never on the CPU).
     DiploidGenotype              src/cython/cgenotype.pyx:131-218
     Population.setup             src/cython/cpopulation.pyx:197-309
     assembleReadsAndDetectVariants  src/cython/assembler.pyx:1429-1476
+    VariantCandidateReader       src/python/variantutils.py:21-163   (over in-memory lines: tabix and file I/O are the integrator's)
 
 The per-call methods (`alignReads`, `alignSingleRead`, `calculateDataLikelihood`) exist for drop-in compatibility
 and launch tiny batches; throughput comes from `Population.setup` (all haplotypes x all individuals of a window in
@@ -112,6 +113,42 @@ class Variant:
         if refFile is None:
             raise ValueError("the indel prior needs the reference sequence around the variant: pass refFile (or set Variant.prior)")
         return indelPrior(self, refFile, indel_length_and_type)
+
+
+class VariantCandidateReader:
+    """variantutils.VariantCandidateReader (variantutils.py:21-163) over lines already in memory.  lines_by_file: one entry per source file,
+    in file order -- either {(chrom, start, end): bytes} (the text a tabix fetch of that region returned, '\\n'-ended lines) or the file's
+    data lines themselves (bytes, or a list of bytes lines), from which Variants() takes the lines whose [POS - 1, POS - 1 + len(REF))
+    overlaps the region, in file order: a stand-in for the fetch, not tabix (a line it cannot place -- fewer than five columns, a POS that is no
+    number -- is left out; a fetch handed over as text is parsed as it is, and such a line raises).  options: maxSize and longHaps are read."""
+
+    def __init__(self, lines_by_file, options):
+        self.options = options
+        self.vcfFiles = list(lines_by_file)
+
+    @staticmethod
+    def fetch(lines, chromosome, start, end):
+        """The stand-in fetch over a file's data lines: those of `chromosome` whose reference span overlaps [start, end)."""
+        if isinstance(lines, (bytes, bytearray)):
+            lines = bytes(lines).split(b"\n")
+        name = chromosome if isinstance(chromosome, bytes) else chromosome.encode()
+        out = []
+        for ln in lines:
+            cols = ln.split(b"\t", 4)
+            if len(cols) < 5 or ln[:1] == b"#" or cols[0] != name or not cols[1].isdigit():
+                continue
+            pos = int(cols[1]) - 1
+            if pos < end and pos + max(1, len(cols[3])) > start:
+                out.append(ln)
+        return b"".join(ln + b"\n" for ln in out)
+
+    def texts(self, chromosome, start, end):
+        """Per source file the text of the region's fetch."""
+        return [f.get((chromosome, start, end), b"") if isinstance(f, dict) else self.fetch(f, chromosome, start, end) for f in self.vcfFiles]
+
+    def Variants(self, chromosome, start, end):
+        from .regionprep import sourceVariants
+        return sourceVariants(chromosome, self.texts(chromosome, start, end), self.options.maxSize, getattr(self.options, "longHaps", 0))
 
 
 class AlignedRead:

@@ -51,6 +51,14 @@ CALL_VARIANTS_OPTIONS = [
 ]
 
 
+SOURCE_HELP = ("FILE[,FILE]: VCF file(s) of known alleles to genotype next to (or, with --getVariantsFromBAMs=0, instead of) the candidates from the "
+               "reads.  With --synthetic=config4:N the files are read as plain or gzip/bgzip text and every region is handed the data lines whose "
+               "[POS-1, POS-1+len(REF)) overlaps it: this is the CLI's OWN STAND-IN for a tabix fetch (no .tbi index is read); an integrator hands "
+               "the library the lines its tabix fetch returned (include/platypus_caller_source.h).  The stand-in cannot place a line without five columns "
+               "or with a POS that is no number and LEAVES IT OUT; the library, handed such a line, ends the call with an error that names it.  "
+               "--longHaps is honoured.")
+
+
 def _list(s):
     return s.split(",")
 
@@ -59,7 +67,7 @@ def build_parser():
     p = argparse.ArgumentParser(prog="Platypus.py callVariants", allow_abbrev=False)
     for flag, dest, typ, default in CALL_VARIANTS_OPTIONS:
         p.add_argument(flag, *(["-o"] if flag == "--output" else []), dest=dest,
-                       type=_list if typ == "list" else typ, default=default)
+                       type=_list if typ == "list" else typ, default=default, **({"help": SOURCE_HELP} if flag == "--source" else {}))
     p.add_argument("--synthetic", dest="synthetic", type=str, default=None,
                    help="(this build) run the hot path on a synthetic BASELINE config instead of BAM input: config1|config2[:N]|config5[:N]")
     return p

@@ -5,8 +5,9 @@ region pipeline"): host logic, same names and argument meaning as the reference.
     filterVariants, filterVariantsByCoverage, computeVariantReadSupportFrac, getHaplotypesInWindow
                                             src/cython/variantFilter.pyx:98-171,359-373,571-622,626-650
     WindowGenerator                         src/python/window.py:18-238
+    sourceLineAlleles, sourceVariants       src/python/variantutils.py:72-163,168-197 (VariantCandidateReader.Variants over text lines)
 
-Pinned by tests/golden/regionprep_cases.json.gz (outputs of the reference's own texts)."""
+Pinned by tests/golden/regionprep_cases.json.gz and source_cases.json.gz (outputs of the reference's own texts)."""
 from .vcfrecords import ASSEMBLER_VAR, FILE_VAR, PLATYPUS_VAR
 
 
@@ -45,6 +46,123 @@ def leftNormaliseIndel(variant, refFile, maxReadLength):
             out.prior = variant.prior
         return out
     return variant
+
+
+# ---- candidates from source VCF lines (variantutils.py:56-197) ------------------------------------------------------------------------
+
+SOURCE_LINE_OK, SOURCE_LINE_SKIPPED, SOURCE_LINE_INVALID, SOURCE_LINE_BAD = 0, 1, 2, 3
+_VALID_BASES = frozenset(b"ACGTN")
+
+
+def sourceLineAlleles(line, maxSize, longHaps=0):
+    """One text line of a source VCF -> (verdict, [(pos, removed, added)], ALT elements over maxSize): the body of the loop of
+    VariantCandidateReader.Variants (variantutils.py:72-159) with isValidVcfLine (:168-197), pos = int(POS) - 1 (TabProxies.pyx:608).
+    `line`: bytes without the newline.  SKIPPED: empty or a '#' line (a fetch returns neither); BAD: fewer than five columns, or a POS
+    that is not 1-10 digits / above 2^31 - 1 / whose trimmed position could leave a C int (pysam raises, atoi is undefined); INVALID:
+    isValidVcfLine says no.  Only CHROM, POS, ID, REF and ALT are looked at."""
+    if not line or line[:1] == b"#":
+        return SOURCE_LINE_SKIPPED, [], 0
+    cols = line.split(b"\t", 5)
+    if len(cols) < 5:
+        return SOURCE_LINE_BAD, [], 0
+    POS, ref, altCol = cols[1], cols[3], cols[4]
+    if not 1 <= len(POS) <= 10 or not all(48 <= c <= 57 for c in POS) or int(POS) > 2 ** 31 - 1 or int(POS) - 1 + len(ref) > 2 ** 31 - 1:
+        return SOURCE_LINE_BAD, [], 0
+    pos = int(POS) - 1
+    alts = altCol.split(b",")
+    if pos < 0 or set(ref) - _VALID_BASES or any(set(a) - _VALID_BASES for a in alts):
+        return SOURCE_LINE_INVALID, [], 0
+    out, over = [], 0
+    lenRef = len(ref)
+    for alt in alts:
+        lenAlt = len(alt)
+        if abs(lenAlt - lenRef) > maxSize:
+            over += 1
+        elif lenRef == 1 and lenAlt == 1:
+            out.append((pos, ref, alt))
+        elif lenRef == lenAlt:                                                     # MNP: leading, then trailing equal bases off
+            r, a, p = ref, alt, pos
+            while r and a and r[0] == a[0]:
+                r, a, p = r[1:], a[1:], p + 1
+            while r and a and r[-1] == a[-1]:
+                r, a = r[:-1], a[:-1]
+            out.append((p, r, a))
+        elif longHaps == 1:
+            out.append((pos, ref, alt))
+        else:                                                                      # the first base of both off unseen, then leading equal bases
+            r, a, p = ref[1:], alt[1:], pos
+            while r and a and r[0] == a[0]:
+                r, a, p = r[1:], a[1:], p + 1
+            out.append((p, r, a))
+    return SOURCE_LINE_OK, out, over
+
+
+def sourceTextAlleles(text, maxSize, longHaps=0):
+    """The lines a fetch returned (bytes, '\\n'-ended; the last may lack it) -> ([(pos, removed, added, line index)] in input order,
+    {lines, skipped, invalid, oversize}, [indices of BAD lines])."""
+    lines = text.split(b"\n")
+    if lines and lines[-1] == b"":
+        lines.pop()
+    alleles, bad = [], []
+    stats = dict(lines=len(lines), skipped=0, invalid=0, oversize=0)
+    for k, ln in enumerate(lines):
+        verdict, out, over = sourceLineAlleles(ln, maxSize, longHaps)
+        stats["oversize"] += over
+        if verdict == SOURCE_LINE_SKIPPED:
+            stats["skipped"] += 1
+        elif verdict == SOURCE_LINE_INVALID:
+            stats["invalid"] += 1
+        elif verdict == SOURCE_LINE_BAD:
+            bad.append(k)
+        alleles.extend((p, r, a, k) for p, r, a in out)
+    return alleles, stats, bad
+
+
+def py2_set_sorted(variants):
+    """sorted(list(set(varList))) (variantutils.py:161) as Python 2 orders it: the set keeps the first of equal variants and yields them
+    in the order of its table's slots (CPython 2.7 setobject.c, probed with Variant.__hash__: vcfrecords.py2_variant_hash); the sort is
+    stable, so variants that compare equal (refPos, varType, nRemoved: two SNPs or two insertions at one position) stay in set order."""
+    from .vcfrecords import py2_variant_hash
+    m = (1 << 64) - 1
+    hashes = [py2_variant_hash(v.refName, v.refPos, v.removed, v.added) for v in variants]
+
+    def slot(table, k):
+        mask = len(table) - 1
+        i, perturb = hashes[k] & mask, hashes[k]
+        while table[i & mask] is not None and not (hashes[table[i & mask]] == hashes[k] and variants[table[i & mask]] == variants[k]):
+            i = (5 * i + perturb + 1) & m
+            perturb >>= 5
+        return i & mask
+    table, used = [None] * 8, 0
+    for k in range(len(variants)):
+        j = slot(table, k)
+        if table[j] is not None:
+            continue
+        table[j] = k
+        used += 1
+        if used * 3 >= len(table) * 2:
+            size = 8
+            while size <= used * (2 if used > 50000 else 4):
+                size <<= 1
+            grown = [None] * size
+            for q in table:
+                if q is not None:
+                    grown[slot(grown, q)] = q
+            table = grown
+    return sorted(variants[k] for k in table if k is not None)
+
+
+def sourceVariants(chrom, texts, maxSize, longHaps=0):
+    """VariantCandidateReader.Variants for the fetches of one region (`texts`: one bytes object per source file, in file order): FILE_VAR
+    variants without supporting reads, set-reduced and sorted.  A line pysam would raise on raises ValueError here."""
+    from .hostapi import Variant
+    out = []
+    for text in texts:
+        alleles, _, bad = sourceTextAlleles(text, maxSize, longHaps)
+        if bad:
+            raise ValueError("source VCF line %d has fewer than five columns or no usable POS" % bad[0])
+        out.extend(Variant(chrom, p, r, a, 0, FILE_VAR) for p, r, a, _ in alleles)
+    return py2_set_sorted(out)
 
 
 def _onlyFromReads(source):

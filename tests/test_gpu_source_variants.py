@@ -1,0 +1,277 @@
+"""GPU tests of candidates from source VCF lines: plat_source_variants_batch against the plain-Python restatement (regionprep) and the host
+parser on hand-built text and a seeded fuzz, against the reference's reader text (tests/golden/source_cases.json.gz) through the C ABI,
+and the native region loop with source lines against the reference's region loop (source_region_cases.json.gz), parsed on the device and,
+with PLAT_CALLER_HOST_SOURCE=1, on the host."""
+import numpy as np
+import pytest
+
+from platypus_amd import fastcaller as F, hostapi as H
+from platypus_amd.options import default_options
+from tests import region_golden as R
+from tests import source_golden as S
+
+pytestmark = pytest.mark.gpu
+
+TILE = 1024                                              # bytes of text per wave of the kernel (SRC_TILE, plat_sourcevcf.hip)
+
+
+@pytest.fixture(scope="module")
+def eng():
+    return H.get_engine()
+
+
+@pytest.fixture(scope="module")
+def host():
+    return F.load()
+
+
+def check(eng, host, regions, names, max_size=1500, long_haps=0, lead=0):
+    """device == host parser == Python, field by field; returns the device's dict."""
+    d = eng.source_variants(regions, names, max_size, long_haps, lead=lead, check=False)
+    h = S.host_parse(host, regions, names, max_size, long_haps)
+    per, stats, hashes, bad = S.python_parse(regions, names, max_size, long_haps)
+    assert d["guard_intact"]
+    n = len(regions)
+    assert list(d["status"]) == list(h["status"]) == [-9 if bad >= 0 else 0, bad, sum(len(p) for p in per), int(stats[:, 0].sum()) if n else 0]
+    assert list(d["region_begin"]) == list(h["region_begin"]) == list(np.concatenate([[0], np.cumsum([len(p) for p in per])]))
+    assert (d["stats"] == stats).all() and (h["stats"] == stats).all()
+    for k in range(n):
+        a, b = int(d["region_begin"][k]), int(d["region_begin"][k + 1])
+        assert S.alleles_of(d, a, b) == per[k] == S.alleles_of(h, a, b), "region %d" % k
+    assert list(d["hash"]) == hashes == list(h["hash"])
+    assert list(d["rem_off"] - lead) == list(h["rem_off"]) and list(d["add_off"] - lead) == list(h["add_off"])      # the same substrings, not equal copies
+    return d
+
+
+def line(pos, ref, alt, chrom=b"20", ident=b".", tail=b"\t50\tPASS\tAC=1\tGT\t0/1"):
+    return b"\t".join([chrom, str(pos).encode(), ident, ref, alt]) + tail + b"\n"
+
+
+def test_one_line_per_rule_branch(eng, host):
+    rules = [line(100, b"A", b"C"), line(101, b"A", b"A"), line(102, b"A", b"C,G,T"),                   # SNPs, equal alleles, several
+             line(110, b"ACGT", b"ACTT"), line(111, b"ACGT", b"ACGT"), line(112, b"AC", b"GT"),           # MNPs: both trims, to nothing, none
+             line(120, b"A", b"ATT"), line(121, b"ATT", b"A"), line(122, b"ATG", b"ATGTG"),               # indels: anchor off, leading trim
+             line(123, b"CA", b"GATT"), line(124, b"AT", b"A,ATTT,C"),                                     # anchors that differ (not compared), mixed
+             line(130, b"A", b"A" + b"T" * 1501 + b",C"), line(131, b"A" * 1502, b"A"),                    # over maxSize next to one that fits
+             line(140, b"A", b"A,"), line(141, b"AT", b","), line(142, b"A", b""), line(143, b"", b"A"),   # empty elements, empty REF
+             line(150, b"A", b"."), line(151, b"A", b"*"), line(152, b"A", b"<DEL>"), line(153, b"a", b"C"), line(154, b"A", b"c"),
+             line(155, b"AN", b"A,R"), line(156, b"A.", b"C"), line(0, b"A", b"C"), line(1, b"N", b"A,N"),   # invalid; POS 0 and 1
+             b"\n", b"#CHROM\tPOS\n", b"20\t200\t.\tG\tT\n", b"20\t201\t.\tG\tT", ]                       # skipped; five columns; no newline
+    text = b"".join(rules)
+    d = check(eng, host, [text], ["20"])
+    assert list(d["stats"][0]) == [len(rules), 2, 8, 2] and int(d["status"][2]) == 26
+    dl = check(eng, host, [text], ["20"], long_haps=1)
+    assert S.alleles_of(dl) != S.alleles_of(d)
+    check(eng, host, [text], ["chr20"], max_size=2)
+    check(eng, host, [text], ["20"], lead=7)                            # the regions do not start at byte 0, nor on a word
+
+
+def test_tabs_and_newlines_on_word_and_tile_edges(eng, host):
+    """Each of the four tabs and the newline at byte offsets = 15 and = 0 (mod 16), and on the tile edge (bytes 1023 / 1024): the ID column is
+    padded so that the byte lands there."""
+    base = line(300, b"AC", b"A,ACC", ident=b"rs1")
+    cols = base[:-1].split(b"\t")
+    where = []                                                          # byte index within the line of tab 1..4 and of the newline
+    at = -1
+    for k in range(4):
+        at += len(cols[k]) + 1
+        where.append(at)
+    where.append(len(base) - 1)
+    for edge in (15, 16, 31, 32, TILE - 1, TILE, 2 * TILE - 1, 2 * TILE):
+        for w in where:
+            front = line(10, b"G", b"T")                                # a line in front, so that the line under test starts mid-text
+            start = len(front)
+            pad = edge - (start + w)
+            while pad < 0:
+                pad += TILE if edge >= TILE - 1 else 16
+            if w >= where[2]:                                           # bytes behind the ID column move with it: pad the ID
+                t = line(300, b"AC", b"A,ACC", ident=b"rs1" + b"x" * pad)
+                head = b""
+            else:                                                       # tabs in front of the ID: shift the whole line with a long first line
+                t, head = base, b""
+                front = line(10, b"G", b"T", ident=b"i" * (pad + 1))
+                pad = 0
+            text = head + front + t + line(400, b"T", b"TA")
+            pos = len(front) + w + (pad if w >= where[2] else 0)
+            assert pos % 16 == edge % 16 and (edge < TILE - 1 or pos % TILE == edge % TILE), (edge, w, pos)
+            assert text[pos:pos + 1] in (b"\t", b"\n")
+            check(eng, host, [text], ["20"])
+            check(eng, host, [text[:-1]], ["20"])
+
+
+def test_wide_lines_empty_regions_and_many_lines(eng, host):
+    wide = line(500, b"A", b"G", tail=b"\tQ\tPASS\tX" + b"\t0/1" * 17499)
+    assert len(wide) > 70000
+    regions = [wide + line(501, b"C", b"CT") + wide, b"", b"#only\n#headers\n", line(7, b"A", b"T"),
+               b"".join(line(1000 + i, b"ACGT"[i % 4:i % 4 + 1], b"ACGT"[(i + 1) % 4:(i + 1) % 4 + 1] + (b",N" if i % 7 == 0 else b"")) for i in range(300)),
+               line(9, b"G", b"GA"), b"", b""]
+    d = check(eng, host, regions, ["20", "20", "1", "X", "20", "chrUn_gl000220", "20", "20"])
+    assert [int(x) for x in d["stats"][:, 0]] == [3, 0, 2, 1, 300, 1, 0, 0] and int(d["line"][-1]) == 0
+    check(eng, host, [], [])
+    check(eng, host, [b"", b""], ["20", "21"])
+
+
+def test_capacity_and_refused_lines(eng, host):
+    regions = [line(5, b"A", b"C,G,T") + line(6, b"A", b"AT"), line(8, b"AT", b"A") + line(9, b"C", b"G,T")]
+    full = eng.source_variants(regions, ["20", "20"])
+    assert int(full["status"][2]) == 7 and full["guard_intact"]
+    for cap in (0, 1, 4, 6):
+        d = eng.source_variants(regions, ["20", "20"], cap_variants=cap, check=False)
+        assert list(d["status"]) == [-8, -1, 7, 4] and d["guard_intact"] and len(d["pos"]) == cap
+        assert S.alleles_of(d) == S.alleles_of(full)[:cap] and list(d["region_begin"]) == [min(x, cap) for x in (0, 4, 7)]
+    assert int(eng.source_variants(regions, ["20", "20"], cap_variants=7)["status"][0]) == 0
+    # one 4-column line and one non-digit POS: BAD_INPUT naming the lowest, everything else parsed; a refused line wins over an overflow
+    bad = [line(5, b"A", b"C"), line(6, b"A", b"T") + b"20\t7\t.\tA\n" + line(8, b"G", b"C"), line(9, b"A", b"T") + b"20\t1e3\t.\tA\tC\n" + line(11, b"A", b"G")]
+    d = check(eng, host, bad, ["20", "20", "20"])
+    assert list(d["status"]) == [-9, (1 << 32) | 1, 5, 7]
+    d = eng.source_variants(bad, ["20", "20", "20"], cap_variants=2, check=False)
+    assert list(d["status"]) == [-9, (1 << 32) | 1, 5, 7] and d["guard_intact"] and len(d["pos"]) == 2
+    for pos_col in (b"", b"12345678901", b"2147483648", b"-5", b" 7", b"7 "):
+        d = check(eng, host, [b"20\t" + pos_col + b"\t.\tA\tC\n"], ["20"])
+        assert int(d["status"][0]) == -9
+    check(eng, host, [b"20\t2147483647\t.\tA\tC\n20\t2147483647\t.\tAC\tAG\n20\t0000000012\t.\tA\tC\n"], ["20"])
+    # offsets that do not ascend: refused whole, nothing written
+    d = eng.source_variants(regions, ["20", "20"], text_off=[0, 60, 40], check=False)
+    assert list(d["status"]) == [-1, -1, 0, 0] and d["guard_intact"]
+
+
+def test_seeded_fuzz_device_host_python(eng, host):
+    rng = np.random.default_rng(77)
+    B = b"ACGTN"
+    seq = lambda n: bytes(B[int(x)] for x in rng.integers(0, 5 if rng.random() < 0.1 else 4, n))
+    regions = []
+    for k in range(8):
+        out = []
+        for _ in range(250):
+            u = rng.random()
+            ref = seq(int(rng.integers(1, 5)) if u < 0.8 else int(rng.integers(0, 40)))
+            alts = [seq(int(rng.integers(0, 6))) if rng.random() < 0.7 else ref[:1] + seq(int(rng.integers(0, 30))) for _ in range(int(rng.integers(1, 4)))]
+            alt = b",".join(alts)
+            if u > 0.97:
+                alt = [b".", b"<INS>", b"a", b"A,*"][int(rng.integers(0, 4))]
+            pos = int(rng.integers(0, 3)) if u < 0.02 else int(rng.integers(1, 50000))
+            tail = b"" if rng.random() < 0.2 else b"\tQ\tF\t" + b"x" * int(rng.integers(0, 300 if rng.random() < 0.9 else 5000))
+            ln = line(pos, ref, alt, ident=b"r" * int(rng.integers(0, 20)), tail=tail)
+            if u > 0.99:
+                ln = [b"\n", b"#c\n"][int(rng.integers(0, 2))]
+            out.append(ln)
+        t = b"".join(out)
+        regions.append(t[:-1] if k % 3 == 0 else t)
+    d = check(eng, host, regions, ["20", "1", "X", "20", "chr1", "2", "20", "Y"], max_size=25, lead=3)
+    assert int(d["status"][3]) == 2000 and int(d["status"][2]) > 2500
+    check(eng, host, regions, ["20"] * 8, long_haps=1)
+
+
+def test_goldens_through_the_c_abi(eng, host):
+    cases = S.load("source_cases.json.gz")
+    for long_haps in (0, 1):
+        for max_size in (25, 1500):
+            sub = [c for c in cases if c["longHaps"] == long_haps and c["maxSize"] == max_size]
+            d = eng.source_variants([c["text"].encode() for c in sub], [c["chrom"] for c in sub], max_size, long_haps)
+            assert int(d["status"][0]) == 0 and d["guard_intact"]
+            for k, c in enumerate(sub):
+                a, b = int(d["region_begin"][k]), int(d["region_begin"][k + 1])
+                assert [(p, r.decode(), x.decode()) for p, r, x, _ in S.alleles_of(d, a, b)] == [tuple(v) for v in c["alleles"]]
+                got = S.alleles_of(d)
+                assert [list((got[i][0], got[i][1].decode(), got[i][2].decode())) for i in S.host_order(host, d["text"], d, a, b)] == c["ordered"]
+
+
+def test_region_loop_with_source_lines(monkeypatch):
+    cases = S.load("source_region_cases.json.gz")
+    nc = F.NativeCaller(0, 2, 2)
+    try:
+        for case in cases:
+            got, rlen, st = S.native_loop_text(case, nc=nc)
+            assert got == case["lines"], R.diff(got, case["lines"])
+            assert rlen == case["rlen_after"] and st["n_windows_failed"] == 0
+            assert st["n_source_variants"] > 0 and st["n_regions_stage_b_device"] == 0 and st["seconds_source"] > 0
+            assert st["n_source_chunks_device"] >= 1 and st["n_source_retries"] == 0          # the kernels parsed them, not the host parser
+            assert st["n_source_lines"] == sum(t.count("\n") for reg in case["regions"] for t in reg["source"])
+        # a following call without source lines on the same caller uses device stage B again
+        base = R.load_cases()[0]
+        fasta, work, names = R.case_work(base)
+        opts = default_options(**base["options"])
+        txt = nc.call_regions([F.RegionReads.from_buffers(c, s, e, fasta, b) for c, s, e, b in work], names, opts)
+        assert txt.split("\n")[:-1] == base["lines"] and nc.stats["n_regions_stage_b_device"] == len(work) and nc.stats["n_source_lines"] == 0
+        monkeypatch.setenv("PLAT_CALLER_HOST_SOURCE", "1")
+        for case in cases:
+            got, rlen, st = S.native_loop_text(case, nc=nc)
+            assert got == case["lines"], R.diff(got, case["lines"])
+            assert st["n_source_variants"] > 0 and st["n_regions_stage_b_device"] == 0 and st["n_source_chunks_device"] == 0
+    finally:
+        nc.close()
+
+
+def test_region_loop_more_alleles_than_the_first_capacity():
+    """More alleles in a chunk than the loop's first capacity (16384): the call is repeated with room and the text is the golden one (the extra
+    records repeat three alleles behind the region: the set collapses them, no window holds them); with a 4-column line among them the call
+    ends with PLAT_ERR_BAD_INPUT naming it -- a refused line wins over the overflow, and nothing is fetched -- and the caller stays usable."""
+    case = S.load("source_region_cases.json.gz")[0]
+    reg = case["regions"][0]
+    far = reg["end"] + 40
+    ref = case["ref"][far - 1]
+    alts = ",".join(b for b in "ACGT" if b != ref)
+    extra = ("20\t%d\t.\t%s\t%s\tq\tPASS\tX\n" % (far, ref, alts)).encode() * 7000               # 21 000 alleles
+    src = [S.region_source(case)[0] + [extra]]
+    fasta, work, names = R.case_work(case)
+    regs = [F.RegionReads.from_buffers(c, s, e, fasta, b) for c, s, e, b in work]
+    nc = F.NativeCaller(0, 2, 2)
+    try:
+        txt = nc.call_regions(regs, names, default_options(**case["options"]), source_lines=src)
+        assert txt.split("\n")[:-1] == case["lines"], R.diff(txt.split("\n")[:-1], case["lines"])
+        st = nc.stats
+        assert st["n_source_retries"] == 1 and st["n_source_chunks_device"] == 1 and st["n_source_lines"] == 7000 + sum(t.count("\n") for t in reg["source"])
+        bad = [src[0] + [b"20\t%d\t.\tA\n" % far]]
+        with pytest.raises(F._lib.PlatypusDeviceError) as e:
+            nc.call_regions(regs, names, default_options(**case["options"]), source_lines=bad)
+        assert e.value.code == -9 and "line %d" % (7000 + sum(t.count("\n") for t in reg["source"])) in str(e.value)
+        txt = nc.call_regions(regs, names, default_options(**case["options"]), source_lines=S.region_source(case))
+        assert txt.split("\n")[:-1] == case["lines"] and nc.stats["n_source_retries"] == 0
+    finally:
+        nc.close()
+
+
+def test_fetched_front_end_drops_the_lines_of_a_dropped_region():
+    """plat_call_fetched_regions with source lines when the loader gives up on a region (maxReads): the lines of the regions that are called
+    stay with them.  Two regions, the one with more fetched reads dropped: the text is that of a call of the other region alone with its
+    own lines."""
+    case = next(c for c in S.load("source_region_cases.json.gz") if len(c["regions"]) == 2)
+    fc = S.load("region_fetched_cases.json.gz")[case["base_case"]]
+    fasta = H.FastaFile({"20": fc["ref"].encode()})
+    mk = lambda lst: [H.AlignedRead(x["seq"].encode(), bytes(ord(c) - 33 for c in x["qual"]), x["pos"], x["mapq"], x["flag"], end=x["end"],
+                                    cigarOps=[tuple(c) for c in x["cigar"]], chromID=x["chromID"], mateChromID=x["mateChromID"], insertSize=x["insertSize"],
+                                    matePos=x["matePos"]) for x in lst]
+    regs = lambda: [F.FetchedRegion.from_reads(r["chrom"], r["start"], r["end"], fasta, [(mk(s["fetched"]), []) for s in r["samples"]]) for r in fc["regions"]]
+    counts = [sum(len(s["fetched"]) for s in r["samples"]) for r in fc["regions"]]
+    assert counts[0] != counts[1]
+    keep = int(np.argmin(counts))
+    src = S.region_source(case)
+    names = fc["sample_names"]
+    opt = lambda: default_options(**dict(case["options"], maxReads=max(counts)))
+    nc = F.NativeCaller(0, 2, 2)
+    try:
+        both = nc.call_fetched_regions(regs(), names, opt(), source_lines=src)
+        assert nc.loaded == [int(k == keep) for k in range(2)] and nc.stats["n_source_lines"] == sum(t.count(b"\n") for t in src[keep])
+        alone = nc.call_fetched_regions([regs()[keep]], names, opt(), source_lines=[src[keep]])
+        other = nc.call_fetched_regions([regs()[keep]], names, opt(), source_lines=[src[1 - keep]])
+        assert both == alone and both != other and both.count("\n") > 0
+        assert nc.call_fetched_regions(regs(), names, opt()) == nc.call_fetched_regions([regs()[keep]], names, opt())      # and gone with the call
+    finally:
+        nc.close()
+
+
+def test_cli_config4_with_a_source_file(tmp_path, capsys):
+    """`callVariants --synthetic=config4:N --source=FILE`: an allele the reads show, listed in the source file, comes out with both sources."""
+    from platypus_amd.__main__ import call_variants
+    args = ["--synthetic", "config4:2", "--bufferSize", "4000", "--nCPU", "1"]
+    call_variants(args + ["--output", str(tmp_path / "plain.vcf")])
+    recs = [ln.split("\t") for ln in open(tmp_path / "plain.vcf") if not ln.startswith("#")]
+    snp = next(r for r in recs if len(r[3]) == 1 and len(r[4]) == 1 and "Source=Platypus" in r[7] and "File" not in r[7])
+    (tmp_path / "known.vcf").write_text("##fileformat=VCFv4.1\n" + "\t".join(snp[:5]) + "\t.\t.\t.\n")
+    call_variants(args + ["--source", str(tmp_path / "known.vcf"), "--output", str(tmp_path / "with.vcf")])
+    got = [ln.split("\t") for ln in open(tmp_path / "with.vcf") if not ln.startswith("#")]
+    assert len(got) == len(recs)
+    hit = next(r for r in got if r[:2] == snp[:2])
+    assert hit[3:5] == snp[3:5] and ("Source=Platypus,File" in hit[7] or "Source=File,Platypus" in hit[7])
+    assert sum("Source=" in r[7] and "File" in r[7].split("Source=")[1].split(";")[0] for r in got) == 1
+    capsys.readouterr()
