@@ -1,8 +1,8 @@
 // bgzf_regions.hpp -- plat_call_bgzf_regions (include/platypus_caller_bgzf.h): the region loop for the BGZF blocks of an index lookup.  A
-// third front end of fetched_regions.hpp, in front of bam_regions.hpp's: the chunks' compressed bytes go to the device as they are,
+// front end on front_end.hpp's frame, in front of bam_regions.hpp's decode: the chunks' compressed bytes go to the device as they are,
 // plat_bgzf_inflate_batch inflates them, plat_bam_find_records is sam_itr_next, plat_bam_decode_batch takes the kept records' offsets where
-// the find left them, and bamStage / fetchedFinish do the rest.  The host reads each block's header and trailer (the BSIZE chain, the ISIZE
-// words that size the inflate's output) and never a payload byte.
+// the find left them (a RecordList), and decodeAndStage does the rest.  The host reads each block's header and trailer (the BSIZE chain, the
+// ISIZE words that size the inflate's output) and never a payload byte.
 // Included at the end of region_caller.cpp, after bam_regions.hpp.
 #pragma once
 #include "../../../include/platypus_caller_bgzf.h"
@@ -16,15 +16,13 @@ namespace plathost {
 
 struct BgzfChunkAt { int region, sample, chunk, blkFirst, blkEnd; };      // where a chunk came from and its blocks in the call's list
 
-static std::string bgzfWhere(const FetchedRegionHead& r, const BgzfChunkAt& a) {
-    return fetchedWhere(r, a.region, a.sample) + ", chunk " + std::to_string(a.chunk);
-}
-
 // The chunks of one call -- every (region, unit) in order, a unit being what one index lookup fetched (a sample; a file for the read-group
 // call of rg_regions.hpp) -- from the host's walk over the block headers to the kept records' offsets on the device.
 struct BgzfFront {
-    std::string entry;
-    int nUnits = 0;
+    FrontCall& F;
+    const std::string& entry;
+    const int nUnits;
+    const char* const unit;                                               // what the messages call one: "sample" or "file"
     // the call's blocks and chunks, all regions: which of them load is known once the device has counted the kept records
     std::vector<BgzfChunkAt> chunkAt;
     std::vector<const plat_bgzf_chunk*> chunkOf;
@@ -36,13 +34,17 @@ struct BgzfFront {
     plat_bam_find_out fo;
     long long capRecords = 0;
     int64_t inflateStatus[4] = {0, -1, 0, 0}, findStatus[4] = {0, -1, 0, 0};
-    std::vector<int32_t> keptBegin;                                       // [streams + 1], of the find that ran last
+
+    BgzfFront(FrontCall& f, int n_units, const char* unit_) : F(f), entry(f.entry), nUnits(n_units), unit(unit_) {}
+
+    std::string where(const BgzfChunkAt& a) const { return F.where(a.region, a.sample, unit) + ", chunk " + std::to_string(a.chunk); }
 
     void addRegion(int32_t t, int32_t b, int32_t e) { tid.push_back(t); beg.push_back(b); end.push_back(e); }
 
     // unit i of region k: its chunks checked, the BSIZE chain of each walked (18 header bytes and the trailer of every block)
-    int addUnit(plat_caller* c, const FetchedRegionHead& head, int k, int i, int n_chunks, const plat_bgzf_chunk* chunks)
+    int addUnit(int k, int i, int n_chunks, const plat_bgzf_chunk* chunks)
     {
+        plat_caller* c = F.c;
         for (int q = 0; q < n_chunks; ++q) {
             const plat_bgzf_chunk& ch = chunks[q];
             if (ch.data_len < 0 || (ch.data_len && !ch.data) || ch.first_uoffset < 0 || ch.first_uoffset > 65535 || ch.end_uoffset < 0 || ch.end_uoffset > 65536 ||
@@ -53,7 +55,7 @@ struct BgzfFront {
             for (int64_t at = 0; at < ch.data_len;) {
                 bgzf::BlockHead h;
                 if (bgzf::parse_header(ch.data, ch.data_len, at, &h) != 0) {
-                    c->lastError = entry + ": the BGZF blocks of " + bgzfWhere(head, a) + " do not chain: no valid block header at offset " +
+                    c->lastError = entry + ": the BGZF blocks of " + where(a) + " do not chain: no valid block header at offset " +
                                    std::to_string(at) + " of its data (bad magic, no BC subfield, or a block that leaves the data)";
                     return PLAT_ERR_BAD_INPUT;
                 }
@@ -64,7 +66,7 @@ struct BgzfFront {
                 if (blkOff.size() >= (size_t)INT_MAX) { c->lastError = entry + ": more blocks than one call takes"; return PLAT_ERR_OVERFLOW; }
             }
             if (endBlk == -2) {
-                c->lastError = entry + ": end_coffset " + std::to_string(ch.end_coffset) + " of " + bgzfWhere(head, a) + " is not a block boundary of its data";
+                c->lastError = entry + ": end_coffset " + std::to_string(ch.end_coffset) + " of " + where(a) + " is not a block boundary of its data";
                 return PLAT_ERR_BAD_INPUT;
             }
             a.blkEnd = (int)blkOff.size();
@@ -76,8 +78,10 @@ struct BgzfFront {
     }
 
     // upload and inflate, back to back
-    void inflate(Slot& z, FetchedDeviceBuffers& dev)
+    void inflate()
     {
+        Slot& z = *F.z;
+        FetchedDeviceBuffers& dev = F.dev;
         void* st = z.stream;
         nBlocks = (int)blkOff.size();
         uint8_t* dBlob = dev.alloc<uint8_t>((size_t)blobBytes);
@@ -99,9 +103,11 @@ struct BgzfFront {
     }
 
     // the find over the streams of the regions `use` marks (stream = unit i of such a region, in order; its chunks lie back to back in the
-    // call's list); returns the number of streams
-    int find(Slot& z, FetchedDeviceBuffers& dev, const std::vector<int>& use)
+    // call's list): the kept records, their counts per stream on their way back
+    void find(const std::vector<int>& use, RecordList& kept)
     {
+        Slot& z = *F.z;
+        FetchedDeviceBuffers& dev = F.dev;
         void* st = z.stream;
         const int n_regions = (int)use.size();
         std::vector<int32_t> chunkBegin(1, 0), cFirst, cEnd, cFirstU, cStopBlk, cStopU, sTid, sBeg, sEnd;
@@ -127,44 +133,58 @@ struct BgzfFront {
         fi.tid = dev.upload(sTid, st); fi.beg = dev.upload(sBeg, st); fi.end = dev.upload(sEnd, st);
         fo.stream_begin = dev.alloc<int32_t>((size_t)n + 1);
         ck(plat_bam_find_records(z.ctx, &fi, &fo, st), "plat_bam_find_records");
-        keptBegin.assign((size_t)n + 1, 0);
-        ck(plat_memcpy_d2h(z.ctx, keptBegin.data(), fo.stream_begin, keptBegin.size() * sizeof(int32_t), st), "plat_memcpy_d2h");
+        kept.blob = io.data; kept.bytes = inflated; kept.off = fo.rec_off; kept.limit = fo.rec_limit; kept.dBegin = fo.stream_begin;
+        kept.begin.assign((size_t)n + 1, 0);
+        ck(plat_memcpy_d2h(z.ctx, kept.begin.data(), fo.stream_begin, kept.begin.size() * sizeof(int32_t), st), "plat_memcpy_d2h");
         ck(plat_memcpy_d2h(z.ctx, findStatus, fo.status, sizeof findStatus, st), "plat_memcpy_d2h");
-        return n;
     }
 
     // after the wait behind the first find (every region took part): 0, or the inflate's or the find's error with its message
-    int firstFailure(plat_caller* c, const std::vector<FetchedRegionHead>& heads) const
+    int firstFailure() const
     {
         if (inflateStatus[0] != 0) {
             const long long b = inflateStatus[1];
             size_t q = 0;
             while (q + 1 < chunkAt.size() && !(b >= chunkAt[q].blkFirst && b < chunkAt[q].blkEnd)) ++q;
             const BgzfChunkAt a = chunkAt.empty() ? BgzfChunkAt{0, 0, 0, 0, 0} : chunkAt[q];
-            c->lastError = entry + ": block " + std::to_string(b - a.blkFirst) + " of " + bgzfWhere(heads[(size_t)a.region], a) +
-                           (inflateStatus[0] == PLAT_ERR_OVERFLOW ? " does not fit the room its ISIZE words asked for"
-                                                                  : " cannot be inflated (a bad header, an invalid deflate stream, output other than ISIZE bytes, or a CRC32 mismatch)");
+            F.c->lastError = entry + ": block " + std::to_string(b - a.blkFirst) + " of " + where(a) +
+                             (inflateStatus[0] == PLAT_ERR_OVERFLOW ? " does not fit the room its ISIZE words asked for"
+                                                                    : " cannot be inflated (a bad header, an invalid deflate stream, output other than ISIZE bytes, or a CRC32 mismatch)");
             return (int)inflateStatus[0];
         }
         if (findStatus[0] != 0) {                                          // (stream s is unit s % nUnits of region s / nUnits)
-            const int s = (int)findStatus[1], k = s / nUnits;
-            c->lastError = entry + ": the record walk of " + fetchedWhere(heads[(size_t)k], k, s % nUnits) +
-                           " fails (a block_size below 32, or a record or its CIGAR running past the chunk's bytes)";
+            const int s = (int)findStatus[1];
+            F.c->lastError = entry + ": the record walk of " + F.where(s / nUnits, s % nUnits, unit) +
+                             " fails (a block_size below 32, or a record or its CIGAR running past the chunk's bytes)";
             return (int)findStatus[0];
         }
         return PLAT_OK;
     }
 
-    // loadBAMData's bail-out (:538-541) on the kept counts of the first find; true when a region is dropped
-    bool bailOut(long long maxReads, std::vector<int>& loaded) const
+    // The find over every region, whatever `behind` enqueues behind it (the read-group call's routes), and the one wait in front of the
+    // decode: two status blocks and the kept counts.  Then loadBAMData's bail-out on those counts; when it drops a region, the find and
+    // `behind` once more over the loaded regions alone, so that their kept records lie back to back.
+    template <class Behind> int findLoaded(RecordList& kept, Behind&& behind)
     {
+        Slot& z = *F.z;
+        std::vector<int>& loaded = F.S.loaded;
+        const std::vector<int> all(loaded.size(), 1);
+        find(all, kept);
+        behind(all);
+        ck(plat_stream_sync(z.ctx, z.stream), "plat_stream_sync");
+        const int rc = firstFailure();
+        if (rc != PLAT_OK) return rc;
         bool dropped = false;
         for (size_t k = 0; k < loaded.size(); ++k) {
-            const long long total = (long long)keptBegin[(k + 1) * (size_t)nUnits] - keptBegin[k * (size_t)nUnits];
-            loaded[k] = !(total > 0 && total >= maxReads);
+            loaded[k] = !F.drops((long long)kept.begin[(k + 1) * (size_t)nUnits] - kept.begin[k * (size_t)nUnits]);
             dropped = dropped || !loaded[k];
         }
-        return dropped;
+        if (!dropped) return PLAT_OK;
+        find(loaded, kept);
+        behind(loaded);
+        ck(plat_stream_sync(z.ctx, z.stream), "plat_stream_sync");
+        if (findStatus[0] != 0) { F.c->lastError = entry + ": the record walk fails on its second run"; return (int)findStatus[0]; }
+        return PLAT_OK;
     }
 
     long long loadedBytes(const std::vector<int>& loaded) const {
@@ -180,81 +200,37 @@ CALLER_EXPORT int plat_call_bgzf_regions(plat_caller* c, const plat_bgzf_region*
                                          const char* const* sample_names, plat_caller_options* options, const plat_caller_qc_options* qc,
                                          char** out_text, size_t* out_len, plat_fetched_region_info* info, plat_caller_stats* stats)
 {
-    SourceLinesGuard sourceGuard(c);
-    int rc = checkCallArgs(c, options, out_text, out_len, n_regions, n_samples);
+    FrontCall F(c, "plat_call_bgzf_regions", n_regions, n_samples, sample_names, options, qc, out_text, out_len, info, stats);
+    int rc = F.open(regions, true, {(const void*)plat_bgzf_inflate_batch, (const void*)plat_bam_find_records, (const void*)plat_bam_decode_batch,
+                                    (const void*)plat_read_buffers_batch}, "plat_bgzf_inflate_batch");
     if (rc != PLAT_OK) return rc;
-    if (!qc || (n_regions > 0 && !regions)) return PLAT_ERR_INVALID;
-    if (!plat_bgzf_inflate_batch || !plat_bam_find_records || !plat_bam_decode_batch || !plat_read_buffers_batch) {
-        c->lastError = "plat_call_bgzf_regions: the device library has no plat_bgzf_inflate_batch";
-        return PLAT_ERR_UNSUPPORTED;
-    }
-    const auto t0 = Clock::now();
-    const std::string entry = "plat_call_bgzf_regions";
-    const double mr = options->maxReads;
-    const long long maxReads = mr >= (double)INT_MAX ? INT_MAX : (mr <= (double)INT_MIN ? INT_MIN : (long long)mr);     // (cdef int maxReads)
-    FetchedStage S;
-    S.loaded.assign((size_t)n_regions, 0);
-    std::vector<FetchedRegionHead> heads;
-    BgzfFront W;
-    W.entry = entry; W.nUnits = n_samples;
+    FetchedStage& S = F.S;
+    BgzfFront W(F, n_samples, "sample");
     for (int k = 0; k < n_regions; ++k) {
         const plat_bgzf_region& r = regions[k];
         if (!r.samples) return PLAT_ERR_INVALID;
-        heads.push_back(FetchedRegionHead{r.chrom, r.start, r.end, r.contig_seq, r.contig_len, r.dev_contig_seq});
         W.addRegion(r.tid, r.itr_beg, r.itr_end);
         for (int i = 0; i < n_samples; ++i) {
             const plat_bgzf_sample& sm = r.samples[i];
-            const plat_bam_records& bm = sm.broken_mates;
-            if (sm.n_chunks < 0 || (sm.n_chunks && !sm.chunks) || bm.n_records < 0 || (bm.n_records && (!bm.data || !bm.rec_off || bm.data_len < 0))) return PLAT_ERR_INVALID;
-            rc = W.addUnit(c, heads.back(), k, i, sm.n_chunks, sm.chunks);
-            if (rc != PLAT_OK) return rc;
+            if (sm.n_chunks < 0 || (sm.n_chunks && !sm.chunks) || !recordsValid(sm.broken_mates)) return PLAT_ERR_INVALID;
+            if ((rc = W.addUnit(k, i, sm.n_chunks, sm.chunks)) != PLAT_OK) return rc;
         }
     }
-    Slot& z = *c->slots[0];
-    void* st = z.stream;
-    FetchedDeviceBuffers dev(z.ctx);
-    try {
-        // upload, inflate, find: back to back
-        W.inflate(z, dev);
-        std::vector<int> all((size_t)n_regions, 1);
-        W.find(z, dev, all);
-        ck(plat_stream_sync(z.ctx, st), "plat_stream_sync");                // the one wait in front of the decode: two status blocks and the kept counts
-        rc = W.firstFailure(c, heads);
+    return F.guarded([&] {
+        W.inflate();                                                       // upload, inflate, find: back to back
+        RecordList kept;
+        int rc = W.findLoaded(kept, [](const std::vector<int>&) {});
         if (rc != PLAT_OK) return rc;
-        if (W.bailOut(maxReads, S.loaded)) {                               // the kept records of the loaded regions alone, back to back
-            W.find(z, dev, S.loaded);
-            ck(plat_stream_sync(z.ctx, st), "plat_stream_sync");
-            if (W.findStatus[0] != 0) { c->lastError = entry + ": the record walk fails on its second run"; return (int)W.findStatus[0]; }
-        }
         std::vector<const plat_bam_records*> broken;
         long long nBroken = 0;
         S.linkBytes += W.loadedBytes(S.loaded);
-        for (int k = 0; k < n_regions; ++k) {
-            if (!S.loaded[(size_t)k]) continue;
-            for (int i = 0; i < n_samples; ++i) {
+        for (int k = 0; k < n_regions; ++k)
+            for (int i = 0; i < n_samples && S.loaded[(size_t)k]; ++i) {
                 const plat_bam_records* t = &regions[k].samples[i].broken_mates;
                 broken.push_back(t); nBroken += t->n_records;
                 S.linkBytes += t->n_records ? t->data_len : 0;
             }
-        }
-        const int nStreams = (int)broken.size();
-        const long long nReads = W.keptBegin.back();
-        if (nReads > INT_MAX - 2ll * nStreams - 1 || nBroken > INT_MAX - (long long)nStreams - 1) {
-            c->lastError = entry + ": more reads than one call takes (call the region list in parts)";
-            return PLAT_ERR_OVERFLOW;
-        }
-        S.nStreams = nStreams; S.N = (int)nReads; S.packed = false;
-        BamDecoded F, B;
-        F.tableBegin = W.keptBegin;
-        bamDecodeLaunch(z, dev, W.io.data, W.inflated, W.fo.rec_off, W.fo.rec_limit, nReads, F);
-        bamDecode(z, dev, broken, B);
-        ck(plat_stream_sync(z.ctx, st), "plat_stream_sync");
-        rc = bamDecodeFailure(c, entry, F, B, S, heads, n_regions, n_samples);
-        if (rc != PLAT_OK) return rc;
-        bamStage(z, dev, S, F, B, nReads, nBroken, nStreams);
-    } catch (const DeviceError& e) {
-        c->lastError = e.what();
-        return e.code;
-    }
-    return fetchedFinish(c, "plat_call_bgzf_regions", dev, S, heads, n_samples, sample_names, options, qc, out_text, out_len, info, stats, t0);
+        if ((rc = F.tooMany(kept.n(), nBroken, (long long)broken.size())) != PLAT_OK) return rc;
+        return decodeAndStage(F, kept, [&] { return uploadRecords(*F.z, F.dev, broken); });
+    });
 }

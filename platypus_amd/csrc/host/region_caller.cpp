@@ -26,6 +26,10 @@
 // on one worker thread with its own plat_ctx and stream (chunk.hpp: Chunk::run); several workers run side by side, so the uploads,
 // kernels and host stages of different chunks overlap.  This file: the feeds, the worker pool, the C entry points, the merge of
 // record texts.  Same text as platypus_amd/caller.py::callVariantsInRegions (tests/test_native_caller_*.py).
+// In front of the loop, for reads that are not split into buffers yet (included at the end of this file):
+//   front_end.hpp          the frame every front end shares: the checks at entry, the bail-out, QC and split on the device, callRegions
+//   fetched_regions.hpp    reads as a BAM fetch returns them, ASCII or packed        bgzf_regions.hpp   the BGZF blocks of an index lookup
+//   bam_regions.hpp        raw BAM alignment records, decoded on the device          rg_regions.hpp     merged files, split by read group
 #include <sys/mman.h>
 
 #include "../../../include/platypus_caller_source.h"
@@ -96,13 +100,6 @@ struct plat_caller {
     std::vector<plat_source_lines> sourceLines;
     bool sourceSet = false;
     int sourceLongHaps = 0;
-    // a front end that drops regions (the loader's maxReads bail-out) before it calls plat_call_regions keeps the lines of the regions it passes on
-    void keepSourceLines(const std::vector<int>& loaded) {
-        if (!sourceSet || sourceLines.size() != loaded.size()) return;
-        size_t j = 0;
-        for (size_t k = 0; k < loaded.size(); ++k) if (loaded[k]) sourceLines[j++] = sourceLines[k];
-        sourceLines.resize(j);
-    }
 };
 // every entry point holds one: the source lines apply to ONE call and are gone when it returns, however it returns
 struct SourceLinesGuard {
@@ -446,13 +443,12 @@ static int checkCallArgs(plat_caller* c, const plat_caller_options* options, cha
     return PLAT_OK;
 }
 
-CALLER_EXPORT int plat_call_regions(plat_caller* c, const plat_region* regions, int n_regions, int n_samples, const char* const* sample_names,
-                                    plat_caller_options* options, char** out_text, size_t* out_len, plat_caller_stats* stats)
+// The region loop over a list that has been checked (checkCallArgs), with its source lines by list position (lines: nullptr without any):
+// plat_call_regions on its own list, the front ends (front_end.hpp) on the regions they loaded and the lines that came for those.
+static int callRegions(plat_caller* c, const plat_region* regions, int n_regions, const plat_source_lines* lines, int n_samples, const char* const* sample_names,
+                       plat_caller_options* options, char** out_text, size_t* out_len, plat_caller_stats* stats)
 {
-    SourceLinesGuard sourceGuard(c);
-    int rc = checkCallArgs(c, options, out_text, out_len, n_regions, n_samples);
-    if (rc != PLAT_OK) return rc;
-    if (n_regions > 0 && !regions) return PLAT_ERR_INVALID;
+    int rc = PLAT_OK;
     const auto t0 = Clock::now();
     plat_caller_stats st;
     memset(&st, 0, sizeof st);
@@ -467,7 +463,7 @@ CALLER_EXPORT int plat_call_regions(plat_caller* c, const plat_region* regions, 
         catch (const std::exception& e) { c->lastError = e.what(); return PLAT_ERR_BAD_INPUT; }          // (a hint that does not describe its table, PLAT_CALLER_CHECK_HINTS=1)
         rlen = nextRlen(rlen, longest, options->maxSize, options->getVariantsFromBAMs);
         r->rlen = rlen;
-        if (c->sourceSet) { r->srcText = c->sourceLines[(size_t)k].text; r->srcLen = c->sourceLines[(size_t)k].len; }
+        if (lines) { r->srcText = lines[k].text; r->srcLen = lines[k].len; }
         work.push_back(std::move(r));
     }
     std::atomic<bool> failed(false);
@@ -480,6 +476,16 @@ CALLER_EXPORT int plat_call_regions(plat_caller* c, const plat_region* regions, 
     traceStages(st, o.sw);
     if (stats) *stats = st;
     return PLAT_OK;
+}
+
+CALLER_EXPORT int plat_call_regions(plat_caller* c, const plat_region* regions, int n_regions, int n_samples, const char* const* sample_names,
+                                    plat_caller_options* options, char** out_text, size_t* out_len, plat_caller_stats* stats)
+{
+    SourceLinesGuard sourceGuard(c);
+    const int rc = checkCallArgs(c, options, out_text, out_len, n_regions, n_samples);
+    if (rc != PLAT_OK) return rc;
+    if (n_regions > 0 && !regions) return PLAT_ERR_INVALID;
+    return callRegions(c, regions, n_regions, c->sourceSet ? c->sourceLines.data() : nullptr, n_samples, sample_names, options, out_text, out_len, stats);
 }
 
 CALLER_EXPORT int plat_call_regions_stream(plat_caller* c, int n_regions, int n_samples, const char* const* sample_names, plat_caller_options* options,
@@ -731,6 +737,7 @@ CALLER_EXPORT void plat_caller_debug_set_order(const char* names, char* out, siz
     snprintf(out, cap, "%s", t.c_str());
 }
 #include "source_variants.hpp"
+#include "front_end.hpp"
 #include "fetched_regions.hpp"
 #include "bam_regions.hpp"
 #include "bgzf_regions.hpp"

@@ -1,6 +1,6 @@
 // switches.hpp -- the PLAT_CALLER_* environment switches of the native region loop (libplat_caller.so), read ONCE PER CALL:
-// plat_call_regions and plat_call_regions_stream call Switches::read() at entry (the fetched / BAM / BGZF front ends end in plat_call_regions
-// and read nothing themselves) and the result travels in Options.  A variable set or cleared between two calls takes effect at the next call;
+// the region loop behind plat_call_regions (callRegions) and plat_call_regions_stream call Switches::read() at entry (the fetched / BAM / BGZF /
+// read-group front ends end in callRegions and read nothing themselves: front_end.hpp) and the result travels in Options.  A variable set or cleared between two calls takes effect at the next call;
 // inside one call nothing changes.  None of them changes the record text (FIRST_OCCURRENCE_ORDER excepted: that is what it is there to show).
 //
 //   variable (PLAT_CALLER_...)   on when            what it does                                                          who sets it

@@ -245,24 +245,75 @@ class ReadTable:
         return t
 
 
-class RegionReads:
+def _u8(a):
+    """bytes, a bytearray or an array as a contiguous uint8 array (no copy where it is one already)."""
+    return np.ascontiguousarray(np.frombuffer(a, dtype=np.uint8) if isinstance(a, (bytes, bytearray)) else a, dtype=np.uint8)
+
+
+def _fill_records(t, data, off):
+    """A plat_bam_records over (data uint8 array, rec_off int64 array)."""
+    t.n_records, t.data, t.data_len, t.rec_off = len(off), data.ctypes.data, len(data), off.ctypes.data
+
+
+def _fill_file_records(t, rec):
+    """A plat_bam_file_records over (data, rec_off, rec_len int32 array)."""
+    _fill_records(t.records, rec[0], rec[1])
+    t.rec_len = rec[2].ctypes.data
+
+
+def _chunk_array(chunks):
+    """The plat_bgzf_chunk array of [(data uint8 array, first_uoffset, end_coffset, end_uoffset)]."""
+    cc = (_BgzfChunk * max(len(chunks), 1))()
+    for q, (d, fu, ec, eu) in enumerate(chunks):
+        cc[q].data, cc[q].data_len, cc[q].first_uoffset, cc[q].end_coffset, cc[q].end_uoffset = d.ctypes.data, len(d), fu, ec, eu
+    return cc
+
+
+class _RegionBase:
+    """What every region class holds: chrom:start-end, the contig's sequence as a contiguous uint8 array, and -- built once, at the first
+    fill -- the C array of its per-class member (UNITS: the samples, or the files of the merged-file regions).  A subclass writes that
+    array in _c_units() and returns it, followed by whatever else has to stay alive with it."""
+    UNITS = "samples"
+
+    def __init__(self, chrom, start, end, contig_seq):
+        self.chrom, self.start, self.end = chrom, int(start), int(end)
+        self.contig = _u8(contig_seq)
+        self._c = None
+
+    def fill(self, a, n_units):
+        """Write this region into the C region struct `a` (the arrays stay owned by, and alive with, this object)."""
+        assert len(getattr(self, self.UNITS)) == n_units
+        if self._c is None:
+            self._c = (self.chrom.encode(),) + tuple(self._c_units())
+        a.chrom, a.contig_seq, a.contig_len = self._c[0], self.contig.ctypes.data, len(self.contig)
+        a.start, a.end = self.start, self.end
+        setattr(a, self.UNITS, self._c[1])
+
+
+class _BgzfWindow(_RegionBase):
+    """... and the iterator's window of the two BGZF region classes."""
+
+    def __init__(self, chrom, start, end, contig_seq, tid, itr_beg, itr_end):
+        super().__init__(chrom, start, end, contig_seq)
+        self.tid, self.itr_beg, self.itr_end = int(tid), int(itr_beg), int(itr_end)
+
+    def fill(self, a, n_units):
+        super().fill(a, n_units)
+        a.tid, a.itr_beg, a.itr_end = self.tid, self.itr_beg, self.itr_end
+
+
+class RegionReads(_RegionBase):
     """One region: chrom:start-end, the contig's sequence and per sample (reads, badReads, brokenMates) as ReadTables."""
 
     def __init__(self, chrom, start, end, contig_seq, samples):
-        self.chrom, self.start, self.end = chrom, int(start), int(end)
-        self.contig = np.ascontiguousarray(np.frombuffer(contig_seq, dtype=np.uint8) if isinstance(contig_seq, (bytes, bytearray)) else contig_seq,
-                                           dtype=np.uint8)
+        super().__init__(chrom, start, end, contig_seq)
         self.samples = samples                                  # [(reads, bad, broken)]
-        self._c = None
 
-    def c_region(self):
-        """(plat_region fields, the plat_sample_reads array they point to), built once per region."""
-        if self._c is None:
-            ss = (_SampleReads * len(self.samples))()
-            for i, (a, b, c) in enumerate(self.samples):
-                ss[i].reads, ss[i].bad_reads, ss[i].broken_mates = a.struct(), b.struct(), c.struct()
-            self._c = (self.chrom.encode(), self.contig.ctypes.data, len(self.contig), ss)
-        return self._c
+    def _c_units(self):
+        ss = (_SampleReads * len(self.samples))()
+        for i, (a, b, c) in enumerate(self.samples):
+            ss[i].reads, ss[i].bad_reads, ss[i].broken_mates = a.struct(), b.struct(), c.struct()
+        return (ss,)
 
     @classmethod
     def from_buffers(cls, chrom, start, end, fasta, buffers, packed=False):
@@ -271,24 +322,14 @@ class RegionReads:
                    [(ReadTable.from_reads(b.reads.array, packed), ReadTable.from_reads(b.badReads.array, packed),
                      ReadTable.from_reads(b.brokenMates.array, packed)) for b in buffers])
 
-    def fill(self, a, n_samples):
-        """Write this region into the plat_region `a` (the arrays stay owned by, and alive with, this object)."""
-        assert len(self.samples) == n_samples
-        a.chrom, a.contig_seq, a.contig_len, ss = self.c_region()
-        a.start, a.end = self.start, self.end
-        a.samples = ss
 
-
-class FetchedRegion:
+class FetchedRegion(_RegionBase):
     """One region as loadBAMData has it in hand (platypusutils.pyx:449-686): per sample the reads a `fetch` returned, in fetch order,
     with chromID / mateChromID / insertSize per read, and the broken mates (sorted by mate position)."""
 
     def __init__(self, chrom, start, end, contig_seq, samples):
-        self.chrom, self.start, self.end = chrom, int(start), int(end)
-        self.contig = np.ascontiguousarray(np.frombuffer(contig_seq, dtype=np.uint8) if isinstance(contig_seq, (bytes, bytearray)) else contig_seq,
-                                           dtype=np.uint8)
+        super().__init__(chrom, start, end, contig_seq)
         self.samples = samples                                  # [(fetched ReadTable, broken ReadTable, chrom_id, mate_chrom_id, insert_size)]
-        self._c = None
 
     @classmethod
     def from_reads(cls, chrom, start, end, fasta, samples, packed=False):
@@ -302,31 +343,23 @@ class FetchedRegion:
                         c(lambda r: r.chromID, np.int16), c(lambda r: r.mateChromID, np.int16), c(lambda r: r.insertSize, np.int32)))
         return cls(chrom, start, end, fasta._seq[chrom], out)
 
-    def fill(self, a, n_samples):
-        """Write this region into the plat_fetched_region `a` (the arrays stay owned by, and alive with, this object)."""
-        assert len(self.samples) == n_samples
-        if self._c is None:
-            ss = (_FetchedReads * len(self.samples))()
-            for i, (f, b, cid, mcid, ins) in enumerate(self.samples):
-                ss[i].fetched, ss[i].broken_mates = f.struct(), b.struct()
-                ss[i].chrom_id, ss[i].mate_chrom_id, ss[i].insert_size = cid.ctypes.data, mcid.ctypes.data, ins.ctypes.data
-            self._c = (self.chrom.encode(), self.contig.ctypes.data, len(self.contig), ss)
-        a.chrom, a.contig_seq, a.contig_len, a.samples = self._c
-        a.start, a.end = self.start, self.end
+    def _c_units(self):
+        ss = (_FetchedReads * len(self.samples))()
+        for i, (f, b, cid, mcid, ins) in enumerate(self.samples):
+            ss[i].fetched, ss[i].broken_mates = f.struct(), b.struct()
+            ss[i].chrom_id, ss[i].mate_chrom_id, ss[i].insert_size = cid.ctypes.data, mcid.ctypes.data, ins.ctypes.data
+        return (ss,)
 
 
-class BamRegion:
+class BamRegion(_RegionBase):
     """One region as the integrator holds it after sam_itr_next (include/platypus_caller_bam.h): per sample the uncompressed BAM alignment
     records of the fetch, in fetch order, and of the broken mates, in mate-position order -- each as (data uint8 array, rec_off int64
     array), record i starting at its refID at data[rec_off[i]]."""
 
     def __init__(self, chrom, start, end, contig_seq, samples):
-        self.chrom, self.start, self.end = chrom, int(start), int(end)
-        self.contig = np.ascontiguousarray(np.frombuffer(contig_seq, dtype=np.uint8) if isinstance(contig_seq, (bytes, bytearray)) else contig_seq,
-                                           dtype=np.uint8)
+        super().__init__(chrom, start, end, contig_seq)
         c = lambda t: (np.ascontiguousarray(t[0], dtype=np.uint8), np.ascontiguousarray(t[1], dtype=np.int64))
         self.samples = [(c(f), c(b)) for f, b in samples]    # [((data, rec_off) fetched, (data, rec_off) broken mates)]
-        self._c = None
 
     @classmethod
     def from_reads(cls, chrom, start, end, fasta, samples, **layout):
@@ -336,33 +369,23 @@ class BamRegion:
         return cls(chrom, start, end, fasta._seq[chrom],
                    [(synth.bam_records(fetched, **layout), synth.bam_records(sorted(broken, key=lambda r: r.matePos))) for fetched, broken in samples])
 
-    def fill(self, a, n_samples):
-        """Write this region into the plat_bam_region `a` (the arrays stay owned by, and alive with, this object)."""
-        assert len(self.samples) == n_samples
-        if self._c is None:
-            ss = (_BamSample * len(self.samples))()
-            for i, pair in enumerate(self.samples):
-                for t, (data, off) in zip((ss[i].fetched, ss[i].broken_mates), pair):
-                    t.n_records, t.data, t.data_len, t.rec_off = len(off), data.ctypes.data, len(data), off.ctypes.data
-            self._c = (self.chrom.encode(), self.contig.ctypes.data, len(self.contig), ss)
-        a.chrom, a.contig_seq, a.contig_len, a.samples = self._c
-        a.start, a.end = self.start, self.end
+    def _c_units(self):
+        ss = (_BamSample * len(self.samples))()
+        for i, (f, b) in enumerate(self.samples):
+            _fill_records(ss[i].fetched, *f)
+            _fill_records(ss[i].broken_mates, *b)
+        return (ss,)
 
 
-class BgzfRegion:
+class BgzfRegion(_BgzfWindow):
     """One region as an index lookup leaves it (include/platypus_caller_bgzf.h): the iterator's window (tid, itr_beg, itr_end) and per
     sample the chunks of the fetch -- each (data uint8 array of whole BGZF blocks, first_uoffset, end_coffset or -1, end_uoffset) -- and
     the broken mates as uncompressed records (data, rec_off), in mate-position order."""
 
     def __init__(self, chrom, start, end, contig_seq, tid, itr_beg, itr_end, samples):
-        self.chrom, self.start, self.end = chrom, int(start), int(end)
-        self.tid, self.itr_beg, self.itr_end = int(tid), int(itr_beg), int(itr_end)
-        self.contig = np.ascontiguousarray(np.frombuffer(contig_seq, dtype=np.uint8) if isinstance(contig_seq, (bytes, bytearray)) else contig_seq,
-                                           dtype=np.uint8)
-        u8 = lambda d: np.frombuffer(d, dtype=np.uint8) if isinstance(d, (bytes, bytearray)) else np.ascontiguousarray(d, dtype=np.uint8)
-        self.samples = [([(u8(d), int(fu), int(ec), int(eu)) for d, fu, ec, eu in chunks],
+        super().__init__(chrom, start, end, contig_seq, tid, itr_beg, itr_end)
+        self.samples = [([(_u8(d), int(fu), int(ec), int(eu)) for d, fu, ec, eu in chunks],
                          (np.ascontiguousarray(b[0], dtype=np.uint8), np.ascontiguousarray(b[1], dtype=np.int64))) for chunks, b in samples]
-        self._c = None
 
     @property
     def compressed_bytes(self):
@@ -414,24 +437,13 @@ class BgzfRegion:
         reg.made = made
         return reg
 
-    def fill(self, a, n_samples):
-        """Write this region into the plat_bgzf_region `a` (the arrays stay owned by, and alive with, this object)."""
-        assert len(self.samples) == n_samples
-        if self._c is None:
-            ss = (_BgzfSample * len(self.samples))()
-            keep = []
-            for i, (chunks, (bdata, boff)) in enumerate(self.samples):
-                cc = (_BgzfChunk * max(len(chunks), 1))()
-                for q, (d, fu, ec, eu) in enumerate(chunks):
-                    cc[q].data, cc[q].data_len, cc[q].first_uoffset, cc[q].end_coffset, cc[q].end_uoffset = d.ctypes.data, len(d), fu, ec, eu
-                keep.append(cc)
-                ss[i].n_chunks, ss[i].chunks = len(chunks), cc
-                t = ss[i].broken_mates
-                t.n_records, t.data, t.data_len, t.rec_off = len(boff), bdata.ctypes.data, len(bdata), boff.ctypes.data
-            self._c = (self.chrom.encode(), self.contig.ctypes.data, len(self.contig), ss, keep)
-        a.chrom, a.contig_seq, a.contig_len, a.samples = self._c[:4]
-        a.start, a.end = self.start, self.end
-        a.tid, a.itr_beg, a.itr_end = self.tid, self.itr_beg, self.itr_end
+    def _c_units(self):
+        ss = (_BgzfSample * len(self.samples))()
+        keep = [_chunk_array(chunks) for chunks, _ in self.samples]
+        for i, (chunks, broken) in enumerate(self.samples):
+            ss[i].n_chunks, ss[i].chunks = len(chunks), keep[i]
+            _fill_records(ss[i].broken_mates, *broken)
+        return ss, keep
 
 
 def merge_by_read_group(entries, key):
@@ -462,24 +474,17 @@ def _file_records(reads, aux):
     return data, off, np.diff(np.append(off, len(data))).astype(np.int32)
 
 
-def _fill_file_records(t, rec):
-    data, off, ln = rec
-    t.records.n_records, t.records.data, t.records.data_len, t.records.rec_off = len(off), data.ctypes.data, len(data), off.ctypes.data
-    t.rec_len = ln.ctypes.data
-
-
-class BamFileRegion:
+class BamFileRegion(_RegionBase):
     """One region of MERGED files (include/platypus_caller_rg.h): per file the uncompressed records of its fetch, in fetch order, and of
     the broken mates it fetched, in mate-position order -- each as (data uint8 array, rec_off int64 array, rec_len int32 array).  Every
     record carries its read group; NativeCaller.call_bam_regions_rg routes them to samples on the device."""
 
+    UNITS = "files"
+
     def __init__(self, chrom, start, end, contig_seq, files):
-        self.chrom, self.start, self.end = chrom, int(start), int(end)
-        self.contig = np.ascontiguousarray(np.frombuffer(contig_seq, dtype=np.uint8) if isinstance(contig_seq, (bytes, bytearray)) else contig_seq,
-                                           dtype=np.uint8)
+        super().__init__(chrom, start, end, contig_seq)
         c = lambda t: (np.ascontiguousarray(t[0], dtype=np.uint8), np.ascontiguousarray(t[1], dtype=np.int64), np.ascontiguousarray(t[2], dtype=np.int32))
         self.files = [(c(f), c(b)) for f, b in files]
-        self._c = None
 
     @property
     def record_bytes(self):
@@ -498,33 +503,25 @@ class BamFileRegion:
             out.append((_file_records(*f), _file_records(*b)))
         return cls(chrom, start, end, fasta._seq[chrom], out)
 
-    def fill(self, a, n_files):
-        """Write this region into the plat_bam_rg_region `a` (the arrays stay owned by, and alive with, this object)."""
-        assert len(self.files) == n_files
-        if self._c is None:
-            ff = (_BamFile * len(self.files))()
-            for i, (f, b) in enumerate(self.files):
-                _fill_file_records(ff[i].fetched, f)
-                _fill_file_records(ff[i].broken_mates, b)
-            self._c = (self.chrom.encode(), self.contig.ctypes.data, len(self.contig), ff)
-        a.chrom, a.contig_seq, a.contig_len, a.files = self._c
-        a.start, a.end = self.start, self.end
+    def _c_units(self):
+        ff = (_BamFile * len(self.files))()
+        for i, (f, b) in enumerate(self.files):
+            _fill_file_records(ff[i].fetched, f)
+            _fill_file_records(ff[i].broken_mates, b)
+        return (ff,)
 
 
-class BgzfFileRegion:
+class BgzfFileRegion(_BgzfWindow):
     """One region of MERGED files as index lookups leave it (include/platypus_caller_rg.h): the iterator's window and per file the chunks
     of its fetch (as BgzfRegion's samples hold them) and its broken mates as uncompressed records (data, rec_off, rec_len)."""
 
+    UNITS = "files"
+
     def __init__(self, chrom, start, end, contig_seq, tid, itr_beg, itr_end, files):
-        self.chrom, self.start, self.end = chrom, int(start), int(end)
-        self.tid, self.itr_beg, self.itr_end = int(tid), int(itr_beg), int(itr_end)
-        self.contig = np.ascontiguousarray(np.frombuffer(contig_seq, dtype=np.uint8) if isinstance(contig_seq, (bytes, bytearray)) else contig_seq,
-                                           dtype=np.uint8)
-        u8 = lambda d: np.frombuffer(d, dtype=np.uint8) if isinstance(d, (bytes, bytearray)) else np.ascontiguousarray(d, dtype=np.uint8)
-        self.files = [([(u8(d), int(fu), int(ec), int(eu)) for d, fu, ec, eu in chunks],
+        super().__init__(chrom, start, end, contig_seq, tid, itr_beg, itr_end)
+        self.files = [([(_u8(d), int(fu), int(ec), int(eu)) for d, fu, ec, eu in chunks],
                        (np.ascontiguousarray(b[0], dtype=np.uint8), np.ascontiguousarray(b[1], dtype=np.int64), np.ascontiguousarray(b[2], dtype=np.int32)))
                       for chunks, b in files]
-        self._c = None
 
     @property
     def compressed_bytes(self):
@@ -546,23 +543,13 @@ class BgzfFileRegion:
         itr = (windows[0][0], min(w[1] for w in windows), max(w[2] for w in windows)) if windows else (0, int(start), int(end))
         return cls(chrom, start, end, fasta._seq[chrom], itr[0], itr[1], itr[2], out)
 
-    def fill(self, a, n_files):
-        """Write this region into the plat_bgzf_rg_region `a` (the arrays stay owned by, and alive with, this object)."""
-        assert len(self.files) == n_files
-        if self._c is None:
-            ff = (_BgzfFile * len(self.files))()
-            keep = []
-            for i, (chunks, b) in enumerate(self.files):
-                cc = (_BgzfChunk * max(len(chunks), 1))()
-                for q, (d, fu, ec, eu) in enumerate(chunks):
-                    cc[q].data, cc[q].data_len, cc[q].first_uoffset, cc[q].end_coffset, cc[q].end_uoffset = d.ctypes.data, len(d), fu, ec, eu
-                keep.append(cc)
-                ff[i].n_chunks, ff[i].chunks = len(chunks), cc
-                _fill_file_records(ff[i].broken_mates, b)
-            self._c = (self.chrom.encode(), self.contig.ctypes.data, len(self.contig), ff, keep)
-        a.chrom, a.contig_seq, a.contig_len, a.files = self._c[:4]
-        a.start, a.end = self.start, self.end
-        a.tid, a.itr_beg, a.itr_end = self.tid, self.itr_beg, self.itr_end
+    def _c_units(self):
+        ff = (_BgzfFile * len(self.files))()
+        keep = [_chunk_array(chunks) for chunks, _ in self.files]
+        for i, (chunks, broken) in enumerate(self.files):
+            ff[i].n_chunks, ff[i].chunks = len(chunks), keep[i]
+            _fill_file_records(ff[i].broken_mates, broken)
+        return ff, keep
 
 
 def region_from_arrays(reg, pin=False, packed=False):
@@ -864,6 +851,21 @@ class NativeCaller:
             raise _lib.PlatypusDeviceError(rc, "plat_caller_set_source_lines", "plat_caller_set_source_lines")
         return texts, arr
 
+    def _finish(self, rc, entry, text, length, o, st, options, raw=False):
+        """What follows every call into the region loop: the library's message as PlatypusDeviceError, or the text (as _native_text hands
+        it over), options.rlen as the reference updates it, self.stats."""
+        if rc != 0:
+            raise _lib.PlatypusDeviceError(rc, (self.lib.plat_caller_last_error(self.h) or b"").decode(), entry)
+        out = _native_text(self.lib, text, length.value, raw)
+        options.rlen = int(o.rlen)
+        self.stats = st.as_dict()
+        return out
+
+    def _call_args(self, sample_names, options):
+        """(names array, plat_caller_options, text pointer, length, stats) of one call."""
+        names = (C.c_char_p * len(sample_names))(*[s.encode() for s in sample_names])
+        return names, CallerOptions.from_options(options), C.c_void_p(), C.c_size_t(), CallerStats()
+
     def call_regions(self, regions, sample_names, options, source_lines=None):
         """regions: list of RegionReads.  Returns the record lines of all regions (str), in region order; options.rlen is updated
         as the reference updates it.  source_lines: per region the text its source VCF fetches returned (set_source_lines; longHaps is
@@ -873,80 +875,67 @@ class NativeCaller:
         arr = (_Region * max(n, 1))()
         for k, r in enumerate(regions):
             r.fill(arr[k], nS)
-        names = (C.c_char_p * nS)(*[s.encode() for s in sample_names])
-        o = CallerOptions.from_options(options)
-        text, length, st = C.c_void_p(), C.c_size_t(), CallerStats()
+        names, o, text, length, st = self._call_args(sample_names, options)
         rc = self.lib.plat_call_regions(self.h, arr, n, nS, names, C.byref(o), C.byref(text), C.byref(length), C.byref(st))
         del keep
-        if rc != 0:
-            raise _lib.PlatypusDeviceError(rc, (self.lib.plat_caller_last_error(self.h) or b"").decode(), "plat_call_regions")
-        try:
-            out = C.string_at(text, length.value).decode("ascii")
-        finally:
-            self.lib.plat_caller_free(text)
-        options.rlen = int(o.rlen)
-        self.stats = st.as_dict()
-        return out
+        return self._finish(rc, "plat_call_regions", text, length, o, st, options)
 
     def call_bam_regions(self, regions, sample_names, options, source_lines=None):
         """regions: list of BamRegion.  As call_fetched_regions, with ReadIterator.get (htslibWrapper.pyx:328-406) on the device in front: the
         records are uploaded as they are and decoded there (plat_bam_decode_batch); the same text, rlen, self.loaded and self.read_counts."""
-        return self.call_fetched_regions(regions, sample_names, options, _entry="plat_call_bam_regions", _struct=_BamRegion, source_lines=source_lines)
+        return self._call_front("plat_call_bam_regions", _BamRegion, regions, sample_names, options, source_lines=source_lines)
 
     def call_bgzf_regions(self, regions, sample_names, options):
         """regions: list of BgzfRegion.  As call_bam_regions, with the BGZF blocks inflated (plat_bgzf_inflate_batch) and sam_itr_next applied
         (plat_bam_find_records) on the device in front: the compressed bytes are uploaded as they are; the same text, rlen, self.loaded and
         self.read_counts; stats["input_bytes"] counts the compressed bytes."""
-        return self.call_fetched_regions(regions, sample_names, options, _entry="plat_call_bgzf_regions", _struct=_BgzfRegion)
+        return self._call_front("plat_call_bgzf_regions", _BgzfRegion, regions, sample_names, options)
 
     def call_bam_regions_rg(self, regions, read_groups, sample_names, options):
         """regions: list of BamFileRegion (all with the same number of files); read_groups: {read-group ID: sample index} or a list of
         (ID, sample index).  As call_bam_regions on the samples' records, with the split by read group (the second branch of loadBAMData,
         platypusutils.pyx:573-666) on the device in front (plat_bam_route_batch): the same text, rlen, self.loaded and self.read_counts."""
-        return self.call_fetched_regions(regions, sample_names, options, _entry="plat_call_bam_regions_rg", _struct=_BamRgRegion, _groups=read_groups)
+        return self._call_front("plat_call_bam_regions_rg", _BamRgRegion, regions, sample_names, options, groups=read_groups)
 
     def call_bgzf_regions_rg(self, regions, read_groups, sample_names, options):
         """regions: list of BgzfFileRegion.  As call_bam_regions_rg, from the files' BGZF blocks (inflate, find, route, decode on the device)."""
-        return self.call_fetched_regions(regions, sample_names, options, _entry="plat_call_bgzf_regions_rg", _struct=_BgzfRgRegion, _groups=read_groups)
+        return self._call_front("plat_call_bgzf_regions_rg", _BgzfRgRegion, regions, sample_names, options, groups=read_groups)
 
-    def call_fetched_regions(self, regions, sample_names, options, _entry="plat_call_fetched_regions", _struct=_FetchedRegion, _groups=None, source_lines=None):
+    def call_fetched_regions(self, regions, sample_names, options, source_lines=None):
         """regions: list of FetchedRegion.  The loader's work (addReadToBuffer's QC and split, isSorted, maxReads) on the device, then the
         region loop as call_regions runs it; the QC options come from the same `options`.  Returns the record lines (str); options.rlen is
         updated as the reference updates it.  self.loaded[k] (0: region k reached maxReads and was not called) and self.read_counts[k]
         (int32 [n_samples, 10]: n_good, n_bad, the 8 reason counts -- filteredReadCountsByType slots 0-6 and secondary alignments) describe
         the last call.  source_lines: as call_regions takes them, one entry per region of THIS list (the regions the loader gives up on
         included: their lines are dropped with them)."""
+        return self._call_front("plat_call_fetched_regions", _FetchedRegion, regions, sample_names, options, source_lines=source_lines)
+
+    def _call_front(self, entry, struct, regions, sample_names, options, groups=None, source_lines=None):
+        """One call of a front end of the region loop (include/platypus_caller_{fetched,bam,bgzf,rg}.h): `struct` is its region struct,
+        `groups` the read-group table of the merged-file calls."""
         n, nS = len(regions), len(sample_names)
         keep_source = self.set_source_lines(source_lines, getattr(options, "longHaps", 0)) if source_lines is not None else None
         extra = ()
         n_units = nS
-        if _groups is not None:                                              # the merged-file calls: regions of files, and the read-group table
+        if groups is not None:                                               # the merged-file calls: regions of files, and the read-group table
             n_units = len(regions[0].files) if regions else 1
-            pairs = list(_groups.items()) if isinstance(_groups, dict) else list(_groups)
+            pairs = list(groups.items()) if isinstance(groups, dict) else list(groups)
             ids = (C.c_char_p * max(len(pairs), 1))(*[g if isinstance(g, bytes) else g.encode() for g, _ in pairs])
             smp = np.array([s for _, s in pairs], dtype=np.int32)
-            groups = _BamReadGroups(len(pairs), ids, smp.ctypes.data)
-            extra = (n_units, C.byref(groups), nS)
-        arr = (_struct * max(n, 1))()
+            table = _BamReadGroups(len(pairs), ids, smp.ctypes.data)
+            extra = (n_units, C.byref(table), nS)
+        arr = (struct * max(n, 1))()
         for k, r in enumerate(regions):
             r.fill(arr[k], n_units)
-        names = (C.c_char_p * nS)(*[s.encode() for s in sample_names])
-        o, q = CallerOptions.from_options(options), CallerQCOptions.from_options(options)
+        names, o, text, length, st = self._call_args(sample_names, options)
+        q = CallerQCOptions.from_options(options)
         counts = np.zeros((max(n, 1), nS, 10), dtype=np.int32)
         info = (_FetchedRegionInfo * max(n, 1))()
         for k in range(n):
             info[k].sample_counts = counts[k].ctypes.data
-        text, length, st = C.c_void_p(), C.c_size_t(), CallerStats()
-        rc = getattr(self.lib, _entry)(self.h, arr, n, *(extra or (nS,)), names, C.byref(o), C.byref(q), C.byref(text), C.byref(length), info, C.byref(st))
+        rc = getattr(self.lib, entry)(self.h, arr, n, *(extra or (nS,)), names, C.byref(o), C.byref(q), C.byref(text), C.byref(length), info, C.byref(st))
         del keep_source
-        if rc != 0:
-            raise _lib.PlatypusDeviceError(rc, (self.lib.plat_caller_last_error(self.h) or b"").decode(), _entry)
-        try:
-            out = C.string_at(text, length.value).decode("ascii")
-        finally:
-            self.lib.plat_caller_free(text)
-        options.rlen = int(o.rlen)
-        self.stats = st.as_dict()
+        out = self._finish(rc, entry, text, length, o, st, options)
         self.loaded = [int(info[k].loaded) for k in range(n)]
         self.read_counts = counts[:n]
         return out
@@ -980,18 +969,11 @@ class NativeCaller:
                     return -9
             keep = LOAD_FN(tramp)
             load = C.cast(keep, C.c_void_p)
-        names = (C.c_char_p * nS)(*[s.encode() for s in sample_names])
-        o = CallerOptions.from_options(options)
-        text, length, st = C.c_void_p(), C.c_size_t(), CallerStats()
+        names, o, text, length, st = self._call_args(sample_names, options)
         rc = self.lib.plat_call_regions_stream(self.h, n_regions, nS, names, C.byref(o), load, user, n_slots, n_loaders, C.byref(text), C.byref(length),
                                                C.byref(st))
         del keep, keep_source
-        if rc != 0:
-            raise _lib.PlatypusDeviceError(rc, (self.lib.plat_caller_last_error(self.h) or b"").decode(), "plat_call_regions_stream")
-        out = _native_text(self.lib, text, length.value, raw)
-        options.rlen = int(o.rlen)
-        self.stats = st.as_dict()
-        return out
+        return self._finish(rc, "plat_call_regions_stream", text, length, o, st, options, raw)
 
 
 LOAD_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(_Region))
