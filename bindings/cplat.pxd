@@ -441,6 +441,32 @@ cdef extern from "platypus_mi355x.h":
         int32_t* region_stats
         int64_t* status
     int plat_source_variants_batch(plat_ctx* ctx, const plat_source_variants_in* inp, const plat_source_variants_out* out, void* stream) nogil
+    # read counts of reference-call blocks (outputRefCall's loop over countReadsCoveringRegion)
+    int PLAT_REFCOV_RAISES
+    int PLAT_REFCOV_EMPTY
+    int PLAT_REFCOV_TILE
+    ctypedef struct plat_refcov_in:
+        int32_t n_intervals
+        int32_t n_slices
+        int32_t n_tiles
+        int32_t n_reads
+        const int32_t* read_pos
+        const int32_t* read_end
+        const int32_t* slice_begin
+        const int32_t* slice_n
+        const int32_t* slice_longest
+        const int32_t* iv_start
+        const int32_t* iv_end
+        const int32_t* iv_slice_first
+        const int32_t* iv_n_samples
+        const int64_t* iv_count_off
+        const int32_t* iv_tile_first
+    ctypedef struct plat_refcov_out:
+        int64_t cap_counts
+        int32_t* iv_min
+        int32_t* counts
+    int plat_refcall_coverage_batch(plat_ctx* ctx, const plat_refcov_in* inp, const plat_refcov_out* out, void* stream) nogil
+    int plat_refcov_lds_reads() nogil
     # the same for a PLAT_READS_PACKED table (one byte per base + exceptions): QC and trimming on the packed bytes, no quality array
     ctypedef struct plat_read_buffers_packed_in:
         plat_readqc_batch qc

@@ -186,6 +186,9 @@ typedef struct plat_caller_stats {
     /* ... chunks whose lines were parsed on the device (plat_source_variants_batch; the others by the host parser), and calls of it that
      * were repeated with room for every allele after PLAT_ERR_OVERFLOW */
     int64_t n_source_chunks_device, n_source_retries;
+    /* outputRefCalls: blocks and window spans whose read counts came from the device (plat_refcall_coverage_batch), the positions they
+     * cover, and REFCALL decisions (lines and the uncalled windows' zero test) that ran the host's per-position loop instead */
+    int64_t n_refcall_intervals_device, n_refcall_positions_device, n_refcall_intervals_host;
 } plat_caller_stats;
 
 typedef struct plat_caller plat_caller;

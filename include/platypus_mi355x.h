@@ -851,6 +851,58 @@ typedef struct plat_source_variants_out {
 
 int plat_source_variants_batch(plat_ctx* ctx, const plat_source_variants_in* in, const plat_source_variants_out* out, void* stream);
 
+/* ---- read counts of reference-call blocks ------------------------------------------------------------------------
+ * Replaces the loop of  outputRefCall   variantcaller.pyx:774-784  over  ReadArray.countReadsCoveringRegion(p, p + 1)   cwindow.pyx:176-206
+ * (one call per position of a block and per sample: the block's QUAL is computed from the smallest count)
+ * for n_intervals half-open intervals [iv_start[k], iv_end[k]) over read tables that are resident and sorted: read_pos / read_end [n_reads]
+ * as plat_stage_b_in takes them.  Interval k belongs to the iv_n_samples[k] slices iv_slice_first[k] ... of slice_begin / slice_n /
+ * slice_longest [n_slices]: the GOOD reads of one sample of one region inside the table, `longest` their getLengthOfLongestRead (:167-172).
+ *
+ * The rule, per slice (pos, end, N, longest) and position p:
+ *   N == 0:    c = 0
+ *   otherwise  s0 = lower_bound(pos, max(1, p - longest)), e0 = lower_bound(pos, p + 1); s0 walks on while s0 < N and end[s0] <= p;
+ *              c = e0 - s0.  c < 0 is where the reference raises ("Read start pointer > read end pointer"); the walk may stop there.
+ * c is a difference of two pointers and not the number of covering reads: a short read lying between two covering reads is counted, and
+ * a read at position 0 is never found by the first bound.  Both are reproduced.
+ *
+ * Output: iv_min[k] = the smallest c over the interval's samples and positions; PLAT_REFCOV_RAISES if any c < 0 (a data verdict, not an
+ * error: the other intervals are unaffected); PLAT_REFCOV_EMPTY if iv_start >= iv_end or iv_n_samples == 0.  Where iv_count_off[k] >= 0
+ * also counts[iv_count_off[k] + (p - iv_start[k])] = the smallest c over the samples at p, PLAT_REFCOV_RAISES where negative; an entry at
+ * or behind cap_counts is not written.  A slice index outside [0, n_slices) or a slice outside [0, n_reads) is refused: it counts as
+ * PLAT_REFCOV_RAISES wherever it is asked.
+ *
+ * One 256-thread workgroup per tile of at most PLAT_REFCOV_TILE consecutive positions of one interval; the caller (who made the
+ * intervals) hands the tile list over as iv_tile_first [n_intervals + 1]: interval k owns the tiles iv_tile_first[k] ... iv_tile_first[k + 1]
+ * - 1, max(1, ceil(length / PLAT_REFCOV_TILE)) of them, n_tiles = iv_tile_first[n_intervals].  With n_tiles == n_intervals (no interval
+ * longer than a tile) iv_tile_first is not read and may be NULL, and the call is one kernel; otherwise a second kernel takes the
+ * intervals' minima over their tiles' (kept in the context's scratch).  An interval's last tile goes on over positions the list left
+ * out, so a list with too few tiles costs time and not values; an interval without any tile is reported as PLAT_REFCOV_RAISES.
+ * Per sample the workgroup finds the index range that holds every bound of its tile by two bisections of the slice, stages the range's
+ * pos / end in LDS when it holds at most plat_refcov_lds_reads() reads (a deeper pile runs the same code on global memory) and bisects
+ * there, one thread per position.  Every output element is written by exactly one workgroup: no fill, no atomics.  The call does not
+ * wait; nothing traps.                                                                                                          */
+#define PLAT_REFCOV_RAISES (-1)
+#define PLAT_REFCOV_EMPTY 2147483647
+#define PLAT_REFCOV_TILE 1024
+
+typedef struct plat_refcov_in {
+    int32_t n_intervals, n_slices, n_tiles, n_reads;
+    const int32_t* read_pos; const int32_t* read_end;
+    const int32_t* slice_begin; const int32_t* slice_n; const int32_t* slice_longest;
+    const int32_t* iv_start; const int32_t* iv_end; const int32_t* iv_slice_first; const int32_t* iv_n_samples;
+    const int64_t* iv_count_off;
+    const int32_t* iv_tile_first;
+} plat_refcov_in;
+
+typedef struct plat_refcov_out {
+    int64_t cap_counts;
+    int32_t* iv_min;
+    int32_t* counts;
+} plat_refcov_out;
+
+int plat_refcall_coverage_batch(plat_ctx* ctx, const plat_refcov_in* in, const plat_refcov_out* out, void* stream);
+int plat_refcov_lds_reads(void);                            /* reads of one sample a tile's range may hold to be staged in LDS */
+
 /* ---- read statistics of the VCF INFO field ---------------------------------------
  * Replaces the per-variant loop over a window's reads in  cdef dict vcfINFO(...)   vcfutils.pyx:1300-1390
  * (readOverlapsVariant :901-913, readQualIsGoodVariantPosition :917-943, variantSupportedByRead :961-1072).

@@ -152,6 +152,19 @@ class InfoStatsBatch(C.Structure):
         "read_pos", "read_end", "read_mapq", "read_flags", "cigar", "cig_off")]
 
 
+class RefCovIn(C.Structure):
+    _fields_ = ([(k, C.c_int32) for k in ("n_intervals", "n_slices", "n_tiles", "n_reads")] +
+                [(k, C.c_void_p) for k in ("read_pos", "read_end", "slice_begin", "slice_n", "slice_longest", "iv_start", "iv_end", "iv_slice_first",
+                                           "iv_n_samples", "iv_count_off", "iv_tile_first")])
+
+
+class RefCovOut(C.Structure):
+    _fields_ = [("cap_counts", C.c_int64), ("iv_min", C.c_void_p), ("counts", C.c_void_p)]
+
+
+PLAT_REFCOV_RAISES, PLAT_REFCOV_EMPTY, PLAT_REFCOV_TILE = -1, 2147483647, 1024
+
+
 class PackedReads(C.Structure):
     _fields_ = [("read_src", C.c_void_p), ("n_exc", C.c_int64), ("exc_index", C.c_void_p), ("exc_base", C.c_void_p), ("exc_qual", C.c_void_p)]
 
@@ -260,6 +273,8 @@ SIGNATURES = {
     "plat_bam_find_records": (C.c_int, [C.c_void_p, C.POINTER(BamFindIn), C.POINTER(BamFindOut), C.c_void_p]),
     "plat_bam_route_batch": (C.c_int, [C.c_void_p, C.POINTER(BamRouteIn), C.POINTER(BamRouteOut), C.c_void_p]),
     "plat_source_variants_batch": (C.c_int, [C.c_void_p, C.POINTER(SourceVariantsIn), C.POINTER(SourceVariantsOut), C.c_void_p]),
+    "plat_refcall_coverage_batch": (C.c_int, [C.c_void_p, C.POINTER(RefCovIn), C.POINTER(RefCovOut), C.c_void_p]),
+    "plat_refcov_lds_reads": (C.c_int, []),
     "plat_variant_read_stats_batch": (C.c_int, [C.c_void_p, C.POINTER(InfoStatsBatch), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
     "plat_variant_info_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -274,7 +289,7 @@ SIGNATURES = {
 # entry points a stand-in library built against an earlier header may lack (the CPU suite's fake device): bind() leaves them
 # unbound there; load() still requires every declared symbol of the real library
 ADDED_LATER = ("plat_read_buffers_batch", "plat_read_buffers_packed_batch", "plat_bam_decode_batch", "plat_bgzf_inflate_batch", "plat_bam_find_records",
-               "plat_bam_route_batch", "plat_source_variants_batch",
+               "plat_bam_route_batch", "plat_source_variants_batch", "plat_refcall_coverage_batch", "plat_refcov_lds_reads",
                "plat_concat_read_tables_src", "plat_pack_codes_pieces", "plat_candidates_batch_packed", "plat_gather_reads_packed",
                "plat_variant_read_stats_packed_batch")
 

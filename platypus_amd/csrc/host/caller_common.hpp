@@ -199,15 +199,20 @@ struct Slot {
     Buffer<uint8_t> src_text;
     View<int64_t> src_off, src_hash, src_status, src_remoff, src_addoff;
     View<int32_t> src_begin, src_stats, src_pos, src_nrem, src_nadd, src_hashes, src_line;
+    // read counts of reference-call blocks (plat_refcall_coverage_batch): slices, intervals, tile list; minima and per-position counts
+    View<int32_t> rc_sbegin, rc_sn, rc_slong, rc_start, rc_end, rc_sfirst, rc_ns, rc_tfirst, rc_min, rc_counts;
+    View<int64_t> rc_off;
     // many small arrays travel as ONE copy: the Views above lie in these blocks (Layout)
-    Arena a_tab, a_desc, a_cin, a_cout, a_mout, a_win, a_wout, a_pin, a_sin, a_sout, a_asin, a_asout, a_bin, a_bout, a_srcin, a_srcout;
+    Arena a_tab, a_desc, a_cin, a_cout, a_mout, a_win, a_wout, a_pin, a_sin, a_sout, a_asin, a_asout, a_bin, a_bout, a_srcin, a_srcout, a_rcin, a_rcout;
     // per-region capacities of plat_stage_b_batch's outputs (they are downloaded whole): doubled when a region does not fit
     int sbCapV = 320, sbCapW = 192, sbCapA = 2048;
     double t_host = 0, t_wait = 0;
+    int64_t nSyncs = 0;                                                    // waits so far: what was enqueued in front of the last one has arrived
 
     void sync(const char* where) {
         const auto t0 = Clock::now();
         const int rc = plat_stream_sync(ctx, stream);
+        ++nSyncs;
         t_wait += secs(t0, Clock::now());
         ck(rc, where);
     }
@@ -446,6 +451,7 @@ struct WindowWork {
     std::string text;                                                      // its record lines (and, with outputRefCalls, the REFCALL lines that belong to it)
     int64_t nRecords = 0, nRefRecords = 0;
     int firstFlat = -1;                                                    // outputRefCalls: index of its first flat-prior posterior (one per variant of `vars`)
+    int covIv = -1;                                                        // outputRefCalls: its span's interval in the chunk's device read counts (Chunk::launchRefCoverage)
     // A fresh window in a recycled object (WindowList): every member back to its initial value, the containers EMPTY BUT WITH THEIR STORAGE --
     // a window is five heap blocks (haplotypes, text, positions, INFO, posteriors) that were allocated and freed once per window and pass.
     void reset() {
@@ -456,7 +462,7 @@ struct WindowWork {
         greedy = false; if (hostState) hostState->clear();
         bw = -1; hapBegin = 0; onDevice = false;
         distinct.clear(); called.clear(); calledPost.clear(); byPos.clear(); info.clear();
-        firstStatVar = 0; firstSite = 0; failed = false; text.clear(); nRecords = 0; nRefRecords = 0; firstFlat = -1;
+        firstStatVar = 0; firstSite = 0; failed = false; text.clear(); nRecords = 0; nRefRecords = 0; firstFlat = -1; covIv = -1;
     }
 };
 // The windows of a region: a vector whose elements outlive the region -- a worker keeps the storage of the regions it has finished and hands
@@ -510,7 +516,10 @@ struct VariantPool {
 };
 
 // what the region loop writes, in the order it writes it: calling windows and (outputRefCalls=1) reference-call blocks
-struct Item { int kind; int window; std::string text; int64_t nRef = 0; };     // kind 0: windows[window]; 1: a block whose line is already in `text`
+// kind 0: windows[window]; 1: a block [start, end) between calling windows, its line written when the chunk's read counts are there (Chunk::run):
+// nReads is the samples' reads between the window pointers as the loop had left them when it met the block (r.cur then), iv the block's
+// interval in the chunk's device read counts or -1
+struct Item { int kind; int window; std::string text; int64_t nRef = 0; int start = 0, end = 0, iv = -1; std::vector<int> nReads; };
 
 struct RegionWork {
     const plat_region* in = nullptr;

@@ -1,6 +1,7 @@
 // chunk.hpp -- one chunk of regions going through the stages on one worker thread
 // (native region loop, libplat_caller.so: see region_caller.cpp for the stage map and the reference citations)
 #pragma once
+#include "../refcov_rule.hpp"
 #include "caller_common.hpp"
 
 namespace plathost {
@@ -41,7 +42,7 @@ struct Chunk {
     }
     Layout lmLayout;
 
-    // -- B on the device (plat_stage_b_batch): regions with one sample, candidates from the reads alone, no reference-call blocks
+    // -- B on the device (plat_stage_b_batch): regions with one sample, candidates from the reads alone (reference-call blocks: the host lays them around the device's windows)
     bool deviceB = false;
     DeviceBatch devBatch;
     int capV = 0, capW = 0, capA = 0;                                       // (of this chunk: the worker's current ones, Slot::sbCap*)
@@ -114,7 +115,15 @@ struct Chunk {
     void regionWindows(RegionWork& r);
     static std::vector<int> snapshotNR(const PtrList& ptrs);
 
-    bool refCallLine(const RegionWork& r, std::string& out, int windowStart, int windowEnd, const std::vector<int>& nReads, bool hasVariants, double maxPost) const;
+    // -- reference-call blocks (outputRefCalls=1, stage_f.hpp): the chunk's read counts from the device, and the host's loop where they do not reach
+    struct CovInterval { int start, end; int64_t off; };                   // off: of its per-position counts in rc_counts, -1: its minimum only (rc_min)
+    std::vector<CovInterval> covIv;
+    bool covLaunched = false;
+    int64_t covSyncMark = 0;
+    void launchRefCoverage();
+    bool coverageReady();
+    long minCoverage(const RegionWork& r, int iv, int a, int b);
+    bool refCallLine(const RegionWork& r, std::string& out, int windowStart, int windowEnd, const std::vector<int>& nReads, bool hasVariants, double maxPost, long minCov) const;
 
     void prepareWindow(RegionWork& r, WindowWork& w);
 
@@ -187,6 +196,7 @@ struct Chunk {
         }
         lap(2);
         greedyRounds();
+        launchRefCoverage();
         lap(3);
         std::vector<WindowWork*> wins, devWins;
         int64_t nWin = 0, nVar = 0, nCand = 0;
@@ -245,11 +255,16 @@ struct Chunk {
             int nHapLast = 0;                                               // haplotypes of the last window set up in this region (Population.nHaplotypes)
             {   // (the region's text in one allocation: it is the sum of its items' texts but for the rare lines written here)
                 size_t need = r->text.size() + 256;
-                for (const Item& it : r->items) need += it.kind == 1 ? it.text.size() : r->windows[(size_t)it.window].text.size();
+                for (const Item& it : r->items) need += it.kind == 1 ? 160 + 8 * it.nReads.size() : r->windows[(size_t)it.window].text.size();
                 r->text.reserve(need);
             }
             for (Item& it : r->items) {
-                if (it.kind == 1) { r->text += it.text; nRec += it.nRef; nRef += it.nRef; continue; }
+                if (it.kind == 1) {                                         // a block between calling windows (:605-607): its line, now that the read counts are here
+                    try {
+                        if (refCallLine(*r, r->text, it.start, it.end, it.nReads, false, 0.0, minCoverage(*r, it.iv, it.start, it.end))) { ++nRec; ++nRef; }
+                    } catch (const WindowError& e) { logWindowFailure(r->in->chrom, it.start, it.end, e.what()); }
+                    continue;
+                }
                 WindowWork& w = r->windows[(size_t)it.window];
                 if (w.failed) continue;
                 if (w.live) { r->text += w.text; nRec += w.nRecords; nRef += w.nRefRecords; nHapLast = (int)w.haps.size(); continue; }
@@ -259,13 +274,13 @@ struct Chunk {
                 // set up for, so calculatePosterior's loop raises (logged, skipped) -- unless it never was set up in this region
                 try {
                     bool ok;
-                    if (w.vars.empty()) ok = refCallLine(*r, r->text, w.startPos, w.endPos, snapshotNR(w.ptrs), false, 0.0);
+                    if (w.vars.empty()) ok = refCallLine(*r, r->text, w.startPos, w.endPos, snapshotNR(w.ptrs), false, 0.0, minCoverage(*r, w.covIv, w.startPos, w.endPos));
                     else {
                         // (minCov == 0 decides before the posterior is asked for)
-                        if (nHapLast > 0 && !coverageHasAZero(*r, w.startPos, w.endPos)) throw WindowError("list index out of range");
+                        if (nHapLast > 0 && !coverageHasAZero(*r, w.covIv, w.startPos, w.endPos)) throw WindowError("list index out of range");
                         const double prior = 0.5;
                         const double post = py2_round0(-10.0 * (log10(1.0 * (1.0 - prior)) - log10(prior + 1.0 * (1.0 - prior))));
-                        ok = refCallLine(*r, r->text, w.startPos, w.endPos, snapshotNR(w.ptrs), true, post);
+                        ok = refCallLine(*r, r->text, w.startPos, w.endPos, snapshotNR(w.ptrs), true, post, minCoverage(*r, w.covIv, w.startPos, w.endPos));
                     }
                     if (ok) { ++nRec; ++nRef; }
                     else throw WindowError("cannot convert float infinity to integer");
@@ -288,17 +303,22 @@ struct Chunk {
         for (int k = 0; k < 8; ++k) { st.seconds_stage[k] += stage[k]; g_stageWait[k] += stageWait[k]; }
         g_stageWait[8] += total - waited; g_stageWait[9] += waited;
     }
-    bool coverageHasAZero(const RegionWork& r, int windowStart, int windowEnd) const {
+    // some position of [windowStart, windowEnd) has no read between its two pointers in some sample (or raises: the caller's refCallLine says so)
+    bool coverageHasAZero(const RegionWork& r, int iv, int windowStart, int windowEnd) {
+        if (iv >= 0 && windowStart < windowEnd && coverageReady()) {
+            const CovInterval& q = covIv[(size_t)iv];
+            if (q.off >= 0 && windowStart >= q.start && windowEnd <= q.end) {
+                const int32_t* c = s.rc_counts.h + q.off + ((int64_t)windowStart - q.start);
+                for (int k = 0; k < windowEnd - windowStart; ++k) if (c[k] <= 0) return true;
+                return false;
+            }
+        }
+        { std::lock_guard<std::mutex> g(stMutex); ++st.n_refcall_intervals_host; }
         for (const SampleView& sv : r.samples) {
             const TableView& tv = sv.reads;
-            const int N = tv.n();
-            if (N == 0) return windowStart < windowEnd;
-            for (int p = windowStart; p < windowEnd; ++p) {
-                int s0 = TableView::lowerBound(tv.t->pos, N, std::max<int64_t>(1, (int64_t)p - tv.longest));
-                const int e0 = TableView::lowerBound(tv.t->pos, N, (int64_t)p + 1);
-                while (s0 < N && tv.t->end[s0] <= p) ++s0;
-                if (std::min(e0, N) - s0 <= 0) return true;
-            }
+            if (tv.n() == 0) return windowStart < windowEnd;
+            for (int p = windowStart; p < windowEnd; ++p)
+                if (refcov::count_at(tv.t->pos, tv.t->end, tv.n(), tv.longest, p) <= 0) return true;
         }
         return false;
     }

@@ -16,7 +16,7 @@
 //                          assembler tiles (plat_assemble_batch)
 //   B  stage_b_device.hpp  regions with one sample: candidates -> variants -> windows -> window pointers -> haplotypes -> the window
 //                          batch, on the device (plat_stage_b_batch), launched behind the merge with no round trip in between
-//      stage_b_host.hpp    the same on the host: cohorts, assembly / reference-call runs, and every region or window the device flags
+//      stage_b_host.hpp    the same on the host: cohorts, assembly runs, and every region or window the device flags
 //                          (greedy haplotype filter: plat_align_window_batch per round)
 //   C-E stage_cde.hpp      window read slices gathered on the device, likelihoods, genotype likelihoods, HapScore, EM (plat_gather_reads,
 //                          plat_align_window_batch_async, plat_genotype_window_batch, plat_haplotype_score_batch, plat_em_window_batch);

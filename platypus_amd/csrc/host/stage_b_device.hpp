@@ -6,7 +6,7 @@
 namespace plathost {
 
 inline bool Chunk::eligibleDeviceB() const {
-    if (nInd != 1 || o.assemble || o.outputRefCalls || !o.getVariantsFromBAMs || o.maxHaplotypes < 3 || regions.empty()) return false;
+    if (nInd != 1 || o.assemble || !o.getVariantsFromBAMs || o.maxHaplotypes < 3 || regions.empty()) return false;
     if (hasSourceLines()) return false;                                 // (a region with source VCF lines takes the host's stage B, as assembly runs do)
     return !o.sw.hostB;                                                 // (measurements / tests: stage B on the host)
 }
@@ -119,8 +119,6 @@ inline void Chunk::stageBFromDevice() {
         }
         PROF("s2.fillRegion");
         const int nV = hdr[1], nW = hdr[2];
-        nReplayed += hdr[6] != 0;
-        r.nCandRecords += hdr[3];
         r.variants.clear();
         const uint8_t* blob = z.sb_added.h + g * (size_t)capA;
         // The device did the scan: these reference lines are cold on the host.  A variant's context (RefContext) is copied here, once, and the lines of
@@ -151,9 +149,44 @@ inline void Chunk::stageBFromDevice() {
             v->bamMinPos = z.sb_vbmin.h[k]; v->bamMaxPos = z.sb_vbmax.h[k];
             r.variants.push_back(v);
         }
+        // outputRefCalls: the blocks between calling windows are laid around ALL bunches of the region's variants, the device reports only the
+        // bunches whose window is within maxSize (plat_stageb.hip: emit()).  The host bunches the list again (variantBunches: the rule regionWindows
+        // runs), lays the blocks and deals the device's windows to the bunches that have one; a device window that is not the bunch's own sends the
+        // region through the host's stage B
+        struct Step { int window, a, b; };                               // window >= 0: the device's window; else the block [a, b)
+        std::vector<Step> steps;                                         // (outputRefCalls only: without it the steps are the device's windows, in order)
+        if (o.outputRefCalls) {
+            const WindowOptions wo{o.mergeClusteredVariants, o.maxVarDist, o.minVarDist, o.maxSize, o.largeWindows, r.rlen, o.maxVariants, o.outputRefCalls, o.refCallBlockSize};
+            const std::vector<VarList> bunches = variantBunches(r.in->start, r.in->end, r.variants, wo);
+            int q = 0, lastMax = 0;
+            bool same = true;
+            for (size_t index = 0; index < bunches.size() && same; ++index) {
+                const int lo = bunchMin(bunches[index]), hi = bunchMax(bunches[index]);
+                refCallGapBlocks(index == 0, lo, lastMax, r.in->start, wo, [&](int a, int b) { steps.push_back(Step{-1, a, b}); });
+                lastMax = hi;
+                const int ws = std::max(lo - o.minVarDist, r.in->start), we = (int)std::min<int64_t>(hi + o.minVarDist, r.fa.len - 1);
+                if (we - ws > o.maxSize) continue;                          // (no window: variantcaller.pyx:566-568)
+                const size_t k = g * (size_t)capW + (size_t)q;
+                same = q < nW && z.sb_wstart.h[k] == ws && z.sb_wend.h[k] == we && z.sb_wvn.h[k] == (int)bunches[index].size() &&
+                       (size_t)z.sb_wvfirst.h[k] < r.variants.size() && r.variants[(size_t)z.sb_wvfirst.h[k]] == bunches[index][0];
+                steps.push_back(Step{q++, 0, 0});
+            }
+            if (!same || q != nW) {
+                for (int w = 0; w < nW; ++w) { const size_t k = g * (size_t)capW + (size_t)w; if (z.sb_wbatch.h[k] >= 0) hapRun += z.sb_wnhaps.h[k]; }   // (its windows stay in the batch, uncalled)
+                const size_t at = g * (size_t)mergeCap * 8, n = (size_t)std::max(0, z.m_n.h[2 * g]) * 8;
+                if (n) { ck(plat_memcpy_d2h(z.ctx, z.m_cand.h + at, z.m_cand.d + at, n * sizeof(int32_t), z.stream), "plat_memcpy_d2h"); z.sync("candidates"); }
+                regionVariants(r, (int)g); regionWindows(r); ++nHostRegions; continue;
+            }
+        }
+        nReplayed += hdr[6] != 0;
+        r.nCandRecords += hdr[3];
         if (r.cur.size() != r.samples.size()) r.cur.assign(r.samples.size(), Ptrs{0, 0, 0, 0, 0, 0});
-        r.windows.reserve(r.windows.size() + (size_t)nW); r.items.reserve(r.items.size() + (size_t)nW);
-        for (int q = 0; q < nW; ++q) {
+        const size_t nSteps = o.outputRefCalls ? steps.size() : (size_t)nW;
+        r.windows.reserve(r.windows.size() + (size_t)nW); r.items.reserve(r.items.size() + nSteps);
+        for (size_t si = 0; si < nSteps; ++si) {
+            const Step step = o.outputRefCalls ? steps[si] : Step{(int)si, 0, 0};
+            if (step.window < 0) { r.items.push_back(Item{1, -1, std::string(), 0, step.a, step.b, -1, snapshotNR(r.cur)}); continue; }
+            const int q = step.window;
             PROF("s2.fill.window");
             const size_t k = g * (size_t)capW + (size_t)q;
             r.items.push_back(Item{0, (int)r.windows.size(), std::string(), 0});
@@ -190,7 +223,7 @@ inline void Chunk::stageBFromDevice() {
                         const uint32_t m = z.sb_hapmask.h[hap0 + h];
                         for (int i = 0; i < vn; ++i) if (m >> i & 1u) w.haps[(size_t)h].variants.push_back(w.vars[(size_t)i]);
                     }
-                    { PROF("s5.build"); prePosterior.add(r, w, false); }  // (the posterior kernel's inputs for this window, while it is in the caches)
+                    { PROF("s5.build"); prePosterior.add(r, w, o.outputRefCalls != 0); }  // (the posterior kernel's inputs for this window, while it is in the caches)
                 }
             }
         }

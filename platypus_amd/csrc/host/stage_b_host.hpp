@@ -209,13 +209,7 @@ inline void Chunk::regionWindows(RegionWork& r) {
     r.windows.reserve(r.windows.size() + wins.size()); r.items.reserve(r.items.size() + wins.size());
     for (Window& win : wins) {
         if (win.variants.empty()) {                                      // a reference-call block between calling windows (:605-607)
-            if (o.outputRefCalls) {
-                Item it{1, -1, std::string(), 0};
-                try {
-                    if (refCallLine(r, it.text, win.startPos, win.endPos, snapshotNR(r.cur), false, 0.0)) it.nRef = 1;
-                } catch (const WindowError& e) { logWindowFailure(r.in->chrom, win.startPos, win.endPos, e.what()); }
-                r.items.push_back(std::move(it));
-            }
+            if (o.outputRefCalls) r.items.push_back(Item{1, -1, std::string(), 0, win.startPos, win.endPos, -1, snapshotNR(r.cur)});
             continue;
         }
         if (win.endPos - win.startPos > o.maxSize) continue;             // variantcaller.pyx:566-568

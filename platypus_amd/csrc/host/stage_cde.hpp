@@ -233,7 +233,7 @@ inline void Chunk::callWindows(std::vector<WindowWork*>& wins, bool fromDevice) 
             } else if (o.outputRefCalls) {
                 double maxPost = 0.0;
                 for (size_t k = 0; k < w->vars.size(); ++k) { const double p = flatPost[(size_t)w->firstFlat + k]; maxPost = k ? std::max(maxPost, p) : p; }
-                if (refCallLine(r, w->text, w->startPos, w->endPos, snapshotNR(w->ptrs), !w->vars.empty(), maxPost)) { ++w->nRecords; ++w->nRefRecords; }
+                if (refCallLine(r, w->text, w->startPos, w->endPos, snapshotNR(w->ptrs), !w->vars.empty(), maxPost, minCoverage(r, w->covIv, w->startPos, w->endPos))) { ++w->nRecords; ++w->nRefRecords; }
                 else throw WindowError("cannot convert float infinity to integer");
             }
         } catch (const WindowError& e) {
@@ -267,7 +267,7 @@ inline void Chunk::refCallBlocksBetween(RegionWork& r, WindowWork& w) {
                     const int blockEnd = std::min(blockStart + o.refCallBlockSize, nextVarPos - 1);
                     if (blockStart == blockEnd) continue;
                     try {
-                        if (refCallLine(r, w.text, blockStart, blockEnd, snapshotNR(w.ptrs), false, 0.0)) { ++w.nRecords; ++w.nRefRecords; }
+                        if (refCallLine(r, w.text, blockStart, blockEnd, snapshotNR(w.ptrs), false, 0.0, minCoverage(r, w.covIv, blockStart, blockEnd))) { ++w.nRecords; ++w.nRefRecords; }
                     } catch (const WindowError& e) { logWindowFailure(r.in->chrom, blockStart, blockEnd, e.what()); }
                 }
         }

@@ -1,32 +1,123 @@
 // stage_f.hpp -- F: INFO / FILTER arithmetic and record text
 // (native region loop, libplat_caller.so: see region_caller.cpp for the stage map and the reference citations)
 #pragma once
+#include "../refcov_rule.hpp"
 #include "chunk.hpp"
 
 namespace plathost {
 
-// outputRefCall (variantcaller.pyx:764-867) for [windowStart, windowEnd): QUAL 0 without coverage somewhere in the block; else the
-// phred-scaled beta-binomial p-value of seeing no variant read at the block's smallest coverage, capped -- when the block holds
-// candidates -- by the best candidate's posterior under a flat prior (maxPost).  nReads: the samples' reads between the window
-// pointers as the loop last left them (the reference does not move them for a block).  Returns false when the reference raises here
-// (an infinite QUAL: logged and skipped by its try/except).
-inline bool Chunk::refCallLine(const RegionWork& r, std::string& out, int windowStart, int windowEnd, const std::vector<int>& nReads, bool hasVariants, double maxPost) const {
+// plat_refcall_coverage_batch is looked up weakly: a device library from before it (the CPU suite's stand-in) leaves the host's loop in charge
+#pragma weak plat_refcall_coverage_batch
+
+// The read counts every REFCALL decision of the chunk is built on, in ONE launch behind the chunk's stage B and greedy rounds: (a) the
+// blocks between calling windows (Item kind 1), their smallest count; (b) every window's span [min(startPos, lo), max(endPos, hi + 1)),
+// lo / hi the smallest minRefPos / largest maxRefPos of its candidates, position by position -- the whole-window line, the zero test of an
+// uncalled window and the blocks between called positions (known only after stage D) read minima of sub-ranges from it.  The values come
+// back with the chunk's next wait (coverageReady).  Nothing is launched without outputRefCalls, under PLAT_CALLER_HOST_REFCOV=1, on a
+// device library without the entry point, or when the arrays would pass the caps below: the host's loop (minCoverage) runs then.
+inline void Chunk::launchRefCoverage() {
+    covLaunched = false;
+    if (!o.outputRefCalls || o.sw.hostRefcov || !plat_refcall_coverage_batch) return;
+    constexpr int64_t CAP_POSITIONS = (int64_t)1 << 24, CAP_TILES = (int64_t)1 << 20;      // 64 MB of counts; a million workgroups
+    Slot& z = s;
+    std::vector<int32_t> ivStart, ivEnd, ivSlice, ivNs, tileFirst{0}, sBegin, sN, sLong;
+    std::vector<int64_t> ivOff;
+    covIv.clear();
+    int64_t total = 0, positions = 0, tiles = 0;
+    auto add = [&](int a, int b, int slice0, int ns, bool perPosition) {
+        ivStart.push_back(a); ivEnd.push_back(b); ivSlice.push_back(slice0); ivNs.push_back(ns);
+        ivOff.push_back(perPosition ? total : -1);
+        covIv.push_back(CovInterval{a, b, perPosition ? total : -1});
+        if (perPosition) total += (int64_t)b - a;
+        positions += (int64_t)b - a;
+        tiles += std::max<int64_t>(1, ((int64_t)b - a + PLAT_REFCOV_TILE - 1) / PLAT_REFCOV_TILE);
+        tileFirst.push_back((int32_t)std::min<int64_t>(tiles, INT32_MAX));
+        return (int)covIv.size() - 1;
+    };
+    for (RegionWork* r : regions) {
+        const int slice0 = (int)sBegin.size(), ns = (int)r->samples.size();
+        for (const SampleView& sv : r->samples) { sBegin.push_back((int32_t)sv.reads.base); sN.push_back(sv.reads.n()); sLong.push_back(sv.reads.longest); }
+        for (Item& it : r->items) if (it.kind == 1 && it.start < it.end) it.iv = add(it.start, it.end, slice0, ns, false);
+        for (WindowWork& w : r->windows) {
+            if (w.failed) continue;
+            int a = w.startPos, b = w.endPos;
+            for (const Variant* v : w.allVars) { a = std::min(a, v->minRefPos); b = std::max(b, v->maxRefPos + 1); }
+            if (a < b) w.covIv = add(a, b, slice0, ns, true);
+        }
+    }
+    if (covIv.empty() || total > CAP_POSITIONS || tiles > CAP_TILES) return;
+    const size_t nI = covIv.size();
+    Layout LI, LO;
+    LI.put(z.rc_sbegin, sBegin); LI.put(z.rc_sn, sN); LI.put(z.rc_slong, sLong); LI.put(z.rc_start, ivStart); LI.put(z.rc_end, ivEnd);
+    LI.put(z.rc_sfirst, ivSlice); LI.put(z.rc_ns, ivNs); LI.put(z.rc_off, ivOff); LI.put(z.rc_tfirst, tileFirst);
+    LI.commit(z, z.a_rcin);
+    LI.upload(z, z.a_rcin);
+    LO.add(z.rc_min, nI); LO.add(z.rc_counts, (size_t)total);
+    LO.commit(z, z.a_rcout);
+    plat_refcov_in in;
+    memset(&in, 0, sizeof in);
+    in.n_intervals = (int32_t)nI; in.n_slices = (int32_t)sBegin.size(); in.n_tiles = (int32_t)tiles; in.n_reads = (int32_t)(nGood + nBad + nBroken);
+    in.read_pos = z.t_pos.d; in.read_end = z.t_end.d; in.slice_begin = z.rc_sbegin.d; in.slice_n = z.rc_sn.d; in.slice_longest = z.rc_slong.d;
+    in.iv_start = z.rc_start.d; in.iv_end = z.rc_end.d; in.iv_slice_first = z.rc_sfirst.d; in.iv_n_samples = z.rc_ns.d; in.iv_count_off = z.rc_off.d;
+    in.iv_tile_first = z.rc_tfirst.d;
+    plat_refcov_out out;
+    memset(&out, 0, sizeof out);
+    out.cap_counts = total; out.iv_min = z.rc_min.d; out.counts = z.rc_counts.d;
+    const int rc = plat_refcall_coverage_batch(z.ctx, &in, &out, z.stream);
+    if (rc == PLAT_ERR_UNSUPPORTED) return;
+    ck(rc, "plat_refcall_coverage_batch");
+    LO.download(z, z.a_rcout);
+    covLaunched = true; covSyncMark = z.nSyncs;
+    std::lock_guard<std::mutex> g(stMutex);
+    st.n_refcall_intervals_device += (int64_t)nI; st.n_refcall_positions_device += positions;
+}
+
+// the launch's values are on the host: any wait of the chunk behind the launch brought them; a chunk that has not waited since (it calls
+// no window) waits here, once
+inline bool Chunk::coverageReady() {
+    if (!covLaunched) return false;
+    if (s.nSyncs == covSyncMark) s.sync("reference-call read counts");
+    return true;
+}
+
+// The smallest countReadsCoveringRegion(p, p + 1) (cwindow.pyx:176-206; refcov_rule.hpp) over the samples and the positions of [a, b), the
+// loop of outputRefCall (variantcaller.pyx:774-784): from interval `iv` of the device's values where it covers the range -- a block's own
+// interval, or a sub-range of a window's span -- else by the loop itself.  Raises where the reference does.  -1: nothing to count.
+inline long Chunk::minCoverage(const RegionWork& r, int iv, int a, int b) {
+    if (iv >= 0 && a < b && coverageReady()) {
+        const CovInterval& q = covIv[(size_t)iv];
+        long m = PLAT_REFCOV_EMPTY;
+        bool have = false;
+        if (q.off < 0) { if (a == q.start && b == q.end) { m = s.rc_min.h[iv]; have = true; } }
+        else if (a >= q.start && b <= q.end) {
+            const int32_t* c = s.rc_counts.h + q.off + ((int64_t)a - q.start);
+            for (int k = 0; k < b - a; ++k) m = std::min<long>(m, c[k]);
+            have = true;
+        }
+        if (have && m != PLAT_REFCOV_EMPTY) {
+            if (m < 0) throw WindowError("This should never happen. Read start pointer > read end pointer!!");
+            return m;
+        }
+    }
+    { std::lock_guard<std::mutex> g(stMutex); ++st.n_refcall_intervals_host; }
     long minCov = -1;
     for (const SampleView& sv : r.samples) {
         const TableView& tv = sv.reads;
-        const int N = tv.n();
-        for (int p = windowStart; p < windowEnd; ++p) {                  // countReadsCoveringRegion(p, p + 1), cwindow.pyx:176-206
-            long c = 0;
-            if (N > 0) {
-                int s0 = TableView::lowerBound(tv.t->pos, N, std::max<int64_t>(1, (int64_t)p - tv.longest));
-                const int e0 = TableView::lowerBound(tv.t->pos, N, (int64_t)p + 1);
-                while (s0 < N && tv.t->end[s0] <= p) ++s0;
-                if (s0 > e0) throw WindowError("This should never happen. Read start pointer > read end pointer!!");
-                c = std::min(e0, N) - s0;
-            }
+        for (int p = a; p < b; ++p) {
+            const long c = refcov::count_at(tv.t->pos, tv.t->end, tv.n(), tv.longest, p);
+            if (c < 0) throw WindowError("This should never happen. Read start pointer > read end pointer!!");
             minCov = minCov == -1 ? c : std::min(minCov, c);
         }
     }
+    return minCov;
+}
+
+// outputRefCall (variantcaller.pyx:764-867) for [windowStart, windowEnd) with the block's smallest read count `minCov` (minCoverage): QUAL 0
+// without coverage somewhere in the block; else the phred-scaled beta-binomial p-value of seeing no variant read at that count, capped
+// -- when the block holds candidates -- by the best candidate's posterior under a flat prior (maxPost).  nReads: the samples' reads
+// between the window pointers as the loop last left them (the reference does not move them for a block).  Returns false when the
+// reference raises here (an infinite QUAL: logged and skipped by its try/except).
+inline bool Chunk::refCallLine(const RegionWork& r, std::string& out, int windowStart, int windowEnd, const std::vector<int>& nReads, bool hasVariants, double maxPost, long minCov) const {
     const int phredPValue = (int)(-10 * log10(betaBinomialCDF(0, minCov, 20, 20)));
     int qual;
     if (minCov == 0) qual = 0;

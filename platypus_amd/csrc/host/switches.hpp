@@ -18,6 +18,7 @@
 //   KEEP_SPARE                   begins with '1'    a worker keeps its spare window storage for the next call             measurements (slower: region_caller.cpp)
 //   CHECK_HINTS                  begins with '1'    plat_read_table.longest_read / most_bases are checked against a walk  tests, a loader under suspicion
 //   HOST_SOURCE                  begins with '1'    source VCF lines are parsed by the host parser, not on the device      tests, measurements (the kernel's A/B)
+//   HOST_REFCOV                  begins with '1'    REFCALL read counts by the host's per-position loop, not on the device   tests, measurements (the kernel's A/B)
 //   TRACE                        set at all         per-chunk / per-call lines on stderr;                                 measurements
 //                                begins with '1'    ... and the per-stage seconds of every call (traceStages)
 // PLAT_CALLER_POLL_US is not here: it is a property of the caller object and is read where that is made (plat_caller_create).
@@ -29,7 +30,7 @@ namespace plathost {
 
 struct Switches {
     bool noCodes = false, expand = false, hostTally = false, hostB = false, noDeviceReplay = false, hostInfo = false, firstOccurrenceOrder = false;
-    bool evenTail = true, keepSpare = false, checkHints = false, noRefCtx = false, noRefPrefetch = false, hostSource = false;
+    bool evenTail = true, keepSpare = false, checkHints = false, noRefCtx = false, noRefPrefetch = false, hostSource = false, hostRefcov = false;
     bool trace = false, traceStages = false;                              // PLAT_CALLER_TRACE: set at all / begins with '1'
 
     static Switches read() {
@@ -49,6 +50,7 @@ struct Switches {
         w.keepSpare = isOne("PLAT_CALLER_KEEP_SPARE");
         w.checkHints = isOne("PLAT_CALLER_CHECK_HINTS");
         w.hostSource = isOne("PLAT_CALLER_HOST_SOURCE");
+        w.hostRefcov = isOne("PLAT_CALLER_HOST_REFCOV");
         w.trace = isSet("PLAT_CALLER_TRACE");
         w.traceStages = isOne("PLAT_CALLER_TRACE");
         return w;

@@ -508,7 +508,11 @@ struct Window { int startPos, endPos; VarList variants; };
 
 struct WindowOptions { int mergeClusteredVariants, maxVarDist, minVarDist, maxSize, largeWindows, rlen, maxVariants, outputRefCalls = 0, refCallBlockSize = 1000; };
 
-inline std::vector<Window> windowsAndVariants(int start, int end, int64_t maxContigPos, const VarList& sortedVariants, const WindowOptions& o) {
+// getBunchesOfVariants (window.py:118-170): the region's variants inside [start, end), grouped by position and the groups merged into bunches --
+// ALL of them, also the ones whose window comes out wider than maxSize (the loop skips those, the reference-call blocks are laid around them)
+inline int bunchMin(const VarList& g) { int m = g[0]->minRefPos; for (const Variant* v : g) m = std::min(m, v->minRefPos); return m; }
+inline int bunchMax(const VarList& g) { int m = g[0]->maxRefPos; for (const Variant* v : g) m = std::max(m, v->maxRefPos); return m; }
+inline std::vector<VarList> variantBunches(int start, int end, const VarList& sortedVariants, const WindowOptions& o) {
     // getVariantsByPos: groups of equal refPos, ascending
     std::vector<VarList> byPos;
     {
@@ -520,13 +524,11 @@ inline std::vector<Window> windowsAndVariants(int start, int end, int64_t maxCon
             byPos.back().push_back(pv.second);
         }
     }
-    auto minOf = [](const VarList& g) { int m = g[0]->minRefPos; for (const Variant* v : g) m = std::min(m, v->minRefPos); return m; };
-    auto maxOf = [](const VarList& g) { int m = g[0]->maxRefPos; for (const Variant* v : g) m = std::max(m, v->maxRefPos); return m; };
     std::vector<VarList> bunches;
     for (VarList& group : byPos) {
         if (bunches.empty()) { bunches.push_back(group); continue; }
-        const int lastMin = minOf(bunches.back()), lastMax = maxOf(bunches.back());
-        const int thisMin = minOf(group), thisMax = maxOf(group);
+        const int lastMin = bunchMin(bunches.back()), lastMax = bunchMax(bunches.back());
+        const int thisMin = bunchMin(group), thisMax = bunchMax(group);
         const int gap = thisMin - lastMax;
         bool merge;
         if (lastMax >= thisMin) merge = true;                                                // overlapping variants always share a window
@@ -537,27 +539,33 @@ inline std::vector<Window> windowsAndVariants(int start, int end, int64_t maxCon
         if (merge) bunches.back().insert(bunches.back().end(), group.begin(), group.end());
         else bunches.push_back(group);
     }
-    std::vector<Window> out;
-    // reference-call blocks in the gaps in front of and between the variant windows (window.py:172-219): windows without variants
-    auto refBlocks = [&](int first, int stop) {
+    return bunches;
+}
+
+// reference-call blocks in the gap in front of a bunch that starts at `lo` (window.py:172-219): from the region's start for the first bunch, from
+// behind the bunch before it (lastVarPos: its largest maxRefPos) otherwise; block(blockStart, blockEnd) per block
+template <class F> inline void refCallGapBlocks(bool first, int lo, int lastVarPos, int start, const WindowOptions& o, F&& block) {
+    auto refBlocks = [&](int from, int stop) {
         if (o.refCallBlockSize <= 0) throw WindowError("range() arg 3 must not be zero");
-        for (int blockStart = first; blockStart < stop; blockStart += o.refCallBlockSize) {
+        for (int blockStart = from; blockStart < stop; blockStart += o.refCallBlockSize) {
             const int blockEnd = std::min(blockStart + o.refCallBlockSize, stop - 1);
-            if (blockStart != blockEnd) out.push_back(Window{blockStart, blockEnd, VarList()});
+            if (blockStart != blockEnd) block(blockStart, blockEnd);
         }
     };
+    if (first) {
+        const int firstVarPos = std::max(lo + 1, start);
+        if (firstVarPos - start >= 1) refBlocks(start, firstVarPos);
+    } else if (lo + 1 - lastVarPos > 1) refBlocks(lastVarPos + 1, lo + 1);
+}
+
+inline std::vector<Window> windowsAndVariants(int start, int end, int64_t maxContigPos, const VarList& sortedVariants, const WindowOptions& o) {
+    std::vector<VarList> bunches = variantBunches(start, end, sortedVariants, o);
+    std::vector<Window> out;
     for (size_t index = 0; index < bunches.size(); ++index) {
         VarList& vs = bunches[index];
-        const int lo = minOf(vs), hi = maxOf(vs);
-        if (o.outputRefCalls) {
-            if (index == 0) {
-                const int firstVarPos = std::max(lo + 1, start);
-                if (firstVarPos - start >= 1) refBlocks(start, firstVarPos);
-            } else {
-                const int lastVarPos = maxOf(bunches[index - 1]);
-                if (lo + 1 - lastVarPos > 1) refBlocks(lastVarPos + 1, lo + 1);
-            }
-        }
+        const int lo = bunchMin(vs), hi = bunchMax(vs);
+        if (o.outputRefCalls)                                              // windows without variants
+            refCallGapBlocks(index == 0, lo, index ? bunchMax(bunches[index - 1]) : 0, start, o, [&](int a, int b) { out.push_back(Window{a, b, VarList()}); });
         Window w;
         w.startPos = std::max(lo - o.minVarDist, start);
         w.endPos = (int)std::min<int64_t>(hi + o.minVarDist, maxContigPos);

@@ -966,6 +966,48 @@ class Engine:
                                            "plat_source_variants_batch")
         return out
 
+    def refcall_coverage(self, read_pos, read_end, slices, intervals, tile_first=None):
+        """plat_refcall_coverage_batch: the loop of outputRefCall (variantcaller.pyx:774-784) over ReadArray.countReadsCoveringRegion
+        (cwindow.pyx:176-206) on the device.  read_pos / read_end: the read table; slices: [(begin, n, longest)], one sample's good reads each;
+        intervals: [(start, end, slice_first, n_samples, per_position)].  tile_first: the tile list to hand over instead of the one the
+        intervals' lengths give (tests).  Returns (iv_min [n_intervals], counts): counts[k] is None or the interval's per-position
+        minima over its samples (no entries for an interval without samples: nothing is written for it); PLAT_REFCOV_RAISES where the reference raises, PLAT_REFCOV_EMPTY for a minimum over nothing."""
+        torch = _torch()
+        nI, nS = len(intervals), len(slices)
+        if nI == 0:
+            return np.zeros(0, dtype=np.int32), []
+        pos, end = np.ascontiguousarray(read_pos, dtype=np.int32), np.ascontiguousarray(read_end, dtype=np.int32)
+        iv = np.asarray([[int(x) for x in t] for t in intervals], dtype=np.int64).reshape(nI, 5)
+        length = np.maximum(iv[:, 1] - iv[:, 0], 0)
+        off = np.full(nI, -1, dtype=np.int64)
+        total = 0
+        for k in range(nI):
+            if iv[k, 4]:
+                off[k] = total
+                total += int(length[k])
+        tiles = np.maximum(1, (length + _lib.PLAT_REFCOV_TILE - 1) // _lib.PLAT_REFCOV_TILE)
+        first = np.concatenate([[0], np.cumsum(tiles)]).astype(np.int32) if tile_first is None else np.asarray(tile_first, dtype=np.int32)
+        n_tiles = int(first[-1])
+
+        def dev(a, dt):
+            return torch.from_numpy(np.append(np.ascontiguousarray(a, dtype=dt), np.zeros(1, dtype=dt))).to(self.device)
+        sl = np.asarray(slices, dtype=np.int64).reshape(nS, 3)
+        d = dict(pos=dev(pos, np.int32), end=dev(end, np.int32), sb=dev(sl[:, 0], np.int32), sn=dev(sl[:, 1], np.int32), slong=dev(sl[:, 2], np.int32),
+                 s=dev(iv[:, 0], np.int32), e=dev(iv[:, 1], np.int32), sf=dev(iv[:, 2], np.int32), ns=dev(iv[:, 3], np.int32), off=dev(off, np.int64),
+                 first=dev(first, np.int32))
+        guard, fill = 16, 0x7EEE7EEE
+        o_min = torch.full((nI + guard,), fill, dtype=torch.int32, device=self.device)
+        o_cnt = torch.full((total + guard,), fill, dtype=torch.int32, device=self.device)
+        qi = _lib.RefCovIn(nI, nS, n_tiles, len(pos), d["pos"].data_ptr(), d["end"].data_ptr(), d["sb"].data_ptr(), d["sn"].data_ptr(), d["slong"].data_ptr(),
+                           d["s"].data_ptr(), d["e"].data_ptr(), d["sf"].data_ptr(), d["ns"].data_ptr(), d["off"].data_ptr(), d["first"].data_ptr())
+        qo = _lib.RefCovOut(total, o_min.data_ptr(), o_cnt.data_ptr())
+        _lib.check(self.lib.plat_refcall_coverage_batch(self.ctx, C.byref(qi), C.byref(qo), self._stream()), "plat_refcall_coverage_batch")
+        self._sync()
+        mins, cnt = o_min.cpu().numpy(), o_cnt.cpu().numpy()
+        if not ((mins[nI:] == fill).all() and (cnt[total:] == fill).all()):
+            raise RuntimeError("plat_refcall_coverage_batch wrote behind its outputs")
+        return mins[:nI].copy(), [cnt[off[k]:off[k] + (length[k] if iv[k, 3] > 0 else 0)].copy() if off[k] >= 0 else None for k in range(nI)]
+
     # ---- SURVEY 8(f) rank 3: read statistics of the VCF INFO field --------------------------------------------
     def variant_read_stats(self, windows, bad_reads_window=11, exact=0, packed=False, gaps=None):
         """vcfINFO's per-read loop for a list of windows.  A window: dict {variants: [dict(pos, removed, added, bam_min,

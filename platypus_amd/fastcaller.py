@@ -87,7 +87,8 @@ class CallerStats(C.Structure):
                 ("unpack_bytes", C.c_int64), ("candidates_bytes", C.c_int64), ("n_unpack_launches", C.c_int64), ("n_candidates_launches", C.c_int64),
                 ("kernel_ms", C.c_double * 32), ("kernel_launches", C.c_int64 * 32),
                 ("n_source_lines", C.c_int64), ("n_source_variants", C.c_int64), ("seconds_source", C.c_double),
-                ("n_source_chunks_device", C.c_int64), ("n_source_retries", C.c_int64)]
+                ("n_source_chunks_device", C.c_int64), ("n_source_retries", C.c_int64),
+                ("n_refcall_intervals_device", C.c_int64), ("n_refcall_positions_device", C.c_int64), ("n_refcall_intervals_host", C.c_int64)]
 
     STAGES = ("upload", "candidate_scan", "variants_windows_haplotypes", "greedy_rounds", "window_batch", "posteriors", "read_stats_calls", "text")
 
@@ -605,6 +606,7 @@ def build(verbose=False):
     srcs = [os.path.join(HOST_SRC, f) for f in sorted(os.listdir(HOST_SRC)) if f.endswith((".cpp", ".hpp"))]
     srcs.append(os.path.join(_lib.CSRC, "bgzf_inflate.hpp"))           # (the BGZF front end reads block headers with the device's own parser)
     srcs.append(os.path.join(_lib.CSRC, "source_rule.hpp"))            # (... and the host parser of source VCF lines is the device's rule)
+    srcs.append(os.path.join(_lib.CSRC, "refcov_rule.hpp"))            # (... as the host's loop over a REFCALL block's positions is)
     if os.path.exists(LIB_PATH) and os.path.getmtime(LIB_PATH) >= max([os.path.getmtime(f) for f in srcs] + [os.path.getmtime(_lib.LIB_PATH)]):
         return LIB_PATH
     # (-O3: the region loop is many small functions over small containers; +10 % windows/s over -O2 on the same box.  No -march: the library
