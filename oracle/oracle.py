@@ -267,15 +267,31 @@ class Oracle:
     # -- read QC / trimming ---------------------------------------------------------------------------
     def check_and_trim(self, reads, opt):
         """reads: one stream, dicts {qual (list/bytes), pos, mapq, flag, chromID, mateChromID, insertSize, matePos, cigar}.
-        Returns (ok, flags_out, quals_out(list of lists), reason)."""
+        Qualities are bytes 0..255 (lists, bytes or uint8 arrays; already signed values are taken as they are) and are read as the
+        reference reads them, as signed chars.  Returns (ok, flags_out, quals_out(list of lists of signed values), reason)."""
         n = len(reads)
+        as_u8 = lambda q: np.frombuffer(q, dtype=np.uint8) if isinstance(q, (bytes, bytearray)) else (np.asarray(q, dtype=np.int64) & 255).astype(np.uint8)
         off = np.concatenate([[0], np.cumsum([len(r["qual"]) for r in reads])]).astype(np.int64)
-        qual = np.concatenate([np.asarray(r["qual"], dtype=np.int8) for r in reads] + [np.zeros(1, dtype=np.int8)])
+        qual = np.concatenate([as_u8(r["qual"]) for r in reads] + [np.zeros(1, dtype=np.uint8)])
         arr = lambda k, dt: np.array([r[k] for r in reads], dtype=dt)
-        pos, mapq, flags = arr("pos", np.int32), arr("mapq", np.uint8), arr("flag", np.int32)
-        cid, mcid, ins, mpos = arr("chromID", np.int16), arr("mateChromID", np.int16), arr("insertSize", np.int32), arr("matePos", np.int32)
         cig = np.array([x for r in reads for c in r["cigar"] for x in c] + [0, 0], dtype=np.int16)
         coff = np.concatenate([[0], np.cumsum([len(r["cigar"]) for r in reads])]).astype(np.int32)
+        ok, flags, qual, reason = self.check_and_trim_arrays(qual, off, arr("pos", np.int32), arr("mapq", np.uint8), arr("flag", np.int32),
+                                                             arr("chromID", np.int16), arr("mateChromID", np.int16), arr("insertSize", np.int32),
+                                                             arr("matePos", np.int32), cig, coff, opt)
+        qual = qual.view(np.int8)
+        return ok, flags, [qual[off[i]:off[i + 1]].tolist() for i in range(n)], reason
+
+    def check_and_trim_arrays(self, qual, off, pos, mapq, flags, chrom_id, mate_chrom_id, insert_size, mate_pos, cigar, cig_off, opt):
+        """check_and_trim on one stream held as arrays: qual uint8 [off[n]] (read as signed chars), off int64 [n + 1] from 0, cigar int16
+        (op, length) pairs flat, cig_off int32 [n + 1] from 0.  Nothing passed in is changed.  Returns (ok, flags_out, qual_out uint8, reason)."""
+        n = len(off) - 1
+        c = lambda a, dt: np.array(a, dtype=dt)                                        # copies: the C side trims and flags in place
+        qual = np.concatenate([c(qual, np.uint8)[:int(off[-1])], np.zeros(1, dtype=np.uint8)])
+        off, pos, mapq, flags = c(off, np.int64), c(pos, np.int32), c(mapq, np.uint8), c(flags, np.int32)
+        cid, mcid, ins, mpos = c(chrom_id, np.int16), c(mate_chrom_id, np.int16), c(insert_size, np.int32), c(mate_pos, np.int32)
+        cig = np.concatenate([c(cigar, np.int16).reshape(-1)[:2 * int(cig_off[-1])], np.zeros(2, dtype=np.int16)])
+        coff = c(cig_off, np.int32)
         en = np.array(opt["enabled"], dtype=np.int32)
         ok = np.zeros(n, dtype=np.int32); reason = np.zeros(n, dtype=np.int32)
         self.lib.orc_check_and_trim(n, qual.ctypes.data, off.ctypes.data, pos.ctypes.data, mapq.ctypes.data, flags.ctypes.data,
@@ -283,7 +299,7 @@ class Oracle:
                                     coff.ctypes.data, opt["minGoodQualBases"], opt["minMapQual"], opt["minBaseQual"],
                                     opt["trimOverlapping"], opt["trimAdapter"], opt["trimReadFlank"], opt["trimSoftClipped"],
                                     en.ctypes.data, ok.ctypes.data, reason.ctypes.data)
-        return ok, flags, [qual[off[i]:off[i + 1]].tolist() for i in range(n)], reason
+        return ok, flags, qual[:-1], reason
 
     # -- read statistics of the VCF INFO field --------------------------------------------------------
     def variant_read_stats(self, variants, samples, var_in_genotype, min_base_qual=20, bad_reads_window=11, exact=0):

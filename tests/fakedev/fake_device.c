@@ -5,7 +5,8 @@
  * test suite, where no GPU is present.  It is built by tests/conftest.py into tests/fakedev/, is never shipped with the
  * package and is never loaded by it: the product binds libplat_mi355x.so (HIP) and fails loudly without a GPU.
  *
- * Only the entry points those host layers use are functional; the rest return PLAT_ERR_UNSUPPORTED.
+ * Only the entry points those host layers use are functional, and plat_read_qc_batch (a statement of checkAndTrimRead of its own, which
+ * tests/test_read_qc_cases_cpu.py holds the oracle against); the rest return PLAT_ERR_UNSUPPORTED.
  */
 #include <math.h>
 #include <stdint.h>
@@ -93,8 +94,71 @@ API int plat_kernel_times(plat_ctx* c, double* ms, int64_t* n) { (void)c; (void)
 API int plat_dp_batch(plat_ctx* c, int n, int lmax, const uint8_t* a, const uint8_t* b, const uint8_t* q, const uint8_t* g,
                       const int32_t* l, int ge, int np_, int32_t* o, void* st)
 { (void)c; (void)n; (void)lmax; (void)a; (void)b; (void)q; (void)g; (void)l; (void)ge; (void)np_; (void)o; (void)st; return PLAT_ERR_UNSUPPORTED; }
+/* ---- checkAndTrimRead (cwindow.pyx:332-481) with addReadToBuffer's theLastRead (:560-595) ------------------------------------------
+ * Written apart from the oracle's and the device's loops, so that tests/test_read_qc_cases_cpu.py has a third statement of the rule to hold
+ * the oracle against: the verdict is a chain of tests in the reference's order, and every trimming rule is turned into ONE interval [lo, hi)
+ * of the read that is zeroed afterwards (the adapter rule's two branches zero the same interval; the soft clips one interval per clip). */
+static void qc_zero(signed char* q, int rlen, long lo, long hi)
+{
+    if (lo < 0) lo = 0;
+    if (hi > rlen) hi = rlen;                                    /* (a CIGAR that claims more than the read holds: as the device, to its end) */
+    for (long i = lo; i < hi; ++i) q[i] = 0;
+}
+
+static int qc_reason(const plat_readqc_batch* b, const plat_readqc_options* o, int r, const signed char* q, int rlen, int* set_qcfail)
+{
+    const int f = b->read_flags[r], paired = (f & 1) != 0, ins = b->insert_size[r];
+    *set_qcfail = 1;
+    if (f & 256) return 7;
+    if ((int)b->read_mapq[r] < o->min_map_qual) return 6;
+    int good = 0;
+    for (int i = 0; i < rlen; ++i) good += q[i] >= o->min_base_qual;
+    if (good < o->min_good_qual_bases) return 0;
+    if (f & 4) return 1;
+    if (o->filter_mate_unmapped && paired && (f & 8)) { *set_qcfail = 0; return 2; }
+    if (o->filter_mate_distant && paired && !(b->chrom_id[r] == b->mate_chrom_id[r] && (f & 2))) { *set_qcfail = 0; return 3; }
+    if (o->filter_small_insert && paired && ins != 0 && labs((long)ins) < rlen) return 4;
+    if (!o->filter_duplicates) return -1;
+    if (f & 1024) return 5;
+    if (r == 0 || b->stream_of[r - 1] != b->stream_of[r]) return -1;         /* the first read of a stream has no theLastRead */
+    const int last_len = (int)(b->read_off[r] - b->read_off[r - 1]);
+    if (b->read_pos[r - 1] != b->read_pos[r] || last_len != rlen) return -1;
+    return (!paired || b->mate_pos[r - 1] == b->mate_pos[r]) ? 5 : -1;
+}
+
 API int plat_read_qc_batch(plat_ctx* c, const plat_readqc_batch* b, const plat_readqc_options* o, int32_t* ok, int32_t* why, void* st)
-{ (void)c; (void)b; (void)o; (void)ok; (void)why; (void)st; return PLAT_ERR_UNSUPPORTED; }
+{
+    (void)st;
+    if (!c || !b || !o || b->n_reads < 0) return PLAT_ERR_INVALID;
+    for (int r = 0; r < b->n_reads; ++r) {
+        signed char* q = (signed char*)b->read_qual + b->read_off[r];
+        const int rlen = (int)(b->read_off[r + 1] - b->read_off[r]);
+        int qcfail;
+        why[r] = qc_reason(b, o, r, q, rlen, &qcfail);
+        ok[r] = why[r] < 0;
+        if (!ok[r]) { if (qcfail) b->read_flags[r] |= 512; continue; }
+        const int f = b->read_flags[r], paired = (f & 1) != 0, reverse = (f & 16) != 0;
+        const long ins = b->insert_size[r], absIns = labs(ins);
+        /* the low-quality end: the outermost trim_read_flank - 1 (forward) or trim_read_flank (reverse) bases, then on while below 5 */
+        int k = 0;
+        if (!reverse) { while (k < rlen && (k + 1 < o->trim_read_flank || q[rlen - 1 - k] < 5)) ++k; qc_zero(q, rlen, rlen - k, rlen); }
+        else { while (k < rlen && (k < o->trim_read_flank || q[k] < 5)) ++k; qc_zero(q, rlen, 0, k); }
+        if (o->trim_overlapping == 1 && paired && absIns > 0 && !reverse && (f & 32) && absIns < 2l * rlen) {
+            const long nOver = 2l * rlen - ins + 1;
+            qc_zero(q, rlen, nOver >= rlen ? 0 : rlen - nOver, rlen);
+        }
+        if (o->trim_adapter == 1 && paired && absIns > 0 && absIns < rlen) qc_zero(q, rlen, absIns, rlen);
+        if (o->trim_soft_clipped == 1) {
+            long at = 0;                                         /* only M and I move the cursor on, besides the clips themselves */
+            for (int p = b->cig_off[r]; p < b->cig_off[r + 1]; ++p) {
+                const int op = b->cigar[2 * p], len = b->cigar[2 * p + 1];
+                if (op == 4) qc_zero(q, rlen, at, at + len);
+                if (op == 0 || op == 1 || op == 4) at += len;
+            }
+        }
+    }
+    return PLAT_OK;
+}
 
 /* ---- Haplotype.alignReads for whole windows --------------------------------------------------------------------------- */
 static int align_impl(const plat_window_batch* b, int calc_flank, double* out_ll, int32_t* out_score, plat_align_stats* st)

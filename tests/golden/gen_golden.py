@@ -514,7 +514,7 @@ def check_and_trim(list reads, int minGoodQualBases, int minMapQual, int minBase
         r = make_read(t["seq"], bytes(qual), t["pos"], t["pos"] + len(t["seq"]), t["mapq"], t["flag"])
         r.qual = <char*>malloc(len(t["seq"]) + 1)
         for k in range(len(t["seq"])):
-            r.qual[k] = t["qual"][k]
+            r.qual[k] = t["qual"][k] - 256 if t["qual"][k] > 127 else t["qual"][k]      # bytes 128..255 as the reference's char* holds them
         r.chromID, r.mateChromID, r.insertSize, r.matePos = t["chromID"], t["mateChromID"], t["insertSize"], t["matePos"]
         r.cigarLen = len(t["cigar"])
         r.cigarOps = <short*>calloc(2 * len(t["cigar"]) + 2, sizeof(short))
@@ -2315,6 +2315,42 @@ def gen_readqc(out):
     print("readqc: %d streams, %d reads, %d rejected" % (len(cases), sum(len(c["reads"]) for c in cases), sum(len(c["ok"]) - sum(c["ok"]) for c in cases)))
 
 
+def gen_readqc_wide(out):
+    """checkAndTrimRead off the shapes of gen_readqc, through the same driver: a dozen streams built by tests/read_qc_cases.py (reads of
+    1..1000 bases, quality bytes up to 255, options off the goldens' values, CIGARs of up to 79 pairs with every operation in front of a soft
+    clip, insert sizes at the edges of the rules).  Qualities are stored as bytes 0..255, in and out."""
+    import hap_drv
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import read_qc_cases as C
+    rng = np.random.default_rng(97)
+    forced = [dict(minBaseQual=64), dict(minBaseQual=63, trimReadFlank=40), dict(minMapQual=255), dict(minGoodQualBases=200, trimReadFlank=2000),
+              dict(minMapQual=0, minBaseQual=0, minGoodQualBases=0), dict(trimOverlapping=2, trimAdapter=2, trimSoftClipped=2)]
+    cases = []
+    for ci in range(12):
+        opt = C.fuzz_options(rng)
+        opt["enabled"] = [int(rng.random() < 0.7) for _ in range(4)]
+        opt.update(forced[ci] if ci < len(forced) else {})
+        stream = [r for r in C.fuzz_stream(rng, 75, 1000, opt) if len(r["seq"]) > 0]
+        reads = [dict(seq="A" * len(r["seq"]), qual=list(r["qual"]), pos=r["pos"], mapq=r["mapq"], flag=r["flag"], chromID=r["chromID"],
+                      mateChromID=r["mateChromID"], insertSize=r["insertSize"], matePos=r["matePos"], cigar=r["cigar"]) for r in stream]
+        assert all(C.consumed(r["cigar"]) <= len(r["seq"]) for r in reads)              # past that checkAndTrimRead writes behind the read
+        tup = [dict(r, seq=r["seq"].encode(), cigar=[tuple(c) for c in r["cigar"]]) for r in reads]
+        res, counts = hap_drv.check_and_trim(tup, opt["minGoodQualBases"], opt["minMapQual"], opt["minBaseQual"], opt["minFlank"],
+                                             opt["trimOverlapping"], opt["trimAdapter"], opt["trimReadFlank"], opt["trimSoftClipped"], opt["enabled"])
+        qout = [[x & 255 for x in t[2]] for t in res]
+        cases.append(dict(options=opt, reads=reads, ok=[int(x[0]) for x in res], flag_out=[x[1] for x in res],
+                          qual_out=[(None if q == r["qual"] else q) for q, r in zip(qout, reads)], counts=counts))       # None: unchanged
+    reads = [r for c in cases for r in c["reads"]]
+    assert {1, 641, 1000} <= {len(r["seq"]) for r in reads} and {33, 79} <= {len(r["cigar"]) for r in reads}
+    assert sum(1 for c in cases for r, k in zip(c["reads"], c["ok"]) if k and max(r["qual"]) >= 128) >= 50
+    for before in (2, 3, 6, 7, 8):
+        assert any(a[0] == before and b[0] == 4 for r in reads for a, b in zip(r["cigar"], r["cigar"][1:])), before
+    with gzip.open(os.path.join(out, "readqc_wide_cases.json.gz"), "wt") as f:
+        json.dump(cases, f, separators=(",", ":"))
+    print("readqc wide: %d streams, %d reads, %d rejected, %d trimmed" % (len(cases), len(reads), sum(len(c["ok"]) - sum(c["ok"]) for c in cases),
+                                                                        sum(q is not None for c in cases for q in c["qual_out"])))
+
+
 def gen_infostats(out):
     """Read statistics of the VCF INFO field: the reference's readOverlapsVariant / readQualIsGoodVariantPosition /
     variantSupportedByRead (vcfutils.pyx:901-943,961-1072) driven by a loop that mirrors vcfINFO (:1300-1390)."""
@@ -3233,7 +3269,7 @@ def main():
         sys.exit("reference tree not found at %s: golden vectors can only be regenerated in the build container" % REF)
     subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle")])
     build_scratch(a.scratch)
-    todo = a.only.split(",") if a.only else ["dp", "dpfuzz", "tandem", "mapalign", "assembler", "population", "haplotype", "filter", "hapseq", "candidates", "readqc", "infostats", "pvalues", "vcf", "regionprep", "indelprior", "refcall", "region"]
+    todo = a.only.split(",") if a.only else ["dp", "dpfuzz", "tandem", "mapalign", "assembler", "population", "haplotype", "filter", "hapseq", "candidates", "readqc", "readqcwide", "infostats", "pvalues", "vcf", "regionprep", "indelprior", "refcall", "region"]
     if "dp" in todo:
         gen_dp(HERE)
     if "dpfuzz" in todo:
@@ -3256,6 +3292,8 @@ def main():
         gen_candidates(HERE)
     if "readqc" in todo:
         gen_readqc(HERE)
+    if "readqcwide" in todo:
+        gen_readqc_wide(HERE)
     if "infostats" in todo:
         gen_infostats(HERE)
     if "pvalues" in todo:

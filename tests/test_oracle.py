@@ -275,6 +275,27 @@ def test_check_and_trim_matches_reference_golden(oracle, golden_dir):
     assert trimmed > 500
 
 
+def test_check_and_trim_matches_reference_golden_off_the_first_fixtures_shapes(oracle, golden_dir):
+    """The same on readqc_wide_cases.json.gz (gen_readqc_wide): reads of 1..1000 bases, quality bytes up to 255 (stored as bytes; the
+    reference and the oracle read them as signed chars), options off the first fixture's values, CIGARs of up to 79 pairs."""
+    cases = json.load(gzip.open(os.path.join(golden_dir, "readqc_wide_cases.json.gz"), "rt"))
+    trimmed = high = 0
+    for c in cases:
+        ok, flags, quals, reason = oracle.check_and_trim(c["reads"], c["options"])
+        assert ok.tolist() == c["ok"] and flags.tolist() == c["flag_out"]
+        for r, q, exp, k in zip(c["reads"], quals, c["qual_out"], c["ok"]):
+            assert [x & 255 for x in q] == (r["qual"] if exp is None else exp)
+            trimmed += exp is not None
+            high += bool(k) and max(r["qual"]) >= 128
+        counts = [int((reason == k).sum()) for k in range(7)]
+        for k in range(7):
+            if c["counts"][k] != -1:
+                assert counts[k] == c["counts"][k]
+    reads = [r for c in cases for r in c["reads"]]
+    assert trimmed > 300 and high >= 50 and {33, 79} <= {len(r["cigar"]) for r in reads} and {1, 1000} <= {len(r["seq"]) for r in reads}
+    assert {c["options"]["minBaseQual"] for c in cases} >= {0, 63, 64} and {c["options"]["minMapQual"] for c in cases} >= {0, 255}
+
+
 # ---- read statistics of the VCF INFO field, pinned by the reference's own leaf functions ------------------------------------
 def infostats_inputs(c):
     variants = [dict(pos=v["pos"], removed=v["removed"].encode(), added=v["added"].encode(), bam_min=v["pos"], bam_max=v["pos"]) for v in c["variants"]]
