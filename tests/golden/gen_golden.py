@@ -2886,6 +2886,107 @@ def gen_regionprep(out):
         sum(len(c["variants"]) for c in norm), len(filt), len(cov), len(arrays), len(wins), sum(len(w["windows"]) for w in wins)))
 
 
+def gen_regionprep_wide(out):
+    """The chain between the candidates and the haplotypes off the shapes of gen_regionprep, on regions built by tests/stage_b_cases.py
+    (indels that move, meet and merge inside planted repeats, overlapping and abutting variants, variant sets that spell one sequence):
+    sorted() by the reference's Variant.__richcmp__, leftNormaliseIndel, sorted(), filterVariants (hap_drv), WindowGenerator (the class text
+    of window.py), isHaplotypeValid over itertools.combinations and the constructor head / getMutatedSequence of Haplotype (hap_drv's
+    HaplotypeSeq) for the windows of up to five variants, eight windows a region.  The contig outside a region's reference window is N."""
+    import types
+    from itertools import combinations
+    import hap_drv
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import stage_b_cases as C
+    swallowed = []
+    sys.unraisablehook = lambda u: swallowed.append(repr(u.exc_value))
+    wpy = open(os.path.join(REF, "src/python/window.py")).read().split("\n")
+    assert wpy[17].startswith("class WindowGenerator(object):") and wpy[237].strip() == "yield thisWindow"
+    ns = dict(xrange=range, logger=logging_stub())
+    exec(compile("from __future__ import division\n" + "\n".join(wpy[17:238]) + "\n", "window_py_slice", "exec"), ns)
+    calls = C.corpus()
+    picked = []
+    for k, c in enumerate(calls[:12]):
+        big = [j for j, g in enumerate(c["regions"]) if len(g["cands"]) >= 12 and g["rlen"] <= 250 and g["merge_status"] == 0 and g["n_cands"] is None]
+        picked += [(k, j) for j in big[:3]]
+    picked += [(0, j) for j in range(15, 43, 3)] + [(1, j) for j in range(15, 31)] + [(2, j) for j in range(15, 22)]
+    picked = sorted(set(picked))
+    cases, tally = [], dict(moved=0, merged=0, windows=0, haplotypes=0, invalid=0, raised=0)
+    for k, j in picked:
+        g, o = calls[k]["regions"][j], calls[k]["o"]
+        rss, L = g["ref_seq_start"], g["rlen"]
+        contig = b"N" * rss + g["ref"] + b"N" * (g["contig_len"] - rss - len(g["ref"]))
+        rf = hap_drv.FastaFile(None, {b"20": contig})
+        case = dict(call=k, region=j, ref=g["ref"].decode(), ref_seq_start=rss, contig_len=g["contig_len"], start=g["start"], end=g["end"], rlen=L,
+                    cands=[[x[0], x[1], x[2].decode(), x[3]] for x in g["cands"]], options={x: o[x] for x in sorted(o)})
+        vs = []
+        for pos, nrem, added, supp in g["cands"]:
+            at = (pos + 1 if (nrem and not added) else pos)
+            vs.append(hap_drv.Variant(b"20", pos, contig[at:at + nrem], added, supp, 1, -1))
+        norm, raised = [], None
+        for v in sorted(vs):
+            try:
+                t = hap_drv.left_normalise(v, rf, L)
+            except Exception as e:
+                raised = str(e).split("\n")[0][:80]
+                break
+            if t[7]:
+                norm.append(v)
+            else:
+                nv = hap_drv.Variant(b"20", t[0], t[1], t[2], t[5], t[6], -1)
+                nv.bamMinPos, nv.bamMaxPos = t[3], t[4]
+                tally["moved"] += t[0] != v.refPos
+                norm.append(nv)
+        case["raised"] = raised
+        if raised is not None:
+            tally["raised"] += 1
+            cases.append(case)
+            continue
+        norm.sort()
+        for i, v in enumerate(norm):
+            v.idx = i
+        case["normalised"] = [[v.refPos, v.removed.decode(), v.added.decode(), v.nSupportingReads, v.bamMinPos, v.bamMaxPos] for v in norm]
+        opts = types.SimpleNamespace(minReads=o["minReads"], maxSize=o["maxSize"], maxVariants=o["maxVariants"], verbosity=0, rlen=L,
+                                     mergeClusteredVariants=o["mergeClusteredVariants"], largeWindows=o["largeWindows"], maxVarDist=o["maxVarDist"],
+                                     minVarDist=o["minVarDist"], outputRefCalls=0, refCallBlockSize=1000)
+        res = hap_drv.filter_variants(list(norm), L, o["minReads"], o["maxSize"], opts)
+        kept = [norm[t[0]] for t in res]
+        tally["merged"] += sum(t[1] > sum(x[3] for x in case["normalised"][t[0]:t[0] + 1]) for t in res)
+        case["filtered"] = [[norm[t[0]].refPos, norm[t[0]].removed.decode(), norm[t[0]].added.decode(), t[1], t[3], t[4]] for t in res]
+        back = {id(v): i for i, v in enumerate(kept)}
+        wins = list(ns["WindowGenerator"]().WindowsAndVariants(b"20", g["start"], g["end"], g["contig_len"] - 1, kept, opts))
+        case["windows"] = [[w["startPos"], w["endPos"], [back[id(v)] for v in w["variants"]]] for w in wins]
+        haps = []
+        for wi, w in enumerate(wins):
+            wv = w["variants"]
+            if not 1 <= len(wv) <= 5 or len(haps) >= 8 or w["endPos"] - w["startPos"] > o["maxSize"]:
+                continue
+            rows = []
+            try:
+                for n in range(0, len(wv) + 1):
+                    for idx in combinations(range(len(wv)), n):
+                        combo = tuple(wv[i] for i in idx)
+                        if not hap_drv.haplotype_valid(combo):
+                            tally["invalid"] += 1
+                            continue
+                        h = hap_drv.HaplotypeSeq(b"20", w["startPos"], w["endPos"], combo, rf, L, hap_drv.Options(0))
+                        rows.append([sum(1 << i for i in idx), h.haplotypeSequence.decode()])
+            except Exception as e:
+                rows = str(e).split("\n")[0][:80]
+            if isinstance(rows, list) and sum(len(r[1]) for r in rows) > 12000:
+                continue                                                         # (kept small: the long ones are compared through their shorter kin)
+            haps.append([wi, rows])
+            tally["haplotypes"] += len(rows) if isinstance(rows, list) else 0
+        tally["windows"] += len(wins)
+        case["haplotypes"] = haps
+        cases.append(case)
+    assert not swallowed, swallowed[:3]
+    assert tally["moved"] >= 100 and tally["merged"] >= 30 and tally["invalid"] >= 20 and tally["haplotypes"] >= 500, tally
+    with open(os.path.join(out, "regionprep_wide_cases.json.gz"), "wb") as f:
+        with gzip.GzipFile(filename="", mode="wb", fileobj=f, mtime=0) as z:         # (no time stamp: the recipe gives the same bytes again)
+            z.write(json.dumps(cases, separators=(",", ":"), sort_keys=True).encode())
+    print("regionprep wide: %d regions, %s" % (len(cases), tally))
+
+
 def logging_stub():
     import logging
     return logging.getLogger("Log")
@@ -3269,7 +3370,7 @@ def main():
         sys.exit("reference tree not found at %s: golden vectors can only be regenerated in the build container" % REF)
     subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle")])
     build_scratch(a.scratch)
-    todo = a.only.split(",") if a.only else ["dp", "dpfuzz", "tandem", "mapalign", "assembler", "population", "haplotype", "filter", "hapseq", "candidates", "readqc", "readqcwide", "infostats", "pvalues", "vcf", "regionprep", "indelprior", "refcall", "region"]
+    todo = a.only.split(",") if a.only else ["dp", "dpfuzz", "tandem", "mapalign", "assembler", "population", "haplotype", "filter", "hapseq", "candidates", "readqc", "readqcwide", "infostats", "pvalues", "vcf", "regionprep", "regionprepwide", "indelprior", "refcall", "region"]
     if "dp" in todo:
         gen_dp(HERE)
     if "dpfuzz" in todo:
@@ -3302,6 +3403,8 @@ def main():
         gen_vcf(HERE)
     if "regionprep" in todo:
         gen_regionprep(HERE)
+    if "regionprepwide" in todo:
+        gen_regionprep_wide(HERE)
     if "indelprior" in todo:
         gen_indelprior(HERE)
     if "refcall" in todo:

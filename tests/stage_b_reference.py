@@ -33,6 +33,8 @@ from platypus_amd.vcfrecords import py2_dict_slot_order, py2_variant_hash
 PLAT_SB_HOST = 1
 SBW_SKIP, SBW_HOST, SBW_DUPLICATE = 1, 2, 4
 SB_CAP, SB_MAXCOMB, SB_STAGE, HASH_SIZE = 1024, 5, 384, 16384
+SB_DICT_CAP = 5400                                                           # distinct records of a scan whose dictionary the device replays
+SB_KEY_RUN = 48                                                              # candidates of one sort key the device looks through (more: reason 2)
 ERR_OVERFLOW, ERR_BAD_INPUT = -8, -9
 
 OPTIONS = dict(minReads=2, maxSize=1500, mergeClusteredVariants=1, maxVarDist=15, minVarDist=9, largeWindows=0, maxVariants=8, maxHaplotypes=50,
@@ -236,6 +238,39 @@ def _window(reg, fasta, opts, o, kept, w, buf):
     return out
 
 
+def _key_runs(norm):
+    """The runs of candidates that compare equal under Variant.__richcmp__'s order, (refPos, type, nRemoved), in a sorted list."""
+    runs, i = [], 0
+    while i < len(norm):
+        e = i + 1
+        while e < len(norm) and not (norm[i] < norm[e]):
+            e += 1
+        runs.append(norm[i:e])
+        i = e
+    return runs
+
+
+def _key_run_over(norm, limit):
+    """The header's rule of reason 2: "more than 48 candidates with one key count as such" -- the device does not look inside so long a
+    run, whatever it holds (caller.order_can_matter, the host's rule, does and lets a run of one variant 49 times pass)."""
+    return any(len(r) > limit for r in _key_runs(norm))
+
+
+def _chain_counts(norm):
+    """What the chain did to a region, for the reach conditions of the seeded inputs (not compared with the device): indels whose position
+    normalisation changed, runs of equal variants merged, and how many of those hold a moved and an unmoved candidate."""
+    moved = lambda v: getattr(v, "given_pos", v.refPos) != v.refPos
+    merged = mixed = 0
+    for run in _key_runs(norm):
+        left = list(run)
+        while left:
+            same = [v for v in left if v == left[0]]
+            left = [v for v in left if not (v == same[0])]
+            merged += len(same) >= 2
+            mixed += len(same) >= 2 and any(moved(v) for v in same) and not all(moved(v) for v in same)
+    return dict(moved=sum(moved(v) for v in norm), merged=merged, mixed=mixed, longest_key_run=max([len(r) for r in _key_runs(norm)], default=0))
+
+
 def expected_region(reg, o, cp, cap_per_scan, exact_records=None):
     """hdr and content of one region.  exact_records: every distinct record of the scan, in first-record order, as (pos, removed, added,
     index into reg['cands'] or None) -- given when the scan's records are handed to the device (cand_rec): the dictionaries are replayed."""
@@ -268,9 +303,11 @@ def expected_region(reg, o, cp, cap_per_scan, exact_records=None):
             if nv is not v:
                 nv.rem_pos = nv.refPos + 1 if nv.nRemoved else nv.refPos
                 nv.moved = True
+                nv.given_pos = v.refPos
                 used += nv.nAdded                                               # its new bases go into the region's blob right away
             norm.append(nv)
         norm.sort()
+        out["normalised"] = [(v.refPos, v.removed, v.added, v.bamMinPos, v.bamMaxPos) for v in norm]  # (before filterVariants adds up the equal ones)
         kept = filterVariants(list(norm), fasta, reg["rlen"], o["minReads"], o["maxSize"], 0, opts)
         return norm, kept, fail, used
     if edge:
@@ -280,9 +317,9 @@ def expected_region(reg, o, cp, cap_per_scan, exact_records=None):
     # capacities first (reason 6 wins over an exception's 1), then the dictionaries
     if fail or used > cp["cap_added"] or len(kept) > cp["cap_vars"]:
         return host(6 if (used > cp["cap_added"] or len(kept) > cp["cap_vars"]) else 1)
-    if caller.order_can_matter(norm, kept):
-        if exact_records is None:
-            return host(2)                                                      # an order that depends on a dictionary, and no records to replay it with
+    if caller.order_can_matter(norm, kept) or _key_run_over(norm, SB_KEY_RUN):
+        if exact_records is None or len(exact_records) > SB_DICT_CAP:
+            return host(2)                                                      # an order that depends on a dictionary, and no records to replay it with (or too many)
         hs = [py2_variant_hash(reg["name"], max(p, 0), r, a) for p, r, a, _ in exact_records]
         first = [k for k in py2_dict_slot_order(hs) if exact_records[k][3] is not None]     # the sample's dictionary walked: who passes enters the second
         second = [first[k] for k in py2_dict_slot_order([hs[x] for x in first])]
@@ -294,6 +331,7 @@ def expected_region(reg, o, cp, cap_per_scan, exact_records=None):
     if used > cp["cap_added"]:
         return host(6)
     out["added_used"] = used
+    out["chain"] = _chain_counts(norm)
     out["variants"] = [dict(pos=v.refPos, nrem=v.nRemoved, nadd=v.nAdded, added=v.added, removed=v.removed, support=v.nSupportingReads, bam_min=v.bamMinPos,
                             bam_max=v.bamMaxPos, rem_pos=v.rem_pos if v.nRemoved else v.refPos) for v in kept]
     wins = [w for w in WindowGenerator().WindowsAndVariants(reg["name"], reg["start"], reg["end"], reg["contig_len"] - 1, kept, opts)
