@@ -441,6 +441,32 @@ cdef extern from "platypus_mi355x.h":
         int32_t* region_stats
         int64_t* status
     int plat_source_variants_batch(plat_ctx* ctx, const plat_source_variants_in* inp, const plat_source_variants_out* out, void* stream) nogil
+    # tabix's iterator over inflated blocks (ti_iter_read, index.c.pysam.c:872-911, on the device)
+    ctypedef struct plat_tabix_fetch_in:
+        int32_t n_streams
+        int32_t n_chunks
+        int32_t n_blocks
+        int32_t _pad
+        const uint8_t* data
+        int64_t data_len
+        const int64_t* out_off
+        const int32_t* stream_chunk_begin
+        const int32_t* chunk_blk_first
+        const int32_t* chunk_blk_end
+        const int32_t* chunk_first_uoffset
+        const int32_t* chunk_stop_blk
+        const int32_t* chunk_stop_uoffset
+        const uint8_t* names
+        const int32_t* name_off
+        const int32_t* beg
+        const int32_t* end
+    ctypedef struct plat_tabix_fetch_out:
+        int64_t cap_text
+        uint8_t* text
+        int64_t* stream_text_off
+        int64_t* stream_counts
+        int64_t* status
+    int plat_tabix_fetch_batch(plat_ctx* ctx, const plat_tabix_fetch_in* inp, const plat_tabix_fetch_out* out, void* stream) nogil
     # read counts of reference-call blocks (outputRefCall's loop over countReadsCoveringRegion)
     int PLAT_REFCOV_RAISES
     int PLAT_REFCOV_EMPTY
@@ -737,3 +763,27 @@ cdef extern from "platypus_caller_source.h":
         const char* text
         int64_t len
     int plat_caller_set_source_lines(plat_caller* c, const plat_source_lines* per_region, int n_regions, int longHaps) nogil
+
+
+# Source VCFs as the BGZF blocks of their tabix fetches (include/platypus_caller_tabix.h): inflated and iterated on the device
+# (plat_bgzf_inflate_batch, plat_tabix_fetch_batch); from there on plat_caller_set_source_lines.
+cdef extern from "platypus_caller_tabix.h":
+    ctypedef struct plat_tabix_fetch:
+        const char* seq_name
+        int32_t itr_beg
+        int32_t itr_end
+        int32_t n_chunks
+        const plat_bgzf_chunk* chunks
+    ctypedef struct plat_source_blocks:
+        int32_t n_fetches
+        const plat_tabix_fetch* fetches
+    ctypedef struct plat_source_blocks_info:
+        int64_t n_blocks
+        int64_t compressed_bytes
+        int64_t inflated_bytes
+        int64_t lines_walked
+        int64_t lines_kept
+        int64_t kept_bytes
+        double seconds
+    int plat_caller_set_source_blocks(plat_caller* c, const plat_source_blocks* per_region, int n_regions, int longHaps,
+                                      plat_source_blocks_info* info) nogil

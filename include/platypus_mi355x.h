@@ -851,6 +851,69 @@ typedef struct plat_source_variants_out {
 
 int plat_source_variants_batch(plat_ctx* ctx, const plat_source_variants_in* in, const plat_source_variants_out* out, void* stream);
 
+/* ---- tabix's iterator over inflated blocks -------------------------------------------------------------------------
+ * Replaces  ti_iter_read  (src/tabix/index.c.pysam.c:872-911) with ti_readline (:86-120), ti_get_intv's VCF preset (:161-225) and
+ *           get_intv (:227-241), as variantutils.py:67 reaches them: vcfFile.fetch(chrom, start, end) = ti_queryi(tid, start, end)
+ * for n_streams fetches over the output of plat_bgzf_inflate_batch (data, out_off; n_blocks blocks; data_len: the room data has, the
+ * inflate's cap_bytes, out_off[n_blocks] at most), without the host seeing an inflated byte.  The chunk geometry is plat_bam_find_in's:
+ * stream s is the chunks stream_chunk_begin[s] .. stream_chunk_begin[s + 1] - 1 of its index lookup (stream_chunk_begin runs from 0 to
+ * n_chunks); chunk c is the contiguous inflated bytes of blocks chunk_blk_first[c] .. chunk_blk_end[c] - 1, its first line starts
+ * chunk_first_uoffset[c] bytes into them, it ends at offset chunk_stop_uoffset[c] of block chunk_stop_blk[c] (-1: at the end of its
+ * bytes; an end outside them is clamped to them).  The chunks' blocks ascend: chunk_blk_first[c] >= chunk_blk_end[c - 1].  Stream s
+ * queries the sequence whose name is names[name_off[s] .. name_off[s + 1]) (what the index holds for the tid) over [beg[s], end[s]),
+ * 0-based half-open.
+ *
+ * The rule, per stream, chunk by chunk, p starting at the chunk's first offset:
+ *   chunk end  when p is at or past the chunk's end E: the last chunk ends the stream; otherwise p > E refuses the stream
+ *              (PLAT_ERR_BAD_INPUT: the reference asserts curr_off == off[i].v) and p == E continues at the next chunk's first offset
+ *   line       the bytes from p up to the next '\n' in the chunk's bytes, or up to their end; p moves behind the '\n'.  A line may
+ *              span blocks and may end behind E
+ *   meta       a line whose first byte is '#' is passed over (it counts as walked)
+ *   columns    split at '\t' and at a NUL byte.  v = strtol(column 2, base 0): leading C white space (a tab is some: an empty column
+ *              2 reads the next one, as the reference's strtol does), an optional sign, 0x / 0X hex, a leading 0 octal, else decimal,
+ *              up to the first byte that is no digit of the base; no digits gives 0.  b = max(v - 1, 0), e = max(v, 1); column 4, when
+ *              it exists and is not empty: e = b + its length; column 8, when it exists: if it starts with END= e is the number behind
+ *              it (the same strtol, inside the column), else if END= occurs in it e is the number behind its first ;END= (none: e
+ *              stays).  Nothing behind the tab that ends column 8 is parsed
+ *   refused    v or e outside +-(2^31 - 1) refuses the stream (the reference narrows a long to int32 there)
+ *   stop       fewer than two columns (an empty line too), e < 0, column 1 differing from the stream's name in any byte or in length,
+ *              or b >= end: the STREAM ends, the line is not kept and nothing behind it is read, later chunks included
+ *   kept       otherwise the line is kept when e > beg and end > b; either way the walk goes on
+ * Every loop is bounded by the line's end, and that by the chunk's bytes: no input makes a lane read outside its chunk -- apart from the
+ * aligned 16-byte words that cover the data, inside data_len + PLAT_BLOB_PAD -- or spin.
+ *
+ * Output: text [cap_text + PLAT_BLOB_PAD], 16-byte aligned: every kept line's bytes (a '\r' stays) followed by one '\n', the streams
+ * back to back in order -- the form plat_source_variants_batch takes -- and PLAT_BLOB_PAD zero bytes behind them; stream_text_off
+ * [n_streams + 1]; stream_counts [2 * n_streams]: lines walked (those ahead of the stop or refusal) and lines kept; status [4]
+ * (device): {0 or the error, the lowest refused stream or -1, kept lines, kept bytes}.  A refused stream yields no text and keeps no
+ * line; the other streams are not touched by it.  More than cap_text bytes is PLAT_ERR_OVERFLOW: nothing is written behind the
+ * capacity, stream_text_off is clamped to it and status[3] still holds the full size (inflated bytes + n_chunks always suffices).  A
+ * refusal wins over an overflow.  Geometry that breaks the above is status {PLAT_ERR_INVALID, -1, 0, 0} and nothing else is written.
+ * The call enqueues seven kernels -- checks; newlines and line starts marked from aligned 16-byte loads, one wave per 1024 bytes; scan;
+ * one lane per line: its end (the r-th newline, by rank and select over the marks: no lane walks a line), columns 1 to 8, the verdict,
+ * the stream's first stop as an atomic minimum in chunk order; the lines ahead of it counted; scan; the kept lines copied wave-wide,
+ * 16 bytes per lane -- keeps its marks (a quarter of the data) and per-tile counts in the context's scratch, and does not wait;
+ * nothing traps.                                                                                                                   */
+typedef struct plat_tabix_fetch_in {
+    int32_t n_streams, n_chunks, n_blocks, _pad;
+    const uint8_t* data; int64_t data_len; const int64_t* out_off;
+    const int32_t* stream_chunk_begin;
+    const int32_t* chunk_blk_first; const int32_t* chunk_blk_end; const int32_t* chunk_first_uoffset;
+    const int32_t* chunk_stop_blk; const int32_t* chunk_stop_uoffset;
+    const uint8_t* names; const int32_t* name_off;
+    const int32_t* beg; const int32_t* end;
+} plat_tabix_fetch_in;
+
+typedef struct plat_tabix_fetch_out {
+    int64_t cap_text;
+    uint8_t* text;
+    int64_t* stream_text_off;
+    int64_t* stream_counts;
+    int64_t* status;
+} plat_tabix_fetch_out;
+
+int plat_tabix_fetch_batch(plat_ctx* ctx, const plat_tabix_fetch_in* in, const plat_tabix_fetch_out* out, void* stream);
+
 /* ---- read counts of reference-call blocks ------------------------------------------------------------------------
  * Replaces the loop of  outputRefCall   variantcaller.pyx:774-784  over  ReadArray.countReadsCoveringRegion(p, p + 1)   cwindow.pyx:176-206
  * (one call per position of a block and per sample: the block's QUAL is computed from the smallest count)

@@ -102,8 +102,16 @@ def call_variants_config4(opts, n_regions):
         nc = F.NativeCaller(local % max(1, torch.cuda.device_count()), int(os.environ.get("PLAT_CALLER_WORKERS", "8")),
                             int(os.environ.get("PLAT_CALLER_CHUNK", "4")))
         t0 = time.time()
-        lines = [b"".join(reader.texts(r["chrom"], r["start"], r["end"])) for r in regs] if reader else None
-        text.write(nc.call_regions(rr, ["S1"], opts, source_lines=lines) if rr else "")
+        if source_files and all(os.path.exists(f + ".tbi") for f in opts.sourceFile):
+            # every source file has a tabix index next to it: the chunks of each region's fetch go to the library as BGZF blocks, inflated
+            # and iterated on the device (include/platypus_caller_tabix.h); a file whose fetch raises (a name its index lacks) is left out
+            from .tabixindex import TabixFile
+            tabix = [TabixFile.open(f) for f in opts.sourceFile]
+            fetches = [[b for b in (t.fetch_blocks(r["chrom"], r["start"], r["end"]) for t in tabix) if b is not None] for r in regs]
+            text.write(nc.call_regions(rr, ["S1"], opts, source_blocks=fetches) if rr else "")
+        else:
+            lines = [b"".join(reader.texts(r["chrom"], r["start"], r["end"])) for r in regs] if reader else None
+            text.write(nc.call_regions(rr, ["S1"], opts, source_lines=lines) if rr else "")
         n_windows = nc.stats["n_windows"] if rr else 0
         nc.close()
     recs = sorted(sharding.records_from_vcf_text(text.getvalue()), key=lambda r: (sharding.chrom_key(r[0]), r[1]))

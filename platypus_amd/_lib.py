@@ -140,6 +140,17 @@ class SourceVariantsOut(C.Structure):
         "region_begin", "pos", "rem_off", "n_rem", "add_off", "n_add", "hash", "line", "region_stats", "status")]
 
 
+class TabixFetchIn(C.Structure):
+    _fields_ = [("n_streams", C.c_int32), ("n_chunks", C.c_int32), ("n_blocks", C.c_int32), ("_pad", C.c_int32), ("data", C.c_void_p),
+                ("data_len", C.c_int64)] + [(k, C.c_void_p) for k in (
+        "out_off", "stream_chunk_begin", "chunk_blk_first", "chunk_blk_end", "chunk_first_uoffset", "chunk_stop_blk", "chunk_stop_uoffset",
+        "names", "name_off", "beg", "end")]
+
+
+class TabixFetchOut(C.Structure):
+    _fields_ = [("cap_text", C.c_int64), ("text", C.c_void_p), ("stream_text_off", C.c_void_p), ("stream_counts", C.c_void_p), ("status", C.c_void_p)]
+
+
 ROUTE_MAX_GROUPS, ROUTE_MAX_SAMPLES, ROUTE_LDS_ID_BYTES = 2048, 256, 24576
 ROUTE_WHY = ("routed", "no RG field", "an RG field that is no string", "an RG value that is not in the table", "an aux field of unknown type",
              "a B array with a negative count", "aux data that runs past the record", "a fixed part that runs past the record")
@@ -273,6 +284,7 @@ SIGNATURES = {
     "plat_bam_find_records": (C.c_int, [C.c_void_p, C.POINTER(BamFindIn), C.POINTER(BamFindOut), C.c_void_p]),
     "plat_bam_route_batch": (C.c_int, [C.c_void_p, C.POINTER(BamRouteIn), C.POINTER(BamRouteOut), C.c_void_p]),
     "plat_source_variants_batch": (C.c_int, [C.c_void_p, C.POINTER(SourceVariantsIn), C.POINTER(SourceVariantsOut), C.c_void_p]),
+    "plat_tabix_fetch_batch": (C.c_int, [C.c_void_p, C.POINTER(TabixFetchIn), C.POINTER(TabixFetchOut), C.c_void_p]),
     "plat_refcall_coverage_batch": (C.c_int, [C.c_void_p, C.POINTER(RefCovIn), C.POINTER(RefCovOut), C.c_void_p]),
     "plat_refcov_lds_reads": (C.c_int, []),
     "plat_variant_read_stats_batch": (C.c_int, [C.c_void_p, C.POINTER(InfoStatsBatch), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
@@ -289,7 +301,7 @@ SIGNATURES = {
 # entry points a stand-in library built against an earlier header may lack (the CPU suite's fake device): bind() leaves them
 # unbound there; load() still requires every declared symbol of the real library
 ADDED_LATER = ("plat_read_buffers_batch", "plat_read_buffers_packed_batch", "plat_bam_decode_batch", "plat_bgzf_inflate_batch", "plat_bam_find_records",
-               "plat_bam_route_batch", "plat_source_variants_batch", "plat_refcall_coverage_batch", "plat_refcov_lds_reads",
+               "plat_bam_route_batch", "plat_source_variants_batch", "plat_tabix_fetch_batch", "plat_refcall_coverage_batch", "plat_refcov_lds_reads",
                "plat_concat_read_tables_src", "plat_pack_codes_pieces", "plat_candidates_batch_packed", "plat_gather_reads_packed",
                "plat_variant_read_stats_packed_batch")
 

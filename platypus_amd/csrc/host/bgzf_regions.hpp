@@ -16,6 +16,23 @@ namespace plathost {
 
 struct BgzfChunkAt { int region, sample, chunk, blkFirst, blkEnd; };      // where a chunk came from and its blocks in the call's list
 
+// what every entry point checks of a chunk before it reads its data
+inline bool bgzfChunkArgsOk(const plat_bgzf_chunk& ch) {
+    return !(ch.data_len < 0 || (ch.data_len && !ch.data) || ch.first_uoffset < 0 || ch.first_uoffset > 65535 || ch.end_uoffset < 0 || ch.end_uoffset > 65536 ||
+             ch.end_coffset < -1 || ch.end_coffset > ch.data_len);
+}
+// The BSIZE chain of one chunk's data (18 header bytes and the trailer of every block): block(at, head) for every block in order, false
+// ends the walk.  Returns -1 when the chain covers the data, -2 when block() ended it, else the offset at which no valid header stands.
+template <class Block> inline int64_t walkBgzfChain(const plat_bgzf_chunk& ch, Block&& block) {
+    for (int64_t at = 0; at < ch.data_len;) {
+        bgzf::BlockHead h;
+        if (bgzf::parse_header(ch.data, ch.data_len, at, &h) != 0) return at;
+        if (!block(at, h)) return -2;
+        at = h.payload + h.payload_len + 8;
+    }
+    return -1;
+}
+
 // The chunks of one call -- every (region, unit) in order, a unit being what one index lookup fetched (a sample; a file for the read-group
 // call of rg_regions.hpp) -- from the host's walk over the block headers to the kept records' offsets on the device.
 struct BgzfFront {
@@ -47,23 +64,20 @@ struct BgzfFront {
         plat_caller* c = F.c;
         for (int q = 0; q < n_chunks; ++q) {
             const plat_bgzf_chunk& ch = chunks[q];
-            if (ch.data_len < 0 || (ch.data_len && !ch.data) || ch.first_uoffset < 0 || ch.first_uoffset > 65535 || ch.end_uoffset < 0 || ch.end_uoffset > 65536 ||
-                ch.end_coffset < -1 || ch.end_coffset > ch.data_len)
-                return PLAT_ERR_INVALID;
+            if (!bgzfChunkArgsOk(ch)) return PLAT_ERR_INVALID;
             BgzfChunkAt a{k, i, q, (int)blkOff.size(), 0};
             int endBlk = ch.end_coffset < 0 || (ch.end_coffset == ch.data_len && ch.end_uoffset == 0) ? -1 : -2;       // -2: not found yet
-            for (int64_t at = 0; at < ch.data_len;) {
-                bgzf::BlockHead h;
-                if (bgzf::parse_header(ch.data, ch.data_len, at, &h) != 0) {
-                    c->lastError = entry + ": the BGZF blocks of " + where(a) + " do not chain: no valid block header at offset " +
-                                   std::to_string(at) + " of its data (bad magic, no BC subfield, or a block that leaves the data)";
-                    return PLAT_ERR_BAD_INPUT;
-                }
+            const int64_t broke = walkBgzfChain(ch, [&](int64_t at, const bgzf::BlockHead& h) {
                 if (at == ch.end_coffset) endBlk = (int)blkOff.size();
                 blkOff.push_back(blobBytes + at); blkLimit.push_back(blobBytes + ch.data_len);
                 inflated += h.isize;
-                at = h.payload + h.payload_len + 8;
-                if (blkOff.size() >= (size_t)INT_MAX) { c->lastError = entry + ": more blocks than one call takes"; return PLAT_ERR_OVERFLOW; }
+                return blkOff.size() < (size_t)INT_MAX;
+            });
+            if (broke == -2) { c->lastError = entry + ": more blocks than one call takes"; return PLAT_ERR_OVERFLOW; }
+            if (broke >= 0) {
+                c->lastError = entry + ": the BGZF blocks of " + where(a) + " do not chain: no valid block header at offset " +
+                               std::to_string(broke) + " of its data (bad magic, no BC subfield, or a block that leaves the data)";
+                return PLAT_ERR_BAD_INPUT;
             }
             if (endBlk == -2) {
                 c->lastError = entry + ": end_coffset " + std::to_string(ch.end_coffset) + " of " + where(a) + " is not a block boundary of its data";

@@ -100,12 +100,13 @@ struct plat_caller {
     std::vector<plat_source_lines> sourceLines;
     bool sourceSet = false;
     int sourceLongHaps = 0;
+    std::vector<char> sourceText;                                           // plat_caller_set_source_blocks: the kept lines sourceLines points into
 };
 // every entry point holds one: the source lines apply to ONE call and are gone when it returns, however it returns
 struct SourceLinesGuard {
     plat_caller* c;
     explicit SourceLinesGuard(plat_caller* c_) : c(c_) {}
-    ~SourceLinesGuard() { if (c) { c->sourceLines.clear(); c->sourceSet = false; c->sourceLongHaps = 0; } }
+    ~SourceLinesGuard() { if (c) { c->sourceLines.clear(); c->sourceSet = false; c->sourceLongHaps = 0; std::vector<char>().swap(c->sourceText); } }
 };
 
 CALLER_EXPORT void plat_caller_default_options(plat_caller_options* o) {
@@ -742,3 +743,4 @@ CALLER_EXPORT void plat_caller_debug_set_order(const char* names, char* out, siz
 #include "bam_regions.hpp"
 #include "bgzf_regions.hpp"
 #include "rg_regions.hpp"
+#include "tabix_source.hpp"

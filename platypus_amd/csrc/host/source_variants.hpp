@@ -238,6 +238,7 @@ CALLER_EXPORT int plat_caller_set_source_lines(plat_caller* c, const plat_source
     if (!c || n_regions < 0 || (n_regions > 0 && !per_region)) return PLAT_ERR_INVALID;
     for (int k = 0; k < n_regions; ++k) if (per_region[k].len < 0 || (per_region[k].len > 0 && !per_region[k].text)) return PLAT_ERR_INVALID;
     c->sourceLines.assign(per_region, per_region + n_regions);
+    std::vector<char>().swap(c->sourceText);                               // (lines plat_caller_set_source_blocks fetched earlier are replaced too)
     c->sourceSet = n_regions > 0;                                          // (an empty list takes back lines set earlier: the next call is one without source lines)
     c->sourceLongHaps = longHaps;
     return PLAT_OK;

@@ -966,6 +966,43 @@ class Engine:
                                            "plat_source_variants_batch")
         return out
 
+    def tabix_fetch(self, inflated, geometry, cap_text=None):
+        """plat_tabix_fetch_batch: tabix's iterator (ti_iter_read, index.c.pysam.c:872-911) over the output of bgzf_inflate(...,
+        keep_device=True).  geometry: the arrays plat_tabix_fetch_in names (stream_chunk_begin, chunk_blk_first, chunk_blk_end,
+        chunk_first_uoffset, chunk_stop_blk, chunk_stop_uoffset, names, name_off, beg, end).  Returns a dict: text (the kept lines, at most
+        cap_text bytes -- default: inflated bytes + chunks, which always suffices), off [n + 1], counts [2 n] (walked, kept per stream),
+        status [4] = {error, lowest refused stream, kept lines, kept bytes} and guard_intact: nothing was written behind the text but the
+        PLAT_BLOB_PAD zeros, or behind any other output (nothing at all but the status when the call is refused as invalid)."""
+        torch = _torch()
+        dv = inflated["device"]
+        total = int(inflated["status"][2])
+        n, n_chunks = len(geometry["beg"]), len(geometry["chunk_blk_first"])
+        cap = total + n_chunks if cap_text is None else int(cap_text)
+        dev = lambda a, dt: torch.from_numpy(np.append(np.asarray(a, dtype=dt), np.zeros(1, dtype=dt))).to(self.device)
+        keys = ("stream_chunk_begin", "chunk_blk_first", "chunk_blk_end", "chunk_first_uoffset", "chunk_stop_blk", "chunk_stop_uoffset")
+        d = {k: dev(geometry[k], np.int32) for k in keys + ("name_off", "beg", "end")}
+        d_names = dev(geometry["names"], np.uint8)
+        guard, fill, f64 = 64, 0xEE, 0x7EEE7EEE7EEE7EEE
+        d_text = torch.full((guard + cap + _lib.PLAT_BLOB_PAD + guard,), fill, dtype=torch.uint8, device=self.device)
+        assert d_text.data_ptr() % 16 == 0
+        d_off = torch.full((n + 1 + 16,), f64, dtype=torch.int64, device=self.device)
+        d_counts = torch.full((2 * n + 16,), f64, dtype=torch.int64, device=self.device)
+        d_status = torch.full((4 + 16,), f64, dtype=torch.int64, device=self.device)
+        fi = _lib.TabixFetchIn(n, n_chunks, dv["n_blocks"], 0, dv["data_ptr"], total, dv["out_off"].data_ptr(), *[d[k].data_ptr() for k in keys],
+                               d_names.data_ptr(), d["name_off"].data_ptr(), d["beg"].data_ptr(), d["end"].data_ptr())
+        fo = _lib.TabixFetchOut(cap, d_text.data_ptr() + guard, d_off.data_ptr(), d_counts.data_ptr(), d_status.data_ptr())
+        _lib.check(self.lib.plat_tabix_fetch_batch(self.ctx, C.byref(fi), C.byref(fo), self._stream()), "plat_tabix_fetch_batch")
+        self._sync()
+        h, off, counts, st = (t.cpu().numpy() for t in (d_text, d_off, d_counts, d_status))
+        invalid = int(st[0]) == -1
+        used = 0 if invalid else min(int(st[3]), cap)
+        pad = 0 if invalid else _lib.PLAT_BLOB_PAD
+        tail = h[guard + used:]
+        n_off, n_counts = (0, 0) if invalid else (n + 1, 2 * n)
+        intact = (bool((h[:guard] == fill).all()) and not tail[:pad].any() and bool((tail[pad:] == fill).all()) and bool((off[n_off:] == f64).all()) and
+                  bool((counts[n_counts:] == f64).all()) and bool((st[4:] == f64).all()))
+        return dict(text=h[guard:guard + used].tobytes(), off=off[:n_off].tolist(), counts=counts[:n_counts].tolist(), status=st[:4].tolist(), guard_intact=intact)
+
     def refcall_coverage(self, read_pos, read_end, slices, intervals, tile_first=None):
         """plat_refcall_coverage_batch: the loop of outputRefCall (variantcaller.pyx:774-784) over ReadArray.countReadsCoveringRegion
         (cwindow.pyx:176-206) on the device.  read_pos / read_end: the read table; slices: [(begin, n, longest)], one sample's good reads each;

@@ -104,6 +104,20 @@ class _SourceLines(C.Structure):
     _fields_ = [("text", C.c_void_p), ("len", C.c_int64)]
 
 
+class _TabixFetch(C.Structure):
+    """plat_tabix_fetch (include/platypus_caller_tabix.h)."""
+    _fields_ = [("seq_name", C.c_char_p), ("itr_beg", C.c_int32), ("itr_end", C.c_int32), ("n_chunks", C.c_int32), ("chunks", C.c_void_p)]
+
+
+class _SourceBlocks(C.Structure):
+    _fields_ = [("n_fetches", C.c_int32), ("fetches", C.c_void_p)]
+
+
+class SourceBlocksInfo(C.Structure):
+    """plat_source_blocks_info."""
+    _fields_ = [(k, C.c_int64) for k in ("n_blocks", "compressed_bytes", "inflated_bytes", "lines_walked", "lines_kept", "kept_bytes")] + [("seconds", C.c_double)]
+
+
 class _FetchedReads(C.Structure):
     _fields_ = [("fetched", _ReadTable), ("broken_mates", _ReadTable), ("chrom_id", C.c_void_p), ("mate_chrom_id", C.c_void_p),
                 ("insert_size", C.c_void_p)]
@@ -607,6 +621,7 @@ def build(verbose=False):
     srcs.append(os.path.join(_lib.CSRC, "bgzf_inflate.hpp"))           # (the BGZF front end reads block headers with the device's own parser)
     srcs.append(os.path.join(_lib.CSRC, "source_rule.hpp"))            # (... and the host parser of source VCF lines is the device's rule)
     srcs.append(os.path.join(_lib.CSRC, "refcov_rule.hpp"))            # (... as the host's loop over a REFCALL block's positions is)
+    srcs.append(os.path.join(_lib.CSRC, "tabix_rule.hpp"))             # (... and the host's walk over a tabix fetch's lines)
     if os.path.exists(LIB_PATH) and os.path.getmtime(LIB_PATH) >= max([os.path.getmtime(f) for f in srcs] + [os.path.getmtime(_lib.LIB_PATH)]):
         return LIB_PATH
     # (-O3: the region loop is many small functions over small containers; +10 % windows/s over -O2 on the same box.  No -march: the library
@@ -651,6 +666,7 @@ def _bind(lib):
     lib.plat_caller_region_text_lengths.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     lib.plat_merge_region_blocks.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
     lib.plat_caller_set_source_lines.argtypes = [C.c_void_p, C.POINTER(_SourceLines), C.c_int, C.c_int]
+    lib.plat_caller_set_source_blocks.argtypes = [C.c_void_p, C.POINTER(_SourceBlocks), C.c_int, C.c_int, C.POINTER(SourceBlocksInfo)]
     lib.plat_caller_free.argtypes = [C.c_void_p]
     lib.plat_caller_free.restype = None
     lib.plat_caller_last_error.argtypes = [C.c_void_p]
@@ -853,6 +869,38 @@ class NativeCaller:
             raise _lib.PlatypusDeviceError(rc, "plat_caller_set_source_lines", "plat_caller_set_source_lines")
         return texts, arr
 
+    def set_source_blocks(self, source_blocks, long_haps=0):
+        """plat_caller_set_source_blocks: the source VCF lines of the NEXT call, fetched on the device from BGZF blocks.  Per region of its
+        list a list of fetches, one per source file in file order: (seq_name, itr_beg, itr_end, chunks), chunks as BgzfRegion takes them --
+        [(data uint8 array, first_uoffset, end_coffset, end_uoffset)] (tabixindex.TabixFile.fetch_blocks makes one).  The blocks are read
+        inside this call; self.source_blocks_info describes it (plat_source_blocks_info as a dict)."""
+        arr = (_SourceBlocks * max(len(source_blocks), 1))()
+        keep = []
+        for k, fetches in enumerate(source_blocks):
+            ff = (_TabixFetch * max(len(fetches), 1))()
+            for j, (name, beg, end, chunks) in enumerate(fetches):
+                chunks = [(_u8(d), fu, ec, eu) for d, fu, ec, eu in chunks]
+                cc = _chunk_array(chunks)
+                ff[j].seq_name, ff[j].itr_beg, ff[j].itr_end = name if isinstance(name, bytes) else name.encode(), int(beg), int(end)
+                ff[j].n_chunks, ff[j].chunks = len(chunks), C.cast(cc, C.c_void_p)
+                keep.append((chunks, cc))
+            arr[k].n_fetches, arr[k].fetches = len(fetches), C.cast(ff, C.c_void_p)
+            keep.append(ff)
+        info = SourceBlocksInfo()
+        rc = self.lib.plat_caller_set_source_blocks(self.h, arr, len(source_blocks), int(long_haps), C.byref(info))
+        del keep
+        if rc != 0:
+            raise _lib.PlatypusDeviceError(rc, (self.lib.plat_caller_last_error(self.h) or b"").decode(), "plat_caller_set_source_blocks")
+        self.source_blocks_info = {k: getattr(info, k) for k, _ in info._fields_}
+
+    def _set_source(self, source_lines, source_blocks, options):
+        """The source of the next call, whichever way it was given (not both); returns what has to stay alive until it has returned."""
+        if source_lines is not None and source_blocks is not None:
+            raise ValueError("source_lines and source_blocks are two ways to say the same thing: give one")
+        if source_blocks is not None:
+            return self.set_source_blocks(source_blocks, getattr(options, "longHaps", 0))
+        return self.set_source_lines(source_lines, getattr(options, "longHaps", 0)) if source_lines is not None else None
+
     def _finish(self, rc, entry, text, length, o, st, options, raw=False):
         """What follows every call into the region loop: the library's message as PlatypusDeviceError, or the text (as _native_text hands
         it over), options.rlen as the reference updates it, self.stats."""
@@ -868,12 +916,13 @@ class NativeCaller:
         names = (C.c_char_p * len(sample_names))(*[s.encode() for s in sample_names])
         return names, CallerOptions.from_options(options), C.c_void_p(), C.c_size_t(), CallerStats()
 
-    def call_regions(self, regions, sample_names, options, source_lines=None):
+    def call_regions(self, regions, sample_names, options, source_lines=None, source_blocks=None):
         """regions: list of RegionReads.  Returns the record lines of all regions (str), in region order; options.rlen is updated
         as the reference updates it.  source_lines: per region the text its source VCF fetches returned (set_source_lines; longHaps is
-        options.longHaps): candidates from the source join those of the reads."""
+        options.longHaps): candidates from the source join those of the reads.  source_blocks: the same from the BGZF blocks of the
+        fetches (set_source_blocks)."""
         n, nS = len(regions), len(sample_names)
-        keep = self.set_source_lines(source_lines, getattr(options, "longHaps", 0)) if source_lines is not None else None
+        keep = self._set_source(source_lines, source_blocks, options)
         arr = (_Region * max(n, 1))()
         for k, r in enumerate(regions):
             r.fill(arr[k], nS)
@@ -882,16 +931,16 @@ class NativeCaller:
         del keep
         return self._finish(rc, "plat_call_regions", text, length, o, st, options)
 
-    def call_bam_regions(self, regions, sample_names, options, source_lines=None):
+    def call_bam_regions(self, regions, sample_names, options, source_lines=None, source_blocks=None):
         """regions: list of BamRegion.  As call_fetched_regions, with ReadIterator.get (htslibWrapper.pyx:328-406) on the device in front: the
         records are uploaded as they are and decoded there (plat_bam_decode_batch); the same text, rlen, self.loaded and self.read_counts."""
-        return self._call_front("plat_call_bam_regions", _BamRegion, regions, sample_names, options, source_lines=source_lines)
+        return self._call_front("plat_call_bam_regions", _BamRegion, regions, sample_names, options, source_lines=source_lines, source_blocks=source_blocks)
 
-    def call_bgzf_regions(self, regions, sample_names, options):
+    def call_bgzf_regions(self, regions, sample_names, options, source_lines=None, source_blocks=None):
         """regions: list of BgzfRegion.  As call_bam_regions, with the BGZF blocks inflated (plat_bgzf_inflate_batch) and sam_itr_next applied
         (plat_bam_find_records) on the device in front: the compressed bytes are uploaded as they are; the same text, rlen, self.loaded and
         self.read_counts; stats["input_bytes"] counts the compressed bytes."""
-        return self._call_front("plat_call_bgzf_regions", _BgzfRegion, regions, sample_names, options)
+        return self._call_front("plat_call_bgzf_regions", _BgzfRegion, regions, sample_names, options, source_lines=source_lines, source_blocks=source_blocks)
 
     def call_bam_regions_rg(self, regions, read_groups, sample_names, options):
         """regions: list of BamFileRegion (all with the same number of files); read_groups: {read-group ID: sample index} or a list of
@@ -903,20 +952,20 @@ class NativeCaller:
         """regions: list of BgzfFileRegion.  As call_bam_regions_rg, from the files' BGZF blocks (inflate, find, route, decode on the device)."""
         return self._call_front("plat_call_bgzf_regions_rg", _BgzfRgRegion, regions, sample_names, options, groups=read_groups)
 
-    def call_fetched_regions(self, regions, sample_names, options, source_lines=None):
+    def call_fetched_regions(self, regions, sample_names, options, source_lines=None, source_blocks=None):
         """regions: list of FetchedRegion.  The loader's work (addReadToBuffer's QC and split, isSorted, maxReads) on the device, then the
         region loop as call_regions runs it; the QC options come from the same `options`.  Returns the record lines (str); options.rlen is
         updated as the reference updates it.  self.loaded[k] (0: region k reached maxReads and was not called) and self.read_counts[k]
         (int32 [n_samples, 10]: n_good, n_bad, the 8 reason counts -- filteredReadCountsByType slots 0-6 and secondary alignments) describe
         the last call.  source_lines: as call_regions takes them, one entry per region of THIS list (the regions the loader gives up on
         included: their lines are dropped with them)."""
-        return self._call_front("plat_call_fetched_regions", _FetchedRegion, regions, sample_names, options, source_lines=source_lines)
+        return self._call_front("plat_call_fetched_regions", _FetchedRegion, regions, sample_names, options, source_lines=source_lines, source_blocks=source_blocks)
 
-    def _call_front(self, entry, struct, regions, sample_names, options, groups=None, source_lines=None):
+    def _call_front(self, entry, struct, regions, sample_names, options, groups=None, source_lines=None, source_blocks=None):
         """One call of a front end of the region loop (include/platypus_caller_{fetched,bam,bgzf,rg}.h): `struct` is its region struct,
         `groups` the read-group table of the merged-file calls."""
         n, nS = len(regions), len(sample_names)
-        keep_source = self.set_source_lines(source_lines, getattr(options, "longHaps", 0)) if source_lines is not None else None
+        keep_source = self._set_source(source_lines, source_blocks, options)
         extra = ()
         n_units = nS
         if groups is not None:                                               # the merged-file calls: regions of files, and the read-group table
@@ -951,13 +1000,13 @@ class NativeCaller:
             raise _lib.PlatypusDeviceError(rc, "no call yet, or another number of regions", "plat_caller_region_text_lengths")
         return out[:n_regions]
 
-    def call_stream(self, n_regions, load, user, sample_names, options, n_slots, n_loaders=2, raw=False, source_lines=None):
+    def call_stream(self, n_regions, load, user, sample_names, options, n_slots, n_loaders=2, raw=False, source_lines=None, source_blocks=None):
         """plat_call_regions_stream: regions loaded on demand.  `load`: a plat_region_load_fn -- the address of a native function (int,
         e.g. tools/synth's generator: no Python in the loader threads) or a Python callable (index, slot, region_struct) -> status (wrapped;
         tests).  Returns the record lines of all regions in region order: str, or bytes with raw=True (a whole-genome share is ~100 MB of
         text: every decode / encode of it is a pass through memory the caller may not want)."""
         nS = len(sample_names)
-        keep_source = self.set_source_lines(source_lines, getattr(options, "longHaps", 0)) if source_lines is not None else None   # (as call_regions)
+        keep_source = self._set_source(source_lines, source_blocks, options)   # (as call_regions)
         keep = None
         if callable(load):
             fn = load

@@ -52,7 +52,10 @@ CALL_VARIANTS_OPTIONS = [
 
 
 SOURCE_HELP = ("FILE[,FILE]: VCF file(s) of known alleles to genotype next to (or, with --getVariantsFromBAMs=0, instead of) the candidates from the "
-               "reads.  With --synthetic=config4:N the files are read as plain or gzip/bgzip text and every region is handed the data lines whose "
+               "reads.  With --synthetic=config4:N: when EVERY file is bgzipped and has a tabix index FILE.tbi next to it, the index is read, the "
+               "chunks of each region's fetch are cut out of the file and handed to the library as BGZF blocks, which inflates and iterates them on "
+               "the device as tabix does (include/platypus_caller_tabix.h).  Otherwise the files are read as plain or gzip/bgzip text and every "
+               "region is handed the data lines whose "
                "[POS-1, POS-1+len(REF)) overlaps it: this is the CLI's OWN STAND-IN for a tabix fetch (no .tbi index is read); an integrator hands "
                "the library the lines its tabix fetch returned (include/platypus_caller_source.h).  The stand-in cannot place a line without five columns "
                "or with a POS that is no number and LEAVES IT OUT; the library, handed such a line, ends the call with an error that names it.  "
