@@ -10,6 +10,7 @@
 //                 1.5 bytes in and 2 bytes out per base: a streaming kernel.
 // Errors go to the status block; nothing traps.
 #include "plat_internal.hpp"
+#include "wave_tiles.hpp"
 
 namespace plat {
 constexpr int SCAN_THREADS = 1024;
@@ -59,14 +60,6 @@ k_bam_core(int n, const uint8_t* __restrict__ blob, long long blob_len, const in
     o.read_off[i + 1] = lSeq; o.cig_off[i + 1] = (int32_t)nCig;
 }
 
-__device__ __forceinline__ long long bam_wave_scan(long long v, int lane) {
-    for (int d = 1; d < 64; d <<= 1) {
-        const long long u = __shfl_up(v, d, 64);
-        if (lane >= d) v += u;
-    }
-    return v;
-}
-
 __global__ void __launch_bounds__(SCAN_THREADS)
 k_bam_scan(int n, plat_bam_decode_out o)
 {
@@ -85,7 +78,7 @@ k_bam_scan(int n, plat_bam_decode_out o)
             b[k] = in ? o.read_off[i0 + k + 1] : 0; c[k] = in ? o.cig_off[i0 + k + 1] : 0;
             sb += b[k]; sc += c[k];
         }
-        const long long ib = bam_wave_scan(sb, lane), ic = bam_wave_scan(sc, lane);
+        const long long ib = wave_incl_scan(sb, lane), ic = wave_incl_scan(sc, lane);
         if (lane == 63) { s_wave[0][wave] = ib; s_wave[1][wave] = ic; }
         __syncthreads();
         long long atB = runB + ib - sb, atP = runP + ic - sc, allB = 0, allP = 0;
@@ -201,17 +194,11 @@ PLAT_EXPORT int plat_bam_decode_batch(plat_ctx* ctx, int n_records, const uint8_
     PLAT_HIP(ctx, hipMemsetAsync(o.status, 0xff, 4 * sizeof(int64_t), st));
     if (n_records == 0) PLAT_HIP(ctx, hipMemsetAsync(o.read_off, 0, sizeof(int64_t), st));
     if (n_records == 0) PLAT_HIP(ctx, hipMemsetAsync(o.cig_off, 0, sizeof(int32_t), st));
-    if (n_records > 0) {
-        PLAT_KT_BEGIN(ctx, PLAT_KT_OTHER, st);
-        hipLaunchKernelGGL(plat::k_bam_core, dim3((unsigned)((n_records + 255) / 256)), dim3(256), 0, st, n_records, blob, (long long)blob_len, rec_off, rec_limit, o);
-        PLAT_KT_END(ctx, PLAT_KT_OTHER, st);
-    }
-    { PLAT_KT_BEGIN(ctx, PLAT_KT_OTHER, st); hipLaunchKernelGGL(plat::k_bam_scan, dim3(1), dim3(plat::SCAN_THREADS), 0, st, n_records, o); PLAT_KT_END(ctx, PLAT_KT_OTHER, st); }
-    if (n_records > 0) {
-        PLAT_KT_BEGIN(ctx, PLAT_KT_OTHER, st);
-        hipLaunchKernelGGL(plat::k_bam_expand, dim3((unsigned)(((long long)n_records * 16 + 255) / 256)), dim3(256), 0, st, n_records, blob, rec_off, o);
-        PLAT_KT_END(ctx, PLAT_KT_OTHER, st);
-    }
+    if (n_records > 0)
+        PLAT_LAUNCH(ctx, PLAT_KT_OTHER, st, plat::k_bam_core, dim3((unsigned)((n_records + 255) / 256)), dim3(256), 0, n_records, blob, (long long)blob_len, rec_off, rec_limit, o);
+    PLAT_LAUNCH(ctx, PLAT_KT_OTHER, st, plat::k_bam_scan, dim3(1), dim3(plat::SCAN_THREADS), 0, n_records, o);
+    if (n_records > 0)
+        PLAT_LAUNCH(ctx, PLAT_KT_OTHER, st, plat::k_bam_expand, dim3((unsigned)(((long long)n_records * 16 + 255) / 256)), dim3(256), 0, n_records, blob, rec_off, o);
     PLAT_HIP(ctx, hipGetLastError());
     return PLAT_OK;
 }

@@ -17,11 +17,11 @@
 
 #include "plat_internal.hpp"
 #include "bam_aux.hpp"
+#include "wave_tiles.hpp"
 
 namespace plat {
 constexpr int ROUTE_TILE = 256;                           // records per tile = threads per workgroup of the tile kernels
 constexpr int ROUTE_WAVES = ROUTE_TILE / 64;
-constexpr int ROUTE_SCAN_THREADS = 1024;
 constexpr int ROUTE_SLOTS = 2 * PLAT_ROUTE_MAX_GROUPS;    // the largest table: a power of two >= 2 * n_groups
 constexpr int ROUTE_TAG_BLOCKS = 2048;                    // the tag kernel's grid is capped: a workgroup stages the table once for many records
 constexpr unsigned long long ROUTE_NO_ERROR = ~0ull;
@@ -34,53 +34,21 @@ struct RouteBytes {
     __device__ __forceinline__ uint8_t operator[](int64_t at) const { return p[at]; }
 };
 
-// a[0 .. n) to its exclusive prefix sums in place, by all ROUTE_SCAN_THREADS threads of one workgroup; returns the total
-__device__ long long route_scan_inplace(int32_t* a, long long n, long long* s_wave)
-{
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    long long run = 0;
-    for (long long t0 = 0; t0 < n; t0 += ROUTE_SCAN_THREADS * 4) {
-        const long long i0 = t0 + (long long)tid * 4;
-        long long v[4], sum = 0;
-        for (int k = 0; k < 4; ++k) { v[k] = i0 + k < n ? a[i0 + k] : 0; sum += v[k]; }
-        long long incl = sum;
-        for (int d = 1; d < 64; d <<= 1) {
-            const long long u = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += u;
-        }
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        long long at = run + incl - sum, all = 0;
-        for (int w = 0; w < ROUTE_SCAN_THREADS / 64; ++w) {
-            if (w < wave) at += s_wave[w];
-            all += s_wave[w];
-        }
-        for (int k = 0; k < 4; ++k) {
-            if (i0 + k >= n) break;
-            a[i0 + k] = (int32_t)at;
-            at += v[k];
-        }
-        run += all;
-        __syncthreads();                                                // (s_wave is rewritten by the next round)
-    }
-    return run;
-}
-
-__global__ void __launch_bounds__(ROUTE_SCAN_THREADS)
+__global__ void __launch_bounds__(BLOCK_SCAN_THREADS)
 k_route_check(plat_bam_route_in in, plat_bam_route_out o, int32_t* __restrict__ tile_begin)
 {
-    __shared__ long long s_wave[ROUTE_SCAN_THREADS / 64];
+    __shared__ long long s_wave[BLOCK_SCAN_THREADS / 64];
     __shared__ int s_bad;
     const int tid = threadIdx.x;
     if (tid == 0) s_bad = 0;
     __syncthreads();
     bool bad = false;
-    for (int g = tid; g < in.n_groups; g += ROUTE_SCAN_THREADS) {
+    for (int g = tid; g < in.n_groups; g += BLOCK_SCAN_THREADS) {
         const int32_t m = in.group_sample[g], a = in.group_off[g], b = in.group_off[g + 1];
         if (m < 0 || m >= in.n_samples || b < a || (g == 0 && a != 0)) bad = true;
     }
     if (tid == 0 && in.stream_begin[0] != 0) bad = true;
-    for (int s = tid; s < in.n_streams; s += ROUTE_SCAN_THREADS) {
+    for (int s = tid; s < in.n_streams; s += BLOCK_SCAN_THREADS) {
         const int32_t b = in.stream_begin[s], e = in.stream_begin[s + 1];
         const bool ok = b >= 0 && e >= b && e <= in.n_records;
         if (!ok) bad = true;
@@ -92,7 +60,7 @@ k_route_check(plat_bam_route_in in, plat_bam_route_out o, int32_t* __restrict__ 
         if (tid == 0) { o.status[0] = PLAT_ERR_INVALID; o.status[1] = -1; o.status[2] = 0; o.status[3] = 0; }
         return;
     }
-    const long long tiles = route_scan_inplace(tile_begin, in.n_streams, s_wave);
+    const long long tiles = block_scan_inplace<BLOCK_SCAN_THREADS>(tile_begin, in.n_streams, s_wave);
     if (tid == 0) {
         tile_begin[in.n_streams] = (int32_t)tiles;
         o.status[0] = 0; o.status[1] = (int64_t)ROUTE_NO_ERROR; o.status[2] = 0; o.status[3] = 0;
@@ -189,16 +157,16 @@ k_route_scan_tiles(plat_bam_route_in in, plat_bam_route_out o, const int32_t* __
     o.out_begin[k] = run;
 }
 
-__global__ void __launch_bounds__(ROUTE_SCAN_THREADS)
+__global__ void __launch_bounds__(BLOCK_SCAN_THREADS)
 k_route_scan_out(plat_bam_route_in in, plat_bam_route_out o)
 {
-    __shared__ long long s_wave[ROUTE_SCAN_THREADS / 64];
+    __shared__ long long s_wave[BLOCK_SCAN_THREADS / 64];
     if (o.status[0] == PLAT_ERR_INVALID) {
         if (threadIdx.x == 0 && o.why) o.why[0] = 0;
         return;
     }
     const long long K = (long long)in.n_streams * in.n_samples;
-    const long long total = route_scan_inplace(o.out_begin, K, s_wave);
+    const long long total = block_scan_inplace<BLOCK_SCAN_THREADS>(o.out_begin, K, s_wave);
     if (threadIdx.x == 0) {
         o.out_begin[K] = (int32_t)total;
         const unsigned long long key = (unsigned long long)o.status[1];
@@ -265,31 +233,16 @@ PLAT_EXPORT int plat_bam_route_batch(plat_ctx* ctx, const plat_bam_route_in* in,
     if (rc != PLAT_OK) return rc;
     int32_t* tileBegin = (int32_t*)ctx->route.ptr;
     int32_t* hist = tileBegin + q.n_streams + 1;
-    PLAT_KT_BEGIN(ctx, PLAT_KT_OTHER, st);
-    hipLaunchKernelGGL(plat::k_route_check, dim3(1), dim3(plat::ROUTE_SCAN_THREADS), 0, st, q, o, tileBegin);
-    PLAT_KT_END(ctx, PLAT_KT_OTHER, st);
+    PLAT_LAUNCH(ctx, PLAT_KT_OTHER, st, plat::k_route_check, dim3(1), dim3(plat::BLOCK_SCAN_THREADS), 0, q, o, tileBegin);
     if (q.n_records > 0 && q.n_streams > 0) {
         const unsigned tagBlocks = (unsigned)std::min<long long>(((long long)q.n_records + plat::ROUTE_TILE - 1) / plat::ROUTE_TILE, plat::ROUTE_TAG_BLOCKS);
-        PLAT_KT_BEGIN(ctx, PLAT_KT_OTHER, st);
-        hipLaunchKernelGGL(plat::k_route_tag, dim3(tagBlocks), dim3(plat::ROUTE_TILE), 0, st, q, o);
-        PLAT_KT_END(ctx, PLAT_KT_OTHER, st);
-        PLAT_KT_BEGIN(ctx, PLAT_KT_OTHER, st);
-        hipLaunchKernelGGL(plat::k_route_hist, dim3((unsigned)tiles), dim3(plat::ROUTE_TILE), 0, st, q, o, tileBegin, hist);
-        PLAT_KT_END(ctx, PLAT_KT_OTHER, st);
+        PLAT_LAUNCH(ctx, PLAT_KT_OTHER, st, plat::k_route_tag, dim3(tagBlocks), dim3(plat::ROUTE_TILE), 0, q, o);
+        PLAT_LAUNCH(ctx, PLAT_KT_OTHER, st, plat::k_route_hist, dim3((unsigned)tiles), dim3(plat::ROUTE_TILE), 0, q, o, tileBegin, hist);
     }
-    if (keys > 0) {
-        PLAT_KT_BEGIN(ctx, PLAT_KT_OTHER, st);
-        hipLaunchKernelGGL(plat::k_route_scan_tiles, dim3((unsigned)((keys + 255) / 256)), dim3(256), 0, st, q, o, tileBegin, hist);
-        PLAT_KT_END(ctx, PLAT_KT_OTHER, st);
-    }
-    PLAT_KT_BEGIN(ctx, PLAT_KT_OTHER, st);
-    hipLaunchKernelGGL(plat::k_route_scan_out, dim3(1), dim3(plat::ROUTE_SCAN_THREADS), 0, st, q, o);
-    PLAT_KT_END(ctx, PLAT_KT_OTHER, st);
-    if (q.n_records > 0 && q.n_streams > 0) {
-        PLAT_KT_BEGIN(ctx, PLAT_KT_OTHER, st);
-        hipLaunchKernelGGL(plat::k_route_place, dim3((unsigned)tiles), dim3(plat::ROUTE_TILE), 0, st, q, o, tileBegin, hist);
-        PLAT_KT_END(ctx, PLAT_KT_OTHER, st);
-    }
+    if (keys > 0) PLAT_LAUNCH(ctx, PLAT_KT_OTHER, st, plat::k_route_scan_tiles, dim3((unsigned)((keys + 255) / 256)), dim3(256), 0, q, o, tileBegin, hist);
+    PLAT_LAUNCH(ctx, PLAT_KT_OTHER, st, plat::k_route_scan_out, dim3(1), dim3(plat::BLOCK_SCAN_THREADS), 0, q, o);
+    if (q.n_records > 0 && q.n_streams > 0)
+        PLAT_LAUNCH(ctx, PLAT_KT_OTHER, st, plat::k_route_place, dim3((unsigned)tiles), dim3(plat::ROUTE_TILE), 0, q, o, tileBegin, hist);
     PLAT_HIP(ctx, hipGetLastError());
     return PLAT_OK;
 }

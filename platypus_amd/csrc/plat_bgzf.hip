@@ -16,6 +16,7 @@
 // Errors go to the status blocks; nothing traps.
 #include "plat_internal.hpp"
 #include "bgzf_inflate.hpp"
+#include "wave_tiles.hpp"
 
 namespace plat {
 constexpr int BGZF_SCAN_THREADS = 1024;
@@ -68,11 +69,7 @@ k_bgzf_scan(int n, plat_bgzf_inflate_out o)
     for (long long t0 = 0; t0 < n; t0 += BGZF_SCAN_THREADS) {
         const long long i = t0 + tid;
         const long long v = i < n ? o.out_off[i + 1] : 0;
-        long long inc = v;
-        for (int d = 1; d < 64; d <<= 1) {
-            const long long u = __shfl_up(inc, d, 64);
-            if (lane >= d) inc += u;
-        }
+        const long long inc = wave_incl_scan(v, lane);
         if (lane == 63) s_wave[wave] = inc;
         __syncthreads();
         long long at = run + inc, all = 0;
@@ -280,17 +277,12 @@ PLAT_EXPORT int plat_bgzf_inflate_batch(plat_ctx* ctx, int n_blocks, const uint8
     const hipStream_t st = (hipStream_t)stream;
     PLAT_HIP(ctx, hipMemsetAsync(o.status, 0xff, 4 * sizeof(int64_t), st));
     if (n_blocks == 0) PLAT_HIP(ctx, hipMemsetAsync(o.out_off, 0, sizeof(int64_t), st));
-    if (n_blocks > 0) {
-        PLAT_KT_BEGIN(ctx, PLAT_KT_OTHER, st);
-        hipLaunchKernelGGL(plat::k_bgzf_head, dim3((unsigned)((n_blocks + 255) / 256)), dim3(256), 0, st, n_blocks, blob, (long long)blob_len, blk_off, blk_limit, o);
-        PLAT_KT_END(ctx, PLAT_KT_OTHER, st);
-    }
-    { PLAT_KT_BEGIN(ctx, PLAT_KT_OTHER, st); hipLaunchKernelGGL(plat::k_bgzf_scan, dim3(1), dim3(plat::BGZF_SCAN_THREADS), 0, st, n_blocks, o); PLAT_KT_END(ctx, PLAT_KT_OTHER, st); }
+    if (n_blocks > 0)
+        PLAT_LAUNCH(ctx, PLAT_KT_OTHER, st, plat::k_bgzf_head, dim3((unsigned)((n_blocks + 255) / 256)), dim3(256), 0, n_blocks, blob, (long long)blob_len, blk_off, blk_limit, o);
+    PLAT_LAUNCH(ctx, PLAT_KT_OTHER, st, plat::k_bgzf_scan, dim3(1), dim3(plat::BGZF_SCAN_THREADS), 0, n_blocks, o);
     if (n_blocks > 0) {
         PLAT_HIP(ctx, hipFuncSetAttribute((const void*)plat::k_bgzf_inflate, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(plat::BgzfLds)));
-        PLAT_KT_BEGIN(ctx, PLAT_KT_OTHER, st);
-        hipLaunchKernelGGL(plat::k_bgzf_inflate, dim3((unsigned)n_blocks), dim3(64), sizeof(plat::BgzfLds), st, n_blocks, blob, (long long)blob_len, blk_off, blk_limit, o);
-        PLAT_KT_END(ctx, PLAT_KT_OTHER, st);
+        PLAT_LAUNCH(ctx, PLAT_KT_OTHER, st, plat::k_bgzf_inflate, dim3((unsigned)n_blocks), dim3(64), sizeof(plat::BgzfLds), n_blocks, blob, (long long)blob_len, blk_off, blk_limit, o);
     }
     hipLaunchKernelGGL(plat::k_bgzf_status, dim3(1), dim3(1), 0, st, o);
     PLAT_HIP(ctx, hipGetLastError());
@@ -310,17 +302,10 @@ PLAT_EXPORT int plat_bam_find_records(plat_ctx* ctx, const plat_bam_find_in* in,
     const hipStream_t st = (hipStream_t)stream;
     PLAT_HIP(ctx, hipMemsetAsync(o.status, 0xff, 2 * sizeof(int64_t), st));
     PLAT_HIP(ctx, hipMemsetAsync(o.status + 2, 0, 2 * sizeof(int64_t), st));
-    if (in->n_streams > 0) {
-        PLAT_KT_BEGIN(ctx, PLAT_KT_OTHER, st);
-        hipLaunchKernelGGL(plat::k_bam_find<false>, dim3((unsigned)in->n_streams), dim3(plat::FIND_THREADS), 0, st, *in, o);
-        PLAT_KT_END(ctx, PLAT_KT_OTHER, st);
-    }
+    if (in->n_streams > 0) PLAT_LAUNCH(ctx, PLAT_KT_OTHER, st, plat::k_bam_find<false>, dim3((unsigned)in->n_streams), dim3(plat::FIND_THREADS), 0, *in, o);
     hipLaunchKernelGGL(plat::k_bam_find_scan, dim3(1), dim3(64), 0, st, in->n_streams, o);
-    if (in->n_streams > 0 && out->cap_records > 0) {
-        PLAT_KT_BEGIN(ctx, PLAT_KT_OTHER, st);
-        hipLaunchKernelGGL(plat::k_bam_find<true>, dim3((unsigned)in->n_streams), dim3(plat::FIND_THREADS), 0, st, *in, o);
-        PLAT_KT_END(ctx, PLAT_KT_OTHER, st);
-    }
+    if (in->n_streams > 0 && out->cap_records > 0)
+        PLAT_LAUNCH(ctx, PLAT_KT_OTHER, st, plat::k_bam_find<true>, dim3((unsigned)in->n_streams), dim3(plat::FIND_THREADS), 0, *in, o);
     PLAT_HIP(ctx, hipGetLastError());
     return PLAT_OK;
 }

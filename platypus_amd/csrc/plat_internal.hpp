@@ -83,6 +83,13 @@ static inline void plat_kt_mark(plat_ctx* ctx, int id, hipStream_t st, bool end)
 }
 #define PLAT_KT_BEGIN(ctx, id, st) plat_kt_mark(ctx, id, (hipStream_t)(st), false)
 #define PLAT_KT_END(ctx, id, st) plat_kt_mark(ctx, id, (hipStream_t)(st), true)
+// one launch between its timer's two marks
+#define PLAT_LAUNCH(ctx, timer_id, st, kernel, grid, block, lds_bytes, ...)                          \
+    do {                                                                                             \
+        PLAT_KT_BEGIN(ctx, timer_id, st);                                                            \
+        hipLaunchKernelGGL(kernel, grid, block, lds_bytes, (hipStream_t)(st), __VA_ARGS__);          \
+        PLAT_KT_END(ctx, timer_id, st);                                                              \
+    } while (0)
 
 #define PLAT_EV_TAB(ctx, i, st) do { if ((ctx)->profile) PLAT_HIP(ctx, hipEventRecord((ctx)->ev_tab[i], st)); } while (0)
 #define PLAT_EV(ctx, i, st) do { if ((ctx)->profile) PLAT_HIP(ctx, hipEventRecord((ctx)->ev[i], st)); } while (0)

@@ -4,19 +4,12 @@
 // plat_read_buffers_packed_batch: the same for PLAT_READS_PACKED tables (k_read_qc_packed, then the same split and a gather of the packed
 // bytes).
 #include "plat_internal.hpp"
+#include "wave_tiles.hpp"
 
 namespace plat {
 constexpr int SPLIT_THREADS = 512;                       // 8 waves per stream
 constexpr int SPLIT_WAVES = SPLIT_THREADS / 64;
 constexpr int SPLIT_MASKS = 4096;                        // verdict masks kept in LDS (32 KB): streams up to 256 k reads are read once
-
-__device__ __forceinline__ long long wave_incl_scan(long long v, int lane) {
-    for (int d = 1; d < 64; d <<= 1) {
-        const long long u = __shfl_up(v, d, 64);
-        if (lane >= d) v += u;
-    }
-    return v;
-}
 
 // One workgroup per stream.  Pass 1 walks the verdicts once in tiles of 512 reads: per wave a ballot of out_ok (kept in LDS), popcounts
 // of the 8 reasons, and the sortedness test against the previous read.  Pass 2 walks the ballots (LDS; re-taken from out_ok only past
@@ -150,13 +143,13 @@ int split_and_gather(plat_ctx* ctx, const plat_readqc_batch& q, int n_streams, c
                      const int32_t* out_ok, const int32_t* out_reason, int32_t* out_perm, int32_t* out_counts, const plat_read_buffers_tables* tab,
                      bool tables, hipStream_t st)
 {
-    { PLAT_KT_BEGIN(ctx, PLAT_KT_OTHER, st); hipLaunchKernelGGL(plat::k_read_split, dim3((unsigned)n_streams), dim3(plat::SPLIT_THREADS), 0, st, q.n_reads, stream_begin,
-                       out_ok, out_reason, q.read_pos, tables ? q.read_off : nullptr, tables ? q.cig_off : nullptr, out_perm, out_counts,
-                       tables ? tab->off : nullptr, tables ? tab->cig_off : nullptr); PLAT_KT_END(ctx, PLAT_KT_OTHER, st); }
+    PLAT_LAUNCH(ctx, PLAT_KT_OTHER, st, plat::k_read_split, dim3((unsigned)n_streams), dim3(plat::SPLIT_THREADS), 0, q.n_reads, stream_begin,
+                out_ok, out_reason, q.read_pos, tables ? q.read_off : nullptr, tables ? q.cig_off : nullptr, out_perm, out_counts,
+                tables ? tab->off : nullptr, tables ? tab->cig_off : nullptr);
     if (tables && q.n_reads > 0) {
         const unsigned blocks = (unsigned)(((long long)q.n_reads + 3) / 4);
-        { PLAT_KT_BEGIN(ctx, PLAT_KT_OTHER, st); hipLaunchKernelGGL(plat::k_read_gather<QUAL>, dim3(blocks), dim3(256), 0, st, q.n_reads, n_streams, stream_begin, q,
-                           seq, end, out_perm, out_counts, *tab); PLAT_KT_END(ctx, PLAT_KT_OTHER, st); }
+        PLAT_LAUNCH(ctx, PLAT_KT_OTHER, st, plat::k_read_gather<QUAL>, dim3(blocks), dim3(256), 0, q.n_reads, n_streams, stream_begin, q,
+                    seq, end, out_perm, out_counts, *tab);
     }
     PLAT_HIP(ctx, hipGetLastError());
     return PLAT_OK;

@@ -136,15 +136,10 @@ PLAT_EXPORT int plat_refcall_coverage_batch(plat_ctx* ctx, const plat_refcov_in*
         if (rc != PLAT_OK) return rc;
         dst = (int32_t*)ctx->refcov.ptr;
     } else k.iv_tile_first = nullptr;
-    PLAT_KT_BEGIN(ctx, PLAT_KT_OTHER, st);
-    hipLaunchKernelGGL(plat::k_refcov_tiles, dim3((unsigned)q.n_tiles), dim3(plat::REFCOV_THREADS), 0, st, k, o, dst);
-    PLAT_KT_END(ctx, PLAT_KT_OTHER, st);
-    if (tiled) {
-        PLAT_KT_BEGIN(ctx, PLAT_KT_OTHER, st);
-        hipLaunchKernelGGL(plat::k_refcov_intervals, dim3((unsigned)((q.n_intervals + plat::REFCOV_THREADS - 1) / plat::REFCOV_THREADS)), dim3(plat::REFCOV_THREADS), 0, st,
-                           k, o, (const int32_t*)dst);
-        PLAT_KT_END(ctx, PLAT_KT_OTHER, st);
-    }
+    PLAT_LAUNCH(ctx, PLAT_KT_OTHER, st, plat::k_refcov_tiles, dim3((unsigned)q.n_tiles), dim3(plat::REFCOV_THREADS), 0, k, o, dst);
+    if (tiled)
+        PLAT_LAUNCH(ctx, PLAT_KT_OTHER, st, plat::k_refcov_intervals, dim3((unsigned)((q.n_intervals + plat::REFCOV_THREADS - 1) / plat::REFCOV_THREADS)),
+                    dim3(plat::REFCOV_THREADS), 0, k, o, (const int32_t*)dst);
     PLAT_HIP(ctx, hipGetLastError());
     return PLAT_OK;
 }

@@ -2,8 +2,9 @@
 // variantutils.VariantCandidateReader.Variants (variantutils.py:72-159) and isValidVcfLine (:168-197) for the lines the tabix fetches of
 // a chunk of regions returned, parsed where they lie: the text goes to the device as it is, and what comes back are the few alleles as
 // offsets into it.  The rule of one line is source_rule.hpp (compiled for the host too and tested there); this file finds the lines,
-// hands them to lanes, scans and reports.  The text is cut into tiles of SRC_TILE bytes = 64 aligned 16-byte words, one word per lane
-// of a wave.  Seven launches:
+// hands them to lanes, scans and reports.  The text is cut into tiles of TILE_BYTES = 64 aligned 16-byte words, one word per lane of a
+// wave; the tile geometry, the newline mask of a word, the workgroup scan and the hand-out of a tile's lines to lanes are wave_tiles.hpp's
+// (shared with plat_tabix.hip).  Seven launches:
 //   k_src_check   one workgroup: text_off checked (ascending inside [0, text_len]), the status block and the per-region counters reset
 //   k_src_mark    one wave per tile: each lane loads its word (one aligned 16-byte load), compares 16 bytes with '\n' and turns that
 //                 into the mask of LINE STARTS of its word -- the byte behind a newline (the carry from the word before comes over a
@@ -22,12 +23,9 @@
 
 #include "plat_internal.hpp"
 #include "source_rule.hpp"
+#include "wave_tiles.hpp"
 
 namespace plat {
-constexpr int SRC_TILE = 1024;                            // bytes of text per tile = 64 lanes x 16 bytes
-constexpr int SRC_WAVES = 4;                              // waves (tiles in flight) per workgroup of the tile kernels
-constexpr int SRC_SCAN_THREADS = 1024;
-constexpr int SRC_TILE_BLOCKS = 4096;                     // the tile kernels' grids are capped (grid-stride over tiles)
 constexpr unsigned long long SRC_NO_ERROR = ~0ull;
 
 struct SrcScratch {
@@ -38,38 +36,6 @@ struct SrcScratch {
     long long* reg_var;                                   // [n_regions + 1] alleles of each region, then in front of each region
     long long tiles;
 };
-
-// a[0 .. n) to its exclusive prefix sums in place, by all SRC_SCAN_THREADS threads of one workgroup; returns the total
-__device__ long long src_scan_inplace(long long* a, long long n, long long* s_wave)
-{
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    long long run = 0;
-    for (long long t0 = 0; t0 < n; t0 += SRC_SCAN_THREADS * 4) {
-        const long long i0 = t0 + (long long)tid * 4;
-        long long v[4], sum = 0;
-        for (int k = 0; k < 4; ++k) { v[k] = i0 + k < n ? a[i0 + k] : 0; sum += v[k]; }
-        long long incl = sum;
-        for (int d = 1; d < 64; d <<= 1) {
-            const long long u = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += u;
-        }
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        long long at = run + incl - sum, all = 0;
-        for (int w = 0; w < SRC_SCAN_THREADS / 64; ++w) {
-            if (w < wave) at += s_wave[w];
-            all += s_wave[w];
-        }
-        for (int k = 0; k < 4; ++k) {
-            if (i0 + k >= n) break;
-            a[i0 + k] = at;
-            at += v[k];
-        }
-        run += all;
-        __syncthreads();                                                // (s_wave is rewritten by the next round)
-    }
-    return run;
-}
 
 // the first k in [0, n] with off[k] >= x (off ascending, n + 1 entries are NOT assumed: k = n means none)
 __device__ __forceinline__ int src_lower_bound(const int64_t* __restrict__ off, int n, int64_t x)
@@ -82,7 +48,7 @@ __device__ __forceinline__ int src_lower_bound(const int64_t* __restrict__ off, 
     return lo;
 }
 
-__global__ void __launch_bounds__(SRC_SCAN_THREADS)
+__global__ void __launch_bounds__(BLOCK_SCAN_THREADS)
 k_src_check(plat_source_variants_in in, plat_source_variants_out o, SrcScratch z)
 {
     __shared__ int s_bad;
@@ -90,7 +56,7 @@ k_src_check(plat_source_variants_in in, plat_source_variants_out o, SrcScratch z
     if (tid == 0) s_bad = 0;
     __syncthreads();
     bool bad = false;
-    for (int k = tid; k < in.n_regions; k += SRC_SCAN_THREADS) {
+    for (int k = tid; k < in.n_regions; k += BLOCK_SCAN_THREADS) {
         const int64_t a = in.text_off[k], b = in.text_off[k + 1];
         if (a < 0 || b < a || b > in.text_len) bad = true;
         z.reg_var[k] = 0;
@@ -98,7 +64,7 @@ k_src_check(plat_source_variants_in in, plat_source_variants_out o, SrcScratch z
     if (bad) s_bad = 1;
     __syncthreads();
     if (!s_bad)                                                         // (refused as invalid: the status block is all that is written)
-        for (int k = tid; k < 4 * in.n_regions; k += SRC_SCAN_THREADS) o.region_stats[k] = 0;
+        for (int k = tid; k < 4 * in.n_regions; k += BLOCK_SCAN_THREADS) o.region_stats[k] = 0;
     if (tid == 0) {
         z.reg_var[in.n_regions] = 0;
         o.status[0] = s_bad ? PLAT_ERR_INVALID : 0;
@@ -107,33 +73,25 @@ k_src_check(plat_source_variants_in in, plat_source_variants_out o, SrcScratch z
     }
 }
 
-__global__ void __launch_bounds__(SRC_WAVES * 64)
+__global__ void __launch_bounds__(TILE_WAVES * 64)
 k_src_mark(plat_source_variants_in in, plat_source_variants_out o, SrcScratch z)
 {
     if (o.status[0] == PLAT_ERR_INVALID) return;
     const int lane = threadIdx.x & 63;
     const int64_t lo = in.n_regions ? in.text_off[0] : 0, hi = in.n_regions ? in.text_off[in.n_regions] : 0;      // the regions' bytes: [lo, hi)
-    for (long long tile = (long long)blockIdx.x * SRC_WAVES + (threadIdx.x >> 6); tile < z.tiles; tile += (long long)gridDim.x * SRC_WAVES) {
-        const int64_t tileAt = tile * SRC_TILE, at = tileAt + 16 * lane;
-        // newlines of this lane's word: an aligned 16-byte load that may run up to 15 bytes past text_len (inside PLAT_BLOB_PAD)
-        unsigned nl = 0;
-        if (at < hi && at + 16 > lo) {
-            const uint4 w = *reinterpret_cast<const uint4*>(in.text + at);
-            const unsigned v[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-            for (int j = 0; j < 16; ++j)
-                if (((v[j >> 2] >> (8 * (j & 3))) & 0xffu) == '\n' && at + j >= lo && at + j < hi) nl |= 1u << j;
-        }
+    for (long long tile = (long long)blockIdx.x * TILE_WAVES + (threadIdx.x >> 6); tile < z.tiles; tile += (long long)gridDim.x * TILE_WAVES) {
+        const int64_t tileAt = tile * TILE_BYTES, at = tileAt + 16 * lane;
+        const unsigned nl = word_newlines(in.text, at, lo, hi);
         // line starts: the byte behind a newline, while it still lies in a region
-        unsigned carry = __shfl_up(nl >> 15, 1, 64);
-        if (lane == 0) carry = (tileAt > lo && tileAt - 1 < hi && in.text[tileAt - 1] == '\n') ? 1u : 0u;
-        unsigned m = ((nl << 1) | carry) & 0xffffu;
+        unsigned before = 0;                                                // (lane 0 reads one byte: is the byte in front of the tile a newline?)
+        if (lane == 0) before = (tileAt > lo && tileAt - 1 < hi && in.text[tileAt - 1] == '\n') ? 1u : 0u;
+        unsigned m = behind_newlines(nl, lane, before);
 #pragma unroll
         for (int j = 0; j < 16; ++j) if (at + j >= hi) m &= ~(1u << j);
         // ... and the first byte of every region that holds one (a region's last line may lack its newline)
         for (int k = src_lower_bound(in.text_off, in.n_regions, tileAt); k < in.n_regions; ++k) {
             const int64_t s = in.text_off[k];
-            if (s >= tileAt + SRC_TILE) break;
+            if (s >= tileAt + TILE_BYTES) break;
             if (in.text_off[k + 1] > s && s >= at && s < at + 16) m |= 1u << (int)(s - at);
         }
         z.marks[tile * 64 + lane] = (uint16_t)m;
@@ -143,12 +101,12 @@ k_src_mark(plat_source_variants_in in, plat_source_variants_out o, SrcScratch z)
     }
 }
 
-__global__ void __launch_bounds__(SRC_SCAN_THREADS)
+__global__ void __launch_bounds__(BLOCK_SCAN_THREADS)
 k_src_scan(plat_source_variants_out o, SrcScratch z)
 {
-    __shared__ long long s_wave[SRC_SCAN_THREADS / 64];
+    __shared__ long long s_wave[BLOCK_SCAN_THREADS / 64];
     if (o.status[0] == PLAT_ERR_INVALID) return;
-    const long long total = src_scan_inplace(z.tile_line, z.tiles, s_wave);
+    const long long total = block_scan_inplace<BLOCK_SCAN_THREADS>(z.tile_line, z.tiles, s_wave);
     if (threadIdx.x == 0) { z.tile_line[z.tiles] = total; o.status[3] = total; }
 }
 
@@ -158,51 +116,8 @@ k_src_regions(plat_source_variants_in in, plat_source_variants_out o, SrcScratch
     if (o.status[0] == PLAT_ERR_INVALID) return;
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k > in.n_regions) return;
-    const int64_t s = in.text_off[k];
-    const long long tile = s / SRC_TILE;
-    long long rank = z.tile_line[z.tiles];
-    if (tile < z.tiles) {                                               // the line starts in front of byte s
-        rank = z.tile_line[tile];
-        const int word = (int)((s - tile * SRC_TILE) >> 4), bit = (int)(s & 15);
-        for (int w = 0; w < word; ++w) rank += __popc((unsigned)z.marks[tile * 64 + w]);
-        rank += __popc((unsigned)z.marks[tile * 64 + word] & ((1u << bit) - 1u));
-    }
-    z.reg_line0[k] = rank;
+    z.reg_line0[k] = marks_rank(z.marks, z.tile_line, z.tiles, in.text_off[k]);      // the line starts in front of its first byte
 }
-
-// The lines of one tile, handed to the lanes of one wave 64 at a time.  Every lane of the wave must call next() together (shuffles).
-struct SrcTileLines {
-    unsigned m; int incl, total, round;
-    long long tile;
-    __device__ __forceinline__ void open(const SrcScratch& z, long long t, int lane) {
-        tile = t; round = 0;
-        m = z.marks[t * 64 + lane];
-        incl = __popc(m);
-        for (int d = 1; d < 64; d <<= 1) {
-            const int u = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += u;
-        }
-        total = __shfl(incl, 63, 64);
-    }
-    // the start of line j = 64 * round + lane of the tile, or -1; *index = j
-    __device__ __forceinline__ int64_t next(int lane, int* index) {
-        const int j = 64 * round + lane;
-        ++round;
-        *index = j;
-        const int want = j < total ? j : total - 1;                       // (lanes without a line search too: the shuffles need every lane)
-        int lo = 0, hi = 63;                                              // the first word whose running count exceeds `want`
-        for (int step = 0; step < 6; ++step) {
-            const int mid = (lo + hi) >> 1;
-            const int c = __shfl(incl, mid, 64);
-            if (c > want) hi = mid; else lo = mid + 1;
-        }
-        unsigned mw = (unsigned)__shfl((int)m, lo, 64);
-        const int before = __shfl(incl, lo, 64) - __popc(mw);
-        for (int t = want - before; t > 0; --t) mw &= mw - 1;             // (at most 15 rounds)
-        const int bit = __ffs((int)mw) - 1;
-        return j < total ? tile * SRC_TILE + 16 * lo + bit : -1;
-    }
-};
 
 // the region of the line that starts at byte s: the last one that begins at or before it (the empty regions in front of it share its offset)
 __device__ __forceinline__ int src_region_of(const plat_source_variants_in& in, int64_t s)
@@ -214,19 +129,19 @@ __device__ __forceinline__ int src_region_of(const plat_source_variants_in& in, 
 }
 
 template <bool WRITE>
-__global__ void __launch_bounds__(SRC_WAVES * 64)
+__global__ void __launch_bounds__(TILE_WAVES * 64)
 k_src_lines(plat_source_variants_in in, plat_source_variants_out o, SrcScratch z)
 {
     if (o.status[0] == PLAT_ERR_INVALID) return;
     const int lane = threadIdx.x & 63;
-    for (long long tile = (long long)blockIdx.x * SRC_WAVES + (threadIdx.x >> 6); tile < z.tiles; tile += (long long)gridDim.x * SRC_WAVES) {
+    for (long long tile = (long long)blockIdx.x * TILE_WAVES + (threadIdx.x >> 6); tile < z.tiles; tile += (long long)gridDim.x * TILE_WAVES) {
         const long long line0 = z.tile_line[tile];
         if (z.tile_line[tile + 1] == line0) {                              // (wave-uniform: most tiles of wide lines hold no line start)
             if (!WRITE && lane == 0) z.tile_var[tile] = 0;
             continue;
         }
-        SrcTileLines L;
-        L.open(z, tile, lane);
+        TileLines L;
+        L.open(z.marks, tile, lane);
         long long run = WRITE ? z.tile_var[tile] : 0;                    // alleles in front of this round's lines
         for (int done = 0; done < L.total; done += 64) {
             int j;
@@ -247,11 +162,7 @@ k_src_lines(plat_source_variants_in in, plat_source_variants_out o, SrcScratch z
             if (!WRITE) {
                 // the round's counts per region: summed over the wave's lanes of one region first (a region's thousands of lines would
                 // otherwise meet at one address), one round per distinct region of the wave -- nearly always one
-                unsigned long long todo = __ballot(s >= 0);
-                while (todo) {                                          // (todo is the same in every lane; each round clears at least one bit)
-                    const int leader = __ffsll((long long)todo) - 1;
-                    const int kk = __shfl(k, leader, 64);
-                    const bool mine = s >= 0 && k == kk;
+                wave_groups(s >= 0, k, [&](int leader, int kk, bool mine) {
                     int v0 = mine ? n : 0, v1 = mine ? nSkipped : 0, v2 = mine ? nInvalid : 0, v3 = mine ? nOver : 0;
                     for (int d = 32; d > 0; d >>= 1) {
                         v0 += __shfl_xor(v0, d, 64); v1 += __shfl_xor(v1, d, 64); v2 += __shfl_xor(v2, d, 64); v3 += __shfl_xor(v3, d, 64);
@@ -262,14 +173,9 @@ k_src_lines(plat_source_variants_in in, plat_source_variants_out o, SrcScratch z
                         if (v2) atomicAdd(&o.region_stats[4 * kk + 2], v2);
                         if (v3) atomicAdd(&o.region_stats[4 * kk + 3], v3);
                     }
-                    todo &= ~__ballot(mine);
-                }
+                });
             }
-            int incl = n;
-            for (int d = 1; d < 64; d <<= 1) {
-                const int u = __shfl_up(incl, d, 64);
-                if (lane >= d) incl += u;
-            }
+            const int incl = wave_incl_scan(n, lane);
             if (WRITE && n) {
                 long long at = run + incl - n;
                 const uint64_t nameHash = (uint64_t)in.name_hash[k];
@@ -291,17 +197,17 @@ k_src_lines(plat_source_variants_in in, plat_source_variants_out o, SrcScratch z
     }
 }
 
-__global__ void __launch_bounds__(SRC_SCAN_THREADS)
+__global__ void __launch_bounds__(BLOCK_SCAN_THREADS)
 k_src_scan2(plat_source_variants_in in, plat_source_variants_out o, SrcScratch z)
 {
-    __shared__ long long s_wave[SRC_SCAN_THREADS / 64];
+    __shared__ long long s_wave[BLOCK_SCAN_THREADS / 64];
     if (o.status[0] == PLAT_ERR_INVALID) return;
-    const long long total = src_scan_inplace(z.tile_var, z.tiles, s_wave);
+    const long long total = block_scan_inplace<BLOCK_SCAN_THREADS>(z.tile_var, z.tiles, s_wave);
     __syncthreads();
-    src_scan_inplace(z.reg_var, in.n_regions, s_wave);
+    block_scan_inplace<BLOCK_SCAN_THREADS>(z.reg_var, in.n_regions, s_wave);
     __syncthreads();
     const long long cap = o.cap_variants;
-    for (int k = threadIdx.x; k <= in.n_regions; k += SRC_SCAN_THREADS) {
+    for (int k = threadIdx.x; k <= in.n_regions; k += BLOCK_SCAN_THREADS) {
         const long long b = k < in.n_regions ? z.reg_var[k] : total;
         o.region_begin[k] = (int32_t)(b < cap ? b : cap);                // (PLAT_ERR_OVERFLOW: clamped, nothing lies behind the capacity)
         if (k < in.n_regions) o.region_stats[4 * k] = (int32_t)(z.reg_line0[k + 1] - z.reg_line0[k]);
@@ -327,11 +233,11 @@ PLAT_EXPORT int plat_source_variants_batch(plat_ctx* ctx, const plat_source_vari
     if (q.n_regions > 0 && (!q.name_hash || !o.region_stats)) return PLAT_ERR_INVALID;
     if (q.text_len > 0 && (!q.text || ((uintptr_t)q.text & 15))) return PLAT_ERR_INVALID;
     if (o.cap_variants > 0 && (!o.pos || !o.rem_off || !o.n_rem || !o.add_off || !o.n_add || !o.hash || !o.line)) return PLAT_ERR_INVALID;
-    if (q.text_len > (int64_t)INT32_MAX - plat::SRC_TILE || o.cap_variants > INT32_MAX) return PLAT_ERR_OVERFLOW;      // (line numbers and region_begin are 32-bit)
+    if (q.text_len > (int64_t)INT32_MAX - plat::TILE_BYTES || o.cap_variants > INT32_MAX) return PLAT_ERR_OVERFLOW;      // (line numbers and region_begin are 32-bit)
     PLAT_HIP(ctx, hipSetDevice(ctx->device));
     const hipStream_t st = (hipStream_t)stream;
     plat::SrcScratch z;
-    z.tiles = (q.text_len + plat::SRC_TILE - 1) / plat::SRC_TILE;
+    z.tiles = (q.text_len + plat::TILE_BYTES - 1) / plat::TILE_BYTES;
     const size_t marksBytes = ((size_t)z.tiles * 64 * sizeof(uint16_t) + 15) & ~(size_t)15;
     const size_t perTile = ((size_t)z.tiles + 2) * sizeof(long long), perRegion = ((size_t)q.n_regions + 2) * sizeof(long long);
     const int rc = plat_reserve(ctx, ctx->srcvcf, marksBytes + 2 * perTile + 2 * perRegion);
@@ -342,22 +248,15 @@ PLAT_EXPORT int plat_source_variants_batch(plat_ctx* ctx, const plat_source_vari
     z.tile_var = (long long*)(base + marksBytes + perTile);
     z.reg_line0 = (long long*)(base + marksBytes + 2 * perTile);
     z.reg_var = (long long*)(base + marksBytes + 2 * perTile + perRegion);
-    const unsigned tileBlocks = (unsigned)std::max<long long>(1, std::min<long long>((z.tiles + plat::SRC_WAVES - 1) / plat::SRC_WAVES, plat::SRC_TILE_BLOCKS));
-    const dim3 tileThreads(plat::SRC_WAVES * 64);
-#define SRC_LAUNCH(kernel, grid, block, ...)                                            \
-    do {                                                                                \
-        PLAT_KT_BEGIN(ctx, PLAT_KT_OTHER, st);                                          \
-        hipLaunchKernelGGL(kernel, grid, block, 0, st, __VA_ARGS__);                    \
-        PLAT_KT_END(ctx, PLAT_KT_OTHER, st);                                            \
-    } while (0)
-    SRC_LAUNCH(plat::k_src_check, dim3(1), dim3(plat::SRC_SCAN_THREADS), q, o, z);
-    SRC_LAUNCH(plat::k_src_mark, dim3(tileBlocks), tileThreads, q, o, z);
-    SRC_LAUNCH(plat::k_src_scan, dim3(1), dim3(plat::SRC_SCAN_THREADS), o, z);
-    SRC_LAUNCH(plat::k_src_regions, dim3((unsigned)(q.n_regions / 256 + 1)), dim3(256), q, o, z);
-    SRC_LAUNCH(plat::k_src_lines<false>, dim3(tileBlocks), tileThreads, q, o, z);
-    SRC_LAUNCH(plat::k_src_scan2, dim3(1), dim3(plat::SRC_SCAN_THREADS), q, o, z);
-    SRC_LAUNCH(plat::k_src_lines<true>, dim3(tileBlocks), tileThreads, q, o, z);
-#undef SRC_LAUNCH
+    const unsigned tileBlocks = (unsigned)std::max<long long>(1, std::min<long long>((z.tiles + plat::TILE_WAVES - 1) / plat::TILE_WAVES, plat::TILE_GRID_CAP));
+    const dim3 tileThreads(plat::TILE_WAVES * 64);
+    PLAT_LAUNCH(ctx, PLAT_KT_OTHER, st, plat::k_src_check, dim3(1), dim3(plat::BLOCK_SCAN_THREADS), 0, q, o, z);
+    PLAT_LAUNCH(ctx, PLAT_KT_OTHER, st, plat::k_src_mark, dim3(tileBlocks), tileThreads, 0, q, o, z);
+    PLAT_LAUNCH(ctx, PLAT_KT_OTHER, st, plat::k_src_scan, dim3(1), dim3(plat::BLOCK_SCAN_THREADS), 0, o, z);
+    PLAT_LAUNCH(ctx, PLAT_KT_OTHER, st, plat::k_src_regions, dim3((unsigned)(q.n_regions / 256 + 1)), dim3(256), 0, q, o, z);
+    PLAT_LAUNCH(ctx, PLAT_KT_OTHER, st, plat::k_src_lines<false>, dim3(tileBlocks), tileThreads, 0, q, o, z);
+    PLAT_LAUNCH(ctx, PLAT_KT_OTHER, st, plat::k_src_scan2, dim3(1), dim3(plat::BLOCK_SCAN_THREADS), 0, q, o, z);
+    PLAT_LAUNCH(ctx, PLAT_KT_OTHER, st, plat::k_src_lines<true>, dim3(tileBlocks), tileThreads, 0, q, o, z);
     PLAT_HIP(ctx, hipGetLastError());
     return PLAT_OK;
 }

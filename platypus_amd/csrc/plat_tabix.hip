@@ -1,8 +1,9 @@
 // plat_tabix.hip -- tabix's iterator over inflated BGZF blocks (plat_tabix_fetch_batch, include/platypus_mi355x.h): ti_iter_read
 // (src/tabix/index.c.pysam.c:872-911) for the streams of a chunk of regions, over the bytes plat_bgzf_inflate_batch left, without the host
 // ever seeing an inflated byte but the kept lines.  The rule of one line is tabix_rule.hpp (compiled for the host too and tested there);
-// this file finds the lines, hands them to lanes, finds each stream's stop, scans and copies.  The data is cut into tiles of TBX_TILE bytes
-// = 64 aligned 16-byte words, one word per lane of a wave.  Seven launches:
+// this file finds the lines, hands them to lanes, finds each stream's stop, scans and copies.  The data is cut into tiles of TILE_BYTES
+// = 64 aligned 16-byte words, one word per lane of a wave; the tile geometry, the newline mask of a word, the rank of a byte among the
+// marks, the workgroup scan and the hand-out of a tile's lines to lanes are wave_tiles.hpp's (shared with plat_sourcevcf.hip).  Seven launches:
 //   k_tbx_check    one workgroup: the geometry checked; per chunk its bytes [lo, hi), its first offset and its stop as offsets into data; the
 //                  streams' keys, counters and the status block reset
 //   k_tbx_mark     one wave per tile: each lane loads its word (one aligned 16-byte load), compares 16 bytes with '\n': nl [word] (16 bits, the
@@ -19,17 +20,13 @@
 //   k_tbx_copy     one wave per tile with kept bytes: one lane per line finds its place, then the WAVE copies each kept line, 16 bytes per
 //                  lane with aligned stores, and ends it with '\n'
 // A line belongs to the tile its first byte lies in, however long it is.  Errors go to the status block; nothing traps.
-// The workgroup scan and the hand-out of a tile's lines to lanes are plat_sourcevcf.hip's, restated here (its kernels are left as they are).
 #include <algorithm>
 
 #include "plat_internal.hpp"
 #include "tabix_rule.hpp"
+#include "wave_tiles.hpp"
 
 namespace plat {
-constexpr int TBX_TILE = 1024;                            // bytes of data per tile = 64 lanes x 16 bytes
-constexpr int TBX_WAVES = 4;                              // waves (tiles in flight) per workgroup of the tile kernels
-constexpr int TBX_SCAN_THREADS = 1024;
-constexpr int TBX_TILE_BLOCKS = 4096;                     // the tile kernels' grids are capped (grid-stride over tiles)
 constexpr unsigned long long TBX_NO_KEY = ~0ull - 1;      // (even: an odd key is a refusal)
 // a stream's key: 8 * (index of a line among the call's lines) + what happens there; line j counts while 8 j + 4 <= key
 constexpr int TBX_AT_CHUNK = 1, TBX_AT_STOP = 2, TBX_AT_REFUSE = 3, TBX_BEHIND = 7;
@@ -46,38 +43,6 @@ struct TbxScratch {
     long long tiles;
 };
 
-// a[0 .. n) to its exclusive prefix sums in place, by all TBX_SCAN_THREADS threads of one workgroup; returns the total
-__device__ long long tbx_scan_inplace(long long* a, long long n, long long* s_wave)
-{
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    long long run = 0;
-    for (long long t0 = 0; t0 < n; t0 += TBX_SCAN_THREADS * 4) {
-        const long long i0 = t0 + (long long)tid * 4;
-        long long v[4], sum = 0;
-        for (int k = 0; k < 4; ++k) { v[k] = i0 + k < n ? a[i0 + k] : 0; sum += v[k]; }
-        long long incl = sum;
-        for (int d = 1; d < 64; d <<= 1) {
-            const long long u = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += u;
-        }
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        long long at = run + incl - sum, all = 0;
-        for (int w = 0; w < TBX_SCAN_THREADS / 64; ++w) {
-            if (w < wave) at += s_wave[w];
-            all += s_wave[w];
-        }
-        for (int k = 0; k < 4; ++k) {
-            if (i0 + k >= n) break;
-            a[i0 + k] = at;
-            at += v[k];
-        }
-        run += all;
-        __syncthreads();                                                // (s_wave is rewritten by the next round)
-    }
-    return run;
-}
-
 // the last k in [0, n) with a[k] <= x (a ascending), or -1
 template <class T> __device__ __forceinline__ int tbx_last_le(const T* __restrict__ a, int n, long long x)
 {
@@ -91,7 +56,7 @@ template <class T> __device__ __forceinline__ int tbx_last_le(const T* __restric
 
 __device__ __forceinline__ void tbx_lower(unsigned long long* key, unsigned long long k) { if (*key > k) atomicMin(key, k); }
 
-__global__ void __launch_bounds__(TBX_SCAN_THREADS)
+__global__ void __launch_bounds__(BLOCK_SCAN_THREADS)
 k_tbx_check(plat_tabix_fetch_in in, plat_tabix_fetch_out o, TbxScratch z)
 {
     __shared__ int s_bad;
@@ -101,7 +66,7 @@ k_tbx_check(plat_tabix_fetch_in in, plat_tabix_fetch_out o, TbxScratch z)
     bool bad = false;
     const long long total = in.n_blocks ? in.out_off[in.n_blocks] : 0;
     if (total < 0 || total > in.data_len) bad = true;
-    for (int s = tid; s <= in.n_streams; s += TBX_SCAN_THREADS) {
+    for (int s = tid; s <= in.n_streams; s += BLOCK_SCAN_THREADS) {
         const int a = in.stream_chunk_begin[s];
         if (a < 0 || a > in.n_chunks || (s == 0 && a != 0) || (s == in.n_streams && a != in.n_chunks)) bad = true;
         if (s < in.n_streams) {
@@ -110,7 +75,7 @@ k_tbx_check(plat_tabix_fetch_in in, plat_tabix_fetch_out o, TbxScratch z)
             z.stream_bytes[s] = 0;
         }
     }
-    for (int c = tid; c < in.n_chunks && !bad; c += TBX_SCAN_THREADS) {
+    for (int c = tid; c < in.n_chunks && !bad; c += BLOCK_SCAN_THREADS) {
         const int b0 = in.chunk_blk_first[c], b1 = in.chunk_blk_end[c], sb = in.chunk_stop_blk[c];
         if (b0 < 0 || b1 < b0 || b1 > in.n_blocks || sb < -1 || sb >= in.n_blocks || in.chunk_first_uoffset[c] < 0 || in.chunk_stop_uoffset[c] < 0 ||
             (c > 0 && b0 < in.chunk_blk_end[c - 1])) { bad = true; break; }
@@ -123,33 +88,23 @@ k_tbx_check(plat_tabix_fetch_in in, plat_tabix_fetch_out o, TbxScratch z)
     if (bad) s_bad = 1;
     __syncthreads();
     if (!s_bad)                                                         // (refused as invalid: the status block is all that is written)
-        for (int k = tid; k < 2 * in.n_streams; k += TBX_SCAN_THREADS) o.stream_counts[k] = 0;
+        for (int k = tid; k < 2 * in.n_streams; k += BLOCK_SCAN_THREADS) o.stream_counts[k] = 0;
     if (tid == 0) {
         o.status[0] = s_bad ? PLAT_ERR_INVALID : 0;
         o.status[1] = -1; o.status[2] = 0; o.status[3] = 0;
     }
 }
 
-__global__ void __launch_bounds__(TBX_WAVES * 64)
+__global__ void __launch_bounds__(TILE_WAVES * 64)
 k_tbx_mark(plat_tabix_fetch_in in, plat_tabix_fetch_out o, TbxScratch z)
 {
     if (o.status[0] == PLAT_ERR_INVALID) return;
     const int lane = threadIdx.x & 63;
     const long long total = in.n_blocks ? in.out_off[in.n_blocks] : 0;
-    for (long long tile = (long long)blockIdx.x * TBX_WAVES + (threadIdx.x >> 6); tile < z.tiles; tile += (long long)gridDim.x * TBX_WAVES) {
-        const long long tileAt = tile * TBX_TILE, at = tileAt + 16 * lane;
-        // newlines of this lane's word: an aligned 16-byte load that may run up to 15 bytes past the data (inside PLAT_BLOB_PAD)
-        unsigned nl = 0;
-        if (at < total) {
-            const uint4 w = *reinterpret_cast<const uint4*>(in.data + at);
-            const unsigned v[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-            for (int j = 0; j < 16; ++j)
-                if (((v[j >> 2] >> (8 * (j & 3))) & 0xffu) == '\n' && at + j < total) nl |= 1u << j;
-        }
-        unsigned carry = __shfl_up(nl >> 15, 1, 64);
-        if (lane == 0) carry = (tileAt > 0 && tileAt - 1 < total && in.data[tileAt - 1] == '\n') ? 1u : 0u;
-        const unsigned behind = ((nl << 1) | carry) & 0xffffu;
+    for (long long tile = (long long)blockIdx.x * TILE_WAVES + (threadIdx.x >> 6); tile < z.tiles; tile += (long long)gridDim.x * TILE_WAVES) {
+        const long long tileAt = tile * TILE_BYTES, at = tileAt + 16 * lane;
+        const unsigned nl = word_newlines(in.data, at, 0, total);
+        const unsigned behind = behind_newlines(nl, lane, (lane == 0 && tileAt > 0 && tileAt - 1 < total && in.data[tileAt - 1] == '\n') ? 1u : 0u);
         // line starts: per chunk that meets this word, its first offset and the bytes behind its newlines, in front of its stop
         unsigned m = 0;
         if (at < total) {
@@ -170,69 +125,24 @@ k_tbx_mark(plat_tabix_fetch_in in, plat_tabix_fetch_out o, TbxScratch z)
     }
 }
 
-// set bits of `marks` in front of byte x of the data (x >= the tiles' bytes: all of them)
-__device__ __forceinline__ long long tbx_rank(const uint16_t* __restrict__ marks, const long long* __restrict__ tile_run, long long tiles, long long x)
-{
-    const long long tile = x / TBX_TILE;
-    if (tile >= tiles) return tile_run[tiles];
-    long long rank = tile_run[tile];
-    const int word = (int)((x - tile * TBX_TILE) >> 4), bit = (int)(x & 15);
-    for (int w = 0; w < word; ++w) rank += __popc((unsigned)marks[tile * 64 + w]);
-    return rank + __popc((unsigned)marks[tile * 64 + word] & ((1u << bit) - 1u));
-}
-
-__global__ void __launch_bounds__(TBX_SCAN_THREADS)
+__global__ void __launch_bounds__(BLOCK_SCAN_THREADS)
 k_tbx_scan(plat_tabix_fetch_in in, plat_tabix_fetch_out o, TbxScratch z)
 {
-    __shared__ long long s_wave[TBX_SCAN_THREADS / 64];
+    __shared__ long long s_wave[BLOCK_SCAN_THREADS / 64];
     if (o.status[0] == PLAT_ERR_INVALID) return;
-    const long long lines = tbx_scan_inplace(z.tile_line, z.tiles, s_wave);
+    const long long lines = block_scan_inplace<BLOCK_SCAN_THREADS>(z.tile_line, z.tiles, s_wave);
     __syncthreads();
-    const long long nls = tbx_scan_inplace(z.tile_nl, z.tiles, s_wave);
+    const long long nls = block_scan_inplace<BLOCK_SCAN_THREADS>(z.tile_nl, z.tiles, s_wave);
     if (threadIdx.x == 0) { z.tile_line[z.tiles] = lines; z.tile_nl[z.tiles] = nls; }
     __syncthreads();
     // a chunk without a line whose first offset lies past its stop, and which is not its stream's last: the stream is refused there
-    for (int c = threadIdx.x; c < in.n_chunks; c += TBX_SCAN_THREADS) {
+    for (int c = threadIdx.x; c < in.n_chunks; c += BLOCK_SCAN_THREADS) {
         const long long f = z.c_first[c];
         if (f <= z.c_stop[c]) continue;
         const int s = tbx_last_le(in.stream_chunk_begin, in.n_streams, c);
-        if (c + 1 < in.stream_chunk_begin[s + 1]) tbx_lower(&z.key[s], 8ull * (unsigned long long)tbx_rank(z.marks, z.tile_line, z.tiles, f) + TBX_AT_CHUNK);
+        if (c + 1 < in.stream_chunk_begin[s + 1]) tbx_lower(&z.key[s], 8ull * (unsigned long long)marks_rank(z.marks, z.tile_line, z.tiles, f) + TBX_AT_CHUNK);
     }
 }
-
-// The lines of one tile, handed to the lanes of one wave 64 at a time.  Every lane of the wave must call next() together (shuffles).
-struct TbxTileLines {
-    unsigned m; int incl, total, round;
-    long long tile;
-    __device__ __forceinline__ void open(const TbxScratch& z, long long t, int lane) {
-        tile = t; round = 0;
-        m = z.marks[t * 64 + lane];
-        incl = __popc(m);
-        for (int d = 1; d < 64; d <<= 1) {
-            const int u = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += u;
-        }
-        total = __shfl(incl, 63, 64);
-    }
-    // the start of line j = 64 * round + lane of the tile, or -1; *index = j
-    __device__ __forceinline__ long long next(int lane, int* index) {
-        const int j = 64 * round + lane;
-        ++round;
-        *index = j;
-        const int want = j < total ? j : total - 1;                       // (lanes without a line search too: the shuffles need every lane)
-        int lo = 0, hi = 63;                                              // the first word whose running count exceeds `want`
-        for (int step = 0; step < 6; ++step) {
-            const int mid = (lo + hi) >> 1;
-            const int c = __shfl(incl, mid, 64);
-            if (c > want) hi = mid; else lo = mid + 1;
-        }
-        unsigned mw = (unsigned)__shfl((int)m, lo, 64);
-        const int before = __shfl(incl, lo, 64) - __popc(mw);
-        for (int t = want - before; t > 0; --t) mw &= mw - 1;             // (at most 15 rounds)
-        const int bit = __ffs((int)mw) - 1;
-        return j < total ? tile * TBX_TILE + 16 * lo + bit : -1;
-    }
-};
 
 // the line that starts at byte s: its chunk, its stream, its end (its newline, or the end of its chunk's bytes) and the offset behind it
 struct TbxLine { int chunk, stream; long long end, behind; bool lastOfChunk; };
@@ -244,10 +154,10 @@ __device__ __forceinline__ TbxLine tbx_line_at(const plat_tabix_fetch_in& in, co
     L.stream = max(tbx_last_le(in.stream_chunk_begin, in.n_streams, L.chunk), 0);
     const long long hi = z.c_hi[L.chunk];
     // the newline that ends it is newline number r of the data, r = the newlines in front of s
-    const long long r = tbx_rank(z.nl, z.tile_nl, z.tiles, s);
+    const long long r = marks_rank(z.nl, z.tile_nl, z.tiles, s);
     long long e = hi;
     if (r < z.tile_nl[z.tiles]) {
-        long long t = s / TBX_TILE;
+        long long t = s / TILE_BYTES;
         if (r >= z.tile_nl[t + 1]) {                                        // not in the line's own tile: the last tile with tile_nl <= r
             long long lo = t + 1, up = z.tiles;
             while (lo < up) {
@@ -256,14 +166,14 @@ __device__ __forceinline__ TbxLine tbx_line_at(const plat_tabix_fetch_in& in, co
             }
             t = lo - 1;
         }
-        if (t * TBX_TILE < hi) {
+        if (t * TILE_BYTES < hi) {
             int want = (int)(r - z.tile_nl[t]);
             for (int w = 0; w < 64; ++w) {
                 unsigned mw = z.nl[t * 64 + w];
                 const int c = __popc(mw);
                 if (want >= c) { want -= c; continue; }
                 for (; want > 0; --want) mw &= mw - 1;
-                const long long at = t * TBX_TILE + 16 * w + (__ffs((int)mw) - 1);
+                const long long at = t * TILE_BYTES + 16 * w + (__ffs((int)mw) - 1);
                 if (at < hi) e = at;
                 break;
             }
@@ -281,16 +191,16 @@ __device__ __forceinline__ int tbx_verdict(const plat_tabix_fetch_in& in, const 
     return tbxrule::line_verdict(in.data, s, L.end, in.names + n0, in.name_off[L.stream + 1] - n0, in.beg[L.stream], in.end[L.stream]);
 }
 
-__global__ void __launch_bounds__(TBX_WAVES * 64)
+__global__ void __launch_bounds__(TILE_WAVES * 64)
 k_tbx_verdict(plat_tabix_fetch_in in, plat_tabix_fetch_out o, TbxScratch z)
 {
     if (o.status[0] == PLAT_ERR_INVALID) return;
     const int lane = threadIdx.x & 63;
-    for (long long tile = (long long)blockIdx.x * TBX_WAVES + (threadIdx.x >> 6); tile < z.tiles; tile += (long long)gridDim.x * TBX_WAVES) {
+    for (long long tile = (long long)blockIdx.x * TILE_WAVES + (threadIdx.x >> 6); tile < z.tiles; tile += (long long)gridDim.x * TILE_WAVES) {
         const long long line0 = z.tile_line[tile];
         if (z.tile_line[tile + 1] == line0) continue;                      // (wave-uniform: most tiles of wide lines hold no line start)
-        TbxTileLines T;
-        T.open(z, tile, lane);
+        TileLines T;
+        T.open(z.marks, tile, lane);
         for (int done = 0; done < T.total; done += 64) {
             int j;
             const long long s = T.next(lane, &j);
@@ -323,17 +233,17 @@ __device__ __forceinline__ TbxWorth tbx_worth(const plat_tabix_fetch_in& in, con
     return w;
 }
 
-__global__ void __launch_bounds__(TBX_WAVES * 64)
+__global__ void __launch_bounds__(TILE_WAVES * 64)
 k_tbx_count(plat_tabix_fetch_in in, plat_tabix_fetch_out o, TbxScratch z)
 {
     if (o.status[0] == PLAT_ERR_INVALID) return;
     const int lane = threadIdx.x & 63;
-    for (long long tile = (long long)blockIdx.x * TBX_WAVES + (threadIdx.x >> 6); tile < z.tiles; tile += (long long)gridDim.x * TBX_WAVES) {
+    for (long long tile = (long long)blockIdx.x * TILE_WAVES + (threadIdx.x >> 6); tile < z.tiles; tile += (long long)gridDim.x * TILE_WAVES) {
         const long long line0 = z.tile_line[tile];
         long long tileBytes = 0;
         if (z.tile_line[tile + 1] != line0) {
-            TbxTileLines T;
-            T.open(z, tile, lane);
+            TileLines T;
+            T.open(z.marks, tile, lane);
             for (int done = 0; done < T.total; done += 64) {
                 int j;
                 const long long s = T.next(lane, &j);
@@ -345,11 +255,7 @@ k_tbx_count(plat_tabix_fetch_in in, plat_tabix_fetch_out o, TbxScratch z)
                     w = tbx_worth(in, z, L, s, line0 + j);
                 }
                 // the round's counts per stream: summed over the wave's lanes of one stream first, one round per distinct stream of the wave
-                unsigned long long todo = __ballot(s >= 0 && w.walked);
-                while (todo) {                                          // (todo is the same in every lane; each round clears at least one bit)
-                    const int leader = __ffsll((long long)todo) - 1;
-                    const int kk = __shfl(k, leader, 64);
-                    const bool mine = s >= 0 && w.walked && k == kk;
+                wave_groups(s >= 0 && w.walked, k, [&](int leader, int kk, bool mine) {
                     int v0 = mine ? w.walked : 0, v1 = mine ? w.kept : 0;
                     long long v2 = mine ? w.bytes : 0;
                     for (int d = 32; d > 0; d >>= 1) { v0 += __shfl_xor(v0, d, 64); v1 += __shfl_xor(v1, d, 64); v2 += __shfl_xor(v2, d, 64); }
@@ -359,29 +265,28 @@ k_tbx_count(plat_tabix_fetch_in in, plat_tabix_fetch_out o, TbxScratch z)
                         if (v2) atomicAdd((unsigned long long*)&z.stream_bytes[kk], (unsigned long long)v2);
                     }
                     tileBytes += v2;
-                    todo &= ~__ballot(mine);
-                }
+                });
             }
         }
         if (lane == 0) z.tile_bytes[tile] = tileBytes;
     }
 }
 
-__global__ void __launch_bounds__(TBX_SCAN_THREADS)
+__global__ void __launch_bounds__(BLOCK_SCAN_THREADS)
 k_tbx_scan2(plat_tabix_fetch_in in, plat_tabix_fetch_out o, TbxScratch z)
 {
-    __shared__ long long s_wave[TBX_SCAN_THREADS / 64];
+    __shared__ long long s_wave[BLOCK_SCAN_THREADS / 64];
     __shared__ int s_refused;
     __shared__ unsigned long long s_kept;
     if (o.status[0] == PLAT_ERR_INVALID) return;
     if (threadIdx.x == 0) { s_refused = INT32_MAX; s_kept = 0; }
-    const long long total = tbx_scan_inplace(z.tile_bytes, z.tiles, s_wave);
+    const long long total = block_scan_inplace<BLOCK_SCAN_THREADS>(z.tile_bytes, z.tiles, s_wave);
     __syncthreads();
-    tbx_scan_inplace(z.stream_bytes, in.n_streams, s_wave);
+    block_scan_inplace<BLOCK_SCAN_THREADS>(z.stream_bytes, in.n_streams, s_wave);
     __syncthreads();
     const long long cap = o.cap_text;
     unsigned long long kept = 0;
-    for (int s = threadIdx.x; s <= in.n_streams; s += TBX_SCAN_THREADS) {
+    for (int s = threadIdx.x; s <= in.n_streams; s += BLOCK_SCAN_THREADS) {
         const long long b = s < in.n_streams ? z.stream_bytes[s] : total;
         o.stream_text_off[s] = b < cap ? b : cap;                        // (PLAT_ERR_OVERFLOW: clamped, nothing lies behind the capacity)
         if (s < in.n_streams) {
@@ -418,28 +323,24 @@ __device__ __forceinline__ void tbx_wave_copy(uint8_t* __restrict__ dst, const u
     if (tail + lane < n) dst[tail + lane] = src[tail + lane];
 }
 
-__global__ void __launch_bounds__(TBX_WAVES * 64)
+__global__ void __launch_bounds__(TILE_WAVES * 64)
 k_tbx_copy(plat_tabix_fetch_in in, plat_tabix_fetch_out o, TbxScratch z)
 {
     if (o.status[0] == PLAT_ERR_INVALID) return;
     const int lane = threadIdx.x & 63;
     const long long cap = o.cap_text;
-    for (long long tile = (long long)blockIdx.x * TBX_WAVES + (threadIdx.x >> 6); tile < z.tiles; tile += (long long)gridDim.x * TBX_WAVES) {
+    for (long long tile = (long long)blockIdx.x * TILE_WAVES + (threadIdx.x >> 6); tile < z.tiles; tile += (long long)gridDim.x * TILE_WAVES) {
         long long run = z.tile_bytes[tile];
         if (z.tile_bytes[tile + 1] == run) continue;                       // (wave-uniform: no kept line starts here)
         const long long line0 = z.tile_line[tile];
-        TbxTileLines T;
-        T.open(z, tile, lane);
+        TileLines T;
+        T.open(z.marks, tile, lane);
         for (int done = 0; done < T.total; done += 64) {
             int j;
             const long long s = T.next(lane, &j);
             long long n = 0;
             if (s >= 0) n = tbx_worth(in, z, tbx_line_at(in, z, s), s, line0 + j).bytes;
-            long long incl = n;
-            for (int d = 1; d < 64; d <<= 1) {
-                const long long u = __shfl_up(incl, d, 64);
-                if (lane >= d) incl += u;
-            }
+            const long long incl = wave_incl_scan(n, lane);
             const long long at = run + incl - n;
             unsigned long long todo = __ballot(n > 0);
             while (todo) {                                                // one kept line per round, copied by the whole wave
@@ -473,7 +374,7 @@ PLAT_EXPORT int plat_tabix_fetch_batch(plat_ctx* ctx, const plat_tabix_fetch_in*
     PLAT_HIP(ctx, hipSetDevice(ctx->device));
     const hipStream_t st = (hipStream_t)stream;
     plat::TbxScratch z;
-    z.tiles = q.n_blocks ? (q.data_len + plat::TBX_TILE - 1) / plat::TBX_TILE : 0;
+    z.tiles = q.n_blocks ? (q.data_len + plat::TILE_BYTES - 1) / plat::TILE_BYTES : 0;
     const size_t marksBytes = ((size_t)z.tiles * 64 * sizeof(uint16_t) + 15) & ~(size_t)15;
     const size_t perTile = ((size_t)z.tiles + 2) * sizeof(long long), perChunk = ((size_t)q.n_chunks + 2) * sizeof(long long);
     const size_t perStream = ((size_t)q.n_streams + 2) * sizeof(long long);
@@ -491,22 +392,15 @@ PLAT_EXPORT int plat_tabix_fetch_batch(plat_ctx* ctx, const plat_tabix_fetch_in*
     z.c_stop = (long long*)base; base += perChunk;
     z.key = (unsigned long long*)base; base += perStream;
     z.stream_bytes = (long long*)base;
-    const unsigned tileBlocks = (unsigned)std::max<long long>(1, std::min<long long>((z.tiles + plat::TBX_WAVES - 1) / plat::TBX_WAVES, plat::TBX_TILE_BLOCKS));
-    const dim3 tileThreads(plat::TBX_WAVES * 64);
-#define TBX_LAUNCH(kernel, grid, block, ...)                                            \
-    do {                                                                                \
-        PLAT_KT_BEGIN(ctx, PLAT_KT_OTHER, st);                                          \
-        hipLaunchKernelGGL(kernel, grid, block, 0, st, __VA_ARGS__);                    \
-        PLAT_KT_END(ctx, PLAT_KT_OTHER, st);                                            \
-    } while (0)
-    TBX_LAUNCH(plat::k_tbx_check, dim3(1), dim3(plat::TBX_SCAN_THREADS), q, o, z);
-    TBX_LAUNCH(plat::k_tbx_mark, dim3(tileBlocks), tileThreads, q, o, z);
-    TBX_LAUNCH(plat::k_tbx_scan, dim3(1), dim3(plat::TBX_SCAN_THREADS), q, o, z);
-    TBX_LAUNCH(plat::k_tbx_verdict, dim3(tileBlocks), tileThreads, q, o, z);
-    TBX_LAUNCH(plat::k_tbx_count, dim3(tileBlocks), tileThreads, q, o, z);
-    TBX_LAUNCH(plat::k_tbx_scan2, dim3(1), dim3(plat::TBX_SCAN_THREADS), q, o, z);
-    TBX_LAUNCH(plat::k_tbx_copy, dim3(tileBlocks), tileThreads, q, o, z);
-#undef TBX_LAUNCH
+    const unsigned tileBlocks = (unsigned)std::max<long long>(1, std::min<long long>((z.tiles + plat::TILE_WAVES - 1) / plat::TILE_WAVES, plat::TILE_GRID_CAP));
+    const dim3 tileThreads(plat::TILE_WAVES * 64);
+    PLAT_LAUNCH(ctx, PLAT_KT_OTHER, st, plat::k_tbx_check, dim3(1), dim3(plat::BLOCK_SCAN_THREADS), 0, q, o, z);
+    PLAT_LAUNCH(ctx, PLAT_KT_OTHER, st, plat::k_tbx_mark, dim3(tileBlocks), tileThreads, 0, q, o, z);
+    PLAT_LAUNCH(ctx, PLAT_KT_OTHER, st, plat::k_tbx_scan, dim3(1), dim3(plat::BLOCK_SCAN_THREADS), 0, q, o, z);
+    PLAT_LAUNCH(ctx, PLAT_KT_OTHER, st, plat::k_tbx_verdict, dim3(tileBlocks), tileThreads, 0, q, o, z);
+    PLAT_LAUNCH(ctx, PLAT_KT_OTHER, st, plat::k_tbx_count, dim3(tileBlocks), tileThreads, 0, q, o, z);
+    PLAT_LAUNCH(ctx, PLAT_KT_OTHER, st, plat::k_tbx_scan2, dim3(1), dim3(plat::BLOCK_SCAN_THREADS), 0, q, o, z);
+    PLAT_LAUNCH(ctx, PLAT_KT_OTHER, st, plat::k_tbx_copy, dim3(tileBlocks), tileThreads, 0, q, o, z);
     PLAT_HIP(ctx, hipGetLastError());
     return PLAT_OK;
 }

@@ -104,6 +104,28 @@ def test_route_partitions_streams_stably(n_samples, n_groups, id_len):
         _check(got, recs, [(R.ROUTED, 0)] * n, sb, 3, off, end)
 
 
+def test_route_scans_take_a_second_round():
+    """One round of the workgroup scan is 4096 elements: 4100 streams of 0, 1, 2 and T + 1 records (a tile table and, with 3 samples, a
+    table of 12 300 stream-sample counts, both longer than one round)."""
+    eng = H.get_engine()
+    n_streams, n_samples, n_groups = 4100, 3, 6
+    rng = np.random.default_rng(n_streams)
+    ids = _ids(n_groups, rng, 1, 8)
+    samples = [g % n_samples for g in range(n_groups)]
+    sb = np.concatenate([[0], np.cumsum([(0, 1, 2, T + 1)[k % 4] for k in range(n_streams)])])
+    n = int(sb[-1])
+    groups = rng.integers(0, n_groups, size=n)
+    f = R.fixed_part(l_seq=3, n_cig=1, name=b"\0")
+    by_group = [f + R.rg(i) for i in ids]
+    recs = [by_group[int(g)] for g in groups]
+    table = R.table_of(ids, samples)
+    assert [R.verdict(recs[i], table) for i in range(0, n, 997)] == [(R.ROUTED, samples[int(groups[i])]) for i in range(0, n, 997)]
+    blob, off, end = _blob(recs, 2)
+    got = eng.bam_route(blob, off, end, sb, ids, samples, n_samples)
+    _check(got, recs, [(R.ROUTED, samples[int(g)]) for g in groups], sb, n_samples, off, end)
+    assert len(got["out_begin"]) == n_streams * n_samples + 1 and int(got["status"][2]) == n == 1025 * (T + 4)
+
+
 def test_refusals_name_the_lowest_record_and_route_the_others():
     eng = H.get_engine()
     cases = dict(R.hand_records())

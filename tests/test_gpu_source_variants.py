@@ -12,7 +12,7 @@ from tests import source_golden as S
 
 pytestmark = pytest.mark.gpu
 
-TILE = 1024                                              # bytes of text per wave of the kernel (SRC_TILE, plat_sourcevcf.hip)
+TILE = 1024                                              # bytes of text per wave of the kernel (TILE_BYTES, csrc/wave_tiles.hpp)
 
 
 @pytest.fixture(scope="module")
@@ -109,6 +109,28 @@ def test_wide_lines_empty_regions_and_many_lines(eng, host):
     assert [int(x) for x in d["stats"][:, 0]] == [3, 0, 2, 1, 300, 1, 0, 0] and int(d["line"][-1]) == 0
     check(eng, host, [], [])
     check(eng, host, [b"", b""], ["20", "21"])
+
+
+def test_scans_take_a_second_round(eng, host):
+    """One round of the workgroup scan is 4096 elements.  More tiles than that, with lines in the tiles of the second round; then more regions
+    than that (the region scan's second round, the regions' first lines found by more than one workgroup)."""
+    ROUND = 4096
+    wide = line(500, b"A", b"G", tail=b"\tQ\tPASS\tX" + b"\t0/1" * 17499)
+    front = [wide * 30, wide * 29]
+    used = sum(len(r) for r in front)
+    short = line(503, b"T", b"C", tail=b"\tQ\tPASS\t")
+    filler = short[:-1] + b"x" * (ROUND * TILE + 5 - used - len(short)) + b"\n"      # ends five bytes into tile 4096
+    narrow = line(501, b"C", b"CT") + line(502, b"G", b"T,A")
+    last = line(504, b"A", b"T", tail=b"\tQ\tPASS\t" + b"x" * 1100)
+    regions = front + [filler + narrow + last]
+    assert used + len(filler) == ROUND * TILE + 5 and (ROUND + 1) * TILE < sum(len(r) for r in regions) < (ROUND + 2) * TILE
+    d = check(eng, host, regions, ["20", "1", "20"])
+    assert [int(x) for x in d["stats"][:, 0]] == [30, 29, 4] and int(d["status"][2]) == 64
+    assert [int(x) for x in d["line"][-4:]] == [1, 2, 2, 3] and int(d["rem_off"][-4]) > ROUND * TILE
+    many = [b"" if k % 7 == 0 else line(100 + k, b"ACGT"[k % 4:k % 4 + 1], b"ACGT"[(k + 1) % 4:(k + 1) % 4 + 1] + (b",N" if k % 5 == 0 else b""))
+            for k in range(ROUND + 4)]
+    d = check(eng, host, many, ["20", "1", "X", "20"] * (ROUND // 4 + 1))
+    assert int(d["status"][3]) == sum(1 for k in range(ROUND + 4) if k % 7) and len(d["region_begin"]) == ROUND + 5
 
 
 def test_capacity_and_refused_lines(eng, host):

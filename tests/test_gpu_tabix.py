@@ -71,14 +71,41 @@ def test_edge_streams_on_the_device(eng, payload):
     same(fetch(eng, streams), want)
 
 
+def many_streams(n):
+    """n streams of one to four lines in blocks of 1 to 50 bytes; every third fetches behind its lines."""
+    line = b"20\t100\t.\tA\tC\t.\t.\tDP=1\n"
+    return [(b"20", 0 if k % 3 else 100, 1000, T.cut(line * (1 + k % 4), 1 + k % 50, [(0, None)])) for k in range(n)]
+
+
 def test_degenerate_batches(eng):
     same(fetch(eng, []), {"text": b"", "off": [0], "counts": [], "status": [0, -1, 0, 0]})
     empty = (b"20", 0, 100, [])
     same(fetch(eng, [empty, empty, empty]), T.mirror([empty] * 3))
-    line = b"20\t100\t.\tA\tC\t.\t.\tDP=1\n"
-    many = [(b"20", 0 if k % 3 else 100, 1000, T.cut(line * (1 + k % 4), 1 + k % 50, [(0, None)])) for k in range(700)]
+    many = many_streams(700)
     want = T.mirror(many)
     assert want["status"][2] == sum(1 + k % 4 for k in range(700) if k % 3)
+    same(fetch(eng, many), want)
+
+
+def test_scans_take_a_second_round(eng):
+    """One round of the workgroup scan is 4096 elements.  One stream of more tiles (1024 bytes) than that, with kept and skipped lines that
+    start in the tiles of the second round; then more streams than that."""
+    ROUND, TILE = 4096, 1024
+    wide = lambda pos: b"20\t%d\t.\tA\tC\t.\t.\tDP=1\tGT" % pos + b"\t0/1" * 17499 + b"\n"
+    front = b"".join(wide(10 if k % 3 == 2 else 100) for k in range(59))                  # every third lies in front of the fetch: skipped
+    short = b"20\t100\t.\tA\tC\t.\t.\tDP=1\t\n"
+    filler = short[:-1] + b"x" * (ROUND * TILE + 5 - len(front) - len(short)) + b"\n"    # ends five bytes into tile 4096
+    behind = [b"20\t101\t.\tG\tT\t.\t.\tDP=2\n", b"20\t11\t.\tG\tT\t.\t.\tDP=3\n", b"20\t102\t.\tGA\tG\t.\t.\tDP=4\n",
+              b"20\t103\t.\tA\tT\t.\t.\tDP=5\t" + b"x" * 1100 + b"\n"]
+    text = front + filler + b"".join(behind)
+    assert len(front) + len(filler) == ROUND * TILE + 5 and (ROUND + 1) * TILE < len(text) < (ROUND + 2) * TILE
+    stream = (b"20", 50, 1000, T.cut(text, 65536, [(0, None)]))
+    want = T.mirror([stream])
+    assert want["counts"] == [64, 44] and want["status"][0] == 0 and want["text"].endswith(filler + behind[0] + behind[2] + behind[3])
+    same(fetch(eng, [stream]), want)
+    many = many_streams(ROUND + 4)
+    want = T.mirror(many)
+    assert want["status"][2] == sum(1 + k % 4 for k in range(ROUND + 4) if k % 3)
     same(fetch(eng, many), want)
 
 
