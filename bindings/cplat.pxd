@@ -369,6 +369,19 @@ cdef extern from "platypus_mi355x.h":
         int64_t* status
     int plat_bgzf_inflate_batch(plat_ctx* ctx, int n_blocks, const uint8_t* blob, int64_t blob_len, const int64_t* blk_off,
                                 const int64_t* blk_limit, const plat_bgzf_inflate_out* out, void* stream) nogil
+    # ---- record text deflated to BGZF blocks on the device (the .gz output)
+    ctypedef struct plat_bgzf_deflate_in:
+        const uint8_t* text
+        int64_t text_len
+        int32_t n_pieces
+        int32_t level
+        const int64_t* piece_off
+    ctypedef struct plat_bgzf_deflate_out:
+        int64_t cap_bytes
+        uint8_t* data
+        int64_t* piece_out_off
+        int64_t* status
+    int plat_bgzf_deflate_batch(plat_ctx* ctx, const plat_bgzf_deflate_in* inp, const plat_bgzf_deflate_out* out, void* stream) nogil
     ctypedef struct plat_bam_find_in:
         int32_t n_streams
         int32_t n_chunks

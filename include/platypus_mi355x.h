@@ -683,6 +683,53 @@ typedef struct plat_bgzf_inflate_out {
 int plat_bgzf_inflate_batch(plat_ctx* ctx, int n_blocks, const uint8_t* blob, int64_t blob_len, const int64_t* blk_off,
                             const int64_t* blk_limit /* may be NULL */, const plat_bgzf_inflate_out* out, void* stream);
 
+/* ---- record text deflated to BGZF blocks on the device ---------------------------------------------------
+ * Replaces the gzip stream the reference writes when --output ends in .gz (filez.Open, variantcaller.pyx:951-956) by BGZF: a valid
+ * multi-member gzip file whose blocks are independent and concatenate.  The encoder is the inverse of plat_bgzf_inflate_batch above and
+ * is written from RFC 1951, RFC 1952 and SAM specification 4.1; csrc/bgzf_deflate.hpp holds the same rule serially and gives the same
+ * bytes.
+ *
+ * Pieces and blocks.  The text is cut into n_pieces pieces, piece i being text[piece_off[i] .. piece_off[i + 1]) -- piece_off ascending
+ * from 0, the last at most text_len; a piece is one region's record text.  Each piece is cut into blocks of 0xff00 payload bytes, the
+ * last block of a piece possibly shorter.  An empty piece gives no block; a block never spans pieces.
+ * A block is the 18-byte header 1f 8b 08 04, MTIME 0, XFL 0, OS ff, XLEN 6, 'B' 'C', SLEN 2, BSIZE = block length - 1; ONE deflate block
+ * with BFINAL = 1; CRC32 and ISIZE.  No EOF marker is written: the standard 28-byte empty block is the writer's to append.
+ * level 0: a stored deflate block (01, LEN, NLEN, the payload).
+ * level 1: LZ77 with one candidate, then fixed Huffman codes (BTYPE 01).  For every position p <= n - 4 of a block of n bytes,
+ *   h = (le32 at p * 2654435761u) >> 17 (15 bits); the candidate of p is the nearest q < p with the same h, every position being
+ *   inserted, those inside matches included; its length is the common prefix of the bytes at q and at p, capped at min 258, n - p; the
+ *   match is valid when the length is at least 4 and p - q at most 32768.  The parse is greedy from p = 0: a valid match emits
+ *   length and distance and advances by the length, otherwise a literal is emitted and p advances by 1; positions past n - 4 are literals.
+ *   Then end-of-block and zero bits to a byte.  When the deflate data would take n + 5 bytes or more the block is stored instead: a
+ *   block is never longer than 18 + 5 + 0xff00 + 8 bytes and BSIZE always fits.
+ *
+ * Output: data [cap_bytes + PLAT_BLOB_PAD], 16-byte aligned, the blocks back to back in piece order (the PLAT_BLOB_PAD bytes behind
+ * the last one zeroed); piece_out_off [n_pieces + 1] from 0: piece i's blocks are data[piece_out_off[i] .. piece_out_off[i + 1]).
+ * status [4] (device): {0 or the error, for PLAT_ERR_OVERFLOW the first piece that does not fit, else -1, total compressed bytes,
+ * blocks}.  More bytes than cap_bytes is PLAT_ERR_OVERFLOW: no payload byte is written, piece_out_off is clamped to cap_bytes and
+ * status[2] still holds the bytes needed, so that a caller can size its buffer and call again; text_len + 31 * blocks always
+ * suffices (blocks <= text_len / 0xff00 + n_pieces).  piece_off values that do not ascend from 0 inside text_len are
+ * PLAT_ERR_BAD_INPUT in status[0] and nothing is read or written through them.  Invalid arguments (a NULL pointer, a negative count,
+ * a level other than 0 or 1, data not 16-byte aligned) return PLAT_ERR_INVALID and nothing is enqueued.
+ * The same input gives the same bytes, whatever the order in which lanes and workgroups run.  Four kernels (block plan; one
+ * workgroup per block with payload, head table, step table and output words in LDS; a scan of the block sizes; the compaction of the
+ * blocks from their slots in scratch memory); the call does not wait and nothing traps.                                          */
+typedef struct plat_bgzf_deflate_in {
+    const uint8_t* text;
+    int64_t text_len;
+    int32_t n_pieces, level;
+    const int64_t* piece_off;        /* [n_pieces + 1] */
+} plat_bgzf_deflate_in;
+
+typedef struct plat_bgzf_deflate_out {
+    int64_t cap_bytes;
+    uint8_t* data;
+    int64_t* piece_out_off;          /* [n_pieces + 1] */
+    int64_t* status;                 /* [4] */
+} plat_bgzf_deflate_out;
+
+int plat_bgzf_deflate_batch(plat_ctx* ctx, const plat_bgzf_deflate_in* in, const plat_bgzf_deflate_out* out, void* stream);
+
 /* ---- the BAM iterator over inflated blocks -----------------------------------------------------------------
  * Replaces  sam_itr_next  (htslibWrapper.pxd:175-177, htslibWrapper.pyx:312,412; the htslib 1.x before 1.10 the reference declares) for
  * n_streams fetches over the output of plat_bgzf_inflate_batch (data, out_off; n_blocks blocks), without the host knowing an inflated

@@ -127,9 +127,25 @@ def call_variants_config4(opts, n_regions):
         vcf = VCF(["S1"])
         vcf.setheader([("fileDate", datetime.date.today()), ("source", "platypus_amd (records as Platypus_Version_0.8.1.1 writes them)"),
                        ("platypusOptions", str(dict(sorted(vars(opts).items()))))])         # variantcaller.pyx:51,942
-        with open(opts.output, "w") as f:
-            vcf.writeheader(f)
-            f.write("".join(line + "\n" for line in merged))
+        if opts.output.endswith(".gz"):
+            # as the reference's filez.Open does for .gz names (variantcaller.pyx:951-956), as BGZF: the header's block(s), the merged
+            # records', the EOF block -- deflated on the device (include/platypus_caller_bgzfout.h)
+            from . import fastcaller as F
+            import torch
+            head = io.StringIO()
+            vcf.writeheader(head)
+            parts = [head.getvalue().encode(), "".join(line + "\n" for line in merged).encode()]
+            zc = F.NativeCaller(int(os.environ.get("LOCAL_RANK", rank)) % max(1, torch.cuda.device_count()), 1, 1)
+            try:
+                packed, _ = zc.compress_text(b"".join(parts), [len(p) for p in parts], level=1, eof=True)
+                with open(opts.output, "wb") as f:
+                    f.write(packed)
+            finally:
+                zc.close()
+        else:
+            with open(opts.output, "w") as f:
+                vcf.writeheader(f)
+                f.write("".join(line + "\n" for line in merged))
         print(json.dumps(dict(regions=n_regions, region_len=size, ranks=world, windows_rank0=n_windows, records=len(merged),
                               seconds=round(dt, 3), output=opts.output)))
     if dist is not None:

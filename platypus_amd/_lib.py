@@ -111,6 +111,14 @@ class BgzfInflateOut(C.Structure):
     _fields_ = [("cap_bytes", C.c_int64), ("data", C.c_void_p), ("out_off", C.c_void_p), ("status", C.c_void_p)]
 
 
+class BgzfDeflateIn(C.Structure):
+    _fields_ = [("text", C.c_void_p), ("text_len", C.c_int64), ("n_pieces", C.c_int32), ("level", C.c_int32), ("piece_off", C.c_void_p)]
+
+
+class BgzfDeflateOut(C.Structure):
+    _fields_ = [("cap_bytes", C.c_int64), ("data", C.c_void_p), ("piece_out_off", C.c_void_p), ("status", C.c_void_p)]
+
+
 class BamFindIn(C.Structure):
     _fields_ = [("n_streams", C.c_int32), ("n_chunks", C.c_int32), ("n_blocks", C.c_int32), ("_pad", C.c_int32)] + [(k, C.c_void_p) for k in (
         "data", "out_off", "stream_chunk_begin", "chunk_blk_first", "chunk_blk_end", "chunk_first_uoffset", "chunk_stop_blk", "chunk_stop_uoffset",
@@ -281,6 +289,7 @@ SIGNATURES = {
                                                  C.c_void_p, C.c_void_p, C.POINTER(ReadBuffersTables), C.c_void_p]),
     "plat_bam_decode_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(BamDecodeOut), C.c_void_p]),
     "plat_bgzf_inflate_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(BgzfInflateOut), C.c_void_p]),
+    "plat_bgzf_deflate_batch": (C.c_int, [C.c_void_p, C.POINTER(BgzfDeflateIn), C.POINTER(BgzfDeflateOut), C.c_void_p]),
     "plat_bam_find_records": (C.c_int, [C.c_void_p, C.POINTER(BamFindIn), C.POINTER(BamFindOut), C.c_void_p]),
     "plat_bam_route_batch": (C.c_int, [C.c_void_p, C.POINTER(BamRouteIn), C.POINTER(BamRouteOut), C.c_void_p]),
     "plat_source_variants_batch": (C.c_int, [C.c_void_p, C.POINTER(SourceVariantsIn), C.POINTER(SourceVariantsOut), C.c_void_p]),
@@ -302,6 +311,7 @@ SIGNATURES = {
 # unbound there; load() still requires every declared symbol of the real library
 ADDED_LATER = ("plat_read_buffers_batch", "plat_read_buffers_packed_batch", "plat_bam_decode_batch", "plat_bgzf_inflate_batch", "plat_bam_find_records",
                "plat_bam_route_batch", "plat_source_variants_batch", "plat_tabix_fetch_batch", "plat_refcall_coverage_batch", "plat_refcov_lds_reads",
+               "plat_bgzf_deflate_batch",
                "plat_concat_read_tables_src", "plat_pack_codes_pieces", "plat_candidates_batch_packed", "plat_gather_reads_packed",
                "plat_variant_read_stats_packed_batch")
 

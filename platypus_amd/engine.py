@@ -845,6 +845,41 @@ class Engine:
             raise _lib.PlatypusDeviceError(int(st[0]), "block %d" % int(st[1]), "plat_bgzf_inflate_batch")
         return out
 
+    def bgzf_deflate(self, text, piece_off, level=1, cap_bytes=None, check=True):
+        """plat_bgzf_deflate_batch: the pieces text[piece_off[i]:piece_off[i + 1]] deflated to BGZF blocks on the device (no EOF block).
+        Returns a dict: data (the blocks, back to back), piece_out_off [n+1], status [4] = {error, first piece that does not fit or -1, total
+        compressed bytes, blocks} and guard_intact: nothing was written in front of data or behind cap_bytes (the PLAT_BLOB_PAD zeros
+        behind the last byte aside; on overflow nothing at all).  cap_bytes defaults to the bound the header gives, text_len + 31 per
+        possible block.  A short capacity or refused offsets raise PlatypusDeviceError (check=False: returns, with status saying so)."""
+        torch = _torch()
+        text = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, dtype=np.uint8)
+        piece_off = np.ascontiguousarray(piece_off, dtype=np.int64)
+        n, nbytes = len(piece_off) - 1, len(text)
+        if n < 0:
+            raise ValueError("piece_off holds n_pieces + 1 offsets")
+        cap = int(nbytes + 31 * (nbytes // 0xff00 + n) if cap_bytes is None else cap_bytes)
+        guard, fill = 64, 0xEE
+        d_text = torch.from_numpy(np.append(text, np.zeros(1, np.uint8))).to(self.device)
+        d_off = torch.from_numpy(piece_off.copy()).to(self.device)
+        d_all = torch.full((guard + cap + _lib.PLAT_BLOB_PAD + guard,), fill, dtype=torch.uint8, device=self.device)
+        assert d_all.data_ptr() % 16 == 0 and guard % 16 == 0
+        d_out_off = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
+        d_status = torch.zeros(4, dtype=torch.int64, device=self.device)
+        i = _lib.BgzfDeflateIn(d_text.data_ptr(), nbytes, n, int(level), d_off.data_ptr())
+        o = _lib.BgzfDeflateOut(cap, d_all.data_ptr() + guard, d_out_off.data_ptr(), d_status.data_ptr())
+        _lib.check(self.lib.plat_bgzf_deflate_batch(self.ctx, C.byref(i), C.byref(o), self._stream()), "plat_bgzf_deflate_batch")
+        self._sync()
+        h, st = d_all.cpu().numpy(), d_status.cpu().numpy()
+        fits = int(st[0]) == 0
+        total = int(st[2]) if fits else 0
+        pad = _lib.PLAT_BLOB_PAD if int(st[0]) != -8 else 0
+        tail = h[guard + total:]
+        intact = bool((h[:guard] == fill).all()) and not tail[:pad].any() and bool((tail[pad:] == fill).all())
+        out = dict(data=h[guard:guard + total], piece_out_off=d_out_off.cpu().numpy(), status=st, guard_intact=intact)
+        if check and int(st[0]) != 0:
+            raise _lib.PlatypusDeviceError(int(st[0]), "piece %d, %d bytes needed" % (int(st[1]), int(st[2])), "plat_bgzf_deflate_batch")
+        return out
+
     def bam_find_records(self, inflated, streams, cap_records=None, check=True):
         """plat_bam_find_records: sam_itr_next over the output of bgzf_inflate(..., keep_device=True).  streams: per stream (tid, beg, end,
         chunks), chunks a list of (blk_first, blk_end, first_uoffset, stop_blk or -1, stop_uoffset).  Returns a dict: rec_off / rec_limit

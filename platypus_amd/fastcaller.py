@@ -622,6 +622,7 @@ def build(verbose=False):
     srcs.append(os.path.join(_lib.CSRC, "source_rule.hpp"))            # (... and the host parser of source VCF lines is the device's rule)
     srcs.append(os.path.join(_lib.CSRC, "refcov_rule.hpp"))            # (... as the host's loop over a REFCALL block's positions is)
     srcs.append(os.path.join(_lib.CSRC, "tabix_rule.hpp"))             # (... and the host's walk over a tabix fetch's lines)
+    srcs.append(os.path.join(_lib.CSRC, "bgzf_deflate.hpp"))           # (... and the host twin of the BGZF encoder)
     if os.path.exists(LIB_PATH) and os.path.getmtime(LIB_PATH) >= max([os.path.getmtime(f) for f in srcs] + [os.path.getmtime(_lib.LIB_PATH)]):
         return LIB_PATH
     # (-O3: the region loop is many small functions over small containers; +10 % windows/s over -O2 on the same box.  No -march: the library
@@ -667,6 +668,8 @@ def _bind(lib):
     lib.plat_merge_region_blocks.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
     lib.plat_caller_set_source_lines.argtypes = [C.c_void_p, C.POINTER(_SourceLines), C.c_int, C.c_int]
     lib.plat_caller_set_source_blocks.argtypes = [C.c_void_p, C.POINTER(_SourceBlocks), C.c_int, C.c_int, C.POINTER(SourceBlocksInfo)]
+    lib.plat_caller_compress_text.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p),
+                                              C.POINTER(C.c_size_t), C.c_void_p]
     lib.plat_caller_free.argtypes = [C.c_void_p]
     lib.plat_caller_free.restype = None
     lib.plat_caller_last_error.argtypes = [C.c_void_p]
@@ -999,6 +1002,25 @@ class NativeCaller:
         if rc != 0:
             raise _lib.PlatypusDeviceError(rc, "no call yet, or another number of regions", "plat_caller_region_text_lengths")
         return out[:n_regions]
+
+    def compress_text(self, text, lengths, level=1, eof=True):
+        """plat_caller_compress_text (include/platypus_caller_bgzfout.h): a record text (str, bytes or a raw view) whose regions take
+        `lengths` bytes each (region_text_lengths) deflated to BGZF blocks on the device, every region a whole number of blocks.  Returns
+        (the compressed bytes as a ctypes char array -- no copy, freed with the array --, the regions' compressed lengths): again a text
+        of per-region pieces, for RegionTextExchange and BlockOrder.merge.  eof=True appends the 28-byte EOF block (not counted in the
+        lengths); level 0 stores."""
+        import numpy as np
+        if isinstance(text, str):
+            text = text.encode("ascii")
+        base, nbytes = text_address(text)
+        lens = np.ascontiguousarray(lengths, dtype=np.int64)
+        out_lens = np.zeros(max(len(lens), 1), dtype=np.int64)
+        out, length = C.c_void_p(), C.c_size_t()
+        rc = self.lib.plat_caller_compress_text(self.h, base, nbytes, lens.ctypes.data, len(lens), int(level), int(bool(eof)), C.byref(out), C.byref(length),
+                                                out_lens.ctypes.data)
+        if rc != 0:
+            raise _lib.PlatypusDeviceError(rc, (self.lib.plat_caller_last_error(self.h) or b"").decode(), "plat_caller_compress_text")
+        return _native_text(self.lib, out, length.value, "view"), out_lens[:len(lens)]
 
     def call_stream(self, n_regions, load, user, sample_names, options, n_slots, n_loaders=2, raw=False, source_lines=None, source_blocks=None):
         """plat_call_regions_stream: regions loaded on demand.  `load`: a plat_region_load_fn -- the address of a native function (int,

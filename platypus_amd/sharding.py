@@ -69,6 +69,11 @@ class RegionTextExchange:
       * gloo / no process group: block copies on up to 16 host threads (plat_merge_region_blocks).
     When regions DO overlap the texts are merged line by line instead (fastcaller.merge_record_texts), as before.
 
+    The blocks are opaque bytes with per-region byte counts, so `text` may as well be a COMPRESSED text with its compressed lengths, as
+    NativeCaller.compress_text returns them with eof=False (every region a whole number of BGZF blocks, include/platypus_caller_bgzfout.h):
+    the payload shrinks by the compression ratio, the merged bytes are a BGZF stream in region order, and rank 0 then appends the EOF
+    block (synth.BGZF_EOF) when it writes the file.  Overlapping regions cannot be merged that way: compress after the merge then.
+
     regions_of_rank[r] = [(chrom, start, end), ...] in rank r's list order (the same on every rank)."""
 
     def __init__(self, regions_of_rank, dist=None, device=None, lib=None, device_index=0):
