@@ -480,6 +480,31 @@ cdef extern from "platypus_mi355x.h":
         int64_t* stream_counts
         int64_t* status
     int plat_tabix_fetch_batch(plat_ctx* ctx, const plat_tabix_fetch_in* inp, const plat_tabix_fetch_out* out, void* stream) nogil
+    # the tabix index of a bgzipped VCF (ti_index_core, index.c.pysam.c:320-393, on the device)
+    int PLAT_TBI_STATUS_WORDS
+    int PLAT_TBI_MAX_REF
+    ctypedef struct plat_tabix_index_in:
+        int32_t n_blocks
+        int32_t _pad
+        const uint8_t* data
+        int64_t data_len
+        const int64_t* out_off
+        const int64_t* blk_addr
+    ctypedef struct plat_tabix_index_out:
+        int64_t cap_runs
+        int64_t cap_names
+        int64_t cap_windows
+        int64_t cap_name_bytes
+        int32_t* run_tid
+        int32_t* run_bin
+        int64_t* run_u
+        int64_t* name_off
+        int32_t* name_len
+        uint8_t* name_bytes
+        int64_t* lin_first
+        int64_t* lin
+        int64_t* status
+    int plat_tabix_index_batch(plat_ctx* ctx, const plat_tabix_index_in* inp, const plat_tabix_index_out* out, void* stream) nogil
     # read counts of reference-call blocks (outputRefCall's loop over countReadsCoveringRegion)
     int PLAT_REFCOV_RAISES
     int PLAT_REFCOV_EMPTY

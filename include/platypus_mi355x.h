@@ -961,6 +961,68 @@ typedef struct plat_tabix_fetch_out {
 
 int plat_tabix_fetch_batch(plat_ctx* ctx, const plat_tabix_fetch_in* in, const plat_tabix_fetch_out* out, void* stream);
 
+/* ---- the tabix index of a bgzipped VCF ------------------------------------------------------------------------------
+ * Replaces  ti_index_core  with ti_conf_vcf (src/tabix/index.c.pysam.c:320-393) over ti_readline (:86-120), get_intv (:227-241),
+ *           insert_offset2 (:266-286) and bgzf_tell -- what `tabix -p vcf` reads of the file -- for the .gz output the caller writes
+ * over the output of plat_bgzf_inflate_batch for the WHOLE file: data (data_len: the room it has, out_off[n_blocks] at most) and
+ * out_off [n_blocks + 1], plus blk_addr [n_blocks + 1]: the file address of every block, the last entry the address behind the last block
+ * that holds data.  out_off ascends from 0 in steps of at most 65536 and blk_addr ascends inside [0, 2^47); anything else is status
+ * {PLAT_ERR_INVALID, -1, 0 ...} and nothing else is written.  csrc/tabix_index.hpp holds the same rule serially (the host twin) and
+ * the finishing stage that turns what this call leaves into the .tbi's bytes.
+ *
+ * The rule:
+ *   lines      a line runs to its '\n' or to the end of the data (a last line without a newline counts); '\r' is an ordinary byte; a line
+ *              whose first byte is '#' is no record wherever it stands.  Lines are numbered from 1, '#' lines included
+ *   offsets    the virtual offset of a line that starts at inflated offset t is blk_addr[b] << 16 | (t - out_off[b]), b the last block
+ *              with out_off[b] <= t: a line behind a newline on a block's last byte sits at offset 0 of the next block.  The end of the
+ *              file is blk_addr[n_blocks] << 16
+ *   record     columns split at '\t' and at a NUL byte, as plat_tabix_fetch_batch above reads them: the name is column 1;
+ *              v = strtol(column 2, base 0), beg = max(v - 1, 0), end = max(v, 1); a non-empty column 4 gives end = beg + its length; in
+ *              column 8, END= at its start gives end = the number behind it, otherwise, when END= occurs at all, the first ;END= does.
+ *              bin = ti_reg2bin(beg, end) in unsigned 32-bit arithmetic; the linear windows are beg >> 14 .. (end - 1) >> 14 in signed
+ *              arithmetic.  END=0 and an END below POS give odd but defined bins and empty window ranges, as in the reference
+ *   refused    where the reference exits -- a line of fewer than two columns, an empty one included (kind 1); end < 0 (kind 3); a beg below
+ *              that of the record in front of it on one contig (kind 4); a contig name that was seen before another one (kind 5) -- and
+ *              a v or an END outside +-(2^31 - 1), which the reference narrows to int32 (kind 2).  The verdict is that of the lowest such
+ *              line; where two kinds hold of it, the lower kind
+ *   contigs    names are compared byte by byte over their whole length (a name that is a prefix of another is another name); tid in order
+ *              of first appearance.  Every contig's name is compared with every earlier one's (by a 64-bit hash and the length first), so a
+ *              file holds at most 65536 contigs: more is status PLAT_ERR_UNSUPPORTED
+ *   runs       a maximal stretch of consecutive records of one contig with one bin (a change of contig ends it even when the bin number
+ *              repeats); u is the offset of its first record
+ *   windows    per contig n = the largest (end - 1 >> 14) + 1 (0 at least) windows; window w holds the offset of the first record in file
+ *              order whose range holds w, offset 0 counting as unset, and 0 where none does
+ *
+ * Output (device): the runs in file order run_tid / run_bin / run_u [cap_runs]; name_off / name_len [cap_names]: each contig's name as
+ * offset and length into data, and name_bytes [cap_name_bytes]: the names' bytes back to back in tid order; lin_first [cap_names + 1] and lin [cap_windows]: contig t's windows are lin[lin_first[t] .. lin_first[t + 1]);
+ * status [PLAT_TBI_STATUS_WORDS]: {0 or the error, the lowest offending line or -1, its kind, records, runs, contigs, windows, the end
+ * offset, 1 when the first record sits at offset 0 and then its first and last window (the finishing stage zeroes those), lines, the names' bytes}.
+ * More runs, contigs, name bytes or windows than the capacities is PLAT_ERR_OVERFLOW: nothing is written behind a capacity (runs and names up to
+ * it, name bytes and windows not at all), the status holds the full counts and the caller calls again.  A refusal wins over PLAT_ERR_UNSUPPORTED and
+ * that over an overflow; of a refused file only the status is defined.
+ * Every loop is bounded by its line's end, the name's length, 64 words of a tile, the logarithm of a table, 65536 / 64 contigs per lane
+ * or the 2^17 windows a 32-bit END spans; every offset is derived from the checked out_off.  No lane walks a contig or the file.
+ * Eleven kernels (csrc/plat_tbxindex.hip names them), the marks in the scratch of plat_tabix_fetch_batch (one of the two calls at a
+ * time per context); the call does not wait and nothing traps.                                                                      */
+#define PLAT_TBI_STATUS_WORDS 13
+#define PLAT_TBI_MAX_REF 65536
+typedef struct plat_tabix_index_in {
+    int32_t n_blocks, _pad;
+    const uint8_t* data; int64_t data_len;
+    const int64_t* out_off;          /* [n_blocks + 1] */
+    const int64_t* blk_addr;         /* [n_blocks + 1] */
+} plat_tabix_index_in;
+
+typedef struct plat_tabix_index_out {
+    int64_t cap_runs, cap_names, cap_windows, cap_name_bytes;
+    int32_t* run_tid; int32_t* run_bin; int64_t* run_u;
+    int64_t* name_off; int32_t* name_len; uint8_t* name_bytes;
+    int64_t* lin_first; int64_t* lin;
+    int64_t* status;                 /* [PLAT_TBI_STATUS_WORDS] */
+} plat_tabix_index_out;
+
+int plat_tabix_index_batch(plat_ctx* ctx, const plat_tabix_index_in* in, const plat_tabix_index_out* out, void* stream);
+
 /* ---- read counts of reference-call blocks ------------------------------------------------------------------------
  * Replaces the loop of  outputRefCall   variantcaller.pyx:774-784  over  ReadArray.countReadsCoveringRegion(p, p + 1)   cwindow.pyx:176-206
  * (one call per position of a block and per sample: the block's QUAL is computed from the smallest count)

@@ -12,6 +12,8 @@ def call_variants(argv):
     opts = build_parser().parse_args(argv)
     if opts.HLATyping:
         sys.exit("platypus_amd: --HLATyping=1 (useMapQualCap) is not implemented on the device path")
+    if opts.outputIndex and not opts.output.endswith(".gz"):
+        sys.exit("platypus_amd: --outputIndex=1 indexes a compressed output: give --output a name that ends in .gz")
     if opts.synthetic is None:
         sys.exit("platypus_amd: BAM/FASTA input needs the reference's htslib I/O layer, which is outside this build's "
                  "scope (see DESIGN.md, 'out of scope').  Use --synthetic=config2[:N] or the in-memory API "
@@ -126,7 +128,7 @@ def call_variants_config4(opts, n_regions):
         import datetime
         vcf = VCF(["S1"])
         vcf.setheader([("fileDate", datetime.date.today()), ("source", "platypus_amd (records as Platypus_Version_0.8.1.1 writes them)"),
-                       ("platypusOptions", str(dict(sorted(vars(opts).items()))))])         # variantcaller.pyx:51,942
+                       ("platypusOptions", str(dict(sorted((k, v) for k, v in vars(opts).items() if k != "outputIndex" or v))))])         # variantcaller.pyx:51,942
         if opts.output.endswith(".gz"):
             # as the reference's filez.Open does for .gz names (variantcaller.pyx:951-956), as BGZF: the header's block(s), the merged
             # records', the EOF block -- deflated on the device (include/platypus_caller_bgzfout.h)
@@ -140,6 +142,10 @@ def call_variants_config4(opts, n_regions):
                 packed, _ = zc.compress_text(b"".join(parts), [len(p) for p in parts], level=1, eof=True)
                 with open(opts.output, "wb") as f:
                     f.write(packed)
+                if opts.outputIndex:
+                    # the index tabix would build of the file, from the bytes just written (include/platypus_caller_tbi.h)
+                    with open(opts.output + ".tbi", "wb") as f:
+                        f.write(zc.index_bgzf(packed))
             finally:
                 zc.close()
         else:

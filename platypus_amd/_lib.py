@@ -159,6 +159,19 @@ class TabixFetchOut(C.Structure):
     _fields_ = [("cap_text", C.c_int64), ("text", C.c_void_p), ("stream_text_off", C.c_void_p), ("stream_counts", C.c_void_p), ("status", C.c_void_p)]
 
 
+class TabixIndexIn(C.Structure):
+    _fields_ = [("n_blocks", C.c_int32), ("_pad", C.c_int32), ("data", C.c_void_p), ("data_len", C.c_int64), ("out_off", C.c_void_p), ("blk_addr", C.c_void_p)]
+
+
+class TabixIndexOut(C.Structure):
+    _fields_ = [("cap_runs", C.c_int64), ("cap_names", C.c_int64), ("cap_windows", C.c_int64), ("cap_name_bytes", C.c_int64)] + [(k, C.c_void_p) for k in (
+        "run_tid", "run_bin", "run_u", "name_off", "name_len", "name_bytes", "lin_first", "lin", "status")]
+
+
+TBI_STATUS_WORDS, TBI_MAX_REF = 13, 65536
+TBI_KINDS = ("", "a line of fewer than two columns", "a POS or END beyond 32 bits", "a negative END", "a position below the one in front of it",
+             "a contig name that appeared before another")
+
 ROUTE_MAX_GROUPS, ROUTE_MAX_SAMPLES, ROUTE_LDS_ID_BYTES = 2048, 256, 24576
 ROUTE_WHY = ("routed", "no RG field", "an RG field that is no string", "an RG value that is not in the table", "an aux field of unknown type",
              "a B array with a negative count", "aux data that runs past the record", "a fixed part that runs past the record")
@@ -294,6 +307,7 @@ SIGNATURES = {
     "plat_bam_route_batch": (C.c_int, [C.c_void_p, C.POINTER(BamRouteIn), C.POINTER(BamRouteOut), C.c_void_p]),
     "plat_source_variants_batch": (C.c_int, [C.c_void_p, C.POINTER(SourceVariantsIn), C.POINTER(SourceVariantsOut), C.c_void_p]),
     "plat_tabix_fetch_batch": (C.c_int, [C.c_void_p, C.POINTER(TabixFetchIn), C.POINTER(TabixFetchOut), C.c_void_p]),
+    "plat_tabix_index_batch": (C.c_int, [C.c_void_p, C.POINTER(TabixIndexIn), C.POINTER(TabixIndexOut), C.c_void_p]),
     "plat_refcall_coverage_batch": (C.c_int, [C.c_void_p, C.POINTER(RefCovIn), C.POINTER(RefCovOut), C.c_void_p]),
     "plat_refcov_lds_reads": (C.c_int, []),
     "plat_variant_read_stats_batch": (C.c_int, [C.c_void_p, C.POINTER(InfoStatsBatch), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
@@ -311,7 +325,7 @@ SIGNATURES = {
 # unbound there; load() still requires every declared symbol of the real library
 ADDED_LATER = ("plat_read_buffers_batch", "plat_read_buffers_packed_batch", "plat_bam_decode_batch", "plat_bgzf_inflate_batch", "plat_bam_find_records",
                "plat_bam_route_batch", "plat_source_variants_batch", "plat_tabix_fetch_batch", "plat_refcall_coverage_batch", "plat_refcov_lds_reads",
-               "plat_bgzf_deflate_batch",
+               "plat_bgzf_deflate_batch", "plat_tabix_index_batch",
                "plat_concat_read_tables_src", "plat_pack_codes_pieces", "plat_candidates_batch_packed", "plat_gather_reads_packed",
                "plat_variant_read_stats_packed_batch")
 

@@ -1038,6 +1038,45 @@ class Engine:
                   bool((counts[n_counts:] == f64).all()) and bool((st[4:] == f64).all()))
         return dict(text=h[guard:guard + used].tobytes(), off=off[:n_off].tolist(), counts=counts[:n_counts].tolist(), status=st[:4].tolist(), guard_intact=intact)
 
+    def tabix_index(self, inflated, blk_addr, cap_runs=None, cap_names=None, cap_windows=None, cap_name_bytes=None):
+        """plat_tabix_index_batch: ti_index_core (index.c.pysam.c:320-393) over the output of bgzf_inflate(..., keep_device=True) for a whole
+        bgzipped VCF.  blk_addr [n_blocks + 1]: the blocks' file addresses and the address behind the last.  Returns a dict: runs [(tid, bin,
+        u)], names [(offset, length)] into the data, name_bytes (the names back to back), lin_first, lin (what fits the capacities -- default: a run per 16 bytes, 4096 contigs,
+        64 KiB of names, 2^18 windows), status [13] and guard_intact: nothing was written behind a capacity or the status block."""
+        torch = _torch()
+        dv = inflated["device"]
+        total, n_blocks = int(inflated["status"][2]), dv["n_blocks"]
+        cap_r = total // 16 + 64 if cap_runs is None else int(cap_runs)
+        cap_n = 4096 if cap_names is None else int(cap_names)
+        cap_w = 1 << 18 if cap_windows is None else int(cap_windows)
+        cap_b = 1 << 16 if cap_name_bytes is None else int(cap_name_bytes)
+        d_nbytes = torch.full((cap_b + 64,), 0xEE, dtype=torch.uint8, device=self.device)
+        f64, f32 = 0x7EEE7EEE7EEE7EEE, 0x7EEE7EEE
+        d_addr = torch.from_numpy(np.ascontiguousarray(blk_addr, dtype=np.int64).copy()).to(self.device)
+        full = lambda n, big: torch.full((n + 16,), f64 if big else f32, dtype=torch.int64 if big else torch.int32, device=self.device)
+        d_tid, d_bin, d_u, d_noff, d_nlen = full(cap_r, False), full(cap_r, False), full(cap_r, True), full(cap_n, True), full(cap_n, False)
+        d_first, d_lin, d_status = full(cap_n + 1, True), full(cap_w, True), full(_lib.TBI_STATUS_WORDS, True)
+        i = _lib.TabixIndexIn(n_blocks, 0, dv["data_ptr"], total, dv["out_off"].data_ptr(), d_addr.data_ptr())
+        o = _lib.TabixIndexOut(cap_r, cap_n, cap_w, cap_b, d_tid.data_ptr(), d_bin.data_ptr(), d_u.data_ptr(), d_noff.data_ptr(), d_nlen.data_ptr(), d_nbytes.data_ptr(), d_first.data_ptr(),
+                               d_lin.data_ptr(), d_status.data_ptr())
+        _lib.check(self.lib.plat_tabix_index_batch(self.ctx, C.byref(i), C.byref(o), self._stream()), "plat_tabix_index_batch")
+        self._sync()
+        tid, b, u, noff, nlen, first, lin, st = (t.cpu().numpy() for t in (d_tid, d_bin, d_u, d_noff, d_nlen, d_first, d_lin, d_status))
+        ok = int(st[0]) in (0, -8)
+        n_r = min(int(st[4]), cap_r) if ok else 0
+        n_n = min(int(st[5]), cap_n) if ok else 0
+        n_w = int(st[6]) if ok and int(st[6]) <= cap_w else 0
+        n_b = int(st[12]) if ok and int(st[12]) <= cap_b else 0
+        nbytes = d_nbytes.cpu().numpy()
+        intact = (bool((st[_lib.TBI_STATUS_WORDS:] == f64).all()) and bool((tid[cap_r:] == f32).all()) and bool((b[cap_r:] == f32).all()) and
+                  bool((u[cap_r:] == f64).all()) and bool((noff[cap_n:] == f64).all()) and bool((nlen[cap_n:] == f32).all()) and
+                  bool((first[cap_n + 1:] == f64).all()) and bool((lin[cap_w:] == f64).all()) and bool((nbytes[cap_b:] == 0xEE).all()))
+        if ok:                                                           # (short of a capacity nothing but what the counts name is written either)
+            intact = (intact and bool((tid[n_r:] == f32).all()) and bool((u[n_r:] == f64).all()) and bool((noff[n_n:] == f64).all()) and
+                      bool((lin[n_w:] == f64).all()) and bool((nbytes[n_b:] == 0xEE).all()))
+        return dict(runs=list(zip(tid[:n_r].tolist(), b[:n_r].tolist(), u[:n_r].tolist())), names=list(zip(noff[:n_n].tolist(), nlen[:n_n].tolist())),
+                    name_bytes=nbytes[:n_b].tobytes(), lin_first=first[:n_n + 1].tolist() if ok else [], lin=lin[:n_w].tolist(), status=st[:_lib.TBI_STATUS_WORDS].tolist(), guard_intact=intact)
+
     def refcall_coverage(self, read_pos, read_end, slices, intervals, tile_first=None):
         """plat_refcall_coverage_batch: the loop of outputRefCall (variantcaller.pyx:774-784) over ReadArray.countReadsCoveringRegion
         (cwindow.pyx:176-206) on the device.  read_pos / read_end: the read table; slices: [(begin, n, longest)], one sample's good reads each;

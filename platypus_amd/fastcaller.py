@@ -614,6 +614,12 @@ def aligned_reads_from_arrays(s):
                         cigarOps=[tuple(x) for x in cig[co[i]:co[i + 1]].tolist()], matePos=int(s["mate_pos"][i])) for i in range(len(s["pos"]))]
 
 
+class TbiInfo(C.Structure):
+    """plat_tbi_info (include/platypus_caller_tbi.h)."""
+    _fields_ = [(k, C.c_int64) for k in ("n_blocks", "compressed_bytes", "inflated_bytes", "lines", "records", "runs", "contigs", "windows", "device_calls",
+                                         "refused_line")] + [("seconds", C.c_double)]
+
+
 def build(verbose=False):
     """g++ the host library and link it to libplat_mi355x.so (built first if needed)."""
     _lib.build()
@@ -623,6 +629,7 @@ def build(verbose=False):
     srcs.append(os.path.join(_lib.CSRC, "refcov_rule.hpp"))            # (... as the host's loop over a REFCALL block's positions is)
     srcs.append(os.path.join(_lib.CSRC, "tabix_rule.hpp"))             # (... and the host's walk over a tabix fetch's lines)
     srcs.append(os.path.join(_lib.CSRC, "bgzf_deflate.hpp"))           # (... and the host twin of the BGZF encoder)
+    srcs.append(os.path.join(_lib.CSRC, "tabix_index.hpp"))            # (... and the host twin of the tabix indexer, with its finishing stage)
     if os.path.exists(LIB_PATH) and os.path.getmtime(LIB_PATH) >= max([os.path.getmtime(f) for f in srcs] + [os.path.getmtime(_lib.LIB_PATH)]):
         return LIB_PATH
     # (-O3: the region loop is many small functions over small containers; +10 % windows/s over -O2 on the same box.  No -march: the library
@@ -670,6 +677,7 @@ def _bind(lib):
     lib.plat_caller_set_source_blocks.argtypes = [C.c_void_p, C.POINTER(_SourceBlocks), C.c_int, C.c_int, C.POINTER(SourceBlocksInfo)]
     lib.plat_caller_compress_text.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p),
                                               C.POINTER(C.c_size_t), C.c_void_p]
+    lib.plat_caller_index_bgzf.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(TbiInfo)]
     lib.plat_caller_free.argtypes = [C.c_void_p]
     lib.plat_caller_free.restype = None
     lib.plat_caller_last_error.argtypes = [C.c_void_p]
@@ -1021,6 +1029,21 @@ class NativeCaller:
         if rc != 0:
             raise _lib.PlatypusDeviceError(rc, (self.lib.plat_caller_last_error(self.h) or b"").decode(), "plat_caller_compress_text")
         return _native_text(self.lib, out, length.value, "view"), out_lens[:len(lens)]
+
+    def index_bgzf(self, data, info=False):
+        """plat_caller_index_bgzf (include/platypus_caller_tbi.h): the tabix index of a whole bgzipped VCF (bytes, or a ctypes array as
+        compress_text returns it, header blocks and EOF block included), built on the device.  Returns the .tbi's bytes (BGZF), with
+        info=True (bytes, TbiInfo).  A file tabix would refuse raises PlatypusDeviceError naming the line."""
+        base, nbytes = text_address(data)
+        out, length, inf = C.c_void_p(), C.c_size_t(), TbiInfo()
+        rc = self.lib.plat_caller_index_bgzf(self.h, base, nbytes, C.byref(out), C.byref(length), C.byref(inf))
+        if rc != 0:
+            raise _lib.PlatypusDeviceError(rc, (self.lib.plat_caller_last_error(self.h) or b"").decode(), "plat_caller_index_bgzf")
+        try:
+            tbi = C.string_at(out, length.value)
+        finally:
+            self.lib.plat_caller_free(out)
+        return (tbi, inf) if info else tbi
 
     def call_stream(self, n_regions, load, user, sample_names, options, n_slots, n_loaders=2, raw=False, source_lines=None, source_blocks=None):
         """plat_call_regions_stream: regions loaded on demand.  `load`: a plat_region_load_fn -- the address of a native function (int,

@@ -73,6 +73,9 @@ def build_parser():
                        type=_list if typ == "list" else typ, default=default, **({"help": SOURCE_HELP} if flag == "--source" else {}))
     p.add_argument("--synthetic", dest="synthetic", type=str, default=None,
                    help="(this build) run the hot path on a synthetic BASELINE config instead of BAM input: config1|config2[:N]|config5[:N]")
+    p.add_argument("--outputIndex", dest="outputIndex", type=int, default=0,
+                   help="(this build) 1: with an --output name that ends in .gz, also write OUTPUT.tbi, the tabix index of the file, built on the "
+                        "device from the bytes just written (include/platypus_caller_tbi.h), so that --source can take the file as it is")
     return p
 
 
