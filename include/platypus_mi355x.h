@@ -42,6 +42,10 @@ extern "C" {
 #define PLAT_ERR_HIP (-2)           /* HIP runtime error; plat_last_hip_error() has the code        */
 #define PLAT_ERR_NOMEM (-3)         /* device allocation failed ("Out of memory in cHaplotype.alignReads") */
 #define PLAT_ERR_HAP_TOO_LONG (-4)  /* haplotype longer than 16384 (chaplotype.pyx:180-183)         */
+/* Also the read-length side of that refusal: the exact vote keeps longest haplotype + longest read + 8 diagonal counters of 16 bits in
+ * LDS next to the haplotype's index; where they do not fit 160 KB the host returns PLAT_ERR_HAP_TOO_LONG before any seeding kernel is
+ * launched (a batch with a 16384-base haplotype and a read of 26221 bases or more, aligned or not; 26220 fits).  Reads of up to 32767
+ * bases pass validation (longer: PLAT_ERR_BAD_INPUT), but a pair is aligned only when hapLen >= readLen + 15, i.e. up to 16369 bases. */
 #define PLAT_ERR_HAP_TOO_SHORT (-5) /* hapLen < readLen+15: the reference reads past the buffer here */
 #define PLAT_ERR_UNSUPPORTED (-6)   /* option combination not implemented on the device path         */
 #define PLAT_ERR_NO_DEVICE (-7)     /* no gfx950 device / HIP runtime unavailable                    */

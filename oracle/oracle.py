@@ -65,6 +65,8 @@ class Oracle:
                                        C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                        C.c_void_p, C.POINTER(C.c_longlong)]
+        L.orc_tb_saturated.restype = C.c_longlong
+        L.orc_tb_saturated.argtypes = [C.c_int]
         L.orc_em_call.restype = C.c_int
         L.orc_em_call.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.POINTER(C.c_double)]
@@ -167,6 +169,17 @@ class Oracle:
                                   mapq.ctypes.data, flags.ctypes.data, kind.ctypes.data, do_flank,
                                   ll.ctypes.data, sc.ctypes.data, C.byref(ndp))
         return ll, sc, ndp.value
+
+    def tb_saturated(self, reset=True):
+        """Traceback-mode DPs since the last reset that returned 15 872 (no final cell below 0x7800).  The reference starts its backtrace at
+        _backpointers[-1] there, so flank-mode results of such a pair are undefined; the oracle returns an empty alignment for them."""
+        return int(self.lib.orc_tb_saturated(1 if reset else 0))
+
+    def align_window_counting(self, haps, hap_start_pos, hap_end_pos, end_buffer, reads, do_flank=1):
+        """align_window plus the number of its traceback-mode DPs that saturated: (loglik, score, n_dp, n_saturated)."""
+        self.tb_saturated()
+        ll, sc, ndp = self.align_window(haps, hap_start_pos, hap_end_pos, end_buffer, reads, do_flank=do_flank)
+        return ll, sc, ndp, self.tb_saturated()
 
     # -- a11 / a12 -----------------------------------------------------------------------------
     def genotype_loglik(self, arr1, arr2, same_hap, n_good):

@@ -33,6 +33,13 @@
 
 #define POS_INF ((int16_t)0x7800)
 
+/* Traceback-mode DPs in which no final cell came below POS_INF, so that the plain return is (0x7800 + 0x8000) >> 2 = 15872.  align.c
+ * keeps minscoreidx = -1 there and starts its backtrace at _backpointers[-1]: the reference's alignment strings, firstpos and the flank
+ * score taken from them are undefined.  Such a DP is counted here and returns empty strings and firstpos 0 (no memory is read outside the
+ * buffer); tests use the count to prove that an input never gets there.  orc_tb_saturated(1) returns the count and sets it to 0. */
+static long long g_tb_saturated = 0;
+ORC_API long long orc_tb_saturated(int reset);
+
 static inline int16_t w16(int v) { return (int16_t)(uint16_t)v; }          /* wrapping narrow */
 static inline int16_t add16(int16_t a, int16_t b) { return w16((int)a + (int)b); }
 static inline int16_t min16(int16_t a, int16_t b) { return a < b ? a : b; }
@@ -155,6 +162,13 @@ ORC_API int orc_dp_align(const char* seq1, const char* seq2, const char* qual2, 
     }
     const int score = ((int)minscore + 0x8000) >> 2;                  /* :520,585 */
     if (!traceback) return score;
+    if (minscoreidx < 0) {                                            /* saturated: undefined in the reference, see g_tb_saturated */
+        ++g_tb_saturated;
+        aln1[0] = 0; aln2[0] = 0;
+        if (firstpos) *firstpos = 0;
+        free(bp);
+        return score;
+    }
 
     /* Backtrace, align.c:523-577.  States: match 0, insert 1, delete 3. */
     {
@@ -196,6 +210,13 @@ ORC_API int orc_dp_align(const char* seq1, const char* seq2, const char* qual2, 
     }
     free(bp);
     return score;
+}
+
+ORC_API long long orc_tb_saturated(int reset)
+{
+    const long long n = g_tb_saturated;
+    if (reset) g_tb_saturated = 0;
+    return n;
 }
 
 /* score-only convenience */

@@ -341,13 +341,16 @@ k_prep_reads(plat_window_batch b, const int32_t* __restrict__ win_rows, const lo
     __syncthreads();
     const unsigned char* gs = b.read_seq + blob0;
     const unsigned char* gq = b.read_qual + blob0;
-    // a thread takes 4 consecutive bases of one read rl (lanes run over rl).  e / nr by multiply-shift (exact for e < 16384, nr <= 64).
+    // a thread takes 4 consecutive bases of one read rl (lanes run over rl).  e / nr by multiply-shift: exact for e < 16384, nr <= 64, and
+    // the 32-bit product e * M < ngrp * nr * (2^22 / nr + 1) holds while ngrp <= 512 (a group of few reads longer than 4096 bases
+    // wrapped it: g, rl and the read's offset were garbage, the byte loop read outside the blob).  Longer reads divide.
     {
         const int ngrp = (rows - 8 + 3) >> 2;            // groups of 4 bases of the window's longest read
         const int ne = ngrp * nr;
         const unsigned M = (1u << 22) / (unsigned)nr + 1u;
+        const bool mulshift = ne <= 16384 && ngrp <= 512;
         for (int e = tid; e < ne; e += nthr) {
-            const int g = ne <= 16384 ? (int)(((unsigned)e * M) >> 22) : e / nr;
+            const int g = mulshift ? (int)(((unsigned)e * M) >> 22) : e / nr;
             const int rl = e - g * nr;
             const int o = s_off[rl], L = s_off[rl + 1] - o;
             if (4 * g >= L) continue;

@@ -65,6 +65,36 @@ def map_and_align(bytes read, bytes qual, int readStart, int hapStart, bytes hap
     if r.hash != NULL:
         free(r.hash)
     return sc
+
+def dp_diagonals(bytes read, int readStart, int hapStart, bytes hap):
+    # Every diagonal at which mapAndAlignReadToHaplotype can start a DP for this pair, from the reference's own hash tables: the diagonals
+    # with the highest vote that pass its range test, in ascending order (calign.pyx:206-228; the walk may end early at a score of 0), and
+    # the mapping position (:252).  A DP for diagonal d reads the haplotype from max(0, d - 8) on.
+    cdef short* table = NULL
+    cdef short* nxt = NULL
+    cdef cAlignedRead r
+    cdef int hapLen = len(hap)
+    cdef int readLen = len(read)
+    cdef char* cread = read
+    cdef char* chap = hap
+    cdef int i, h, best = 0
+    r.seq = cread
+    r.rlen = readLen
+    r.hash = NULL
+    if readLen < 7:
+        return [], None
+    calign.hash_sequence_multihit(chap, hapLen, &table, &nxt)
+    calign.hashReadForMapping(&r)
+    votes = [0] * (hapLen + readLen)
+    for i in range(readLen - 7):
+        h = table[r.hash[i]]
+        while h != 0:
+            votes[h - i - 1 + readLen] += 1
+            h = nxt[h]
+    free(table); free(nxt); free(r.hash)
+    best = max(votes)
+    cands = [j - readLen for j in range(hapLen + readLen) if best > 0 and votes[j] == best and j - readLen + readLen + 15 < hapLen]
+    return cands, min(readStart - hapStart, hapLen - readLen - 15)
 '''
 
 ASM_DRV = r'''
@@ -1871,6 +1901,188 @@ def gen_mapalign(out):
     print("mapalign_cases:", len(cases))
 
 
+SATURATED = 15872          # fastAlignmentRoutine's return when no final cell is below 0x7800: (0x7800 + 0x8000) >> 2
+
+
+def palette_quals(rng, L, top=94):
+    """Qualities of low entropy (the two wide fixtures stay small): one value, or draws from four values of 0..top-1."""
+    if rng.random() < 0.25:
+        return np.full(L, int(rng.integers(0, top)), dtype=np.uint8)
+    return rng.choice(rng.integers(0, top, 4), L).astype(np.uint8)
+
+
+def save_npz_fixed(path, **arrays):
+    """np.savez_compressed with the members' timestamps fixed: the same arrays give the same bytes."""
+    import io
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
+        for name, a in arrays.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(a), allow_pickle=False)
+            zi = zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            zi.compress_type = zipfile.ZIP_DEFLATED
+            z.writestr(zi, buf.getvalue())
+
+
+def gen_mapalign_wide(out):
+    """gen_mapalign's recipe with the read lengths of tests/long_read_cases.LADDER (251 .. 2000, each 20 times) and haplotypes of L + 200 ..
+    3 L + 1200 bases (16 000 at the most): the four haplotype kinds, the read edits, mapping positions off by up to 200.  Qualities come from a
+    palette (palette_quals), up to 59 as there or, in a third of the cases, up to 93, and are written as a hex string.
+
+    Flank mode.  align.c keeps minscoreidx = -1 when no final cell of a DP is below 0x7800 and then starts its backtrace at
+    _backpointers[-1]: a flank-mode result is undefined as soon as ONE DP of the pair saturates, whatever the final score.  A flank-mode case
+    is therefore drawn again until every DP the reference can run for it scores below 15 872.  That is decided per DP: calign_drv.dp_diagonals
+    lists, from the reference's own hash tables, every diagonal with the highest vote that passes the range test plus the mapping position --
+    a superset of what the walk runs, which may end early at a score of 0 -- and the unmodified align.c scores each of them in plain mode
+    (the scores of the two modes are equal: the traceback only uses the two low bits of cells that hold multiples of 4).  The list is tied to
+    the reference by replaying calign.pyx:222-267 on it: the replayed plain score must equal mapAndAlignReadToHaplotype's on every case."""
+    import calign_drv
+    from oracle.oracle import Oracle, RefAlign
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from long_read_cases import LADDER
+    o, ref = Oracle(), RefAlign()
+    rng = np.random.default_rng(20261020)
+    cases, redrawn = [], 0
+    while len(cases) < 300:
+        L = int(LADDER[len(cases) % len(LADDER)])
+        hapLen = int(rng.integers(L + 200, min(3 * L + 1200, 16000) + 1))
+        kind = int(rng.integers(0, 4))
+        hap = bytearray(rnd(rng, hapLen))
+        if kind == 1:
+            p = int(rng.integers(50, hapLen - 200)); ln = int(rng.integers(20, 150)); hap[p:p + ln] = tandem(rng, ln)
+        if kind == 2:
+            for _ in range(5):
+                hap[int(rng.integers(0, hapLen))] = ord("N")
+        if kind == 3:
+            hap = bytearray(tandem(rng, hapLen))
+        start = int(rng.integers(-L // 2, hapLen - L // 2))
+        read = bytearray()
+        for p in range(start, start + L):
+            read.append(hap[p] if 0 <= p < hapLen else B[int(rng.integers(0, 4))])
+        for _ in range(int(rng.integers(0, 9))):
+            read[int(rng.integers(0, L))] = B[int(rng.integers(0, 4))]
+        m = int(rng.integers(0, 4))
+        if m == 1:
+            p = int(rng.integers(5, L - 5)); k = int(rng.integers(1, 13)); read = (read[:p] + bytearray(rnd(rng, k)) + read[p:])[:L]
+        if m == 2:
+            p = int(rng.integers(5, L - 15)); k = int(rng.integers(1, 13)); read = read[:p] + read[p + k:] + bytearray(rnd(rng, k))
+        if rng.random() < 0.1:
+            read[int(rng.integers(0, L))] = ord("N")
+        read = bytes(read[:L])
+        qual = bytes(palette_quals(rng, L, 94 if rng.random() < 0.33 else 60).tolist())
+        hap = bytes(hap)
+        go = o.gap_open(hap)
+        hapStart = 1000
+        readStart = hapStart + start + (int(rng.integers(-200, 201)) if rng.random() < 0.5 else 0)
+        flank = int(rng.choice([0, 200, 300]))
+        doFlank = int(rng.random() < 0.3) if flank > 0 else 0   # reference dereferences NULL aln when flank==0
+        cands, mapped = calign_drv.dp_diagonals(read, readStart, hapStart, hap)
+        dp = lambda d: ref.dp_score(hap[max(0, d - 8):max(0, d - 8) + L + 15], read, qual, go[max(0, d - 8):max(0, d - 8) + L + 15])
+        scores = {d: dp(d) for d in cands + [mapped]}
+        best, best_d = 1000000, -1                              # calign.pyx:222-267 in plain mode, on the listed diagonals
+        for d in cands:
+            if scores[d] < best:
+                best, best_d = scores[d], d
+                if best == 0:
+                    break
+        if best != 0 and mapped != best_d:
+            best = min(best, scores[mapped])
+        plain = int(calign_drv.map_and_align(read, qual, readStart, hapStart, hap, go, flank, 0))
+        assert plain == best, (len(cases), plain, best)
+        if doFlank and max(scores.values()) >= SATURATED:
+            redrawn += 1
+            continue
+        sc = plain if not doFlank else int(calign_drv.map_and_align(read, qual, readStart, hapStart, hap, go, flank, 1))
+        cases.append(dict(read=read.decode(), qual=qual.hex(), readStart=readStart, hapStart=hapStart, hap=hap.decode(), flank=flank,
+                          doFlank=doFlank, score=sc))
+    with open(os.path.join(out, "mapalign_wide_cases.json.gz"), "wb") as f:
+        with gzip.GzipFile(filename="", mode="wb", fileobj=f, mtime=0) as g:
+            g.write(json.dumps(cases).encode())
+    print("mapalign_wide_cases: %d cases, %d in flank mode (%d drawn again), %d plain scores saturated" % (
+        len(cases), sum(c["doFlank"] for c in cases), redrawn, sum(c["score"] == SATURATED for c in cases)))
+
+
+def ops_of(a1, a2):
+    """An alignment's columns as run-length text (M both bases, I a base of the read only, D a base of the haplotype only): with firstpos
+    and the two sequences it gives the strings back (tests/test_long_read_cases_cpu.py: strings_of)."""
+    out, prev, n = [], "", 0
+    for x, y in zip(a1, a2):
+        c = "I" if x == ord("-") else "D" if y == ord("-") else "M"
+        if c != prev and n:
+            out.append("%d%s" % (n, prev)); n = 0
+        prev = c; n += 1
+    if n:
+        out.append("%d%s" % (n, prev))
+    return "".join(out)
+
+
+def gen_dp_wide(out):
+    """600 rows {haplotype slice, read, qualities, gap-open -> score} with the read lengths of tests/long_read_cases.LADDER, 40 rows each, scored by
+    the unmodified align.c.  Row kinds: a few substitutions; an insertion or a deletion; haplotype N's; a read N; a tandem repeat; a
+    substitution in every 20th base; EVERY base substituted at qualities 60..93 (saturates from about 900 bases on).  Where the score is below
+    15 872 the row also has the traceback (firstpos and the columns as ops_of writes them) and, where it is above 0, calculateFlankScore for a
+    flank of 20; at 15 872 the reference's traceback starts at _backpointers[-1] and nothing of it is recorded (firstpos, flank = -1)."""
+    from oracle.oracle import Oracle, RefAlign
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from long_read_cases import LADDER
+    o, ref = Oracle(), RefAlign()
+    rng = np.random.default_rng(20261021)
+    n, LMAX = 600, max(LADDER)
+    haps = np.zeros((n, LMAX + 15), dtype=np.uint8)
+    reads = np.zeros((n, LMAX), dtype=np.uint8)
+    quals = np.zeros((n, LMAX), dtype=np.uint8)
+    gos = np.zeros((n, LMAX + 15), dtype=np.uint8)
+    lens = np.zeros(n, dtype=np.int32)
+    score = np.zeros(n, dtype=np.int32)
+    firstpos = np.full(n, -1, dtype=np.int32)
+    flank = np.full(n, -1, dtype=np.int32)
+    ops = []
+    for j in range(n):
+        L = int(LADDER[j % len(LADDER)])
+        mode = (j // len(LADDER)) % 8
+        hap = bytearray(tandem(rng, L + 15) if mode == 5 else rnd(rng, L + 15))
+        off = int(rng.integers(0, 16))
+        read = bytearray(hap[off:off + L])
+        if mode == 7:
+            for p in range(L):
+                read[p] = B[(B.index(read[p]) + 1 + int(rng.integers(0, 3))) % 4]
+        else:
+            for p in (range(0, L, 20) if mode == 6 else rng.integers(0, L, int(rng.integers(0, 5)))):
+                read[int(p)] = B[int(rng.integers(0, 4))]
+        if mode in (1, 2, 5):
+            p = int(rng.integers(5, L - 15)); k = int(rng.integers(1, 7))
+            read = (read[:p] + bytearray(rnd(rng, k)) + read[p:])[:L] if mode == 1 else read[:p] + read[p + k:] + bytearray(rnd(rng, k))
+        if mode == 3:
+            for _ in range(3):
+                hap[int(rng.integers(0, L + 15))] = ord("N")
+        if mode == 4:
+            read[int(rng.integers(0, L))] = ord("N")
+        q = 60 + palette_quals(rng, L, 34) if mode == 7 else palette_quals(rng, L)
+        if mode == 0:
+            q[rng.random(L) < 0.2] = 0                          # trimmed bases (cwindow.pyx:415-479 set qual 0)
+        go = np.frombuffer(o.gap_open(bytes(hap))[:L + 15], dtype=np.uint8) if j % 3 else rng.choice(rng.integers(1, 46, 4), L + 15).astype(np.uint8)
+        hs, rs, qs, gs = bytes(hap), bytes(read[:L]), bytes(q.tolist()), bytes(go.tolist())
+        haps[j, :L + 15] = np.frombuffer(hs, dtype=np.uint8)
+        reads[j, :L] = np.frombuffer(rs, dtype=np.uint8)
+        quals[j, :L] = q
+        gos[j, :L + 15] = go
+        lens[j] = L
+        score[j] = ref.dp_score(hs, rs, qs, gs)
+        if score[j] < SATURATED:
+            sc, a1, a2, fp = ref.dp_align(hs, rs, qs, gs)
+            assert sc == score[j]
+            firstpos[j] = fp
+            ops.append(ops_of(a1, a2))
+            if sc > 0:
+                flank[j] = ref.flank_score(L + 15, 20, qs, gs, fp, a1, a2)
+        else:
+            ops.append("")
+    save_npz_fixed(os.path.join(out, "dp_wide_cases.npz"), haps=haps, reads=reads, quals=quals, gos=gos, lens=lens, score=score,
+                   firstpos=firstpos, flank=flank, ops=np.array(ops))
+    print("dp_wide_cases: %d rows, %d saturated, %d with a flank score, %d with a quality sum above 15000" % (
+        n, int((score == SATURATED).sum()), int((flank >= 0).sum()), int((quals.astype(np.int64).sum(axis=1) > 15000).sum())))
+
+
 # ------------------------------------------------------------------------------------------------
 def synth_region(rng, ref_len, nh, L, depth, nvar, in_window=True, low_q=0.05, err=0.002):
     ref = bytearray(rnd(rng, ref_len))
@@ -3370,7 +3582,7 @@ def main():
         sys.exit("reference tree not found at %s: golden vectors can only be regenerated in the build container" % REF)
     subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle")])
     build_scratch(a.scratch)
-    todo = a.only.split(",") if a.only else ["dp", "dpfuzz", "tandem", "mapalign", "assembler", "population", "haplotype", "filter", "hapseq", "candidates", "readqc", "readqcwide", "infostats", "pvalues", "vcf", "regionprep", "regionprepwide", "indelprior", "refcall", "region"]
+    todo = a.only.split(",") if a.only else ["dp", "dpfuzz", "dpwide", "tandem", "mapalign", "mapalignwide", "assembler", "population", "haplotype", "filter", "hapseq", "candidates", "readqc", "readqcwide", "infostats", "pvalues", "vcf", "regionprep", "regionprepwide", "indelprior", "refcall", "region"]
     if "dp" in todo:
         gen_dp(HERE)
     if "dpfuzz" in todo:
@@ -3379,6 +3591,10 @@ def main():
         gen_tandem(HERE)
     if "mapalign" in todo:
         gen_mapalign(HERE)
+    if "mapalignwide" in todo:
+        gen_mapalign_wide(HERE)
+    if "dpwide" in todo:
+        gen_dp_wide(HERE)
     if "assembler" in todo:
         gen_assembler(HERE)
     if "population" in todo:
