@@ -12,36 +12,39 @@
 //   * a node keeps the (up to) four successors with the smallest first-occurrence tickets, in ticket order
 //     (assembler.pyx:813-824: a fifth distinct successor is silently dropped);
 //   * bubble starts are visited in allNodes order, which for REF_AND_READ nodes is increasing position.
-// One workgroup assembles one region; everything an AddEdge event touches lives in the workgroup's LDS (the "LDS path"):
-//   * the k-mer hash table (ASM_LDS_SLOTS slots: byte offsets of representative occurrences while the k-mers are inserted, then
-//     node id << 18 | offset), one word per node for its first touch and one for its colours + the summed weight of its
-//     first-claimed successor slot (ASM_LDS_NODES nodes), and the region's reference bytes (ASM_REF_CACHE);
-//   * phase A inserts the reference's k-mers first, so a k-mer the reference holds is represented by a reference occurrence
-//     and a read's k-mer is compared with its representative in LDS; the reads' bases and qualities are loaded as 256-byte
-//     windows, one aligned dword per lane, and every lane gathers its edge's k+1 bytes from the other lanes (per-lane
-//     unaligned 64-bit loads were bound by the texture addresser); every edge leaves one word (table slot, weight, appended
-//     base) so that phase C neither hashes nor compares: it is a loop over tickets;
-//   * node ids follow the reference (bitmap of representative positions + popcount ranks): reads are sorted by position,
-//     so the few global words an event still updates (successor slots other than a node's first-claimed one) are neighbours
-//     in memory and stay in the L2;
-//   * which node a successor slot leads to is looked up once per slot (phase D), and first tickets -- which only order the
-//     successors of a node that has several -- are collected for those nodes alone in a second pass over the event words.
-// Measured on BASELINE config 3 (2000 tiles, PLAT_ASM_TIMING=1 prints the split): 84 k regions/s with the table in LDS but
-// three global atomics and two hash look-ups per event; 123 k with reference-first insertion + LDS reference + one look-up per
-// event; 141 k with the window loads; 174 k with one global atomic per event; 183 k with ordered ids; 214 k with the
-// first-claimed slot's weight in LDS; 246 k with the slot words kept clean between regions.
-// Round 4 (the fused pass, see "LDS path, fused" below): k-mers and events of the reads in one pass 278 k; the edges that pass the
+// One workgroup assembles one region, on one of two paths.
+// The LDS path (the default shape: k <= 15, at most ASM_LDS_LIMIT distinct k-mers, reference and read blob below 2^18 bytes) keeps
+// everything an AddEdge event touches in the workgroup's LDS:
+//   * the k-mer hash table (ASM_LDS_SLOTS slots of node id << 18 | byte offset of the representative occurrence), one word per node
+//     for its first touch and one for its colours + the summed weight of its first-claimed successor slot (ASM_LDS_NODES nodes), and
+//     the region's reference bytes (ASM_REF_CACHE);
+//   * the reference's k-mers are inserted first, so a k-mer the reference holds is represented by a reference occurrence and a read's
+//     k-mer is compared with its representative in LDS; node ids follow the reference (bitmap of representative positions + popcount
+//     ranks): reads are sorted by position, so the few global words an event still updates (successor slots other than a node's
+//     first-claimed one) are neighbours in memory and stay in the L2;
+//   * the reads' bases and qualities are loaded as 256-byte windows, one aligned dword per lane, and every lane gathers its edge's k+1
+//     bytes from the other lanes (per-lane unaligned 64-bit loads were bound by the texture addresser); ONE pass over the reads finds
+//     or creates an edge's two nodes and applies its event at once, keeping the first ticket and the end node of every successor slot,
+//     so that phase D picks the successors without hashing, comparing or passing over the events again (see "LDS path" below);
+//   * phases D-G then run on the table's LDS: an edge word per node, the bubble walks' stacks and path elements.
+// The global path (the round-1 code) keeps table, node words and successor lists in the workgroup's slice of a global scratch buffer:
+// it takes a region with k > 15, a reference / read blob beyond 2^18 bytes or more distinct k-mers than ASM_LDS_LIMIT (deep or very
+// divergent data) -- the LDS pass hands such a region over when its node arrays fill up half-way.
+// History, measured on BASELINE config 3 (2000 tiles, PLAT_ASM_TIMING=1 prints the split).  Rounds 2-3 built the LDS graph in three passes
+// (insert every k-mer, number the nodes, apply the events from one word per edge, then collect first tickets in a second pass over those
+// words): 84 k regions/s with the table in LDS but three global atomics and two hash look-ups per event; 123 k with reference-first
+// insertion + LDS reference + one look-up per event; 141 k with the window loads; 174 k with one global atomic per event; 183 k with
+// ordered ids; 214 k with the first-claimed slot's weight in LDS; 246 k with the slot words kept clean between regions.
+// Round 4 fused the passes: k-mers and events of the reads in one pass 278 k; the edges that pass the
 // quality rule compacted before the probes 322 k; phases D-G on LDS (edge word per node in the table's space, walk stacks, path
 // elements, one thread per finished path) and the claimed slots' end nodes in a dense array 336 k (768 threads: at 1024 the kernel
 // spilled 139-175 registers to slots that live in HBM); phase boundaries without the L1 invalidate where only plainly stored words
 // are read back (asm_sync_wg) 404 k; per-thread values re-derived per phase + no machine LICM (32 spilled registers) and 1024
-// threads again 449-458 k; colour bits by unconditional LDS atomics, the walk's path array, used slots counted in phase D, one L1 invalidate per region: 545 k, 1.05 GB of
-// HBM traffic per 2000 tiles (round 3: 252 k, 4.76 GB).  A region with more distinct k-mers than ASM_LDS_LIMIT (deep or very divergent data),
-// k > 15, or a reference / read blob beyond 2^18 bytes is done with table, node words and successor lists in the workgroup's
-// slice of a global scratch buffer (the "global path", the round-1 code).
+// threads again 449-458 k; colour bits by unconditional LDS atomics, the walk's path array, used slots counted in phase D, one L1
+// invalidate per region: 545 k, 1.05 GB of HBM traffic per 2000 tiles (round 3: 252 k, 4.76 GB).  The three-pass sequence stayed behind
+// a switch as the comparand of the fused pass until round 15 retired it (profiles/HISTORY.md); the oracle is the comparand now.
 #include "plat_internal.hpp"
 #include "switches.hpp"
-#include <type_traits>
 
 namespace plat {
 
@@ -67,9 +70,8 @@ struct AsmParams {
     int cap;                           // hash slots per region (power of two)
     int max_pos;                       // max k-mer occurrences per region (dense node capacity)
     int timing;                        // PLAT_ASM_TIMING: phase timers on
-    int debug;                         // PLAT_ASM_DEBUG: 1 = no events in the fused reads pass, 2 = no table probes either (measurement only, results are garbage);
-                                       // 4 = walk stacks in the slice and path elements in the global arena, 8 = variants extracted by one thread (tests: same results)
-    int fused;                         // LDS path: k-mers and AddEdge events of the reads in ONE pass (round 4; PLAT_ASM_FUSED=0: rounds 2-3's passes)
+    int debug;                         // PLAT_ASM_DEBUG & 12: 4 = walk stacks in the slice and path elements in the global arena, 8 = variants extracted by
+                                       // one thread (tests: same results)
 };
 
 struct AsmNodeE { int end[4]; int w[4]; int n; };   // finalised out-edges
@@ -323,18 +325,6 @@ template <int KW> __device__ inline int asm_lds_insert_words(int* tab, const Asm
         s = (s + 1u) & (unsigned)(ASM_LDS_SLOTS - 1);
     }
 }
-// lookup phase: slots hold (node id << ASM_OFF_BITS | offset); ids below n_ref_nodes have their representative in the reference
-template <int KW> __device__ inline int asm_lds_node_words(const int* tab, const AsmWords<KW>& K, int k, int n_ref_nodes, const unsigned long long* s_ref, bool refc,
-                                         const uint8_t* ref, const uint8_t* rseq) {
-    unsigned s = asm_hash_words(K, k) & (unsigned)(ASM_LDS_SLOTS - 1);
-    for (;;) {
-        const int v = tab[s];
-        if (v == -1) return -1;
-        const int id = (int)((unsigned)v >> ASM_OFF_BITS), o = v & ((1 << ASM_OFF_BITS) - 1);
-        if (asm_eq_words(K, k, id < n_ref_nodes, o, s_ref, refc, ref, rseq)) return id;
-        s = (s + 1u) & (unsigned)(ASM_LDS_SLOTS - 1);
-    }
-}
 // Fused pass (round 4): the table holds its FINAL words from the start of the reads' pass -- node id << ASM_OFF_BITS | offset of the
 // representative -- so that an edge's nodes are known the moment its k-mers are found: a k-mer met for the first time takes the next
 // read-node id (an id whose insertion loses the race for the slot stays unused: a hole in the node arrays, nothing else).  Returns the
@@ -422,20 +412,6 @@ __device__ __forceinline__ int asm_select64(unsigned long long m, int n) {
     }
     return pos;
 }
-// an 'N' among the edge's k + 1 bases?
-template <int KW> __device__ __forceinline__ bool asm_edge_has_n(const AsmWords<KW>& S, int k) {
-    const int n = k + 1;
-    unsigned long long zero = 0ull;
-#pragma unroll
-    for (int c = 0; c < KW; ++c)
-        if (8 * c < n) {
-            const unsigned long long m = asm_tailmask(n - 8 * c);
-            const unsigned long long x = (S.w[c] ^ 0x4E4E4E4E4E4E4E4Eull) | ~m;
-            zero |= (x - 0x0101010101010101ull) & ~x & 0x8080808080808080ull;
-        }
-    return zero != 0ull;
-}
-
 // exclusive prefix sum of one value per thread over the workgroup (wave scans by lane shifts, the wave totals through `s_wsum`);
 // every thread gets the total too.  All threads must call it.
 __device__ __forceinline__ int asm_block_exscan(int v, int* s_wsum, int& total) {
@@ -470,7 +446,7 @@ __device__ __forceinline__ void asm_sync() {
 // write-through, so nothing can be stale.  The agent-scope invalidate above empties that L1 -- the next phase then fetches everything
 // again from L2, its spilled registers included -- and with ~25 boundaries per region that was a quarter of the kernel's time: it stays
 // only where words updated by L2 ATOMICS are read back by plain loads (the slot words before phase D; every boundary of the
-// three-pass and global paths).
+// global path).
 __device__ __forceinline__ void asm_sync_wg() { __syncthreads(); }
 
 // measurement only (PLAT_ASM_TIMING=1): 100 MHz ticks the first thread of every workgroup spent up to each phase boundary, summed
@@ -491,7 +467,7 @@ k_assemble(plat_assembly_batch b, AsmParams P, char* scratch, int max_ref, int m
         for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < b.n_regions; g += gridDim.x * blockDim.x) { status[g] = (int)verdict[3]; var_count[g] = 0; }
         return;
     }
-    __shared__ int s_n, s_ntasks, s_err, s_cycle, s_k, s_pool, s_distinct, s_lds, s_nrefnodes, s_nreadnodes, s_nv;
+    __shared__ int s_n, s_ntasks, s_err, s_cycle, s_k, s_pool, s_distinct, s_nrefnodes, s_nreadnodes, s_nv;
     extern __shared__ __attribute__((aligned(16))) int s_tab[];  // [ASM_LDS_SLOTS] the k-mer table, then the node words, then the reference
     unsigned* s_first = (unsigned*)(s_tab + ASM_LDS_SLOTS);      // [ASM_LDS_NODES] min touch code (2*ticket + isEnd)
     unsigned* s_wc = s_first + ASM_LDS_NODES;                    // [ASM_LDS_NODES] weight | colour << 30
@@ -510,12 +486,12 @@ k_assemble(plat_assembly_batch b, AsmParams P, char* scratch, int max_ref, int m
     // scratch (address, sizes, the allocation's epoch) -- in wg_sig[blockIdx.x]; the next launch that finds the same value there skips the
     // 1.4 MB of stores below (a third of the kernel's HBM traffic when a launch holds one tile per workgroup, as the region loop's do).
     __shared__ int s_dirty;
-    const bool keep = wg_sig != nullptr && wg_sig[blockIdx.x] == sig && P.debug == 0 && P.fused;
+    const bool keep = wg_sig != nullptr && wg_sig[blockIdx.x] == sig && P.debug == 0;
     __syncthreads();
-    if (tid == 0) { s_dirty = (P.debug != 0 || !P.fused) ? 1 : 0; if (wg_sig) wg_sig[blockIdx.x] = 0ull; }     // (nothing is promised while the launch runs)
+    if (tid == 0) { s_dirty = P.debug != 0 ? 1 : 0; if (wg_sig) wg_sig[blockIdx.x] = 0ull; }     // (nothing is promised while the launch runs)
     if (!keep)
     for (int i = tid; i < ASM_LDS_NODES * ASM_MAX_SUCC; i += nthr) { S.succ_cw[i] = 0ull; S.succ_c[i] = 0; S.succ_t[i] = 0xFFFFFFFFu; }
-    // fused LDS path: the first ticket of a node's LDS-summed slot when a READ claimed it (read-only nodes; a reference-claimed slot's ticket
+    // LDS path: the first ticket of a node's LDS-summed slot when a READ claimed it (read-only nodes; a reference-claimed slot's ticket
     // is the node's position) lives in S.weight[node] -- the LDS path has no other use for that array --, 0xFFFFFFFF between regions
     unsigned* own_t = (unsigned*)S.weight;
     // ... and the node that slot leads to in own_n[node] (S.succ_w, which only the global path sums into): one dense word per node
@@ -541,7 +517,7 @@ k_assemble(plat_assembly_batch b, AsmParams P, char* scratch, int max_ref, int m
         const long long blobLen = nR > 0 ? b.read_off[rb + nR] - rblob0 : 0;
         asm_sync_wg(); ASM_FRESH();
 
-        // Fast path of the phases after the graph is built (round 4; fused LDS path, noCycles off): the k-mer table is not needed once the
+        // Fast path of the phases after the graph is built (round 4; LDS path, noCycles off): the k-mer table is not needed once the
         // successors are picked, so its 64 KB take (a) ONE WORD PER NODE -- end node | weight >= min_weight << 14 | number of out-edges << 15
         // -- which is the whole out-edge list of the nodes with at most one successor (all but the branch points, whose AsmNodeE stays in
         // global memory), (b) the tasks' finished-path counts and (c) the first ASM_LDS_ARENA path elements of the bubble walks.  First
@@ -550,8 +526,8 @@ k_assemble(plat_assembly_batch b, AsmParams P, char* scratch, int max_ref, int m
         // Layout of the table's words on the fast path: [0, nNodes) edge words, then one finished-path count per task, then the tasks' stacks
         // of pending path elements (when they fit: else in the slice), then path elements (node, parent, depth) up to the table's end.
         bool fast = false, ldsStk = false, ldsPath = false;
-        bool relax = false;                                  // the fused LDS path is running: phase boundaries without the L1 invalidate (asm_sync_wg)
-        auto sync_phase = [&]() { if (relax) asm_sync_wg(); else asm_sync(); };
+        bool lds = false;                                    // the LDS pass finished this region's graph (else: the global path) -- its phase
+        auto sync_phase = [&]() { if (lds) asm_sync_wg(); else asm_sync(); };   // boundaries go without the L1 invalidate (asm_sync_wg)
         int* const s_edge = s_tab;
         int* s_tnfin = s_tab; int* s_stk = s_tab; int* s_path = s_tab; int* s_arena = s_tab;
         int arenaCap = 0;
@@ -621,87 +597,28 @@ k_assemble(plat_assembly_batch b, AsmParams P, char* scratch, int max_ref, int m
                     }
                 }
             };
-            // LDS path: the edges of the reads, one read per wave at a time.  A window of 256 bytes of the read's bases and one of its
-            // qualities are loaded one aligned dword per lane; the lanes then take the window's edges in rounds of 64, each gathering
-            // its k+1 bytes from the other lanes.  stage1(i, ro, E, w) -> tag >= 0 for every valid edge; stage2(ticket offset, ro + i,
-            // E, w, tag, tag of the next edge or -1) after the wave has exchanged tags; skipped(ticket offset) for a filtered edge.
-            auto read_pass = [&](auto KWc, auto&& stage1, auto&& stage2, auto&& skipped, auto&& stop) {
-                constexpr int KW = decltype(KWc)::value;
-                const int lane = tid & 63, wv = tid >> 6, nwv = nthr >> 6;
-                constexpr int WIN = 4 * (64 - 2 * KW) - 3;     // edges per window: the last one still finds its 2 KW + 1 dwords in lanes <= 63
-                // A wave's reads are a chain of dependent round trips (the read's offsets, then its bytes): the offsets of the read after
-                // next and the first window of the next read are requested before the current read is worked on.
-                struct Meta { int base, cnt, ro; };
-                struct Win { unsigned dS, dQ; int sS, sQ, nE; };
-                auto load_meta = [&](int r) -> Meta {
-                    Meta m{0, 0, 0};
-                    if (r < nR) { m.base = S.read_base[r]; m.cnt = S.read_base[r + 1] - m.base; m.ro = (int)(b.read_off[rb + r] - rblob0); }
-                    return m;
-                };
-                auto load_win = [&](const Meta& m, int c0) -> Win {
-                    Win w;
-                    w.nE = max(0, min(WIN, m.cnt - c0));
-                    const uintptr_t pS = (uintptr_t)(rseq + m.ro + c0), pQ = (uintptr_t)(rqual + m.ro + c0);
-                    w.sS = (int)(pS & 3); w.sQ = (int)(pQ & 3);
-                    // (lanes past the window's last needed byte load nothing: the blobs' slack is a few bytes, not a window)
-                    w.dS = (w.nE > 0 && 4 * lane < w.sS + w.nE + k + 1) ? *(const unsigned*)((pS & ~(uintptr_t)3) + 4 * lane) : 0u;
-                    w.dQ = (w.nE > 0 && 4 * lane < w.sQ + w.nE + k + 1) ? *(const unsigned*)((pQ & ~(uintptr_t)3) + 4 * lane) : 0u;
-                    return w;
-                };
-                Meta m0 = load_meta(wv), m1 = load_meta(wv + nwv);
-                Win w0 = load_win(m0, 0);
-                for (int r = wv; r < nR; r += nwv) {
-                    const Meta m2 = load_meta(r + 2 * nwv);
-                    const Win w1 = load_win(m1, 0);
-                    const int base = m0.base, cnt = m0.cnt, ro = m0.ro;
-                    for (int c0 = 0; c0 < cnt; c0 += WIN) {
-                        if (stop()) return;
-                        const Win w = c0 == 0 ? w0 : load_win(m0, c0);
-                        const int nE = w.nE;
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) {
-                            if (64 * u < nE) {                              // wave-uniform
-                                if (u > 0 && stop()) return;                // (checked every round: between two checks the workgroup inserts
-                                                                            //  at most 2 x 1024 k-mers, which the table's spare slots take)
-                                const int j = 64 * u + lane, i = c0 + j;
-                                const AsmWords<KW> E = asm_mask_words(asm_gather_words<KW>(w.dS, j + w.sS), k + 1);
-                                const AsmWords<KW> Q = asm_mask_words(asm_gather_words<KW>(w.dQ, j + w.sQ), k + 1);
-                                int wq = -1, tag = -1;
-                                if (j < nE) {
-                                    wq = asm_edge_q_words(E, Q, k, P.min_qual);
-                                    if (wq == -2) wq = asm_read_edge_q(rseq + ro, rqual + ro, i, k, P.min_qual);
-                                    if (wq >= 0) tag = stage1(i, ro, E, wq);
-                                }
-                                int ntag = __shfl_down(tag, 1);
-                                if (lane == 63) ntag = -1;
-                                if (wq >= 0) stage2(base + i, ro + i, E, wq, tag, ntag);
-                                else if (j < nE) skipped(base + i);
-                            }
-                        }
-                    }
-                    m0 = m1; m1 = m2; w0 = w1;
-                }
-            };
-            // ---- phase A: insert every k-mer that takes part in a (valid) edge; LDS table first, the global one if it overflows
-            // (or if k, the reference or the reads' bytes are beyond what the LDS path packs into its words)
-            if (tid == 0) s_lds = (k <= 15 && nRefE < ASM_LDS_LIMIT && refLen < (1 << ASM_OFF_BITS) && blobLen < (1ll << ASM_OFF_BITS)) ? 1 : 0;
-            __syncthreads();
-            // ---- LDS path, fused (round 4).  Rounds 2-3 inserted every k-mer (phase A), numbered the nodes (B), and only then ran the AddEdge
-            // events (C) from one 4-byte word per edge that phase A had left in global memory -- 0.5 MB per region written, read, and read
-            // again for the first tickets (D): two thirds of the kernel's HBM traffic.  Now:
-            //   1. the reference's k-mers are inserted and its nodes numbered along the reference (bitmap + ranks, as before); the table then
-            //      holds final words;
+            // ---- LDS path: phases A-C in one go -- k-mers found or created, nodes numbered and AddEdge events applied as the edges are met.
+            // (Rounds 2-3 did this in three passes -- insert every k-mer, number the nodes, then run the events from one 4-byte word per edge
+            // that the insert pass had left in global memory, 0.5 MB per region written, read, and read again for the first tickets: two thirds
+            // of the kernel's HBM traffic.  Round 4 fused the passes; the three-pass sequence was retired in round 15.)
+            //   1. the reference's k-mers are inserted first -- a k-mer the reference holds is then represented by a reference occurrence and
+            //      compared in the LDS copy of the reference -- and its nodes numbered along the reference (a bitmap of the representatives'
+            //      positions + popcount ranks, when the LDS has room for it): reads arrive sorted by position and walk along the reference, so
+            //      the global slot words they update are neighbours in memory and stay in the L2.  The table then holds final words;
             //   2. the reference's events: first touches, barrier -- every reference node's position is final, reads only come later --, then
-            //      the successor slots: the edge that leaves a node at its FIRST reference occurrence claims the node's LDS-summed slot (bit
-            //      27 of its word); its first ticket is the node's position and needs no word of its own.  Edges of later occurrences (repeats)
-            //      take the global slot words, with their first ticket (atomicMin);
+            //      the successor slots.  The slot is picked by the byte the edge appends (A, C, G, T: slots 0..3 by the byte's bits; anything
+            //      else shares slots 4..7 by search).  The weight of a node's FIRST-CLAIMED slot is summed in the node's LDS word (bits 0..22,
+            //      the slot + 1 in bits 23..25): the edges along the path most reads take never leave the CU.  Other slots, and a sum about
+            //      to leave its 23 bits, take one global atomic on the slot's (event count, weight) word.  The edge that leaves a node at its
+            //      FIRST reference occurrence claims the LDS-summed slot (bit 27 of the word); its first ticket is the node's position and
+            //      needs no word of its own.  Edges of later occurrences (repeats) take the global slot words, with their first ticket (atomicMin);
             //   3. the reads, ONE pass: an edge finds or creates its two nodes (asm_lds_insert_final) and is applied at once.  First tickets are
             //      kept (one global atomicMin) for every slot but a reference-claimed LDS slot, whose ticket no read can lower;
             //   4. phase D picks the successors from those tickets: no pass over the events, no event words for the reads at all.
-            bool fused_done = false;
-            relax = false;
-            if (P.fused && s_lds) {
-                relax = true;
+            // A region whose k, reference or read bytes are beyond what the table's words pack does not start it, and a region that turns out
+            // to have more nodes than the LDS takes leaves it half-way: both are built on the global path below.
+            lds = false;
+            if (k <= 15 && nRefE < ASM_LDS_LIMIT && refLen < (1 << ASM_OFF_BITS) && blobLen < (1ll << ASM_OFF_BITS)) {
                 for (int i = tid; i < ASM_LDS_SLOTS; i += nthr) s_tab[i] = -1;
                 for (int i = tid; i < ASM_LDS_NODES; i += nthr) { s_first[i] = 0xFFFFFFFFu; s_wc[i] = 0u; }
                 if (tid == 0) { s_distinct = 0; s_nrefnodes = 0; s_nreadnodes = 0; }
@@ -748,7 +665,6 @@ k_assemble(plat_assembly_batch b, AsmParams P, char* scratch, int max_ref, int m
                     }
                 }
                 __syncthreads();
-                if (tid == 0) s_nrefnodes = nRefNodes0;
                 auto node_of = [&](int slot) -> int { return (int)((unsigned)s_tab[slot] >> ASM_OFF_BITS); };
                 // slot of a successor byte; bytes other than A, C, G, T share slots 4..7 (claimed in the node's global byte word)
                 auto succ_slot = [&](int sn, unsigned c) -> int {
@@ -808,10 +724,13 @@ k_assemble(plat_assembly_batch b, AsmParams P, char* scratch, int max_ref, int m
                 {
                     const int lane = tid & 63, wv = tid >> 6, nwv = nthr >> 6;
                     // A wave takes one read at a time; a window of 256 bytes of its bases and of its qualities is held one aligned dword per
-                    // lane (as in read_pass).  The window's edges that pass the quality / N rule are compacted and worked NRB rounds of 64 side by
-                    // side (`work` below): the pass is bound by vector issue plus chains of LDS round trips (gather -> table -> representative ->
-                    // node words), and independent chains per lane share each wait (four rounds at once spilled registers: two are kept).
-                    constexpr int WIN = 4 * (64 - 2 * KW) - 3;
+                    // lane, and every lane gathers its edge's k+1 bytes from the other lanes.  The window's edges that pass the quality / N rule
+                    // are compacted and worked NRB rounds of 64 side by side (`work` below): the pass is bound by vector issue plus chains of LDS
+                    // round trips (gather -> table -> representative -> node words), and independent chains per lane share each wait (four rounds
+                    // at once spilled registers: two are kept).  A wave's reads are a chain of dependent round trips (the read's offsets, then its
+                    // bytes): the offsets of the read after next and the first window of the next read are requested before the current read is
+                    // worked on.
+                    constexpr int WIN = 4 * (64 - 2 * KW) - 3;     // edges per window: the last one still finds its 2 KW + 1 dwords in lanes <= 63
                     struct Meta { int base, cnt, ro; };
                     struct Win { unsigned dS, dQ; int sS, sQ, nE; };
                     auto load_meta = [&](int r) -> Meta {
@@ -824,6 +743,7 @@ k_assemble(plat_assembly_batch b, AsmParams P, char* scratch, int max_ref, int m
                         w.nE = max(0, min(WIN, m.cnt - c0));
                         const uintptr_t pS = (uintptr_t)(rseq + m.ro + c0), pQ = (uintptr_t)(rqual + m.ro + c0);
                         w.sS = (int)(pS & 3); w.sQ = (int)(pQ & 3);
+                        // (lanes past the window's last needed byte load nothing: the blobs' slack is a few bytes, not a window)
                         w.dS = (w.nE > 0 && 4 * lane < w.sS + w.nE + k + 1) ? *(const unsigned*)((pS & ~(uintptr_t)3) + 4 * lane) : 0u;
                         w.dQ = (w.nE > 0 && 4 * lane < w.sQ + w.nE + k + 1) ? *(const unsigned*)((pQ & ~(uintptr_t)3) + 4 * lane) : 0u;
                         return w;
@@ -861,7 +781,7 @@ k_assemble(plat_assembly_batch b, AsmParams P, char* scratch, int max_ref, int m
                                 }
                                 ASM_SEC(2);
                                 // the start k-mers, found or created: NRB probe sequences per lane side by side
-                                if (!(P.debug & 2)) {
+                                {
                                     unsigned sl[NRB]; bool todo[NRB];
                                     AsmWords<KW> Ks[NRB];
 #pragma unroll
@@ -911,7 +831,7 @@ k_assemble(plat_assembly_batch b, AsmParams P, char* scratch, int max_ref, int m
                                 }
 #pragma unroll
                                 for (int u = 0; u < NRB; ++u) {
-                                    if (jj[u] < 0 || slots[u] < 0 || (P.debug & 1)) continue;
+                                    if (jj[u] < 0 || slots[u] < 0) continue;
                                     const int off = ro + c0 + jj[u];
                                     int nslot = nsl[u];
                                     if (nslot < 0) nslot = asm_lds_insert_final(s_tab, asm_kmer_end(E[u], k), k, off + 1, s_ref, refc, ref, rseq, nRefNodes0, &s_nreadnodes, S.rep);
@@ -1029,428 +949,165 @@ k_assemble(plat_assembly_batch b, AsmParams P, char* scratch, int max_ref, int m
                         if (s_wc[n] >> 26 & 1u)
                             for (int j = 0; j < ASM_MAX_SUCC; ++j) { S.succ_cw[n * ASM_MAX_SUCC + j] = 0ull; S.succ_c[n * ASM_MAX_SUCC + j] = 0; S.succ_t[n * ASM_MAX_SUCC + j] = 0xFFFFFFFFu; }
                     }
-                    __syncthreads();
-                    if (tid == 0) s_lds = 0;
-                    relax = false;
                 } else {
                     if (tid == 0) s_n = nRefNodes0 + s_nreadnodes;
-                    fused_done = true;
+                    lds = true;
                 }
                 asm_sync(); ASM_FRESH();
                 ASM_TICK(2);
             }
-            bool failed = false;
-            for (;;) {
-                if (fused_done) break;
-                if (tid == 0) s_dirty = 1;                   // (the three-pass and global paths tidy up too, but only the fused path's word is given across launches)
-                const bool lds = s_lds != 0;
-                if (lds) { for (int i = tid; i < ASM_LDS_SLOTS; i += nthr) s_tab[i] = -1; if (tid == 0) s_distinct = 0; }
-                else {
-                    if ((long long)nEv * 4 > (long long)P.cap * 3) { failed = true; break; }
-                    for (int i = tid; i < P.cap; i += nthr) S.key[i] = -1;
+            // ---- global path, phase A: insert every k-mer that takes part in a (valid) edge
+            if (!lds) {
+                if (tid == 0) s_dirty = 1;                   // (the global path tidies up too, but only the LDS path's word is given across launches)
+                if ((long long)nEv * 4 > (long long)P.cap * 3) {
+                    if (tid == 0) s_err = PLAT_ERR_OVERFLOW;
+                    asm_sync(); ASM_FRESH();
+                    break;
                 }
+                for (int i = tid; i < P.cap; i += nthr) S.key[i] = -1;
                 asm_sync(); ASM_FRESH();
-                if (lds) {
-                    // every edge leaves a word for phase C: table slot of its start k-mer | weight << 14 | appended base << 22 |
-                    // (its end k-mer was inserted by this edge and its slot is in ev_end) << 30;  -1 for a filtered edge
-                    int* ev = S.stack;
-                    int* ev_end = S.stack + P.max_pos;
-                    auto insert_all = [&](auto KWc) {
-                        constexpr int KW = decltype(KWc)::value;
-                        // the reference's k-mers first: a k-mer the reference holds is then represented by a reference occurrence, and
-                        // comparing a read's k-mer with its representative reads the LDS copy of the reference
-                        for (int e = tid; e < nRefE; e += nthr) {
-                            const AsmWords<KW> E = refc ? asm_load_words_lds<KW>(s_ref, e, k + 1) : asm_load_words<KW>(ref + e, k + 1);
-                            const int slot = asm_lds_insert_words(s_tab, asm_kmer_start(E, k), k, e, s_ref, refc, ref, rseq, &s_distinct);
-                            int word = slot | 1 << 14 | (int)(asm_byte_k(E, k) & 0xFFu) << 22;
-                            if (e == nRefE - 1) {
-                                ev_end[e] = asm_lds_insert_words(s_tab, asm_kmer_end(E, k), k, e + 1, s_ref, refc, ref, rseq, &s_distinct);
-                                word |= 1 << 30;
-                            }
-                            ev[e] = word;
-                        }
-                        __syncthreads();
-                        // the reads: the end k-mer of an edge is the start k-mer of the next one, which inserts it unless it is filtered
-                        read_pass(KWc,
-                            [&](int i, int ro, const AsmWords<KW>& E, int w) -> int {
-                                (void)w;
-                                return asm_lds_insert_words(s_tab, asm_kmer_start(E, k), k, 0x40000000 + ro + i, s_ref, refc, ref, rseq, &s_distinct);
-                            },
-                            [&](int t, int off, const AsmWords<KW>& E, int w, int slot, int nslot) {
-                                int word = slot | (w & 0xFF) << 14 | (int)(asm_byte_k(E, k) & 0xFFu) << 22;
-                                if (nslot < 0) {
-                                    ev_end[nRefE + t] = asm_lds_insert_words(s_tab, asm_kmer_end(E, k), k, 0x40000000 + off + 1, s_ref, refc, ref, rseq, &s_distinct);
-                                    word |= 1 << 30;
-                                }
-                                ev[nRefE + t] = word;
-                            },
-                            [&](int t) { ev[nRefE + t] = -1; },
-                            [&]() -> bool { return *(volatile int*)&s_distinct > ASM_LDS_LIMIT; });
-                    };
-                    insert_all(std::integral_constant<int, 2>{});
-                } else {
-                    for_each_event([&](int e, int so, int eo, int col, int w) -> bool {
-                        (void)w;
-                        asm_slot(S, ref, rseq, so, k, capmask, true);
-                        if (col == 2 || e == nRefE - 1) asm_slot(S, ref, rseq, eo, k, capmask, true);
-                        return true;
-                    });
-                }
+                for_each_event([&](int e, int so, int eo, int col, int w) -> bool {
+                    (void)w;
+                    asm_slot(S, ref, rseq, so, k, capmask, true);
+                    if (col == 2 || e == nRefE - 1) asm_slot(S, ref, rseq, eo, k, capmask, true);
+                    return true;
+                });
                 asm_sync(); ASM_FRESH();
-                if (!lds || s_distinct <= ASM_LDS_LIMIT) break;
-                __syncthreads();
-                if (tid == 0) s_lds = 0;                                    // more distinct k-mers than the LDS table takes: global table
-                __syncthreads();
-            }
-            if (failed) {
-                if (tid == 0) s_err = PLAT_ERR_OVERFLOW;
-                asm_sync(); ASM_FRESH();
-                break;
             }
             ASM_TICK(1);
-            const bool lds = s_lds != 0;
-            // ---- phase B: dense node ids + field initialisation
-            auto init_node = [&](int id, int rep_off) {
-                S.rep[id] = rep_off;
-                if (lds) return;                          // (first touch / colours come from the LDS words; the slot words are clean)
-                S.first[id] = 0xFFFFFFFFu; S.weight[id] = 0; S.colour[id] = 0;
-                for (int j = 0; j < ASM_MAX_SUCC; ++j) {
-                    S.succ_c[id * ASM_MAX_SUCC + j] = 0; S.succ_t[id * ASM_MAX_SUCC + j] = 0xFFFFFFFFu;
-                    S.succ_w[id * ASM_MAX_SUCC + j] = 0; S.succ_n[id * ASM_MAX_SUCC + j] = -1;
-                }
-            };
-            if (fused_done) {
-                // (the fused pass numbered the nodes as it went)
-            } else if (lds) {
-                // Nodes represented by a reference occurrence get the low ids (a slot then tells where its representative lives), in the
-                // order of their representatives along the reference when the LDS has room for a bitmap of the positions: reads arrive
-                // sorted by position and walk along the reference, so the successor slots they update then lie next to each other in
-                // memory and stay in the L2 (with ids in table order every update was an L2 miss).
-                const int refBytes = ((refLen + 16 + 7) >> 3) << 3, nW32 = (refLen >> 5) + 1;
-                const bool ordered = refc && refBytes + 8 * nW32 <= ASM_REF_CACHE && nW32 <= nthr;
-                unsigned* s_bm = (unsigned*)((char*)s_ref + refBytes);       // [nW32] bit p: reference position p represents a node
-                unsigned* s_bp = s_bm + nW32;                                // [nW32] nodes before the word
-                if (tid == 0) { s_nrefnodes = 0; s_nreadnodes = 0; }
-                if (ordered) for (int i = tid; i < nW32; i += nthr) s_bm[i] = 0u;
-                __syncthreads();
-                int nRefNodes0;
-                if (ordered) {
-                    for (int sidx = tid; sidx < ASM_LDS_SLOTS; sidx += nthr) {
-                        const int off = s_tab[sidx];
-                        if (off != -1 && off < 0x40000000) atomicOr(&s_bm[off >> 5], 1u << (off & 31));
+            // ---- global path, phase B: dense node ids + field initialisation (the LDS pass numbered its nodes as it went)
+            if (!lds) {
+                auto init_node = [&](int id, int rep_off) {
+                    S.rep[id] = rep_off;
+                    S.first[id] = 0xFFFFFFFFu; S.weight[id] = 0; S.colour[id] = 0;
+                    for (int j = 0; j < ASM_MAX_SUCC; ++j) {
+                        S.succ_c[id * ASM_MAX_SUCC + j] = 0; S.succ_t[id * ASM_MAX_SUCC + j] = 0xFFFFFFFFu;
+                        S.succ_w[id * ASM_MAX_SUCC + j] = 0; S.succ_n[id * ASM_MAX_SUCC + j] = -1;
                     }
-                    __syncthreads();
-                    const int mine = tid < nW32 ? __popc(s_bm[tid]) : 0;
-                    const int before = asm_block_exscan(mine, s_wsum, nRefNodes0);
-                    if (tid < nW32) s_bp[tid] = (unsigned)before;
-                    __syncthreads();
-                } else {
-                    int mine = 0;
-                    for (int sidx = tid; sidx < ASM_LDS_SLOTS; sidx += nthr) { const int off = s_tab[sidx]; mine += off != -1 && off < 0x40000000; }
-                    if (mine) atomicAdd(&s_nrefnodes, mine);
-                    __syncthreads();
-                    nRefNodes0 = s_nrefnodes;
-                    __syncthreads();
-                    if (tid == 0) s_nrefnodes = 0;
-                    __syncthreads();
-                }
-                for (int sidx = tid; sidx < ASM_LDS_SLOTS; sidx += nthr) {
-                    const int off = s_tab[sidx];
-                    if (off != -1) {
-                        const bool isref = off < 0x40000000;
-                        int id;
-                        if (!isref) id = nRefNodes0 + atomicAdd(&s_nreadnodes, 1);
-                        else if (ordered) id = (int)s_bp[off >> 5] + __popc(s_bm[off >> 5] & ((1u << (off & 31)) - 1u));
-                        else id = atomicAdd(&s_nrefnodes, 1);
-                        init_node(id, off);
-                        s_tab[sidx] = (int)(((unsigned)id << ASM_OFF_BITS) | (unsigned)(isref ? off : off - 0x40000000));
-                        s_first[id] = 0xFFFFFFFFu; s_wc[id] = 0u;
-                    }
-                }
-                __syncthreads();
-                if (tid == 0) { s_nrefnodes = nRefNodes0; s_n = nRefNodes0 + s_nreadnodes; }
-            } else {
+                };
                 for (int sidx = tid; sidx < P.cap; sidx += nthr)
                     if (S.key[sidx] != -1) { const int id = atomicAdd(&s_n, 1); S.slot_id[sidx] = id; init_node(id, S.key[sidx]); }
             }
-            if (fused_done) asm_sync_wg(); else asm_sync();       // (fused: only s_n, in LDS, was written since the fence that ended the pass over the reads)
-            ASM_FRESH();
+            sync_phase(); ASM_FRESH();
             ASM_TICK(2);
             const int nNodes = s_n;
-            // ---- phase C: AddEdge events (assembler.pyx:801-827)
-            const int nRefNodes = s_nrefnodes;
-            if (fused_done) {
-                // (... and applied the events)
-            } else if (lds) {
-                // one event per thread, from the word phase A left: node words in LDS; the successor slot of the start node is picked by the
-                // byte the edge appends (A, C, G, T: slots 0..3 by the byte's bits; anything else shares slots 4..7 by search), and takes ONE
-                // global atomic: its event count and weight.  Which node a slot leads to is looked up once per slot in phase D; first
-                // tickets only matter where a node has several successors and are collected for those nodes alone in a second pass.
-                const int* ev = S.stack;
-                const int* ev_end = S.stack + P.max_pos;
-                // (four tickets per thread and trip, their words loaded before the first is used)
-                for (int e0 = tid; e0 < nEv; e0 += 4 * nthr) {
-                  int words[4], nexts[4];
-#pragma unroll
-                  for (int u = 0; u < 4; ++u) {
-                      const int e = e0 + u * nthr;
-                      words[u] = e < nEv ? ev[e] : -1;
-                      nexts[u] = e + 1 < nEv ? ev[e + 1] : -1;
-                  }
-#pragma unroll
-                  for (int u = 0; u < 4; ++u) {
-                    const int e = e0 + u * nthr, word = words[u];
-                    if (word < 0) continue;
-                    const int w = (word >> 14) & 0xFF, col = e < nRefE ? 1 : 2;
-                    const unsigned c = (unsigned)(word >> 22) & 0xFFu;
-                    const int sn = (int)((unsigned)s_tab[word & 0x3FFF] >> ASM_OFF_BITS);
-                    const int en = (int)((unsigned)s_tab[(word >> 30 & 1) ? ev_end[e] : (nexts[u] & 0x3FFF)] >> ASM_OFF_BITS);
-                    atomicMin(&s_first[sn], 2u * (unsigned)e);
-                    atomicMin(&s_first[en], 2u * (unsigned)e + 1u);
-                    // (a node's own weight, assembler.pyx:795, is never read again: only its colours are kept)
-                    unsigned x = s_wc[sn];
-                    if ((x >> 30 & (unsigned)col) == 0u) atomicOr(&s_wc[sn], (unsigned)col << 30);
-                    if ((s_wc[en] >> 30 & (unsigned)col) == 0u) atomicOr(&s_wc[en], (unsigned)col << 30);
+            // ---- global path, phase C: AddEdge events (assembler.pyx:801-827; the LDS pass applied its own)
+            if (!lds) {
+                for_each_event([&](int e, int so, int eo, int col, int w) -> bool {
+                    const int sn = S.slot_id[asm_slot(S, ref, rseq, so, k, capmask, false)];
+                    const int en = S.slot_id[asm_slot(S, ref, rseq, eo, k, capmask, false)];
+                    atomicMin(&S.first[sn], 2u * (unsigned)e);
+                    atomicMin(&S.first[en], 2u * (unsigned)e + 1u);
+                    atomicAdd(&S.weight[sn], w); atomicAdd(&S.weight[en], w);
+                    atomicOr(&S.colour[sn], col); atomicOr(&S.colour[en], col);
                     if (e < nRefE) { S.ref_node[e] = sn; if (e == nRefE - 1) S.ref_node[e + 1] = en; }
+                    // successor slot keyed by the byte appended to the start k-mer
+                    const unsigned char c = asm_ptr(ref, rseq, eo)[k - 1];
+                    unsigned* cw = (unsigned*)(S.succ_c + (size_t)sn * ASM_MAX_SUCC);       // 8 bytes = 2 dwords
                     int slot = -1;
-                    if (c == 'A' || c == 'C' || c == 'G' || c == 'T') slot = (int)((c >> 1) & 3u);
-                    else {
-                        unsigned* cw = (unsigned*)(S.succ_c + (size_t)sn * ASM_MAX_SUCC) + 1;         // bytes 4..7
-                        for (int j = 0; j < 4 && slot < 0; ++j) {
-                            for (;;) {
-                                const unsigned wd = *(volatile unsigned*)cw;
-                                const unsigned cur = (wd >> (8 * j)) & 0xFFu;
-                                if (cur == c) { slot = 4 + j; break; }
-                                if (cur != 0u) break;
-                                const unsigned old = atomicCAS(cw, wd, wd | (c << (8 * j)));
-                                if (old == wd) { slot = 4 + j; break; }
-                            }
-                        }
-                        if (slot < 0) { s_err = PLAT_ERR_UNSUPPORTED; continue; }                     // > 4 distinct other bytes
-                        if (!(x >> 26 & 1u)) atomicOr(&s_wc[sn], 1u << 26);                           // the node's global slot words are in use
-                    }
-                    // The weight of the node's FIRST-CLAIMED successor slot is summed in the node's LDS word (bits 0..22, the slot + 1 in
-                    // bits 23..25): the edges along the path most reads take never leave the CU.  Other slots, and a sum about to leave
-                    // its 23 bits, take a global atomic on the slot's (event count, weight) word.
-                    bool local = false;
-                    if (slot < 7) {
+                    for (int j = 0; j < ASM_MAX_SUCC && slot < 0; ++j) {
                         for (;;) {
-                            const unsigned d = (x >> 23) & 7u;
-                            if (d == 0u) {
-                                const unsigned old = atomicCAS(&s_wc[sn], x, x | (unsigned)(slot + 1) << 23);
-                                x = old == x ? (x | (unsigned)(slot + 1) << 23) : old;
-                                continue;
-                            }
-                            local = d == (unsigned)slot + 1u && (x & 0x7FFFFFu) < 0x780000u;
-                            break;
+                            const unsigned word = cw[j >> 2];
+                            const unsigned cur = (word >> (8 * (j & 3))) & 0xFFu;
+                            if (cur == c) { slot = j; break; }
+                            if (cur != 0u) break;
+                            const unsigned old = atomicCAS(&cw[j >> 2], word, word | ((unsigned)c << (8 * (j & 3))));
+                            if (old == word) { slot = j; break; }
                         }
                     }
-                    if (local) atomicAdd(&s_wc[sn], (unsigned)w);
-                    else {
-                        if (!(x >> 26 & 1u)) atomicOr(&s_wc[sn], 1u << 26);                           // (bit 26: global slot words in use)
-                        atomicAdd(&S.succ_cw[sn * ASM_MAX_SUCC + slot], (1ull << 32) | (unsigned long long)(unsigned)w);
-                    }
-                  }
-                }
-            } else
-            for_each_event([&](int e, int so, int eo, int col, int w) -> bool {
-                const int sn = S.slot_id[asm_slot(S, ref, rseq, so, k, capmask, false)];
-                const int en = S.slot_id[asm_slot(S, ref, rseq, eo, k, capmask, false)];
-                atomicMin(&S.first[sn], 2u * (unsigned)e);
-                atomicMin(&S.first[en], 2u * (unsigned)e + 1u);
-                atomicAdd(&S.weight[sn], w); atomicAdd(&S.weight[en], w);
-                atomicOr(&S.colour[sn], col); atomicOr(&S.colour[en], col);
-                if (e < nRefE) { S.ref_node[e] = sn; if (e == nRefE - 1) S.ref_node[e + 1] = en; }
-                // successor slot keyed by the byte appended to the start k-mer
-                const unsigned char c = asm_ptr(ref, rseq, eo)[k - 1];
-                unsigned* cw = (unsigned*)(S.succ_c + (size_t)sn * ASM_MAX_SUCC);       // 8 bytes = 2 dwords
-                int slot = -1;
-                for (int j = 0; j < ASM_MAX_SUCC && slot < 0; ++j) {
-                    for (;;) {
-                        const unsigned word = cw[j >> 2];
-                        const unsigned cur = (word >> (8 * (j & 3))) & 0xFFu;
-                        if (cur == c) { slot = j; break; }
-                        if (cur != 0u) break;
-                        const unsigned old = atomicCAS(&cw[j >> 2], word, word | ((unsigned)c << (8 * (j & 3))));
-                        if (old == word) { slot = j; break; }
-                    }
-                }
-                if (slot < 0) { s_err = PLAT_ERR_UNSUPPORTED; return true; }             // > 8 distinct successor bytes
-                // (a stale look at the ticket only costs the atomic it could have saved)
-                if (S.succ_t[sn * ASM_MAX_SUCC + slot] > (unsigned)e) atomicMin(&S.succ_t[sn * ASM_MAX_SUCC + slot], (unsigned)e);
-                atomicAdd(&S.succ_w[sn * ASM_MAX_SUCC + slot], w);
-                S.succ_n[sn * ASM_MAX_SUCC + slot] = en;
-                return true;
-            });
-            if (!fused_done) { asm_sync(); ASM_FRESH(); }        // (fused: phase C is empty)
+                    if (slot < 0) { s_err = PLAT_ERR_UNSUPPORTED; return true; }             // > 8 distinct successor bytes
+                    // (a stale look at the ticket only costs the atomic it could have saved)
+                    if (S.succ_t[sn * ASM_MAX_SUCC + slot] > (unsigned)e) atomicMin(&S.succ_t[sn * ASM_MAX_SUCC + slot], (unsigned)e);
+                    atomicAdd(&S.succ_w[sn * ASM_MAX_SUCC + slot], w);
+                    S.succ_n[sn * ASM_MAX_SUCC + slot] = en;
+                    return true;
+                });
+                asm_sync(); ASM_FRESH();
+            }
             ASM_TICK(3);
-            fast = lds && fused_done && !P.no_cycles;
+            fast = lds && !P.no_cycles;
             if (lds && !fast) {                                               // the node words the later phases read, to the slice
-                for (int n = tid; n < nNodes; n += nthr) { S.first[n] = s_first[n]; if (!fused_done) S.weight[n] = 0; S.colour[n] = (int)(s_wc[n] >> 30); }
+                for (int n = tid; n < nNodes; n += nthr) { S.first[n] = s_first[n]; S.colour[n] = (int)(s_wc[n] >> 30); }
                 asm_sync(); ASM_FRESH();
             }
             ASM_TICK(9);
             // ---- phase D: per node, the four successors with the smallest first tickets, in ticket order
             if (lds) {
-                // nodes with more than one successor slot in use (few): their slots' first tickets from a second pass over the events
-                // (the fused path counts a node's used slots where it picks them, from the slot words it has loaded anyway: no pass here)
-                for (int n = tid; n < nNodes && !fused_done; n += nthr) {
-                    if (!(s_wc[n] >> 26 & 1u)) continue;               // only its LDS slot, or none
-                    int used = 0;
-                    const int own = (int)(s_wc[n] >> 23 & 7u) - 1;      // the slot summed in the LDS word, -1 none
-                    for (int j = 0; j < ASM_MAX_SUCC; ++j) used += j == own || (S.succ_cw[n * ASM_MAX_SUCC + j] >> 32) != 0ull;
-                    if (used > 1) {
-                        s_wc[n] |= 1u << 29;
-                        if (!fused_done) for (int j = 0; j < ASM_MAX_SUCC; ++j) S.succ_t[n * ASM_MAX_SUCC + j] = 0xFFFFFFFFu;
-                    }
-                }
-                if (!fused_done) { sync_phase(); ASM_FRESH(); }
-                ASM_TICK(10);
-                if (!fused_done) {                                  // (the fused pass kept the first tickets as it went)
-                    const int* ev = S.stack;
-                    for (int e0 = tid; e0 < nEv; e0 += 4 * nthr) {
-                      int words[4];
+                // LDS path: every used slot knows its end node (own_n, succ_n) and its first ticket, and a node's used slots are counted here from
+                // the slot words loaded anyway; nothing was written since the fence that ended the pass over the reads.  Eight nodes per thread
+                // and trip, the one global word most of them need -- the end of their only slot -- requested for all eight before the first is used
+                constexpr int DB = 8;
+                for (int n0 = tid; n0 < nNodes; n0 += DB * nthr) {
+                    unsigned xs[DB]; int ends[DB];
 #pragma unroll
-                      for (int u = 0; u < 4; ++u) words[u] = e0 + u * nthr < nEv ? ev[e0 + u * nthr] : -1;
-#pragma unroll
-                      for (int u = 0; u < 4; ++u) {
-                        const int e = e0 + u * nthr, word = words[u];
-                        if (word < 0) continue;
-                        const int sn = (int)((unsigned)s_tab[word & 0x3FFF] >> ASM_OFF_BITS);
-                        if (!(s_wc[sn] >> 29 & 1u)) continue;
-                        const unsigned c = (unsigned)(word >> 22) & 0xFFu;
-                        int slot = -1;
-                        if (c == 'A' || c == 'C' || c == 'G' || c == 'T') slot = (int)((c >> 1) & 3u);
-                        else for (int j = 4; j < ASM_MAX_SUCC; ++j) if (S.succ_c[sn * ASM_MAX_SUCC + j] == c) slot = j;
-                        if (slot >= 0) atomicMin(&S.succ_t[sn * ASM_MAX_SUCC + slot], (unsigned)e);
-                      }
+                    for (int u = 0; u < DB; ++u) {
+                        const int n = n0 + u * nthr;
+                        xs[u] = n < nNodes ? s_wc[n] : 0u;
+                        const int own = (int)(xs[u] >> 23 & 7u) - 1;
+                        ends[u] = (n < nNodes && own >= 0) ? own_n[n] : -1;
                     }
-                }
-                if (!fused_done) { asm_sync(); ASM_FRESH(); }           // (fused: nothing was written since the fence that ended the pass over the reads)
-                auto pick_edges = [&](auto KWc) {
-                    constexpr int KW = decltype(KWc)::value;
-                    for (int n = tid; n < nNodes; n += nthr) {
-                        AsmNodeE E; E.n = 0;
-                        const bool several = (s_wc[n] >> 29 & 1u) != 0u, dirty = (s_wc[n] >> 26 & 1u) != 0u;
-                        const int own = (int)(s_wc[n] >> 23 & 7u) - 1;
-                        int rep_off = -1;
-                        AsmWords<KW> R;
-                        unsigned last = 0; bool firstpick = true;
-                        for (int pick = 0; pick < 4; ++pick) {
-                            int bj = -1; unsigned bt = 0xFFFFFFFFu;
+#pragma unroll
+                    for (int u = 0; u < DB; ++u) {
+                        const int n = n0 + u * nthr;
+                        if (n >= nNodes) continue;
+                        const unsigned x = xs[u];
+                        const bool dirty = (x >> 26 & 1u) != 0u;
+                        bool several = false;                                                  // more than one slot in use (counted below)
+                        const int own = (int)(x >> 23 & 7u) - 1;
+                        // (written field by field: a local AsmNodeE indexed by the pick count would live in scratch memory)
+                        AsmNodeE* Eo = &S.edges[n];
+                        int en_ = 0, end0 = 0, w0 = 0;
+                        if (!dirty) {
+                            if (own >= 0) {
+                                end0 = ends[u]; w0 = (int)(x & 0x7FFFFFu); en_ = 1;
+                                if (!fast) { Eo->end[0] = end0; Eo->w[0] = w0; }           // (fast path: the node's edge word says it all)
+                            }
+                            if (!fast) Eo->n = en_;
+                        } else {
+                            // the node's slot words, all requested before the first is looked at (a branch point's picks were a chain of
+                            // dependent global round trips: most of this phase's time)
+                            unsigned long long cw[ASM_MAX_SUCC]; unsigned tt[ASM_MAX_SUCC]; int nn[ASM_MAX_SUCC];
+#pragma unroll
                             for (int j = 0; j < ASM_MAX_SUCC; ++j) {
-                                if (j != own && (!dirty || (S.succ_cw[n * ASM_MAX_SUCC + j] >> 32) == 0ull)) continue;
-                                // first ticket of the slot; fused pass: a node's reference-claimed LDS slot (bit 27) is the edge that leaves
-                                // its first reference occurrence, whose ticket is the node's position
-                                unsigned t = 0u;
-                                if (several) {
-                                    if (fused_done && j == own && (s_wc[n] >> 27 & 1u)) { const unsigned ft = s_first[n]; t = (ft >> 1) + (ft & 1u); }
-                                    else t = S.succ_t[n * ASM_MAX_SUCC + j];
-                                }
-                                if (!firstpick && t <= last) continue;
-                                if (t < bt) { bt = t; bj = j; }
+                                cw[j] = S.succ_cw[n * ASM_MAX_SUCC + j]; tt[j] = S.succ_t[n * ASM_MAX_SUCC + j]; nn[j] = S.succ_n[n * ASM_MAX_SUCC + j];
                             }
-                            if (bj < 0) break;
-                            // the node the slot leads to: this node's k-mer without its first base, plus the slot's byte
-                            if (rep_off < 0) {
-                                rep_off = S.rep[n];
-                                const bool isref = rep_off < 0x40000000;
-                                R = (isref && refc) ? asm_load_words_lds<KW>(s_ref, rep_off, k + 1)
-                                                    : asm_load_words<KW>(isref ? ref + rep_off : rseq + (rep_off - 0x40000000), k + 1);
+                            {
+                                int used = 0;
+#pragma unroll
+                                for (int j = 0; j < ASM_MAX_SUCC; ++j) used += j == own || (cw[j] >> 32) != 0ull;
+                                several = used > 1;
                             }
-                            const unsigned c = bj < 4 ? (unsigned)"ACTG"[bj] : (unsigned)S.succ_c[n * ASM_MAX_SUCC + bj];
-                            AsmWords<KW> T = asm_kmer_end(R, k);
-#pragma unroll
-                            for (int cc = 0; cc < KW; ++cc)
-                                if (((k - 1) >> 3) == cc) T.w[cc] = (T.w[cc] & ~(0xFFull << (8 * ((k - 1) & 7)))) | ((unsigned long long)c << (8 * ((k - 1) & 7)));
-                            E.end[E.n] = asm_lds_node_words(s_tab, T, k, nRefNodes, s_ref, refc, ref, rseq);
-                            E.w[E.n] = (dirty ? (int)(unsigned)S.succ_cw[n * ASM_MAX_SUCC + bj] : 0) + (bj == own ? (int)(s_wc[n] & 0x7FFFFFu) : 0);
-                            ++E.n;
-                            last = bt; firstpick = false;
-                            if (!several) break;
-                        }
-                        S.edges[n] = E;
-                        if (dirty)                                  // leave the node's slot words clean for the next region
-                            for (int j = 0; j < ASM_MAX_SUCC; ++j) { S.succ_cw[n * ASM_MAX_SUCC + j] = 0ull; S.succ_c[n * ASM_MAX_SUCC + j] = 0; S.succ_t[n * ASM_MAX_SUCC + j] = 0xFFFFFFFFu; }
-                    }
-                };
-                if (!fused_done) pick_edges(std::integral_constant<int, 2>{});
-                else {
-                    // fused pass: every used slot knows its end node (succ_n).  Eight nodes per thread and trip, the one global word most of them
-                    // need -- the end of their only slot -- requested for all eight before the first is used
-                    constexpr int DB = 8;
-                    for (int n0 = tid; n0 < nNodes; n0 += DB * nthr) {
-                        unsigned xs[DB]; int ends[DB];
-#pragma unroll
-                        for (int u = 0; u < DB; ++u) {
-                            const int n = n0 + u * nthr;
-                            xs[u] = n < nNodes ? s_wc[n] : 0u;
-                            const int own = (int)(xs[u] >> 23 & 7u) - 1;
-                            ends[u] = (n < nNodes && own >= 0) ? own_n[n] : -1;
-                        }
-#pragma unroll
-                        for (int u = 0; u < DB; ++u) {
-                            const int n = n0 + u * nthr;
-                            if (n >= nNodes) continue;
-                            const unsigned x = xs[u];
-                            const bool dirty = (x >> 26 & 1u) != 0u;
-                            bool several = false;                                                  // more than one slot in use (counted below)
-                            const int own = (int)(x >> 23 & 7u) - 1;
-                            // (written field by field: a local AsmNodeE indexed by the pick count would live in scratch memory)
-                            AsmNodeE* Eo = &S.edges[n];
-                            int en_ = 0, end0 = 0, w0 = 0;
-                            if (!dirty) {
-                                if (own >= 0) {
-                                    end0 = ends[u]; w0 = (int)(x & 0x7FFFFFu); en_ = 1;
-                                    if (!fast) { Eo->end[0] = end0; Eo->w[0] = w0; }           // (fast path: the node's edge word says it all)
-                                }
-                                if (!fast) Eo->n = en_;
-                            } else {
-                                // the node's slot words, all requested before the first is looked at (a branch point's picks were a chain of
-                                // dependent global round trips: most of this phase's time)
-                                unsigned long long cw[ASM_MAX_SUCC]; unsigned tt[ASM_MAX_SUCC]; int nn[ASM_MAX_SUCC];
+                            unsigned last = 0; bool firstpick = true;
+                            for (int pick = 0; pick < 4; ++pick) {
+                                int bj = -1, bend = 0, bw = 0; unsigned bt = 0xFFFFFFFFu;
 #pragma unroll
                                 for (int j = 0; j < ASM_MAX_SUCC; ++j) {
-                                    cw[j] = S.succ_cw[n * ASM_MAX_SUCC + j]; tt[j] = S.succ_t[n * ASM_MAX_SUCC + j]; nn[j] = S.succ_n[n * ASM_MAX_SUCC + j];
-                                }
-                                {
-                                    int used = 0;
-#pragma unroll
-                                    for (int j = 0; j < ASM_MAX_SUCC; ++j) used += j == own || (cw[j] >> 32) != 0ull;
-                                    several = used > 1;
-                                }
-                                unsigned last = 0; bool firstpick = true;
-                                for (int pick = 0; pick < 4; ++pick) {
-                                    int bj = -1, bend = 0, bw = 0; unsigned bt = 0xFFFFFFFFu;
-#pragma unroll
-                                    for (int j = 0; j < ASM_MAX_SUCC; ++j) {
-                                        if (j != own && (cw[j] >> 32) == 0ull) continue;
-                                        unsigned t = 0u;
-                                        if (several) {
-                                            t = tt[j];                                                      // (events of the slot that went to the global words)
-                                            if (j == own) {
-                                                if (x >> 27 & 1u) { const unsigned ft = s_first[n]; t = (ft >> 1) + (ft & 1u); }
-                                                else t = min(t, own_t[n]);
-                                            }
+                                    if (j != own && (cw[j] >> 32) == 0ull) continue;
+                                    unsigned t = 0u;
+                                    if (several) {
+                                        t = tt[j];                                                      // (events of the slot that went to the global words)
+                                        if (j == own) {
+                                            if (x >> 27 & 1u) { const unsigned ft = s_first[n]; t = (ft >> 1) + (ft & 1u); }
+                                            else t = min(t, own_t[n]);
                                         }
-                                        if (!firstpick && t <= last) continue;
-                                        if (t < bt) { bt = t; bj = j; bend = j == own ? ends[u] : nn[j]; bw = (int)(unsigned)cw[j] + (j == own ? (int)(x & 0x7FFFFFu) : 0); }
                                     }
-                                    if (bj < 0) break;
-                                    Eo->end[en_] = bend;
-                                    Eo->w[en_] = bw;
-                                    if (en_ == 0) { end0 = bend; w0 = bw; }
-                                    ++en_;
-                                    last = bt; firstpick = false;
-                                    if (!several) break;
+                                    if (!firstpick && t <= last) continue;
+                                    if (t < bt) { bt = t; bj = j; bend = j == own ? ends[u] : nn[j]; bw = (int)(unsigned)cw[j] + (j == own ? (int)(x & 0x7FFFFFu) : 0); }
                                 }
-                                Eo->n = en_;
-#pragma unroll
-                                for (int j = 0; j < ASM_MAX_SUCC; ++j) { S.succ_cw[n * ASM_MAX_SUCC + j] = 0ull; S.succ_c[n * ASM_MAX_SUCC + j] = 0; S.succ_t[n * ASM_MAX_SUCC + j] = 0xFFFFFFFFu; }
+                                if (bj < 0) break;
+                                Eo->end[en_] = bend;
+                                Eo->w[en_] = bw;
+                                if (en_ == 0) { end0 = bend; w0 = bw; }
+                                ++en_;
+                                last = bt; firstpick = false;
+                                if (!several) break;
                             }
-                            if (fast) s_edge[n] = en_ > 0 ? (end0 | (w0 >= P.min_weight ? 1 << 14 : 0) | en_ << 15) : 0;
-                            if (x >> 28 & 1u) own_t[n] = 0xFFFFFFFFu;
+                            Eo->n = en_;
+#pragma unroll
+                            for (int j = 0; j < ASM_MAX_SUCC; ++j) { S.succ_cw[n * ASM_MAX_SUCC + j] = 0ull; S.succ_c[n * ASM_MAX_SUCC + j] = 0; S.succ_t[n * ASM_MAX_SUCC + j] = 0xFFFFFFFFu; }
                         }
+                        if (fast) s_edge[n] = en_ > 0 ? (end0 | (w0 >= P.min_weight ? 1 << 14 : 0) | en_ << 15) : 0;
+                        if (x >> 28 & 1u) own_t[n] = 0xFFFFFFFFu;
                     }
                 }
             } else
@@ -1470,7 +1127,7 @@ k_assemble(plat_assembly_batch b, AsmParams P, char* scratch, int max_ref, int m
                     last = bt; firstpick = false;
                 }
                 S.edges[n] = E;
-                if (n < ASM_LDS_NODES) S.weight[n] = -1;            // (= 0xFFFFFFFF: the fused LDS path's per-node ticket word)
+                if (n < ASM_LDS_NODES) S.weight[n] = -1;            // (= 0xFFFFFFFF: the LDS path's per-node ticket word)
                 if (n < ASM_LDS_NODES)                              // the LDS path of the regions that follow expects these words clean
                     for (int j = 0; j < ASM_MAX_SUCC; ++j) { S.succ_cw[n * ASM_MAX_SUCC + j] = 0ull; S.succ_c[n * ASM_MAX_SUCC + j] = 0; S.succ_t[n * ASM_MAX_SUCC + j] = 0xFFFFFFFFu; }
             }
@@ -1753,7 +1410,7 @@ k_assemble(plat_assembly_batch b, AsmParams P, char* scratch, int max_ref, int m
             status[g] = err;
             if (err) s_dirty = 1;                            // (a region that gave up did not tidy up behind itself)
         }
-        if (s_lds == 0)                                   // a region done on the global path has written successor bytes of low node ids
+        if (!lds)                                         // a region done on the global path has written successor bytes of low node ids
             for (int i = tid; i < ASM_LDS_NODES * ASM_MAX_SUCC; i += nthr) S.succ_c[i] = 0;
         sync_phase(); ASM_FRESH();
         ASM_TICK(8);
@@ -1874,7 +1531,7 @@ static int asm_launch(plat_ctx* ctx, const plat_assembly_batch& b, int kmer_size
     P.kmer = kmer_size; P.min_qual = min_qual; P.min_weight = min_weight; P.no_cycles = no_cycles;
     P.max_vars = max_vars_per_region; P.blob_per_region = blob_per_region; P.cap = cap; P.max_pos = (int)max_pos;
     const AsmSwitches sw = AsmSwitches::read();     // once per call (switches.hpp)
-    P.timing = sw.timing; P.fused = sw.fused; P.debug = sw.debug;
+    P.timing = sw.timing; P.debug = sw.debug;
     const size_t per_block = asm_scratch_bytes(cap, (int)max_pos, max_ref, max_reads);
     P.scratch_per_block = (long long)per_block;
     // the kernel is bound by the latency of dependent L2 accesses, not by bandwidth or issue: one region per CU at a time (its graph takes

@@ -23,8 +23,7 @@
 //                                                                                                                                          once per process before this table)
 //   AsmSwitches (plat_assemble_batch, plat_assemble_batch_async)
 //   PLAT_ASM_TIMING        set at all                       k_assemble's ticks per phase on stderr (waits for the stream)     measurements                 per call
-//   PLAT_ASM_FUSED         not beginning '0'                the fused kernel path ("0": the three-pass path)                  tests, measurements          per call
-//   PLAT_ASM_DEBUG         integer, 0 when unset            bits 1, 2: measurements (garbage); 4, 8: the rare paths forced    tests                        per call
+//   PLAT_ASM_DEBUG         integer, bits 4, 8 only          4: walks in the slice, 8: one-thread extraction (rare paths)      tests                        per call
 //   PLAT_ASM_WG_PER_CU     integer > 0, else not given      workgroups per CU instead of the computed 1                       measurements                 per call
 //   PLAT_ASM_NO_KEEP       set at all                       no workgroup keeps its scratch slice's signature                  tests                        per call
 //   EmSwitches (plat_em_window_batch)
@@ -33,8 +32,8 @@
 //   PLAT_SYNC_SPIN         begins with '1'                  hipStreamSynchronize, the runtime's own wait                      measurements                 per process
 //   PLAT_SYNC_POLL_US      integer >= 0, else not given     poll interval in microseconds, wins over plat_sync_poll_us        measurements                 per process
 //
-// Retired, read by nothing (profiles/HISTORY.md, round 11, has what each measured): PLAT_DP_IMPL, PLAT_DP_TILES, PLAT_ASM_STATIC, and bit 256
-// of PLAT_SEED_DEBUG.  -DPLAT_ASM_SECTIONS is a build flag, not a variable.
+// Retired, read by nothing (profiles/HISTORY.md, rounds 11 and 15, has what each measured): PLAT_DP_IMPL, PLAT_DP_TILES, PLAT_ASM_STATIC,
+// PLAT_ASM_FUSED, bit 256 of PLAT_SEED_DEBUG, and bits 1, 2 of PLAT_ASM_DEBUG.  -DPLAT_ASM_SECTIONS is a build flag, not a variable.
 #pragma once
 #include <cstdlib>
 #include <ctime>
@@ -72,14 +71,13 @@ struct AlignSwitches {
 };
 
 struct AsmSwitches {
-    bool timing = false, fused = true, noKeep = false;
+    bool timing = false, noKeep = false;
     int debug = 0, wgPerCu = 0;                            // wgPerCu 0: not given
 
     static AsmSwitches read() {
         AsmSwitches w;
         w.timing = env::isSet("PLAT_ASM_TIMING");
-        w.fused = env::notZero("PLAT_ASM_FUSED");
-        w.debug = env::number("PLAT_ASM_DEBUG", 0);
+        w.debug = env::number("PLAT_ASM_DEBUG", 0) & 12;
         { const int v = env::number("PLAT_ASM_WG_PER_CU", 0); if (v > 0) w.wgPerCu = v; }
         w.noKeep = env::isSet("PLAT_ASM_NO_KEEP");
         return w;

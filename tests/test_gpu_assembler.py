@@ -146,24 +146,22 @@ def test_config3_shape_regions(eng, oracle):
     assert tot > 0
 
 
-def test_fused_lds_pass_equals_the_three_pass_path(eng, golden_dir):
+def test_lds_path_equals_the_oracle_on_goldens_fuzz_and_config3_shapes(eng, golden_dir, oracle):
     """Round 4: on the LDS path the reads' k-mers and AddEdge events are ONE pass (reference nodes numbered first, ids for read-only nodes as
-    they appear, first tickets kept as the events go); PLAT_ASM_FUSED=0 is rounds 2-3's insert / number / apply / collect-tickets sequence.
-    The same variants in the same order on the reference's golden regions, on fuzz regions with repeats, N runs and low-quality stretches,
-    and on config-3 shaped regions; several regions per workgroup, so the slot words a region leaves clean are met by the next one."""
+    they appear, first tickets kept as the events go).  Its comparand was rounds 2-3's insert / number / apply / collect-tickets sequence
+    until that was retired; it is the oracle now.  The oracle's variants in the oracle's order on the reference's golden regions, on fuzz
+    regions with repeats, N runs and low-quality stretches, and on config-3 shaped regions; several regions per workgroup, so the slot
+    words a region leaves clean are met by the next one."""
     cases = json.load(gzip.open(os.path.join(golden_dir, "assembler_cases.json.gz"), "rt"))
     regs = [to_region(c) for c in cases if c["noCycles"] == 0] * 3
     rng = np.random.default_rng(4242)
     regs += [synth_region(rng, int(rng.integers(300, 2500)), 2, int(rng.choice([75, 100, 150, 250])), int(rng.integers(5, 40)), int(rng.integers(0, 6))) for _ in range(400)]
     regs += [synth_region(rng, 4500, 2, 250, 30, 4) for _ in range(48)]                      # config-3 shape
-    out = {}
-    for mode in ("1", "0"):
-        os.environ["PLAT_ASM_FUSED"] = mode
-        try:
-            out[mode] = eng.assemble(regs, kmer_size=15, min_qual=20, min_weight=40, no_cycles=0)
-        finally:
-            os.environ.pop("PLAT_ASM_FUSED", None)
-    assert out["1"] == out["0"] and sum(len(v) for v in out["1"]) > 300
+    got = eng.assemble(regs, kmer_size=15, min_qual=20, min_weight=40, no_cycles=0)
+    for r, g in zip(regs, got):
+        exp, _ = oracle.assemble(r["ref"], r["ref_start"], r["assem_start"], r["assem_end"], r["seqs"], r["quals"], 15, 20, 40, 0)
+        assert g == exp
+    assert sum(len(v) for v in got) > 300
 
 
 def test_walks_in_the_slice_equal_walks_in_lds(eng, golden_dir):
@@ -188,21 +186,18 @@ def test_walks_in_the_slice_equal_walks_in_lds(eng, golden_dir):
     assert out["4"] == out[""] and out["8"] == out[""] and out["12"] == out[""] and sum(len(v) for v in out[""]) > 300
 
 
-def test_a_dozen_regions_per_workgroup_fused_equals_three_pass(eng):
-    """The fused LDS path leaves the L1 invalidate out of the phase boundaries where only plainly stored words are read back (a workgroup
-    barrier is enough inside a CU) and keeps it where words updated by L2 atomics are read by plain loads; the three-pass path keeps it at
-    every boundary.  3 000 regions in one launch = a dozen regions after one another on every workgroup, whose slices and LDS still hold
-    the region before: the same variants from both paths."""
+def test_a_dozen_regions_per_workgroup_equal_the_oracle(eng, oracle):
+    """The LDS path leaves the L1 invalidate out of the phase boundaries where only plainly stored words are read back (a workgroup
+    barrier is enough inside a CU) and keeps it where words updated by L2 atomics are read by plain loads (once per region, before the
+    successors are picked); the global path keeps it at every boundary.  3 000 regions in one launch = a dozen regions after one another
+    on every workgroup, whose slices and LDS still hold the region before: the oracle's variants, region by region."""
     rng = np.random.default_rng(90210)
     regs = [synth_region(rng, int(rng.integers(400, 1300)), 2, int(rng.choice([100, 150])), int(rng.integers(8, 30)), int(rng.integers(0, 5))) for _ in range(3000)]
-    out = {}
-    for mode in ("1", "0"):
-        os.environ["PLAT_ASM_FUSED"] = mode
-        try:
-            out[mode] = eng.assemble(regs, kmer_size=15, min_qual=20, min_weight=40, no_cycles=0)
-        finally:
-            os.environ.pop("PLAT_ASM_FUSED", None)
-    assert out["1"] == out["0"] and sum(len(v) for v in out["1"]) > 2000
+    got = eng.assemble(regs, kmer_size=15, min_qual=20, min_weight=40, no_cycles=0)
+    for r, g in zip(regs, got):
+        exp, _ = oracle.assemble(r["ref"], r["ref_start"], r["assem_start"], r["assem_end"], r["seqs"], r["quals"], 15, 20, 40, 0)
+        assert g == exp
+    assert sum(len(v) for v in got) > 2000
 
 
 def test_async_entry_with_the_callers_sizes_equals_the_entry_that_reads_them_back(eng, golden_dir):
@@ -227,22 +222,22 @@ def test_async_entry_with_the_callers_sizes_equals_the_entry_that_reads_them_bac
 
 
 def test_a_slice_kept_clean_across_launches_gives_the_variants_of_a_fresh_context(eng, monkeypatch):
-    """Round 5: a workgroup that ends a launch on the fused path without an error leaves the signature of its slice of the scratch behind,
+    """Round 5: a workgroup that ends a launch on the LDS path without an error leaves the signature of its slice of the scratch behind,
     and the next launch with the same layout skips the stores that establish the clean slot words.  A sequence of launches on ONE context
-    that keeps, drops and re-establishes that promise -- fused (k = 15), again (kept), the global path (k = 21: dropped), fused again,
-    a launch whose tiles overflow their output room (error: dropped), fused again, the three-pass path (PLAT_ASM_FUSED=0: dropped),
-    fused -- gives launch by launch what a context without the promise (PLAT_ASM_NO_KEEP=1) gives."""
+    that keeps, drops and re-establishes that promise -- LDS path (k = 15), again (kept), the global path (k = 21: dropped), LDS again,
+    a launch whose tiles overflow their output room (error: dropped), LDS again, a launch with the walks forced into the slice
+    (PLAT_ASM_DEBUG=4: dropped, same variants), LDS -- gives launch by launch what a context without the promise (PLAT_ASM_NO_KEEP=1) gives."""
     from platypus_amd import _lib
     from platypus_amd.engine import Engine
     rng = np.random.default_rng(5005)
     sets = [[synth_region(rng, 4500, 2, 250, 30, 4) for _ in range(40)] for _ in range(3)]
-    plan = [(0, 15, {}), (1, 15, {}), (0, 21, {}), (2, 15, {}), (1, 15, dict(max_vars=1)), (0, 15, {}), (2, 15, dict(env="PLAT_ASM_FUSED")), (1, 15, {}), (1, 15, {})]
+    plan = [(0, 15, {}), (1, 15, {}), (0, 21, {}), (2, 15, {}), (1, 15, dict(max_vars=1)), (0, 15, {}), (2, 15, dict(env="PLAT_ASM_DEBUG")), (1, 15, {}), (1, 15, {})]
 
     def run(e):
         out = []
         for which, k, kw in plan:
             if kw.get("env"):
-                monkeypatch.setenv(kw["env"], "0")
+                monkeypatch.setenv(kw["env"], "4")
             try:
                 out.append(e.assemble(sets[which], kmer_size=k, max_vars=kw.get("max_vars", 512)))
             except _lib.PlatypusDeviceError as err:

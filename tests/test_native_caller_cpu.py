@@ -468,8 +468,8 @@ DEVICE_SWITCH_TABLE = {
     #                                                                         (the sweeps alone) is retired; -3 = ...11111101 has bit 512, 2000000 = 0x1E8480 has not
     "PLAT_DP_GRID_PER_CU": {"dpGridPerCu": (8, 8, 8, 1, 8, 7, 8, 33, 2000000, 512, 256, 768)},   # plat_align.hip:2034: atoi > 0, else 8
     "PLAT_ASM_TIMING": {"asmTiming": _D_SET_AT_ALL},                        # plat_assemble.hip:1877
-    "PLAT_ASM_FUSED": {"asmFused": _D_NOT_BEGINNING_0},                     # plat_assemble.hip:1878
-    "PLAT_ASM_DEBUG": {"asmDebug": (0, 0, 0, 1, 0, 7, -3, 33, 2000000, 512, 256, 768)},     # plat_assemble.hip:1879: atoi, 0 when unset
+    "PLAT_ASM_DEBUG": {"asmDebug": (0, 0, 0, 0, 0, 4, 12, 0, 0, 0, 0, 0)},                  # plat_assemble.hip:1879: atoi then, & 12 since bits 1 and 2 (the
+    #                                                                         reads pass without events / probes) are retired; 7 -> 4, -3 = ...11111101 -> 12, 2000000 = 0x1E8480 -> 0
     "PLAT_ASM_WG_PER_CU": {"asmWgPerCu": (0, 0, 0, 1, 0, 7, 0, 33, 2000000, 512, 256, 768)},     # plat_assemble.hip:1885: atoi > 0 overrides; 0 = not given
     "PLAT_ASM_NO_KEEP": {"asmNoKeep": _D_SET_AT_ALL},                       # plat_assemble.hip:1897
     "PLAT_EM_NARROW": {"emNarrow": _D_SET_AT_ALL},                          # plat_population.hip:549
@@ -477,13 +477,14 @@ DEVICE_SWITCH_TABLE = {
     "PLAT_SYNC_POLL_US": {"syncPollNs": (-1, 0, 0, 1000, 0, 7000, -1, 33000, 2000000000, 512000, 256000, 768000)},   # plat_ctx.hip:243: atol; negative or unset = not
 }                                                                           #                                                  given (-1), else x 1000 ns
 DEVICE_SWITCH_DEFAULTS = dict(noUngapped=0, noExact=0, noNlow=0, ungappedBigq=0, seedXcd=1, slowGroup=8, slowWaves=4, slowTiming=0, seedDebug=0, dpGridPerCu=8,
-                              asmTiming=0, asmFused=1, asmDebug=0, asmWgPerCu=0, asmNoKeep=0, emNarrow=0, syncSpin=0, syncPollNs=-1)
+                              asmTiming=0, asmDebug=0, asmWgPerCu=0, asmNoKeep=0, emNarrow=0, syncSpin=0, syncPollNs=-1)
 
 
 def test_every_device_switch_parses_as_it_did_at_its_old_site(tmp_path):
     """tests/device_switches_driver.cpp (a stand-alone program over csrc/switches.hpp alone, built with -fsanitize=address,undefined) sets every variable
     of the device library to every spelling and prints the four read()s: each field follows its own variable by its old site's rule, and no other field
-    moves.  The retired variables (PLAT_DP_IMPL, PLAT_DP_TILES, PLAT_ASM_STATIC; PLAT_SEED_DEBUG's bit 256 in the table above) move nothing.  A poll
+    moves.  The retired variables (PLAT_DP_IMPL, PLAT_DP_TILES, PLAT_ASM_STATIC, PLAT_ASM_FUSED=0; PLAT_SEED_DEBUG's bit 256 and PLAT_ASM_DEBUG's bits 1
+    and 2 in the table above) move nothing.  A poll
     interval splits into seconds and nanoseconds below a second, the total kept."""
     import os
     import subprocess
@@ -506,7 +507,7 @@ def test_every_device_switch_parses_as_it_did_at_its_old_site(tmp_path):
     for name, rules in DEVICE_SWITCH_TABLE.items():
         for k, spelling in enumerate(DEVICE_SPELLINGS):
             want[(name, spelling)] = dict(DEVICE_SWITCH_DEFAULTS, **{field: rule[k] for field, rule in rules.items()})
-    assert len(DEVICE_SWITCH_TABLE) == 18 and len(want) == 18 * 12 + 1
+    assert len(DEVICE_SWITCH_TABLE) == 17 and len(want) == 17 * 12 + 1
     assert set(f for r in DEVICE_SWITCH_TABLE.values() for f in r) == set(DEVICE_SWITCH_DEFAULTS)
     assert all(len(rule) == len(DEVICE_SPELLINGS) for r in DEVICE_SWITCH_TABLE.values() for rule in r.values())
     assert got == want
