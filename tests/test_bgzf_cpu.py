@@ -2,8 +2,9 @@
 their ctypes mirrors, the new header compiles as C, the Cython declarations build, the caller library linked against the CPU stand-in
 device refuses the call cleanly, the BGZF writer (synth.bgzf_block / bgzf_stream) writes what the specification says, and the HOST BUILD
 of csrc/bgzf_inflate.hpp -- the code that indexes memory from input data, the same text the device compiles -- inflates the whole grid as
-zlib does, refuses the corrupt corpus without touching a guard band (under AddressSanitizer and UBSan where libasan is installed), and
-walks records by the rule restated in tests/bgzf_cases.py."""
+zlib does, refuses the corrupt corpus without touching a guard band (under AddressSanitizer and UBSan where libasan is installed), gives
+zlib's verdict on the streams of tests/deflate_writer.py that zlib's encoder never writes, and walks records -- the window-seam ladder
+included -- by the rule restated in tests/bgzf_cases.py."""
 import ctypes as C
 import gzip
 import os
@@ -293,3 +294,30 @@ def test_host_build_walks_records_by_the_rule(driver):
     assert len(off) == 2
     got = driver("walk", [(stream, struct.pack("<iiiiii", 0, 1, 0, 3, 1000, 2000))], "boundary")
     assert got == [(0, [4, 4 + one], 2)]
+
+
+def test_host_build_gives_zlibs_verdict_on_streams_zlib_never_writes(driver):
+    """tests/deflate_writer.py's streams (tests/test_deflate_writer_cpu.py says what they reach): the slow canonical walk at every depth,
+    the headers' full ranges, every length and distance symbol, the overlap ladder, the dependence chains at the batch border -- which the
+    driver replays in the device's order too --, the far edges, the block sequences, the refusals, 400 seeded streams and of each a copy
+    with bits of its first header flipped.  zlib decides every verdict and every payload."""
+    named = [(n, b) for n, _, b in K.foreign_blocks()]
+    fuzz, _ = K.foreign_fuzz()
+    cases = named + [(n, b) for n, _, b, _ in fuzz] + [(n + ", flipped", f) for n, _, _, f in fuzz]
+    got = driver("inflate", [b for _, b in cases], "foreign")
+    want = [K.reference_verdict(b) for _, b in cases]
+    assert [n for (n, _), g, w in zip(cases, got, want) if g != w] == []
+    n_ok = sum(1 for w in want if w is not None)
+    assert n_ok >= 630 and len(want) - n_ok >= 300
+
+
+def test_host_build_walks_the_window_seam_ladder_by_the_rule(driver):
+    """The host build has no windows: this pins the cases themselves (every stream walks to its end by walk_step as by rule_walk) before
+    the device sees them, which is where the windows are."""
+    cases, _ = K.walk_seam_cases()
+    for bp in (65536, 37):
+        packed = [_walk_case_bytes(data, first, stop, tid, beg, end, bp)[:2] for _, data, first, stop, tid, beg, end in cases]
+        got = driver("walk", packed, "seam%d" % bp)
+        for (name, data, first, stop, tid, beg, end), (rc, kept, walked) in zip(cases, got):
+            w_rc, w_kept, w_walked, _ = K.rule_walk(data, first, stop, tid, beg, end)
+            assert (rc, kept, walked) == (0, w_kept, w_walked) and w_rc == 0, (name, bp)

@@ -39,6 +39,7 @@ def test_oracle_equals_the_wide_dp_fixture(oracle, golden_dir):
     lens = g["lens"]
     assert len(lens) == 600 and set(lens.tolist()) == set(LC.LADDER)
     assert (g["score"] == LC.SATURATED).sum() >= 3 and (g["flank"] >= 0).sum() > 400
+    oracle.tb_saturated()                                               # (the counter is the process's: what tests before this one left is not this test's)
     for j in range(len(lens)):
         L = int(lens[j])
         hap, read = g["haps"][j, :L + 15].tobytes(), g["reads"][j, :L].tobytes()
