@@ -505,6 +505,36 @@ cdef extern from "platypus_mi355x.h":
         int64_t* lin
         int64_t* status
     int plat_tabix_index_batch(plat_ctx* ctx, const plat_tabix_index_in* inp, const plat_tabix_index_out* out, void* stream) nogil
+    # region queries over a flattened tabix or BAM index (ti_iter_query, index.c.pysam.c:776-870, on the device)
+    int PLAT_IDXQ_STATUS_WORDS
+    int PLAT_IDXQ_MAX_CHUNKS
+    int PLAT_IDXQ_NO_ITERATOR
+    int PLAT_IDXQ_HANDED_OVER
+    ctypedef struct plat_index_query_in:
+        int32_t n_ref
+        int32_t n_queries
+        int64_t n_bins
+        int64_t n_chunks
+        int64_t n_lin
+        const int64_t* ref_bin_first
+        const int32_t* bin_id
+        const int64_t* bin_chunk_first
+        const int64_t* chunk_u
+        const int64_t* chunk_v
+        const int64_t* ref_lin_first
+        const int64_t* lin_fill
+        const int32_t* tid
+        const int32_t* beg
+        const int32_t* end
+    ctypedef struct plat_index_query_out:
+        int64_t cap_chunks
+        int32_t* count
+        int32_t* gathered
+        int64_t* q_first
+        int64_t* out_u
+        int64_t* out_v
+        int64_t* status
+    int plat_index_query_batch(plat_ctx* ctx, const plat_index_query_in* inp, const plat_index_query_out* out, void* stream) nogil
     # read counts of reference-call blocks (outputRefCall's loop over countReadsCoveringRegion)
     int PLAT_REFCOV_RAISES
     int PLAT_REFCOV_EMPTY
@@ -825,3 +855,34 @@ cdef extern from "platypus_caller_tabix.h":
         double seconds
     int plat_caller_set_source_blocks(plat_caller* c, const plat_source_blocks* per_region, int n_regions, int longHaps,
                                       plat_source_blocks_info* info) nogil
+
+
+cdef extern from "platypus_caller_index.h":
+    int PLAT_INDEX_TBI
+    int PLAT_INDEX_BAI
+    ctypedef struct plat_index:
+        pass
+    int plat_index_open(plat_caller* c, const uint8_t* bytes, size_t len, int kind, plat_index** out) nogil
+    int plat_index_close(plat_index* idx) nogil
+    int plat_index_n_refs(const plat_index* idx) nogil
+    const char* plat_index_ref_name(const plat_index* idx, int tid) nogil
+    int plat_index_tid(const plat_index* idx, const char* name) nogil
+    ctypedef struct plat_index_query_info:
+        int64_t queries
+        int64_t handed_over
+        int64_t chunks
+        int64_t device_calls
+        double seconds
+    int plat_index_query(plat_index* idx, int n, const int32_t* tid, const int32_t* beg, const int32_t* end, const int64_t** first,
+                         const int64_t** u, const int64_t** v, const int32_t** count, plat_index_query_info* info) nogil
+    ctypedef struct plat_source_file:
+        const uint8_t* data
+        int64_t data_len
+        plat_index* index
+    ctypedef struct plat_source_region:
+        const char* chrom
+        int32_t start
+        int32_t end
+    int plat_caller_set_source_files(plat_caller* c, const plat_source_file* files, int n_files, const plat_source_region* regions, int n_regions,
+                                     int longHaps, plat_source_blocks_info* info) nogil
+    int plat_caller_source_lines(const plat_caller* c, int region, const char** text, int64_t* len) nogil

@@ -22,7 +22,8 @@
  * "line walk": a line that runs past the end of a chunk that is not the fetch's last, or a POS or END beyond 32 bits).  A library
  * linked against a device library without plat_tabix_fetch_batch returns PLAT_ERR_UNSUPPORTED.  PLAT_CALLER_HOST_TABIX=1 inflates and
  * walks on the host instead (tests, measurements).
- * Not handled: the .tbi / .csi index, file I/O and the choice of chunks (the integrator's), the generic, SAM and UCSC presets.
+ * Not handled: the .csi index and file I/O (the integrator's; the .tbi and the choice of chunks are include/platypus_caller_index.h's:
+ * plat_caller_set_source_files makes these structures itself), the generic, SAM and UCSC presets.
  */
 #ifndef PLATYPUS_CALLER_TABIX_H
 #define PLATYPUS_CALLER_TABIX_H

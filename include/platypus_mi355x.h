@@ -1027,6 +1027,69 @@ typedef struct plat_tabix_index_out {
 
 int plat_tabix_index_batch(plat_ctx* ctx, const plat_tabix_index_in* in, const plat_tabix_index_out* out, void* stream);
 
+/* ---- region queries over a tabix or BAM index ---------------------------------------------------------------------------
+ * Replaces  ti_iter_query  (src/tabix/index.c.pysam.c:799-870) over reg2bins (:776-789) -- the chunk list `fetch(chrom, start, end)`
+ * reads -- for n_queries x (tid, beg, end) against ONE index in one call.  A BAM index (.bai) has the same bins, linear index and
+ * rule, so the call serves both.  The index comes as flat tables that are resident on the device (csrc/index_query.hpp makes them of
+ * the .tbi's or .bai's bytes on the host, once per file: the format is serial, every count moves what follows it):
+ *   ref_bin_first [n_ref + 1] into bin_id [n_bins], bin ids ascending within a reference (the metadata pseudo-bin 37450 left out);
+ *   bin_chunk_first [n_bins + 1] into chunk_u / chunk_v [n_chunks], a bin's chunks in file order;
+ *   ref_lin_first [n_ref + 1] into lin_fill [n_lin]: the linear index with every zero entry replaced by the last non-zero one below it
+ *   (0 where there is none) -- the reference's backward scan for indexes written before tabix 0.1.4, done once.
+ * Offsets that do not ascend inside their tables from 0 to the tables' sizes, a bin id outside [0, 37450), ids that do not ascend within
+ * a reference, or a query whose tid lies outside [0, n_ref) is status {PLAT_ERR_INVALID, the lowest such query or -1, 0 ...} and
+ * nothing else is written.
+ *
+ * The rule, per query:
+ *   window     beg = max(beg, 0).  end < beg: no iterator, count -1.  beg == end: an iterator without chunks, count 0
+ *   bins       reg2bins(beg, end): end clamped to 2^29, then end - 1 used; bin 0 and, for the shifts 26, 23, 20, 17, 14, the bins
+ *              first + (beg >> shift) .. first + (end - 1 >> shift), first = 1, 9, 73, 585, 4681.  The bins of a level range that the
+ *              reference holds are consecutive in bin_id: a lower bound for the range's first bin, another for the bin behind its last
+ *   min_off    lin_fill[min(beg >> 14, n - 1)] of the reference's n linear entries; 0 when it has none
+ *   gathered   every chunk of every listed bin with v > min_off, strictly; virtual offsets compare as unsigned 64-bit numbers
+ *   sorted     by (u, v) ascending (the reference's introsort leaves ties in u open; a valid index has none: u is a record's offset)
+ *   resolved   chunk i goes when v[i] <= the largest v in front of it; then v[i] = min(v[i], u[i + 1]); then chunk i opens an output chunk
+ *              exactly when v[i - 1] >> 16 != u[i] >> 16, and an output chunk ends at the v of the last member of its run.  These are the
+ *              reference's three loops; with M[i] the largest v in front of i they are one scan: i opens an output chunk when i = 0 or
+ *              v[i] > M[i] and M[i] >> 16 < u[i] >> 16, the output chunk in front of it ends at M[i], the last at the largest v of all
+ *   limit      a query that gathers more than PLAT_IDXQ_MAX_CHUNKS chunks is HANDED OVER: count -2, no chunks; this is no error -- the
+ *              caller answers it with the host twin (csrc/index_query.hpp, query)
+ *
+ * Output (device): count [n_queries] (the output chunks, -1, -2), gathered [n_queries] (0 for count -1), q_first [n_queries + 1] from 0
+ * (a query with a negative count takes no room), out_u / out_v [cap_chunks]: query q's chunks at q_first[q] .. q_first[q + 1];
+ * status [PLAT_IDXQ_STATUS_WORDS]: {0 or the error, the lowest query with a bad tid or -1, output chunks, gathered chunks, queries handed
+ * over, queries without an iterator}.  More output chunks than cap_chunks is PLAT_ERR_OVERFLOW: count, gathered, q_first and the status
+ * hold the full counts, no chunk is written, and the caller calls again.
+ * Every loop is bounded by the chunks of one level range's bins, the logarithm of a table, or PLAT_IDXQ_MAX_CHUNKS; a whole-contig
+ * query makes six pairs of searches, not 37449 probes.  One wave per query (up to 64 gathered chunks: sorted in registers), one workgroup
+ * per query above that (32 KiB of LDS).  Seven kernels (csrc/plat_idxquery.hip names them), two words and the list of workgroup queries in
+ * the scratch of plat_tabix_fetch_batch (one of these calls at a time per context); the call does not wait and nothing traps.           */
+#define PLAT_IDXQ_STATUS_WORDS 6
+#define PLAT_IDXQ_MAX_CHUNKS 2048
+#define PLAT_IDXQ_NO_ITERATOR (-1)
+#define PLAT_IDXQ_HANDED_OVER (-2)
+typedef struct plat_index_query_in {
+    int32_t n_ref, n_queries;
+    int64_t n_bins, n_chunks, n_lin;
+    const int64_t* ref_bin_first;    /* [n_ref + 1] */
+    const int32_t* bin_id;           /* [n_bins] */
+    const int64_t* bin_chunk_first;  /* [n_bins + 1] */
+    const int64_t* chunk_u; const int64_t* chunk_v;      /* [n_chunks] */
+    const int64_t* ref_lin_first;    /* [n_ref + 1] */
+    const int64_t* lin_fill;         /* [n_lin] */
+    const int32_t* tid; const int32_t* beg; const int32_t* end;      /* [n_queries] */
+} plat_index_query_in;
+
+typedef struct plat_index_query_out {
+    int64_t cap_chunks;
+    int32_t* count; int32_t* gathered;                   /* [n_queries] */
+    int64_t* q_first;                /* [n_queries + 1] */
+    int64_t* out_u; int64_t* out_v;  /* [cap_chunks] */
+    int64_t* status;                 /* [PLAT_IDXQ_STATUS_WORDS] */
+} plat_index_query_out;
+
+int plat_index_query_batch(plat_ctx* ctx, const plat_index_query_in* in, const plat_index_query_out* out, void* stream);
+
 /* ---- read counts of reference-call blocks ------------------------------------------------------------------------
  * Replaces the loop of  outputRefCall   variantcaller.pyx:774-784  over  ReadArray.countReadsCoveringRegion(p, p + 1)   cwindow.pyx:176-206
  * (one call per position of a block and per sample: the block's QUAL is computed from the smallest count)

@@ -105,12 +105,16 @@ def call_variants_config4(opts, n_regions):
                             int(os.environ.get("PLAT_CALLER_CHUNK", "4")))
         t0 = time.time()
         if source_files and all(os.path.exists(f + ".tbi") for f in opts.sourceFile):
-            # every source file has a tabix index next to it: the chunks of each region's fetch go to the library as BGZF blocks, inflated
-            # and iterated on the device (include/platypus_caller_tabix.h); a file whose fetch raises (a name its index lacks) is left out
-            from .tabixindex import TabixFile
-            tabix = [TabixFile.open(f) for f in opts.sourceFile]
-            fetches = [[b for b in (t.fetch_blocks(r["chrom"], r["start"], r["end"]) for t in tabix) if b is not None] for r in regs]
-            text.write(nc.call_regions(rr, ["S1"], opts, source_blocks=fetches) if rr else "")
+            # every source file has a tabix index next to it: the library takes each file and its index once, answers every region's
+            # lookup in one device batch per file, and inflates and iterates the chunks on the device (include/platypus_caller_index.h);
+            # a file whose fetch raises (a name its index lacks) is left out of that region
+            files = []
+            for f in opts.sourceFile:
+                with open(f, "rb") as data, open(f + ".tbi", "rb") as tbi:
+                    files.append((data.read(), nc.open_index(tbi.read(), "tbi")))
+            text.write(nc.call_regions(rr, ["S1"], opts, source_files=files) if rr else "")
+            for _, index in files:
+                index.close()
         else:
             lines = [b"".join(reader.texts(r["chrom"], r["start"], r["end"])) for r in regs] if reader else None
             text.write(nc.call_regions(rr, ["S1"], opts, source_lines=lines) if rr else "")

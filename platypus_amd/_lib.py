@@ -172,6 +172,20 @@ TBI_STATUS_WORDS, TBI_MAX_REF = 13, 65536
 TBI_KINDS = ("", "a line of fewer than two columns", "a POS or END beyond 32 bits", "a negative END", "a position below the one in front of it",
              "a contig name that appeared before another")
 
+
+
+class IndexQueryIn(C.Structure):
+    """plat_index_query_in: the flat tables of one index (resident) and a call's queries."""
+    _fields_ = [("n_ref", C.c_int32), ("n_queries", C.c_int32), ("n_bins", C.c_int64), ("n_chunks", C.c_int64), ("n_lin", C.c_int64)] + [(k, C.c_void_p) for k in (
+        "ref_bin_first", "bin_id", "bin_chunk_first", "chunk_u", "chunk_v", "ref_lin_first", "lin_fill", "tid", "beg", "end")]
+
+
+class IndexQueryOut(C.Structure):
+    _fields_ = [("cap_chunks", C.c_int64)] + [(k, C.c_void_p) for k in ("count", "gathered", "q_first", "out_u", "out_v", "status")]
+
+
+IDXQ_STATUS_WORDS, IDXQ_MAX_CHUNKS, IDXQ_NO_ITERATOR, IDXQ_HANDED_OVER = 6, 2048, -1, -2
+
 ROUTE_MAX_GROUPS, ROUTE_MAX_SAMPLES, ROUTE_LDS_ID_BYTES = 2048, 256, 24576
 ROUTE_WHY = ("routed", "no RG field", "an RG field that is no string", "an RG value that is not in the table", "an aux field of unknown type",
              "a B array with a negative count", "aux data that runs past the record", "a fixed part that runs past the record")
@@ -308,6 +322,7 @@ SIGNATURES = {
     "plat_source_variants_batch": (C.c_int, [C.c_void_p, C.POINTER(SourceVariantsIn), C.POINTER(SourceVariantsOut), C.c_void_p]),
     "plat_tabix_fetch_batch": (C.c_int, [C.c_void_p, C.POINTER(TabixFetchIn), C.POINTER(TabixFetchOut), C.c_void_p]),
     "plat_tabix_index_batch": (C.c_int, [C.c_void_p, C.POINTER(TabixIndexIn), C.POINTER(TabixIndexOut), C.c_void_p]),
+    "plat_index_query_batch": (C.c_int, [C.c_void_p, C.POINTER(IndexQueryIn), C.POINTER(IndexQueryOut), C.c_void_p]),
     "plat_refcall_coverage_batch": (C.c_int, [C.c_void_p, C.POINTER(RefCovIn), C.POINTER(RefCovOut), C.c_void_p]),
     "plat_refcov_lds_reads": (C.c_int, []),
     "plat_variant_read_stats_batch": (C.c_int, [C.c_void_p, C.POINTER(InfoStatsBatch), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
@@ -325,7 +340,7 @@ SIGNATURES = {
 # unbound there; load() still requires every declared symbol of the real library
 ADDED_LATER = ("plat_read_buffers_batch", "plat_read_buffers_packed_batch", "plat_bam_decode_batch", "plat_bgzf_inflate_batch", "plat_bam_find_records",
                "plat_bam_route_batch", "plat_source_variants_batch", "plat_tabix_fetch_batch", "plat_refcall_coverage_batch", "plat_refcov_lds_reads",
-               "plat_bgzf_deflate_batch", "plat_tabix_index_batch",
+               "plat_bgzf_deflate_batch", "plat_tabix_index_batch", "plat_index_query_batch",
                "plat_concat_read_tables_src", "plat_pack_codes_pieces", "plat_candidates_batch_packed", "plat_gather_reads_packed",
                "plat_variant_read_stats_packed_batch")
 

@@ -25,6 +25,8 @@
 //                                                                                                                         read when that entry point is called
 //   HOST_TBI                     begins with '1'    plat_caller_index_bgzf inflates and indexes on the host (csrc/tabix_index.hpp)   tests, measurements (the kernels' A/B);
 //                                                                                                                         read when that entry point is called
+//   HOST_INDEX                   begins with '1'    plat_index_query and plat_caller_set_source_files answer every index query with the host twin (csrc/index_query.hpp)   tests, measurements (the kernels' A/B);
+//                                                                                                                         read when those entry points are called
 //   TRACE                        set at all         per-chunk / per-call lines on stderr;                                 measurements
 //                                begins with '1'    ... and the per-stage seconds of every call (traceStages)
 // PLAT_CALLER_POLL_US is not here: it is a property of the caller object and is read where that is made (plat_caller_create).
@@ -36,7 +38,7 @@ namespace plathost {
 
 struct Switches {
     bool noCodes = false, expand = false, hostTally = false, hostB = false, noDeviceReplay = false, hostInfo = false, firstOccurrenceOrder = false;
-    bool evenTail = true, keepSpare = false, checkHints = false, noRefCtx = false, noRefPrefetch = false, hostSource = false, hostRefcov = false, hostTabix = false, hostDeflate = false, hostTbi = false;
+    bool evenTail = true, keepSpare = false, checkHints = false, noRefCtx = false, noRefPrefetch = false, hostSource = false, hostRefcov = false, hostTabix = false, hostDeflate = false, hostTbi = false, hostIndex = false;
     bool trace = false, traceStages = false;                              // PLAT_CALLER_TRACE: set at all / begins with '1'
 
     static Switches read() {
@@ -60,6 +62,7 @@ struct Switches {
         w.hostTabix = isOne("PLAT_CALLER_HOST_TABIX");
         w.hostDeflate = isOne("PLAT_CALLER_HOST_DEFLATE");
         w.hostTbi = isOne("PLAT_CALLER_HOST_TBI");
+        w.hostIndex = isOne("PLAT_CALLER_HOST_INDEX");
         w.trace = isSet("PLAT_CALLER_TRACE");
         w.traceStages = isOne("PLAT_CALLER_TRACE");
         return w;

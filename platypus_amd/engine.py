@@ -1077,6 +1077,49 @@ class Engine:
         return dict(runs=list(zip(tid[:n_r].tolist(), b[:n_r].tolist(), u[:n_r].tolist())), names=list(zip(noff[:n_n].tolist(), nlen[:n_n].tolist())),
                     name_bytes=nbytes[:n_b].tobytes(), lin_first=first[:n_n + 1].tolist() if ok else [], lin=lin[:n_w].tolist(), status=st[:_lib.TBI_STATUS_WORDS].tolist(), guard_intact=intact)
 
+    def index_tables(self, flat):
+        """The flat tables of one index (a dict of ref_bin_first, bin_id, bin_chunk_first, chunk_u, chunk_v, ref_lin_first, lin_fill, as
+        tests/index_query_cases.py and csrc/index_query.hpp make them) uploaded once: what index_query takes."""
+        torch = _torch()
+        dt = dict(bin_id=np.int32)
+        up = lambda k: torch.from_numpy(np.append(np.asarray(flat[k], dtype=dt.get(k, np.int64)), np.zeros(1, dtype=dt.get(k, np.int64)))).to(self.device)
+        d = {k: up(k) for k in ("ref_bin_first", "bin_id", "bin_chunk_first", "chunk_u", "chunk_v", "ref_lin_first", "lin_fill")}
+        d["sizes"] = (len(flat["ref_bin_first"]) - 1, len(flat["bin_id"]), len(flat["chunk_u"]), len(flat["lin_fill"]))
+        return d
+
+    def index_query(self, tables, queries, cap_chunks=None, sizes=None):
+        """plat_index_query_batch: ti_iter_query (index.c.pysam.c:776-870) for queries [(tid, beg, end)] over index_tables(...).  sizes: (n_ref,
+        n_bins, n_chunks, n_lin) to hand over instead of the tables' own (tests of the checks).  Returns a dict: chunks [per query a list of
+        (u, v), None for count -1 and -2, all None when they do not fit cap_chunks -- default 4 per query + 4096], count, gathered, first
+        [n + 1], status [6] and guard_intact: nothing was written behind a capacity (nothing at all but the status when the call is
+        refused as invalid, no chunk on an overflow)."""
+        torch = _torch()
+        n = len(queries)
+        cap = 4 * n + 4096 if cap_chunks is None else int(cap_chunks)
+        q = np.asarray(queries, dtype=np.int32).reshape(n, 3)
+        d_q = [torch.from_numpy(np.append(q[:, k], np.zeros(1, dtype=np.int32)).astype(np.int32)).to(self.device) for k in range(3)]
+        f64, f32, guard = 0x7EEE7EEE7EEE7EEE, 0x7EEE7EEE, 16
+        full = lambda k, big: torch.full((k + guard,), f64 if big else f32, dtype=torch.int64 if big else torch.int32, device=self.device)
+        d_count, d_gath, d_first, d_u, d_v, d_status = full(n, False), full(n, False), full(n + 1, True), full(cap, True), full(cap, True), full(_lib.IDXQ_STATUS_WORDS, True)
+        n_ref, n_bins, n_chunks, n_lin = tables["sizes"] if sizes is None else sizes
+        i = _lib.IndexQueryIn(n_ref, n, n_bins, n_chunks, n_lin, *[tables[k].data_ptr() for k in ("ref_bin_first", "bin_id", "bin_chunk_first", "chunk_u", "chunk_v",
+                                                                                              "ref_lin_first", "lin_fill")], *[t.data_ptr() for t in d_q])
+        o = _lib.IndexQueryOut(cap, d_count.data_ptr(), d_gath.data_ptr(), d_first.data_ptr(), d_u.data_ptr(), d_v.data_ptr(), d_status.data_ptr())
+        _lib.check(self.lib.plat_index_query_batch(self.ctx, C.byref(i), C.byref(o), self._stream()), "plat_index_query_batch")
+        self._sync()
+        count, gath, first, u, v, st = (t.cpu().numpy() for t in (d_count, d_gath, d_first, d_u, d_v, d_status))
+        verdict = int(st[0])
+        n_q = n if verdict in (0, -8) else 0
+        used = int(st[2]) if verdict == 0 else 0
+        intact = (bool((st[_lib.IDXQ_STATUS_WORDS:] == f64).all()) and bool((count[n_q:] == f32).all()) and bool((gath[n_q:] == f32).all()) and
+                  bool((first[(n + 1 if verdict in (0, -8) else 0):] == f64).all()) and bool((u[used:] == f64).all()) and bool((v[used:] == f64).all()))
+        chunks = None
+        if verdict == 0:
+            u64, v64 = u.view(np.uint64), v.view(np.uint64)
+            chunks = [None if count[k] < 0 else list(zip(u64[first[k]:first[k + 1]].tolist(), v64[first[k]:first[k + 1]].tolist())) for k in range(n)]
+        return dict(chunks=chunks, count=count[:n_q].tolist(), gathered=gath[:n_q].tolist(), first=first[:n_q + 1].tolist() if verdict in (0, -8) else [],
+                    status=st[:_lib.IDXQ_STATUS_WORDS].tolist(), guard_intact=intact)
+
     def refcall_coverage(self, read_pos, read_end, slices, intervals, tile_first=None):
         """plat_refcall_coverage_batch: the loop of outputRefCall (variantcaller.pyx:774-784) over ReadArray.countReadsCoveringRegion
         (cwindow.pyx:176-206) on the device.  read_pos / read_end: the read table; slices: [(begin, n, longest)], one sample's good reads each;

@@ -118,6 +118,24 @@ class SourceBlocksInfo(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ("n_blocks", "compressed_bytes", "inflated_bytes", "lines_walked", "lines_kept", "kept_bytes")] + [("seconds", C.c_double)]
 
 
+class IndexQueryInfo(C.Structure):
+    """plat_index_query_info (include/platypus_caller_index.h)."""
+    _fields_ = [(k, C.c_int64) for k in ("queries", "handed_over", "chunks", "device_calls")] + [("seconds", C.c_double)]
+
+
+class _SourceFile(C.Structure):
+    """plat_source_file."""
+    _fields_ = [("data", C.c_void_p), ("data_len", C.c_int64), ("index", C.c_void_p)]
+
+
+class _SourceRegion(C.Structure):
+    """plat_source_region."""
+    _fields_ = [("chrom", C.c_char_p), ("start", C.c_int32), ("end", C.c_int32)]
+
+
+INDEX_KINDS = {"tbi": 0, "bai": 1}
+
+
 class _FetchedReads(C.Structure):
     _fields_ = [("fetched", _ReadTable), ("broken_mates", _ReadTable), ("chrom_id", C.c_void_p), ("mate_chrom_id", C.c_void_p),
                 ("insert_size", C.c_void_p)]
@@ -630,6 +648,7 @@ def build(verbose=False):
     srcs.append(os.path.join(_lib.CSRC, "tabix_rule.hpp"))             # (... and the host's walk over a tabix fetch's lines)
     srcs.append(os.path.join(_lib.CSRC, "bgzf_deflate.hpp"))           # (... and the host twin of the BGZF encoder)
     srcs.append(os.path.join(_lib.CSRC, "tabix_index.hpp"))            # (... and the host twin of the tabix indexer, with its finishing stage)
+    srcs.append(os.path.join(_lib.CSRC, "index_query.hpp"))            # (... and the flatten and the host twin of the index query)
     if os.path.exists(LIB_PATH) and os.path.getmtime(LIB_PATH) >= max([os.path.getmtime(f) for f in srcs] + [os.path.getmtime(_lib.LIB_PATH)]):
         return LIB_PATH
     # (-O3: the region loop is many small functions over small containers; +10 % windows/s over -O2 on the same box.  No -march: the library
@@ -678,6 +697,15 @@ def _bind(lib):
     lib.plat_caller_compress_text.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p),
                                               C.POINTER(C.c_size_t), C.c_void_p]
     lib.plat_caller_index_bgzf.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(TbiInfo)]
+    lib.plat_index_open.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_void_p)]
+    lib.plat_index_close.argtypes = [C.c_void_p]
+    lib.plat_index_n_refs.argtypes = [C.c_void_p]
+    lib.plat_index_ref_name.argtypes = [C.c_void_p, C.c_int]
+    lib.plat_index_ref_name.restype = C.c_char_p
+    lib.plat_index_tid.argtypes = [C.c_void_p, C.c_char_p]
+    lib.plat_index_query.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p] + [C.POINTER(C.c_void_p)] * 4 + [C.POINTER(IndexQueryInfo)]
+    lib.plat_caller_set_source_files.argtypes = [C.c_void_p, C.POINTER(_SourceFile), C.c_int, C.POINTER(_SourceRegion), C.c_int, C.c_int, C.POINTER(SourceBlocksInfo)]
+    lib.plat_caller_source_lines.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
     lib.plat_caller_free.argtypes = [C.c_void_p]
     lib.plat_caller_free.restype = None
     lib.plat_caller_last_error.argtypes = [C.c_void_p]
@@ -831,6 +859,30 @@ class BlockOrder:
         return _native_text(lib, out, total, "view")
 
 
+class NativeIndex:
+    """plat_index (include/platypus_caller_index.h): a .tbi or .bai opened on a NativeCaller; close it before the caller."""
+
+    def __init__(self, caller, handle):
+        self.caller, self.h = caller, handle
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.caller, "h", None):
+            self.caller.lib.plat_index_close(self.h)
+        self.h = None
+
+    @property
+    def n_refs(self):
+        return self.caller.lib.plat_index_n_refs(self.h)
+
+    def ref_name(self, tid):
+        return self.caller.lib.plat_index_ref_name(self.h, int(tid))
+
+    def tid(self, name):
+        """-1 when the index does not hold the name (a name with a NUL byte cannot be one)."""
+        name = name if isinstance(name, bytes) else name.encode()
+        return -1 if b"\x00" in name else self.caller.lib.plat_index_tid(self.h, name)
+
+
 class NativeCaller:
     """plat_caller: `workers` threads, each with its own plat_ctx and stream on `device`; `regions_per_chunk` regions go through
     the device stages together."""
@@ -904,6 +956,59 @@ class NativeCaller:
             raise _lib.PlatypusDeviceError(rc, (self.lib.plat_caller_last_error(self.h) or b"").decode(), "plat_caller_set_source_blocks")
         self.source_blocks_info = {k: getattr(info, k) for k, _ in info._fields_}
 
+    def open_index(self, raw, kind="tbi"):
+        """plat_index_open: the bytes of a .tbi (BGZF, as on disk) or a .bai flattened on the host and uploaded once.  Returns a NativeIndex."""
+        raw = bytes(raw)
+        h = C.c_void_p()
+        rc = self.lib.plat_index_open(self.h, raw, len(raw), INDEX_KINDS[kind], C.byref(h))
+        if rc != 0:
+            raise _lib.PlatypusDeviceError(rc, (self.lib.plat_caller_last_error(self.h) or b"").decode(), "plat_index_open")
+        return NativeIndex(self, h)
+
+    def query_index(self, index, queries, info=False):
+        """plat_index_query: queries [(tid, beg, end)] in one device batch.  Returns per query the chunk list [(u, v)] ti_iter_query returns,
+        None where it returns no iterator; with info=True (that, plat_index_query_info as a dict)."""
+        n = len(queries)
+        q = np.ascontiguousarray(np.asarray(queries, dtype=np.int32).reshape(n, 3).T)
+        first, u, v, count, inf = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), IndexQueryInfo()
+        rc = self.lib.plat_index_query(index.h, n, q[0].ctypes.data, q[1].ctypes.data, q[2].ctypes.data, C.byref(first), C.byref(u), C.byref(v), C.byref(count), C.byref(inf))
+        if rc != 0:
+            raise _lib.PlatypusDeviceError(rc, (self.lib.plat_caller_last_error(self.h) or b"").decode(), "plat_index_query")
+        take = lambda ptr, k, dt: np.ctypeslib.as_array(C.cast(ptr, C.POINTER(np.ctypeslib.as_ctypes_type(dt))), shape=(k,)).copy() if k and ptr.value else np.zeros(0, dtype=dt)
+        fi, cn = take(first, n + 1, np.int64), take(count, n, np.int32)
+        total = int(fi[n]) if n else 0
+        uu, vv = take(u, total, np.uint64).tolist(), take(v, total, np.uint64).tolist()
+        out = [None if cn[k] < 0 else list(zip(uu[fi[k]:fi[k + 1]], vv[fi[k]:fi[k + 1]])) for k in range(n)]
+        return (out, {k: getattr(inf, k) for k, _ in inf._fields_}) if info else out
+
+    def set_source_files(self, files, regions, long_haps=0):
+        """plat_caller_set_source_files: the source VCF lines of the NEXT call from whole files.  files: [(the .vcf.gz's bytes or uint8 array,
+        its NativeIndex)]; regions: [(chrom, start, end)] in the order of that call's list.  self.source_blocks_info describes it."""
+        ff = (_SourceFile * max(len(files), 1))()
+        keep = [_u8(d) for d, _ in files]
+        for k, (_, index) in enumerate(files):
+            ff[k].data, ff[k].data_len, ff[k].index = keep[k].ctypes.data, len(keep[k]), index.h
+        rr = (_SourceRegion * max(len(regions), 1))()
+        for k, (chrom, start, end) in enumerate(regions):
+            rr[k].chrom, rr[k].start, rr[k].end = chrom if isinstance(chrom, bytes) else chrom.encode(), int(start), int(end)
+        info = SourceBlocksInfo()
+        rc = self.lib.plat_caller_set_source_files(self.h, ff, len(files), rr, len(regions), int(long_haps), C.byref(info))
+        del keep
+        if rc != 0:
+            raise _lib.PlatypusDeviceError(rc, (self.lib.plat_caller_last_error(self.h) or b"").decode(), "plat_caller_set_source_files")
+        self.source_blocks_info = {k: getattr(info, k) for k, _ in info._fields_}
+
+    def source_lines_set(self, n_regions):
+        """plat_caller_source_lines: the source lines set for the next call, [bytes] per region of its list."""
+        out = []
+        for k in range(n_regions):
+            text, length = C.c_void_p(), C.c_int64()
+            rc = self.lib.plat_caller_source_lines(self.h, k, C.byref(text), C.byref(length))
+            if rc != 0:
+                raise _lib.PlatypusDeviceError(rc, "region %d: nothing is set for it" % k, "plat_caller_source_lines")
+            out.append(C.string_at(text, length.value) if length.value else b"")
+        return out
+
     def _set_source(self, source_lines, source_blocks, options):
         """The source of the next call, whichever way it was given (not both); returns what has to stay alive until it has returned."""
         if source_lines is not None and source_blocks is not None:
@@ -927,13 +1032,19 @@ class NativeCaller:
         names = (C.c_char_p * len(sample_names))(*[s.encode() for s in sample_names])
         return names, CallerOptions.from_options(options), C.c_void_p(), C.c_size_t(), CallerStats()
 
-    def call_regions(self, regions, sample_names, options, source_lines=None, source_blocks=None):
+    def call_regions(self, regions, sample_names, options, source_lines=None, source_blocks=None, source_files=None):
         """regions: list of RegionReads.  Returns the record lines of all regions (str), in region order; options.rlen is updated
         as the reference updates it.  source_lines: per region the text its source VCF fetches returned (set_source_lines; longHaps is
         options.longHaps): candidates from the source join those of the reads.  source_blocks: the same from the BGZF blocks of the
-        fetches (set_source_blocks)."""
+        fetches (set_source_blocks).  source_files: the same from whole files and their open indexes, [(data, NativeIndex)], fetched for
+        every region's chrom:start-end (set_source_files)."""
         n, nS = len(regions), len(sample_names)
-        keep = self._set_source(source_lines, source_blocks, options)
+        if source_files is not None:
+            if source_lines is not None or source_blocks is not None:
+                raise ValueError("source_lines, source_blocks and source_files are three ways to say the same thing: give one")
+            keep = self.set_source_files(source_files, [(r.chrom, r.start, r.end) for r in regions], getattr(options, "longHaps", 0))
+        else:
+            keep = self._set_source(source_lines, source_blocks, options)
         arr = (_Region * max(n, 1))()
         for k, r in enumerate(regions):
             r.fill(arr[k], nS)

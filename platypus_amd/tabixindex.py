@@ -1,6 +1,7 @@
 """A tabix index (.tbi) read in plain Python, and a query's chunks cut out of the bgzipped file as BGZF blocks -- what an integrator's
-loader does in front of plat_caller_set_source_blocks (include/platypus_caller_tabix.h).  The C library reads no index; this module serves
-the command line and the tests.
+loader does in front of plat_caller_set_source_blocks (include/platypus_caller_tabix.h).  The C library reads an index itself
+(include/platypus_caller_index.h: opened once, queried in device batches); this module is the plain-Python statement of the same rule and
+serves the tests, and TabixFile.fetch_blocks_batch hands a list of fetches to the library's index.
 
 The layout is the public one (the tabix format description: magic TBI\\1, n_ref, format, col_seq, col_beg, col_end, meta, skip, l_nm, the
 names, then per sequence the bins with their chunks and the linear index), gzip-compressed.  The chunk list of a query is chosen as
@@ -96,6 +97,46 @@ class TabixIndex:
         return [tuple(c) for c in out]
 
 
+BAI_MAGIC = b"BAI\x01"
+PSEUDO_BIN = 37450
+
+
+class BamIndex:
+    """A BAM index (.bai, uncompressed): the same bins, chunks and linear index per reference, no names; the metadata pseudo-bin 37450 is
+    left out of bins and kept in pseudo[tid]; n_no_coor is the trailing count, None when the file has none.  query is TabixIndex's."""
+
+    def __init__(self, raw):
+        data = bytes(raw)
+        if data[:4] != BAI_MAGIC:
+            raise ValueError("not a BAM index (no BAI\\1 magic)")
+        n_ref, = struct.unpack_from("<i", data, 4)
+        at = 8
+        self.bins, self.linear, self.pseudo = [], [], []
+        for _ in range(n_ref):
+            n_bin, = struct.unpack_from("<i", data, at)
+            at += 4
+            bins, pseudo = {}, None
+            for _ in range(n_bin):
+                b, n_chunk = struct.unpack_from("<Ii", data, at)
+                at += 8
+                v = struct.unpack_from("<%dQ" % (2 * n_chunk), data, at)
+                at += 16 * n_chunk
+                if b == PSEUDO_BIN:
+                    pseudo = list(zip(v[0::2], v[1::2]))
+                else:
+                    bins[b] = list(zip(v[0::2], v[1::2]))
+            n_intv, = struct.unpack_from("<i", data, at)
+            at += 4
+            self.linear.append(list(struct.unpack_from("<%dQ" % n_intv, data, at)))
+            at += 8 * n_intv
+            self.bins.append(bins)
+            self.pseudo.append(pseudo)
+        self.n_no_coor = struct.unpack_from("<Q", data, at)[0] if len(data) - at >= 8 else None
+        self.names = []
+
+    query = TabixIndex.query
+
+
 def block_length(data, at):
     """The length of the BGZF block at data[at] (its BSIZE + 1), the BC subfield looked for among the extra subfields."""
     if data[at:at + 4] != b"\x1f\x8b\x08\x04":
@@ -126,6 +167,7 @@ class TabixFile:
 
     def __init__(self, data, index):
         self.data = bytes(data)
+        self.raw_index = None if isinstance(index, TabixIndex) else bytes(index)
         self.index = index if isinstance(index, TabixIndex) else TabixIndex(index)
 
     @classmethod
@@ -141,3 +183,21 @@ class TabixFile:
         if chunks is None:
             return None
         return (self.index.names[tid], max(beg, 0), end, cut_chunks(self.data, chunks))
+
+    def fetch_blocks_batch(self, queries, caller, native_index=None):
+        """fetch_blocks for a list of (name, beg, end), the chunk lists chosen by the library in one device batch (NativeCaller.query_index
+        over this file's index, opened on `caller` unless native_index is one already).  Needs the index's bytes (TabixFile(data, raw))."""
+        opened = native_index is None
+        idx = caller.open_index(self.raw_index, "tbi") if opened else native_index
+        try:
+            tids = [idx.tid(name) for name, _, _ in queries]
+            asked = [(t, b, e) for t, (_, b, e) in zip(tids, queries) if t >= 0]
+            lists = iter(caller.query_index(idx, asked))
+            out = []
+            for t, (_, beg, end) in zip(tids, queries):
+                chunks = next(lists) if t >= 0 else None
+                out.append(None if chunks is None else (self.index.names[t], max(beg, 0), end, cut_chunks(self.data, chunks)))
+            return out
+        finally:
+            if opened:
+                idx.close()
