@@ -7,7 +7,7 @@
 #include "../../../include/platypus_caller_bgzfout.h"
 #include "../bgzf_deflate.hpp"
 
-// referenced weakly, as plat_bgzf_inflate_batch (bgzf_regions.hpp): the CPU suite's stand-in device library predates it
+// referenced weakly, as plat_bgzf_inflate_batch (bgzf_blocks.hpp): the CPU suite's stand-in device library predates it
 #pragma weak plat_bgzf_deflate_batch
 
 namespace plathost {
@@ -50,8 +50,7 @@ struct BgzfOut {
     }
 
     void onDevice(Slice& s, Slot& z) const {
-        FetchedDeviceBuffers dev;
-        dev.ctx = z.ctx;
+        FetchedDeviceBuffers dev(z);
         void* st = z.stream;
         const int n = s.end - s.first;
         const std::vector<int64_t> off = offsets(s);
@@ -72,8 +71,8 @@ struct BgzfOut {
             o.cap_bytes = cap;
             o.data = dev.alloc<uint8_t>((size_t)cap + PLAT_BLOB_PAD);
             ck(plat_bgzf_deflate_batch(z.ctx, &in, &o, st), "plat_bgzf_deflate_batch");
-            ck(plat_memcpy_d2h(z.ctx, status, o.status, sizeof status, st), "plat_memcpy_d2h");
-            ck(plat_memcpy_d2h(z.ctx, s.off.data(), o.piece_out_off, s.off.size() * sizeof(int64_t), st), "plat_memcpy_d2h");
+            dev.download(status, o.status, 4, st);
+            dev.download(s.off, o.piece_out_off, st);
             ck(plat_stream_sync(z.ctx, st), "plat_stream_sync");
             if (status[0] != PLAT_ERR_OVERFLOW || attempt == 1) break;
             cap = status[2];
@@ -106,49 +105,46 @@ CALLER_EXPORT int plat_caller_compress_text(plat_caller* c, const char* text, si
           return PLAT_ERR_INVALID;
       } }
     const bool onHost = Switches::read().hostDeflate;
-    if (!onHost && !plat_bgzf_deflate_batch) {
-        c->lastError = "plat_caller_compress_text: the device library has no plat_bgzf_deflate_batch";
-        return PLAT_ERR_UNSUPPORTED;
-    }
-    BgzfOut W(text, region_len, n_regions, level);
-    // the workers take slices in turn
-    const int nT = (int)std::max<size_t>(1, std::min(c->slots.size(), W.slices.size()));
-    std::atomic<size_t> next(0);
-    std::mutex errMutex;
-    int firstError = PLAT_OK;
-    std::string errText;
-    auto work = [&](Slot* z) {
-        try {
-            std::unique_ptr<bgzf::Deflater> d(onHost ? new bgzf::Deflater : nullptr);
-            for (size_t k; (k = next.fetch_add(1)) < W.slices.size();) {
-                if (onHost) W.onHost(W.slices[k], *d); else W.onDevice(W.slices[k], *z);
+    const std::string entry = "plat_caller_compress_text";
+    const int rc = onHost ? PLAT_OK : needsEntryPoints(c, entry, {(const void*)plat_bgzf_deflate_batch}, "plat_bgzf_deflate_batch");
+    if (rc != PLAT_OK) return rc;
+    return guardedEntry(c, entry, [&] {
+        BgzfOut W(text, region_len, n_regions, level);
+        // the workers take slices in turn (an exception cannot cross their threads: each keeps the first error for the call)
+        const int nT = (int)std::max<size_t>(1, std::min(c->slots.size(), W.slices.size()));
+        std::atomic<size_t> next(0);
+        std::mutex errMutex;
+        int firstError = PLAT_OK;
+        std::string errText;
+        auto work = [&](Slot* z) {
+            try {
+                std::unique_ptr<bgzf::Deflater> d(onHost ? new bgzf::Deflater : nullptr);
+                for (size_t k; (k = next.fetch_add(1)) < W.slices.size();) {
+                    if (onHost) W.onHost(W.slices[k], *d); else W.onDevice(W.slices[k], *z);
+                }
+            } catch (const std::exception& e) {
+                std::lock_guard<std::mutex> g(errMutex);
+                if (firstError == PLAT_OK) firstError = errorOf(e, entry, errText);
+                next.store(W.slices.size());
             }
-        } catch (const DeviceError& e) {
-            std::lock_guard<std::mutex> g(errMutex);
-            if (firstError == PLAT_OK) { firstError = e.code; errText = e.what(); }
-            next.store(W.slices.size());
-        } catch (const std::exception& e) {
-            std::lock_guard<std::mutex> g(errMutex);
-            if (firstError == PLAT_OK) { firstError = PLAT_ERR_NOMEM; errText = std::string("plat_caller_compress_text: ") + e.what(); }
-            next.store(W.slices.size());
+        };
+        { std::vector<std::thread> threads;
+          for (int i = 1; i < nT; ++i) threads.emplace_back(work, c->slots[(size_t)i].get());
+          work(c->slots[0].get());
+          for (std::thread& t : threads) t.join(); }
+        if (firstError != PLAT_OK) { c->lastError = errText; return firstError; }
+        size_t total = with_eof ? sizeof bgzf::EOF_BLOCK : 0;
+        for (const BgzfOut::Slice& s : W.slices) total += s.data.size();
+        uint8_t* block = (uint8_t*)malloc(total ? total : 1);
+        if (!block) return (int)PLAT_ERR_NOMEM;
+        size_t at = 0;
+        for (const BgzfOut::Slice& s : W.slices) {
+            if (!s.data.empty()) memcpy(block + at, s.data.data(), s.data.size());
+            if (region_out_len) for (int k = s.first; k < s.end; ++k) region_out_len[k] = s.off[(size_t)(k - s.first) + 1] - s.off[(size_t)(k - s.first)];
+            at += s.data.size();
         }
-    };
-    { std::vector<std::thread> threads;
-      for (int i = 1; i < nT; ++i) threads.emplace_back(work, c->slots[(size_t)i].get());
-      work(c->slots[0].get());
-      for (std::thread& t : threads) t.join(); }
-    if (firstError != PLAT_OK) { c->lastError = errText; return firstError; }
-    size_t total = with_eof ? sizeof bgzf::EOF_BLOCK : 0;
-    for (const BgzfOut::Slice& s : W.slices) total += s.data.size();
-    uint8_t* block = (uint8_t*)malloc(total ? total : 1);
-    if (!block) return PLAT_ERR_NOMEM;
-    size_t at = 0;
-    for (const BgzfOut::Slice& s : W.slices) {
-        if (!s.data.empty()) memcpy(block + at, s.data.data(), s.data.size());
-        if (region_out_len) for (int k = s.first; k < s.end; ++k) region_out_len[k] = s.off[(size_t)(k - s.first) + 1] - s.off[(size_t)(k - s.first)];
-        at += s.data.size();
-    }
-    if (with_eof) memcpy(block + at, bgzf::EOF_BLOCK, sizeof bgzf::EOF_BLOCK);
-    *out = block; *out_len = total;
-    return PLAT_OK;
+        if (with_eof) memcpy(block + at, bgzf::EOF_BLOCK, sizeof bgzf::EOF_BLOCK);
+        *out = block; *out_len = total;
+        return (int)PLAT_OK;
+    });
 }

@@ -1,119 +1,55 @@
 // bgzf_regions.hpp -- plat_call_bgzf_regions (include/platypus_caller_bgzf.h): the region loop for the BGZF blocks of an index lookup.  A
 // front end on front_end.hpp's frame, in front of bam_regions.hpp's decode: the chunks' compressed bytes go to the device as they are,
-// plat_bgzf_inflate_batch inflates them, plat_bam_find_records is sam_itr_next, plat_bam_decode_batch takes the kept records' offsets where
-// the find left them (a RecordList), and decodeAndStage does the rest.  The host reads each block's header and trailer (the BSIZE chain, the
-// ISIZE words that size the inflate's output) and never a payload byte.
-// Included at the end of region_caller.cpp, after bam_regions.hpp.
+// plat_bgzf_inflate_batch inflates them (bgzf_blocks.hpp: the walk over the block headers, the upload and the inflate), plat_bam_find_records
+// is sam_itr_next, plat_bam_decode_batch takes the kept records' offsets where the find left them (a RecordList), and decodeAndStage does
+// the rest.  The host never reads a payload byte.
+// Included at the end of region_caller.cpp, after bam_regions.hpp and bgzf_blocks.hpp.
 #pragma once
 #include "../../../include/platypus_caller_bgzf.h"
-#include "../bgzf_inflate.hpp"
 
-// referenced weakly, as plat_bam_decode_batch: the CPU suite's stand-in device library predates them
-#pragma weak plat_bgzf_inflate_batch
+// referenced weakly, as plat_bam_decode_batch: the CPU suite's stand-in device library predates it
 #pragma weak plat_bam_find_records
 
 namespace plathost {
 
-struct BgzfChunkAt { int region, sample, chunk, blkFirst, blkEnd; };      // where a chunk came from and its blocks in the call's list
-
-// what every entry point checks of a chunk before it reads its data
-inline bool bgzfChunkArgsOk(const plat_bgzf_chunk& ch) {
-    return !(ch.data_len < 0 || (ch.data_len && !ch.data) || ch.first_uoffset < 0 || ch.first_uoffset > 65535 || ch.end_uoffset < 0 || ch.end_uoffset > 65536 ||
-             ch.end_coffset < -1 || ch.end_coffset > ch.data_len);
-}
-// The BSIZE chain of one chunk's data (18 header bytes and the trailer of every block): block(at, head) for every block in order, false
-// ends the walk.  Returns -1 when the chain covers the data, -2 when block() ended it, else the offset at which no valid header stands.
-template <class Block> inline int64_t walkBgzfChain(const plat_bgzf_chunk& ch, Block&& block) {
-    for (int64_t at = 0; at < ch.data_len;) {
-        bgzf::BlockHead h;
-        if (bgzf::parse_header(ch.data, ch.data_len, at, &h) != 0) return at;
-        if (!block(at, h)) return -2;
-        at = h.payload + h.payload_len + 8;
-    }
-    return -1;
-}
-
 // The chunks of one call -- every (region, unit) in order, a unit being what one index lookup fetched (a sample; a file for the read-group
-// call of rg_regions.hpp) -- from the host's walk over the block headers to the kept records' offsets on the device.
+// call of rg_regions.hpp) -- from the block list to the kept records' offsets on the device.
 struct BgzfFront {
     FrontCall& F;
     const std::string& entry;
     const int nUnits;
     const char* const unit;                                               // what the messages call one: "sample" or "file"
-    // the call's blocks and chunks, all regions: which of them load is known once the device has counted the kept records
-    std::vector<BgzfChunkAt> chunkAt;
-    std::vector<const plat_bgzf_chunk*> chunkOf;
-    std::vector<int64_t> blkOff, blkLimit;
-    std::vector<int32_t> firstU, stopBlk, stopU, tid, beg, end;           // per chunk; tid / beg / end per region
-    long long blobBytes = 0, inflated = 0;
-    int nBlocks = 0;
+    BgzfBlockList L;                                                      // the call's blocks and chunks, all regions: which of them load is known once the device has counted the kept records
+    std::vector<int32_t> tid, beg, end;                                   // per region
     plat_bgzf_inflate_out io;
     plat_bam_find_out fo;
     long long capRecords = 0;
     int64_t inflateStatus[4] = {0, -1, 0, 0}, findStatus[4] = {0, -1, 0, 0};
 
-    BgzfFront(FrontCall& f, int n_units, const char* unit_) : F(f), entry(f.entry), nUnits(n_units), unit(unit_) {}
-
-    std::string where(const BgzfChunkAt& a) const { return F.where(a.region, a.sample, unit) + ", chunk " + std::to_string(a.chunk); }
+    BgzfFront(FrontCall& f, int n_units, const char* unit_)
+        : F(f), entry(f.entry), nUnits(n_units), unit(unit_),
+          L(f.entry, [this](const BgzfChunkAt& a) { return F.where(a.region, a.unit, unit) + ", chunk " + std::to_string(a.chunk); }, false, f.c->lastError) {}
 
     void addRegion(int32_t t, int32_t b, int32_t e) { tid.push_back(t); beg.push_back(b); end.push_back(e); }
 
-    // unit i of region k: its chunks checked, the BSIZE chain of each walked (18 header bytes and the trailer of every block)
+    // unit i of region k: its chunks onto the list
     int addUnit(int k, int i, int n_chunks, const plat_bgzf_chunk* chunks)
     {
-        plat_caller* c = F.c;
-        for (int q = 0; q < n_chunks; ++q) {
-            const plat_bgzf_chunk& ch = chunks[q];
-            if (!bgzfChunkArgsOk(ch)) return PLAT_ERR_INVALID;
-            BgzfChunkAt a{k, i, q, (int)blkOff.size(), 0};
-            int endBlk = ch.end_coffset < 0 || (ch.end_coffset == ch.data_len && ch.end_uoffset == 0) ? -1 : -2;       // -2: not found yet
-            const int64_t broke = walkBgzfChain(ch, [&](int64_t at, const bgzf::BlockHead& h) {
-                if (at == ch.end_coffset) endBlk = (int)blkOff.size();
-                blkOff.push_back(blobBytes + at); blkLimit.push_back(blobBytes + ch.data_len);
-                inflated += h.isize;
-                return blkOff.size() < (size_t)INT_MAX;
-            });
-            if (broke == -2) { c->lastError = entry + ": more blocks than one call takes"; return PLAT_ERR_OVERFLOW; }
-            if (broke >= 0) {
-                c->lastError = entry + ": the BGZF blocks of " + where(a) + " do not chain: no valid block header at offset " +
-                               std::to_string(broke) + " of its data (bad magic, no BC subfield, or a block that leaves the data)";
-                return PLAT_ERR_BAD_INPUT;
-            }
-            if (endBlk == -2) {
-                c->lastError = entry + ": end_coffset " + std::to_string(ch.end_coffset) + " of " + where(a) + " is not a block boundary of its data";
-                return PLAT_ERR_BAD_INPUT;
-            }
-            a.blkEnd = (int)blkOff.size();
-            chunkAt.push_back(a); chunkOf.push_back(&ch);
-            firstU.push_back(ch.first_uoffset); stopBlk.push_back(endBlk); stopU.push_back(endBlk < 0 ? 0 : ch.end_uoffset);
-            blobBytes += ch.data_len;
-        }
+        for (int q = 0; q < n_chunks; ++q) { const int rc = L.add(k, i, q, chunks[q]); if (rc != PLAT_OK) return rc; }
         return PLAT_OK;
     }
 
-    // upload and inflate, back to back
+    // upload and inflate, back to back; room for the find's records
     void inflate()
     {
-        Slot& z = *F.z;
         FetchedDeviceBuffers& dev = F.dev;
-        void* st = z.stream;
-        nBlocks = (int)blkOff.size();
-        uint8_t* dBlob = dev.alloc<uint8_t>((size_t)blobBytes);
-        { long long base = 0;
-          for (const plat_bgzf_chunk* ch : chunkOf) {
-              if (ch->data_len) ck(plat_memcpy_h2d(z.ctx, dBlob + base, ch->data, (size_t)ch->data_len, st), "plat_memcpy_h2d(blocks)");
-              base += ch->data_len;
-          } }
-        memset(&io, 0, sizeof io);
-        io.cap_bytes = inflated;
-        io.data = dev.alloc<uint8_t>((size_t)inflated + PLAT_BLOB_PAD); io.out_off = dev.alloc<int64_t>((size_t)nBlocks + 1); io.status = dev.alloc<int64_t>(4);
-        ck(plat_bgzf_inflate_batch(z.ctx, nBlocks, dBlob, blobBytes, dev.upload(blkOff, st), dev.upload(blkLimit, st), &io, st), "plat_bgzf_inflate_batch");
+        io = L.inflateOnDevice(*F.z, dev);
         // every record has a block_size word and 32 fixed bytes
-        capRecords = inflated / 36 + 1;
+        capRecords = L.inflated / 36 + 1;
         memset(&fo, 0, sizeof fo);
         fo.cap_records = capRecords; fo.rec_off = dev.alloc<int64_t>((size_t)capRecords); fo.rec_limit = dev.alloc<int64_t>((size_t)capRecords);
         fo.status = dev.alloc<int64_t>(4);
-        ck(plat_memcpy_d2h(z.ctx, inflateStatus, io.status, sizeof inflateStatus, st), "plat_memcpy_d2h");
+        dev.download(inflateStatus, io.status, 4, F.z->stream);
     }
 
     // the find over the streams of the regions `use` marks (stream = unit i of such a region, in order; its chunks lie back to back in the
@@ -128,10 +64,10 @@ struct BgzfFront {
         size_t q = 0;
         for (int k = 0; k < n_regions; ++k)
             for (int i = 0; i < nUnits; ++i) {
-                for (; q < chunkAt.size() && chunkAt[q].region == k && chunkAt[q].sample == i; ++q) {
+                for (; q < L.chunkAt.size() && L.chunkAt[q].region == k && L.chunkAt[q].unit == i; ++q) {
                     if (!use[(size_t)k]) continue;
-                    cFirst.push_back(chunkAt[q].blkFirst); cEnd.push_back(chunkAt[q].blkEnd);
-                    cFirstU.push_back(firstU[q]); cStopBlk.push_back(stopBlk[q]); cStopU.push_back(stopU[q]);
+                    cFirst.push_back(L.chunkAt[q].blkFirst); cEnd.push_back(L.chunkAt[q].blkEnd);
+                    cFirstU.push_back(L.firstU[q]); cStopBlk.push_back(L.stopBlk[q]); cStopU.push_back(L.stopU[q]);
                 }
                 if (!use[(size_t)k]) continue;
                 chunkBegin.push_back((int32_t)cFirst.size());
@@ -140,32 +76,23 @@ struct BgzfFront {
         const int n = (int)sTid.size();
         plat_bam_find_in fi;
         memset(&fi, 0, sizeof fi);
-        fi.n_streams = n; fi.n_chunks = (int)cFirst.size(); fi.n_blocks = nBlocks; fi.data = io.data; fi.out_off = io.out_off;
+        fi.n_streams = n; fi.n_chunks = (int)cFirst.size(); fi.n_blocks = L.nBlocks(); fi.data = io.data; fi.out_off = io.out_off;
         fi.chunk_blk_first = dev.upload(cFirst, st); fi.chunk_blk_end = dev.upload(cEnd, st); fi.chunk_first_uoffset = dev.upload(cFirstU, st);
         fi.chunk_stop_blk = dev.upload(cStopBlk, st); fi.chunk_stop_uoffset = dev.upload(cStopU, st);
         fi.stream_chunk_begin = dev.upload(chunkBegin, st);
         fi.tid = dev.upload(sTid, st); fi.beg = dev.upload(sBeg, st); fi.end = dev.upload(sEnd, st);
         fo.stream_begin = dev.alloc<int32_t>((size_t)n + 1);
         ck(plat_bam_find_records(z.ctx, &fi, &fo, st), "plat_bam_find_records");
-        kept.blob = io.data; kept.bytes = inflated; kept.off = fo.rec_off; kept.limit = fo.rec_limit; kept.dBegin = fo.stream_begin;
+        kept.blob = io.data; kept.bytes = L.inflated; kept.off = fo.rec_off; kept.limit = fo.rec_limit; kept.dBegin = fo.stream_begin;
         kept.begin.assign((size_t)n + 1, 0);
-        ck(plat_memcpy_d2h(z.ctx, kept.begin.data(), fo.stream_begin, kept.begin.size() * sizeof(int32_t), st), "plat_memcpy_d2h");
-        ck(plat_memcpy_d2h(z.ctx, findStatus, fo.status, sizeof findStatus, st), "plat_memcpy_d2h");
+        dev.download(kept.begin, fo.stream_begin, st);
+        dev.download(findStatus, fo.status, 4, st);
     }
 
     // after the wait behind the first find (every region took part): 0, or the inflate's or the find's error with its message
     int firstFailure() const
     {
-        if (inflateStatus[0] != 0) {
-            const long long b = inflateStatus[1];
-            size_t q = 0;
-            while (q + 1 < chunkAt.size() && !(b >= chunkAt[q].blkFirst && b < chunkAt[q].blkEnd)) ++q;
-            const BgzfChunkAt a = chunkAt.empty() ? BgzfChunkAt{0, 0, 0, 0, 0} : chunkAt[q];
-            F.c->lastError = entry + ": block " + std::to_string(b - a.blkFirst) + " of " + where(a) +
-                             (inflateStatus[0] == PLAT_ERR_OVERFLOW ? " does not fit the room its ISIZE words asked for"
-                                                                    : " cannot be inflated (a bad header, an invalid deflate stream, output other than ISIZE bytes, or a CRC32 mismatch)");
-            return (int)inflateStatus[0];
-        }
+        if (inflateStatus[0] != 0) return L.blockRefused(inflateStatus[1], (int)inflateStatus[0]);
         if (findStatus[0] != 0) {                                          // (stream s is unit s % nUnits of region s / nUnits)
             const int s = (int)findStatus[1];
             F.c->lastError = entry + ": the record walk of " + F.where(s / nUnits, s % nUnits, unit) +
@@ -203,7 +130,7 @@ struct BgzfFront {
 
     long long loadedBytes(const std::vector<int>& loaded) const {
         long long b = 0;
-        for (const BgzfChunkAt& a : chunkAt) if (loaded[(size_t)a.region]) b += chunkOf[(size_t)(&a - chunkAt.data())]->data_len;
+        for (size_t q = 0; q < L.chunkAt.size(); ++q) if (loaded[(size_t)L.chunkAt[q].region]) b += L.chunkOf[q]->data_len;
         return b;
     }
 };
@@ -219,21 +146,22 @@ CALLER_EXPORT int plat_call_bgzf_regions(plat_caller* c, const plat_bgzf_region*
                                     (const void*)plat_read_buffers_batch}, "plat_bgzf_inflate_batch");
     if (rc != PLAT_OK) return rc;
     FetchedStage& S = F.S;
-    BgzfFront W(F, n_samples, "sample");
-    for (int k = 0; k < n_regions; ++k) {
-        const plat_bgzf_region& r = regions[k];
-        if (!r.samples) return PLAT_ERR_INVALID;
-        W.addRegion(r.tid, r.itr_beg, r.itr_end);
-        for (int i = 0; i < n_samples; ++i) {
-            const plat_bgzf_sample& sm = r.samples[i];
-            if (sm.n_chunks < 0 || (sm.n_chunks && !sm.chunks) || !recordsValid(sm.broken_mates)) return PLAT_ERR_INVALID;
-            if ((rc = W.addUnit(k, i, sm.n_chunks, sm.chunks)) != PLAT_OK) return rc;
-        }
-    }
     return F.guarded([&] {
+        BgzfFront W(F, n_samples, "sample");
+        int rc;
+        for (int k = 0; k < n_regions; ++k) {
+            const plat_bgzf_region& r = regions[k];
+            if (!r.samples) return PLAT_ERR_INVALID;
+            W.addRegion(r.tid, r.itr_beg, r.itr_end);
+            for (int i = 0; i < n_samples; ++i) {
+                const plat_bgzf_sample& sm = r.samples[i];
+                if (sm.n_chunks < 0 || (sm.n_chunks && !sm.chunks) || !recordsValid(sm.broken_mates)) return PLAT_ERR_INVALID;
+                if ((rc = W.addUnit(k, i, sm.n_chunks, sm.chunks)) != PLAT_OK) return rc;
+            }
+        }
         W.inflate();                                                       // upload, inflate, find: back to back
         RecordList kept;
-        int rc = W.findLoaded(kept, [](const std::vector<int>&) {});
+        rc = W.findLoaded(kept, [](const std::vector<int>&) {});
         if (rc != PLAT_OK) return rc;
         std::vector<const plat_bam_records*> broken;
         long long nBroken = 0;

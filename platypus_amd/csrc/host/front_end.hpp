@@ -1,9 +1,12 @@
 // front_end.hpp -- what the front ends of the region loop share (fetched_regions.hpp, bam_regions.hpp, bgzf_regions.hpp, rg_regions.hpp): the
-// frame of one call (FrontCall: the checks at entry, loadBAMData's bail-out, the overflow test, the one try/catch, the names of places in
-// messages) and everything from the QC call on (FrontCall::finish: checkAndTrimRead, reads / badReads, isSorted on the device --
+// frame of one call (FrontCall: the checks at entry, loadBAMData's bail-out, the overflow test, the names of places in messages) and
+// everything from the QC call on (FrontCall::finish: checkAndTrimRead, reads / badReads, isSorted on the device --
 // plat_read_buffers_batch, plat_read_buffers_packed_batch -- the host's copies of the split tables, the region loop, info and stats).  A
 // front end leaves the call's read table on the device plus the host mirror the later stages need (FetchedStage) and ends in finish.
 // RecordList is the one form in which raw BAM records reach the decode (bam_regions.hpp), whoever put them on the device.
+// Every entry point that runs a batch on slot 0's stream, the side ones too (tabix_source.hpp, index_source.hpp, bgzf_out.hpp, tbi_out.hpp),
+// shares the check for device entry points (needsEntryPoints), the one try/catch (guardedEntry) and the call's device memory
+// (FetchedDeviceBuffers).
 // Included at the end of region_caller.cpp, in front of the four (it calls callRegions and reads plat_caller).
 #pragma once
 #include <climits>
@@ -20,6 +23,8 @@ namespace plathost {
 struct FetchedDeviceBuffers {
     plat_ctx* ctx = nullptr;
     std::vector<void*> held;
+    FetchedDeviceBuffers() {}
+    explicit FetchedDeviceBuffers(Slot& z) : ctx(z.ctx) {}
     template <class T> T* alloc(size_t n) {
         void* p = nullptr;
         ck(plat_malloc(ctx, std::max<size_t>(n, 1) * sizeof(T), &p), "plat_malloc");
@@ -31,8 +36,30 @@ struct FetchedDeviceBuffers {
         if (!h.empty()) ck(plat_memcpy_h2d(ctx, d, h.data(), h.size() * sizeof(T), stream), "plat_memcpy_h2d");
         return d;
     }
+    // n elements back, behind what the stream holds (the caller waits); a vector: all of it, nothing queued for an empty one
+    template <class T> void download(T* host, const T* dev, size_t n, void* stream) { ck(plat_memcpy_d2h(ctx, host, dev, n * sizeof(T), stream), "plat_memcpy_d2h"); }
+    template <class T> void download(std::vector<T>& host, const T* dev, void* stream) { if (!host.empty()) download(host.data(), dev, host.size(), stream); }
     ~FetchedDeviceBuffers() { for (void* p : held) plat_free(ctx, p); }
 };
+
+// 0, or PLAT_ERR_UNSUPPORTED with its message when one of the device entry points `fns` is not there
+inline int needsEntryPoints(plat_caller* c, const std::string& entry, std::initializer_list<const void*> fns, const char* missing) {
+    for (const void* f : fns)
+        if (!f) { c->lastError = entry + ": the device library has no " + missing; return PLAT_ERR_UNSUPPORTED; }
+    return PLAT_OK;
+}
+
+// what an exception leaves of a call: a device error's code and text, PLAT_ERR_NOMEM and the entry point's name in front of any other
+inline int errorOf(const std::exception& e, const std::string& entry, std::string& text) {
+    if (const DeviceError* d = dynamic_cast<const DeviceError*>(&e)) { text = d->what(); return d->code; }
+    text = entry + ": " + e.what();
+    return PLAT_ERR_NOMEM;
+}
+// fn() with whatever it throws turned into the call's error: no exception leaves a C entry point
+template <class Fn> inline int guardedEntry(plat_caller* c, const std::string& entry, Fn&& fn) {
+    try { return fn(); }
+    catch (const std::exception& e) { return errorOf(e, entry, c->lastError); }
+}
 
 // one buffer (reads or badReads) of one sample as the host's stages see it: per-read arrays and bases, no qualities (packed: the bytes as
 // handed over -- the host's stages read their base bits only -- and the exceptions, indexed into the buffer, with the trimmed qualities)
@@ -116,12 +143,7 @@ struct FrontCall {
         : sourceGuard(c_), c(c_), entry(entry_), n_regions(n_regions_), n_samples(n_samples_), sample_names(sample_names_), options(options_), qc(qc_),
           out_text(out_text_), out_len(out_len_), info(info_), stats(stats_) {}
 
-    // 0, or PLAT_ERR_UNSUPPORTED with its message when one of the device entry points `fns` is not there
-    int needs(std::initializer_list<const void*> fns, const char* missing) {
-        for (const void* f : fns)
-            if (!f) { c->lastError = entry + ": the device library has no " + missing; return PLAT_ERR_UNSUPPORTED; }
-        return PLAT_OK;
-    }
+    int needs(std::initializer_list<const void*> fns, const char* missing) { return needsEntryPoints(c, entry, fns, missing); }
 
     // The checks at entry, in the order every front end has made them: the call's arguments, the front end's own (argsOk) and the regions
     // pointer, the device entry points; then the clock, maxReads as the loader holds it, slot 0, nothing loaded yet, the regions' heads.
@@ -158,11 +180,7 @@ struct FrontCall {
         return PLAT_OK;
     }
 
-    // fn() with a device error turned into the call's error
-    template <class Fn> int guarded(Fn&& fn) {
-        try { return fn(); }
-        catch (const DeviceError& e) { c->lastError = e.what(); return e.code; }
-    }
+    template <class Fn> int guarded(Fn&& fn) { return guardedEntry(c, entry, fn); }
 
     // "region K (chr:a-b), sample I" (unit: what I counts -- a sample, or a file of the merged-file calls)
     std::string where(int k, int i, const char* unit = "sample") const {
@@ -209,12 +227,9 @@ inline int FrontCall::finish()
     else if (nStreams) ck(plat_read_buffers_batch(z->ctx, &S.in, &qo, dOk, dWhy, dPerm, dCounts, &g, st), "plat_read_buffers_batch");
     // what the host's stages need back: the split, the counts and the flags after QC (QCFail, improper pairs)
     std::vector<int32_t> perm((size_t)N), flagsQc((size_t)N), counts((size_t)nStreams * 10, 0);
-    if (N) {
-        ck(plat_memcpy_d2h(z->ctx, perm.data(), dPerm, sizeof(int32_t) * (size_t)N, st), "plat_memcpy_d2h");
-        ck(plat_memcpy_d2h(z->ctx, flagsQc.data(), S.in.qc.read_flags, sizeof(int32_t) * (size_t)N, st), "plat_memcpy_d2h");
-    }
-    if (nStreams) ck(plat_memcpy_d2h(z->ctx, counts.data(), dCounts, sizeof(int32_t) * counts.size(), st), "plat_memcpy_d2h");
-    if (S.dExcQual) ck(plat_memcpy_d2h(z->ctx, S.excQual.data(), S.dExcQual, S.excQual.size(), st), "plat_memcpy_d2h");     // (trimmed)
+    dev.download(perm, dPerm, st); dev.download(flagsQc, S.in.qc.read_flags, st);
+    dev.download(counts, dCounts, st);
+    if (S.dExcQual) dev.download(S.excQual.data(), S.dExcQual, S.excQual.size(), st);     // (trimmed)
     ck(plat_stream_sync(z->ctx, st), "plat_stream_sync");
 
     // the buffers, as the host sees them and as the device holds them

@@ -1,5 +1,5 @@
 // index_source.hpp -- plat_index_* and plat_caller_set_source_files (include/platypus_caller_index.h): a .tbi or .bai opened once --
-// inflated (a .tbi) and flattened on the host by idxq::flatten (csrc/index_query.hpp), the tables uploaded --, a call's queries answered
+// inflated (a .tbi: bgzf_blocks.hpp's host inflate over the file as one chunk) and flattened on the host by idxq::flatten (csrc/index_query.hpp), the tables uploaded --, a call's queries answered
 // by plat_index_query_batch in one batch on slot 0's stream with one wait (queries the device hands over, and every query under
 // PLAT_CALLER_HOST_INDEX=1, by idxq::query, the host twin), and source VCFs taken as files: per file one batch of queries, every chunk
 // cut out of the file as tabixindex.cut_chunks cuts it, and from there plat_caller_set_source_blocks.
@@ -28,20 +28,13 @@ namespace plathost {
 inline bool inflateIndexBytes(const uint8_t* file, int64_t len, std::vector<uint8_t>& out)
 {
     out.clear();
-    uint32_t crcTable[256];
-    for (uint32_t i = 0; i < 256; ++i) crcTable[i] = bgzf::crc_table_entry(i);
-    std::unique_ptr<bgzf::Tables> tables(new bgzf::Tables);
     if (len <= 0) return false;
-    for (int64_t at = 0; at < len;) {
-        bgzf::BlockHead h;
-        if (bgzf::parse_header(file, len, at, &h) != 0) return false;
-        const size_t before = out.size();
-        if (before + h.isize > ((size_t)1 << 31)) return false;
-        out.resize(before + h.isize);
-        if (bgzf::inflate_block(file, len, at, out.data() + before, (int64_t)h.isize, *tables, crcTable) != (int64_t)h.isize) return false;
-        at = h.payload + h.payload_len + 8;
-    }
-    return true;
+    plat_bgzf_chunk ch;
+    memset(&ch, 0, sizeof ch);
+    ch.data = file; ch.data_len = len; ch.end_coffset = -1;
+    std::string why;                                                      // (plat_index_open has one message for all of it)
+    BgzfBlockList L("plat_index_open", [](const BgzfChunkAt&) { return std::string(); }, false, why);
+    return L.add(0, 0, 0, ch) == PLAT_OK && L.inflated <= ((long long)1 << 31) && L.inflateOnHost(out) < 0;
 }
 
 inline void uploadIndexTables(plat_index& I)
@@ -81,18 +74,14 @@ inline int queryIndex(plat_index& I, int n, const int32_t* tid, const int32_t* b
     if (info) memset(info, 0, sizeof *info);
     I.first.assign((size_t)n + 1, 0); I.u.clear(); I.v.clear(); I.count.assign((size_t)n, 0);
     const bool onHost = Switches::read().hostIndex;
-    if (!onHost && !plat_index_query_batch) {
-        c->lastError = "plat_index_query: the device library has no plat_index_query_batch";
-        return PLAT_ERR_UNSUPPORTED;
-    }
+    if (!onHost) { const int rc = needsEntryPoints(c, "plat_index_query", {(const void*)plat_index_query_batch}, "plat_index_query_batch"); if (rc != PLAT_OK) return rc; }
     std::vector<int> handed;
     int deviceCalls = 0;
     if (onHost) { for (int q = 0; q < n; ++q) handed.push_back(q); }
     else if (n > 0) {
         if (!I.uploaded) uploadIndexTables(I);
         Slot& z = *c->slots[0];
-        FetchedDeviceBuffers dev;
-        dev.ctx = z.ctx;
+        FetchedDeviceBuffers dev(z);
         void* st = z.stream;
         plat_index_query_in in = I.dev;
         in.n_queries = n;
@@ -111,11 +100,8 @@ inline int queryIndex(plat_index& I, int n, const int32_t* tid, const int32_t* b
             I.u.resize((size_t)cap); I.v.resize((size_t)cap);
             ck(plat_index_query_batch(z.ctx, &in, &o, st), "plat_index_query_batch");
             ++deviceCalls;
-            ck(plat_memcpy_d2h(z.ctx, status, o.status, sizeof status, st), "plat_memcpy_d2h");
-            ck(plat_memcpy_d2h(z.ctx, I.count.data(), o.count, (size_t)n * sizeof(int32_t), st), "plat_memcpy_d2h");
-            ck(plat_memcpy_d2h(z.ctx, I.first.data(), o.q_first, ((size_t)n + 1) * sizeof(int64_t), st), "plat_memcpy_d2h");
-            ck(plat_memcpy_d2h(z.ctx, I.u.data(), o.out_u, (size_t)cap * sizeof(int64_t), st), "plat_memcpy_d2h");
-            ck(plat_memcpy_d2h(z.ctx, I.v.data(), o.out_v, (size_t)cap * sizeof(int64_t), st), "plat_memcpy_d2h");
+            dev.download(status, o.status, (size_t)idxq::ST_WORDS, st);
+            dev.download(I.count, o.count, st); dev.download(I.first, o.q_first, st); dev.download(I.u, o.out_u, st); dev.download(I.v, o.out_v, st);
             ck(plat_stream_sync(z.ctx, st), "plat_stream_sync");              // the one wait
             if (status[idxq::ST_VERDICT] != PLAT_ERR_OVERFLOW || attempt == 1) break;
             cap = status[idxq::ST_CHUNKS];
@@ -153,13 +139,13 @@ CALLER_EXPORT int plat_index_open(plat_caller* c, const uint8_t* bytes, size_t l
 {
     if (!c || !out || (len > 0 && !bytes) || (kind != PLAT_INDEX_TBI && kind != PLAT_INDEX_BAI)) return PLAT_ERR_INVALID;
     *out = nullptr;
-    try {
+    return guardedEntry(c, "plat_index_open", [&] {
         std::unique_ptr<plat_index> I(new plat_index);
         I->c = c;
         std::vector<uint8_t> raw;
         if (kind == PLAT_INDEX_TBI && !inflateIndexBytes(bytes, (int64_t)len, raw)) {
             c->lastError = "plat_index_open: the .tbi's bytes are no BGZF stream that inflates (bad magic, no BC subfield, an invalid deflate stream or a CRC32 mismatch)";
-            return PLAT_ERR_BAD_INPUT;
+            return (int)PLAT_ERR_BAD_INPUT;
         }
         const int rc = kind == PLAT_INDEX_TBI ? idxq::flatten(raw.data(), raw.size(), idxq::KIND_TBI, I->F) : idxq::flatten(bytes, len, idxq::KIND_BAI, I->F);
         if (rc == PLAT_ERR_UNSUPPORTED) { c->lastError = "plat_index_open: only the VCF preset of tabix and at most " + std::to_string(idxq::MAX_REF) + " references are handled"; return rc; }
@@ -170,10 +156,8 @@ CALLER_EXPORT int plat_index_open(plat_caller* c, const uint8_t* bytes, size_t l
         for (size_t t = 0; t < I->F.names.size(); ++t) I->tidOf.emplace(I->F.names[t], (int)t);
         if (plat_index_query_batch) uploadIndexTables(*I);
         *out = I.release();
-    }
-    catch (const DeviceError& e) { c->lastError = e.what(); return e.code; }
-    catch (const std::exception& e) { c->lastError = std::string("plat_index_open: ") + e.what(); return PLAT_ERR_NOMEM; }
-    return PLAT_OK;
+        return (int)PLAT_OK;
+    });
 }
 
 CALLER_EXPORT int plat_index_close(plat_index* idx) { if (!idx) return PLAT_ERR_INVALID; delete idx; return PLAT_OK; }
@@ -191,10 +175,7 @@ CALLER_EXPORT int plat_index_query(plat_index* idx, int n, const int32_t* tid, c
 {
     if (!idx || n < 0 || (n > 0 && (!tid || !beg || !end)) || !first || !u || !v || !count) return PLAT_ERR_INVALID;
     *first = nullptr; *u = nullptr; *v = nullptr; *count = nullptr;
-    int rc;
-    try { rc = queryIndex(*idx, n, tid, beg, end, info); }
-    catch (const DeviceError& e) { idx->c->lastError = e.what(); return e.code; }
-    catch (const std::exception& e) { idx->c->lastError = std::string("plat_index_query: ") + e.what(); return PLAT_ERR_NOMEM; }
+    const int rc = guardedEntry(idx->c, "plat_index_query", [&] { return queryIndex(*idx, n, tid, beg, end, info); });
     if (rc != PLAT_OK) return rc;
     *first = idx->first.data(); *u = idx->u.data(); *v = idx->v.data(); *count = idx->count.data();
     return PLAT_OK;
@@ -218,8 +199,8 @@ CALLER_EXPORT int plat_caller_set_source_files(plat_caller* c, const plat_source
     if (n_regions == 0) return PLAT_OK;
     // per file: the regions it serves, their queries in one batch, every chunk cut out of the file
     struct Served { int region; std::vector<plat_bgzf_chunk> chunks; const char* name; };
-    std::vector<std::vector<Served>> served((size_t)n_files);
-    try {
+    return guardedEntry(c, "plat_caller_set_source_files", [&] {
+        std::vector<std::vector<Served>> served((size_t)n_files);
         for (int f = 0; f < n_files; ++f) {
             plat_index& I = *files[f].index;
             std::vector<int32_t> tid, beg, end;
@@ -246,7 +227,7 @@ CALLER_EXPORT int plat_caller_set_source_files(plat_caller* c, const plat_source
                     if (!ok) {
                         c->lastError = "plat_caller_set_source_files: chunk " + std::to_string(j - I.first[s]) + " of region " + std::to_string(S[s].region) + ", file " + std::to_string(f) +
                                        " (virtual offsets " + std::to_string(u) + " .. " + std::to_string(v) + ") does not begin and end at BGZF block headers inside the file's data";
-                        return PLAT_ERR_BAD_INPUT;
+                        return (int)PLAT_ERR_BAD_INPUT;
                     }
                     plat_bgzf_chunk ch;
                     memset(&ch, 0, sizeof ch);
@@ -254,23 +235,21 @@ CALLER_EXPORT int plat_caller_set_source_files(plat_caller* c, const plat_source
                     S[s].chunks.push_back(ch);
                 }
         }
-    }
-    catch (const DeviceError& e) { c->lastError = e.what(); return e.code; }
-    catch (const std::exception& e) { c->lastError = std::string("plat_caller_set_source_files: ") + e.what(); return PLAT_ERR_NOMEM; }
-    std::vector<std::vector<plat_tabix_fetch>> fetches((size_t)n_regions);
-    std::vector<size_t> at((size_t)n_files, 0);
-    for (int k = 0; k < n_regions; ++k)
-        for (int f = 0; f < n_files; ++f) {
-            std::vector<Served>& S = served[(size_t)f];
-            if (at[(size_t)f] >= S.size() || S[at[(size_t)f]].region != k) continue;
-            const Served& s = S[at[(size_t)f]++];
-            plat_tabix_fetch ft;
-            memset(&ft, 0, sizeof ft);
-            ft.seq_name = s.name; ft.itr_beg = std::max(regions[k].start, 0); ft.itr_end = regions[k].end;
-            ft.n_chunks = (int32_t)s.chunks.size(); ft.chunks = s.chunks.data();
-            fetches[(size_t)k].push_back(ft);
-        }
-    std::vector<plat_source_blocks> per((size_t)n_regions);
-    for (int k = 0; k < n_regions; ++k) per[(size_t)k] = plat_source_blocks{(int32_t)fetches[(size_t)k].size(), fetches[(size_t)k].data()};
-    return plat_caller_set_source_blocks(c, per.data(), n_regions, longHaps, info);
+        std::vector<std::vector<plat_tabix_fetch>> fetches((size_t)n_regions);
+        std::vector<size_t> at((size_t)n_files, 0);
+        for (int k = 0; k < n_regions; ++k)
+            for (int f = 0; f < n_files; ++f) {
+                std::vector<Served>& S = served[(size_t)f];
+                if (at[(size_t)f] >= S.size() || S[at[(size_t)f]].region != k) continue;
+                const Served& s = S[at[(size_t)f]++];
+                plat_tabix_fetch ft;
+                memset(&ft, 0, sizeof ft);
+                ft.seq_name = s.name; ft.itr_beg = std::max(regions[k].start, 0); ft.itr_end = regions[k].end;
+                ft.n_chunks = (int32_t)s.chunks.size(); ft.chunks = s.chunks.data();
+                fetches[(size_t)k].push_back(ft);
+            }
+        std::vector<plat_source_blocks> per((size_t)n_regions);
+        for (int k = 0; k < n_regions; ++k) per[(size_t)k] = plat_source_blocks{(int32_t)fetches[(size_t)k].size(), fetches[(size_t)k].data()};
+        return plat_caller_set_source_blocks(c, per.data(), n_regions, longHaps, info);
+    });
 }

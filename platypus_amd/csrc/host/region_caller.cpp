@@ -27,7 +27,11 @@
 // kernels and host stages of different chunks overlap.  This file: the feeds, the worker pool, the C entry points, the merge of
 // record texts.  Same text as platypus_amd/caller.py::callVariantsInRegions (tests/test_native_caller_*.py).
 // In front of the loop, for reads that are not split into buffers yet (included at the end of this file):
-//   front_end.hpp          the frame every front end shares: the checks at entry, the bail-out, QC and split on the device, callRegions
+//   front_end.hpp          the frame every front end shares: the checks at entry, the bail-out, QC and split on the device, callRegions;
+//                          and what every entry point behind it shares: the needs check, the one guard, the call's device memory
+//   bgzf_blocks.hpp        the BGZF blocks of one call: the walk over their headers, the inflate on the device and on the host, the refusals
+//                          (after bam_regions.hpp, in front of every header that takes compressed bytes: bgzf_regions.hpp, rg_regions.hpp,
+//                          tabix_source.hpp, index_source.hpp, tbi_out.hpp)
 //   fetched_regions.hpp    reads as a BAM fetch returns them, ASCII or packed        bgzf_regions.hpp   the BGZF blocks of an index lookup
 //   bam_regions.hpp        raw BAM alignment records, decoded on the device          rg_regions.hpp     merged files, split by read group
 // next to it: tabix_source.hpp, source VCFs as the BGZF blocks of their fetches, and index_source.hpp, a .tbi or .bai opened once and queried
@@ -745,6 +749,7 @@ CALLER_EXPORT void plat_caller_debug_set_order(const char* names, char* out, siz
 #include "front_end.hpp"
 #include "fetched_regions.hpp"
 #include "bam_regions.hpp"
+#include "bgzf_blocks.hpp"
 #include "bgzf_regions.hpp"
 #include "rg_regions.hpp"
 #include "tabix_source.hpp"

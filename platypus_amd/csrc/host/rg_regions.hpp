@@ -87,9 +87,9 @@ static void rgRouteLaunch(FrontCall& F, const RgTable& t, const RecordList& L, l
     q.blob = L.blob; q.blob_len = L.bytes; q.rec_off = L.off; q.rec_end = L.limit; q.stream_begin = L.dBegin;
     q.group_ids = t.ids; q.group_off = t.off; q.group_sample = t.sample;
     ck(plat_bam_route_batch(z.ctx, &q, &r.o, z.stream), "plat_bam_route_batch");
-    ck(plat_memcpy_d2h(z.ctx, r.outBegin.data(), r.o.out_begin, r.outBegin.size() * sizeof(int32_t), z.stream), "plat_memcpy_d2h");
-    ck(plat_memcpy_d2h(z.ctx, r.status, r.o.status, sizeof r.status, z.stream), "plat_memcpy_d2h");
-    ck(plat_memcpy_d2h(z.ctx, &r.why, r.o.why, sizeof r.why, z.stream), "plat_memcpy_d2h");
+    dev.download(r.outBegin, r.o.out_begin, z.stream);
+    dev.download(r.status, r.o.status, 4, z.stream);
+    dev.download(&r.why, r.o.why, 1, z.stream);
 }
 
 // a route's status block, read back: 0, or the error with its message (L: the list it routed; stream s = file s % n_files of the
@@ -212,21 +212,21 @@ CALLER_EXPORT int plat_call_bgzf_regions_rg(plat_caller* c, const plat_bgzf_rg_r
                                             (const void*)plat_bam_decode_batch, (const void*)plat_read_buffers_batch}, "plat_bam_route_batch");
     if (rc != PLAT_OK) return rc;
     FetchedStage& S = F.S;
-    BgzfFront W(F, n_files, "file");                                      // (its units are the files)
-    for (int k = 0; k < n_regions; ++k) {
-        const plat_bgzf_rg_region& r = regions[k];
-        if (!r.files) return PLAT_ERR_INVALID;
-        W.addRegion(r.tid, r.itr_beg, r.itr_end);
-        for (int f = 0; f < n_files; ++f) {
-            const plat_bgzf_file& fl = r.files[f];
-            if (fl.n_chunks < 0 || (fl.n_chunks && !fl.chunks) || !rgRecordsValid(F, fl.broken_mates)) return PLAT_ERR_INVALID;
-            if ((rc = W.addUnit(k, f, fl.n_chunks, fl.chunks)) != PLAT_OK) return rc;
-        }
-    }
     return F.guarded([&] {
+        BgzfFront W(F, n_files, "file");                                  // (its units are the files)
+        int rc;
+        for (int k = 0; k < n_regions; ++k) {
+            const plat_bgzf_rg_region& r = regions[k];
+            if (!r.files) return PLAT_ERR_INVALID;
+            W.addRegion(r.tid, r.itr_beg, r.itr_end);
+            for (int f = 0; f < n_files; ++f) {
+                const plat_bgzf_file& fl = r.files[f];
+                if (fl.n_chunks < 0 || (fl.n_chunks && !fl.chunks) || !rgRecordsValid(F, fl.broken_mates)) return PLAT_ERR_INVALID;
+                if ((rc = W.addUnit(k, f, fl.n_chunks, fl.chunks)) != PLAT_OK) return rc;
+            }
+        }
         RgTable table;
-        int rc = rgTableUpload(F, groups, table);
-        if (rc != PLAT_OK) return rc;
+        if ((rc = rgTableUpload(F, groups, table)) != PLAT_OK) return rc;
         // upload, inflate, then find and route (the fetched records where the find leaves them, the broken mates of the same regions): back to back
         W.inflate();
         RgRouted rf, rb;

@@ -1,7 +1,7 @@
-// tbi_out.hpp -- plat_caller_index_bgzf (include/platypus_caller_tbi.h): the tabix index of a whole .vcf.gz.  The host walks the block
-// headers (bgzf_regions.hpp's chain walk; an empty block with data behind it is refused, as tabix_source.hpp refuses it), the file goes
-// up in one copy, plat_bgzf_inflate_batch and plat_tabix_index_batch run back to back on slot 0's stream, one wait for their status
-// blocks, then runs, names and windows come back and tbxindex::finish (csrc/tabix_index.hpp) makes the index of them, deflated by
+// tbi_out.hpp -- plat_caller_index_bgzf (include/platypus_caller_tbi.h): the tabix index of a whole .vcf.gz.  The file is one chunk of a
+// block list (bgzf_blocks.hpp: the walk over the block headers, an empty block with data behind it refused; the file goes up in one
+// copy), plat_bgzf_inflate_batch and plat_tabix_index_batch run back to back on slot 0's stream, one wait for their status blocks, then
+// runs, names and windows come back and tbxindex::finish (csrc/tabix_index.hpp) makes the index of them, deflated by
 // bgzf::deflate_pieces.  PLAT_CALLER_HOST_TBI=1 inflates on the host and runs tbxindex::build_serial instead: the same intermediate.
 // Included at the end of region_caller.cpp, after bgzf_out.hpp.
 #pragma once
@@ -15,52 +15,34 @@ namespace plathost {
 
 struct TbiOut {
     plat_caller* c;
-    const uint8_t* file;
-    int64_t fileLen;
+    plat_bgzf_chunk file;
     const std::string entry = "plat_caller_index_bgzf";
-    std::vector<int64_t> blkOff, blkInflated, blkAddr;                    // the blocks up to the last that holds data; blkAddr has the address behind it too
-    int64_t allBlocks = 0, inflated = 0;
+    BgzfBlockList L;                                                      // the file's blocks up to the last that holds data
+    std::vector<int64_t> blkAddr;                                         // their addresses in the file, and the address behind them
+    int64_t allBlocks = 0;
     tbxindex::Intermediate I;
     std::vector<std::string> names;
     int deviceCalls = 0;
 
-    TbiOut(plat_caller* c_, const uint8_t* file_, size_t len) : c(c_), file(file_), fileLen((int64_t)len) {}
+    TbiOut(plat_caller* c_, const uint8_t* file_, size_t len) : c(c_), L(entry, [](const BgzfChunkAt&) { return std::string(); }, true, c_->lastError) {
+        memset(&file, 0, sizeof file);
+        file.data = file_; file.data_len = (int64_t)len; file.end_coffset = -1;
+    }
 
+    // the chain walked; the empty blocks at the file's end (the EOF block) are no work for the inflate and no address of a line
     int walk() {
-        plat_bgzf_chunk ch;
-        memset(&ch, 0, sizeof ch);
-        ch.data = file; ch.data_len = fileLen; ch.end_coffset = -1;
-        std::vector<int64_t> off, isize;
-        const int64_t broke = walkBgzfChain(ch, [&](int64_t at, const bgzf::BlockHead& h) {
-            off.push_back(at); isize.push_back(h.isize);
-            return off.size() < (size_t)INT_MAX;
-        });
-        if (broke == -2) { c->lastError = entry + ": more blocks than one call takes"; return PLAT_ERR_OVERFLOW; }
-        if (broke >= 0) {
-            c->lastError = entry + ": the file's BGZF blocks do not chain: no valid block header at offset " + std::to_string(broke) +
-                           " (bad magic, no BC subfield, or a block that leaves the file)";
-            return PLAT_ERR_BAD_INPUT;
-        }
-        allBlocks = (int64_t)off.size();
-        size_t nData = off.size();
-        while (nData > 0 && isize[nData - 1] == 0) --nData;
-        for (size_t b = 0; b < nData; ++b) {
-            if (isize[b] == 0) {
-                c->lastError = entry + ": block " + std::to_string(b) + " is empty (ISIZE 0) with data behind it: tabix ends the file there";
-                return PLAT_ERR_BAD_INPUT;
-            }
-            blkOff.push_back(off[b]); blkInflated.push_back(inflated);
-            inflated += isize[b];
-        }
-        blkAddr = blkOff;
-        blkAddr.push_back(nData < off.size() ? off[nData] : fileLen);
+        const int rc = L.add(0, 0, 0, file);
+        if (rc != PLAT_OK) return rc;
+        allBlocks = L.nBlocks();
+        size_t nData = L.blkOff.size();
+        while (nData > 0 && L.inflatedEnd((int)nData - 1) == L.blkInflated[nData - 1]) --nData;
+        blkAddr.assign(L.blkOff.begin(), L.blkOff.begin() + (long)nData);
+        blkAddr.push_back(nData < L.blkOff.size() ? L.blkOff[nData] : file.data_len);
+        L.blkOff.resize(nData); L.blkLimit.resize(nData); L.blkInflated.resize(nData);
+        L.chunkAt[0].blkEnd = (int)nData;
         return PLAT_OK;
     }
 
-    int blockRefused(long long b) {
-        c->lastError = entry + ": block " + std::to_string(b) + " cannot be inflated (a bad header, an invalid deflate stream, output other than ISIZE bytes, or a CRC32 mismatch)";
-        return PLAT_ERR_BAD_INPUT;
-    }
     // what the status block says of a file that is no index's: the message, the code
     int verdict() {
         static const char* const kinds[] = {"", "it has fewer than two columns", "its POS or END lies beyond 32 bits", "its END is negative",
@@ -77,17 +59,11 @@ struct TbiOut {
 
     int onDevice() {
         Slot& z = *c->slots[0];
-        FetchedDeviceBuffers dev;
-        dev.ctx = z.ctx;
+        FetchedDeviceBuffers dev(z);
         void* st = z.stream;
-        const int nBlocks = (int)blkOff.size();
-        uint8_t* dFile = dev.alloc<uint8_t>((size_t)fileLen);
-        if (fileLen) ck(plat_memcpy_h2d(z.ctx, dFile, file, (size_t)fileLen, st), "plat_memcpy_h2d(file)");
-        plat_bgzf_inflate_out io;
-        memset(&io, 0, sizeof io);
-        io.cap_bytes = inflated;
-        io.data = dev.alloc<uint8_t>((size_t)inflated + PLAT_BLOB_PAD); io.out_off = dev.alloc<int64_t>((size_t)nBlocks + 1); io.status = dev.alloc<int64_t>(4);
-        ck(plat_bgzf_inflate_batch(z.ctx, nBlocks, dFile, fileLen, dev.upload(blkOff, st), nullptr, &io, st), "plat_bgzf_inflate_batch");
+        const int nBlocks = L.nBlocks();
+        const int64_t inflated = L.inflated;
+        const plat_bgzf_inflate_out io = L.inflateOnDevice(z, dev, false, "plat_memcpy_h2d(file)");      // (no limits: one chunk, the blob's end is its end)
         plat_tabix_index_in in;
         memset(&in, 0, sizeof in);
         in.n_blocks = nBlocks; in.data = io.data; in.data_len = inflated; in.out_off = io.out_off; in.blk_addr = dev.upload(blkAddr, st);
@@ -106,27 +82,19 @@ struct TbiOut {
             o.lin_first = dev.alloc<int64_t>((size_t)capNames + 1); o.lin = dev.alloc<int64_t>((size_t)capWindows); o.name_bytes = dev.alloc<uint8_t>((size_t)capNameBytes);
             ck(plat_tabix_index_batch(z.ctx, &in, &o, st), "plat_tabix_index_batch");
             ++deviceCalls;
-            if (attempt == 0) ck(plat_memcpy_d2h(z.ctx, inflateStatus, io.status, sizeof inflateStatus, st), "plat_memcpy_d2h");
-            ck(plat_memcpy_d2h(z.ctx, I.status, o.status, sizeof I.status, st), "plat_memcpy_d2h");
+            if (attempt == 0) dev.download(inflateStatus, io.status, 4, st);
+            dev.download(I.status, o.status, (size_t)tbxindex::ST_WORDS, st);
             ck(plat_stream_sync(z.ctx, st), "plat_stream_sync");
-            if (inflateStatus[0] != 0) return blockRefused(inflateStatus[1]);
+            if (inflateStatus[0] != 0) return L.blockRefused(inflateStatus[1], PLAT_ERR_BAD_INPUT);
             if (I.status[tbxindex::ST_VERDICT] != PLAT_ERR_OVERFLOW || attempt == 1) break;
             capRuns = I.status[tbxindex::ST_RUNS]; capWindows = I.status[tbxindex::ST_WINDOWS]; capNameBytes = I.status[tbxindex::ST_NAME_BYTES];
         }
         if (I.status[tbxindex::ST_VERDICT] != 0) return verdict();
         const size_t nRuns = (size_t)I.status[tbxindex::ST_RUNS], nRef = (size_t)I.status[tbxindex::ST_CONTIGS], nWin = (size_t)I.status[tbxindex::ST_WINDOWS];
         I.runTid.resize(nRuns); I.runBin.resize(nRuns); I.runU.resize(nRuns); I.nameOff.resize(nRef); I.nameLen.resize(nRef); I.linFirst.resize(nRef + 1); I.lin.resize(nWin);
-        if (nRuns) {
-            ck(plat_memcpy_d2h(z.ctx, I.runTid.data(), o.run_tid, nRuns * sizeof(int32_t), st), "plat_memcpy_d2h");
-            ck(plat_memcpy_d2h(z.ctx, I.runBin.data(), o.run_bin, nRuns * sizeof(int32_t), st), "plat_memcpy_d2h");
-            ck(plat_memcpy_d2h(z.ctx, I.runU.data(), o.run_u, nRuns * sizeof(int64_t), st), "plat_memcpy_d2h");
-        }
-        if (nRef) {
-            ck(plat_memcpy_d2h(z.ctx, I.nameOff.data(), o.name_off, nRef * sizeof(int64_t), st), "plat_memcpy_d2h");
-            ck(plat_memcpy_d2h(z.ctx, I.nameLen.data(), o.name_len, nRef * sizeof(int32_t), st), "plat_memcpy_d2h");
-        }
-        ck(plat_memcpy_d2h(z.ctx, I.linFirst.data(), o.lin_first, (nRef + 1) * sizeof(int64_t), st), "plat_memcpy_d2h");
-        if (nWin) ck(plat_memcpy_d2h(z.ctx, I.lin.data(), o.lin, nWin * sizeof(int64_t), st), "plat_memcpy_d2h");
+        dev.download(I.runTid, o.run_tid, st); dev.download(I.runBin, o.run_bin, st); dev.download(I.runU, o.run_u, st);
+        dev.download(I.nameOff, o.name_off, st); dev.download(I.nameLen, o.name_len, st);
+        dev.download(I.linFirst, o.lin_first, st); dev.download(I.lin, o.lin, st);
         I.nameBytes.resize((size_t)I.status[tbxindex::ST_NAME_BYTES]);     // the names' bytes: the only text the host sees
         if (!I.nameBytes.empty()) ck(plat_memcpy_d2h(z.ctx, I.nameBytes.data(), o.name_bytes, I.nameBytes.size(), st), "plat_memcpy_d2h(names)");
         ck(plat_stream_sync(z.ctx, st), "plat_stream_sync");
@@ -138,18 +106,12 @@ struct TbiOut {
     }
 
     int onHost() {
-        const int nBlocks = (int)blkOff.size();
-        std::vector<uint8_t> data((size_t)inflated + PLAT_BLOB_PAD, 0);
-        uint32_t crcTable[256];
-        for (uint32_t i = 0; i < 256; ++i) crcTable[i] = bgzf::crc_table_entry(i);
-        std::unique_ptr<bgzf::Tables> tables(new bgzf::Tables);
-        std::vector<int64_t> outOff = blkInflated;
-        outOff.push_back(inflated);
-        for (int b = 0; b < nBlocks; ++b) {
-            const int64_t room = outOff[(size_t)b + 1] - outOff[(size_t)b];
-            if (bgzf::inflate_block(file, fileLen, blkOff[(size_t)b], data.data() + outOff[(size_t)b], room, *tables, crcTable) != room) return blockRefused(b);
-        }
-        tbxindex::build_serial(data.data(), inflated, outOff.data(), blkAddr.data(), nBlocks, I);
+        std::vector<uint8_t> data;
+        const int64_t bad = L.inflateOnHost(data, PLAT_BLOB_PAD);
+        if (bad >= 0) return L.blockRefused(bad, PLAT_ERR_BAD_INPUT);
+        std::vector<int64_t> outOff = L.blkInflated;
+        outOff.push_back(L.inflated);
+        tbxindex::build_serial(data.data(), L.inflated, outOff.data(), blkAddr.data(), L.nBlocks(), I);
         if (I.status[tbxindex::ST_VERDICT] != 0) return verdict();
         names = tbxindex::names_of(I);
         return PLAT_OK;
@@ -165,34 +127,33 @@ CALLER_EXPORT int plat_caller_index_bgzf(plat_caller* c, const uint8_t* file, si
     *tbi = nullptr; *tbi_len = 0;
     if (info) { memset(info, 0, sizeof *info); info->refused_line = -1; }
     const bool onHost = Switches::read().hostTbi;
-    if (!onHost && (!plat_bgzf_inflate_batch || !plat_tabix_index_batch)) {
-        c->lastError = "plat_caller_index_bgzf: the device library has no plat_tabix_index_batch";
-        return PLAT_ERR_UNSUPPORTED;
-    }
-    TbiOut W(c, file, len);
-    int rc = W.walk();
+    const std::string entry = "plat_caller_index_bgzf";
+    int rc = onHost ? PLAT_OK : needsEntryPoints(c, entry, {(const void*)plat_bgzf_inflate_batch, (const void*)plat_tabix_index_batch}, "plat_tabix_index_batch");
     if (rc != PLAT_OK) return rc;
-    try { rc = onHost ? W.onHost() : W.onDevice(); }
-    catch (const DeviceError& e) { c->lastError = e.what(); return e.code; }
-    catch (const std::exception& e) { c->lastError = std::string("plat_caller_index_bgzf: ") + e.what(); return PLAT_ERR_NOMEM; }
-    if (info) {
-        info->n_blocks = W.allBlocks; info->compressed_bytes = (int64_t)len; info->inflated_bytes = W.inflated; info->device_calls = W.deviceCalls;
-        info->refused_line = W.I.status[tbxindex::ST_LINE]; info->seconds = secs(t0, Clock::now());
-    }
-    if (rc != PLAT_OK) return rc;
-    const std::vector<uint8_t> raw = tbxindex::finish(W.I, W.names);
-    std::vector<uint8_t> packed;
-    { bgzf::Deflater d;
-      const int64_t piece[2] = {0, (int64_t)raw.size()};
-      bgzf::deflate_pieces(d, raw.data(), piece, 1, 1, packed, nullptr); }
-    packed.insert(packed.end(), bgzf::EOF_BLOCK, bgzf::EOF_BLOCK + sizeof bgzf::EOF_BLOCK);
-    uint8_t* block = (uint8_t*)malloc(packed.size());
-    if (!block) return PLAT_ERR_NOMEM;
-    memcpy(block, packed.data(), packed.size());
-    *tbi = block; *tbi_len = packed.size();
-    if (info) {
-        info->lines = W.I.status[tbxindex::ST_LINES]; info->records = W.I.status[tbxindex::ST_RECORDS]; info->runs = W.I.status[tbxindex::ST_RUNS];
-        info->contigs = W.I.status[tbxindex::ST_CONTIGS]; info->windows = W.I.status[tbxindex::ST_WINDOWS]; info->seconds = secs(t0, Clock::now());
-    }
-    return PLAT_OK;
+    return guardedEntry(c, entry, [&] {
+        TbiOut W(c, file, len);
+        int rc = W.walk();
+        if (rc != PLAT_OK) return rc;
+        rc = onHost ? W.onHost() : W.onDevice();
+        if (info) {
+            info->n_blocks = W.allBlocks; info->compressed_bytes = (int64_t)len; info->inflated_bytes = W.L.inflated; info->device_calls = W.deviceCalls;
+            info->refused_line = W.I.status[tbxindex::ST_LINE]; info->seconds = secs(t0, Clock::now());
+        }
+        if (rc != PLAT_OK) return rc;
+        const std::vector<uint8_t> raw = tbxindex::finish(W.I, W.names);
+        std::vector<uint8_t> packed;
+        { bgzf::Deflater d;
+          const int64_t piece[2] = {0, (int64_t)raw.size()};
+          bgzf::deflate_pieces(d, raw.data(), piece, 1, 1, packed, nullptr); }
+        packed.insert(packed.end(), bgzf::EOF_BLOCK, bgzf::EOF_BLOCK + sizeof bgzf::EOF_BLOCK);
+        uint8_t* block = (uint8_t*)malloc(packed.size());
+        if (!block) return (int)PLAT_ERR_NOMEM;
+        memcpy(block, packed.data(), packed.size());
+        *tbi = block; *tbi_len = packed.size();
+        if (info) {
+            info->lines = W.I.status[tbxindex::ST_LINES]; info->records = W.I.status[tbxindex::ST_RECORDS]; info->runs = W.I.status[tbxindex::ST_RUNS];
+            info->contigs = W.I.status[tbxindex::ST_CONTIGS]; info->windows = W.I.status[tbxindex::ST_WINDOWS]; info->seconds = secs(t0, Clock::now());
+        }
+        return (int)PLAT_OK;
+    });
 }

@@ -1,5 +1,6 @@
-// The host build of the tabix rule (platypus_amd/csrc/tabix_rule.hpp -- the text the device compiles) over blocks inflated by the host build of
-// csrc/bgzf_inflate.hpp, as a stand-alone program for tests/test_tabix_cpu.py: built with -fsanitize=address,undefined where that links.
+// The host build of the tabix rule (platypus_amd/csrc/tabix_rule.hpp -- the text the device compiles) over blocks walked and inflated by the
+// caller library's own block list (csrc/host/bgzf_blocks.hpp over csrc/bgzf_inflate.hpp), as a stand-alone program for
+// tests/test_tabix_cpu.py: built with -fsanitize=address,undefined where that links.
 //   driver IN OUT
 // IN:  u32 n_cases; per case u32 n_streams; per stream u32 name_len, name, i32 beg, i32 end, u32 n_chunks; per chunk u32 data_len, data,
 //      i32 first_uoffset, i64 end_coffset, i32 end_uoffset
@@ -14,7 +15,8 @@
 #include <string>
 #include <vector>
 
-#include "bgzf_inflate.hpp"
+#define PLAT_BGZF_BLOCKS_HOST_ONLY
+#include "host/bgzf_blocks.hpp"
 #include "tabix_rule.hpp"
 
 static std::vector<uint8_t> readAll(const char* path) {
@@ -44,9 +46,6 @@ int main(int argc, char** argv) {
     In in{raw};
     FILE* out = fopen(argv[2], "wb");
     if (!out) { perror(argv[2]); return 2; }
-    uint32_t crcTable[256];
-    for (uint32_t i = 0; i < 256; ++i) crcTable[i] = bgzf::crc_table_entry(i);
-    std::unique_ptr<bgzf::Tables> tables(new bgzf::Tables);
     const uint32_t nCases = in.take<uint32_t>();
     for (uint32_t k = 0; k < nCases; ++k) {
         std::vector<Stream> streams(in.take<uint32_t>());
@@ -69,37 +68,20 @@ int main(int argc, char** argv) {
         for (size_t si = 0; si < streams.size(); ++si) {
             const Stream& s = streams[si];
             // the chunks' blocks inflated back to back between the guard bands, the chunks' geometry as the caller library derives it
-            int64_t inflated = 0;
-            for (const Chunk& c : s.chunks)
-                for (int64_t at = 0; at < (int64_t)c.data.size();) {
-                    bgzf::BlockHead h;
-                    if (bgzf::parse_header(c.data.data(), (int64_t)c.data.size(), at, &h) != 0) { fprintf(stderr, "case %u: the blocks do not chain\n", k); return 2; }
-                    inflated += h.isize;
-                    at = h.payload + h.payload_len + 8;
-                }
+            std::string error;
+            plathost::BgzfBlockList L("driver", [](const plathost::BgzfChunkAt& a) { return "chunk " + std::to_string(a.chunk); }, false, error);
+            std::vector<plat_bgzf_chunk> chunks;
+            for (const Chunk& c : s.chunks) chunks.push_back(plat_bgzf_chunk{c.data.data(), (int64_t)c.data.size(), c.firstU, c.endC, c.endU});
+            for (size_t q = 0; q < chunks.size(); ++q)
+                if (L.add((int)k, (int)si, (int)q, chunks[q]) != 0) { fprintf(stderr, "case %u: %s\n", k, error.c_str()); return 2; }
+            const int64_t inflated = L.inflated;
             std::unique_ptr<uint8_t[]> buf(new uint8_t[(size_t)inflated + 2 * GUARD]);
             memset(buf.get(), GUARD_BYTE, (size_t)inflated + 2 * GUARD);
             uint8_t* data = buf.get() + GUARD;
-            std::vector<int64_t> first, stop, hi;
-            int64_t done = 0;
-            for (const Chunk& c : s.chunks) {
-                const int64_t lo = done;
-                int64_t e = -1;
-                for (int64_t at = 0; at < (int64_t)c.data.size();) {
-                    bgzf::BlockHead h;
-                    bgzf::parse_header(c.data.data(), (int64_t)c.data.size(), at, &h);
-                    if (at == c.endC) e = done + c.endU;
-                    if (bgzf::inflate_block(c.data.data(), (int64_t)c.data.size(), at, data + done, inflated - done, *tables, crcTable) != (int64_t)h.isize) {
-                        fprintf(stderr, "case %u: a block cannot be inflated\n", k);
-                        return 2;
-                    }
-                    done += h.isize;
-                    at = h.payload + h.payload_len + 8;
-                }
-                if (c.endC < 0 || (c.endC == (int64_t)c.data.size() && c.endU == 0)) e = done;
-                if (e < 0) { fprintf(stderr, "case %u: end_coffset is no block boundary\n", k); return 2; }
-                first.push_back(lo + c.firstU); hi.push_back(done); stop.push_back(e < lo ? lo : e > done ? done : e);
-            }
+            const int64_t bad = L.inflateOnHost(data);
+            if (bad >= 0) { L.blockRefused(bad, -9); fprintf(stderr, "case %u: %s\n", k, error.c_str()); return 2; }
+            std::vector<int64_t> first(chunks.size()), stop(chunks.size()), hi(chunks.size());
+            for (size_t q = 0; q < chunks.size(); ++q) L.span(q, first[q], stop[q], hi[q]);
             int64_t walked = 0, kept = 0;
             const size_t before = text.size();
             const bool ok = tbxrule::walk_stream(data, (int)s.chunks.size(), first.data(), stop.data(), hi.data(), s.name.data(), (int32_t)s.name.size(), s.beg, s.end,

@@ -1,6 +1,6 @@
 // The host twin of the tabix indexer and its finishing stage (platypus_amd/csrc/tabix_index.hpp -- the record's rule is the text the device
-// compiles) over blocks inflated by the host build of csrc/bgzf_inflate.hpp, as a stand-alone program for tests/test_tabix_index_cpu.py:
-// built with -fsanitize=address,undefined where that links.
+// compiles) over blocks walked and inflated by the caller library's own block list (csrc/host/bgzf_blocks.hpp over csrc/bgzf_inflate.hpp,
+// the file as one chunk), as a stand-alone program for tests/test_tabix_index_cpu.py: built with -fsanitize=address,undefined where that links.
 //   driver IN OUT
 // IN:  u32 n_cases; per case i64 len, the bgzipped file's bytes
 // OUT: per case i64 status[13]; i64 n_runs, i32 run_tid[], i32 run_bin[], i64 run_u[]; i64 n_ref, i64 name_off[], i32 name_len[],
@@ -13,7 +13,8 @@
 #include <string>
 #include <vector>
 
-#include "bgzf_inflate.hpp"
+#define PLAT_BGZF_BLOCKS_HOST_ONLY
+#include "host/bgzf_blocks.hpp"
 #include "tabix_index.hpp"
 
 static std::vector<uint8_t> readAll(const char* path) {
@@ -34,9 +35,6 @@ int main(int argc, char** argv) {
     const std::vector<uint8_t> raw = readAll(argv[1]);
     FILE* out = fopen(argv[2], "wb");
     if (!out) { perror(argv[2]); return 2; }
-    uint32_t crcTable[256];
-    for (uint32_t i = 0; i < 256; ++i) crcTable[i] = bgzf::crc_table_entry(i);
-    std::unique_ptr<bgzf::Tables> tables(new bgzf::Tables);
     size_t at = 0;
     auto need = [&](size_t n) { if (at + n > raw.size()) { fprintf(stderr, "short input\n"); exit(2); } };
     need(4);
@@ -48,26 +46,20 @@ int main(int argc, char** argv) {
         need((size_t)len);
         const std::vector<uint8_t> file(raw.begin() + (long)at, raw.begin() + (long)at + (long)len);
         at += (size_t)len;
-        // the chain walk of host/tbi_out.hpp: the blocks up to the last that holds data, the address behind it
-        std::vector<int64_t> off, isize;
-        for (int64_t p = 0; p < len;) {
-            bgzf::BlockHead h;
-            if (bgzf::parse_header(file.data(), len, p, &h) != 0) { fprintf(stderr, "case %u: the blocks do not chain\n", k); return 2; }
-            off.push_back(p); isize.push_back(h.isize);
-            p = h.payload + h.payload_len + 8;
-        }
-        size_t nData = off.size();
-        while (nData > 0 && isize[nData - 1] == 0) --nData;
-        std::vector<int64_t> outOff(1, 0), addr(off.begin(), off.begin() + (long)nData);
-        for (size_t b = 0; b < nData; ++b) outOff.push_back(outOff.back() + isize[b]);
-        addr.push_back(nData < off.size() ? off[nData] : len);
-        const int64_t inflated = outOff.back();
+        // as host/tbi_out.hpp: the file as one chunk, the blocks up to the last that holds data, the address behind it
+        std::string error;
+        plathost::BgzfBlockList L("driver", [](const plathost::BgzfChunkAt&) { return std::string(); }, false, error);
+        plat_bgzf_chunk ch{file.data(), len, 0, -1, 0};
+        if (L.add(0, 0, 0, ch) != 0) { fprintf(stderr, "case %u: %s\n", k, error.c_str()); return 2; }
+        size_t nData = L.blkOff.size();
+        while (nData > 0 && L.inflatedEnd((int)nData - 1) == L.blkInflated[nData - 1]) --nData;
+        std::vector<int64_t> outOff(L.blkInflated.begin(), L.blkInflated.begin() + (long)nData), addr(L.blkOff.begin(), L.blkOff.begin() + (long)nData);
+        outOff.push_back(L.inflated);
+        addr.push_back(nData < L.blkOff.size() ? L.blkOff[nData] : len);
+        const int64_t inflated = L.inflated;
         std::unique_ptr<uint8_t[]> data(new uint8_t[(size_t)inflated ? (size_t)inflated : 1]);
-        for (size_t b = 0; b < nData; ++b)
-            if (bgzf::inflate_block(file.data(), len, off[b], data.get() + outOff[b], isize[b], *tables, crcTable) != isize[b]) {
-                fprintf(stderr, "case %u: a block cannot be inflated\n", k);
-                return 2;
-            }
+        const int64_t bad = L.inflateOnHost(data.get());
+        if (bad >= 0) { L.blockRefused(bad, -9); fprintf(stderr, "case %u: %s\n", k, error.c_str()); return 2; }
         tbxindex::Intermediate I;
         tbxindex::build_serial(data.get(), inflated, outOff.data(), addr.data(), (int)nData, I);
         fwrite(I.status, sizeof(int64_t), tbxindex::ST_WORDS, out);

@@ -227,6 +227,24 @@ def test_a_corrupted_block_is_named_with_its_unit(nc, base):
         _refused(nc, base, way, regions, -9, "block 0 of " + _where(2, unit, 0) + ", chunk 0" + NO_INFLATE)
 
 
+def test_blocks_that_do_not_chain_are_named_with_their_unit(nc, base):
+    """Region 0's first unit in blocks of 200 bytes (three and the EOF block), the high byte of the second block's BSIZE flipped: the block
+    then leaves its chunk's data, and the host's walk names the offset at which it starts."""
+    at1 = []
+
+    def flip(d, fu, ec, eu):
+        d = bytearray(d.tobytes())
+        at1.append(struct.unpack_from("<H", d, 16)[0] + 1)
+        assert struct.unpack_from("<H", d, at1[-1] + 16)[0] < 32768 and len(d) < 32768 and d[at1[-1]:at1[-1] + 4] == b"\x1f\x8b\x08\x04"
+        d[at1[-1] + 17] ^= 0x80
+        return bytes(d), fu, ec, eu
+    for way, unit in (("bgzf", "sample"), ("bgzf_rg", "file")):
+        regions = WAYS[way][1](_lists(), block_payload=200)
+        regions[0] = _edit_first_chunk(way, regions[0], BOUNDS[0], flip)
+        _refused(nc, base, way, regions, -9, "the BGZF blocks of " + _where(0, unit, 0) + ", chunk 0 do not chain: no valid block header at offset %d of its data "
+                 "(bad magic, no BC subfield, or a block that leaves the data)" % at1[-1])
+
+
 def test_an_end_coffset_off_a_block_boundary_is_named_with_its_unit(nc, base):
     # "file" for plat_call_bgzf_regions_rg: the front-end refactor gives BgzfFront its unit word, so the host-side chunk checks of that call
     # say `file F` (they said `sample F` before, for a number that is a file index)
