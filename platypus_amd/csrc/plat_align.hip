@@ -2066,6 +2066,7 @@ static int align_impl(plat_ctx* ctx, const plat_window_batch* batch, const plat_
         // traceback mode: 2*(maxread+8) back-pointer words per job; the job list is processed in slabs of bounded size
         const long long rows = 2ll * (maxread + 8);
         long long slab = (long long)((6ull << 30) / ((unsigned long long)rows * 8ull));
+        if (sw.tbSlab > 0 && sw.tbSlab < slab) slab = sw.tbSlab;                 // (PLAT_TB_SLAB, tests: smaller slabs, never larger ones)
         if (slab > ngrid) slab = ngrid;
         slab = (slab + 255) & ~255ll;
         if ((rc = plat_reserve(ctx, ctx->tb, (size_t)rows * (size_t)slab * 8))) return rc;

@@ -21,6 +21,8 @@
 //   PLAT_SEED_DEBUG        integer, bit 512 only            k_pairs counts why a pair reached the DP; printed with stats      measurements                 per call
 //   PLAT_DP_GRID_PER_CU    integer > 0, else 8              k_dp_jobs: workgroups of the fixed grid per CU                    measurements                 per call (it was
 //                                                                                                                                          once per process before this table)
+//   PLAT_TB_SLAB           integer >= 256, else not given   traceback mode: jobs per slab of back-pointers, rounded up to a    tests                        per call
+//                                                           multiple of 256, where that is less than what 6 GiB hold
 //   AsmSwitches (plat_assemble_batch, plat_assemble_batch_async)
 //   PLAT_ASM_TIMING        set at all                       k_assemble's ticks per phase on stderr (waits for the stream)     measurements                 per call
 //   PLAT_ASM_DEBUG         integer, bits 4, 8 only          4: walks in the slice, 8: one-thread extraction (rare paths)      tests                        per call
@@ -52,6 +54,7 @@ inline int number(const char* name, int unset) { const char* e = getenv(name); r
 struct AlignSwitches {
     bool noUngapped = false, noExact = false, noNlow = false, ungappedBigq = false, seedXcd = true, slowTiming = false, seedOneDiag = false;
     int slowGroup = 8, slowWaves = SLOW_WAVES, seedDebug = 0, dpGridPerCu = 8;
+    long long tbSlab = 0;                                  // 0: not given (the 6 GiB rule holds)
 
     static AlignSwitches read() {
         AlignSwitches w;
@@ -66,6 +69,7 @@ struct AlignSwitches {
         { const int v = env::number("PLAT_SLOW_WAVES", 0); if (v > 0 && v <= SLOW_WAVES) w.slowWaves = v; }
         w.seedDebug = env::number("PLAT_SEED_DEBUG", 0) & 0x200;
         { const int v = env::number("PLAT_DP_GRID_PER_CU", 0); if (v > 0) w.dpGridPerCu = v; }
+        { const int v = env::number("PLAT_TB_SLAB", 0); if (v >= 256) w.tbSlab = ((long long)v + 255) & ~255ll; }
         return w;
     }
 };

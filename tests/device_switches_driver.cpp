@@ -11,18 +11,18 @@ static void show(const char* name, const char* spelling) {
     const plat::AsmSwitches s = plat::AsmSwitches::read();
     const plat::EmSwitches e = plat::EmSwitches::read();
     const plat::SyncSwitches y = plat::SyncSwitches::read();
-    printf("%s %s: noUngapped=%d noExact=%d noNlow=%d ungappedBigq=%d seedXcd=%d slowGroup=%d slowWaves=%d slowTiming=%d seedDebug=%d dpGridPerCu=%d "
+    printf("%s %s: noUngapped=%d noExact=%d noNlow=%d ungappedBigq=%d seedXcd=%d slowGroup=%d slowWaves=%d slowTiming=%d seedDebug=%d dpGridPerCu=%d tbSlab=%lld "
            "asmTiming=%d asmDebug=%d asmWgPerCu=%d asmNoKeep=%d emNarrow=%d syncSpin=%d syncPollNs=%ld\n", name, spelling,
-           a.noUngapped, a.noExact, a.noNlow, a.ungappedBigq, a.seedXcd, a.slowGroup, a.slowWaves, a.slowTiming, a.seedDebug, a.dpGridPerCu,
+           a.noUngapped, a.noExact, a.noNlow, a.ungappedBigq, a.seedXcd, a.slowGroup, a.slowWaves, a.slowTiming, a.seedDebug, a.dpGridPerCu, a.tbSlab,
            s.timing, s.debug, s.wgPerCu, s.noKeep, e.narrow, y.spin, y.pollNs);
 }
 
 int main() {
     const char* names[] = {"PLAT_NO_UNGAPPED", "PLAT_NO_EXACT", "PLAT_NO_NLOW", "PLAT_UNGAPPED_BIGQ", "PLAT_SEED_XCD", "PLAT_SLOW_GROUP", "PLAT_SLOW_WAVES",
-                           "PLAT_SLOW_TIMING", "PLAT_SEED_DEBUG", "PLAT_DP_GRID_PER_CU", "PLAT_ASM_TIMING", "PLAT_ASM_DEBUG",
+                           "PLAT_SLOW_TIMING", "PLAT_SEED_DEBUG", "PLAT_DP_GRID_PER_CU", "PLAT_TB_SLAB", "PLAT_ASM_TIMING", "PLAT_ASM_DEBUG",
                            "PLAT_ASM_WG_PER_CU", "PLAT_ASM_NO_KEEP", "PLAT_EM_NARROW", "PLAT_SYNC_SPIN", "PLAT_SYNC_POLL_US"};
     const char* retired[][2] = {{"PLAT_DP_IMPL", "unpacked"}, {"PLAT_DP_TILES", "1"}, {"PLAT_ASM_STATIC", "1"}, {"PLAT_ASM_FUSED", "0"}};
-    const char* spellings[] = {"", "0", "1", "yes", "7", "-3", "33", "2000000", "512", "256", "768"};
+    const char* spellings[] = {"", "0", "1", "yes", "7", "-3", "33", "2000000", "512", "256", "768", "255", "257"};
     for (const char* n : names) unsetenv(n);
     for (const auto& r : retired) unsetenv(r[0]);
     for (const char* n : names) {

@@ -40,9 +40,10 @@ def run_align(eng, hb, do_flank=0):
     return db, st, db.loglik.cpu().numpy()[:hb.n_pairs], db.score.cpu().numpy()[:hb.n_pairs]
 
 
-def check_against_oracle(oracle, hb, ll, sc, st=None, do_flank=0):
+def check_against_oracle(oracle, hb, ll, sc, st=None, do_flank=0, windows=None):
+    """windows: what oracle_windows(oracle, hb, do_flank=do_flank) gave, where a module computes it once for several runs."""
     ndp = 0
-    for w, (oll, osc, n) in enumerate(oracle_windows(oracle, hb, do_flank=do_flank)):
+    for w, (oll, osc, n) in enumerate(oracle_windows(oracle, hb, do_flank=do_flank) if windows is None else windows):
         a, b = hb.pair_off[w], hb.pair_off[w + 1]
         assert np.array_equal(sc[a:b].reshape(osc.shape), osc), "scores differ in window %d" % w
         # score -> log-likelihood is one fp64 multiply + one add of a host-computed table entry: bit-identical

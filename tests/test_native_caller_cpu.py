@@ -450,33 +450,35 @@ def test_every_switch_parses_as_it_did_at_its_old_site(tmp_path):
 
 
 # The device library's PLAT_* switches (platypus_amd/csrc/switches.hpp), each by the rule its own getenv site applied at commit 223080b (file:line under
-# platypus_amd/csrc/).  Per field: its value with the variable unset and set to "", "0", "1", "yes", "7", "-3", "33", "2000000", "512", "256", "768".
-DEVICE_SPELLINGS = ("unset", "empty", "0", "1", "yes", "7", "-3", "33", "2000000", "512", "256", "768")
-_D_SET_AT_ALL = (0,) + (1,) * 11                                            # getenv(...) != nullptr
-_D_BEGINS_WITH_1 = (0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0)                     # e && e[0] == '1'
-_D_NOT_BEGINNING_0 = (1, 1, 0, 1, 1, 1, 1, 1, 1, 1, 1, 1)                   # !(e && e[0] == '0')
+# platypus_amd/csrc/).  Per field: its value with the variable unset and set to "", "0", "1", "yes", "7", "-3", "33", "2000000", "512", "256", "768", "255", "257".
+DEVICE_SPELLINGS = ("unset", "empty", "0", "1", "yes", "7", "-3", "33", "2000000", "512", "256", "768", "255", "257")
+_D_SET_AT_ALL = (0,) + (1,) * 13                                            # getenv(...) != nullptr
+_D_BEGINS_WITH_1 = (0, 0, 0, 1) + (0,) * 10                                 # e && e[0] == '1'
+_D_NOT_BEGINNING_0 = (1, 1, 0) + (1,) * 11                                  # !(e && e[0] == '0')
 DEVICE_SWITCH_TABLE = {
     "PLAT_NO_UNGAPPED": {"noUngapped": _D_BEGINS_WITH_1},                   # plat_align.hip:1981-1982
     "PLAT_NO_EXACT": {"noExact": _D_BEGINS_WITH_1},                         # plat_align.hip:1983-1984
     "PLAT_NO_NLOW": {"noNlow": _D_BEGINS_WITH_1},                           # plat_align.hip:1986,1989
     "PLAT_UNGAPPED_BIGQ": {"ungappedBigq": _D_BEGINS_WITH_1},               # plat_align.hip:1987,1989
     "PLAT_SEED_XCD": {"seedXcd": _D_NOT_BEGINNING_0},                       # plat_align.hip:1819-1820, 1964-1965
-    "PLAT_SLOW_GROUP": {"slowGroup": (8, 8, 8, 1, 8, 7, 8, 8, 8, 8, 8, 8)},                 # plat_align.hip:1811: atoi in 1..32 (SLOW_GROUP), else 8
-    "PLAT_SLOW_WAVES": {"slowWaves": (4, 4, 4, 1, 4, 4, 4, 4, 4, 4, 4, 4)},                 # plat_align.hip:1813: atoi in 1..4 (SLOW_WAVES), else 4
+    "PLAT_SLOW_GROUP": {"slowGroup": (8, 8, 8, 1, 8, 7, 8, 8, 8, 8, 8, 8, 8, 8)},                 # plat_align.hip:1811: atoi in 1..32 (SLOW_GROUP), else 8
+    "PLAT_SLOW_WAVES": {"slowWaves": (4, 4, 4, 1, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4)},                 # plat_align.hip:1813: atoi in 1..4 (SLOW_WAVES), else 4
     "PLAT_SLOW_TIMING": {"slowTiming": _D_SET_AT_ALL},                      # plat_align.hip:1844-1845
-    "PLAT_SEED_DEBUG": {"seedDebug": (0, 0, 0, 0, 0, 0, 512, 0, 0, 512, 0, 512)},           # plat_align.hip:1985,1990,2083: atoi & 0x300 then, & 0x200 since bit 256
+    "PLAT_SEED_DEBUG": {"seedDebug": (0, 0, 0, 0, 0, 0, 512, 0, 0, 512, 0, 512, 0, 0)},           # plat_align.hip:1985,1990,2083: atoi & 0x300 then, & 0x200 since bit 256
     #                                                                         (the sweeps alone) is retired; -3 = ...11111101 has bit 512, 2000000 = 0x1E8480 has not
-    "PLAT_DP_GRID_PER_CU": {"dpGridPerCu": (8, 8, 8, 1, 8, 7, 8, 33, 2000000, 512, 256, 768)},   # plat_align.hip:2034: atoi > 0, else 8
+    "PLAT_DP_GRID_PER_CU": {"dpGridPerCu": (8, 8, 8, 1, 8, 7, 8, 33, 2000000, 512, 256, 768, 255, 257)},   # plat_align.hip:2034: atoi > 0, else 8
+    "PLAT_TB_SLAB": {"tbSlab": (0, 0, 0, 0, 0, 0, 0, 0, 2000128, 512, 256, 768, 0, 512)},   # atoi >= 256 rounded up to a multiple of 256, else 0 = not
+    #                                                                         given (the 6 GiB rule); the variable came after that commit, with this rule
     "PLAT_ASM_TIMING": {"asmTiming": _D_SET_AT_ALL},                        # plat_assemble.hip:1877
-    "PLAT_ASM_DEBUG": {"asmDebug": (0, 0, 0, 0, 0, 4, 12, 0, 0, 0, 0, 0)},                  # plat_assemble.hip:1879: atoi then, & 12 since bits 1 and 2 (the
+    "PLAT_ASM_DEBUG": {"asmDebug": (0, 0, 0, 0, 0, 4, 12, 0, 0, 0, 0, 0, 12, 0)},                  # plat_assemble.hip:1879: atoi then, & 12 since bits 1 and 2 (the
     #                                                                         reads pass without events / probes) are retired; 7 -> 4, -3 = ...11111101 -> 12, 2000000 = 0x1E8480 -> 0
-    "PLAT_ASM_WG_PER_CU": {"asmWgPerCu": (0, 0, 0, 1, 0, 7, 0, 33, 2000000, 512, 256, 768)},     # plat_assemble.hip:1885: atoi > 0 overrides; 0 = not given
+    "PLAT_ASM_WG_PER_CU": {"asmWgPerCu": (0, 0, 0, 1, 0, 7, 0, 33, 2000000, 512, 256, 768, 255, 257)},     # plat_assemble.hip:1885: atoi > 0 overrides; 0 = not given
     "PLAT_ASM_NO_KEEP": {"asmNoKeep": _D_SET_AT_ALL},                       # plat_assemble.hip:1897
     "PLAT_EM_NARROW": {"emNarrow": _D_SET_AT_ALL},                          # plat_population.hip:549
     "PLAT_SYNC_SPIN": {"syncSpin": _D_BEGINS_WITH_1},                       # plat_ctx.hip:242
-    "PLAT_SYNC_POLL_US": {"syncPollNs": (-1, 0, 0, 1000, 0, 7000, -1, 33000, 2000000000, 512000, 256000, 768000)},   # plat_ctx.hip:243: atol; negative or unset = not
+    "PLAT_SYNC_POLL_US": {"syncPollNs": (-1, 0, 0, 1000, 0, 7000, -1, 33000, 2000000000, 512000, 256000, 768000, 255000, 257000)},   # plat_ctx.hip:243: atol; negative or unset = not
 }                                                                           #                                                  given (-1), else x 1000 ns
-DEVICE_SWITCH_DEFAULTS = dict(noUngapped=0, noExact=0, noNlow=0, ungappedBigq=0, seedXcd=1, slowGroup=8, slowWaves=4, slowTiming=0, seedDebug=0, dpGridPerCu=8,
+DEVICE_SWITCH_DEFAULTS = dict(noUngapped=0, noExact=0, noNlow=0, ungappedBigq=0, seedXcd=1, slowGroup=8, slowWaves=4, slowTiming=0, seedDebug=0, dpGridPerCu=8, tbSlab=0,
                               asmTiming=0, asmDebug=0, asmWgPerCu=0, asmNoKeep=0, emNarrow=0, syncSpin=0, syncPollNs=-1)
 
 
@@ -507,7 +509,7 @@ def test_every_device_switch_parses_as_it_did_at_its_old_site(tmp_path):
     for name, rules in DEVICE_SWITCH_TABLE.items():
         for k, spelling in enumerate(DEVICE_SPELLINGS):
             want[(name, spelling)] = dict(DEVICE_SWITCH_DEFAULTS, **{field: rule[k] for field, rule in rules.items()})
-    assert len(DEVICE_SWITCH_TABLE) == 17 and len(want) == 17 * 12 + 1
+    assert len(DEVICE_SWITCH_TABLE) == 18 and len(want) == 18 * 14 + 1
     assert set(f for r in DEVICE_SWITCH_TABLE.values() for f in r) == set(DEVICE_SWITCH_DEFAULTS)
     assert all(len(rule) == len(DEVICE_SPELLINGS) for r in DEVICE_SWITCH_TABLE.values() for rule in r.values())
     assert got == want
