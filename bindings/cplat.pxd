@@ -535,6 +535,37 @@ cdef extern from "platypus_mi355x.h":
         int64_t* out_v
         int64_t* status
     int plat_index_query_batch(plat_ctx* ctx, const plat_index_query_in* inp, const plat_index_query_out* out, void* stream) nogil
+    # indexed sequence fetch from the bytes of a FASTA file (FastaFile.getSequence, fastafile.pyx:173-207, on the device)
+    int PLAT_FASTA_STATUS_WORDS
+    int PLAT_FASTA_OK
+    int PLAT_FASTA_INDEX_ERROR
+    int PLAT_FASTA_ZERO_LINE
+    int PLAT_FASTA_BAD_INDEX
+    int PLAT_FASTA_LEFT_OF_CUT
+    int PLAT_FASTA_RIGHT_OF_CUT
+    int PLAT_FASTA_MODE_SEQUENCE
+    int PLAT_FASTA_MODE_CONTIG
+    ctypedef struct plat_fasta_fetch_in:
+        const uint8_t* file
+        int64_t file_len
+        int64_t file_base
+        int64_t file_size
+        int64_t n_queries
+        const int64_t* start_pos
+        const int64_t* line_len
+        const int64_t* full_len
+        const int64_t* seq_len
+        const int64_t* beg
+        const int64_t* end
+        const uint8_t* mode
+    ctypedef struct plat_fasta_fetch_out:
+        int64_t cap_bytes
+        int64_t* out_off
+        int32_t* out_status
+        uint8_t* out
+        int64_t* totals
+    int plat_fasta_fetch_batch(plat_ctx* ctx, const plat_fasta_fetch_in* inp, const plat_fasta_fetch_out* out, void* stream) nogil
+    int plat_fasta_tile_bytes() nogil
     # read counts of reference-call blocks (outputRefCall's loop over countReadsCoveringRegion)
     int PLAT_REFCOV_RAISES
     int PLAT_REFCOV_EMPTY
@@ -886,3 +917,27 @@ cdef extern from "platypus_caller_index.h":
     int plat_caller_set_source_files(plat_caller* c, const plat_source_file* files, int n_files, const plat_source_region* regions, int n_regions,
                                      int longHaps, plat_source_blocks_info* info) nogil
     int plat_caller_source_lines(const plat_caller* c, int region, const char** text, int64_t* len) nogil
+
+
+cdef extern from "platypus_caller_fasta.h":
+    ctypedef struct plat_fasta:
+        pass
+    int plat_fasta_open(plat_caller* c, const uint8_t* file_bytes, int64_t file_len, const uint8_t* fai_bytes, int64_t fai_len, int parseNCBI,
+                        plat_fasta** out) nogil
+    int plat_fasta_close(plat_fasta* ref) nogil
+    int plat_fasta_n_refs(const plat_fasta* ref) nogil
+    int plat_fasta_ref(const plat_fasta* ref, int i, const char** name, int64_t* seq_len) nogil
+    int plat_fasta_ref_line(const plat_fasta* ref, int i, int64_t* start_pos, int64_t* line_len, int64_t* full_line_len) nogil
+    int plat_fasta_tid(const plat_fasta* ref, const char* name) nogil
+    int64_t plat_fasta_total_length(const plat_fasta* ref) nogil
+    ctypedef struct plat_fasta_info:
+        int64_t queries
+        int64_t file_bytes
+        int64_t out_bytes
+        int64_t device_calls
+        double seconds
+    int plat_fasta_load(plat_fasta* ref, const int32_t* tids, int n, plat_fasta_info* info) nogil
+    int plat_fasta_contig(plat_fasta* ref, int tid, const uint8_t** host_seq, const uint8_t** dev_seq, int64_t* len) nogil
+    int plat_fasta_get_sequences(plat_fasta* ref, int n, const int32_t* tid, const int64_t* beg, const int64_t* end, const int64_t** first,
+                                 const uint8_t** bytes, const int32_t** status, plat_fasta_info* info) nogil
+    int plat_fasta_get_character(const plat_fasta* ref, int tid, int64_t pos, uint8_t* out, int32_t* n_out) nogil

@@ -1090,6 +1090,69 @@ typedef struct plat_index_query_out {
 
 int plat_index_query_batch(plat_ctx* ctx, const plat_index_query_in* in, const plat_index_query_out* out, void* stream);
 
+/* ---- indexed sequence fetch from the bytes of a FASTA file -------------------------------------------------------------
+ * Replaces  FastaFile.getSequence  (src/cython/fastafile.pyx:173-207; setCacheSequence :141-171 is the same arithmetic) for n_queries
+ * queries against the bytes of ONE file in one call, and adds the whole-contig fetch the region loop needs (plat_region.contig_seq holds
+ * all SeqLength bases; getSequence never returns the last one).  A query brings the four numbers of its contig's .fai line (StartPos,
+ * LineLength, FullLineLength, SeqLength as FastaIndex.getRefs reads them, :64-82), beg, end and a mode.  csrc/fasta_rule.hpp is the
+ * rule as code, for the device and for the host twin.
+ *
+ * The file: `file` [file_len], 16-byte aligned, is a CUT of the real file -- its bytes file_base .. file_base + file_len; file_size is
+ * the real file's length.  An integrator uploads only the contigs it wants.  No byte outside [file, file + file_len) is read.
+ *
+ * The rule, per query:
+ *   offset(p)  StartPos + p + (FullLineLength - LineLength) * (long long)((double)p / LineLength): the quotient in fp64, truncated
+ *   mode 0     b = max(0, beg), e = min(SeqLength - 1, end); e < b is PLAT_FASTA_INDEX_ERROR (the reference's IndexError); the span is
+ *              the file's bytes [offset(b), offset(e)) -- b == e is an empty answer, status 0
+ *   mode 1     the whole contig: [offset(0), offset(SeqLength - 1) + 1); beg and end are not read; SeqLength <= 0 is an empty answer
+ *   the end    both ends of the span are cut at file_size (a read at or past the end of a file returns what is there)
+ *   bytes      every 0x0A of the span is dropped, a-z become A-Z, every other byte -- '\r', NUL, bytes >= 0x80 -- is kept.  The
+ *              reference never looks at what it seeks over: an index that lies (a ragged line) returns whatever lies there, header
+ *              bytes included, and so does this call
+ *   other ends LineLength == 0, which the reference divides by: PLAT_FASTA_ZERO_LINE.  StartPos < 0, LineLength < 0,
+ *              FullLineLength < LineLength or offsets that leave 63 bits (the reference would seek to a negative offset or read a
+ *              negative count): PLAT_FASTA_BAD_INDEX -- a stated limit, not parity.  A non-empty span that begins in front of the cut:
+ *              PLAT_FASTA_LEFT_OF_CUT; one that ends behind it: PLAT_FASTA_RIGHT_OF_CUT.  Such a query has no bytes
+ *
+ * Output (device): out_status [n_queries] (PLAT_FASTA_*), out_off [n_queries + 1] from 0 (an exclusive scan taken on the device),
+ * out [cap_bytes]: query q's bytes at out_off[q] .. out_off[q + 1]; totals [PLAT_FASTA_STATUS_WORDS]: {0 or PLAT_ERR_OVERFLOW, the bytes
+ * of all answers, the tiles walked, the queries whose status is not 0}.  More bytes than cap_bytes is PLAT_ERR_OVERFLOW in totals[0]:
+ * out_off, out_status and the totals hold the full counts, no byte is written, and the caller calls again with totals[1] bytes of room.
+ *
+ * The work is cut by tiles of the file spans, plat_fasta_tile_bytes() bytes of aligned 16-byte words each, not by queries: tens of
+ * thousands of 200-base contexts and a handful of 250 MB contigs go through the same five launches (csrc/plat_fasta.hip names them:
+ * spans, a scan of the tile counts, a count pass, a scan of the byte counts, a write pass).  Scratch: three words per query and two
+ * per wave of the grid, in the context (one of these calls at a time per context); the call does not wait, reads nothing back and
+ * nothing traps.                                                                                                                  */
+#define PLAT_FASTA_STATUS_WORDS 4
+#define PLAT_FASTA_OK 0
+#define PLAT_FASTA_INDEX_ERROR 1
+#define PLAT_FASTA_ZERO_LINE 2
+#define PLAT_FASTA_BAD_INDEX 3
+#define PLAT_FASTA_LEFT_OF_CUT 4
+#define PLAT_FASTA_RIGHT_OF_CUT 5
+#define PLAT_FASTA_MODE_SEQUENCE 0
+#define PLAT_FASTA_MODE_CONTIG 1
+typedef struct plat_fasta_fetch_in {
+    const uint8_t* file;             /* [file_len] 16-byte aligned */
+    int64_t file_len, file_base, file_size;
+    int64_t n_queries;
+    const int64_t* start_pos; const int64_t* line_len; const int64_t* full_len; const int64_t* seq_len;      /* [n_queries] */
+    const int64_t* beg; const int64_t* end;              /* [n_queries] */
+    const uint8_t* mode;             /* [n_queries] PLAT_FASTA_MODE_* */
+} plat_fasta_fetch_in;
+
+typedef struct plat_fasta_fetch_out {
+    int64_t cap_bytes;
+    int64_t* out_off;                /* [n_queries + 1] */
+    int32_t* out_status;             /* [n_queries] */
+    uint8_t* out;                    /* [cap_bytes] */
+    int64_t* totals;                 /* [PLAT_FASTA_STATUS_WORDS] */
+} plat_fasta_fetch_out;
+
+int plat_fasta_fetch_batch(plat_ctx* ctx, const plat_fasta_fetch_in* in, const plat_fasta_fetch_out* out, void* stream);
+int plat_fasta_tile_bytes(void);                            /* the bytes of one tile of a file span */
+
 /* ---- read counts of reference-call blocks ------------------------------------------------------------------------
  * Replaces the loop of  outputRefCall   variantcaller.pyx:774-784  over  ReadArray.countReadsCoveringRegion(p, p + 1)   cwindow.pyx:176-206
  * (one call per position of a block and per sample: the block's QUAL is computed from the smallest count)

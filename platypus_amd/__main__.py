@@ -1,7 +1,8 @@
 """`python -m platypus_amd callVariants ...` -- the reference's entry point name (Platypus.py:23-46).
 
-BAM/CRAM/FASTA I/O (htslib) is outside the hot-path scope of this build; without
-`--synthetic` the command explains that instead of silently doing something else."""
+BAM/CRAM I/O (htslib) is outside the hot-path scope of this build; without
+`--synthetic` the command explains that instead of silently doing something else.  With `--synthetic=config4:N`, `--refFile FILE`
+takes the regions' contigs from FILE and FILE.fai, fetched on the device (include/platypus_caller_fasta.h)."""
 import json
 import sys
 
@@ -83,10 +84,18 @@ def call_variants_config4(opts, n_regions):
     if source_files:
         # the CLI's own stand-in for a tabix fetch: the data lines whose [POS - 1, POS - 1 + len(REF)) overlaps the region, in file order
         reader = H.VariantCandidateReader(source_files, opts)
+    no_contig = "Invalid contig name %s. Make sure your FASTA reference file and query regions have the same naming convention"     # fastafile.pyx:145
     if os.environ.get("PLAT_PYTHON_CALLER") == "1" or opts.assemble or (not opts.getVariantsFromBAMs and not source_files):
         # the Python region loop (platypus_amd.caller): window lists, haplotypes and records as Python objects
         regs = [synth.config4_region(i, region_len=size, n_samples=1, read_len=int(opts.rlen)) for i in mine]
-        fasta = H.FastaFile({r["chrom"]: r["ref"] for r in regs})
+        if opts.refFile:
+            # the contigs come from the file: sequence windows fetched on the device, cached per region as the reference's callers do
+            fasta = H.IndexedFastaFile(opts.refFile, opts.refFile + ".fai", autoCache=1 << 20)
+            for r in regs:
+                if r["chrom"] not in fasta.refs:
+                    sys.exit(no_contig % r["chrom"])
+        else:
+            fasta = H.FastaFile({r["chrom"]: r["ref"] for r in regs})
         work = [(r["chrom"], r["start"], r["end"],
                  [H.bamReadBuffer([H.AlignedRead(x["seq"], x["qual"], x["pos"], x["mapq"], x["flag"], end=x["end"], cigarOps=x["cigar"])
                                    for x in r["samples"][0]], sample="S1")]) for r in regs]
@@ -94,6 +103,8 @@ def call_variants_config4(opts, n_regions):
         names, opts.sourceFile = opts.sourceFile, (source_files or None)      # (the Python loop's reader takes the lines themselves)
         n_windows = caller.callVariantsInRegions(work, fasta, opts, VCF(["S1"]), text) if work else 0
         opts.sourceFile = names
+        if opts.refFile:
+            fasta.close()
     else:
         # the native region loop (libplat_caller.so): reads as arrays, host threads, every device stage batched per chunk
         from . import fastcaller as F
@@ -103,6 +114,20 @@ def call_variants_config4(opts, n_regions):
         import torch
         nc = F.NativeCaller(local % max(1, torch.cuda.device_count()), int(os.environ.get("PLAT_CALLER_WORKERS", "8")),
                             int(os.environ.get("PLAT_CALLER_CHUNK", "4")))
+        ref_file = ref_map = None
+        if opts.refFile:
+            # contig_seq and dev_contig_seq of every region come from the file: mapped, its contigs fetched whole in one device batch
+            import mmap
+            import numpy as np
+            with open(opts.refFile, "rb") as f, open(opts.refFile + ".fai", "rb") as fai:
+                ref_map = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
+                ref_file = nc.open_fasta(np.frombuffer(ref_map, dtype=np.uint8), fai.read(), 1)
+            tids = [ref_file.tid(r["chrom"]) for r in regs]
+            if -1 in tids:
+                sys.exit(no_contig % regs[tids.index(-1)]["chrom"])
+            if tids:
+                ref_file.load(sorted(set(tids)))
+            rr = [F.FastaContigRegion(x, ref_file, t) for x, t in zip(rr, tids)]
         t0 = time.time()
         if source_files and all(os.path.exists(f + ".tbi") for f in opts.sourceFile):
             # every source file has a tabix index next to it: the library takes each file and its index once, answers every region's
@@ -119,6 +144,8 @@ def call_variants_config4(opts, n_regions):
             lines = [b"".join(reader.texts(r["chrom"], r["start"], r["end"])) for r in regs] if reader else None
             text.write(nc.call_regions(rr, ["S1"], opts, source_lines=lines) if rr else "")
         n_windows = nc.stats["n_windows"] if rr else 0
+        if ref_file is not None:
+            ref_file.close()
         nc.close()
     recs = sorted(sharding.records_from_vcf_text(text.getvalue()), key=lambda r: (sharding.chrom_key(r[0]), r[1]))
     device = None

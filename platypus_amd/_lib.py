@@ -186,6 +186,21 @@ class IndexQueryOut(C.Structure):
 
 IDXQ_STATUS_WORDS, IDXQ_MAX_CHUNKS, IDXQ_NO_ITERATOR, IDXQ_HANDED_OVER = 6, 2048, -1, -2
 
+
+class FastaFetchIn(C.Structure):
+    """plat_fasta_fetch_in: a cut of a FASTA file on the device and a call's queries."""
+    _fields_ = [("file", C.c_void_p), ("file_len", C.c_int64), ("file_base", C.c_int64), ("file_size", C.c_int64), ("n_queries", C.c_int64)] + [(k, C.c_void_p) for k in (
+        "start_pos", "line_len", "full_len", "seq_len", "beg", "end", "mode")]
+
+
+class FastaFetchOut(C.Structure):
+    _fields_ = [("cap_bytes", C.c_int64)] + [(k, C.c_void_p) for k in ("out_off", "out_status", "out", "totals")]
+
+
+FASTA_STATUS_WORDS = 4
+FASTA_OK, FASTA_INDEX_ERROR, FASTA_ZERO_LINE, FASTA_BAD_INDEX, FASTA_LEFT_OF_CUT, FASTA_RIGHT_OF_CUT = range(6)
+FASTA_MODE_SEQUENCE, FASTA_MODE_CONTIG = 0, 1
+
 ROUTE_MAX_GROUPS, ROUTE_MAX_SAMPLES, ROUTE_LDS_ID_BYTES = 2048, 256, 24576
 ROUTE_WHY = ("routed", "no RG field", "an RG field that is no string", "an RG value that is not in the table", "an aux field of unknown type",
              "a B array with a negative count", "aux data that runs past the record", "a fixed part that runs past the record")
@@ -323,6 +338,8 @@ SIGNATURES = {
     "plat_tabix_fetch_batch": (C.c_int, [C.c_void_p, C.POINTER(TabixFetchIn), C.POINTER(TabixFetchOut), C.c_void_p]),
     "plat_tabix_index_batch": (C.c_int, [C.c_void_p, C.POINTER(TabixIndexIn), C.POINTER(TabixIndexOut), C.c_void_p]),
     "plat_index_query_batch": (C.c_int, [C.c_void_p, C.POINTER(IndexQueryIn), C.POINTER(IndexQueryOut), C.c_void_p]),
+    "plat_fasta_fetch_batch": (C.c_int, [C.c_void_p, C.POINTER(FastaFetchIn), C.POINTER(FastaFetchOut), C.c_void_p]),
+    "plat_fasta_tile_bytes": (C.c_int, []),
     "plat_refcall_coverage_batch": (C.c_int, [C.c_void_p, C.POINTER(RefCovIn), C.POINTER(RefCovOut), C.c_void_p]),
     "plat_refcov_lds_reads": (C.c_int, []),
     "plat_variant_read_stats_batch": (C.c_int, [C.c_void_p, C.POINTER(InfoStatsBatch), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
@@ -340,7 +357,7 @@ SIGNATURES = {
 # unbound there; load() still requires every declared symbol of the real library
 ADDED_LATER = ("plat_read_buffers_batch", "plat_read_buffers_packed_batch", "plat_bam_decode_batch", "plat_bgzf_inflate_batch", "plat_bam_find_records",
                "plat_bam_route_batch", "plat_source_variants_batch", "plat_tabix_fetch_batch", "plat_refcall_coverage_batch", "plat_refcov_lds_reads",
-               "plat_bgzf_deflate_batch", "plat_tabix_index_batch", "plat_index_query_batch",
+               "plat_bgzf_deflate_batch", "plat_tabix_index_batch", "plat_index_query_batch", "plat_fasta_fetch_batch", "plat_fasta_tile_bytes",
                "plat_concat_read_tables_src", "plat_pack_codes_pieces", "plat_candidates_batch_packed", "plat_gather_reads_packed",
                "plat_variant_read_stats_packed_batch")
 

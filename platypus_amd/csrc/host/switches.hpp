@@ -27,6 +27,8 @@
 //                                                                                                                         read when that entry point is called
 //   HOST_INDEX                   begins with '1'    plat_index_query and plat_caller_set_source_files answer every index query with the host twin (csrc/index_query.hpp)   tests, measurements (the kernels' A/B);
 //                                                                                                                         read when those entry points are called
+//   HOST_FASTA                   begins with '1'    plat_fasta_load, plat_fasta_contig and plat_fasta_get_sequences answer with the host twin (csrc/fasta_rule.hpp)   tests, measurements (the kernels' A/B);
+//                                                                                                                         read when those entry points are called
 //   TRACE                        set at all         per-chunk / per-call lines on stderr;                                 measurements
 //                                begins with '1'    ... and the per-stage seconds of every call (traceStages)
 // PLAT_CALLER_POLL_US is not here: it is a property of the caller object and is read where that is made (plat_caller_create).
@@ -38,7 +40,7 @@ namespace plathost {
 
 struct Switches {
     bool noCodes = false, expand = false, hostTally = false, hostB = false, noDeviceReplay = false, hostInfo = false, firstOccurrenceOrder = false;
-    bool evenTail = true, keepSpare = false, checkHints = false, noRefCtx = false, noRefPrefetch = false, hostSource = false, hostRefcov = false, hostTabix = false, hostDeflate = false, hostTbi = false, hostIndex = false;
+    bool evenTail = true, keepSpare = false, checkHints = false, noRefCtx = false, noRefPrefetch = false, hostSource = false, hostRefcov = false, hostTabix = false, hostDeflate = false, hostTbi = false, hostIndex = false, hostFasta = false;
     bool trace = false, traceStages = false;                              // PLAT_CALLER_TRACE: set at all / begins with '1'
 
     static Switches read() {
@@ -63,6 +65,7 @@ struct Switches {
         w.hostDeflate = isOne("PLAT_CALLER_HOST_DEFLATE");
         w.hostTbi = isOne("PLAT_CALLER_HOST_TBI");
         w.hostIndex = isOne("PLAT_CALLER_HOST_INDEX");
+        w.hostFasta = isOne("PLAT_CALLER_HOST_FASTA");
         w.trace = isSet("PLAT_CALLER_TRACE");
         w.traceStages = isOne("PLAT_CALLER_TRACE");
         return w;

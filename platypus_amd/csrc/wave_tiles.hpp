@@ -1,5 +1,5 @@
 // wave_tiles.hpp -- device-only pieces the front ends share: the wave and workgroup scans, and for the line front ends (plat_sourcevcf.hip,
-// plat_tabix.hip) the tile geometry, a word's newline mask, the rank of a byte among a tile table's marks and the hand-out of a tile's
+// plat_tabix.hip; plat_fasta.hip takes the geometry, the scans and the masks of a loaded word) the tile geometry, a word's newline mask, the rank of a byte among a tile table's marks and the hand-out of a tile's
 // marked bytes to the lanes of a wave.  A byte stream is cut into tiles of TILE_BYTES = 64 aligned 16-byte words, one word per lane of a
 // wave; a table of marks holds 16 bits per word, and next to it goes a table of the tiles' running mark counts ([tiles + 1]).
 #pragma once
@@ -65,6 +65,27 @@ __device__ __forceinline__ unsigned word_newlines(const uint8_t* text, long long
             if (((v[j >> 2] >> (8 * (j & 3))) & 0xffu) == '\n' && at + j >= lo && at + j < hi) nl |= 1u << j;
     }
     return nl;
+}
+
+// ... of a word the caller has loaded (plat_fasta.hip loads a file's last word byte by byte): the '\n' among its sixteen bytes, one bit per byte
+__device__ __forceinline__ unsigned loaded_word_newlines(const uint4& w)
+{
+    const unsigned v[4] = {w.x, w.y, w.z, w.w};
+    unsigned nl = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const unsigned x = v[j] ^ 0x0a0a0a0au;                              // a zero byte where v has a newline
+        const unsigned zero = ~(((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x | 0x7f7f7f7fu);     // 0x80 in exactly those bytes
+        nl |= (((zero >> 7) & 1u) | ((zero >> 14) & 2u) | ((zero >> 21) & 4u) | ((zero >> 28) & 8u)) << (4 * j);
+    }
+    return nl;
+}
+
+// the bytes of the word at `at` that lie in [lo, hi), one bit per byte
+__device__ __forceinline__ unsigned word_inside(long long at, long long lo, long long hi)
+{
+    const long long a = lo > at ? lo - at : 0, b = hi - at < 16 ? hi - at : 16;
+    return a < b ? ((1u << b) - 1u) & ~((1u << a) - 1u) : 0u;
 }
 
 // the bytes of a lane's word that lie behind a newline (nl: word_newlines of the wave's 64 words): the carry from the word before comes

@@ -1120,6 +1120,39 @@ class Engine:
         return dict(chunks=chunks, count=count[:n_q].tolist(), gathered=gath[:n_q].tolist(), first=first[:n_q + 1].tolist() if verdict in (0, -8) else [],
                     status=st[:_lib.IDXQ_STATUS_WORDS].tolist(), guard_intact=intact)
 
+    def fasta_fetch(self, cut, queries, file_base=0, file_size=None, cap_bytes=None, guard=64):
+        """plat_fasta_fetch_batch: FastaFile.getSequence (fastafile.pyx:173-207) and the whole-contig fetch for queries [(StartPos, LineLength,
+        FullLineLength, SeqLength, beg, end, mode)] over `cut`, the bytes file_base .. file_base + len(cut) of a file of file_size bytes
+        (default: the cut is the file's end).  Returns a dict: seqs [per query bytes, None when they do not fit cap_bytes -- default: the
+        cut's length], status [n], off [n + 1], totals [4] and guard_intact: no byte in front of the blob, behind the bytes the totals name
+        or behind an array's end was written."""
+        torch = _torch()
+        n = len(queries)
+        cut = np.frombuffer(bytes(cut), dtype=np.uint8)
+        size = file_base + len(cut) if file_size is None else int(file_size)
+        cap = len(cut) if cap_bytes is None else int(cap_bytes)
+        q = np.asarray([[int(x) for x in t] for t in queries], dtype=np.int64).reshape(n, 7)
+        d_file = torch.from_numpy(np.append(cut, np.zeros(16, dtype=np.uint8))).to(self.device)[:len(cut)]        # (torch allocates aligned)
+        d_q = [torch.from_numpy(np.append(q[:, k], np.zeros(1, dtype=np.int64))).to(self.device) for k in range(6)]
+        d_mode = torch.from_numpy(np.append(q[:, 6], np.zeros(1, dtype=np.int64)).astype(np.uint8)).to(self.device)
+        f64, f32 = 0x7EEE7EEE7EEE7EEE, 0x7EEE7EEE
+        d_off = torch.full((n + 1 + 16,), f64, dtype=torch.int64, device=self.device)
+        d_status = torch.full((n + 16,), f32, dtype=torch.int32, device=self.device)
+        d_totals = torch.full((_lib.FASTA_STATUS_WORDS + 16,), f64, dtype=torch.int64, device=self.device)
+        d_out = torch.full((guard + cap + guard,), 0xEE, dtype=torch.uint8, device=self.device)
+        i = _lib.FastaFetchIn(d_file.data_ptr(), len(cut), int(file_base), size, n, *[t.data_ptr() for t in d_q], d_mode.data_ptr())
+        o = _lib.FastaFetchOut(cap, d_off.data_ptr(), d_status.data_ptr(), d_out.data_ptr() + guard, d_totals.data_ptr())
+        _lib.check(self.lib.plat_fasta_fetch_batch(self.ctx, C.byref(i), C.byref(o), self._stream()), "plat_fasta_fetch_batch")
+        self._sync()
+        off, status, totals, out = (t.cpu().numpy() for t in (d_off, d_status, d_totals, d_out))
+        fits = int(totals[0]) == 0
+        used = int(totals[1]) if fits else 0
+        intact = (bool((off[n + 1:] == f64).all()) and bool((status[n:] == f32).all()) and bool((totals[_lib.FASTA_STATUS_WORDS:] == f64).all()) and
+                  bool((out[:guard] == 0xEE).all()) and bool((out[guard + used:] == 0xEE).all()))
+        blob = out[guard:guard + used].tobytes()
+        return dict(seqs=[blob[off[k]:off[k + 1]] if fits else None for k in range(n)], status=status[:n].tolist(), off=off[:n + 1].tolist(),
+                    totals=totals[:_lib.FASTA_STATUS_WORDS].tolist(), guard_intact=intact)
+
     def refcall_coverage(self, read_pos, read_end, slices, intervals, tile_first=None):
         """plat_refcall_coverage_batch: the loop of outputRefCall (variantcaller.pyx:774-784) over ReadArray.countReadsCoveringRegion
         (cwindow.pyx:176-206) on the device.  read_pos / read_end: the read table; slices: [(begin, n, longest)], one sample's good reads each;

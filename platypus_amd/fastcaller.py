@@ -136,6 +136,11 @@ class _SourceRegion(C.Structure):
 INDEX_KINDS = {"tbi": 0, "bai": 1}
 
 
+class FastaInfo(C.Structure):
+    """plat_fasta_info (include/platypus_caller_fasta.h)."""
+    _fields_ = [(k, C.c_int64) for k in ("queries", "file_bytes", "out_bytes", "device_calls")] + [("seconds", C.c_double)]
+
+
 class _FetchedReads(C.Structure):
     _fields_ = [("fetched", _ReadTable), ("broken_mates", _ReadTable), ("chrom_id", C.c_void_p), ("mate_chrom_id", C.c_void_p),
                 ("insert_size", C.c_void_p)]
@@ -649,6 +654,7 @@ def build(verbose=False):
     srcs.append(os.path.join(_lib.CSRC, "bgzf_deflate.hpp"))           # (... and the host twin of the BGZF encoder)
     srcs.append(os.path.join(_lib.CSRC, "tabix_index.hpp"))            # (... and the host twin of the tabix indexer, with its finishing stage)
     srcs.append(os.path.join(_lib.CSRC, "index_query.hpp"))            # (... and the flatten and the host twin of the index query)
+    srcs.append(os.path.join(_lib.CSRC, "fasta_rule.hpp"))             # (... and the rule, the .fai parse and the host twin of the FASTA fetch)
     if os.path.exists(LIB_PATH) and os.path.getmtime(LIB_PATH) >= max([os.path.getmtime(f) for f in srcs] + [os.path.getmtime(_lib.LIB_PATH)]):
         return LIB_PATH
     # (-O3: the region loop is many small functions over small containers; +10 % windows/s over -O2 on the same box.  No -march: the library
@@ -706,6 +712,18 @@ def _bind(lib):
     lib.plat_index_query.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p] + [C.POINTER(C.c_void_p)] * 4 + [C.POINTER(IndexQueryInfo)]
     lib.plat_caller_set_source_files.argtypes = [C.c_void_p, C.POINTER(_SourceFile), C.c_int, C.POINTER(_SourceRegion), C.c_int, C.c_int, C.POINTER(SourceBlocksInfo)]
     lib.plat_caller_source_lines.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+    lib.plat_fasta_open.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]
+    lib.plat_fasta_close.argtypes = [C.c_void_p]
+    lib.plat_fasta_n_refs.argtypes = [C.c_void_p]
+    lib.plat_fasta_ref.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+    lib.plat_fasta_ref_line.argtypes = [C.c_void_p, C.c_int] + [C.POINTER(C.c_int64)] * 3
+    lib.plat_fasta_tid.argtypes = [C.c_void_p, C.c_char_p]
+    lib.plat_fasta_total_length.argtypes = [C.c_void_p]
+    lib.plat_fasta_total_length.restype = C.c_int64
+    lib.plat_fasta_load.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(FastaInfo)]
+    lib.plat_fasta_contig.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+    lib.plat_fasta_get_sequences.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p] + [C.POINTER(C.c_void_p)] * 3 + [C.POINTER(FastaInfo)]
+    lib.plat_fasta_get_character.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_uint8), C.POINTER(C.c_int32)]
     lib.plat_caller_free.argtypes = [C.c_void_p]
     lib.plat_caller_free.restype = None
     lib.plat_caller_last_error.argtypes = [C.c_void_p]
@@ -883,6 +901,101 @@ class NativeIndex:
         return -1 if b"\x00" in name else self.caller.lib.plat_index_tid(self.h, name)
 
 
+class NativeFasta:
+    """plat_fasta (include/platypus_caller_fasta.h): a FASTA file's bytes and its .fai opened on a NativeCaller; close it before the caller.
+    The file's bytes are kept alive by this object."""
+
+    def __init__(self, caller, handle, keep):
+        self.caller, self.h, self._keep = caller, handle, keep
+        self.info = None
+
+    def _check(self, rc, entry):
+        if rc != 0:
+            raise _lib.PlatypusDeviceError(rc, (self.caller.lib.plat_caller_last_error(self.caller.h) or b"").decode(errors="replace"), entry)
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.caller, "h", None):
+            self.caller.lib.plat_fasta_close(self.h)
+        self.h = None
+
+    @property
+    def refs(self):
+        """[(name bytes, SeqLength, StartPos, LineLength, FullLineLength)] in file order."""
+        lib, out = self.caller.lib, []
+        for i in range(lib.plat_fasta_n_refs(self.h)):
+            name, v = C.c_void_p(), [C.c_int64() for _ in range(4)]
+            self._check(lib.plat_fasta_ref(self.h, i, C.byref(name), C.byref(v[0])), "plat_fasta_ref")
+            self._check(lib.plat_fasta_ref_line(self.h, i, C.byref(v[1]), C.byref(v[2]), C.byref(v[3])), "plat_fasta_ref_line")
+            out.append((C.string_at(name),) + tuple(x.value for x in v))
+        return out
+
+    def tid(self, name):
+        """-1 when the index does not hold the name (a name with a NUL byte cannot be one)."""
+        name = name if isinstance(name, bytes) else name.encode()
+        return -1 if b"\x00" in name else self.caller.lib.plat_fasta_tid(self.h, name)
+
+    @property
+    def total_length(self):
+        return self.caller.lib.plat_fasta_total_length(self.h)
+
+    def load(self, tids=()):
+        """plat_fasta_load: the contigs `tids` (none: all) fetched whole in one device batch; self.info describes the call."""
+        t = np.ascontiguousarray(list(tids), dtype=np.int32)
+        inf = FastaInfo()
+        self._check(self.caller.lib.plat_fasta_load(self.h, t.ctypes.data if len(t) else None, len(t), C.byref(inf)), "plat_fasta_load")
+        self.info = {k: getattr(inf, k) for k, _ in inf._fields_}
+
+    def contig_pointers(self, tid):
+        """plat_fasta_contig: (host address, device address or None, length) -- what goes into plat_region.contig_seq / dev_contig_seq / contig_len."""
+        host, dev, n = C.c_void_p(), C.c_void_p(), C.c_int64()
+        self._check(self.caller.lib.plat_fasta_contig(self.h, int(tid), C.byref(host), C.byref(dev), C.byref(n)), "plat_fasta_contig")
+        return host.value, dev.value, n.value
+
+    def contig(self, tid):
+        """(the contig's bases as a uint8 array over the object's own host memory -- no copy, valid until close --, its device address or None)."""
+        host, dev, n = self.contig_pointers(tid)
+        arr = np.ctypeslib.as_array(C.cast(host, C.POINTER(C.c_uint8)), shape=(n,)) if n else np.zeros(0, dtype=np.uint8)
+        return arr, dev
+
+    def get_sequences(self, queries, info=False):
+        """plat_fasta_get_sequences: queries [(tid, beg, end)] in one device batch.  Returns per query the bytes getSequence returns, or the
+        status (an int, _lib.FASTA_*) where it does not return."""
+        n = len(queries)
+        t = np.ascontiguousarray([q[0] for q in queries], dtype=np.int32)
+        b, e = (np.ascontiguousarray([q[k] for q in queries], dtype=np.int64) for k in (1, 2))
+        first, data, status, inf = C.c_void_p(), C.c_void_p(), C.c_void_p(), FastaInfo()
+        self._check(self.caller.lib.plat_fasta_get_sequences(self.h, n, t.ctypes.data, b.ctypes.data, e.ctypes.data, C.byref(first), C.byref(data), C.byref(status),
+                                                             C.byref(inf)), "plat_fasta_get_sequences")
+        fi = np.ctypeslib.as_array(C.cast(first, C.POINTER(C.c_int64)), shape=(n + 1,)).copy()
+        st = np.ctypeslib.as_array(C.cast(status, C.POINTER(C.c_int32)), shape=(n,)).copy() if n else np.zeros(0, dtype=np.int32)
+        blob = C.string_at(data, int(fi[n])) if fi[n] else b""
+        out = [blob[fi[k]:fi[k + 1]] if st[k] == 0 else int(st[k]) for k in range(n)]
+        self.info = {k: getattr(inf, k) for k, _ in inf._fields_}
+        return (out, self.info) if info else out
+
+    def get_character(self, tid, pos):
+        c, n = C.c_uint8(), C.c_int32()
+        self._check(self.caller.lib.plat_fasta_get_character(self.h, int(tid), int(pos), C.byref(c), C.byref(n)), "plat_fasta_get_character")
+        return bytes([c.value]) if n.value else b""
+
+
+class FastaContigRegion:
+    """A region class over another (RegionReads, FetchedRegion, ...) whose contig is a NativeFasta's: contig_seq, dev_contig_seq and
+    contig_len come from plat_fasta_contig."""
+
+    def __init__(self, region, fasta, tid):
+        self.region, self.chrom, self.start, self.end = region, region.chrom, region.start, region.end
+        self.pointers = fasta.contig_pointers(tid)
+        self._fasta = fasta
+
+    def __getattr__(self, name):
+        return getattr(self.region, name)
+
+    def fill(self, a, n_units):
+        self.region.fill(a, n_units)
+        a.contig_seq, a.dev_contig_seq, a.contig_len = self.pointers
+
+
 class NativeCaller:
     """plat_caller: `workers` threads, each with its own plat_ctx and stream on `device`; `regions_per_chunk` regions go through
     the device stages together."""
@@ -964,6 +1077,16 @@ class NativeCaller:
         if rc != 0:
             raise _lib.PlatypusDeviceError(rc, (self.lib.plat_caller_last_error(self.h) or b"").decode(), "plat_index_open")
         return NativeIndex(self, h)
+
+    def open_fasta(self, file_bytes, fai_bytes, parseNCBI=0):
+        """plat_fasta_open: a FASTA file's bytes (bytes, or a uint8 array / mapped file, which is not copied) and its .fai's.  Returns a NativeFasta."""
+        data = _u8(file_bytes)
+        fai = bytes(fai_bytes)
+        h = C.c_void_p()
+        rc = self.lib.plat_fasta_open(self.h, data.ctypes.data if len(data) else None, len(data), fai, len(fai), int(parseNCBI), C.byref(h))
+        if rc != 0:
+            raise _lib.PlatypusDeviceError(rc, (self.lib.plat_caller_last_error(self.h) or b"").decode(errors="replace"), "plat_fasta_open")
+        return NativeFasta(self, h, data)
 
     def query_index(self, index, queries, info=False):
         """plat_index_query: queries [(tid, beg, end)] in one device batch.  Returns per query the chunk list [(u, v)] ti_iter_query returns,

@@ -17,6 +17,7 @@ and launch tiny batches; throughput comes from `Population.setup` (all haplotype
 one launch) and, beyond that, from batching many windows through `Engine.call_windows` directly.
 """
 import bisect
+import os
 from types import SimpleNamespace
 
 import numpy as np
@@ -306,6 +307,98 @@ class FastaFile:
     def getCharacter(self, seqName, pos):                                         # fastafile.pyx:120-132
         s = self._seq[seqName]
         return b"-" if (pos >= len(s) or pos < 0) else s[pos:pos + 1]
+
+
+class IndexedFastaFile:
+    """fastafile.pyx's FastaFile over a FASTA file and its .fai, with the reference's constructor signature: refs (name -> SeqLength,
+    StartPos, LineLength, FullLineLength), getSequence, getCharacter, setCacheSequence, getTotalSequenceLength, close.  The sequence
+    comes from the file's bytes through the device fetch (fastcaller.NativeCaller.open_fasta, include/platypus_caller_fasta.h), so the
+    Python region loop runs on it wherever it takes a FastaFile.  Names are str, as FastaFile's are; the file is mapped, not read.
+
+    caller: a NativeCaller to open the file on (default: one of its own on `device`, closed with the file).  autoCache: a getSequence
+    the cache does not answer first sets the cache to [beginPos - autoCache, endPos + autoCache) -- the reference's callers set it per
+    region -- and is answered from it where the reference's own cache test lets it; 0: never.  Unlike the reference's, the cache test
+    compares the contig's name too (there a cache set for one contig answers for every other)."""
+
+    def __init__(self, fileName, indexName, mode="rb", parseNCBI=True, caller=None, device=0, autoCache=0):
+        import mmap
+        from . import fastcaller as F
+        self._file = open(fileName, "rb")
+        size = os.fstat(self._file.fileno()).st_size
+        self._map = mmap.mmap(self._file.fileno(), 0, access=mmap.ACCESS_READ) if size else None
+        with open(indexName, "rb") as f:
+            fai = f.read()
+        self._own = caller is None
+        self._caller = F.NativeCaller(device, 1, 1) if caller is None else caller
+        try:
+            self._native = self._caller.open_fasta(np.frombuffer(self._map, dtype=np.uint8) if size else b"", fai, 1 if parseNCBI else 0)
+        except Exception:
+            self.close()
+            raise
+        self._tid, self.refs = {}, {}
+        for tid, (name, seqLength, startPos, lineLength, fullLineLength) in enumerate(self._native.refs):
+            name = name.decode("latin-1")
+            self._tid[name] = tid
+            self.refs[name] = SimpleNamespace(SeqName=name, SeqLength=seqLength, StartPos=startPos, LineLength=lineLength, FullLineLength=fullLineLength)
+        self.autoCache = int(autoCache)
+        self.cacheRefName, self.cacheStartPos, self.cacheEndPos, self.cache = None, -1, -1, None
+
+    def close(self):
+        if getattr(self, "_native", None) is not None:
+            self._native.close()
+            self._native = None
+        if getattr(self, "_own", False) and getattr(self, "_caller", None) is not None:
+            self._caller.close()
+        self._caller = None
+        if getattr(self, "_map", None) is not None:
+            try:
+                self._map.close()
+            except BufferError:                                                    # (an array over the map is still alive: it goes with it)
+                pass
+            self._map = None
+        if getattr(self, "_file", None) is not None:
+            self._file.close()
+            self._file = None
+
+    def getTotalSequenceLength(self):                                              # fastafile.pyx:108-118
+        return sum(r.SeqLength for r in self.refs.values())
+
+    def _fetch(self, seqName, beginPos, endPos):
+        got = self._native.get_sequences([(self._tid[seqName], beginPos, endPos)])[0]
+        if isinstance(got, bytes):
+            return got
+        from . import _lib
+        n = self.refs[seqName].SeqLength
+        if got == _lib.FASTA_INDEX_ERROR:
+            raise IndexError("Cannot have beginPos = %s, endPos = %s" % (max(0, beginPos), min(n - 1, endPos)))
+        raise ZeroDivisionError("float division") if got == _lib.FASTA_ZERO_LINE else ValueError("the index line of %s cannot be used (status %d)" % (seqName, got))
+
+    def getCharacter(self, seqName, pos):                                          # fastafile.pyx:120-139
+        r = self.refs[seqName]
+        if pos >= r.SeqLength or pos < 0:
+            return b"-"
+        if r.LineLength == 0:
+            raise ZeroDivisionError("float division")
+        return self._native.get_character(self._tid[seqName], pos)
+
+    def setCacheSequence(self, seqName, beginPos, endPos):                         # fastafile.pyx:141-171
+        if seqName not in self.refs:
+            raise Exception("Invalid contig name %s. Make sure your FASTA reference file and query regions have the same naming convention" % (seqName))
+        n = self.refs[seqName].SeqLength
+        self.cache = self._fetch(seqName, beginPos, endPos)
+        self.cacheRefName, self.cacheStartPos, self.cacheEndPos = seqName, max(0, beginPos), min(n - 1, endPos)
+
+    def _cached(self, seqName, beginPos, endPos):
+        if self.cache is not None and seqName == self.cacheRefName and beginPos >= self.cacheStartPos and endPos < self.cacheEndPos:
+            return self.cache[beginPos - self.cacheStartPos:endPos - self.cacheStartPos]
+        return None
+
+    def getSequence(self, seqName, beginPos, endPos):                              # fastafile.pyx:173-207
+        got = self._cached(seqName, beginPos, endPos)
+        if got is None and self.autoCache > 0 and seqName in self.refs and 0 <= beginPos <= endPos:
+            self.setCacheSequence(seqName, beginPos - self.autoCache, endPos + self.autoCache)
+            got = self._cached(seqName, beginPos, endPos)
+        return got if got is not None else self._fetch(seqName, beginPos, endPos)
 
 
 def _pack_windows(specs):

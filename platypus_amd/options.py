@@ -62,6 +62,14 @@ SOURCE_HELP = ("FILE[,FILE]: VCF file(s) of known alleles to genotype next to (o
                "--longHaps is honoured.")
 
 
+REF_HELP = ("FILE: the reference FASTA; its index is read from FILE.fai.  With --synthetic=config4:N the regions' contigs are taken from FILE instead of from "
+            "the generator: the file is mapped, the index parsed on the host and the sequence fetched on the device by the reference's own line "
+            "arithmetic (include/platypus_caller_fasta.h) -- whole contigs for the native region loop (contig_seq and dev_contig_seq), "
+            "getSequence / getCharacter through hostapi.IndexedFastaFile for the Python loop.  A region whose contig the index lacks ends the run "
+            "with the reference's message.  bgzipped FASTA is not read.  Without --synthetic=config4 the option is parsed and not used; without "
+            "--refFile nothing changes.")
+
+
 def _list(s):
     return s.split(",")
 
@@ -70,7 +78,7 @@ def build_parser():
     p = argparse.ArgumentParser(prog="Platypus.py callVariants", allow_abbrev=False)
     for flag, dest, typ, default in CALL_VARIANTS_OPTIONS:
         p.add_argument(flag, *(["-o"] if flag == "--output" else []), dest=dest,
-                       type=_list if typ == "list" else typ, default=default, **({"help": SOURCE_HELP} if flag == "--source" else {}))
+                       type=_list if typ == "list" else typ, default=default, **({"help": SOURCE_HELP} if flag == "--source" else {"help": REF_HELP} if flag == "--refFile" else {}))
     p.add_argument("--synthetic", dest="synthetic", type=str, default=None,
                    help="(this build) run the hot path on a synthetic BASELINE config instead of BAM input: config1|config2[:N]|config5[:N]")
     p.add_argument("--outputIndex", dest="outputIndex", type=int, default=0,

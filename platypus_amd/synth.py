@@ -356,6 +356,31 @@ def config3(n_regions=2000, seed=3003, ref_len=4500, tile=1500, read_len=250, de
                 read_seq=seq.reshape(-1), read_qual=qual.reshape(-1), read_off=np.arange(nR + 1, dtype=np.int64) * read_len, truth=truth)
 
 
+def config4_contig(index, seed=4004, region_len=100000, flank=1000, arrays=True):
+    """The contig `r<index>` of config4_region_arrays (arrays=True) or config4_region (False) alone: the generators' first draw."""
+    rng = np.random.Generator(np.random.PCG64([seed, index, 7] if arrays else [seed, index]))
+    return bytes(_rand_bases(rng, region_len + 2 * flank))
+
+
+def write_config4_fasta(path, n_regions, region_len, line_len=60, arrays=True, seed=4004, flank=1000):
+    """The contigs r0 .. r<n_regions - 1> of BASELINE config 4 as a FASTA file at `path` with lines of line_len bases, and its index at
+    path + '.fai' (name, SeqLength, StartPos, LineLength, FullLineLength, as `samtools faidx` writes one): what --refFile takes next to
+    --synthetic=config4:N.  arrays: the contigs of config4_region_arrays (the native loop's regions) or of config4_region (the Python
+    loop's); the two generators draw differently.  Returns the contigs' names."""
+    names = []
+    with open(path, "wb") as f, open(path + ".fai", "wb") as fai:
+        at = 0
+        for i in range(n_regions):
+            ref = config4_contig(i, seed, region_len, flank, arrays)
+            head = b">r%d config4 region %d\n" % (i, i)
+            fai.write(b"r%d\t%d\t%d\t%d\t%d\n" % (i, len(ref), at + len(head), line_len, line_len + 1))
+            body = b"".join(ref[k:k + line_len] + b"\n" for k in range(0, len(ref), line_len))
+            f.write(head + body)
+            at += len(head) + len(body)
+            names.append("r%d" % i)
+    return names
+
+
 def config4_region_arrays(index, seed=4004, region_len=100000, n_samples=1, depth=30, read_len=150, snp_rate=1e-3, indel_rate=1e-4,
                           flank=1000, err=1e-3):
     """One region of BASELINE config 4 as ARRAYS (the form a BAM loader leaves reads in, and what the native region loop takes):
