@@ -919,6 +919,65 @@ cdef extern from "platypus_caller_index.h":
     int plat_caller_source_lines(const plat_caller* c, int region, const char** text, int64_t* len) nogil
 
 
+cdef extern from "platypus_caller_bamfile.h":
+    int PLAT_BAM_FILES_PRESPLIT
+    int PLAT_BAM_FILES_MERGED
+    ctypedef struct plat_bamfile:
+        pass
+    int plat_bam_file_open(plat_caller* c, const uint8_t* data, int64_t data_len, const uint8_t* bai, size_t bai_len, const char* file_name,
+                           plat_bamfile** out) nogil
+    int plat_bam_file_close(plat_bamfile* f) nogil
+    int plat_bam_file_n_refs(const plat_bamfile* f) nogil
+    const char* plat_bam_file_ref_name(const plat_bamfile* f, int tid) nogil
+    int64_t plat_bam_file_ref_len(const plat_bamfile* f, int tid) nogil
+    int plat_bam_file_tid(const plat_bamfile* f, const char* name) nogil
+    const char* plat_bam_file_header_text(const plat_bamfile* f, int64_t* len) nogil
+    int plat_bam_file_n_read_groups(const plat_bamfile* f) nogil
+    int plat_bam_file_read_group(const plat_bamfile* f, int i, const char** id, const char** sm) nogil
+    int plat_bam_file_n_samples(const plat_bamfile* f) nogil
+    const char* plat_bam_file_sample(const plat_bamfile* f, int i) nogil
+    int plat_bam_file_header_raised(const plat_bamfile* f, const char** why) nogil
+    int plat_bam_file_n_header_sq(const plat_bamfile* f) nogil
+    int plat_bam_file_header_sq(const plat_bamfile* f, int i, const char** name, int64_t* len) nogil
+    plat_index* plat_bam_file_index(const plat_bamfile* f) nogil
+    ctypedef struct plat_bam_plan:
+        int32_t mode
+        int32_t n_samples
+        const char* const* sample_names
+        const int32_t* sample_file
+        plat_bam_read_groups groups
+    int plat_bam_files_plan(plat_bamfile* const* files, int n_files, plat_bam_plan** plan) nogil
+    void plat_bam_plan_free(plat_bam_plan* plan) nogil
+    ctypedef struct plat_bam_call_region:
+        const char* chrom
+        int32_t start
+        int32_t end
+        const uint8_t* contig_seq
+        int64_t contig_len
+        const uint8_t* dev_contig_seq
+    ctypedef struct plat_bam_fetch:
+        int32_t tid
+        int32_t itr_beg
+        int32_t itr_end
+        int32_t n_chunks
+        const plat_bgzf_chunk* chunks
+    ctypedef struct plat_bam_fetch_plan:
+        int32_t n_regions
+        int32_t n_files
+        const plat_bam_fetch* fetches
+        int64_t queries
+        int64_t handed_over
+        int64_t chunks
+        int64_t device_calls
+        double seconds
+    int plat_bam_files_fetch_plan(plat_bamfile* const* files, int n_files, const plat_bam_call_region* regions, int n_regions,
+                                  plat_bam_fetch_plan** plan) nogil
+    void plat_bam_fetch_plan_free(plat_bam_fetch_plan* plan) nogil
+    int plat_call_bam_files(plat_caller* c, plat_bamfile* const* files, int n_files, const plat_bam_call_region* regions, int n_regions,
+                            plat_caller_options* options, const plat_caller_qc_options* qc, char** out_text, size_t* out_len,
+                            plat_fetched_region_info* info, plat_caller_stats* stats) nogil
+
+
 cdef extern from "platypus_caller_fasta.h":
     ctypedef struct plat_fasta:
         pass

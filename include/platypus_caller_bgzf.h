@@ -29,8 +29,9 @@
  * everything plat_call_bam_regions refuses.  plat_caller_stats.input_bytes counts the compressed bytes of the loaded regions'
  * chunks plus their broken-mate blobs.  A library linked against a device library without plat_bgzf_inflate_batch returns
  * PLAT_ERR_UNSUPPORTED.
- * Not handled: the CSI index, file I/O, the BAM header, CRAM (the choice of chunks from a BAI is plat_index_query's, include/
- * platypus_caller_index.h; cutting them out of the file stays with the integrator).  For merged files, whose records are split by read group on the
+ * Not handled: the CSI index, file I/O, CRAM.  The choice of chunks from a BAI is plat_index_query's (include/platypus_caller_index.h);
+ * the BAM header and the cut of the chunks out of the file are include/platypus_caller_bamfile.h's, whose plat_call_bam_files ends in
+ * this call.  For merged files, whose records are split by read group on the
  * device behind the iterator, see platypus_caller_rg.h.
  */
 #ifndef PLATYPUS_CALLER_BGZF_H

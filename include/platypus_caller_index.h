@@ -35,8 +35,8 @@
  * against a device library without plat_index_query_batch returns PLAT_ERR_UNSUPPORTED from plat_index_query and
  * plat_caller_set_source_files, naming the symbol; PLAT_CALLER_HOST_INDEX=1 answers every query with the host twin instead (tests,
  * measurements; read once per call with the other switches).
- * Not handled: CSI indexes; the generic, SAM and UCSC presets; an entry point that takes whole BAM files (the BAM header, broken-mate
- * fetches and file I/O stay with the integrator: a BAI gets the query only, its chunks go into plat_bgzf_chunk as before).
+ * Not handled: CSI indexes; the generic, SAM and UCSC presets; file I/O.  Whole BAM files -- the header, the samples, a call's queries
+ * against the .bai and the cut of their chunks -- are include/platypus_caller_bamfile.h's.
  */
 #ifndef PLATYPUS_CALLER_INDEX_H
 #define PLATYPUS_CALLER_INDEX_H

@@ -27,7 +27,8 @@
  * a sample index outside 0 .. n_samples - 1, rec_len missing or below 32.  More than PLAT_ROUTE_MAX_GROUPS read groups or
  * PLAT_ROUTE_MAX_SAMPLES samples, or a device library without plat_bam_route_batch: PLAT_ERR_UNSUPPORTED.
  * plat_caller_stats.input_bytes counts the blobs as handed over plus the table's bytes.
- * Not handled: parsing the @RG header lines, the CG-tag convention for CIGARs of more than 65535 operations, CRAM.
+ * Not handled: the CG-tag convention for CIGARs of more than 65535 operations, CRAM.  The table from the files' @RG header lines and
+ * the choice between this call and its pre-split neighbour are include/platypus_caller_bamfile.h's (plat_bam_files_plan).
  */
 #ifndef PLATYPUS_CALLER_RG_H
 #define PLATYPUS_CALLER_RG_H

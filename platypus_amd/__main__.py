@@ -1,8 +1,10 @@
 """`python -m platypus_amd callVariants ...` -- the reference's entry point name (Platypus.py:23-46).
 
-BAM/CRAM I/O (htslib) is outside the hot-path scope of this build; without
-`--synthetic` the command explains that instead of silently doing something else.  With `--synthetic=config4:N`, `--refFile FILE`
-takes the regions' contigs from FILE and FILE.fai, fetched on the device (include/platypus_caller_fasta.h)."""
+With `--bamFiles F[,F]` AND `--refFile R` (and no `--synthetic`) the files themselves are read (call_variants_bam_files,
+include/platypus_caller_bamfile.h): header, samples, regions, the .bai fetch and the records on the device, the contigs from R.  CRAM, the
+rest of htslib's I/O and `--bamFiles` without `--refFile` stay outside this build; there the command explains that
+instead of silently doing something else.  With `--synthetic=config4:N`, `--refFile FILE` takes the regions' contigs from FILE and
+FILE.fai, fetched on the device (include/platypus_caller_fasta.h)."""
 import json
 import sys
 
@@ -15,6 +17,8 @@ def call_variants(argv):
         sys.exit("platypus_amd: --HLATyping=1 (useMapQualCap) is not implemented on the device path")
     if opts.outputIndex and not opts.output.endswith(".gz"):
         sys.exit("platypus_amd: --outputIndex=1 indexes a compressed output: give --output a name that ends in .gz")
+    if opts.synthetic is None and opts.bamFiles and opts.refFile:
+        return call_variants_bam_files(opts)
     if opts.synthetic is None:
         sys.exit("platypus_amd: BAM/FASTA input needs the reference's htslib I/O layer, which is outside this build's "
                  "scope (see DESIGN.md, 'out of scope').  Use --synthetic=config2[:N] or the in-memory API "
@@ -52,6 +56,140 @@ def read_source_lines(path):
         magic = f.read(2)
     with (gzip.open(path, "rb") if magic == b"\x1f\x8b" else open(path, "rb")) as f:
         return [ln.rstrip(b"\r\n") for ln in f if ln.strip() and not ln.startswith(b"#")]
+
+
+def write_output(opts, sample_names, merged, local_rank=0):
+    """The VCF header for `sample_names` and the merged record lines to --output: plain text, or -- for a name that ends in .gz -- BGZF
+    deflated on the device, with its tabix index under --outputIndex=1."""
+    import datetime
+    import io
+    from .vcfrecords import VCF
+    vcf = VCF(list(sample_names))
+    vcf.setheader([("fileDate", datetime.date.today()), ("source", "platypus_amd (records as Platypus_Version_0.8.1.1 writes them)"),
+                   ("platypusOptions", str(dict(sorted((k, v) for k, v in vars(opts).items() if k != "outputIndex" or v))))])         # variantcaller.pyx:51,942
+    if opts.output.endswith(".gz"):
+        # as the reference's filez.Open does for .gz names (variantcaller.pyx:951-956), as BGZF: the header's block(s), the merged
+        # records', the EOF block -- deflated on the device (include/platypus_caller_bgzfout.h)
+        from . import fastcaller as F
+        import torch
+        head = io.StringIO()
+        vcf.writeheader(head)
+        parts = [head.getvalue().encode(), "".join(line + "\n" for line in merged).encode()]
+        zc = F.NativeCaller(local_rank % max(1, torch.cuda.device_count()), 1, 1)
+        try:
+            packed, _ = zc.compress_text(b"".join(parts), [len(p) for p in parts], level=1, eof=True)
+            with open(opts.output, "wb") as f:
+                f.write(packed)
+            if opts.outputIndex:
+                # the index tabix would build of the file, from the bytes just written (include/platypus_caller_tbi.h)
+                with open(opts.output + ".tbi", "wb") as f:
+                    f.write(zc.index_bgzf(packed))
+        finally:
+            zc.close()
+    else:
+        with open(opts.output, "w") as f:
+            vcf.writeheader(f)
+            f.write("".join(line + "\n" for line in merged))
+
+
+def bam_regions(header_sq, fai_refs, asked, buffer_size):
+    """The region list of getRegions (platypusutils.pyx:999-1085) for --regions=None or a list of chr / chr:start-end.  header_sq: the
+    (SN, LN) pairs of the first BAM file's @SQ lines, None where reading them raises (NativeBamFile.header_sq); fai_refs: (name, length)
+    of the FASTA index in file order -- where the reference falls back to ALL of them it walks a dict, whose order is Python 2's; file
+    order is this build's choice there.  Returns [(chrom, start, end)]."""
+    lengths = dict(fai_refs)
+    regions = []
+    if asked is None:
+        regions = [(n, 0, l) for n, l in (header_sq if header_sq is not None else fai_refs)]
+    else:
+        for region in asked:
+            split = region.rsplit(":", 1)
+            chrom = split[0]
+            if len(split) == 2:
+                start, end = split[1].split("-")
+                regions.append((chrom, int(start) - 1, int(end)))
+                if regions[-1][2] - regions[-1][1] > 1e9:
+                    raise ValueError("Invalid input region: %s" % region)
+            elif header_sq is not None and chrom in dict(header_sq):
+                regions.append((chrom, 0, dict(header_sq)[chrom]))
+            else:
+                regions = [(n, 0, l) for n, l in fai_refs if n == chrom]          # (the reference's list starts over here, :1033)
+    final = []
+    for chrom, start, end in regions:
+        if chrom not in lengths or start > lengths[chrom]:
+            continue
+        if end - start > buffer_size:
+            final.extend((chrom, i, min(i + buffer_size, end)) for i in range(start, end, buffer_size))
+        else:
+            final.append((chrom, start, end))
+    return final
+
+
+def call_variants_bam_files(opts):
+    """--bamFiles with --refFile: whole BAM files through the native region loop (include/platypus_caller_bamfile.h).  Every file and its
+    .bai (FILE.bai, else FILE without .bam plus .bai) and the FASTA are mapped; samples and mode are the library's plan, the regions
+    getRegions' (bam_regions), the contigs the FASTA's, fetched on the device; header and merged records go through write_output."""
+    import mmap
+    import os
+    import time
+    import numpy as np
+    import torch
+    from . import fastcaller as F, sharding
+    if opts.regions is not None and os.path.exists(opts.regions[0]):
+        sys.exit("platypus_amd: --regions=%s names a file; region files (.txt / .bed) are not read: give a list of chr or chr:start-end" % opts.regions[0])
+    if opts.skipRegionsFile:
+        sys.exit("platypus_amd: --skipRegionsFile is not read")
+    opts.originalMaxHaplotypes = opts.maxHaplotypes
+    nc = F.NativeCaller(int(os.environ.get("LOCAL_RANK", 0)) % max(1, torch.cuda.device_count()), int(os.environ.get("PLAT_CALLER_WORKERS", "8")),
+                        int(os.environ.get("PLAT_CALLER_CHUNK", "4")))
+    maps, files, ref_file = [], [], None
+
+    def mapped(path):
+        with open(path, "rb") as f:
+            if os.fstat(f.fileno()).st_size == 0:
+                return np.zeros(0, dtype=np.uint8)
+            maps.append(mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ))
+        return np.frombuffer(maps[-1], dtype=np.uint8)
+    try:
+        for name in opts.bamFiles:
+            if not name.lower().endswith(".bam"):
+                sys.exit("platypus_amd: input file %s is not a BAM file (CRAM and text files of file names are not read)" % name)
+            bai = name + ".bai" if os.path.exists(name + ".bai") else name[:-4] + ".bai"
+            with open(bai, "rb") as f:
+                files.append(nc.open_bam(mapped(name), f.read(), name))
+        with open(opts.refFile + ".fai", "rb") as f:
+            ref_file = nc.open_fasta(mapped(opts.refFile), f.read(), int(opts.parseNCBI))
+        plan = nc.bam_plan(files)
+        sq = files[0].header_sq
+        regions = bam_regions(None if sq is None else [(n.decode(), l) for n, l in sq], [(r[0].decode(), r[1]) for r in ref_file.refs], opts.regions,
+                              int(opts.bufferSize))
+        tids = [ref_file.tid(c) for c, _, _ in regions]
+        if tids:
+            ref_file.load(sorted(set(tids)))
+        rr = [F.FastaContigRegion(F.BamFilesRegion(c, s, e, b""), ref_file, t) for (c, s, e), t in zip(regions, tids)]
+        t0 = time.time()
+        source = None
+        if opts.sourceFile:
+            source = []
+            for f in opts.sourceFile:
+                with open(f, "rb") as data, open(f + ".tbi", "rb") as tbi:
+                    source.append((data.read(), nc.open_index(tbi.read(), "tbi")))
+        text = nc.call_bam_files(files, rr, opts, source_files=source) if rr else ""
+        for _, index in source or []:
+            index.close()
+        dt = time.time() - t0
+        n_windows = nc.stats["n_windows"] if rr else 0
+    finally:
+        for f in files:
+            f.close()
+        if ref_file is not None:
+            ref_file.close()
+        nc.close()
+    recs = sorted(sharding.records_from_vcf_text(text), key=lambda r: (sharding.chrom_key(r[0]), r[1]))
+    merged = sharding.merge_record_streams([recs])
+    write_output(opts, [s.decode(errors="surrogateescape") for s in plan["samples"]], merged)
+    print(json.dumps(dict(files=len(opts.bamFiles), mode=plan["mode"], samples=len(plan["samples"]), regions=len(regions), windows=n_windows,
+                          records=len(merged), seconds=round(dt, 3), output=opts.output)))
 
 
 def call_variants_config4(opts, n_regions):
@@ -156,33 +294,7 @@ def call_variants_config4(opts, n_regions):
     dt = time.time() - t0
     if rank == 0:
         merged = sharding.merge_record_streams([sharding.decode_records(p) for p in got])
-        import datetime
-        vcf = VCF(["S1"])
-        vcf.setheader([("fileDate", datetime.date.today()), ("source", "platypus_amd (records as Platypus_Version_0.8.1.1 writes them)"),
-                       ("platypusOptions", str(dict(sorted((k, v) for k, v in vars(opts).items() if k != "outputIndex" or v))))])         # variantcaller.pyx:51,942
-        if opts.output.endswith(".gz"):
-            # as the reference's filez.Open does for .gz names (variantcaller.pyx:951-956), as BGZF: the header's block(s), the merged
-            # records', the EOF block -- deflated on the device (include/platypus_caller_bgzfout.h)
-            from . import fastcaller as F
-            import torch
-            head = io.StringIO()
-            vcf.writeheader(head)
-            parts = [head.getvalue().encode(), "".join(line + "\n" for line in merged).encode()]
-            zc = F.NativeCaller(int(os.environ.get("LOCAL_RANK", rank)) % max(1, torch.cuda.device_count()), 1, 1)
-            try:
-                packed, _ = zc.compress_text(b"".join(parts), [len(p) for p in parts], level=1, eof=True)
-                with open(opts.output, "wb") as f:
-                    f.write(packed)
-                if opts.outputIndex:
-                    # the index tabix would build of the file, from the bytes just written (include/platypus_caller_tbi.h)
-                    with open(opts.output + ".tbi", "wb") as f:
-                        f.write(zc.index_bgzf(packed))
-            finally:
-                zc.close()
-        else:
-            with open(opts.output, "w") as f:
-                vcf.writeheader(f)
-                f.write("".join(line + "\n" for line in merged))
+        write_output(opts, ["S1"], merged, int(os.environ.get("LOCAL_RANK", rank)))
         print(json.dumps(dict(regions=n_regions, region_len=size, ranks=world, windows_rank0=n_windows, records=len(merged),
                               seconds=round(dt, 3), output=opts.output)))
     if dist is not None:

@@ -133,6 +133,23 @@ inline int queryIndex(plat_index& I, int n, const int32_t* tid, const int32_t* b
     return PLAT_OK;
 }
 
+// One chunk [u, v) of an index query cut out of the file's bytes as plat_bgzf_chunk takes it: from the block at u's coffset through the
+// block at v's coffset, that block included when v's uoffset is non-zero, its length read from its own BSIZE.  false: the chunk does not
+// begin and end at block headers inside the data.  (plat_caller_set_source_files for a .tbi, bam_file.hpp for a .bai.)
+inline bool cutIndexChunk(const uint8_t* data, int64_t len, uint64_t u, uint64_t v, plat_bgzf_chunk& ch)
+{
+    const int64_t c0 = (int64_t)(u >> 16), c1 = (int64_t)(v >> 16);
+    int64_t stop = c1;
+    bgzf::BlockHead h;
+    bool ok = c0 <= c1 && c1 <= len;
+    if (ok && (v & 0xffff)) { ok = bgzf::parse_header(data, len, c1, &h) == 0; if (ok) stop = h.payload + h.payload_len + 8; }
+    if (ok && stop > c0) ok = bgzf::parse_header(data, len, c0, &h) == 0;
+    if (!ok) return false;
+    memset(&ch, 0, sizeof ch);
+    ch.data = data + c0; ch.data_len = stop - c0; ch.first_uoffset = (int32_t)(u & 0xffff); ch.end_coffset = c1 - c0; ch.end_uoffset = (int32_t)(v & 0xffff);
+    return true;
+}
+
 }  // namespace plathost
 
 CALLER_EXPORT int plat_index_open(plat_caller* c, const uint8_t* bytes, size_t len, int kind, plat_index** out)
@@ -218,20 +235,12 @@ CALLER_EXPORT int plat_caller_set_source_files(plat_caller* c, const plat_source
             for (size_t s = 0; s < S.size(); ++s)
                 for (int64_t j = I.first[s]; j < I.first[s + 1]; ++j) {
                     const uint64_t u = (uint64_t)I.u[(size_t)j], v = (uint64_t)I.v[(size_t)j];
-                    const int64_t c0 = (int64_t)(u >> 16), c1 = (int64_t)(v >> 16);
-                    int64_t stop = c1;
-                    bgzf::BlockHead h;
-                    bool ok = c0 <= c1 && c1 <= len;
-                    if (ok && (v & 0xffff)) { ok = bgzf::parse_header(data, len, c1, &h) == 0; if (ok) stop = h.payload + h.payload_len + 8; }
-                    if (ok && stop > c0) ok = bgzf::parse_header(data, len, c0, &h) == 0;
-                    if (!ok) {
+                    plat_bgzf_chunk ch;
+                    if (!cutIndexChunk(data, len, u, v, ch)) {
                         c->lastError = "plat_caller_set_source_files: chunk " + std::to_string(j - I.first[s]) + " of region " + std::to_string(S[s].region) + ", file " + std::to_string(f) +
                                        " (virtual offsets " + std::to_string(u) + " .. " + std::to_string(v) + ") does not begin and end at BGZF block headers inside the file's data";
                         return (int)PLAT_ERR_BAD_INPUT;
                     }
-                    plat_bgzf_chunk ch;
-                    memset(&ch, 0, sizeof ch);
-                    ch.data = data + c0; ch.data_len = stop - c0; ch.first_uoffset = (int32_t)(u & 0xffff); ch.end_coffset = c1 - c0; ch.end_uoffset = (int32_t)(v & 0xffff);
                     S[s].chunks.push_back(ch);
                 }
         }

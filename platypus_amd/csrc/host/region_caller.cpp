@@ -35,8 +35,9 @@
 //   fetched_regions.hpp    reads as a BAM fetch returns them, ASCII or packed        bgzf_regions.hpp   the BGZF blocks of an index lookup
 //   bam_regions.hpp        raw BAM alignment records, decoded on the device          rg_regions.hpp     merged files, split by read group
 // next to it: tabix_source.hpp, source VCFs as the BGZF blocks of their fetches, and index_source.hpp, a .tbi or .bai opened once and queried
-// in device batches (plat_index_*, plat_caller_set_source_files), and fasta_source.hpp, the reference FASTA as the file's bytes and its .fai
-// (plat_fasta_*: contigs and sequence windows fetched on the device);
+// in device batches (plat_index_*, plat_caller_set_source_files), bam_file.hpp, whole BAM files: the header, the samples, the .bai fetch of a
+// call's regions, and from there bgzf_regions.hpp or rg_regions.hpp (plat_bam_file_*, plat_call_bam_files), and fasta_source.hpp, the
+// reference FASTA as the file's bytes and its .fai (plat_fasta_*: contigs and sequence windows fetched on the device);
 // and behind it: bgzf_out.hpp, the record text of a call deflated to BGZF blocks (plat_caller_compress_text), and tbi_out.hpp, the tabix
 // index of the file those blocks make (plat_caller_index_bgzf).
 #include <sys/mman.h>
@@ -755,6 +756,7 @@ CALLER_EXPORT void plat_caller_debug_set_order(const char* names, char* out, siz
 #include "rg_regions.hpp"
 #include "tabix_source.hpp"
 #include "index_source.hpp"
+#include "bam_file.hpp"
 #include "fasta_source.hpp"
 #include "bgzf_out.hpp"
 #include "tbi_out.hpp"

@@ -223,6 +223,32 @@ class _BgzfRgRegion(C.Structure):
                 ("dev_contig_seq", C.c_void_p), ("tid", C.c_int32), ("itr_beg", C.c_int32), ("itr_end", C.c_int32), ("files", C.POINTER(_BgzfFile))]
 
 
+class _BamPlan(C.Structure):
+    """plat_bam_plan (include/platypus_caller_bamfile.h)."""
+    _fields_ = [("mode", C.c_int32), ("n_samples", C.c_int32), ("sample_names", C.POINTER(C.c_char_p)), ("sample_file", C.POINTER(C.c_int32)),
+                ("groups", _BamReadGroups)]
+
+
+class _BamCallRegion(C.Structure):
+    """plat_bam_call_region."""
+    _fields_ = [("chrom", C.c_char_p), ("start", C.c_int32), ("end", C.c_int32), ("contig_seq", C.c_void_p), ("contig_len", C.c_int64),
+                ("dev_contig_seq", C.c_void_p)]
+
+
+class _BamFetch(C.Structure):
+    """plat_bam_fetch."""
+    _fields_ = [("tid", C.c_int32), ("itr_beg", C.c_int32), ("itr_end", C.c_int32), ("n_chunks", C.c_int32), ("chunks", C.POINTER(_BgzfChunk))]
+
+
+class _BamFetchPlan(C.Structure):
+    """plat_bam_fetch_plan."""
+    _fields_ = [("n_regions", C.c_int32), ("n_files", C.c_int32), ("fetches", C.POINTER(_BamFetch))] + \
+               [(k, C.c_int64) for k in ("queries", "handed_over", "chunks", "device_calls")] + [("seconds", C.c_double)]
+
+
+BAM_FILES_MODES = ("presplit", "merged")
+
+
 class ReadTable:
     """One ReadArray as arrays (cAlignedRead fields, htslibWrapper.pxd:187-201).  `reads`: the order the ReadArray holds them in
     (sorted by pos; brokenMates by mate position)."""
@@ -724,6 +750,33 @@ def _bind(lib):
     lib.plat_fasta_contig.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
     lib.plat_fasta_get_sequences.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p] + [C.POINTER(C.c_void_p)] * 3 + [C.POINTER(FastaInfo)]
     lib.plat_fasta_get_character.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_uint8), C.POINTER(C.c_int32)]
+    lib.plat_bam_file_open.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_char_p, C.POINTER(C.c_void_p)]
+    for name in ("close", "n_refs", "n_read_groups", "n_samples"):
+        getattr(lib, "plat_bam_file_" + name).argtypes = [C.c_void_p]
+    lib.plat_bam_file_ref_name.argtypes = [C.c_void_p, C.c_int]
+    lib.plat_bam_file_ref_name.restype = C.c_char_p
+    lib.plat_bam_file_ref_len.argtypes = [C.c_void_p, C.c_int]
+    lib.plat_bam_file_ref_len.restype = C.c_int64
+    lib.plat_bam_file_tid.argtypes = [C.c_void_p, C.c_char_p]
+    lib.plat_bam_file_header_text.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+    lib.plat_bam_file_header_text.restype = C.c_void_p
+    lib.plat_bam_file_read_group.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p)]
+    lib.plat_bam_file_sample.argtypes = [C.c_void_p, C.c_int]
+    lib.plat_bam_file_sample.restype = C.c_char_p
+    lib.plat_bam_file_header_raised.argtypes = [C.c_void_p, C.POINTER(C.c_char_p)]
+    lib.plat_bam_file_n_header_sq.argtypes = [C.c_void_p]
+    lib.plat_bam_file_header_sq.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64)]
+    lib.plat_bam_file_index.argtypes = [C.c_void_p]
+    lib.plat_bam_file_index.restype = C.c_void_p
+    lib.plat_bam_files_plan.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.POINTER(_BamPlan))]
+    lib.plat_bam_plan_free.argtypes = [C.POINTER(_BamPlan)]
+    lib.plat_bam_plan_free.restype = None
+    lib.plat_bam_files_fetch_plan.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(_BamCallRegion), C.c_int, C.POINTER(C.POINTER(_BamFetchPlan))]
+    lib.plat_bam_fetch_plan_free.argtypes = [C.POINTER(_BamFetchPlan)]
+    lib.plat_bam_fetch_plan_free.restype = None
+    lib.plat_call_bam_files.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.POINTER(_BamCallRegion), C.c_int, C.POINTER(CallerOptions),
+                                        C.POINTER(CallerQCOptions), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(_FetchedRegionInfo),
+                                        C.POINTER(CallerStats)]
     lib.plat_caller_free.argtypes = [C.c_void_p]
     lib.plat_caller_free.restype = None
     lib.plat_caller_last_error.argtypes = [C.c_void_p]
@@ -996,6 +1049,91 @@ class FastaContigRegion:
         a.contig_seq, a.dev_contig_seq, a.contig_len = self.pointers
 
 
+class NativeBamFile:
+    """plat_bamfile (include/platypus_caller_bamfile.h): a BAM file's bytes and its .bai opened on a NativeCaller; close it before the
+    caller.  The file's bytes are kept alive by this object."""
+
+    def __init__(self, caller, handle, keep, file_name):
+        self.caller, self.h, self._keep, self.file_name = caller, handle, keep, file_name
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.caller, "h", None):
+            self.caller.lib.plat_bam_file_close(self.h)
+        self.h = None
+
+    @property
+    def data(self):
+        return self._keep
+
+    @property
+    def refs(self):
+        """The reference names (bytes) in header order."""
+        lib = self.caller.lib
+        return [lib.plat_bam_file_ref_name(self.h, t) for t in range(lib.plat_bam_file_n_refs(self.h))]
+
+    @property
+    def lengths(self):
+        lib = self.caller.lib
+        return [lib.plat_bam_file_ref_len(self.h, t) for t in range(lib.plat_bam_file_n_refs(self.h))]
+
+    def tid(self, name):
+        """-1 when the header does not hold the name (a name with a NUL byte cannot be one)."""
+        name = name if isinstance(name, bytes) else name.encode()
+        return -1 if b"\x00" in name else self.caller.lib.plat_bam_file_tid(self.h, name)
+
+    @property
+    def header_text(self):
+        n = C.c_int64()
+        p = self.caller.lib.plat_bam_file_header_text(self.h, C.byref(n))
+        return C.string_at(p, n.value) if n.value else b""
+
+    @property
+    def read_groups(self):
+        """[(ID, SM)] (bytes) in header order: what this file enters into the call's read-group table."""
+        lib, out = self.caller.lib, []
+        for i in range(lib.plat_bam_file_n_read_groups(self.h)):
+            a, b = C.c_char_p(), C.c_char_p()
+            lib.plat_bam_file_read_group(self.h, i, C.byref(a), C.byref(b))
+            out.append((a.value, b.value))
+        return out
+
+    @property
+    def samples(self):
+        """The samples (bytes) this file adds to the sample list."""
+        lib = self.caller.lib
+        return [lib.plat_bam_file_sample(self.h, i) for i in range(lib.plat_bam_file_n_samples(self.h))]
+
+    @property
+    def header_sq(self):
+        """[(SN bytes, LN)] of the header text's @SQ lines as getRegions reads them; None where that read raises."""
+        lib = self.caller.lib
+        n = lib.plat_bam_file_n_header_sq(self.h)
+        if n < 0:
+            return None
+        out = []
+        for i in range(n):
+            name, length = C.c_char_p(), C.c_int64()
+            lib.plat_bam_file_header_sq(self.h, i, C.byref(name), C.byref(length))
+            out.append((name.value, length.value))
+        return out
+
+    @property
+    def header_raised(self):
+        """None, or the reference's words for why reading the header raised (the file's sample is then its name's)."""
+        why = C.c_char_p()
+        return (why.value or b"").decode(errors="replace") if self.caller.lib.plat_bam_file_header_raised(self.h, C.byref(why)) == 1 else None
+
+
+class BamFilesRegion(_RegionBase):
+    """One region of NativeCaller.call_bam_files: chrom:start-end and the contig (wrap it in FastaContigRegion for a NativeFasta's)."""
+
+    def fill(self, a, n_units=0):
+        if self._c is None:
+            self._c = (self.chrom.encode(),)
+        a.chrom, a.contig_seq, a.contig_len = self._c[0], self.contig.ctypes.data, len(self.contig)
+        a.start, a.end = self.start, self.end
+
+
 class NativeCaller:
     """plat_caller: `workers` threads, each with its own plat_ctx and stream on `device`; `regions_per_chunk` regions go through
     the device stages together."""
@@ -1087,6 +1225,109 @@ class NativeCaller:
         if rc != 0:
             raise _lib.PlatypusDeviceError(rc, (self.lib.plat_caller_last_error(self.h) or b"").decode(errors="replace"), "plat_fasta_open")
         return NativeFasta(self, h, data)
+
+    def _error(self, rc, entry):
+        return _lib.PlatypusDeviceError(rc, (self.lib.plat_caller_last_error(self.h) or b"").decode(errors="replace"), entry)
+
+    def open_bam(self, data, bai, file_name):
+        """plat_bam_file_open: a BAM file's bytes (bytes, or a uint8 array / mapped file, which is not copied), its .bai's bytes and the
+        name the sample falls back to.  Returns a NativeBamFile."""
+        keep = _u8(data)
+        bai = bytes(bai)
+        name = file_name if isinstance(file_name, bytes) else file_name.encode()
+        h = C.c_void_p()
+        rc = self.lib.plat_bam_file_open(self.h, keep.ctypes.data if len(keep) else None, len(keep), bai, len(bai), name, C.byref(h))
+        if rc != 0:
+            raise self._error(rc, "plat_bam_file_open")
+        return NativeBamFile(self, h, keep, file_name)
+
+    @staticmethod
+    def _bam_handles(files):
+        return (C.c_void_p * max(len(files), 1))(*[f.h for f in files])
+
+    def bam_plan(self, files):
+        """plat_bam_files_plan: loadBAMData's decision for these NativeBamFiles.  Returns dict(mode "presplit" / "merged", samples [bytes]
+        sorted, sample_file [file index per sample] or None, read_groups [(ID bytes, sample index)])."""
+        plan = C.POINTER(_BamPlan)()
+        rc = self.lib.plat_bam_files_plan(self._bam_handles(files), len(files), C.byref(plan))
+        if rc != 0:
+            raise self._error(rc, "plat_bam_files_plan")
+        try:
+            p = plan.contents
+            groups = np.ctypeslib.as_array(C.cast(p.groups.sample, C.POINTER(C.c_int32)), shape=(p.groups.n_groups,)).tolist() if p.groups.n_groups else []
+            return dict(mode=BAM_FILES_MODES[p.mode], samples=[p.sample_names[s] for s in range(p.n_samples)],
+                        sample_file=[p.sample_file[s] for s in range(p.n_samples)] if p.sample_file else None,
+                        read_groups=[(p.groups.id[g], groups[g]) for g in range(p.groups.n_groups)])
+        finally:
+            self.lib.plat_bam_plan_free(plan)
+
+    @staticmethod
+    def _bam_regions(regions):
+        """The plat_bam_call_region array of region objects (fill) or (chrom, start, end) tuples, and what keeps it alive."""
+        arr = (_BamCallRegion * max(len(regions), 1))()
+        keep = []
+        for k, r in enumerate(regions):
+            if isinstance(r, (tuple, list)):
+                chrom = r[0] if isinstance(r[0], bytes) else r[0].encode()
+                keep.append(chrom)
+                arr[k].chrom, arr[k].start, arr[k].end = chrom, int(r[1]), int(r[2])
+            else:
+                r.fill(arr[k], 0)
+        return arr, keep
+
+    def bam_fetch_plan(self, files, regions):
+        """plat_bam_files_fetch_plan for regions [(chrom, start, end)]: per region and file dict(tid, itr_beg, itr_end, chunks), a chunk as
+        (its offset in the file, data_len, first_uoffset, end_coffset, end_uoffset); self.bam_fetch_info holds the plan's counts."""
+        arr, keep = self._bam_regions(regions)
+        plan = C.POINTER(_BamFetchPlan)()
+        rc = self.lib.plat_bam_files_fetch_plan(self._bam_handles(files), len(files), arr, len(regions), C.byref(plan))
+        del keep
+        if rc != 0:
+            raise self._error(rc, "plat_bam_files_fetch_plan")
+        try:
+            p = plan.contents
+            base = [f.data.ctypes.data for f in files]
+            out = []
+            for k in range(p.n_regions):
+                per = []
+                for f in range(p.n_files):
+                    ft = p.fetches[k * p.n_files + f]
+                    per.append(dict(tid=ft.tid, itr_beg=ft.itr_beg, itr_end=ft.itr_end,
+                                    chunks=[(ft.chunks[q].data - base[f], ft.chunks[q].data_len, ft.chunks[q].first_uoffset, ft.chunks[q].end_coffset,
+                                             ft.chunks[q].end_uoffset) for q in range(ft.n_chunks)]))
+                out.append(per)
+            self.bam_fetch_info = {k: getattr(p, k) for k in ("queries", "handed_over", "chunks", "device_calls", "seconds")}
+            return out
+        finally:
+            self.lib.plat_bam_fetch_plan_free(plan)
+
+    def call_bam_files(self, files, regions, options, source_lines=None, source_blocks=None, source_files=None):
+        """plat_call_bam_files: files [NativeBamFile], regions [BamFilesRegion, or FastaContigRegion over one].  The samples, the mode, the
+        windows and the chunks are the library's (bam_plan, bam_fetch_plan); from there it is call_bgzf_regions or call_bgzf_regions_rg:
+        the same text, rlen, self.loaded and self.read_counts.  self.sample_names holds the call's samples (str)."""
+        n = len(regions)
+        names = self.bam_plan(files)["samples"]
+        nS = len(names)
+        if source_files is not None:
+            if source_lines is not None or source_blocks is not None:
+                raise ValueError("source_lines, source_blocks and source_files are three ways to say the same thing: give one")
+            keep_source = self.set_source_files(source_files, [(r.chrom, r.start, r.end) for r in regions], getattr(options, "longHaps", 0))
+        else:
+            keep_source = self._set_source(source_lines, source_blocks, options)
+        arr, keep = self._bam_regions(regions)
+        o, text, length, st = CallerOptions.from_options(options), C.c_void_p(), C.c_size_t(), CallerStats()
+        q = CallerQCOptions.from_options(options)
+        counts = np.zeros((max(n, 1), nS, 10), dtype=np.int32)
+        info = (_FetchedRegionInfo * max(n, 1))()
+        for k in range(n):
+            info[k].sample_counts = counts[k].ctypes.data
+        rc = self.lib.plat_call_bam_files(self.h, self._bam_handles(files), len(files), arr, n, C.byref(o), C.byref(q), C.byref(text), C.byref(length), info, C.byref(st))
+        del keep_source, keep
+        out = self._finish(rc, "plat_call_bam_files", text, length, o, st, options)
+        self.sample_names = [s.decode(errors="surrogateescape") for s in names]
+        self.loaded = [int(info[k].loaded) for k in range(n)]
+        self.read_counts = counts[:n]
+        return out
 
     def query_index(self, index, queries, info=False):
         """plat_index_query: queries [(tid, beg, end)] in one device batch.  Returns per query the chunk list [(u, v)] ti_iter_query returns,

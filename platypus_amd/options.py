@@ -4,7 +4,11 @@ src/python/runner.py:519-597), kept so that scripts driving Platypus keep workin
 Only the options that reach the hot path are interpreted by this package (rlen/maxReadLength,
 calculateFlankScore, HLATyping, the assembly and QC thresholds, nCPU -> number of GPU ranks); the others are
 accepted, stored on the options object and ignored here (their consumers are outside the hot-path scope,
-SURVEY.md 2.1)."""
+SURVEY.md 2.1).
+
+With --bamFiles AND --refFile and no --synthetic the files themselves are read (platypus_amd.__main__.call_variants_bam_files,
+include/platypus_caller_bamfile.h): --bamFiles, --regions (None, or a list of chr / chr:start-end; region files are refused),
+--bufferSize, --refFile, --source, --output and --outputIndex are then interpreted as well."""
 import argparse
 
 # (flag, dest, type, default)  -- facts of the reference's CLI, no help texts
@@ -70,6 +74,14 @@ REF_HELP = ("FILE: the reference FASTA; its index is read from FILE.fai.  With -
             "--refFile nothing changes.")
 
 
+BAM_HELP = ("FILE[,FILE]: BAM files, each with its index FILE.bai (or FILE without .bam plus .bai) next to it.  Read only together with --refFile and "
+            "without --synthetic: the files are mapped, samples come from the @RG header lines as the reference reads them (one sample per file, or "
+            "files split by read group on the device), regions from --regions (a list of chr or chr:start-end; by default the header's @SQ lines), "
+            "cut at --bufferSize; every region's reads are fetched through the .bai, inflated and decoded on the device "
+            "(include/platypus_caller_bamfile.h).  Region files (.txt / .bed), CRAM, CSI indexes and --assembleBrokenPairs=1 with --assemble=1 are "
+            "refused.  Without --refFile the option is parsed and not used.")
+
+
 def _list(s):
     return s.split(",")
 
@@ -78,7 +90,7 @@ def build_parser():
     p = argparse.ArgumentParser(prog="Platypus.py callVariants", allow_abbrev=False)
     for flag, dest, typ, default in CALL_VARIANTS_OPTIONS:
         p.add_argument(flag, *(["-o"] if flag == "--output" else []), dest=dest,
-                       type=_list if typ == "list" else typ, default=default, **({"help": SOURCE_HELP} if flag == "--source" else {"help": REF_HELP} if flag == "--refFile" else {}))
+                       type=_list if typ == "list" else typ, default=default, **({"help": {"--source": SOURCE_HELP, "--refFile": REF_HELP, "--bamFiles": BAM_HELP}[flag]} if flag in ("--source", "--refFile", "--bamFiles") else {}))
     p.add_argument("--synthetic", dest="synthetic", type=str, default=None,
                    help="(this build) run the hot path on a synthetic BASELINE config instead of BAM input: config1|config2[:N]|config5[:N]")
     p.add_argument("--outputIndex", dest="outputIndex", type=int, default=0,
