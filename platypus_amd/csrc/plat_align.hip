@@ -1886,18 +1886,18 @@ static int align_seed_launch(plat_ctx* ctx, const AlignSwitches& sw, const plat_
     if (lds_pairs > 160 * 1024) return PLAT_ERR_HAP_TOO_LONG;
     if (lds > 48 * 1024) PLAT_HIP(ctx, hipFuncSetAttribute((const void*)k_sweep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     if (lds_pairs > 48 * 1024) PLAT_HIP(ctx, hipFuncSetAttribute((const void*)k_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pairs));
-    { PLAT_KT_BEGIN(ctx, PLAT_KT_SWEEP, st); hipLaunchKernelGGL(k_sweep, dim3(gx), dim3(64), lds, st, b, (uint8_t*)ctx->hapw.ptr, (uint8_t*)ctx->hap_flags.ptr, cnt, tsize_max, maxhap, shortcuts,
-                       (unsigned char*)ctx->seedstate.ptr); PLAT_KT_END(ctx, PLAT_KT_SWEEP, st); }
+    PLAT_LAUNCH(ctx, PLAT_KT_SWEEP, st, k_sweep, dim3(gx), dim3(64), lds, b, (uint8_t*)ctx->hapw.ptr, (uint8_t*)ctx->hap_flags.ptr, cnt, tsize_max, maxhap, shortcuts,
+                       (unsigned char*)ctx->seedstate.ptr);
     PLAT_EV(ctx, 8, st);
     const unsigned gp = (unsigned)(xcd ? ((wave_cap + 7) / 8) * 8 : wave_cap);
-    { PLAT_KT_BEGIN(ctx, PLAT_KT_PAIRS, st); hipLaunchKernelGGL(k_pairs, dim3(gp > 0 ? gp : 1), dim3(64), lds_pairs, st, b, wave_win, wave_first, tile_off, (const ReadInfo*)ctx->rinfo.ptr,
+    PLAT_LAUNCH(ctx, PLAT_KT_PAIRS, st, k_pairs, dim3(gp > 0 ? gp : 1), dim3(64), lds_pairs, b, wave_win, wave_first, tile_off, (const ReadInfo*)ctx->rinfo.ptr,
                        (const uint16_t*)ctx->codes.ptr, (PairRec*)ctx->pair_rec.ptr, (Job*)ctx->jobs.ptr, npairs, extra_cap, cnt,
                        (SlowRec*)ctx->slow.ptr, tsize_max, maxhap, shortcuts, dense, segcap, (const double*)ctx->d_mapq_lut, out_ll, out_score,
-                       (const unsigned char*)ctx->seedstate.ptr); PLAT_KT_END(ctx, PLAT_KT_PAIRS, st); }
+                       (const unsigned char*)ctx->seedstate.ptr);
     PLAT_EV(ctx, 5, st);                                       // k_sweep + k_pairs: ev[1] .. ev[5], ev[8] between the two
-    { PLAT_KT_BEGIN(ctx, PLAT_KT_SEED_SLOW, st); hipLaunchKernelGGL(k_seed_slow, dim3(2048), dim3(64 * slow_waves), lds_slow, st, b, hap_win, tile_off, (const ReadInfo*)ctx->rinfo.ptr,
+    PLAT_LAUNCH(ctx, PLAT_KT_SEED_SLOW, st, k_seed_slow, dim3(2048), dim3(64 * slow_waves), lds_slow, b, hap_win, tile_off, (const ReadInfo*)ctx->rinfo.ptr,
                        (const uint16_t*)ctx->codes.ptr, (PairRec*)ctx->pair_rec.ptr, (Job*)ctx->jobs.ptr, npairs, extra_cap, cnt,
-                       (const SlowRec*)ctx->slow.ptr, tsize_max, maxhap, cw, dense, segcap, sw.slowTiming ? 1 : 0, slow_group); PLAT_KT_END(ctx, PLAT_KT_SEED_SLOW, st); }
+                       (const SlowRec*)ctx->slow.ptr, tsize_max, maxhap, cw, dense, segcap, sw.slowTiming ? 1 : 0, slow_group);
     if (sw.slowTiming) {
         unsigned long long t[8];
         PLAT_HIP(ctx, hipStreamSynchronize(st));
@@ -1960,8 +1960,8 @@ static int align_impl(plat_ctx* ctx, const plat_window_batch* batch, const plat_
     if (async) hv = *hints;
     {   // a wave per window, a thread per haplotype; a small batch (a chunk of the region loop) does not pay for 2048 workgroups
         const long long want = std::max<long long>(((long long)b.n_windows * 64 + 255) / 256, ((long long)b.n_haps + 255) / 256);
-        { PLAT_KT_BEGIN(ctx, PLAT_KT_VALIDATE, st); hipLaunchKernelGGL(k_validate, dim3((unsigned)std::min<long long>(2048, std::max<long long>(1, want))), dim3(256), 0, st, b, cnt, hap_win,
-                           win_rows, calc_flank_score); PLAT_KT_END(ctx, PLAT_KT_VALIDATE, st); }
+        PLAT_LAUNCH(ctx, PLAT_KT_VALIDATE, st, k_validate, dim3((unsigned)std::min<long long>(2048, std::max<long long>(1, want))), dim3(256), 0, b, cnt, hap_win,
+                           win_rows, calc_flank_score);
     }
     // waves of k_pairs: <= n_pairs / 64 + n_haps / 5 + n_windows (64 pairs per wave; windows with < 13 reads give a wave 5 whole haplotypes)
     // (asynchronous: the caller stated n_pairs, so the wave map is sized and built right here; synchronous: after the read-back below)
@@ -1978,7 +1978,7 @@ static int align_impl(plat_ctx* ctx, const plat_window_batch* batch, const plat_
         return PLAT_OK;
     };
     if (async && (rc = reserve_wave_map(hv.n_pairs))) return rc;
-    { PLAT_KT_BEGIN(ctx, PLAT_KT_TILE_SCAN, st); hipLaunchKernelGGL(k_tile_scan, dim3(1), dim3(1024), 0, st, b, win_rows, tile_off, cnt, hv, async ? 1 : 0, wave_win, wave_first, wave_cap); PLAT_KT_END(ctx, PLAT_KT_TILE_SCAN, st); }
+    PLAT_LAUNCH(ctx, PLAT_KT_TILE_SCAN, st, k_tile_scan, dim3(1), dim3(1024), 0, b, win_rows, tile_off, cnt, hv, async ? 1 : 0, wave_win, wave_first, wave_cap);
     PLAT_HIP(ctx, hipGetLastError());
     int64_t* hb = ctx->h_readback;
     long long tile_total;
@@ -1992,7 +1992,7 @@ static int align_impl(plat_ctx* ctx, const plat_window_batch* batch, const plat_
         tile_total = hb[CNT_TILE_TOTAL];
         if (hv.n_pairs > 0) {                                 // the wave map of k_pairs, now that the number of pairs is known (the scan again: same offsets)
             if ((rc = reserve_wave_map(hv.n_pairs))) return rc;
-            { PLAT_KT_BEGIN(ctx, PLAT_KT_TILE_SCAN, st); hipLaunchKernelGGL(k_tile_scan, dim3(1), dim3(1024), 0, st, b, win_rows, tile_off, cnt, hv, 0, wave_win, wave_first, wave_cap); PLAT_KT_END(ctx, PLAT_KT_TILE_SCAN, st); }
+            PLAT_LAUNCH(ctx, PLAT_KT_TILE_SCAN, st, k_tile_scan, dim3(1), dim3(1024), 0, b, win_rows, tile_off, cnt, hv, 0, wave_win, wave_first, wave_cap);
         }
     } else {
         tile_total = (long long)(hv.max_read_len + 8) * b.n_reads + 4ll * b.n_windows;     // upper bound of k_tile_scan's total
@@ -2020,8 +2020,8 @@ static int align_impl(plat_ctx* ctx, const plat_window_batch* batch, const plat_
     {
         const bool xcd = sw.seedXcd && b.n_windows >= 64;       // (PLAT_SEED_XCD=0: window w on workgroup w)
         const unsigned gx = xcd ? (unsigned)((b.n_windows + 7) / 8) * 8u : (unsigned)b.n_windows;
-        { PLAT_KT_BEGIN(ctx, PLAT_KT_PREP_READS, st); hipLaunchKernelGGL(k_prep_reads, dim3(gx, prep_groups), dim3(256), prep_lds, st, b, win_rows, tile_off,
-                           (uint16_t*)ctx->codes.ptr, (ReadInfo*)ctx->rinfo.ptr, cnt, prep_qoff, xcd ? 1 : 0); PLAT_KT_END(ctx, PLAT_KT_PREP_READS, st); }
+        PLAT_LAUNCH(ctx, PLAT_KT_PREP_READS, st, k_prep_reads, dim3(gx, prep_groups), dim3(256), prep_lds, b, win_rows, tile_off,
+                           (uint16_t*)ctx->codes.ptr, (ReadInfo*)ctx->rinfo.ptr, cnt, prep_qoff, xcd ? 1 : 0);
     }
     long long njobs = 0;
     PLAT_EV(ctx, 1, st);
@@ -2081,21 +2081,21 @@ static int align_impl(plat_ctx* ctx, const plat_window_batch* batch, const plat_
         // a fixed grid walks the list (its length lives on the device): two rounds of the blocks a device holds at 4 waves/SIMD
         // (8 workgroups per CU; PLAT_DP_GRID_PER_CU: measurements)
         const long long want = (ngrid + 255) / 256, fixed = (long long)sw.dpGridPerCu * ctx->n_cu;
-        { PLAT_KT_BEGIN(ctx, PLAT_KT_DP_JOBS, st); hipLaunchKernelGGL(k_dp_jobs, dim3((unsigned)(want < fixed ? want : fixed)), dim3(256), 0, st, b, (const uint8_t*)ctx->hapw.ptr,
+        PLAT_LAUNCH(ctx, PLAT_KT_DP_JOBS, st, k_dp_jobs, dim3((unsigned)(want < fixed ? want : fixed)), dim3(256), 0, b, (const uint8_t*)ctx->hapw.ptr,
                            (const uint8_t*)ctx->hap_flags.ptr, (const Job*)ctx->jobs.ptr,
                            (const PairRec*)ctx->pair_rec.ptr, ctx->d_mapq_lut, npairs, dense, segcap, cnt, extra_cap,
-                           (int32_t*)ctx->job_score.ptr, out_loglik, out_score); PLAT_KT_END(ctx, PLAT_KT_DP_JOBS, st); }
+                           (int32_t*)ctx->job_score.ptr, out_loglik, out_score);
     }
     PLAT_EV(ctx, 3, st);
     if (async) {
         const long long want = (ngrid + 255) / 256, fixed = 8ll * ctx->n_cu;
-        { PLAT_KT_BEGIN(ctx, PLAT_KT_FINALIZE, st); hipLaunchKernelGGL(k_finalize_dense, dim3((unsigned)(want < fixed ? std::max(want, 1ll) : fixed)), dim3(256), 0, st,
+        PLAT_LAUNCH(ctx, PLAT_KT_FINALIZE, st, k_finalize_dense, dim3((unsigned)(want < fixed ? std::max(want, 1ll) : fixed)), dim3(256), 0,
                            (const PairRec*)ctx->pair_rec.ptr, (const Job*)ctx->jobs.ptr, (const int32_t*)ctx->job_score.ptr,
-                           ctx->d_mapq_lut, npairs, dense, segcap, cnt, extra_cap, out_loglik, out_score, (long long*)ctx->d_sticky); PLAT_KT_END(ctx, PLAT_KT_FINALIZE, st); }
+                           ctx->d_mapq_lut, npairs, dense, segcap, cnt, extra_cap, out_loglik, out_score, (long long*)ctx->d_sticky);
     } else
-        { PLAT_KT_BEGIN(ctx, PLAT_KT_FINALIZE, st); hipLaunchKernelGGL(k_finalize_multi, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, st,
+        PLAT_LAUNCH(ctx, PLAT_KT_FINALIZE, st, k_finalize_multi, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0,
                            (const PairRec*)ctx->pair_rec.ptr, (const Job*)ctx->jobs.ptr,
-                           (const int32_t*)ctx->job_score.ptr, ctx->d_mapq_lut, npairs, cnt, extra_cap, out_loglik, out_score); PLAT_KT_END(ctx, PLAT_KT_FINALIZE, st); }
+                           (const int32_t*)ctx->job_score.ptr, ctx->d_mapq_lut, npairs, cnt, extra_cap, out_loglik, out_score);
     PLAT_EV(ctx, 4, st);
     if (async) {                                               // (k_finalize_dense left the batch's verdict in the sticky word)
         PLAT_HIP(ctx, hipGetLastError());

@@ -45,6 +45,7 @@
 // a switch as the comparand of the fused pass until round 15 retired it (profiles/HISTORY.md); the oracle is the comparand now.
 #include "plat_internal.hpp"
 #include "switches.hpp"
+#include "wave_tiles.hpp"
 
 namespace plat {
 
@@ -412,28 +413,6 @@ __device__ __forceinline__ int asm_select64(unsigned long long m, int n) {
     }
     return pos;
 }
-// exclusive prefix sum of one value per thread over the workgroup (wave scans by lane shifts, the wave totals through `s_wsum`);
-// every thread gets the total too.  All threads must call it.
-__device__ __forceinline__ int asm_block_exscan(int v, int* s_wsum, int& total) {
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nw = blockDim.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(x, o); if (lane >= o) x += y; }
-    if (lane == 63) s_wsum[wv] = x;
-    __syncthreads();
-    if (tid < 64) {
-        int t = tid < nw ? s_wsum[tid] : 0;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(t, o); if (lane >= o) t += y; }
-        s_wsum[tid] = t;
-    }
-    __syncthreads();
-    const int before = wv ? s_wsum[wv - 1] : 0;
-    total = s_wsum[nw - 1];
-    __syncthreads();
-    return before + x - v;
-}
-
 // workgroup barrier + agent-scope acquire: the graph lives in global memory and is updated with L2 atomics, so the
 // CU's vector L1 must be invalidated before plain loads re-read it (MI355X_MICROARCH.md, inter-workgroup visibility;
 // here producer and consumer are the same CU but the stale-L1 hazard is the same).
@@ -564,7 +543,7 @@ k_assemble(plat_assembly_batch b, AsmParams P, char* scratch, int max_ref, int m
                     acc += L - k - 1 > 0 ? L - k - 1 : 0;
                 }
                 int total;
-                acc = asm_block_exscan(acc, s_wsum, total);
+                acc = block_excl_scan<ASM_THREADS>(acc, s_wsum, total);
                 if (tid == 0) { S.read_base[nR] = total; s_n = 0; s_ntasks = 0; s_pool = 0; }
                 for (int r = r0; r < r1; ++r) {
                     S.read_base[r] = acc;
@@ -652,7 +631,7 @@ k_assemble(plat_assembly_batch b, AsmParams P, char* scratch, int max_ref, int m
                     }
                     __syncthreads();
                     const int mine = tid < nW32 ? __popc(s_bm[tid]) : 0;
-                    const int before = asm_block_exscan(mine, s_wsum, nRefNodes0);
+                    const int before = block_excl_scan<ASM_THREADS>(mine, s_wsum, nRefNodes0);
                     if (tid < nW32) s_bp[tid] = (unsigned)before;
                     __syncthreads();
                 } else nRefNodes0 = s_distinct;
@@ -1188,7 +1167,7 @@ k_assemble(plat_assembly_batch b, AsmParams P, char* scratch, int max_ref, int m
                     }
                     int total;
                     const int sofar = s_ntasks;
-                    int at = sofar + asm_block_exscan(cnt, s_wsum, total);
+                    int at = sofar + block_excl_scan<ASM_THREADS>(cnt, s_wsum, total);
                     if (sofar + total > ASM_MAX_TASKS) { at = ASM_MAX_TASKS; if (tid == 0) s_err = PLAT_ERR_OVERFLOW; }
                     else if (tid == 0) s_ntasks = sofar + total;
                     for (int j = 0; j < 4 && cnt > 0; ++j)
@@ -1320,7 +1299,7 @@ k_assemble(plat_assembly_batch b, AsmParams P, char* scratch, int max_ref, int m
             const int nTasks = err0 == 0 ? s_ntasks : 0;
             const int mynf = tid < nTasks ? s_tnfin[tid] : 0;                 // (ASM_MAX_TASKS <= threads)
             int NP;
-            const int pbase = asm_block_exscan(mynf, s_wsum, NP);
+            const int pbase = block_excl_scan<ASM_THREADS>(mynf, s_wsum, NP);
             int* plast = S.stack; int* ptask = S.stack + NP;
             for (int f = 0; f < mynf; ++f) { plast[pbase + f] = S.task_fin[tid * ASM_MAX_FIN + f]; ptask[pbase + f] = tid; }
             asm_sync_wg(); ASM_FRESH();
@@ -1357,15 +1336,13 @@ k_assemble(plat_assembly_batch b, AsmParams P, char* scratch, int max_ref, int m
             if (NP <= 64) {
                 if (tid < 64)
                     chunk(0, [&](int v, int& tot) -> int {
-                        int x = v;
-#pragma unroll
-                        for (int d = 1; d < 64; d <<= 1) { const int y = __shfl_up(x, d); if ((tid & 63) >= d) x += y; }
+                        const int x = wave_incl_scan(v, tid & 63);
                         tot = __shfl(x, 63);
                         return x - v;
                     });
             } else
                 for (int c0 = 0; c0 < NP; c0 += nthr) {
-                    if (!chunk(c0, [&](int v, int& tot) -> int { return asm_block_exscan(v, s_wsum, tot); })) break;
+                    if (!chunk(c0, [&](int v, int& tot) -> int { return block_excl_scan<ASM_THREADS>(v, s_wsum, tot); })) break;
                     __syncthreads();                                              // (the bytes of this chunk are done with)
                 }
             asm_sync_wg(); ASM_FRESH();
@@ -1569,8 +1546,8 @@ static int asm_launch(plat_ctx* ctx, const plat_assembly_batch& b, int kmer_size
     sig |= 1ull;
     const int lds_bytes = ASM_LDS_BYTES;
     PLAT_HIP(ctx, hipFuncSetAttribute((const void*)k_assemble, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-    { PLAT_KT_BEGIN(ctx, PLAT_KT_ASSEMBLE, st); hipLaunchKernelGGL(k_assemble, dim3(nblk), dim3(ASM_THREADS), lds_bytes, st, b, P, (char*)ctx->asm_scratch.ptr, max_ref, max_reads,
-                       var_count, var_pos, var_nrem, var_nadd, var_off, var_blob, status, verdict, work, wg_sig, sig); PLAT_KT_END(ctx, PLAT_KT_ASSEMBLE, st); }
+    PLAT_LAUNCH(ctx, PLAT_KT_ASSEMBLE, st, k_assemble, dim3(nblk), dim3(ASM_THREADS), lds_bytes, b, P, (char*)ctx->asm_scratch.ptr, max_ref, max_reads,
+                       var_count, var_pos, var_nrem, var_nadd, var_off, var_blob, status, verdict, work, wg_sig, sig);
     PLAT_HIP(ctx, hipGetLastError());
     if (P.timing) {
         unsigned long long t[16];

@@ -7,8 +7,8 @@
 // any ordering step.  Merging equal variants and counting their supporting reads (addVariantToList, :499-527) is a
 // dictionary operation over the few records that come back; it stays on the host (hostapi.VariantCandidateGenerator).
 #include "plat_internal.hpp"
-#include <mutex>
-#include <math.h>
+#include "wave_tiles.hpp"
+#include "read_source.hpp"
 
 namespace plat {
 
@@ -23,17 +23,6 @@ struct CandEmit {
         ++n;
     }
 };
-
-// 8 bytes from any address (global memory takes unaligned 64-bit loads)
-__device__ __forceinline__ unsigned long long load_u64_bytes(const uint8_t* p) {
-    typedef unsigned long long __attribute__((aligned(1))) u64u;
-    return *(const u64u*)p;
-}
-
-__device__ __forceinline__ bool has_n(const uint8_t* s, int n) {
-    for (int i = 0; i < n; ++i) if (s[i] == 'N') return true;
-    return false;
-}
 
 __global__ void __launch_bounds__(64)
 k_candidates(plat_candidate_batch b, int min_flank, int min_base_qual, int gen_snps, int gen_indels, int max_per_read,
@@ -201,61 +190,6 @@ __device__ __forceinline__ unsigned long long codes_at(const unsigned long long*
     if (sh == 0) return lo;
     return (lo >> sh) | (c[w + 1] << (64 - sh));
 }
-
-// ---- a read's letters and qualities, wherever they lie ------------------------------------------------------------------------------------
-// The kernels that start from a READ (the scan on codes, the read statistics, the gather) are written once over one of these: base(i) /
-// qual(i) of the read's i-th base (qual: the raw byte; the scan reads it unsigned, the statistics signed, as the reference's two loops do).
-// ASCII tables: the expanded bytes.
-struct ReadAscii {
-    const uint8_t* s; const uint8_t* q;
-    __device__ __forceinline__ uint8_t base(int i) const { return s[i]; }
-    __device__ __forceinline__ uint8_t qual(int i) const { return q[i]; }
-    __device__ __forceinline__ bool has_n(int at, int n) const { return plat::has_n(s + at, n); }
-};
-struct SrcAscii {
-    static constexpr bool packed = false;
-    const uint8_t* seq; const uint8_t* qual;
-    __device__ __forceinline__ ReadAscii read(int, long long soff, long long) const { return ReadAscii{seq + soff, qual + soff}; }
-};
-// PLAT_READS_PACKED bytes at their source: letter "ACTG"[b & 3], quality b >> 2 -- or the exception's, where the blob index at + i is listed
-// in exc_index[e0, e1) (the read's own exceptions: two lower bounds per read, and only in a chunk that has any; most reads have none and
-// never touch the exception arrays)
-struct ReadPacked {
-    const uint8_t* p; long long at; const int64_t* idx; const uint8_t* eb; const uint8_t* eq; long long e0, e1;
-    __device__ __forceinline__ long long find(int i) const {
-        long long lo = e0, hi = e1;
-        while (lo < hi) { const long long mid = (lo + hi) >> 1; if (idx[mid] < at + i) lo = mid + 1; else hi = mid; }
-        return lo < e1 && idx[lo] == at + i ? lo : -1;
-    }
-    __device__ __forceinline__ uint8_t base(int i) const {
-        if (e0 != e1) { const long long k = find(i); if (k >= 0) return eb[k]; }
-        return (uint8_t)((0x47544341u >> (8u * (p[i] & 3u))) & 0xFFu);
-    }
-    __device__ __forceinline__ uint8_t qual(int i) const {
-        if (e0 != e1) { const long long k = find(i); if (k >= 0) return eq[k]; }
-        return (uint8_t)(p[i] >> 2);
-    }
-    __device__ __forceinline__ bool has_n(int a, int n) const {                    // (only an exception can be an N)
-        for (long long k = e0; k < e1; ++k) if (idx[k] >= at + a && idx[k] < at + a + n && eb[k] == 'N') return true;
-        return false;
-    }
-};
-struct SrcPacked {
-    static constexpr bool packed = true;
-    plat_packed_reads pk;
-    // read r, whose bytes are [soff, soff + rlen) of the blob
-    __device__ __forceinline__ ReadPacked read(int r, long long soff, long long rlen) const {
-        long long e0 = 0, e1 = 0;
-        if (pk.n_exc > 0) {
-            long long lo = 0, hi = pk.n_exc;
-            while (lo < hi) { const long long mid = (lo + hi) >> 1; if (pk.exc_index[mid] < soff) lo = mid + 1; else hi = mid; }
-            e0 = lo; hi = pk.n_exc;
-            while (lo < hi) { const long long mid = (lo + hi) >> 1; if (pk.exc_index[mid] < soff + rlen) lo = mid + 1; else hi = mid; }
-            e1 = lo;
-        }
-        return ReadPacked{pk.read_src[r], soff, pk.exc_index, pk.exc_base, pk.exc_qual, e0, e1};
-    }
-};
 
 // the scan of read r on codes, over either storage.  SrcPacked: no expanded bytes exist, so the lane leaves the read-side allele of every
 // record it finds in b.read_seq (the chunk's t_seq) at the record's own offset -- all that the kernels starting from a RECORD (merge, filter,
@@ -435,11 +369,9 @@ PLAT_EXPORT int plat_candidates_batch_codes(plat_ctx* ctx, const plat_candidate_
         return PLAT_ERR_INVALID;
     PLAT_HIP(ctx, hipSetDevice(ctx->device));
     PLAT_EV_TAB(ctx, 2, (hipStream_t)stream);
-    { PLAT_KT_BEGIN(ctx, PLAT_KT_CANDIDATES, (hipStream_t)stream);
-      hipLaunchKernelGGL(plat::k_candidates_codes, dim3((unsigned)((b.n_reads + 63) / 64)), dim3(64), 0, (hipStream_t)stream, b, (const unsigned long long*)read_codes,
+    PLAT_LAUNCH(ctx, PLAT_KT_CANDIDATES, stream, plat::k_candidates_codes, dim3((unsigned)((b.n_reads + 63) / 64)), dim3(64), 0, b, (const unsigned long long*)read_codes,
                          (const unsigned long long*)ref_codes, ref_irregular, min_flank, min_base_qual, gen_snps, gen_indels, max_per_read, read_region, out_rec, out_count,
                          out_status);
-      PLAT_KT_END(ctx, PLAT_KT_CANDIDATES, (hipStream_t)stream); }
     PLAT_EV_TAB(ctx, 3, (hipStream_t)stream);
     ctx->ev_valid_cand = ctx->profile;
     PLAT_HIP(ctx, hipGetLastError());
@@ -462,11 +394,9 @@ PLAT_EXPORT int plat_candidates_batch_packed(plat_ctx* ctx, const plat_candidate
         return PLAT_ERR_INVALID;
     PLAT_HIP(ctx, hipSetDevice(ctx->device));
     PLAT_EV_TAB(ctx, 2, (hipStream_t)stream);
-    { PLAT_KT_BEGIN(ctx, PLAT_KT_CANDIDATES, (hipStream_t)stream);
-      hipLaunchKernelGGL(plat::k_candidates_packed, dim3((unsigned)((b.n_reads + 63) / 64)), dim3(64), 0, (hipStream_t)stream, b, pk, (const unsigned long long*)read_codes,
+    PLAT_LAUNCH(ctx, PLAT_KT_CANDIDATES, stream, plat::k_candidates_packed, dim3((unsigned)((b.n_reads + 63) / 64)), dim3(64), 0, b, pk, (const unsigned long long*)read_codes,
                          (const unsigned long long*)ref_codes, ref_irregular, min_flank, min_base_qual, gen_snps, gen_indels, max_per_read, read_region, out_rec, out_count,
                          out_status);
-      PLAT_KT_END(ctx, PLAT_KT_CANDIDATES, (hipStream_t)stream); }
     PLAT_EV_TAB(ctx, 3, (hipStream_t)stream);
     ctx->ev_valid_cand = ctx->profile;
     PLAT_HIP(ctx, hipGetLastError());
@@ -486,8 +416,8 @@ PLAT_EXPORT int plat_candidates_batch(plat_ctx* ctx, const plat_candidate_batch*
         return PLAT_ERR_INVALID;
     PLAT_HIP(ctx, hipSetDevice(ctx->device));
     PLAT_EV_TAB(ctx, 2, (hipStream_t)stream);
-    { PLAT_KT_BEGIN(ctx, PLAT_KT_CANDIDATES, (hipStream_t)stream); hipLaunchKernelGGL(plat::k_candidates, dim3((unsigned)((b.n_reads + 63) / 64)), dim3(64), 0, (hipStream_t)stream, b,
-                       min_flank, min_base_qual, gen_snps, gen_indels, max_per_read, read_region, out_rec, out_count, out_status); PLAT_KT_END(ctx, PLAT_KT_CANDIDATES, (hipStream_t)stream); }
+    PLAT_LAUNCH(ctx, PLAT_KT_CANDIDATES, stream, plat::k_candidates, dim3((unsigned)((b.n_reads + 63) / 64)), dim3(64), 0, b,
+                       min_flank, min_base_qual, gen_snps, gen_indels, max_per_read, read_region, out_rec, out_count, out_status);
     PLAT_EV_TAB(ctx, 3, (hipStream_t)stream);
     ctx->ev_valid_cand = ctx->profile;
     PLAT_HIP(ctx, hipGetLastError());
@@ -528,22 +458,6 @@ struct MergeLds {
     int32_t wsum[MERGE_THREADS / 64];
     int32_t distinct, full, bad, need, n_out, st_out;
 };
-
-// exclusive prefix of v over the workgroup's threads and the total; every thread calls it
-__device__ __forceinline__ int merge_block_scan(int v, int32_t* wsum, int& total) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(inc, d, 64); if (lane >= d) inc += t; }
-    if (lane == 63) wsum[wv] = inc;
-    __syncthreads();
-    int off = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < MERGE_THREADS / 64; ++w) { const int s = wsum[w]; if (w < wv) off += s; tot += s; }
-    __syncthreads();
-    total = tot;
-    return off + inc - v;
-}
 
 __device__ __forceinline__ void merge_load(const int32_t* __restrict__ rec, int id, int32_t* w) {
     const int32_t* me = rec + 5ll * id;
@@ -650,7 +564,7 @@ k_candidates_merge(const uint8_t* __restrict__ ref_seq, const uint8_t* __restric
             mine += c[j];
         }
         int tot;
-        const int off = merge_block_scan(mine, L.wsum, tot);
+        const int off = block_excl_scan<MERGE_THREADS>(mine, L.wsum, tot);
         const int hi = base + tot;
         for (;;) {
             int at = base + off - qstart;
@@ -692,7 +606,7 @@ k_candidates_merge(const uint8_t* __restrict__ ref_seq, const uint8_t* __restric
     for (int j = 0; j < SPT / 4; ++j) gtab[tid * (SPT / 4) + j] = make_int4(idp[4 * j], idp[4 * j + 1], idp[4 * j + 2], idp[4 * j + 3]);
     int n_occ;
     {
-        int at = merge_block_scan(occ, L.wsum, n_occ);
+        int at = block_excl_scan<MERGE_THREADS>(occ, L.wsum, n_occ);
 #pragma unroll
         for (int j = 0; j < SPT; ++j) if (idp[j] != 0) L.queue[at++] = tid * SPT + j;
     }
@@ -803,989 +717,8 @@ PLAT_EXPORT int plat_candidates_merge_batch(plat_ctx* ctx, const plat_candidate_
         PLAT_HIP(ctx, hipFuncSetAttribute((const void*)plat::k_candidates_merge, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(plat::MergeLds)));
         ctx->merge_attr_set = true;
     }
-    { PLAT_KT_BEGIN(ctx, PLAT_KT_CAND_MERGE, (hipStream_t)stream);
-      hipLaunchKernelGGL(plat::k_candidates_merge, dim3((unsigned)n_scans), dim3(plat::MERGE_THREADS), sizeof(plat::MergeLds), (hipStream_t)stream, b.ref_seq, b.read_seq,
+    PLAT_LAUNCH(ctx, PLAT_KT_CAND_MERGE, stream, plat::k_candidates_merge, dim3((unsigned)n_scans), dim3(plat::MERGE_THREADS), sizeof(plat::MergeLds), b.ref_seq, b.read_seq,
                          b.read_pos, read_end, scan_read_begin, scan_longest, max_per_read, rec, count, status, mtab, min_var_freq, cap_per_scan, out_cand, out_n);
-      PLAT_KT_END(ctx, PLAT_KT_CAND_MERGE, (hipStream_t)stream); }
-    PLAT_HIP(ctx, hipGetLastError());
-    return PLAT_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Read QC / trimming: checkAndTrimRead (cwindow.pyx:332-481).  One lane per read; `theLastRead` of
-// bamReadBuffer.addReadToBuffer (:560-595) is simply the previous read of the same stream and only its position, length
-// and mate position are looked at, so the reads of a stream are independent of each other.
-namespace plat {
-
-// The qualities of one read as checkAndTrimRead sees them: get(i) (a signed char, as the reference's `char*`) and trim(i) (quality 0).
-// ASCII tables: the raw phred bytes.
-struct QualBytes {
-    int8_t* q;
-    __device__ __forceinline__ int get(int i) const { return q[i]; }
-    __device__ __forceinline__ void trim(int i) const { q[i] = 0; }
-};
-
-// PLAT_READS_PACKED tables: the quality bits of the packed byte, or the exception's quality where the byte is listed.  e0 / e1: the
-// read's exceptions (exc_index[e0, e1) lie inside the read's bytes); a read without exceptions never touches the exception arrays.
-struct QualPacked {
-    uint8_t* p;                       // the read's first byte
-    int64_t at;                       // its index in the blob
-    const int64_t* idx;
-    uint8_t* eq;
-    int64_t e0, e1;
-    __device__ __forceinline__ int64_t find(int i) const {
-        if (e0 == e1) return -1;
-        int64_t lo = e0, hi = e1;
-        while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (idx[mid] < at + i) lo = mid + 1; else hi = mid; }
-        return lo < e1 && idx[lo] == at + i ? lo : -1;
-    }
-    __device__ __forceinline__ int get(int i) const { const int64_t k = find(i); return k >= 0 ? (int)(int8_t)eq[k] : (int)(p[i] >> 2); }
-    __device__ __forceinline__ void trim(int i) const { p[i] &= 3; const int64_t k = find(i); if (k >= 0) eq[k] = 0; }
-};
-
-// ... and a read of such a table without exceptions (most of them): the quality bits only, loops as tight as QualBytes'
-struct QualPackedPlain {
-    uint8_t* p;
-    __device__ __forceinline__ int get(int i) const { return p[i] >> 2; }
-    __device__ __forceinline__ void trim(int i) const { p[i] &= 3; }
-};
-
-// checkAndTrimRead on read r over either storage: the one copy of the verdicts and the trimming
-template <class Q>
-__device__ __forceinline__ void read_qc_one(const plat_readqc_batch& b, const plat_readqc_options& o, int r, const Q& q, int32_t* __restrict__ ok,
-                                            int32_t* __restrict__ reason)
-{
-    const int rlen = (int)(b.read_off[r + 1] - b.read_off[r]);
-    const int f = b.read_flags[r];
-    const bool paired = f & 1, proper = f & 2, unmapped = f & 4, mateUnmapped = f & 8, reverse = f & 16, mateReverse = f & 32;
-    const int ins = b.insert_size[r];
-    const int absIns = ins < 0 ? -ins : ins;
-    int why = -1, qcfail = 1;
-    if (f & 256) why = 7;                                                            // secondary alignment, :337-339
-    else if ((int)b.read_mapq[r] < o.min_map_qual) why = 6;                          // :341-344
-    else {
-        int nBelow = 0;
-        for (int i = 0; i < rlen; ++i) nBelow += q.get(i) < o.min_base_qual;
-        if (rlen - nBelow < o.min_good_qual_bases) why = 0;                          // :354-357
-        else if (unmapped) why = 1;                                                  // :360-363
-        else if (o.filter_mate_unmapped && paired && mateUnmapped) { why = 2; qcfail = 0; }          // :367-371 (no QCFail flag)
-        else if (o.filter_mate_distant && paired && (b.chrom_id[r] != b.mate_chrom_id[r] || !proper)) { why = 3; qcfail = 0; }
-        else if (o.filter_small_insert && paired && ins != 0 && absIns < rlen) why = 4;
-        else if (o.filter_duplicates) {                                              // :389-409
-            if (f & 1024) why = 5;
-            else if (r > 0 && b.stream_of[r - 1] == b.stream_of[r] && b.read_pos[r] == b.read_pos[r - 1] &&
-                     rlen == (int)(b.read_off[r] - b.read_off[r - 1])) {
-                if (!paired || b.mate_pos[r - 1] == b.mate_pos[r]) why = 5;
-            }
-        }
-    }
-    if (why >= 0) {
-        if (qcfail) b.read_flags[r] = f | 512;
-        ok[r] = 0; reason[r] = why;
-        return;
-    }
-    if (!reverse) {                                                                  // low-quality tail, :415-421
-        for (int i = 1; i <= rlen; ++i) {
-            if (i < o.trim_read_flank || q.get(rlen - i) < 5) q.trim(rlen - i); else break;
-        }
-    } else {
-        for (int i = 0; i < rlen; ++i) {
-            if (i < o.trim_read_flank || q.get(i) < 5) q.trim(i); else break;
-        }
-    }
-    if (o.trim_overlapping == 1 && paired && absIns > 0 && !reverse && mateReverse && absIns < 2 * rlen) {   // :438-440
-        int lim = (2 * rlen - ins) + 1;
-        if (lim > rlen) lim = rlen;
-        for (int i = 1; i <= lim; ++i) q.trim(rlen - i);
-    }
-    if (o.trim_adapter == 1 && paired && absIns > 0 && absIns < rlen) {               // :445-452
-        if (reverse) { for (int i = 1; i < rlen - absIns + 1; ++i) q.trim(rlen - i); }
-        else { for (int i = absIns; i < rlen; ++i) q.trim(i); }
-    }
-    if (o.trim_soft_clipped == 1) {                                                   // :462-479 (only M and I advance the cursor)
-        int index = 0;
-        for (int c = b.cig_off[r]; c < b.cig_off[r + 1]; ++c) {
-            const int op = b.cigar[2 * c], len = b.cigar[2 * c + 1];
-            if (op == 0 || op == 1) index += len;
-            else if (op == 4) for (int j = 0; j < len && index < rlen; ++j) q.trim(index++);
-        }
-    }
-    ok[r] = 1; reason[r] = -1;
-}
-
-__global__ void __launch_bounds__(64)
-k_read_qc(plat_readqc_batch b, plat_readqc_options o, int32_t* __restrict__ ok, int32_t* __restrict__ reason)
-{
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= b.n_reads) return;
-    read_qc_one(b, o, r, QualBytes{(int8_t*)b.read_qual + b.read_off[r]}, ok, reason);
-}
-
-// The same on PLAT_READS_PACKED bytes: the read's exceptions by two lower bounds of its byte range in exc_index
-__global__ void __launch_bounds__(64)
-k_read_qc_packed(plat_readqc_batch b, plat_readqc_options o, uint8_t* __restrict__ packed, int64_t n_exc, const int64_t* __restrict__ exc_index,
-                 uint8_t* __restrict__ exc_qual, int32_t* __restrict__ ok, int32_t* __restrict__ reason)
-{
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= b.n_reads) return;
-    const int64_t a = b.read_off[r], z = b.read_off[r + 1];
-    int64_t e0 = 0, e1 = 0;
-    if (n_exc > 0) {
-        int64_t lo = 0, hi = n_exc;
-        while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (exc_index[mid] < a) lo = mid + 1; else hi = mid; }
-        e0 = lo; hi = n_exc;
-        while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (exc_index[mid] < z) lo = mid + 1; else hi = mid; }
-        e1 = lo;
-    }
-    if (e0 == e1) read_qc_one(b, o, r, QualPackedPlain{packed + a}, ok, reason);
-    else read_qc_one(b, o, r, QualPacked{packed + a, a, exc_index, exc_qual, e0, e1}, ok, reason);
-}
-
-}  // namespace plat
-
-PLAT_EXPORT int plat_read_qc_batch(plat_ctx* ctx, const plat_readqc_batch* batch, const plat_readqc_options* options,
-                                   int32_t* out_ok, int32_t* out_reason, void* stream)
-{
-    if (!ctx || !batch || !options) return PLAT_ERR_INVALID;
-    const plat_readqc_batch b = *batch;
-    if (b.n_reads < 0) return PLAT_ERR_INVALID;
-    if (b.n_reads == 0) return PLAT_OK;
-    if (!b.read_qual || !b.read_off || !b.read_pos || !b.read_mapq || !b.read_flags || !b.chrom_id || !b.mate_chrom_id ||
-        !b.insert_size || !b.mate_pos || !b.cigar || !b.cig_off || !b.stream_of || !out_ok || !out_reason)
-        return PLAT_ERR_INVALID;
-    PLAT_HIP(ctx, hipSetDevice(ctx->device));
-    { PLAT_KT_BEGIN(ctx, PLAT_KT_READ_QC, (hipStream_t)stream); hipLaunchKernelGGL(plat::k_read_qc, dim3((unsigned)((b.n_reads + 63) / 64)), dim3(64), 0, (hipStream_t)stream, b, *options,
-                       out_ok, out_reason); PLAT_KT_END(ctx, PLAT_KT_READ_QC, (hipStream_t)stream); }
-    PLAT_HIP(ctx, hipGetLastError());
-    return PLAT_OK;
-}
-
-// (plat_read_buffers_packed_batch, plat_readbuf.hip: the packed table's checkAndTrimRead; arguments checked there)
-int plat_read_qc_packed_launch(plat_ctx* ctx, const plat_read_buffers_packed_in& in, const plat_readqc_options& options, int32_t* out_ok,
-                               int32_t* out_reason, hipStream_t stream)
-{
-    const plat_readqc_batch& b = in.qc;
-    if (b.n_reads == 0) return PLAT_OK;
-    { PLAT_KT_BEGIN(ctx, PLAT_KT_READ_QC, stream); hipLaunchKernelGGL(plat::k_read_qc_packed, dim3((unsigned)((b.n_reads + 63) / 64)), dim3(64), 0, stream, b, options,
-                       in.read_packed, in.n_exc, in.exc_index, in.exc_qual, out_ok, out_reason); PLAT_KT_END(ctx, PLAT_KT_READ_QC, stream); }
-    PLAT_HIP(ctx, hipGetLastError());
-    return PLAT_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Read statistics of the VCF INFO field: vcfINFO's loop over the reads of a window
-// (vcfutils.pyx:1300-1390) with readOverlapsVariant (:901-913), readQualIsGoodVariantPosition (:917-943) and
-// variantSupportedByRead (:961-1072).  One wave per variant; lanes over the reads of one sample at a time; every count is a
-// ballot popcount, the MMLQ window minima are written in read order (prefix popcount).
-namespace plat {
-
-template <class R>
-__device__ __forceinline__ bool qual_good_at(const R& rd, int rlen, int readPos, int vmin, int vmax) {
-    int a = max(0, min(rlen, vmin - readPos)), e = max(0, min(rlen, vmax - readPos));
-    for (int i = a; i < e; ++i) if ((int8_t)rd.qual(i) < 5) return false;
-    return true;
-}
-
-template <class R>
-__device__ __forceinline__ bool bytes_equal(const R& rd, int at, const uint8_t* b, int n) {
-    for (int i = 0; i < n; ++i) if (rd.base(at + i) != b[i]) return false;
-    return true;
-}
-
-template <class R>
-__device__ __forceinline__ bool read_supports(const R& seq, int rlen, int readStart, const int16_t* ops, int ncig, int varPos,
-                                              int nAdded, int nRemoved, const uint8_t* added, int exact)
-{
-    int refOffset = 0, readOffset = 0;
-    for (int ci = 0; ci < ncig; ++ci) {
-        const int flag = ops[2 * ci], length = ops[2 * ci + 1];
-        if (flag == 1) {                                                     // insertion, :984-1003
-            if (nAdded != nRemoved) {
-                if (!exact) return true;
-                if (nAdded - nRemoved == length && readOffset + nAdded <= rlen && bytes_equal(seq, readOffset, added, nAdded)) return true;
-                return false;
-            }
-            readOffset += length;
-        } else if (flag == 2) {                                              // deletion, :1005-1024
-            if (nAdded != nRemoved) return exact ? (nRemoved - nAdded == length) : true;
-            refOffset += length;
-        } else if (flag == 0 || flag == 7 || flag == 8) {                    // M, =, X, :1027-1048
-            const int start = varPos - readStart + readOffset - refOffset;
-            if (refOffset + readStart <= varPos && refOffset + readStart + length > varPos && nAdded == nRemoved &&
-                start >= 0 && start + nAdded <= rlen && bytes_equal(seq, start, added, nAdded))
-                return true;
-            readOffset += length;
-            refOffset += length;
-        } else if (flag == 3) {                                              // N: the reference advances both, :1051-1053
-            readOffset += length;
-            refOffset += length;
-        } else if (flag == 4) {
-            readOffset += length;
-            if (ci == 0) refOffset += length;
-        }
-    }
-    return false;
-}
-
-template <class S>
-__device__ __forceinline__ void variant_read_stats_one(const plat_infostats_batch& b, const S& src, int bad_reads_window, int exact, int64_t* __restrict__ out,
-                                                       int32_t* __restrict__ per_sample, int32_t* __restrict__ minq, int32_t* __restrict__ nminq)
-{
-    const int v = blockIdx.x, lane = threadIdx.x;
-    const int w = b.var_window[v];
-    const int vmin = b.var_bam_min[v], vmax = b.var_bam_max[v], varPos = b.var_pos[v];
-    const int nAdded = b.var_n_added[v], nRemoved = b.var_n_removed[v];
-    const uint8_t* added = b.var_added + b.var_added_off[v];
-    int32_t* mq = minq + b.minq_off[v];
-    long long c[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) c[k] = 0;
-    int nmq = 0;
-    const int half = (bad_reads_window - 1) / 2;
-    for (int i = 0; i < b.n_ind; ++i) {
-        const long long seg = (long long)w * b.n_ind + i;
-        const bool inGt = b.var_in_genotype[(long long)v * b.n_ind + i] != 0;
-        const int gb = b.good_begin[seg], ge = b.good_end[seg], bb = b.bad_begin[seg], be = b.bad_end[seg];
-        c[13] += ge - gb; c[14] += be - bb;
-        for (int r0 = bb; r0 < be; r0 += 64) {                               // bad reads: coverage and mapping quality only
-            const int r = r0 + lane;
-            bool hit = false; long long m2 = 0;
-            if (r < be) {
-                const int rlen = (int)(b.read_off[r + 1] - b.read_off[r]);
-                hit = b.read_pos[r] <= vmax && b.read_end[r] > vmin &&
-                      qual_good_at(src.read(r, b.read_off[r], rlen), rlen, b.read_pos[r], vmin, vmax);
-                if (hit) m2 = (long long)b.read_mapq[r] * b.read_mapq[r];
-            }
-            c[1] += __popcll(__ballot(hit));
-#pragma unroll
-            for (int s = 32; s > 0; s >>= 1) m2 += __shfl_xor(m2, s);
-            c[15] += m2;
-        }
-        int nReads = 0, nVarReads = 0;
-        for (int r0 = gb; r0 < ge; r0 += 64) {
-            const int r = r0 + lane;
-            bool hit = false, rev = false, sup = false; long long m2 = 0; int wmin = 0;
-            if (r < ge) {
-                const long long so = b.read_off[r];
-                const int rlen = (int)(b.read_off[r + 1] - so);
-                const int rp = b.read_pos[r];
-                if (rp <= vmax && b.read_end[r] > vmin) {
-                    const auto rd = src.read(r, so, rlen);
-                    hit = qual_good_at(rd, rlen, rp, vmin, vmax);
-                    if (hit) {
-                    rev = (b.read_flags[r] & 16) != 0;
-                    m2 = (long long)b.read_mapq[r] * b.read_mapq[r];
-                    sup = read_supports(rd, rlen, rp, b.cigar + 2ll * b.cig_off[r], b.cig_off[r + 1] - b.cig_off[r], varPos,
-                                        nAdded, nRemoved, added, exact);
-                    if (sup && inGt) {                                       // MMLQ window, :1372-1383
-                        const int ws = max(0, vmin - rp - half), we = min(rlen, vmax - rp + half);
-                        for (int k = ws; k < we; ++k) { const int qk = (int)(int8_t)rd.qual(k); wmin = (k == ws) ? qk : min(wmin, qk); }
-                    }
-                    }
-                }
-            }
-            const unsigned long long mh = __ballot(hit), mr = __ballot(hit && rev), ms = __ballot(sup), msr = __ballot(sup && rev);
-            const int nh = __popcll(mh), nhr = __popcll(mr), ns = __popcll(ms), nsr = __popcll(msr);
-            nReads += nh; c[0] += nh; c[7] += nhr; c[8] += nh - nhr;
-            c[2] += ns; nVarReads += ns; c[11] += nsr; c[12] += ns - nsr;
-            if (inGt) {
-                c[3] += nh; c[9] += nhr; c[10] += nh - nhr;
-                c[4] += ns; c[5] += nsr; c[6] += ns - nsr;
-                if (sup) mq[nmq + __popcll(ms & ((1ull << lane) - 1ull))] = wmin;
-                nmq += ns;
-            }
-#pragma unroll
-            for (int s = 32; s > 0; s >>= 1) m2 += __shfl_xor(m2, s);
-            c[15] += m2;
-        }
-        if (lane == 0) {
-            per_sample[((long long)v * b.n_ind + i) * 2] = nReads;
-            per_sample[((long long)v * b.n_ind + i) * 2 + 1] = nVarReads;
-        }
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < 16; ++k) out[16ll * v + k] = c[k];
-        nminq[v] = nmq;
-    }
-}
-
-__global__ void __launch_bounds__(64)
-k_variant_read_stats(plat_infostats_batch b, int bad_reads_window, int exact, int64_t* __restrict__ out, int32_t* __restrict__ per_sample,
-                     int32_t* __restrict__ minq, int32_t* __restrict__ nminq)
-{
-    variant_read_stats_one(b, SrcAscii{b.read_seq, b.read_qual}, bad_reads_window, exact, out, per_sample, minq, nminq);
-}
-
-// ... and on packed bytes at their source (plat_variant_read_stats_packed_batch)
-__global__ void __launch_bounds__(64)
-k_variant_read_stats_packed(plat_infostats_batch b, plat_packed_reads pk, int bad_reads_window, int exact, int64_t* __restrict__ out,
-                            int32_t* __restrict__ per_sample, int32_t* __restrict__ minq, int32_t* __restrict__ nminq)
-{
-    variant_read_stats_one(b, SrcPacked{pk}, bad_reads_window, exact, out, per_sample, minq, nminq);
-}
-
-}  // namespace plat
-
-PLAT_EXPORT int plat_variant_read_stats_batch(plat_ctx* ctx, const plat_infostats_batch* batch, int bad_reads_window,
-                                              int count_only_exact_indel_matches, int64_t* out_counts, int32_t* out_per_sample,
-                                              int32_t* out_minq, int32_t* out_nminq, void* stream)
-{
-    if (!ctx || !batch || bad_reads_window < 1) return PLAT_ERR_INVALID;
-    const plat_infostats_batch b = *batch;
-    if (b.n_vars < 0 || b.n_ind < 1) return PLAT_ERR_INVALID;
-    if (b.n_vars == 0) return PLAT_OK;
-    if (!b.var_window || !b.var_pos || !b.var_bam_min || !b.var_bam_max || !b.var_n_added || !b.var_n_removed || !b.var_added ||
-        !b.var_added_off || !b.var_in_genotype || !b.minq_off || !b.good_begin || !b.good_end || !b.bad_begin || !b.bad_end ||
-        !b.read_seq || !b.read_qual || !b.read_off || !b.read_pos || !b.read_end || !b.read_mapq || !b.read_flags || !b.cigar ||
-        !b.cig_off || !out_counts || !out_per_sample || !out_minq || !out_nminq)
-        return PLAT_ERR_INVALID;
-    PLAT_HIP(ctx, hipSetDevice(ctx->device));
-    { PLAT_KT_BEGIN(ctx, PLAT_KT_VARIANT_READ_STATS, (hipStream_t)stream); hipLaunchKernelGGL(plat::k_variant_read_stats, dim3(b.n_vars), dim3(64), 0, (hipStream_t)stream, b, bad_reads_window,
-                       count_only_exact_indel_matches, out_counts, out_per_sample, out_minq, out_nminq); PLAT_KT_END(ctx, PLAT_KT_VARIANT_READ_STATS, (hipStream_t)stream); }
-    PLAT_HIP(ctx, hipGetLastError());
-    return PLAT_OK;
-}
-
-PLAT_EXPORT int plat_variant_read_stats_packed_batch(plat_ctx* ctx, const plat_infostats_batch* batch, const plat_packed_reads* packed, int bad_reads_window,
-                                                     int count_only_exact_indel_matches, int64_t* out_counts, int32_t* out_per_sample,
-                                                     int32_t* out_minq, int32_t* out_nminq, void* stream)
-{
-    if (!ctx || !batch || !packed || bad_reads_window < 1) return PLAT_ERR_INVALID;
-    const plat_infostats_batch b = *batch;
-    const plat_packed_reads pk = *packed;
-    if (b.n_vars < 0 || b.n_ind < 1 || pk.n_exc < 0) return PLAT_ERR_INVALID;
-    if (b.n_vars == 0) return PLAT_OK;
-    if (!b.var_window || !b.var_pos || !b.var_bam_min || !b.var_bam_max || !b.var_n_added || !b.var_n_removed || !b.var_added ||
-        !b.var_added_off || !b.var_in_genotype || !b.minq_off || !b.good_begin || !b.good_end || !b.bad_begin || !b.bad_end ||
-        !pk.read_src || (pk.n_exc > 0 && (!pk.exc_index || !pk.exc_base || !pk.exc_qual)) || !b.read_off || !b.read_pos || !b.read_end ||
-        !b.read_mapq || !b.read_flags || !b.cigar || !b.cig_off || !out_counts || !out_per_sample || !out_minq || !out_nminq)
-        return PLAT_ERR_INVALID;
-    PLAT_HIP(ctx, hipSetDevice(ctx->device));
-    { PLAT_KT_BEGIN(ctx, PLAT_KT_VARIANT_READ_STATS, (hipStream_t)stream); hipLaunchKernelGGL(plat::k_variant_read_stats_packed, dim3(b.n_vars), dim3(64), 0, (hipStream_t)stream, b, pk,
-                       bad_reads_window, count_only_exact_indel_matches, out_counts, out_per_sample, out_minq, out_nminq); PLAT_KT_END(ctx, PLAT_KT_VARIANT_READ_STATS, (hipStream_t)stream); }
-    PLAT_HIP(ctx, hipGetLastError());
-    return PLAT_OK;
-}
-
-// ---- the loops of INFO ABPV / SbPval / MMLQ on the device (plat_variant_info_batch) -----------------------------------------------------
-namespace plat {
-constexpr int LOGFACT_N = 4096;
-// betaBinomialCDF(k, n, alpha, beta) as its three terms (platypusutils.pyx:267-315): t[1] = logBeta(beta + n - k - 1, alpha + k + 1),
-// t[2] = threeFTwo(k, n, alpha, beta), t[3] = logBeta(alpha, beta) + logBeta(n - k, k + 2) + log(n + 1).  Returns the state word: 1, or 2
-// when a log-factorial lies beyond the table.  (k == n is the caller's: the function returns 1.0 there.)
-__device__ __forceinline__ double cdf_terms(long long k, long long n, long long alpha, long long beta, const double* __restrict__ LF, double* t)
-{
-    const double* LOGI = LF + LOGFACT_N;                                  // LOGI[m - 1] = log((double)m), m = 1 .. 4096
-    auto in = [](long long x) { return x >= 0 && x < LOGFACT_N; };
-    const long long x1 = beta + n - k - 1, y1 = alpha + k + 1, x3 = n - k, y3 = k + 2;
-    if (!in(x1 - 1) || !in(y1 - 1) || !in(x1 + y1 - 1) || !in(alpha - 1) || !in(beta - 1) || !in(alpha + beta - 1) || !in(x3 - 1) || !in(y3 - 1) ||
-        !in(x3 + y3 - 1) || n + 1 < 1 || n + 1 > LOGFACT_N)
-        return 2.0;
-    auto logBeta = [&](long long x, long long y) { return (LF[x - 1] + LF[y - 1]) - LF[x + y - 1]; };
-    const double a_2 = (double)alpha + (double)k + 1.0, a_3 = (double)k - (double)n + 1.0, b_1 = (double)k + 2.0,
-                 b_2 = -(double)beta - (double)n + (double)k + 2.0;
-    double theSum = 1.0, lastTerm = 1.0;
-    const long long m = k - n + 1 < 0 ? -(k - n + 1) : k - n + 1;
-    for (long long i = 1; i <= m; ++i) {
-        const double di = (double)i;
-        const double newTerm = lastTerm * (a_2 + di - 1) * (a_3 + di - 1) / ((b_1 + di - 1) * (b_2 + di - 1));
-        theSum += newTerm;
-        lastTerm = newTerm;
-    }
-    t[1] = logBeta(x1, y1);
-    t[2] = theSum;
-    t[3] = logBeta(alpha, beta) + logBeta(x3, y3) + LOGI[n];              // log((double)(n + 1))
-    return 1.0;
-}
-
-// one wave per variant: lane 0 the two p-values' terms, the wave the median
-__global__ void __launch_bounds__(64)
-k_variant_info(int n_vars, const int64_t* __restrict__ counts, const int64_t* __restrict__ minq_off, const int32_t* __restrict__ minq,
-               const int32_t* __restrict__ n_minq, const double* __restrict__ LF, double* __restrict__ out_terms, int32_t* __restrict__ out_mmlq)
-{
-    const int v = blockIdx.x, lane = threadIdx.x;
-    if (v >= n_vars) return;
-    const int64_t* c = counts + 16ll * v;
-    if (lane == 0) {
-        double* t = out_terms + 8ll * v;
-        // computeAlleleBiasPValue(totalReads = TC_ab, variantReads = TR_ab), vcfutils.pyx:1156-1173
-        const long long total = c[3], var = c[4];
-        t[0] = 0.0; t[1] = 1.0; t[2] = 0.0; t[3] = 0.0;
-        if (!(total > 0 && (double)var / (double)total >= 0.5) && total != 0) {
-            if (var == total) { t[1] = 0.0; }                            // betaBinomialCDF == 1.0: min(1.0, 0.0)
-            else t[0] = cdf_terms(var, total, 20, 20, LF, t);
-        }
-        // computeStrandBiasPValue(nFwdReads = TCF_sb, nRevReads = TCR_sb, nFwdVarReads = NF_sb, nRevVarReads = NR_sb), :1177-1222
-        double* u = t + 4;
-        const long long nF = c[10], nR = c[9], vF = c[6], vR = c[5];
-        u[0] = 0.0; u[1] = 1.0; u[2] = 0.0; u[3] = 0.0;
-        if (!(nF == 0 || nR == 0) && nF + nR > 0 && vF + vR > 0) {
-            const bool useForward = !(nF < nR);
-            const double freq = (double)(useForward ? nF : nR) / (double)(nF + nR);
-            long long alpha, beta;
-            if (freq < 0.5) { alpha = 20; beta = (long long)((double)alpha / freq - (double)alpha); }
-            else if (freq > 0.5) { beta = 20; alpha = (long long)((double)beta * freq / (1.0 - freq)); }
-            else alpha = beta = 20;
-            const long long k = useForward ? vF : vR, n = vF + vR;
-            if (k == n) u[1] = 1.0;                                      // betaBinomialCDF's own early exit
-            else u[0] = cdf_terms(k, n, alpha, beta, LF, u);
-        }
-    }
-    // sorted(values)[n // 2]: the element with n // 2 smaller-or-earlier-equal ones in front of it
-    const int n = n_minq[v];
-    const int32_t* q = minq + minq_off[v];
-    int med = 100;
-    for (int i0 = 0; i0 < n; i0 += 64) {
-        const int i = i0 + lane;
-        const int mine = i < n ? q[i] : 0;
-        int rank = 0;
-        for (int j = 0; j < n; ++j) { const int o = q[j]; rank += (o < mine) || (o == mine && j < i); }
-        const unsigned long long hit = __ballot(i < n && rank == n / 2);
-        if (hit) med = __shfl(mine, (int)__builtin_ctzll(hit), 64);
-    }
-    if (lane == 0) out_mmlq[v] = med;
-}
-}  // namespace plat
-
-PLAT_EXPORT int plat_variant_info_batch(plat_ctx* ctx, int n_vars, const int64_t* counts, const int64_t* minq_off, const int32_t* minq,
-                                        const int32_t* n_minq, double* out_terms, int32_t* out_mmlq, void* stream)
-{
-    if (!ctx || n_vars < 0) return PLAT_ERR_INVALID;
-    if (n_vars == 0) return PLAT_OK;
-    if (!counts || !minq_off || !minq || !n_minq || !out_terms || !out_mmlq) return PLAT_ERR_INVALID;
-    PLAT_HIP(ctx, hipSetDevice(ctx->device));
-    if (!ctx->d_logfact) {
-        // logFactorial as the reference computes it (platypusutils.pyx:178-191: a sum of logs below 15, Stirling's series with pow() above) and
-        // log(m), both with the HOST's libm: the device adds table entries, it never calls a transcendental function for these fields
-        static double lut[2 * plat::LOGFACT_N];
-        static bool made = false;
-        static std::mutex mk;
-        {
-            std::lock_guard<std::mutex> g(mk);
-            if (!made) {
-                for (int x = 0; x < plat::LOGFACT_N; ++x) {
-                    double ans = 0.0;
-                    if (x < 15) for (int i = 1; i <= x; ++i) ans += log((double)i);
-                    else {
-                        const double y = (double)x;
-                        ans = (y * log(y) + log(2.0 * M_PI * y) / 2 - y + (pow(y, -1)) / 12 - (pow(y, -3)) / 360 + (pow(y, -5)) / 1260 - (pow(y, -7)) / 1680 + (pow(y, -9)) / 1188);
-                    }
-                    lut[x] = ans;
-                    lut[plat::LOGFACT_N + x] = log((double)(x + 1));
-                }
-                made = true;
-            }
-        }
-        PLAT_HIP(ctx, hipMalloc(&ctx->d_logfact, sizeof(lut)));
-        PLAT_HIP(ctx, hipMemcpy(ctx->d_logfact, lut, sizeof(lut), hipMemcpyHostToDevice));
-    }
-    { PLAT_KT_BEGIN(ctx, PLAT_KT_VARIANT_INFO, (hipStream_t)stream); hipLaunchKernelGGL(plat::k_variant_info, dim3((unsigned)n_vars), dim3(64), 0, (hipStream_t)stream, n_vars, counts, minq_off, minq, n_minq,
-                       (const double*)ctx->d_logfact, out_terms, out_mmlq); PLAT_KT_END(ctx, PLAT_KT_VARIANT_INFO, (hipStream_t)stream); }
-    PLAT_HIP(ctx, hipGetLastError());
-    return PLAT_OK;
-}
-
-
-// ---- window read slices out of a resident read table (plat_gather_reads) --------------------------------------------------
-namespace plat {
-// Four destination reads per wave, sixteen lanes each: lanes 0-7 of the sixteen move the bases, 8-15 the qualities, 16 bytes at a time
-// from and to any address (global memory takes unaligned 64-bit loads and stores).  A read's copy is a chain of three dependent loads
-// (index -> offsets -> bytes) that a wave waits out whatever its width: with one read per wave (rounds 3-4) the 230 k reads of a chunk of
-// 64 regions were 28 rounds of waves on the chip, 76-85 us for 86 MB; four per wave share each wait.
-__global__ void __launch_bounds__(256)
-k_gather_reads(long long n_dst, const int32_t* __restrict__ src_index, const int64_t* __restrict__ dst_off,
-               const uint8_t* __restrict__ src_seq, const uint8_t* __restrict__ src_qual, const int64_t* __restrict__ src_off,
-               const int32_t* __restrict__ src_pos, const int32_t* __restrict__ src_end, const uint8_t* __restrict__ src_mapq,
-               const int32_t* __restrict__ src_flags, uint8_t* __restrict__ dst_seq, uint8_t* __restrict__ dst_qual,
-               int32_t* __restrict__ dst_pos, int32_t* __restrict__ dst_end, uint8_t* __restrict__ dst_mapq, int32_t* __restrict__ dst_flags)
-{
-    typedef unsigned long long __attribute__((aligned(1))) u64u;
-    const int l16 = threadIdx.x & 15, l8 = l16 & 7;
-    const long long ng = ((long long)gridDim.x * blockDim.x) >> 4;
-    for (long long d = (((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 4); d < n_dst; d += ng) {
-        const int s = src_index[d];
-        const long long so = src_off[s], n = src_off[s + 1] - so, to = dst_off[d];
-        const uint8_t* src = l16 < 8 ? src_seq + so : src_qual + so;
-        uint8_t* dst = l16 < 8 ? dst_seq + to : dst_qual + to;
-        if (n >= 16) {                                                  // pieces of 16 bytes; the last one ends AT the read's end (it may overlap the one before)
-            const long long np = (n + 15) >> 4;
-            for (long long k = l8; k < np; k += 8) {
-                const long long i = k + 1 < np ? 16 * k : n - 16;
-                const unsigned long long a = *(const u64u*)(src + i), c = *(const u64u*)(src + i + 8);
-                *(u64u*)(dst + i) = a; *(u64u*)(dst + i + 8) = c;
-            }
-        } else for (long long i = l8; i < n; i += 8) dst[i] = src[i];
-        if (l16 == 0) { dst_pos[d] = src_pos[s]; dst_end[d] = src_end[s]; dst_mapq[d] = src_mapq[s]; dst_flags[d] = src_flags[s]; }
-    }
-}
-
-// The same from packed sources (plat_gather_reads_packed): sixteen lanes per destination read, each turns 16 packed bytes into the base line
-// AND the quality line (half the bytes in for the same bytes out).  A read with exceptions -- rare -- goes byte by byte through the accessor.
-__global__ void __launch_bounds__(256)
-k_gather_reads_packed(long long n_dst, const int32_t* __restrict__ src_index, const int64_t* __restrict__ dst_off, plat_packed_reads pk,
-                      const int64_t* __restrict__ src_off, const int32_t* __restrict__ src_pos, const int32_t* __restrict__ src_end,
-                      const uint8_t* __restrict__ src_mapq, const int32_t* __restrict__ src_flags, uint8_t* __restrict__ dst_seq,
-                      uint8_t* __restrict__ dst_qual, int32_t* __restrict__ dst_pos, int32_t* __restrict__ dst_end, uint8_t* __restrict__ dst_mapq,
-                      int32_t* __restrict__ dst_flags)
-{
-    typedef unsigned long long __attribute__((aligned(1))) u64u;
-    const int l16 = threadIdx.x & 15;
-    const long long ng = ((long long)gridDim.x * blockDim.x) >> 4;
-    const SrcPacked sp{pk};
-    for (long long d = (((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 4); d < n_dst; d += ng) {
-        const int s = src_index[d];
-        const long long so = src_off[s], n = src_off[s + 1] - so, to = dst_off[d];
-        const ReadPacked rd = sp.read(s, so, n);
-        uint8_t* dseq = dst_seq + to;
-        uint8_t* dqual = dst_qual + to;
-        if (n >= 16 && rd.e0 == rd.e1) {                                // pieces of 16 bytes; the last one ends AT the read's end (it may overlap the one before)
-            const long long np = (n + 15) >> 4;
-            for (long long k = l16; k < np; k += 16) {
-                const long long i = k + 1 < np ? 16 * k : n - 16;
-                const unsigned long long a = *(const u64u*)(rd.p + i), c = *(const u64u*)(rd.p + i + 8);
-                const uint32_t w[4] = {(uint32_t)a, (uint32_t)(a >> 32), (uint32_t)c, (uint32_t)(c >> 32)};
-                uint32_t sq[4], ql[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    sq[q] = __builtin_amdgcn_perm(0u, 0x47544341u, w[q] & 0x03030303u);       // byte selector 0..3 -> 'A' 'C' 'T' 'G'
-                    ql[q] = (w[q] >> 2) & 0x3F3F3F3Fu;
-                }
-                *(u64u*)(dseq + i) = (unsigned long long)sq[0] | ((unsigned long long)sq[1] << 32);
-                *(u64u*)(dseq + i + 8) = (unsigned long long)sq[2] | ((unsigned long long)sq[3] << 32);
-                *(u64u*)(dqual + i) = (unsigned long long)ql[0] | ((unsigned long long)ql[1] << 32);
-                *(u64u*)(dqual + i + 8) = (unsigned long long)ql[2] | ((unsigned long long)ql[3] << 32);
-            }
-        } else for (long long i = l16; i < n; i += 16) { dseq[i] = rd.base((int)i); dqual[i] = rd.qual((int)i); }
-        if (l16 == 0) { dst_pos[d] = src_pos[s]; dst_end[d] = src_end[s]; dst_mapq[d] = src_mapq[s]; dst_flags[d] = src_flags[s]; }
-    }
-}
-}  // namespace plat
-
-PLAT_EXPORT int plat_gather_reads_packed(plat_ctx* ctx, int64_t n_dst, const int32_t* src_index, const int64_t* dst_off, const plat_packed_reads* packed,
-                                         const int64_t* src_off, const int32_t* src_pos, const int32_t* src_end, const uint8_t* src_mapq,
-                                         const int32_t* src_flags, uint8_t* dst_seq, uint8_t* dst_qual, int32_t* dst_pos, int32_t* dst_end,
-                                         uint8_t* dst_mapq, int32_t* dst_flags, void* stream)
-{
-    if (!ctx || n_dst < 0 || !packed || packed->n_exc < 0) return PLAT_ERR_INVALID;
-    if (n_dst == 0) return PLAT_OK;
-    const plat_packed_reads pk = *packed;
-    if (!src_index || !dst_off || !pk.read_src || (pk.n_exc > 0 && (!pk.exc_index || !pk.exc_base || !pk.exc_qual)) || !src_off || !src_pos || !src_end ||
-        !src_mapq || !src_flags || !dst_seq || !dst_qual || !dst_pos || !dst_end || !dst_mapq || !dst_flags)
-        return PLAT_ERR_INVALID;
-    PLAT_HIP(ctx, hipSetDevice(ctx->device));
-    const long long nblk = (n_dst + 15) / 16;                         // 256 threads = 16 reads
-    { PLAT_KT_BEGIN(ctx, PLAT_KT_GATHER_READS, (hipStream_t)stream); hipLaunchKernelGGL(plat::k_gather_reads_packed, dim3((unsigned)(nblk < 65535 * 8 ? nblk : 65535 * 8)), dim3(256), 0, (hipStream_t)stream,
-                       (long long)n_dst, src_index, dst_off, pk, src_off, src_pos, src_end, src_mapq, src_flags, dst_seq, dst_qual, dst_pos, dst_end, dst_mapq,
-                       dst_flags); PLAT_KT_END(ctx, PLAT_KT_GATHER_READS, (hipStream_t)stream); }
-    PLAT_HIP(ctx, hipGetLastError());
-    return PLAT_OK;
-}
-
-PLAT_EXPORT int plat_gather_reads(plat_ctx* ctx, int64_t n_dst, const int32_t* src_index, const int64_t* dst_off,
-                                  const uint8_t* src_seq, const uint8_t* src_qual, const int64_t* src_off, const int32_t* src_pos,
-                                  const int32_t* src_end, const uint8_t* src_mapq, const int32_t* src_flags, uint8_t* dst_seq,
-                                  uint8_t* dst_qual, int32_t* dst_pos, int32_t* dst_end, uint8_t* dst_mapq, int32_t* dst_flags,
-                                  void* stream)
-{
-    if (!ctx || n_dst < 0) return PLAT_ERR_INVALID;
-    if (n_dst == 0) return PLAT_OK;
-    if (!src_index || !dst_off || !src_seq || !src_qual || !src_off || !src_pos || !src_end || !src_mapq || !src_flags || !dst_seq ||
-        !dst_qual || !dst_pos || !dst_end || !dst_mapq || !dst_flags)
-        return PLAT_ERR_INVALID;
-    PLAT_HIP(ctx, hipSetDevice(ctx->device));
-    const long long nblk = (n_dst + 15) / 16;                         // 256 threads = 16 reads
-    { PLAT_KT_BEGIN(ctx, PLAT_KT_GATHER_READS, (hipStream_t)stream); hipLaunchKernelGGL(plat::k_gather_reads, dim3((unsigned)(nblk < 65535 * 8 ? nblk : 65535 * 8)), dim3(256), 0, (hipStream_t)stream, (long long)n_dst,
-                       src_index, dst_off, src_seq, src_qual, src_off, src_pos, src_end, src_mapq, src_flags, dst_seq, dst_qual, dst_pos,
-                       dst_end, dst_mapq, dst_flags); PLAT_KT_END(ctx, PLAT_KT_GATHER_READS, (hipStream_t)stream); }
-    PLAT_HIP(ctx, hipGetLastError());
-    return PLAT_OK;
-}
-
-
-// ---- read tables packed at one byte per base (plat_unpack_reads) ----------------------------------------------------------
-namespace plat {
-// 16 packed bytes per thread: one 128-bit load (two 64-bit ones from any address when the source does not share the outputs' alignment:
-// global memory takes unaligned loads), two 128-bit stores.  The two OUTPUT arrays may start anywhere as long as they share their
-// misalignment `mis` (a read table inside a chunk's blob does): thread t takes the 16-byte line [16 t - mis, 16 t - mis + 16) of them,
-// clipped to [0, n) at the two ends.
-__global__ void __launch_bounds__(256)
-k_unpack_reads(long long n, int mis, int vec, int src_aligned, const uint8_t* __restrict__ packed, uint8_t* __restrict__ out_seq, uint8_t* __restrict__ out_qual)
-{
-    const long long i0 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 16 - mis;
-    if (i0 >= n) return;
-    if (vec && i0 >= 0 && i0 + 16 <= n) {
-        uint32_t w[4];
-        if (src_aligned) { const uint4 v = *(const uint4*)(packed + i0); w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w; }
-        else {
-            const unsigned long long lo = load_u64_bytes(packed + i0), hi = load_u64_bytes(packed + i0 + 8);
-            w[0] = (uint32_t)lo; w[1] = (uint32_t)(lo >> 32); w[2] = (uint32_t)hi; w[3] = (uint32_t)(hi >> 32);
-        }
-        uint32_t sq[4], ql[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const uint32_t code = w[k] & 0x03030303u;
-            sq[k] = __builtin_amdgcn_perm(0u, 0x47544341u, code);           // byte selector 0..3 -> 'A' 'C' 'T' 'G'
-            ql[k] = (w[k] >> 2) & 0x3F3F3F3Fu;
-        }
-        *(uint4*)(out_seq + i0) = make_uint4(sq[0], sq[1], sq[2], sq[3]);
-        *(uint4*)(out_qual + i0) = make_uint4(ql[0], ql[1], ql[2], ql[3]);
-    } else {
-        for (long long i = i0 < 0 ? 0 : i0; i < n && i < i0 + 16; ++i) {
-            const unsigned b = packed[i];
-            out_seq[i] = (uint8_t)((0x47544341u >> (8u * (b & 3u))) & 0xFFu);
-            out_qual[i] = (uint8_t)(b >> 2);
-        }
-    }
-}
-__global__ void __launch_bounds__(256)
-k_unpack_exceptions(long long n_exc, long long n, const int64_t* __restrict__ idx, const uint8_t* __restrict__ eb, const uint8_t* __restrict__ eq,
-                    uint8_t* __restrict__ out_seq, uint8_t* __restrict__ out_qual, uint32_t* __restrict__ codes = nullptr)
-{
-    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n_exc) return;
-    const long long i = idx[k];
-    if (i < 0 || i >= n) return;
-    out_seq[i] = eb[k]; out_qual[i] = eq[k];
-    if (codes) {                                                           // the base's code follows its byte: (ASCII >> 1) & 3
-        const unsigned sh = 2u * (unsigned)(i & 15);
-        atomicAnd(&codes[i >> 4], ~(3u << sh));
-        atomicOr(&codes[i >> 4], (((unsigned)eb[k] >> 1) & 3u) << sh);
-    }
-}
-}  // namespace plat
-
-PLAT_EXPORT int plat_unpack_reads(plat_ctx* ctx, int64_t n_bytes, const uint8_t* packed, uint8_t* out_seq, uint8_t* out_qual,
-                                  int64_t n_exc, const int64_t* exc_index, const uint8_t* exc_base, const uint8_t* exc_qual, void* stream)
-{
-    if (!ctx || n_bytes < 0 || n_exc < 0) return PLAT_ERR_INVALID;
-    if (n_bytes == 0) return PLAT_OK;
-    if (!packed || !out_seq || !out_qual || (n_exc > 0 && (!exc_index || !exc_base || !exc_qual))) return PLAT_ERR_INVALID;
-    PLAT_HIP(ctx, hipSetDevice(ctx->device));
-    // lanes work on 16-byte lines of the OUTPUT arrays: possible when the two share their misalignment (else byte by byte); a source
-    // with another misalignment (a resident table expanded into its place in a chunk's blob) is read with unaligned loads
-    const int m0 = (int)((uintptr_t)packed & 15), m1 = (int)((uintptr_t)out_seq & 15), m2 = (int)((uintptr_t)out_qual & 15);
-    const int vec = m1 == m2, mis = vec ? m1 : 0;                          // (not shared: every thread walks its own 16 bytes)
-    const long long nthr = (n_bytes + mis + 15) / 16;
-    hipLaunchKernelGGL(plat::k_unpack_reads, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (long long)n_bytes,
-                       mis, vec, (int)(m0 == mis), packed, out_seq, out_qual);
-    if (n_exc > 0)
-        hipLaunchKernelGGL(plat::k_unpack_exceptions, dim3((unsigned)((n_exc + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (long long)n_exc,
-                           (long long)n_bytes, exc_index, exc_base, exc_qual, out_seq, out_qual);
-    PLAT_HIP(ctx, hipGetLastError());
-    return PLAT_OK;
-}
-
-
-namespace plat {
-// k_unpack_reads for a list of pieces: blockIdx.y = piece; lanes work on 16-byte lines of the piece's place in the output
-__global__ void __launch_bounds__(256)
-k_unpack_pieces(const plat_unpack_piece* __restrict__ pieces, uint8_t* __restrict__ out_seq, uint8_t* __restrict__ out_qual, int same_base_alignment,
-                uint32_t* __restrict__ codes)
-{
-    // codes (round 6, may be null): the bases again as 2 bits each (A 0, C 1, T 2, G 3 = the packed byte's low bits = (ASCII >> 1) & 3), base i of the
-    // blob at bits 2 (i & 15) of dword i >> 4 -- what plat_candidates_batch_codes compares 32 bases per 64-bit word.  A whole line of 16 bases is one
-    // plain store; the bases of a partial line (a piece's first and last) are OR-ed in, the buffer having been zeroed by the caller.
-    const plat_unpack_piece pc = pieces[blockIdx.y];
-    const uint8_t* packed = pc.src;
-    uint8_t* oseq = out_seq + pc.dst;
-    uint8_t* oqual = out_qual + pc.dst;
-    const long long n = pc.n;
-    const int mis = same_base_alignment ? (int)((uintptr_t)oseq & 15) : 0;
-    const bool srcAligned = (((uintptr_t)packed - (uintptr_t)mis) & 15) == 0 || (((uintptr_t)packed & 15) == (unsigned)mis);
-    const long long lines = (n + mis + 15) / 16;
-    for (long long ln = (long long)blockIdx.x * blockDim.x + threadIdx.x; ln < lines; ln += (long long)gridDim.x * blockDim.x) {
-        const long long i0 = ln * 16 - mis;
-        if (same_base_alignment && i0 >= 0 && i0 + 16 <= n) {
-            uint32_t w[4];
-            if (srcAligned) { const uint4 v = *(const uint4*)(packed + i0); w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w; }
-            else {
-                const unsigned long long lo = load_u64_bytes(packed + i0), hi = load_u64_bytes(packed + i0 + 8);
-                w[0] = (uint32_t)lo; w[1] = (uint32_t)(lo >> 32); w[2] = (uint32_t)hi; w[3] = (uint32_t)(hi >> 32);
-            }
-            uint32_t sq[4], ql[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const uint32_t code = w[k] & 0x03030303u;
-                sq[k] = __builtin_amdgcn_perm(0u, 0x47544341u, code);
-                ql[k] = (w[k] >> 2) & 0x3F3F3F3Fu;
-            }
-            *(uint4*)(oseq + i0) = make_uint4(sq[0], sq[1], sq[2], sq[3]);
-            *(uint4*)(oqual + i0) = make_uint4(ql[0], ql[1], ql[2], ql[3]);
-            if (codes) {
-                uint32_t cw = 0;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    uint32_t t = w[k] & 0x03030303u;
-                    t = (t | (t >> 6)) & 0x000F000Fu;
-                    cw |= ((t | (t >> 12)) & 0xFFu) << (8 * k);
-                }
-                const long long at = pc.dst + i0;                          // blob index of the line's first base
-                if ((at & 15) == 0) codes[at >> 4] = cw;
-                else for (int k = 0; k < 16; ++k) atomicOr(&codes[(at + k) >> 4], ((cw >> (2 * k)) & 3u) << (2 * ((at + k) & 15)));
-            }
-        } else {
-            for (long long i = i0 < 0 ? 0 : i0; i < n && i < i0 + 16; ++i) {
-                const unsigned bb = packed[i];
-                oseq[i] = (uint8_t)((0x47544341u >> (8u * (bb & 3u))) & 0xFFu);
-                oqual[i] = (uint8_t)(bb >> 2);
-                if (codes) atomicOr(&codes[(pc.dst + i) >> 4], (bb & 3u) << (2 * ((pc.dst + i) & 15)));
-            }
-        }
-    }
-}
-}  // namespace plat
-
-static int unpack_pieces(plat_ctx* ctx, int n_pieces, int64_t max_piece_bytes, const plat_unpack_piece* pieces, uint8_t* out_seq, uint8_t* out_qual, uint32_t* out_codes,
-                         int64_t total_bytes, int64_t n_exc, const int64_t* exc_index, const uint8_t* exc_base, const uint8_t* exc_qual, void* stream);
-
-PLAT_EXPORT int plat_unpack_reads_pieces(plat_ctx* ctx, int n_pieces, int64_t max_piece_bytes, const plat_unpack_piece* pieces, uint8_t* out_seq, uint8_t* out_qual,
-                                         int64_t total_bytes, int64_t n_exc, const int64_t* exc_index, const uint8_t* exc_base, const uint8_t* exc_qual, void* stream)
-{
-    return unpack_pieces(ctx, n_pieces, max_piece_bytes, pieces, out_seq, out_qual, nullptr, total_bytes, n_exc, exc_index, exc_base, exc_qual, stream);
-}
-
-PLAT_EXPORT int plat_unpack_reads_pieces_codes(plat_ctx* ctx, int n_pieces, int64_t max_piece_bytes, const plat_unpack_piece* pieces, uint8_t* out_seq, uint8_t* out_qual,
-                                               uint32_t* out_codes, int64_t total_bytes, int64_t n_exc, const int64_t* exc_index, const uint8_t* exc_base,
-                                               const uint8_t* exc_qual, void* stream)
-{
-    if (!out_codes) return PLAT_ERR_INVALID;
-    return unpack_pieces(ctx, n_pieces, max_piece_bytes, pieces, out_seq, out_qual, out_codes, total_bytes, n_exc, exc_index, exc_base, exc_qual, stream);
-}
-
-static int unpack_pieces(plat_ctx* ctx, int n_pieces, int64_t max_piece_bytes, const plat_unpack_piece* pieces, uint8_t* out_seq, uint8_t* out_qual, uint32_t* out_codes,
-                         int64_t total_bytes, int64_t n_exc, const int64_t* exc_index, const uint8_t* exc_base, const uint8_t* exc_qual, void* stream)
-{
-    if (!ctx || n_pieces < 0 || max_piece_bytes < 0 || total_bytes < 0 || n_exc < 0) return PLAT_ERR_INVALID;
-    if (n_pieces == 0) return PLAT_OK;
-    if (!pieces || !out_seq || !out_qual || (n_exc > 0 && (!exc_index || !exc_base || !exc_qual))) return PLAT_ERR_INVALID;
-    PLAT_HIP(ctx, hipSetDevice(ctx->device));
-    // (the code words of partial lines are OR-ed in: the buffer starts as zeros; + 8 words: plat_candidates_batch_codes reads a 64-bit word past the last base)
-    if (out_codes) PLAT_HIP(ctx, hipMemsetAsync(out_codes, 0, ((size_t)(total_bytes + 15) / 16 + 8) * sizeof(uint32_t), (hipStream_t)stream));
-    const int same = ((uintptr_t)out_seq & 15) == ((uintptr_t)out_qual & 15);
-    long long gx = (max_piece_bytes / 16 + 256) / 256;
-    gx = gx < 1 ? 1 : (gx > 1024 ? 1024 : gx);
-    PLAT_EV_TAB(ctx, 0, (hipStream_t)stream);
-    for (int p0 = 0; p0 < n_pieces; p0 += PLAT_GRID_Y_MAX) {      // (gridDim.y holds at most 65 535 pieces: one launch per batch of them)
-        const int np = n_pieces - p0 < PLAT_GRID_Y_MAX ? n_pieces - p0 : PLAT_GRID_Y_MAX;
-        { PLAT_KT_BEGIN(ctx, PLAT_KT_UNPACK_PIECES, (hipStream_t)stream); hipLaunchKernelGGL(plat::k_unpack_pieces, dim3((unsigned)gx, (unsigned)np), dim3(256), 0, (hipStream_t)stream, pieces + p0, out_seq, out_qual, same, out_codes); PLAT_KT_END(ctx, PLAT_KT_UNPACK_PIECES, (hipStream_t)stream); }
-    }
-    PLAT_EV_TAB(ctx, 1, (hipStream_t)stream);
-    ctx->ev_valid_unpack = ctx->profile;
-    if (n_exc > 0)
-        hipLaunchKernelGGL(plat::k_unpack_exceptions, dim3((unsigned)((n_exc + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (long long)n_exc,
-                           (long long)total_bytes, exc_index, exc_base, exc_qual, out_seq, out_qual, out_codes);
-    PLAT_HIP(ctx, hipGetLastError());
-    return PLAT_OK;
-}
-
-// ---- the codes alone, the packed bytes staying where they are (plat_pack_codes_pieces) ------------------------------------------------------
-namespace plat {
-// Before the pass: the code dwords a piece does not fill by itself -- the one holding its first base and the one behind its last, where they are
-// shared with a neighbouring piece or with nothing -- and the 8 words behind the blob's last base start as zeros; everything else is stored whole.
-// (The whole-buffer memset of plat_unpack_reads_pieces_codes was a quarter byte per base written twice.)
-__global__ void __launch_bounds__(256)
-k_codes_edges(const plat_unpack_piece* __restrict__ pieces, int n_pieces, long long total_bytes, uint32_t* __restrict__ codes)
-{
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k < n_pieces) {
-        const plat_unpack_piece pc = pieces[k];
-        if (pc.n > 0) {
-            if (pc.dst & 15) codes[pc.dst >> 4] = 0u;
-            if ((pc.dst + pc.n) & 15) codes[(pc.dst + pc.n) >> 4] = 0u;
-        }
-    } else if (k < n_pieces + 8) codes[(total_bytes + 15) / 16 + (k - n_pieces)] = 0u;
-}
-
-// blockIdx.y = piece; one thread per code dword of the piece's place in the blob (16 bases: one 128-bit load, or two 64-bit ones from a source of
-// another alignment, and one 32-bit store); a dword the piece shares is OR-ed in, once
-__global__ void __launch_bounds__(256)
-k_unpack_pieces_codes(const plat_unpack_piece* __restrict__ pieces, uint32_t* __restrict__ codes)
-{
-    const plat_unpack_piece pc = pieces[blockIdx.y];
-    const uint8_t* packed = pc.src;
-    const long long n = pc.n;
-    if (n <= 0) return;
-    const long long d0 = pc.dst >> 4, d1 = (pc.dst + n + 15) >> 4;
-    const bool srcAligned = (((uintptr_t)packed - (uintptr_t)(pc.dst & 15)) & 15) == 0;
-    for (long long d = d0 + (long long)blockIdx.x * blockDim.x + threadIdx.x; d < d1; d += (long long)gridDim.x * blockDim.x) {
-        const long long i0 = 16 * d - pc.dst;                              // the dword's first base, counted from the piece's
-        if (i0 >= 0 && i0 + 16 <= n) {
-            uint32_t w[4];
-            if (srcAligned) { const uint4 v = *(const uint4*)(packed + i0); w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w; }
-            else {
-                const unsigned long long lo = load_u64_bytes(packed + i0), hi = load_u64_bytes(packed + i0 + 8);
-                w[0] = (uint32_t)lo; w[1] = (uint32_t)(lo >> 32); w[2] = (uint32_t)hi; w[3] = (uint32_t)(hi >> 32);
-            }
-            uint32_t cw = 0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                uint32_t t = w[k] & 0x03030303u;
-                t = (t | (t >> 6)) & 0x000F000Fu;
-                cw |= ((t | (t >> 12)) & 0xFFu) << (8 * k);
-            }
-            codes[d] = cw;
-        } else {
-            uint32_t cw = 0;
-            for (long long i = i0 < 0 ? 0 : i0; i < n && i < i0 + 16; ++i) cw |= ((uint32_t)packed[i] & 3u) << (2 * (int)(i - i0));
-            atomicOr(&codes[d], cw);
-        }
-    }
-}
-
-__global__ void __launch_bounds__(256)
-k_codes_exceptions(long long n_exc, long long n, const int64_t* __restrict__ idx, const uint8_t* __restrict__ eb, uint32_t* __restrict__ codes)
-{
-    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n_exc) return;
-    const long long i = idx[k];
-    if (i < 0 || i >= n) return;
-    const unsigned sh = 2u * (unsigned)(i & 15);                           // the base's code follows its byte: (ASCII >> 1) & 3
-    atomicAnd(&codes[i >> 4], ~(3u << sh));
-    atomicOr(&codes[i >> 4], (((unsigned)eb[k] >> 1) & 3u) << sh);
-}
-}  // namespace plat
-
-PLAT_EXPORT int plat_pack_codes_pieces(plat_ctx* ctx, int n_pieces, int64_t max_piece_bytes, const plat_unpack_piece* pieces, uint32_t* out_codes,
-                                       int64_t total_bytes, int64_t n_exc, const int64_t* exc_index, const uint8_t* exc_base, void* stream)
-{
-    if (!ctx || n_pieces < 0 || max_piece_bytes < 0 || total_bytes < 0 || n_exc < 0) return PLAT_ERR_INVALID;
-    if (n_pieces == 0) return PLAT_OK;
-    if (!pieces || !out_codes || (n_exc > 0 && (!exc_index || !exc_base))) return PLAT_ERR_INVALID;
-    PLAT_HIP(ctx, hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(plat::k_codes_edges, dim3((unsigned)((n_pieces + 8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, pieces, n_pieces, (long long)total_bytes, out_codes);
-    long long gx = (max_piece_bytes / 16 + 256) / 256;
-    gx = gx < 1 ? 1 : (gx > 1024 ? 1024 : gx);
-    PLAT_EV_TAB(ctx, 0, (hipStream_t)stream);
-    for (int p0 = 0; p0 < n_pieces; p0 += PLAT_GRID_Y_MAX) {      // (gridDim.y holds at most 65 535 pieces: one launch per batch of them)
-        const int np = n_pieces - p0 < PLAT_GRID_Y_MAX ? n_pieces - p0 : PLAT_GRID_Y_MAX;
-        { PLAT_KT_BEGIN(ctx, PLAT_KT_UNPACK_PIECES, (hipStream_t)stream); hipLaunchKernelGGL(plat::k_unpack_pieces_codes, dim3((unsigned)gx, (unsigned)np), dim3(256), 0, (hipStream_t)stream, pieces + p0, out_codes); PLAT_KT_END(ctx, PLAT_KT_UNPACK_PIECES, (hipStream_t)stream); }
-    }
-    PLAT_EV_TAB(ctx, 1, (hipStream_t)stream);
-    ctx->ev_valid_unpack = ctx->profile;
-    if (n_exc > 0)
-        hipLaunchKernelGGL(plat::k_codes_exceptions, dim3((unsigned)((n_exc + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (long long)n_exc, (long long)total_bytes,
-                           exc_index, exc_base, out_codes);
-    PLAT_HIP(ctx, hipGetLastError());
-    return PLAT_OK;
-}
-
-// ---- a chunk's read table put together on the device from resident tables (plat_concat_read_tables) ----------------------------------
-namespace plat {
-__device__ __forceinline__ void concat_src(const plat_table_desc&, int, long long, const uint8_t**) {}
-__device__ __forceinline__ void concat_src(const plat_table_src_desc& d, int i, long long r, const uint8_t** dst_src) { dst_src[r] = d.src + d.off[i]; }
-
-// (D = plat_table_src_desc: + the per-read source pointer column of a chunk whose packed bytes are read where they lie)
-template <class D>
-__device__ __forceinline__ void concat_tables_one(const D* __restrict__ desc, int64_t* __restrict__ dst_off, int32_t* __restrict__ dst_pos, int32_t* __restrict__ dst_end,
-                uint8_t* __restrict__ dst_mapq, int32_t* __restrict__ dst_flags, int32_t* __restrict__ dst_cig_off, int16_t* __restrict__ dst_cigar,
-                int32_t* __restrict__ dst_region, const uint8_t** __restrict__ dst_src, long long n_total, long long total_bytes, long long total_pairs)
-{
-    const D d = desc[blockIdx.y];
-    const int stride = gridDim.x * blockDim.x;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < d.n; i += stride) {
-        const long long r = d.first_read + i;
-        dst_off[r] = d.first_byte + d.off[i];
-        concat_src(d, i, r, dst_src);
-        dst_pos[r] = d.pos[i]; dst_end[r] = d.end[i]; dst_mapq[r] = d.mapq[i]; dst_flags[r] = d.flags[i];
-        const int c0 = d.cig_off[i], c1 = d.cig_off[i + 1];
-        dst_cig_off[r] = (int32_t)(d.first_pair + c0);
-        for (int c = c0; c < c1; ++c) {
-            dst_cigar[2 * (d.first_pair + c)] = d.cigar[2 * c];
-            dst_cigar[2 * (d.first_pair + c) + 1] = d.cigar[2 * c + 1];
-        }
-        if (d.scan >= 0) dst_region[r] = d.scan;
-    }
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
-        dst_off[n_total] = total_bytes; dst_cig_off[n_total] = (int32_t)total_pairs;
-        dst_cigar[2 * total_pairs] = 0; dst_cigar[2 * total_pairs + 1] = 0;
-    }
-}
-
-__global__ void __launch_bounds__(256)
-k_concat_tables(const plat_table_desc* __restrict__ desc, int64_t* __restrict__ dst_off, int32_t* __restrict__ dst_pos, int32_t* __restrict__ dst_end,
-                uint8_t* __restrict__ dst_mapq, int32_t* __restrict__ dst_flags, int32_t* __restrict__ dst_cig_off, int16_t* __restrict__ dst_cigar,
-                int32_t* __restrict__ dst_region, long long n_total, long long total_bytes, long long total_pairs)
-{
-    concat_tables_one(desc, dst_off, dst_pos, dst_end, dst_mapq, dst_flags, dst_cig_off, dst_cigar, dst_region, nullptr, n_total, total_bytes, total_pairs);
-}
-
-__global__ void __launch_bounds__(256)
-k_concat_tables_src(const plat_table_src_desc* __restrict__ desc, int64_t* __restrict__ dst_off, int32_t* __restrict__ dst_pos, int32_t* __restrict__ dst_end,
-                    uint8_t* __restrict__ dst_mapq, int32_t* __restrict__ dst_flags, int32_t* __restrict__ dst_cig_off, int16_t* __restrict__ dst_cigar,
-                    int32_t* __restrict__ dst_region, const uint8_t** __restrict__ dst_src, long long n_total, long long total_bytes, long long total_pairs)
-{
-    concat_tables_one(desc, dst_off, dst_pos, dst_end, dst_mapq, dst_flags, dst_cig_off, dst_cigar, dst_region, dst_src, n_total, total_bytes, total_pairs);
-}
-}  // namespace plat
-
-PLAT_EXPORT int plat_concat_read_tables_src(plat_ctx* ctx, int n_tables, int max_reads_per_table, const plat_table_src_desc* desc, int64_t* dst_off, int32_t* dst_pos,
-                                            int32_t* dst_end, uint8_t* dst_mapq, int32_t* dst_flags, int32_t* dst_cig_off, int16_t* dst_cigar,
-                                            int32_t* dst_region, const uint8_t** dst_src, int64_t n_total_reads, int64_t total_bytes, int64_t total_pairs, void* stream)
-{
-    if (!ctx || n_tables < 0 || max_reads_per_table < 0 || n_total_reads < 0) return PLAT_ERR_INVALID;
-    if (!dst_off || !dst_pos || !dst_end || !dst_mapq || !dst_flags || !dst_cig_off || !dst_cigar || !dst_region || !dst_src) return PLAT_ERR_INVALID;
-    if (n_tables < 1 || !desc) return PLAT_ERR_INVALID;
-    PLAT_HIP(ctx, hipSetDevice(ctx->device));
-    unsigned gx = (unsigned)((max_reads_per_table + 255) / 256);
-    gx = gx < 1 ? 1 : (gx > 64 ? 64 : gx);
-    for (int t0 = 0; t0 < n_tables; t0 += PLAT_GRID_Y_MAX) {      // (every batch's first block also writes the table's closing entries: the same values)
-        const int nt = n_tables - t0 < PLAT_GRID_Y_MAX ? n_tables - t0 : PLAT_GRID_Y_MAX;
-        { PLAT_KT_BEGIN(ctx, PLAT_KT_CONCAT_TABLES, (hipStream_t)stream); hipLaunchKernelGGL(plat::k_concat_tables_src, dim3(gx, (unsigned)nt), dim3(256), 0, (hipStream_t)stream, desc + t0, dst_off, dst_pos, dst_end,
-                           dst_mapq, dst_flags, dst_cig_off, dst_cigar, dst_region, dst_src, (long long)n_total_reads, (long long)total_bytes, (long long)total_pairs); PLAT_KT_END(ctx, PLAT_KT_CONCAT_TABLES, (hipStream_t)stream); }
-    }
-    PLAT_HIP(ctx, hipGetLastError());
-    return PLAT_OK;
-}
-
-PLAT_EXPORT int plat_concat_read_tables(plat_ctx* ctx, int n_tables, int max_reads_per_table, const plat_table_desc* desc, int64_t* dst_off, int32_t* dst_pos,
-                                        int32_t* dst_end, uint8_t* dst_mapq, int32_t* dst_flags, int32_t* dst_cig_off, int16_t* dst_cigar,
-                                        int32_t* dst_region, int64_t n_total_reads, int64_t total_bytes, int64_t total_pairs, void* stream)
-{
-    if (!ctx || n_tables < 0 || max_reads_per_table < 0 || n_total_reads < 0) return PLAT_ERR_INVALID;
-    if (!dst_off || !dst_pos || !dst_end || !dst_mapq || !dst_flags || !dst_cig_off || !dst_cigar || !dst_region) return PLAT_ERR_INVALID;
-    if (n_tables < 1 || !desc) return PLAT_ERR_INVALID;
-    PLAT_HIP(ctx, hipSetDevice(ctx->device));
-    unsigned gx = (unsigned)((max_reads_per_table + 255) / 256);
-    gx = gx < 1 ? 1 : (gx > 64 ? 64 : gx);
-    for (int t0 = 0; t0 < n_tables; t0 += PLAT_GRID_Y_MAX) {      // (every batch's first block also writes the table's closing entries: the same values)
-        const int nt = n_tables - t0 < PLAT_GRID_Y_MAX ? n_tables - t0 : PLAT_GRID_Y_MAX;
-        { PLAT_KT_BEGIN(ctx, PLAT_KT_CONCAT_TABLES, (hipStream_t)stream); hipLaunchKernelGGL(plat::k_concat_tables, dim3(gx, (unsigned)nt), dim3(256), 0, (hipStream_t)stream, desc + t0, dst_off, dst_pos, dst_end,
-                           dst_mapq, dst_flags, dst_cig_off, dst_cigar, dst_region, (long long)n_total_reads, (long long)total_bytes, (long long)total_pairs); PLAT_KT_END(ctx, PLAT_KT_CONCAT_TABLES, (hipStream_t)stream); }
-    }
-    PLAT_HIP(ctx, hipGetLastError());
-    return PLAT_OK;
-}
-
-
-// ---- pieces of device memory into one blob (plat_copy_pieces) -----------------------------------------------------------------------------
-namespace plat {
-__global__ void __launch_bounds__(256)
-k_copy_pieces(const plat_unpack_piece* __restrict__ pieces, uint8_t* __restrict__ dst_blob)
-{
-    typedef unsigned long long __attribute__((aligned(1))) u64u;
-    const plat_unpack_piece pc = pieces[blockIdx.y];
-    const uint8_t* src = pc.src;
-    uint8_t* dst = dst_blob + pc.dst;
-    const long long n8 = pc.n & ~7ll;
-    const long long stride = 8ll * gridDim.x * blockDim.x;
-    for (long long i = 8ll * ((long long)blockIdx.x * blockDim.x + threadIdx.x); i < n8; i += stride) *(u64u*)(dst + i) = *(const u64u*)(src + i);
-    if (blockIdx.x == 0) for (long long i = n8 + threadIdx.x; i < pc.n; i += blockDim.x) dst[i] = src[i];
-}
-}  // namespace plat
-
-PLAT_EXPORT int plat_copy_pieces(plat_ctx* ctx, int n_pieces, int64_t max_piece_bytes, const plat_unpack_piece* pieces, uint8_t* dst_blob, void* stream)
-{
-    if (!ctx || n_pieces < 0 || max_piece_bytes < 0) return PLAT_ERR_INVALID;
-    if (n_pieces == 0) return PLAT_OK;
-    if (!pieces || !dst_blob) return PLAT_ERR_INVALID;
-    PLAT_HIP(ctx, hipSetDevice(ctx->device));
-    long long gx = (max_piece_bytes / 8 + 256) / 256;
-    gx = gx < 1 ? 1 : (gx > 256 ? 256 : gx);
-    for (int p0 = 0; p0 < n_pieces; p0 += PLAT_GRID_Y_MAX) {      // (a whole job's regions are one piece each in the exchange: more than gridDim.y holds)
-        const int np = n_pieces - p0 < PLAT_GRID_Y_MAX ? n_pieces - p0 : PLAT_GRID_Y_MAX;
-        { PLAT_KT_BEGIN(ctx, PLAT_KT_COPY_PIECES, (hipStream_t)stream); hipLaunchKernelGGL(plat::k_copy_pieces, dim3((unsigned)gx, (unsigned)np), dim3(256), 0, (hipStream_t)stream, pieces + p0, dst_blob); PLAT_KT_END(ctx, PLAT_KT_COPY_PIECES, (hipStream_t)stream); }
-    }
     PLAT_HIP(ctx, hipGetLastError());
     return PLAT_OK;
 }

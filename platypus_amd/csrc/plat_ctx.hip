@@ -144,16 +144,18 @@ PLAT_EXPORT int plat_kernel_timer_only(plat_ctx* ctx, int id) {
 
 PLAT_EXPORT int plat_kernel_times(plat_ctx* ctx, double* out_ms, int64_t* out_launches) {
     if (!ctx || !out_ms || !out_launches) return PLAT_ERR_INVALID;
+    hipError_t bad = hipSuccess;                                         // the first failed wait: the pairs behind it are not waited for (their times are dropped), every pair is still recycled, then it is returned
     for (int k = 0; k < ctx->kt_pending_n; ++k) {
         plat_ctx::KtPair& q = ctx->kt_pending[k];
-        if (q.closed) {
-            PLAT_HIP(ctx, hipEventSynchronize(q.b));
+        if (q.closed && bad == hipSuccess) {
+            bad = hipEventSynchronize(q.b);
             float ms = 0.f;
-            if (hipEventElapsedTime(&ms, q.a, q.b) == hipSuccess) { out_ms[q.id] += (double)ms; out_launches[q.id] += 1; }
+            if (bad == hipSuccess && hipEventElapsedTime(&ms, q.a, q.b) == hipSuccess) { out_ms[q.id] += (double)ms; out_launches[q.id] += 1; }
         }
         ctx->kt_pool[ctx->kt_pool_n++] = q.a; ctx->kt_pool[ctx->kt_pool_n++] = q.b;
     }
     ctx->kt_pending_n = 0; ctx->kt_open = -1;
+    PLAT_HIP(ctx, bad);
     return PLAT_OK;
 }
 

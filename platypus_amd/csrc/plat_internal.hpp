@@ -71,7 +71,10 @@ static inline void plat_kt_mark(plat_ctx* ctx, int id, hipStream_t st, bool end)
         if (ctx->kt_pending_n >= plat_ctx::KT_PENDING) return;               // (too many unresolved pairs: this launch is not timed -- and takes no events)
         hipEvent_t a = nullptr, b = nullptr;
         if (ctx->kt_pool_n >= 2) { a = ctx->kt_pool[--ctx->kt_pool_n]; b = ctx->kt_pool[--ctx->kt_pool_n]; }
-        else if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return;
+        else {
+            if (hipEventCreate(&a) != hipSuccess) return;
+            if (hipEventCreate(&b) != hipSuccess) { (void)hipEventDestroy(a); return; }
+        }
         ctx->kt_pending[ctx->kt_pending_n] = {id, a, b, false};
         ctx->kt_open = ctx->kt_pending_n++;
         (void)hipEventRecord(a, st);
@@ -103,7 +106,3 @@ static inline int plat_reserve(plat_ctx* ctx, plat_scratch& s, size_t bytes) {
     s.cap = want;
     return PLAT_OK;
 }
-
-// checkAndTrimRead over a PLAT_READS_PACKED table (k_read_qc_packed, plat_candidates.hip): the first step of plat_read_buffers_packed_batch
-int plat_read_qc_packed_launch(plat_ctx* ctx, const plat_read_buffers_packed_in& in, const plat_readqc_options& options, int32_t* out_ok,
-                               int32_t* out_reason, hipStream_t stream);

@@ -1,11 +1,174 @@
 // plat_readbuf.hip -- the read buffers of fetched streams (plat_read_buffers_batch, include/platypus_mi355x.h):
-// checkAndTrimRead (k_read_qc, plat_candidates.hip) in place, then bamReadBuffer.addReadToBuffer's split into `reads` / `badReads`
+// checkAndTrimRead (k_read_qc, below) in place, then bamReadBuffer.addReadToBuffer's split into `reads` / `badReads`
 // (cwindow.pyx:560-595) as a stable per-stream partition, then, optionally, the two buffers gathered into device tables.
 // plat_read_buffers_packed_batch: the same for PLAT_READS_PACKED tables (k_read_qc_packed, then the same split and a gather of the packed
 // bytes).
 #include "plat_internal.hpp"
 #include "wave_tiles.hpp"
 
+// ------------------------------------------------------------------------------------------------
+// Read QC / trimming: checkAndTrimRead (cwindow.pyx:332-481).  One lane per read; `theLastRead` of
+// bamReadBuffer.addReadToBuffer (:560-595) is simply the previous read of the same stream and only its position, length
+// and mate position are looked at, so the reads of a stream are independent of each other.
+namespace plat {
+
+// The qualities of one read as checkAndTrimRead sees them: get(i) (a signed char, as the reference's `char*`) and trim(i) (quality 0).
+// ASCII tables: the raw phred bytes.
+struct QualBytes {
+    int8_t* q;
+    __device__ __forceinline__ int get(int i) const { return q[i]; }
+    __device__ __forceinline__ void trim(int i) const { q[i] = 0; }
+};
+
+// PLAT_READS_PACKED tables: the quality bits of the packed byte, or the exception's quality where the byte is listed.  e0 / e1: the
+// read's exceptions (exc_index[e0, e1) lie inside the read's bytes); a read without exceptions never touches the exception arrays.
+struct QualPacked {
+    uint8_t* p;                       // the read's first byte
+    int64_t at;                       // its index in the blob
+    const int64_t* idx;
+    uint8_t* eq;
+    int64_t e0, e1;
+    __device__ __forceinline__ int64_t find(int i) const {
+        if (e0 == e1) return -1;
+        int64_t lo = e0, hi = e1;
+        while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (idx[mid] < at + i) lo = mid + 1; else hi = mid; }
+        return lo < e1 && idx[lo] == at + i ? lo : -1;
+    }
+    __device__ __forceinline__ int get(int i) const { const int64_t k = find(i); return k >= 0 ? (int)(int8_t)eq[k] : (int)(p[i] >> 2); }
+    __device__ __forceinline__ void trim(int i) const { p[i] &= 3; const int64_t k = find(i); if (k >= 0) eq[k] = 0; }
+};
+
+// ... and a read of such a table without exceptions (most of them): the quality bits only, loops as tight as QualBytes'
+struct QualPackedPlain {
+    uint8_t* p;
+    __device__ __forceinline__ int get(int i) const { return p[i] >> 2; }
+    __device__ __forceinline__ void trim(int i) const { p[i] &= 3; }
+};
+
+// checkAndTrimRead on read r over either storage: the one copy of the verdicts and the trimming
+template <class Q>
+__device__ __forceinline__ void read_qc_one(const plat_readqc_batch& b, const plat_readqc_options& o, int r, const Q& q, int32_t* __restrict__ ok,
+                                            int32_t* __restrict__ reason)
+{
+    const int rlen = (int)(b.read_off[r + 1] - b.read_off[r]);
+    const int f = b.read_flags[r];
+    const bool paired = f & 1, proper = f & 2, unmapped = f & 4, mateUnmapped = f & 8, reverse = f & 16, mateReverse = f & 32;
+    const int ins = b.insert_size[r];
+    const int absIns = ins < 0 ? -ins : ins;
+    int why = -1, qcfail = 1;
+    if (f & 256) why = 7;                                                            // secondary alignment, :337-339
+    else if ((int)b.read_mapq[r] < o.min_map_qual) why = 6;                          // :341-344
+    else {
+        int nBelow = 0;
+        for (int i = 0; i < rlen; ++i) nBelow += q.get(i) < o.min_base_qual;
+        if (rlen - nBelow < o.min_good_qual_bases) why = 0;                          // :354-357
+        else if (unmapped) why = 1;                                                  // :360-363
+        else if (o.filter_mate_unmapped && paired && mateUnmapped) { why = 2; qcfail = 0; }          // :367-371 (no QCFail flag)
+        else if (o.filter_mate_distant && paired && (b.chrom_id[r] != b.mate_chrom_id[r] || !proper)) { why = 3; qcfail = 0; }
+        else if (o.filter_small_insert && paired && ins != 0 && absIns < rlen) why = 4;
+        else if (o.filter_duplicates) {                                              // :389-409
+            if (f & 1024) why = 5;
+            else if (r > 0 && b.stream_of[r - 1] == b.stream_of[r] && b.read_pos[r] == b.read_pos[r - 1] &&
+                     rlen == (int)(b.read_off[r] - b.read_off[r - 1])) {
+                if (!paired || b.mate_pos[r - 1] == b.mate_pos[r]) why = 5;
+            }
+        }
+    }
+    if (why >= 0) {
+        if (qcfail) b.read_flags[r] = f | 512;
+        ok[r] = 0; reason[r] = why;
+        return;
+    }
+    if (!reverse) {                                                                  // low-quality tail, :415-421
+        for (int i = 1; i <= rlen; ++i) {
+            if (i < o.trim_read_flank || q.get(rlen - i) < 5) q.trim(rlen - i); else break;
+        }
+    } else {
+        for (int i = 0; i < rlen; ++i) {
+            if (i < o.trim_read_flank || q.get(i) < 5) q.trim(i); else break;
+        }
+    }
+    if (o.trim_overlapping == 1 && paired && absIns > 0 && !reverse && mateReverse && absIns < 2 * rlen) {   // :438-440
+        int lim = (2 * rlen - ins) + 1;
+        if (lim > rlen) lim = rlen;
+        for (int i = 1; i <= lim; ++i) q.trim(rlen - i);
+    }
+    if (o.trim_adapter == 1 && paired && absIns > 0 && absIns < rlen) {               // :445-452
+        if (reverse) { for (int i = 1; i < rlen - absIns + 1; ++i) q.trim(rlen - i); }
+        else { for (int i = absIns; i < rlen; ++i) q.trim(i); }
+    }
+    if (o.trim_soft_clipped == 1) {                                                   // :462-479 (only M and I advance the cursor)
+        int index = 0;
+        for (int c = b.cig_off[r]; c < b.cig_off[r + 1]; ++c) {
+            const int op = b.cigar[2 * c], len = b.cigar[2 * c + 1];
+            if (op == 0 || op == 1) index += len;
+            else if (op == 4) for (int j = 0; j < len && index < rlen; ++j) q.trim(index++);
+        }
+    }
+    ok[r] = 1; reason[r] = -1;
+}
+
+__global__ void __launch_bounds__(64)
+k_read_qc(plat_readqc_batch b, plat_readqc_options o, int32_t* __restrict__ ok, int32_t* __restrict__ reason)
+{
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= b.n_reads) return;
+    read_qc_one(b, o, r, QualBytes{(int8_t*)b.read_qual + b.read_off[r]}, ok, reason);
+}
+
+// The same on PLAT_READS_PACKED bytes: the read's exceptions by two lower bounds of its byte range in exc_index
+__global__ void __launch_bounds__(64)
+k_read_qc_packed(plat_readqc_batch b, plat_readqc_options o, uint8_t* __restrict__ packed, int64_t n_exc, const int64_t* __restrict__ exc_index,
+                 uint8_t* __restrict__ exc_qual, int32_t* __restrict__ ok, int32_t* __restrict__ reason)
+{
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= b.n_reads) return;
+    const int64_t a = b.read_off[r], z = b.read_off[r + 1];
+    int64_t e0 = 0, e1 = 0;
+    if (n_exc > 0) {
+        int64_t lo = 0, hi = n_exc;
+        while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (exc_index[mid] < a) lo = mid + 1; else hi = mid; }
+        e0 = lo; hi = n_exc;
+        while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (exc_index[mid] < z) lo = mid + 1; else hi = mid; }
+        e1 = lo;
+    }
+    if (e0 == e1) read_qc_one(b, o, r, QualPackedPlain{packed + a}, ok, reason);
+    else read_qc_one(b, o, r, QualPacked{packed + a, a, exc_index, exc_qual, e0, e1}, ok, reason);
+}
+
+}  // namespace plat
+
+PLAT_EXPORT int plat_read_qc_batch(plat_ctx* ctx, const plat_readqc_batch* batch, const plat_readqc_options* options,
+                                   int32_t* out_ok, int32_t* out_reason, void* stream)
+{
+    if (!ctx || !batch || !options) return PLAT_ERR_INVALID;
+    const plat_readqc_batch b = *batch;
+    if (b.n_reads < 0) return PLAT_ERR_INVALID;
+    if (b.n_reads == 0) return PLAT_OK;
+    if (!b.read_qual || !b.read_off || !b.read_pos || !b.read_mapq || !b.read_flags || !b.chrom_id || !b.mate_chrom_id ||
+        !b.insert_size || !b.mate_pos || !b.cigar || !b.cig_off || !b.stream_of || !out_ok || !out_reason)
+        return PLAT_ERR_INVALID;
+    PLAT_HIP(ctx, hipSetDevice(ctx->device));
+    PLAT_LAUNCH(ctx, PLAT_KT_READ_QC, stream, plat::k_read_qc, dim3((unsigned)((b.n_reads + 63) / 64)), dim3(64), 0, b, *options,
+                       out_ok, out_reason);
+    PLAT_HIP(ctx, hipGetLastError());
+    return PLAT_OK;
+}
+
+// (plat_read_buffers_packed_batch: the packed table's checkAndTrimRead; arguments checked there)
+static int plat_read_qc_packed_launch(plat_ctx* ctx, const plat_read_buffers_packed_in& in, const plat_readqc_options& options, int32_t* out_ok,
+                               int32_t* out_reason, hipStream_t stream)
+{
+    const plat_readqc_batch& b = in.qc;
+    if (b.n_reads == 0) return PLAT_OK;
+    PLAT_LAUNCH(ctx, PLAT_KT_READ_QC, stream, plat::k_read_qc_packed, dim3((unsigned)((b.n_reads + 63) / 64)), dim3(64), 0, b, options,
+                       in.read_packed, in.n_exc, in.exc_index, in.exc_qual, out_ok, out_reason);
+    PLAT_HIP(ctx, hipGetLastError());
+    return PLAT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The split of the verdicts into `reads` / `badReads` and the gather of the two buffers.
 namespace plat {
 constexpr int SPLIT_THREADS = 512;                       // 8 waves per stream
 constexpr int SPLIT_WAVES = SPLIT_THREADS / 64;

@@ -31,6 +31,7 @@
 #include <math.h>
 
 #include "plat_internal.hpp"
+#include "wave_tiles.hpp"
 
 namespace plat {
 
@@ -52,21 +53,6 @@ __device__ __forceinline__ int sb_type(int nrem, int nadd) {          // variant
     return 4;
 }
 
-// exclusive scan over the threads of a workgroup (up to 16 waves); total in *tot (LDS scratch of 16 ints)
-__device__ __forceinline__ int sb_block_scan(int v, int* wsum, int* tot) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const int y = __shfl_up(x, d, 64); if (lane >= d) x += y; }
-    if (lane == 63) wsum[w] = x;
-    __syncthreads();
-    int base = 0;
-    for (int k = 0; k < w; ++k) base += wsum[k];
-    if (threadIdx.x == blockDim.x - 1) *tot = base + x;
-    __syncthreads();
-    return base + x - v;
-}
-
 struct SbRegion {                                  // per-region LDS state of k_sb_variants
     unsigned long long key[SB_CAP];                // pos << 32 | type << 28 | nrem
     int id[SB_CAP];                                // first-record id (the dictionary's insertion order), then: rank in the first sort
@@ -74,7 +60,7 @@ struct SbRegion {                                  // per-region LDS state of k_
     unsigned short perm[SB_CAP];                   // sorted position -> element
     unsigned char head[SB_CAP], keep[SB_CAP];
     int list[SB_CAP];
-    int wsum[16], tot, nIndel, addedUsed, status, nKept;
+    int wsum[16], nIndel, addedUsed, status, nKept;
     // the Python-2 dictionaries of the candidate generator, replayed when an order depends on them (sb_dict_order)
     int dId[SB_DICT_CAP];                          // first-record ids of ALL distinct records of the scan, ascending = insertion order
     int dHash[SB_DICT_CAP];                        // hash(Variant) narrowed to a C int (variant.pxd:31); before that: scratch of the sort
@@ -130,7 +116,7 @@ __device__ __forceinline__ int sb_py2_variant_hash(unsigned long long nameHash, 
 //  * the slot order of the finished table (a scan) is the next table's insertion order.
 // owner: 8192 words; step: one byte per key; ord: out (and the old table's order in between); tmp: n entries.  n <= SB_DICT_CAP.
 __device__ void sb_py2_dict_order(int n, const int* __restrict__ H, unsigned* owner, unsigned char* step, unsigned short* ord, unsigned short* tmp,
-                                  int* wsum, int* tot, int* flag)
+                                  int* wsum, int* flag)
 {
     const int tid = threadIdx.x, nthr = blockDim.x;
     int size = 8, m = 0;                                               // m keys are in the table (ord[0..m): its slot order)
@@ -174,7 +160,8 @@ __device__ void sb_py2_dict_order(int n, const int* __restrict__ H, unsigned* ow
             const int per = (size + nthr - 1) / nthr, s0 = tid * per, s1 = min(size, s0 + per);
             int cnt = 0;
             for (int i = s0; i < s1; ++i) cnt += owner[i] != 0xFFFFFFFFu;
-            int at = sb_block_scan(cnt, wsum, tot);
+            int total;
+            int at = block_excl_scan<SB_THREADS>(cnt, wsum, total);
             for (int i = s0; i < s1; ++i) if (owner[i] != 0xFFFFFFFFu) { const int p = (int)owner[i]; tmp[at++] = (unsigned short)(p < m ? (int)ord[p] : p); }
         }
         __syncthreads();
@@ -358,11 +345,10 @@ k_sb_variants(SbIn in, plat_stage_b_out out, const int32_t* __restrict__ mtab)
         const int per = (n + SB_THREADS - 1) / SB_THREADS, r0 = tid * per, r1 = min(n, r0 + per);
         int cnt = 0;
         for (int r = r0; r < r1; ++r) cnt += R.keep[r];
-        int at = sb_block_scan(cnt, R.wsum, &R.tot);
+        int at = block_excl_scan<SB_THREADS>(cnt, R.wsum, nk);
         for (int r = r0; r < r1; ++r) if (R.keep[r]) R.list[at++] = R.perm[r];
     }
     __syncthreads();
-    nk = R.tot;
     //  (b) two survivors that compare equal
     for (int k = tid + 1; k < nk; k += SB_THREADS) if (pass == 0 && R.key[R.list[k]] == R.key[R.list[k - 1]]) atomicOr(&R.status, 2);
     if (nk > b.cap_vars) atomicOr(&R.status, 5);                      // (bit 2: a capacity of the caller, not an exception)
@@ -411,7 +397,8 @@ k_sb_variants(SbIn in, plat_stage_b_out out, const int32_t* __restrict__ mtab)
             for (int i = tid; i < n1; i += SB_THREADS) atomicAdd(&bcnt[(R.dHash[i] - lo) >> sh], 1);
             __syncthreads();
             const int mine = bcnt[tid];
-            const int ex = sb_block_scan(mine, R.wsum, &R.tot);
+            int total;
+            const int ex = block_excl_scan<SB_THREADS>(mine, R.wsum, total);
             bstart[tid] = ex;
             bcnt[tid] = 0;
             __syncthreads();
@@ -453,21 +440,22 @@ k_sb_variants(SbIn in, plat_stage_b_out out, const int32_t* __restrict__ mtab)
 #endif
         unsigned* owner = (unsigned*)R.key;                               // 8192 words = key, id, pos, nrem, nadd, supp, remc
         unsigned char* step = (unsigned char*)R.addo;                    // one byte per key (addo, bmin: 8 KB)
-        sb_py2_dict_order(n1, R.dHash, owner, step, R.dOrd, R.dScr, R.wsum, &R.tot, &R.dN2);
+        sb_py2_dict_order(n1, R.dHash, owner, step, R.dOrd, R.dScr, R.wsum, &R.dN2);
 #ifdef PLAT_SB_TIMING
         const long long tq3 = wall_clock64();
 #endif
         // the sample's dictionary walked in its order: the keys that pass enter the second dictionary in that order
+        int passed;
         {
             const int per = (n1 + SB_THREADS - 1) / SB_THREADS, r0 = tid * per, r1 = min(n1, r0 + per);
             int cnt = 0;
             for (int r = r0; r < r1; ++r) cnt += R.dCand[R.dOrd[r]] != 0;
-            int at = sb_block_scan(cnt, R.wsum, &R.tot);
+            int at = block_excl_scan<SB_THREADS>(cnt, R.wsum, passed);
             for (int r = r0; r < r1; ++r) if (R.dCand[R.dOrd[r]] && at < SB_CAP) { R.dP2[at] = R.dOrd[r]; R.dId[at] = R.dHash[R.dOrd[r]]; ++at; }
         }
         __syncthreads();
-        const int m2 = min(R.tot, SB_CAP);
-        sb_py2_dict_order(m2, R.dId, owner, step, R.dO2, R.dS2, R.wsum, &R.tot, &R.dN2);
+        const int m2 = min(passed, SB_CAP);
+        sb_py2_dict_order(m2, R.dId, owner, step, R.dO2, R.dS2, R.wsum, &R.dN2);
         // rank of every candidate in the second dictionary's order: candidate -> rank in dOrd (free now)
         for (int r = tid; r < m2; r += SB_THREADS) R.dOrd[R.dCand[R.dP2[R.dO2[r]]] - 1] = (unsigned short)r;
         __syncthreads();
@@ -718,22 +706,6 @@ static __device__ void sb_one_window(const plat_stage_b_in& b, const plat_stage_
     sc[0] = flags; sc[1] = nHaps; sc[2] = nReads; sc[3] = (int)hapBytes; sc[4] = (int)readBytes; sc[5] = maxLen; sc[6] = 0; sc[7] = 0;
 }
 
-
-// exclusive scan of a 64-bit value over the 256 threads of a workgroup, total in *tot
-__device__ __forceinline__ long long sb_block_scan64(long long v, long long* wsum, long long* tot) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    long long x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const long long y = __shfl_up(x, d, 64); if (lane >= d) x += y; }
-    if (lane == 63) wsum[w] = x;
-    __syncthreads();
-    long long base = 0;
-    for (int k = 0; k < w; ++k) base += wsum[k];
-    if (threadIdx.x == blockDim.x - 1) *tot = base + x;
-    __syncthreads();
-    return base + x - v;
-}
-
 // one workgroup per region: its windows, one per thread
 __global__ void __launch_bounds__(256)
 k_sb_windows(SbIn in, plat_stage_b_out out)
@@ -750,7 +722,7 @@ __global__ void __launch_bounds__(256)
 k_sb_prefix(SbIn in, plat_stage_b_out out)
 {
     const plat_stage_b_in& b = in.b;
-    __shared__ long long wsum[4], tot, carry[7];
+    __shared__ long long wsum[4], carry[7];
     __shared__ int mx[3];
     const int g = blockIdx.x, tid = threadIdx.x;
     const int32_t* hdr = out.hdr + 8 * g;
@@ -771,7 +743,8 @@ k_sb_prefix(SbIn in, plat_stage_b_out out)
         }
         long long* pf = k < nW ? sb_prefix(b, out, t) : nullptr;
         for (int q = 0; q < 7; ++q) {
-            const long long ex = sb_block_scan64(v[q], wsum, &tot);
+            long long tot;
+            const long long ex = block_excl_scan<256>(v[q], wsum, tot);
             if (pf) pf[q] = carry[q] + ex;
             __syncthreads();
             if (tid == 0) carry[q] += tot;
@@ -1132,14 +1105,14 @@ PLAT_EXPORT int plat_stage_b_batch(plat_ctx* ctx, const plat_stage_b_in* batch, 
         PLAT_HIP(ctx, hipFuncSetAttribute((const void*)plat::k_sb_variants, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(plat::SbRegion)));
         ctx->sb_attr_set = true;
     }
-    { PLAT_KT_BEGIN(ctx, PLAT_KT_SB_VARIANTS, st); hipLaunchKernelGGL(plat::k_sb_variants, dim3((unsigned)b.n_regions), dim3(plat::SB_THREADS), sizeof(plat::SbRegion), st, in, o,
-                       (const int32_t*)ctx->merge_tab.ptr); PLAT_KT_END(ctx, PLAT_KT_SB_VARIANTS, st); }
-    { PLAT_KT_BEGIN(ctx, PLAT_KT_SB_WINDOWS, st); hipLaunchKernelGGL(plat::k_sb_windows, dim3((unsigned)b.n_regions), dim3(256), 0, st, in, o); PLAT_KT_END(ctx, PLAT_KT_SB_WINDOWS, st); }
-    { PLAT_KT_BEGIN(ctx, PLAT_KT_SB_HAPS_RANK, st); hipLaunchKernelGGL(plat::k_sb_haps_rank, dim3(48, (unsigned)b.n_regions), dim3(256), 0, st, in, o); PLAT_KT_END(ctx, PLAT_KT_SB_HAPS_RANK, st); }
-    { PLAT_KT_BEGIN(ctx, PLAT_KT_SB_PREFIX, st); hipLaunchKernelGGL(plat::k_sb_prefix, dim3((unsigned)b.n_regions), dim3(256), 0, st, in, o); PLAT_KT_END(ctx, PLAT_KT_SB_PREFIX, st); }
-    { PLAT_KT_BEGIN(ctx, PLAT_KT_SB_SCAN, st); hipLaunchKernelGGL(plat::k_sb_scan, dim3(1), dim3(64), 0, st, in, o); PLAT_KT_END(ctx, PLAT_KT_SB_SCAN, st); }
-    { PLAT_KT_BEGIN(ctx, PLAT_KT_SB_HAPS_WRITE, st); hipLaunchKernelGGL(plat::k_sb_haps_write, dim3(48, (unsigned)b.n_regions), dim3(256), 0, st, in, o); PLAT_KT_END(ctx, PLAT_KT_SB_HAPS_WRITE, st); }
-    { PLAT_KT_BEGIN(ctx, PLAT_KT_SB_READS, st); hipLaunchKernelGGL(plat::k_sb_reads, dim3(12, (unsigned)b.n_regions), dim3(256), 0, st, in, o); PLAT_KT_END(ctx, PLAT_KT_SB_READS, st); }
+    PLAT_LAUNCH(ctx, PLAT_KT_SB_VARIANTS, st, plat::k_sb_variants, dim3((unsigned)b.n_regions), dim3(plat::SB_THREADS), sizeof(plat::SbRegion), in, o,
+                       (const int32_t*)ctx->merge_tab.ptr);
+    PLAT_LAUNCH(ctx, PLAT_KT_SB_WINDOWS, st, plat::k_sb_windows, dim3((unsigned)b.n_regions), dim3(256), 0, in, o);
+    PLAT_LAUNCH(ctx, PLAT_KT_SB_HAPS_RANK, st, plat::k_sb_haps_rank, dim3(48, (unsigned)b.n_regions), dim3(256), 0, in, o);
+    PLAT_LAUNCH(ctx, PLAT_KT_SB_PREFIX, st, plat::k_sb_prefix, dim3((unsigned)b.n_regions), dim3(256), 0, in, o);
+    PLAT_LAUNCH(ctx, PLAT_KT_SB_SCAN, st, plat::k_sb_scan, dim3(1), dim3(64), 0, in, o);
+    PLAT_LAUNCH(ctx, PLAT_KT_SB_HAPS_WRITE, st, plat::k_sb_haps_write, dim3(48, (unsigned)b.n_regions), dim3(256), 0, in, o);
+    PLAT_LAUNCH(ctx, PLAT_KT_SB_READS, st, plat::k_sb_reads, dim3(12, (unsigned)b.n_regions), dim3(256), 0, in, o);
     PLAT_HIP(ctx, hipGetLastError());
     return PLAT_OK;
 }

@@ -1,4 +1,5 @@
-// wave_tiles.hpp -- device-only pieces the front ends share: the wave and workgroup scans, and for the line front ends (plat_sourcevcf.hip,
+// wave_tiles.hpp -- device-only pieces the kernel files share: the wave and workgroup scans (wave_incl_scan, block_excl_scan: the hot path's
+// too -- candidate merge, k_sb_variants and k_sb_prefix of stage B, the assembler; block_scan_inplace), and for the line front ends (plat_sourcevcf.hip,
 // plat_tabix.hip; plat_fasta.hip takes the geometry, the scans and the masks of a loaded word) the tile geometry, a word's newline mask, the rank of a byte among a tile table's marks and the hand-out of a tile's
 // marked bytes to the lanes of a wave.  A byte stream is cut into tiles of TILE_BYTES = 64 aligned 16-byte words, one word per lane of a
 // wave; a table of marks holds 16 bits per word, and next to it goes a table of the tiles' running mark counts ([tiles + 1]).
@@ -21,6 +22,22 @@ template <class T> __device__ __forceinline__ T wave_incl_scan(T v, int lane)
         if (lane >= d) v += u;
     }
     return v;
+}
+
+// exclusive prefix of v over the THREADS threads of a workgroup; every thread gets the total in a register (s_wave: THREADS / 64 entries
+// of LDS).  Two barriers; every thread calls it.
+template <int THREADS, class T> __device__ __forceinline__ T block_excl_scan(T v, T* s_wave, T& total)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const T incl = wave_incl_scan(v, lane);
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    T before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < THREADS / 64; ++w) { const T s = s_wave[w]; if (w < wave) before += s; all += s; }
+    __syncthreads();                                                    // (s_wave is rewritten by the next call)
+    total = all;
+    return before + incl - v;
 }
 
 // a[0 .. n) to its exclusive prefix sums in place, by all THREADS threads of one workgroup (s_wave: THREADS / 64 entries of LDS); returns

@@ -186,6 +186,39 @@ def test_walks_in_the_slice_equal_walks_in_lds(eng, golden_dir):
     assert out["4"] == out[""] and out["8"] == out[""] and out["12"] == out[""] and sum(len(v) for v in out[""]) > 300
 
 
+def many_path_tile(n_events, seed):
+    """One donor with n_events events 26 .. 40 bases apart -- SNPs, every fifth an insertion of 1 .. 8 bases -- read end to end by reads of
+    100 bases every 4 bases: each event is one bubble start with one finished path, so the tile yields n_events paths of unequal lengths."""
+    rng = np.random.default_rng(seed)
+    B = b"ACGT"
+    gaps = rng.integers(26, 41, n_events)
+    at = (200 + np.cumsum(gaps)).tolist()
+    ref = bytes(rng.choice(list(B), at[-1] + 200).tolist())
+    d = bytearray(ref)
+    for i in reversed(range(n_events)):
+        p = at[i]
+        if i % 5 == 4:
+            d[p:p] = bytes(rng.choice(list(B), int(rng.integers(1, 9))).tolist())
+        else:
+            d[p] = [b for b in B if b != ref[p]][i % 3]
+    d = bytes(d)
+    seqs = [d[q:q + 100] for q in range(0, len(d) - 100, 4)]
+    return dict(ref=ref, ref_start=1000, assem_start=1100, assem_end=1000 + len(ref) - 100, seqs=seqs, quals=[bytes([35]) * 100] * len(seqs))
+
+
+def test_tiles_of_more_than_64_paths_equal_the_oracle(eng, oracle):
+    """The variants are extracted one finished path per thread, their slots from scans over the paths: up to 64 paths are the first wave's
+    alone, more take the workgroup's scan (wave_tiles.hpp, block_excl_scan) with paths in two and three waves, the last wave part full.
+    63 / 64 / 65 / 70 / 150 paths on both sides of that seam, beside a small tile."""
+    regs = [many_path_tile(n, 600 + n) for n in (63, 64, 65, 70, 150, 3)]
+    got = eng.assemble(regs, kmer_size=15, min_qual=20, min_weight=40, no_cycles=0)
+    for r, g in zip(regs, got):
+        exp, _ = oracle.assemble(r["ref"], r["ref_start"], r["assem_start"], r["assem_end"], r["seqs"], r["quals"], 15, 20, 40, 0)
+        assert g == exp
+    assert [len(g) for g in got] == [63, 64, 65, 70, 150, 3]
+    assert len({len(a) for _, _, a in got[3]}) > 2                                # (paths of unequal lengths: SNPs and insertions)
+
+
 def test_a_dozen_regions_per_workgroup_equal_the_oracle(eng, oracle):
     """The LDS path leaves the L1 invalidate out of the phase boundaries where only plainly stored words are read back (a workgroup
     barrier is enough inside a CU) and keeps it where words updated by L2 atomics are read by plain loads (once per region, before the

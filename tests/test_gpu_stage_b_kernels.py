@@ -205,6 +205,25 @@ def test_sort_merge_and_filter_rules(eng):
     assert int(out["var_pos"][0, out["hdr"][0, 1] - 1]) == 600
 
 
+def _thinned_region(n=200):
+    """n SNPs three bases apart; the first ten and every third of the rest are seen in one read only (below minReads = 2)."""
+    ref = R.synth_ref(1000, 19)
+    cands = [(120 + 3 * i, 1, b"A" if ref[120 + 3 * i] != ord("A") else b"C", 1 if i < 10 or i % 3 == 0 else 2) for i in range(n)]
+    return R.region(ref, cands, rlen=100), [int(c[3] >= 2) for c in cands]
+
+
+def test_survivors_of_more_than_one_wave_with_gaps_in_the_first(eng):
+    """The survivors are listed in order by a scan over the workgroup's threads, one sorted candidate a thread (wave_tiles.hpp,
+    block_excl_scan): 200 candidates in four waves, the filter drops 28 of the first 64 and other counts of the later waves, so every
+    wave's survivors start behind an offset that is not a multiple of 64."""
+    reg, keep = _thinned_region()
+    per_wave = [sum(keep[i:i + 64]) for i in range(0, 200, 64)]
+    assert per_wave == [36, 43, 43, 5]
+    out, exp = run(eng, [reg], R.options(minReads=2, maxVariants=8), R.caps(cap_vars=256, cap_windows=256), name="filter, survivors over waves")
+    assert out["hdr"][0, :2].tolist() == [0, sum(keep)]
+    assert out["var_pos"][0, :sum(keep)].tolist() == [120 + 3 * i for i in range(200) if keep[i]]
+
+
 def test_equal_variants_from_different_placements_widen_the_bam_range(eng):
     """Two reads report one deletion at two places of a run LONGER than a normalisation window (rlen + 1 on either side): both walk to the
     run's left end, but the placement further left cannot see the run's right end and stops at its own window's end, so the two equal
