@@ -431,6 +431,36 @@ cdef extern from "platypus_mi355x.h":
         int64_t* status
         int32_t* why
     int plat_bam_route_batch(plat_ctx* ctx, const plat_bam_route_in* inp, const plat_bam_route_out* out, void* stream) nogil
+    # broken mates: the mate coordinates of kept records, the mates of a second-round fetch (platypusutils.pyx:522-559)
+    enum:
+        PLAT_MATES_COORDS
+        PLAT_MATES_FETCH
+    ctypedef struct plat_bam_mates_in:
+        int32_t n_streams
+        int32_t n_records
+        int32_t mode
+        int32_t _pad
+        const uint8_t* data
+        int64_t data_len
+        const int64_t* rec_off
+        const int64_t* rec_limit
+        const int32_t* stream_begin
+        const int32_t* want_tid
+        const int32_t* lo
+        const int32_t* hi
+    ctypedef struct plat_bam_mates_out:
+        int64_t cap_records
+        int64_t cap_bytes
+        int32_t* coords
+        int32_t* coord_begin
+        uint8_t* out_data
+        int64_t* out_rec_off
+        int32_t* out_rec_len
+        int32_t* out_mpos
+        int32_t* out_begin
+        int64_t* status
+        int64_t* need_bytes
+    int plat_bam_mates_batch(plat_ctx* ctx, const plat_bam_mates_in* inp, const plat_bam_mates_out* out, void* stream) nogil
     # candidate alleles from source VCF lines (variantutils.py:72-159,168-197 on the device)
     ctypedef struct plat_source_variants_in:
         int32_t n_regions
@@ -976,6 +1006,35 @@ cdef extern from "platypus_caller_bamfile.h":
     int plat_call_bam_files(plat_caller* c, plat_bamfile* const* files, int n_files, const plat_bam_call_region* regions, int n_regions,
                             plat_caller_options* options, const plat_caller_qc_options* qc, char** out_text, size_t* out_len,
                             plat_fetched_region_info* info, plat_caller_stats* stats) nogil
+    ctypedef struct plat_bam_mate_query:
+        int32_t tid
+        int32_t _pad
+        int64_t start
+        int64_t end
+    ctypedef struct plat_bam_mates:
+        int32_t n_coords
+        int32_t n_queries
+        const plat_bam_mate_query* queries
+        plat_bam_file_records mates
+    ctypedef struct plat_bam_mates_plan:
+        int32_t n_regions
+        int32_t n_files
+        const plat_bam_mates* units
+        const int32_t* loaded
+        int64_t coords
+        int64_t queries
+        int64_t chunks
+        int64_t records_looked_at
+        int64_t records_kept
+        int64_t device_calls
+        int64_t input_bytes
+        double seconds
+    int plat_bam_files_mates_plan(plat_bamfile* const* files, int n_files, const plat_bam_call_region* regions, int n_regions,
+                                  const plat_bam_fetch_plan* fetch_plan, const plat_caller_options* options, plat_bam_mates_plan** plan) nogil
+    void plat_bam_mates_plan_free(plat_bam_mates_plan* plan) nogil
+    int plat_call_bam_files_mates(plat_caller* c, plat_bamfile* const* files, int n_files, const plat_bam_call_region* regions, int n_regions,
+                                  plat_caller_options* options, const plat_caller_qc_options* qc, char** out_text, size_t* out_len,
+                                  plat_fetched_region_info* info, plat_caller_stats* stats) nogil
 
 
 cdef extern from "platypus_caller_fasta.h":

@@ -58,8 +58,33 @@
  * their symbols included (PLAT_CALLER_HOST_INDEX=1 answers the index queries on the host: plat_bam_files_fetch_plan then needs no device).
  *
  * Broken mates (options.assemble && options.assembleBrokenPairs, platypusutils.pyx:522-559 and :617-654: a second round of fetches for
- * the mates of improper pairs) are not fetched: plat_call_bam_files returns PLAT_ERR_UNSUPPORTED with a message for that pair of options.
- * With either option 0 the reference fetches none and the call is complete.
+ * the mates of improper pairs) are fetched by plat_bam_files_mates_plan and handed on by plat_call_bam_files_mates:
+ *
+ *   plat_bam_files_mates_plan   round one, one device batch for the call: the fetch plan's chunks uploaded and inflated,
+ *                          plat_bam_find_records, plat_bam_mates_batch(PLAT_MATES_COORDS): every kept record with
+ *                          !(flag & 0x2) || (flag & 0x4) || (flag & 0x8) and mtid != -1 gives (mtid, mpos), QC playing no part.  A region
+ *                          whose kept records, summed over the files, reach options.maxReads is dropped by the call before any mate is
+ *                          fetched (:538-541): it gets no second round.  On the host, per file and region: the coordinates sorted by
+ *                          (contig name bytewise, mtid, mpos) and merged as mergeQueries merges them (:690-707: a query [s, e) grows to
+ *                          mpos + 1 while the name is equal, mpos - e < 10000 and mpos - s < 100000).  A query is fetched by NAME: its tid
+ *                          is plat_bam_file_tid(name), its window max(s - 1, 0) .. e.  Round two: ONE plat_index_query batch per file for
+ *                          all its queries, the chunks cut, then one device batch: inflate, plat_bam_find_records,
+ *                          plat_bam_mates_batch(PLAT_MATES_FETCH) -- a record is a broken mate when mtid == the region's tid and
+ *                          start <= mpos <= end with loadBAMData's arguments, both ends inclusive -- and one read-back of the kept
+ *                          records.  A record that two queries return is kept twice, as the reference appends it twice.  Per (region,
+ *                          file) the mates are ordered by mate position, equal positions in fetch order (query, then record):
+ *                          sortBrokenMates (cwindow.pyx:761-766) as fastcaller.py states it
+ *   plat_call_bam_files_mates   plat_call_bam_files with that plan: with assemble && assembleBrokenPairs the fetch plan, the mates plan,
+ *                          then plat_call_bgzf_regions (a sample's broken_mates are its file's) or plat_call_bgzf_regions_rg (a file's
+ *                          broken_mates, routed by RG as its fetched records are); stats.input_bytes then includes the second round's
+ *                          compressed bytes.  With either option 0 it IS plat_call_bam_files: the same text and no added launch.
+ *
+ * plat_call_bam_files itself still returns PLAT_ERR_UNSUPPORTED with a message for that pair of options.
+ * Refused by the mates plan, the caller staying usable: a coordinate with mpos < 0, for which nothing in the reference tree defines the
+ * region string (PLAT_ERR_BAD_INPUT, naming region, file and record); an mtid outside the file's header (PLAT_ERR_BAD_INPUT); everything
+ * the index query, the inflate and the record walk refuse (naming region, file, and query where there is one); a device library without
+ * plat_bam_mates_batch (PLAT_ERR_UNSUPPORTED, naming the symbol).
+ * Known cost: round one is inflated for the mates plan and again inside the BGZF call.
  * Not handled: CRAM, CSI indexes, file I/O, region files, the CG-tag convention for long CIGARs, fileCaching and locks.
  */
 #ifndef PLATYPUS_CALLER_BAMFILE_H
@@ -148,6 +173,39 @@ void plat_bam_fetch_plan_free(plat_bam_fetch_plan* plan);
 int plat_call_bam_files(plat_caller* c, plat_bamfile* const* files, int n_files, const plat_bam_call_region* regions, int n_regions,
                         plat_caller_options* options, const plat_caller_qc_options* qc, char** out_text, size_t* out_len,
                         plat_fetched_region_info* info, plat_caller_stats* stats);
+
+/* One query of the second round: the contig by name (the first of equal names) and [start, end) as mergeQueries leaves them. */
+typedef struct plat_bam_mate_query {
+    int32_t tid, _pad;
+    int64_t start, end;
+} plat_bam_mate_query;
+
+/* The broken mates of one file for one region. */
+typedef struct plat_bam_mates {
+    int32_t n_coords;                    /* kept first-round records that gave a mate coordinate */
+    int32_t n_queries;
+    const plat_bam_mate_query* queries;  /* [n_queries] in fetch order */
+    plat_bam_file_records mates;         /* in mate-position order; records (without rec_len) is what plat_bgzf_sample.broken_mates takes */
+} plat_bam_mates;
+
+typedef struct plat_bam_mates_plan {
+    int32_t n_regions, n_files;
+    const plat_bam_mates* units;         /* [n_regions * n_files]: region k, file f at k * n_files + f */
+    const int32_t* loaded;               /* [n_regions] 0: the region reached maxReads in round one and has no second round */
+    int64_t coords, queries, chunks, records_looked_at, records_kept, device_calls, input_bytes;     /* chunks, records and compressed bytes: the second round's */
+    double seconds;
+} plat_bam_mates_plan;
+
+/* fetch_plan: plat_bam_files_fetch_plan's for the same files and regions.  options: maxReads is read.  Freed with plat_bam_mates_plan_free;
+ * the plan does not outlive the files. */
+int plat_bam_files_mates_plan(plat_bamfile* const* files, int n_files, const plat_bam_call_region* regions, int n_regions,
+                              const plat_bam_fetch_plan* fetch_plan, const plat_caller_options* options, plat_bam_mates_plan** plan);
+void plat_bam_mates_plan_free(plat_bam_mates_plan* plan);
+
+/* As plat_call_bam_files, the broken mates fetched (see above). */
+int plat_call_bam_files_mates(plat_caller* c, plat_bamfile* const* files, int n_files, const plat_bam_call_region* regions, int n_regions,
+                              plat_caller_options* options, const plat_caller_qc_options* qc, char** out_text, size_t* out_len,
+                              plat_fetched_region_info* info, plat_caller_stats* stats);
 
 #ifdef __cplusplus
 }

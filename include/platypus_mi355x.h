@@ -844,6 +844,55 @@ typedef struct plat_bam_route_out {
 
 int plat_bam_route_batch(plat_ctx* ctx, const plat_bam_route_in* in, const plat_bam_route_out* out, void* stream);
 
+/* ---- broken mates: the mates of improper pairs ------------------------------------------------------------------
+ * Replaces  the two record loops of loadBAMData's broken-mate fetch  platypusutils.pyx:522-533 / :617-627 (which kept record gives a
+ * mate coordinate) and :555-559 / :646-654 (which record of a second-round fetch is a broken mate), over the output of
+ * plat_bam_find_records: data (data_len bytes + PLAT_BLOB_PAD), rec_off / rec_limit, stream_begin [n_streams + 1] on the device.
+ * n_records bounds stream_begin[n_streams] (it may be the find's capacity: the host need not have read a count).  csrc/mate_rule.hpp
+ * holds the rule for host and device.  Fixed fields count from a record's refID and lie at any alignment: flag uint16 at 14, next_refID
+ * (mtid) int32 at 20, next_pos (mpos) int32 at 24.
+ *
+ * PLAT_MATES_COORDS  a record gives (mtid, mpos) when (!(flag & 0x2) || (flag & 0x4) || (flag & 0x8)) && mtid != -1.  Output: coords
+ *     [2 * cap_records], the pairs of stream after stream in record order, back to back; coord_begin [n_streams + 1].  A negative mpos is
+ *     written as it is (the host refuses it).  want_tid / lo / hi are not read.
+ * PLAT_MATES_FETCH   a record of stream s is a broken mate when mtid == want_tid[s] && lo[s] <= mpos <= hi[s] (loadBAMData's chromID,
+ *     start and end, both ends inclusive).  Output: out_data [cap_bytes + PLAT_BLOB_PAD], 16-byte aligned: the kept records' bytes from
+ *     refID through rec_limit back to back, PLAT_BLOB_PAD zero bytes behind the last; out_rec_off / out_rec_len / out_mpos [cap_records];
+ *     out_begin [n_streams + 1].  A record two streams return is copied twice.
+ *
+ * status [4] (device): {0 or the error, the lowest offending stream or -1, records kept, records looked at}; need_bytes [1] (may be
+ * NULL): the bytes all kept records take.  More kept records than cap_records, or more bytes than cap_bytes, is PLAT_ERR_OVERFLOW
+ * naming the lowest stream with a record that does not fit: nothing is written behind a capacity (no pad either), coord_begin /
+ * out_begin are clamped to cap_records, status[2] and need_bytes still hold the full counts, and the caller can size its buffers and
+ * call again (n_records and data_len always suffice).  A record with rec_off < 0, rec_limit > data_len, or fewer than 32 bytes
+ * (or more than 2^31 - 1) refuses its stream (PLAT_ERR_BAD_INPUT, which wins over an overflow): that record is left out, the other
+ * streams are not touched by it.  A stream_begin that is no partition of [0, n_records] from 0 is status {PLAT_ERR_INVALID, -1, 0, 0}
+ * and every begin 0.  Invalid arguments (a NULL pointer, a negative count, an unknown mode, out_data not 16-byte aligned) return
+ * PLAT_ERR_INVALID and nothing is enqueued.
+ * Three kernels (count: a lane per record, a workgroup per 256 records; scan: one workgroup over the tiles' sums; write: the slots by a
+ * workgroup scan, the copy a wave per record with aligned 16-byte stores), the tile sums in the context's scratch; no wait, nothing
+ * traps.                                                                                                                          */
+#define PLAT_MATES_COORDS 0
+#define PLAT_MATES_FETCH 1
+
+typedef struct plat_bam_mates_in {
+    int32_t n_streams, n_records, mode, _pad;
+    const uint8_t* data; int64_t data_len;
+    const int64_t* rec_off; const int64_t* rec_limit;
+    const int32_t* stream_begin;
+    const int32_t* want_tid; const int32_t* lo; const int32_t* hi;       /* [n_streams], PLAT_MATES_FETCH */
+} plat_bam_mates_in;
+
+typedef struct plat_bam_mates_out {
+    int64_t cap_records, cap_bytes;
+    int32_t* coords; int32_t* coord_begin;                               /* PLAT_MATES_COORDS */
+    uint8_t* out_data; int64_t* out_rec_off; int32_t* out_rec_len; int32_t* out_mpos; int32_t* out_begin;       /* PLAT_MATES_FETCH */
+    int64_t* status;
+    int64_t* need_bytes;
+} plat_bam_mates_out;
+
+int plat_bam_mates_batch(plat_ctx* ctx, const plat_bam_mates_in* in, const plat_bam_mates_out* out, void* stream);
+
 /* ---- candidate alleles from source VCF lines ---------------------------------------------------------------------
  * Replaces  VariantCandidateReader.Variants   src/python/variantutils.py:72-159   (the loop over the lines a tabix fetch returned: ALT
  *           split at commas, the size test, SNP / MNP / indel trimming) with  isValidVcfLine  :168-197  and the tabix proxy's

@@ -174,7 +174,9 @@ def call_variants_bam_files(opts):
             for f in opts.sourceFile:
                 with open(f, "rb") as data, open(f + ".tbi", "rb") as tbi:
                     source.append((data.read(), nc.open_index(tbi.read(), "tbi")))
-        text = nc.call_bam_files(files, rr, opts, source_files=source) if rr else ""
+        # (--assemble 1 with --assembleBrokenPairs 1: the mates of improper pairs are fetched too; every other combination is call_bam_files)
+        mates = int(getattr(opts, "assemble", 0)) and int(getattr(opts, "assembleBrokenPairs", 0))
+        text = (nc.call_bam_files_mates if mates else nc.call_bam_files)(files, rr, opts, source_files=source) if rr else ""
         for _, index in source or []:
             index.close()
         dt = time.time() - t0

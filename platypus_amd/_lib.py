@@ -138,6 +138,21 @@ class BamRouteOut(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("rec_off", "rec_limit", "out_begin", "rec_sample", "status", "why")]
 
 
+class BamMatesIn(C.Structure):
+    """plat_bam_mates_in."""
+    _fields_ = [("n_streams", C.c_int32), ("n_records", C.c_int32), ("mode", C.c_int32), ("_pad", C.c_int32), ("data", C.c_void_p), ("data_len", C.c_int64)] + \
+               [(k, C.c_void_p) for k in ("rec_off", "rec_limit", "stream_begin", "want_tid", "lo", "hi")]
+
+
+class BamMatesOut(C.Structure):
+    """plat_bam_mates_out."""
+    _fields_ = [("cap_records", C.c_int64), ("cap_bytes", C.c_int64)] + \
+               [(k, C.c_void_p) for k in ("coords", "coord_begin", "out_data", "out_rec_off", "out_rec_len", "out_mpos", "out_begin", "status", "need_bytes")]
+
+
+MATES_COORDS, MATES_FETCH = 0, 1
+
+
 class SourceVariantsIn(C.Structure):
     _fields_ = [("n_regions", C.c_int32), ("maxSize", C.c_int32), ("longHaps", C.c_int32), ("_pad", C.c_int32), ("text", C.c_void_p),
                 ("text_len", C.c_int64), ("text_off", C.c_void_p), ("name_hash", C.c_void_p)]
@@ -334,6 +349,7 @@ SIGNATURES = {
     "plat_bgzf_deflate_batch": (C.c_int, [C.c_void_p, C.POINTER(BgzfDeflateIn), C.POINTER(BgzfDeflateOut), C.c_void_p]),
     "plat_bam_find_records": (C.c_int, [C.c_void_p, C.POINTER(BamFindIn), C.POINTER(BamFindOut), C.c_void_p]),
     "plat_bam_route_batch": (C.c_int, [C.c_void_p, C.POINTER(BamRouteIn), C.POINTER(BamRouteOut), C.c_void_p]),
+    "plat_bam_mates_batch": (C.c_int, [C.c_void_p, C.POINTER(BamMatesIn), C.POINTER(BamMatesOut), C.c_void_p]),
     "plat_source_variants_batch": (C.c_int, [C.c_void_p, C.POINTER(SourceVariantsIn), C.POINTER(SourceVariantsOut), C.c_void_p]),
     "plat_tabix_fetch_batch": (C.c_int, [C.c_void_p, C.POINTER(TabixFetchIn), C.POINTER(TabixFetchOut), C.c_void_p]),
     "plat_tabix_index_batch": (C.c_int, [C.c_void_p, C.POINTER(TabixIndexIn), C.POINTER(TabixIndexOut), C.c_void_p]),
@@ -359,7 +375,7 @@ ADDED_LATER = ("plat_read_buffers_batch", "plat_read_buffers_packed_batch", "pla
                "plat_bam_route_batch", "plat_source_variants_batch", "plat_tabix_fetch_batch", "plat_refcall_coverage_batch", "plat_refcov_lds_reads",
                "plat_bgzf_deflate_batch", "plat_tabix_index_batch", "plat_index_query_batch", "plat_fasta_fetch_batch", "plat_fasta_tile_bytes",
                "plat_concat_read_tables_src", "plat_pack_codes_pieces", "plat_candidates_batch_packed", "plat_gather_reads_packed",
-               "plat_variant_read_stats_packed_batch")
+               "plat_variant_read_stats_packed_batch", "plat_bam_mates_batch")
 
 _lib = None
 

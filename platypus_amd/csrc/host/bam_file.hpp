@@ -426,21 +426,19 @@ CALLER_EXPORT int plat_bam_files_fetch_plan(plat_bamfile* const* files, int n_fi
 }
 CALLER_EXPORT void plat_bam_fetch_plan_free(plat_bam_fetch_plan* plan) { delete static_cast<plat_bam_fetch_plan_impl*>(plan); }
 
-CALLER_EXPORT int plat_call_bam_files(plat_caller* c, plat_bamfile* const* files, int n_files, const plat_bam_call_region* regions, int n_regions,
-                                      plat_caller_options* options, const plat_caller_qc_options* qc, char** out_text, size_t* out_len,
-                                      plat_fetched_region_info* info, plat_caller_stats* stats)
+namespace plathost {
+
+// plat_call_bam_files and plat_call_bam_files_mates (bam_mates.hpp): the plan, the fetch plan, one tid per region, then the BGZF call on
+// those structures.  mates(P, X, &units): PLAT_OK with units NULL (no broken mates) or the [n_regions * n_files] units of a mates plan
+// (their second round's compressed bytes in *mateBytes), made once the fetch plan stands.
+template <class Mates>
+inline int callBamFilesWith(plat_caller* c, const char* entry, plat_bamfile* const* files, int n_files, const plat_bam_call_region* regions, int n_regions,
+                            plat_caller_options* options, const plat_caller_qc_options* qc, char** out_text, size_t* out_len,
+                            plat_fetched_region_info* info, plat_caller_stats* stats, Mates&& mates)
 {
-    if (!c || !options || !out_text || !out_len || !bamFilesOk(files, n_files, c) || n_regions < 0 || (n_regions > 0 && !regions)) return PLAT_ERR_INVALID;
-    *out_text = nullptr; *out_len = 0;
-    for (int k = 0; k < n_regions; ++k) if (!regions[k].chrom) return PLAT_ERR_INVALID;
-    SourceLinesGuard sourceGuard(c);                                       // (whichever way this call ends; the BGZF call behind it holds its own)
-    if (options->assemble && options->assembleBrokenPairs) {
-        c->lastError = "plat_call_bam_files: assemble=1 with assembleBrokenPairs=1 asks for the mates of improper pairs, a second round of fetches this entry point does not make";
-        return PLAT_ERR_UNSUPPORTED;
-    }
     plat_bam_plan_impl P;
     plat_bam_fetch_plan_impl X;
-    int rc = guardedEntry(c, "plat_call_bam_files", [&] {
+    int rc = guardedEntry(c, entry, [&] {
         const int r = makeBamPlan(files, n_files, P);
         return r != PLAT_OK ? r : makeBamFetchPlan(files, n_files, regions, n_regions, X);
     });
@@ -454,12 +452,15 @@ CALLER_EXPORT int plat_call_bam_files(plat_caller* c, plat_bamfile* const* files
             if (ft.tid < 0) continue;
             if (first < 0) { first = f; tid[(size_t)k] = ft.tid; }
             else if (ft.tid != tid[(size_t)k]) {
-                c->lastError = "plat_call_bam_files: region " + std::to_string(k) + " (" + regions[k].chrom + "): file " + std::to_string(first) + " has the contig as tid " +
+                c->lastError = std::string(entry) + ": region " + std::to_string(k) + " (" + regions[k].chrom + "): file " + std::to_string(first) + " has the contig as tid " +
                                std::to_string(tid[(size_t)k]) + ", file " + std::to_string(f) + " as tid " + std::to_string(ft.tid) + "; one call takes one tid per region";
                 return PLAT_ERR_UNSUPPORTED;
             }
         }
     }
+    const plat_bam_mates* M = nullptr;
+    long long mateBytes = 0;
+    if ((rc = mates(P, X, &M, &mateBytes)) != PLAT_OK) return rc;
     if (P.mode == PLAT_BAM_FILES_PRESPLIT) {
         const int nS = P.n_samples;
         std::vector<plat_bgzf_sample> units((size_t)n_regions * (size_t)nS);
@@ -470,6 +471,7 @@ CALLER_EXPORT int plat_call_bam_files(plat_caller* c, plat_bamfile* const* files
                 plat_bgzf_sample& u = units[(size_t)k * nS + s];
                 memset(&u, 0, sizeof u);
                 u.n_chunks = ft.n_chunks; u.chunks = ft.chunks;
+                if (M) u.broken_mates = M[(size_t)k * n_files + P.sample_file[s]].mates.records;
             }
             plat_bgzf_region& r = R[(size_t)k];
             memset(&r, 0, sizeof r);
@@ -477,22 +479,45 @@ CALLER_EXPORT int plat_call_bam_files(plat_caller* c, plat_bamfile* const* files
             r.dev_contig_seq = regions[k].dev_contig_seq; r.tid = tid[(size_t)k]; r.itr_beg = X.F[(size_t)k * n_files].itr_beg; r.itr_end = X.F[(size_t)k * n_files].itr_end;
             r.samples = units.data() + (size_t)k * nS;
         }
-        return plat_call_bgzf_regions(c, R.data(), n_regions, nS, P.sample_names, options, qc, out_text, out_len, info, stats);
-    }
-    std::vector<plat_bgzf_file> units((size_t)n_regions * (size_t)n_files);
-    std::vector<plat_bgzf_rg_region> R((size_t)n_regions);
-    for (int k = 0; k < n_regions; ++k) {
-        for (int f = 0; f < n_files; ++f) {
-            const plat_bam_fetch& ft = X.F[(size_t)k * n_files + f];
-            plat_bgzf_file& u = units[(size_t)k * n_files + f];
-            memset(&u, 0, sizeof u);
-            u.n_chunks = ft.n_chunks; u.chunks = ft.chunks;
+        rc = plat_call_bgzf_regions(c, R.data(), n_regions, nS, P.sample_names, options, qc, out_text, out_len, info, stats);
+    } else {
+        std::vector<plat_bgzf_file> units((size_t)n_regions * (size_t)n_files);
+        std::vector<plat_bgzf_rg_region> R((size_t)n_regions);
+        for (int k = 0; k < n_regions; ++k) {
+            for (int f = 0; f < n_files; ++f) {
+                const plat_bam_fetch& ft = X.F[(size_t)k * n_files + f];
+                plat_bgzf_file& u = units[(size_t)k * n_files + f];
+                memset(&u, 0, sizeof u);
+                u.n_chunks = ft.n_chunks; u.chunks = ft.chunks;
+                if (M) u.broken_mates = M[(size_t)k * n_files + f].mates;
+            }
+            plat_bgzf_rg_region& r = R[(size_t)k];
+            memset(&r, 0, sizeof r);
+            r.chrom = regions[k].chrom; r.start = regions[k].start; r.end = regions[k].end; r.contig_seq = regions[k].contig_seq; r.contig_len = regions[k].contig_len;
+            r.dev_contig_seq = regions[k].dev_contig_seq; r.tid = tid[(size_t)k]; r.itr_beg = X.F[(size_t)k * n_files].itr_beg; r.itr_end = X.F[(size_t)k * n_files].itr_end;
+            r.files = units.data() + (size_t)k * n_files;
         }
-        plat_bgzf_rg_region& r = R[(size_t)k];
-        memset(&r, 0, sizeof r);
-        r.chrom = regions[k].chrom; r.start = regions[k].start; r.end = regions[k].end; r.contig_seq = regions[k].contig_seq; r.contig_len = regions[k].contig_len;
-        r.dev_contig_seq = regions[k].dev_contig_seq; r.tid = tid[(size_t)k]; r.itr_beg = X.F[(size_t)k * n_files].itr_beg; r.itr_end = X.F[(size_t)k * n_files].itr_end;
-        r.files = units.data() + (size_t)k * n_files;
+        rc = plat_call_bgzf_regions_rg(c, R.data(), n_regions, n_files, &P.groups, P.n_samples, P.sample_names, options, qc, out_text, out_len, info, stats);
     }
-    return plat_call_bgzf_regions_rg(c, R.data(), n_regions, n_files, &P.groups, P.n_samples, P.sample_names, options, qc, out_text, out_len, info, stats);
+    if (rc == PLAT_OK && stats) stats->input_bytes += mateBytes;
+    return rc;
+}
+
+}  // namespace plathost
+
+CALLER_EXPORT int plat_call_bam_files(plat_caller* c, plat_bamfile* const* files, int n_files, const plat_bam_call_region* regions, int n_regions,
+                                      plat_caller_options* options, const plat_caller_qc_options* qc, char** out_text, size_t* out_len,
+                                      plat_fetched_region_info* info, plat_caller_stats* stats)
+{
+    if (!c || !options || !out_text || !out_len || !bamFilesOk(files, n_files, c) || n_regions < 0 || (n_regions > 0 && !regions)) return PLAT_ERR_INVALID;
+    *out_text = nullptr; *out_len = 0;
+    for (int k = 0; k < n_regions; ++k) if (!regions[k].chrom) return PLAT_ERR_INVALID;
+    SourceLinesGuard sourceGuard(c);                                       // (whichever way this call ends; the BGZF call behind it holds its own)
+    if (options->assemble && options->assembleBrokenPairs) {
+        c->lastError = "plat_call_bam_files: assemble=1 with assembleBrokenPairs=1 asks for the mates of improper pairs, a second round of fetches this entry point does not make "
+                       "(plat_call_bam_files_mates makes it)";
+        return PLAT_ERR_UNSUPPORTED;
+    }
+    return callBamFilesWith(c, "plat_call_bam_files", files, n_files, regions, n_regions, options, qc, out_text, out_len, info, stats,
+                            [](const plat_bam_plan_impl&, const plat_bam_fetch_plan_impl&, const plat_bam_mates**, long long*) { return (int)PLAT_OK; });
 }

@@ -757,6 +757,7 @@ CALLER_EXPORT void plat_caller_debug_set_order(const char* names, char* out, siz
 #include "tabix_source.hpp"
 #include "index_source.hpp"
 #include "bam_file.hpp"
+#include "bam_mates.hpp"
 #include "fasta_source.hpp"
 #include "bgzf_out.hpp"
 #include "tbi_out.hpp"

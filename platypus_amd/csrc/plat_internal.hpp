@@ -23,7 +23,7 @@ struct plat_ctx {
     double* d_mapq_lut = nullptr;       // log(1 - exp(mLTOT*mapq)), chaplotype.pyx:621, host libm
     double* d_logfact = nullptr;        // logFactorial(0 .. 4095) then log(1 .. 4096) (platypusutils.pyx:178-191), host libm: plat_variant_info_batch
     // device scratch (grow-only)
-    plat_scratch hapw, tile, codes, rinfo, hap_flags, pair_rec, jobs, job_score, counters, asm_scratch, tb, slow, dense, pop_scratch, merge_tab, seedmap, seedstate, asm_sig, route, srcvcf, refcov, tabix, deflate, fasta;
+    plat_scratch hapw, tile, codes, rinfo, hap_flags, pair_rec, jobs, job_score, counters, asm_scratch, tb, slow, dense, pop_scratch, merge_tab, seedmap, seedstate, asm_sig, route, srcvcf, refcov, tabix, deflate, fasta, mates;
     unsigned long long asm_epoch = 0;   // counts the (re)allocations of asm_scratch AND the changes of the slice layout between launches: part of the signature k_assemble leaves in asm_sig
     unsigned long long asm_last_layout = 0;   // the previous launch's slice layout (sizes asm_carve is given)
     bool sb_attr_set = false;           // k_sb_variants' dynamic-LDS limit has been raised on this context's device

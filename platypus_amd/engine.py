@@ -959,6 +959,67 @@ class Engine:
                                            "plat_bam_route_batch")
         return out
 
+    def bam_mates(self, blob, rec_off, rec_limit, stream_begin, mode, want_tid=None, lo=None, hi=None, cap_records=None, cap_bytes=None,
+                  n_records=None, check=True):
+        """plat_bam_mates_batch: the device pass of the broken-mate fetch over records as plat_bam_find_records leaves them (blob, rec_off /
+        rec_limit, stream_begin [n_streams + 1]).  mode "coords": the (mtid, mpos) pairs of the records that give one; "fetch": the records
+        of stream s with mtid == want_tid[s] and lo[s] <= mpos <= hi[s], copied back to back.  cap_records / cap_bytes: the capacities
+        handed over (default: every record, every byte).  Returns a dict: status [4] = {error, lowest offending stream, kept, looked at},
+        need_bytes, begin [n_streams + 1], coords [kept, 2] or data / rec_off / rec_len / mpos, pad (the PLAT_BLOB_PAD bytes behind the last
+        record) and guard_intact: nothing was written behind a capacity.  A refusal raises PlatypusDeviceError (check=False: returns)."""
+        torch = _torch()
+        blob = np.frombuffer(blob, dtype=np.uint8) if isinstance(blob, (bytes, bytearray)) else np.ascontiguousarray(blob, dtype=np.uint8)
+        rec_off, rec_limit = np.ascontiguousarray(rec_off, dtype=np.int64), np.ascontiguousarray(rec_limit, dtype=np.int64)
+        stream_begin = np.ascontiguousarray(stream_begin, dtype=np.int32)
+        fetch = mode == "fetch"
+        n = len(rec_off) if n_records is None else int(n_records)
+        n_streams = len(stream_begin) - 1
+        pad = _lib.PLAT_BLOB_PAD
+        cap_r = n if cap_records is None else int(cap_records)
+        cap_b = len(blob) if cap_bytes is None else int(cap_bytes)
+        dev = lambda a, dt: torch.from_numpy(np.append(np.asarray(a, dtype=dt), np.zeros(1, dtype=dt))).to(self.device)
+        d_blob = torch.from_numpy(np.concatenate([blob, np.zeros(pad, dtype=np.uint8)])).to(self.device)
+        d_off, d_lim, d_sb = dev(rec_off, np.int64), dev(rec_limit, np.int64), dev(stream_begin, np.int32)
+        zeros = np.zeros(n_streams, dtype=np.int32)
+        d_want, d_lo, d_hi = (dev(zeros if a is None else a, np.int32) for a in (want_tid, lo, hi))
+        guard, f64, f32, f8 = 16, 0x7EEE7EEE7EEE7EEE, 0x7EEE7EEE, 0xEE
+        o_coords = torch.full((2 * cap_r + guard,), f32, dtype=torch.int32, device=self.device)
+        o_begin = torch.full((n_streams + 1 + guard,), f32, dtype=torch.int32, device=self.device)
+        o_data = torch.full((cap_b + pad + 4 * guard,), f8, dtype=torch.uint8, device=self.device)
+        o_off = torch.full((cap_r + guard,), f64, dtype=torch.int64, device=self.device)
+        o_len = torch.full((cap_r + guard,), f32, dtype=torch.int32, device=self.device)
+        o_mpos = torch.full((cap_r + guard,), f32, dtype=torch.int32, device=self.device)
+        o_status = torch.full((4 + guard,), f64, dtype=torch.int64, device=self.device)
+        o_need = torch.full((1 + guard,), f64, dtype=torch.int64, device=self.device)
+        mi = _lib.BamMatesIn(n_streams, n, _lib.MATES_FETCH if fetch else _lib.MATES_COORDS, 0, d_blob.data_ptr(), len(blob), d_off.data_ptr(), d_lim.data_ptr(),
+                             d_sb.data_ptr(), d_want.data_ptr(), d_lo.data_ptr(), d_hi.data_ptr())
+        mo = _lib.BamMatesOut(cap_r, cap_b, o_coords.data_ptr(), o_begin.data_ptr(), o_data.data_ptr(), o_off.data_ptr(), o_len.data_ptr(), o_mpos.data_ptr(),
+                              o_begin.data_ptr(), o_status.data_ptr(), o_need.data_ptr())
+        _lib.check(self.lib.plat_bam_mates_batch(self.ctx, C.byref(mi), C.byref(mo), self._stream()), "plat_bam_mates_batch")
+        self._sync()
+        coords, begin, data, off, ln, mpos, st, need = (t.cpu().numpy() for t in (o_coords, o_begin, o_data, o_off, o_len, o_mpos, o_status, o_need))
+        over = int(st[0]) == -8
+        kept = min(int(st[2]), cap_r) if int(st[0]) != -1 else 0
+        nb = int(need[0])
+        out = dict(status=st[:4], need_bytes=nb, begin=begin[:n_streams + 1])
+        intact = bool((begin[n_streams + 1:] == f32).all() and (st[4:] == f64).all() and (need[1:] == f64).all())
+        if fetch:
+            end = min(nb, cap_b) + (0 if over else pad)
+            if over:                                                           # (what was written is a prefix that fits both capacities)
+                fits = (off[:kept] != f64) & (off[:kept] + ln[:kept] <= cap_b)
+                kept = int(fits.sum()) if fits.all() or not fits.any() else int(np.argmin(fits))
+                end = int(off[kept - 1] + ln[kept - 1]) if kept else 0
+            intact = intact and bool((data[end:] == f8).all() and (off[kept:] == f64).all() and (ln[kept:] == f32).all() and (mpos[kept:] == f32).all() and
+                                     (coords == f32).all())
+            out.update(data=data[:min(nb, cap_b)], rec_off=off[:kept], rec_len=ln[:kept], mpos=mpos[:kept], pad=data[min(nb, cap_b):min(nb, cap_b) + pad])
+        else:
+            intact = intact and bool((coords[2 * kept:] == f32).all() and (data == f8).all() and (off == f64).all() and (ln == f32).all() and (mpos == f32).all())
+            out.update(coords=coords[:2 * kept].reshape(-1, 2))
+        out["guard_intact"] = intact
+        if check and int(st[0]) != 0:
+            raise _lib.PlatypusDeviceError(int(st[0]), "stream %d" % int(st[1]), "plat_bam_mates_batch")
+        return out
+
     def source_variants(self, regions, names, max_size=1500, long_haps=0, cap_variants=None, lead=0, text_off=None, check=True):
         """plat_source_variants_batch: VariantCandidateReader.Variants' line loop (variantutils.py:72-159,168-197) on the device.  regions:
         per region the bytes a fetch returned (the source files' fetches back to back); names: the regions' chromosomes (bytes / str) or

@@ -246,6 +246,22 @@ class _BamFetchPlan(C.Structure):
                [(k, C.c_int64) for k in ("queries", "handed_over", "chunks", "device_calls")] + [("seconds", C.c_double)]
 
 
+class _BamMateQuery(C.Structure):
+    """plat_bam_mate_query."""
+    _fields_ = [("tid", C.c_int32), ("_pad", C.c_int32), ("start", C.c_int64), ("end", C.c_int64)]
+
+
+class _BamMates(C.Structure):
+    """plat_bam_mates."""
+    _fields_ = [("n_coords", C.c_int32), ("n_queries", C.c_int32), ("queries", C.POINTER(_BamMateQuery)), ("mates", _BamFileRecords)]
+
+
+class _BamMatesPlan(C.Structure):
+    """plat_bam_mates_plan."""
+    _fields_ = [("n_regions", C.c_int32), ("n_files", C.c_int32), ("units", C.POINTER(_BamMates)), ("loaded", C.POINTER(C.c_int32))] + \
+               [(k, C.c_int64) for k in ("coords", "queries", "chunks", "records_looked_at", "records_kept", "device_calls", "input_bytes")] + [("seconds", C.c_double)]
+
+
 BAM_FILES_MODES = ("presplit", "merged")
 
 
@@ -681,6 +697,7 @@ def build(verbose=False):
     srcs.append(os.path.join(_lib.CSRC, "tabix_index.hpp"))            # (... and the host twin of the tabix indexer, with its finishing stage)
     srcs.append(os.path.join(_lib.CSRC, "index_query.hpp"))            # (... and the flatten and the host twin of the index query)
     srcs.append(os.path.join(_lib.CSRC, "fasta_rule.hpp"))             # (... and the rule, the .fai parse and the host twin of the FASTA fetch)
+    srcs.append(os.path.join(_lib.CSRC, "mate_rule.hpp"))              # (... and the rule of the broken-mate fetch)
     if os.path.exists(LIB_PATH) and os.path.getmtime(LIB_PATH) >= max([os.path.getmtime(f) for f in srcs] + [os.path.getmtime(_lib.LIB_PATH)]):
         return LIB_PATH
     # (-O3: the region loop is many small functions over small containers; +10 % windows/s over -O2 on the same box.  No -march: the library
@@ -777,6 +794,11 @@ def _bind(lib):
     lib.plat_call_bam_files.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.POINTER(_BamCallRegion), C.c_int, C.POINTER(CallerOptions),
                                         C.POINTER(CallerQCOptions), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(_FetchedRegionInfo),
                                         C.POINTER(CallerStats)]
+    lib.plat_call_bam_files_mates.argtypes = lib.plat_call_bam_files.argtypes
+    lib.plat_bam_files_mates_plan.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(_BamCallRegion), C.c_int, C.POINTER(_BamFetchPlan), C.POINTER(CallerOptions),
+                                              C.POINTER(C.POINTER(_BamMatesPlan))]
+    lib.plat_bam_mates_plan_free.argtypes = [C.POINTER(_BamMatesPlan)]
+    lib.plat_bam_mates_plan_free.restype = None
     lib.plat_caller_free.argtypes = [C.c_void_p]
     lib.plat_caller_free.restype = None
     lib.plat_caller_last_error.argtypes = [C.c_void_p]
@@ -1301,7 +1323,50 @@ class NativeCaller:
         finally:
             self.lib.plat_bam_fetch_plan_free(plan)
 
-    def call_bam_files(self, files, regions, options, source_lines=None, source_blocks=None, source_files=None):
+    def bam_mates_plan(self, files, regions, options):
+        """plat_bam_files_mates_plan for regions [(chrom, start, end)]: the broken-mate fetch of loadBAMData (platypusutils.pyx:522-559) on
+        the device.  Per region and file dict(n_coords, queries [(tid, start, end)], records [bytes] in mate-position order);
+        self.bam_mates_info holds the plan's counters and loaded [per region: 0 where round one reached maxReads]."""
+        arr, keep = self._bam_regions(regions)
+        handles = self._bam_handles(files)
+        fetch = C.POINTER(_BamFetchPlan)()
+        rc = self.lib.plat_bam_files_fetch_plan(handles, len(files), arr, len(regions), C.byref(fetch))
+        if rc != 0:
+            raise self._error(rc, "plat_bam_files_fetch_plan")
+        plan = C.POINTER(_BamMatesPlan)()
+        try:
+            o = CallerOptions.from_options(options)
+            rc = self.lib.plat_bam_files_mates_plan(handles, len(files), arr, len(regions), fetch, C.byref(o), C.byref(plan))
+            if rc != 0:
+                raise self._error(rc, "plat_bam_files_mates_plan")
+            p = plan.contents
+            out = []
+            for k in range(p.n_regions):
+                per = []
+                for f in range(p.n_files):
+                    u = p.units[k * p.n_files + f]
+                    r = u.mates.records
+                    n = r.n_records
+                    off = np.ctypeslib.as_array(C.cast(r.rec_off, C.POINTER(C.c_int64)), shape=(n,)) if n else []
+                    ln = np.ctypeslib.as_array(C.cast(u.mates.rec_len, C.POINTER(C.c_int32)), shape=(n,)) if n else []
+                    per.append(dict(n_coords=u.n_coords, queries=[(u.queries[q].tid, u.queries[q].start, u.queries[q].end) for q in range(u.n_queries)],
+                                    records=[C.string_at(r.data + int(off[i]), int(ln[i])) for i in range(n)]))
+                out.append(per)
+            self.bam_mates_info = {k: getattr(p, k) for k in ("coords", "queries", "chunks", "records_looked_at", "records_kept", "device_calls", "input_bytes", "seconds")}
+            self.bam_mates_info["loaded"] = [p.loaded[k] for k in range(p.n_regions)]
+            return out
+        finally:
+            del keep
+            if plan:
+                self.lib.plat_bam_mates_plan_free(plan)
+            self.lib.plat_bam_fetch_plan_free(fetch)
+
+    def call_bam_files_mates(self, files, regions, options, source_lines=None, source_blocks=None, source_files=None):
+        """plat_call_bam_files_mates: call_bam_files with the broken mates fetched -- with options.assemble and options.assembleBrokenPairs
+        set, the mates plan's records go into the BGZF call as broken_mates; with either 0 it is call_bam_files."""
+        return self.call_bam_files(files, regions, options, source_lines, source_blocks, source_files, _entry="plat_call_bam_files_mates")
+
+    def call_bam_files(self, files, regions, options, source_lines=None, source_blocks=None, source_files=None, _entry="plat_call_bam_files"):
         """plat_call_bam_files: files [NativeBamFile], regions [BamFilesRegion, or FastaContigRegion over one].  The samples, the mode, the
         windows and the chunks are the library's (bam_plan, bam_fetch_plan); from there it is call_bgzf_regions or call_bgzf_regions_rg:
         the same text, rlen, self.loaded and self.read_counts.  self.sample_names holds the call's samples (str)."""
@@ -1321,9 +1386,9 @@ class NativeCaller:
         info = (_FetchedRegionInfo * max(n, 1))()
         for k in range(n):
             info[k].sample_counts = counts[k].ctypes.data
-        rc = self.lib.plat_call_bam_files(self.h, self._bam_handles(files), len(files), arr, n, C.byref(o), C.byref(q), C.byref(text), C.byref(length), info, C.byref(st))
+        rc = getattr(self.lib, _entry)(self.h, self._bam_handles(files), len(files), arr, n, C.byref(o), C.byref(q), C.byref(text), C.byref(length), info, C.byref(st))
         del keep_source, keep
-        out = self._finish(rc, "plat_call_bam_files", text, length, o, st, options)
+        out = self._finish(rc, _entry, text, length, o, st, options)
         self.sample_names = [s.decode(errors="surrogateescape") for s in names]
         self.loaded = [int(info[k].loaded) for k in range(n)]
         self.read_counts = counts[:n]
