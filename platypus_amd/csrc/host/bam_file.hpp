@@ -2,8 +2,9 @@
 // a BAM file and its .bai opened once -- the header inflated on the host as far as it reaches (bgzf_blocks.hpp's block list and host
 // inflate over a growing prefix of the file), its text read by the rule of Samfile.header and getSampleNamesAndLoadIterators (bamhdr::
 // below, the standard library alone), the .bai through plat_index_open --, loadBAMData's choice between one stream per sample and the
-// split by read group, per file one batch of index queries for all regions of a call, every chunk cut out of the file (cutIndexChunk,
-// index_source.hpp), and from there plat_call_bgzf_regions or plat_call_bgzf_regions_rg on those structures.
+// split by read group, per file one index fetch for all regions of a call (fetchIndexChunks, index_source.hpp: the queries in one batch,
+// every chunk cut out of the file), and from there plat_call_bgzf_regions or plat_call_bgzf_regions_rg on those structures
+// (callBamFilesWith: the frame plat_call_bam_files_mates of bam_mates.hpp shares, as it shares the entry points' argument checks).
 // Included at the end of region_caller.cpp, after index_source.hpp.
 #pragma once
 #include <algorithm>
@@ -318,12 +319,36 @@ CALLER_EXPORT plat_index* plat_bam_file_index(const plat_bamfile* f) { return f 
 
 namespace plathost {
 
-// the files of one call: all there, all of one caller
-inline bool bamFilesOk(plat_bamfile* const* files, int n_files, const plat_caller* c = nullptr)
+// what every files entry point checks of its lists: the files all there and all of one caller, the regions pointer, chrom of every region
+inline bool bamFilesArgsOk(plat_bamfile* const* files, int n_files, const plat_bam_call_region* regions, int n_regions, const plat_caller* c = nullptr)
 {
-    if (!files || n_files < 1) return false;
+    if (!files || n_files < 1 || n_regions < 0 || (n_regions > 0 && !regions)) return false;
     for (int f = 0; f < n_files; ++f) if (!files[f] || files[f]->c != (c ? c : files[0]->c)) return false;
+    for (int k = 0; k < n_regions; ++k) if (!regions[k].chrom) return false;
     return true;
+}
+// A plan entry point: its plan cleared (as bamFilesCallArgsOk clears the text's outputs: in front of the other checks, so a call refused
+// for another argument leaves them NULL / 0), its other arguments (argsOk) and its lists checked, the plan made under the guard.
+template <class Impl, class Plan, class Make>
+inline int bamFilesPlanEntry(const char* entry, Plan** plan, plat_bamfile* const* files, int n_files, const plat_bam_call_region* regions, int n_regions, bool argsOk, Make&& make)
+{
+    if (!plan) return PLAT_ERR_INVALID;
+    *plan = nullptr;
+    if (!argsOk || !bamFilesArgsOk(files, n_files, regions, n_regions)) return PLAT_ERR_INVALID;
+    return guardedEntry(files[0]->c, entry, [&] {
+        std::unique_ptr<Impl> I(new Impl);
+        const int rc = make(*I);
+        if (rc == PLAT_OK) *plan = I.release();
+        return rc;
+    });
+}
+// ... and what the two call entry points check: the text's outputs, cleared, the caller and the options
+inline bool bamFilesCallArgsOk(plat_caller* c, plat_bamfile* const* files, int n_files, const plat_bam_call_region* regions, int n_regions,
+                               const plat_caller_options* options, char** out_text, size_t* out_len)
+{
+    if (!out_text || !out_len) return false;
+    *out_text = nullptr; *out_len = 0;
+    return c && options && bamFilesArgsOk(files, n_files, regions, n_regions, c);
 }
 
 inline int makeBamPlan(plat_bamfile* const* files, int n_files, plat_bam_plan_impl& I)
@@ -365,7 +390,6 @@ inline int makeBamFetchPlan(plat_bamfile* const* files, int n_files, const plat_
         for (int f = 0; f < n_files; ++f) { plat_bam_fetch& ft = I.F[(size_t)k * n_files + f]; ft.itr_beg = beg; ft.itr_end = r.end; ft.tid = plat_bam_file_tid(files[f], r.chrom); }
     }
     for (int f = 0; f < n_files; ++f) {
-        plat_index& X = *files[f]->index;
         std::vector<int32_t> tid, beg, end;
         std::vector<int> served;
         for (int k = 0; k < n_regions; ++k) {
@@ -374,22 +398,12 @@ inline int makeBamFetchPlan(plat_bamfile* const* files, int n_files, const plat_
             tid.push_back(ft.tid); beg.push_back(ft.itr_beg); end.push_back(ft.itr_end); served.push_back(k);
         }
         plat_index_query_info qi;
-        const int rc = queryIndex(X, (int)tid.size(), tid.data(), beg.data(), end.data(), &qi);
-        if (rc != PLAT_OK) { if (rc == PLAT_ERR_UNSUPPORTED) c->lastError = "plat_bam_files_fetch_plan: the device library has no plat_index_query_batch"; return rc; }
+        std::vector<std::vector<plat_bgzf_chunk>> chunks;
+        const int rc = fetchIndexChunks(c, "plat_bam_files_fetch_plan", files[f]->data, files[f]->len, *files[f]->index, tid, beg, end,
+                                        [&](size_t s) { return "region " + std::to_string(served[s]) + ", file " + std::to_string(f); }, chunks, &qi);
+        if (rc != PLAT_OK) return rc;
         p.queries += qi.queries; p.handed_over += qi.handed_over; p.chunks += qi.chunks; p.device_calls += qi.device_calls;
-        for (size_t s = 0; s < served.size(); ++s) {
-            std::vector<plat_bgzf_chunk>& out = I.chunks[(size_t)served[s] * n_files + f];
-            for (int64_t j = X.first[s]; j < X.first[s + 1]; ++j) {
-                plat_bgzf_chunk ch;
-                if (!cutIndexChunk(files[f]->data, files[f]->len, (uint64_t)X.u[(size_t)j], (uint64_t)X.v[(size_t)j], ch)) {
-                    c->lastError = "plat_bam_files_fetch_plan: chunk " + std::to_string(j - X.first[s]) + " of region " + std::to_string(served[s]) + ", file " + std::to_string(f) +
-                                   " (virtual offsets " + std::to_string((uint64_t)X.u[(size_t)j]) + " .. " + std::to_string((uint64_t)X.v[(size_t)j]) +
-                                   ") does not begin and end at BGZF block headers inside the file's data";
-                    return PLAT_ERR_BAD_INPUT;
-                }
-                out.push_back(ch);
-            }
-        }
+        for (size_t s = 0; s < served.size(); ++s) I.chunks[(size_t)served[s] * n_files + f].swap(chunks[s]);
     }
     for (size_t i = 0; i < I.F.size(); ++i) { I.F[i].n_chunks = (int32_t)I.chunks[i].size(); I.F[i].chunks = I.chunks[i].data(); }
     p.n_regions = n_regions; p.n_files = n_files; p.fetches = I.F.data();
@@ -401,28 +415,14 @@ inline int makeBamFetchPlan(plat_bamfile* const* files, int n_files, const plat_
 
 CALLER_EXPORT int plat_bam_files_plan(plat_bamfile* const* files, int n_files, plat_bam_plan** plan)
 {
-    if (!plan || !bamFilesOk(files, n_files)) return PLAT_ERR_INVALID;
-    *plan = nullptr;
-    return guardedEntry(files[0]->c, "plat_bam_files_plan", [&] {
-        std::unique_ptr<plat_bam_plan_impl> I(new plat_bam_plan_impl);
-        const int rc = makeBamPlan(files, n_files, *I);
-        if (rc == PLAT_OK) *plan = I.release();
-        return rc;
-    });
+    return bamFilesPlanEntry<plat_bam_plan_impl>("plat_bam_files_plan", plan, files, n_files, nullptr, 0, true, [&](plat_bam_plan_impl& I) { return makeBamPlan(files, n_files, I); });
 }
 CALLER_EXPORT void plat_bam_plan_free(plat_bam_plan* plan) { delete static_cast<plat_bam_plan_impl*>(plan); }
 
 CALLER_EXPORT int plat_bam_files_fetch_plan(plat_bamfile* const* files, int n_files, const plat_bam_call_region* regions, int n_regions, plat_bam_fetch_plan** plan)
 {
-    if (!plan || !bamFilesOk(files, n_files) || n_regions < 0 || (n_regions > 0 && !regions)) return PLAT_ERR_INVALID;
-    *plan = nullptr;
-    for (int k = 0; k < n_regions; ++k) if (!regions[k].chrom) return PLAT_ERR_INVALID;
-    return guardedEntry(files[0]->c, "plat_bam_files_fetch_plan", [&] {
-        std::unique_ptr<plat_bam_fetch_plan_impl> I(new plat_bam_fetch_plan_impl);
-        const int rc = makeBamFetchPlan(files, n_files, regions, n_regions, *I);
-        if (rc == PLAT_OK) *plan = I.release();
-        return rc;
-    });
+    return bamFilesPlanEntry<plat_bam_fetch_plan_impl>("plat_bam_files_fetch_plan", plan, files, n_files, regions, n_regions, true,
+                                                       [&](plat_bam_fetch_plan_impl& I) { return makeBamFetchPlan(files, n_files, regions, n_regions, I); });
 }
 CALLER_EXPORT void plat_bam_fetch_plan_free(plat_bam_fetch_plan* plan) { delete static_cast<plat_bam_fetch_plan_impl*>(plan); }
 
@@ -461,42 +461,35 @@ inline int callBamFilesWith(plat_caller* c, const char* entry, plat_bamfile* con
     const plat_bam_mates* M = nullptr;
     long long mateBytes = 0;
     if ((rc = mates(P, X, &M, &mateBytes)) != PLAT_OK) return rc;
+    // the BGZF call's structures (R: plat_bgzf_region or plat_bgzf_rg_region, the units its samples or files): n units per region under the
+    // region's head, unit i the fetch of file fileOf(i) with that file's broken mates
+    auto fill = [&](auto& units, auto& R, auto unitsOf, int n, auto fileOf, auto setMates) {
+        units.resize((size_t)n_regions * (size_t)n); R.resize((size_t)n_regions);
+        for (int k = 0; k < n_regions; ++k) {
+            for (int i = 0; i < n; ++i) {
+                const size_t at = (size_t)k * n_files + fileOf(i);
+                auto& u = units[(size_t)k * n + i];
+                memset(&u, 0, sizeof u);
+                u.n_chunks = X.F[at].n_chunks; u.chunks = X.F[at].chunks;
+                if (M) setMates(u, M[at].mates);
+            }
+            auto& r = R[(size_t)k];
+            memset(&r, 0, sizeof r);
+            r.chrom = regions[k].chrom; r.start = regions[k].start; r.end = regions[k].end; r.contig_seq = regions[k].contig_seq; r.contig_len = regions[k].contig_len;
+            r.dev_contig_seq = regions[k].dev_contig_seq; r.tid = tid[(size_t)k]; r.itr_beg = X.F[(size_t)k * n_files].itr_beg; r.itr_end = X.F[(size_t)k * n_files].itr_end;
+            r.*unitsOf = units.data() + (size_t)k * n;
+        }
+    };
     if (P.mode == PLAT_BAM_FILES_PRESPLIT) {
-        const int nS = P.n_samples;
-        std::vector<plat_bgzf_sample> units((size_t)n_regions * (size_t)nS);
-        std::vector<plat_bgzf_region> R((size_t)n_regions);
-        for (int k = 0; k < n_regions; ++k) {
-            for (int s = 0; s < nS; ++s) {
-                const plat_bam_fetch& ft = X.F[(size_t)k * n_files + P.sample_file[s]];
-                plat_bgzf_sample& u = units[(size_t)k * nS + s];
-                memset(&u, 0, sizeof u);
-                u.n_chunks = ft.n_chunks; u.chunks = ft.chunks;
-                if (M) u.broken_mates = M[(size_t)k * n_files + P.sample_file[s]].mates.records;
-            }
-            plat_bgzf_region& r = R[(size_t)k];
-            memset(&r, 0, sizeof r);
-            r.chrom = regions[k].chrom; r.start = regions[k].start; r.end = regions[k].end; r.contig_seq = regions[k].contig_seq; r.contig_len = regions[k].contig_len;
-            r.dev_contig_seq = regions[k].dev_contig_seq; r.tid = tid[(size_t)k]; r.itr_beg = X.F[(size_t)k * n_files].itr_beg; r.itr_end = X.F[(size_t)k * n_files].itr_end;
-            r.samples = units.data() + (size_t)k * nS;
-        }
-        rc = plat_call_bgzf_regions(c, R.data(), n_regions, nS, P.sample_names, options, qc, out_text, out_len, info, stats);
+        std::vector<plat_bgzf_sample> units;
+        std::vector<plat_bgzf_region> R;
+        fill(units, R, &plat_bgzf_region::samples, P.n_samples, [&](int s) { return P.sample_file[s]; },
+             [](plat_bgzf_sample& u, const plat_bam_file_records& m) { u.broken_mates = m.records; });
+        rc = plat_call_bgzf_regions(c, R.data(), n_regions, P.n_samples, P.sample_names, options, qc, out_text, out_len, info, stats);
     } else {
-        std::vector<plat_bgzf_file> units((size_t)n_regions * (size_t)n_files);
-        std::vector<plat_bgzf_rg_region> R((size_t)n_regions);
-        for (int k = 0; k < n_regions; ++k) {
-            for (int f = 0; f < n_files; ++f) {
-                const plat_bam_fetch& ft = X.F[(size_t)k * n_files + f];
-                plat_bgzf_file& u = units[(size_t)k * n_files + f];
-                memset(&u, 0, sizeof u);
-                u.n_chunks = ft.n_chunks; u.chunks = ft.chunks;
-                if (M) u.broken_mates = M[(size_t)k * n_files + f].mates;
-            }
-            plat_bgzf_rg_region& r = R[(size_t)k];
-            memset(&r, 0, sizeof r);
-            r.chrom = regions[k].chrom; r.start = regions[k].start; r.end = regions[k].end; r.contig_seq = regions[k].contig_seq; r.contig_len = regions[k].contig_len;
-            r.dev_contig_seq = regions[k].dev_contig_seq; r.tid = tid[(size_t)k]; r.itr_beg = X.F[(size_t)k * n_files].itr_beg; r.itr_end = X.F[(size_t)k * n_files].itr_end;
-            r.files = units.data() + (size_t)k * n_files;
-        }
+        std::vector<plat_bgzf_file> units;
+        std::vector<plat_bgzf_rg_region> R;
+        fill(units, R, &plat_bgzf_rg_region::files, n_files, [](int f) { return f; }, [](plat_bgzf_file& u, const plat_bam_file_records& m) { u.broken_mates = m; });
         rc = plat_call_bgzf_regions_rg(c, R.data(), n_regions, n_files, &P.groups, P.n_samples, P.sample_names, options, qc, out_text, out_len, info, stats);
     }
     if (rc == PLAT_OK && stats) stats->input_bytes += mateBytes;
@@ -509,9 +502,7 @@ CALLER_EXPORT int plat_call_bam_files(plat_caller* c, plat_bamfile* const* files
                                       plat_caller_options* options, const plat_caller_qc_options* qc, char** out_text, size_t* out_len,
                                       plat_fetched_region_info* info, plat_caller_stats* stats)
 {
-    if (!c || !options || !out_text || !out_len || !bamFilesOk(files, n_files, c) || n_regions < 0 || (n_regions > 0 && !regions)) return PLAT_ERR_INVALID;
-    *out_text = nullptr; *out_len = 0;
-    for (int k = 0; k < n_regions; ++k) if (!regions[k].chrom) return PLAT_ERR_INVALID;
+    if (!bamFilesCallArgsOk(c, files, n_files, regions, n_regions, options, out_text, out_len)) return PLAT_ERR_INVALID;
     SourceLinesGuard sourceGuard(c);                                       // (whichever way this call ends; the BGZF call behind it holds its own)
     if (options->assemble && options->assembleBrokenPairs) {
         c->lastError = "plat_call_bam_files: assemble=1 with assembleBrokenPairs=1 asks for the mates of improper pairs, a second round of fetches this entry point does not make "

@@ -1,9 +1,9 @@
 // bam_mates.hpp -- plat_bam_files_mates_plan and plat_call_bam_files_mates (include/platypus_caller_bamfile.h): the broken-mate fetch of
 // loadBAMData (platypusutils.pyx:522-559, :617-654) for whole files.  Two device batches on slot 0's stream, each the fetches of the whole
-// call: the chunks uploaded and inflated (bgzf_blocks.hpp), plat_bam_find_records, plat_bam_mates_batch -- round one over the fetch plan's
-// chunks for the mate coordinates, round two over the chunks of the merged queries for the mates themselves -- and between them, on the
-// host, csrc/mate_rule.hpp's sort and mergeQueries, one queryIndex batch per file and cutIndexChunk.  The call hands the plan's records to
-// plat_call_bgzf_regions / _rg as broken_mates (callBamFilesWith, bam_file.hpp).
+// call: bgzf_blocks.hpp's BgzfStreams (the chunks uploaded and inflated, plat_bam_find_records) with plat_bam_mates_batch behind it -- round
+// one over the fetch plan's chunks for the mate coordinates, round two over the chunks of the merged queries for the mates themselves --
+// and between them, on the host, csrc/mate_rule.hpp's sort and mergeQueries and one index fetch per file (fetchIndexChunks,
+// index_source.hpp).  The call hands the plan's records to plat_call_bgzf_regions / _rg as broken_mates (callBamFilesWith, bam_file.hpp).
 // Included at the end of region_caller.cpp, after bam_file.hpp.
 #pragma once
 #include "../mate_rule.hpp"
@@ -13,39 +13,34 @@
 
 namespace plathost {
 
-// One batch of fetches through the device.  A stream is one fetch: its window and its chunks, added in order; run() enqueues everything
-// and waits once for the statuses and the streams' begins.
+// One batch of fetches through the device.  A stream is one fetch: its window and its chunks, added in order; run() enqueues the shared
+// batch and the mates pass behind it and waits once for the statuses and the streams' begins.
 struct MatesBatch {
     plat_caller* c;
     const std::string entry;
     Slot& z;
     FetchedDeviceBuffers dev;
     const std::function<std::string(int)> whereStream;                    // "region K (chr:a-b), file F[, query Q (...)]"
-    BgzfBlockList L;
-    std::vector<int32_t> sTid, sBeg, sEnd, chunkBegin;
-    plat_bgzf_inflate_out io;
-    plat_bam_find_out fo;
+    BgzfStreams batch;
+    std::vector<BgzfStream> streams;
+    RecordList kept;                                                      // the find's records, per stream
     plat_bam_mates_out mo;
-    long long capRecords = 0;
-    int64_t inflateStatus[4] = {0, -1, 0, 0}, findStatus[4] = {0, -1, 0, 0}, matesStatus[4] = {0, -1, 0, 0}, needBytes = 0;
-    std::vector<int32_t> keptBegin, outBegin;                             // per stream: the find's records, the pass's outputs
+    int64_t matesStatus[4] = {0, -1, 0, 0}, needBytes = 0;
+    std::vector<int32_t> outBegin;                                        // per stream: the pass's outputs
     int deviceCalls = 0;
 
     MatesBatch(plat_caller* c_, const char* entry_, std::function<std::string(int)> where)
         : c(c_), entry(entry_), z(*c_->slots[0]), dev(z), whereStream(std::move(where)),
-          L(entry_, [this](const BgzfChunkAt& a) { return whereStream(a.region) + ", chunk " + std::to_string(a.chunk); }, false, c_->lastError), chunkBegin(1, 0)
+          batch(z, dev, entry, [this](const BgzfChunkAt& a) { return whereStream(a.region) + ", chunk " + std::to_string(a.chunk); }, c_->lastError)
     {
-        memset(&io, 0, sizeof io); memset(&fo, 0, sizeof fo); memset(&mo, 0, sizeof mo);
+        memset(&mo, 0, sizeof mo);
     }
-
-    int nStreams() const { return (int)sTid.size(); }
 
     int addStream(int32_t tid, int32_t beg, int32_t end, int n_chunks, const plat_bgzf_chunk* chunks)
     {
-        const int s = nStreams();
-        for (int q = 0; q < n_chunks; ++q) { const int rc = L.add(s, 0, q, chunks[q]); if (rc != PLAT_OK) return rc; }
-        sTid.push_back(tid); sBeg.push_back(beg); sEnd.push_back(end);
-        chunkBegin.push_back((int32_t)L.chunkAt.size());
+        const int s = (int)streams.size(), first = (int)batch.L.chunkAt.size();
+        for (int q = 0; q < n_chunks; ++q) { const int rc = batch.L.add(s, 0, q, chunks[q]); if (rc != PLAT_OK) return rc; }
+        streams.push_back(BgzfStream{first, (int)batch.L.chunkAt.size(), tid, beg, end});
         return PLAT_OK;
     }
 
@@ -53,49 +48,33 @@ struct MatesBatch {
     int run(int mode, const std::vector<int32_t>& want, const std::vector<int32_t>& lo, const std::vector<int32_t>& hi)
     {
         void* st = z.stream;
-        const int n = nStreams();
-        capRecords = L.inflated / 36 + 1;                                  // (every record has a block_size word and 32 fixed bytes)
-        if (capRecords > INT_MAX) { c->lastError = entry + ": more records than one call takes (call the region list in parts)"; return PLAT_ERR_OVERFLOW; }
-        io = L.inflateOnDevice(z, dev);
-        fo.cap_records = capRecords; fo.rec_off = dev.alloc<int64_t>((size_t)capRecords); fo.rec_limit = dev.alloc<int64_t>((size_t)capRecords);
-        fo.status = dev.alloc<int64_t>(4); fo.stream_begin = dev.alloc<int32_t>((size_t)n + 1);
-        std::vector<int32_t> cFirst, cEnd;
-        for (const BgzfChunkAt& a : L.chunkAt) { cFirst.push_back(a.blkFirst); cEnd.push_back(a.blkEnd); }
-        plat_bam_find_in fi;
-        memset(&fi, 0, sizeof fi);
-        fi.n_streams = n; fi.n_chunks = (int)cFirst.size(); fi.n_blocks = L.nBlocks(); fi.data = io.data; fi.out_off = io.out_off;
-        fi.chunk_blk_first = dev.upload(cFirst, st); fi.chunk_blk_end = dev.upload(cEnd, st); fi.chunk_first_uoffset = dev.upload(L.firstU, st);
-        fi.chunk_stop_blk = dev.upload(L.stopBlk, st); fi.chunk_stop_uoffset = dev.upload(L.stopU, st);
-        fi.stream_chunk_begin = dev.upload(chunkBegin, st);
-        fi.tid = dev.upload(sTid, st); fi.beg = dev.upload(sBeg, st); fi.end = dev.upload(sEnd, st);
-        ck(plat_bam_find_records(z.ctx, &fi, &fo, st), "plat_bam_find_records");
+        const size_t n = streams.size();
+        if (batch.recordCap() > INT_MAX) { c->lastError = entry + ": more records than one call takes (call the region list in parts)"; return PLAT_ERR_OVERFLOW; }
+        batch.inflate();
+        batch.find(streams, kept);
+        const size_t capRecords = (size_t)batch.capRecords;
         plat_bam_mates_in mi;
         memset(&mi, 0, sizeof mi);
-        mi.n_streams = n; mi.n_records = (int32_t)capRecords; mi.mode = mode; mi.data = io.data; mi.data_len = L.inflated;
-        mi.rec_off = fo.rec_off; mi.rec_limit = fo.rec_limit; mi.stream_begin = fo.stream_begin;
-        mo.cap_records = capRecords; mo.status = dev.alloc<int64_t>(4); mo.need_bytes = dev.alloc<int64_t>(1);
-        int32_t* dBegin = dev.alloc<int32_t>((size_t)n + 1);
-        if (mode == PLAT_MATES_COORDS) { mo.coords = dev.alloc<int32_t>(2 * (size_t)capRecords); mo.coord_begin = dBegin; }
+        mi.n_streams = (int)n; mi.n_records = (int32_t)capRecords; mi.mode = mode; mi.data = kept.blob; mi.data_len = kept.bytes;
+        mi.rec_off = kept.off; mi.rec_limit = kept.limit; mi.stream_begin = kept.dBegin;
+        mo.cap_records = batch.capRecords; mo.status = dev.alloc<int64_t>(4); mo.need_bytes = dev.alloc<int64_t>(1);
+        int32_t* dBegin = dev.alloc<int32_t>(n + 1);
+        if (mode == PLAT_MATES_COORDS) { mo.coords = dev.alloc<int32_t>(2 * capRecords); mo.coord_begin = dBegin; }
         else {
             mi.want_tid = dev.upload(want, st); mi.lo = dev.upload(lo, st); mi.hi = dev.upload(hi, st);
-            mo.cap_bytes = L.inflated; mo.out_data = dev.alloc<uint8_t>((size_t)L.inflated + PLAT_BLOB_PAD);
-            mo.out_rec_off = dev.alloc<int64_t>((size_t)capRecords); mo.out_rec_len = dev.alloc<int32_t>((size_t)capRecords); mo.out_mpos = dev.alloc<int32_t>((size_t)capRecords);
+            mo.cap_bytes = kept.bytes; mo.out_data = dev.alloc<uint8_t>((size_t)kept.bytes + PLAT_BLOB_PAD);
+            mo.out_rec_off = dev.alloc<int64_t>(capRecords); mo.out_rec_len = dev.alloc<int32_t>(capRecords); mo.out_mpos = dev.alloc<int32_t>(capRecords);
             mo.out_begin = dBegin;
         }
         ck(plat_bam_mates_batch(z.ctx, &mi, &mo, st), "plat_bam_mates_batch");
         deviceCalls += 3;
-        keptBegin.assign((size_t)n + 1, 0); outBegin.assign((size_t)n + 1, 0);
-        dev.download(inflateStatus, io.status, 4, st); dev.download(findStatus, fo.status, 4, st); dev.download(matesStatus, mo.status, 4, st);
-        dev.download(&needBytes, mo.need_bytes, 1, st);
-        dev.download(keptBegin, fo.stream_begin, st); dev.download(outBegin, dBegin, st);
+        outBegin.assign(n + 1, 0);
+        dev.download(matesStatus, mo.status, 4, st); dev.download(&needBytes, mo.need_bytes, 1, st); dev.download(outBegin, dBegin, st);
         ck(plat_stream_sync(z.ctx, st), "plat_stream_sync");
-        if (inflateStatus[0] != 0) return L.blockRefused(inflateStatus[1], (int)inflateStatus[0]);
-        if (findStatus[0] != 0) {
-            c->lastError = entry + ": the record walk of " + whereStream((int)findStatus[1]) + " fails (a block_size below 32, or a record or its CIGAR running past the chunk's bytes)";
-            return (int)findStatus[0];
-        }
+        const int rc = batch.firstFailure(whereStream);
+        if (rc != PLAT_OK) return rc;
         // (the capacities are the find's and the inflated bytes: the pass has nothing left to refuse)
-        if (matesStatus[0] != 0 || outBegin[(size_t)n] != matesStatus[2]) throw DeviceError(matesStatus[0] != 0 ? (int)matesStatus[0] : PLAT_ERR_INVALID, "plat_bam_mates_batch");
+        if (matesStatus[0] != 0 || outBegin[n] != matesStatus[2]) throw DeviceError(matesStatus[0] != 0 ? (int)matesStatus[0] : PLAT_ERR_INVALID, "plat_bam_mates_batch");
         return PLAT_OK;
     }
 };
@@ -161,12 +140,9 @@ inline int makeBamMatesPlan(plat_bamfile* const* files, int n_files, const plat_
         if ((rc = B.run(PLAT_MATES_COORDS, {}, {}, {})) != PLAT_OK) return rc;
         p.device_calls += B.deviceCalls;
         // loadBAMData's bail-out (:538-541) on the kept records of a region, summed over its files: no mate is fetched for it
-        const double mr = options.maxReads;
-        const long long maxReads = mr >= (double)INT_MAX ? INT_MAX : (mr <= (double)INT_MIN ? INT_MIN : (long long)mr);     // (cdef int maxReads)
-        for (int k = 0; k < n_regions; ++k) {
-            const long long total = (long long)B.keptBegin[(size_t)(k + 1) * n_files] - B.keptBegin[(size_t)k * n_files];
-            I.loadedRegions[(size_t)k] = !(total > 0 && total >= maxReads);
-        }
+        const long long maxReads = maxReadsOf(options);
+        for (int k = 0; k < n_regions; ++k)
+            I.loadedRegions[(size_t)k] = !dropsRegion((long long)B.kept.begin[(size_t)(k + 1) * n_files] - B.kept.begin[(size_t)k * n_files], maxReads);
         coordBegin = B.outBegin;
         std::vector<int32_t> flat(2 * (size_t)coordBegin.back());
         B.dev.download(flat, B.mo.coords, B.z.stream);
@@ -238,27 +214,20 @@ inline int makeBamMatesPlan(plat_bamfile* const* files, int n_files, const plat_
         mate::query_window(mate::Query{q.tid, q.start, q.end}, &wBeg[s], &wEnd[s]);
     }
     for (int f = 0; f < n_files; ++f) {
-        plat_index& Xi = *files[f]->index;
         std::vector<int32_t> tid, beg, end;
         std::vector<size_t> served;
         for (size_t s = 0; s < streams.size(); ++s)
             if (streams[s].f == f) { tid.push_back(wTid[s]); beg.push_back(wBeg[s]); end.push_back(wEnd[s]); served.push_back(s); }
         if (served.empty()) continue;
         plat_index_query_info qi;
-        rc = queryIndex(Xi, (int)tid.size(), tid.data(), beg.data(), end.data(), &qi);
-        if (rc != PLAT_OK) { if (rc == PLAT_ERR_UNSUPPORTED) c->lastError = std::string(entry) + ": the device library has no plat_index_query_batch"; return rc; }
+        std::vector<std::vector<plat_bgzf_chunk>> chunks;
+        rc = fetchIndexChunks(c, entry, files[f]->data, files[f]->len, *files[f]->index, tid, beg, end, [&](size_t j) { return whereStream((int)served[j]); }, chunks, &qi);
+        if (rc != PLAT_OK) return rc;
         p.device_calls += qi.device_calls;
-        for (size_t j = 0; j < served.size(); ++j)
-            for (int64_t at = Xi.first[j]; at < Xi.first[j + 1]; ++at) {
-                plat_bgzf_chunk ch;
-                if (!cutIndexChunk(files[f]->data, files[f]->len, (uint64_t)Xi.u[(size_t)at], (uint64_t)Xi.v[(size_t)at], ch)) {
-                    c->lastError = std::string(entry) + ": chunk " + std::to_string(at - Xi.first[j]) + " of " + whereStream((int)served[j]) + " (virtual offsets " +
-                                   std::to_string((uint64_t)Xi.u[(size_t)at]) + " .. " + std::to_string((uint64_t)Xi.v[(size_t)at]) + ") does not begin and end at BGZF block headers inside the file's data";
-                    return PLAT_ERR_BAD_INPUT;
-                }
-                I.chunks[served[j]].push_back(ch);
-                p.input_bytes += ch.data_len;
-            }
+        for (size_t j = 0; j < served.size(); ++j) {
+            for (const plat_bgzf_chunk& ch : chunks[j]) p.input_bytes += ch.data_len;
+            I.chunks[served[j]].swap(chunks[j]);
+        }
     }
     MatesBatch B(c, entry, whereStream);
     std::vector<int32_t> want, lo, hi;
@@ -305,14 +274,8 @@ inline int makeBamMatesPlan(plat_bamfile* const* files, int n_files, const plat_
 CALLER_EXPORT int plat_bam_files_mates_plan(plat_bamfile* const* files, int n_files, const plat_bam_call_region* regions, int n_regions,
                                             const plat_bam_fetch_plan* fetch_plan, const plat_caller_options* options, plat_bam_mates_plan** plan)
 {
-    if (!plan || !fetch_plan || !options || !bamFilesOk(files, n_files) || n_regions < 0 || (n_regions > 0 && !regions)) return PLAT_ERR_INVALID;
-    *plan = nullptr;
-    for (int k = 0; k < n_regions; ++k) if (!regions[k].chrom) return PLAT_ERR_INVALID;
-    return guardedEntry(files[0]->c, "plat_bam_files_mates_plan", [&] {
-        std::unique_ptr<plat_bam_mates_plan_impl> I(new plat_bam_mates_plan_impl);
-        const int rc = makeBamMatesPlan(files, n_files, regions, n_regions, *fetch_plan, *options, *I);
-        if (rc == PLAT_OK) *plan = I.release();
-        return rc;
+    return bamFilesPlanEntry<plat_bam_mates_plan_impl>("plat_bam_files_mates_plan", plan, files, n_files, regions, n_regions, fetch_plan && options, [&](plat_bam_mates_plan_impl& I) {
+        return makeBamMatesPlan(files, n_files, regions, n_regions, *fetch_plan, *options, I);
     });
 }
 CALLER_EXPORT void plat_bam_mates_plan_free(plat_bam_mates_plan* plan) { delete static_cast<plat_bam_mates_plan_impl*>(plan); }
@@ -323,9 +286,7 @@ CALLER_EXPORT int plat_call_bam_files_mates(plat_caller* c, plat_bamfile* const*
 {
     if (!options || !(options->assemble && options->assembleBrokenPairs))  // (the reference fetches no mates: the call is plat_call_bam_files)
         return plat_call_bam_files(c, files, n_files, regions, n_regions, options, qc, out_text, out_len, info, stats);
-    if (!c || !out_text || !out_len || !bamFilesOk(files, n_files, c) || n_regions < 0 || (n_regions > 0 && !regions)) return PLAT_ERR_INVALID;
-    *out_text = nullptr; *out_len = 0;
-    for (int k = 0; k < n_regions; ++k) if (!regions[k].chrom) return PLAT_ERR_INVALID;
+    if (!bamFilesCallArgsOk(c, files, n_files, regions, n_regions, options, out_text, out_len)) return PLAT_ERR_INVALID;
     SourceLinesGuard sourceGuard(c);                                       // (whichever way this call ends; the BGZF call behind it holds its own)
     const int rc = needsEntryPoints(c, "plat_call_bam_files_mates", {(const void*)plat_bam_mates_batch}, "plat_bam_mates_batch");
     if (rc != PLAT_OK) return rc;

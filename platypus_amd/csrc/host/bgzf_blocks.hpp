@@ -1,10 +1,13 @@
 // bgzf_blocks.hpp -- the BGZF blocks of one call, for every host entry point that takes compressed bytes (bgzf_regions.hpp and through it
-// rg_regions.hpp, tabix_source.hpp, tbi_out.hpp, index_source.hpp): the walk over a chunk's BSIZE chain with its refusals (18 header bytes
-// and the trailer of every block, never a payload byte), the upload and plat_bgzf_inflate_batch on the device, the same inflate on the
-// host (bgzf::inflate_block), and the message for a block either of them refused.  The list does not know which front end it serves: the
-// entry point's name and the words for a chunk's place are the caller's, and errors go to the string the caller hands over.
-// Everything but inflateOnDevice needs csrc/bgzf_inflate.hpp, plat_bgzf_chunk and the standard library alone.  PLAT_BGZF_BLOCKS_HOST_ONLY:
-// without inflateOnDevice, for a stand-alone program (tests/bgzf_blocks_driver.cpp and the tabix drivers run this walk under the sanitizers).
+// rg_regions.hpp, bam_mates.hpp, tabix_source.hpp, tbi_out.hpp, index_source.hpp): the walk over a chunk's BSIZE chain with its refusals
+// (18 header bytes and the trailer of every block, never a payload byte), the upload and plat_bgzf_inflate_batch on the device, the same
+// inflate on the host (bgzf::inflate_block), and the message for a block either of them refused (BgzfBlockList); and, for the callers that
+// fetch BAM records, the batch from such a list to the kept records' offsets on the device (BgzfStreams: the inflate,
+// plat_bam_find_records over the caller's streams, the two status blocks and their messages).  Neither knows which front end it serves:
+// the entry point's name and the words for a chunk's or a stream's place are the caller's, and errors go to the string the caller hands over.
+// The block list without inflateOnDevice needs csrc/bgzf_inflate.hpp, plat_bgzf_chunk and the standard library alone.
+// PLAT_BGZF_BLOCKS_HOST_ONLY: without inflateOnDevice and BgzfStreams, for a stand-alone program (tests/bgzf_blocks_driver.cpp and the tabix
+// drivers run this walk under the sanitizers).  With them: included behind front_end.hpp (Slot, FetchedDeviceBuffers, RecordList).
 #pragma once
 #include <climits>
 #include <cstring>
@@ -17,8 +20,9 @@
 #include "../bgzf_inflate.hpp"
 
 #ifndef PLAT_BGZF_BLOCKS_HOST_ONLY
-// referenced weakly, as plat_bam_decode_batch: the CPU suite's stand-in device library predates it
+// referenced weakly, as plat_bam_decode_batch: the CPU suite's stand-in device library predates them
 #pragma weak plat_bgzf_inflate_batch
+#pragma weak plat_bam_find_records
 #endif
 
 namespace plathost {
@@ -161,5 +165,81 @@ struct BgzfBlockList {
     }
 #endif
 };
+
+#ifndef PLAT_BGZF_BLOCKS_HOST_ONLY
+// one stream of the record walk: chunks [chunkBegin, chunkEnd) of the batch's list, walked in order for the records of tid:[beg, end)
+struct BgzfStream { int chunkBegin, chunkEnd; int32_t tid, beg, end; };
+
+// One batch from chunks to kept records on a slot's stream, for every caller that fetches BAM records (BgzfFront, bgzf_regions.hpp;
+// MatesBatch, bam_mates.hpp): the block list, the upload and the inflate, plat_bam_find_records (sam_itr_next) over whatever streams the
+// caller lays over the list's chunks, and the messages of the two status blocks.  Nothing here waits: the statuses and the streams' begins
+// are on their way back when inflate() and find() return, and firstFailure() reads them behind the caller's one wait.
+struct BgzfStreams {
+    Slot& z;
+    FetchedDeviceBuffers& dev;
+    BgzfBlockList L;
+    plat_bgzf_inflate_out io;
+    plat_bam_find_out fo;
+    long long capRecords = 0;
+    int64_t inflateStatus[4] = {0, -1, 0, 0}, findStatus[4] = {0, -1, 0, 0};
+
+    BgzfStreams(Slot& z_, FetchedDeviceBuffers& dev_, const std::string& entry, std::function<std::string(const BgzfChunkAt&)> place, std::string& error)
+        : z(z_), dev(dev_), L(entry, std::move(place), false, error) { memset(&io, 0, sizeof io); memset(&fo, 0, sizeof fo); }
+
+    // room for the find: every record has a block_size word and 32 fixed bytes
+    long long recordCap() const { return L.inflated / 36 + 1; }
+
+    // upload and inflate, back to back; room for the find's records
+    void inflate()
+    {
+        io = L.inflateOnDevice(z, dev);
+        capRecords = recordCap();
+        memset(&fo, 0, sizeof fo);
+        fo.cap_records = capRecords; fo.rec_off = dev.alloc<int64_t>((size_t)capRecords); fo.rec_limit = dev.alloc<int64_t>((size_t)capRecords);
+        fo.status = dev.alloc<int64_t>(4);
+        dev.download(inflateStatus, io.status, 4, z.stream);
+    }
+
+    // the find over `streams`: the kept records where the decode, the route and the mates pass take them, their counts per stream
+    void find(const std::vector<BgzfStream>& streams, RecordList& kept)
+    {
+        void* st = z.stream;
+        const int n = (int)streams.size();
+        std::vector<int32_t> chunkBegin(1, 0), cFirst, cEnd, cFirstU, cStopBlk, cStopU, sTid, sBeg, sEnd;
+        for (const BgzfStream& s : streams) {
+            for (int q = s.chunkBegin; q < s.chunkEnd; ++q) {
+                cFirst.push_back(L.chunkAt[(size_t)q].blkFirst); cEnd.push_back(L.chunkAt[(size_t)q].blkEnd);
+                cFirstU.push_back(L.firstU[(size_t)q]); cStopBlk.push_back(L.stopBlk[(size_t)q]); cStopU.push_back(L.stopU[(size_t)q]);
+            }
+            chunkBegin.push_back((int32_t)cFirst.size());
+            sTid.push_back(s.tid); sBeg.push_back(s.beg); sEnd.push_back(s.end);
+        }
+        plat_bam_find_in fi;
+        memset(&fi, 0, sizeof fi);
+        fi.n_streams = n; fi.n_chunks = (int)cFirst.size(); fi.n_blocks = L.nBlocks(); fi.data = io.data; fi.out_off = io.out_off;
+        fi.chunk_blk_first = dev.upload(cFirst, st); fi.chunk_blk_end = dev.upload(cEnd, st); fi.chunk_first_uoffset = dev.upload(cFirstU, st);
+        fi.chunk_stop_blk = dev.upload(cStopBlk, st); fi.chunk_stop_uoffset = dev.upload(cStopU, st);
+        fi.stream_chunk_begin = dev.upload(chunkBegin, st);
+        fi.tid = dev.upload(sTid, st); fi.beg = dev.upload(sBeg, st); fi.end = dev.upload(sEnd, st);
+        fo.stream_begin = dev.alloc<int32_t>((size_t)n + 1);
+        ck(plat_bam_find_records(z.ctx, &fi, &fo, st), "plat_bam_find_records");
+        kept.blob = io.data; kept.bytes = L.inflated; kept.off = fo.rec_off; kept.limit = fo.rec_limit; kept.dBegin = fo.stream_begin;
+        kept.begin.assign((size_t)n + 1, 0);
+        dev.download(kept.begin, fo.stream_begin, st);
+        dev.download(findStatus, fo.status, 4, st);
+    }
+
+    // behind the wait: 0, or the inflate's or the find's error with its message (whereStream(s): the words for stream s of the last find)
+    template <class Where> int firstFailure(Where&& whereStream) const
+    {
+        if (inflateStatus[0] != 0) return L.blockRefused(inflateStatus[1], (int)inflateStatus[0]);
+        if (findStatus[0] != 0) {
+            L.error = L.entry + ": the record walk of " + whereStream((int)findStatus[1]) + " fails (a block_size below 32, or a record or its CIGAR running past the chunk's bytes)";
+            return (int)findStatus[0];
+        }
+        return PLAT_OK;
+    }
+};
+#endif
 
 }  // namespace plathost

@@ -106,7 +106,7 @@ struct FetchedStage {
 };
 
 // Records on the device as the decode takes them: one blob, every record's offset and limit in it (-1: the record leaves its own blob, the
-// device refuses it), stream after stream.  The uploader, BgzfFront::find and rgRegroup make one.
+// device refuses it), stream after stream.  The uploader, BgzfStreams::find (bgzf_blocks.hpp) and rgRegroup make one.
 struct RecordList {
     const uint8_t* blob = nullptr;
     long long bytes = 0;
@@ -117,6 +117,15 @@ struct RecordList {
     int nStreams() const { return (int)begin.size() - 1; }
     long long n() const { return begin.empty() ? 0 : begin.back(); }
 };
+
+// options.maxReads as the loader holds it (cdef int maxReads)
+inline long long maxReadsOf(const plat_caller_options& o) {
+    const double mr = o.maxReads;
+    return mr >= (double)INT_MAX ? INT_MAX : (mr <= (double)INT_MIN ? INT_MIN : (long long)mr);
+}
+// loadBAMData's bail-out (platypusutils.pyx:538-541): `totalReads >= maxReads` after each fetched read, summed over the region's
+// samples (or files); a region with no reads never gets there
+inline bool dropsRegion(long long total, long long maxReads) { return total > 0 && total >= maxReads; }
 
 // One call of a front end: the caller, the entry point's name (for messages), the arguments every front end passes through, slot 0 and
 // the call's device memory, the stage it fills and the regions' heads.
@@ -153,8 +162,7 @@ struct FrontCall {
         if (!qc || !argsOk || (n_regions > 0 && !regions)) return PLAT_ERR_INVALID;
         if ((rc = needs(fns, missing)) != PLAT_OK) return rc;
         t0 = Clock::now();
-        const double mr = options->maxReads;
-        maxReads = mr >= (double)INT_MAX ? INT_MAX : (mr <= (double)INT_MIN ? INT_MIN : (long long)mr);     // (cdef int maxReads)
+        maxReads = maxReadsOf(*options);
         z = c->slots[0].get();
         dev.ctx = z->ctx;
         S.loaded.assign((size_t)n_regions, 0);
@@ -165,9 +173,7 @@ struct FrontCall {
         return PLAT_OK;
     }
 
-    // loadBAMData's bail-out (platypusutils.pyx:538-541): `totalReads >= maxReads` after each fetched read, summed over the region's
-    // samples (or files); a region with no reads never gets there
-    bool drops(long long total) const { return total > 0 && total >= maxReads; }
+    bool drops(long long total) const { return dropsRegion(total, maxReads); }
 
     // 0 and the stage's counts set, or PLAT_ERR_OVERFLOW with its message: the reads, broken mates and CIGAR pairs of one call are counted in
     // 32 bits (streamLimit: the read-group calls bound their streams too)

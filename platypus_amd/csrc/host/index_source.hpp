@@ -2,7 +2,8 @@
 // inflated (a .tbi: bgzf_blocks.hpp's host inflate over the file as one chunk) and flattened on the host by idxq::flatten (csrc/index_query.hpp), the tables uploaded --, a call's queries answered
 // by plat_index_query_batch in one batch on slot 0's stream with one wait (queries the device hands over, and every query under
 // PLAT_CALLER_HOST_INDEX=1, by idxq::query, the host twin), and source VCFs taken as files: per file one batch of queries, every chunk
-// cut out of the file as tabixindex.cut_chunks cuts it, and from there plat_caller_set_source_blocks.
+// cut out of the file as tabixindex.cut_chunks cuts it (fetchIndexChunks: the one index fetch of a file, which the BAM files of
+// bam_file.hpp and bam_mates.hpp go through too), and from there plat_caller_set_source_blocks.
 // Included at the end of region_caller.cpp, after tabix_source.hpp.
 #pragma once
 #include "../../../include/platypus_caller_index.h"
@@ -150,6 +151,31 @@ inline bool cutIndexChunk(const uint8_t* data, int64_t len, uint64_t u, uint64_t
     return true;
 }
 
+// One file's share of a call's index fetch, for every entry point that takes whole files (plat_caller_set_source_files, bam_file.hpp,
+// bam_mates.hpp): its queries answered in one batch (queryIndex), every chunk of every answer cut out of the file's bytes -- chunks[j]:
+// query j's.  The messages carry the entry point's name; whereQuery(j) names query j's place in the call.
+template <class Where>
+inline int fetchIndexChunks(plat_caller* c, const std::string& entry, const uint8_t* data, int64_t len, plat_index& I, const std::vector<int32_t>& tid,
+                            const std::vector<int32_t>& beg, const std::vector<int32_t>& end, Where&& whereQuery,
+                            std::vector<std::vector<plat_bgzf_chunk>>& chunks, plat_index_query_info* info)
+{
+    const int rc = queryIndex(I, (int)tid.size(), tid.data(), beg.data(), end.data(), info);
+    if (rc != PLAT_OK) { if (rc == PLAT_ERR_UNSUPPORTED) c->lastError = entry + ": the device library has no plat_index_query_batch"; return rc; }
+    chunks.assign(tid.size(), {});
+    for (size_t j = 0; j < tid.size(); ++j)
+        for (int64_t at = I.first[j]; at < I.first[j + 1]; ++at) {
+            const uint64_t u = (uint64_t)I.u[(size_t)at], v = (uint64_t)I.v[(size_t)at];
+            plat_bgzf_chunk ch;
+            if (!cutIndexChunk(data, len, u, v, ch)) {
+                c->lastError = entry + ": chunk " + std::to_string(at - I.first[j]) + " of " + whereQuery(j) + " (virtual offsets " + std::to_string(u) + " .. " + std::to_string(v) +
+                               ") does not begin and end at BGZF block headers inside the file's data";
+                return PLAT_ERR_BAD_INPUT;
+            }
+            chunks[j].push_back(ch);
+        }
+    return PLAT_OK;
+}
+
 }  // namespace plathost
 
 CALLER_EXPORT int plat_index_open(plat_caller* c, const uint8_t* bytes, size_t len, int kind, plat_index** out)
@@ -228,21 +254,11 @@ CALLER_EXPORT int plat_caller_set_source_files(plat_caller* c, const plat_source
                 tid.push_back(t); beg.push_back(std::max(regions[k].start, 0)); end.push_back(regions[k].end);
                 S.push_back(Served{k, {}, I.F.names[(size_t)t].c_str()});
             }
-            const int rc = queryIndex(I, (int)tid.size(), tid.data(), beg.data(), end.data(), nullptr);
-            if (rc != PLAT_OK) { if (rc == PLAT_ERR_UNSUPPORTED) c->lastError = "plat_caller_set_source_files: the device library has no plat_index_query_batch"; return rc; }
-            const uint8_t* data = files[f].data;
-            const int64_t len = files[f].data_len;
-            for (size_t s = 0; s < S.size(); ++s)
-                for (int64_t j = I.first[s]; j < I.first[s + 1]; ++j) {
-                    const uint64_t u = (uint64_t)I.u[(size_t)j], v = (uint64_t)I.v[(size_t)j];
-                    plat_bgzf_chunk ch;
-                    if (!cutIndexChunk(data, len, u, v, ch)) {
-                        c->lastError = "plat_caller_set_source_files: chunk " + std::to_string(j - I.first[s]) + " of region " + std::to_string(S[s].region) + ", file " + std::to_string(f) +
-                                       " (virtual offsets " + std::to_string(u) + " .. " + std::to_string(v) + ") does not begin and end at BGZF block headers inside the file's data";
-                        return (int)PLAT_ERR_BAD_INPUT;
-                    }
-                    S[s].chunks.push_back(ch);
-                }
+            std::vector<std::vector<plat_bgzf_chunk>> chunks;
+            const int rc = fetchIndexChunks(c, "plat_caller_set_source_files", files[f].data, files[f].data_len, I, tid, beg, end,
+                                            [&](size_t s) { return "region " + std::to_string(S[s].region) + ", file " + std::to_string(f); }, chunks, nullptr);
+            if (rc != PLAT_OK) return rc;
+            for (size_t s = 0; s < S.size(); ++s) S[s].chunks.swap(chunks[s]);
         }
         std::vector<std::vector<plat_tabix_fetch>> fetches((size_t)n_regions);
         std::vector<size_t> at((size_t)n_files, 0);

@@ -29,7 +29,7 @@
 // In front of the loop, for reads that are not split into buffers yet (included at the end of this file):
 //   front_end.hpp          the frame every front end shares: the checks at entry, the bail-out, QC and split on the device, callRegions;
 //                          and what every entry point behind it shares: the needs check, the one guard, the call's device memory
-//   bgzf_blocks.hpp        the BGZF blocks of one call: the walk over their headers, the inflate on the device and on the host, the refusals
+//   bgzf_blocks.hpp        the BGZF blocks of one call: the walk over their headers, the inflate on the device and on the host, the refusals; the batch from chunks to kept BAM records
 //                          (after bam_regions.hpp, in front of every header that takes compressed bytes: bgzf_regions.hpp, rg_regions.hpp,
 //                          tabix_source.hpp, index_source.hpp, tbi_out.hpp)
 //   fetched_regions.hpp    reads as a BAM fetch returns them, ASCII or packed        bgzf_regions.hpp   the BGZF blocks of an index lookup

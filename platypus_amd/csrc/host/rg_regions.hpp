@@ -228,11 +228,11 @@ CALLER_EXPORT int plat_call_bgzf_regions_rg(plat_caller* c, const plat_bgzf_rg_r
         RgTable table;
         if ((rc = rgTableUpload(F, groups, table)) != PLAT_OK) return rc;
         // upload, inflate, then find and route (the fetched records where the find leaves them, the broken mates of the same regions): back to back
-        W.inflate();
+        W.batch.inflate();
         RgRouted rf, rb;
         RecordList kept, ub;
         rc = W.findLoaded(kept, [&](const std::vector<int>& use) {
-            rgRouteLaunch(F, table, kept, W.capRecords, rf);
+            rgRouteLaunch(F, table, kept, W.batch.capRecords, rf);
             std::vector<const plat_bam_file_records*> broken;
             for (int k = 0; k < n_regions; ++k)
                 for (int f = 0; f < n_files && use[(size_t)k]; ++f) broken.push_back(&regions[k].files[f].broken_mates);

@@ -162,6 +162,31 @@ def fetch(f, chrom, start, end):
                 chunks=[(u >> 16, len(d), fu, ec, eu) for (u, _), (d, fu, ec, eu) in zip(chunks, cut)], cut=cut)
 
 
+def first_chunk_off_the_data(data, chunks):
+    """(n, u, v) of the first of a query's chunks [(u, v)] that cannot be cut out of `data` -- no whole block stands at u's coffset, or
+    at v's when v's uoffset says the chunk reaches into it, or the offsets leave the data --, None when every chunk can: the rule of
+    tabixindex.cut_chunks turned into its refusal, for data that is a prefix of a stream of valid blocks."""
+    def block_end(at):
+        if at + 26 > len(data) or data[at:at + 4] != b"\x1f\x8b\x08\x04":
+            return None
+        e = at + struct.unpack_from("<H", data, at + 16)[0] + 1
+        return e if e <= len(data) else None
+    for n, (u, v) in enumerate(chunks):
+        c0, c1, stop = u >> 16, v >> 16, v >> 16
+        ok = c0 <= c1 <= len(data)
+        if ok and v & 0xffff:
+            stop = block_end(c1)
+            ok = stop is not None
+        if ok and stop > c0:
+            ok = block_end(c0) is not None
+        if not ok:
+            return n, u, v
+    return None
+
+
+NO_CUT = "does not begin and end at BGZF block headers inside the file's data"
+
+
 def kept_records(f, chrom, start, end):
     """The records of a built file sam_itr_next keeps for chrom:start-end, by the rule: indices into f["records"]."""
     names = [n for n, _ in f["refs"]]

@@ -16,6 +16,7 @@ import pytest
 from platypus_amd import _lib, fastcaller as F, tabixindex
 from platypus_amd.options import default_options
 from tests import index_query_cases as Q, tabix_cases as T
+from tests.bam_file_cases import NO_CUT, first_chunk_off_the_data
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TBI, BAI = 0, 1
@@ -315,6 +316,15 @@ def test_fake_device_host_index_takes_whole_files_and_returns_the_golden_lines(m
             with pytest.raises(_lib.PlatypusDeviceError) as e:
                 nc.set_source_files([(f["vcf_gz"][:30], idx)], regions[:12])
             assert e.value.code == -9 and "region" in str(e.value) and "file 0" in str(e.value) and "chunk" in str(e.value)
+            # ... the file cut short behind its first block: the whole message, the offsets read off the file's own index
+            cut = f["vcf_gz"][:struct.unpack_from("<H", f["vcf_gz"], 16)[0] + 1]
+            with pytest.raises(_lib.PlatypusDeviceError) as e:
+                nc.set_source_files([(f["vcf_gz"], idx), (cut, idx)], regions)
+            bad = [(k, first_chunk_off_the_data(cut, mirror.query(q["tid"], q["beg"], q["end"]) or [])) for k, q in enumerate(f["queries"])]
+            k, (n, u, v) = [b for b in bad if b[1] is not None][0]
+            entry = "plat_caller_set_source_files"
+            assert e.value.code == -9 and str(e.value) == str(_lib.PlatypusDeviceError(
+                -9, "%s: chunk %d of region %d, file 1 (virtual offsets %d .. %d) %s" % (entry, n, k, u, v, NO_CUT), entry))
             with pytest.raises(_lib.PlatypusDeviceError) as e:
                 nc.query_index(idx, [(0, 0, 5), (len(f["names"]), 0, 5)])
             assert e.value.code == -1 and "query 1" in str(e.value)

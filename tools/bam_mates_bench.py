@@ -13,8 +13,8 @@ mates lie 150 kb further on, is written in memory with its .bai and called in re
                          plat_call_bam_files_mates and next to the BGZF call that follows it (the difference)
     options off          plat_call_bam_files_mates against plat_call_bam_files with assembleBrokenPairs = 0 on the same file, alternating,
                          with the run-to-run spread of each: the same launches (tests/test_gpu_bam_mates.py), so the two must overlap
-                         within that spread.  --label names the code the figures belong to (this / parent): a run at the parent commit,
-                         where only plat_call_bam_files exists, adds its own entry to the same file
+                         within that spread.  --label names the code the figures belong to (any name: this, parent, head_2 ...): a run
+                         of another build adds its own entry to the same file (options_off, and runs: the plan and the call too)
 
 One process, one GPU; a record, not a bar.
 
@@ -155,12 +155,14 @@ def main():
         h.close()
     finally:
         nc.close()
-    old = {}
+    old, runs = {}, {}
     if a.out and os.path.exists(a.out):
         with open(a.out) as fh:
-            old = json.loads(fh.read() or "{}").get("options_off", {})
+            prev = json.loads(fh.read() or "{}")
+        old, runs = prev.get("options_off", {}), prev.get("runs", {})
     res["options_off"] = dict(old, **{a.label: entry})
-    if "parent" not in res["options_off"]:
+    res["runs"] = dict(runs, **{a.label: dict(plan_and_call=res.get("plan_and_call"), options_off=entry)})       # every label's own figures, whichever ran last
+    if not any(k.startswith("parent") for k in res["options_off"]):
         res["options_off"]["parent"] = "not measured"
     line = json.dumps(res)
     print(line)
